@@ -9,11 +9,17 @@ Contract (one JSON line on rank 0):
             for N > 1 every rank runs its own K steps (weak scaling: pairs shard with no data-path
             dependency) and each step ends with ONE RCCL all-gather of the step's pointmaps+confidences,
             the exchange that assembles the aligner input.
+  ms_per_step = wall clock of one timed step; --steps sets their number.
+
+A plain run does only that: set-up, warm-up, the timed steps, --dump-outputs if given, the result line.
+--full adds, each in a region of its own after the timed steps (the --no-* options leave single ones out):
   extra   = align_iters_per_s: a3r_align_step on the config-2 graph (N=16, E=84, P=196608), timed in its own
             region after the forward region (rank-local replica; see DESIGN.md for why it is not sharded).
-  roofline      : the dominant kernel (the nn.Linear GEMM) -- algorithmic FLOP / HIP-event duration, live.
+  roofline      : the dominant kernel (the nn.Linear GEMM) -- algorithmic FLOP / HIP-event duration, from a replay of
+                  the timed steps with the per-kernel HIP events on (they cost host time per launch).
   roofline_align: the fused aligner kernel -- algorithmic bytes / HIP-event duration, live.
   cpu_baseline  : the numpy/C oracle timed on this box's host cores (rank 0, N=1 only), bounded sample.
+  and the extras encoder_cached, clip_wall_clock, bf16_mode / f16_mode, raft_flow, align_config3, align_config4.
 """
 from __future__ import annotations
 
@@ -97,7 +103,47 @@ def parse():
     ap.add_argument("--no-bf16-run", action="store_true", help="skip the extra throughput figure of BASELINE config 5's plain-bf16 mode")
     ap.add_argument("--no-align-config3", action="store_true", help="skip the extra aligner figure at BASELINE config 3's size (19 GB)")
     ap.add_argument("--no-raft-run", action="store_true", help="skip the extra throughput figure of the RAFT2 flow network (BASELINE config 4)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure the roofline / per-kernel figures, the aligner, "
+                                                        "the extras and the CPU baseline (the --no-* options leave single ones out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the four outputs of the last timed step (all ranks' pairs) as float32 "
+                                                          "DIR/<name>.npy; above 2^20 pixels, a fixed seeded sample of the same pixels "
+                                                          "of each")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+def synthetic_weights(cfg):
+    """weights.synthetic_state_dict(cfg, 0), bit for bit, with the tensors generated on a thread pool (numpy releases the GIL in
+    the hash): the serial form spends ~15 s of one core on ViT-L's 603 M parameters, which a plain run pays as set-up."""
+    from concurrent.futures import ThreadPoolExecutor
+    from align3r_amd.weights import param_spec, synthetic_tensor
+    spec = param_spec(cfg)
+    with ThreadPoolExecutor(max_workers=max(1, min(16, os.cpu_count() or 1))) as ex:
+        vals = list(ex.map(lambda s: synthetic_tensor(s[0], s[1], s[2], 0), spec))
+    return {s[0]: v for s, v in zip(spec, vals)}
+
+
+DUMP_MAX_PIXELS = 1 << 20     # 32 MiB of float32 for the four outputs
+
+
+def dump_outputs(dirname, bufs):
+    """The arrays the timed path hands its caller in its last step -- pts3d_1 / conf_1 / pts3d_2 / conf_2 of every pair of the
+    step, all ranks' rows after the all-gather -- as float32 .npy files.  When a step has more than DUMP_MAX_PIXELS pixels, each
+    file holds the same sample of them (seeded, a function of the shapes alone): [DUMP_MAX_PIXELS, 3] and [DUMP_MAX_PIXELS]."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    n = bufs["conf1"].numel()
+    idx = None
+    if n > DUMP_MAX_PIXELS:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_PIXELS, replace=False))
+        idx = torch.from_numpy(idx).to(bufs["conf1"].device)
+    for name, key in (("pts3d_1", "pts1"), ("conf_1", "conf1"), ("pts3d_2", "pts2"), ("conf_2", "conf2")):
+        t = bufs[key]
+        if idx is not None:
+            t = t.reshape(n, -1)[idx].reshape(DUMP_MAX_PIXELS, *t.shape[3:])
+        np.save(os.path.join(dirname, name + ".npy"), t.float().cpu().numpy())
 
 
 def _free_port():
@@ -165,7 +211,7 @@ def main():
     pairs = make_pairs([dict(idx=i) for i in range(a.frames)], a.scene_graph, symmetrize=True)
     edges = [(p["idx"], q["idx"]) for p, q in pairs]
     E = len(edges)
-    sd = synthetic_state_dict(VITL, 0)
+    sd = synthetic_weights(VITL)
     eng = PairEngine(VITL, sd, dev)
 
     def batch_inputs(step):
@@ -196,45 +242,20 @@ def main():
     for s in range(a.warmup):
         step(s)
     barrier()
-    _lib.prof_enable(True)
     t0 = time.perf_counter()
     for s in range(a.steps):
         step(a.warmup + s)
     barrier()
     dt = time.perf_counter() - t0
-    _lib.prof_enable(False)
-    prof = _lib.prof_report()
     if use_dist:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     pairs_per_s = world * B * a.steps / dt
-    byname = {p["name"]: p for p in prof}
-    # roofline of the DOMINANT matrix-core kernel class (largest share of the timed region).  Ceiling for ALGORITHMIC fp32 FLOP =
-    # dense fp16 / bf16 MFMA peak / (matrix passes per fp32 product): fh2 evaluates 3 fp16 passes, bf3 6 bf16 passes; the
-    # exact-fp32 kernel is priced against the fp32 MFMA peak.
-    mfma_classes = {
-        "gemm_fh2_kernel (linear, split-fp16 MFMA)": dict(
-            passes=3, pmc="gemm_fh2_kernel", desc="gemm_fh2_kernel (nn.Linear on the fp16 matrix cores: two-plane fp16 split of both fp32 "
-            "operands = 22-bit operands, 3 exact fp16 MFMA passes, fp32 accumulate)"),
-        "gemm_bf3_kernel (linear, split-bf16 MFMA)": dict(
-            passes=6, pmc="gemm_bf3_kernel", desc="gemm_bf3_kernel (nn.Linear on the bf16 matrix cores: exact 3-plane split of both fp32 "
-            "operands, 6 bf16 MFMA passes, fp32 accumulate)"),
-        "gemm_kernel<0> (linear)": dict(passes=0, pmc="gemm_kernel<0>", desc="gemm_kernel<0> (fp32 MFMA GEMM, all nn.Linear)"),
-    }
-    lin_name = max(mfma_classes, key=lambda n: byname[n]["ms"] if n in byname else -1.0)
-    lin, cls = byname[lin_name], mfma_classes[lin_name]
-    use_split = cls["passes"] > 0
-    achieved = lin["work"] / (lin["ms"] * 1e-3) / 1e12 if lin["ms"] > 0 else 0.0
-    peak = PEAK_BF16_MFMA_TFLOPS / cls["passes"] if use_split else PEAK_F32_MFMA_TFLOPS
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, bufs)
     mode = os.environ.get("A3R_GEMM", "fh2")
-    kernels = {p["name"]: dict(launches=p["launches"], total_ms=round(p["ms"], 3),
-                               avg_us=round(1e3 * p["ms"] / p["launches"], 2) if p["launches"] else None,
-                               rate=round(p["work"] / (p["ms"] * 1e-3) / 1e12, 3) if p["ms"] > 0 else None)
-               for p in prof if p["launches"]}
     flop_pair = FLOP_PER_PAIR.get((H, W))
-    lin_traffic, lin_traffic_src = pmc_traffic(cls["pmc"]) if (B, H, W) == (42, 384, 512) else (None, None)
-    lin_bytes = lin.get("bytes", 0.0) / max(lin["launches"], 1)
     res = {
         "metric": "frame-pairs/s ViT-L 512px + global-align iters/s, 1/2/4/8 MI355X", "value": round(pairs_per_s, 4),
         "unit": "frame-pairs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -253,20 +274,62 @@ def main():
                               "count -- the plan runs each DPT fusion block's 1x1 out_conv before the bilinear 2x (a quarter of the rows), "
                               "so it executes ~0.7 % fewer FLOP than the reference for the same result"),
         "rccl_ranks": rccl_ranks,
+    }
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if use_dist:
+            dist.destroy_process_group()
+        return
+
+    # ---- roofline + per-kernel durations: the timed steps replayed with a HIP event pair around every launch
+    _lib.prof_enable(True)
+    t0 = time.perf_counter()
+    for s in range(a.steps):
+        step(a.warmup + s)
+    barrier()
+    dtp = time.perf_counter() - t0
+    _lib.prof_enable(False)
+    prof = _lib.prof_report()
+    byname = {p["name"]: p for p in prof}
+    # roofline of the DOMINANT matrix-core kernel class (largest share of the timed region).  Ceiling for ALGORITHMIC fp32 FLOP =
+    # dense fp16 / bf16 MFMA peak / (matrix passes per fp32 product): fh2 evaluates 3 fp16 passes, bf3 6 bf16 passes; the
+    # exact-fp32 kernel is priced against the fp32 MFMA peak.
+    mfma_classes = {
+        "gemm_fh2_kernel (linear, split-fp16 MFMA)": dict(
+            passes=3, pmc="gemm_fh2_kernel", desc="gemm_fh2_kernel (nn.Linear on the fp16 matrix cores: two-plane fp16 split of both fp32 "
+            "operands = 22-bit operands, 3 exact fp16 MFMA passes, fp32 accumulate)"),
+        "gemm_bf3_kernel (linear, split-bf16 MFMA)": dict(
+            passes=6, pmc="gemm_bf3_kernel", desc="gemm_bf3_kernel (nn.Linear on the bf16 matrix cores: exact 3-plane split of both fp32 "
+            "operands, 6 bf16 MFMA passes, fp32 accumulate)"),
+        "gemm_kernel<0> (linear)": dict(passes=0, pmc="gemm_kernel<0>", desc="gemm_kernel<0> (fp32 MFMA GEMM, all nn.Linear)"),
+    }
+    lin_name = max(mfma_classes, key=lambda n: byname[n]["ms"] if n in byname else -1.0)
+    lin, cls = byname[lin_name], mfma_classes[lin_name]
+    use_split = cls["passes"] > 0
+    achieved = lin["work"] / (lin["ms"] * 1e-3) / 1e12 if lin["ms"] > 0 else 0.0
+    peak = PEAK_BF16_MFMA_TFLOPS / cls["passes"] if use_split else PEAK_F32_MFMA_TFLOPS
+    kernels = {p["name"]: dict(launches=p["launches"], total_ms=round(p["ms"], 3),
+                               avg_us=round(1e3 * p["ms"] / p["launches"], 2) if p["launches"] else None,
+                               rate=round(p["work"] / (p["ms"] * 1e-3) / 1e12, 3) if p["ms"] > 0 else None)
+               for p in prof if p["launches"]}
+    lin_traffic, lin_traffic_src = pmc_traffic(cls["pmc"]) if (B, H, W) == (42, 384, 512) else (None, None)
+    lin_bytes = lin.get("bytes", 0.0) / max(lin["launches"], 1)
+    res.update({
         "roofline": {"bound": "mfma", "kernel": cls["desc"],
                      "achieved": round(achieved, 2), "peak": round(peak, 1), "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
                      "peak_note": (f"dense fp16/bf16 MFMA peak 2500 / {cls['passes']} passes = ceiling for algorithmic fp32 FLOP; executed MFMA rate = "
                                    f"{cls['passes'] * achieved:.0f} TFLOP/s; the exact-fp32 MFMA peak is {PEAK_F32_MFMA_TFLOPS}" if use_split
                                    else "v_mfma_f32_32x32x2_f32 dense peak"),
                      "frac_of_f32_mfma_peak": round(achieved / PEAK_F32_MFMA_TFLOPS, 4),
-                     "share_of_step": round(lin["ms"] / (1e3 * dt), 3),
+                     "share_of_step": round(lin["ms"] / (1e3 * dtp), 3),
                      "traffic": lin_traffic, "traffic_source": lin_traffic_src,
                      "algorithmic_bytes_per_launch": round(lin_bytes) if lin_bytes else None,
                      "traffic_over_algorithmic": round(lin_traffic / lin_bytes, 2) if (lin_traffic and lin_bytes) else None,
                      "algorithmic_flop_per_launch": round(lin["work"] / max(lin["launches"], 1)),
                      "launches": lin["launches"], "avg_launch_us": round(1e3 * lin["ms"] / max(lin["launches"], 1), 2)},
         "kernels": kernels,
-    }
+    })
 
     # ---- extra (not the headline): the same clip with per-frame encoder caching (each frame encoded once, not per pair)
     if not a.no_cache_run:

@@ -3,7 +3,7 @@
 A=$1; B=$2; R=${3:-2}
 for i in $(seq $R); do
   for L in $A $B; do
-    A3R_LIB=$L python bench.py --steps 2 --no-cpu-baseline --no-align --no-cache-run --no-clip-run --no-bf16-run 2>/dev/null | python -c "
+    A3R_LIB=$L python bench.py --full --steps 2 --no-cpu-baseline --no-align --no-cache-run --no-clip-run --no-bf16-run 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.readline())
 k=r['kernels']
