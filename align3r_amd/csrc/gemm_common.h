@@ -429,6 +429,8 @@ static inline int check_epilogue(const a3r_epilogue* e, int M, int N, const char
                       "%s: aux_bf3 needs N %% 8 == 0, a 16-byte aligned buffer and no PIXSHUF", who);
     }
     A3R_CHECK_ARG(e->epi >= A3R_EPI_NONE && e->epi <= A3R_EPI_HEAD, "%s: unknown epilogue %d", who, e->epi);
+    A3R_CHECK_ARG((!e->relu_acc && !e->relu_out) || e->epi == A3R_EPI_RESID || e->epi == A3R_EPI_RESID2,
+                  "%s: relu_acc / relu_out need a RESID / RESID2 epilogue", who);
     if (e->epi == A3R_EPI_HEAD)
         A3R_CHECK_ARG(fh2_kernel && N == 128 && e->head_w && e->head_b && e->head_conf && !e->out_fh2 && !e->aux_fh2 && !e->out_bf3 && !e->aux_bf3,
                       "%s: the HEAD epilogue is available on the fh2 kernels for N == 128 with head_w, head_b, head_conf and no other output form", who);

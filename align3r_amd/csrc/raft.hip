@@ -207,6 +207,15 @@ __global__ __launch_bounds__(256) void scale_kernel(float* __restrict__ x, float
 }
 
 // dst[r, c0 + c] = src[r, c] (c < Cs): channel concatenation of channels-last maps (torch.cat(dim=1) of the reference's NCHW tensors)
+// max |x| of each of gridDim.y equally long images (out: one zeroed word per image; a non-negative float compares like its bit pattern)
+__global__ __launch_bounds__(256) void image_absmax_kernel(const float* __restrict__ x, long n_per, unsigned* __restrict__ out) {
+    const float* p = x + (size_t)blockIdx.y * n_per;
+    float m = 0.f;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_per; i += (long)gridDim.x * 256) m = fmaxf(m, fabsf(p[i]));
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0) atomicMax(out + blockIdx.y, __float_as_uint(m));
+}
+
 __global__ __launch_bounds__(256) void pack_cols_kernel(float* __restrict__ dst, int ldd, int c0, const float* __restrict__ src, int lds, int Cs, long rows) {
     const long total = rows * Cs;
     for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
@@ -761,7 +770,35 @@ int raft_plan(a3r_raft_s* m, bool dry, const float* img1, const float* img2, int
             if (hipMemcpyAsync(f1s, fm, (size_t)Bhw * D * 4, hipMemcpyDeviceToDevice, as_stream(stream)) != hipSuccess) { set_error("a3r_raft_forward: copy failed"); P.rc = A3R_EHIP; }
         }
         P.launch([&](hipStream_t st) { hipLaunchKernelGGL(scale_kernel, dim3(grid1d(Bhw * D)), dim3(256), 0, st, f1s, 1.f / sqrtf((float)D), Bhw * D); });
-        P.split(f1s, D, fm3, Bhw, D);
+        // fh2 operands of the correlation: feature maps have no fixed magnitude (a checkpoint's final_conv decides it), and two fp16
+        // planes at scale 1 are fp32-grade only while max|x| is in [2^-2, 2^15] (fh2.h).  So every image's map is stored with its own
+        // power of two, the one a weight matrix would get (max|s x| in [2^12, 2^13)), from that image's max|fmap| -- read back here,
+        // one wait per call.  Per image, not per batch: a pair's flow must not depend on what else is in the batch.
+        std::vector<float> s1(B, 1.f), s2(B, 1.f);
+        float* amx = ar.alloc(2 * B);
+        if (P.fh2() && !P.skip()) {
+            std::vector<float> mx(2 * B, 0.f);
+            hipStream_t st = as_stream(stream);
+            const long n_per = hw * D;
+            bool ok = hipMemsetAsync(amx, 0, (size_t)2 * B * 4, st) == hipSuccess;
+            if (ok) {
+                const long blocks = (n_per + 1023) / 1024;
+                hipLaunchKernelGGL(image_absmax_kernel, dim3((unsigned)(blocks < 64 ? blocks : 64), 2 * B), dim3(256), 0, st, fm, n_per, reinterpret_cast<unsigned*>(amx));
+                ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(mx.data(), amx, (size_t)2 * B * 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+                     hipStreamSynchronize(st) == hipSuccess;
+            }
+            if (!ok) { set_error("a3r_raft_forward: reading the feature maps' range failed"); P.rc = A3R_EHIP; }
+            for (int b = 0; b < B && ok; b++) {                     // (zero / non-finite maximum: scale 1; the split then reports it)
+                s1[b] = a3r_fh2_weight_scale(mx[b] / sqrtf((float)D));
+                s2[b] = a3r_fh2_weight_scale(mx[B + b]);
+            }
+        }
+        if (P.fh2()) {
+            for (int b = 0; b < B && !P.skip(); b++)
+                P.rc = a3r_split_fh2(f1s + (size_t)b * hw * D, D, reinterpret_cast<char*>(fm3) + (size_t)b * hw * D * 4, hw, D, s1[b], m->stat, stream);
+        } else {
+            P.split(f1s, D, fm3, Bhw, D);
+        }
         float* f2 = fm + (size_t)Bhw * D;                           // level 0 of fmap2
         float* f2n = ar.alloc((size_t)B * (h / 2) * (w / 2) * D);
         float* f2m = ar.alloc((size_t)B * (h / 4 > 0 ? h / 4 : 1) * (w / 4 > 0 ? w / 4 : 1) * D);
@@ -772,8 +809,10 @@ int raft_plan(a3r_raft_s* m, bool dry, const float* img1, const float* img2, int
                 if (P.skip()) break;
                 a3r_epilogue e = {};
                 if (P.fh2()) {
-                    P.rc = a3r_split_fh2(f2 + (size_t)b * n2 * D, D, w3, n2, D, 1.f, m->stat, stream);
-                    if (!P.rc) P.rc = a3r_linear_fh2(reinterpret_cast<char*>(fm3) + (size_t)b * hw * D * 4, w3, 1.f, corr[l] + (size_t)b * hw * n2, (int)n2, (int)hw, (int)n2, D, &e, stream);
+                    // (the coarser levels are 2 x 2 means of level 0: their maximum is not above its, one s2 serves all levels)
+                    e.x_scale = s1[b];
+                    P.rc = a3r_split_fh2(f2 + (size_t)b * n2 * D, D, w3, n2, D, s2[b], m->stat, stream);
+                    if (!P.rc) P.rc = a3r_linear_fh2(reinterpret_cast<char*>(fm3) + (size_t)b * hw * D * 4, w3, s2[b], corr[l] + (size_t)b * hw * n2, (int)n2, (int)hw, (int)n2, D, &e, stream);
                     continue;
                 }
                 P.rc = a3r_split_bf3_w(f2 + (size_t)b * n2 * D, D, w3, n2, D, stream);

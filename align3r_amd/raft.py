@@ -76,7 +76,9 @@ class RaftEngine:
 
     def _ranged(self, launch):
         """Run `launch` (which enqueues one call and returns its output); in fh2 arithmetic read the call's range statistic and, if a
-        stored activation reached 2^15 (fp16 tops out at 65504; NaN counts), repeat the call on the three-plane bf16 kernels."""
+        stored activation reached 2^15 (fp16 tops out at 65504; NaN counts), repeat the call on the three-plane bf16 kernels.
+        There is no low-side check: the only activations without a fixed magnitude, the correlation's feature-map operands, are stored
+        with a per-image power of two inside the call (csrc/raft.hip), so small feature maps lose nothing."""
         out = launch()
         if not self.fh2:
             return out

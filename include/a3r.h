@@ -136,7 +136,7 @@ typedef struct {
      * same relu-ed value */
     int relu_out;
     /* RESID / RESID2 only: the branch is clamped BEFORE the addition, y = resid + relu(acc + bias) (then relu_out) -- BasicBlock's
-     * `y = relu(bn2(conv2(y))); return relu(x + y)` (layer.py:135-141) */
+     * `y = relu(bn2(conv2(y))); return relu(x + y)` (layer.py:135-141).  Either flag with any other epilogue is refused (A3R_EINVAL). */
     int relu_acc;
 } a3r_epilogue;
 
@@ -472,7 +472,10 @@ int a3r_raft_forward(a3r_raft_t m, const float* image1, const float* image2, int
  * fp16 MFMA passes, operands stored with scale 1), 0 = the three-plane bf16 form (six passes, fp32 range).  The fh2 form is fp32-grade
  * while every stored activation stays inside fp16's range; every fh2 producer of a call reports max |stored value| into one device
  * word that a3r_raft_range reads back (it waits for the stream): a caller that finds it at or above 2^15 (or NaN) repeats the call
- * after a3r_raft_set_arith(m, 0) -- align3r_amd.raft.RaftEngine does.  set_arith returns the previous setting. */
+ * after a3r_raft_set_arith(m, 0) -- align3r_amd.raft.RaftEngine does.  set_arith returns the previous setting.
+ * The one activation without a fixed magnitude, the feature map (the correlation's operands fmap1 / sqrt(dim) and fmap2), is stored per
+ * image with the power of two that puts that image's max |x| into [2^12, 2^13): the forward reads the per-image maxima back (one wait
+ * on the stream), so small or large feature maps cost neither accuracy nor a repeat (absolute error <= 2^-37 max|x| per operand). */
 int a3r_raft_set_arith(a3r_raft_t m, int fh2);
 int a3r_raft_range(a3r_raft_t m, float* max_abs_host, void* stream);
 /* The feature network alone: fmap [B, H/8, W/8, 2 dim] = fnet(2 image / 255 - 1) for B frames (raft.py:222-223).  A frame's features do

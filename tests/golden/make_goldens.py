@@ -2,7 +2,7 @@
 """Generate the golden fixtures under tests/golden/ by RUNNING THE REFERENCE in the build container.
 
 Usage (build container only -- /root/reference does not exist on the GPU box):
-    python tests/golden/make_goldens.py [--only pairs|ops|tiny|vitl|vitlhi|align|alignx|alignflow|alignprior|prep|hier|flowgeo|raft] [--out tests/golden]
+    python tests/golden/make_goldens.py [--only pairs|ops|tiny|vitl|vitlhi|align|alignx|alignflow|alignprior|prep|hier|flowgeo|raft|raftclip|raftclip64] [--out tests/golden]
 
 What it does
   * puts /root/reference on sys.path (read-only, bytecode writing disabled) and imports the
@@ -840,15 +840,9 @@ def gen_flowgeo(out):
     print("flowgeo: ok")
 
 
-def gen_raft(out):
-    """RAFT2 ("SEA-RAFT", third_party/RAFT/core/raft.py:152-246) -- the flow network cloud_opt_flow runs in its constructor
-    (dust3r/cloud_opt_flow/optimizer.py:118-154).  The reference's own modules with the build's synthetic weights
-    (align3r_amd/raft_weights.py, loaded strict=True).  Harness patch: ResNetFPN._init_weights -> no-op (it imports torchvision and
-    downloads ImageNet weights, extractor.py:300-322; every value is overwritten by load_state_dict anyway).
-    raft.npz: TINY configuration, 2 pairs 128x160, 3 iterations: final flow + intermediates (context / feature maps, the first
-    correlation lookup, the hidden state and coarse flow after every iteration, every up-sampled prediction);
-    RAFT_M (the configuration load_RAFT builds), 1 pair 128x160 and 1 pair 160x192, 20 iterations as the reference calls it: the
-    final flow and the coarse flow after iterations 1 and 20."""
+def _raft_reference():
+    """The reference's RAFT modules, importable on the CPU: (build(cfg, sd=None) -> RAFT2 in eval mode with the given or the synthetic
+    weights loaded strict=True, corr module, utils module).  See gen_raft for the one harness patch."""
     import importlib
     core = os.path.join(REF, "third_party", "RAFT", "core")
     if core not in sys.path:
@@ -858,15 +852,30 @@ def gen_raft(out):
     raft_mod = importlib.import_module("raft")
     corr_mod = importlib.import_module("corr")
     utils_mod = importlib.import_module("utils.utils")
-    from align3r_amd.raft_weights import RAFT_M, RAFT_TINY, synthetic_raft_state_dict, synthetic_raft_frames as raft_images
+    from align3r_amd.raft_weights import synthetic_raft_state_dict
 
-    def build(cfg):
+    def build(cfg, sd=None):
         j = json.load(open(os.path.join(core, "configs", "congif_spring_M.json")))
         j.update(initial_dim=cfg.initial_dim, block_dims=list(cfg.block_dims), radius=cfg.radius, dim=cfg.dim, num_blocks=cfg.num_blocks,
                  iters=cfg.iters, pretrain={(3, 4, 6): "resnet34", (2, 2, 2): "resnet18"}[tuple(cfg.n_blocks)])
         net = raft_mod.RAFT2(argparse.Namespace(**j)).eval()
-        net.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in synthetic_raft_state_dict(cfg, 0).items()}, strict=True)
+        sd = synthetic_raft_state_dict(cfg, 0) if sd is None else sd
+        net.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
         return net
+    return build, corr_mod, utils_mod
+
+
+def gen_raft(out):
+    """RAFT2 ("SEA-RAFT", third_party/RAFT/core/raft.py:152-246) -- the flow network cloud_opt_flow runs in its constructor
+    (dust3r/cloud_opt_flow/optimizer.py:118-154).  The reference's own modules with the build's synthetic weights
+    (align3r_amd/raft_weights.py, loaded strict=True).  Harness patch: ResNetFPN._init_weights -> no-op (it imports torchvision and
+    downloads ImageNet weights, extractor.py:300-322; every value is overwritten by load_state_dict anyway).
+    raft.npz: TINY configuration, 2 pairs 128x160, 3 iterations: final flow + intermediates (context / feature maps, the first
+    correlation lookup, the hidden state and coarse flow after every iteration, every up-sampled prediction);
+    RAFT_M (the configuration load_RAFT builds), 1 pair 128x160 and 1 pair 160x192, 20 iterations as the reference calls it: the
+    final flow and the coarse flow after iterations 1 and 20."""
+    from align3r_amd.raft_weights import RAFT_M, RAFT_TINY, synthetic_raft_frames as raft_images
+    build, corr_mod, utils_mod = _raft_reference()
 
     g = {}
     # ---- TINY with intermediates: the forward of raft.py:203-246 stepped by hand with the reference's own sub-modules
@@ -917,6 +926,134 @@ def gen_raft(out):
         g[f"{tag}_flow_up_1"] = ref[0][1].numpy()
     np.savez_compressed(os.path.join(out, "raft.npz"), **g)
     print("raft:", {k: v.shape for k, v in g.items()})
+
+
+RAFTCLIP_PART_BYTES = 1000000     # every committed part of raft_clip stays below this
+RAFTCLIP_SIZES = (("c288", 288, 512, 23), ("c384", 384, 512, 29))          # tag, H, W, frame seed
+RAFTCLIP_LOW = (("low8", 2.0 ** -8), ("low16", 2.0 ** -16))                # tag, scale of fnet.final_conv (weight and bias)
+# low16's feature maps / correlation taps are low8's times this power of two, bit for bit (a power-of-two scale of final_conv commutes
+# with every fp32 rounding up to there): the generator asserts it and stores them once; motion0 and the flow are stored for both
+RAFTCLIP_LOW16_FROM_LOW8 = dict(fmap1=-8, fmap2=-8, corr_pyr0=-16, corr_pyr1=-16, corr_pyr2=-16, corr_pyr3=-16, corr_lookup0=-16)
+
+
+def _raftclip_arrays(dtype):
+    """Every array of the raft_clip fixture, computed by the reference's modules in `dtype` (float32: what is stored; float64: the
+    yardstick gen_raftclip64 measures the stored values against)."""
+    from align3r_amd.raft_weights import RAFT_M, RAFT_TINY, synthetic_raft_state_dict, synthetic_raft_frames as raft_images
+    build, corr_mod, utils_mod = _raft_reference()
+    t = lambda a: torch.from_numpy(a).to(dtype)
+    g = {}
+    # ---- RAFT_M as the reference calls it, at the two sizes the pipeline runs
+    net = build(RAFT_M).to(dtype)
+    for tag, H, W, seed in RAFTCLIP_SIZES:
+        i1, i2 = raft_images(1, H, W, seed)
+        with torch.no_grad():
+            ref = net(t(i1), t(i2), iters=20, test_mode=True)
+        g[f"{tag}_flow"] = ref[1].numpy()
+    # ---- small feature maps: RAFT_TINY with fnet.final_conv (weight and bias) scaled down, stepped by hand as gen_raft does
+    B, H, W, iters = 1, 128, 160, 3
+    i1, i2 = raft_images(B, H, W, 31)
+    for tag, scale in RAFTCLIP_LOW:
+        sd = dict(synthetic_raft_state_dict(RAFT_TINY, 0))
+        for k in ("fnet.final_conv.weight", "fnet.final_conv.bias"):
+            sd[k] = sd[k] * np.float32(scale)
+        net = build(RAFT_TINY, sd).to(dtype)
+        with torch.no_grad():
+            ref = net(t(i1), t(i2), iters=iters, test_mode=True)
+            a = 2 * (t(i1) / 255.0) - 1.0
+            b = 2 * (t(i2) / 255.0) - 1.0
+            cnet = net.init_conv(net.cnet(torch.cat([a, b], dim=1)))
+            d = RAFT_TINY.dim
+            hid, context = torch.split(cnet, [d, d], dim=1)
+            fu = net.flow_head(hid)
+            flow8 = fu[:, :2]
+            f1, f2 = net.fnet(a), net.fnet(b)
+            g[f"{tag}_fmap1"], g[f"{tag}_fmap2"] = f1.permute(0, 2, 3, 1).numpy(), f2.permute(0, 2, 3, 1).numpy()
+            corr_fn = corr_mod.CorrBlock2(f1, f2, net.args)
+            for lv, c in enumerate(corr_fn.corr_pyramid):
+                g[f"{tag}_corr_pyr{lv}"] = c[:, 0].numpy()
+            dil = torch.ones(B, 1, H // 8, W // 8, dtype=dtype)
+            for it in range(iters):
+                coords2 = utils_mod.coords_grid2(B, H // 8, W // 8, device="cpu").to(dtype) + flow8
+                corr = corr_fn(coords2, dilation=dil)
+                if it == 0:
+                    g[f"{tag}_corr_lookup0"] = corr.permute(0, 2, 3, 1).numpy()
+                    g[f"{tag}_motion0"] = net.update_block.encoder(flow8, corr).permute(0, 2, 3, 1).numpy()
+                hid = net.update_block(hid, context, corr, flow8)
+                fu = net.flow_head(hid)
+                flow8 = flow8 + fu[:, :2]
+            up, _ = net.upsample_data(flow8, fu[:, 2:], .25 * net.upsample_weight(hid))
+            assert torch.equal(up, ref[1]), "hand-stepped forward differs from RAFT2.forward"
+            g[f"{tag}_flow"] = up.numpy()
+    return {k: np.ascontiguousarray(v) for k, v in g.items()}
+
+
+def gen_raftclip(out):
+    """RAFT2 at the sizes the pipeline runs, and with small feature maps -- kept out of raft.npz so that file regenerates unchanged.
+
+    raft_clip: the reference's own RAFT_M (synthetic weights, iters = 20, test_mode = True), one pair each at 288 x 512 (the 1/8 map is
+    36 x 64, the correlation pyramid 36, 18, 9, 4: an odd level in H) and 384 x 512 (BASELINE config 4, bench.py's raft_flow): the
+    final flow, float32.  Frames: synthetic_raft_frames(1, H, W, seed) with the seeds of RAFTCLIP_SIZES.
+    Low range: RAFT_TINY, 1 pair 128 x 160 (frame seed 31), 3 iterations, weight AND bias of fnet.final_conv scaled by 2^-8 (low8) and
+    by 2^-16 (low16), stepped by hand as gen_raft does: both feature maps, the four correlation levels, the first correlation lookup
+    and motion features, the final flow.  These are the magnitudes where a two-plane fp16 activation stored at scale 1 stops being
+    fp32-grade (csrc/fh2.h); the fp32 reference has no range problem there.  `--only raftclip64` repeats everything in float64 and
+    prints max|fp32 - fp64| / max|fp64| of every stored array (the reference's own rounding noise, which the tests' 1e-4 has to sit
+    well above).  Measured:
+        c288_flow 2.7e-06 (max|flow| 156.2)   c384_flow 1.7e-06 (max|flow| 180.4)
+        low8 : fmap1 3.4e-07  fmap2 4.1e-07  corr_pyr0..3 4.9e-07 3.7e-07 4.3e-07 4.0e-07  corr_lookup0 1.5e-06  motion0 6.4e-07  flow 7.1e-07
+        low16: the same figures (its maps are exact power-of-two multiples of low8's) except                                  flow 7.3e-07
+        max|fmap1| 7.9e-3 / 3.1e-5, max|corr_pyr0| 6.5e-5 / 9.9e-10 (low8 / low16)
+    all below 1e-5, so no case needed a milder scale.  max|flow| is 3.0419796 (low8) and 3.0419750 (low16): the final flow hardly
+    depends on the correlation volume with these weights, which is why the tests assert the taps.
+
+    No committed file may exceed 1 MiB and the two flows alone are 2.75 MB of float32 that hardly compresses, so the arrays are written as
+    numbered parts raft_clip.<n>.npz, each below RAFTCLIP_PART_BYTES (3.7 MB together): arrays in insertion order, an array larger than a part cut
+    along its flattened length into `name@k` pieces (tests/test_gpu_raft.py:load_parts puts them back together)."""
+    g = _raftclip_arrays(torch.float32)
+    assert all(v.dtype == np.float32 for v in g.values())
+    for k, p2 in RAFTCLIP_LOW16_FROM_LOW8.items():              # exact in fp32 (checked here), so stored once
+        assert np.array_equal(g.pop("low16_" + k), g["low8_" + k] * np.float32(2.0 ** p2)), k
+    parts, cur, size = [], {}, 0
+    room = RAFTCLIP_PART_BYTES - 20000                          # zip directory and .npy headers
+    for k, v in g.items():
+        flat, k0, n = v.reshape(-1), 0, 0
+        while k0 < flat.size:
+            if size >= room - 4096:
+                parts.append(cur)
+                cur, size = {}, 0
+            take = min(flat.size - k0, (room - size) // 4)
+            cur[f"{k}@{n}"] = flat[k0:k0 + take]
+            size += 4 * take
+            k0, n = k0 + take, n + 1
+        cur[k + "@shape"] = np.asarray(v.shape, np.int64)
+    parts.append(cur)
+    for f in os.listdir(out):
+        assert not (f.startswith("raft_clip.") and f.endswith(".npz") and int(f.split(".")[1]) >= len(parts)), f"stale part {f}"
+    for n, part in enumerate(parts):
+        path = os.path.join(out, f"raft_clip.{n}.npz")
+        np.savez_compressed(path, **part)
+        assert os.path.getsize(path) < RAFTCLIP_PART_BYTES, (path, os.path.getsize(path))
+    print("raftclip:", {k: v.shape for k, v in g.items()}, f"in {len(parts)} parts")
+    print("raftclip: max|flow|", {k: float(np.abs(v).max()) for k, v in g.items() if k.endswith("_flow")})
+    print("raftclip: max|tap| ", {k: float(np.abs(v).max()) for k, v in g.items() if k.startswith("low") and "fmap" in k})
+
+
+def gen_raftclip64(out):
+    """Writes nothing: the float32-versus-float64 margin of every array gen_raftclip stores (quoted in its docstring).  Harness patch
+    for the float64 pass only: Tensor.float -> Tensor.double (corr.py:50,61,101 and utils.py:8 cast to float32 by name)."""
+    g32 = _raftclip_arrays(torch.float32)
+    keep = torch.Tensor.float
+    torch.Tensor.float = lambda self, *a, **k: self.double()
+    try:
+        g64 = _raftclip_arrays(torch.float64)
+    finally:
+        torch.Tensor.float = keep
+    assert all(v.dtype == np.float64 for v in g64.values())
+    for k in g32:
+        e = np.abs(g32[k].astype(np.float64) - g64[k]).max() / np.abs(g64[k]).max()
+        print(f"raftclip64: {k:20s} max|fp64| {np.abs(g64[k]).max():.6g}  fp32-vs-fp64 {e:.2e}")
+        assert e < 1e-5, (k, e)
 
 
 def main():

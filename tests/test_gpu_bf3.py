@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+from test_gpu_fh2 import FLOW_CONVS, RELU_CONVS, RELU_LINEARS, relu_case      # the flow network's conv shapes; shared inputs of the relu tests
+
 pytestmark = pytest.mark.gpu
 TOL = 2e-5
 
@@ -145,9 +147,61 @@ def test_weight_layout_split_is_exact(ops, N, K):
     assert torch.equal((p[0] + p[1]) + p[2], w)
 
 
+@pytest.mark.parametrize("resid2", [False, True])
+@pytest.mark.parametrize("tile", ["0", "1", "2"])
+@pytest.mark.parametrize("shape", RELU_CONVS)
+def test_conv3x3_bf3_relu_acc_relu_out(ops, monkeypatch, tile, shape, resid2):
+    """relu_acc / relu_out (include/a3r.h; the BasicBlock tail relu(x + relu(bn2(conv2(y)))), layer.py:135-141) on the bf3 conv, every
+    tile, RESID and RESID2, all four flag combinations, against float64 (inputs and their 20 % condition: test_gpu_fh2.relu_case) at the
+    bound of test_linear_bf3_error_not_larger_than_fp32_mfma, 4e-7 of sum|x||w| + |resid| (per element: stricter than this module's
+    tensor-max TOL); with an aux_bf3 twin -- the form the flow network's range fallback launches -- which must be exactly the split of
+    the fp32 output."""
+    from align3r_amd import _lib
+    monkeypatch.setenv("A3R_BF3_TILE", tile)
+    (x, w, b, rs), ref, den = relu_case("conv", shape, resid2)
+    B, H, W, Cin, Cout, stride = shape
+    x3 = ops.split_bf3(x.cuda())
+    wp3 = ops.split_bf3_w(ops.pack_conv3x3(w.cuda()).reshape(Cout, 9 * Cin))
+    kw = dict(epi=_lib.EPI_RESID2, resid=rs[0].cuda(), resid2=rs[1].cuda()) if resid2 else dict(epi=_lib.EPI_RESID, resid=rs[0].cuda())
+    for (ra, ro), want in ref.items():
+        aux = torch.zeros(want.numel() * 6, dtype=torch.uint8, device="cuda")
+        y = ops.conv3x3_bf3(x3, wp3, (B, H, W, Cin), b.cuda(), stride=stride, relu_acc=bool(ra), relu_out=bool(ro), aux_bf3=aux, **kw)
+        e = float(((y.double().cpu() - want).abs() / den).max())
+        assert e < 4e-7, (ra, ro, e)
+        assert rel_err(cpu(y), cpu(want)) < TOL
+        assert torch.equal(aux, ops.split_bf3(y).data), (ra, ro)
+        plain = ops.conv3x3_bf3(x3, wp3, (B, H, W, Cin), b.cuda(), stride=stride, relu_acc=bool(ra), relu_out=bool(ro), **kw)
+        assert torch.equal(plain, y), (ra, ro)
+    with pytest.raises(RuntimeError, match="relu_acc / relu_out"):   # other epilogues would ignore the flags: refused
+        ops.conv3x3_bf3(x3, wp3, (B, H, W, Cin), b.cuda(), stride=stride, epi=_lib.EPI_RELU, relu_out=True)
+
+
+@pytest.mark.parametrize("resid2", [False, True])
+@pytest.mark.parametrize("tile", ["0", "1", "2", "3"])
+@pytest.mark.parametrize("shape", RELU_LINEARS)
+def test_linear_bf3_relu_acc_relu_out(ops, monkeypatch, tile, shape, resid2):
+    """As test_conv3x3_bf3_relu_acc_relu_out for a3r_linear_bf3 on every linear tile."""
+    from align3r_amd import _lib
+    monkeypatch.setenv("A3R_BF3_TILE", tile)
+    (x, w, b, rs), ref, den = relu_case("linear", shape, resid2)
+    M, N, K = shape
+    x3, w3 = ops.split_bf3(x.cuda()), ops.split_bf3_w(w.cuda())
+    kw = dict(epi=_lib.EPI_RESID2, resid=rs[0].cuda(), resid2=rs[1].cuda()) if resid2 else dict(epi=_lib.EPI_RESID, resid=rs[0].cuda())
+    for (ra, ro), want in ref.items():
+        aux = torch.zeros(M * N * 6, dtype=torch.uint8, device="cuda")
+        y = ops.linear_bf3(x3, w3, b.cuda(), relu_acc=bool(ra), relu_out=bool(ro), aux_bf3=aux, **kw)
+        e = float(((y.double().cpu() - want).abs() / den).max())
+        assert e < 4e-7, (ra, ro, e)
+        assert rel_err(cpu(y), cpu(want)) < TOL
+        assert torch.equal(aux, ops.split_bf3(y).data), (ra, ro)
+        assert torch.equal(ops.linear_bf3(x3, w3, b.cuda(), relu_acc=bool(ra), relu_out=bool(ro), **kw), y), (ra, ro)
+    with pytest.raises(RuntimeError, match="relu_acc / relu_out"):
+        ops.linear_bf3(x3, w3, b.cuda(), epi=_lib.EPI_GELU, relu_acc=True)
+
+
 @pytest.mark.parametrize("tile", ["0", "1", "2"])
 @pytest.mark.parametrize("B,H,W,Cin,Cout,stride", [(2, 12, 16, 64, 64, 1), (1, 24, 32, 96, 256, 1), (2, 9, 7, 32, 128, 2),
-                                                    (1, 5, 5, 256, 64, 1), (1, 48, 64, 128, 128, 1)])
+                                                    (1, 5, 5, 256, 64, 1), (1, 48, 64, 128, 128, 1)] + FLOW_CONVS)
 def test_conv3x3_bf3_vs_float64(ops, monkeypatch, tile, B, H, W, Cin, Cout, stride):
     """DPT-head 3x3 convs (dpt_block.py:33-142,323-329) as an implicit GEMM on the bf3 kernel, incl. padding and stride 2."""
     from align3r_amd import _lib

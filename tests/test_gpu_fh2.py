@@ -189,9 +189,102 @@ def test_linear_fh2_rope_to_fh2(ops):
             assert float((got - ref).abs().max() / ref.abs().max()) < 3e-6
 
 
-@pytest.mark.parametrize("tile", ["0", "2"])
+# The flow network's own 3x3 convs (csrc/raft.hip: ResNet stages 64 / 128 / 256, init_conv, the update block's 192-wide convc2, the heads):
+# Cout in {64, 128, 192, 256} x Cin in {64, 96, 128, 256}; stride 2 on even (18 x 32) and odd (17 x 23) maps; pixel counts that fill
+# 128-row tiles and 128- / 64-column tiles exactly (1 x 16 x 16 -> 128, 1 x 8 x 16 -> 64) and ones that leave a ragged last tile in M and
+# in N (1 x 36 x 64 and 2 x 9 x 7 at Cout 192: the 1/8 map of a 288 x 512 frame, and 126 rows)
+FLOW_CONVS = [(1, 36, 64, 128, 192, 1), (2, 9, 7, 64, 192, 1), (1, 16, 16, 64, 128, 1), (1, 8, 16, 128, 64, 1), (1, 18, 32, 64, 64, 2),
+              (1, 17, 23, 96, 128, 2), (1, 36, 64, 256, 256, 1), (1, 18, 32, 96, 256, 2)]
+
+
+def relu_case(kind, shape, epi_resid2, seed=0):
+    """Inputs (CPU fp32) and float64 references for the BasicBlock-tail epilogue: y = resid (+ resid2) + (relu if relu_acc)(acc + bias),
+    then relu if relu_out.  kind "conv": shape = (B, H, W, Cin, Cout, stride); "linear": shape = (M, N, K).  The residuals have a negative
+    mean so that relu_out bites.  Asserts (numpy / CPU only) that in the float64 reference each flag changes at least 20 % of the output
+    elements whatever the other flag is -- a kernel that ignores a flag cannot pass.  Returns (inputs, ref[(relu_acc, relu_out)], den)
+    with den = sum|x||w| + |bias| + |resid| (+ |resid2|)."""
+    g = torch.Generator(device="cpu").manual_seed(1000 + seed)
+    r_ = lambda *sh, scale=1.0: torch.randn(*sh, generator=g) * scale
+    if kind == "conv":
+        B, H, W, Cin, Cout, stride = shape
+        x, w, b = r_(B, H, W, Cin), r_(Cout, Cin, 3, 3, scale=(9 * Cin) ** -0.5), r_(Cout)
+        cv = lambda a, k, c: torch.nn.functional.conv2d(a.permute(0, 3, 1, 2), k, c, stride=stride, padding=1).permute(0, 2, 3, 1)
+        acc, den = cv(x.double(), w.double(), b.double()), cv(x.double().abs(), w.double().abs(), b.double().abs())
+    else:
+        M, N, K = shape
+        x, w, b = r_(M, K), r_(N, K, scale=K ** -0.5), r_(N)
+        acc = x.double() @ w.double().T + b.double()
+        den = x.double().abs() @ w.double().abs().T + b.double().abs()
+    n = 2 if epi_resid2 else 1
+    rs = [r_(*acc.shape, scale=3.0 / n ** 0.5) - 0.3 / n for _ in range(n)]
+    rsum = sum(t.double() for t in rs)
+    den = den + sum(t.double().abs() for t in rs)
+    ref = {}
+    for ra in (0, 1):
+        for ro in (0, 1):
+            y = rsum + (torch.relu(acc) if ra else acc)
+            ref[ra, ro] = torch.relu(y) if ro else y
+    for o in (0, 1):
+        assert float((ref[0, o] != ref[1, o]).double().mean()) >= 0.2, ("relu_acc changes too little", kind, shape, o)
+        assert float((ref[o, 0] != ref[o, 1]).double().mean()) >= 0.2, ("relu_out changes too little", kind, shape, o)
+    return (x, w, b, rs), ref, den
+
+
+RELU_CONVS = [(1, 36, 64, 128, 192, 1), (2, 9, 7, 64, 64, 1), (1, 17, 23, 96, 128, 2)]
+RELU_LINEARS = [(300, 192, 96), (256, 256, 64), (1000, 384, 128)]
+
+
+@pytest.mark.parametrize("resid2", [False, True])
+@pytest.mark.parametrize("tile", ["0", "1", "2"])
+@pytest.mark.parametrize("shape", RELU_CONVS)
+def test_conv3x3_fh2_relu_acc_relu_out(ops, monkeypatch, tile, shape, resid2):
+    """relu_acc / relu_out (include/a3r.h; the BasicBlock tail relu(x + relu(bn2(conv2(y)))), layer.py:135-141) on the fh2 conv, every
+    tile, RESID and RESID2, all four flag combinations, against float64 at the bound of test_conv3x3_fh2_vs_float64 (3e-7 of sum|x||w| +
+    |resid|); with an aux_fh2 twin -- the form the flow network launches (RESID + relu_acc + relu_out + aux_fh2) -- which must be
+    exactly the split of the fp32 output."""
+    monkeypatch.setenv("A3R_FH2_TILE", tile)
+    (x, w, b, rs), ref, den = relu_case("conv", shape, resid2)
+    B, H, W, Cin, Cout, stride = shape
+    x2 = ops.split_fh2(x.cuda())
+    wp2 = ops.split_fh2_w(ops.pack_conv3x3(w.cuda()).reshape(Cout, 9 * Cin))
+    kw = dict(epi=_lib.EPI_RESID2, resid=rs[0].cuda(), resid2=rs[1].cuda()) if resid2 else dict(epi=_lib.EPI_RESID, resid=rs[0].cuda())
+    for (ra, ro), want in ref.items():
+        aux = ops.Fh2(torch.zeros(want.numel() * 4, dtype=torch.uint8, device="cuda"), want.numel() // Cout, Cout)
+        y = ops.conv3x3_fh2(x2, wp2, (B, H, W, Cin), b.cuda(), stride=stride, relu_acc=bool(ra), relu_out=bool(ro), aux_fh2=aux, **kw)
+        e = float(((y.double().cpu() - want).abs() / den).max())
+        assert e < 3e-7, (ra, ro, e)
+        assert torch.equal(aux.data, ops.split_fh2(y).data), (ra, ro)
+        plain = ops.conv3x3_fh2(x2, wp2, (B, H, W, Cin), b.cuda(), stride=stride, relu_acc=bool(ra), relu_out=bool(ro), **kw)
+        assert torch.equal(plain, y), (ra, ro)                       # the twin does not change the fp32 output
+    with pytest.raises(RuntimeError, match="relu_acc / relu_out"):   # other epilogues would ignore the flags: refused
+        ops.conv3x3_fh2(x2, wp2, (B, H, W, Cin), b.cuda(), stride=stride, epi=_lib.EPI_RELU, relu_out=True)
+
+
+@pytest.mark.parametrize("resid2", [False, True])
+@pytest.mark.parametrize("tile", ["0", "1", "2", "3"])
+@pytest.mark.parametrize("shape", RELU_LINEARS)
+def test_linear_fh2_relu_acc_relu_out(ops, monkeypatch, tile, shape, resid2):
+    """As test_conv3x3_fh2_relu_acc_relu_out for a3r_linear_fh2 on every linear tile (bound: test_linear_fh2_error_not_larger_than_fp32_mfma's
+    3e-7 of sum|x||w| + |resid|)."""
+    monkeypatch.setenv("A3R_FH2_TILE", tile)
+    (x, w, b, rs), ref, den = relu_case("linear", shape, resid2)
+    M, N, K = shape
+    x2, w2 = ops.split_fh2(x.cuda()), ops.split_fh2_w(w.cuda())
+    kw = dict(epi=_lib.EPI_RESID2, resid=rs[0].cuda(), resid2=rs[1].cuda()) if resid2 else dict(epi=_lib.EPI_RESID, resid=rs[0].cuda())
+    for (ra, ro), want in ref.items():
+        aux = ops.Fh2(torch.zeros(M * N * 4, dtype=torch.uint8, device="cuda"), M, N)
+        y = ops.linear_fh2(x2, w2, b.cuda(), relu_acc=bool(ra), relu_out=bool(ro), aux_fh2=aux, **kw)
+        e = float(((y.double().cpu() - want).abs() / den).max())
+        assert e < 3e-7, (ra, ro, e)
+        assert torch.equal(aux.data, ops.split_fh2(y).data), (ra, ro)
+        assert torch.equal(ops.linear_fh2(x2, w2, b.cuda(), relu_acc=bool(ra), relu_out=bool(ro), **kw), y), (ra, ro)
+    with pytest.raises(RuntimeError, match="relu_acc / relu_out"):
+        ops.linear_fh2(x2, w2, b.cuda(), epi=_lib.EPI_GELU, relu_acc=True)
+
+
+@pytest.mark.parametrize("tile", ["0", "1", "2"])
 @pytest.mark.parametrize("B,H,W,Cin,Cout,stride", [(2, 12, 16, 64, 64, 1), (1, 24, 32, 96, 256, 1), (2, 9, 7, 32, 128, 2),
-                                                    (1, 5, 5, 256, 64, 1), (1, 48, 64, 128, 128, 1)])
+                                                    (1, 5, 5, 256, 64, 1), (1, 48, 64, 128, 128, 1)] + FLOW_CONVS)
 def test_conv3x3_fh2_vs_float64(ops, monkeypatch, tile, B, H, W, Cin, Cout, stride):
     """DPT-head 3x3 convs (dpt_block.py:33-142,323-329) as an implicit GEMM on the fh2 kernel, incl. padding and stride 2: error
     against float64 not larger than the exact-fp32 MFMA conv's; the fused outputs are exactly the splits of the fp32 results."""
@@ -228,6 +321,7 @@ def test_upsample2x_fh2(ops):
     assert torch.equal(ops.upsample2x_fh2(x, crop=(13, 18)).data, ops.split_fh2(ops.upsample2x(x, crop=(13, 18))).data)
 
 
+# (tiles 0 and 2 only: launch_fh2 maps the HEAD epilogue to tile 0 or 2 by design, the 128 x 64 tile has no HEAD instantiation)
 @pytest.mark.parametrize("tile", ["0", "2"])
 @pytest.mark.parametrize("B,H,W", [(1, 16, 24), (2, 19, 13)])
 def test_conv3x3_fh2_head_epilogue(ops, monkeypatch, tile, B, H, W):

@@ -208,10 +208,15 @@ def test_head_final_128(ops):
 
 
 def test_errors_are_loud(ops):
+    from align3r_amd import _lib
     with pytest.raises(RuntimeError, match="multiple of 32"):
         ops.linear(rnd(4, 40), rnd(8, 40))
     with pytest.raises(RuntimeError):
         ops.linear(torch.zeros(4, 32), rnd(8, 32))      # CPU tensor
+    with pytest.raises(RuntimeError, match="relu_acc / relu_out"):      # only the RESID / RESID2 epilogues evaluate these flags
+        ops.linear(rnd(4, 32), rnd(8, 32), epi=_lib.EPI_RELU, relu_out=True)
+    with pytest.raises(RuntimeError, match="relu_acc / relu_out"):
+        ops.linear(rnd(4, 32), rnd(8, 32), relu_acc=True)
 
 
 def test_umeyama_moments_kernel():

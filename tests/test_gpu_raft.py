@@ -8,6 +8,19 @@ tests/golden/make_goldens.py --only raft; inputs are rebuilt here by align3r_amd
     every iteration -- at max|a - b| / max|b| < 1e-4, and the final up-sampled flow at 1e-4;
   * RAFT_M (the configuration the reference's load_RAFT builds), called as the reference calls it (iters = 20, test_mode = True):
     first prediction and final flow, both at 1e-4 (measured: 2-5e-6 after 20 recurrent steps).
+
+Both of the above run in BOTH arithmetics (A3R_RAFT = fh2, bf3): the fallback is compared with the reference, not only with itself
+(measured: TINY stages <= 1.5e-6 fh2 / 1.9e-6 bf3; M after 20 iterations 2.7e-6 / 3.6e-6 fh2, 3.1e-6 / 4.9e-6 bf3).  Further
+(tests/golden/raft_clip.<n>.npz, make_goldens.py --only raftclip):
+  * RAFT_M at the sizes the pipeline runs, 288 x 512 (odd pyramid level in H) and 384 x 512, final flow at 1e-4: 6.0e-6 / 3.1e-6 fh2,
+    6.7e-6 / 5.4e-6 bf3 (the reference's own fp32-versus-float64 difference: 2.7e-6 / 1.7e-6); B = 3 at 288 x 512 with the middle pair
+    bitwise the B = 1 result;
+  * small feature maps (fnet.final_conv x 2^-8 and x 2^-16): feature maps, the four correlation levels, the first lookup and motion
+    features at 1e-4 of each tap's maximum.  Before the correlation operands got a per-image power-of-two scale (csrc/raft.hip) the fh2
+    correlation taps measured 2.5e-5 (2^-8) and 5.7e-3 (2^-16, failing); now <= 7.8e-7 in both cases, bf3 <= 8.5e-7.
+What is pinned: every stage at 128 x 160 in both arithmetics, the final flow at four sizes, the correlation path over a 2^16 range of
+feature-map magnitudes.  Not pinned: intermediate stages of RAFT_M, and large (> 2^15) feature maps against the reference (the
+fallback test checks those bitwise against bf3 only).
 """
 import os
 
@@ -31,10 +44,22 @@ def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def test_raft_tiny_stages_and_flow(g):
+ARITH = ["fh2", "bf3"]          # A3R_RAFT: the default two-plane fp16 kernels and the documented range fallback, both against the reference
+
+
+def engine(monkeypatch, arith, cfg, sd):
+    """A RaftEngine whose arithmetic is chosen as a user chooses it (A3R_RAFT, read when the engine is built)."""
     from align3r_amd.raft import RaftEngine
+    monkeypatch.setenv("A3R_RAFT", arith)
+    eng = RaftEngine(cfg, sd)
+    assert eng.fh2 == (arith == "fh2")
+    return eng
+
+
+@pytest.mark.parametrize("arith", ARITH)
+def test_raft_tiny_stages_and_flow(g, monkeypatch, arith):
     cfg = RAFT_TINY
-    eng = RaftEngine(cfg, synthetic_raft_state_dict(cfg, 0))
+    eng = engine(monkeypatch, arith, cfg, synthetic_raft_state_dict(cfg, 0))
     B, H, W, iters = 2, 128, 160, 3
     h, w, d = H // 8, W // 8, cfg.dim
     i1, i2 = synthetic_raft_frames(B, H, W, 7)
@@ -66,9 +91,10 @@ def test_raft_tiny_stages_and_flow(g):
         m[f"net{it}"] = rel_err(t[f"net{it}"], g[f"t_net_{it}"])
         m[f"flow8_{it}"] = rel_err(t[f"flow8_{it}"], g[f"t_flow8_{it}"])
     m["flow"] = rel_err(flow.cpu().numpy(), g["t_flow"])
-    record_margin("raft_tiny_vs_reference", **m)
+    record_margin("raft_tiny_vs_reference" + ("" if arith == "fh2" else "_" + arith), **m)
     bad = {k: v for k, v in m.items() if not v < TOL}
     assert not bad, bad
+    assert eng.range_fallbacks == 0                                 # the arithmetic asked for is the one that was compared
     # zero iterations: the prediction from the context network alone (raft.py:213-220)
     f0 = eng.forward(dev(i1), dev(i2), iters=0)
     assert rel_err(f0.cpu().numpy(), g["t_flow_up_0"]) < TOL
@@ -77,20 +103,123 @@ def test_raft_tiny_stages_and_flow(g):
     assert rel_err(f1.cpu().numpy(), flow[1:].cpu().numpy()) < 1e-5
 
 
+@pytest.mark.parametrize("arith", ARITH)
 @pytest.mark.parametrize("tag,H,W,seed", [("m1", 128, 160, 11), ("m2", 160, 192, 13)])
-def test_raft_m_as_the_reference_calls_it(g, tag, H, W, seed):
+def test_raft_m_as_the_reference_calls_it(g, monkeypatch, arith, tag, H, W, seed):
     """RAFT_M, iters = 20: the first iteration's prediction and the final flow (|flow| up to ~130 px with these random weights, 20
     recurrent steps) at 1e-4 of their maximum (measured: 2-5e-6; margins are recorded)."""
     from align3r_amd.raft import RAFT2
+    monkeypatch.setenv("A3R_RAFT", arith)
     net = RAFT2(RAFT_M, synthetic_raft_state_dict(RAFT_M, 0)).to("cuda").eval()
+    assert net._engine.fh2 == (arith == "fh2")
     i1, i2 = synthetic_raft_frames(1, H, W, seed)
     one = net(dev(i1), dev(i2), iters=1, test_mode=True)[1].cpu().numpy()
     out = net(dev(i1), dev(i2), iters=20, test_mode=True)
     assert isinstance(out, list) and len(out) == 2 and tuple(out[1].shape) == (1, 2, H, W)
     e1, e20 = rel_err(one, g[f"{tag}_flow_up_1"]), rel_err(out[1].cpu().numpy(), g[f"{tag}_flow"])
-    record_margin(f"raft_m_{tag}_vs_reference", flow_iter1=e1, flow_iter20=e20)
+    record_margin(f"raft_m_{tag}_vs_reference" + ("" if arith == "fh2" else "_" + arith), flow_iter1=e1, flow_iter20=e20)
     assert e1 < TOL, e1
     assert e20 < TOL, e20
+    assert net._engine.range_fallbacks == 0
+
+
+def load_parts(stem):
+    """tests/golden/<stem>.<n>.npz -> dict name -> array: a fixture written as numbered parts (no committed file above 1 MiB), an
+    array larger than a part cut along its flattened length into `name@k` pieces (make_goldens.py:gen_raftclip)."""
+    pieces, shapes, n = {}, {}, 0
+    while os.path.exists(os.path.join(GOLDEN, f"{stem}.{n}.npz")):
+        with np.load(os.path.join(GOLDEN, f"{stem}.{n}.npz")) as z:
+            assert all(z[k].dtype in (np.float32, np.int64) for k in z.files)          # arrays only
+            for k in z.files:
+                name, idx = k.rsplit("@", 1)
+                if idx == "shape":
+                    shapes[name] = tuple(int(x) for x in z[k])
+                else:
+                    pieces.setdefault(name, {})[int(idx)] = z[k]
+        n += 1
+    assert n > 0 and set(pieces) == set(shapes), (stem, n)
+    return {k: np.concatenate([pieces[k][i] for i in range(len(pieces[k]))]).reshape(shapes[k]) for k in shapes}
+
+
+@pytest.fixture(scope="module")
+def gc():
+    """raft_clip (make_goldens.py --only raftclip).  low16's feature maps and correlation taps are low8's times 2^-8 / 2^-16 bit for bit
+    in the fp32 reference (the generator asserts it), so they are stored once and rebuilt here by that exact multiplication."""
+    g = load_parts("raft_clip")
+    for k, p2 in dict(fmap1=-8, fmap2=-8, corr_pyr0=-16, corr_pyr1=-16, corr_pyr2=-16, corr_pyr3=-16, corr_lookup0=-16).items():
+        g["low16_" + k] = g["low8_" + k] * np.float32(2.0 ** p2)
+    return g
+
+
+@pytest.mark.parametrize("arith", ARITH)
+@pytest.mark.parametrize("tag,H,W,seed", [("c288", 288, 512, 23), ("c384", 384, 512, 29)])
+def test_raft_m_at_the_sizes_the_pipeline_runs(gc, monkeypatch, arith, tag, H, W, seed):
+    """RAFT_M as the reference calls it at 288 x 512 (what the loader emits for 16:9 clips: the 1/8 map is 36 x 64 and the correlation
+    pyramid 36, 18, 9, 4 -- an odd level in H) and 384 x 512 (BASELINE config 4, bench.py's raft_flow): widths 256 / 128 / 64 in the
+    stems and strided convs, and other GEMM tiles than at the small test sizes.  Final flow at TOL = 1e-4 of max|flow| (156 / 180 px);
+    the reference's own fp32-versus-float64 difference is 2.7e-6 / 1.7e-6 there (make_goldens.py:gen_raftclip)."""
+    from align3r_amd.raft import RAFT2
+    monkeypatch.setenv("A3R_RAFT", arith)
+    net = RAFT2(RAFT_M, synthetic_raft_state_dict(RAFT_M, 0)).to("cuda").eval()
+    assert net._engine.fh2 == (arith == "fh2")
+    i1, i2 = synthetic_raft_frames(1, H, W, seed)
+    out = net(dev(i1), dev(i2), iters=20, test_mode=True)
+    assert isinstance(out, list) and len(out) == 2 and tuple(out[1].shape) == (1, 2, H, W)
+    e = rel_err(out[1].cpu().numpy(), gc[f"{tag}_flow"])
+    record_margin(f"raft_m_{tag}_vs_reference_{arith}", flow_iter20=e, max_abs_flow=float(np.abs(gc[f"{tag}_flow"]).max()))
+    assert e < TOL, e
+    assert net._engine.range_fallbacks == 0
+    if H == 288:
+        # batch invariance at this shape: the same pair in the middle of a batch of three is the B = 1 result bit for bit
+        a1, a2 = synthetic_raft_frames(2, H, W, seed + 1)
+        j1, j2 = np.stack([a1[0], i1[0], a1[1]]), np.stack([a2[0], i2[0], a2[1]])
+        out3 = net(dev(j1), dev(j2), iters=20, test_mode=True)[1]
+        assert tuple(out3.shape) == (3, 2, H, W)
+        assert torch.equal(out3[1], out[1][0])
+        assert not torch.equal(out3[0], out[1][0])
+
+
+@pytest.mark.parametrize("arith", ARITH)
+@pytest.mark.parametrize("tag,scale", [("low8", 2.0 ** -8), ("low16", 2.0 ** -16)])
+def test_raft_small_feature_maps(gc, monkeypatch, arith, tag, scale):
+    """A checkpoint whose feature maps are small: weight and bias of fnet.final_conv scaled by 2^-8 / 2^-16, so max|fmap| is 7.9e-3 /
+    3.1e-5 and the correlation volume tops out at 6.5e-5 / 9.9e-10 -- where two fp16 planes stored at scale 1 stop being fp32-grade
+    (csrc/fh2.h: absolute error 2^-25 / s below the band).  Every tap on the correlation path against the fp32 reference, each at
+    TOL = 1e-4 of that tap's own maximum (the reference's fp32-versus-float64 noise on these taps is 3e-7 .. 1.5e-6).  The three-plane
+    bf16 form has fp32's range: it passing shows the fixture is fair.
+    The final flow is compared too, but it cannot see this path: max|flow| is 3.0419796 for low8 and 3.0419750 for low16 -- with the
+    synthetic weights the flow hardly depends on the correlation volume (asserted below), so the taps are the assertion."""
+    cfg = RAFT_TINY
+    sd = dict(synthetic_raft_state_dict(cfg, 0))
+    for k in ("fnet.final_conv.weight", "fnet.final_conv.bias"):
+        sd[k] = sd[k] * np.float32(scale)
+    eng = engine(monkeypatch, arith, cfg, sd)
+    B, H, W, iters = 1, 128, 160, 3
+    h, w, d = H // 8, W // 8, cfg.dim
+    i1, i2 = synthetic_raft_frames(B, H, W, 31)
+    ccp = (cfg.corr_channel + 31) // 32 * 32
+    z = lambda *s: torch.zeros(*s, device="cuda")
+    taps = dict(fmap=z(2 * B, h, w, 2 * d), lookup0=z(B, h, w, ccp), motion0=z(B, h, w, d))
+    hl, wl = h, w
+    for l in range(cfg.corr_levels):
+        taps[f"corr_pyr{l}"] = z(B * h * w, hl, wl)
+        hl, wl = hl // 2, wl // 2
+    flow = eng.forward(dev(i1), dev(i2), iters=iters, taps=taps)
+    t = {k: v.cpu().numpy() for k, v in taps.items()}
+    m = dict(fmap1=rel_err(t["fmap"][:B], gc[f"{tag}_fmap1"]), fmap2=rel_err(t["fmap"][B:], gc[f"{tag}_fmap2"]))
+    for l in range(cfg.corr_levels):
+        m[f"corr_pyr{l}"] = rel_err(t[f"corr_pyr{l}"], gc[f"{tag}_corr_pyr{l}"])
+    m["lookup0"] = rel_err(t["lookup0"][..., :cfg.corr_channel], gc[f"{tag}_corr_lookup0"])
+    m["motion0"] = rel_err(t["motion0"], gc[f"{tag}_motion0"])
+    m["flow"] = rel_err(flow.cpu().numpy(), gc[f"{tag}_flow"])
+    record_margin(f"raft_tiny_{tag}_vs_reference_{arith}", max_abs_flow=float(np.abs(gc[f"{tag}_flow"]).max()), **m)
+    bad = {k: v for k, v in m.items() if not v < TOL}
+    assert not bad, bad
+    assert eng.range_fallbacks == 0                                 # small maps are handled in the arithmetic asked for, not by a repeat
+    # written down beside the test: the reference's final flows of the two cases agree to 2.7e-5 of their maximum although their
+    # correlation volumes differ by a factor 2^16 -- inside what TOL allows, so a final-flow comparison alone could not tell a
+    # correlation volume that is wrong by that factor from a right one
+    assert rel_err(gc["low8_flow"], gc["low16_flow"]) < TOL
 
 
 def test_raft_per_frame_feature_cache_is_bitwise_the_full_forward():
