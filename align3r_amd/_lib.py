@@ -181,6 +181,14 @@ SIGNATURES = {
     "a3r_align_steps_done": (C.c_int, [c_void]),
     "a3r_align_invalidate": (C.c_int, [c_void]),
     "a3r_align_pose_matrices": (C.c_int, [c_void, c_void, c_void, c_void]),
+    "a3r_align_shard_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "a3r_align_shard_reduce_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "a3r_align_shard_create": (C.c_int, [C.POINTER(AlignDesc), C.c_int, C.c_int, C.POINTER(c_void), c_void]),
+    "a3r_align_shard_partial": (C.c_int, [c_void, c_void, C.c_size_t, c_void]),
+    "a3r_align_shard_apply": (C.c_int, [c_void, c_void, C.c_size_t, C.c_float, c_void]),
+    "a3r_align_shard_grad": (C.c_int, [c_void, c_void, C.c_size_t, c_void, c_void, c_void, c_void, c_void]),
+    "a3r_align_shard_sum": (C.c_int, [c_void, c_void, C.c_int, C.c_size_t, c_void]),
+    "a3r_align_shard_run_local": (C.c_int, [c_void, C.c_int, c_void, C.c_size_t, c_void, C.c_int, c_void]),
 }
 
 _lib = None

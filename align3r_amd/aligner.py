@@ -277,3 +277,257 @@ class AlignEngine:
         with torch.cuda.device(self.device):
             check(self.lib.a3r_align_pose_matrices(self.handle, ptr(eM), ptr(iR), stream_ptr()), "a3r_align_pose_matrices")
         return eM, iR
+
+
+class _ShardReplica:
+    """One a3r_align_shard handle: the observation rows [e0, e1) and a full copy of the parameters, Adam moments and loss history."""
+
+    def __init__(self, e0, e1):
+        self.e0, self.e1 = int(e0), int(e1)
+        self.handle = None
+
+
+class ShardedAlignEngine:
+    """Edge-sharded AlignEngine: every shard walks its own rows of the stacked observations, the additive partial results (one flat
+    fp32 buffer: depth-parameter gradient map, per-image sums, per-edge sums) are summed, and every shard applies the same update
+    to its replica of the parameters -- ONE reduction per iteration.  Two reducers:
+
+      local_shards=K   K shard handles on this device, summed in a fixed order by a3r_align_shard_sum (bitwise reproducible);
+      group=pg         one shard per rank of a torch.distributed group, exactly one all_reduce(SUM) of the buffer per iteration.
+
+    Shard bounds are parallel.shard_rows(E, rank, world); shards that come out empty are skipped with local_shards and refused
+    with group.  The observations are either the whole graph's [E, ...] (each shard takes a view of its rows) or, with group,
+    this rank's rows only [e1 - e0, ...] (a rank's inference output is its shard).  Limits: plain cloud_opt only (no flow
+    variant, no depth prior); the initial state comes through set_params.  Same surface as AlignEngine: params, set_params,
+    loss, loss_grad, step, run, steps_done, trainable, pose_matrices."""
+
+    def __init__(self, ei, ej, pred_i, pred_j, w_i, w_j, imshapes, mono=None, base_scale=0.5, pw_break=20.0, focal_break=20.0,
+                 norm_pw_scale=True, dist="l1", train_poses=True, train_focals=True, train_pp=False, train_adaptors=False,
+                 device="cuda:0", loss_capacity=4096, local_shards=None, group=None, **unsupported):
+        from .parallel import shard_rows
+        if unsupported.get("flow") is not None or unsupported.get("shared_focal") or unsupported.get("temporal_smoothing_weight", 0) > 0:
+            raise NotImplementedError("ShardedAlignEngine: the flow variant (shared focal, temporal smoothing, ego-flow) is not edge-sharded")
+        bad = set(unsupported) - {"flow", "shared_focal", "temporal_smoothing_weight", "translation_weight"}
+        if bad:
+            raise TypeError(f"ShardedAlignEngine: unexpected arguments {sorted(bad)}")
+        if (local_shards is None) == (group is None):
+            raise ValueError("ShardedAlignEngine: pass exactly one of local_shards=K and group=<process group>")
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("ShardedAlignEngine needs a HIP device (there is no CPU fallback)")
+        dev = self.device
+        f32 = lambda a: torch.as_tensor(a, dtype=torch.float32).to(dev).contiguous()
+        self.ei = np.ascontiguousarray(ei, dtype=np.int32)
+        self.ej = np.ascontiguousarray(ej, dtype=np.int32)
+        E, N = len(self.ei), len(imshapes)
+        self.group = group
+        self._all_reduce = None
+        if group is not None:
+            import torch.distributed as tdist
+            from .parallel import GradientAllReduce
+            self._all_reduce = GradientAllReduce(group)
+            world, rank = tdist.get_world_size(group), tdist.get_rank(group)
+            e0, e1, _ = shard_rows(E, rank, world)
+            if e0 >= e1:
+                raise ValueError(f"ShardedAlignEngine: rank {rank} of {world} gets no edge of a graph with {E} edges; use fewer ranks")
+            bounds = [(e0, e1)]
+        else:
+            K = int(local_shards)
+            if K < 1:
+                raise ValueError("ShardedAlignEngine: local_shards must be >= 1")
+            bounds = [b[:2] for b in (shard_rows(E, r, K) for r in range(K)) if b[0] < b[1]]
+        self.bounds = bounds
+        rows = torch.as_tensor(w_i).shape[0]
+        if rows == E:
+            lo = 0
+            if group is not None and not torch.as_tensor(w_i).is_cuda:      # upload this rank's rows only
+                lo = bounds[0][0]
+                pred_i, pred_j, w_i, w_j = (torch.as_tensor(t)[lo:bounds[0][1]] for t in (pred_i, pred_j, w_i, w_j))
+        elif group is not None and rows == bounds[0][1] - bounds[0][0]:
+            lo = bounds[0][0]
+        else:
+            raise ValueError(f"ShardedAlignEngine: {rows} observation rows for a graph with {E} edges (shards {bounds})")
+        self._row0 = lo                          # graph edge of row 0 of the observation tensors held here
+        self.w_i, self.w_j = f32(w_i).reshape(len(w_i), -1), f32(w_j).reshape(len(w_j), -1)
+        P = self.w_i.shape[1]
+        self.E, self.N, self.P = E, N, P
+        self.pred_i, self.pred_j = f32(pred_i).reshape(-1, P, 3), f32(pred_j).reshape(-1, P, 3)
+        self.imshapes = [tuple(int(v) for v in s) for s in imshapes]
+        self.imw = np.asarray([w for h, w in self.imshapes], dtype=np.int32)
+        self.imarea = np.asarray([h * w for h, w in self.imshapes], dtype=np.int32)
+        self.pp0 = f32([(w / 2, h / 2) for h, w in self.imshapes])
+        self.use_mono = mono is not None
+        self.mono = f32(mono).reshape(N, P) if self.use_mono else None
+        self.flags = dict(norm_pw_scale=bool(norm_pw_scale), dist_l2=(dist == "l2"), train_poses=bool(train_poses),
+                          train_focals=bool(train_focals), train_pp=bool(train_pp), train_adaptors=bool(train_adaptors))
+        self.base_scale, self.pw_break, self.focal_break = base_scale, pw_break, focal_break
+        self.shared_focal, self.flow, self.prior = False, None, None
+        self.loss_capacity = loss_capacity
+        self.total_area_i = float(sum(int(self.imarea[i]) for i in self.ei))       # the WHOLE graph's (optimizer.py:70-71)
+        self.total_area_j = float(sum(int(self.imarea[j]) for j in self.ej))
+        self.n_floats = int(self.lib.a3r_align_shard_reduce_floats(E, N, P))
+        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
+        self.replicas = []
+        for e0, e1 in bounds:
+            r = _ShardReplica(e0, e1)
+            r.params = dict(pw_poses=z(E, 8), pw_adaptors=z(E, 2), depth=z(N, P), shifts=z(N), im_poses=z(N, 7), im_focals=z(N), im_pp=z(N, 2))
+            r.adam = dict(pw_poses=z(2, E, 8), depth=z(2, N, P), small=z(2, N, 16), pw_adaptors=z(2, E, 2))
+            r.loss_history = z(loss_capacity)
+            r.workspace = torch.empty(int(self.lib.a3r_align_shard_workspace_bytes(E, e1 - e0, N, P)), dtype=torch.uint8, device=dev)
+            r.buf = z(self.n_floats)
+            self.replicas.append(r)
+        self.params = self.replicas[0].params           # the replicas hold identical values; this one is the public view
+        self.loss_history = self.replicas[0].loss_history
+        self._create()
+
+    def _create(self):
+        for r in self.replicas:
+            if r.handle:
+                h_old, r.handle = r.handle, None
+                self.lib.a3r_align_destroy(h_old)
+            d = AlignDesc()
+            d.E, d.N, d.P = self.E, self.N, self.P
+            d.use_mono = int(self.use_mono)
+            d.norm_pw_scale = int(self.flags["norm_pw_scale"]); d.dist_l2 = int(self.flags["dist_l2"])
+            d.train_poses = int(self.flags["train_poses"]); d.train_focals = int(self.flags["train_focals"])
+            d.train_pp = int(self.flags["train_pp"])
+            d.train_adaptors = int(self.flags.get("train_adaptors", False))
+            d.adam_pw_adaptors = r.adam["pw_adaptors"].data_ptr()
+            d.base_scale, d.pw_break, d.focal_break = self.base_scale, self.pw_break, self.focal_break
+            d.total_area_i, d.total_area_j = self.total_area_i, self.total_area_j
+            d.ei_host, d.ej_host = self.ei.ctypes.data, self.ej.ctypes.data
+            d.imw_host, d.imarea_host = self.imw.ctypes.data, self.imarea.ctypes.data
+            a, b = r.e0 - self._row0, r.e1 - self._row0            # the shard's rows of the tensors held here (views)
+            d.pred_i, d.pred_j = self.pred_i[a:b].data_ptr(), self.pred_j[a:b].data_ptr()
+            d.w_i, d.w_j = self.w_i[a:b].data_ptr(), self.w_j[a:b].data_ptr()
+            d.mono = self.mono.data_ptr() if self.use_mono else None
+            d.pp0 = self.pp0.data_ptr()
+            p = r.params
+            d.pw_poses, d.pw_adaptors, d.depth, d.shifts = (p[k].data_ptr() for k in ("pw_poses", "pw_adaptors", "depth", "shifts"))
+            d.im_poses, d.im_focals, d.im_pp = (p[k].data_ptr() for k in ("im_poses", "im_focals", "im_pp"))
+            d.adam_pw_poses, d.adam_depth, d.adam_small = (r.adam[k].data_ptr() for k in ("pw_poses", "depth", "small"))
+            d.workspace, d.workspace_bytes = r.workspace.data_ptr(), r.workspace.numel()
+            d.loss_history, d.loss_capacity = r.loss_history.data_ptr(), self.loss_capacity
+            h = C.c_void_p()
+            with torch.cuda.device(self.device):
+                check(self.lib.a3r_align_shard_create(C.byref(d), r.e0, r.e1, C.byref(h), stream_ptr()), "a3r_align_shard_create")
+            r.handle = h
+
+    def __del__(self):
+        try:
+            for r in getattr(self, "replicas", []):
+                if r.handle:
+                    self.lib.a3r_align_destroy(r.handle)
+                    r.handle = None
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------------ state
+    def set_params(self, pw_poses=None, depth=None, im_poses=None, im_focals=None, shifts=None, im_pp=None,
+                   pw_adaptors=None, reset_optimizer=True):
+        for k, v in dict(pw_poses=pw_poses, depth=depth, im_poses=im_poses, im_focals=im_focals, shifts=shifts, im_pp=im_pp,
+                         pw_adaptors=pw_adaptors).items():
+            if v is not None:
+                t = torch.as_tensor(v, dtype=torch.float32).to(self.device)
+                for r in self.replicas:
+                    r.params[k].copy_(t.reshape(r.params[k].shape))
+        if reset_optimizer:
+            for r in self.replicas:
+                for t in r.adam.values():
+                    t.zero_()
+            self._create()     # step counter restarts with fresh Adam moments
+        else:
+            for r in self.replicas:
+                check(self.lib.a3r_align_invalidate(r.handle))
+
+    def set_depth_prior(self, weight, dyn=None, init=None):
+        if weight > 0:
+            raise NotImplementedError("ShardedAlignEngine: the depth prior belongs to the flow variant, which is not edge-sharded")
+
+    def set_trainable(self, **flags):
+        self.flags.update(flags)
+        self._create()
+
+    trainable = AlignEngine.trainable
+
+    @property
+    def steps_done(self):
+        return int(self.lib.a3r_align_steps_done(self.replicas[0].handle))
+
+    @property
+    def flow_dropped(self):
+        return False
+
+    # ------------------------------------------------------------------ compute
+    def _partials(self):
+        for r in self.replicas:
+            check(self.lib.a3r_align_shard_partial(r.handle, ptr(r.buf), self.n_floats, stream_ptr()), "a3r_align_shard_partial")
+
+    def _reduce(self):
+        """The one reduction of an iteration; the reduced buffer is replica 0's."""
+        if self._all_reduce is not None:
+            self._all_reduce(self.replicas[0].buf)
+        elif len(self.replicas) > 1:
+            srcs = (C.c_void_p * len(self.replicas))(*[r.buf.data_ptr() for r in self.replicas])
+            check(self.lib.a3r_align_shard_sum(ptr(self.replicas[0].buf), srcs, len(self.replicas), self.n_floats, stream_ptr()),
+                  "a3r_align_shard_sum")
+        return self.replicas[0].buf
+
+    def loss_grad(self, epoch=9999):
+        r0 = self.replicas[0]
+        g_pw = torch.zeros_like(r0.params["pw_poses"])
+        g_ad = torch.zeros_like(r0.params["pw_adaptors"])
+        g_small = torch.zeros(self.N, 16, device=self.device)
+        loss = torch.zeros(1, device=self.device)
+        with torch.cuda.device(self.device):
+            self._partials()
+            red = self._reduce()
+            check(self.lib.a3r_align_shard_grad(r0.handle, ptr(red), self.n_floats, ptr(g_pw), ptr(g_ad), ptr(g_small), ptr(loss),
+                                                stream_ptr()), "a3r_align_shard_grad")
+        g_depth = red[:self.N * self.P].reshape(self.N, self.P).clone()
+        g = dict(pw_poses=g_pw, pw_adaptors=g_ad, depth=g_depth, im_poses=g_small[:, 0:7], im_focals=g_small[:, 7], im_pp=g_small[:, 8:10],
+                 shifts=g_small[:, 10])
+        return float(loss.item()), {k: g[k] for k in self.trainable()}
+
+    def loss(self):
+        return torch.tensor([self.loss_grad()[0]], device=self.device)
+
+    @property
+    def collectives(self):
+        """all-reduces issued so far (group form)."""
+        return self._all_reduce.calls if self._all_reduce is not None else 0
+
+    def _apply(self, red, lr):
+        for r in self.replicas:
+            check(self.lib.a3r_align_shard_apply(r.handle, ptr(red), self.n_floats, float(lr), stream_ptr()), "a3r_align_shard_apply")
+
+    def step(self, lr, epoch=None):
+        from .parallel import sharded_step
+        with torch.cuda.device(self.device):
+            sharded_step(self._partials, lambda _: self._reduce(), self._apply, lr)
+
+    def run(self, niter, lr, schedule="cosine", lr_min=1e-6, first_iter=0, total_iters=None):
+        total = total_iters or niter
+        start = self.steps_done
+        if start + niter > self.loss_capacity:
+            raise RuntimeError(f"loss_history too small ({start} + {niter} > {self.loss_capacity})")
+        lrs = np.asarray([schedule_lr(schedule, it / total, lr, lr_min) for it in range(first_iter, first_iter + niter)], dtype=np.float32)
+        if self.group is not None:
+            for v in lrs:
+                self.step(float(v))
+        else:
+            K = len(self.replicas)
+            hs = (C.c_void_p * K)(*[r.handle.value for r in self.replicas])
+            bufs = (C.c_void_p * K)(*[r.buf.data_ptr() for r in self.replicas])
+            with torch.cuda.device(self.device):
+                check(self.lib.a3r_align_shard_run_local(hs, K, bufs, self.n_floats, lrs.ctypes.data_as(C.c_void_p), int(niter), stream_ptr()),
+                      "a3r_align_shard_run_local")
+        return self.loss_history[start:start + niter].cpu().numpy().astype(np.float64)
+
+    def pose_matrices(self):
+        eM = torch.empty(self.E, 3, 4, device=self.device)
+        iR = torch.empty(self.N, 3, 4, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.lib.a3r_align_pose_matrices(self.replicas[0].handle, ptr(eM), ptr(iR), stream_ptr()), "a3r_align_pose_matrices")
+        return eM, iR

@@ -1260,6 +1260,119 @@ __global__ __launch_bounds__(TPB) void align_finalize_b_kernel(AlignDev d, AdamA
     finalize_b_body<MODE>(d, ad, o, sh, shd);
 }
 
+// ------------------------------------------------------------------------------------------- edge shards
+// A shard handle (a3r_align_shard_*) walks only the edges [e0, e1) of the graph: the main kernel runs in MODE 1 on the shard's
+// incidence lists (local edge codes, edge_xf argument advanced by e0 rows) and stores the depth-parameter gradient of its edges
+// with plain 16-byte stores into the reduce buffer; the kernel below adds the chunk partials in the fixed order of the monolithic
+// tail and writes the per-image and per-edge rows behind it.  Nothing non-linear has happened yet: buffers of different shards add.
+//
+// grid (E + N) x 64 threads.  Rows of edges outside the shard are zero.
+__global__ __launch_bounds__(64) void align_shard_gather_kernel(AlignDev d, int e0, int e1, float* rowsN, float* rowsE, float* pad, int npad) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    float t0[16], t1[16];
+    if (b == 0 && lane < npad) pad[lane] = 0.f;          // the floats that round N*P up to a multiple of four
+    if (b < d.E) {
+        float v = 0.f;
+        if (b >= e0 && b < e1) {                          // block-uniform
+            const int el = b - e0;
+            quad_to_all(wave_sum_rows(d.partE + (size_t)d.slot_of[el * 2 + 0] * d.nchunks * 16, d.nchunks, lane), t0);
+            quad_to_all(wave_sum_rows(d.partE + (size_t)d.slot_of[el * 2 + 1] * d.nchunks * 16, d.nchunks, lane), t1);
+#pragma unroll
+            for (int j = 0; j < 13; j++)
+                if (lane == j) v = (float)((double)t0[j] + (double)t1[j]);
+        }
+        if (lane < 16) rowsE[(size_t)b * 16 + lane] = v;
+    } else {
+        const int n = b - d.E;
+        quad_to_all(wave_sum_rows(d.partN + (size_t)n * d.nchunks * 16, d.nchunks, lane), t0);
+        float v = 0.f;
+#pragma unroll
+        for (int j = 0; j < 16; j++)
+            if (lane == j) v = t0[j];
+        if (lane < 16) rowsN[(size_t)n * 16 + lane] = v;
+    }
+}
+
+// Chain rules of every edge and image from the REDUCED rows (what finalize A does from the chunk partials of one handle).
+__global__ __launch_bounds__(TPB) void align_shard_chain_kernel(AlignDev d, const float* __restrict__ rowsN, const float* __restrict__ rowsE) {
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i < d.E) {
+        const f32x4* r = reinterpret_cast<const f32x4*>(rowsE + (size_t)i * 16);
+        const f32x4 a = r[0], b = r[1], c = r[2], e = r[3];
+        const double s[13] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, e.x};
+        edge_chain(d, i, s, false);
+    } else if (i < d.E + d.N) {
+        const int n = i - d.E;
+        const f32x4* r = reinterpret_cast<const f32x4*>(rowsN + (size_t)n * 16);
+        const f32x4 a = r[0], b = r[1], c = r[2], e = r[3];
+        double s[16] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, e.x, e.y, e.z, e.w};
+        image_chain(d, n, s);
+    }
+}
+
+// Adam on the [N, P] depth parameters from the reduced gradient map: reads p, g, m, v and writes p, m, v (28 B per pixel) in
+// 16-byte accesses, two independent quads per thread requested before either is used; HBM-bound.  n4 quads, then < 4 floats.
+constexpr int ADAM_MAP_UNROLL = 2;
+__global__ __launch_bounds__(TPB) void align_adam_map_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                             float* __restrict__ v, size_t n, AdamArgs ad) {
+    const size_t n4 = n / 4;
+    const size_t q0 = ((size_t)blockIdx.x * ADAM_MAP_UNROLL) * TPB + threadIdx.x;
+    f32x4 pv[ADAM_MAP_UNROLL], gv[ADAM_MAP_UNROLL], mv[ADAM_MAP_UNROLL], vv[ADAM_MAP_UNROLL];
+#pragma unroll
+    for (int u = 0; u < ADAM_MAP_UNROLL; u++) {
+        const size_t q = q0 + (size_t)u * TPB;
+        if (q < n4) {
+            pv[u] = reinterpret_cast<const f32x4*>(p)[q]; gv[u] = reinterpret_cast<const f32x4*>(g)[q];
+            mv[u] = reinterpret_cast<const f32x4*>(m)[q]; vv[u] = reinterpret_cast<const f32x4*>(v)[q];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < ADAM_MAP_UNROLL; u++) {
+        const size_t q = q0 + (size_t)u * TPB;
+        if (q < n4) {
+            float pf[4] = {pv[u].x, pv[u].y, pv[u].z, pv[u].w}, mf[4] = {mv[u].x, mv[u].y, mv[u].z, mv[u].w};
+            float vf[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
+            const float gf[4] = {gv[u].x, gv[u].y, gv[u].z, gv[u].w};
+#pragma unroll
+            for (int i = 0; i < 4; i++) adam_update(pf[i], gf[i], mf[i], vf[i], ad);
+            reinterpret_cast<f32x4*>(p)[q] = f32x4{pf[0], pf[1], pf[2], pf[3]};
+            reinterpret_cast<f32x4*>(m)[q] = f32x4{mf[0], mf[1], mf[2], mf[3]};
+            reinterpret_cast<f32x4*>(v)[q] = f32x4{vf[0], vf[1], vf[2], vf[3]};
+        }
+    }
+    if (blockIdx.x == 0 && n4 * 4 + threadIdx.x < n) {
+        const size_t i = n4 * 4 + threadIdx.x;
+        float pp = p[i], mm = m[i], vw = v[i];
+        adam_update(pp, g[i], mm, vw, ad);
+        p[i] = pp; m[i] = mm; v[i] = vw;
+    }
+}
+
+// dst = ((s0 + s1) + s2) + ... over up to SUM_MAX buffers per launch, in this order whatever K is.  dst may be s0.
+constexpr int SUM_MAX = 8;
+struct SumSrcs { const float* s[SUM_MAX]; int k; };
+__global__ __launch_bounds__(TPB) void align_shard_sum_kernel(float* dst, SumSrcs src, size_t n) {
+    const size_t n4 = n / 4;
+    const size_t q = (size_t)blockIdx.x * TPB + threadIdx.x;
+    if (q < n4) {
+        f32x4 x[SUM_MAX];
+#pragma unroll
+        for (int j = 0; j < SUM_MAX; j++)
+            if (j < src.k) x[j] = reinterpret_cast<const f32x4*>(src.s[j])[q];
+        f32x4 acc = x[0];
+#pragma unroll
+        for (int j = 1; j < SUM_MAX; j++)
+            if (j < src.k) acc += x[j];
+        reinterpret_cast<f32x4*>(dst)[q] = acc;
+    }
+    if (blockIdx.x == 0 && n4 * 4 + threadIdx.x < n) {
+        const size_t i = n4 * 4 + threadIdx.x;
+        float acc = src.s[0][i];
+        for (int j = 1; j < src.k; j++) acc += src.s[j][i];
+        dst[i] = acc;
+    }
+}
+
 __global__ void align_export_xf_kernel(AlignDev d, float* edge_M, float* img_R) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < d.E * 12) edge_M[i] = d.edge_xf[(i / 12) * 16 + i % 12];
@@ -1279,6 +1392,10 @@ struct a3r_align_s {
     bool dirty;      // parameters changed by the caller since the transforms were last built
     std::vector<int> ei, ej, inc;     // host copies of the graph (for a3r_align_set_flow)
     int flow_start_iter = 0;
+    // edge shard (a3r_align_shard_create): the incidence tables, partE and the observation buffers cover the edges [e0, e1) only,
+    // with local edge codes; everything indexed by a global edge (edge_xf, gE, lossE, gA, the parameters) has d.E rows
+    bool shard = false;
+    int e0 = 0, e1 = 0;
 };
 
 static void refresh_if_dirty(a3r_align_s* a, hipStream_t st) {
@@ -1288,24 +1405,25 @@ static void refresh_if_dirty(a3r_align_s* a, hipStream_t st) {
     }
 }
 
-static size_t ws_layout(int E, int N, int P, size_t* off /*[17]*/) {
+// Es: edges whose observations the handle walks (== E except for a shard handle)
+static size_t ws_layout(int E, int Es, int N, int P, size_t* off /*[17]*/) {
     const int nch = (P + CHUNK - 1) / CHUNK;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
     off[0] = take((size_t)E * 16 * 4);              // edge_xf
     off[1] = take((size_t)N * 16 * 4);              // img_xf
-    off[2] = take((size_t)2 * E * nch * 16 * 4);    // partE
+    off[2] = take((size_t)2 * Es * nch * 16 * 4);   // partE
     off[3] = take((size_t)N * nch * 16 * 4);        // partN
     off[4] = take((size_t)E * 8 * 4);               // gE
     off[5] = take((size_t)N * 16 * 4);              // gN
     off[6] = take((size_t)E * 4);                   // lossE
     off[7] = take((size_t)(N + 1) * 4);             // inc_ptr
-    off[8] = take((size_t)2 * E * 4);               // inc
-    off[9] = take((size_t)2 * E * 4);               // slot_of
+    off[8] = take((size_t)2 * Es * 4);              // inc
+    off[9] = take((size_t)2 * Es * 4);              // slot_of
     off[10] = take((size_t)N * 4);                  // imw
     off[11] = take((size_t)N * 4);                  // imarea
     off[12] = take((size_t)E * 2 * 4);              // gA
-    off[13] = take((size_t)2 * E * 16 * 4);         // sumE
+    off[13] = take((size_t)2 * Es * 16 * 4);        // sumE
     off[14] = take((size_t)N * 16 * 4);             // sumN
     off[15] = take((size_t)(N + 1) * 4);            // tick
     off[16] = take((size_t)N * 8 * 4);              // order: per dispatch slot {image, kbeg, kend, code0, code1, code2, 0, 0}
@@ -1314,10 +1432,11 @@ static size_t ws_layout(int E, int N, int P, size_t* off /*[17]*/) {
 
 extern "C" size_t a3r_align_workspace_bytes(int E, int N, int P) {
     size_t off[17];
-    return ws_layout(E, N, P, off);
+    return ws_layout(E, E, N, P, off);
 }
 
-extern "C" int a3r_align_create(const a3r_align_desc* s, a3r_align_t* out, void* stream) {
+// e0 == 0, e1 == s->E, shard == false: the monolithic handle
+static int align_create_impl(const a3r_align_desc* s, int e0, int e1, bool shard, a3r_align_t* out, void* stream) {
     A3R_CHECK_ARG(s && out, "a3r_align_create: null argument");
     A3R_CHECK_ARG(s->E > 0 && s->N > 0 && s->P > 0, "a3r_align_create: E, N, P must be positive");
     A3R_CHECK_ARG(s->pred_i && s->pred_j && s->w_i && s->w_j && s->pp0, "a3r_align_create: missing observation buffers");
@@ -1327,7 +1446,8 @@ extern "C" int a3r_align_create(const a3r_align_desc* s, a3r_align_t* out, void*
     A3R_CHECK_ARG(s->adam_pw_poses && s->adam_depth && s->adam_small, "a3r_align_create: missing Adam state");
     A3R_CHECK_ARG(s->loss_history && s->loss_capacity > 0, "a3r_align_create: missing loss_history");
     size_t off[17];
-    const size_t need = ws_layout(s->E, s->N, s->P, off);
+    const int Es = e1 - e0;
+    const size_t need = ws_layout(s->E, Es, s->N, s->P, off);
     A3R_CHECK_ARG(!s->train_adaptors || s->adam_pw_adaptors, "a3r_align_create: train_adaptors needs adam_pw_adaptors");
     A3R_CHECK_ARG(s->workspace && s->workspace_bytes >= need, "a3r_align_create: workspace too small (%zu < %zu)",
                   s->workspace_bytes, need);
@@ -1335,7 +1455,7 @@ extern "C" int a3r_align_create(const a3r_align_desc* s, a3r_align_t* out, void*
         // the per-chunk partial rows are addressed with 32-bit byte offsets from a buffer resource (store16_wt): both arrays must
         // stay below 2 GiB (config 3: 2 * 4032 * 144 * 64 B = 74 MB)
         const size_t nch = ((size_t)s->P + 1023) / 1024;
-        A3R_CHECK_ARG(2 * (size_t)s->E * nch * 64 < (1ull << 31) && (size_t)s->N * nch * 64 < (1ull << 31),
+        A3R_CHECK_ARG(2 * (size_t)Es * nch * 64 < (1ull << 31) && (size_t)s->N * nch * 64 < (1ull << 31),
                       "a3r_align_create: E * P / 1024 too large for the 32-bit partial-sum offsets (E=%d N=%d P=%d)", s->E, s->N, s->P);
     }
     // edge indices must be dense 0..N-1 (base_opt.py:164-167)
@@ -1343,7 +1463,8 @@ extern "C" int a3r_align_create(const a3r_align_desc* s, a3r_align_t* out, void*
     for (int e = 0; e < s->E; e++) {
         const int i = s->ei_host[e], j = s->ej_host[e];
         A3R_CHECK_ARG(i >= 0 && i < s->N && j >= 0 && j < s->N, "a3r_align_create: bad pair indices (edge %d = %d,%d)", e, i, j);
-        deg[i + 1]++; deg[j + 1]++; seen[i] = seen[j] = 1;
+        seen[i] = seen[j] = 1;
+        if (e >= e0 && e < e1) { deg[i + 1]++; deg[j + 1]++; }
     }
     for (int n = 0; n < s->N; n++) A3R_CHECK_ARG(seen[n], "bad pair indices: missing values (image %d has no edge)", n);
     for (int n = 0; n < s->N; n++)
@@ -1353,9 +1474,9 @@ extern "C" int a3r_align_create(const a3r_align_desc* s, a3r_align_t* out, void*
                       "a3r_align_create: bad image shape for image %d", n);
         deg[n + 1] += deg[n];
     }
-    std::vector<int> inc(2 * s->E), slot(2 * s->E), fill(s->N, 0);
-    for (int e = 0; e < s->E; e++) {
-        const int i = s->ei_host[e], j = s->ej_host[e];
+    std::vector<int> inc(2 * Es), slot(2 * Es), fill(s->N, 0);
+    for (int e = 0; e < Es; e++) {            // codes and slots are local to the walked rows [e0, e1)
+        const int i = s->ei_host[e0 + e], j = s->ej_host[e0 + e];
         int k = deg[i] + fill[i]++; inc[k] = e * 2 + 0; slot[e * 2 + 0] = k;
         k = deg[j] + fill[j]++;     inc[k] = e * 2 + 1; slot[e * 2 + 1] = k;
     }
@@ -1365,8 +1486,8 @@ extern "C" int a3r_align_create(const a3r_align_desc* s, a3r_align_t* out, void*
     hipStream_t st = as_stream(stream);
     auto up = [&](size_t o, const void* src, size_t bytes) { return hipMemcpyAsync(ws + o, src, bytes, hipMemcpyHostToDevice, st); };
     hipError_t err = up(off[7], deg.data(), (s->N + 1) * 4);
-    if (err == hipSuccess) err = up(off[8], inc.data(), 2 * s->E * 4);
-    if (err == hipSuccess) err = up(off[9], slot.data(), 2 * s->E * 4);
+    if (err == hipSuccess) err = up(off[8], inc.data(), (size_t)2 * Es * 4);
+    if (err == hipSuccess) err = up(off[9], slot.data(), (size_t)2 * Es * 4);
     if (err == hipSuccess) err = up(off[10], s->imw_host, s->N * 4);
     if (err == hipSuccess) err = up(off[11], s->imarea_host, s->N * 4);
     // dispatch order of the images: most incident edge sides first (stable: ties keep the image order)
@@ -1413,7 +1534,7 @@ extern "C" int a3r_align_create(const a3r_align_desc* s, a3r_align_t* out, void*
         // rows, the edge chain rules, the single-block Adam -- not the two launch boundaries, so the
         // separate launches, whose E + N workgroups reduce in parallel, stay the default.
         const char* t = getenv("A3R_ALIGN_TAIL");
-        d.fused_tail = (t && !strcmp(t, "fused")) ? 1 : 0;
+        d.fused_tail = (t && !strcmp(t, "fused") && !shard) ? 1 : 0;     // a shard's iteration ends after the reduction
     }
     d.inc_ptr = (const int*)(ws + off[7]); d.inc = (const int*)(ws + off[8]); d.slot_of = (const int*)(ws + off[9]);
     d.imw = (const int*)(ws + off[10]); d.imarea = (const int*)(ws + off[11]);
@@ -1423,8 +1544,14 @@ extern "C" int a3r_align_create(const a3r_align_desc* s, a3r_align_t* out, void*
     a->ei.assign(s->ei_host, s->ei_host + s->E);
     a->ej.assign(s->ej_host, s->ej_host + s->E);
     a->inc = inc;
+    a->shard = shard; a->e0 = e0; a->e1 = e1;
     *out = a;
     return A3R_OK;
+}
+
+extern "C" int a3r_align_create(const a3r_align_desc* s, a3r_align_t* out, void* stream) {
+    A3R_CHECK_ARG(s && out, "a3r_align_create: null argument");
+    return align_create_impl(s, 0, s->E, false, out, stream);
 }
 
 extern "C" int a3r_align_destroy(a3r_align_t a) {
@@ -1436,15 +1563,16 @@ template <int MODE>
 static void launch_main(a3r_align_s* a, const AdamArgs& ad, float* g_depth, const TailOut& tout, hipStream_t st) {
     dim3 grid(a->d.nchunks, a->d.N), block(TPB);
     // algorithmic bytes of one iteration: 32 B per edge-pixel + 24 B per image-pixel (+4 mono)
-    const double bytes = 32.0 * a->d.E * a->d.P + (MODE == 2 ? 24.0 : 4.0) * a->d.N * a->d.P + (a->use_mono ? 4.0 * a->d.N * a->d.P : 0.0);
-    ProfScope prof(PK_ALIGN_MAIN, bytes, st);
+    const float* edge_xf = a->d.edge_xf + (size_t)a->e0 * 16;        // local edge codes of a shard index from its first edge
+    const double bytes = 32.0 * (a->e1 - a->e0) * a->d.P + (MODE == 2 ? 24.0 : 4.0) * a->d.N * a->d.P + (a->use_mono ? 4.0 * a->d.N * a->d.P : 0.0);
+    ProfScope prof(a->shard ? PK_ALIGN_SHARD_PARTIAL : PK_ALIGN_MAIN, bytes, st);
     const bool vec = a->d.P % 4 == 0;
 #define A3R_ALIGN_LAUNCH(MONOV, L2V)                                                                                      \
     do {                                                                                                                 \
         if (vec) hipLaunchKernelGGL((align_main_kernel<MONOV, L2V, MODE, true>), grid, block, 0, st, a->d, ad, g_depth, tout, \
-                                    a->d.inc_ptr, a->d.inc, a->d.edge_xf, a->d.img_xf, a->d.imw, a->d.imarea, a->d.order); \
+                                    a->d.inc_ptr, a->d.inc, edge_xf, a->d.img_xf, a->d.imw, a->d.imarea, a->d.order); \
         else hipLaunchKernelGGL((align_main_kernel<MONOV, L2V, MODE, false>), grid, block, 0, st, a->d, ad, g_depth, tout, \
-                                a->d.inc_ptr, a->d.inc, a->d.edge_xf, a->d.img_xf, a->d.imw, a->d.imarea, a->d.order);  \
+                                a->d.inc_ptr, a->d.inc, edge_xf, a->d.img_xf, a->d.imw, a->d.imarea, a->d.order);  \
     } while (0)
     if (a->use_mono) {
         if (a->dist_l2) A3R_ALIGN_LAUNCH(true, true); else A3R_ALIGN_LAUNCH(true, false);
@@ -1475,6 +1603,7 @@ extern "C" size_t a3r_align_flow_workspace_bytes(int E, int N, int P) {
 
 extern "C" int a3r_align_set_flow(a3r_align_t a, const a3r_align_flow_desc* f, void* stream) {
     A3R_CHECK_ARG(a && f, "a3r_align_set_flow: null argument");
+    A3R_CHECK_ARG(!a->shard, "a3r_align_set_flow: an edge-shard handle has no flow variant (the ego-flow terms are not sharded)");
     A3R_CHECK_ARG(!a->use_mono, "a3r_align_set_flow: the flow variant has no mono-depth parameterisation (cloud_opt_flow/optimizer.py:52)");
     AlignDev& d = a->d;
     size_t off[6];
@@ -1513,6 +1642,7 @@ extern "C" size_t a3r_align_depth_prior_workspace_bytes(int N, int P) {
 extern "C" int a3r_align_set_depth_prior(a3r_align_t a, float weight, const float* init_log_depth, const unsigned char* dynamic_mask,
                                          void* workspace, size_t workspace_bytes, void* stream) {
     A3R_CHECK_ARG(a, "a3r_align_set_depth_prior: null handle");
+    A3R_CHECK_ARG(!a->shard, "a3r_align_set_depth_prior: an edge-shard handle has no depth prior (it belongs to the flow variant)");
     A3R_CHECK_ARG(weight >= 0.f, "a3r_align_set_depth_prior: negative weight");
     AlignDev& d = a->d;
     if (weight == 0.f) {
@@ -1549,6 +1679,7 @@ static void launch_flow(a3r_align_s* a, int epoch, hipStream_t st) {
 
 extern "C" int a3r_align_step_epoch(a3r_align_t a, float lr, int epoch, void* stream) {
     A3R_CHECK_ARG(a, "a3r_align_step: null handle");
+    A3R_CHECK_ARG(!a->shard, "a3r_align_step: edge-shard handle (use a3r_align_shard_partial / a3r_align_shard_apply)");
     A3R_CHECK_ARG(a->steps < a->loss_capacity, "a3r_align_step: loss_history full (%d)", a->loss_capacity);
     hipStream_t st = as_stream(stream);
     const int t = a->steps + 1;
@@ -1588,6 +1719,7 @@ extern "C" int a3r_align_step(a3r_align_t a, float lr, void* stream) {
 
 extern "C" int a3r_align_loss(a3r_align_t a, float* loss_dev, void* stream) {
     A3R_CHECK_ARG(a && loss_dev, "a3r_align_loss: null argument");
+    A3R_CHECK_ARG(!a->shard, "a3r_align_loss: edge-shard handle (use a3r_align_shard_partial / a3r_align_shard_grad)");
     hipStream_t st = as_stream(stream);
     AdamArgs ad = {};
     refresh_if_dirty(a, st);
@@ -1605,6 +1737,7 @@ extern "C" int a3r_align_loss(a3r_align_t a, float* loss_dev, void* stream) {
 extern "C" int a3r_align_grad_full(a3r_align_t a, int epoch, float* g_pw_poses, float* g_pw_adaptors, float* g_depth, float* g_small,
                                    float* loss_dev, void* stream) {
     A3R_CHECK_ARG(a && g_pw_poses && g_depth && g_small && loss_dev, "a3r_align_grad: null argument");
+    A3R_CHECK_ARG(!a->shard, "a3r_align_grad: edge-shard handle (use a3r_align_shard_partial / a3r_align_shard_grad)");
     hipStream_t st = as_stream(stream);
     AdamArgs ad = {};
     refresh_if_dirty(a, st);
@@ -1660,5 +1793,141 @@ extern "C" int a3r_align_pose_matrices(a3r_align_t a, float* edge_M, float* img_
     const int n = (a->d.E > a->d.N ? a->d.E : a->d.N) * 12;
     hipLaunchKernelGGL(align_export_xf_kernel, dim3((n + 255) / 256), dim3(256), 0, st, a->d, edge_M, img_R);
     A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+// ---- edge shards -----------------------------------------------------------------------------------------------
+extern "C" size_t a3r_align_shard_workspace_bytes(int E, int E_shard, int N, int P) {
+    size_t off[17];
+    return ws_layout(E, E_shard, N, P, off);
+}
+
+static size_t shard_depth_floats(int N, int P) { return align_up((size_t)N * P, 4); }
+
+extern "C" size_t a3r_align_shard_reduce_floats(int E, int N, int P) {
+    return shard_depth_floats(N, P) + (size_t)N * 16 + (size_t)E * 16;
+}
+
+extern "C" int a3r_align_shard_create(const a3r_align_desc* s, int e0, int e1, a3r_align_t* out, void* stream) {
+    A3R_CHECK_ARG(s && out, "a3r_align_shard_create: null argument");
+    A3R_CHECK_ARG(e0 < e1, "a3r_align_shard_create: empty shard (e0 = %d >= e1 = %d)", e0, e1);
+    A3R_CHECK_ARG(e0 >= 0 && e1 <= s->E, "a3r_align_shard_create: rows [%d, %d) out of range (the graph has %d edges)", e0, e1, s->E);
+    return align_create_impl(s, e0, e1, true, out, stream);
+}
+
+static int shard_check(a3r_align_t a, const float* buf, size_t n_floats, const char* who) {
+    A3R_CHECK_ARG(a && buf, "%s: null argument", who);
+    A3R_CHECK_ARG(a->shard, "%s: not an edge-shard handle (a3r_align_shard_create)", who);
+    const size_t want = a3r_align_shard_reduce_floats(a->d.E, a->d.N, a->d.P);
+    A3R_CHECK_ARG(n_floats == want, "%s: reduce buffer of the wrong length (%zu floats, expected %zu)", who, n_floats, want);
+    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(buf) & 15) == 0, "%s: the reduce buffer must be 16-byte aligned", who);
+    return A3R_OK;
+}
+
+extern "C" int a3r_align_shard_partial(a3r_align_t a, float* reduce_buf, size_t n_floats, void* stream) {
+    if (int rc = shard_check(a, reduce_buf, n_floats, "a3r_align_shard_partial")) return rc;
+    hipStream_t st = as_stream(stream);
+    const AlignDev& d = a->d;
+    AdamArgs ad = {};
+    refresh_if_dirty(a, st);
+    const TailOut tout = {nullptr, nullptr, nullptr, nullptr};
+    launch_main<1>(a, ad, reduce_buf, tout, st);
+    {
+        ProfScope prof(PK_ALIGN_SMALL, 0.0, st);
+        const size_t np = (size_t)d.N * d.P, npad = shard_depth_floats(d.N, d.P);
+        float* rowsN = reduce_buf + npad;
+        hipLaunchKernelGGL(align_shard_gather_kernel, dim3(d.E + d.N), dim3(64), 0, st, d, a->e0, a->e1, rowsN, rowsN + (size_t)d.N * 16,
+                           reduce_buf + np, (int)(npad - np));
+    }
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+static void launch_shard_chain(a3r_align_s* a, const float* reduced, hipStream_t st) {
+    const AlignDev& d = a->d;
+    const float* rowsN = reduced + shard_depth_floats(d.N, d.P);
+    hipLaunchKernelGGL(align_shard_chain_kernel, dim3((d.E + d.N + TPB - 1) / TPB), dim3(TPB), 0, st, d, rowsN, rowsN + (size_t)d.N * 16);
+}
+
+extern "C" int a3r_align_shard_apply(a3r_align_t a, const float* reduced, size_t n_floats, float lr, void* stream) {
+    if (int rc = shard_check(a, reduced, n_floats, "a3r_align_shard_apply")) return rc;
+    A3R_CHECK_ARG(a->steps < a->loss_capacity, "a3r_align_shard_apply: loss_history full (%d)", a->loss_capacity);
+    hipStream_t st = as_stream(stream);
+    const AlignDev& d = a->d;
+    const int t = a->steps + 1;
+    AdamArgs ad;
+    ad.lr = lr;
+    ad.step_size = (float)((double)lr / (1.0 - pow((double)ADAM_B1, t)));
+    ad.bc2_sqrt = (float)sqrt(1.0 - pow((double)ADAM_B2, t));
+    ad.step = a->steps;
+    refresh_if_dirty(a, st);
+    {
+        // the [N, P] update first: it reads nothing the small kernels write
+        const size_t n = (size_t)d.N * d.P;
+        ProfScope prof(PK_ALIGN_ADAM_MAP, 28.0 * (double)n, st);
+        const size_t quads = n / 4, per_block = (size_t)TPB * ADAM_MAP_UNROLL;
+        const unsigned blocks = (unsigned)std::max<size_t>(1, (quads + per_block - 1) / per_block);
+        hipLaunchKernelGGL(align_adam_map_kernel, dim3(blocks), dim3(TPB), 0, st, d.depth, reduced, d.adam_depth, d.adam_depth + n, n, ad);
+    }
+    {
+        ProfScope prof(PK_ALIGN_SMALL, 0.0, st);
+        const TailOut tout = {nullptr, nullptr, nullptr, nullptr};
+        launch_shard_chain(a, reduced, st);
+        hipLaunchKernelGGL((align_finalize_b_kernel<2>), dim3(1), dim3(TPB), 0, st, d, ad, tout);
+    }
+    A3R_LAUNCH_CHECK();
+    a->steps++;
+    return A3R_OK;
+}
+
+extern "C" int a3r_align_shard_grad(a3r_align_t a, const float* reduced, size_t n_floats, float* g_pw_poses, float* g_pw_adaptors,
+                                    float* g_small, float* loss_dev, void* stream) {
+    if (int rc = shard_check(a, reduced, n_floats, "a3r_align_shard_grad")) return rc;
+    A3R_CHECK_ARG(g_pw_poses && g_small && loss_dev, "a3r_align_shard_grad: null argument");
+    hipStream_t st = as_stream(stream);
+    AdamArgs ad = {};
+    refresh_if_dirty(a, st);
+    const TailOut tout = {g_pw_poses, g_small, loss_dev, g_pw_adaptors};
+    launch_shard_chain(a, reduced, st);
+    hipLaunchKernelGGL((align_finalize_b_kernel<1>), dim3(1), dim3(TPB), 0, st, a->d, ad, tout);
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+extern "C" int a3r_align_shard_sum(float* dst, const float* const* srcs_host, int K, size_t n_floats, void* stream) {
+    A3R_CHECK_ARG(dst && srcs_host && K >= 1 && n_floats > 0, "a3r_align_shard_sum: bad argument");
+    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(dst) & 15) == 0, "a3r_align_shard_sum: buffers must be 16-byte aligned");
+    for (int k = 0; k < K; k++)
+        A3R_CHECK_ARG(srcs_host[k] && (reinterpret_cast<uintptr_t>(srcs_host[k]) & 15) == 0,
+                      "a3r_align_shard_sum: buffer %d is null or not 16-byte aligned", k);
+    hipStream_t st = as_stream(stream);
+    ProfScope prof(PK_ALIGN_SMALL, 0.0, st);
+    const size_t quads = n_floats / 4;
+    const unsigned blocks = (unsigned)std::max<size_t>(1, (quads + TPB - 1) / TPB);
+    // groups of SUM_MAX buffers; from the second group on the running total in dst is the first addend: the order of the additions
+    // is that of one left-to-right sum
+    for (int k = 0; k < K;) {
+        SumSrcs src;
+        src.k = 0;
+        if (k > 0) src.s[src.k++] = dst;
+        while (src.k < SUM_MAX && k < K) src.s[src.k++] = srcs_host[k++];
+        for (int j = src.k; j < SUM_MAX; j++) src.s[j] = nullptr;
+        hipLaunchKernelGGL(align_shard_sum_kernel, dim3(blocks), dim3(TPB), 0, st, dst, src, n_floats);
+    }
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+extern "C" int a3r_align_shard_run_local(const a3r_align_t* handles_host, int K, float* const* bufs_host, size_t n_floats,
+                                         const float* lrs_host, int n, void* stream) {
+    A3R_CHECK_ARG(handles_host && bufs_host && lrs_host && K >= 1 && n >= 0, "a3r_align_shard_run_local: bad argument");
+    for (int it = 0; it < n; it++) {
+        for (int k = 0; k < K; k++)
+            if (int rc = a3r_align_shard_partial(handles_host[k], bufs_host[k], n_floats, stream)) return rc;
+        if (K > 1)
+            if (int rc = a3r_align_shard_sum(bufs_host[0], bufs_host, K, n_floats, stream)) return rc;
+        for (int k = 0; k < K; k++)
+            if (int rc = a3r_align_shard_apply(handles_host[k], bufs_host[0], n_floats, lrs_host[it], stream)) return rc;
+    }
     return A3R_OK;
 }

@@ -38,7 +38,8 @@ static const char* g_names[PK_COUNT] = {"gemm_kernel<0> (linear)", "gemm_kernel<
                                         "align_finalize/prep kernels", "gemm_bf3_kernel (linear, split-bf16 MFMA)",
                                         "split_bf3_kernel", "gemm_bf3_kernel<1> (conv3x3, split-bf16 MFMA)",
                                         "attn_bf3_kernel", "gemm_fh2_kernel (linear, split-fp16 MFMA)", "attn_fh2_kernel",
-                                        "gemm_fh2_kernel<1> (conv3x3, split-fp16 MFMA)"};
+                                        "gemm_fh2_kernel<1> (conv3x3, split-fp16 MFMA)", "align_main_kernel (edge-shard partial)",
+                                        "align_adam_map_kernel"};
 static hipEvent_t get_event() {
     if (!g_pool.empty()) { hipEvent_t e = g_pool.back(); g_pool.pop_back(); return e; }
     hipEvent_t e;

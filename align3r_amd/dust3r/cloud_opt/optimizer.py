@@ -26,7 +26,12 @@ class PointCloudOptimizer:
 
     def __init__(self, view1, view2, pred1, pred2, if_use_mono, mono_depths, dist='l1', conf='log', min_conf_thr=3,
                  base_scale=0.5, allow_pw_adaptors=False, pw_break=20, rand_pose=torch.randn, iterationsCount=None,
-                 verbose=True, optimize_pp=False, focal_break=20):
+                 verbose=True, optimize_pp=False, focal_break=20, edge_shards=None, edge_shard_group=None):
+        # edge_shards=K / edge_shard_group=<process group>: the edge-sharded engine (aligner.ShardedAlignEngine) instead of the fused
+        # one; the initialisations (init='mst' / 'known_poses') still work on the gathered observations
+        if edge_shards is not None and edge_shard_group is not None:
+            raise ValueError('pass edge_shards or edge_shard_group, not both')
+        self.edge_shards, self.edge_shard_group = edge_shards, edge_shard_group
         idx1 = view1['idx'] if isinstance(view1['idx'], list) else torch.as_tensor(view1['idx']).tolist()
         idx2 = view2['idx'] if isinstance(view2['idx'], list) else torch.as_tensor(view2['idx']).tolist()
         self.edges = [(int(i), int(j)) for i, j in zip(idx1, idx2)]
@@ -154,6 +159,12 @@ class PointCloudOptimizer:
 
     def _build_engine(self, device):
         w_i, w_j = self._stacked_weights()
+        if self.edge_shards is not None or self.edge_shard_group is not None:
+            from ...aligner import ShardedAlignEngine
+            return ShardedAlignEngine([i for i, j in self.edges], [j for i, j in self.edges], self._pred_i, self._pred_j, w_i, w_j,
+                                      self.imshapes, mono=self.mono_depths, base_scale=self.base_scale, pw_break=self.pw_break,
+                                      focal_break=self.focal_break, norm_pw_scale=self.norm_pw_scale, dist=self.dist, device=device,
+                                      local_shards=self.edge_shards, group=self.edge_shard_group, **self._flags)
         return AlignEngine([i for i, j in self.edges], [j for i, j in self.edges], self._pred_i, self._pred_j, w_i, w_j,
                            self.imshapes, mono=self.mono_depths, base_scale=self.base_scale, pw_break=self.pw_break,
                            focal_break=self.focal_break, norm_pw_scale=self.norm_pw_scale, dist=self.dist, device=device, **self._flags)

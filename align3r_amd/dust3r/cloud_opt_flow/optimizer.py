@@ -32,6 +32,9 @@ class PointCloudOptimizer(_Base):
             raise NotImplementedError("only flow_loss_fn='smooth_l1' (the reference's 'mse' branch is broken: optimizer.py:101)")
         if sam2_mask_refine:
             raise NotImplementedError('sam2_mask_refine: SAM-2 is out of scope (SURVEY section 2)')
+        if kwargs.get('edge_shards') is not None or kwargs.get('edge_shard_group') is not None:
+            raise NotImplementedError('edge_shards: the flow variant (shared focal, temporal smoothing, ego-flow, depth prior) is not '
+                                      'edge-sharded; only cloud_opt.PointCloudOptimizer is')
         super().__init__(view1, view2, pred1, pred2, False, [], optimize_pp=optimize_pp, focal_break=focal_break, **kwargs)
         self.shared_focal = bool(shared_focal)
         self.num_total_iter = num_total_iter

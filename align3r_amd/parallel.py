@@ -129,3 +129,24 @@ def sharded_inference(pairs, forward_fn, device, batch_size=8, group=None, force
     return dict(view1=view1, view2=view2,
                 pred1=dict(pts3d=bufs["pts1"][:n], conf=bufs["conf1"][:n], pred_mask=[0] * n),
                 pred2=dict(pts3d_in_other_view=bufs["pts2"][:n], conf=bufs["conf2"][:n], pred_mask=[0] * n), loss=None)
+
+
+# ---------------------------------------------------------------------------------------------- edge-sharded global alignment
+class GradientAllReduce:
+    """The ONE collective of an edge-sharded alignment iteration (option B): all_reduce(SUM) of the flat reduce buffer
+    in place (RCCL on GPUs, gloo on CPU tensors).  `calls` counts the collectives issued."""
+
+    def __init__(self, group=None):
+        self.group = group
+        self.calls = 0
+
+    def __call__(self, buf):
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.group)
+        self.calls += 1
+        return buf
+
+
+def sharded_step(partial, reduce, apply, lr):
+    """One iteration of the sharded aligner: partial() -> this rank's additive buffer; reduce(buf) -> the graph's; apply(buf, lr) ->
+    the replicated update.  aligner.ShardedAlignEngine drives its HIP entry points through this; tests drive a CPU stand-in."""
+    apply(reduce(partial()), lr)

@@ -596,6 +596,37 @@ int a3r_align_invalidate(a3r_align_t a);
 /* per-edge [E,3,4] = [s*R*diag(a) | s*T] and per-image [N,3,4] = [R | t] (get_pw_poses/get_im_poses rows 0-2) */
 int a3r_align_pose_matrices(a3r_align_t a, float* edge_M, float* img_R, void* stream);
 
+/* Edge-sharded form of the same loop ("option B"): a shard handle owns the observation rows [e0, e1) of a graph
+ * with desc->E edges and a full replica of every parameter and Adam moment.  One iteration is
+ *     a3r_align_shard_partial   (every shard: loss + gradient sums of its own edges -> one flat fp32 reduce buffer)
+ *     sum of the buffers        (one all-reduce(SUM) between ranks, or a3r_align_shard_sum inside one process)
+ *     a3r_align_shard_apply     (every shard: chain rules, scale-normalisation coupling and Adam from the REDUCED buffer)
+ * Everything in the reduce buffer is additive over edges; every non-linear step runs after the reduction, so the replicas stay
+ * identical.  Layout (floats): [N*P rounded up to 4] d loss / d depth parameter, [N][16] per-image sums, [E][16] per-edge sums
+ * (12 gradient sums, the loss of the edge, 3 zeros; rows outside [e0, e1) are zero).
+ * desc is read as by a3r_align_create, except: pred_i / pred_j / w_i / w_j hold the shard's rows only ([e1 - e0, P, 3] / [e1 - e0, P],
+ * row 0 = edge e0); ei_host / ej_host, total_area_i / j and the parameter buffers describe the WHOLE graph; workspace holds
+ * a3r_align_shard_workspace_bytes(E, e1 - e0, N, P).  a3r_align_step / _loss / _grad*, a3r_align_set_flow and
+ * a3r_align_set_depth_prior refuse a shard handle; destroy, steps_done, invalidate and pose_matrices work on it. */
+size_t a3r_align_shard_workspace_bytes(int E, int E_shard, int N, int P);
+size_t a3r_align_shard_reduce_floats(int E, int N, int P);
+int a3r_align_shard_create(const a3r_align_desc* desc, int e0, int e1, a3r_align_t* out, void* stream);
+/* reduce_buf: device, 16-byte aligned, n_floats == a3r_align_shard_reduce_floats(E, N, P); every float is written. */
+int a3r_align_shard_partial(a3r_align_t a, float* reduce_buf, size_t n_floats, void* stream);
+/* One update from the reduced buffer with learning rate lr; the loss lands in loss_history like a3r_align_step's. */
+int a3r_align_shard_apply(a3r_align_t a, const float* reduced, size_t n_floats, float lr, void* stream);
+/* Gradients of the small parameters and the loss from the reduced buffer, without updating (layouts of a3r_align_grad_full;
+ * g_pw_adaptors may be NULL); the gradient of the depth parameters is the first N*P floats of the reduced buffer itself. */
+int a3r_align_shard_grad(a3r_align_t a, const float* reduced, size_t n_floats, float* g_pw_poses, float* g_pw_adaptors,
+                         float* g_small, float* loss_dev, void* stream);
+/* dst = ((src[0] + src[1]) + src[2]) + ... over K device buffers of n_floats floats (srcs_host: HOST array of K device pointers),
+ * always in this order: bitwise reproducible.  dst may be src[0]. */
+int a3r_align_shard_sum(float* dst, const float* const* srcs_host, int K, size_t n_floats, void* stream);
+/* n iterations of K shard handles of ONE graph living in one process on one device (learning rates as a3r_align_run): per
+ * iteration K partials into bufs_host[k], their fixed-order sum into bufs_host[0], K applies. */
+int a3r_align_shard_run_local(const a3r_align_t* handles_host, int K, float* const* bufs_host, size_t n_floats,
+                              const float* lrs_host, int n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
