@@ -166,6 +166,7 @@ SIGNATURES = {
     "a3r_align_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "a3r_align_create": (C.c_int, [C.POINTER(AlignDesc), C.POINTER(c_void), c_void]),
     "a3r_align_destroy": (C.c_int, [c_void]),
+    "a3r_align_set_train_masks": (C.c_int, [c_void, c_void, c_void, c_void, c_void, c_void]),
     "a3r_align_step": (C.c_int, [c_void, C.c_float, c_void]),
     "a3r_align_loss": (C.c_int, [c_void, c_void, c_void]),
     "a3r_align_grad": (C.c_int, [c_void, c_void, c_void, c_void, c_void, c_void]),

@@ -155,6 +155,32 @@ class AlignEngine:
                                                          pr["workspace"].data_ptr(), pr["workspace"].numel(), stream_ptr()),
                       "a3r_align_set_depth_prior")
         self.handle = h
+        self._push_train_masks()
+
+    def _push_train_masks(self, force=False):
+        m = getattr(self, "train_masks", None)
+        if m is None or (not force and all(v is None for v in m.values())):
+            return
+        arg = lambda v: None if v is None else v.ctypes.data_as(C.c_void_p)
+        with torch.cuda.device(self.device):
+            check(self.lib.a3r_align_set_train_masks(self.handle, arg(m["pose"]), arg(m["focal"]), arg(m["pp"]), arg(m["depth"]),
+                                                     stream_ptr()), "a3r_align_set_train_masks")
+
+    def set_train_masks(self, pose=None, focal=None, pp=None, depth=None):
+        """Per-image train masks ([N] booleans, True = trained; None = no per-image freeze, the train_* flag alone decides).
+        A frozen group gets no Adam step and keeps its moments; loss_grad() returns exact zeros in its rows.  The masks survive
+        set_params / set_trainable (the handle is re-created with them).  Every call replaces all four."""
+        if focal is not None and self.shared_focal:
+            raise ValueError("a per-image focal mask cannot be combined with shared_focal (one focal parameter for all images)")
+        m = {}
+        for k, v in dict(pose=pose, focal=focal, pp=pp, depth=depth).items():
+            if v is not None:
+                v = np.ascontiguousarray(np.asarray(v).astype(bool).astype(np.uint8)).reshape(-1)
+                if v.shape[0] != self.N:
+                    raise ValueError(f"train mask {k!r}: expected {self.N} entries, got {v.shape[0]}")
+            m[k] = v
+        self.train_masks = m
+        self._push_train_masks(force=True)
 
     def __del__(self):
         try:

@@ -34,6 +34,7 @@ constexpr int CHUNK = PXT * TPB;       // pixels per workgroup
 #endif
 constexpr int EB = A3R_ALIGN_NBUF == 3 ? 9 : 8;   // (edge,side) entries per LDS reduction batch (a multiple of the buffers)
 constexpr int MAX_INC = 2048;          // edge sides incident to one image (their codes sit in LDS: 8 KB)
+constexpr int FREEZE_POSE = 1, FREEZE_FOCAL = 2, FREEZE_PP = 4, FREEZE_DEPTH = 8;
 constexpr float ADAM_B1 = 0.9f, ADAM_B2 = 0.9f, ADAM_EPS = 1e-8f;  // base_opt.py:435
 
 struct AlignDev {
@@ -50,6 +51,10 @@ struct AlignDev {
     int* tick;                        // [N + 1] arrival counters of the in-kernel tail: per image, then all images (zero between launches)
     int fused_tail;                   // 1: the main kernel finishes the iteration itself (last-block-done tickets); 0: finalize A/B launches
     const int *inc_ptr, *inc, *slot_of, *imw, *imarea, *order;
+    // per-image freeze bits (a3r_align_set_train_masks; all zero otherwise): a set bit takes the image's parameter group out of
+    // the update whatever the handle-wide train_* switch says, and zeroes its rows of the MODE 1 gradients.  The depth-map bit is
+    // mirrored in slot 6 of the image's dispatch row (order[]), which the main kernel has in scalar registers anyway.
+    const int* freeze;                // [N] FREEZE_* bits
     float* loss_history;
     // cloud_opt_flow extras (a3r_align_set_flow); all zero / null for the plain cloud_opt aligner
     int shared_focal;
@@ -284,6 +289,7 @@ __global__ __launch_bounds__(TPB, VEC ? A3R_ALIGN_MIN_WAVES : 2) void align_main
     // which the workgroup streamed nothing (15 % of its lifetime by s_memtime stamps, tools/align_stamps.py)
     const int* tb = order + blockIdx.y * 8;
     const int n = tb[0], kbeg = tb[1], kend = tb[2];
+    const bool depth_frozen = (tb[6] & FREEZE_DEPTH) != 0;          // workgroup-uniform: the image is fixed per workgroup
     const int chunk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int P = d.P;
     constexpr int PSTEP = VEC ? 1 : TPB;
@@ -498,7 +504,7 @@ __global__ __launch_bounds__(TPB, VEC ? A3R_ALIGN_MIN_WAVES : 2) void align_main
     if (MODE != 0) {
     // the Adam moments of this thread's pixels are requested now: their latency runs under the per-image sums below
     f32x4 m4 = {0.f, 0.f, 0.f, 0.f}, v4 = {0.f, 0.f, 0.f, 0.f};
-    if (VEC && MODE == 2 && valid[0]) {
+    if (VEC && MODE == 2 && valid[0] && !depth_frozen) {
         const size_t off = (size_t)n * P + pix0;
         m4 = *reinterpret_cast<const f32x4*>(d.adam_depth + off);
         v4 = *reinterpret_cast<const f32x4*>(d.adam_depth + (size_t)d.N * P + off);
@@ -540,8 +546,9 @@ __global__ __launch_bounds__(TPB, VEC ? A3R_ALIGN_MIN_WAVES : 2) void align_main
             const size_t off = (size_t)n * P + pix0;
             if (MODE == 1) {
                 f32x4 g4 = {gout[0], gout[1], gout[2], gout[3]};
+                if (depth_frozen) g4 = f32x4{0.f, 0.f, 0.f, 0.f};
                 *reinterpret_cast<f32x4*>(g_depth + off) = g4;
-            } else {
+            } else if (!depth_frozen) {       // a frozen depth map and its Adam moments are not touched
                 float pm[4] = {m4.x, m4.y, m4.z, m4.w}, pv[4] = {v4.x, v4.y, v4.z, v4.w}, pp[4];
 #pragma unroll
                 for (int i = 0; i < PXT; i++) { pp[i] = raw[i]; adam_update(pp[i], gout[i], pm[i], pv[i], ad); }
@@ -557,8 +564,8 @@ __global__ __launch_bounds__(TPB, VEC ? A3R_ALIGN_MIN_WAVES : 2) void align_main
             if (!valid[i]) continue;
             const size_t off = (size_t)n * P + pix0 + i * PSTEP;
             if (MODE == 1) {
-                g_depth[off] = gout[i];
-            } else {
+                g_depth[off] = depth_frozen ? 0.f : gout[i];
+            } else if (!depth_frozen) {
                 float m = d.adam_depth[off], v = d.adam_depth[NP + off], pv = raw[i];
                 adam_update(pv, gout[i], m, v, ad);
                 d.depth[off] = pv; d.adam_depth[off] = m; d.adam_depth[NP + off] = v;
@@ -1227,7 +1234,12 @@ __device__ void finalize_b_body(const AlignDev& d, const AdamArgs& ad, const Tai
     for (int i = tid; i < d.N * 16; i += TPB) {
         const int n = i >> 4, j = i & 15;
         const float g = d.gN[i];
-        if (MODE == 1) { g_small[i] = g; continue; }
+        // a frozen group of this image: no Adam step, moments untouched (torch leaves a parameter without requires_grad out of
+        // the optimiser altogether); its gradient row reads as exact zeros
+        const int fz = d.freeze[n];
+        const bool frozen = j < 7 ? (fz & FREEZE_POSE) : j == 7 ? (fz & FREEZE_FOCAL) : j < 10 ? (fz & FREEZE_PP) : false;
+        if (MODE == 1) { g_small[i] = frozen ? 0.f : g; continue; }
+        if (frozen) continue;
         float* target = nullptr;
         if (j < 7) { if (d.train_poses) target = d.im_poses + n * 7 + j; }
         else if (j == 7) { if (d.train_focals && !d.shared_focal) target = d.im_focals + n; }
@@ -1391,11 +1403,13 @@ struct a3r_align_s {
     int loss_capacity;
     bool dirty;      // parameters changed by the caller since the transforms were last built
     std::vector<int> ei, ej, inc;     // host copies of the graph (for a3r_align_set_flow)
+    std::vector<int> tab;             // host copy of the dispatch rows (a3r_align_set_train_masks rewrites slot 6)
     int flow_start_iter = 0;
     // edge shard (a3r_align_shard_create): the incidence tables, partE and the observation buffers cover the edges [e0, e1) only,
     // with local edge codes; everything indexed by a global edge (edge_xf, gE, lossE, gA, the parameters) has d.E rows
     bool shard = false;
     int e0 = 0, e1 = 0;
+    bool has_focal_mask = false;      // a3r_align_set_flow refuses shared_focal next to a per-image focal mask
 };
 
 static void refresh_if_dirty(a3r_align_s* a, hipStream_t st) {
@@ -1406,7 +1420,7 @@ static void refresh_if_dirty(a3r_align_s* a, hipStream_t st) {
 }
 
 // Es: edges whose observations the handle walks (== E except for a shard handle)
-static size_t ws_layout(int E, int Es, int N, int P, size_t* off /*[17]*/) {
+static size_t ws_layout(int E, int Es, int N, int P, size_t* off /*[18]*/) {
     const int nch = (P + CHUNK - 1) / CHUNK;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
@@ -1426,12 +1440,13 @@ static size_t ws_layout(int E, int Es, int N, int P, size_t* off /*[17]*/) {
     off[13] = take((size_t)2 * Es * 16 * 4);        // sumE
     off[14] = take((size_t)N * 16 * 4);             // sumN
     off[15] = take((size_t)(N + 1) * 4);            // tick
-    off[16] = take((size_t)N * 8 * 4);              // order: per dispatch slot {image, kbeg, kend, code0, code1, code2, 0, 0}
+    off[16] = take((size_t)N * 8 * 4);              // order: per dispatch slot {image, kbeg, kend, code0, code1, code2, freeze bits, 0}
+    off[17] = take((size_t)N * 4);                  // freeze
     return o;
 }
 
 extern "C" size_t a3r_align_workspace_bytes(int E, int N, int P) {
-    size_t off[17];
+    size_t off[18];
     return ws_layout(E, E, N, P, off);
 }
 
@@ -1445,7 +1460,7 @@ static int align_create_impl(const a3r_align_desc* s, int e0, int e1, bool shard
     A3R_CHECK_ARG(!s->use_mono || (s->mono && s->shifts), "a3r_align_create: use_mono needs mono and shifts");
     A3R_CHECK_ARG(s->adam_pw_poses && s->adam_depth && s->adam_small, "a3r_align_create: missing Adam state");
     A3R_CHECK_ARG(s->loss_history && s->loss_capacity > 0, "a3r_align_create: missing loss_history");
-    size_t off[17];
+    size_t off[18];
     const int Es = e1 - e0;
     const size_t need = ws_layout(s->E, Es, s->N, s->P, off);
     A3R_CHECK_ARG(!s->train_adaptors || s->adam_pw_adaptors, "a3r_align_create: train_adaptors needs adam_pw_adaptors");
@@ -1504,6 +1519,7 @@ static int align_create_impl(const a3r_align_desc* s, int e0, int e1, bool shard
     }
     if (err == hipSuccess) err = up(off[16], tab.data(), tab.size() * 4);
     if (err == hipSuccess) err = hipMemsetAsync(ws + off[15], 0, (size_t)(s->N + 1) * 4, st);
+    if (err == hipSuccess) err = hipMemsetAsync(ws + off[17], 0, (size_t)s->N * 4, st);
     if (err == hipSuccess) err = hipStreamSynchronize(st);   // host vectors go out of scope
     if (err != hipSuccess) {
         delete a;
@@ -1526,7 +1542,7 @@ static int align_create_impl(const a3r_align_desc* s, int e0, int e1, bool shard
     d.gE = (float*)(ws + off[4]); d.gN = (float*)(ws + off[5]); d.lossE = (float*)(ws + off[6]);
     d.gA = (float*)(ws + off[12]);
     d.sumE = (float*)(ws + off[13]); d.sumN = (float*)(ws + off[14]); d.tick = (int*)(ws + off[15]);
-    d.order = (const int*)(ws + off[16]);
+    d.order = (const int*)(ws + off[16]); d.freeze = (const int*)(ws + off[17]);
     {
         // A3R_ALIGN_TAIL=fused: finish the iteration inside the main launch (last-block-done tickets) instead of the two small
         // finalize launches.  Correct and bitwise identical, but measured SLOWER on MI355X (config 2: 147 vs 124 + 18 us per
@@ -1544,6 +1560,7 @@ static int align_create_impl(const a3r_align_desc* s, int e0, int e1, bool shard
     a->ei.assign(s->ei_host, s->ei_host + s->E);
     a->ej.assign(s->ej_host, s->ej_host + s->E);
     a->inc = inc;
+    a->tab = tab;
     a->shard = shard; a->e0 = e0; a->e1 = e1;
     *out = a;
     return A3R_OK;
@@ -1552,6 +1569,28 @@ static int align_create_impl(const a3r_align_desc* s, int e0, int e1, bool shard
 extern "C" int a3r_align_create(const a3r_align_desc* s, a3r_align_t* out, void* stream) {
     A3R_CHECK_ARG(s && out, "a3r_align_create: null argument");
     return align_create_impl(s, 0, s->E, false, out, stream);
+}
+
+extern "C" int a3r_align_set_train_masks(a3r_align_t a, const unsigned char* pose_host, const unsigned char* focal_host,
+                                         const unsigned char* pp_host, const unsigned char* depth_host, void* stream) {
+    A3R_CHECK_ARG(a, "a3r_align_set_train_masks: null handle");
+    A3R_CHECK_ARG(!a->shard, "a3r_align_set_train_masks: an edge-shard handle has no per-image train masks (the shard engine is not extended)");
+    A3R_CHECK_ARG(!(focal_host && a->d.shared_focal), "a3r_align_set_train_masks: a focal mask needs one focal per image (shared_focal is set)");
+    const int N = a->d.N;
+    std::vector<int> fz(N, 0);
+    for (int n = 0; n < N; n++) {
+        if (pose_host && !pose_host[n]) fz[n] |= FREEZE_POSE;
+        if (focal_host && !focal_host[n]) fz[n] |= FREEZE_FOCAL;
+        if (pp_host && !pp_host[n]) fz[n] |= FREEZE_PP;
+        if (depth_host && !depth_host[n]) fz[n] |= FREEZE_DEPTH;
+    }
+    for (int y = 0; y < N; y++) a->tab[(size_t)y * 8 + 6] = fz[a->tab[(size_t)y * 8]];
+    hipStream_t st = as_stream(stream);
+    A3R_HIP(hipMemcpyAsync(const_cast<int*>(a->d.freeze), fz.data(), (size_t)N * 4, hipMemcpyHostToDevice, st));
+    A3R_HIP(hipMemcpyAsync(const_cast<int*>(a->d.order), a->tab.data(), a->tab.size() * 4, hipMemcpyHostToDevice, st));
+    A3R_HIP(hipStreamSynchronize(st));                   // fz goes out of scope
+    a->has_focal_mask = focal_host != nullptr;
+    return A3R_OK;
 }
 
 extern "C" int a3r_align_destroy(a3r_align_t a) {
@@ -1605,6 +1644,7 @@ extern "C" int a3r_align_set_flow(a3r_align_t a, const a3r_align_flow_desc* f, v
     A3R_CHECK_ARG(a && f, "a3r_align_set_flow: null argument");
     A3R_CHECK_ARG(!a->shard, "a3r_align_set_flow: an edge-shard handle has no flow variant (the ego-flow terms are not sharded)");
     A3R_CHECK_ARG(!a->use_mono, "a3r_align_set_flow: the flow variant has no mono-depth parameterisation (cloud_opt_flow/optimizer.py:52)");
+    A3R_CHECK_ARG(!(f->shared_focal && a->has_focal_mask), "a3r_align_set_flow: shared_focal next to a per-image focal mask (a3r_align_set_train_masks)");
     AlignDev& d = a->d;
     size_t off[6];
     const size_t need = flow_ws_layout(d.E, d.N, d.P, off);
@@ -1798,7 +1838,7 @@ extern "C" int a3r_align_pose_matrices(a3r_align_t a, float* edge_M, float* img_
 
 // ---- edge shards -----------------------------------------------------------------------------------------------
 extern "C" size_t a3r_align_shard_workspace_bytes(int E, int E_shard, int N, int P) {
-    size_t off[17];
+    size_t off[18];
     return ws_layout(E, E_shard, N, P, off);
 }
 

@@ -18,5 +18,6 @@ def global_aligner(dust3r_output, if_use_mono, mono_depths, device, mode=GlobalA
         from .pair_viewer import PairViewer
         return PairViewer(view1, view2, pred1, pred2, if_use_mono, mono_depths, **optim_kw).to(device)
     if mode == GlobalAlignerMode.ModularPointCloudOptimizer:
-        raise NotImplementedError(f'{mode}: only the stacked PointCloudOptimizer fast path is on the hot path (SURVEY.md 8a-12)')
+        from .modular_optimizer import ModularPointCloudOptimizer
+        return ModularPointCloudOptimizer(view1, view2, pred1, pred2, if_use_mono, mono_depths, **optim_kw).to(device)
     raise NotImplementedError(f'Unknown mode {mode}')

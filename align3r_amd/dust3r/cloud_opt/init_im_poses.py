@@ -517,23 +517,38 @@ def _mst_device(scene, niter_PnP=10):
         print(' init loss =', float(scene()))
 
 
+def _frozen_masks(scene):
+    """Per image: is the pose / the focal preset?  (get_known_poses / get_known_focal_mask of the reference.)  The stacked class
+    presets all images at once (its train_* flags); ModularPointCloudOptimizer keeps per-image masks in scene._frozen."""
+    eng, N = scene._need_engine(), scene.n_imgs
+    fz = getattr(scene, '_frozen', None)
+    pose = np.ones(N, bool) if not eng.flags['train_poses'] else (fz['pose'].copy() if fz else np.zeros(N, bool))
+    focal = np.ones(N, bool) if not eng.flags['train_focals'] else (fz['focal'].copy() if fz else np.zeros(N, bool))
+    return pose, focal
+
+
 def init_minimum_spanning_tree(scene, init_priors=None, niter_PnP=10):
     """init_minimum_spanning_tree + init_from_pts3d (:69-126) on a mirror PointCloudOptimizer that is already on a device."""
     eng = scene._need_engine()
     dev = eng.device
-    if getattr(scene, '_fast', False) and init_priors is None and eng.flags['train_poses'] and scene.n_imgs > 1:
+    known_pose, known_focal = _frozen_masks(scene)
+    fz = getattr(scene, '_frozen', None)
+    per_image = fz is not None and (fz['pose'].any() or fz['focal'].any())       # the device path knows handle-wide switches only
+    if getattr(scene, '_fast', False) and init_priors is None and eng.flags['train_poses'] and scene.n_imgs > 1 and not per_image:
         return _mst_device(scene, niter_PnP)
     E, N, P = len(scene.edges), scene.n_imgs, scene.max_area
     pred_i, pred_j, conf_i, conf_j = edge_views(scene, dev)
     pts3d, _, im_focals, im_poses = minimum_spanning_tree(scene.imshapes, scene.edges, pred_i, pred_j, conf_i, conf_j, scene.im_conf,
                                                           scene.min_conf_thr, dev, init_priors=init_priors, verbose=scene.verbose)
     # ---- init_from_pts3d (:83-126); the known-poses branch (nkp > 1) re-aligns everything on the preset poses
-    if not eng.flags['train_poses']:
-        # every pose is preset (preset_pose takes all images at once here): one global similarity carries the tree's cameras
-        # and pointmaps onto the known poses (:88-99); the preset poses themselves are left alone below, as _set_pose does
-        if N == 1:
-            raise NotImplementedError('Would be simpler to just align everything afterwards on the single known pose')
-        s, R, T = align_multiple_poses(im_poses, scene.get_im_poses())
+    nkp = int(known_pose.sum())
+    if nkp == 1:
+        raise NotImplementedError('Would be simpler to just align everything afterwards on the single known pose')
+    if nkp > 1:
+        # one global similarity carries the tree's cameras and pointmaps onto the known poses (:88-99); the preset poses themselves
+        # are left alone below, as _set_pose without force does
+        kp = torch.from_numpy(known_pose).to(im_poses.device)
+        s, R, T = align_multiple_poses(im_poses[kp], scene.get_im_poses().to(im_poses.device)[kp])
         trf = sRT_to_4x4(s, R, T, dev)
         im_poses = trf @ im_poses
         im_poses[:, :3, :3] /= s
@@ -560,11 +575,12 @@ def init_minimum_spanning_tree(scene, init_priors=None, niter_PnP=10):
         for i in range(N):
             d = geotrf(w2c[i], pts3d[i].reshape(-1, 3))[:, 2]
             depth[i] = pad(d).log().nan_to_num(neginf=0)          # _set_depthmap: _ravel_hw zero-fill, log(0) -> 0
-    if eng.flags['train_poses']:
-        poses[:, 0:4] = rotmat_to_unitquat_batched(im_poses[:, :3, :3])
-        poses[:, 4:7] = signed_log1p(im_poses[:, :3, 3])
+    free = torch.from_numpy(~known_pose).to(poses.device)
+    if free.any():
+        poses[free, 0:4] = rotmat_to_unitquat_batched(im_poses[:, :3, :3])[free].to(poses.dtype)
+        poses[free, 4:7] = signed_log1p(im_poses[:, :3, 3])[free].to(poses.dtype)
     for i in range(N):
-        if im_focals[i] is not None and eng.flags['train_focals'] and not getattr(eng, 'shared_focal', False):
+        if im_focals[i] is not None and not known_focal[i] and not getattr(eng, 'shared_focal', False):
             focals[i] = scene.focal_break * float(np.log(im_focals[i]))
     if getattr(eng, 'shared_focal', False) and eng.flags['train_focals'] and im_focals[0] is not None:
         focals[0] = scene.focal_break * float(np.log(im_focals[0]))

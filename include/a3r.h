@@ -539,6 +539,15 @@ typedef struct a3r_align_s* a3r_align_t;
 size_t a3r_align_workspace_bytes(int E, int N, int P);
 int a3r_align_create(const a3r_align_desc* desc, a3r_align_t* out, void* stream);
 int a3r_align_destroy(a3r_align_t a);
+/* Per-image train masks (ModularPointCloudOptimizer: preset_pose / preset_focal / preset_principal_point on a SUBSET of the images,
+ * dust3r/cloud_opt/modular_optimizer.py:73-110).  Each argument is a HOST array of N bytes (non-zero = this image's group is trained,
+ * zero = frozen) or NULL (no per-image freeze: the handle-wide train_* switch alone decides, as on a handle that never calls this).
+ * A group is updated only where both the switch and the mask allow it.  A frozen entry gets no Adam step and its moments are not
+ * touched; a frozen depth map (no counterpart in the reference) is neither read for its moments nor written.  a3r_align_grad*
+ * return exact zeros in the rows of frozen groups.  Every call replaces all four masks.  A focal mask is refused with shared_focal,
+ * every mask on an edge-shard handle.  Synchronises the stream. */
+int a3r_align_set_train_masks(a3r_align_t a, const uint8_t* pose_host, const uint8_t* focal_host, const uint8_t* pp_host,
+                              const uint8_t* depth_host, void* stream);
 /* One global_alignment_iter (base_opt.py:450-464): loss + gradients + Adam(betas .9,.9, eps 1e-8) with
  * learning rate lr.  Fully asynchronous; the loss lands in loss_history[step]. */
 int a3r_align_step(a3r_align_t a, float lr, void* stream);
