@@ -49,27 +49,29 @@ def schedule_lr(schedule, t, lr, lr_min):
     raise ValueError(f"bad lr schedule={schedule!r}")
 
 
-class AlignEngine:
-    def __init__(self, ei, ej, pred_i, pred_j, w_i, w_j, imshapes, mono=None, base_scale=0.5, pw_break=20.0,
-                 focal_break=20.0, norm_pw_scale=True, dist="l1", train_poses=True, train_focals=True, train_pp=False,
-                 train_adaptors=False, device="cuda:0", loss_capacity=4096, shared_focal=False, temporal_smoothing_weight=0.0,
-                 translation_weight=0.1, flow=None):
-        """flow (cloud_opt_flow variant): dict(flow_ij [E,2,P], flow_ji [E,2,P], dyn [N,P] bool, weight, thre, start_epoch,
-        num_total_iter, pxl_thre) -- the optical-flow fields and dynamic masks are inputs (optimizer.py:104-116)."""
+_PARAM_KEYS = ("pw_poses", "pw_adaptors", "depth", "shifts", "im_poses", "im_focals", "im_pp")
+
+
+class _AlignEngineBase:
+    """What the fused and the edge-sharded engine share: the graph, the uploaded observations, the flags and the bookkeeping of
+    their handle states.  A state is anything with handle / params / adam / workspace / loss_history: the fused engine is its own
+    single state, the sharded one has a _ShardReplica per shard (`_states`)."""
+
+    def __init__(self, ei, ej, pred_i, pred_j, w_i, w_j, imshapes, mono, base_scale, pw_break, focal_break, norm_pw_scale, dist,
+                 train_poses, train_focals, train_pp, train_adaptors, device, loss_capacity, shared_focal=False):
         self.lib = _lib.load()
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise RuntimeError("AlignEngine needs a HIP device (there is no CPU fallback)")
-        dev = self.device
-        f32 = lambda a: torch.as_tensor(a, dtype=torch.float32).to(dev).contiguous()
+            raise RuntimeError(f"{type(self).__name__} needs a HIP device (there is no CPU fallback)")
+        f32 = self._f32
         self.ei = np.ascontiguousarray(ei, dtype=np.int32)
         self.ej = np.ascontiguousarray(ej, dtype=np.int32)
-        E = len(self.ei)
-        N = len(imshapes)
-        self.w_i, self.w_j = f32(w_i).reshape(E, -1), f32(w_j).reshape(E, -1)
+        E, N = len(self.ei), len(imshapes)
+        rows, pred_i, pred_j, w_i, w_j = self._select_rows(E, pred_i, pred_j, w_i, w_j)
+        self.w_i, self.w_j = f32(w_i).reshape(rows, -1), f32(w_j).reshape(rows, -1)
         P = self.w_i.shape[1]
         self.E, self.N, self.P = E, N, P
-        self.pred_i, self.pred_j = f32(pred_i).reshape(E, P, 3), f32(pred_j).reshape(E, P, 3)
+        self.pred_i, self.pred_j = f32(pred_i).reshape(rows, P, 3), f32(pred_j).reshape(rows, P, 3)
         self.imshapes = [tuple(int(v) for v in s) for s in imshapes]
         self.imw = np.asarray([w for h, w in self.imshapes], dtype=np.int32)
         self.imarea = np.asarray([h * w for h, w in self.imshapes], dtype=np.int32)
@@ -79,58 +81,161 @@ class AlignEngine:
         self.flags = dict(norm_pw_scale=bool(norm_pw_scale), dist_l2=(dist == "l2"), train_poses=bool(train_poses),
                           train_focals=bool(train_focals), train_pp=bool(train_pp), train_adaptors=bool(train_adaptors))
         self.base_scale, self.pw_break, self.focal_break = base_scale, pw_break, focal_break
-        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
         self.shared_focal = bool(shared_focal)
-        self.tsw, self.trans_w = float(temporal_smoothing_weight), float(translation_weight)
         self.flow = None
-        if flow is not None and flow.get("weight", 0) > 0:
-            if self.use_mono or len(set(self.imshapes)) != 1:
-                raise RuntimeError("the flow variant needs images of one shape and no mono-depth parameterisation")
-            self.flow = dict(flow)
-            self.flow["flow_ij"] = f32(flow["flow_ij"]).reshape(E, 2, P)
-            self.flow["flow_ji"] = f32(flow["flow_ji"]).reshape(E, 2, P)
-            self.flow["dyn"] = torch.as_tensor(np.ascontiguousarray(flow["dyn"])).reshape(N, P).to(dev, torch.uint8).contiguous()
-        self.flow_variant = self.shared_focal or self.tsw > 0 or self.flow is not None
-        self.prior = None             # set_depth_prior(): dict(weight, init [N,P], dyn [N,P] uint8 | None, workspace)
-        self.params = dict(pw_poses=z(E, 8), pw_adaptors=z(E, 2), depth=z(N, P), shifts=z(N), im_poses=z(N, 7),
-                           im_focals=z(1 if self.shared_focal else N), im_pp=z(N, 2))
-        self.flow_workspace = (torch.empty(int(self.lib.a3r_align_flow_workspace_bytes(E, N, P)), dtype=torch.uint8, device=dev)
-                               if self.flow_variant else None)
-        self.adam = dict(pw_poses=z(2, E, 8), depth=z(2, N, P), small=z(2, N, 16), pw_adaptors=z(2, E, 2))
+        self.prior = None             # AlignEngine.set_depth_prior(): dict(weight, init [N,P], dyn [N,P] uint8 | None, workspace)
         self.loss_capacity = loss_capacity
-        self.loss_history = z(loss_capacity)
-        self.total_area_i = float(sum(int(self.imarea[i]) for i in self.ei))
+        self.total_area_i = float(sum(int(self.imarea[i]) for i in self.ei))       # the WHOLE graph's (optimizer.py:70-71)
         self.total_area_j = float(sum(int(self.imarea[j]) for j in self.ej))
-        self.workspace = torch.empty(int(self.lib.a3r_align_workspace_bytes(E, N, P)), dtype=torch.uint8, device=dev)
-        self.handle = None
-        self._create()
 
-    def _create(self):
-        if self.handle:
-            h_old, self.handle = self.handle, None          # never leave a destroyed handle behind if the re-creation below fails
-            self.lib.a3r_align_destroy(h_old)
+    def _select_rows(self, E, pred_i, pred_j, w_i, w_j):
+        """(number of observation rows to hold, the observations to upload): one row per edge of the graph here."""
+        return E, pred_i, pred_j, w_i, w_j
+
+    def _f32(self, a):
+        return torch.as_tensor(a, dtype=torch.float32).to(self.device).contiguous()
+
+    def _alloc_state(self, st, workspace_bytes):
+        """Zeroed parameters, Adam moments and loss history plus the workspace of one handle, as attributes of `st`."""
+        E, N, P = self.E, self.N, self.P
+        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=self.device)
+        st.params = dict(pw_poses=z(E, 8), pw_adaptors=z(E, 2), depth=z(N, P), shifts=z(N), im_poses=z(N, 7),
+                         im_focals=z(1 if self.shared_focal else N), im_pp=z(N, 2))
+        st.adam = dict(pw_poses=z(2, E, 8), depth=z(2, N, P), small=z(2, N, 16), pw_adaptors=z(2, E, 2))
+        st.loss_history = z(self.loss_capacity)
+        st.workspace = torch.empty(int(workspace_bytes), dtype=torch.uint8, device=self.device)
+        st.handle = None
+
+    def _fill_desc(self, params, adam, workspace, loss_history, row_slice):
+        """The a3r_align_desc of one handle; row_slice selects its rows of the observation tensors held here (views)."""
         d = AlignDesc()
         d.E, d.N, d.P = self.E, self.N, self.P
         d.use_mono = int(self.use_mono)
-        d.norm_pw_scale = int(self.flags["norm_pw_scale"]); d.dist_l2 = int(self.flags["dist_l2"])
-        d.train_poses = int(self.flags["train_poses"]); d.train_focals = int(self.flags["train_focals"])
-        d.train_pp = int(self.flags["train_pp"])
-        d.train_adaptors = int(self.flags.get("train_adaptors", False))
-        d.adam_pw_adaptors = self.adam["pw_adaptors"].data_ptr()
+        for k in ("norm_pw_scale", "dist_l2", "train_poses", "train_focals", "train_pp", "train_adaptors"):
+            setattr(d, k, int(self.flags[k]))
         d.base_scale, d.pw_break, d.focal_break = self.base_scale, self.pw_break, self.focal_break
         d.total_area_i, d.total_area_j = self.total_area_i, self.total_area_j
         d.ei_host, d.ej_host = self.ei.ctypes.data, self.ej.ctypes.data
         d.imw_host, d.imarea_host = self.imw.ctypes.data, self.imarea.ctypes.data
-        d.pred_i, d.pred_j = self.pred_i.data_ptr(), self.pred_j.data_ptr()
-        d.w_i, d.w_j = self.w_i.data_ptr(), self.w_j.data_ptr()
+        d.pred_i, d.pred_j = self.pred_i[row_slice].data_ptr(), self.pred_j[row_slice].data_ptr()
+        d.w_i, d.w_j = self.w_i[row_slice].data_ptr(), self.w_j[row_slice].data_ptr()
         d.mono = self.mono.data_ptr() if self.use_mono else None
         d.pp0 = self.pp0.data_ptr()
-        p = self.params
-        d.pw_poses, d.pw_adaptors, d.depth, d.shifts = (p[k].data_ptr() for k in ("pw_poses", "pw_adaptors", "depth", "shifts"))
-        d.im_poses, d.im_focals, d.im_pp = (p[k].data_ptr() for k in ("im_poses", "im_focals", "im_pp"))
-        d.adam_pw_poses, d.adam_depth, d.adam_small = (self.adam[k].data_ptr() for k in ("pw_poses", "depth", "small"))
-        d.workspace, d.workspace_bytes = self.workspace.data_ptr(), self.workspace.numel()
-        d.loss_history, d.loss_capacity = self.loss_history.data_ptr(), self.loss_capacity
+        for k in _PARAM_KEYS:
+            setattr(d, k, params[k].data_ptr())
+        d.adam_pw_poses, d.adam_depth, d.adam_small, d.adam_pw_adaptors = (adam[k].data_ptr() for k in ("pw_poses", "depth", "small", "pw_adaptors"))
+        d.workspace, d.workspace_bytes = workspace.data_ptr(), workspace.numel()
+        d.loss_history, d.loss_capacity = loss_history.data_ptr(), self.loss_capacity
+        return d
+
+    def _destroy(self, st):
+        if st.handle:
+            h_old, st.handle = st.handle, None              # never leave a destroyed handle behind if a re-creation fails
+            self.lib.a3r_align_destroy(h_old)
+
+    def __del__(self):
+        try:
+            for st in self._states:
+                self._destroy(st)
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------------ state
+    def set_params(self, pw_poses=None, depth=None, im_poses=None, im_focals=None, shifts=None, im_pp=None,
+                   pw_adaptors=None, reset_optimizer=True):
+        for k, v in dict(pw_poses=pw_poses, depth=depth, im_poses=im_poses, im_focals=im_focals, shifts=shifts, im_pp=im_pp,
+                         pw_adaptors=pw_adaptors).items():
+            if v is not None:
+                t = torch.as_tensor(v, dtype=torch.float32).to(self.device)
+                if k == "im_focals" and self.shared_focal:
+                    t = t.reshape(-1)[:1]          # one focal shared by all images (optimizer.py:56-58)
+                for st in self._states:
+                    st.params[k].copy_(t.reshape(st.params[k].shape))
+        if reset_optimizer:
+            for st in self._states:
+                for t in st.adam.values():
+                    t.zero_()
+            self._create()     # step counter restarts with fresh Adam moments
+        else:
+            for st in self._states:
+                check(self.lib.a3r_align_invalidate(st.handle))
+
+    def set_trainable(self, **flags):
+        """preset_pose / preset_focal / preset_principal_point semantics (optimizer.py:76-113)."""
+        self.flags.update(flags)
+        self._create()
+
+    def trainable(self):
+        t = ["pw_poses", "depth"]
+        if self.flags["train_adaptors"]:
+            t.append("pw_adaptors")
+        if self.use_mono:
+            t.append("shifts")
+        if self.flags["train_poses"]:
+            t.append("im_poses")
+        if self.flags["train_focals"]:
+            t.append("im_focals")
+        if self.flags["train_pp"]:
+            t.append("im_pp")
+        return t
+
+    @property
+    def steps_done(self):
+        return int(self.lib.a3r_align_steps_done(self._states[0].handle))
+
+    def _lrs(self, niter, lr, schedule, lr_min, first_iter, total_iters):
+        """The learning rates of run(): the schedule is evaluated here (float64, as the reference does), the iterations are
+        enqueued by one native loop."""
+        total = total_iters or niter
+        return np.asarray([schedule_lr(schedule, it / total, lr, lr_min) for it in range(first_iter, first_iter + niter)], dtype=np.float32)
+
+    def _grad_dict(self, g_pw, g_ad, g_depth, g_small):
+        """Gradients of the trained parameters by name, from the [N,16] rows of the per-image parameters."""
+        g_f = g_small[:, 7].sum().reshape(1) if self.shared_focal else g_small[:, 7]
+        g = dict(pw_poses=g_pw, pw_adaptors=g_ad, depth=g_depth, im_poses=g_small[:, 0:7], im_focals=g_f, im_pp=g_small[:, 8:10],
+                 shifts=g_small[:, 10])
+        return {k: g[k] for k in self.trainable()}
+
+    def pose_matrices(self):
+        eM = torch.empty(self.E, 3, 4, device=self.device)
+        iR = torch.empty(self.N, 3, 4, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.lib.a3r_align_pose_matrices(self._states[0].handle, ptr(eM), ptr(iR), stream_ptr()), "a3r_align_pose_matrices")
+        return eM, iR
+
+
+class AlignEngine(_AlignEngineBase):
+    def __init__(self, ei, ej, pred_i, pred_j, w_i, w_j, imshapes, mono=None, base_scale=0.5, pw_break=20.0,
+                 focal_break=20.0, norm_pw_scale=True, dist="l1", train_poses=True, train_focals=True, train_pp=False,
+                 train_adaptors=False, device="cuda:0", loss_capacity=4096, shared_focal=False, temporal_smoothing_weight=0.0,
+                 translation_weight=0.1, flow=None):
+        """flow (cloud_opt_flow variant): dict(flow_ij [E,2,P], flow_ji [E,2,P], dyn [N,P] bool, weight, thre, start_epoch,
+        num_total_iter, pxl_thre) -- the optical-flow fields and dynamic masks are inputs (optimizer.py:104-116)."""
+        super().__init__(ei, ej, pred_i, pred_j, w_i, w_j, imshapes, mono, base_scale, pw_break, focal_break, norm_pw_scale, dist,
+                         train_poses, train_focals, train_pp, train_adaptors, device, loss_capacity, shared_focal=shared_focal)
+        E, N, P, dev = self.E, self.N, self.P, self.device
+        self.tsw, self.trans_w = float(temporal_smoothing_weight), float(translation_weight)
+        if flow is not None and flow.get("weight", 0) > 0:
+            if self.use_mono or len(set(self.imshapes)) != 1:
+                raise RuntimeError("the flow variant needs images of one shape and no mono-depth parameterisation")
+            self.flow = dict(flow)
+            self.flow["flow_ij"] = self._f32(flow["flow_ij"]).reshape(E, 2, P)
+            self.flow["flow_ji"] = self._f32(flow["flow_ji"]).reshape(E, 2, P)
+            self.flow["dyn"] = torch.as_tensor(np.ascontiguousarray(flow["dyn"])).reshape(N, P).to(dev, torch.uint8).contiguous()
+        self.flow_variant = self.shared_focal or self.tsw > 0 or self.flow is not None
+        self.train_masks = None       # set_train_masks(): dict(pose, focal, pp, depth) of [N] uint8 | None
+        self.flow_workspace = (torch.empty(int(self.lib.a3r_align_flow_workspace_bytes(E, N, P)), dtype=torch.uint8, device=dev)
+                               if self.flow_variant else None)
+        self._alloc_state(self, self.lib.a3r_align_workspace_bytes(E, N, P))
+        self._create()
+
+    @property
+    def _states(self):
+        return (self,)
+
+    def _create(self):
+        self._destroy(self)
+        d = self._fill_desc(self.params, self.adam, self.workspace, self.loss_history, slice(None))
         h = C.c_void_p()
         with torch.cuda.device(self.device):
             check(self.lib.a3r_align_create(C.byref(d), C.byref(h), stream_ptr()), "a3r_align_create")
@@ -158,7 +263,7 @@ class AlignEngine:
         self._push_train_masks()
 
     def _push_train_masks(self, force=False):
-        m = getattr(self, "train_masks", None)
+        m = self.train_masks
         if m is None or (not force and all(v is None for v in m.values())):
             return
         arg = lambda v: None if v is None else v.ctypes.data_as(C.c_void_p)
@@ -182,31 +287,6 @@ class AlignEngine:
         self.train_masks = m
         self._push_train_masks(force=True)
 
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                self.lib.a3r_align_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
-
-    # ------------------------------------------------------------------ state
-    def set_params(self, pw_poses=None, depth=None, im_poses=None, im_focals=None, shifts=None, im_pp=None,
-                   pw_adaptors=None, reset_optimizer=True):
-        for k, v in dict(pw_poses=pw_poses, depth=depth, im_poses=im_poses, im_focals=im_focals, shifts=shifts, im_pp=im_pp,
-                         pw_adaptors=pw_adaptors).items():
-            if v is not None:
-                t = torch.as_tensor(v, dtype=torch.float32).to(self.device)
-                if k == "im_focals" and self.shared_focal:
-                    t = t.reshape(-1)[:1]          # one focal shared by all images (optimizer.py:56-58)
-                self.params[k].copy_(t.reshape(self.params[k].shape))
-        if reset_optimizer:
-            for t in self.adam.values():
-                t.zero_()
-            self._create()     # step counter restarts with fresh Adam moments
-        else:
-            check(self.lib.a3r_align_invalidate(self.handle))
-
     def set_depth_prior(self, weight, dyn=None, init=None):
         """depth_regularize_weight of the flow variant (optimizer.py:546-555).  `init`: [N,P] log-depth parameters to regularise
         towards (default: a copy of the current ones, which is what _set_init_depthmap captures); `dyn`: [N,P] dynamic masks."""
@@ -227,29 +307,6 @@ class AlignEngine:
                                                      pr["workspace"].data_ptr() if pr else None, pr["workspace"].numel() if pr else 0,
                                                      stream_ptr()), "a3r_align_set_depth_prior")
 
-    def set_trainable(self, **flags):
-        """preset_pose / preset_focal / preset_principal_point semantics (optimizer.py:76-113)."""
-        self.flags.update(flags)
-        self._create()
-
-    def trainable(self):
-        t = ["pw_poses", "depth"]
-        if self.flags.get("train_adaptors"):
-            t.append("pw_adaptors")
-        if self.use_mono:
-            t.append("shifts")
-        if self.flags["train_poses"]:
-            t.append("im_poses")
-        if self.flags["train_focals"]:
-            t.append("im_focals")
-        if self.flags["train_pp"]:
-            t.append("im_pp")
-        return t
-
-    @property
-    def steps_done(self):
-        return int(self.lib.a3r_align_steps_done(self.handle))
-
     # ------------------------------------------------------------------ compute
     def loss(self):
         out = torch.zeros(1, device=self.device)
@@ -266,10 +323,7 @@ class AlignEngine:
         with torch.cuda.device(self.device):
             check(self.lib.a3r_align_grad_full(self.handle, int(epoch), ptr(g_pw), ptr(g_ad), ptr(g_depth), ptr(g_small), ptr(loss),
                                                stream_ptr()), "a3r_align_grad")
-        g_f = g_small[:, 7].sum().reshape(1) if self.shared_focal else g_small[:, 7]
-        g = dict(pw_poses=g_pw, pw_adaptors=g_ad, depth=g_depth, im_poses=g_small[:, 0:7], im_focals=g_f, im_pp=g_small[:, 8:10],
-                 shifts=g_small[:, 10])
-        return float(loss.item()), {k: g[k] for k in self.trainable()}
+        return float(loss.item()), self._grad_dict(g_pw, g_ad, g_depth, g_small)
 
     def step(self, lr, epoch=None):
         with torch.cuda.device(self.device):
@@ -289,20 +343,11 @@ class AlignEngine:
 
     def run(self, niter, lr, schedule="cosine", lr_min=1e-6, first_iter=0, total_iters=None):
         """global_alignment_loop (base_opt.py:424-447) without per-iteration host syncs; returns the losses."""
-        total = total_iters or niter
         start = self.steps_done
-        # the schedule is evaluated here (float64, as the reference does), the iterations are enqueued by one native loop
-        lrs = np.asarray([schedule_lr(schedule, it / total, lr, lr_min) for it in range(first_iter, first_iter + niter)], dtype=np.float32)
+        lrs = self._lrs(niter, lr, schedule, lr_min, first_iter, total_iters)
         with torch.cuda.device(self.device):
             check(self.lib.a3r_align_run(self.handle, lrs.ctypes.data_as(C.c_void_p), int(niter), int(first_iter), stream_ptr()), "a3r_align_run")
         return self.loss_history[start:start + niter].cpu().numpy().astype(np.float64)
-
-    def pose_matrices(self):
-        eM = torch.empty(self.E, 3, 4, device=self.device)
-        iR = torch.empty(self.N, 3, 4, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self.lib.a3r_align_pose_matrices(self.handle, ptr(eM), ptr(iR), stream_ptr()), "a3r_align_pose_matrices")
-        return eM, iR
 
 
 class _ShardReplica:
@@ -313,7 +358,7 @@ class _ShardReplica:
         self.handle = None
 
 
-class ShardedAlignEngine:
+class ShardedAlignEngine(_AlignEngineBase):
     """Edge-sharded AlignEngine: every shard walks its own rows of the stacked observations, the additive partial results (one flat
     fp32 buffer: depth-parameter gradient map, per-image sums, per-edge sums) are summed, and every shard applies the same update
     to its replica of the parameters -- ONE reduction per iteration.  Two reducers:
@@ -330,7 +375,6 @@ class ShardedAlignEngine:
     def __init__(self, ei, ej, pred_i, pred_j, w_i, w_j, imshapes, mono=None, base_scale=0.5, pw_break=20.0, focal_break=20.0,
                  norm_pw_scale=True, dist="l1", train_poses=True, train_focals=True, train_pp=False, train_adaptors=False,
                  device="cuda:0", loss_capacity=4096, local_shards=None, group=None, **unsupported):
-        from .parallel import shard_rows
         if unsupported.get("flow") is not None or unsupported.get("shared_focal") or unsupported.get("temporal_smoothing_weight", 0) > 0:
             raise NotImplementedError("ShardedAlignEngine: the flow variant (shared focal, temporal smoothing, ego-flow) is not edge-sharded")
         bad = set(unsupported) - {"flow", "shared_focal", "temporal_smoothing_weight", "translation_weight"}
@@ -338,28 +382,39 @@ class ShardedAlignEngine:
             raise TypeError(f"ShardedAlignEngine: unexpected arguments {sorted(bad)}")
         if (local_shards is None) == (group is None):
             raise ValueError("ShardedAlignEngine: pass exactly one of local_shards=K and group=<process group>")
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("ShardedAlignEngine needs a HIP device (there is no CPU fallback)")
-        dev = self.device
-        f32 = lambda a: torch.as_tensor(a, dtype=torch.float32).to(dev).contiguous()
-        self.ei = np.ascontiguousarray(ei, dtype=np.int32)
-        self.ej = np.ascontiguousarray(ej, dtype=np.int32)
-        E, N = len(self.ei), len(imshapes)
-        self.group = group
+        self.group, self._local_shards = group, local_shards
         self._all_reduce = None
         if group is not None:
-            import torch.distributed as tdist
             from .parallel import GradientAllReduce
             self._all_reduce = GradientAllReduce(group)
+        super().__init__(ei, ej, pred_i, pred_j, w_i, w_j, imshapes, mono, base_scale, pw_break, focal_break, norm_pw_scale, dist,
+                         train_poses, train_focals, train_pp, train_adaptors, device, loss_capacity)
+        E, N, P = self.E, self.N, self.P
+        self.n_floats = int(self.lib.a3r_align_shard_reduce_floats(E, N, P))
+        self.replicas = []
+        for e0, e1 in self.bounds:
+            r = _ShardReplica(e0, e1)
+            self._alloc_state(r, self.lib.a3r_align_shard_workspace_bytes(E, e1 - e0, N, P))
+            r.buf = torch.zeros(self.n_floats, dtype=torch.float32, device=self.device)
+            self.replicas.append(r)
+        self.params = self.replicas[0].params           # the replicas hold identical values; this one is the public view
+        self.loss_history = self.replicas[0].loss_history
+        self._create()
+
+    def _select_rows(self, E, pred_i, pred_j, w_i, w_j):
+        """The shard bounds, and which rows of the observations are held here: the whole graph's [E, ...] or, with group, this
+        rank's."""
+        from .parallel import shard_rows
+        group = self.group
+        if group is not None:
+            import torch.distributed as tdist
             world, rank = tdist.get_world_size(group), tdist.get_rank(group)
             e0, e1, _ = shard_rows(E, rank, world)
             if e0 >= e1:
                 raise ValueError(f"ShardedAlignEngine: rank {rank} of {world} gets no edge of a graph with {E} edges; use fewer ranks")
             bounds = [(e0, e1)]
         else:
-            K = int(local_shards)
+            K = int(self._local_shards)
             if K < 1:
                 raise ValueError("ShardedAlignEngine: local_shards must be >= 1")
             bounds = [b[:2] for b in (shard_rows(E, r, K) for r in range(K)) if b[0] < b[1]]
@@ -375,111 +430,25 @@ class ShardedAlignEngine:
         else:
             raise ValueError(f"ShardedAlignEngine: {rows} observation rows for a graph with {E} edges (shards {bounds})")
         self._row0 = lo                          # graph edge of row 0 of the observation tensors held here
-        self.w_i, self.w_j = f32(w_i).reshape(len(w_i), -1), f32(w_j).reshape(len(w_j), -1)
-        P = self.w_i.shape[1]
-        self.E, self.N, self.P = E, N, P
-        self.pred_i, self.pred_j = f32(pred_i).reshape(-1, P, 3), f32(pred_j).reshape(-1, P, 3)
-        self.imshapes = [tuple(int(v) for v in s) for s in imshapes]
-        self.imw = np.asarray([w for h, w in self.imshapes], dtype=np.int32)
-        self.imarea = np.asarray([h * w for h, w in self.imshapes], dtype=np.int32)
-        self.pp0 = f32([(w / 2, h / 2) for h, w in self.imshapes])
-        self.use_mono = mono is not None
-        self.mono = f32(mono).reshape(N, P) if self.use_mono else None
-        self.flags = dict(norm_pw_scale=bool(norm_pw_scale), dist_l2=(dist == "l2"), train_poses=bool(train_poses),
-                          train_focals=bool(train_focals), train_pp=bool(train_pp), train_adaptors=bool(train_adaptors))
-        self.base_scale, self.pw_break, self.focal_break = base_scale, pw_break, focal_break
-        self.shared_focal, self.flow, self.prior = False, None, None
-        self.loss_capacity = loss_capacity
-        self.total_area_i = float(sum(int(self.imarea[i]) for i in self.ei))       # the WHOLE graph's (optimizer.py:70-71)
-        self.total_area_j = float(sum(int(self.imarea[j]) for j in self.ej))
-        self.n_floats = int(self.lib.a3r_align_shard_reduce_floats(E, N, P))
-        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
-        self.replicas = []
-        for e0, e1 in bounds:
-            r = _ShardReplica(e0, e1)
-            r.params = dict(pw_poses=z(E, 8), pw_adaptors=z(E, 2), depth=z(N, P), shifts=z(N), im_poses=z(N, 7), im_focals=z(N), im_pp=z(N, 2))
-            r.adam = dict(pw_poses=z(2, E, 8), depth=z(2, N, P), small=z(2, N, 16), pw_adaptors=z(2, E, 2))
-            r.loss_history = z(loss_capacity)
-            r.workspace = torch.empty(int(self.lib.a3r_align_shard_workspace_bytes(E, e1 - e0, N, P)), dtype=torch.uint8, device=dev)
-            r.buf = z(self.n_floats)
-            self.replicas.append(r)
-        self.params = self.replicas[0].params           # the replicas hold identical values; this one is the public view
-        self.loss_history = self.replicas[0].loss_history
-        self._create()
+        return len(w_i), pred_i, pred_j, w_i, w_j
+
+    @property
+    def _states(self):
+        return self.replicas
 
     def _create(self):
         for r in self.replicas:
-            if r.handle:
-                h_old, r.handle = r.handle, None
-                self.lib.a3r_align_destroy(h_old)
-            d = AlignDesc()
-            d.E, d.N, d.P = self.E, self.N, self.P
-            d.use_mono = int(self.use_mono)
-            d.norm_pw_scale = int(self.flags["norm_pw_scale"]); d.dist_l2 = int(self.flags["dist_l2"])
-            d.train_poses = int(self.flags["train_poses"]); d.train_focals = int(self.flags["train_focals"])
-            d.train_pp = int(self.flags["train_pp"])
-            d.train_adaptors = int(self.flags.get("train_adaptors", False))
-            d.adam_pw_adaptors = r.adam["pw_adaptors"].data_ptr()
-            d.base_scale, d.pw_break, d.focal_break = self.base_scale, self.pw_break, self.focal_break
-            d.total_area_i, d.total_area_j = self.total_area_i, self.total_area_j
-            d.ei_host, d.ej_host = self.ei.ctypes.data, self.ej.ctypes.data
-            d.imw_host, d.imarea_host = self.imw.ctypes.data, self.imarea.ctypes.data
-            a, b = r.e0 - self._row0, r.e1 - self._row0            # the shard's rows of the tensors held here (views)
-            d.pred_i, d.pred_j = self.pred_i[a:b].data_ptr(), self.pred_j[a:b].data_ptr()
-            d.w_i, d.w_j = self.w_i[a:b].data_ptr(), self.w_j[a:b].data_ptr()
-            d.mono = self.mono.data_ptr() if self.use_mono else None
-            d.pp0 = self.pp0.data_ptr()
-            p = r.params
-            d.pw_poses, d.pw_adaptors, d.depth, d.shifts = (p[k].data_ptr() for k in ("pw_poses", "pw_adaptors", "depth", "shifts"))
-            d.im_poses, d.im_focals, d.im_pp = (p[k].data_ptr() for k in ("im_poses", "im_focals", "im_pp"))
-            d.adam_pw_poses, d.adam_depth, d.adam_small = (r.adam[k].data_ptr() for k in ("pw_poses", "depth", "small"))
-            d.workspace, d.workspace_bytes = r.workspace.data_ptr(), r.workspace.numel()
-            d.loss_history, d.loss_capacity = r.loss_history.data_ptr(), self.loss_capacity
+            self._destroy(r)
+            # the shard's rows of the tensors held here
+            d = self._fill_desc(r.params, r.adam, r.workspace, r.loss_history, slice(r.e0 - self._row0, r.e1 - self._row0))
             h = C.c_void_p()
             with torch.cuda.device(self.device):
                 check(self.lib.a3r_align_shard_create(C.byref(d), r.e0, r.e1, C.byref(h), stream_ptr()), "a3r_align_shard_create")
             r.handle = h
 
-    def __del__(self):
-        try:
-            for r in getattr(self, "replicas", []):
-                if r.handle:
-                    self.lib.a3r_align_destroy(r.handle)
-                    r.handle = None
-        except Exception:
-            pass
-
-    # ------------------------------------------------------------------ state
-    def set_params(self, pw_poses=None, depth=None, im_poses=None, im_focals=None, shifts=None, im_pp=None,
-                   pw_adaptors=None, reset_optimizer=True):
-        for k, v in dict(pw_poses=pw_poses, depth=depth, im_poses=im_poses, im_focals=im_focals, shifts=shifts, im_pp=im_pp,
-                         pw_adaptors=pw_adaptors).items():
-            if v is not None:
-                t = torch.as_tensor(v, dtype=torch.float32).to(self.device)
-                for r in self.replicas:
-                    r.params[k].copy_(t.reshape(r.params[k].shape))
-        if reset_optimizer:
-            for r in self.replicas:
-                for t in r.adam.values():
-                    t.zero_()
-            self._create()     # step counter restarts with fresh Adam moments
-        else:
-            for r in self.replicas:
-                check(self.lib.a3r_align_invalidate(r.handle))
-
     def set_depth_prior(self, weight, dyn=None, init=None):
         if weight > 0:
             raise NotImplementedError("ShardedAlignEngine: the depth prior belongs to the flow variant, which is not edge-sharded")
-
-    def set_trainable(self, **flags):
-        self.flags.update(flags)
-        self._create()
-
-    trainable = AlignEngine.trainable
-
-    @property
-    def steps_done(self):
-        return int(self.lib.a3r_align_steps_done(self.replicas[0].handle))
 
     @property
     def flow_dropped(self):
@@ -512,9 +481,7 @@ class ShardedAlignEngine:
             check(self.lib.a3r_align_shard_grad(r0.handle, ptr(red), self.n_floats, ptr(g_pw), ptr(g_ad), ptr(g_small), ptr(loss),
                                                 stream_ptr()), "a3r_align_shard_grad")
         g_depth = red[:self.N * self.P].reshape(self.N, self.P).clone()
-        g = dict(pw_poses=g_pw, pw_adaptors=g_ad, depth=g_depth, im_poses=g_small[:, 0:7], im_focals=g_small[:, 7], im_pp=g_small[:, 8:10],
-                 shifts=g_small[:, 10])
-        return float(loss.item()), {k: g[k] for k in self.trainable()}
+        return float(loss.item()), self._grad_dict(g_pw, g_ad, g_depth, g_small)
 
     def loss(self):
         return torch.tensor([self.loss_grad()[0]], device=self.device)
@@ -534,11 +501,10 @@ class ShardedAlignEngine:
             sharded_step(self._partials, lambda _: self._reduce(), self._apply, lr)
 
     def run(self, niter, lr, schedule="cosine", lr_min=1e-6, first_iter=0, total_iters=None):
-        total = total_iters or niter
         start = self.steps_done
         if start + niter > self.loss_capacity:
             raise RuntimeError(f"loss_history too small ({start} + {niter} > {self.loss_capacity})")
-        lrs = np.asarray([schedule_lr(schedule, it / total, lr, lr_min) for it in range(first_iter, first_iter + niter)], dtype=np.float32)
+        lrs = self._lrs(niter, lr, schedule, lr_min, first_iter, total_iters)
         if self.group is not None:
             for v in lrs:
                 self.step(float(v))
@@ -550,10 +516,3 @@ class ShardedAlignEngine:
                 check(self.lib.a3r_align_shard_run_local(hs, K, bufs, self.n_floats, lrs.ctypes.data_as(C.c_void_p), int(niter), stream_ptr()),
                       "a3r_align_shard_run_local")
         return self.loss_history[start:start + niter].cpu().numpy().astype(np.float64)
-
-    def pose_matrices(self):
-        eM = torch.empty(self.E, 3, 4, device=self.device)
-        iR = torch.empty(self.N, 3, 4, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self.lib.a3r_align_pose_matrices(self.replicas[0].handle, ptr(eM), ptr(iR), stream_ptr()), "a3r_align_pose_matrices")
-        return eM, iR

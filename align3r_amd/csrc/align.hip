@@ -27,13 +27,10 @@ namespace a3r {
 constexpr int PXT = 4;                 // pixels per thread
 constexpr int TPB = 256;
 constexpr int CHUNK = PXT * TPB;       // pixels per workgroup
-// register buffers of raw edge data per thread: 2 (one edge side in flight behind the one being consumed; fits four waves per SIMD)
-// or 3 (two in flight; lab variant, needs A3R_ALIGN_MIN_WAVES=3)
-#ifndef A3R_ALIGN_NBUF
-#define A3R_ALIGN_NBUF 2
-#endif
-constexpr int EB = A3R_ALIGN_NBUF == 3 ? 9 : 8;   // (edge,side) entries per LDS reduction batch (a multiple of the buffers)
-constexpr int MAX_INC = 2048;          // edge sides incident to one image (their codes sit in LDS: 8 KB)
+// The main kernel keeps TWO register buffers of raw edge data per thread (one edge side in flight behind the one being consumed):
+// that fits four waves per SIMD.  Three buffers (two in flight) at three waves per SIMD were measured and lost.
+constexpr int EB = 8;                  // (edge,side) entries per LDS reduction batch (a multiple of the two buffers)
+constexpr int MAX_INC = 2048;          // edge sides incident to one image (a3r_align_create refuses more)
 constexpr int FREEZE_POSE = 1, FREEZE_FOCAL = 2, FREEZE_PP = 4, FREEZE_DEPTH = 8;
 constexpr float ADAM_B1 = 0.9f, ADAM_B2 = 0.9f, ADAM_EPS = 1e-8f;  // base_opt.py:435
 
@@ -266,11 +263,8 @@ __device__ unsigned long long g_align_stamps[8192 * 8];
 #define A3R_STAMP(i)
 #endif
 // >= 4 waves per SIMD: the streaming loop needs <= 128 VGPRs; the (cold) tail may not raise the allocation
-#ifndef A3R_ALIGN_MIN_WAVES
-#define A3R_ALIGN_MIN_WAVES 4
-#endif
 template <bool MONO, bool L2, int MODE, bool VEC>
-__global__ __launch_bounds__(TPB, VEC ? A3R_ALIGN_MIN_WAVES : 2) void align_main_kernel(
+__global__ __launch_bounds__(TPB, VEC ? 4 : 2) void align_main_kernel(
     AlignDev d, AdamArgs ad, float* g_depth, TailOut tout,
     // read-only, wave-uniform tables as noalias kernel arguments: the compiler can then use SCALAR loads
     // (s_load), which do not sit on the vector-memory counter -- with vector loads every lookup of the next
@@ -298,9 +292,6 @@ __global__ __launch_bounds__(TPB, VEC ? A3R_ALIGN_MIN_WAVES : 2) void align_main
 #pragma unroll
     for (int i = 0; i < PXT; i++) valid[i] = pix0 + i * PSTEP < P;
     EdgeData<VEC> ea, eb;
-#if A3R_ALIGN_NBUF == 3
-    EdgeData<VEC> ec;
-#endif
     const float* ix = img_xf + n * 16;
     float R[9], T[3];
 #pragma unroll
@@ -348,9 +339,6 @@ __global__ __launch_bounds__(TPB, VEC ? A3R_ALIGN_MIN_WAVES : 2) void align_main
         // arithmetic below waits for the depth alone and runs while the edge data is still on its way
         if (kbeg < kend) load_edge(d, tb[3], P, pix0, valid, ea);
         if (kbeg + 1 < kend) load_edge(d, tb[4], P, pix0, valid, eb);
-#if A3R_ALIGN_NBUF == 3
-        if (kbeg + 2 < kend) load_edge(d, tb[5], P, pix0, valid, ec);
-#endif
         raw[0] = r4.x; raw[1] = r4.y; raw[2] = r4.z; raw[3] = r4.w;
         monov[0] = m4.x; monov[1] = m4.y; monov[2] = m4.z; monov[3] = m4.w;
     } else {
@@ -362,9 +350,6 @@ __global__ __launch_bounds__(TPB, VEC ? A3R_ALIGN_MIN_WAVES : 2) void align_main
         }
         if (kbeg < kend) load_edge(d, tb[3], P, pix0, valid, ea);
         if (kbeg + 1 < kend) load_edge(d, tb[4], P, pix0, valid, eb);
-#if A3R_ALIGN_NBUF == 3
-        if (kbeg + 2 < kend) load_edge(d, tb[5], P, pix0, valid, ec);
-#endif
     }
 #pragma unroll
     for (int i = 0; i < PXT; i++) {
@@ -450,42 +435,26 @@ __global__ __launch_bounds__(TPB, VEC ? A3R_ALIGN_MIN_WAVES : 2) void align_main
     // The incidence codes are read with SCALAR loads (a uniform index into a noalias table: s_load, counted on lgkmcnt): a vector
     // load here would need s_waitcnt vmcnt(0) before its value could form the next address and would drain the edge data in flight.
     // (Rounds 1-2 copied the image's codes to LDS first, which cost the prologue a vector load, an LDS pass and a barrier.)
-#ifndef A3R_ALIGN_SCALAR_CODES
-#define A3R_ALIGN_SCALAR_CODES 1
-#endif
-#if A3R_ALIGN_SCALAR_CODES
     auto code_at = [&](int k) { return inc[__builtin_amdgcn_readfirstlane(k)]; };
-#else
-    __shared__ int s_inc[MAX_INC];
-    for (int i = tid; i < kend - kbeg; i += TPB) s_inc[i] = inc[kbeg + i];
-    __syncthreads();
-    auto code_at = [&](int k) { return __builtin_amdgcn_readfirstlane(s_inc[k - kbeg]); };
-#endif
     int buf = 0;
     A3R_STAMP(1);
     // one flat loop, two edge sides per trip, each register buffer re-requested right after it has been consumed (one edge side
     // in flight behind the one being worked on); the LDS batch of EB slots is flushed inside
     int kb = 0, k0 = kbeg;
 #pragma unroll 1
-    for (int k = kbeg; k < kend; k += A3R_ALIGN_NBUF) {
+    for (int k = kbeg; k < kend; k += 2) {
         const bool has1 = k + 1 < kend;
         consume(code_at(k), ea, buf, kb);
 #ifdef A3R_ALIGN_STAMPS
         if (k == kbeg) { asm volatile("" :: "v"(gp[0][0])); A3R_STAMP(2); }
 #endif
-        if (k + A3R_ALIGN_NBUF < kend) load_edge(d, code_at(k + A3R_ALIGN_NBUF), P, pix0, valid, ea);
+        if (k + 2 < kend) load_edge(d, code_at(k + 2), P, pix0, valid, ea);
         if (has1) {
             consume(code_at(k + 1), eb, buf, kb + 1);
-            if (k + 1 + A3R_ALIGN_NBUF < kend) load_edge(d, code_at(k + 1 + A3R_ALIGN_NBUF), P, pix0, valid, eb);
+            if (k + 3 < kend) load_edge(d, code_at(k + 3), P, pix0, valid, eb);
         }
-#if A3R_ALIGN_NBUF == 3
-        if (k + 2 < kend) {
-            consume(code_at(k + 2), ec, buf, kb + 2);
-            if (k + 5 < kend) load_edge(d, code_at(k + 5), P, pix0, valid, ec);
-        }
-#endif
-        kb += A3R_ALIGN_NBUF;
-        if (kb == EB || k + A3R_ALIGN_NBUF >= kend) {
+        kb += 2;
+        if (kb == EB || k + 2 >= kend) {
             __syncthreads();
             if (tid < EB * 4) {
                 // one 16-byte quarter of a slot's row per thread, rows r added in order (the row is handed to the image's last workgroup)
@@ -874,13 +843,9 @@ __global__ __launch_bounds__(TPB, 4) void align_flow_vec_kernel(AlignDev d, cons
             const float Y2 = r02 * v0 + r12 * v1 + r22 * v2;
             const float qx = ft * Y0 + cxt * Y2, qy = ft * Y1 + cyt * Y2;
             const float den = Y2 + 1e-6f * dpv[i];
-#ifdef A3R_FLOW_IEEE_DIV
-            const float iz = 1.f / den;
-#else
             // v_rcp_f32 (1 ulp) + one Newton step instead of the IEEE division's expansion (a dozen instructions per pixel side)
             const float r0 = __builtin_amdgcn_rcpf(den);
             const float iz = r0 * (2.f - den * r0);
-#endif
             const float e0 = qx * iz - px[i], e1 = qy * iz - py[i];
             float gn0 = 0.f, gn1 = 0.f;
             if (ok[i]) {
@@ -1419,36 +1384,41 @@ static void refresh_if_dirty(a3r_align_s* a, hipStream_t st) {
     }
 }
 
-// Es: edges whose observations the handle walks (== E except for a shard handle)
-static size_t ws_layout(int E, int Es, int N, int P, size_t* off /*[18]*/) {
+// Byte offsets of the buffers carved out of a handle's workspace.  Es: edges whose observations the handle walks (== E except
+// for a shard handle)
+struct AlignWs {
+    size_t edge_xf, img_xf, partE, partN, gE, gN, lossE, inc_ptr, inc, slot_of, imw, imarea, gA, sumE, sumN, tick, order, freeze;
+    size_t bytes;
+};
+
+static AlignWs ws_layout(int E, int Es, int N, int P) {
     const int nch = (P + CHUNK - 1) / CHUNK;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
-    off[0] = take((size_t)E * 16 * 4);              // edge_xf
-    off[1] = take((size_t)N * 16 * 4);              // img_xf
-    off[2] = take((size_t)2 * Es * nch * 16 * 4);   // partE
-    off[3] = take((size_t)N * nch * 16 * 4);        // partN
-    off[4] = take((size_t)E * 8 * 4);               // gE
-    off[5] = take((size_t)N * 16 * 4);              // gN
-    off[6] = take((size_t)E * 4);                   // lossE
-    off[7] = take((size_t)(N + 1) * 4);             // inc_ptr
-    off[8] = take((size_t)2 * Es * 4);              // inc
-    off[9] = take((size_t)2 * Es * 4);              // slot_of
-    off[10] = take((size_t)N * 4);                  // imw
-    off[11] = take((size_t)N * 4);                  // imarea
-    off[12] = take((size_t)E * 2 * 4);              // gA
-    off[13] = take((size_t)2 * Es * 16 * 4);        // sumE
-    off[14] = take((size_t)N * 16 * 4);             // sumN
-    off[15] = take((size_t)(N + 1) * 4);            // tick
-    off[16] = take((size_t)N * 8 * 4);              // order: per dispatch slot {image, kbeg, kend, code0, code1, code2, freeze bits, 0}
-    off[17] = take((size_t)N * 4);                  // freeze
-    return o;
+    AlignWs w;
+    w.edge_xf = take((size_t)E * 16 * 4);
+    w.img_xf = take((size_t)N * 16 * 4);
+    w.partE = take((size_t)2 * Es * nch * 16 * 4);
+    w.partN = take((size_t)N * nch * 16 * 4);
+    w.gE = take((size_t)E * 8 * 4);
+    w.gN = take((size_t)N * 16 * 4);
+    w.lossE = take((size_t)E * 4);
+    w.inc_ptr = take((size_t)(N + 1) * 4);
+    w.inc = take((size_t)2 * Es * 4);
+    w.slot_of = take((size_t)2 * Es * 4);
+    w.imw = take((size_t)N * 4);
+    w.imarea = take((size_t)N * 4);
+    w.gA = take((size_t)E * 2 * 4);
+    w.sumE = take((size_t)2 * Es * 16 * 4);
+    w.sumN = take((size_t)N * 16 * 4);
+    w.tick = take((size_t)(N + 1) * 4);
+    w.order = take((size_t)N * 8 * 4);              // per dispatch slot {image, kbeg, kend, code0, code1, code2, freeze bits, 0}
+    w.freeze = take((size_t)N * 4);
+    w.bytes = o;
+    return w;
 }
 
-extern "C" size_t a3r_align_workspace_bytes(int E, int N, int P) {
-    size_t off[18];
-    return ws_layout(E, E, N, P, off);
-}
+extern "C" size_t a3r_align_workspace_bytes(int E, int N, int P) { return ws_layout(E, E, N, P).bytes; }
 
 // e0 == 0, e1 == s->E, shard == false: the monolithic handle
 static int align_create_impl(const a3r_align_desc* s, int e0, int e1, bool shard, a3r_align_t* out, void* stream) {
@@ -1460,9 +1430,9 @@ static int align_create_impl(const a3r_align_desc* s, int e0, int e1, bool shard
     A3R_CHECK_ARG(!s->use_mono || (s->mono && s->shifts), "a3r_align_create: use_mono needs mono and shifts");
     A3R_CHECK_ARG(s->adam_pw_poses && s->adam_depth && s->adam_small, "a3r_align_create: missing Adam state");
     A3R_CHECK_ARG(s->loss_history && s->loss_capacity > 0, "a3r_align_create: missing loss_history");
-    size_t off[18];
     const int Es = e1 - e0;
-    const size_t need = ws_layout(s->E, Es, s->N, s->P, off);
+    const AlignWs ws = ws_layout(s->E, Es, s->N, s->P);
+    const size_t need = ws.bytes;
     A3R_CHECK_ARG(!s->train_adaptors || s->adam_pw_adaptors, "a3r_align_create: train_adaptors needs adam_pw_adaptors");
     A3R_CHECK_ARG(s->workspace && s->workspace_bytes >= need, "a3r_align_create: workspace too small (%zu < %zu)",
                   s->workspace_bytes, need);
@@ -1497,14 +1467,14 @@ static int align_create_impl(const a3r_align_desc* s, int e0, int e1, bool shard
     }
     a3r_align_s* a = new (std::nothrow) a3r_align_s();
     A3R_CHECK_ARG(a, "out of host memory");
-    char* ws = (char*)s->workspace;
+    char* base = (char*)s->workspace;
     hipStream_t st = as_stream(stream);
-    auto up = [&](size_t o, const void* src, size_t bytes) { return hipMemcpyAsync(ws + o, src, bytes, hipMemcpyHostToDevice, st); };
-    hipError_t err = up(off[7], deg.data(), (s->N + 1) * 4);
-    if (err == hipSuccess) err = up(off[8], inc.data(), (size_t)2 * Es * 4);
-    if (err == hipSuccess) err = up(off[9], slot.data(), (size_t)2 * Es * 4);
-    if (err == hipSuccess) err = up(off[10], s->imw_host, s->N * 4);
-    if (err == hipSuccess) err = up(off[11], s->imarea_host, s->N * 4);
+    auto up = [&](size_t o, const void* src, size_t bytes) { return hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, st); };
+    hipError_t err = up(ws.inc_ptr, deg.data(), (s->N + 1) * 4);
+    if (err == hipSuccess) err = up(ws.inc, inc.data(), (size_t)2 * Es * 4);
+    if (err == hipSuccess) err = up(ws.slot_of, slot.data(), (size_t)2 * Es * 4);
+    if (err == hipSuccess) err = up(ws.imw, s->imw_host, s->N * 4);
+    if (err == hipSuccess) err = up(ws.imarea, s->imarea_host, s->N * 4);
     // dispatch order of the images: most incident edge sides first (stable: ties keep the image order)
     std::vector<int> order(s->N);
     for (int n = 0; n < s->N; n++) order[n] = n;
@@ -1517,9 +1487,9 @@ static int align_create_impl(const a3r_align_desc* s, int e0, int e1, bool shard
         tab[y * 8 + 4] = kb + 1 < ke ? inc[kb + 1] : 0;
         tab[y * 8 + 5] = kb + 2 < ke ? inc[kb + 2] : 0;
     }
-    if (err == hipSuccess) err = up(off[16], tab.data(), tab.size() * 4);
-    if (err == hipSuccess) err = hipMemsetAsync(ws + off[15], 0, (size_t)(s->N + 1) * 4, st);
-    if (err == hipSuccess) err = hipMemsetAsync(ws + off[17], 0, (size_t)s->N * 4, st);
+    if (err == hipSuccess) err = up(ws.order, tab.data(), tab.size() * 4);
+    if (err == hipSuccess) err = hipMemsetAsync(base + ws.tick, 0, (size_t)(s->N + 1) * 4, st);
+    if (err == hipSuccess) err = hipMemsetAsync(base + ws.freeze, 0, (size_t)s->N * 4, st);
     if (err == hipSuccess) err = hipStreamSynchronize(st);   // host vectors go out of scope
     if (err != hipSuccess) {
         delete a;
@@ -1537,12 +1507,12 @@ static int align_create_impl(const a3r_align_desc* s, int e0, int e1, bool shard
     d.pw_poses = s->pw_poses; d.pw_adaptors = s->pw_adaptors; d.depth = s->depth; d.shifts = s->shifts;
     d.im_poses = s->im_poses; d.im_focals = s->im_focals; d.im_pp = s->im_pp;
     d.adam_pw_poses = s->adam_pw_poses; d.adam_depth = s->adam_depth; d.adam_small = s->adam_small;
-    d.edge_xf = (float*)(ws + off[0]); d.img_xf = (float*)(ws + off[1]);
-    d.partE = (float*)(ws + off[2]); d.partN = (float*)(ws + off[3]);
-    d.gE = (float*)(ws + off[4]); d.gN = (float*)(ws + off[5]); d.lossE = (float*)(ws + off[6]);
-    d.gA = (float*)(ws + off[12]);
-    d.sumE = (float*)(ws + off[13]); d.sumN = (float*)(ws + off[14]); d.tick = (int*)(ws + off[15]);
-    d.order = (const int*)(ws + off[16]); d.freeze = (const int*)(ws + off[17]);
+    d.edge_xf = (float*)(base + ws.edge_xf); d.img_xf = (float*)(base + ws.img_xf);
+    d.partE = (float*)(base + ws.partE); d.partN = (float*)(base + ws.partN);
+    d.gE = (float*)(base + ws.gE); d.gN = (float*)(base + ws.gN); d.lossE = (float*)(base + ws.lossE);
+    d.gA = (float*)(base + ws.gA);
+    d.sumE = (float*)(base + ws.sumE); d.sumN = (float*)(base + ws.sumN); d.tick = (int*)(base + ws.tick);
+    d.order = (const int*)(base + ws.order); d.freeze = (const int*)(base + ws.freeze);
     {
         // A3R_ALIGN_TAIL=fused: finish the iteration inside the main launch (last-block-done tickets) instead of the two small
         // finalize launches.  Correct and bitwise identical, but measured SLOWER on MI355X (config 2: 147 vs 124 + 18 us per
@@ -1552,8 +1522,8 @@ static int align_create_impl(const a3r_align_desc* s, int e0, int e1, bool shard
         const char* t = getenv("A3R_ALIGN_TAIL");
         d.fused_tail = (t && !strcmp(t, "fused") && !shard) ? 1 : 0;     // a shard's iteration ends after the reduction
     }
-    d.inc_ptr = (const int*)(ws + off[7]); d.inc = (const int*)(ws + off[8]); d.slot_of = (const int*)(ws + off[9]);
-    d.imw = (const int*)(ws + off[10]); d.imarea = (const int*)(ws + off[11]);
+    d.inc_ptr = (const int*)(base + ws.inc_ptr); d.inc = (const int*)(base + ws.inc); d.slot_of = (const int*)(base + ws.slot_of);
+    d.imw = (const int*)(base + ws.imw); d.imarea = (const int*)(base + ws.imarea);
     d.loss_history = s->loss_history;
     a->use_mono = s->use_mono != 0; a->dist_l2 = s->dist_l2 != 0; a->steps = 0; a->loss_capacity = s->loss_capacity;
     a->dirty = true;
@@ -1622,23 +1592,27 @@ static void launch_main(a3r_align_s* a, const AdamArgs& ad, float* g_depth, cons
 }
 
 // ---- cloud_opt_flow extras -------------------------------------------------------------------------------------
-static size_t flow_ws_layout(int E, int N, int P, size_t* off /*[6]*/) {
+struct FlowWs {
+    size_t gflow, partF, sumF, flow_state, lossN, other;
+    size_t bytes;
+};
+
+static FlowWs flow_ws_layout(int E, int N, int P) {
     const int nch = (P + CHUNK - 1) / CHUNK;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
-    off[0] = take((size_t)2 * N * P * 3 * 4);          // gflow
-    off[1] = take((size_t)2 * E * nch * NFP * 4);      // partF
-    off[2] = take((size_t)2 * E * NFP * 4);            // sumF
-    off[3] = take(8 * 4);                              // flow_state
-    off[4] = take((size_t)N * 4);                      // lossN
-    off[5] = take((size_t)2 * E * 4);                  // other
-    return o;
+    FlowWs w;
+    w.gflow = take((size_t)2 * N * P * 3 * 4);
+    w.partF = take((size_t)2 * E * nch * NFP * 4);
+    w.sumF = take((size_t)2 * E * NFP * 4);
+    w.flow_state = take(8 * 4);
+    w.lossN = take((size_t)N * 4);
+    w.other = take((size_t)2 * E * 4);
+    w.bytes = o;
+    return w;
 }
 
-extern "C" size_t a3r_align_flow_workspace_bytes(int E, int N, int P) {
-    size_t off[6];
-    return flow_ws_layout(E, N, P, off);
-}
+extern "C" size_t a3r_align_flow_workspace_bytes(int E, int N, int P) { return flow_ws_layout(E, N, P).bytes; }
 
 extern "C" int a3r_align_set_flow(a3r_align_t a, const a3r_align_flow_desc* f, void* stream) {
     A3R_CHECK_ARG(a && f, "a3r_align_set_flow: null argument");
@@ -1646,30 +1620,30 @@ extern "C" int a3r_align_set_flow(a3r_align_t a, const a3r_align_flow_desc* f, v
     A3R_CHECK_ARG(!a->use_mono, "a3r_align_set_flow: the flow variant has no mono-depth parameterisation (cloud_opt_flow/optimizer.py:52)");
     A3R_CHECK_ARG(!(f->shared_focal && a->has_focal_mask), "a3r_align_set_flow: shared_focal next to a per-image focal mask (a3r_align_set_train_masks)");
     AlignDev& d = a->d;
-    size_t off[6];
-    const size_t need = flow_ws_layout(d.E, d.N, d.P, off);
+    const FlowWs ws = flow_ws_layout(d.E, d.N, d.P);
+    const size_t need = ws.bytes;
     A3R_CHECK_ARG(f->workspace && f->workspace_bytes >= need, "a3r_align_set_flow: workspace too small (%zu < %zu)", f->workspace_bytes, need);
     A3R_CHECK_ARG(f->temporal_smoothing_weight >= 0.f && f->flow_loss_weight >= 0.f, "a3r_align_set_flow: negative weight");
     if (f->flow_loss_weight > 0.f) {
         A3R_CHECK_ARG(f->flow_ij && f->flow_ji && f->dynamic_mask, "a3r_align_set_flow: flow_loss_weight > 0 needs flow_ij, flow_ji and dynamic_mask");
         A3R_CHECK_ARG(f->H > 0 && f->W > 0 && f->H * f->W == d.P, "a3r_align_set_flow: H*W must equal P (all images of one shape)");
     }
-    char* ws = (char*)f->workspace;
+    char* base = (char*)f->workspace;
     hipStream_t st = as_stream(stream);
     std::vector<int> other(2 * d.E);
     for (int k = 0; k < 2 * d.E; k++) {
         const int e = a->inc[k] >> 1, side = a->inc[k] & 1;
         other[k] = side ? a->ei[e] : a->ej[e];
     }
-    A3R_HIP(hipMemcpyAsync(ws + off[5], other.data(), other.size() * 4, hipMemcpyHostToDevice, st));
-    A3R_HIP(hipMemsetAsync(ws + off[3], 0, 32, st));
-    A3R_HIP(hipMemsetAsync(ws + off[4], 0, (size_t)d.N * 4, st));
+    A3R_HIP(hipMemcpyAsync(base + ws.other, other.data(), other.size() * 4, hipMemcpyHostToDevice, st));
+    A3R_HIP(hipMemsetAsync(base + ws.flow_state, 0, 32, st));
+    A3R_HIP(hipMemsetAsync(base + ws.lossN, 0, (size_t)d.N * 4, st));
     A3R_HIP(hipStreamSynchronize(st));
     d.shared_focal = f->shared_focal; d.tsw = f->temporal_smoothing_weight; d.trans_w = f->translation_weight;
     d.flow_w = f->flow_loss_weight; d.flow_thre = f->flow_loss_thre; d.pxl_thre = f->pxl_thre;
     d.fH = f->H; d.fW = f->W; d.flow_ij = f->flow_ij; d.flow_ji = f->flow_ji; d.dyn = f->dynamic_mask;
-    d.gflow = (float*)(ws + off[0]); d.partF = (float*)(ws + off[1]); d.sumF = (float*)(ws + off[2]);
-    d.flow_state = (float*)(ws + off[3]); d.lossN = (float*)(ws + off[4]); d.other = (const int*)(ws + off[5]);
+    d.gflow = (float*)(base + ws.gflow); d.partF = (float*)(base + ws.partF); d.sumF = (float*)(base + ws.sumF);
+    d.flow_state = (float*)(base + ws.flow_state); d.lossN = (float*)(base + ws.lossN); d.other = (const int*)(base + ws.other);
     a->flow_start_iter = f->flow_start_iter;
     a->dirty = true;
     return A3R_OK;
@@ -1701,6 +1675,29 @@ extern "C" int a3r_align_set_depth_prior(a3r_align_t a, float weight, const floa
     return A3R_OK;
 }
 
+// The two small launches that end an iteration (per-slot sums and chain rules, then the single-block Adam / gradient export /
+// loss); nothing to do when the main kernel finishes the iteration itself (A3R_ALIGN_TAIL=fused).  The caller names its MODE's
+// finalize B kernel (a function argument, not a template parameter of this helper): a kernel template is instantiated where it is
+// first named, and that order is the order of the kernels in the code object, which stays what it was.
+using FinalizeB = void (*)(AlignDev, AdamArgs, TailOut);
+static void launch_tail(a3r_align_s* a, FinalizeB finalize_b, const AdamArgs& ad, const TailOut& tout, int loss_only, hipStream_t st) {
+    if (a->d.fused_tail) return;
+    ProfScope prof(PK_ALIGN_SMALL, 0.0, st);
+    hipLaunchKernelGGL(align_finalize_a_kernel, dim3(a->d.E + a->d.N), dim3(64), 0, st, a->d, loss_only);
+    hipLaunchKernelGGL(finalize_b, dim3(1), dim3(TPB), 0, st, a->d, ad, tout);
+}
+
+// torch.optim.Adam's bias corrections for the handle's next step (evaluated in double, as adam.py does with Python floats)
+static AdamArgs adam_args(const a3r_align_s* a, float lr) {
+    const int t = a->steps + 1;
+    AdamArgs ad;
+    ad.lr = lr;
+    ad.step_size = (float)((double)lr / (1.0 - pow((double)ADAM_B1, t)));
+    ad.bc2_sqrt = (float)sqrt(1.0 - pow((double)ADAM_B2, t));
+    ad.step = a->steps;
+    return ad;
+}
+
 // the ego-flow pass of one iteration (before the main kernel): unscaled sums, then the normalisers / drop decision
 static void launch_flow(a3r_align_s* a, int epoch, hipStream_t st) {
     AlignDev& d = a->d;
@@ -1722,21 +1719,12 @@ extern "C" int a3r_align_step_epoch(a3r_align_t a, float lr, int epoch, void* st
     A3R_CHECK_ARG(!a->shard, "a3r_align_step: edge-shard handle (use a3r_align_shard_partial / a3r_align_shard_apply)");
     A3R_CHECK_ARG(a->steps < a->loss_capacity, "a3r_align_step: loss_history full (%d)", a->loss_capacity);
     hipStream_t st = as_stream(stream);
-    const int t = a->steps + 1;
-    AdamArgs ad;
-    ad.lr = lr;
-    ad.step_size = (float)((double)lr / (1.0 - pow((double)ADAM_B1, t)));
-    ad.bc2_sqrt = (float)sqrt(1.0 - pow((double)ADAM_B2, t));
-    ad.step = a->steps;
+    const AdamArgs ad = adam_args(a, lr);
     refresh_if_dirty(a, st);
     launch_flow(a, epoch, st);
     const TailOut tout = {nullptr, nullptr, nullptr, nullptr};
     launch_main<2>(a, ad, nullptr, tout, st);
-    if (!a->d.fused_tail) {
-        ProfScope prof(PK_ALIGN_SMALL, 0.0, st);
-        hipLaunchKernelGGL(align_finalize_a_kernel, dim3(a->d.E + a->d.N), dim3(64), 0, st, a->d, 0);
-        hipLaunchKernelGGL((align_finalize_b_kernel<2>), dim3(1), dim3(TPB), 0, st, a->d, ad, tout);
-    }
+    launch_tail(a, align_finalize_b_kernel<2>, ad, tout, 0, st);
     A3R_LAUNCH_CHECK();
     a->steps++;
     return A3R_OK;
@@ -1766,10 +1754,7 @@ extern "C" int a3r_align_loss(a3r_align_t a, float* loss_dev, void* stream) {
     launch_flow(a, 1 << 30, st);                                       // net() defaults to epoch=9999: flow term active
     const TailOut tout = {nullptr, nullptr, loss_dev, nullptr};
     launch_main<0>(a, ad, nullptr, tout, st);
-    if (!a->d.fused_tail) {
-        hipLaunchKernelGGL(align_finalize_a_kernel, dim3(a->d.E + a->d.N), dim3(64), 0, st, a->d, 1);
-        hipLaunchKernelGGL((align_finalize_b_kernel<0>), dim3(1), dim3(TPB), 0, st, a->d, ad, tout);
-    }
+    launch_tail(a, align_finalize_b_kernel<0>, ad, tout, 1, st);
     A3R_LAUNCH_CHECK();
     return A3R_OK;
 }
@@ -1784,10 +1769,7 @@ extern "C" int a3r_align_grad_full(a3r_align_t a, int epoch, float* g_pw_poses, 
     launch_flow(a, epoch, st);
     const TailOut tout = {g_pw_poses, g_small, loss_dev, g_pw_adaptors};
     launch_main<1>(a, ad, g_depth, tout, st);
-    if (!a->d.fused_tail) {
-        hipLaunchKernelGGL(align_finalize_a_kernel, dim3(a->d.E + a->d.N), dim3(64), 0, st, a->d, 0);
-        hipLaunchKernelGGL((align_finalize_b_kernel<1>), dim3(1), dim3(TPB), 0, st, a->d, ad, tout);
-    }
+    launch_tail(a, align_finalize_b_kernel<1>, ad, tout, 0, st);
     A3R_LAUNCH_CHECK();
     return A3R_OK;
 }
@@ -1837,10 +1819,7 @@ extern "C" int a3r_align_pose_matrices(a3r_align_t a, float* edge_M, float* img_
 }
 
 // ---- edge shards -----------------------------------------------------------------------------------------------
-extern "C" size_t a3r_align_shard_workspace_bytes(int E, int E_shard, int N, int P) {
-    size_t off[18];
-    return ws_layout(E, E_shard, N, P, off);
-}
+extern "C" size_t a3r_align_shard_workspace_bytes(int E, int E_shard, int N, int P) { return ws_layout(E, E_shard, N, P).bytes; }
 
 static size_t shard_depth_floats(int N, int P) { return align_up((size_t)N * P, 4); }
 
@@ -1894,12 +1873,7 @@ extern "C" int a3r_align_shard_apply(a3r_align_t a, const float* reduced, size_t
     A3R_CHECK_ARG(a->steps < a->loss_capacity, "a3r_align_shard_apply: loss_history full (%d)", a->loss_capacity);
     hipStream_t st = as_stream(stream);
     const AlignDev& d = a->d;
-    const int t = a->steps + 1;
-    AdamArgs ad;
-    ad.lr = lr;
-    ad.step_size = (float)((double)lr / (1.0 - pow((double)ADAM_B1, t)));
-    ad.bc2_sqrt = (float)sqrt(1.0 - pow((double)ADAM_B2, t));
-    ad.step = a->steps;
+    const AdamArgs ad = adam_args(a, lr);
     refresh_if_dirty(a, st);
     {
         // the [N, P] update first: it reads nothing the small kernels write

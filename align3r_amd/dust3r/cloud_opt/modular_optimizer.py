@@ -18,7 +18,6 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .commons import rotmat_to_unitquat, signed_log1p
 from .optimizer import PointCloudOptimizer
 
 
@@ -92,46 +91,19 @@ class ModularPointCloudOptimizer(PointCloudOptimizer):
         return msk_indices(msk, self.n_imgs)
 
     # ------------------------------------------------------------------ presets (modular_optimizer.py:38-68)
-    def preset_pose(self, known_poses, pose_msk=None):          # cam-to-world
-        if isinstance(known_poses, torch.Tensor) and known_poses.ndim == 2:
-            known_poses = [known_poses]
-        e = self._need_engine()
-        poses = self.im_poses.clone()
-        for idx, pose in zip(self._msk_indices(pose_msk), known_poses):
-            pose = torch.as_tensor(pose, dtype=torch.float32).cpu()
-            if self.verbose:
-                print(f' (setting pose #{idx} = {pose[:3, 3]})')
-            poses[idx, 0:4] = rotmat_to_unitquat(pose[:3, :3]).to(poses.device)
-            poses[idx, 4:7] = signed_log1p(pose[:3, 3]).to(poses.device)
-            self._frozen['pose'][idx] = True
-        # normalize scale if there's less than 1 known pose (:46-48)
-        self.norm_pw_scale = bool(self._frozen['pose'].sum() <= 1)
-        e.flags.update(norm_pw_scale=self.norm_pw_scale)
-        e.set_train_masks(**self._train_masks())
-        e.set_params(im_poses=poses)
+    def _set_known(self, group, idxs, msk):
+        """Exactly the touched images become known: their rows are frozen through the engine's per-image train masks."""
+        for idx in idxs:
+            self._frozen[group][idx] = True
+        if group == 'pose':
+            # normalize scale if there's less than 1 known pose (:46-48)
+            self.norm_pw_scale = bool(self._frozen['pose'].sum() <= 1)
+            self.engine.flags.update(norm_pw_scale=self.norm_pw_scale)
+        self.engine.set_train_masks(**self._train_masks())
 
-    def preset_focal(self, known_focals, msk=None):
-        e = self._need_engine()
-        f = e.params['im_focals'].clone()
-        for idx, focal in zip(self._msk_indices(msk), known_focals):
-            if self.verbose:
-                print(f' (setting focal #{idx} = {focal})')
-            f[idx] = self.focal_break * float(np.log(float(focal)))
-            self._frozen['focal'][idx] = True
-        e.set_train_masks(**self._train_masks())
-        e.set_params(im_focals=f)
-
-    def preset_principal_point(self, known_pp, msk=None):
-        e = self._need_engine()
-        pp = self.im_pp.clone()
-        for idx, p in zip(self._msk_indices(msk), known_pp):
-            if self.verbose:
-                print(f' (setting principal point #{idx} = {p})')
-            H, W = self.imshapes[idx]
-            pp[idx] = (torch.as_tensor(p, dtype=torch.float32).to(pp.device) - torch.tensor([W / 2, H / 2], device=pp.device)) / 10
-            self._frozen['pp'][idx] = True
-        e.set_train_masks(**self._train_masks())
-        e.set_params(im_pp=pp)
+    def _announce_preset(self, group, idx, value):
+        if self.verbose:
+            print(f" (setting {dict(pose='pose', focal='focal', pp='principal point')[group]} #{idx} = {value})")
 
     def preset_intrinsics(self, known_intrinsics, msk=None):
         if isinstance(known_intrinsics, torch.Tensor) and known_intrinsics.ndim == 2:

@@ -157,17 +157,19 @@ class PointCloudOptimizer:
             out.append(w.reshape(E, P))
         return out
 
-    def _build_engine(self, device):
+    def _engine_kwargs(self, device):
+        """What every engine of this class and its variants is built from: the graph, the stacked observations and the settings."""
         w_i, w_j = self._stacked_weights()
+        return dict(ei=[i for i, j in self.edges], ej=[j for i, j in self.edges], pred_i=self._pred_i, pred_j=self._pred_j,
+                    w_i=w_i, w_j=w_j, imshapes=self.imshapes, mono=self.mono_depths, base_scale=self.base_scale,
+                    pw_break=self.pw_break, focal_break=self.focal_break, norm_pw_scale=self.norm_pw_scale, dist=self.dist,
+                    device=device, **self._flags)
+
+    def _build_engine(self, device):
         if self.edge_shards is not None or self.edge_shard_group is not None:
             from ...aligner import ShardedAlignEngine
-            return ShardedAlignEngine([i for i, j in self.edges], [j for i, j in self.edges], self._pred_i, self._pred_j, w_i, w_j,
-                                      self.imshapes, mono=self.mono_depths, base_scale=self.base_scale, pw_break=self.pw_break,
-                                      focal_break=self.focal_break, norm_pw_scale=self.norm_pw_scale, dist=self.dist, device=device,
-                                      local_shards=self.edge_shards, group=self.edge_shard_group, **self._flags)
-        return AlignEngine([i for i, j in self.edges], [j for i, j in self.edges], self._pred_i, self._pred_j, w_i, w_j,
-                           self.imshapes, mono=self.mono_depths, base_scale=self.base_scale, pw_break=self.pw_break,
-                           focal_break=self.focal_break, norm_pw_scale=self.norm_pw_scale, dist=self.dist, device=device, **self._flags)
+            return ShardedAlignEngine(local_shards=self.edge_shards, group=self.edge_shard_group, **self._engine_kwargs(device))
+        return AlignEngine(**self._engine_kwargs(device))
 
     def _current_state(self):
         """Parameter values of the live engine (host copies), or None before the first .to()."""
@@ -375,42 +377,49 @@ class PointCloudOptimizer:
         msk = np.asarray(msk)
         return np.where(msk)[0].tolist() if msk.dtype == bool else msk.tolist()
 
-    def _check_all(self, msk):
+    def _set_known(self, group, idxs, msk):
+        """How the images `idxs` touched by a preset_* call become known.  Here: all images at once or not at all, the handle-wide
+        train_* switch of the group goes off (and known poses end the normalisation of the pairwise scales)."""
         assert self._msk_indices(msk) == list(range(self.n_imgs)), 'incomplete mask!'
+        flag = dict(pose='train_poses', focal='train_focals', pp='train_pp')[group]
+        self._flags[flag] = self.engine.flags[flag] = False
+        if group == 'pose':
+            self.norm_pw_scale = self.engine.flags['norm_pw_scale'] = False
 
-    def preset_pose(self, known_poses, pose_msk=None):
-        self._check_all(pose_msk)
+    def _announce_preset(self, group, idx, value):
+        pass
+
+    def _preset(self, group, key, values, msk, encode):
+        """The body of the preset_* methods: encode(idx, value) -> (the parameter row of image idx, what to announce) for the
+        images msk selects, written into parameter `key`; the images become known (_set_known)."""
+        e = self._need_engine()
+        p = e.params[key].clone()
+        idxs = []
+        for idx, value in zip(self._msk_indices(msk), values):
+            p[idx], shown = encode(idx, value)
+            self._announce_preset(group, idx, shown)
+            idxs.append(idx)
+        self._set_known(group, idxs, msk)
+        e.set_params(**{key: p})
+
+    def preset_pose(self, known_poses, pose_msk=None):          # cam-to-world
         if isinstance(known_poses, torch.Tensor) and known_poses.ndim == 2:
             known_poses = [known_poses]
-        poses = self.im_poses.clone()
-        for idx, pose in zip(self._msk_indices(pose_msk), known_poses):
+
+        def encode(idx, pose):
             pose = torch.as_tensor(pose, dtype=torch.float32).cpu()
-            poses[idx, 0:4] = rotmat_to_unitquat(pose[:3, :3]).to(poses.device)
-            poses[idx, 4:7] = signed_log1p(pose[:3, 3]).to(poses.device)
-        self.norm_pw_scale = False
-        self._flags['train_poses'] = False
-        e = self._need_engine()
-        e.flags.update(norm_pw_scale=False, train_poses=False)
-        e.set_params(im_poses=poses)
+            return torch.cat((rotmat_to_unitquat(pose[:3, :3]), signed_log1p(pose[:3, 3]))).to(self.device), pose[:3, 3]
+        self._preset('pose', 'im_poses', known_poses, pose_msk, encode)
 
     def preset_focal(self, known_focals, msk=None):
-        self._check_all(msk)
-        f = self._need_engine().params['im_focals'].clone()
-        for idx, focal in zip(self._msk_indices(msk), known_focals):
-            f[idx] = self.focal_break * float(np.log(float(focal)))
-        self._flags['train_focals'] = False
-        self.engine.flags.update(train_focals=False)
-        self.engine.set_params(im_focals=f)
+        self._preset('focal', 'im_focals', known_focals, msk,
+                     lambda idx, focal: (self.focal_break * float(np.log(float(focal))), focal))
 
     def preset_principal_point(self, known_pp, msk=None):
-        self._check_all(msk)
-        pp = self.im_pp.clone()
-        for idx, p in zip(self._msk_indices(msk), known_pp):
+        def encode(idx, p):
             H, W = self.imshapes[idx]
-            pp[idx] = (torch.as_tensor(p, dtype=torch.float32).to(pp.device) - torch.tensor([W / 2, H / 2], device=pp.device)) / 10
-        self._flags['train_pp'] = False
-        self.engine.flags.update(train_pp=False)
-        self.engine.set_params(im_pp=pp)
+            return (torch.as_tensor(p, dtype=torch.float32).to(self.device) - torch.tensor([W / 2, H / 2], device=self.device)) / 10, p
+        self._preset('pp', 'im_pp', known_pp, msk, encode)
 
     # ------------------------------------------------------------------ optimisation (base_opt.py:373-464)
     def forward(self):
@@ -419,30 +428,40 @@ class PointCloudOptimizer:
 
     __call__ = forward
 
-    def compute_global_alignment(self, init=None, init_priors=None, niter_PnP=10, lr=0.01, niter=300, schedule='cosine',
-                                 lr_min=1e-6):
-        e = self._need_engine()
+    def _init_known_poses(self, niter_PnP):
+        from .init_im_poses import init_from_known_poses              # parity unpinned (see that module)
+        init_from_known_poses(self, niter_PnP=niter_PnP, min_conf_thr=self.min_conf_thr)
+
+    def _init_from(self, init, init_priors, niter_PnP):
         if init is None:
             pass
         elif init in ('msp', 'mst'):
             from .init_im_poses import init_minimum_spanning_tree       # parity unpinned (see that module)
             init_minimum_spanning_tree(self, init_priors=init_priors, niter_PnP=niter_PnP)
         elif init == 'known_poses':
-            from .init_im_poses import init_from_known_poses              # parity unpinned (see that module)
-            init_from_known_poses(self, niter_PnP=niter_PnP, min_conf_thr=self.min_conf_thr)
+            self._init_known_poses(niter_PnP)
         else:
             raise ValueError(f'bad value for {init=}')
+
+    def _run_and_report(self, niter, lr, schedule, lr_min, note=''):
+        e = self._need_engine()
+        e.set_params(reset_optimizer=True)            # a fresh torch.optim.Adam per call (base_opt.py:435)
+        losses = e.run(niter, lr, schedule, lr_min)
+        if self.verbose:
+            print(f'Global alignement - {niter} iterations,{note} loss={losses[-1]:g}')
+        return float(losses[-1])
+
+    def compute_global_alignment(self, init=None, init_priors=None, niter_PnP=10, lr=0.01, niter=300, schedule='cosine',
+                                 lr_min=1e-6):
+        e = self._need_engine()
+        self._init_from(init, init_priors, niter_PnP)
         if schedule not in ('cosine', 'linear'):
             raise ValueError(f'bad lr {schedule=}')
         if niter <= 0:
             return float('inf')
         if e.steps_done + niter > e.loss_capacity:
             raise RuntimeError('loss history capacity exceeded')
-        e.set_params(reset_optimizer=True)            # a fresh torch.optim.Adam per call (base_opt.py:435)
-        losses = e.run(niter, lr, schedule, lr_min)
-        if self.verbose:
-            print(f'Global alignement - {niter} iterations, final lr={lr_min if niter > 1 else lr:g} loss={losses[-1]:g}')
-        return float(losses[-1])
+        return self._run_and_report(niter, lr, schedule, lr_min, note=f' final lr={lr_min if niter > 1 else lr:g}')
 
 
 def _ravel_hw(tensor, fill=0):

@@ -173,16 +173,8 @@ class PointCloudOptimizer(_Base):
         """The base class's .to() with the flow variant's extras (shared focal, temporal smoothing, ego-flow inputs)."""
         if not self._uniform and self._flow is not None:
             raise RuntimeError('the flow term needs images of one shape (flow fields are stacked [E,2,H,W], optimizer.py:118-154)')
-        w_i, w_j = self._stacked_weights()
-        return AlignEngine([i for i, j in self.edges], [j for i, j in self.edges], self._pred_i, self._pred_j, w_i, w_j,
-                           self.imshapes, mono=None, base_scale=self.base_scale, pw_break=self.pw_break,
-                           focal_break=self.focal_break, norm_pw_scale=self.norm_pw_scale, dist=self.dist, device=device,
-                           shared_focal=self.shared_focal, temporal_smoothing_weight=float(self.temporal_smoothing_weight),
-                           translation_weight=float(self.translation_weight), flow=self._flow, **self._flags)
-
-    @property
-    def im_focals(self):
-        return self._need_engine().params['im_focals'][:, None]
+        return AlignEngine(shared_focal=self.shared_focal, temporal_smoothing_weight=float(self.temporal_smoothing_weight),
+                           translation_weight=float(self.translation_weight), flow=self._flow, **self._engine_kwargs(device))
 
     def get_focals(self):
         lf = self.im_focals
@@ -231,26 +223,17 @@ class PointCloudOptimizer(_Base):
             raise NotImplementedError('preset_focal with shared_focal')
         super().preset_focal(known_focals, msk)
 
+    def _init_known_poses(self, niter_PnP):
+        raise NotImplementedError("init='known_poses': the reference's own branch cannot run (base_opt.py:468 hands preset_pose a "
+                                  "python list, optimizer.py:325 takes .shape of it); preset_pose + init='mst' is the working route")
+
     def compute_global_alignment(self, init=None, init_priors=None, niter_PnP=10, lr=0.01, niter=300, schedule='cosine',
                                  lr_min=1e-3, **kw):
-        e = self._need_engine()
-        if init is None:
-            pass
-        elif init in ('msp', 'mst'):
-            from ..cloud_opt.init_im_poses import init_minimum_spanning_tree       # parity unpinned (see that module)
-            init_minimum_spanning_tree(self, init_priors=init_priors, niter_PnP=niter_PnP)
-            if self.n_imgs > 2:
-                self._set_init_depthmap()                                          # cloud_opt_flow/init_im_poses.py:149-150
-        elif init == 'known_poses':
-            raise NotImplementedError("init='known_poses': the reference's own branch cannot run (base_opt.py:468 hands preset_pose a "
-                                      "python list, optimizer.py:325 takes .shape of it); preset_pose + init='mst' is the working route")
-        else:
-            raise ValueError(f'bad value for {init=}')
+        self._need_engine()
+        self._init_from(init, init_priors, niter_PnP)
+        if init in ('msp', 'mst') and self.n_imgs > 2:
+            self._set_init_depthmap()                                          # cloud_opt_flow/init_im_poses.py:149-150
         if niter <= 0:
             return float('inf')
         self._check_depth_prior()
-        e.set_params(reset_optimizer=True)
-        losses = e.run(niter, lr, schedule, lr_min)
-        if self.verbose:
-            print(f'Global alignement - {niter} iterations, loss={losses[-1]:g}')
-        return float(losses[-1])
+        return self._run_and_report(niter, lr, schedule, lr_min)
