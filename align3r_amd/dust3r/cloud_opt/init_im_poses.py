@@ -1,14 +1,16 @@
 """MST initialisation of the global aligner, after dust3r/cloud_opt/init_im_poses.py:69-252.
 
-PARITY UNPINNED: the reference builds this step on third-party solvers that are not available here and whose
-results it never pins -- roma.rigid_points_registration (SVD Procrustes, :415-418) and cv2.solvePnPRansac with
-SQPNP (:442-482, stochastic).  This module restates the published algorithms (weighted Umeyama; PnP with known
-intrinsics as a closed-form start + robust Gauss-Newton on the reprojection error instead of RANSAC; both solved on the device by
-the kernels of csrc/init.hip -- no LAPACK, no host round trip per problem) and is validated
-by what it is for: the alignment loss after initialisation and the recovered geometry on synthetic scenes
-(tests/test_gpu_api.py).  The order of operations, the edge scores (commons.py:20-25), the spanning tree
-(scipy.sparse.csgraph), the Weiszfeld focal (post_process.py:36-60) and what gets written into the optimiser
-(init_from_pts3d :83-126) follow the reference.  It is a one-off O(E*P) host-orchestrated step, not the inner loop.
+The reference builds this step on third-party solvers that are not available here -- roma.rigid_points_registration (SVD
+Procrustes, :415-418) and cv2.solvePnPRansac with SQPNP (:442-482, stochastic).  This module restates the published algorithms
+(weighted Umeyama; PnP with known intrinsics as a closed-form start + robust Gauss-Newton on the reprojection error instead of
+RANSAC; both solved on the device by the kernels of csrc/init.hip -- no LAPACK, no host round trip per problem).
+PINNED against the reference's own code run on the CPU (tests/golden/mst.npz from make_goldens_mst.py, tests/test_gpu_mst_parity.py):
+the edge scores (commons.py:20-25), the spanning tree (scipy.sparse.csgraph) and the walk over it as the verbose lines print it,
+the Weiszfeld focals (post_process.py:36-60) with the stale-`i_j` quirk, the chain of registrations, and what init_from_pts3d
+(:83-126) writes into the optimiser -- with closed-form stand-ins for two roma functions in the fixture.  The PnP SOLVE stays
+UNPINNED (cv2's RANSAC is stochastic and absent; the fixture replaces it by a recorder) and is validated by what it is for: the
+alignment loss after initialisation and the recovered geometry on synthetic scenes (tests/test_gpu_api.py).
+It is a one-off O(E*P) host-orchestrated step, not the inner loop.
 """
 from __future__ import annotations
 
@@ -148,8 +150,10 @@ def estimate_focals(pts3d):
         return [f for k in range(0, B, 256) for f in estimate_focals(pts3d[k:k + 256])]
     dev = pts3d.device
     ys, xs = torch.meshgrid(torch.arange(H, device=dev), torch.arange(W, device=dev), indexing='ij')
-    pixels = torch.stack((xs - W / 2, ys - H / 2), -1).reshape(1, -1, 2).float()
-    p = pts3d.reshape(B, -1, 3)
+    # float64 throughout: a focal is one number per map, and an fp32 Weiszfeld iteration leaves it an ulp or two off the value the
+    # reference's arithmetic converges to (measured against its float64 run, tests/test_gpu_mst_parity.py); this path is the fallback
+    pixels = torch.stack((xs - W / 2, ys - H / 2), -1).reshape(1, -1, 2).double()
+    p = pts3d.reshape(B, -1, 3).double()
     xy_over_z = (p[..., :2] / p[..., 2:3]).nan_to_num(posinf=0, neginf=0)
     dot_xy_px = (xy_over_z * pixels).sum(-1)
     dot_xy_xy = xy_over_z.square().sum(-1)
@@ -301,6 +305,8 @@ def minimum_spanning_tree(imshapes, edges, pred_i, pred_j, conf_i, conf_j, im_co
         if im_focals[i] is None:
             im_focals[i] = edge_focal[last_k]      # the reference uses the PREVIOUS edge's map here (:199)
         if i in done:
+            if verbose:
+                print(f' init edge ({i},{j}*) {score=}')
             assert j not in done
             k = last_k = eidx[(i, j)]
             s, R, T = rigid_points_registration(pred_i[k], pts3d[i], conf_i[k])
@@ -310,6 +316,8 @@ def minimum_spanning_tree(imshapes, edges, pred_i, pred_j, conf_i, conf_j, im_co
             if has_im_poses and im_poses[i] is None:
                 im_poses[i] = sRT_to_4x4(1, R, T, device)
         elif j in done:
+            if verbose:
+                print(f' init edge ({i}*,{j}) {score=}')
             assert i not in done
             k = last_k = eidx[(i, j)]
             s, R, T = rigid_points_registration(pred_j[k], pts3d[j], conf_j[k])
@@ -432,11 +440,15 @@ def _mst_device(scene, niter_PnP=10):
         if im_focals[i] is None:
             im_focals[i] = edge_focal[last_k]      # the reference uses the PREVIOUS edge's map here (:199)
         if i in done:
+            if scene.verbose:
+                print(f' init edge ({i},{j}*) {score=}')
             assert j not in done
             k = last_k = eidx[(i, j)]
             steps.append((k, 0, i, j))
             done.add(j)
         elif j in done:
+            if scene.verbose:
+                print(f' init edge ({i}*,{j}) {score=}')
             assert i not in done
             k = last_k = eidx[(i, j)]
             steps.append((k, 1, j, i))
@@ -505,14 +517,29 @@ def _mst_device(scene, niter_PnP=10):
     if eng.flags['train_focals']:
         focals = eng.params['im_focals'].cpu().numpy().copy()
         if getattr(eng, 'shared_focal', False):
-            if im_focals[0] is not None:
-                focals[0] = scene.focal_break * float(np.log(im_focals[0]))
+            focals[0] = scene.focal_break * float(np.log(_shared_focal(im_focals)))
         else:
             for i in range(N):
                 if im_focals[i] is not None:
                     focals[i] = scene.focal_break * float(np.log(im_focals[i]))
         new['im_focals'] = torch.from_numpy(focals)
     eng.set_params(**new)
+    _state_written(scene)
+
+
+def _shared_focal(im_focals):
+    """The one focal of a shared_focal problem: the mean of the per-image estimates (cloud_opt_flow/init_im_poses.py:147-148)."""
+    if any(f is None for f in im_focals):      # an image that is no edge's first view and whose PnP failed: the reference's sum() raises too
+        raise ValueError('shared_focal: an image got no focal estimate')
+    return sum(im_focals) / len(im_focals)
+
+
+def _state_written(scene):
+    """The end of init_from_pts3d: the flow variant captures the depth maps for its prior BEFORE the loss is evaluated
+    (cloud_opt_flow/init_im_poses.py:149-154), then the verbose line."""
+    hook = getattr(scene, '_mst_state_written', None)
+    if hook is not None:
+        hook()
     if scene.verbose:
         print(' init loss =', float(scene()))
 
@@ -582,11 +609,10 @@ def init_minimum_spanning_tree(scene, init_priors=None, niter_PnP=10):
     for i in range(N):
         if im_focals[i] is not None and not known_focal[i] and not getattr(eng, 'shared_focal', False):
             focals[i] = scene.focal_break * float(np.log(im_focals[i]))
-    if getattr(eng, 'shared_focal', False) and eng.flags['train_focals'] and im_focals[0] is not None:
-        focals[0] = scene.focal_break * float(np.log(im_focals[0]))
+    if getattr(eng, 'shared_focal', False) and eng.flags['train_focals']:
+        focals[0] = scene.focal_break * float(np.log(_shared_focal(im_focals)))
     eng.set_params(pw_poses=pw, depth=depth, im_poses=poses, im_focals=focals)
-    if scene.verbose:
-        print(' init loss =', float(scene()))
+    _state_written(scene)
 
 
 # ------------------------------------------------------------------------------------------------ known poses

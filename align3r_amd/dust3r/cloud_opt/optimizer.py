@@ -5,8 +5,9 @@ constructor keywords, parameter names / parameterisation (pw_poses [E,8], im_dep
 im_poses [N,7], im_focals = focal_break*log f, im_pp), same random initial state for the same torch seed
 (parameters are drawn in the reference's order), same getters and the same optimisation loop
 (Adam betas (0.9, 0.9), cosine/linear schedule).  Gradients are analytic (the reference uses autograd).
-init='mst' is available but PARITY UNPINNED (init_im_poses.py of this package: roma / cv2 are absent).
-init='known_poses' and init='mst' on preset poses are available too (same caveat: the PnP is a linear stand-in for cv2's).
+init='mst' (also on preset poses) is pinned against the reference's own control flow -- tree, scores, focals, registrations and the
+written state (tests/golden/mst.npz, roma stand-ins in the fixture); its PnP solve and init='known_poses', whose only non-trivial
+step is that PnP, are a stand-in for cv2's RANSAC: unpinned, validated by purpose (init_im_poses.py of this package).
 allow_pw_adaptors=True (gradient + Adam on pw_adaptors in the kernels) and images of different shapes in one problem (per-edge
 lists, every map zero-filled to max_area like _ravel_hw) are supported and pinned against reference goldens (tests/golden/alignx.npz).
 """
@@ -429,14 +430,14 @@ class PointCloudOptimizer:
     __call__ = forward
 
     def _init_known_poses(self, niter_PnP):
-        from .init_im_poses import init_from_known_poses              # parity unpinned (see that module)
+        from .init_im_poses import init_from_known_poses              # PnP stand-in: parity unpinned (see that module)
         init_from_known_poses(self, niter_PnP=niter_PnP, min_conf_thr=self.min_conf_thr)
 
     def _init_from(self, init, init_priors, niter_PnP):
         if init is None:
             pass
         elif init in ('msp', 'mst'):
-            from .init_im_poses import init_minimum_spanning_tree       # parity unpinned (see that module)
+            from .init_im_poses import init_minimum_spanning_tree       # pinned except the PnP solve (see that module)
             init_minimum_spanning_tree(self, init_priors=init_priors, niter_PnP=niter_PnP)
         elif init == 'known_poses':
             self._init_known_poses(niter_PnP)

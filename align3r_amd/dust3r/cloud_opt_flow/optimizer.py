@@ -200,6 +200,11 @@ class PointCloudOptimizer(_Base):
                                    "torch.stack(None), optimizer.py:549)")
             e.set_depth_prior(float(self.depth_regularize_weight), dyn=torch.stack(self.dynamic_masks))
 
+    def _mst_state_written(self):
+        """Called by init='mst' once the state is written and before its verbose loss line (cloud_opt_flow/init_im_poses.py:149-150)."""
+        if self.n_imgs > 2:
+            self._set_init_depthmap()
+
     def get_init_depthmaps(self, raw=False):
         res = self.init_depthmap
         if not raw:
@@ -230,9 +235,7 @@ class PointCloudOptimizer(_Base):
     def compute_global_alignment(self, init=None, init_priors=None, niter_PnP=10, lr=0.01, niter=300, schedule='cosine',
                                  lr_min=1e-3, **kw):
         self._need_engine()
-        self._init_from(init, init_priors, niter_PnP)
-        if init in ('msp', 'mst') and self.n_imgs > 2:
-            self._set_init_depthmap()                                          # cloud_opt_flow/init_im_poses.py:149-150
+        self._init_from(init, init_priors, niter_PnP)            # init='mst' ends in _mst_state_written below
         if niter <= 0:
             return float('inf')
         self._check_depth_prior()

@@ -22,8 +22,9 @@ Harness-side patches (nothing in the reference tree is modified):
     stand-in providing ONLY the closed-form unit-quaternion(XYZW)->4x4 used by the inner loop
     (base_opt.py:188).  The fixtures' metadata records this.  Everything else in the aligner
     iteration -- forward, autograd, Adam, schedules -- is the reference's own code.
-    The MST/PnP initialisation (init_im_poses.py) needs roma's SVD registration and cv2's
-    RANSAC-PnP and is therefore NOT exercised: goldens start from a captured parameter state.
+    The MST initialisation (init_im_poses.py) needs roma's SVD registration and cv2's RANSAC-PnP and
+    is NOT exercised here: these goldens start from a captured parameter state.  make_goldens_mst.py
+    pins it (more roma stand-ins, fast_pnp replaced by a recorder); only the PnP solve stays unpinned.
 """
 from __future__ import annotations
 

@@ -200,7 +200,7 @@ def _geom_scene(N, H, W, seed=0):
 
 
 def test_mst_initialisation_recovers_geometry(model):
-    """init='mst' (parity unpinned: roma / cv2 absent) is validated by its purpose: a consistent scene must come out
+    """init='mst' by its purpose (its parity with the reference -- all but the PnP solve -- is test_gpu_mst_parity.py's): a consistent scene must come out
     with a small alignment loss, the true focal, and relative camera poses equal to the truth up to the global scale."""
     from dust3r.cloud_opt import global_aligner
     N, H, W = 4, 32, 48
@@ -278,7 +278,7 @@ def test_known_poses_initialisation(model):
 
 
 def test_mst_init_with_preset_poses(model):
-    """init='mst' after preset_pose (init_from_pts3d's nkp > 1 branch, init_im_poses.py:88-99; parity unpinned): the spanning
+    """init='mst' after preset_pose (init_from_pts3d's nkp > 1 branch, init_im_poses.py:88-99; pinned numerically by test_gpu_mst_parity.py's `preset2`), by purpose: the spanning
     tree's cameras and pointmaps are carried onto the preset poses by one similarity, the presets stay untouched, and the scene
     lands at the presets' metric scale (the generator's pointmaps are 0.7x metric)."""
     from dust3r.cloud_opt import global_aligner

@@ -2,8 +2,8 @@
 
 The pair forward is replaced by a synthetic, geometrically consistent pointmap generator (a TINY random-weight model cannot
 produce consistent geometry), so the test pins what the driver adds: clip cutting, the keyframe pass, `init_priors` chaining
-(every clip must land in the keyframes' world frame) and the output files.  MST init is parity-unpinned (roma / cv2 absent)
-and is validated by its purpose, as in test_gpu_api.py.
+(every clip must land in the keyframes' world frame) and the output files.  MST init is judged by its purpose here, as in test_gpu_api.py;
+its parity with the reference (both `init_priors` branches included, all but the PnP solve) is test_gpu_mst_parity.py's.
 """
 import os
 

@@ -348,7 +348,8 @@ def test_init_map_kernels():
 def test_mst_fast_path_matches_generic_path():
     """The device fast path of init='mst' (one image shape, predictions on the GPU: per-pixel passes as launches, pose algebra in
     numpy) against the generic torch implementation of the same steps on the same scene: same tree, same poses / focals / depths
-    up to fp32 rounding.  (Both are the parity-unpinned restatement of init_im_poses.py:69-252; this pins them to each other.)"""
+    up to fp32 rounding.  (Both restate init_im_poses.py:69-252; this pins them to each other at a size the reference fixture of test_gpu_mst_parity.py,
+    which pins each of them to the reference, does not reach.)"""
     import bench
     from align3r_amd.dust3r.cloud_opt import global_aligner
     from align3r_amd.dust3r.image_pairs import make_pairs
