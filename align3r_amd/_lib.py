@@ -190,6 +190,11 @@ SIGNATURES = {
     "a3r_align_shard_grad": (C.c_int, [c_void, c_void, C.c_size_t, c_void, c_void, c_void, c_void, c_void]),
     "a3r_align_shard_sum": (C.c_int, [c_void, c_void, C.c_int, C.c_size_t, c_void]),
     "a3r_align_shard_run_local": (C.c_int, [c_void, C.c_int, c_void, C.c_size_t, c_void, C.c_int, c_void]),
+    "a3r_align_scene_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "a3r_align_scene_points": (C.c_int, [c_void, c_void, c_void]),
+    "a3r_align_scene_count": (C.c_int, [c_void, c_void, C.c_float, c_void, c_void, C.c_size_t, c_void, C.POINTER(C.c_longlong), c_void]),
+    "a3r_align_scene_export": (C.c_int, [c_void, c_void, C.c_float, c_void, c_void, c_void, C.c_size_t, C.c_longlong, c_void, c_void, c_void,
+                                         C.POINTER(C.c_longlong), c_void]),
 }
 
 _lib = None

@@ -203,6 +203,61 @@ class _AlignEngineBase:
             check(self.lib.a3r_align_pose_matrices(self._states[0].handle, ptr(eM), ptr(iR), stream_ptr()), "a3r_align_pose_matrices")
         return eM, iR
 
+    # ------------------------------------------------------------------ scene out (csrc/scene.hip)
+    def points(self):
+        """World points [N,P,3] of the current state (depth_to_pts3d of the reference, optimizer.py:244-251); zeros at the padding
+        pixels of a mixed-shape scene.  The sharded engine reads replica 0 (the replicas are identical)."""
+        out = torch.empty(self.N, self.P, 3, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.lib.a3r_align_scene_points(self._states[0].handle, ptr(out), stream_ptr()), "a3r_align_scene_points")
+        return out
+
+    def _scene_inputs(self, conf, dyn, rgb):
+        N, P, dev = self.N, self.P, self.device
+        conf = torch.as_tensor(conf).to(dev, torch.float32).reshape(N, P).contiguous()
+        if dyn is not None:
+            dyn = torch.as_tensor(dyn).reshape(N, P).to(dev).ne(0).to(torch.uint8).contiguous()
+        if rgb is not None:
+            rgb = torch.as_tensor(rgb)
+            if rgb.dtype != torch.uint8:
+                raise TypeError(f"export_points: rgb must be uint8, got {rgb.dtype}")
+            rgb = rgb.to(dev).reshape(N, P, 3).contiguous()
+        ws = torch.empty(int(self.lib.a3r_align_scene_workspace_bytes(N, P)), dtype=torch.uint8, device=dev)
+        return conf, dyn, rgb, ws
+
+    def count_points(self, conf, thr, dyn=None):
+        """(kept pixels of the scene, per-image counts [N] int32 on the device) under the rule of export_points."""
+        conf, dyn, _, ws = self._scene_inputs(conf, dyn, None)
+        counts = torch.empty(self.N, dtype=torch.int32, device=self.device)
+        total = C.c_longlong(0)
+        with torch.cuda.device(self.device):
+            check(self.lib.a3r_align_scene_count(self._states[0].handle, ptr(conf), float(thr), ptr(dyn), ptr(ws), ws.numel(), ptr(counts),
+                                                 C.byref(total), stream_ptr()), "a3r_align_scene_count")
+        return int(total.value), counts
+
+    def export_points(self, conf, thr, dyn=None, rgb=None, with_index=False):
+        """The scene compacted to the pixels with conf > thr (strict), dyn == 0 and finite coordinates, image-major and row-major:
+        dict(xyz [M,3] float32, rgb [M,3] uint8 when `rgb` [N,P,3] uint8 is given, index [M] int32 = n * P + p with with_index).
+        conf [N,P] (padding pixels of smaller images are never kept whatever it holds there); dyn [N,P], non-zero = dropped."""
+        conf, dyn, rgb, ws = self._scene_inputs(conf, dyn, rgb)
+        h, dev = self._states[0].handle, self.device
+        total = C.c_longlong(0)
+        with torch.cuda.device(dev):
+            check(self.lib.a3r_align_scene_count(h, ptr(conf), float(thr), ptr(dyn), ptr(ws), ws.numel(), None, C.byref(total), stream_ptr()),
+                  "a3r_align_scene_count")
+            M = int(total.value)
+            out = dict(xyz=torch.empty(M, 3, dtype=torch.float32, device=dev))
+            if rgb is not None:
+                out["rgb"] = torch.empty(M, 3, dtype=torch.uint8, device=dev)
+            if with_index:
+                out["index"] = torch.empty(M, dtype=torch.int32, device=dev)
+            written = C.c_longlong(0)
+            check(self.lib.a3r_align_scene_export(h, ptr(conf), float(thr), ptr(dyn), ptr(rgb), ptr(ws), ws.numel(), M, ptr(out["xyz"]),
+                                                  ptr(out.get("rgb")), ptr(out.get("index")), C.byref(written), stream_ptr()),
+                  "a3r_align_scene_export")
+        assert written.value == M
+        return out
+
 
 class AlignEngine(_AlignEngineBase):
     def __init__(self, ei, ej, pred_i, pred_j, w_i, w_j, imshapes, mono=None, base_scale=0.5, pw_break=20.0,
@@ -370,7 +425,7 @@ class ShardedAlignEngine(_AlignEngineBase):
     with group.  The observations are either the whole graph's [E, ...] (each shard takes a view of its rows) or, with group,
     this rank's rows only [e1 - e0, ...] (a rank's inference output is its shard).  Limits: plain cloud_opt only (no flow
     variant, no depth prior); the initial state comes through set_params.  Same surface as AlignEngine: params, set_params,
-    loss, loss_grad, step, run, steps_done, trainable, pose_matrices."""
+    loss, loss_grad, step, run, steps_done, trainable, pose_matrices, points, export_points (replica 0)."""
 
     def __init__(self, ei, ej, pred_i, pred_j, w_i, w_j, imshapes, mono=None, base_scale=0.5, pw_break=20.0, focal_break=20.0,
                  norm_pw_scale=True, dist="l1", train_poses=True, train_focals=True, train_pp=False, train_adaptors=False,

@@ -16,6 +16,7 @@
 //     adds in a fixed order: results are bitwise reproducible (no float atomics).
 //   * the pose / focal / scale parameters (a few KB) get their chain rule + Adam in two small kernels.
 #include "common.h"
+#include "scene.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -1945,3 +1946,18 @@ extern "C" int a3r_align_shard_run_local(const a3r_align_t* handles_host, int K,
     }
     return A3R_OK;
 }
+
+// ---- scene out (scene.hip) -------------------------------------------------------------------------------------
+// The handle side of a3r_align_scene_*: the transforms are rebuilt by the prep kernel exactly as for a3r_align_pose_matrices, so
+// the export decodes poses, focals, principal points and shifts through build_transforms and nothing else.
+namespace a3r {
+int align_scene_view(a3r_align_t a, hipStream_t st, SceneView* v, const char* who) {
+    A3R_CHECK_ARG(a, "%s: null handle", who);
+    a->dirty = true;
+    refresh_if_dirty(a, st);
+    const AlignDev& d = a->d;
+    v->N = d.N; v->P = d.P;
+    v->depth = d.depth; v->mono = d.mono; v->img_xf = d.img_xf; v->imw = d.imw; v->imarea = d.imarea;
+    return A3R_OK;
+}
+}  // namespace a3r

@@ -1,0 +1,354 @@
+// Scene out for gfx950: the aligned scene of an aligner handle as world points, dense ([N,P,3]) or compacted to the pixels a
+// confidence threshold and a dynamic mask keep (what get_3D_model_from_scene of the reference's tool/demo.py builds on the host
+// from get_pts3d() and get_masks()).
+//
+//   world = R_n * (d (x - ppx) / f, d (y - ppy) / f, d) + t_n,   d = exp(log_depth)  |  mono * exp(scalemap) + shift
+//
+// with R, t, f, pp, shift read from the handle's img_xf rows (build_transforms of align.hip: the decoding the iteration uses) and
+// the arithmetic of align_main_kernel's pixel_forward.  Streaming kernels, HBM-bound:
+//   * a workgroup owns SCHUNK = 1024 consecutive pixels of one image, a thread 4 CONSECUTIVE pixels (16-byte loads when P % 4 == 0
+//     and the buffers are 16-byte aligned, scalar loads otherwise);
+//   * compaction in two passes, no atomics: pass 1 counts the kept pixels of every chunk (wave64 ballots + popcounts), one small
+//     kernel turns the N * nchunks counts into exclusive offsets, pass 2 recomputes the points and places them.  A kept pixel's
+//     position is offset[chunk] + (kept pixels of lower waves) + (kept pixels of lower lanes) + (kept among the thread's own
+//     earlier pixels): image-major, row-major, a function of the inputs alone.
+//   * pass 2 stages a workgroup's points in LDS (its output range is contiguous) and writes them with consecutive lanes on
+//     consecutive addresses.
+#include "common.h"
+#include "scene.h"
+
+namespace a3r {
+
+constexpr int SPX = 4;                  // consecutive pixels per thread
+constexpr int STPB = 256;
+constexpr int SCHUNK = SPX * STPB;      // pixels per workgroup
+constexpr int SCAN_TPB = 1024;
+
+struct SceneCam {
+    float R[9], T[3], inv_f, ppx, ppy, shift;
+    int W, area;
+};
+
+// wave-uniform reads (noalias tables, uniform index): scalar loads
+__device__ __forceinline__ SceneCam load_cam(const float* __restrict__ img_xf, const int* __restrict__ imw, const int* __restrict__ imarea, int n) {
+    SceneCam c;
+    const float* ix = img_xf + n * 16;
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        c.R[r * 3 + 0] = ix[r * 4 + 0]; c.R[r * 3 + 1] = ix[r * 4 + 1]; c.R[r * 3 + 2] = ix[r * 4 + 2];
+        c.T[r] = ix[r * 4 + 3];
+    }
+    c.inv_f = 1.f / ix[12]; c.ppx = ix[13]; c.ppy = ix[14]; c.shift = ix[15];
+    c.W = imw[n]; c.area = imarea[n];
+    return c;
+}
+
+// world point of pixel (x, y) from the raw depth parameter (align_main_kernel: pixel_forward, then R * rel + T)
+template <bool MONO>
+__device__ __forceinline__ void scene_point(const SceneCam& c, int x, int y, float rawv, float monov, float* w) {
+    const float dep = MONO ? monov * expf(rawv) + c.shift : expf(rawv);
+    const float r0 = dep * ((float)x - c.ppx) * c.inv_f;
+    const float r1 = dep * ((float)y - c.ppy) * c.inv_f;
+#pragma unroll
+    for (int r = 0; r < 3; r++) w[r] = c.R[r * 3] * r0 + c.R[r * 3 + 1] * r1 + c.R[r * 3 + 2] * dep + c.T[r];
+}
+
+// the thread's 4 raw depth parameters (and mono values); pixels at and beyond P read as 0
+template <bool MONO, bool VEC>
+__device__ __forceinline__ void load_depth4(const SceneView& v, int n, int p0, float* raw, float* mono) {
+    const size_t base = (size_t)n * v.P;
+    if (VEC) {                      // P % 4 == 0 and p0 % 4 == 0: the four pixels are inside P together
+        f32x4 r4 = {0.f, 0.f, 0.f, 0.f}, m4 = {0.f, 0.f, 0.f, 0.f};
+        if (p0 < v.P) {
+            r4 = *reinterpret_cast<const f32x4*>(v.depth + base + p0);
+            if (MONO) m4 = *reinterpret_cast<const f32x4*>(v.mono + base + p0);
+        }
+        raw[0] = r4.x; raw[1] = r4.y; raw[2] = r4.z; raw[3] = r4.w;
+        mono[0] = m4.x; mono[1] = m4.y; mono[2] = m4.z; mono[3] = m4.w;
+    } else {
+#pragma unroll
+        for (int i = 0; i < SPX; i++) {
+            const bool in = p0 + i < v.P;
+            raw[i] = in ? v.depth[base + p0 + i] : 0.f;
+            mono[i] = (MONO && in) ? v.mono[base + p0 + i] : 0.f;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------- dense
+// grid (nchunks, N).  out[n, p, :] for every p < P; zeros at the padding pixels p >= h_n * w_n of a mixed-shape scene.
+template <bool MONO, bool VEC>
+__global__ __launch_bounds__(STPB) void scene_points_kernel(SceneView v, float* __restrict__ out, const float* __restrict__ img_xf,
+                                                           const int* __restrict__ imw, const int* __restrict__ imarea) {
+    const int n = blockIdx.y, p0 = blockIdx.x * SCHUNK + threadIdx.x * SPX;
+    if (p0 >= v.P) return;
+    const SceneCam c = load_cam(img_xf, imw, imarea, n);
+    float raw[SPX], mono[SPX], w[SPX][3];
+    load_depth4<MONO, VEC>(v, n, p0, raw, mono);
+    int y = p0 / c.W, x = p0 - y * c.W;
+#pragma unroll
+    for (int i = 0; i < SPX; i++) {
+        scene_point<MONO>(c, x, y, raw[i], mono[i], w[i]);
+        if (p0 + i >= c.area) w[i][0] = w[i][1] = w[i][2] = 0.f;
+        if (++x == c.W) { x = 0; y++; }
+    }
+    float* o = out + ((size_t)n * v.P + p0) * 3;
+    if (VEC) {                      // 48 contiguous bytes, 16-byte aligned
+        f32x4* o4 = reinterpret_cast<f32x4*>(o);
+        o4[0] = f32x4{w[0][0], w[0][1], w[0][2], w[1][0]};
+        o4[1] = f32x4{w[1][1], w[1][2], w[2][0], w[2][1]};
+        o4[2] = f32x4{w[2][2], w[3][0], w[3][1], w[3][2]};
+    } else {
+#pragma unroll
+        for (int i = 0; i < SPX; i++)
+            if (p0 + i < v.P) { o[i * 3 + 0] = w[i][0]; o[i * 3 + 1] = w[i][1]; o[i * 3 + 2] = w[i][2]; }
+    }
+}
+
+// ------------------------------------------------------------------------------------------- compaction
+struct SceneSel {
+    const float* conf;              // [N, P]
+    const unsigned char* dyn;       // [N, P] or null
+    const unsigned char* rgb;       // [N, P, 3] or null (pass 2)
+    float thr;
+    int* offsets;                   // [N * nchunks + 1]: pass 1 writes the chunk counts, the scan turns them into offsets
+    float* out_xyz;                 // pass 2
+    unsigned char* out_rgb;
+    int* out_index;
+};
+
+// grid (nchunks, N).  WRITE = false: offsets[chunk] = kept pixels of the chunk.  WRITE = true: the kept pixels go to
+// offsets[chunk] + (their rank inside the chunk).
+template <bool MONO, bool VEC, bool WRITE>
+__global__ __launch_bounds__(STPB) void scene_compact_kernel(SceneView v, SceneSel s, const float* __restrict__ img_xf,
+                                                            const int* __restrict__ imw, const int* __restrict__ imarea) {
+    __shared__ int wave_total[STPB / 64];
+    __shared__ float st_xyz[WRITE ? SCHUNK * 3 : 1];
+    __shared__ int st_index[WRITE ? SCHUNK : 1];
+    __shared__ unsigned char st_rgb[WRITE ? SCHUNK * 3 : 4];
+    const int n = blockIdx.y, tid = threadIdx.x, wave = tid >> 6;
+    const int nchunks = gridDim.x, p0 = blockIdx.x * SCHUNK + tid * SPX;
+    const SceneCam c = load_cam(img_xf, imw, imarea, n);
+    const size_t base = (size_t)n * v.P;
+    float raw[SPX], mono[SPX], cf[SPX], w[SPX][3];
+    unsigned dy[SPX];
+    load_depth4<MONO, VEC>(v, n, p0, raw, mono);
+    if (VEC) {
+        f32x4 c4 = {0.f, 0.f, 0.f, 0.f};
+        unsigned d4 = 0;
+        if (p0 < v.P) {
+            c4 = *reinterpret_cast<const f32x4*>(s.conf + base + p0);
+            if (s.dyn) d4 = *reinterpret_cast<const unsigned*>(s.dyn + base + p0);
+        }
+        cf[0] = c4.x; cf[1] = c4.y; cf[2] = c4.z; cf[3] = c4.w;
+#pragma unroll
+        for (int i = 0; i < SPX; i++) dy[i] = (d4 >> (8 * i)) & 0xffu;
+    } else {
+#pragma unroll
+        for (int i = 0; i < SPX; i++) {
+            const bool in = p0 + i < v.P;
+            cf[i] = in ? s.conf[base + p0 + i] : 0.f;
+            dy[i] = (in && s.dyn) ? s.dyn[base + p0 + i] : 0u;
+        }
+    }
+    // the kept rule: inside the image, confidence strictly above the threshold, not dynamic, all three coordinates finite
+    bool keep[SPX];
+    int y = p0 < v.P ? p0 / c.W : 0, x = p0 - y * c.W;
+#pragma unroll
+    for (int i = 0; i < SPX; i++) {
+        scene_point<MONO>(c, x, y, raw[i], mono[i], w[i]);
+        keep[i] = p0 + i < c.area && cf[i] > s.thr && dy[i] == 0u &&
+                  __builtin_isfinite(w[i][0]) && __builtin_isfinite(w[i][1]) && __builtin_isfinite(w[i][2]);
+        if (++x == c.W) { x = 0; y++; }
+    }
+    // rank inside the wave: the threads own consecutive pixel quads, so the order is (lane, i)
+    int below = 0, in_wave = 0, mine = 0;
+#pragma unroll
+    for (int i = 0; i < SPX; i++) {
+        const unsigned long long b = __ballot(keep[i]);
+        below += __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+        in_wave += __popcll(b);
+    }
+    if ((tid & 63) == 0) wave_total[wave] = in_wave;
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int k = 0; k < STPB / 64; k++) {
+        const int t = wave_total[k];
+        if (k < wave) before += t;
+        total += t;
+    }
+    if (!WRITE) {
+        if (tid == 0) s.offsets[n * nchunks + blockIdx.x] = total;
+        return;
+    }
+    if (total == 0) return;         // workgroup-uniform
+    unsigned c3[3] = {0u, 0u, 0u};
+    const bool any = keep[0] || keep[1] || keep[2] || keep[3];
+    if (s.rgb && any) {
+        const unsigned char* src = s.rgb + (base + p0) * 3;
+        if (VEC) {                  // 12 contiguous bytes, 4-byte aligned
+            const unsigned* s4 = reinterpret_cast<const unsigned*>(src);
+            c3[0] = s4[0]; c3[1] = s4[1]; c3[2] = s4[2];
+        } else {
+#pragma unroll
+            for (int k = 0; k < SPX * 3; k++)
+                if (p0 + k / 3 < v.P) c3[k >> 2] |= (unsigned)src[k] << (8 * (k & 3));
+        }
+    }
+    int l = before + below;
+#pragma unroll
+    for (int i = 0; i < SPX; i++) {
+        if (!keep[i]) continue;
+        st_xyz[l * 3 + 0] = w[i][0]; st_xyz[l * 3 + 1] = w[i][1]; st_xyz[l * 3 + 2] = w[i][2];
+        st_index[l] = (int)(base + p0 + i);
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const int byte = i * 3 + k;
+            st_rgb[l * 3 + k] = (unsigned char)(c3[byte >> 2] >> (8 * (byte & 3)));
+        }
+        l++;
+    }
+    __syncthreads();
+    const int slot = n * nchunks + blockIdx.x;
+    const size_t o = (size_t)s.offsets[slot];
+    // pass 1 saw the same inputs, so this is its count; should the caller have rewritten them in between, stay inside the range
+    total = min(total, s.offsets[slot + 1] - s.offsets[slot]);
+    for (int k = tid; k < total * 3; k += STPB) s.out_xyz[o * 3 + k] = st_xyz[k];
+    if (s.out_index)
+        for (int k = tid; k < total; k += STPB) s.out_index[o + k] = st_index[k];
+    if (s.out_rgb)
+        for (int k = tid; k < total * 3; k += STPB) s.out_rgb[o * 3 + k] = st_rgb[k];
+}
+
+// One workgroup: cnt[0 .. T) (chunk counts) -> exclusive offsets in place, cnt[T] = total; per-image counts when asked for.
+// A thread owns a contiguous segment; the SCAN_TPB segment sums are scanned through LDS.
+__global__ __launch_bounds__(SCAN_TPB) void scene_scan_kernel(int* cnt, int T, int N, int nchunks, int* counts_img) {
+    __shared__ int sh[2][SCAN_TPB];
+    const int tid = threadIdx.x;
+    const int seg = (T + SCAN_TPB - 1) / SCAN_TPB;
+    const int lo = min(tid * seg, T), hi = min(lo + seg, T);
+    int sum = 0;
+    for (int k = lo; k < hi; k++) sum += cnt[k];
+    int cur = 0;
+    sh[0][tid] = sum;
+    __syncthreads();
+    for (int off = 1; off < SCAN_TPB; off <<= 1) {       // inclusive Hillis-Steele scan, double-buffered
+        int val = sh[cur][tid];
+        if (tid >= off) val += sh[cur][tid - off];
+        sh[cur ^ 1][tid] = val;
+        cur ^= 1;
+        __syncthreads();
+    }
+    int run = sh[cur][tid] - sum;
+    for (int k = lo; k < hi; k++) {
+        const int t = cnt[k];
+        cnt[k] = run;
+        run += t;
+    }
+    if (tid == SCAN_TPB - 1) cnt[T] = sh[cur][tid];
+    __syncthreads();                                     // the offsets are read back by other threads below
+    if (counts_img)
+        for (int n = tid; n < N; n += SCAN_TPB) counts_img[n] = cnt[(n + 1) * nchunks] - cnt[n * nchunks];
+}
+
+static int scene_nchunks(int P) { return (P + SCHUNK - 1) / SCHUNK; }
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace a3r
+
+// =============================================================================================== host
+using namespace a3r;
+
+extern "C" size_t a3r_align_scene_workspace_bytes(int N, int P) {
+    if (N <= 0 || P <= 0) return 0;
+    return align_up(((size_t)N * scene_nchunks(P) + 1) * sizeof(int), 256);
+}
+
+extern "C" int a3r_align_scene_points(a3r_align_t a, float* out_xyz, void* stream) {
+    A3R_CHECK_ARG(out_xyz, "a3r_align_scene_points: null output");
+    hipStream_t st = as_stream(stream);
+    SceneView v;
+    if (int rc = align_scene_view(a, st, &v, "a3r_align_scene_points")) return rc;
+    const bool vec = v.P % 4 == 0 && aligned16(v.depth) && aligned16(out_xyz) && (!v.mono || aligned16(v.mono));
+    const dim3 grid(scene_nchunks(v.P), v.N), block(STPB);
+#define A3R_SCENE_LAUNCH(MONOV, VECV) \
+    hipLaunchKernelGGL((scene_points_kernel<MONOV, VECV>), grid, block, 0, st, v, out_xyz, v.img_xf, v.imw, v.imarea)
+    if (v.mono) { if (vec) A3R_SCENE_LAUNCH(true, true); else A3R_SCENE_LAUNCH(true, false); }
+    else        { if (vec) A3R_SCENE_LAUNCH(false, true); else A3R_SCENE_LAUNCH(false, false); }
+#undef A3R_SCENE_LAUNCH
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+template <bool WRITE>
+static void launch_compact(const SceneView& v, const SceneSel& s, bool vec, hipStream_t st) {
+    const dim3 grid(scene_nchunks(v.P), v.N), block(STPB);
+#define A3R_SCENE_LAUNCH(MONOV, VECV) \
+    hipLaunchKernelGGL((scene_compact_kernel<MONOV, VECV, WRITE>), grid, block, 0, st, v, s, v.img_xf, v.imw, v.imarea)
+    if (v.mono) { if (vec) A3R_SCENE_LAUNCH(true, true); else A3R_SCENE_LAUNCH(true, false); }
+    else        { if (vec) A3R_SCENE_LAUNCH(false, true); else A3R_SCENE_LAUNCH(false, false); }
+#undef A3R_SCENE_LAUNCH
+}
+
+// pass 1 + scan; the kept count of the whole scene comes back to the host (synchronises the stream)
+static int scene_count(a3r_align_t a, const char* who, const float* conf, float thr, const uint8_t* dyn, const uint8_t* rgb,
+                       void* workspace, size_t workspace_bytes, int* counts_dev, hipStream_t st, SceneView* v, SceneSel* s, bool* vec,
+                       long long* total) {
+    A3R_CHECK_ARG(conf, "%s: null confidence buffer", who);
+    if (int rc = align_scene_view(a, st, v, who)) return rc;
+    A3R_CHECK_ARG((size_t)v->N * v->P < (1ull << 31), "%s: N * P = %zu does not fit the int32 point index", who, (size_t)v->N * v->P);
+    const size_t need = a3r_align_scene_workspace_bytes(v->N, v->P);
+    A3R_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
+    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "%s: workspace must be 4-byte aligned", who);
+    *vec = v->P % 4 == 0 && aligned16(v->depth) && aligned16(conf) && (!v->mono || aligned16(v->mono)) && (!dyn || aligned16(dyn)) &&
+           (!rgb || aligned16(rgb));
+    s->conf = conf; s->dyn = dyn; s->rgb = rgb; s->thr = thr; s->offsets = static_cast<int*>(workspace);
+    s->out_xyz = nullptr; s->out_rgb = nullptr; s->out_index = nullptr;
+    const int nch = scene_nchunks(v->P), T = v->N * nch;
+    launch_compact<false>(*v, *s, *vec, st);
+    hipLaunchKernelGGL(scene_scan_kernel, dim3(1), dim3(SCAN_TPB), 0, st, s->offsets, T, v->N, nch, counts_dev);
+    A3R_LAUNCH_CHECK();
+    int total_i = 0;
+    A3R_HIP(hipMemcpyAsync(&total_i, s->offsets + T, sizeof(int), hipMemcpyDeviceToHost, st));
+    A3R_HIP(hipStreamSynchronize(st));
+    *total = total_i;
+    return A3R_OK;
+}
+
+extern "C" int a3r_align_scene_count(a3r_align_t a, const float* conf, float thr, const uint8_t* dyn, void* workspace,
+                                     size_t workspace_bytes, int* counts_dev, long long* total_host, void* stream) {
+    A3R_CHECK_ARG(total_host, "a3r_align_scene_count: null total_host");
+    SceneView v;
+    SceneSel s;
+    bool vec;
+    return scene_count(a, "a3r_align_scene_count", conf, thr, dyn, nullptr, workspace, workspace_bytes, counts_dev, as_stream(stream), &v, &s,
+                       &vec, total_host);
+}
+
+extern "C" int a3r_align_scene_export(a3r_align_t a, const float* conf, float thr, const uint8_t* dyn, const uint8_t* rgb, void* workspace,
+                                      size_t workspace_bytes, long long capacity, float* out_xyz, uint8_t* out_rgb, int* out_index,
+                                      long long* n_written_host, void* stream) {
+    A3R_CHECK_ARG(n_written_host, "a3r_align_scene_export: null n_written_host");
+    A3R_CHECK_ARG(capacity >= 0, "a3r_align_scene_export: negative capacity");
+    A3R_CHECK_ARG(out_xyz || capacity == 0, "a3r_align_scene_export: null out_xyz (only a capacity of 0 needs no buffer)");
+    A3R_CHECK_ARG(!out_rgb || rgb, "a3r_align_scene_export: out_rgb needs the rgb source buffer");
+    hipStream_t st = as_stream(stream);
+    SceneView v;
+    SceneSel s;
+    bool vec;
+    long long total = 0;
+    *n_written_host = 0;
+    // the count is always taken afresh: the offsets in the workspace then belong to exactly these inputs
+    if (int rc = scene_count(a, "a3r_align_scene_export", conf, thr, dyn, out_rgb ? rgb : nullptr, workspace, workspace_bytes, nullptr, st, &v,
+                             &s, &vec, &total))
+        return rc;
+    *n_written_host = total;
+    A3R_CHECK_ARG(total <= capacity, "a3r_align_scene_export: capacity %lld is smaller than the %lld kept points (nothing was written)",
+                  capacity, total);
+    if (total == 0) return A3R_OK;
+    s.out_xyz = out_xyz; s.out_rgb = out_rgb; s.out_index = out_index;
+    launch_compact<true>(v, s, vec, st);
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}

@@ -360,6 +360,39 @@ class PointCloudOptimizer:
     def get_masks(self):
         return [(conf > self.min_conf_thr) for conf in self.im_conf]
 
+    # ------------------------------------------------------------------ scene out (tool/demo.py: get_3D_model_from_scene)
+    def _mask_confidences(self):
+        """The confidence maps get_masks() thresholds."""
+        return self.im_conf
+
+    def get_pointcloud(self, min_conf_thr=None, mask_dynamic=False, with_index=False):
+        """The aligned scene as one compacted point cloud, computed on the device by the aligner handle (csrc/scene.hip): dict of
+        device tensors xyz [M,3] float32, rgb [M,3] uint8 (when the scene holds its frames) and, with_index, index [M] int32 =
+        n * max_area + p.  Kept: conf > min_conf_thr (as given; None = self.min_conf_thr, the pixels of get_masks()), finite
+        coordinates and, with mask_dynamic, outside the scene's dynamic masks.  Image-major, row-major order."""
+        e = self._need_engine()
+        N, P = self.n_imgs, self.max_area
+        thr = self.min_conf_thr if min_conf_thr is None else min_conf_thr
+        conf = torch.stack([_ravel_hw(c.to(self.device).float()[..., None], P)[:, 0] for c in self._mask_confidences()])
+        dyn = None
+        if mask_dynamic:
+            masks = getattr(self, 'dynamic_masks', None)
+            if masks is None:
+                raise RuntimeError('get_pointcloud(mask_dynamic=True): this scene has no dynamic masks')
+            dyn = torch.stack([_ravel_hw(torch.as_tensor(m).to(self.device).to(torch.uint8)[..., None], P)[:, 0] for m in masks])
+        rgb = None
+        if self.imgs is not None:
+            rgb = torch.stack([_ravel_hw(torch.from_numpy(np.clip(np.rint(255.0 * np.asarray(im)), 0, 255).astype(np.uint8)), P)
+                               for im in self.imgs])
+        return e.export_points(conf, float(thr), dyn=dyn, rgb=rgb, with_index=with_index)
+
+    def save_pointcloud(self, path, **kw):
+        """get_pointcloud(**kw) written as a binary little-endian PLY (tool/pointcloud.py); returns the dict."""
+        from ...tool.pointcloud import write_ply
+        pc = self.get_pointcloud(**kw)
+        write_ply(path, pc['xyz'].cpu().numpy(), pc['rgb'].cpu().numpy() if 'rgb' in pc else None)
+        return pc
+
     def clean_pointcloud(self, **kw):
         """base_opt.py:268-278: lower the confidence of points that another, more confident view sees through."""
         cams = inv_rigid(self.get_im_poses())

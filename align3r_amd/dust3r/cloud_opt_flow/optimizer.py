@@ -186,6 +186,9 @@ class PointCloudOptimizer(_Base):
         src = self.init_conf_maps if self.thr_for_init_conf else self.im_conf
         return [(conf > self.min_conf_thr) for conf in src]
 
+    def _mask_confidences(self):
+        return self.init_conf_maps if self.thr_for_init_conf else self.im_conf
+
     @property
     def flow_loss_flag(self):
         return self._need_engine().flow_dropped

@@ -87,11 +87,14 @@ def save_frame_arrays(arrays, folder, pattern, start=0):
 
 # ------------------------------------------------------------------------------------------- the driver
 def hierarchical_alignment(imgs, model, device, *, clip_size=50, niter=300, schedule='linear', lr=0.05, min_conf_thr=3,
-                           if_use_mono=False, mono_depths=(), batch_size=1, clamp_conf=True, verbose=False, output_dir=None):
+                           if_use_mono=False, mono_depths=(), batch_size=1, clamp_conf=True, verbose=False, output_dir=None,
+                           pointcloud_collector=None):
     """Keyframe pass + per-clip passes (depth_test.py:636-676).  `imgs`: view dicts (load_images).  Returns a dict with the
     per-frame lists `depths`, `confs`, `poses` ([4,4] cam-to-world in the keyframes' frame), `focals`, `intrinsics`, plus
     `keyframes_id`, `clip_size` and the keyframe scene's own results; writes pred_traj.txt / pred_intrinsics.txt /
-    frame_XXXX.npy / conf_X.npy under `output_dir` when given (demo.py:225-243)."""
+    frame_XXXX.npy / conf_X.npy under `output_dir` when given (demo.py:225-243).
+    `pointcloud_collector`: a list that receives, in clip order, every clip scene's get_pointcloud() as host arrays
+    dict(xyz, rgb | None); off by default."""
     from ..dust3r.cloud_opt import GlobalAlignerMode, global_aligner
     from ..dust3r.inference import inference
 
@@ -128,6 +131,9 @@ def hierarchical_alignment(imgs, model, device, *, clip_size=50, niter=300, sche
         res['poses'] += list(scene.get_im_poses().detach().cpu().numpy())
         res['focals'] += scene.get_focals().detach().cpu().numpy().reshape(-1).tolist()
         res['intrinsics'] += list(scene.get_intrinsics().detach().cpu().numpy())
+        if pointcloud_collector is not None:
+            pc = scene.get_pointcloud()
+            pointcloud_collector.append(dict(xyz=pc['xyz'].cpu().numpy(), rgb=pc['rgb'].cpu().numpy() if 'rgb' in pc else None))
     if output_dir is not None:
         os.makedirs(output_dir, exist_ok=True)
         save_trajectory_tum_format(get_tum_poses(res['poses']), os.path.join(output_dir, 'pred_traj.txt'))

@@ -4,9 +4,11 @@
 The flow of the reference's tool/demo.py and tool/depth_test.py through this package only:
     load_images (N3)  ->  make_pairs  ->  inference (HIP pair forward)  ->  global_aligner / hierarchical_alignment (HIP aligner, N2)
     ->  pred_traj.txt, pred_intrinsics.txt, frame_XXXX.npy, conf_X.npy   (+ depth metrics when ground truth is given)
+    ->  --pointcloud PATH: the aligned scene as a binary PLY (points above --min-conf-thr, compacted on the device)
 
     python -m align3r_amd.tool.run_clip --images DIR --weights CKPT.pth --out OUT [--size 512] [--scene-graph swin-3-noncyclic]
            [--hierarchical --clip-size 50] [--niter 300] [--schedule linear] [--lr 0.01] [--traj-format custom] [--gt-depth DIR]
+           [--pointcloud scene.ply]
 """
 from __future__ import annotations
 
@@ -40,6 +42,8 @@ def parse(argv=None):
     ap.add_argument("--gt-depth", default=None, help="folder of per-frame ground-truth depth .npy (same order) -> AbsRel etc.")
     ap.add_argument("--depth-max", type=float, default=70.0)
     ap.add_argument("--gt-traj", default=None, help="ground-truth camera trajectory, TUM file `t x y z qx qy qz qw` (same frames) -> ATE / RPE")
+    ap.add_argument("--pointcloud", default=None, metavar="PATH",
+                    help="write the aligned scene as a binary PLY (with --hierarchical: every clip's points, appended in clip order)")
     ap.add_argument("--quiet", action="store_true")
     return ap.parse_args(argv)
 
@@ -53,16 +57,21 @@ def main(argv=None):
     from ..dust3r.utils.image_pose import load_images
     from . import hierarchical as hz
     from .depth_metrics import evaluate_depth
+    from .pointcloud import write_ply_parts
 
     verbose = not a.quiet
     model = AsymmetricCroCo3DStereo.from_pretrained(a.weights).to(a.device)
     imgs, _ = load_images(a.images, a.size, verbose=verbose, traj_format=a.traj_format, start=a.start, interval=a.interval,
                           depth_prior_name=a.depth_prior_name, dynamic_mask_root=os.path.join(a.out, "__no_masks__"))
     os.makedirs(a.out, exist_ok=True)
+    clouds, n_points = ([] if a.pointcloud else None), None
     if a.hierarchical and len(imgs) >= 3:
         res = hz.hierarchical_alignment(imgs, model, a.device, clip_size=a.clip_size, niter=a.niter, schedule=a.schedule, lr=a.lr,
-                                        min_conf_thr=a.min_conf_thr, batch_size=a.batch_size, verbose=verbose, output_dir=a.out)
+                                        min_conf_thr=a.min_conf_thr, batch_size=a.batch_size, verbose=verbose, output_dir=a.out,
+                                        pointcloud_collector=clouds)
         depths = res["depths"]
+        if a.pointcloud:
+            n_points = write_ply_parts(a.pointcloud, [(c["xyz"], c["rgb"]) for c in clouds])
     else:
         if len(imgs) == 1:
             imgs = [imgs[0], dict(imgs[0], idx=1)]
@@ -77,6 +86,10 @@ def main(argv=None):
         hz.save_intrinsics(scene.get_intrinsics(), os.path.join(a.out, "pred_intrinsics.txt"))
         hz.save_frame_arrays(depths, a.out, "frame_{:04d}.npy")
         hz.save_frame_arrays(scene.get_conf(), a.out, "conf_{}.npy")
+        if a.pointcloud:
+            if mode != GlobalAlignerMode.PointCloudOptimizer:
+                raise RuntimeError("--pointcloud needs at least 3 frames (the two-frame PairViewer has no aligner handle to export from)")
+            n_points = int(scene.save_pointcloud(a.pointcloud)["xyz"].shape[0])
     metrics = None
     if a.gt_depth:
         files = sorted(glob.glob(os.path.join(a.gt_depth, "*.npy")))[a.start:a.start + len(depths)]
@@ -94,7 +107,10 @@ def main(argv=None):
         pose = dict(ate=ate, rpe_trans=rpe_t, rpe_rot=rpe_r)
         if verbose:
             print("pose metrics (Sim(3)-aligned):", {k: round(v, 5) for k, v in pose.items()})
-    return dict(n_frames=len(depths), out=a.out, metrics=metrics, pose_metrics=pose)
+    res_out = dict(n_frames=len(depths), out=a.out, metrics=metrics, pose_metrics=pose)
+    if a.pointcloud:
+        res_out["pointcloud"], res_out["n_points"] = a.pointcloud, n_points
+    return res_out
 
 
 if __name__ == "__main__":

@@ -636,6 +636,32 @@ int a3r_align_shard_sum(float* dst, const float* const* srcs_host, int K, size_t
 int a3r_align_shard_run_local(const a3r_align_t* handles_host, int K, float* const* bufs_host, size_t n_floats,
                               const float* lrs_host, int n, void* stream);
 
+/* Scene out: the aligned scene of a handle as world points (what tool/demo.py's get_3D_model_from_scene assembles from get_pts3d()
+ * and get_masks()).  For image n and pixel p < h_n * w_n (x = p % w_n, y = p / w_n):
+ *     world = R_n * (d (x - ppx) / f, d (y - ppy) / f, d) + t_n,  d = exp(log_depth) | mono * exp(scalemap) + shift
+ * from the handle's CURRENT parameters, decoded as for a3r_align_pose_matrices (shared_focal: the focal of image 0 for all).
+ * Fused and edge-shard handles are both accepted (a shard holds a full replica of everything read here).
+ *
+ * a3r_align_scene_points: dense out_xyz [N,P,3]; the padding pixels p >= h_n * w_n of a mixed-shape scene are written as zeros.
+ *
+ * Compacted form.  A pixel is kept iff p < h_n * w_n, conf[n,p] > thr (strict), dyn == NULL or dyn[n,p] == 0, and its three world
+ * coordinates are finite.  Kept pixels come out image-major, row-major; the result is a deterministic function of the inputs (two
+ * passes: per-chunk counts, an exclusive scan, then placement -- no atomics).  All buffers are device memory unless named *_host;
+ * workspace: a3r_align_scene_workspace_bytes(N, P) bytes, 4-byte aligned.  Both entry points synchronise the stream (the kept
+ * count returns to the host).  N * P must be below 2^31.
+ *   a3r_align_scene_count : *total_host = kept pixels of the scene; counts_dev [N] (or NULL) = kept pixels per image.
+ *   a3r_align_scene_export: counts afresh, then writes out_xyz [M,3] fp32 and, where non-NULL, out_rgb [M,3] (gathered from
+ *     rgb [N,P,3] uint8) and out_index [M] (n * P + p).  *n_written_host = M.  capacity (in points, of every output given) < M is
+ *     A3R_EINVAL BEFORE any output element is written, with *n_written_host = the needed count; elements at and beyond M are never
+ *     written; M = 0 is a success. */
+size_t a3r_align_scene_workspace_bytes(int N, int P);
+int a3r_align_scene_points(a3r_align_t a, float* out_xyz, void* stream);
+int a3r_align_scene_count(a3r_align_t a, const float* conf, float thr, const uint8_t* dyn, void* workspace, size_t workspace_bytes,
+                          int* counts_dev, long long* total_host, void* stream);
+int a3r_align_scene_export(a3r_align_t a, const float* conf, float thr, const uint8_t* dyn, const uint8_t* rgb, void* workspace,
+                           size_t workspace_bytes, long long capacity, float* out_xyz, uint8_t* out_rgb, int* out_index,
+                           long long* n_written_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
