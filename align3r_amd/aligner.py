@@ -258,6 +258,19 @@ class _AlignEngineBase:
         assert written.value == M
         return out
 
+    def clean_confidences(self, conf, tol=0.001, bad_conf=0.0):
+        """clean_pointcloud of the reference (cloud_opt/base_opt.py:468-503) on the current state: a new [N,P] float32 device tensor
+        in which conf[i,p] is clipped to bad_conf wherever another, more confident view sees the point of (i,p) in front of its own
+        depth map by more than `tol` (images in order, each reading the finished rows below it; include/a3r.h has the rule).  The
+        input is left untouched; padding entries and NaNs pass through."""
+        N, P, dev = self.N, self.P, self.device
+        out = torch.as_tensor(conf).to(dev, torch.float32).reshape(N, P).clone(memory_format=torch.contiguous_format)
+        ws = torch.empty(int(self.lib.a3r_align_scene_clean_workspace_bytes(N, P)), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            check(self.lib.a3r_align_scene_clean(self._states[0].handle, ptr(out), float(tol), float(bad_conf), ptr(ws), ws.numel(),
+                                                 stream_ptr()), "a3r_align_scene_clean")
+        return out
+
 
 class AlignEngine(_AlignEngineBase):
     def __init__(self, ei, ej, pred_i, pred_j, w_i, w_j, imshapes, mono=None, base_scale=0.5, pw_break=20.0,

@@ -252,6 +252,125 @@ __global__ __launch_bounds__(SCAN_TPB) void scene_scan_kernel(int* cnt, int T, i
         for (int n = tid; n < N; n += SCAN_TPB) counts_img[n] = cnt[(n + 1) * nchunks] - cnt[n * nchunks];
 }
 
+// ------------------------------------------------------------------------------------------- clean_pointcloud
+// cloud_opt/base_opt.py:468-503 on the handle's state.  conf[i,p] drops to bad_conf when some other view j sees the world point of
+// (i,p) in front of its own depth map (z < (1 - tol) * depth_j[v,u] at the rounded projection (u,v)) while being the more
+// confident of the two (conf[i,p] < conf[j,v,u]).  Image i reads the FINISHED rows of the images below it, so the images are N
+// launches in stream order; inside launch i every pixel is independent, row i is the only row written and never read.
+//
+// World-to-camera table, CLEAN_CAM floats per image: R^T (9), t (3), f, ppx, ppy, W, H, pad to 20 (five 16-byte scalar loads).
+constexpr int CLEAN_CAM = 20;
+
+static size_t clean_cam_bytes(int N) { return align_up((size_t)N * CLEAN_CAM * sizeof(float), 256); }
+
+// grid (nchunks, N).  dense[n,p] = the depth scene_point uses (same expf, same fma order); the first thread of chunk 0 writes the
+// table row of image n.  Padding pixels p >= h_n * w_n are written too (never read: the padding of an image is never visible).
+template <bool MONO, bool VEC>
+__global__ __launch_bounds__(STPB) void scene_clean_prep_kernel(SceneView v, float* __restrict__ cam, float* __restrict__ dense,
+                                                               const float* __restrict__ img_xf, const int* __restrict__ imw,
+                                                               const int* __restrict__ imarea) {
+    const int n = blockIdx.y, p0 = blockIdx.x * SCHUNK + threadIdx.x * SPX;
+    const float* ix = img_xf + n * 16;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        float* o = cam + n * CLEAN_CAM;
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            o[r * 3 + 0] = ix[0 * 4 + r]; o[r * 3 + 1] = ix[1 * 4 + r]; o[r * 3 + 2] = ix[2 * 4 + r];     // row r of R^T
+            o[9 + r] = ix[r * 4 + 3];
+        }
+        const int W = imw[n];
+        o[12] = ix[12]; o[13] = ix[13]; o[14] = ix[14];
+        o[15] = (float)W; o[16] = (float)(W > 0 ? imarea[n] / W : 0);
+        o[17] = o[18] = o[19] = 0.f;
+    }
+    if (p0 >= v.P) return;
+    const float shift = ix[15];
+    float raw[SPX], mono[SPX], d[SPX];
+    load_depth4<MONO, VEC>(v, n, p0, raw, mono);
+#pragma unroll
+    for (int i = 0; i < SPX; i++) d[i] = MONO ? mono[i] * expf(raw[i]) + shift : expf(raw[i]);
+    float* o = dense + (size_t)n * v.P + p0;
+    if (VEC) {
+        *reinterpret_cast<f32x4*>(o) = f32x4{d[0], d[1], d[2], d[3]};
+    } else {
+#pragma unroll
+        for (int i = 0; i < SPX; i++)
+            if (p0 + i < v.P) o[i] = d[i];
+    }
+}
+
+// grid (nchunks): target image `img`.  A thread owns 4 consecutive pixels and walks the other views in increasing order until
+// each of its pixels is clipped; the walk ends for the whole wave when no lane has a live pixel (a wave-uniform exit, so the
+// table reads stay scalar loads).  Skipped outright: padding pixels, confidences already <= bad_conf (NaN included: the compare
+// is false) and non-finite world points.  A non-finite projection fails the float range tests before it becomes an index.
+template <bool MONO, bool VEC>
+__global__ __launch_bounds__(STPB) void scene_clean_kernel(SceneView v, float* conf, int img, const float* __restrict__ cam,
+                                                          const float* __restrict__ dense, float keep_frac, float bad_conf,
+                                                          const float* __restrict__ img_xf, const int* __restrict__ imw,
+                                                          const int* __restrict__ imarea) {
+    const int p0 = blockIdx.x * SCHUNK + threadIdx.x * SPX;
+    const bool inside = p0 < v.P;
+    const SceneCam c = load_cam(img_xf, imw, imarea, img);
+    float raw[SPX], mono[SPX], cf[SPX], w[SPX][3];
+    load_depth4<MONO, VEC>(v, img, p0, raw, mono);
+    float* row = conf + (size_t)img * v.P;
+    if (VEC) {
+        f32x4 c4 = {0.f, 0.f, 0.f, 0.f};
+        if (inside) c4 = *reinterpret_cast<const f32x4*>(row + p0);
+        cf[0] = c4.x; cf[1] = c4.y; cf[2] = c4.z; cf[3] = c4.w;
+    } else {
+#pragma unroll
+        for (int i = 0; i < SPX; i++) cf[i] = p0 + i < v.P ? row[p0 + i] : 0.f;
+    }
+    bool live[SPX], hit[SPX];
+    int y = inside ? p0 / c.W : 0, x = p0 - y * c.W;
+#pragma unroll
+    for (int i = 0; i < SPX; i++) {
+        scene_point<MONO>(c, x, y, raw[i], mono[i], w[i]);
+        live[i] = p0 + i < c.area && cf[i] > bad_conf &&
+                  __builtin_isfinite(w[i][0]) && __builtin_isfinite(w[i][1]) && __builtin_isfinite(w[i][2]);
+        hit[i] = false;
+        if (++x == c.W) { x = 0; y++; }
+    }
+    for (int j = 0; j < v.N; j++) {
+        if (__ballot(live[0] || live[1] || live[2] || live[3]) == 0ull) break;
+        if (j == img) continue;
+        const float* cj = cam + j * CLEAN_CAM;
+        const float f = cj[12], ppx = cj[13], ppy = cj[14], Wf = cj[15], Hf = cj[16];
+        const float* dj = dense + (size_t)j * v.P;
+        const float* fj = conf + (size_t)j * v.P;
+        float z[SPX], dep[SPX], oc[SPX];
+        bool vis[SPX];
+#pragma unroll
+        for (int i = 0; i < SPX; i++) {     // all gathers of the step are issued before the first is consumed
+            const float d0 = w[i][0] - cj[9], d1 = w[i][1] - cj[10], d2 = w[i][2] - cj[11];
+            const float cx = cj[0] * d0 + cj[1] * d1 + cj[2] * d2;
+            const float cy = cj[3] * d0 + cj[4] * d1 + cj[5] * d2;
+            z[i] = cj[6] * d0 + cj[7] * d1 + cj[8] * d2;
+            const float iz = 1.f / z[i];
+            const float u = rintf(f * cx * iz + ppx), vv = rintf(f * cy * iz + ppy);
+            vis[i] = live[i] && z[i] > 0.f && u >= 0.f && u < Wf && vv >= 0.f && vv < Hf;      // NaN / inf: every compare is false
+            dep[i] = 0.f; oc[i] = 0.f;
+            if (vis[i]) {
+                const int q = (int)vv * (int)Wf + (int)u;
+                dep[i] = dj[q]; oc[i] = fj[q];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < SPX; i++)
+            if (vis[i] && z[i] < keep_frac * dep[i] && cf[i] < oc[i]) { hit[i] = true; live[i] = false; }
+    }
+    if (!(hit[0] || hit[1] || hit[2] || hit[3])) return;
+    if (VEC) {                          // the quad goes back whole: the unclipped lanes hold the bits that were loaded
+        *reinterpret_cast<f32x4*>(row + p0) = f32x4{hit[0] ? bad_conf : cf[0], hit[1] ? bad_conf : cf[1], hit[2] ? bad_conf : cf[2],
+                                                    hit[3] ? bad_conf : cf[3]};
+    } else {
+#pragma unroll
+        for (int i = 0; i < SPX; i++)
+            if (hit[i]) row[p0 + i] = bad_conf;
+    }
+}
+
 static int scene_nchunks(int P) { return (P + SCHUNK - 1) / SCHUNK; }
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -349,6 +468,44 @@ extern "C" int a3r_align_scene_export(a3r_align_t a, const float* conf, float th
     if (total == 0) return A3R_OK;
     s.out_xyz = out_xyz; s.out_rgb = out_rgb; s.out_index = out_index;
     launch_compact<true>(v, s, vec, st);
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+extern "C" size_t a3r_align_scene_clean_workspace_bytes(int N, int P) {
+    if (N <= 0 || P <= 0) return 0;
+    return clean_cam_bytes(N) + align_up((size_t)N * P * sizeof(float), 256);
+}
+
+// Enqueues 1 + N kernels on `stream`: no allocation, no synchronisation, nothing read back (graph-capturable).
+extern "C" int a3r_align_scene_clean(a3r_align_t a, float* conf, float tol, float bad_conf, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    const char* who = "a3r_align_scene_clean";
+    A3R_CHECK_ARG(conf, "%s: null confidence buffer", who);
+    A3R_CHECK_ARG(tol >= 0.f && tol < 1.f, "%s: tol = %g is outside [0, 1)", who, (double)tol);          // false for NaN too
+    A3R_CHECK_ARG(bad_conf == bad_conf, "%s: bad_conf is NaN", who);
+    hipStream_t st = as_stream(stream);
+    SceneView v;
+    if (int rc = align_scene_view(a, st, &v, who)) return rc;
+    const size_t need = a3r_align_scene_clean_workspace_bytes(v.N, v.P);
+    A3R_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
+    A3R_CHECK_ARG(aligned16(workspace), "%s: workspace must be 16-byte aligned", who);
+    float* cam = static_cast<float*>(workspace);
+    float* dense = reinterpret_cast<float*>(static_cast<char*>(workspace) + clean_cam_bytes(v.N));
+    const bool vec = v.P % 4 == 0 && aligned16(v.depth) && aligned16(conf) && (!v.mono || aligned16(v.mono));
+    const float keep_frac = (float)(1.0 - (double)tol);
+    const int nch = scene_nchunks(v.P);
+#define A3R_SCENE_LAUNCH(MONOV, VECV)                                                                                                      \
+    do {                                                                                                                                   \
+        hipLaunchKernelGGL((scene_clean_prep_kernel<MONOV, VECV>), dim3(nch, v.N), dim3(STPB), 0, st, v, cam, dense, v.img_xf, v.imw,      \
+                           v.imarea);                                                                                                      \
+        for (int i = 0; i < v.N; i++)                                                                                                      \
+            hipLaunchKernelGGL((scene_clean_kernel<MONOV, VECV>), dim3(nch), dim3(STPB), 0, st, v, conf, i, cam, dense, keep_frac,         \
+                               bad_conf, v.img_xf, v.imw, v.imarea);                                                                       \
+    } while (0)
+    if (v.mono) { if (vec) A3R_SCENE_LAUNCH(true, true); else A3R_SCENE_LAUNCH(true, false); }
+    else        { if (vec) A3R_SCENE_LAUNCH(false, true); else A3R_SCENE_LAUNCH(false, false); }
+#undef A3R_SCENE_LAUNCH
     A3R_LAUNCH_CHECK();
     return A3R_OK;
 }

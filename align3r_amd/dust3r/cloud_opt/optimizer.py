@@ -13,6 +13,8 @@ lists, every map zero-filled to max_area like _ravel_hw) are supported and pinne
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 
@@ -393,13 +395,22 @@ class PointCloudOptimizer:
         write_ply(path, pc['xyz'].cpu().numpy(), pc['rgb'].cpu().numpy() if 'rgb' in pc else None)
         return pc
 
-    def clean_pointcloud(self, **kw):
-        """base_opt.py:268-278: lower the confidence of points that another, more confident view sees through."""
-        cams = inv_rigid(self.get_im_poses())
-        new_confs = clean_pointcloud([c.to(self.device) for c in self.im_conf], self.get_intrinsics(), cams, self.get_depthmaps(),
-                                     self.get_pts3d(), **kw)
-        for i, c in enumerate(new_confs):
-            self.im_conf[i] = c.to(self.im_conf[i].device)
+    def clean_pointcloud(self, tol=0.001, bad_conf=0, dbg=()):
+        """base_opt.py:268-278: lower the confidence of points that another, more confident view sees through.  Computed by the
+        aligner handle from its own state (csrc/scene.hip, AlignEngine.clean_confidences): the decisions are those of the
+        module-level clean_pointcloud() below except at pixels within rounding distance of one of its comparisons.
+        A3R_CLEAN=torch (read at every call) takes that torch function instead."""
+        if os.environ.get('A3R_CLEAN', '') == 'torch':
+            cams = inv_rigid(self.get_im_poses())
+            new_confs = clean_pointcloud([c.to(self.device) for c in self.im_conf], self.get_intrinsics(), cams, self.get_depthmaps(),
+                                         self.get_pts3d(), tol=tol, bad_conf=bad_conf, dbg=dbg)
+            for i, c in enumerate(new_confs):
+                self.im_conf[i] = c.to(self.im_conf[i].device)
+            return self
+        e = self._need_engine()
+        out = e.clean_confidences(torch.stack([_ravel_hw(c.to(self.device).float(), self.max_area) for c in self.im_conf]), tol, bad_conf)
+        for i, (c, (h, w)) in enumerate(zip(self.im_conf, self.imshapes)):
+            self.im_conf[i] = out[i, :h * w].view(h, w).to(device=c.device, dtype=c.dtype)
         return self
 
     # ------------------------------------------------------------------ presets (optimizer.py:76-113)

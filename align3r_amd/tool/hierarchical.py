@@ -88,13 +88,15 @@ def save_frame_arrays(arrays, folder, pattern, start=0):
 # ------------------------------------------------------------------------------------------- the driver
 def hierarchical_alignment(imgs, model, device, *, clip_size=50, niter=300, schedule='linear', lr=0.05, min_conf_thr=3,
                            if_use_mono=False, mono_depths=(), batch_size=1, clamp_conf=True, verbose=False, output_dir=None,
-                           pointcloud_collector=None):
+                           pointcloud_collector=None, clean=False):
     """Keyframe pass + per-clip passes (depth_test.py:636-676).  `imgs`: view dicts (load_images).  Returns a dict with the
     per-frame lists `depths`, `confs`, `poses` ([4,4] cam-to-world in the keyframes' frame), `focals`, `intrinsics`, plus
     `keyframes_id`, `clip_size` and the keyframe scene's own results; writes pred_traj.txt / pred_intrinsics.txt /
     frame_XXXX.npy / conf_X.npy under `output_dir` when given (demo.py:225-243).
     `pointcloud_collector`: a list that receives, in clip order, every clip scene's get_pointcloud() as host arrays
-    dict(xyz, rgb | None); off by default."""
+    dict(xyz, rgb | None); off by default.
+    `clean`: scene.clean_pointcloud() on the keyframe scene and on every clip scene right after its alignment (pose_test.py:205,475),
+    so the confidences returned, written and thresholded by the collector are the cleaned ones; off by default."""
     from ..dust3r.cloud_opt import GlobalAlignerMode, global_aligner
     from ..dust3r.inference import inference
 
@@ -113,6 +115,8 @@ def hierarchical_alignment(imgs, model, device, *, clip_size=50, niter=300, sche
         scene = global_aligner(out, if_use_mono, list(mono_depths), device=device, mode=GlobalAlignerMode.PointCloudOptimizer,
                                verbose=verbose, min_conf_thr=min_conf_thr)
         scene.compute_global_alignment(init='mst', init_priors=init_priors, niter=niter, schedule=schedule, lr=lr)
+        if clean:
+            scene.clean_pointcloud()
         return scene
 
     key_scene = None

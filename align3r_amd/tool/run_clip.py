@@ -8,7 +8,7 @@ The flow of the reference's tool/demo.py and tool/depth_test.py through this pac
 
     python -m align3r_amd.tool.run_clip --images DIR --weights CKPT.pth --out OUT [--size 512] [--scene-graph swin-3-noncyclic]
            [--hierarchical --clip-size 50] [--niter 300] [--schedule linear] [--lr 0.01] [--traj-format custom] [--gt-depth DIR]
-           [--pointcloud scene.ply]
+           [--pointcloud scene.ply] [--clean]
 """
 from __future__ import annotations
 
@@ -44,6 +44,9 @@ def parse(argv=None):
     ap.add_argument("--gt-traj", default=None, help="ground-truth camera trajectory, TUM file `t x y z qx qy qz qw` (same frames) -> ATE / RPE")
     ap.add_argument("--pointcloud", default=None, metavar="PATH",
                     help="write the aligned scene as a binary PLY (with --hierarchical: every clip's points, appended in clip order)")
+    ap.add_argument("--clean", action="store_true",
+                    help="scene.clean_pointcloud() after every alignment: confidences of points another, more confident view sees through "
+                         "drop to 0 before conf_X.npy and --pointcloud are written (tool/demo.py: clean_depth)")
     ap.add_argument("--quiet", action="store_true")
     return ap.parse_args(argv)
 
@@ -68,7 +71,7 @@ def main(argv=None):
     if a.hierarchical and len(imgs) >= 3:
         res = hz.hierarchical_alignment(imgs, model, a.device, clip_size=a.clip_size, niter=a.niter, schedule=a.schedule, lr=a.lr,
                                         min_conf_thr=a.min_conf_thr, batch_size=a.batch_size, verbose=verbose, output_dir=a.out,
-                                        pointcloud_collector=clouds)
+                                        pointcloud_collector=clouds, clean=a.clean)
         depths = res["depths"]
         if a.pointcloud:
             n_points = write_ply_parts(a.pointcloud, [(c["xyz"], c["rgb"]) for c in clouds])
@@ -81,6 +84,8 @@ def main(argv=None):
         scene = global_aligner(out, False, [], a.device, mode=mode, verbose=verbose, min_conf_thr=a.min_conf_thr)
         if mode == GlobalAlignerMode.PointCloudOptimizer:
             scene.compute_global_alignment(init="mst", niter=a.niter, schedule=a.schedule, lr=a.lr)
+            if a.clean:
+                scene.clean_pointcloud()
         depths = [d.detach().cpu().numpy() for d in scene.get_depthmaps()]
         hz.save_trajectory_tum_format(hz.get_tum_poses(scene.get_im_poses()), os.path.join(a.out, "pred_traj.txt"))
         hz.save_intrinsics(scene.get_intrinsics(), os.path.join(a.out, "pred_intrinsics.txt"))

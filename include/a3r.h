@@ -662,6 +662,21 @@ int a3r_align_scene_export(a3r_align_t a, const float* conf, float thr, const ui
                            size_t workspace_bytes, long long capacity, float* out_xyz, uint8_t* out_rgb, int* out_index,
                            long long* n_written_host, void* stream);
 
+/* clean_pointcloud (cloud_opt/base_opt.py:468-503) on the handle's CURRENT state: conf [N,P] fp32 (device) is updated in place, as if
+ * the images were processed in order i = 0 .. N-1 and, for every pixel p < h_i * w_i of image i, the other views j in increasing order:
+ *     (cx, cy, z) = R_j^T (world(i,p) - t_j);  u = rint(f_j cx / z + ppx_j), v = rint(f_j cy / z + ppy_j)   (half to even)
+ *     visible  iff z > 0, 0 <= u < w_j, 0 <= v < h_j, everything finite (a non-finite value is "not visible", never an index)
+ *     bad      iff visible, z < (1 - tol) * depth_j[v,u] and conf[i,p] < conf[j, v * w_j + u]                (both strict)
+ *     bad  =>  conf[i,p] = min(conf[i,p], bad_conf)
+ * The rows j < i are read as FINISHED, the rows j > i as given.  Padding entries p >= h_i * w_i and NaN confidences are never
+ * written; padding pixels of image j are never visible.  One small preparation kernel and N kernels in stream order (image i writes
+ * row i only and reads the other rows), no atomics: the result is a function of the inputs alone.  Nothing is allocated,
+ * synchronised or read back, so the call can be captured into a graph.  workspace: a3r_align_scene_clean_workspace_bytes(N, P)
+ * bytes, 16-byte aligned (a world-to-camera table and the dense depth maps).  A3R_EINVAL before conf is touched: null conf, a
+ * workspace that is too small or misaligned, tol outside [0, 1) or NaN, bad_conf NaN. */
+size_t a3r_align_scene_clean_workspace_bytes(int N, int P);
+int a3r_align_scene_clean(a3r_align_t a, float* conf, float tol, float bad_conf, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
