@@ -76,6 +76,18 @@ class AlignFlowDesc(C.Structure):
                 ("dynamic_mask", c_void), ("workspace", c_void), ("workspace_bytes", C.c_size_t)]
 
 
+class MotionEntry(C.Structure):
+    _fields_ = [("depth_row", C.c_int), ("flow_row", C.c_int), ("image", C.c_int), ("pad", C.c_int), ("depth_rt", C.c_float * 4),
+                ("Hm", C.c_float * 9), ("Kt", C.c_float * 3)]
+
+
+class MotionDesc(C.Structure):
+    _fields_ = [("M", C.c_int), ("N", C.c_int), ("E", C.c_int), ("H", C.c_int), ("W", C.c_int), ("motion_mask_thre", C.c_float),
+                ("pred_i", c_void), ("pred_j", c_void), ("flow_ij", c_void), ("flow_ji", c_void), ("entries", c_void),
+                ("entries_host", c_void), ("list_start", c_void), ("list_start_host", c_void), ("list_entry", c_void),
+                ("list_entry_host", c_void)]
+
+
 EPI_NONE, EPI_GELU, EPI_RESID, EPI_RELU, EPI_ROPE, EPI_RESID2, EPI_PIXSHUF, EPI_HEAD = range(8)
 
 # name -> (restype, argtypes); every symbol declared in include/a3r.h
@@ -197,6 +209,8 @@ SIGNATURES = {
                                          C.POINTER(C.c_longlong), c_void]),
     "a3r_align_scene_clean_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "a3r_align_scene_clean": (C.c_int, [c_void, c_void, C.c_float, C.c_float, c_void, C.c_size_t, c_void]),
+    "a3r_motion_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "a3r_motion_masks": (C.c_int, [C.POINTER(MotionDesc), c_void, C.c_size_t, c_void, c_void, c_void]),
 }
 
 _lib = None

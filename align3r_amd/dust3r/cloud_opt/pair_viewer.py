@@ -117,3 +117,45 @@ class PairViewer:
         return float('nan')
 
     __call__ = forward
+
+
+def pair_geometry(edges, pred_i, pred_j, conf_i, conf_j, device, min_conf_thr=3):
+    """What get_motion_mask_from_pairs takes from its E/2 PairViewer objects, for all symmetric pairs (e, e + E/2) in one batch: one
+    estimate_focals call on `device` for the E first-view pointmaps, one linear_pnp_many call for the E PnP problems, one read-back
+    of the poses.  PairViewer's rules (__init__ above) are applied as they stand: the masks are im_conf > min_conf_thr of the
+    pair's own two edges, pp = (W/2, H/2), the identity when PnP returns nothing, `confs[0] > confs[1]` decides whose camera is
+    the world frame.  The solvers sum in a fixed order per problem, so the numbers are those of the per-pair loop bit for bit.
+    pred_* [E,H,W,3], conf_* [E,H,W] (host or device; the confidence product is evaluated where conf_* live, like PairViewer's).
+    Returns CPU float32 tensors, M = E/2:  K_i, K_j [M,3,3];  pose_i, pose_j [M,4,4];  depth_i, depth_j = (row [M] int64,
+    rt [M,4]) -- the depth map of the view is r . pt + t over pointmap `row` of the stack cat(pred_i, pred_j): (0,0,1,0) for the
+    z of a first-view pointmap, the third row of inv(rel_pose) otherwise.  The maps themselves are not materialised."""
+    from .init_im_poses import estimate_focals, linear_pnp_many
+    E = len(edges)
+    M = E // 2
+    assert E == 2 * M and E > 0
+    dev = torch.device(device)
+    _, H, W = conf_i.shape
+    f32 = lambda t: torch.as_tensor(t).to(device=dev, dtype=torch.float32).contiguous()
+    pi, pj = f32(pred_i).reshape(E, H, W, 3), f32(pred_j).reshape(E, H, W, 3)
+    if conf_i.is_cuda:
+        score = (conf_i.reshape(E, -1).float().mean(1) * conf_j.reshape(E, -1).float().mean(1)).cpu().tolist()
+    else:
+        score = [float(conf_i[k].float().mean() * conf_j[k].float().mean()) for k in range(E)]
+    ci, cj = f32(conf_i), f32(conf_j)
+    # row k < M: view 0 of pair k, row k + M: view 1 -- its focal from pred_i[k], its pixels see pred_j of the reverse edge, its
+    # mask is the maximum of the two confidence maps the image has inside the pair
+    masks = (torch.maximum(ci, torch.cat((cj[M:], cj[:M]))) > min_conf_thr).to(torch.uint8)
+    focals = estimate_focals(pi)
+    res = linear_pnp_many([(pj[(k + M) % E], focals[k], masks[k], (W / 2, H / 2)) for k in range(E)])
+    eye = torch.eye(4, device=dev)
+    rel = torch.stack([r[1].float() if r else eye for r in res]).cpu()            # the one read-back
+    inv = torch.linalg.inv(rel)
+    K = torch.zeros((E, 3, 3))
+    K[:, 0, 0] = K[:, 1, 1] = torch.tensor(focals)
+    K[:, 0, 2], K[:, 1, 2], K[:, 2, 2] = W / 2, H / 2, 1
+    first = torch.tensor([score[e] > score[e + M] for e in range(M)])             # the point cloud is expressed in camera 0 of the pair
+    I4, z = torch.eye(4).expand(M, 4, 4), torch.tensor([0., 0., 1., 0.]).expand(M, 4)
+    ar = torch.arange(M)
+    sel = lambda a, b: torch.where(first.reshape(-1, *([1] * (a.dim() - 1))), a, b)
+    return dict(K_i=K[:M].clone(), K_j=K[M:].clone(), pose_i=sel(I4, rel[:M]).clone(), pose_j=sel(rel[M:], I4).clone(),
+                depth_i=(sel(ar, E + ar + M), sel(z, inv[:M, 2]).clone()), depth_j=(sel(E + ar, ar + M), sel(inv[M:, 2], z).clone()))

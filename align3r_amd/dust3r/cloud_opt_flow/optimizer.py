@@ -22,6 +22,65 @@ from ...aligner import AlignEngine
 from ..cloud_opt.optimizer import PointCloudOptimizer as _Base
 
 
+def motion_vote_lists(edges, n_imgs):
+    """Per image the directed entries whose normalised errors it averages, in the order the reference appends them
+    (optimizer.py:228-232): e ascending, err_i[e] (entry e) to image edges[e][0] and err_j[e] (entry M + e) to image edges[e][1]."""
+    M = len(edges) // 2
+    lists = [[] for _ in range(n_imgs)]
+    for e in range(M):
+        i, j = edges[e]
+        lists[i].append(e)
+        lists[j].append(M + e)
+    return lists
+
+
+def motion_entries(geom, edges, n_rows):
+    """The 2M records of ops.MOTION_ENTRY from pair geometry (pair_viewer.pair_geometry's dict): entry e < M is the ego flow i -> j of
+    pair e against flow_ij[e], entry M + e the flow j -> i against flow_ji[e].  H = K_tgt R_rel K_src^-1 and K_tgt t_rel are built
+    in fp32 on the host by the same tensor expressions as warp_by_disp (goem_opt.py:22-33).  n_rows = E, the rows of a stack."""
+    from ...ops import MOTION_ENTRY
+    from ..utils.goem_opt import get_relative_transform
+    M = len(edges) // 2
+    f = lambda t: torch.as_tensor(t).float().cpu()
+    K_i, K_j, pose_i, pose_j = f(geom['K_i']), f(geom['K_j']), f(geom['pose_i']), f(geom['pose_j'])
+    R_i, R_j, T_i, T_j = pose_i[:, :3, :3], pose_j[:, :3, :3], pose_i[:, :3, 3:], pose_j[:, :3, 3:]
+    rec = np.zeros(2 * M, MOTION_ENTRY)
+    sides = ((R_i, T_i, R_j, T_j, K_j, torch.linalg.inv(K_i), geom['depth_i'], 0, 0),
+             (R_j, T_j, R_i, T_i, K_i, torch.linalg.inv(K_j), geom['depth_j'], n_rows, 1))
+    for half, (src_R, src_t, tgt_R, tgt_t, K, inv_K, (row, rt), flow0, side) in enumerate(sides):
+        rel_R, rel_t = get_relative_transform(src_R, src_t, tgt_R, tgt_t)
+        sl = slice(half * M, (half + 1) * M)
+        rec['Hm'][sl] = K.matmul(rel_R.matmul(inv_K)).reshape(M, 9).numpy()
+        rec['Kt'][sl] = torch.matmul(K, rel_t).reshape(M, 3).numpy()
+        rec['depth_row'][sl] = np.asarray(row)
+        rec['depth_rt'][sl] = f(rt).numpy()
+        rec['flow_row'][sl] = flow0 + np.arange(M)
+        rec['image'][sl] = [edges[e][side] for e in range(M)]
+    return rec
+
+
+def motion_masks_torch(edges, n_imgs, K_i, K_j, R_i, R_j, T_i, T_j, D_i, D_j, flow_ij, flow_ji, thre):
+    """The reference's arithmetic after the pair geometry (optimizer.py:207-235) in torch, on the device of its inputs: depth maps
+    D_* [M,H,W], intrinsics and poses of the M pairs.  Returns (masks, mean normalised errors), one [H,W] tensor per image."""
+    from ..utils.goem_opt import DepthBasedWarping
+    half = len(edges) // 2
+    D_i, D_j = D_i.unsqueeze(1), D_j.unsqueeze(1)
+    warp = DepthBasedWarping()
+    ego_1_2, _ = warp(R_i, T_i, R_j, T_j, 1 / (D_i + 1e-6), K_j, torch.linalg.inv(K_i))
+    ego_2_1, _ = warp(R_j, T_j, R_i, T_i, 1 / (D_j + 1e-6), K_i, torch.linalg.inv(K_j))
+    err_i = torch.norm(ego_1_2[:, :2] - flow_ij[:half], dim=1)
+    err_j = torch.norm(ego_2_1[:, :2] - flow_ji[:half], dim=1)
+    norm = lambda x: (x - x.amin(dim=(1, 2), keepdim=True)) / (x.amax(dim=(1, 2), keepdim=True) - x.amin(dim=(1, 2), keepdim=True))
+    err_i, err_j = norm(err_i), norm(err_j)
+    acc = [[] for _ in range(n_imgs)]
+    for e in range(half):
+        i, j = edges[e]
+        acc[i].append(err_i[e])
+        acc[j].append(err_j[e])
+    means = [torch.stack(a).mean(dim=0) for a in acc]
+    return [m > thre for m in means], means
+
+
 class PointCloudOptimizer(_Base):
     def __init__(self, view1, view2, pred1, pred2, optimize_pp=False, focal_break=20, shared_focal=False,
                  flow_loss_fn='smooth_l1', flow_loss_weight=0.0, depth_regularize_weight=0.0, num_total_iter=300,
@@ -58,6 +117,7 @@ class PointCloudOptimizer(_Base):
             self.dynamic_masks = masks
         self._flow = None
         self._flow_pair = None
+        self._flow_dev = None
         if flow_loss_weight > 0:
             if flow is None:
                 flow = self.get_flow(flow_net)
@@ -66,7 +126,7 @@ class PointCloudOptimizer(_Base):
                 self.get_motion_mask_from_pairs(view1, view2, pred1, pred2, torch.as_tensor(flow[0]).float(), torch.as_tensor(flow[1]).float())
             if self.dynamic_masks is None:
                 raise RuntimeError("flow loss needs view['dynamic_mask'] (the reference fails on torch.stack(None), optimizer.py:531)")
-            fij, fji = flow
+            fij, fji = getattr(self, '_flow_dev', None) or flow              # already uploaded by the mask kernels' path
             self._flow = dict(flow_ij=torch.as_tensor(fij).float(), flow_ji=torch.as_tensor(fji).float(),
                               dyn=torch.stack(self.dynamic_masks), weight=float(flow_loss_weight), thre=float(flow_loss_thre),
                               start_epoch=float(flow_loss_start_epoch), num_total_iter=int(num_total_iter), pxl_thre=float(pxl_thre))
@@ -135,10 +195,41 @@ class PointCloudOptimizer(_Base):
         """cloud_opt_flow/optimizer.py:154-235: self-computed dynamic masks.  For every symmetric pair (e, e + E/2) a closed-form
         PairViewer gives intrinsics, relative pose and depth; the ego-motion flow they imply is compared with the optical flow;
         the per-pair error maps are min-max normalised, averaged per image and thresholded at motion_mask_thre.
-        Parity unpinned where PairViewer's PnP stand-in enters (cv2 absent); the flow geometry itself is pinned (goem_opt)."""
-        from ..cloud_opt.pair_viewer import PairViewer
-        from ..utils.goem_opt import DepthBasedWarping
+        On the device: the pair geometry of all pairs in one batch (pair_viewer.pair_geometry), then the mask kernels of
+        csrc/motion.hip (ops.motion_masks) on the stacked predictions, which are uploaded once -- the engine is later built from
+        the same device tensors (the constructor does not know the aligner's device yet: the current HIP device, or the one the
+        flow fields already live on, is used, and .to() moves the stacks only if it names another one).  The decisions are those of
+        _motion_masks_torch except at pixels within rounding distance of the threshold.  A3R_MOTION=torch (read at
+        every call) takes that torch function instead.  Parity unpinned only where PairViewer's PnP stand-in enters (cv2 absent)."""
+        import os
         assert self.is_symmetrized, 'only support symmetric case'
+        if os.environ.get('A3R_MOTION', '') == 'torch':
+            return self._motion_masks_torch(view1, view2, pred1, pred2, flow_ij, flow_ji)
+        from ... import ops
+        from ..cloud_opt.pair_viewer import pair_geometry
+        E, (H, W) = len(self.edges), self.imshape
+        if not self._uniform:
+            raise RuntimeError('use_self_mask needs images of one shape (the reference stacks the depth maps, optimizer.py:207)')
+        if E % 2:
+            raise RuntimeError('use_self_mask needs the edges in symmetric order: edge e + E/2 is the reverse of edge e')
+        lists = motion_vote_lists(self.edges, self.n_imgs)
+        empty = [n for n, l in enumerate(lists) if not l]
+        if empty:
+            raise RuntimeError(f'use_self_mask: images {empty} are in no pair of the first half of the edge list (the reference fails on '
+                               'torch.stack([]), optimizer.py:235)')
+        dev = flow_ij.device if flow_ij.is_cuda else torch.device('cuda', torch.cuda.current_device())
+        up = lambda t: torch.as_tensor(t).to(device=dev, dtype=torch.float32).contiguous()
+        self._pred_i, self._pred_j = up(self._pred_i), up(self._pred_j)          # [E,P,3]: what the engine is built from
+        fij, fji = up(flow_ij), up(flow_ji)
+        geom = pair_geometry(self.edges, self._pred_i.view(E, H, W, 3), self._pred_j.view(E, H, W, 3), self._conf_i.reshape(E, H, W),
+                             self._conf_j.reshape(E, H, W), dev)
+        masks = ops.motion_masks(self._pred_i, self._pred_j, fij, fji, motion_entries(geom, self.edges, E), lists, self.motion_mask_thre)
+        self._flow_dev = (fij, fji)
+        self.dynamic_masks = list(masks.cpu())
+
+    def _motion_masks_torch(self, view1, view2, pred1, pred2, flow_ij, flow_ji):
+        """The checker of get_motion_mask_from_pairs: the reference's per-pair loop and torch arithmetic (A3R_MOTION=torch)."""
+        from ..cloud_opt.pair_viewer import PairViewer
         half = len(self.edges) // 2
         K_i, K_j, R_i, R_j, T_i, T_j, D_i, D_j = [], [], [], [], [], [], [], []
         p1, p2 = torch.as_tensor(pred1['pts3d']).float(), torch.as_tensor(pred2['pts3d_in_other_view']).float()
@@ -153,21 +244,31 @@ class PointCloudOptimizer(_Base):
             T_i.append(poses[0][:3, 3:]); T_j.append(poses[1][:3, 3:])
             D_i.append(depth[0]); D_j.append(depth[1])
         dev = flow_ij.device
-        K_i, K_j, R_i, R_j, T_i, T_j = (torch.stack(x).to(dev) for x in (K_i, K_j, R_i, R_j, T_i, T_j))
-        D_i, D_j = torch.stack(D_i).unsqueeze(1).to(dev), torch.stack(D_j).unsqueeze(1).to(dev)
-        warp = DepthBasedWarping()
-        ego_1_2, _ = warp(R_i, T_i, R_j, T_j, 1 / (D_i + 1e-6), K_j, torch.linalg.inv(K_i))
-        ego_2_1, _ = warp(R_j, T_j, R_i, T_i, 1 / (D_j + 1e-6), K_i, torch.linalg.inv(K_j))
-        err_i = torch.norm(ego_1_2[:, :2] - flow_ij[:half], dim=1)
-        err_j = torch.norm(ego_2_1[:, :2] - flow_ji[:half], dim=1)
-        norm = lambda x: (x - x.amin(dim=(1, 2), keepdim=True)) / (x.amax(dim=(1, 2), keepdim=True) - x.amin(dim=(1, 2), keepdim=True))
-        err_i, err_j = norm(err_i), norm(err_j)
-        acc = [[] for _ in range(self.n_imgs)]
-        for e in range(half):
-            i, j = self.edges[e]
-            acc[i].append(err_i[e])
-            acc[j].append(err_j[e])
-        self.dynamic_masks = [(torch.stack(a).mean(dim=0) > self.motion_mask_thre).cpu() for a in acc]
+        K_i, K_j, R_i, R_j, T_i, T_j, D_i, D_j = (torch.stack(x).to(dev) for x in (K_i, K_j, R_i, R_j, T_i, T_j, D_i, D_j))
+        masks, _ = motion_masks_torch(self.edges, self.n_imgs, K_i, K_j, R_i, R_j, T_i, T_j, D_i, D_j, flow_ij, flow_ji, self.motion_mask_thre)
+        self.dynamic_masks = [m.cpu() for m in masks]
+
+    # ------------------------------------------------------------------ output files (cloud_opt_flow/base_opt.py:358-388)
+    def get_init_conf(self, mode=None):
+        from ..cloud_opt.commons import get_conf_trf
+        trf = self.conf_trf if mode is None else get_conf_trf(mode)
+        return [trf(c) for c in self.init_conf_maps]
+
+    def save_dynamic_masks(self, path, start=0):
+        """dynamic_mask_{start+i}.png per image: 8-bit, 0 / 255 (written with PIL; the reference uses cv2.imwrite)."""
+        import PIL.Image
+        if self.dynamic_masks is None:
+            raise RuntimeError('save_dynamic_masks: this scene has no dynamic masks')
+        for i, m in enumerate(self.dynamic_masks):
+            arr = (torch.as_tensor(m).detach().cpu().numpy().astype(bool) * 255).astype(np.uint8)
+            PIL.Image.fromarray(arr).save(f'{path}/dynamic_mask_{start + i}.png')
+        return self.dynamic_masks
+
+    def save_init_conf_maps(self, path, start=0):
+        conf = self.get_init_conf()
+        for i, c in enumerate(conf):
+            np.save(f'{path}/init_conf_{start + i}.npy', c.detach().cpu().numpy())
+        return conf
 
     def _build_engine(self, device):
         """The base class's .to() with the flow variant's extras (shared focal, temporal smoothing, ego-flow inputs)."""

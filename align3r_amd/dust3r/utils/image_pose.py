@@ -8,6 +8,7 @@ imageio dependencies:
   pixel_to_pointcloud, normalize_pointcloud   image_pose.py:206-244
   load_images                            image_pose.py:246-407  (image files; video needs cv2.VideoCapture: not available)
   depth_read, cam_read, flow_read        image_pose.py:30-72    (Sintel binary formats)
+  enlarge_seg_masks                      image_pose.py:409-415  (cv2.dilate with a k x k box restated in numpy)
 
 Parity: everything that is PIL / numpy arithmetic is pinned bit for bit against the reference (tests/golden/prep.npz).
 `resize_numpy_image` resizes the un-projected mono point map with cv2.resize (INTER_LANCZOS4 when shrinking, INTER_CUBIC
@@ -294,3 +295,26 @@ def load_images(folder_or_list, size, square_ok=False, verbose=True, dynamic_mas
     if verbose:
         print(f' (Found {len(imgs)} images)')
     return imgs, imgs_raw
+
+
+def enlarge_seg_masks(folder, kernel_size=5, prefix='dynamic_mask'):
+    """image_pose.py:409-415: every {prefix}_*.png of `folder` dilated by a kernel_size x kernel_size box (cv2.dilate, one iteration:
+    the maximum over the window anchored at its centre kernel_size // 2, pixels outside the image ignored) and written as
+    enlarged_dynamic_mask_*.png.  Returns the written paths."""
+    import glob
+    k = int(kernel_size)
+    before, after = k // 2, k - 1 - k // 2
+    written = []
+    for mask_path in sorted(glob.glob(f'{folder}/{prefix}_*.png')):
+        mask = np.array(PIL.Image.open(mask_path).convert('L'))
+        H, W = mask.shape
+        padded = np.zeros((H + k - 1, W + k - 1), mask.dtype)
+        padded[before:before + H, before:before + W] = mask
+        out = np.zeros_like(mask)
+        for dy in range(k):
+            for dx in range(k):
+                np.maximum(out, padded[dy:dy + H, dx:dx + W], out=out)
+        dst = os.path.join(os.path.dirname(mask_path), os.path.basename(mask_path).replace(prefix, 'enlarged_dynamic_mask'))
+        PIL.Image.fromarray(out).save(dst)
+        written.append(dst)
+    return written

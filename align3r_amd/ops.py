@@ -487,3 +487,42 @@ def head_final(x, w, b):
     check(_lib.load().a3r_head_final(ptr(x), ptr(_req(w.reshape(4, Cc), "w")), ptr(_req(b, "b")), ptr(pts), ptr(conf), P, Cc,
                                      stream_ptr()), "head_final")
     return pts, conf
+
+
+MOTION_ENTRY = np.dtype([('depth_row', '<i4'), ('flow_row', '<i4'), ('image', '<i4'), ('pad', '<i4'), ('depth_rt', '<f4', (4,)),
+                         ('Hm', '<f4', (9,)), ('Kt', '<f4', (3,))])
+
+
+def motion_masks(pred_i, pred_j, flow_ij, flow_ji, entries, lists, thre, want_mean=False):
+    """Self-computed motion masks from prepared pair geometry (cloud_opt_flow/optimizer.py:201-235; a3r_motion_masks, csrc/motion.hip).
+    pred_i, pred_j [E,P,3] (or [E,H,W,3]) and flow_ij, flow_ji [E,2,H,W]: contiguous float32 device tensors.  entries: numpy array of
+    MOTION_ENTRY, one record per directed entry (2M of them).  lists: per image the entry indices whose normalised errors are
+    averaged, in that order.  Returns masks [N,H,W] bool (device), and the mean normalised error [N,H,W] with want_mean."""
+    lib = _lib.load()
+    for t, name in ((pred_i, "pred_i"), (pred_j, "pred_j"), (flow_ij, "flow_ij"), (flow_ji, "flow_ji")):
+        _req(t, name)
+    E, _, H, W = flow_ij.shape
+    P, N = H * W, len(lists)
+    if not (flow_ji.shape == flow_ij.shape and pred_i.numel() == pred_j.numel() == E * P * 3):
+        raise RuntimeError("motion_masks: pred_i / pred_j [E,P,3] and flow_ij / flow_ji [E,2,H,W] do not agree")
+    entries = np.ascontiguousarray(entries, dtype=MOTION_ENTRY)
+    assert MOTION_ENTRY.itemsize == C.sizeof(_lib.MotionEntry)
+    if len(entries) % 2 or not len(entries):
+        raise RuntimeError("motion_masks: the entry table holds two records per symmetric pair")
+    M = len(entries) // 2
+    start = np.zeros(N + 1, np.int32)
+    start[1:] = np.cumsum([len(l) for l in lists])
+    flat = np.ascontiguousarray([k for l in lists for k in l], dtype=np.int32)
+    dev = pred_i.device
+    up = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to(dev)
+    entries_dev, start_dev, flat_dev = up(entries), up(start), up(flat)
+    ws_bytes = int(lib.a3r_motion_workspace_bytes(M, N, P))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    masks = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+    mean = torch.empty((N, H, W), dtype=torch.float32, device=dev) if want_mean else None
+    d = _lib.MotionDesc(M, N, E, H, W, float(thre), ptr(pred_i), ptr(pred_j), ptr(flow_ij), ptr(flow_ji), ptr(entries_dev),
+                        entries.ctypes.data, ptr(start_dev), start.ctypes.data, ptr(flat_dev), flat.ctypes.data if len(flat) else None)
+    with torch.cuda.device(dev):
+        check(lib.a3r_motion_masks(C.byref(d), ptr(ws), ws_bytes, ptr(masks), ptr(mean), stream_ptr()), "a3r_motion_masks")
+    masks = masks.bool()          # stream-ordered after the kernels; the uploaded tables and the workspace are freed stream-ordered too
+    return (masks, mean) if want_mean else masks

@@ -9,6 +9,11 @@ The flow of the reference's tool/demo.py and tool/depth_test.py through this pac
     python -m align3r_amd.tool.run_clip --images DIR --weights CKPT.pth --out OUT [--size 512] [--scene-graph swin-3-noncyclic]
            [--hierarchical --clip-size 50] [--niter 300] [--schedule linear] [--lr 0.01] [--traj-format custom] [--gt-depth DIR]
            [--pointcloud scene.ply] [--clean]
+           [--flow [--flow-weights RAFT.pth] [--gt-masks DIR] [--not-shared-focal]]
+
+--flow is the sequence of the reference's tool/pose_test.py:154-216: the flow-regularised aligner (cloud_opt_flow) with self-computed
+motion masks on a swinstride-5-noncyclic graph, and on top of the usual outputs pred_focal.txt, dynamic_mask_X.png, their 3x3-enlarged
+copies enlarged_dynamic_mask_X.png (5x5 with --gt-masks) and init_conf_X.npy.
 """
 from __future__ import annotations
 
@@ -31,7 +36,7 @@ def parse(argv=None):
     ap.add_argument("--depth-prior-name", default="depthpro")
     ap.add_argument("--start", type=int, default=0)
     ap.add_argument("--interval", type=int, default=10 ** 9)
-    ap.add_argument("--scene-graph", default="swin-3-noncyclic")
+    ap.add_argument("--scene-graph", default=None, help="default: swin-3-noncyclic, with --flow swinstride-5-noncyclic")
     ap.add_argument("--batch-size", type=int, default=16)
     ap.add_argument("--hierarchical", action="store_true", help="keyframe -> clip alignment (tool/depth_test.py:628-676)")
     ap.add_argument("--clip-size", type=int, default=50)
@@ -47,8 +52,22 @@ def parse(argv=None):
     ap.add_argument("--clean", action="store_true",
                     help="scene.clean_pointcloud() after every alignment: confidences of points another, more confident view sees through "
                          "drop to 0 before conf_X.npy and --pointcloud are written (tool/demo.py: clean_depth)")
+    ap.add_argument("--flow", action="store_true",
+                    help="flow-regularised alignment with self-computed motion masks (tool/pose_test.py:154-216)")
+    ap.add_argument("--flow-weights", default=None, metavar="PATH", help="RAFT checkpoint of --flow (flow_net=)")
+    ap.add_argument("--gt-masks", default=None, metavar="DIR", help="--flow with motion masks read from DIR instead of self-computed ones")
+    ap.add_argument("--not-shared-focal", action="store_true", help="--flow: one focal per image instead of a shared one")
     ap.add_argument("--quiet", action="store_true")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.flow and a.hierarchical:
+        ap.error("--flow cannot be combined with --hierarchical: the keyframe / clip alignment has no flow term")
+    if not a.flow:
+        for given, name in ((a.flow_weights, "--flow-weights"), (a.gt_masks, "--gt-masks"), (a.not_shared_focal, "--not-shared-focal")):
+            if given:
+                ap.error(f"{name} belongs to --flow")
+    if a.scene_graph is None:
+        a.scene_graph = "swinstride-5-noncyclic" if a.flow else "swin-3-noncyclic"
+    return a
 
 
 def main(argv=None):
@@ -65,7 +84,8 @@ def main(argv=None):
     verbose = not a.quiet
     model = AsymmetricCroCo3DStereo.from_pretrained(a.weights).to(a.device)
     imgs, _ = load_images(a.images, a.size, verbose=verbose, traj_format=a.traj_format, start=a.start, interval=a.interval,
-                          depth_prior_name=a.depth_prior_name, dynamic_mask_root=os.path.join(a.out, "__no_masks__"))
+                          depth_prior_name=a.depth_prior_name,
+                          dynamic_mask_root=a.gt_masks if a.flow and a.gt_masks else os.path.join(a.out, "__no_masks__"))
     os.makedirs(a.out, exist_ok=True)
     clouds, n_points = ([] if a.pointcloud else None), None
     if a.hierarchical and len(imgs) >= 3:
@@ -81,7 +101,17 @@ def main(argv=None):
         pairs = make_pairs(imgs, scene_graph=a.scene_graph, prefilter=None, symmetrize=True)
         out = inference(pairs, model, a.device, batch_size=a.batch_size, verbose=verbose)
         mode = GlobalAlignerMode.PointCloudOptimizer if len(imgs) > 2 else GlobalAlignerMode.PairViewer
-        scene = global_aligner(out, False, [], a.device, mode=mode, verbose=verbose, min_conf_thr=a.min_conf_thr)
+        if a.flow:
+            if len(imgs) <= 2:
+                raise RuntimeError("--flow needs at least 3 frames (two frames go to the PairViewer, which has no flow term)")
+            from ..dust3r.cloud_opt_flow import global_aligner as flow_aligner
+            # tool/pose_test.py:170-179 with its argument defaults (translation_weight 1, flow_loss_thre 40 outside temple_3)
+            scene = flow_aligner(out, a.device, verbose=verbose, min_conf_thr=a.min_conf_thr, shared_focal=not a.not_shared_focal,
+                                 flow_loss_weight=0.01, temporal_smoothing_weight=0.01, translation_weight=1.0, flow_loss_start_epoch=0.1,
+                                 flow_loss_thre=40, pxl_thre=50, motion_mask_thre=0.35, use_self_mask=not a.gt_masks,
+                                 num_total_iter=a.niter, flow_net=a.flow_weights)
+        else:
+            scene = global_aligner(out, False, [], a.device, mode=mode, verbose=verbose, min_conf_thr=a.min_conf_thr)
         if mode == GlobalAlignerMode.PointCloudOptimizer:
             scene.compute_global_alignment(init="mst", niter=a.niter, schedule=a.schedule, lr=a.lr)
             if a.clean:
@@ -91,6 +121,12 @@ def main(argv=None):
         hz.save_intrinsics(scene.get_intrinsics(), os.path.join(a.out, "pred_intrinsics.txt"))
         hz.save_frame_arrays(depths, a.out, "frame_{:04d}.npy")
         hz.save_frame_arrays(scene.get_conf(), a.out, "conf_{}.npy")
+        if a.flow:
+            from ..dust3r.utils.image_pose import enlarge_seg_masks
+            scene.save_focals(os.path.join(a.out, "pred_focal.txt"))
+            scene.save_dynamic_masks(a.out, 0)
+            scene.save_init_conf_maps(a.out, 0)
+            enlarge_seg_masks(a.out, kernel_size=5 if a.gt_masks else 3)
         if a.pointcloud:
             if mode != GlobalAlignerMode.PointCloudOptimizer:
                 raise RuntimeError("--pointcloud needs at least 3 frames (the two-frame PairViewer has no aligner handle to export from)")

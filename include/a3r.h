@@ -677,6 +677,46 @@ int a3r_align_scene_export(a3r_align_t a, const float* conf, float thr, const ui
 size_t a3r_align_scene_clean_workspace_bytes(int N, int P);
 int a3r_align_scene_clean(a3r_align_t a, float* conf, float tol, float bad_conf, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Self-computed motion masks of the flow aligner (dust3r/cloud_opt_flow/optimizer.py:201-235): everything after the pair geometry of
+ * get_motion_mask_from_pairs.  M symmetric pairs give 2M DIRECTED entries; entry k compares the ego flow its pair geometry implies
+ * with one optical-flow field and votes for one image.  Per entry and pixel (x, y), fp32, in this order of operations:
+ *     D = r . pt + t;  disp = 1 / (D + 1e-6);  tgt = Hm (x, y, 1) + disp * Kt;  tgt /= tgt_z + 1e-6;
+ *     err = | tgt_xy - (x, y) - flow(x, y) |
+ * per entry nerr = (err - min) / (max - min) over the whole map; per image the mean of its entries' nerr in list order;
+ * masks = mean > motion_mask_thre.  IEEE as torch evaluates it: a NaN anywhere in an entry's map, or a constant map (0 / 0), makes
+ * that entry's contribution NaN at every pixel, and every image it votes for gets an all-false mask and a NaN mean.
+ * Three kernels in stream order, no atomics, fixed-order reductions: the result is a function of the inputs alone.  Nothing is
+ * allocated, synchronised or read back, so the call can be captured into a graph. */
+typedef struct {
+    int depth_row;       /* row of the stacked pointmaps that supplies the depth: [0, E) = pred_i, [E, 2E) = pred_j[row - E] */
+    int flow_row;        /* [0, E) = flow_ij, [E, 2E) = flow_ji[row - E] */
+    int image;           /* the image this entry votes for (must agree with the lists below) */
+    int pad;
+    float depth_rt[4];   /* (r, t): D = r . pt + t; (0,0,1,0) = z of the pointmap, or the third row of inv(rel_pose) */
+    float Hm[9];         /* K_tgt R_rel K_src^-1, row-major */
+    float Kt[3];         /* K_tgt t_rel */
+} a3r_motion_entry;
+typedef struct {
+    int M, N, E;                        /* symmetric pairs, images, rows of the stacked buffers */
+    int H, W;                           /* one image shape, P = H * W */
+    float motion_mask_thre;
+    const float* pred_i;                /* [E, P, 3] device */
+    const float* pred_j;                /* [E, P, 3] device */
+    const float* flow_ij;               /* [E, 2, H, W] device */
+    const float* flow_ji;               /* [E, 2, H, W] device */
+    const a3r_motion_entry* entries;    /* [2M] device */
+    const a3r_motion_entry* entries_host; /* the same table in host memory: validated before anything is launched */
+    const int* list_start;              /* [N + 1] device: image n owns list_entry[list_start[n] .. list_start[n + 1]) */
+    const int* list_start_host;
+    const int* list_entry;              /* [list_start[N]] device: entry indices, per image in the order their errors are averaged */
+    const int* list_entry_host;
+} a3r_motion_desc;
+/* workspace: a3r_motion_workspace_bytes(M, N, P) bytes, 16-byte aligned (the error maps [2M, P], per-chunk and per-entry min / max).
+ * masks [N, P] bytes 0 / 1; mean_err [N, P] fp32 or NULL.  A3R_EINVAL before anything is written: a null pointer, a workspace that
+ * is too small or misaligned, M, N, E, H or W <= 0, an image with an empty list, a table or list index out of range, NaN thre. */
+size_t a3r_motion_workspace_bytes(int M, int N, int P);
+int a3r_motion_masks(const a3r_motion_desc* d, void* ws, size_t ws_bytes, unsigned char* masks, float* mean_err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

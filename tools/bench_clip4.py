@@ -4,7 +4,9 @@
 with the per-frame encoder cache) -> cloud_opt_flow global_aligner with its own RAFT2 optical flow (2460 fields, synthetic weights of
 the reference's configuration) -> init='mst' -> 300 iterations of the flow-regularised alignment.  As in bench.py's clip extra the
 prediction buffers are overwritten, outside the timed regions, with a consistent synthetic scene so that the aligner has a problem it
-can solve; the frames RAFT sees are smooth synthetic images (tools/../raft_weights.synthetic_raft_frames)."""
+can solve; the frames RAFT sees are smooth synthetic images (tools/../raft_weights.synthetic_raft_frames).
+`--self-mask` (after the optional frame count): use_self_mask=True, the dynamic masks are computed from the pair predictions and the
+flow (get_motion_mask_from_pairs) inside the timed construction instead of being given as all-false maps."""
 import math, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -16,7 +18,9 @@ from align3r_amd.dust3r.cloud_opt_flow import global_aligner
 from align3r_amd.raft import RAFT2
 from align3r_amd.raft_weights import RAFT_M, synthetic_raft_state_dict, synthetic_raft_frames
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 128
+SELF_MASK = "--self-mask" in sys.argv
+_args = [v for v in sys.argv[1:] if v != "--self-mask"]
+N = int(_args[0]) if _args else 128
 H, W, B = 384, 512, 42
 dev = torch.device("cuda:0")
 torch.set_num_threads(8)
@@ -60,10 +64,10 @@ torch.manual_seed(0)
 torch.cuda.synchronize()
 t0 = time.perf_counter()
 scene = global_aligner(outp, dev, verbose=False, min_conf_thr=3, flow_loss_weight=0.01, flow_net=net, num_total_iter=300,
-                       flow_loss_start_epoch=0.1, shared_focal=True, temporal_smoothing_weight=0.01)
+                       flow_loss_start_epoch=0.1, shared_focal=True, temporal_smoothing_weight=0.01, use_self_mask=SELF_MASK)
 torch.cuda.synchronize()
 t_build = time.perf_counter() - t0
-print(f"global_aligner construction incl. {2 * E} RAFT2 flow fields: {t_build:.2f} s (range fallbacks: {net._engine.range_fallbacks})", flush=True)
+print(f"global_aligner construction incl. {2 * E} RAFT2 flow fields{' and self-computed motion masks' if SELF_MASK else ''}: {t_build:.2f} s (range fallbacks: {net._engine.range_fallbacks})", flush=True)
 t0 = time.perf_counter()
 scene.compute_global_alignment(init="mst", niter=0)
 torch.cuda.synchronize()
