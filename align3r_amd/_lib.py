@@ -88,6 +88,12 @@ class MotionDesc(C.Structure):
                 ("list_entry_host", c_void)]
 
 
+class PrepDesc(C.Structure):
+    _fields_ = [("Hs", C.c_int), ("Ws", C.c_int), ("Hr", C.c_int), ("Wr", C.c_int), ("taps", C.c_int), ("y0", C.c_int), ("x0", C.c_int),
+                ("Hc", C.c_int), ("Wc", C.c_int), ("idx_x", c_void), ("idx_x_host", c_void), ("w_x", c_void), ("idx_y", c_void),
+                ("idx_y_host", c_void), ("w_y", c_void)]
+
+
 EPI_NONE, EPI_GELU, EPI_RESID, EPI_RELU, EPI_ROPE, EPI_RESID2, EPI_PIXSHUF, EPI_HEAD = range(8)
 
 # name -> (restype, argtypes); every symbol declared in include/a3r.h
@@ -211,6 +217,10 @@ SIGNATURES = {
     "a3r_align_scene_clean": (C.c_int, [c_void, c_void, C.c_float, C.c_float, c_void, C.c_size_t, c_void]),
     "a3r_motion_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "a3r_motion_masks": (C.c_int, [C.POINTER(MotionDesc), c_void, C.c_size_t, c_void, c_void, c_void]),
+    "a3r_prep_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "a3r_prep_pointmap": (C.c_int, [c_void, C.c_double, C.POINTER(PrepDesc), c_void, C.c_size_t, c_void, c_void]),
+    "a3r_prep_resize3": (C.c_int, [c_void, C.POINTER(PrepDesc), c_void, C.c_size_t, c_void, c_void]),
+    "a3r_prep_image": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void, c_void]),
 }
 
 _lib = None

@@ -18,6 +18,7 @@ anti-aliasing) and that function is PARITY UNPINNED.
 """
 from __future__ import annotations
 
+import functools
 import os
 
 import numpy as np
@@ -126,8 +127,10 @@ def _cubic_weights(frac, A=-0.75):
     return w
 
 
-def _resize_axis(img, new_len, axis, lanczos):
-    n = img.shape[axis]
+def resize_tables(n, new_len, lanczos):
+    """The resample of one axis from n to new_len samples as tables: idx int64 [new_len, taps] clipped source indices and w float64
+    [new_len, taps] weights, taps = 8 (Lanczos-4) or 4 (cubic).  The one place the filters are evaluated: the host resize below and the
+    device path (ops.PrepTables, csrc/prep.hip) both apply these tables, tap 0 first."""
     scale = n / float(new_len)
     fx = (np.arange(new_len, dtype=np.float64) + 0.5) * scale - 0.5        # pixel-centre alignment
     sx = np.floor(fx)
@@ -137,6 +140,11 @@ def _resize_axis(img, new_len, axis, lanczos):
     else:
         w, offs = _cubic_weights(frac), np.arange(-1, 3)
     idx = np.clip(sx[:, None].astype(np.int64) + offs[None, :], 0, n - 1)   # BORDER_REPLICATE
+    return idx, w
+
+
+def _resize_axis(img, new_len, axis, lanczos):
+    idx, w = resize_tables(img.shape[axis], new_len, lanczos)
     src = np.moveaxis(img, axis, 0).astype(np.float64)
     out = np.zeros((new_len,) + src.shape[1:], np.float64)
     for k in range(w.shape[1]):
@@ -154,10 +162,14 @@ def cv2_resize(img, new_size, lanczos):
 
 def resize_numpy_image(img, long_edge_size):
     """image_pose.py:120-147: long edge -> long_edge_size, LANCZOS4 when shrinking, CUBIC otherwise."""
-    h, w = img.shape[:2]
+    new_size, lanczos = _numpy_resize_plan(*img.shape[:2], long_edge_size)
+    return cv2_resize(img, new_size, lanczos=lanczos)
+
+
+def _numpy_resize_plan(h, w, long_edge_size):
+    """((new width, new height), lanczos) of resize_numpy_image for an h x w array."""
     S = max(h, w)
-    new_size = (int(round(w * long_edge_size / S)), int(round(h * long_edge_size / S)))
-    return cv2_resize(img, new_size, lanczos=S > long_edge_size)
+    return (int(round(w * long_edge_size / S)), int(round(h * long_edge_size / S))), S > long_edge_size
 
 
 def crop_center(img, crop_width, crop_height):
@@ -168,13 +180,66 @@ def crop_center(img, crop_width, crop_height):
     return img[max(r_mid - r_half, 0):min(r_mid + r_half, rows), max(c_mid - c_half, 0):min(c_mid + c_half, cols)]
 
 
-def crop_img(img, size, pred_depth=None, square_ok=False, nearest=False, crop=True):
+class _DevicePrior:
+    """The point map of a float32 depth prior on its way through crop_img(device=...): the sizes follow the image, and the kernels run
+    once the final window is known (ops.prep_pointmap: un-project, normalise, resize and crop in one call)."""
+
+    def __init__(self, depth, focal_px, device):
+        from ... import ops
+        self.ops, self.device = ops, torch.device(device)
+        self.focal = float(np.asarray(focal_px, dtype=np.float64).reshape(-1)[0])
+        self.depth = (depth if isinstance(depth, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(depth))).to(self.device)
+        self.tables = None
+
+    def resize(self, long_edge_size):
+        (w, h), lanczos = _numpy_resize_plan(*self.depth.shape, long_edge_size)
+        self.tables = _device_tables(*self.depth.shape, h, w, bool(lanczos), str(self.depth.device))
+
+    def crop(self, crop_width, crop_height):
+        rows, cols = self.tables.Hr, self.tables.Wr
+        win = crop_center(np.empty((rows, cols, 0), np.float32), crop_width, crop_height)       # raises what the host path raises
+        if win.shape[0] == 0 or win.shape[1] == 0:
+            return torch.empty(win.shape[:2] + (3,), dtype=torch.float32, device=self.depth.device)
+        window = (max(rows // 2 - crop_height // 2, 0), max(cols // 2 - crop_width // 2, 0), win.shape[0], win.shape[1])
+        return self.ops.prep_pointmap(self.depth, self.focal, self.tables, window)
+
+    def squeeze(self, target):
+        """The not-crop branch: the whole resized map, rounded to float32, resized again with the cubic filter."""
+        w, h = target
+        np.zeros((h, 0))                                            # a fractional target raises what cv2_resize raises
+        full = self.ops.prep_pointmap(self.depth, self.focal, self.tables)
+        return self.ops.prep_resize3(full, _device_tables(self.tables.Hr, self.tables.Wr, h, w, False, str(self.depth.device)))
+
+
+def _device_prior_ok(depth, focal_px):
+    """What the kernels take as it is: a float32 [H, W] depth map and one finite, non-zero focal (anything else: the host functions)."""
+    if not (depth.dtype == np.float32 and depth.ndim == 2 and depth.size and np.size(focal_px) == 1):
+        return False
+    f = float(np.asarray(focal_px, dtype=np.float64).reshape(-1)[0])
+    return bool(np.isfinite(f)) and f != 0.0
+
+
+@functools.lru_cache(maxsize=16)
+def _device_tables(Hs, Ws, Hr, Wr, lanczos, device):
+    from ... import ops
+    return ops.PrepTables(resize_tables(Ws, Wr, lanczos), resize_tables(Hs, Hr, lanczos), device)
+
+
+def crop_img(img, size, pred_depth=None, square_ok=False, nearest=False, crop=True, device=None):
     """image_pose.py:172-204.  size == 224: short side -> 224, centre square.  Otherwise: long side -> size, then the centre
     window whose sides are multiples of 16 (4:3 for square inputs unless square_ok), cut out (crop) or squeezed into (not crop).
-    The point map `pred_depth` [H, W, 3] follows the image."""
+    The point map `pred_depth` [H, W, 3] follows the image.
+
+    device (extension, default None: the host path, untouched): `pred_depth` is then the pair (depth [Hs, Ws] float32, focal_px) that
+    pixel_to_pointcloud would take, and the returned point map is a float32 tensor on that device holding the same numbers as
+    crop_img(img, size, pixel_to_pointcloud(depth, focal_px), ...) (csrc/prep.hip); the PIL image is handled as always."""
     W1, H1 = img.size
     long_edge = round(size * max(W1 / H1, H1 / W1)) if size == 224 else size
     img = _resize_pil_image(img, long_edge, nearest=nearest)
+    prior = None
+    if device is not None and pred_depth is not None:
+        prior, pred_depth = _DevicePrior(*pred_depth, device), None
+        prior.resize(long_edge)
     if pred_depth is not None:
         pred_depth = resize_numpy_image(pred_depth, long_edge)
     W, H = img.size
@@ -190,11 +255,11 @@ def crop_img(img, size, pred_depth=None, square_ok=False, nearest=False, crop=Tr
             img = img.resize(target, PIL.Image.LANCZOS)
             if pred_depth is not None:
                 pred_depth = cv2_resize(pred_depth, target, lanczos=False)
-            return img, pred_depth
+            return img, (pred_depth if prior is None else prior.squeeze(target))
     img = img.crop((cx - halfw, cy - halfh, cx + halfw, cy + halfh))
     if pred_depth is not None:
         pred_depth = crop_center(pred_depth, 2 * halfw, 2 * halfh)
-    return img, pred_depth
+    return img, (pred_depth if prior is None else prior.crop(2 * halfw, 2 * halfh))
 
 
 def normalize_pointcloud(point_cloud):
@@ -261,11 +326,19 @@ def _dynamic_mask_for(full_path, name, size, square_ok, dynamic_mask_root, like)
 
 
 def load_images(folder_or_list, size, square_ok=False, verbose=True, dynamic_mask_root=None, crop=True, fps=0, traj_format="sintel",
-                start=0, interval=30, depth_prior_name='depthpro'):
+                start=0, interval=30, depth_prior_name='depthpro', prep_device=None):
     """Image files (+ their mono-depth .npz priors) -> the view dicts of the pair forward (image_pose.py:246-407).
 
     Returns (imgs, imgs_raw): imgs[k] = dict(img [1,3,H,W] in [-1,1], pred_depth [1,H,W,3] in [0,1], true_shape int32 [1,2],
-    idx, instance, mask, dynamic_mask).  Files are taken in name order, `interval` of them from `start`."""
+    idx, instance, mask, dynamic_mask).  Files are taken in name order, `interval` of them from `start`.
+
+    prep_device (extension, default None: the host path, untouched): a HIP device.  The .npz is still read and the image still resized
+    by PIL on the host; the depth map and the uint8 image are uploaded, and the point map, `img` and `mask` of every view are made by
+    the kernels of csrc/prep.hip and stay on that device: torch tensors of the host path's shapes and dtypes holding the same numbers
+    (`pred_depth` float32 [1,H,W,3]).  A prior whose `depth` is not a float32 [H, W] array (or whose focal is not one number) goes
+    through the host functions for that frame and the result is uploaded, so its values are the host's by construction.  Everything
+    else of a view, `dynamic_mask` included, is built as on the host path, and the same inputs raise the same exceptions."""
+    prep_device = None if prep_device is None else torch.device(prep_device)
     root, names = _list_inputs(folder_or_list, verbose)
     names = sorted(names, key=lambda x: x.split('/')[-1])[start: start + interval]
     imgs, imgs_raw = [], []
@@ -284,12 +357,25 @@ def load_images(folder_or_list, size, square_ok=False, verbose=True, dynamic_mas
         depth = prior['depth']
         if depth.ndim == 3:
             depth = np.squeeze(depth)
-        img, pointmap = crop_img(raw, size, pixel_to_pointcloud(depth, focal_px), square_ok=square_ok, crop=crop)
+        if prep_device is not None and _device_prior_ok(depth, focal_px):
+            img, pointmap = crop_img(raw, size, (depth, focal_px), square_ok=square_ok, crop=crop, device=prep_device)
+        else:
+            img, pointmap = crop_img(raw, size, pixel_to_pointcloud(depth, focal_px), square_ok=square_ok, crop=crop)
+            if prep_device is not None:
+                pointmap = torch.from_numpy(np.ascontiguousarray(pointmap)).to(prep_device)
         if verbose:
             print(f' - Adding {name} with resolution {raw.size[0]}x{raw.size[1]} --> {img.size[0]}x{img.size[1]}')
-        view = dict(img=ImgNorm(img)[None], pred_depth=pointmap[None, ...], true_shape=np.int32([img.size[::-1]]), idx=len(imgs),
-                    instance=full_path, mask=~(ToTensor(img)[None].sum(1) <= 0.01))
-        view['dynamic_mask'] = _dynamic_mask_for(full_path, name, size, square_ok, dynamic_mask_root, view['mask'])
+        if prep_device is None:
+            view = dict(img=ImgNorm(img)[None], pred_depth=pointmap[None, ...], true_shape=np.int32([img.size[::-1]]), idx=len(imgs),
+                        instance=full_path, mask=~(ToTensor(img)[None].sum(1) <= 0.01))
+            like = view['mask']
+        else:
+            from ... import ops
+            img_dev, mask_dev = ops.prep_image(torch.from_numpy(np.array(img, copy=True)).to(prep_device))
+            view = dict(img=img_dev[None], pred_depth=pointmap[None, ...], true_shape=np.int32([img.size[::-1]]), idx=len(imgs),
+                        instance=full_path, mask=mask_dev[None])
+            like = torch.empty(mask_dev[None].shape, dtype=torch.bool)              # dynamic_mask stays a host tensor
+        view['dynamic_mask'] = _dynamic_mask_for(full_path, name, size, square_ok, dynamic_mask_root, like)
         imgs.append(view)
     assert imgs, 'No images found at ' + root
     if verbose:

@@ -526,3 +526,78 @@ def motion_masks(pred_i, pred_j, flow_ij, flow_ji, entries, lists, thre, want_me
         check(lib.a3r_motion_masks(C.byref(d), ptr(ws), ws_bytes, ptr(masks), ptr(mean), stream_ptr()), "a3r_motion_masks")
     masks = masks.bool()          # stream-ordered after the kernels; the uploaded tables and the workspace are freed stream-ordered too
     return (masks, mean) if want_mean else masks
+
+
+class PrepTables:
+    """The resample tables of one (source size, resized size, filter) on one device (a3r_prep_desc, csrc/prep.hip): per axis
+    [new_len, taps] clipped source indices and float64 weights, exactly what image_pose.resize_tables returns, kept on the host (int32:
+    validated there by the C call) and on the device.  x_tab = (idx, w) of the width axis [Wr, taps], y_tab of the height axis."""
+
+    def __init__(self, x_tab, y_tab, device):
+        self.device = torch.device(device)
+        (ix, wx), (iy, wy) = x_tab, y_tab
+        self.idx_x, self.idx_y = (np.ascontiguousarray(a, dtype=np.int32) for a in (ix, iy))
+        self.w_x, self.w_y = (np.ascontiguousarray(a, dtype=np.float64) for a in (wx, wy))
+        if not (self.idx_x.ndim == 2 and self.idx_x.shape == self.w_x.shape and self.idx_y.shape == self.w_y.shape and
+                self.idx_x.shape[1] == self.idx_y.shape[1]):
+            raise RuntimeError("PrepTables: idx and w of an axis are [new_len, taps], with one taps for both axes")
+        if not (np.array_equal(self.idx_x, ix) and np.array_equal(self.idx_y, iy)):
+            raise RuntimeError("PrepTables: an index does not fit int32")
+        self.Wr, self.taps = self.idx_x.shape
+        self.Hr = self.idx_y.shape[0]
+        up = lambda a: torch.from_numpy(a).to(self.device)
+        self.idx_x_dev, self.w_x_dev, self.idx_y_dev, self.w_y_dev = up(self.idx_x), up(self.w_x), up(self.idx_y), up(self.w_y)
+        self.device = self.idx_x_dev.device                        # with its index: 'cuda' has become 'cuda:0'
+
+    def desc(self, Hs, Ws, crop):
+        y0, x0, Hc, Wc = (int(c) for c in crop)
+        return _lib.PrepDesc(Hs, Ws, self.Hr, self.Wr, self.taps, y0, x0, Hc, Wc, ptr(self.idx_x_dev), self.idx_x.ctypes.data,
+                             ptr(self.w_x_dev), ptr(self.idx_y_dev), self.idx_y.ctypes.data, ptr(self.w_y_dev))
+
+
+def _prep_resample(call, what, src, Hs, Ws, tables, crop, *lead):
+    lib = _lib.load()
+    if not isinstance(tables, PrepTables):
+        tables = PrepTables(tables[0], tables[1], src.device)
+    if tables.device != src.device:
+        raise RuntimeError(f"{what}: the tables are on {tables.device}, the source on {src.device}")
+    crop = (0, 0, tables.Hr, tables.Wr) if crop is None else crop
+    d = tables.desc(Hs, Ws, crop)
+    ws_bytes = int(lib.a3r_prep_workspace_bytes(Hs, Ws, d.Wc))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=src.device)
+    out = torch.empty((max(d.Hc, 0), max(d.Wc, 0), 3), dtype=torch.float32, device=src.device)
+    with torch.cuda.device(src.device):
+        check(getattr(lib, call)(ptr(src), *lead, C.byref(d), ptr(ws), ws_bytes, ptr(out), stream_ptr()), what)
+    return out            # the workspace is freed stream-ordered after the kernels
+
+
+def prep_pointmap(depth, focal, tables, crop=None):
+    """crop_center(resize(pixel_to_pointcloud(depth, focal))) of dust3r/utils/image_pose.py on the device, the same numbers
+    (a3r_prep_pointmap, csrc/prep.hip).  depth [Hs, Ws]: contiguous float32 device tensor.  focal: anything float() takes (a float32
+    0-d array, the integer 200).  tables: a PrepTables, or ((idx_x, w_x), (idx_y, w_y)) from image_pose.resize_tables.
+    crop = (y0, x0, Hc, Wc): the window of the resized map (default: all of it).  Returns [Hc, Wc, 3] float32 on depth's device."""
+    _req(depth, "depth")
+    if depth.dim() != 2:
+        raise RuntimeError("prep_pointmap: depth is [Hs, Ws]")
+    return _prep_resample("a3r_prep_pointmap", "prep_pointmap", depth, depth.shape[0], depth.shape[1], tables, crop, float(focal))
+
+
+def prep_resize3(src, tables, crop=None):
+    """cv2_resize of image_pose.py (then crop_center) on a float32 [Hs, Ws, 3] device tensor with the host's tables (a3r_prep_resize3)."""
+    _req(src, "src")
+    if src.dim() != 3 or src.shape[2] != 3:
+        raise RuntimeError("prep_resize3: src is [Hs, Ws, 3]")
+    return _prep_resample("a3r_prep_resize3", "prep_resize3", src, src.shape[0], src.shape[1], tables, crop)
+
+
+def prep_image(u8):
+    """ImgNorm and the validity mask of load_images on the device (a3r_prep_image).  u8 [H, W, 3]: contiguous uint8 device tensor (the PIL
+    image after resize and crop).  Returns img [3, H, W] float32 = (u / 255 - 0.5) / 0.5 and mask [H, W] bool = ~(sum_c u_c / 255 <= 0.01)."""
+    if not (isinstance(u8, torch.Tensor) and u8.is_cuda and u8.dtype == torch.uint8 and u8.is_contiguous() and u8.dim() == 3 and u8.shape[2] == 3):
+        raise RuntimeError("prep_image: u8 must be a contiguous uint8 CUDA tensor [H, W, 3]")
+    H, W = u8.shape[:2]
+    img = torch.empty((3, H, W), dtype=torch.float32, device=u8.device)
+    mask = torch.empty((H, W), dtype=torch.uint8, device=u8.device)
+    with torch.cuda.device(u8.device):
+        check(_lib.load().a3r_prep_image(ptr(u8), H, W, ptr(img), ptr(mask), stream_ptr()), "prep_image")
+    return img, mask.view(torch.bool)

@@ -8,7 +8,7 @@ The flow of the reference's tool/demo.py and tool/depth_test.py through this pac
 
     python -m align3r_amd.tool.run_clip --images DIR --weights CKPT.pth --out OUT [--size 512] [--scene-graph swin-3-noncyclic]
            [--hierarchical --clip-size 50] [--niter 300] [--schedule linear] [--lr 0.01] [--traj-format custom] [--gt-depth DIR]
-           [--pointcloud scene.ply] [--clean]
+           [--pointcloud scene.ply] [--clean] [--device-prep]
            [--flow [--flow-weights RAFT.pth] [--gt-masks DIR] [--not-shared-focal]]
 
 --flow is the sequence of the reference's tool/pose_test.py:154-216: the flow-regularised aligner (cloud_opt_flow) with self-computed
@@ -57,6 +57,9 @@ def parse(argv=None):
     ap.add_argument("--flow-weights", default=None, metavar="PATH", help="RAFT checkpoint of --flow (flow_net=)")
     ap.add_argument("--gt-masks", default=None, metavar="DIR", help="--flow with motion masks read from DIR instead of self-computed ones")
     ap.add_argument("--not-shared-focal", action="store_true", help="--flow: one focal per image instead of a shared one")
+    ap.add_argument("--device-prep", action="store_true",
+                    help="un-project, normalise, resize and crop the mono-depth priors, and normalise the images, on --device (csrc/prep.hip: "
+                         "the same numbers as the host path, which stays the default)")
     ap.add_argument("--quiet", action="store_true")
     a = ap.parse_args(argv)
     if a.flow and a.hierarchical:
@@ -84,7 +87,7 @@ def main(argv=None):
     verbose = not a.quiet
     model = AsymmetricCroCo3DStereo.from_pretrained(a.weights).to(a.device)
     imgs, _ = load_images(a.images, a.size, verbose=verbose, traj_format=a.traj_format, start=a.start, interval=a.interval,
-                          depth_prior_name=a.depth_prior_name,
+                          depth_prior_name=a.depth_prior_name, prep_device=a.device if a.device_prep else None,
                           dynamic_mask_root=a.gt_masks if a.flow and a.gt_masks else os.path.join(a.out, "__no_masks__"))
     os.makedirs(a.out, exist_ok=True)
     clouds, n_points = ([] if a.pointcloud else None), None

@@ -717,6 +717,39 @@ typedef struct {
 size_t a3r_motion_workspace_bytes(int M, int N, int P);
 int a3r_motion_masks(const a3r_motion_desc* d, void* ws, size_t ws_bytes, unsigned char* masks, float* mean_err, void* stream);
 
+/* Input preprocessing (dust3r/utils/image_pose.py: pixel_to_pointcloud, normalize_pointcloud, cv2_resize, crop_center, ImgNorm): the
+ * mono-depth prior becomes the point map the network reads, with the same numbers as the host path.  Per depth pixel, float64 with
+ * every operation rounded on its own:  x = f32(((px - Ws/2) * d) / f),  y = f32(((py - Hs/2) * d) / f),  z = d;  per channel
+ * n = (v - min) / (max - min) in float32 over the whole map (a NaN anywhere makes the channel's min and max NaN, a constant channel
+ * gives 0 / 0);  then the separable resample  acc = acc + v_k * w_k, k = 0 .. taps - 1, in float64 from acc = 0: horizontally into a
+ * float64 intermediate, vertically with one final rounding to float32.  The tables are the host's: per output column (row) `taps`
+ * clipped source indices and float64 weights, taps = 8 (Lanczos-4) or 4 (cubic).  Only the crop window (y0, x0, Hc, Wc) of the
+ * resized Hr x Wr map is computed.  No atomics, fixed-order reductions: the result is a function of the inputs alone.  Nothing is
+ * allocated, synchronised or read back, so the calls can be captured into a graph. */
+typedef struct {
+    int Hs, Ws;                 /* source rows and columns */
+    int Hr, Wr;                 /* the resized map: rows of the y tables and of the x tables */
+    int taps;                   /* 8 or 4 */
+    int y0, x0, Hc, Wc;         /* the window of the resized map that is written: out [Hc, Wc, 3] */
+    const int* idx_x;           /* [Wr, taps] device, 16-byte aligned: source columns in [0, Ws) */
+    const int* idx_x_host;      /* the same table in host memory: validated before anything is launched */
+    const double* w_x;          /* [Wr, taps] device, 16-byte aligned */
+    const int* idx_y;           /* [Hr, taps] device, 16-byte aligned: source rows in [0, Hs) */
+    const int* idx_y_host;
+    const double* w_y;          /* [Hr, taps] device, 16-byte aligned */
+} a3r_prep_desc;
+/* workspace: a3r_prep_workspace_bytes(Hs, Ws, Wc) bytes, 16-byte aligned (the float64 intermediate [Hs, Wc, 3], the per-chunk and the
+ * final min / max); 0 for an empty size.  a3r_prep_pointmap: depth [Hs, Ws] float32 -> out [Hc, Wc, 3] float32 (four kernels).
+ * a3r_prep_resize3: the resample alone on a float32 [Hs, Ws, 3] map (two kernels).  A3R_EINVAL before anything is launched: a null
+ * pointer, a workspace that is too small or misaligned, a non-positive size, taps other than 4 or 8, a crop window outside the resized
+ * map, a focal that is zero or not finite, an index-table entry outside its range, misaligned device tables.
+ * a3r_prep_image: u8 [H, W, 3] -> img [3, H, W] = (u / 255 - 0.5) / 0.5 and mask [H, W] bytes 0 / 1 = ((c0/255 + c1/255) + c2/255) > 0.01,
+ * written as !(sum <= 0.01) (one kernel). */
+size_t a3r_prep_workspace_bytes(int Hs, int Ws, int Wc);
+int a3r_prep_pointmap(const float* depth, double focal, const a3r_prep_desc* d, void* ws, size_t ws_bytes, float* out, void* stream);
+int a3r_prep_resize3(const float* src, const a3r_prep_desc* d, void* ws, size_t ws_bytes, float* out, void* stream);
+int a3r_prep_image(const unsigned char* u8, int H, int W, float* img, unsigned char* mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
