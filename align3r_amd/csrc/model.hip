@@ -9,29 +9,12 @@
 // Data layout: tokens [rows, C] with rows = (side, batch, token): the first B*N rows belong to view 1,
 // the next B*N rows to view 2 (this is the reference's torch.cat((img1, img2)) batch order), maps are
 // channels-last.  All buffers live in the caller's workspace; nothing here allocates device memory.
-#include "common.h"
-#include <map>
-#include <string>
-#include <vector>
+#include "plan.h"
 #include <new>
 #include <cstdlib>
-#include <cmath>
 #include <cstring>
 
 namespace a3r {
-
-struct WRef { const float* p = nullptr; std::vector<int64_t> shape; };
-
-struct Arena {
-    char* base; size_t off, cap; bool dry; size_t peak; bool overflow = false;
-    float* alloc(size_t nfloat) {
-        size_t o = off;
-        off = align_up(off + nfloat * 4, 256);
-        if (off > peak) peak = off;
-        if (!dry && off > cap) { overflow = true; return reinterpret_cast<float*>(base); }
-        return dry ? nullptr : reinterpret_cast<float*>(base + o);
-    }
-};
 
 struct BlockW {
     const float *n1w, *n1b, *qkvw, *qkvb, *projw, *projb, *n2w, *n2b, *fc1w, *fc1b, *fc2w, *fc2b;
@@ -53,7 +36,7 @@ using namespace a3r;
 
 struct a3r_model_s {
     a3r_model_config cfg;
-    std::map<std::string, WRef> w;
+    WeightTable w;
     bool finalized = false;
     std::vector<BlockW> enc, pc, dec1, dec2;
     HeadW head[2];
@@ -62,16 +45,13 @@ struct a3r_model_s {
     const float *rope_cos = nullptr, *rope_sin = nullptr;
     std::vector<float> host_cos, host_sin;
     std::map<std::string, std::pair<const float*, size_t>> taps;
-    // nn.Linear weights also kept in bf3 form (gemm_bf3.hip) unless A3R_GEMM=f32: fp32 pointer -> bf3 twin in `packed`
-    bool use_bf3 = true;
+    // arithmetic mode, decoded once in a3r_model_create from A3R_GEMM x A3R_CONV ("Arithmetic modes")
+    Form gemm_form = Form::FH2;   // operands of the transformer GEMMs (nn.Linear inputs and weights) and of attention
+    Form map_form = Form::FH2;    // DPT maps: operands of the 3x3 convs and of the fusion blocks' 1x1 out_conv
     int fh2_passes = 3;       // fh2 matrix passes per product: 3 = fp32-grade; A3R_GEMM=f16 -> 1 (plain fp16 operands, reduced precision)
     int products = 6;         // bf3 plane products per multiply: 6 = fp32-accurate; A3R_GEMM=bf3x3 -> 3, A3R_GEMM=bf16 -> 1 (reduced precision)
-    std::map<const float*, const void*> w3;
-    // transformer nn.Linear weights in fh2 form (two fp16 planes, gemm_fh2.hip) unless A3R_GEMM names another mode:
-    // fp32 pointer -> (fh2 twin in `packed`, the power-of-two scale it was stored with)
-    bool use_fh2 = true;
-    bool conv_fh2 = true;     // fh2 mode: the DPT maps / 3x3 convs on the fh2 kernel too (A3R_CONV=bf3 keeps them on the three-plane bf16 kernel)
-    std::map<const float*, std::pair<const void*, float>> w2;
+    // fp32 weight pointer (nn.Linear weight or packed conv weight) -> its twin in `packed`, in the form of the GEMMs / maps that read it
+    TwinTable<const float*> twins;
     static constexpr int MAX_POS = 256;
     // fh2 range control (fh2.h, RANGE; a3r_model_range_check): one power-of-two scale per fh2-producing site of the launch plan, kept
     // per plan phase (forward / encode / decode walk different plans), and the device words the sites record max |stored value| in
@@ -100,18 +80,17 @@ extern "C" int a3r_model_create(const a3r_model_config* cfg, a3r_model_t* out) {
     a3r_model_s* m = new (std::nothrow) a3r_model_s();
     A3R_CHECK_ARG(m, "out of host memory");
     m->cfg = *cfg;
-    if (const char* e = getenv("A3R_GEMM")) {
-        const std::string mode(e);
-        // f32: exact-fp32 MFMA kernels; bf3: every GEMM on the exact three-plane bf16 form (6 passes); bf3x3 / bf16: reduced-precision
-        // bf3 modes; anything else (default, "fh2"): transformer GEMMs on the two-plane fp16 form (3 passes), DPT convs / attention on bf3
-        // f16: the fh2 kernels with ONE pass per product (plain fp16 operands under the same range control): the fast 16-bit mode
-        m->use_bf3 = mode != "f32";
-        m->products = mode == "bf16" ? 1 : mode == "bf3x3" ? 3 : 6;
-        m->use_fh2 = !(mode == "f32" || mode == "bf3" || mode == "bf3x3" || mode == "bf16");
-        m->fh2_passes = mode == "f16" ? 1 : 3;
-    }
-    if (const char* e = getenv("A3R_CONV")) m->conv_fh2 = std::string(e) != "bf3";
-    m->conv_fh2 = m->conv_fh2 && m->use_bf3 && m->use_fh2;
+    // f32: the exact-fp32 MFMA kernels; bf3: GEMMs, attention and DPT maps on the exact three-plane bf16 form (6 products); bf3x3 /
+    // bf16: the same kernels with 3 / 1 products (reduced precision); f16: the fh2 kernels with ONE pass per product (plain fp16
+    // operands under the same range control: the fast 16-bit mode); anything else (unset, "fh2"): everything on the two-plane fp16
+    // form, 3 passes.  Under fh2 GEMMs A3R_CONV=bf3 keeps the DPT maps on the three-plane bf16 kernels.
+    struct Mode { const char* name; Form gemm; int products, passes; };
+    static const Mode modes[] = {{"f32", Form::F32, 6, 3}, {"bf3", Form::BF3, 6, 3}, {"bf3x3", Form::BF3, 3, 3}, {"bf16", Form::BF3, 1, 3},
+                                 {"f16", Form::FH2, 6, 1}};
+    const char *gemm = getenv("A3R_GEMM"), *conv = getenv("A3R_CONV");
+    for (const Mode& md : modes)
+        if (gemm && !strcmp(gemm, md.name)) { m->gemm_form = md.gemm; m->products = md.products; m->fh2_passes = md.passes; }
+    m->map_form = m->gemm_form == Form::FH2 && conv && !strcmp(conv, "bf3") ? Form::BF3 : m->gemm_form;
     // sized here so that the host-side sizing pass (a3r_model_workspace_bytes) works before finalize
     m->enc.assign(cfg->enc_depth, BlockW());
     m->pc.assign(n_pc_blocks(*cfg), BlockW());
@@ -129,19 +108,16 @@ extern "C" int a3r_model_destroy(a3r_model_t m) {
 }
 
 extern "C" int a3r_model_set_weight(a3r_model_t m, const char* name, const float* ptr, int ndim, const int64_t* shape) {
-    A3R_CHECK_ARG(m && name && ptr && ndim >= 1 && ndim <= 4 && shape, "a3r_model_set_weight: bad argument");
-    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(ptr) & 15) == 0, "a3r_model_set_weight: %s is not 16-byte aligned", name);
-    WRef r;
-    r.p = ptr;
-    r.shape.assign(shape, shape + ndim);
-    m->w[name] = r;
+    A3R_CHECK_ARG(m, "a3r_model_set_weight: bad argument");
+    if (int rc = m->w.set("a3r_model_set_weight", name, ptr, ndim, shape)) return rc;
     m->finalized = false;
     return A3R_OK;
 }
 
 // ------------------------------------------------------------------------------------------- packing plan
 namespace {
-// kind 0: conv3x3 [Cout=a,Cin=b]; 1: convT [Cin=a,Cout=b,s]; 2: kv-concat (D=a); 3: rope tables; 4: bf3 twin of the [a, b] nn.Linear weight `name`
+// kind 0: conv3x3 [Cout=a,Cin=b]; 1: convT [Cin=a,Cout=b,s]; 2: kv-concat (D=a); 3: rope tables; 4: twin of the [a, b] weight `name` in
+// Form s (an fh2 twin has 256 bytes behind it: scratch of the max|w| reduction that fixes its scale); 6: range statistics words
 struct PackItem { std::string name; int kind; int a, b, s; size_t off; };
 
 std::vector<PackItem> pack_plan(a3r_model_s* m, size_t* total) {
@@ -174,19 +150,14 @@ std::vector<PackItem> pack_plan(a3r_model_s* m, size_t* total) {
         }
     v.push_back({"rope", 3, 0, 0, 0, off});
     off = align_up(off + (size_t)2 * a3r_model_s::MAX_POS * 16 * 4, 256);
-    v.push_back({"range_stats", 6, 0, 0, 0, off});        // kind 6: the range statistics words of the fh2 sites
+    v.push_back({"range_stats", 6, 0, 0, 0, off});
     off = align_up(off + (size_t)a3r_model_s::MAX_SITES * 4, 256);
-    if (m->use_bf3) {
-        auto twin = [&](const std::string& n, int N, int K) {
-            v.push_back({n, 4, N, K, 0, off});
-            off = align_up(off + a3r_bf3_w_bytes(N, K), 256);
+    if (m->gemm_form != Form::F32) {
+        auto twin = [&](const std::string& n, int N, int K, Form f) {
+            v.push_back({n, 4, N, K, (int)f, off});
+            off = align_up(off + (f == Form::FH2 ? a3r_fh2_bytes(N, K) + 256 : a3r_bf3_w_bytes(N, K)), 256);
         };
-        // kind 5: fh2 twin (+ 256 bytes behind it: scratch of the max|w| reduction that fixes its scale)
-        auto twin_lin = [&](const std::string& n, int N, int K) {
-            if (!m->use_fh2) { twin(n, N, K); return; }
-            v.push_back({n, 5, N, K, 0, off});
-            off = align_up(off + a3r_fh2_bytes(N, K) + 256, 256);
-        };
+        auto twin_lin = [&](const std::string& n, int N, int K) { twin(n, N, K, m->gemm_form); };
         auto block = [&](const std::string& p, int Dm, bool cross) {
             twin_lin(p + ".attn.qkv.weight", 3 * Dm, Dm); twin_lin(p + ".attn.proj.weight", Dm, Dm);
             twin_lin(p + ".mlp.fc1.weight", Dm * c.mlp_ratio, Dm); twin_lin(p + ".mlp.fc2.weight", Dm, Dm * c.mlp_ratio);
@@ -206,7 +177,7 @@ std::vector<PackItem> pack_plan(a3r_model_s* m, size_t* total) {
         twin_lin("patch_embed_point_cloud.proj.weight", D, 768);
         twin_lin("decoder_embed.weight", D, E);
         for (int i = 0; i <= n_pc_blocks(c); i++) twin_lin("zero_convs." + std::to_string(i) + ".0.weight", D, D);
-        if (m->use_fh2)        // the 1x1 adapters of the DPT heads (act_postprocess.*.0): [layer_dim, D or E, 1, 1] = an nn.Linear weight
+        if (m->gemm_form == Form::FH2)        // the 1x1 adapters of the DPT heads (act_postprocess.*.0): [layer_dim, D or E, 1, 1] = an nn.Linear weight
             for (int h = 1; h <= 2; h++) {
                 const std::string p = "downstream_head" + std::to_string(h) + ".dpt.act_postprocess.";
                 twin_lin(p + "0.0.weight", c.layer_dims[0], E);
@@ -216,14 +187,10 @@ std::vector<PackItem> pack_plan(a3r_model_s* m, size_t* total) {
         std::vector<PackItem> convs;
         for (const PackItem& it : v)
             if (it.kind == 0) convs.push_back(it);
-        auto twin_conv = [&](const std::string& n, int N, int K) {
-            if (m->conv_fh2) twin_lin(n, N, K);
-            else twin(n, N, K);
-        };
-        for (const PackItem& it : convs) twin_conv(it.name, it.a, 9 * it.b);
+        for (const PackItem& it : convs) twin(it.name, it.a, 9 * it.b, m->map_form);
         for (int h = 1; h <= 2; h++)
             for (int r = 1; r <= 4; r++)
-                twin_conv("downstream_head" + std::to_string(h) + ".dpt.scratch.refinenet" + std::to_string(r) + ".out_conv.weight", F, F);
+                twin("downstream_head" + std::to_string(h) + ".dpt.scratch.refinenet" + std::to_string(r) + ".out_conv.weight", F, F, m->map_form);
     }
     *total = off;
     return v;
@@ -237,26 +204,9 @@ extern "C" size_t a3r_model_packed_bytes(a3r_model_t m) {
     return total;
 }
 
-static int need(a3r_model_s* m, const std::string& name, std::vector<int64_t> shape, const float** out) {
-    auto it = m->w.find(name);
-    if (it == m->w.end()) {
-        set_error("a3r_model_finalize: missing weight '%s'", name.c_str());
-        return A3R_ESTATE;
-    }
-    if (it->second.shape != shape) {
-        std::string got, want;
-        for (auto d : it->second.shape) got += std::to_string(d) + ",";
-        for (auto d : shape) want += std::to_string(d) + ",";
-        set_error("a3r_model_finalize: weight '%s' has shape [%s] but [%s] is required", name.c_str(), got.c_str(), want.c_str());
-        return A3R_EINVAL;
-    }
-    *out = it->second.p;
-    return A3R_OK;
-}
-
-#define NEED(name, out, ...)                                         \
-    do {                                                             \
-        if (int rc__ = need(m, name, {__VA_ARGS__}, out)) return rc__; \
+#define NEED(name, out, ...)                                                                        \
+    do {                                                                                            \
+        if (int rc__ = m->w.need(name, {__VA_ARGS__}, "a3r_model_finalize", out)) return rc__; \
     } while (0)
 
 static int bind_block(a3r_model_s* m, const std::string& p, int D, int hidden, bool cross, BlockW* b) {
@@ -312,7 +262,7 @@ extern "C" int a3r_model_finalize(a3r_model_t m, void* packed, size_t packed_byt
     // --- repack
     for (const PackItem& it : plan) {
         float* dst = reinterpret_cast<float*>(pk + it.off);
-        if (it.kind == 4 || it.kind == 5) continue;      // after binding (shapes are validated there)
+        if (it.kind == 4) continue;      // after binding (shapes are validated there)
         if (it.kind == 6) {
             m->stats = reinterpret_cast<unsigned*>(dst);
             A3R_HIP(hipMemsetAsync(dst, 0, (size_t)a3r_model_s::MAX_SITES * 4, st));
@@ -407,7 +357,7 @@ extern "C" int a3r_model_finalize(a3r_model_t m, void* packed, size_t packed_byt
     }
     // --- static scales of the LayerNorm -> fh2 sites (fh2 mode)
     m->ln_scale.clear();
-    if (m->use_bf3 && m->use_fh2) {
+    if (m->gemm_form == Form::FH2) {
         std::vector<std::pair<const float*, const float*>> lns;      // (gamma, beta) of every LayerNorm whose output feeds a GEMM
         auto add_block = [&](const BlockW& b, bool cross) {
             lns.push_back({b.n1w, b.n1b}); lns.push_back({b.n2w, b.n2b});
@@ -433,34 +383,14 @@ extern "C" int a3r_model_finalize(a3r_model_t m, void* packed, size_t packed_byt
         }
         A3R_HIP(hipMemsetAsync(m->stats, 0, 8, st));
     }
-    // --- bf3 twins of the nn.Linear weights
-    m->w3.clear();
-    m->w2.clear();
+    // --- twins of the nn.Linear and conv weights
+    m->twins.t.clear();
     for (const PackItem& it : plan) {
-        if (it.kind != 4 && it.kind != 5) continue;
-        const float* src = nullptr;
-        auto pit = packed_ptr.find(it.name);
-        if (pit != packed_ptr.end()) src = pit->second;                 // the concatenated cross-attention k/v projection
-        else src = m->w.at(it.name).p;                                   // bound (and shape-checked) above
-        void* dst = pk + it.off;
-        if (it.kind == 4) {
-            if (int rc = a3r_split_bf3_w(src, it.b, dst, it.a, it.b, stream)) return rc;     // weights: row-pair layout (bf3.h)
-            m->w3[src] = dst;
-        } else {
-            // fh2 twin: scale = the power of two that puts max|w| into [2^12, 2^13) (one small reduction + read-back per matrix)
-            float* scratch = reinterpret_cast<float*>(pk + it.off + a3r_fh2_bytes(it.a, it.b));
-            if (int rc = a3r_absmax(src, (long)it.a * it.b, scratch, stream)) return rc;
-            float amax = 0.f;
-            A3R_HIP(hipMemcpyAsync(&amax, scratch, 4, hipMemcpyDeviceToHost, st));
-            A3R_HIP(hipStreamSynchronize(st));
-            if (!std::isfinite(amax)) {
-                set_error("a3r_model_finalize: weight '%s' contains non-finite values", it.name.c_str());
-                return A3R_EINVAL;
-            }
-            const float scale = a3r_fh2_weight_scale(amax);
-            if (int rc = a3r_split_fh2(src, it.b, dst, it.a, it.b, scale, nullptr, stream)) return rc;
-            m->w2[src] = {dst, scale};
-        }
+        if (it.kind != 4) continue;
+        auto pit = packed_ptr.find(it.name);                             // a repacked weight (3x3 convs, the concatenated cross-attention k/v) ...
+        const float* src = pit != packed_ptr.end() ? pit->second : m->w.find(it.name)->p;      // ... or one bound (and shape-checked) above
+        float* scratch = reinterpret_cast<float*>(pk + it.off + a3r_fh2_bytes(it.a, it.b));
+        if (int rc = m->twins.pack(src, (Form)it.s, src, pk + it.off, it.a, it.b, scratch, "a3r_model_finalize", it.name.c_str(), stream)) return rc;
     }
     m->finalized = true;
     return A3R_OK;
@@ -506,13 +436,8 @@ struct Plan {
         }
         return it->second;
     }
-    bool skip() {
-        if (ar.overflow && !rc) {
-            set_error("a3r_model_forward: internal workspace plan overflow (sizing pass and launch pass disagree)");
-            rc = A3R_ESTATE;
-        }
-        return dry() || rc != A3R_OK;
-    }
+    static constexpr const char* WHO = "a3r_model_forward";
+    bool skip() { return ar.skip(rc, WHO); }
     void traced(const char* what, int a = 0, int b = 0, int c = 0) {
         if (!trace || dry()) return;
         hipError_t e = hipStreamSynchronize(as_stream(stream));
@@ -521,69 +446,40 @@ struct Plan {
         fflush(stderr);
     }
 
-    a3r_epilogue epi(int kind, const float* bias, const float* resid = nullptr, const float* resid2 = nullptr) {
-        a3r_epilogue e = {};
+    OpEpi epi(int kind, const float* bias, const float* resid = nullptr, const float* resid2 = nullptr) {
+        OpEpi e = {};
         e.epi = kind; e.bias = bias; e.resid = resid; e.resid2 = resid2;
         return e;
     }
-    // ---- "GEMM input" (gin) buffers: [rows, K] fp32 in f32 mode, the bf3 form of it (1.5x the bytes, bf3.h) otherwise
-    bool bf3() const { return m->use_bf3; }
-    bool fh2() const { return m->use_bf3 && m->use_fh2; }    // transformer GEMM operands in fh2 form (attention operands stay bf3)
-    // bf3 mode: buffers that are only ever read as the A operand of a GEMM (LayerNorm / attention / fc1+GELU outputs, split
+    // ---- operand forms.  gf: the "GEMM input" (gin) buffers -- [rows, K] rows that only feed a transformer GEMM -- and the attention
+    // operands (q / k / v written by the RoPE projections); mf: the DPT maps that only feed a conv or the fusion blocks' 1x1 out_conv
+    Form gf = Form::FH2, mf = Form::FH2;
+    // BF3 GEMMs only: buffers that are only ever read as the A operand of a GEMM (LayerNorm / attention / fc1+GELU outputs, split
     // activations) are kept in the row-pair form of the layout (bf3.h) when the row counts of both views are even
     bool pair = false;
-    // (an fh2 matrix has exactly the bytes of the fp32 one)
-    float* gin_alloc(size_t rows, int K) { return ar.alloc(bf3() && !fh2() ? rows * K * 3 / 2 : rows * K); }
-    float* gin_scratch(size_t rows, int K) { return ar.alloc(fh2() ? rows * K : bf3() ? rows * K * 3 / 2 : 0); }     // only needed for splitting
-    template <class T> T* gin_at(T* base, size_t rows, int K) const { return base + (bf3() && !fh2() ? rows * K * 3 / 2 : rows * K); }
-    // ---- attention operands (q / k / v written by the RoPE projections): fh2 in fh2 mode, bf3 in the bf3 modes
-    float* att_alloc(size_t rows, int K) { return ar.alloc(bf3() && !fh2() ? rows * K * 3 / 2 : rows * K); }
-    template <class T> T* att_at(T* base, size_t rows, int K) const { return base + (bf3() && !fh2() ? rows * K * 3 / 2 : rows * K); }
-    bool cf2() const { return m->conv_fh2; }                  // DPT maps in fh2 form (else bf3 form in every bf3 / fh2 mode)
-    // maps that are only ever conv inputs (DPT)
-    float* map_alloc(size_t rows, int K) { return ar.alloc(bf3() && !cf2() ? rows * K * 3 / 2 : rows * K); }
-    // a "bf3 output" request of the DPT plan means "the conv-input form": fh2 when the convs run on the fh2 kernel
-    a3r_epilogue map_epi(const a3r_epilogue& e0) const {
-        a3r_epilogue e = e0;
-        if (cf2()) {
-            if (e.out_bf3) { e.out_bf3 = 0; e.out_fh2 = 1; }
-            if (e.aux_bf3) { e.aux_fh2 = e.aux_bf3; e.aux_bf3 = nullptr; }
-        }
-        return e;
-    }
+    float* gin_alloc(size_t rows, int K) { return ar.alloc(form_floats(gf, rows, K)); }
+    float* gin_scratch(size_t rows, int K) { return ar.alloc(gf == Form::F32 ? 0 : form_floats(gf, rows, K)); }     // only needed for splitting
+    template <class T> T* gin_at(T* base, size_t rows, int K) const { return base + form_floats(gf, rows, K); }
     // column `col` (a multiple of 8) of a gin row
-    const float* gin_col(const float* base, int col) const {
-        return bf3() && !fh2() ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + (size_t)col * 6) : base + col;
+    const float* gin_col(const float* base, int col) const { return base + form_floats(gf, 1, col); }
+    float* map_alloc(size_t rows, int K) { return ar.alloc(form_floats(mf, rows, K)); }
+    // the site of an output written in form f (only fh2 outputs are sites)
+    Site out_site(Form f, const void* buf) { return f == Form::FH2 ? site(buf) : Site{1.f, nullptr}; }
+    // fp32 [M, K] -> form f, which is not F32
+    void split(Form f, bool row_pair, const char* what, const float* x, float* y, long M, int K) {
+        if (skip()) return;
+        traced(what, (int)M, K);
+        const Site s = out_site(f, y);
+        if (!rc) rc = op_split(f, x, K, y, M, K, row_pair, s.scale, s.stat, stream);
     }
-    // fp32 activation -> GEMM input: a split pass into `scratch` in bf3 mode, the array itself otherwise
+    // fp32 activation -> GEMM input: a split pass into `scratch`, the array itself on the exact-fp32 kernels
     const float* gin_from(const float* x, float* scratch, long M, int K) {
-        if (!bf3()) return x;
-        if (skip()) return scratch;
-        traced("split_bf3", (int)M, K);
-        if (fh2()) {
-            const Site s = site(scratch);
-            rc = a3r_split_fh2(x, K, scratch, M, K, s.scale, s.stat, stream);
-        } else rc = pair ? a3r_split_bf3_w(x, K, scratch, M, K, stream) : a3r_split_bf3(x, K, scratch, M, K, stream);
+        if (gf == Form::F32) return x;
+        split(gf, pair, "split_gin", x, scratch, M, K);
         return scratch;
     }
-    const std::pair<const void*, float>* twin2(const float* w) {
-        auto it = m->w2.find(w);
-        if (it == m->w2.end()) {
-            set_error("a3r_model_forward: nn.Linear weight without an fh2 twin");
-            rc = A3R_ESTATE;
-            return nullptr;
-        }
-        return &it->second;
-    }
-    const void* twin(const float* w) {
-        auto it = m->w3.find(w);
-        if (it == m->w3.end()) {
-            set_error("a3r_model_forward: nn.Linear weight without a bf3 twin");
-            rc = A3R_ESTATE;
-            return nullptr;
-        }
-        return it->second;
-    }
+    void split_map(const float* x, float* ym, long M, int K) { split(mf, false, "split_map", x, ym, M, K); }
+    const Twin* twin(const float* w, Form f) { return f == Form::F32 ? nullptr : m->twins.get(w, f, WHO, rc); }
     // the range fields of an fh2 launch: the operand's scale, and a site for the fh2 output (y itself or the aux twin)
     void range_epi(a3r_epilogue& e, const void* x2, const void* y) {
         e.x_scale = scale_of(x2);
@@ -592,25 +488,15 @@ struct Plan {
             e.out_scale = s.scale; e.out_absmax = s.stat;
         }
     }
-    // nn.Linear on a GEMM-input buffer (bf3 MFMA path unless A3R_GEMM=f32); plain_x: xg is a plain-rows bf3 matrix (DPT maps)
-    void linear(const float* xg, int lda, const float* w, float* y, int ldc, int M, int N, int K, const a3r_epilogue& e0,
-                bool plain_x = false) {
+    // nn.Linear on a GEMM-input buffer; plain_x: xg is a DPT map instead (map form, plain rows)
+    void linear(const float* xg, int lda, const float* w, float* y, int ldc, int M, int N, int K, const OpEpi& e0, bool plain_x = false) {
         if (skip()) return;
         traced("linear", M, N, K);
-        if (fh2() && (!plain_x || cf2())) {
-            const auto* w2 = twin2(w);
-            a3r_epilogue e = plain_x ? map_epi(e0) : e0;
-            range_epi(e, xg, y);
-            if (w2 && !rc) rc = a3r_linear_fh2(xg, w2->first, w2->second, y, ldc, M, N, K, &e, stream);
-        } else if (bf3()) {
-            const void* w3 = twin(w);
-            a3r_epilogue e = e0;
-            e.x_pair = (pair && !plain_x) ? 1 : 0;
-            if (w3) rc = a3r_linear_bf3(xg, w3, y, ldc, M, N, K, &e, stream);
-        } else {
-            const a3r_epilogue& e = e0;
-            rc = a3r_linear(xg, lda, w, y, ldc, M, N, K, &e, stream);
-        }
+        const Form f = plain_x ? mf : gf;
+        const Twin* tw = twin(w, f);
+        a3r_epilogue e = retarget(e0, f, [&](a3r_epilogue& r) { range_epi(r, xg, y); });
+        e.x_pair = (f == Form::BF3 && pair && !plain_x) ? 1 : 0;
+        if (!rc) rc = op_linear(f, xg, lda, w, tw, y, ldc, M, N, K, e, stream);
     }
     // nn.Linear / 1x1 conv on a plain fp32 activation (DPT adapters), exact-fp32 MFMA
     void linear_f32(const float* x, int lda, const float* w, float* y, int ldc, int M, int N, int K, const a3r_epilogue& e) {
@@ -620,93 +506,65 @@ struct Plan {
     }
     // the same-shape projection of both decoders (dec_blocks[i] on view 1, dec_blocks2[i] on view 2) in one launch
     void linear2(const float* x0, const float* x1, int lda, const float* w0, const float* w1, const float* b0, const float* b1,
-                 float* y0, float* y1, int ldc, int M, int N, int K, a3r_epilogue e, const float* r0 = nullptr,
-                 const float* r1 = nullptr) {
+                 float* y0, float* y1, int ldc, int M, int N, int K, const OpEpi& e0, const float* r0 = nullptr, const float* r1 = nullptr) {
         if (skip()) return;
         traced("linear2", M, N, K);
-        if (fh2()) {
-            const auto *w20 = twin2(w0), *w21 = twin2(w1);
-            if (!w20 || !w21) return;
-            // the two sides' outputs are ONE site (one scale: the attention kernel reads both sides in one launch)
-            Site so = {1.f, nullptr};
-            if (e.out_fh2) so = site(y0, y1);
-            a3r_group_ptrs_fh2 g[2] = {{x0, w20->first, y0, b0, r0, nullptr, w20->second, scale_of(x0), so.scale, so.stat},
-                                       {x1, w21->first, y1, b1, r1, nullptr, w21->second, scale_of(x1), so.scale, so.stat}};
-            if (!rc) rc = a3r_linear_fh2_grouped(g, 2, ldc, M, N, K, &e, stream);
-        } else if (bf3()) {
-            const void *w30 = twin(w0), *w31 = twin(w1);
-            if (!w30 || !w31) return;
-            a3r_group_ptrs_bf3 g[2] = {{x0, w30, y0, b0, r0, nullptr}, {x1, w31, y1, b1, r1, nullptr}};
-            e.x_pair = pair ? 1 : 0;
-            rc = a3r_linear_bf3_grouped(g, 2, ldc, M, N, K, &e, stream);
-        } else {
-            a3r_group_ptrs g[2] = {{x0, w0, y0, b0, r0, nullptr}, {x1, w1, y1, b1, r1, nullptr}};
-            rc = a3r_linear_grouped(g, 2, lda, ldc, M, N, K, &e, stream);
-        }
+        const Twin *t0 = twin(w0, gf), *t1 = twin(w1, gf);
+        if (rc) return;
+        const bool fh2 = gf == Form::FH2;
+        // the two sides' outputs are ONE site (one scale: the attention kernel reads both sides in one launch)
+        const Site so = fh2 && e0.out_op ? site(y0, y1) : Site{1.f, nullptr};
+        const GroupSide g[2] = {{x0, w0, t0, y0, b0, r0, fh2 ? scale_of(x0) : 1.f}, {x1, w1, t1, y1, b1, r1, fh2 ? scale_of(x1) : 1.f}};
+        a3r_epilogue e = retarget(e0, gf, [](a3r_epilogue&) {});      // (the grouped entry point takes the range fields per side)
+        e.x_pair = pair ? 1 : 0;
+        if (!rc) rc = op_linear_grouped(gf, g, so.scale, so.stat, lda, ldc, M, N, K, e, stream);
     }
-    // ---- bf3-mode helpers of the DPT heads
-    float* alloc3(size_t rows, int K) { return ar.alloc(cf2() ? rows * K : rows * K * 3 / 2); }      // a conv-input [rows, K] buffer (bf3 or fh2 form)
-    void split(const float* x, float* y3, long M, int K) {
-        if (skip()) return;
-        traced("split_map", (int)M, K);
-        if (cf2()) {
-            const Site s = site(y3);
-            rc = a3r_split_fh2(x, K, y3, M, K, s.scale, s.stat, stream);
-        } else rc = a3r_split_bf3(x, K, y3, M, K, stream);
-    }
-    void conv3(const float* x3, const float* wp, float* y, int B, int H, int W, int Cin, int Cout, int stride, const a3r_epilogue& e0) {
+    // ---- the DPT heads' ops on maps in operand form
+    void conv_map(const float* xm, const float* wp, float* y, int B, int H, int W, int Cin, int Cout, int stride, const OpEpi& e0) {
         if (skip()) return;
         traced("conv3x3_map", H, W, Cin);
-        if (cf2()) {
-            const auto* w2 = twin2(wp);
-            a3r_epilogue e = map_epi(e0);
-            range_epi(e, x3, y);
-            if (w2 && !rc) rc = a3r_conv3x3_fh2(x3, w2->first, w2->second, y, B, H, W, Cin, Cout, stride, &e, stream);
-            return;
-        }
-        const void* w3 = twin(wp);
-        if (w3) rc = a3r_conv3x3_bf3(x3, w3, y, B, H, W, Cin, Cout, stride, &e0, stream);
+        const Twin* tw = twin(wp, mf);
+        const a3r_epilogue e = retarget(e0, mf, [&](a3r_epilogue& r) { range_epi(r, xm, y); });
+        if (!rc) rc = op_conv3x3(mf, xm, wp, tw, y, B, H, W, Cin, Cout, stride, e, stream);
     }
-    void up3(const float* x, float* y3, int B, int H, int W, int C, int Hc, int Wc) {
+    void up_map(const float* x, float* ym, int B, int H, int W, int C, int Hc, int Wc) {
         if (skip()) return;
         traced("upsample2x_map", H, W, C);
-        if (cf2()) {
-            const Site s = site(y3);
-            rc = a3r_upsample2x_fh2(x, y3, B, H, W, C, Hc, Wc, s.scale, s.stat, stream);
-        } else rc = a3r_upsample2x_bf3(x, y3, B, H, W, C, Hc, Wc, stream);
+        const Site s = out_site(mf, ym);
+        if (!rc) rc = op_upsample2x(mf, x, ym, B, H, W, C, Hc, Wc, s.scale, s.stat, stream);
     }
-    // LayerNorm whose output feeds a GEMM (written directly in bf3 form in bf3 mode)
+    // LayerNorm whose output feeds a GEMM (written directly in the GEMMs' operand form)
     void ln(const float* x, const float* w, const float* b, float* yg, int M, int D) {
         if (skip()) return;
         traced("layernorm", M, D);
-        if (fh2()) {
+        if (gf == Form::FH2) {
             // static scale (ln_static_scale): no statistics, the kernel keeps its one-row-per-wave grid
             auto it = m->ln_scale.find(w);
             const float sc = it == m->ln_scale.end() ? 1.f : it->second;
             buf_scale[yg] = sc;
             rc = a3r_layernorm_fh2(x, w, b, yg, M, D, 1e-6f, sc, nullptr, stream);
-        } else rc = bf3() ? a3r_layernorm_bf3(x, w, b, yg, M, D, 1e-6f, pair, stream) : a3r_layernorm(x, w, b, yg, M, D, 1e-6f, stream);
+        } else rc = gf == Form::BF3 ? a3r_layernorm_bf3(x, w, b, yg, M, D, 1e-6f, pair, stream) : a3r_layernorm(x, w, b, yg, M, D, 1e-6f, stream);
     }
     void ln_f32(const float* x, const float* w, const float* b, float* y, int M, int D) {
         if (skip()) return;
         traced("layernorm_f32", M, D);
         rc = a3r_layernorm(x, w, b, y, M, D, 1e-6f, stream);
     }
-    // q, k, v, o are gin buffers (bf3 mode: straight from / to the projection GEMMs, no fp32 round trip)
+    // q, k, v, o are gin buffers (operand forms: straight from / to the projection GEMMs, no fp32 round trip)
     // kv_buf: the buffer k and v are columns of when it is not q's (cross-attention); o_alias: the second side's rows of o when the
     // consumer addresses them by their own pointer (linear2)
     void attn(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o, int ldo, int B, int H, int Nq, int Nk,
               const float* kv_buf = nullptr, const float* o_alias = nullptr) {
         if (skip()) return;
         traced("attention", B, Nq, Nk);
-        if (fh2()) {
+        if (gf == Form::FH2) {
             const float sq = scale_of(q), skv = kv_buf ? scale_of(kv_buf) : sq;
             const Site so = site(o, o_alias);
             const a3r_fh2_attn_range r = {sq, skv, skv, so.scale, so.stat};
             if (!rc) rc = a3r_attention_fh2(q, ldq, k, ldk, v, ldv, o, ldo, B, H, Nq, Nk, &r, stream);
             return;
         }
-        rc = bf3() ? a3r_attention_bf3(q, ldq, k, ldk, v, ldv, o, ldo, B, H, Nq, Nk, pair, stream)
+        rc = gf == Form::BF3 ? a3r_attention_bf3(q, ldq, k, ldk, v, ldv, o, ldo, B, H, Nq, Nk, pair, stream)
                    : a3r_attention(q, ldq, k, ldk, v, ldv, o, ldo, B, H, Nq, Nk, stream);
     }
     void conv(const float* x, const float* wp, float* y, int B, int H, int W, int Cin, int Cout, int stride, const a3r_epilogue& e) {
@@ -720,10 +578,9 @@ struct Plan {
         rc = a3r_upsample2x(x, y, B, H, W, C, Hc, Wc, stream);
     }
     // projection feeding attention: RoPE on the leading columns, output in gin form
-    a3r_epilogue rope_epi(const float* bias, int rope_cols, int ntok, int gw) {
-        a3r_epilogue e = epi(A3R_EPI_ROPE, bias);
-        if (fh2()) e.out_fh2 = 1;
-        else e.out_bf3 = bf3() ? 1 : 0;
+    OpEpi rope_epi(const float* bias, int rope_cols, int ntok, int gw) {
+        OpEpi e = epi(A3R_EPI_ROPE, bias);
+        e.out_op = 1;
         e.rope_cols = rope_cols; e.tokens_per_image = ntok; e.grid_w = gw;
         e.rope_cos = m->rope_cos; e.rope_sin = m->rope_sin;
         return e;
@@ -740,11 +597,10 @@ struct Plan {
         linear(att, D, w.projw, x, D, M, D, D, epi(A3R_EPI_RESID, w.projb, resid_src));
     }
     // hid: gin [M, hidden] -- fc1's GELU epilogue writes the GEMM-input form directly (Mlp blocks.py:73-77)
-    a3r_epilogue gin_epi(int kind, const float* bias) {
-        a3r_epilogue e = epi(kind, bias);
-        if (fh2()) { e.out_fh2 = 1; return e; }
-        e.out_bf3 = bf3() ? 1 : 0;
-        e.out_pair = (bf3() && pair) ? 1 : 0;
+    OpEpi gin_epi(int kind, const float* bias) {
+        OpEpi e = epi(kind, bias);
+        e.out_op = 1;
+        e.out_pair = pair ? 1 : 0;
         return e;
     }
     void mlp(const BlockW& w, const float* nw, const float* nb, float* x, int M, int D, int hidden, float* xn, float* hid) {
@@ -756,10 +612,10 @@ struct Plan {
 
 // rcu (dpt_block.py:120-142): out = conv2(relu(conv1(relu(x)))) + x (+ extra)
 void rcu(Plan& P, const RcuW& w, const float* x, const float* extra, float* tmp, float* out, int B, int H, int W, int F) {
-    a3r_epilogue e1 = P.epi(A3R_EPI_RELU, w.c1b);
+    OpEpi e1 = P.epi(A3R_EPI_RELU, w.c1b);
     e1.relu_a = 1;
     P.conv(x, w.c1w, tmp, B, H, W, F, F, 1, e1);
-    a3r_epilogue e2 = extra ? P.epi(A3R_EPI_RESID2, w.c2b, x, extra) : P.epi(A3R_EPI_RESID, w.c2b, x);
+    OpEpi e2 = extra ? P.epi(A3R_EPI_RESID2, w.c2b, x, extra) : P.epi(A3R_EPI_RESID, w.c2b, x);
     P.conv(tmp, w.c2w, out, B, H, W, F, F, 1, e2);
 }
 
@@ -786,31 +642,31 @@ float* fusion(Plan& P, const FusionW& w, const float* x0, const float* x1, bool 
     return r;
 }
 
-// ---- the same blocks on the bf3 kernels.  A conv input lives in bf3 form; where the fp32 value is also needed (skip
-// connections) the producer writes both (aux_bf3), pre-activated when the consumer is an RCU (which starts with a ReLU).
-// x: fp32 [B,H,W,F]; xr3: bf3 of relu(x); tmp3: bf3 scratch; out: fp32; out_r3: bf3 of relu(out) or null
-// (aux_relu = false: out_r3 is the bf3 form of out itself, for a consumer that does not start with a ReLU)
-void rcu_bf3(Plan& P, const RcuW& w, const float* x, const float* xr3, const float* extra, float* tmp3, float* out, float* out_r3,
+// ---- the same blocks on maps in operand form (bf3 or fh2).  A conv input lives in operand form; where the fp32 value is also needed
+// (skip connections) the producer writes both (aux_op), pre-activated when the consumer is an RCU (which starts with a ReLU).
+// x: fp32 [B,H,W,F]; xr3: operand form of relu(x); tmp3: operand-form scratch; out: fp32; out_r3: operand form of relu(out) or null
+// (aux_relu = false: out_r3 is the operand form of out itself, for a consumer that does not start with a ReLU)
+void rcu_map(Plan& P, const RcuW& w, const float* x, const float* xr3, const float* extra, float* tmp3, float* out, float* out_r3,
              int B, int H, int W, int F, bool aux_relu = true) {
-    a3r_epilogue e1 = P.epi(A3R_EPI_RELU, w.c1b);
-    e1.out_bf3 = 1;
-    P.conv3(xr3, w.c1w, tmp3, B, H, W, F, F, 1, e1);
-    a3r_epilogue e2 = extra ? P.epi(A3R_EPI_RESID2, w.c2b, x, extra) : P.epi(A3R_EPI_RESID, w.c2b, x);
-    if (out_r3) { e2.aux_bf3 = out_r3; e2.aux_relu = aux_relu ? 1 : 0; }
-    P.conv3(tmp3, w.c2w, out, B, H, W, F, F, 1, e2);
+    OpEpi e1 = P.epi(A3R_EPI_RELU, w.c1b);
+    e1.out_op = 1;
+    P.conv_map(xr3, w.c1w, tmp3, B, H, W, F, F, 1, e1);
+    OpEpi e2 = extra ? P.epi(A3R_EPI_RESID2, w.c2b, x, extra) : P.epi(A3R_EPI_RESID, w.c2b, x);
+    if (out_r3) { e2.aux_op = out_r3; e2.aux_relu = aux_relu ? 1 : 0; }
+    P.conv_map(tmp3, w.c2w, out, B, H, W, F, F, 1, e2);
 }
 
-// returns fp32 [B, Hc, Wc, F], or its bf3 form when `last` (refinenet1's output only feeds head.0's 3x3 conv)
-float* fusion_bf3(Plan& P, const FusionW& w, const float* x0, const float* x0r3, const float* x1, const float* x1r3, bool two, int B,
+// returns fp32 [B, Hc, Wc, F], or its operand form when `last` (refinenet1's output only feeds head.0's 3x3 conv)
+float* fusion_map(Plan& P, const FusionW& w, const float* x0, const float* x0r3, const float* x1, const float* x1r3, bool two, int B,
                   int H, int W, int F, int Hc, int Wc, bool last) {
     Arena& ar = P.ar;
     const size_t px = (size_t)B * H * W, n = px * F;
-    float* tmp3 = P.alloc3(px, F);
+    float* tmp3 = P.map_alloc(px, F);
     const float *cur, *cur3;
     if (two) {
         float* s = ar.alloc(n);
-        float* sr3 = P.alloc3(px, F);
-        rcu_bf3(P, w.r1, x1, x1r3, x0, tmp3, s, sr3, B, H, W, F);     // output + resConfUnit1(xs[1])
+        float* sr3 = P.map_alloc(px, F);
+        rcu_map(P, w.r1, x1, x1r3, x0, tmp3, s, sr3, B, H, W, F);     // output + resConfUnit1(xs[1])
         cur = s; cur3 = sr3;
     } else {
         cur = x0; cur3 = x0r3;
@@ -818,13 +674,13 @@ float* fusion_bf3(Plan& P, const FusionW& w, const float* x0, const float* x0r3,
     static const bool ref_order = getenv("A3R_DPT_REF_ORDER") != nullptr;    // A/B switch: up-sample first, as the reference does
     if (ref_order) {
         float* o = ar.alloc(n);
-        rcu_bf3(P, w.r2, cur, cur3, nullptr, tmp3, o, nullptr, B, H, W, F);
+        rcu_map(P, w.r2, cur, cur3, nullptr, tmp3, o, nullptr, B, H, W, F);
         const size_t opx = (size_t)B * Hc * Wc;
-        float* u3 = P.alloc3(opx, F);
-        P.up3(o, u3, B, H, W, F, Hc, Wc);
-        a3r_epilogue e = P.epi(A3R_EPI_NONE, w.ob);
+        float* u3 = P.map_alloc(opx, F);
+        P.up_map(o, u3, B, H, W, F, Hc, Wc);
+        OpEpi e = P.epi(A3R_EPI_NONE, w.ob);
         float* r;
-        if (last) { r = P.alloc3(opx, F); e.out_bf3 = 1; }
+        if (last) { r = P.map_alloc(opx, F); e.out_op = 1; }
         else r = ar.alloc(opx * F);
         P.linear(u3, F, w.ow, r, F, (int)opx, F, F, e, /*plain_x=*/true);
         return r;
@@ -833,15 +689,15 @@ float* fusion_bf3(Plan& P, const FusionW& w, const float* x0, const float* x0r3,
     // different axes (channels / pixels) and the interpolation weights sum to one, so conv(up(x)) + b == up(conv(x) + b) up
     // to fp32 rounding -- a quarter of the 1x1 GEMM's rows, and the full-resolution map is written once instead of three times.
     float* o = ar.alloc(n);
-    float* o3 = P.alloc3(px, F);
-    rcu_bf3(P, w.r2, cur, cur3, nullptr, tmp3, o, o3, B, H, W, F, /*aux_relu=*/false);
+    float* o3 = P.map_alloc(px, F);
+    rcu_map(P, w.r2, cur, cur3, nullptr, tmp3, o, o3, B, H, W, F, /*aux_relu=*/false);
     float* lo = ar.alloc(n);
     P.linear(o3, F, w.ow, lo, F, (int)px, F, F, P.epi(A3R_EPI_NONE, w.ob), /*plain_x=*/true);
     const size_t opx = (size_t)B * Hc * Wc;
     float* r;
     if (last) {
-        r = P.alloc3(opx, F);
-        P.up3(lo, r, B, H, W, F, Hc, Wc);
+        r = P.map_alloc(opx, F);
+        P.up_map(lo, r, B, H, W, F, Hc, Wc);
     } else {
         r = ar.alloc(opx * F);
         P.up(lo, r, B, H, W, F, Hc, Wc);
@@ -862,15 +718,15 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
         int prev; bool on;
         ProductsGuard(bool on_, int p) : prev(6), on(on_) { if (on) prev = a3r_bf3_set_products(p); }
         ~ProductsGuard() { if (on) a3r_bf3_set_products(prev); }
-    } products_guard(!dry && m->use_bf3, m->products);
+    } products_guard(!dry && m->gemm_form != Form::F32, m->products);
     struct PassesGuard {
         int prev; bool on;
         PassesGuard(bool on_, int p) : prev(3), on(on_) { if (on) prev = a3r_fh2_set_passes(p); }
         ~PassesGuard() { if (on) a3r_fh2_set_passes(prev); }
-    } passes_guard(!dry && m->use_bf3 && m->use_fh2, m->fh2_passes);
+    } passes_guard(!dry && m->gemm_form == Form::FH2, m->fh2_passes);
     Plan P;
-    P.m = m; P.stream = stream; P.phase = phase;
-    if (!dry && m->use_bf3 && m->use_fh2) {
+    P.m = m; P.stream = stream; P.phase = phase; P.gf = m->gemm_form; P.mf = m->map_form;
+    if (!dry && P.gf == Form::FH2) {
         if (hipMemsetAsync(m->stats, 0, (size_t)a3r_model_s::MAX_SITES * 4, as_stream(stream)) != hipSuccess) {
             set_error("a3r_model_forward: clearing the range statistics failed");
             return A3R_EHIP;
@@ -883,7 +739,7 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
         ~SitesGuard() { if (on) m->last_sites = P->site_no < a3r_model_s::MAX_SITES ? P->site_no : a3r_model_s::MAX_SITES; }
     } sites_guard{m, &P, !dry};
     static const bool plain_act = getenv("A3R_BF3_PLAIN_ACT") != nullptr;      // A/B switch: keep every activation in plain rows
-    P.pair = m->use_bf3 && !m->use_fh2 && BN % 2 == 0 && !plain_act;
+    P.pair = P.gf == Form::BF3 && BN % 2 == 0 && !plain_act;
     P.ar = {static_cast<char*>(ws), 0, ws_bytes, dry, 0};
     Arena& ar = P.ar;
     if (phase == 1) {
@@ -893,7 +749,7 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
         float* cols3 = P.gin_scratch(BN, 768);
         float* x = ar.alloc((size_t)BN * E);
         float* xn = P.gin_alloc(BN, E);
-        float* qkv = P.att_alloc(BN, 3 * E);
+        float* qkv = P.gin_alloc(BN, 3 * E);
         float* att = P.gin_alloc(BN, E);
         float* hid = P.gin_alloc(BN, E * c.mlp_ratio);
         if (!dry) {
@@ -946,7 +802,7 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
         float* cols3 = P.gin_scratch(M2, 768);
         float* x = ar.alloc((size_t)M2 * E);
         float* xn = P.gin_alloc(M2, E);
-        float* qkv = P.att_alloc(M2, 3 * E);
+        float* qkv = P.gin_alloc(M2, 3 * E);
         float* att = P.gin_alloc(M2, E);
         float* hid = P.gin_alloc(M2, E * c.mlp_ratio);
         if (!dry) {
@@ -977,9 +833,9 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
         const int hidden = D * c.mlp_ratio;
         float* xn = P.gin_alloc(M2, D);
         float* yn = P.gin_alloc(M2, D);
-        float* qkv = P.att_alloc(M2, 3 * D);
-        float* qb = P.att_alloc(M2, D);
-        float* kv = P.att_alloc(M2, 2 * D);
+        float* qkv = P.gin_alloc(M2, 3 * D);
+        float* qb = P.gin_alloc(M2, D);
+        float* kv = P.gin_alloc(M2, 2 * D);
         float* att = P.gin_alloc(M2, D);
         float* hid = P.gin_alloc(M2, hidden);
         float* pc3 = P.gin_scratch(M2, D);
@@ -1012,7 +868,7 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
                 P.ln(x0, w0.n1w, w0.n1b, xn, BN, D);
                 P.ln(x1, w1.n1w, w1.n1b, xn1, BN, D);
                 float* att1 = P.gin_at(att, BN, D);
-                P.linear2(xn, xn1, D, w0.qkvw, w1.qkvw, w0.qkvb, w1.qkvb, qkv, P.att_at(qkv, BN, 3 * D), 3 * D, BN, 3 * D, D,
+                P.linear2(xn, xn1, D, w0.qkvw, w1.qkvw, w0.qkvb, w1.qkvb, qkv, P.gin_at(qkv, BN, 3 * D), 3 * D, BN, 3 * D, D,
                           P.rope_epi(nullptr, 2 * D, N, nw));
                 P.attn(qkv, 3 * D, P.gin_col(qkv, D), 3 * D, P.gin_col(qkv, 2 * D), 3 * D, att, D, 2 * B, c.dec_num_heads, N, N, nullptr, att1);
                 P.linear2(att, att1, D, w0.projw, w1.projw, w0.projb, w1.projb, o0, o1, D, BN, D, D,
@@ -1022,8 +878,8 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
                 P.ln(x0, w1.nyw, w1.nyb, yn1, BN, D);
                 P.ln(o0, w0.n2w, w0.n2b, xn, BN, D);
                 P.ln(o1, w1.n2w, w1.n2b, xn1, BN, D);
-                P.linear2(xn, xn1, D, w0.qw, w1.qw, w0.qb, w1.qb, qb, P.att_at(qb, BN, D), D, BN, D, D, P.rope_epi(nullptr, D, N, nw));
-                P.linear2(yn, yn1, D, w0.kvw, w1.kvw, w0.kvb, w1.kvb, kv, P.att_at(kv, BN, 2 * D), 2 * D, BN, 2 * D, D,
+                P.linear2(xn, xn1, D, w0.qw, w1.qw, w0.qb, w1.qb, qb, P.gin_at(qb, BN, D), D, BN, D, D, P.rope_epi(nullptr, D, N, nw));
+                P.linear2(yn, yn1, D, w0.kvw, w1.kvw, w0.kvb, w1.kvb, kv, P.gin_at(kv, BN, 2 * D), 2 * D, BN, 2 * D, D,
                           P.rope_epi(nullptr, D, N, nw));
                 P.attn(qb, D, kv, 2 * D, P.gin_col(kv, D), 2 * D, att, D, 2 * B, c.dec_num_heads, N, N, kv, att1);
                 P.linear2(att, att1, D, w0.cprojw, w1.cprojw, w0.cprojb, w1.cprojb, o0, o1, D, BN, D, D,
@@ -1071,7 +927,7 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
         // act_postprocess (dpt_block.py:353-405)
         // 1x1 adapters: in fh2 mode a split pass + the fh2 GEMM (5x the exact-fp32 MFMA kernel's rate) instead of a3r_linear
         auto adapter = [&](const float* t, int K, const float* w, const float* b, float* y, int N) {
-            if (!P.fh2()) { P.linear_f32(t, K, w, y, N, BN, N, K, P.epi(A3R_EPI_NONE, b)); return; }
+            if (P.gf != Form::FH2) { P.linear_f32(t, K, w, y, N, BN, N, K, P.epi(A3R_EPI_NONE, b)); return; }
             const size_t keep = ar.off;
             float* t2 = P.gin_scratch(BN, K);
             P.linear(P.gin_from(t, t2, BN, K), K, w, y, N, BN, N, K, P.epi(A3R_EPI_NONE, b));
@@ -1081,7 +937,7 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
         adapter(t0, E, Hd.a0w, Hd.a0b, a0, ld[0]);
         float* l0 = ar.alloc((size_t)BN * 16 * ld[0]);
         {
-            a3r_epilogue e = P.epi(A3R_EPI_PIXSHUF, Hd.a0tb);
+            OpEpi e = P.epi(A3R_EPI_PIXSHUF, Hd.a0tb);
             e.ps_s = 4; e.ps_h = nh; e.ps_w = nw; e.ps_cout = ld[0];
             P.linear_f32(a0, ld[0], Hd.a0tw, l0, ld[0], BN, 16 * ld[0], ld[0], e);
         }
@@ -1089,7 +945,7 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
         adapter(t1, D, Hd.a1w, Hd.a1b, a1, ld[1]);
         float* l1 = ar.alloc((size_t)BN * 4 * ld[1]);
         {
-            a3r_epilogue e = P.epi(A3R_EPI_PIXSHUF, Hd.a1tb);
+            OpEpi e = P.epi(A3R_EPI_PIXSHUF, Hd.a1tb);
             e.ps_s = 2; e.ps_h = nh; e.ps_w = nw; e.ps_cout = ld[1];
             P.linear_f32(a1, ld[1], Hd.a1tw, l1, ld[1], BN, 4 * ld[1], ld[1], e);
         }
@@ -1097,20 +953,20 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
         adapter(t2, D, Hd.a2w, Hd.a2b, l2, ld[2]);
         float* a3 = ar.alloc((size_t)BN * ld[3]);
         adapter(t3, D, Hd.a3w, Hd.a3b, a3, ld[3]);
-        float* l3 = P.map_alloc((size_t)B * h3 * w3, ld[3]);          // only feeds layer4_rn's conv: bf3 in bf3 mode
-        if (!P.bf3()) {
+        float* l3 = P.map_alloc((size_t)B * h3 * w3, ld[3]);          // only feeds layer4_rn's conv: in map form
+        if (P.mf == Form::F32) {
             P.conv(a3, Hd.a3cw, l3, B, nh, nw, ld[3], ld[3], 2, P.epi(A3R_EPI_NONE, Hd.a3cb));
         } else {
-            float* a33 = P.alloc3(BN, ld[3]);
-            P.split(a3, a33, BN, ld[3]);
-            a3r_epilogue e = P.epi(A3R_EPI_NONE, Hd.a3cb);
-            e.out_bf3 = 1;
-            P.conv3(a33, Hd.a3cw, l3, B, nh, nw, ld[3], ld[3], 2, e);
+            float* a33 = P.map_alloc(BN, ld[3]);
+            P.split_map(a3, a33, BN, ld[3]);
+            OpEpi e = P.epi(A3R_EPI_NONE, Hd.a3cb);
+            e.out_op = 1;
+            P.conv_map(a33, Hd.a3cw, l3, B, nh, nw, ld[3], ld[3], 2, e);
         }
         float* h2 = nullptr;
         bool fused_tail = false;
         const int Hh = 8 * nh, Wh = 8 * nw;
-        if (!P.bf3()) {
+        if (P.mf == Form::F32) {
             // scratch.layer_rn (no bias)
             float* r0 = ar.alloc((size_t)BN * 16 * F);
             P.conv(l0, Hd.rn[0], r0, B, 4 * nh, 4 * nw, ld[0], F, 1, P.epi(A3R_EPI_NONE, nullptr));
@@ -1134,47 +990,47 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
             P.conv(hu, Hd.h2w, h2, B, H, W, F / 2, L, 1, P.epi(A3R_EPI_RELU, Hd.h2b));
 
         } else {
-            // conv inputs in bf3 form (small maps: plain split passes)
-            float* l03 = P.alloc3((size_t)BN * 16, ld[0]);
-            P.split(l0, l03, (long)BN * 16, ld[0]);
-            float* l13 = P.alloc3((size_t)BN * 4, ld[1]);
-            P.split(l1, l13, (long)BN * 4, ld[1]);
-            float* l23 = P.alloc3(BN, ld[2]);
-            P.split(l2, l23, BN, ld[2]);
-            // scratch.layer_rn (no bias): fp32 for the skip connection + pre-activated bf3 for the first RCU conv
+            // conv inputs in map form (small maps: plain split passes)
+            float* l03 = P.map_alloc((size_t)BN * 16, ld[0]);
+            P.split_map(l0, l03, (long)BN * 16, ld[0]);
+            float* l13 = P.map_alloc((size_t)BN * 4, ld[1]);
+            P.split_map(l1, l13, (long)BN * 4, ld[1]);
+            float* l23 = P.map_alloc(BN, ld[2]);
+            P.split_map(l2, l23, BN, ld[2]);
+            // scratch.layer_rn (no bias): fp32 for the skip connection + pre-activated map form for the first RCU conv
             float* r0 = ar.alloc((size_t)BN * 16 * F);
-            float* r0r3 = P.alloc3((size_t)BN * 16, F);
+            float* r0r3 = P.map_alloc((size_t)BN * 16, F);
             float* r1 = ar.alloc((size_t)BN * 4 * F);
-            float* r1r3 = P.alloc3((size_t)BN * 4, F);
+            float* r1r3 = P.map_alloc((size_t)BN * 4, F);
             float* r2 = ar.alloc((size_t)BN * F);
-            float* r2r3 = P.alloc3(BN, F);
+            float* r2r3 = P.map_alloc(BN, F);
             float* r3 = ar.alloc((size_t)B * h3 * w3 * F);
-            float* r3r3 = P.alloc3((size_t)B * h3 * w3, F);
-            auto rn_epi = [&](float* aux) { a3r_epilogue e = P.epi(A3R_EPI_NONE, nullptr); e.aux_bf3 = aux; e.aux_relu = 1; return e; };
-            P.conv3(l03, Hd.rn[0], r0, B, 4 * nh, 4 * nw, ld[0], F, 1, rn_epi(r0r3));
-            P.conv3(l13, Hd.rn[1], r1, B, 2 * nh, 2 * nw, ld[1], F, 1, rn_epi(r1r3));
-            P.conv3(l23, Hd.rn[2], r2, B, nh, nw, ld[2], F, 1, rn_epi(r2r3));
-            P.conv3(l3, Hd.rn[3], r3, B, h3, w3, ld[3], F, 1, rn_epi(r3r3));      // l3 is bf3 in this mode
+            float* r3r3 = P.map_alloc((size_t)B * h3 * w3, F);
+            auto rn_epi = [&](float* aux) { OpEpi e = P.epi(A3R_EPI_NONE, nullptr); e.aux_op = aux; e.aux_relu = 1; return e; };
+            P.conv_map(l03, Hd.rn[0], r0, B, 4 * nh, 4 * nw, ld[0], F, 1, rn_epi(r0r3));
+            P.conv_map(l13, Hd.rn[1], r1, B, 2 * nh, 2 * nw, ld[1], F, 1, rn_epi(r1r3));
+            P.conv_map(l23, Hd.rn[2], r2, B, nh, nw, ld[2], F, 1, rn_epi(r2r3));
+            P.conv_map(l3, Hd.rn[3], r3, B, h3, w3, ld[3], F, 1, rn_epi(r3r3));      // l3 is in map form already
             // refinement (dpt_head.py:57-60)
-            float* p4 = fusion_bf3(P, Hd.ref[3], r3, r3r3, nullptr, nullptr, false, B, h3, w3, F, nh, nw, false);
-            float* p3 = fusion_bf3(P, Hd.ref[2], p4, nullptr, r2, r2r3, true, B, nh, nw, F, 2 * nh, 2 * nw, false);
-            float* p2 = fusion_bf3(P, Hd.ref[1], p3, nullptr, r1, r1r3, true, B, 2 * nh, 2 * nw, F, 4 * nh, 4 * nw, false);
-            float* p13 = fusion_bf3(P, Hd.ref[0], p2, nullptr, r0, r0r3, true, B, 4 * nh, 4 * nw, F, 8 * nh, 8 * nw, true);
+            float* p4 = fusion_map(P, Hd.ref[3], r3, r3r3, nullptr, nullptr, false, B, h3, w3, F, nh, nw, false);
+            float* p3 = fusion_map(P, Hd.ref[2], p4, nullptr, r2, r2r3, true, B, nh, nw, F, 2 * nh, 2 * nw, false);
+            float* p2 = fusion_map(P, Hd.ref[1], p3, nullptr, r1, r1r3, true, B, 2 * nh, 2 * nw, F, 4 * nh, 4 * nw, false);
+            float* p13 = fusion_map(P, Hd.ref[0], p2, nullptr, r0, r0r3, true, B, 4 * nh, 4 * nw, F, 8 * nh, 8 * nw, true);
             // head (dpt_block.py:323-330)
             float* h0 = ar.alloc((size_t)B * Hh * Wh * (F / 2));
-            P.conv3(p13, Hd.h0w, h0, B, Hh, Wh, F, F / 2, 1, P.epi(A3R_EPI_NONE, Hd.h0b));
-            float* hu3 = P.alloc3((size_t)B * H * W, F / 2);
-            P.up3(h0, hu3, B, Hh, Wh, F / 2, H, W);
-            if (P.cf2() && L == 128) {
+            P.conv_map(p13, Hd.h0w, h0, B, Hh, Wh, F, F / 2, 1, P.epi(A3R_EPI_NONE, Hd.h0b));
+            float* hu3 = P.map_alloc((size_t)B * H * W, F / 2);
+            P.up_map(h0, hu3, B, Hh, Wh, F / 2, H, W);
+            if (P.mf == Form::FH2 && L == 128) {
                 // head.2 (3x3 conv + ReLU), head.4 (1x1 conv 128 -> 4) and the postprocess in ONE launch: the [B H W, 128] map is
                 // neither written nor read back (8.4 GB per head and step at 42 pairs), dpt_block.py:323-329 + postprocess.py:10-58
-                a3r_epilogue e = P.epi(A3R_EPI_HEAD, Hd.h2b);
+                OpEpi e = P.epi(A3R_EPI_HEAD, Hd.h2b);
                 e.head_w = Hd.h4w; e.head_b = Hd.h4b; e.head_conf = s ? conf2 : conf1;
-                P.conv3(hu3, Hd.h2w, s ? pts2 : pts1, B, H, W, F / 2, L, 1, e);
+                P.conv_map(hu3, Hd.h2w, s ? pts2 : pts1, B, H, W, F / 2, L, 1, e);
                 fused_tail = true;
             } else {
                 h2 = ar.alloc((size_t)B * H * W * L);
-                P.conv3(hu3, Hd.h2w, h2, B, H, W, F / 2, L, 1, P.epi(A3R_EPI_RELU, Hd.h2b));
+                P.conv_map(hu3, Hd.h2w, h2, B, H, W, F / 2, L, 1, P.epi(A3R_EPI_RELU, Hd.h2b));
             }
         }
         if (!fused_tail && !P.skip())
@@ -1274,7 +1130,7 @@ extern "C" int a3r_model_range_check(a3r_model_t m, void* stream, int* n_adjuste
     A3R_CHECK_ARG(m && n_adjusted && n_nonfinite, "a3r_model_range_check: null argument");
     *n_adjusted = 0;
     *n_nonfinite = 0;
-    if (!(m->use_bf3 && m->use_fh2) || m->last_phase < 0 || m->last_sites <= 0) return A3R_OK;     // fp32-range modes / nothing ran
+    if (m->gemm_form != Form::FH2 || m->last_phase < 0 || m->last_sites <= 0) return A3R_OK;     // fp32-range modes / nothing ran
     std::vector<unsigned> st((size_t)m->last_sites);
     A3R_HIP(hipMemcpyAsync(st.data(), m->stats, st.size() * 4, hipMemcpyDeviceToHost, as_stream(stream)));
     A3R_HIP(hipStreamSynchronize(as_stream(stream)));

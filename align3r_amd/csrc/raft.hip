@@ -17,13 +17,9 @@
 // convex up-sampling.  BatchNorm (evaluation mode) is folded into the convolutions by the caller (align3r_amd/raft_weights.py
 // fold_batchnorm), as are the ConvNeXt layer scale (into pwconv2) and the 0.25 of the up-sampling weights (raft.py:216).
 // Maps are channels-last fp32 [B, h, w, C]; all buffers live in the caller's workspace.
-#include "common.h"
-#include <cmath>
+#include "plan.h"
 #include <cstdlib>
-#include <map>
 #include <new>
-#include <string>
-#include <vector>
 
 namespace a3r {
 
@@ -321,19 +317,17 @@ static void launch_direct_conv(const DirectConvArgs& a, hipStream_t st) {
     else hipLaunchKernelGGL(direct_conv_kernel, dim3(grid1d((long)a.B * a.Ho * ((a.Wo + DC_PX - 1) / DC_PX) * a.Cout)), dim3(256), 0, st, a);
 }
 
-struct RWRef { const float* p = nullptr; std::vector<int64_t> shape; };
-
 }  // namespace a3r
 using namespace a3r;
 
 struct a3r_raft_s {
     a3r_raft_config cfg;
-    std::map<std::string, RWRef> w;
+    WeightTable w;
     bool finalized = false;
-    std::map<std::string, const void*> twin;        // conv / linear weight name -> bf3 twin in the packed buffer (weight layout)
+    // conv / linear weight name -> its twins in the packed buffer: BOTH the bf3 image and the fh2 image (the default arithmetic), so
+    // that a3r_raft_set_arith can switch between them after finalize
+    TwinTable<std::string> twins;
     std::map<std::string, const float*> aux;        // depthwise weights transposed
-    // the same weights in fh2 form (two fp16 planes of scale * w) with their power-of-two scales: the default arithmetic (round 3)
-    std::map<std::string, std::pair<const void*, float>> twin2;
     bool use_fh2 = true;                            // a3r_raft_set_arith
     unsigned* stat = nullptr;                       // device word: max |value written in fh2 form| of the last forward (range check)
 };
@@ -408,35 +402,6 @@ std::vector<RItem> raft_pack_plan(const a3r_raft_config& c, size_t* total) {
     return v;
 }
 
-int rneed(a3r_raft_s* m, const std::string& name, std::vector<int64_t> shape, const float** out) {
-    auto it = m->w.find(name);
-    if (it == m->w.end()) { set_error("a3r_raft_finalize: missing weight '%s'", name.c_str()); return A3R_ESTATE; }
-    if (it->second.shape != shape) {
-        std::string got, want;
-        for (auto d : it->second.shape) got += std::to_string(d) + ",";
-        for (auto d : shape) want += std::to_string(d) + ",";
-        set_error("a3r_raft_finalize: weight '%s' has shape [%s] but [%s] is required", name.c_str(), got.c_str(), want.c_str());
-        return A3R_EINVAL;
-    }
-    *out = it->second.p;
-    return A3R_OK;
-}
-
-// fh2 image of one weight ([N, K] fp32 at src) with its power-of-two scale (max |w| into [2^12, 2^13))
-int pack_fh2(a3r_raft_s* m, const RItem& it, const float* src, char* pk, size_t total, void* stream) {
-    float* scratch = reinterpret_cast<float*>(pk + total - 128);
-    if (int rc = a3r_absmax(src, (long)it.N * it.K, scratch, stream)) return rc;
-    float amax = 0.f;
-    if (hipMemcpyAsync(&amax, scratch, 4, hipMemcpyDeviceToHost, as_stream(stream)) != hipSuccess || hipStreamSynchronize(as_stream(stream)) != hipSuccess) {
-        set_error("a3r_raft_finalize: reading the weight range failed");
-        return A3R_EHIP;
-    }
-    A3R_CHECK_ARG(std::isfinite(amax), "a3r_raft_finalize: weight '%s' is not finite", it.name.c_str());
-    const float scale = a3r_fh2_weight_scale(amax);
-    if (int rc = a3r_split_fh2(src, it.K, pk + it.off2, it.N, it.K, scale, nullptr, stream)) return rc;
-    m->twin2[it.name] = {pk + it.off2, scale};
-    return A3R_OK;
-}
 }  // namespace
 
 extern "C" int a3r_raft_create(const a3r_raft_config* cfg, a3r_raft_t* out) {
@@ -459,12 +424,8 @@ extern "C" int a3r_raft_destroy(a3r_raft_t m) {
 }
 
 extern "C" int a3r_raft_set_weight(a3r_raft_t m, const char* name, const float* ptr, int ndim, const int64_t* shape) {
-    A3R_CHECK_ARG(m && name && ptr && ndim >= 1 && ndim <= 4 && shape, "a3r_raft_set_weight: bad argument");
-    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(ptr) & 15) == 0, "a3r_raft_set_weight: %s is not 16-byte aligned", name);
-    RWRef r;
-    r.p = ptr;
-    r.shape.assign(shape, shape + ndim);
-    m->w[name] = r;
+    A3R_CHECK_ARG(m, "a3r_raft_set_weight: bad argument");
+    if (int rc = m->w.set("a3r_raft_set_weight", name, ptr, ndim, shape)) return rc;
     m->finalized = false;
     return A3R_OK;
 }
@@ -483,38 +444,39 @@ extern "C" int a3r_raft_finalize(a3r_raft_t m, void* packed, size_t packed_bytes
     A3R_CHECK_ARG(packed_bytes >= total, "a3r_raft_finalize: packed buffer too small (%zu < %zu)", packed_bytes, total);
     A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(packed) & 255) == 0, "a3r_raft_finalize: packed buffer must be 256-byte aligned");
     char* pk = static_cast<char*>(packed);
-    m->twin.clear();
-    m->twin2.clear();
+    m->twins.t.clear();
     m->aux.clear();
     m->stat = reinterpret_cast<unsigned*>(pk + total - 256);
+    const char* who = "a3r_raft_finalize";
+    float* scratch = reinterpret_cast<float*>(pk + total - 128);     // the absmax word of the fh2 packing
     for (const RItem& it : plan) {
         const float* src;
-        if (it.kind == 0) {
-            const int cin = it.K / 9;
-            if (int rc = rneed(m, it.name, {it.N, cin, 3, 3}, &src)) return rc;
-            float* tmp = reinterpret_cast<float*>(pk + it.tmp);
-            if (int rc = a3r_pack_conv3x3(src, tmp, it.N, cin, stream)) return rc;
-            if (int rc = a3r_split_bf3_w(tmp, it.K, pk + it.off, it.N, it.K, stream)) return rc;
-            m->twin[it.name] = pk + it.off;
-            if (int rc = pack_fh2(m, it, tmp, pk, total, stream)) return rc;
-        } else if (it.kind == 1) {
-            // Linear weights are [N, K]; 1x1 convolutions [N, K, 1, 1]
-            auto wi = m->w.find(it.name);
-            if (wi == m->w.end()) { set_error("a3r_raft_finalize: missing weight '%s'", it.name.c_str()); return A3R_ESTATE; }
-            const std::vector<int64_t>& sh = wi->second.shape;
-            const bool ok = (sh.size() == 2 && sh[0] == it.N && sh[1] == it.K) || (sh.size() == 4 && sh[0] == it.N && sh[1] == it.K && sh[2] == 1 && sh[3] == 1);
-            A3R_CHECK_ARG(ok, "a3r_raft_finalize: weight '%s' must be [%d, %d] (or [%d, %d, 1, 1])", it.name.c_str(), it.N, it.K, it.N, it.K);
-            if (int rc = a3r_split_bf3_w(wi->second.p, it.K, pk + it.off, it.N, it.K, stream)) return rc;
-            m->twin[it.name] = pk + it.off;
-            if (int rc = pack_fh2(m, it, wi->second.p, pk, total, stream)) return rc;
+        if (it.kind == 0 || it.kind == 1) {
+            if (it.kind == 0) {
+                const int cin = it.K / 9;
+                if (int rc = m->w.need(it.name, {it.N, cin, 3, 3}, who, &src)) return rc;
+                float* tmp = reinterpret_cast<float*>(pk + it.tmp);
+                if (int rc = a3r_pack_conv3x3(src, tmp, it.N, cin, stream)) return rc;
+                src = tmp;
+            } else {
+                // Linear weights are [N, K]; 1x1 convolutions [N, K, 1, 1]
+                const WeightTable::Ref* wi = m->w.find(it.name);
+                if (!wi) { set_error("a3r_raft_finalize: missing weight '%s'", it.name.c_str()); return A3R_ESTATE; }
+                const std::vector<int64_t>& sh = wi->shape;
+                const bool ok = (sh.size() == 2 && sh[0] == it.N && sh[1] == it.K) || (sh.size() == 4 && sh[0] == it.N && sh[1] == it.K && sh[2] == 1 && sh[3] == 1);
+                A3R_CHECK_ARG(ok, "a3r_raft_finalize: weight '%s' must be [%d, %d] (or [%d, %d, 1, 1])", it.name.c_str(), it.N, it.K, it.N, it.K);
+                src = wi->p;
+            }
+            if (int rc = m->twins.pack(it.name, Form::BF3, src, pk + it.off, it.N, it.K, nullptr, who, it.name.c_str(), stream)) return rc;
+            if (int rc = m->twins.pack(it.name, Form::FH2, src, pk + it.off2, it.N, it.K, scratch, who, it.name.c_str(), stream)) return rc;
         } else if (it.kind == 3) {
-            if (int rc = rneed(m, it.name, {it.N, it.K / 49, 7, 7}, &src)) return rc;
+            if (int rc = m->w.need(it.name, {it.N, it.K / 49, 7, 7}, who, &src)) return rc;
             float* wt = reinterpret_cast<float*>(pk + it.off);
             hipLaunchKernelGGL(transpose_kernel, dim3((it.N * it.K + 255) / 256), dim3(256), 0, as_stream(stream), src, wt, it.N, it.K);
             A3R_LAUNCH_CHECK();
             m->aux[it.name] = wt;
         } else {
-            if (int rc = rneed(m, it.name, {it.N, 1, 7, 7}, &src)) return rc;
+            if (int rc = m->w.need(it.name, {it.N, 1, 7, 7}, who, &src)) return rc;
             float* wt = reinterpret_cast<float*>(pk + it.off);
             hipLaunchKernelGGL(transpose_kernel, dim3((it.N * 49 + 255) / 256), dim3(256), 0, as_stream(stream), src, wt, it.N, 49);
             A3R_LAUNCH_CHECK();
@@ -527,86 +489,55 @@ extern "C" int a3r_raft_finalize(a3r_raft_t m, void* packed, size_t packed_bytes
 
 // ------------------------------------------------------------------------------------------- launch plan
 namespace {
-struct RArena {
-    char* base; size_t off, cap; bool dry; size_t peak;
-    float* alloc(size_t nfloat) {
-        const size_t o = off;
-        off = align_up(off + nfloat * 4, 256);
-        if (off > peak) peak = off;
-        return dry ? nullptr : reinterpret_cast<float*>(base + o);
-    }
-    float* alloc3(size_t rows, int K) { return alloc(rows * K * 3 / 2); }      // a bf3 [rows, K] matrix
-};
-
 struct RPlan {
     a3r_raft_s* m;
-    RArena ar;
+    Arena ar;
     void* stream;
     int rc = A3R_OK;
-    bool skip() const { return ar.dry || rc != A3R_OK; }
+    static constexpr const char* WHO = "a3r_raft_forward";
+    bool skip() { return ar.skip(rc, WHO); }
     const float* wptr(const std::string& n) {
-        auto it = m->w.find(n);
-        if (it == m->w.end()) { if (!rc) { set_error("a3r_raft_forward: missing weight '%s'", n.c_str()); rc = A3R_ESTATE; } return nullptr; }
-        return it->second.p;
+        const WeightTable::Ref* r = m->w.find(n);
+        if (!r && !rc) { set_error("a3r_raft_forward: missing weight '%s'", n.c_str()); rc = A3R_ESTATE; }
+        return r ? r->p : nullptr;
     }
     const float* auxw(const std::string& n) {
         auto it = m->aux.find(n);
         if (it == m->aux.end()) { if (!rc) { set_error("a3r_raft_forward: weight '%s' was not packed", n.c_str()); rc = A3R_ESTATE; } return nullptr; }
         return it->second;
     }
-    const void* twin(const std::string& n) {
-        auto it = m->twin.find(n);
-        if (it == m->twin.end()) { if (!rc) { set_error("a3r_raft_forward: weight '%s' was not packed", n.c_str()); rc = A3R_ESTATE; } return nullptr; }
-        return it->second;
-    }
-    a3r_epilogue epi(int kind, const float* bias, const float* resid = nullptr) {
-        a3r_epilogue e = {};
+    OpEpi epi(int kind, const float* bias, const float* resid = nullptr) {
+        OpEpi e = {};
         e.epi = kind; e.bias = bias; e.resid = resid;
         return e;
     }
-    // The plan below is written for the three-plane bf16 form ("x3" operands, out_bf3 / aux_bf3 epilogues).  With m->use_fh2 the
-    // same calls run on the fh2 kernels (3 fp16 passes instead of 6 bf16 ones, 4 instead of 6 operand bytes): operands are fh2
-    // matrices with scale 1 (they fit the buffers sized for bf3), out_bf3 / aux_bf3 mean out_fh2 / aux_fh2, and every fh2 producer
-    // reports max |stored value| into m->stat, which the caller checks against fp16's range after the forward.
-    bool fh2() const { return m->use_fh2; }
-    std::pair<const void*, float> twin2(const std::string& n) {
-        auto it = m->twin2.find(n);
-        if (it == m->twin2.end()) { if (!rc) { set_error("a3r_raft_forward: weight '%s' was not packed", n.c_str()); rc = A3R_ESTATE; } return {nullptr, 1.f}; }
-        return it->second;
-    }
-    void to_fh2(a3r_epilogue& e) {
-        e.out_fh2 = e.out_bf3; e.out_bf3 = 0;
-        e.aux_fh2 = e.aux_bf3; e.aux_bf3 = nullptr;
-        e.out_absmax = (e.out_fh2 || e.aux_fh2) ? m->stat : nullptr;
-    }
-    // 3x3 convolution `name` (weight / bias) on the bf3 / fh2 map x3 [B, H, W, Cin]
-    void conv3(const float* x3, const std::string& name, float* y, int B, int H, int W, int Cin, int Cout, int stride, a3r_epilogue e) {
-        if (skip()) return;
+    // Operands ("xo" maps and matrices, out_op / aux_op epilogues) are in form f: FH2 (3 fp16 passes, 4 operand bytes) unless
+    // a3r_raft_set_arith chose BF3 (6 bf16 passes, 6 bytes).  Every operand buffer is sized for BF3, the larger, so that the workspace
+    // layout does not depend on the arithmetic.  Range policy: fh2 operands carry scale 1 (but the correlation's, below), and every
+    // fh2 producer reports max |stored value| into the one word m->stat, which the caller checks against fp16's range after the forward.
+    Form f = Form::FH2;
+    float* alloc_op(size_t rows, int K) { return ar.alloc(form_floats(Form::BF3, rows, K)); }
+    a3r_epilogue target(const OpEpi& e0, const std::string& name) {
+        a3r_epilogue e = retarget(e0, f, [&](a3r_epilogue& r) { r.out_absmax = (r.out_fh2 || r.aux_fh2) ? m->stat : nullptr; });
         e.bias = wptr(name + ".bias");
-        if (fh2()) {
-            const auto w2 = twin2(name + ".weight");
-            to_fh2(e);
-            if (!rc) rc = a3r_conv3x3_fh2(x3, w2.first, w2.second, y, B, H, W, Cin, Cout, stride, &e, stream);
-            return;
-        }
-        const void* w3 = twin(name + ".weight");
-        if (!rc) rc = a3r_conv3x3_bf3(x3, w3, y, B, H, W, Cin, Cout, stride, &e, stream);
+        return e;
     }
-    void linear(const float* x3, const std::string& name, float* y, int ldc, long M, int N, int K, a3r_epilogue e) {
+    // 3x3 convolution `name` (weight / bias) on the operand-form map xo [B, H, W, Cin]
+    void conv3(const float* xo, const std::string& name, float* y, int B, int H, int W, int Cin, int Cout, int stride, const OpEpi& e0) {
         if (skip()) return;
-        e.bias = wptr(name + ".bias");
-        if (fh2()) {
-            const auto w2 = twin2(name + ".weight");
-            to_fh2(e);
-            if (!rc) rc = a3r_linear_fh2(x3, w2.first, w2.second, y, ldc, (int)M, N, K, &e, stream);
-            return;
-        }
-        const void* w3 = twin(name + ".weight");
-        if (!rc) rc = a3r_linear_bf3(x3, w3, y, ldc, (int)M, N, K, &e, stream);
+        const a3r_epilogue e = target(e0, name);
+        const Twin* tw = m->twins.get(name + ".weight", f, WHO, rc);
+        if (!rc) rc = op_conv3x3(f, xo, nullptr, tw, y, B, H, W, Cin, Cout, stride, e, stream);
     }
-    void split(const float* x, int ldx, float* y3, long M, int K) {
+    void linear(const float* xo, const std::string& name, float* y, int ldc, long M, int N, int K, const OpEpi& e0) {
         if (skip()) return;
-        rc = fh2() ? a3r_split_fh2(x, ldx, y3, M, K, 1.f, m->stat, stream) : a3r_split_bf3(x, ldx, y3, M, K, stream);
+        const a3r_epilogue e = target(e0, name);
+        const Twin* tw = m->twins.get(name + ".weight", f, WHO, rc);
+        if (!rc) rc = op_linear(f, xo, 0, nullptr, tw, y, ldc, (int)M, N, K, e, stream);
+    }
+    void split(const float* x, int ldx, float* yo, long M, int K) {
+        if (skip()) return;
+        rc = op_split(f, x, ldx, yo, M, K, false, 1.f, m->stat, stream);
     }
     template <class F> void launch(F&& f) {
         if (skip()) return;
@@ -619,13 +550,13 @@ struct RPlan {
 };
 
 // ResNetFPN.forward (extractor.py:338-350) after the stem: s = relu(bn1(conv1(x))) [nimg, H2, W2, C0] fp32 is given.  Writes
-// final_conv's output to out (fp32 [nimg, h, w, out_dim]) or, when out3 is given, in bf3 form to out3.
+// final_conv's output to out (fp32 [nimg, h, w, out_dim]) or, when out3 is given, in operand form to out3.
 void resnet(RPlan& P, const std::string& p, float* s, int nimg, int H2, int W2, float* out, float* out3, int out_dim) {
     const a3r_raft_config& c = P.m->cfg;
-    RArena& ar = P.ar;
+    Arena& ar = P.ar;
     int h = H2, w = W2, in_planes = c.initial_dim;
     const float* x = s;                                  // fp32 block input
-    float* x3 = ar.alloc3((size_t)nimg * h * w, in_planes);
+    float* x3 = P.alloc_op((size_t)nimg * h * w, in_planes);
     P.split(x, in_planes, x3, (long)nimg * h * w, in_planes);
     for (int li = 0; li < 3; li++) {
         const int dim = c.block_dims[li];
@@ -635,9 +566,9 @@ void resnet(RPlan& P, const std::string& p, float* s, int nimg, int H2, int W2, 
             const int ho = (h - 1) / stride + 1, wo = (w - 1) / stride + 1;
             const size_t px = (size_t)nimg * ho * wo;
             // y = relu(bn1(conv1(x)))                                                        layer.py:134
-            float* y3 = ar.alloc3(px, dim);
-            a3r_epilogue e1 = P.epi(A3R_EPI_RELU, nullptr);
-            e1.out_bf3 = 1;
+            float* y3 = P.alloc_op(px, dim);
+            OpEpi e1 = P.epi(A3R_EPI_RELU, nullptr);
+            e1.out_op = 1;
             P.conv3(x3, q + ".conv1", y3, nimg, h, w, cin, dim, stride, e1);
             // shortcut: x, or bn3(conv1x1 stride s (x))                                      layer.py:122-129,137-138
             const float* sc = x;
@@ -648,7 +579,7 @@ void resnet(RPlan& P, const std::string& p, float* s, int nimg, int H2, int W2, 
                     P.launch([&](hipStream_t st) {
                         hipLaunchKernelGGL(gather_s2_kernel, dim3(grid1d((long)px * cin / 4)), dim3(256), 0, st, x, gx, nimg, h, w, ho, wo, cin / 4);
                     });
-                    float* gx3 = ar.alloc3(px, cin);
+                    float* gx3 = P.alloc_op(px, cin);
                     P.split(gx, cin, gx3, (long)px, cin);
                     g3 = gx3;
                 }
@@ -658,16 +589,16 @@ void resnet(RPlan& P, const std::string& p, float* s, int nimg, int H2, int W2, 
             }
             // y = relu(bn2(conv2(y))); out = relu(shortcut + y)                              layer.py:135-141: ONE launch
             float* o = ar.alloc(px * dim);
-            float* o3 = ar.alloc3(px, dim);
-            a3r_epilogue e2 = P.epi(A3R_EPI_RESID, nullptr, sc);
-            e2.relu_acc = 1; e2.relu_out = 1; e2.aux_bf3 = o3;
+            float* o3 = P.alloc_op(px, dim);
+            OpEpi e2 = P.epi(A3R_EPI_RESID, nullptr, sc);
+            e2.relu_acc = 1; e2.relu_out = 1; e2.aux_op = o3;
             P.conv3(y3, q + ".conv2", o, nimg, ho, wo, dim, dim, 1, e2);
             x = o; x3 = o3; h = ho; w = wo;
         }
         in_planes = dim;
     }
-    a3r_epilogue ef = P.epi(A3R_EPI_NONE, nullptr);
-    if (out3) ef.out_bf3 = 1;
+    OpEpi ef = P.epi(A3R_EPI_NONE, nullptr);
+    if (out3) ef.out_op = 1;
     P.linear(x3, p + ".final_conv", out3 ? out3 : out, out_dim, (long)nimg * h * w, out_dim, c.block_dims[2], ef);
 }
 
@@ -684,10 +615,11 @@ int raft_plan(a3r_raft_s* m, bool dry, const float* img1, const float* img2, int
     const long hw = (long)h * w, Bhw = (long)B * hw;
     const int win = 2 * c.radius + 1, cc = c.corr_levels * win * win, ccp = (cc + 31) / 32 * 32;
     RPlan P;
-    P.m = m; P.stream = stream;
+    P.m = m; P.stream = stream; P.f = m->use_fh2 ? Form::FH2 : Form::BF3;
+    const bool fh2 = P.f == Form::FH2;
     P.ar = {static_cast<char*>(ws), 0, ws_bytes, dry, 0};
-    RArena& ar = P.ar;
-    if (!dry && m->use_fh2 && m->stat && hipMemsetAsync(m->stat, 0, 4, as_stream(stream)) != hipSuccess) {
+    Arena& ar = P.ar;
+    if (!dry && fh2 && m->stat && hipMemsetAsync(m->stat, 0, 4, as_stream(stream)) != hipSuccess) {
         set_error("a3r_raft_forward: clearing the range statistic failed");
         return A3R_EHIP;
     }
@@ -710,7 +642,7 @@ int raft_plan(a3r_raft_s* m, bool dry, const float* img1, const float* img2, int
     }
     // ---------------- persistent buffers
     float* cn = ar.alloc(Bhw * 2 * d);                  // init_conv output: [net | context]
-    float* fm3 = ar.alloc3(2 * Bhw, 2 * d);             // fnet(image1), fnet(image2) in bf3 form (rows: all of image1, then image2)
+    float* fm3 = P.alloc_op(2 * Bhw, 2 * d);             // fnet(image1), fnet(image2) in operand form (rows: all of image1, then image2)
     float* fm = ar.alloc(2 * Bhw * 2 * d);              // the same in fp32 (the pyramid's 2x2 means, the taps)
     float* corr[4] = {nullptr, nullptr, nullptr, nullptr};
     int hl[4], wl[4];
@@ -732,7 +664,7 @@ int raft_plan(a3r_raft_s* m, bool dry, const float* img1, const float* img2, int
                                 P.auxw("cnet.conv1.weight"), P.wptr("cnet.conv1.bias"), 1, s};
             launch_direct_conv(a, st);
         });
-        float* c3 = ar.alloc3(Bhw, 2 * d);
+        float* c3 = P.alloc_op(Bhw, 2 * d);
         resnet(P, "cnet", s, B, H2, W2, nullptr, c3, 2 * d);
         P.conv3(c3, "init_conv", cn, B, h, w, 2 * d, 2 * d, 1, P.epi(A3R_EPI_NONE, nullptr));
     }
@@ -776,7 +708,7 @@ int raft_plan(a3r_raft_s* m, bool dry, const float* img1, const float* img2, int
         // one wait per call.  Per image, not per batch: a pair's flow must not depend on what else is in the batch.
         std::vector<float> s1(B, 1.f), s2(B, 1.f);
         float* amx = ar.alloc(2 * B);
-        if (P.fh2() && !P.skip()) {
+        if (fh2 && !P.skip()) {
             std::vector<float> mx(2 * B, 0.f);
             hipStream_t st = as_stream(stream);
             const long n_per = hw * D;
@@ -793,9 +725,9 @@ int raft_plan(a3r_raft_s* m, bool dry, const float* img1, const float* img2, int
                 s2[b] = a3r_fh2_weight_scale(mx[B + b]);
             }
         }
-        if (P.fh2()) {
+        if (fh2) {
             for (int b = 0; b < B && !P.skip(); b++)
-                P.rc = a3r_split_fh2(f1s + (size_t)b * hw * D, D, reinterpret_cast<char*>(fm3) + (size_t)b * hw * D * 4, hw, D, s1[b], m->stat, stream);
+                P.rc = op_split(P.f, f1s + (size_t)b * hw * D, D, fm3 + form_floats(P.f, (size_t)b * hw, D), hw, D, false, s1[b], m->stat, stream);
         } else {
             P.split(f1s, D, fm3, Bhw, D);
         }
@@ -807,16 +739,13 @@ int raft_plan(a3r_raft_s* m, bool dry, const float* img1, const float* img2, int
             const long n2 = (long)hl[l] * wl[l];
             for (int b = 0; b < B; b++) {
                 if (P.skip()) break;
+                // fmap2_l[b] in the weight layout of the form, with image b's scale under fh2
+                // (the coarser levels are 2 x 2 means of level 0: their maximum is not above its, one s2 serves all levels)
                 a3r_epilogue e = {};
-                if (P.fh2()) {
-                    // (the coarser levels are 2 x 2 means of level 0: their maximum is not above its, one s2 serves all levels)
-                    e.x_scale = s1[b];
-                    P.rc = a3r_split_fh2(f2 + (size_t)b * n2 * D, D, w3, n2, D, s2[b], m->stat, stream);
-                    if (!P.rc) P.rc = a3r_linear_fh2(reinterpret_cast<char*>(fm3) + (size_t)b * hw * D * 4, w3, s2[b], corr[l] + (size_t)b * hw * n2, (int)n2, (int)hw, (int)n2, D, &e, stream);
-                    continue;
-                }
-                P.rc = a3r_split_bf3_w(f2 + (size_t)b * n2 * D, D, w3, n2, D, stream);
-                if (!P.rc) P.rc = a3r_linear_bf3(reinterpret_cast<char*>(fm3) + (size_t)b * hw * D * 6, w3, corr[l] + (size_t)b * hw * n2, (int)n2, (int)hw, (int)n2, D, &e, stream);
+                if (fh2) e.x_scale = s1[b];
+                const Twin tw = {w3, w3, s2[b]};
+                P.rc = op_split(P.f, f2 + (size_t)b * n2 * D, D, w3, n2, D, /*row_pair=*/true, s2[b], m->stat, stream);
+                if (!P.rc) P.rc = op_linear(P.f, fm3 + form_floats(P.f, (size_t)b * hw, D), 0, nullptr, &tw, corr[l] + (size_t)b * hw * n2, (int)n2, (int)hw, (int)n2, D, e, stream);
             }
             if (l + 1 < c.corr_levels) {                             // fmap2 <- interpolate(fmap2, 0.5) (corr.py:22)
                 float* dst = (f2 == f2n) ? f2m : f2n;
@@ -830,12 +759,12 @@ int raft_plan(a3r_raft_s* m, bool dry, const float* img1, const float* img2, int
     ar.off = mark;
     if (taps) for (int l = 0; l < c.corr_levels; l++) tap(taps->corr_pyr[l], corr[l], (size_t)Bhw * hl[l] * wl[l]);
     // ---------------- heads on a hidden state (raft.py:213-216, 230-231): fu = flow_head(net), wgt = .25 * upsample_weight(net)
-    float* n3 = ar.alloc3(Bhw, d);
-    float* t3 = ar.alloc3(Bhw, 2 * d);
+    float* n3 = P.alloc_op(Bhw, d);
+    float* t3 = P.alloc_op(Bhw, 2 * d);
     auto heads = [&]() {
         P.split(net, d, n3, Bhw, d);
-        a3r_epilogue er = P.epi(A3R_EPI_RELU, nullptr);
-        er.out_bf3 = 1;
+        OpEpi er = P.epi(A3R_EPI_RELU, nullptr);
+        er.out_op = 1;
         P.conv3(n3, "flow_head.0", t3, B, h, w, d, 2 * d, 1, er);
         P.conv3(t3, "flow_head.2", fu, B, h, w, 2 * d, 6, 1, P.epi(A3R_EPI_NONE, nullptr));
         P.conv3(n3, "upsample_weight.0", t3, B, h, w, d, 2 * d, 1, er);
@@ -847,18 +776,18 @@ int raft_plan(a3r_raft_s* m, bool dry, const float* img1, const float* img2, int
     P.pack_cols(flow8, 2, 0, fu, 6, 2, Bhw);                         // flow_8x = flow_update[:, :2] (raft.py:217)
     // ---------------- iterations (raft.py:225-238)
     float* lk = ar.alloc(Bhw * ccp);
-    float* lk3 = ar.alloc3(Bhw, ccp);
-    float* c13 = ar.alloc3(Bhw, 2 * d);
+    float* lk3 = P.alloc_op(Bhw, ccp);
+    float* c13 = P.alloc_op(Bhw, 2 * d);
     float* cf = ar.alloc(Bhw * 2 * d);                                // cat([cor, flo]) (update.py:113)
     float* tmp = ar.alloc(Bhw * 2 * d);
     float* f1 = ar.alloc(Bhw * d);
-    float* f13 = ar.alloc3(Bhw, d);
-    float* cf3 = ar.alloc3(Bhw, 2 * d);
+    float* f13 = P.alloc_op(Bhw, d);
+    float* cf3 = P.alloc_op(Bhw, 2 * d);
     float* dw = ar.alloc(Bhw * 3 * d);
-    float* ln3 = ar.alloc3(Bhw, 3 * d);
-    float* hid3 = ar.alloc3(Bhw, 4 * d);
+    float* ln3 = P.alloc_op(Bhw, 3 * d);
+    float* hid3 = P.alloc_op(Bhw, 4 * d);
     float* S = ar.alloc(Bhw * 3 * d);
-    float* S3 = ar.alloc3(Bhw, 3 * d);
+    float* S3 = P.alloc_op(Bhw, 3 * d);
     const std::string enc = "update_block.encoder.";
     for (int it = 0; it < iters; it++) {
         // corr = corr_fn(coords_grid + flow_8x) (raft.py:227-228)
@@ -871,8 +800,8 @@ int raft_plan(a3r_raft_s* m, bool dry, const float* img1, const float* img2, int
         if (it == 0) tap(taps ? taps->lookup0 : nullptr, lk, (size_t)Bhw * ccp);
         // BasicMotionEncoder2 (update.py:99-117)
         P.split(lk, ccp, lk3, Bhw, ccp);
-        a3r_epilogue er = P.epi(A3R_EPI_RELU, nullptr);
-        er.out_bf3 = 1;
+        OpEpi er = P.epi(A3R_EPI_RELU, nullptr);
+        er.out_op = 1;
         P.linear(lk3, enc + "convc1", c13, 2 * d, Bhw, 2 * d, ccp, er);                                     // cor = relu(convc1(corr))
         P.conv3(c13, enc + "convc2", tmp, B, h, w, 2 * d, d + d / 2, 1, P.epi(A3R_EPI_RELU, nullptr));     // cor = relu(convc2(cor))
         P.pack_cols(cf, 2 * d, 0, tmp, d + d / 2, d + d / 2, Bhw);
@@ -901,13 +830,13 @@ int raft_plan(a3r_raft_s* m, bool dry, const float* img1, const float* img2, int
                 hipLaunchKernelGGL(dwconv7_kernel, dim3(grid1d((long)B * h * ((w + 3) / 4) * 3 * d)), dim3(256), 0, st, X, wi->second, P.wptr(q + "dwconv.bias"), dw, B, h, w, 3 * d);
             });
             if (!P.skip())
-                P.rc = P.fh2() ? a3r_layernorm_fh2(dw, P.wptr(q + "norm.weight"), P.wptr(q + "norm.bias"), ln3, (int)Bhw, 3 * d, 1e-6f, 1.f, m->stat, stream)
+                P.rc = fh2 ? a3r_layernorm_fh2(dw, P.wptr(q + "norm.weight"), P.wptr(q + "norm.bias"), ln3, (int)Bhw, 3 * d, 1e-6f, 1.f, m->stat, stream)
                                : a3r_layernorm_bf3(dw, P.wptr(q + "norm.weight"), P.wptr(q + "norm.bias"), ln3, (int)Bhw, 3 * d, 1e-6f, 0, stream);
-            a3r_epilogue eg = P.epi(A3R_EPI_GELU, nullptr);
-            eg.out_bf3 = 1;
+            OpEpi eg = P.epi(A3R_EPI_GELU, nullptr);
+            eg.out_op = 1;
             P.linear(ln3, q + "pwconv1", hid3, 4 * d, Bhw, 4 * d, 3 * d, eg);
-            a3r_epilogue es = P.epi(A3R_EPI_RESID, nullptr, X);                                              // input + gamma * pwconv2(...) (gamma folded)
-            es.aux_bf3 = S3;
+            OpEpi es = P.epi(A3R_EPI_RESID, nullptr, X);                                              // input + gamma * pwconv2(...) (gamma folded)
+            es.aux_op = S3;
             P.linear(hid3, q + "pwconv2", S, 3 * d, Bhw, 3 * d, 4 * d, es);
             P.linear(S3, q + "final", net, d, Bhw, d, 3 * d, P.epi(A3R_EPI_NONE, nullptr));
         }

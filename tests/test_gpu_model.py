@@ -226,6 +226,29 @@ def test_reduced_precision_modes_state_their_tolerance(monkeypatch, mode, tol):
     assert ops.bf3_set_products(6) == 6             # the handle's mode does not leak out of its forward
 
 
+@pytest.mark.parametrize("gemm,conv", [("bf3", None), (None, "bf3")])
+def test_fp32_grade_modes_beside_the_default_hold_the_fp32_tolerance(monkeypatch, gemm, conv):
+    """The two fp32-grade combinations of operand forms that neither the default nor the tests above walk end to end:
+    A3R_GEMM=bf3 (GEMMs, attention and DPT maps all on the three-plane bf16 form, row-pair activations: B N = 48 rows is even) and
+    the default fh2 GEMMs with A3R_CONV=bf3 (the two forms side by side: fh2 tokens, bf3 maps).  Same golden, same TOL."""
+    from align3r_amd.engine import PairEngine
+    t = np.load(os.path.join(GOLDEN, "tiny_e2e.npz"))
+    H, W = 64, 96
+    v = make_view_arrays(2, H, W)
+    img1, img2 = np.concatenate([v[1][0], v[0][0]]), np.concatenate([v[0][0], v[1][0]])
+    pd1, pd2 = np.concatenate([v[1][1], v[0][1]]), np.concatenate([v[0][1], v[1][1]])
+    for name, value in (("A3R_GEMM", gemm), ("A3R_CONV", conv)):
+        if value is None:
+            monkeypatch.delenv(name, raising=False)
+        else:
+            monkeypatch.setenv(name, value)
+    eng = PairEngine(TINY, synthetic_state_dict(TINY, 0))
+    r = eng.forward(*to_dev(img1, img2, pd1, pd2))
+    errs = {k: rel_err(host(r[k]), t[f"a_{k}"]) for k in ("pts3d_1", "conf_1", "pts3d_2", "conf_2")}
+    print(gemm, conv, errs)
+    assert max(errs.values()) < TOL, errs
+
+
 @pytest.mark.parametrize("H,W,B", [(48, 80, 1), (64, 96, 2), (48, 80, 3)])
 def test_forward_stays_inside_its_buffers(tiny_engine, H, W, B):
     """Guard derived from the one GPU fault in this repository's records (gpurun_out/dbg2.log of round 1, 04:05, before the first
