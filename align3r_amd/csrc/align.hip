@@ -666,6 +666,61 @@ __global__ __launch_bounds__(PRIOR_TPB) void align_depth_prior_kernel(AlignDev d
 // (edge, side) the loss sums and the gradient sums of the TARGET camera.
 constexpr int NF = 17, NFP = 20;    // per-slot sums: S, C, d/df_t, d/dcx_t, d/dcy_t, sum gY[3], sum v (x) gY [9]
 
+// The per-(pixel, edge side) arithmetic of the pass, written once for its two kernel forms below.  They differ in who owns which pixels,
+// in the loads, the wave reduction and the loop shape, and in ONE expression: the reciprocal of flow_pixel_side (FAST_RCP).
+// The per-pixel set-up (un-projection through Rs / Ts) and the batch flush stay spelled out in each kernel: as helper functions they
+// are simplified before they are inlined, the compiler then orders the operands of Pw's sums differently, another product is fused
+// into them, and Pw changes in its last bit (seen against tests/golden/align_flow_parent.npz).
+struct FlowTarget { float r00, r01, r02, t0, r10, r11, r12, t1, r20, r21, r22, t2, ft, cxt, cyt; };      // the partner image of an edge side
+
+// (scalar loads where tx is wave-uniform)
+__device__ __forceinline__ FlowTarget load_flow_target(const float* __restrict__ tx) {
+    return {tx[0], tx[1], tx[2], tx[3], tx[4], tx[5], tx[6], tx[7], tx[8], tx[9], tx[10], tx[11], tx[12], tx[13], tx[14]};
+}
+
+// One pixel against one edge side: the 17 sums of the slot into acc, the gradient w.r.t. the pixel's world point into gw.
+// FAST_RCP: v_rcp_f32 (1 ulp) + one Newton step instead of the IEEE division's expansion (a dozen instructions per pixel side).
+template <bool FAST_RCP>
+__device__ __forceinline__ void flow_pixel_side(const FlowTarget& T, const float (&Pw)[3], float dpv, float px, float py, bool ok, float gt0,
+                                                float gt1, float pxl_thre, float (&acc)[NF], float (&gw)[3]) {
+    const float v0 = Pw[0] - T.t0, v1 = Pw[1] - T.t1, v2 = Pw[2] - T.t2;
+    const float Y0 = T.r00 * v0 + T.r10 * v1 + T.r20 * v2;        // Y = R_t^T v
+    const float Y1 = T.r01 * v0 + T.r11 * v1 + T.r21 * v2;
+    const float Y2 = T.r02 * v0 + T.r12 * v1 + T.r22 * v2;
+    const float qx = T.ft * Y0 + T.cxt * Y2, qy = T.ft * Y1 + T.cyt * Y2;
+    // the reference normalises disp*K*Y by (disp*z + 1e-6), i.e. K*Y by (z + 1e-6 / disp)
+    const float den = Y2 + 1e-6f * dpv;
+    float iz;
+    if (FAST_RCP) {
+        const float r0 = __builtin_amdgcn_rcpf(den);
+        iz = r0 * (2.f - den * r0);
+    } else {
+        iz = 1.f / den;
+    }
+    const float e0 = qx * iz - px, e1 = qy * iz - py;
+    float gn0 = 0.f, gn1 = 0.f;
+    if (ok) {
+        const float d0 = e0 - gt0, a0 = fabsf(d0), l0 = a0 < 1.f ? 0.5f * d0 * d0 : a0 - 0.5f;
+        const float d1 = e1 - gt1, a1 = fabsf(d1), l1 = a1 < 1.f ? 0.5f * d1 * d1 : a1 - 0.5f;
+        if (l0 < pxl_thre) { acc[0] += l0; acc[1] += 1.f; gn0 = a0 < 1.f ? d0 : (d0 > 0.f ? 1.f : -1.f); }
+        if (l1 < pxl_thre) { acc[0] += l1; acc[1] += 1.f; gn1 = a1 < 1.f ? d1 : (d1 > 0.f ? 1.f : -1.f); }
+    }
+    const float gq0 = gn0 * iz, gq1 = gn1 * iz, gq2 = -(gn0 * qx + gn1 * qy) * iz * iz;
+    const float gY0 = T.ft * gq0, gY1 = T.ft * gq1, gY2 = T.cxt * gq0 + T.cyt * gq1 + gq2;
+    acc[2] += gq0 * Y0 + gq1 * Y1;
+    acc[3] += gq0 * Y2;
+    acc[4] += gq1 * Y2;
+    acc[5] += gY0; acc[6] += gY1; acc[7] += gY2;
+    acc[8] += v0 * gY0; acc[9] += v0 * gY1; acc[10] += v0 * gY2;
+    acc[11] += v1 * gY0; acc[12] += v1 * gY1; acc[13] += v1 * gY2;
+    acc[14] += v2 * gY0; acc[15] += v2 * gY1; acc[16] += v2 * gY2;
+    gw[0] = T.r00 * gY0 + T.r01 * gY1 + T.r02 * gY2;              // gPw = R_t gY
+    gw[1] = T.r10 * gY0 + T.r11 * gY1 + T.r12 * gY2;
+    gw[2] = T.r20 * gY0 + T.r21 * gY1 + T.r22 * gY2;
+}
+
+// The scalar form: a thread owns PXT pixels TPB apart.  It runs when P % 4 != 0, when a buffer is misaligned, or under
+// A3R_ALIGN_FLOW=v1.
 __global__ __launch_bounds__(TPB) void align_flow_kernel(AlignDev d, const int* __restrict__ inc_ptr, const int* __restrict__ inc,
                                                           const int* __restrict__ other, const float* __restrict__ img_xf) {
     __shared__ float red[2][EB][16][NFP];
@@ -701,50 +756,17 @@ __global__ __launch_bounds__(TPB) void align_flow_kernel(AlignDev d, const int* 
         for (int kb = 0; kb < EB; kb++) {
             const int k = k0 + kb;
             if (k >= kend) break;
-            const int code = inc[k], e = code >> 1, side = code & 1, t = other[k];
-            const float* tx = img_xf + t * 16;
-            const float r00 = tx[0], r01 = tx[1], r02 = tx[2], t0 = tx[3];
-            const float r10 = tx[4], r11 = tx[5], r12 = tx[6], t1 = tx[7];
-            const float r20 = tx[8], r21 = tx[9], r22 = tx[10], t2 = tx[11];
-            const float ft = tx[12], cxt = tx[13], cyt = tx[14];
+            const int code = inc[k], e = code >> 1, side = code & 1;
+            const FlowTarget tgt = load_flow_target(img_xf + other[k] * 16);
             const float* fl = (side ? d.flow_ji : d.flow_ij) + (size_t)e * 2 * P;
-            float acc[NF];
-#pragma unroll
-            for (int j = 0; j < NF; j++) acc[j] = 0.f;
+            float acc[NF] = {};
 #pragma unroll
             for (int i = 0; i < PXT; i++) {
                 const int p = chunk * CHUNK + i * TPB + tid;
-                const float gt0 = ok[i] ? fl[p] : 0.f, gt1 = ok[i] ? fl[P + p] : 0.f;
-                const float v0 = Pw[i][0] - t0, v1 = Pw[i][1] - t1, v2 = Pw[i][2] - t2;
-                const float Y0 = r00 * v0 + r10 * v1 + r20 * v2;        // Y = R_t^T v
-                const float Y1 = r01 * v0 + r11 * v1 + r21 * v2;
-                const float Y2 = r02 * v0 + r12 * v1 + r22 * v2;
-                const float qx = ft * Y0 + cxt * Y2, qy = ft * Y1 + cyt * Y2;
-                // the reference normalises disp*K*Y by (disp*z + 1e-6), i.e. K*Y by (z + 1e-6 / disp)
-                const float den = Y2 + 1e-6f * dpv[i];
-                const float iz = 1.f / den;
-                const float e0 = qx * iz - px[i], e1 = qy * iz - py[i];
-                float gn0 = 0.f, gn1 = 0.f;
-                if (ok[i]) {
-                    const float d0 = e0 - gt0, a0 = fabsf(d0), l0 = a0 < 1.f ? 0.5f * d0 * d0 : a0 - 0.5f;
-                    const float d1 = e1 - gt1, a1 = fabsf(d1), l1 = a1 < 1.f ? 0.5f * d1 * d1 : a1 - 0.5f;
-                    if (l0 < d.pxl_thre) { acc[0] += l0; acc[1] += 1.f; gn0 = a0 < 1.f ? d0 : (d0 > 0.f ? 1.f : -1.f); }
-                    if (l1 < d.pxl_thre) { acc[0] += l1; acc[1] += 1.f; gn1 = a1 < 1.f ? d1 : (d1 > 0.f ? 1.f : -1.f); }
-                }
-                const float gq0 = gn0 * iz, gq1 = gn1 * iz, gq2 = -(gn0 * qx + gn1 * qy) * iz * iz;
-                const float gY0 = ft * gq0, gY1 = ft * gq1, gY2 = cxt * gq0 + cyt * gq1 + gq2;
-                acc[2] += gq0 * Y0 + gq1 * Y1;
-                acc[3] += gq0 * Y2;
-                acc[4] += gq1 * Y2;
-                acc[5] += gY0; acc[6] += gY1; acc[7] += gY2;
-                acc[8] += v0 * gY0; acc[9] += v0 * gY1; acc[10] += v0 * gY2;
-                acc[11] += v1 * gY0; acc[12] += v1 * gY1; acc[13] += v1 * gY2;
-                acc[14] += v2 * gY0; acc[15] += v2 * gY1; acc[16] += v2 * gY2;
-                const float gw0 = r00 * gY0 + r01 * gY1 + r02 * gY2;     // gPw = R_t gY
-                const float gw1 = r10 * gY0 + r11 * gY1 + r12 * gY2;
-                const float gw2 = r20 * gY0 + r21 * gY1 + r22 * gY2;
-                if (side) { g1[i][0] += gw0; g1[i][1] += gw1; g1[i][2] += gw2; }
-                else { g0[i][0] += gw0; g0[i][1] += gw1; g0[i][2] += gw2; }
+                float gw[3];
+                flow_pixel_side<false>(tgt, Pw[i], dpv[i], px[i], py[i], ok[i], ok[i] ? fl[p] : 0.f, ok[i] ? fl[P + p] : 0.f, d.pxl_thre, acc, gw);
+                if (side) { g1[i][0] += gw[0]; g1[i][1] += gw[1]; g1[i][2] += gw[2]; }
+                else { g0[i][0] += gw[0]; g0[i][1] += gw[1]; g0[i][2] += gw[2]; }
             }
 #pragma unroll
             for (int j = 0; j < NF; j++) {
@@ -826,48 +848,12 @@ __global__ __launch_bounds__(TPB, 4) void align_flow_vec_kernel(AlignDev d, cons
     }
     auto consume = [&](int k, const f32x4& fx, const f32x4& fy, int buf, int kb) {
         const int ku = __builtin_amdgcn_readfirstlane(k);
-        const int side = inc[ku] & 1, t = other[ku];
-        const float* tx = img_xf + t * 16;
-        const float r00 = tx[0], r01 = tx[1], r02 = tx[2], t0 = tx[3];
-        const float r10 = tx[4], r11 = tx[5], r12 = tx[6], t1 = tx[7];
-        const float r20 = tx[8], r21 = tx[9], r22 = tx[10], t2 = tx[11];
-        const float ft = tx[12], cxt = tx[13], cyt = tx[14];
-        float acc[NF], gw[PXT][3];
+        const int side = inc[ku] & 1;
+        const FlowTarget tgt = load_flow_target(img_xf + other[ku] * 16);
+        float acc[NF] = {}, gw[PXT][3];
 #pragma unroll
-        for (int j = 0; j < NF; j++) acc[j] = 0.f;
-#pragma unroll
-        for (int i = 0; i < PXT; i++) {
-            const float gt0 = ok[i] ? fx[i] : 0.f, gt1 = ok[i] ? fy[i] : 0.f;
-            const float v0 = Pw[i][0] - t0, v1 = Pw[i][1] - t1, v2 = Pw[i][2] - t2;
-            const float Y0 = r00 * v0 + r10 * v1 + r20 * v2;        // Y = R_t^T v
-            const float Y1 = r01 * v0 + r11 * v1 + r21 * v2;
-            const float Y2 = r02 * v0 + r12 * v1 + r22 * v2;
-            const float qx = ft * Y0 + cxt * Y2, qy = ft * Y1 + cyt * Y2;
-            const float den = Y2 + 1e-6f * dpv[i];
-            // v_rcp_f32 (1 ulp) + one Newton step instead of the IEEE division's expansion (a dozen instructions per pixel side)
-            const float r0 = __builtin_amdgcn_rcpf(den);
-            const float iz = r0 * (2.f - den * r0);
-            const float e0 = qx * iz - px[i], e1 = qy * iz - py[i];
-            float gn0 = 0.f, gn1 = 0.f;
-            if (ok[i]) {
-                const float d0 = e0 - gt0, a0 = fabsf(d0), l0 = a0 < 1.f ? 0.5f * d0 * d0 : a0 - 0.5f;
-                const float d1 = e1 - gt1, a1 = fabsf(d1), l1 = a1 < 1.f ? 0.5f * d1 * d1 : a1 - 0.5f;
-                if (l0 < d.pxl_thre) { acc[0] += l0; acc[1] += 1.f; gn0 = a0 < 1.f ? d0 : (d0 > 0.f ? 1.f : -1.f); }
-                if (l1 < d.pxl_thre) { acc[0] += l1; acc[1] += 1.f; gn1 = a1 < 1.f ? d1 : (d1 > 0.f ? 1.f : -1.f); }
-            }
-            const float gq0 = gn0 * iz, gq1 = gn1 * iz, gq2 = -(gn0 * qx + gn1 * qy) * iz * iz;
-            const float gY0 = ft * gq0, gY1 = ft * gq1, gY2 = cxt * gq0 + cyt * gq1 + gq2;
-            acc[2] += gq0 * Y0 + gq1 * Y1;
-            acc[3] += gq0 * Y2;
-            acc[4] += gq1 * Y2;
-            acc[5] += gY0; acc[6] += gY1; acc[7] += gY2;
-            acc[8] += v0 * gY0; acc[9] += v0 * gY1; acc[10] += v0 * gY2;
-            acc[11] += v1 * gY0; acc[12] += v1 * gY1; acc[13] += v1 * gY2;
-            acc[14] += v2 * gY0; acc[15] += v2 * gY1; acc[16] += v2 * gY2;
-            gw[i][0] = r00 * gY0 + r01 * gY1 + r02 * gY2;            // gPw = R_t gY
-            gw[i][1] = r10 * gY0 + r11 * gY1 + r12 * gY2;
-            gw[i][2] = r20 * gY0 + r21 * gY1 + r22 * gY2;
-        }
+        for (int i = 0; i < PXT; i++)
+            flow_pixel_side<true>(tgt, Pw[i], dpv[i], px[i], py[i], ok[i], ok[i] ? fx[i] : 0.f, ok[i] ? fy[i] : 0.f, d.pxl_thre, acc, gw[i]);
         if (side) {                                                  // wave-uniform (a scalar load): a scalar branch, no selects
 #pragma unroll
             for (int i = 0; i < PXT; i++) { g1[i][0] += gw[i][0]; g1[i][1] += gw[i][1]; g1[i][2] += gw[i][2]; }
@@ -1677,9 +1663,9 @@ extern "C" int a3r_align_set_depth_prior(a3r_align_t a, float weight, const floa
 }
 
 // The two small launches that end an iteration (per-slot sums and chain rules, then the single-block Adam / gradient export /
-// loss); nothing to do when the main kernel finishes the iteration itself (A3R_ALIGN_TAIL=fused).  The caller names its MODE's
-// finalize B kernel (a function argument, not a template parameter of this helper): a kernel template is instantiated where it is
-// first named, and that order is the order of the kernels in the code object, which stays what it was.
+// loss); nothing to do when the main kernel finishes the iteration itself (A3R_ALIGN_TAIL=fused).  The entry point names its MODE's
+// finalize B kernel (a function argument that run_iteration hands on, not a template parameter of these helpers): a kernel template
+// is instantiated where it is first named, and that order is the order of the kernels in the code object, which stays what it was.
 using FinalizeB = void (*)(AlignDev, AdamArgs, TailOut);
 static void launch_tail(a3r_align_s* a, FinalizeB finalize_b, const AdamArgs& ad, const TailOut& tout, int loss_only, hipStream_t st) {
     if (a->d.fused_tail) return;
@@ -1715,18 +1701,27 @@ static void launch_flow(a3r_align_s* a, int epoch, hipStream_t st) {
     hipLaunchKernelGGL(align_flow_decide_kernel, dim3(1), dim3(TPB), 0, st, d, d.inc);
 }
 
+// The launches of one iteration of a fused handle: transforms if stale, the ego-flow pass, the main kernel, the tail.  Like
+// launch_tail it takes its MODE's launchers as function arguments and is no template itself: with the MODE as a template parameter
+// here the finalize B kernels moved in the code object.  The entry points name MODE 2, 0, 1 in that order, main before finalize B.
+using LaunchMain = void (*)(a3r_align_s*, const AdamArgs&, float*, const TailOut&, hipStream_t);
+static int run_iteration(a3r_align_s* a, int epoch, LaunchMain main, FinalizeB finalize_b, const AdamArgs& ad, float* g_depth,
+                         const TailOut& tout, int loss_only, void* stream) {
+    hipStream_t st = as_stream(stream);
+    refresh_if_dirty(a, st);
+    launch_flow(a, epoch, st);
+    main(a, ad, g_depth, tout, st);
+    launch_tail(a, finalize_b, ad, tout, loss_only, st);
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
 extern "C" int a3r_align_step_epoch(a3r_align_t a, float lr, int epoch, void* stream) {
     A3R_CHECK_ARG(a, "a3r_align_step: null handle");
     A3R_CHECK_ARG(!a->shard, "a3r_align_step: edge-shard handle (use a3r_align_shard_partial / a3r_align_shard_apply)");
     A3R_CHECK_ARG(a->steps < a->loss_capacity, "a3r_align_step: loss_history full (%d)", a->loss_capacity);
-    hipStream_t st = as_stream(stream);
-    const AdamArgs ad = adam_args(a, lr);
-    refresh_if_dirty(a, st);
-    launch_flow(a, epoch, st);
     const TailOut tout = {nullptr, nullptr, nullptr, nullptr};
-    launch_main<2>(a, ad, nullptr, tout, st);
-    launch_tail(a, align_finalize_b_kernel<2>, ad, tout, 0, st);
-    A3R_LAUNCH_CHECK();
+    if (int rc = run_iteration(a, epoch, launch_main<2>, align_finalize_b_kernel<2>, adam_args(a, lr), nullptr, tout, 0, stream)) return rc;
     a->steps++;
     return A3R_OK;
 }
@@ -1749,30 +1744,17 @@ extern "C" int a3r_align_step(a3r_align_t a, float lr, void* stream) {
 extern "C" int a3r_align_loss(a3r_align_t a, float* loss_dev, void* stream) {
     A3R_CHECK_ARG(a && loss_dev, "a3r_align_loss: null argument");
     A3R_CHECK_ARG(!a->shard, "a3r_align_loss: edge-shard handle (use a3r_align_shard_partial / a3r_align_shard_grad)");
-    hipStream_t st = as_stream(stream);
-    AdamArgs ad = {};
-    refresh_if_dirty(a, st);
-    launch_flow(a, 1 << 30, st);                                       // net() defaults to epoch=9999: flow term active
     const TailOut tout = {nullptr, nullptr, loss_dev, nullptr};
-    launch_main<0>(a, ad, nullptr, tout, st);
-    launch_tail(a, align_finalize_b_kernel<0>, ad, tout, 1, st);
-    A3R_LAUNCH_CHECK();
-    return A3R_OK;
+    // net() defaults to epoch=9999: flow term active
+    return run_iteration(a, 1 << 30, launch_main<0>, align_finalize_b_kernel<0>, {}, nullptr, tout, 1, stream);
 }
 
 extern "C" int a3r_align_grad_full(a3r_align_t a, int epoch, float* g_pw_poses, float* g_pw_adaptors, float* g_depth, float* g_small,
                                    float* loss_dev, void* stream) {
     A3R_CHECK_ARG(a && g_pw_poses && g_depth && g_small && loss_dev, "a3r_align_grad: null argument");
     A3R_CHECK_ARG(!a->shard, "a3r_align_grad: edge-shard handle (use a3r_align_shard_partial / a3r_align_shard_grad)");
-    hipStream_t st = as_stream(stream);
-    AdamArgs ad = {};
-    refresh_if_dirty(a, st);
-    launch_flow(a, epoch, st);
     const TailOut tout = {g_pw_poses, g_small, loss_dev, g_pw_adaptors};
-    launch_main<1>(a, ad, g_depth, tout, st);
-    launch_tail(a, align_finalize_b_kernel<1>, ad, tout, 0, st);
-    A3R_LAUNCH_CHECK();
-    return A3R_OK;
+    return run_iteration(a, epoch, launch_main<1>, align_finalize_b_kernel<1>, {}, g_depth, tout, 0, stream);
 }
 
 extern "C" int a3r_align_grad_epoch(a3r_align_t a, int epoch, float* g_pw_poses, float* g_depth, float* g_small, float* loss_dev,

@@ -9,12 +9,16 @@
   align_flow_decide_kernel             kept / dropped a factor 2 either side of the threshold, the sticky flag, the start gate;
   align_depth_prior_kernel             P > 1024 (strided loops run more than once), the clamp branch, own dynamic weights.
 
+The two forms of the ego-flow pass share one per-pixel body; test_flow_pass_bitwise_parent pins both, bit for bit, to what the
+commit before that sharing computed (tests/golden/align_flow_parent.npz, written by make_goldens_align_flow_parent.py).
+
 Problems come from tests/align_cases.py; tests/test_align_cases_cpu.py shows on the CPU that they are well posed (guard band
 around pxl_thre, shares that bite).  Tolerances are those of tests/test_gpu_align.py and tests/test_oracle_align.py: first
 loss 1e-6, gradients 1e-5 of the tensor max, trajectory losses 1e-5, states 1e-4, a term in isolation 1e-3.
 
 Runtime of the whole file on one MI355X: not measured yet (DESIGN.md section 6.3 says what is still open); the problems have at
 most 15 frames of 2080 pixels and one oracle evaluation of them takes well under a second."""
+import importlib.util
 import os
 import subprocess
 import sys
@@ -246,7 +250,9 @@ def test_depth_prior_clamp_and_strides_vs_oracle(name, Engine):
 
 
 # ------------------------------------------------------------------------------------------------- A3R_ALIGN_FLOW=v1
-# (last in the file: if the child process ends abnormally, nothing else is started on the GPU after it)
+# (last in the file: if a child process ends abnormally, nothing else is started on the GPU after it)
+_child_ended_badly = False
+
 _CHILD = r"""
 import sys
 sys.path[:0] = [{repo!r}, {tests!r}]
@@ -280,6 +286,8 @@ def test_flow_v1_switch_at_vec_shape(Engine, tmp_path):
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, A3R_ALIGN_FLOW="v1"), stdout=subprocess.PIPE,
                        stderr=subprocess.STDOUT, text=True, timeout=600)
     if r.returncode != 0 or not os.path.exists(out):
+        global _child_ended_badly
+        _child_ended_badly = True
         pytest.fail(f"the A3R_ALIGN_FLOW=v1 child process ended with status {r.returncode}:\n{r.stdout}", pytrace=False)
     c = np.load(out)
     m = dict(loss_v1_first=abs(float(c["loss"]) - lo) / abs(lo), v1_loss_vs_vec=abs(float(c["loss"]) - la) / abs(la))
@@ -288,3 +296,40 @@ def test_flow_v1_switch_at_vec_shape(Engine, tmp_path):
         m[f"grad_v1_{k}"] = rel_err(c[k].reshape(go[k].shape), go[k])
         m[f"v1_{k}_vs_vec"] = rel_err(c[k], ga[k])
     _check("flow_v1_switch_" + name, m)
+
+
+# ------------------------------------------------------------------------------------------------- bitwise against the parent
+def _flow_parent_generator():
+    spec = importlib.util.spec_from_file_location("make_goldens_align_flow_parent",
+                                                  os.path.join(REPO, "tests", "golden", "make_goldens_align_flow_parent.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+_PARENT = _flow_parent_generator()
+
+
+@pytest.mark.parametrize("name", list(_PARENT.CASES))          # the case that needs a child process is the last one
+def test_flow_pass_bitwise_parent(name, golden_dir, tmp_path):
+    """Loss, every gradient tensor and the parameters after five steps with the flow term on are, byte for byte, those of the
+    commit before the two flow kernels shared their per-pixel body: no tolerance.  The generator's own measure_case() runs the
+    case, the v1_* one in a fresh child process under its own time limit (any non-zero status raises)."""
+    global _child_ended_badly
+    assert not _child_ended_badly, "not started: an earlier child process of this file ended abnormally"
+    try:
+        got = _PARENT.measure_case(name, str(tmp_path))
+    except (RuntimeError, subprocess.TimeoutExpired):
+        _child_ended_badly = True
+        raise
+    with np.load(os.path.join(golden_dir, "align_flow_parent.npz")) as z:
+        want = {k.split("/", 1)[1]: z[k] for k in z.files if k.startswith(name + "/")}
+    assert {"loss", "grad_depth", "grad_pw_poses", "grad_im_poses", "param_depth", "run_losses"} <= set(want)
+    assert set(got) == set(want)
+    differing = {}
+    for k, w in want.items():
+        g = np.asarray(got[k])
+        assert g.dtype == w.dtype and g.shape == w.shape, (name, k, g.dtype, w.dtype, g.shape, w.shape)
+        if not np.array_equal(np.frombuffer(g.tobytes(), np.uint8), np.frombuffer(w.tobytes(), np.uint8)):
+            differing[k] = (int((g != w).sum()), float(np.abs(g.astype(np.float64) - w).max()))
+    assert not differing, (name, "key: (elements that differ, largest difference)", differing)
