@@ -1,9 +1,10 @@
 // Small dense solvers of the MST initialisation (reference: dust3r/cloud_opt/init_im_poses.py:129-252, 415-482) on the
 // device, so that init='mst' runs without LAPACK and without a host round trip per problem:
 //   a3r_umeyama_solve   closed-form weighted similarity registration from the 17 raw moments of a3r_umeyama_moments
-//                       (the reference calls roma.rigid_points_registration, :415-418): 3x3 SVD by Jacobi, one thread per problem;
+//                       (the reference calls roma.rigid_points_registration, :415-418): 3x3 SVD by one-sided Jacobi, one thread per problem;
 //   a3r_pnp_solve       camera pose of an image from its world-space point map with known intrinsics (stands in for
-//                       cv2.solvePnPRansac + SQPNP of fast_pnp, :442-482, which is stochastic and absent here -- PARITY UNPINNED):
+//                       cv2.solvePnPRansac + SQPNP of fast_pnp, :442-482, which is stochastic and absent here -- parity with it is unpinned; the solver
+//                       itself is pinned to a float64 restatement of this header, tests/init_cases.py + tests/test_gpu_init.py):
 //                       closed-form start (the similarity carrying the pixel rays onto the world points, a least-squares fit over
 //                       all points), then damped Gauss-Newton on the reprojection error with redescending (Cauchy) weights whose
 //                       scale is annealed from 40 px to the 5 px inlier threshold -- robust to the gross outliers RANSAC is there
@@ -14,45 +15,6 @@
 
 namespace a3r {
 
-// cyclic Jacobi eigen-decomposition of the symmetric N x N matrix A (destroyed: its diagonal holds the eigenvalues on return);
-// the columns of V are the eigenvectors.  Arrays live wherever the caller put them (LDS for N = 12, registers for N = 3).
-template <int N, class Mat>
-__device__ inline void jacobi_eigh(Mat& A, Mat& V, int max_sweeps) {
-    for (int i = 0; i < N; i++)
-        for (int j = 0; j < N; j++) V[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < max_sweeps; sweep++) {
-        double off = 0.0, diag = 0.0;
-        for (int i = 0; i < N; i++) {
-            diag += A[i][i] * A[i][i];
-            for (int j = i + 1; j < N; j++) off += A[i][j] * A[i][j];
-        }
-        if (off <= 1e-30 * diag || off == 0.0) break;
-        for (int p = 0; p < N - 1; p++)
-            for (int q = p + 1; q < N; q++) {
-                const double apq = A[p][q];
-                if (apq == 0.0) continue;
-                const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < N; k++) {                      // A <- J^T A J on rows / columns p, q
-                    const double akp = A[k][p], akq = A[k][q];
-                    A[k][p] = c * akp - s * akq;
-                    A[k][q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < N; k++) {
-                    const double apk = A[p][k], aqk = A[q][k];
-                    A[p][k] = c * apk - s * aqk;
-                    A[q][k] = s * apk + c * aqk;
-                }
-                for (int k = 0; k < N; k++) {
-                    const double vkp = V[k][p], vkq = V[k][q];
-                    V[k][p] = c * vkp - s * vkq;
-                    V[k][q] = s * vkp + c * vkq;
-                }
-            }
-    }
-}
-
 struct M3 { double m[3][3]; __device__ double* operator[](int i) { return m[i]; } __device__ const double* operator[](int i) const { return m[i]; } };
 
 __device__ inline double det3(const M3& a) {
@@ -60,24 +22,49 @@ __device__ inline double det3(const M3& a) {
            a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
 }
 
-// A = U diag(S) V^T with det(U) = +1 and S[2] carrying the sign that makes this true (|S| are the singular values, descending):
-// V and S^2 from the Jacobi eigen-decomposition of A^T A, u_i = A v_i / s_i for the two leading directions, u_2 = u_0 x u_1.
+// A = U diag(S) V^T with det(U) = +1 and S[2] carrying the sign that makes this true (|S| are the singular values, descending).
+// One-sided (Hestenes) Jacobi: plane rotations from the right make the columns of B = A V mutually orthogonal; their norms are the
+// singular values and u_i = b_i / s_i for the two leading directions, u_2 = u_0 x u_1.  Working on A itself keeps the small singular
+// directions of a nearly rank-1 A (a nearly collinear cloud) to full relative accuracy; an eigen-decomposition of A^T A, which this
+// replaced, squares the condition number and was off by 3e-6 there (tests/test_gpu_init.py, scene d).
 __device__ inline void svd3(const M3& A, M3& U, double S[3], M3& V) {
-    M3 ata, ev;
+    M3 B = A, W;
     for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) ata[i][j] = A[0][i] * A[0][j] + A[1][i] * A[1][j] + A[2][i] * A[2][j];
-    jacobi_eigh<3>(ata, ev, 30);
-    int idx[3] = {0, 1, 2};                                        // descending eigenvalues
+        for (int j = 0; j < 3; j++) W[i][j] = i == j ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 30; sweep++) {
+        bool rotated = false;
+        for (int p = 0; p < 2; p++)
+            for (int q = p + 1; q < 3; q++) {
+                double alpha = 0.0, beta = 0.0, gamma = 0.0;
+                for (int k = 0; k < 3; k++) { alpha += B[k][p] * B[k][p]; beta += B[k][q] * B[k][q]; gamma += B[k][p] * B[k][q]; }
+                if (gamma == 0.0 || gamma * gamma <= 1e-32 * alpha * beta) continue;      // orthogonal to working precision
+                rotated = true;
+                const double zeta = (beta - alpha) / (2.0 * gamma);
+                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < 3; k++) {
+                    const double bp = B[k][p], bq = B[k][q];
+                    B[k][p] = c * bp - s * bq;
+                    B[k][q] = s * bp + c * bq;
+                    const double wp = W[k][p], wq = W[k][q];
+                    W[k][p] = c * wp - s * wq;
+                    W[k][q] = s * wp + c * wq;
+                }
+            }
+        if (!rotated) break;
+    }
+    double n2[3];
+    for (int c = 0; c < 3; c++) n2[c] = B[0][c] * B[0][c] + B[1][c] * B[1][c] + B[2][c] * B[2][c];
+    int idx[3] = {0, 1, 2};                                        // descending singular values
     for (int a = 0; a < 2; a++)
         for (int b = a + 1; b < 3; b++)
-            if (ata[idx[b]][idx[b]] > ata[idx[a]][idx[a]]) { const int t = idx[a]; idx[a] = idx[b]; idx[b] = t; }
+            if (n2[idx[b]] > n2[idx[a]]) { const int t = idx[a]; idx[a] = idx[b]; idx[b] = t; }
     for (int c = 0; c < 3; c++)
-        for (int r = 0; r < 3; r++) V[r][c] = ev[r][idx[c]];
+        for (int r = 0; r < 3; r++) V[r][c] = W[r][idx[c]];
     double u[3][3];
     for (int c = 0; c < 2; c++) {
-        double n = 0.0;
-        for (int r = 0; r < 3; r++) { u[c][r] = A[r][0] * V[0][c] + A[r][1] * V[1][c] + A[r][2] * V[2][c]; n += u[c][r] * u[c][r]; }
-        n = sqrt(n);
+        for (int r = 0; r < 3; r++) u[c][r] = B[r][idx[c]];
+        double n = sqrt(n2[idx[c]]);
         S[c] = n;
         if (c == 1) {                                              // re-orthogonalise against u_0 (nearly rank-1 inputs)
             const double d = u[1][0] * u[0][0] + u[1][1] * u[0][1] + u[1][2] * u[0][2];

@@ -7,8 +7,9 @@ RANSAC; both solved on the device by the kernels of csrc/init.hip -- no LAPACK, 
 PINNED against the reference's own code run on the CPU (tests/golden/mst.npz from make_goldens_mst.py, tests/test_gpu_mst_parity.py):
 the edge scores (commons.py:20-25), the spanning tree (scipy.sparse.csgraph) and the walk over it as the verbose lines print it,
 the Weiszfeld focals (post_process.py:36-60) with the stale-`i_j` quirk, the chain of registrations, and what init_from_pts3d
-(:83-126) writes into the optimiser -- with closed-form stand-ins for two roma functions in the fixture.  The PnP SOLVE stays
-UNPINNED (cv2's RANSAC is stochastic and absent; the fixture replaces it by a recorder) and is validated by what it is for: the
+(:83-126) writes into the optimiser -- with closed-form stand-ins for two roma functions in the fixture.  The PnP SOLVE has no
+parity with cv2 (its RANSAC is stochastic and absent; the fixture replaces it by a recorder): it is pinned to a float64 restatement
+of its own algorithm and to ground truth (tests/init_cases.py, tests/test_gpu_init.py) and validated by what it is for: the
 alignment loss after initialisation and the recovered geometry on synthetic scenes (tests/test_gpu_api.py).
 It is a one-off O(E*P) host-orchestrated step, not the inner loop.
 """
@@ -42,7 +43,7 @@ def _solve_from_moments(m):
 
 def umeyama_solve(x, y, w, x_off, y_off, w_off, P):
     """B weighted similarity registrations on the device, no synchronisation: a3r_umeyama_moments (17 float64 moments per problem,
-    fixed summation order) + a3r_umeyama_solve (closed form, 3x3 SVD by Jacobi).  x, y, w flat float32 device tensors, *_off int64
+    fixed summation order) + a3r_umeyama_solve (closed form, 3x3 SVD by one-sided Jacobi).  x, y, w flat float32 device tensors, *_off int64
     element offsets [B] (device).  Returns a float32 device tensor [B,13] = (s, R row-major, T)."""
     from ... import _lib
     from ..._lib import check, ptr, stream_ptr
