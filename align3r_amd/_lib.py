@@ -66,7 +66,8 @@ class AlignDesc(C.Structure):
                 ("shifts", c_void), ("im_poses", c_void), ("im_focals", c_void), ("im_pp", c_void),
                 ("adam_pw_poses", c_void), ("adam_depth", c_void), ("adam_small", c_void),
                 ("workspace", c_void), ("workspace_bytes", C.c_size_t), ("loss_history", c_void),
-                ("loss_capacity", C.c_int), ("train_adaptors", C.c_int), ("adam_pw_adaptors", c_void)]
+                ("loss_capacity", C.c_int), ("train_adaptors", C.c_int), ("adam_pw_adaptors", c_void),
+                ("obs_format", C.c_int), ("obs_i", c_void), ("obs_j", c_void), ("obs_exp_i", c_void), ("obs_exp_j", c_void)]
 
 
 class AlignFlowDesc(C.Structure):
@@ -183,6 +184,7 @@ SIGNATURES = {
     "a3r_raft_forward": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void, C.c_size_t, C.POINTER(RaftTaps), c_void]),
     "a3r_align_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "a3r_align_create": (C.c_int, [C.POINTER(AlignDesc), C.POINTER(c_void), c_void]),
+    "a3r_align_pack_obs": (C.c_int, [c_void, c_void, C.c_int, C.c_long, c_void, c_void, c_void]),
     "a3r_align_destroy": (C.c_int, [c_void]),
     "a3r_align_set_train_masks": (C.c_int, [c_void, c_void, c_void, c_void, c_void, c_void]),
     "a3r_align_step": (C.c_int, [c_void, C.c_float, c_void]),

@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import AlignDesc, AlignFlowDesc, check, ptr, stream_ptr
+from .obs16 import check_obs_dtype
 
 
 def cosine_schedule(t, lr_start, lr_end):   # commons.py:123-125
@@ -58,7 +59,9 @@ class _AlignEngineBase:
     single state, the sharded one has a _ShardReplica per shard (`_states`)."""
 
     def __init__(self, ei, ej, pred_i, pred_j, w_i, w_j, imshapes, mono, base_scale, pw_break, focal_break, norm_pw_scale, dist,
-                 train_poses, train_focals, train_pp, train_adaptors, device, loss_capacity, shared_focal=False):
+                 train_poses, train_focals, train_pp, train_adaptors, device, loss_capacity, shared_focal=False, obs_dtype="fp32",
+                 pack_budget_bytes=1 << 30):
+        self.obs_dtype = check_obs_dtype(obs_dtype)
         self.lib = _lib.load()
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -68,10 +71,17 @@ class _AlignEngineBase:
         self.ej = np.ascontiguousarray(ej, dtype=np.int32)
         E, N = len(self.ei), len(imshapes)
         rows, pred_i, pred_j, w_i, w_j = self._select_rows(E, pred_i, pred_j, w_i, w_j)
-        self.w_i, self.w_j = f32(w_i).reshape(rows, -1), f32(w_j).reshape(rows, -1)
-        P = self.w_i.shape[1]
+        if self.obs_dtype == "fp32":
+            self.w_i, self.w_j = f32(w_i).reshape(rows, -1), f32(w_j).reshape(rows, -1)
+            P = self.w_i.shape[1]
+            self.pred_i, self.pred_j = f32(pred_i).reshape(rows, P, 3), f32(pred_j).reshape(rows, P, 3)
+        else:
+            # packed fp16 records + one exponent per edge side (obs16.py); no fp32 copy of the observations is kept here
+            P = torch.as_tensor(w_i).reshape(rows, -1).shape[1]
+            self.pred_i = self.pred_j = self.w_i = self.w_j = None
+            self.obs_i, self.exp_i = self._pack(pred_i, w_i, rows, P, pack_budget_bytes)
+            self.obs_j, self.exp_j = self._pack(pred_j, w_j, rows, P, pack_budget_bytes)
         self.E, self.N, self.P = E, N, P
-        self.pred_i, self.pred_j = f32(pred_i).reshape(rows, P, 3), f32(pred_j).reshape(rows, P, 3)
         self.imshapes = [tuple(int(v) for v in s) for s in imshapes]
         self.imw = np.asarray([w for h, w in self.imshapes], dtype=np.int32)
         self.imarea = np.asarray([h * w for h, w in self.imshapes], dtype=np.int32)
@@ -95,6 +105,39 @@ class _AlignEngineBase:
     def _f32(self, a):
         return torch.as_tensor(a, dtype=torch.float32).to(self.device).contiguous()
 
+    def _pack(self, pred, w, rows, P, budget_bytes):
+        """One side's observations as (records [rows, P, 4] float16, exponents [rows] int32) on the device: uploaded and packed in
+        row chunks of at most budget_bytes of fp32 rows (16 P bytes each), so the whole fp32 stack is never resident."""
+        dev = self.device
+        pred, w = torch.as_tensor(pred).reshape(rows, P, 3), torch.as_tensor(w).reshape(rows, P)
+        obs = torch.empty(rows, P, 4, dtype=torch.float16, device=dev)
+        exps = torch.empty(rows, dtype=torch.int32, device=dev)
+        step = max(1, int(budget_bytes) // (16 * P))
+        with torch.cuda.device(dev):
+            for r0 in range(0, rows, step):
+                r1 = min(rows, r0 + step)
+                p32, w32 = (t[r0:r1].to(dev, torch.float32).contiguous() for t in (pred, w))
+                check(self.lib.a3r_align_pack_obs(ptr(p32), ptr(w32), r1 - r0, P, ptr(obs[r0:r1]), ptr(exps[r0:r1]), stream_ptr()),
+                      "a3r_align_pack_obs")
+        return obs, exps
+
+    @property
+    def observation_bytes(self):
+        """Device bytes of the observations held here: 32 per edge-pixel in fp32, 16 (+ 8 per edge for the exponents) packed."""
+        held = (self.pred_i, self.pred_j, self.w_i, self.w_j) if self.obs_dtype == "fp32" else (self.obs_i, self.obs_j, self.exp_i, self.exp_j)
+        return sum(t.numel() * t.element_size() for t in held)
+
+    def decoded_observations(self):
+        """(pred_i', pred_j', w_i', w_j') as fp32 tensors: the observations the loss is evaluated on.  With fp16 storage
+        pred' = float(h) 2^-k and w' = float(h_w) (exact in fp32, obs16.py); with fp32 storage the tensors held here."""
+        if self.obs_dtype == "fp32":
+            return self.pred_i, self.pred_j, self.w_i, self.w_j
+        # 2^-k from its bit pattern (|k| <= 100: a normal number); the product with an fp16 value is exact
+        scale = lambda exps: (127 - exps).bitwise_left_shift(23).view(torch.float32)[:, None, None]
+        dec = lambda obs, exps: (obs[..., :3].float() * scale(exps), obs[..., 3].float().contiguous())
+        (pi, wi), (pj, wj) = dec(self.obs_i, self.exp_i), dec(self.obs_j, self.exp_j)
+        return pi, pj, wi, wj
+
     def _alloc_state(self, st, workspace_bytes):
         """Zeroed parameters, Adam moments and loss history plus the workspace of one handle, as attributes of `st`."""
         E, N, P = self.E, self.N, self.P
@@ -117,8 +160,13 @@ class _AlignEngineBase:
         d.total_area_i, d.total_area_j = self.total_area_i, self.total_area_j
         d.ei_host, d.ej_host = self.ei.ctypes.data, self.ej.ctypes.data
         d.imw_host, d.imarea_host = self.imw.ctypes.data, self.imarea.ctypes.data
-        d.pred_i, d.pred_j = self.pred_i[row_slice].data_ptr(), self.pred_j[row_slice].data_ptr()
-        d.w_i, d.w_j = self.w_i[row_slice].data_ptr(), self.w_j[row_slice].data_ptr()
+        if self.obs_dtype == "fp32":
+            d.pred_i, d.pred_j = self.pred_i[row_slice].data_ptr(), self.pred_j[row_slice].data_ptr()
+            d.w_i, d.w_j = self.w_i[row_slice].data_ptr(), self.w_j[row_slice].data_ptr()
+        else:
+            d.obs_format = 1
+            d.obs_i, d.obs_j = self.obs_i[row_slice].data_ptr(), self.obs_j[row_slice].data_ptr()
+            d.obs_exp_i, d.obs_exp_j = self.exp_i[row_slice].data_ptr(), self.exp_j[row_slice].data_ptr()
         d.mono = self.mono.data_ptr() if self.use_mono else None
         d.pp0 = self.pp0.data_ptr()
         for k in _PARAM_KEYS:
@@ -276,11 +324,14 @@ class AlignEngine(_AlignEngineBase):
     def __init__(self, ei, ej, pred_i, pred_j, w_i, w_j, imshapes, mono=None, base_scale=0.5, pw_break=20.0,
                  focal_break=20.0, norm_pw_scale=True, dist="l1", train_poses=True, train_focals=True, train_pp=False,
                  train_adaptors=False, device="cuda:0", loss_capacity=4096, shared_focal=False, temporal_smoothing_weight=0.0,
-                 translation_weight=0.1, flow=None):
-        """flow (cloud_opt_flow variant): dict(flow_ij [E,2,P], flow_ji [E,2,P], dyn [N,P] bool, weight, thre, start_epoch,
+                 translation_weight=0.1, flow=None, obs_dtype="fp32", pack_budget_bytes=1 << 30):
+        """obs_dtype: 'fp32', or 'fp16' = the observations are packed on upload (obs16.py: 16 bytes per edge-pixel instead of 32, in
+        row chunks of at most pack_budget_bytes of fp32 rows); everything else stays fp32.
+        flow (cloud_opt_flow variant): dict(flow_ij [E,2,P], flow_ji [E,2,P], dyn [N,P] bool, weight, thre, start_epoch,
         num_total_iter, pxl_thre) -- the optical-flow fields and dynamic masks are inputs (optimizer.py:104-116)."""
         super().__init__(ei, ej, pred_i, pred_j, w_i, w_j, imshapes, mono, base_scale, pw_break, focal_break, norm_pw_scale, dist,
-                         train_poses, train_focals, train_pp, train_adaptors, device, loss_capacity, shared_focal=shared_focal)
+                         train_poses, train_focals, train_pp, train_adaptors, device, loss_capacity, shared_focal=shared_focal,
+                         obs_dtype=obs_dtype, pack_budget_bytes=pack_budget_bytes)
         E, N, P, dev = self.E, self.N, self.P, self.device
         self.tsw, self.trans_w = float(temporal_smoothing_weight), float(translation_weight)
         if flow is not None and flow.get("weight", 0) > 0:
@@ -437,12 +488,15 @@ class ShardedAlignEngine(_AlignEngineBase):
     Shard bounds are parallel.shard_rows(E, rank, world); shards that come out empty are skipped with local_shards and refused
     with group.  The observations are either the whole graph's [E, ...] (each shard takes a view of its rows) or, with group,
     this rank's rows only [e1 - e0, ...] (a rank's inference output is its shard).  Limits: plain cloud_opt only (no flow
-    variant, no depth prior); the initial state comes through set_params.  Same surface as AlignEngine: params, set_params,
+    variant, no depth prior); the initial state comes through set_params.  obs_dtype='fp16': packed observations as in AlignEngine
+    (every shard gets its rows of the records and of the exponent tables).  Same surface as AlignEngine: params, set_params,
     loss, loss_grad, step, run, steps_done, trainable, pose_matrices, points, export_points (replica 0)."""
 
     def __init__(self, ei, ej, pred_i, pred_j, w_i, w_j, imshapes, mono=None, base_scale=0.5, pw_break=20.0, focal_break=20.0,
                  norm_pw_scale=True, dist="l1", train_poses=True, train_focals=True, train_pp=False, train_adaptors=False,
-                 device="cuda:0", loss_capacity=4096, local_shards=None, group=None, **unsupported):
+                 device="cuda:0", loss_capacity=4096, local_shards=None, group=None, obs_dtype="fp32", pack_budget_bytes=1 << 30,
+                 **unsupported):
+        check_obs_dtype(obs_dtype)
         if unsupported.get("flow") is not None or unsupported.get("shared_focal") or unsupported.get("temporal_smoothing_weight", 0) > 0:
             raise NotImplementedError("ShardedAlignEngine: the flow variant (shared focal, temporal smoothing, ego-flow) is not edge-sharded")
         bad = set(unsupported) - {"flow", "shared_focal", "temporal_smoothing_weight", "translation_weight"}
@@ -456,7 +510,8 @@ class ShardedAlignEngine(_AlignEngineBase):
             from .parallel import GradientAllReduce
             self._all_reduce = GradientAllReduce(group)
         super().__init__(ei, ej, pred_i, pred_j, w_i, w_j, imshapes, mono, base_scale, pw_break, focal_break, norm_pw_scale, dist,
-                         train_poses, train_focals, train_pp, train_adaptors, device, loss_capacity)
+                         train_poses, train_focals, train_pp, train_adaptors, device, loss_capacity, obs_dtype=obs_dtype,
+                         pack_budget_bytes=pack_budget_bytes)
         E, N, P = self.E, self.N, self.P
         self.n_floats = int(self.lib.a3r_align_shard_reduce_floats(E, N, P))
         self.replicas = []

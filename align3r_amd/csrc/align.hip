@@ -178,14 +178,22 @@ __global__ __launch_bounds__(TPB) void align_prep_kernel(AlignDev d) {
 // !VEC: ragged P, pixels strided by the workgroup size, scalar loads.
 // Raw loaded registers of one (edge, side); nothing may TOUCH them between the load and consume(), or the
 // compiler has to wait for the data right where it was issued and the prefetch is gone.
-template <bool VEC> struct EdgeData;
-template <> struct EdgeData<true> { f32x4 a, b, c, w; };                    // 4 consecutive pixels: xyz xyz xyz xyz, wwww
-template <> struct EdgeData<false> { float x[PXT][3]; float w[PXT]; };
+// OBS_PACKED (a3r_align_desc.obs_format = 1, P % 4 == 0 only): the observations are 8-byte records {x, y, z, w} of fp16 with one
+// power-of-two exponent per edge side (obs.hip has the format), so a thread's 4 consecutive pixels are TWO 16-byte loads.
+enum ObsForm { OBS_SCALAR = 0, OBS_VEC = 1, OBS_PACKED = 2 };
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+template <int FORM> struct EdgeData;
+template <> struct EdgeData<OBS_VEC> { f32x4 a, b, c, w; };                 // 4 consecutive pixels: xyz xyz xyz xyz, wwww
+template <> struct EdgeData<OBS_SCALAR> { float x[PXT][3]; float w[PXT]; };
+template <> struct EdgeData<OBS_PACKED> { f16x8 a, b; };                    // 4 consecutive pixels: xyzw xyzw, xyzw xyzw
+// The packed rows and exponent tables of a handle: kernel arguments of the packed kernels only (AlignDev, and with it the argument
+// block of every other kernel, is what it was).  The exponent tables are noalias there, so their lookups are scalar loads.
+struct PackedObs { const f16x8 *obs_i, *obs_j; const int *exp_i, *exp_j; };
 
 // (Inline-asm loads with hand-placed counted waits were tried here to keep TWO edge sides per wave in flight -- hipcc's waitcnt
 // pass puts a vmcnt wait in front of the next buffer's loads -- and abandoned: the register allocator copies the asm loads'
 // destination registers at the loop's phi points while the data may still be landing, which no source-level form prevents.)
-__device__ __forceinline__ void load_edge(const AlignDev& d, int code, int P, int pix0, const bool* valid, EdgeData<true>& o) {
+__device__ __forceinline__ void load_edge(const AlignDev& d, int code, int P, int pix0, const bool* valid, EdgeData<OBS_VEC>& o) {
     const int e = code >> 1, side = code & 1;
     const float* X = (side ? d.pred_j : d.pred_i) + (size_t)e * P * 3;
     const float* Wt = (side ? d.w_j : d.w_i) + (size_t)e * P;
@@ -194,7 +202,7 @@ __device__ __forceinline__ void load_edge(const AlignDev& d, int code, int P, in
     o.a = xp[0]; o.b = xp[1]; o.c = xp[2];
     o.w = *reinterpret_cast<const f32x4*>(Wt + p);
 }
-__device__ __forceinline__ void load_edge(const AlignDev& d, int code, int P, int pix0, const bool* valid, EdgeData<false>& o) {
+__device__ __forceinline__ void load_edge(const AlignDev& d, int code, int P, int pix0, const bool* valid, EdgeData<OBS_SCALAR>& o) {
     const int e = code >> 1, side = code & 1;
     const float* X = (side ? d.pred_j : d.pred_i) + (size_t)e * P * 3;
     const float* Wt = (side ? d.w_j : d.w_i) + (size_t)e * P;
@@ -205,16 +213,38 @@ __device__ __forceinline__ void load_edge(const AlignDev& d, int code, int P, in
         o.w[i] = Wt[pp];
     }
 }
-__device__ __forceinline__ void unpack_edge(const EdgeData<true>& e, float (*x)[3], float* w) {
+__device__ __forceinline__ void load_edge(const PackedObs& pk, int code, int P, int pix0, const bool* valid, EdgeData<OBS_PACKED>& o) {
+    const int e = code >> 1, side = code & 1;
+    const int p = valid[0] ? pix0 : 0;     // a multiple of 4: 32 bytes into a 32-byte aligned row (P % 4 == 0)
+    const f16x8* rp = (side ? pk.obs_j : pk.obs_i) + ((size_t)e * P + p) / 2;
+    o.a = rp[0]; o.b = rp[1];
+}
+__device__ __forceinline__ void unpack_edge(const EdgeData<OBS_VEC>& e, float (*x)[3], float* w) {
     x[0][0] = e.a.x; x[0][1] = e.a.y; x[0][2] = e.a.z;
     x[1][0] = e.a.w; x[1][1] = e.b.x; x[1][2] = e.b.y;
     x[2][0] = e.b.z; x[2][1] = e.b.w; x[2][2] = e.c.x;
     x[3][0] = e.c.y; x[3][1] = e.c.z; x[3][2] = e.c.w;
     w[0] = e.w.x; w[1] = e.w.y; w[2] = e.w.z; w[3] = e.w.w;
 }
-__device__ __forceinline__ void unpack_edge(const EdgeData<false>& e, float (*x)[3], float* w) {
+__device__ __forceinline__ void unpack_edge(const EdgeData<OBS_SCALAR>& e, float (*x)[3], float* w) {
 #pragma unroll
     for (int i = 0; i < PXT; i++) { x[i][0] = e.x[i][0]; x[i][1] = e.x[i][1]; x[i][2] = e.x[i][2]; w[i] = e.w[i]; }
+}
+// The decoded observation float(h) * 2^-k, the factor applied right after the conversion: the product is exact, so everything
+// downstream sees the fp32 loop's operands and rounds as the fp32 loop does on the decoded observations.
+__device__ __forceinline__ void unpack_edge(const EdgeData<OBS_PACKED>& e, float scale, float (*x)[3], float* w) {
+#pragma unroll
+    for (int i = 0; i < PXT; i++) {
+        const f16x8& r = i < 2 ? e.a : e.b;
+        const int o = (i & 1) * 4;
+        x[i][0] = (float)r[o] * scale; x[i][1] = (float)r[o + 1] * scale; x[i][2] = (float)r[o + 2] * scale;
+        w[i] = (float)r[o + 3];
+    }
+}
+// 2^-k of an edge side, |k| <= 100 (wave-uniform: a scalar load and two scalar operations)
+__device__ __forceinline__ float packed_scale(const PackedObs& pk, int code) {
+    const int k = (code & 1 ? pk.exp_j : pk.exp_i)[code >> 1];
+    return __builtin_bit_cast(float, (127 - k) << 23);
 }
 
 // the tail of an iteration (defined below the flow kernels)
@@ -272,339 +302,29 @@ __global__ __launch_bounds__(TPB, VEC ? 4 : 2) void align_main_kernel(
     // edge id drained the prefetched edge data (s_waitcnt vmcnt(0)) and serialised the loop
     const int* __restrict__ inc_ptr, const int* __restrict__ inc, const float* __restrict__ edge_xf,
     const float* __restrict__ img_xf, const int* __restrict__ imw, const int* __restrict__ imarea, const int* __restrict__ order) {
-    __shared__ float red[2][EB][16][16];
-#ifdef A3R_ALIGN_STAMPS
-    unsigned long long stamp[6] = {0, 0, 0, 0, 0, 0};
-#endif
-    A3R_STAMP(0);
-    // images are dispatched longest first (order[] sorts them by their number of incident edge sides): the last round of
-    // workgroups is then made of the short ones.  A dispatch slot's row of the table is {image, first and last incidence slot, the
-    // first two (edge, side) codes}: ONE scalar load after which the first two edge sides are requested, before anything else --
-    // the prologue used to be a chain of five dependent memory round trips (order -> inc_ptr -> inc -> LDS -> edge data) during
-    // which the workgroup streamed nothing (15 % of its lifetime by s_memtime stamps, tools/align_stamps.py)
-    const int* tb = order + blockIdx.y * 8;
-    const int n = tb[0], kbeg = tb[1], kend = tb[2];
-    const bool depth_frozen = (tb[6] & FREEZE_DEPTH) != 0;          // workgroup-uniform: the image is fixed per workgroup
-    const int chunk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int P = d.P;
-    constexpr int PSTEP = VEC ? 1 : TPB;
-    const int pix0 = chunk * CHUNK + (VEC ? tid * PXT : tid);       // pixel i of this thread: pix0 + i * PSTEP
-    bool valid[PXT];
-#pragma unroll
-    for (int i = 0; i < PXT; i++) valid[i] = pix0 + i * PSTEP < P;
-    EdgeData<VEC> ea, eb;
-    const float* ix = img_xf + n * 16;
-    float R[9], T[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        R[r * 3 + 0] = ix[r * 4 + 0]; R[r * 3 + 1] = ix[r * 4 + 1]; R[r * 3 + 2] = ix[r * 4 + 2];
-        T[r] = ix[r * 4 + 3];
-    }
-    const float f = ix[12], ppx = ix[13], ppy = ix[14], shift = ix[15];
-    const int W = imw[n], area = imarea[n];
-    const float invW = 1.f / (float)W, inv_f = 1.f / f;
+    constexpr int FORM = VEC ? OBS_VEC : OBS_SCALAR;
+#define A3R_OBS_LOAD(code, buf) load_edge(d, code, P, pix0, valid, buf)
+#define A3R_OBS_UNPACK(code, ed, x, w) unpack_edge(ed, x, w)
+#include "align_main_body.inc"
+#undef A3R_OBS_LOAD
+#undef A3R_OBS_UNPACK
+}
 
-    // forward of the image side: depth -> camera point -> world point (optimizer.py:190-200,244-251)
-    auto pixel_forward = [&](int i, float rawv, float monov, float& dep, float& ddp, float& gxm, float& gym, float* rel) {
-        const int p = pix0 + i * PSTEP;
-        float gx = 0.f, gy = 0.f;
-        if (p < area) {
-            int y = (int)((float)p * invW);          // p < 2^24: exact up to +-1, fixed below
-            int x = p - y * W;
-            if (x < 0) { y--; x += W; }
-            if (x >= W) { y++; x -= W; }
-            gx = (float)x; gy = (float)y;
-        }
-        if (MONO) {
-            const float es = expf(rawv);
-            dep = monov * es + shift;
-            ddp = monov * es;
-        } else {
-            dep = expf(rawv);
-            ddp = dep;
-        }
-        gxm = gx - ppx; gym = gy - ppy;
-        rel[0] = dep * gxm * inv_f;  // optimizer.py:251: depth * (pixel_grid - pp) / focal  (1/f: one IEEE divide per thread)
-        rel[1] = dep * gym * inv_f;
-        rel[2] = dep;
-    };
-
-    float raw[PXT], monov[PXT], proj[PXT][3], gp[PXT][3];
-    if (VEC) {
-        f32x4 r4 = {0.f, 0.f, 0.f, 0.f}, m4 = {0.f, 0.f, 0.f, 0.f};
-        if (valid[0]) {
-            r4 = *reinterpret_cast<const f32x4*>(d.depth + (size_t)n * P + pix0);
-            if (MONO) m4 = *reinterpret_cast<const f32x4*>(d.mono + (size_t)n * P + pix0);
-        }
-        // the first two edge sides are requested right behind the depth: the memory counter retires in order, so the forward
-        // arithmetic below waits for the depth alone and runs while the edge data is still on its way
-        if (kbeg < kend) load_edge(d, tb[3], P, pix0, valid, ea);
-        if (kbeg + 1 < kend) load_edge(d, tb[4], P, pix0, valid, eb);
-        raw[0] = r4.x; raw[1] = r4.y; raw[2] = r4.z; raw[3] = r4.w;
-        monov[0] = m4.x; monov[1] = m4.y; monov[2] = m4.z; monov[3] = m4.w;
-    } else {
-#pragma unroll
-        for (int i = 0; i < PXT; i++) {
-            const size_t off = (size_t)n * P + (valid[i] ? pix0 + i * PSTEP : 0);
-            raw[i] = valid[i] ? d.depth[off] : 0.f;
-            monov[i] = (MONO && valid[i]) ? d.mono[off] : 0.f;
-        }
-        if (kbeg < kend) load_edge(d, tb[3], P, pix0, valid, ea);
-        if (kbeg + 1 < kend) load_edge(d, tb[4], P, pix0, valid, eb);
-    }
-#pragma unroll
-    for (int i = 0; i < PXT; i++) {
-        float dep, ddp, gxm, gym, rel[3];
-        pixel_forward(i, raw[i], monov[i], dep, ddp, gxm, gym, rel);
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            proj[i][r] = R[r * 3] * rel[0] + R[r * 3 + 1] * rel[1] + R[r * 3 + 2] * rel[2] + T[r];
-            gp[i][r] = 0.f;
-        }
-    }
-    if (MODE != 0 && d.flow_on) {
-        // ego-flow term (align_flow_kernel): its gradient w.r.t. this pixel's world point, scaled by weight / sum(mask)
-        const float c0 = d.flow_state[0], c1 = d.flow_state[1];
-        const size_t NP3 = (size_t)d.N * P * 3;
-#pragma unroll
-        for (int i = 0; i < PXT; i++) {
-            if (!valid[i]) continue;
-            const float* gf = d.gflow + ((size_t)n * P + pix0 + i * PSTEP) * 3;
-#pragma unroll
-            for (int r = 0; r < 3; r++) gp[i][r] = c0 * gf[r] + c1 * gf[NP3 + r];
-        }
-    }
-
-    // one (edge, side): residuals, loss, gradient w.r.t. the world point, per-edge sums (12 + loss)
-    auto consume = [&](int code, const EdgeData<VEC>& ed, int buf, int kb) {
-        float ex[PXT][3], ew[PXT];
-        unpack_edge(ed, ex, ew);
-        const int e = code >> 1, side = code & 1;
-        const float* M = edge_xf + e * 16;
-        const float m00 = M[0], m01 = M[1], m02 = M[2], m03 = M[3];
-        const float m10 = M[4], m11 = M[5], m12 = M[6], m13 = M[7];
-        const float m20 = M[8], m21 = M[9], m22 = M[10], m23 = M[11];
-        const float inva = side ? d.inv_area_j : d.inv_area_i;
-        float acc[13];
-#pragma unroll
-        for (int j = 0; j < 13; j++) acc[j] = 0.f;
-#pragma unroll
-        for (int i = 0; i < PXT; i++) {
-            const float x0 = ex[i][0], x1 = ex[i][1], x2 = ex[i][2], w = valid[i] ? ew[i] : 0.f;
-            const float r0 = proj[i][0] - (m00 * x0 + m01 * x1 + m02 * x2 + m03);
-            const float r1 = proj[i][1] - (m10 * x0 + m11 * x1 + m12 * x2 + m13);
-            const float r2 = proj[i][2] - (m20 * x0 + m21 * x1 + m22 * x2 + m23);
-            const float sq = r0 * r0 + r1 * r1 + r2 * r2;
-            float cf;
-            if (L2) {
-                acc[12] += sq * w * inva;
-                cf = 2.f * w * inva;
-            } else {
-                // v_rsq_f32 (1 ulp) instead of an IEEE sqrt + an IEEE divide: this loop is VALU-bound (PMC:
-                // 68 % VALU-active at 4 TB/s), and the two expansions were a quarter of its instructions
-                const float inv = sq > 0.f ? __builtin_amdgcn_rsqf(sq) : 0.f;
-                const float wa = w * inva;
-                acc[12] += sq * inv * wa;
-                cf = wa * inv;
-            }
-            if (MODE != 0) {
-                const float g0 = cf * r0, g1 = cf * r1, g2 = cf * r2;
-                gp[i][0] += g0; gp[i][1] += g1; gp[i][2] += g2;
-                acc[0] += g0 * x0; acc[1] += g0 * x1; acc[2] += g0 * x2;
-                acc[3] += g1 * x0; acc[4] += g1 * x1; acc[5] += g1 * x2;
-                acc[6] += g2 * x0; acc[7] += g2 * x1; acc[8] += g2 * x2;
-                acc[9] += g0; acc[10] += g1; acc[11] += g2;
-            }
-        }
-        if (MODE == 0) {
-            const float s = dpp_row_sum16(acc[12]);
-            if ((lane & 15) == 0) red[buf][kb][wave * 4 + (lane >> 4)][12] = s;
-        } else {
-            // the 13 sums of a 16-lane row by a reduce-scatter (common.h): 29 VALU operations and ONE 16-byte LDS store per quad
-            // instead of 13 four-step butterflies with a masked 4-byte store each -- this loop is bound by instruction issue
-            // (tools/align_stream_lab.hip: its access pattern alone streams at 6.3 TB/s), and the butterflies, their DPP wait
-            // states and the 13 exec-masked stores were a third of its instructions
-            float v16[16], u[4];
-#pragma unroll
-            for (int j = 0; j < 13; j++) v16[j] = acc[j];
-            v16[13] = v16[14] = v16[15] = 0.f;
-            row_reduce_scatter16<13>(v16, u);
-            if ((lane & 3) == 0) *reinterpret_cast<f32x4*>(&red[buf][kb][wave * 4 + (lane >> 4)][lane & 12]) = f32x4{u[0], u[1], u[2], u[3]};
-        }
-    };
-
-    // The incidence codes are read with SCALAR loads (a uniform index into a noalias table: s_load, counted on lgkmcnt): a vector
-    // load here would need s_waitcnt vmcnt(0) before its value could form the next address and would drain the edge data in flight.
-    // (Rounds 1-2 copied the image's codes to LDS first, which cost the prologue a vector load, an LDS pass and a barrier.)
-    auto code_at = [&](int k) { return inc[__builtin_amdgcn_readfirstlane(k)]; };
-    int buf = 0;
-    A3R_STAMP(1);
-    // one flat loop, two edge sides per trip, each register buffer re-requested right after it has been consumed (one edge side
-    // in flight behind the one being worked on); the LDS batch of EB slots is flushed inside
-    int kb = 0, k0 = kbeg;
-#pragma unroll 1
-    for (int k = kbeg; k < kend; k += 2) {
-        const bool has1 = k + 1 < kend;
-        consume(code_at(k), ea, buf, kb);
-#ifdef A3R_ALIGN_STAMPS
-        if (k == kbeg) { asm volatile("" :: "v"(gp[0][0])); A3R_STAMP(2); }
-#endif
-        if (k + 2 < kend) load_edge(d, code_at(k + 2), P, pix0, valid, ea);
-        if (has1) {
-            consume(code_at(k + 1), eb, buf, kb + 1);
-            if (k + 3 < kend) load_edge(d, code_at(k + 3), P, pix0, valid, eb);
-        }
-        kb += 2;
-        if (kb == EB || k + 2 >= kend) {
-            __syncthreads();
-            if (tid < EB * 4) {
-                // one 16-byte quarter of a slot's row per thread, rows r added in order (the row is handed to the image's last workgroup)
-                const int sb = tid >> 2, q = tid & 3, ks = k0 + sb;
-                if (ks < kend) {
-                    f32x4 s4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int r = 0; r < 16; r++) s4 += *reinterpret_cast<const f32x4*>(&red[buf][sb][r][4 * q]);
-                    store16_wt(d.partE, (unsigned)(((size_t)ks * d.nchunks + chunk) * 64 + 16 * q), s4);
-                }
-            }
-            buf ^= 1; kb = 0; k0 += EB;
-        }
-    }
-    A3R_STAMP(3);
-    if (MODE != 0) {
-    // the Adam moments of this thread's pixels are requested now: their latency runs under the per-image sums below
-    f32x4 m4 = {0.f, 0.f, 0.f, 0.f}, v4 = {0.f, 0.f, 0.f, 0.f};
-    if (VEC && MODE == 2 && valid[0] && !depth_frozen) {
-        const size_t off = (size_t)n * P + pix0;
-        m4 = *reinterpret_cast<const f32x4*>(d.adam_depth + off);
-        v4 = *reinterpret_cast<const f32x4*>(d.adam_depth + (size_t)d.N * P + off);
-    }
-
-    // per-image sums and the per-pixel parameter (forward quantities are recomputed: cheaper than keeping them live)
-    float accN[16], gout[PXT];
-#pragma unroll
-    for (int j = 0; j < 16; j++) accN[j] = 0.f;
-#pragma unroll
-    for (int i = 0; i < PXT; i++) {
-        float dep, ddp, gxm, gym, rel[3];
-        pixel_forward(i, raw[i], monov[i], dep, ddp, gxm, gym, rel);
-        const float h0 = R[0] * gp[i][0] + R[3] * gp[i][1] + R[6] * gp[i][2];
-        const float h1 = R[1] * gp[i][0] + R[4] * gp[i][1] + R[7] * gp[i][2];
-        const float h2 = R[2] * gp[i][0] + R[5] * gp[i][1] + R[8] * gp[i][2];
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            accN[r * 3 + 0] += gp[i][r] * rel[0];
-            accN[r * 3 + 1] += gp[i][r] * rel[1];
-            accN[r * 3 + 2] += gp[i][r] * rel[2];
-            accN[9 + r] += gp[i][r];
-        }
-        const float gd = h0 * gxm * inv_f + h1 * gym * inv_f + h2;
-        accN[12] += -(h0 * rel[0] + h1 * rel[1]) / d.focal_break;
-        accN[13] += -h0 * dep * inv_f * 10.f;
-        accN[14] += -h1 * dep * inv_f * 10.f;
-        accN[15] += gd;
-        gout[i] = gd * ddp;
-    }
-    if (MODE != 0 && d.gprior) {      // depth prior (align_depth_prior_kernel): already w.r.t. the log-depth parameter
-#pragma unroll
-        for (int i = 0; i < PXT; i++)
-            if (valid[i]) gout[i] += d.gprior[(size_t)n * P + pix0 + i * PSTEP];
-    }
-    const size_t NP = (size_t)d.N * P;
-    if (VEC) {
-        if (valid[0]) {
-            const size_t off = (size_t)n * P + pix0;
-            if (MODE == 1) {
-                f32x4 g4 = {gout[0], gout[1], gout[2], gout[3]};
-                if (depth_frozen) g4 = f32x4{0.f, 0.f, 0.f, 0.f};
-                *reinterpret_cast<f32x4*>(g_depth + off) = g4;
-            } else if (!depth_frozen) {       // a frozen depth map and its Adam moments are not touched
-                float pm[4] = {m4.x, m4.y, m4.z, m4.w}, pv[4] = {v4.x, v4.y, v4.z, v4.w}, pp[4];
-#pragma unroll
-                for (int i = 0; i < PXT; i++) { pp[i] = raw[i]; adam_update(pp[i], gout[i], pm[i], pv[i], ad); }
-                f32x4 o0 = {pp[0], pp[1], pp[2], pp[3]}, o1 = {pm[0], pm[1], pm[2], pm[3]}, o2 = {pv[0], pv[1], pv[2], pv[3]};
-                *reinterpret_cast<f32x4*>(d.depth + off) = o0;
-                *reinterpret_cast<f32x4*>(d.adam_depth + off) = o1;
-                *reinterpret_cast<f32x4*>(d.adam_depth + NP + off) = o2;
-            }
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < PXT; i++) {
-            if (!valid[i]) continue;
-            const size_t off = (size_t)n * P + pix0 + i * PSTEP;
-            if (MODE == 1) {
-                g_depth[off] = depth_frozen ? 0.f : gout[i];
-            } else if (!depth_frozen) {
-                float m = d.adam_depth[off], v = d.adam_depth[NP + off], pv = raw[i];
-                adam_update(pv, gout[i], m, v, ad);
-                d.depth[off] = pv; d.adam_depth[off] = m; d.adam_depth[NP + off] = v;
-            }
-        }
-    }
-    A3R_STAMP(4);
-    __syncthreads();   // red[] may still be read by the last batch
-    {
-        float u[4];
-        row_reduce_scatter16<16>(accN, u);
-        if ((lane & 3) == 0) *reinterpret_cast<f32x4*>(&red[0][0][wave * 4 + (lane >> 4)][lane & 12]) = f32x4{u[0], u[1], u[2], u[3]};
-    }
-    __syncthreads();
-    if (tid < 4) {
-        f32x4 s4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int r = 0; r < 16; r++) s4 += *reinterpret_cast<const f32x4*>(&red[0][0][r][4 * tid]);
-        store16_wt(d.partN, (unsigned)(((size_t)n * d.nchunks + chunk) * 64 + 16 * tid), s4);
-    }
-    }   // MODE != 0
-#ifdef A3R_ALIGN_STAMPS
-    A3R_STAMP(5);
-    if (tid == 0 && MODE == 2) {
-        unsigned long long* o = g_align_stamps + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) % 8192 * 8;
-        for (int i = 0; i < 6; i++) o[i] = stamp[i];
-        o[6] = (unsigned long long)(kend - kbeg);
-        o[7] = ((unsigned long long)n << 32) | (unsigned)chunk;
-    }
-#endif
-    if (!d.fused_tail) return;
-
-    // ---- tail of the iteration inside this launch (no finalize launches): last-block-done tickets, two levels.
-    // Level 1, per image: the workgroup that completes image n adds the chunk partials of the image's incidence slots and of the
-    // image itself in a fixed order (one wave per row set: the order does not depend on who runs it -> bitwise reproducible).
-    __syncthreads();                                   // red[] is free again
-    int* flag = reinterpret_cast<int*>(&red[0][0][0][0]);
-    if (!arrive_last(d.tick + n, gridDim.x, flag)) return;
-    for (int k = kbeg + wave; k < kend; k += TPB / 64) {
-        const f32x4 t = wave_sum_rows(d.partE + (size_t)k * d.nchunks * 16, d.nchunks, lane);
-        if (lane < 4) store16_wt(d.sumE, (unsigned)(k * 64 + 16 * lane), t);
-    }
-    if (MODE != 0 && wave == 0) {
-        const f32x4 t = wave_sum_rows(d.partN + (size_t)n * d.nchunks * 16, d.nchunks, lane);
-        if (lane < 4) store16_wt(d.sumN, (unsigned)(n * 64 + 16 * lane), t);
-    }
-    // Level 2: the workgroup that completes the last image runs the chain rules of all edges and images, then the single-block
-    // finalisation (scale coupling, loss, Adam on the small parameters, next iteration's transforms).
-    if (!arrive_last(d.tick + d.N, d.N, flag)) return;
-    for (int e = tid; e < d.E; e += TPB) {
-        const float* s0 = d.sumE + d.slot_of[e * 2 + 0] * 16;
-        const float* s1 = d.sumE + d.slot_of[e * 2 + 1] * 16;
-        double s[13];
-#pragma unroll
-        for (int j = 0; j < 13; j++) s[j] = (double)s0[j] + (double)s1[j];
-        edge_chain(d, e, s, MODE == 0);
-    }
-    for (int m = tid; m < d.N; m += TPB) {
-        double s[16];
-#pragma unroll
-        for (int j = 0; j < 16; j++) s[j] = (double)d.sumN[m * 16 + j];
-        image_chain(d, m, s);
-    }
-    for (int i = tid; i <= d.N; i += TPB)              // counters back to zero for the next launch (write-through stores)
-        __hip_atomic_store(d.tick + i, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();                                   // the chain-rule results are visible to the whole workgroup
-    float* sh = &red[0][0][0][0];
-    double (*shd)[4] = reinterpret_cast<double (*)[4]>(&red[1][0][0][0]);
-    finalize_b_body<MODE>(d, ad, tout, sh, shd);
+// The packed-observation form: the same arguments, then the packed rows and (noalias, like the tables above) the exponent tables.
+// Vectorised pixel ownership only (P % 4 == 0; a3r_align_create refuses anything else).
+template <bool MONO, bool L2, int MODE>
+__global__ __launch_bounds__(TPB, 4) void align_main_packed_kernel(
+    AlignDev d, AdamArgs ad, float* g_depth, TailOut tout, const int* __restrict__ inc_ptr, const int* __restrict__ inc,
+    const float* __restrict__ edge_xf, const float* __restrict__ img_xf, const int* __restrict__ imw, const int* __restrict__ imarea,
+    const int* __restrict__ order, const f16x8* obs_i, const f16x8* obs_j, const int* __restrict__ exp_i, const int* __restrict__ exp_j) {
+    constexpr int FORM = OBS_PACKED;
+    constexpr bool VEC = true;
+    const PackedObs pk = {obs_i, obs_j, exp_i, exp_j};
+#define A3R_OBS_LOAD(code, buf) load_edge(pk, code, P, pix0, valid, buf)
+#define A3R_OBS_UNPACK(code, ed, x, w) unpack_edge(ed, packed_scale(pk, code), x, w)
+#include "align_main_body.inc"
+#undef A3R_OBS_LOAD
+#undef A3R_OBS_UNPACK
 }
 
 // ------------------------------------------------------------------------------------------- depth prior (cloud_opt_flow)
@@ -1362,6 +1082,9 @@ struct a3r_align_s {
     bool shard = false;
     int e0 = 0, e1 = 0;
     bool has_focal_mask = false;      // a3r_align_set_flow refuses shared_focal next to a per-image focal mask
+    // obs_format = 1: the packed rows and exponent tables the handle walks (row 0 = edge e0); d.pred_* / d.w_* are null then
+    bool packed = false;
+    PackedObs pk = {nullptr, nullptr, nullptr, nullptr};
 };
 
 static void refresh_if_dirty(a3r_align_s* a, hipStream_t st) {
@@ -1411,7 +1134,23 @@ extern "C" size_t a3r_align_workspace_bytes(int E, int N, int P) { return ws_lay
 static int align_create_impl(const a3r_align_desc* s, int e0, int e1, bool shard, a3r_align_t* out, void* stream) {
     A3R_CHECK_ARG(s && out, "a3r_align_create: null argument");
     A3R_CHECK_ARG(s->E > 0 && s->N > 0 && s->P > 0, "a3r_align_create: E, N, P must be positive");
-    A3R_CHECK_ARG(s->pred_i && s->pred_j && s->w_i && s->w_j && s->pp0, "a3r_align_create: missing observation buffers");
+    A3R_CHECK_ARG(s->obs_format == 0 || s->obs_format == 1, "a3r_align_create: obs_format must be 0 (fp32) or 1 (packed fp16), got %d", s->obs_format);
+    if (s->obs_format == 1) {
+        A3R_CHECK_ARG(s->pp0, "a3r_align_create: missing observation buffers");
+        A3R_CHECK_ARG(s->P % 4 == 0, "a3r_align_create: packed observations (obs_format = 1) need P %% 4 == 0 (P = %d)", s->P);
+        const struct { const void* p; const char* name; } fp32[4] = {{s->pred_i, "pred_i"}, {s->pred_j, "pred_j"}, {s->w_i, "w_i"}, {s->w_j, "w_j"}};
+        for (const auto& f : fp32)
+            A3R_CHECK_ARG(!f.p, "a3r_align_create: %s must be null with packed observations (obs_format = 1)", f.name);
+        const struct { const void* p; const char* name; } pk[4] = {{s->obs_i, "obs_i"}, {s->obs_j, "obs_j"}, {s->obs_exp_i, "obs_exp_i"}, {s->obs_exp_j, "obs_exp_j"}};
+        for (const auto& f : pk)
+            A3R_CHECK_ARG(f.p, "a3r_align_create: %s is missing (obs_format = 1)", f.name);
+        A3R_CHECK_ARG(((reinterpret_cast<uintptr_t>(s->obs_i) | reinterpret_cast<uintptr_t>(s->obs_j)) & 15) == 0,
+                      "a3r_align_create: packed observations (obs_i, obs_j) must be 16-byte aligned");
+    } else {
+        A3R_CHECK_ARG(s->pred_i && s->pred_j && s->w_i && s->w_j && s->pp0, "a3r_align_create: missing observation buffers");
+        A3R_CHECK_ARG(!s->obs_i && !s->obs_j && !s->obs_exp_i && !s->obs_exp_j,
+                      "a3r_align_create: obs_i / obs_j / obs_exp_i / obs_exp_j must be null with fp32 observations (obs_format = 0)");
+    }
     A3R_CHECK_ARG(s->pw_poses && s->pw_adaptors && s->depth && s->im_poses && s->im_focals && s->im_pp,
                   "a3r_align_create: missing parameter buffers");
     A3R_CHECK_ARG(!s->use_mono || (s->mono && s->shifts), "a3r_align_create: use_mono needs mono and shifts");
@@ -1519,6 +1258,8 @@ static int align_create_impl(const a3r_align_desc* s, int e0, int e1, bool shard
     a->inc = inc;
     a->tab = tab;
     a->shard = shard; a->e0 = e0; a->e1 = e1;
+    a->packed = s->obs_format == 1;
+    if (a->packed) a->pk = {static_cast<const f16x8*>(s->obs_i), static_cast<const f16x8*>(s->obs_j), s->obs_exp_i, s->obs_exp_j};
     *out = a;
     return A3R_OK;
 }
@@ -1555,13 +1296,18 @@ extern "C" int a3r_align_destroy(a3r_align_t a) {
     return A3R_OK;
 }
 
+// The launch of the packed-observation kernels of a MODE (defined at the end of this file)
+static void launch_main_packed(int mode, a3r_align_s* a, const AdamArgs& ad, float* g_depth, const TailOut& tout, dim3 grid,
+                               const float* edge_xf, hipStream_t st);
+
 template <int MODE>
 static void launch_main(a3r_align_s* a, const AdamArgs& ad, float* g_depth, const TailOut& tout, hipStream_t st) {
     dim3 grid(a->d.nchunks, a->d.N), block(TPB);
-    // algorithmic bytes of one iteration: 32 B per edge-pixel + 24 B per image-pixel (+4 mono)
+    // algorithmic bytes of one iteration: 32 B per edge-pixel (16 B packed) + 24 B per image-pixel (+4 mono)
     const float* edge_xf = a->d.edge_xf + (size_t)a->e0 * 16;        // local edge codes of a shard index from its first edge
-    const double bytes = 32.0 * (a->e1 - a->e0) * a->d.P + (MODE == 2 ? 24.0 : 4.0) * a->d.N * a->d.P + (a->use_mono ? 4.0 * a->d.N * a->d.P : 0.0);
+    const double bytes = (a->packed ? 16.0 : 32.0) * (a->e1 - a->e0) * a->d.P + (MODE == 2 ? 24.0 : 4.0) * a->d.N * a->d.P + (a->use_mono ? 4.0 * a->d.N * a->d.P : 0.0);
     ProfScope prof(a->shard ? PK_ALIGN_SHARD_PARTIAL : PK_ALIGN_MAIN, bytes, st);
+    if (a->packed) return launch_main_packed(MODE, a, ad, g_depth, tout, grid, edge_xf, st);
     const bool vec = a->d.P % 4 == 0;
 #define A3R_ALIGN_LAUNCH(MONOV, L2V)                                                                                      \
     do {                                                                                                                 \
@@ -1943,3 +1689,28 @@ int align_scene_view(a3r_align_t a, hipStream_t st, SceneView* v, const char* wh
     return A3R_OK;
 }
 }  // namespace a3r
+
+// ---- packed observations (obs_format = 1) ------------------------------------------------------------------------
+// The packed kernels are named here, at the end of the file, and nowhere before: a kernel template is instantiated where it is
+// first named, so the twelve packed instantiations come after every other kernel of the code object, which keep their places (see
+// run_iteration on what that order is worth).
+template <int MODE>
+static void launch_main_packed_mode(a3r_align_s* a, const AdamArgs& ad, float* g_depth, const TailOut& tout, dim3 grid, const float* edge_xf,
+                               hipStream_t st) {
+#define A3R_ALIGN_LAUNCH(MONOV, L2V)                                                                                             \
+    hipLaunchKernelGGL((align_main_packed_kernel<MONOV, L2V, MODE>), grid, dim3(TPB), 0, st, a->d, ad, g_depth, tout, a->d.inc_ptr, \
+                       a->d.inc, edge_xf, a->d.img_xf, a->d.imw, a->d.imarea, a->d.order, a->pk.obs_i, a->pk.obs_j, a->pk.exp_i, a->pk.exp_j)
+    if (a->use_mono) {
+        if (a->dist_l2) A3R_ALIGN_LAUNCH(true, true); else A3R_ALIGN_LAUNCH(true, false);
+    } else {
+        if (a->dist_l2) A3R_ALIGN_LAUNCH(false, true); else A3R_ALIGN_LAUNCH(false, false);
+    }
+#undef A3R_ALIGN_LAUNCH
+}
+
+static void launch_main_packed(int mode, a3r_align_s* a, const AdamArgs& ad, float* g_depth, const TailOut& tout, dim3 grid,
+                               const float* edge_xf, hipStream_t st) {
+    if (mode == 2) launch_main_packed_mode<2>(a, ad, g_depth, tout, grid, edge_xf, st);
+    else if (mode == 0) launch_main_packed_mode<0>(a, ad, g_depth, tout, grid, edge_xf, st);
+    else launch_main_packed_mode<1>(a, ad, g_depth, tout, grid, edge_xf, st);
+}

@@ -347,18 +347,18 @@ def minimum_spanning_tree(imshapes, edges, pred_i, pred_j, conf_i, conf_j, im_co
     return pts3d, msp_edges, im_focals, im_poses
 
 
-def edge_views(scene, dev):
+def edge_views(scene, dev, preds=None):
     """Per-edge [h,w,3] / [h,w] views of the engine's stacked (zero-filled to max_area) predictions and raw confidences: one
     tensor per edge, shaped like the image it belongs to (side i: image i of the edge, side j: image j)."""
-    eng = scene.engine
     E = len(scene.edges)
     ci, cj = scene._raw_conf_i.to(dev).reshape(E, -1), scene._raw_conf_j.to(dev).reshape(E, -1)
+    pred_i, pred_j = preds if preds is not None else scene._device_predictions(dev)
     if scene._uniform:
         H, W = scene.imshape
-        return eng.pred_i.reshape(E, H, W, 3), eng.pred_j.reshape(E, H, W, 3), ci.reshape(E, H, W), cj.reshape(E, H, W)
+        return pred_i.reshape(E, H, W, 3), pred_j.reshape(E, H, W, 3), ci.reshape(E, H, W), cj.reshape(E, H, W)
     sh = scene.imshapes
-    pi = [eng.pred_i[e, :sh[i][0] * sh[i][1]].view(*sh[i], 3) for e, (i, j) in enumerate(scene.edges)]
-    pj = [eng.pred_j[e, :sh[j][0] * sh[j][1]].view(*sh[j], 3) for e, (i, j) in enumerate(scene.edges)]
+    pi = [pred_i[e, :sh[i][0] * sh[i][1]].view(*sh[i], 3) for e, (i, j) in enumerate(scene.edges)]
+    pj = [pred_j[e, :sh[j][0] * sh[j][1]].view(*sh[j], 3) for e, (i, j) in enumerate(scene.edges)]
     return (pi, pj, [ci[e, :sh[i][0] * sh[i][1]].view(*sh[i]) for e, (i, j) in enumerate(scene.edges)],
             [cj[e, :sh[j][0] * sh[j][1]].view(*sh[j]) for e, (i, j) in enumerate(scene.edges)])
 
@@ -405,7 +405,7 @@ def _mst_device(scene, niter_PnP=10):
     E, N, P = len(edges), scene.n_imgs, scene.max_area
     H, W = scene.imshape
     eidx = {e: k for k, e in enumerate(edges)}
-    pred_i, pred_j = eng.pred_i, eng.pred_j                                  # [E, P, 3]
+    pred_i, pred_j = scene._device_predictions(dev)                         # [E, P, 3]
     conf_i, conf_j = scene._raw_conf_i, scene._raw_conf_j                    # [E, P]
     # ---- edge scores (commons.py:20-25) and every edge's Weiszfeld focal of its first view: two launches, one read-back each
     mean = scene._edge_conf_mean
@@ -565,7 +565,8 @@ def init_minimum_spanning_tree(scene, init_priors=None, niter_PnP=10):
     if getattr(scene, '_fast', False) and init_priors is None and eng.flags['train_poses'] and scene.n_imgs > 1 and not per_image:
         return _mst_device(scene, niter_PnP)
     E, N, P = len(scene.edges), scene.n_imgs, scene.max_area
-    pred_i, pred_j, conf_i, conf_j = edge_views(scene, dev)
+    stacked = scene._device_predictions(dev)               # held to the end of this function: the registrations below read side i again
+    pred_i, pred_j, conf_i, conf_j = edge_views(scene, dev, stacked)
     pts3d, _, im_focals, im_poses = minimum_spanning_tree(scene.imshapes, scene.edges, pred_i, pred_j, conf_i, conf_j, scene.im_conf,
                                                           scene.min_conf_thr, dev, init_priors=init_priors, verbose=scene.verbose)
     # ---- init_from_pts3d (:83-126); the known-poses branch (nkp > 1) re-aligns everything on the preset poses
@@ -585,7 +586,7 @@ def init_minimum_spanning_tree(scene, init_priors=None, niter_PnP=10):
     # all E pairwise registrations pred_i[e] -> pts3d[i] in ONE launch of the moments kernel + one batched 3x3 SVD
     # (stacked buffers zero-filled to max_area; the padded tail carries zero confidence = zero weight)
     pad = lambda t: torch.cat((t, t.new_zeros((P - len(t),) + tuple(t.shape[1:])))) if len(t) < P else t
-    sols = rigid_points_registration_batched(eng.pred_i.reshape(E, P, 3),
+    sols = rigid_points_registration_batched(stacked[0].reshape(E, P, 3),
                                              torch.stack([pad(p.reshape(-1, 3).float()) for p in pts3d]).contiguous(),
                                              scene._raw_conf_i.to(dev).reshape(E, P).float().contiguous(), [i for i, _ in scene.edges])
     pw[:, 0:4] = rotmat_to_unitquat_batched(sols[:, 1:10].reshape(E, 3, 3))

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from ...aligner import AlignEngine
+from ...obs16 import check_obs_dtype
 from . import _native
 from .init_im_poses import inv_rigid
 from .commons import get_conf_trf, get_imshapes, rotmat_to_unitquat, signed_expm1, signed_log1p, unitquat_to_rotmat
@@ -29,7 +30,10 @@ class PointCloudOptimizer:
 
     def __init__(self, view1, view2, pred1, pred2, if_use_mono, mono_depths, dist='l1', conf='log', min_conf_thr=3,
                  base_scale=0.5, allow_pw_adaptors=False, pw_break=20, rand_pose=torch.randn, iterationsCount=None,
-                 verbose=True, optimize_pp=False, focal_break=20, edge_shards=None, edge_shard_group=None):
+                 verbose=True, optimize_pp=False, focal_break=20, edge_shards=None, edge_shard_group=None, obs_dtype='fp32'):
+        # obs_dtype='fp16': the engine stores the pair observations packed (aligner.AlignEngine, obs16.py); the initialisations keep
+        # reading the fp32 predictions, which then stay in host memory and are staged on the device while an initialisation runs
+        self.obs_dtype = check_obs_dtype(obs_dtype)
         # edge_shards=K / edge_shard_group=<process group>: the edge-sharded engine (aligner.ShardedAlignEngine) instead of the fused
         # one; the initialisations (init='mst' / 'known_poses') still work on the gathered observations
         if edge_shards is not None and edge_shard_group is not None:
@@ -140,10 +144,24 @@ class PointCloudOptimizer:
         self.engine.set_params(**(state or self._init))
         # keep handles on the engine's device tensors instead of the (possibly host) originals: no second copy stays alive, and
         # .to() can be called again like nn.Module.to (the confidences are re-derived from the raw host copies)
-        self._pred_i, self._pred_j = self.engine.pred_i, self.engine.pred_j
+        if self.obs_dtype == 'fp32':
+            self._pred_i, self._pred_j = self.engine.pred_i, self.engine.pred_j
+        else:
+            # the engine holds packed records only, and nothing here keeps an fp32 stack on the device: the predictions stay in host
+            # memory (moved there if they came on the device, so that the caller can free its copy) and the initialisations stage
+            # them through _device_predictions for as long as they run
+            self._pred_i, self._pred_j = self._pred_i.cpu(), self._pred_j.cpu()
         self._conf_i, self._conf_j = self._raw_conf_i, self._raw_conf_j
         self._grid = None
         return self
+
+    def _device_predictions(self, device):
+        """The stacked fp32 predictions [E,P,3] of both sides on `device`, for the initialisations.  obs_dtype='fp32': the engine's own
+        tensors.  obs_dtype='fp16': a temporary upload of the host copies kept here -- 24 E P bytes that live only while the caller
+        holds them (the peak during an initialisation is the packed records plus this; afterwards the records alone)."""
+        if self.obs_dtype == 'fp32':
+            return self._pred_i, self._pred_j
+        return tuple(t.to(device, torch.float32).contiguous() for t in (self._pred_i, self._pred_j))
 
     def _stacked_weights(self):
         E, P = len(self.edges), self.max_area
@@ -166,7 +184,7 @@ class PointCloudOptimizer:
         return dict(ei=[i for i, j in self.edges], ej=[j for i, j in self.edges], pred_i=self._pred_i, pred_j=self._pred_j,
                     w_i=w_i, w_j=w_j, imshapes=self.imshapes, mono=self.mono_depths, base_scale=self.base_scale,
                     pw_break=self.pw_break, focal_break=self.focal_break, norm_pw_scale=self.norm_pw_scale, dist=self.dist,
-                    device=device, **self._flags)
+                    device=device, obs_dtype=self.obs_dtype, **self._flags)
 
     def _build_engine(self, device):
         if self.edge_shards is not None or self.edge_shard_group is not None:

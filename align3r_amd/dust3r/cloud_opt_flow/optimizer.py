@@ -219,11 +219,14 @@ class PointCloudOptimizer(_Base):
                                'torch.stack([]), optimizer.py:235)')
         dev = flow_ij.device if flow_ij.is_cuda else torch.device('cuda', torch.cuda.current_device())
         up = lambda t: torch.as_tensor(t).to(device=dev, dtype=torch.float32).contiguous()
-        self._pred_i, self._pred_j = up(self._pred_i), up(self._pred_j)          # [E,P,3]: what the engine is built from
+        pred_i, pred_j = up(self._pred_i), up(self._pred_j)                       # [E,P,3]
+        if self.obs_dtype == 'fp32':
+            self._pred_i, self._pred_j = pred_i, pred_j                          # what the engine is built from
+        # (obs_dtype='fp16': the upload lives to the end of this function; the engine packs from the originals in row chunks)
         fij, fji = up(flow_ij), up(flow_ji)
-        geom = pair_geometry(self.edges, self._pred_i.view(E, H, W, 3), self._pred_j.view(E, H, W, 3), self._conf_i.reshape(E, H, W),
+        geom = pair_geometry(self.edges, pred_i.view(E, H, W, 3), pred_j.view(E, H, W, 3), self._conf_i.reshape(E, H, W),
                              self._conf_j.reshape(E, H, W), dev)
-        masks = ops.motion_masks(self._pred_i, self._pred_j, fij, fji, motion_entries(geom, self.edges, E), lists, self.motion_mask_thre)
+        masks = ops.motion_masks(pred_i, pred_j, fij, fji, motion_entries(geom, self.edges, E), lists, self.motion_mask_thre)
         self._flow_dev = (fij, fji)
         self.dynamic_masks = list(masks.cpu())
 

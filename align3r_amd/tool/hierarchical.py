@@ -88,7 +88,7 @@ def save_frame_arrays(arrays, folder, pattern, start=0):
 # ------------------------------------------------------------------------------------------- the driver
 def hierarchical_alignment(imgs, model, device, *, clip_size=50, niter=300, schedule='linear', lr=0.05, min_conf_thr=3,
                            if_use_mono=False, mono_depths=(), batch_size=1, clamp_conf=True, verbose=False, output_dir=None,
-                           pointcloud_collector=None, clean=False):
+                           pointcloud_collector=None, clean=False, obs_dtype='fp32'):
     """Keyframe pass + per-clip passes (depth_test.py:636-676).  `imgs`: view dicts (load_images).  Returns a dict with the
     per-frame lists `depths`, `confs`, `poses` ([4,4] cam-to-world in the keyframes' frame), `focals`, `intrinsics`, plus
     `keyframes_id`, `clip_size` and the keyframe scene's own results; writes pred_traj.txt / pred_intrinsics.txt /
@@ -113,7 +113,7 @@ def hierarchical_alignment(imgs, model, device, *, clip_size=50, niter=300, sche
 
     def align(out, init_priors=None):
         scene = global_aligner(out, if_use_mono, list(mono_depths), device=device, mode=GlobalAlignerMode.PointCloudOptimizer,
-                               verbose=verbose, min_conf_thr=min_conf_thr)
+                               verbose=verbose, min_conf_thr=min_conf_thr, obs_dtype=obs_dtype)
         scene.compute_global_alignment(init='mst', init_priors=init_priors, niter=niter, schedule=schedule, lr=lr)
         if clean:
             scene.clean_pointcloud()

@@ -60,6 +60,9 @@ def parse(argv=None):
     ap.add_argument("--device-prep", action="store_true",
                     help="un-project, normalise, resize and crop the mono-depth priors, and normalise the images, on --device (csrc/prep.hip: "
                          "the same numbers as the host path, which stays the default)")
+    ap.add_argument("--obs-dtype", choices=("fp32", "fp16"), default="fp32",
+                    help="storage of the aligner's pair observations: fp16 = packed records, half the bytes per edge (obs16.py); the "
+                         "parameters and all arithmetic stay fp32 (no effect with two frames: the PairViewer has no aligner)")
     ap.add_argument("--quiet", action="store_true")
     a = ap.parse_args(argv)
     if a.flow and a.hierarchical:
@@ -94,7 +97,7 @@ def main(argv=None):
     if a.hierarchical and len(imgs) >= 3:
         res = hz.hierarchical_alignment(imgs, model, a.device, clip_size=a.clip_size, niter=a.niter, schedule=a.schedule, lr=a.lr,
                                         min_conf_thr=a.min_conf_thr, batch_size=a.batch_size, verbose=verbose, output_dir=a.out,
-                                        pointcloud_collector=clouds, clean=a.clean)
+                                        pointcloud_collector=clouds, clean=a.clean, obs_dtype=a.obs_dtype)
         depths = res["depths"]
         if a.pointcloud:
             n_points = write_ply_parts(a.pointcloud, [(c["xyz"], c["rgb"]) for c in clouds])
@@ -112,9 +115,12 @@ def main(argv=None):
             scene = flow_aligner(out, a.device, verbose=verbose, min_conf_thr=a.min_conf_thr, shared_focal=not a.not_shared_focal,
                                  flow_loss_weight=0.01, temporal_smoothing_weight=0.01, translation_weight=1.0, flow_loss_start_epoch=0.1,
                                  flow_loss_thre=40, pxl_thre=50, motion_mask_thre=0.35, use_self_mask=not a.gt_masks,
-                                 num_total_iter=a.niter, flow_net=a.flow_weights)
+                                 num_total_iter=a.niter, flow_net=a.flow_weights, obs_dtype=a.obs_dtype)
         else:
-            scene = global_aligner(out, False, [], a.device, mode=mode, verbose=verbose, min_conf_thr=a.min_conf_thr)
+            kw = dict(obs_dtype=a.obs_dtype) if mode == GlobalAlignerMode.PointCloudOptimizer else {}    # the PairViewer has no engine
+            if verbose and a.obs_dtype != "fp32" and not kw:
+                print(f"--obs-dtype {a.obs_dtype} has no effect: two frames go to the PairViewer, which holds no aligner observations")
+            scene = global_aligner(out, False, [], a.device, mode=mode, verbose=verbose, min_conf_thr=a.min_conf_thr, **kw)
         if mode == GlobalAlignerMode.PointCloudOptimizer:
             scene.compute_global_alignment(init="mst", niter=a.niter, schedule=a.schedule, lr=a.lr)
             if a.clean:

@@ -532,9 +532,29 @@ typedef struct {
      * is required when train_adaptors != 0 and ignored otherwise. */
     int train_adaptors;
     float* adam_pw_adaptors;
+    /* Storage of the observations.  obs_format = 0 (a zeroed tail: every caller that predates these fields): fp32 in pred_i / pred_j /
+     * w_i / w_j, the four pointers below null.  obs_format = 1: packed fp16, half the bytes -- per edge side and pixel one 8-byte record
+     * {half(x 2^k), half(y 2^k), half(z 2^k), half(w)} in obs_i / obs_j [E, P] (16-byte aligned) and one exponent k per edge side in
+     * obs_exp_i / obs_exp_j [E] int32, as a3r_align_pack_obs writes them; pred_i / pred_j / w_i / w_j must be null and P % 4 == 0.
+     * The handle then computes exactly what an fp32 handle computes on the decoded observations float(h) 2^-k, float(h_w): parameters,
+     * moments and all arithmetic stay fp32.  Everything else (flow variant, depth prior, train masks, shards) is unchanged. */
+    int obs_format;
+    const void* obs_i;           /* [E, P] records (device) */
+    const void* obs_j;
+    const int32_t* obs_exp_i;    /* [E] (device) */
+    const int32_t* obs_exp_j;
 } a3r_align_desc;
 
 typedef struct a3r_align_s* a3r_align_t;
+
+/* Packs `rows` edge sides of fp32 observations (pred [rows, P, 3], w [rows, P], device) into the obs_format = 1 form: obs [rows, P]
+ * 8-byte records, exps [rows] int32.  Per row: m = max |v| over the FINITE components of pred; k = 0 if m == 0 or nothing is finite,
+ * else clamp(14 - ilogb(m), -100, 100), which puts the largest finite magnitude into [2^14, 2^15); every value is scaled by 2^k
+ * (exact) and rounded to fp16 to nearest-even, the weight is rounded unscaled; non-finite values convert by the IEEE rule.  Decoded,
+ * |pred' - pred| <= max(2^-11 |pred|, 2^-25 2^-k).  Deterministic.  Any row range of larger buffers can be passed (offset all four
+ * pointers), so a caller can stream chunks through one staging buffer and never hold the whole fp32 stack on the device.
+ * obs must be 8-byte aligned; 16-byte loads and stores are used when P % 4 == 0 and pred, w and obs are 16-byte aligned. */
+int a3r_align_pack_obs(const float* pred, const float* w, int rows, long P, void* obs, int32_t* exps, void* stream);
 
 size_t a3r_align_workspace_bytes(int E, int N, int P);
 int a3r_align_create(const a3r_align_desc* desc, a3r_align_t* out, void* stream);
@@ -613,8 +633,9 @@ int a3r_align_pose_matrices(a3r_align_t a, float* edge_M, float* img_R, void* st
  * Everything in the reduce buffer is additive over edges; every non-linear step runs after the reduction, so the replicas stay
  * identical.  Layout (floats): [N*P rounded up to 4] d loss / d depth parameter, [N][16] per-image sums, [E][16] per-edge sums
  * (12 gradient sums, the loss of the edge, 3 zeros; rows outside [e0, e1) are zero).
- * desc is read as by a3r_align_create, except: pred_i / pred_j / w_i / w_j hold the shard's rows only ([e1 - e0, P, 3] / [e1 - e0, P],
- * row 0 = edge e0); ei_host / ej_host, total_area_i / j and the parameter buffers describe the WHOLE graph; workspace holds
+ * desc is read as by a3r_align_create, except: pred_i / pred_j / w_i / w_j (with obs_format = 1: obs_i / obs_j / obs_exp_i /
+ * obs_exp_j) hold the shard's rows only ([e1 - e0, P, 3] / [e1 - e0, P], row 0 = edge e0); ei_host / ej_host, total_area_i / j and
+ * the parameter buffers describe the WHOLE graph; workspace holds
  * a3r_align_shard_workspace_bytes(E, e1 - e0, N, P).  a3r_align_step / _loss / _grad*, a3r_align_set_flow and
  * a3r_align_set_depth_prior refuse a shard handle; destroy, steps_done, invalidate and pose_matrices work on it. */
 size_t a3r_align_shard_workspace_bytes(int E, int E_shard, int N, int P);
