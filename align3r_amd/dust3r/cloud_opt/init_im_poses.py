@@ -388,12 +388,15 @@ def _signed_log1p_np(x):
     return (np.sign(x) * np.log1p(np.abs(x))).astype(np.float32)
 
 
-def _mst_device(scene, niter_PnP=10):
+def _mst_device(scene, niter_PnP=10, init_priors=None):
     """init_minimum_spanning_tree + init_from_pts3d for a problem whose images share one shape and whose predictions are on the GPU:
     the same steps as the generic code below, with every per-pixel pass a launch of liba3r (csrc/init_maps.hip, the Umeyama / PnP
     solvers of init.hip) and the algebra on poses / quaternions in numpy on the host from three small read-backs -- no torch
     arithmetic on the device, hence no dependence on which torch kernels (or rocBLAS) a process has loaded so far: the first call
-    costs what every later call costs."""
+    costs what every later call costs.
+    init_priors = [key pose, key depth, [key focal]] (the clip stage of tool/hierarchical.py; cloud_opt_flow/init_im_poses.py:173-215):
+    the tree is rooted at the first edge that touches image 0, image 0 gets the key pose and the key focal, and the two root maps
+    are moved by the key pose with a3r_sim3_apply reading an uploaded (1, R, T) record -- a launch, like every other map here."""
     import ctypes as C
     from ... import _lib
     from ..._lib import check, ptr, stream_ptr
@@ -423,17 +426,47 @@ def _mst_device(scene, niter_PnP=10):
     # ---- the walk over the tree is decided on the host (it depends on the scores only), then enqueued: per tree edge one
     # registration of the known side onto the world points so far and one similarity applied to the other side
     im_focals = [None] * N
-    pose_src = {}                                 # image -> 'eye' | index of the tree step whose (R, T) is its pose
-    score, i, j = todo.pop()
+    pose_src = {}                                 # image -> 'eye' | 'key' | index of the tree step whose (R, T) is its pose
+    if init_priors is None:
+        score, i, j = todo.pop()
+    else:
+        while todo:                               # the first tree edge that touches image 0; the others go back to the far end
+            score, i, j = todo.pop()
+            if i == 0 or j == 0:
+                break
+            todo.insert(0, (score, i, j))
     if scene.verbose:
         print(f' init edge ({i}*,{j}*) {score=}')
     k0 = eidx[(i, j)]
     pts = torch.empty((N, P, 3), dtype=torch.float32, device=dev)
-    pts[i].copy_(pred_i[k0])
-    pts[j].copy_(pred_j[k0])
     done = {i, j}
-    pose_src[i] = 'eye'
-    im_focals[i] = edge_focal[k0]
+    keypose = None
+    if init_priors is None:
+        pts[i].copy_(pred_i[k0])
+        pts[j].copy_(pred_j[k0])
+        pose_src[i] = 'eye'
+        im_focals[i] = edge_focal[k0]
+    else:
+        keypose = np.array(init_priors[0]).astype(np.float32)
+        keyfocal = float(init_priors[2][0])
+        if i == 0:
+            root = ((pred_i, k0, i), (pred_j, k0, j))
+        elif j == 0:                              # the reverse edge's maps live in image 0's frame
+            kk = eidx[(j, i)]
+            root = ((pred_j, kk, i), (pred_i, kk, j))
+        else:                                     # no tree edge touches image 0: the reference leaves the maps where they are
+            root = None
+            pts[i].copy_(pred_i[k0])
+            pts[j].copy_(pred_j[k0])
+        if root is not None:
+            pose_src[0] = 'key'
+            im_focals[0] = keyfocal
+            rec = np.concatenate(([1.0], keypose[:3, :3].reshape(9), keypose[:3, 3])).astype(np.float32)
+            rec_dev = torch.from_numpy(rec).to(dev)
+            with torch.cuda.device(dev):
+                for src, k, img in root:
+                    check(lib.a3r_sim3_apply(C.c_void_p(src.data_ptr() + 12 * P * k), ptr(rec_dev), 0, 1.0,
+                                             C.c_void_p(pts.data_ptr() + 12 * P * img), P, stream_ptr()), "a3r_sim3_apply")
     steps = []                                    # (edge k, known side 0 = i | 1 = j, known image, new image)
     last_k = k0
     while todo:
@@ -482,7 +515,9 @@ def _mst_device(scene, niter_PnP=10):
     tree = tree_sols.cpu().numpy() if T else np.zeros((0, 13), np.float32)
     im_poses = np.tile(np.eye(4, dtype=np.float32), (N, 1, 1))
     for img, src in pose_src.items():
-        if src != 'eye':
+        if src == 'key':
+            im_poses[img] = keypose
+        elif src != 'eye':
             im_poses[img, :3, :3] = tree[src, 1:10].reshape(3, 3)
             im_poses[img, :3, 3] = tree[src, 10:13]
     order = sorted(scores.items(), key=lambda kv: -kv[1])
@@ -562,8 +597,8 @@ def init_minimum_spanning_tree(scene, init_priors=None, niter_PnP=10):
     known_pose, known_focal = _frozen_masks(scene)
     fz = getattr(scene, '_frozen', None)
     per_image = fz is not None and (fz['pose'].any() or fz['focal'].any())       # the device path knows handle-wide switches only
-    if getattr(scene, '_fast', False) and init_priors is None and eng.flags['train_poses'] and scene.n_imgs > 1 and not per_image:
-        return _mst_device(scene, niter_PnP)
+    if getattr(scene, '_fast', False) and eng.flags['train_poses'] and scene.n_imgs > 1 and not per_image:
+        return _mst_device(scene, niter_PnP, init_priors)
     E, N, P = len(scene.edges), scene.n_imgs, scene.max_area
     stacked = scene._device_predictions(dev)               # held to the end of this function: the registrations below read side i again
     pred_i, pred_j, conf_i, conf_j = edge_views(scene, dev, stacked)

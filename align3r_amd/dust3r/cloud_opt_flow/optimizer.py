@@ -81,6 +81,34 @@ def motion_masks_torch(edges, n_imgs, K_i, K_j, R_i, R_j, T_i, T_j, D_i, D_j, fl
     return [m > thre for m in means], means
 
 
+def load_flow_net(flow_net=None):
+    """flow_net= of the flow aligner -> a RAFT2: a loaded network as it is; a checkpoint path, or None for the reference's default
+    path (cloud_opt_flow/optimizer.py:125), loaded.  Shared by get_flow and tool/hierarchical.py, which loads once per run."""
+    import os
+    from ...raft import RAFT2, load_RAFT
+    if flow_net is None or isinstance(flow_net, (str, os.PathLike)):
+        path = flow_net or 'third_party/RAFT/models/Tartan-C-T432x960-M.pth'
+        if not os.path.isfile(path):
+            raise RuntimeError(f'flow_loss_weight > 0 needs optical flow: no RAFT checkpoint at {path!r} -- pass flow_net= (a loaded '
+                               'align3r_amd.raft.RAFT2 or a checkpoint path) or precomputed flow=(flow_ij, flow_ji) [E,2,H,W]')
+        flow_net = load_RAFT(path)
+    if not isinstance(flow_net, RAFT2):
+        raise TypeError('flow_net must be an align3r_amd.raft.RAFT2 (or a checkpoint path)')
+    return flow_net
+
+
+def place_flow_net(flow_net, device):
+    """flow_net.to(device).eval(), except that a network which already holds an engine on that device keeps it: .to() rebuilds the
+    whole engine (weight upload, packing, synchronising read-backs) -- once per network, not once per scene."""
+    want = torch.device(device)
+    if want.type == 'cuda' and want.index is None:
+        want = torch.device('cuda', torch.cuda.current_device())
+    held = getattr(flow_net, '_engine', None)
+    if held is None or held.device != want:
+        flow_net = flow_net.to(device)
+    return flow_net.eval()
+
+
 class PointCloudOptimizer(_Base):
     def __init__(self, view1, view2, pred1, pred2, optimize_pp=False, focal_break=20, shared_focal=False,
                  flow_loss_fn='smooth_l1', flow_loss_weight=0.0, depth_regularize_weight=0.0, num_total_iter=300,
@@ -136,20 +164,12 @@ class PointCloudOptimizer(_Base):
         pairs (`flow_net(img_i * 255, img_j * 255, iters=20, test_mode=True)[1]`), and the forward-backward consistency masks
         (OccMask(th=3.0); the reference computes and keeps them, its loss does not read them).  Returns (flow_ij, flow_ji)."""
         import os
-        from ...raft import RAFT2, load_RAFT
-        if flow_net is None or isinstance(flow_net, (str, os.PathLike)):
-            path = flow_net or 'third_party/RAFT/models/Tartan-C-T432x960-M.pth'          # optimizer.py:125
-            if not os.path.isfile(path):
-                raise RuntimeError(f'flow_loss_weight > 0 needs optical flow: no RAFT checkpoint at {path!r} -- pass flow_net= (a loaded '
-                                   'align3r_amd.raft.RAFT2 or a checkpoint path) or precomputed flow=(flow_ij, flow_ji) [E,2,H,W]')
-            flow_net = load_RAFT(path)
-        if not isinstance(flow_net, RAFT2):
-            raise TypeError('flow_net must be an align3r_amd.raft.RAFT2 (or a checkpoint path)')
+        flow_net = load_flow_net(flow_net)
         if self.imgs is None:
             raise RuntimeError("get_flow needs the frames: view['img'] is missing")
         if not self._uniform:
             raise RuntimeError('the flow term needs images of one shape (np.stack(self.imgs), optimizer.py:122)')
-        flow_net = flow_net.to(device).eval()
+        flow_net = place_flow_net(flow_net, device)
         imgs = np.stack(self.imgs)                                                          # [N, H, W, 3] in [0, 1]
         ei, ej = [i for i, _ in self.edges], [j for _, j in self.edges]
         f_ij, f_ji = [], []
@@ -250,6 +270,26 @@ class PointCloudOptimizer(_Base):
         K_i, K_j, R_i, R_j, T_i, T_j, D_i, D_j = (torch.stack(x).to(dev) for x in (K_i, K_j, R_i, R_j, T_i, T_j, D_i, D_j))
         masks, _ = motion_masks_torch(self.edges, self.n_imgs, K_i, K_j, R_i, R_j, T_i, T_j, D_i, D_j, flow_ij, flow_ji, self.motion_mask_thre)
         self.dynamic_masks = [m.cpu() for m in masks]
+
+    # ------------------------------------------------------------------ re-anchoring (cloud_opt_flow/base_opt.py:305-330)
+    def align_poses(self, init_keypose, poses):
+        """[N,4,4] cam-to-world poses moved rigidly so that frame 0 IS init_keypose: frames 1.. are left-multiplied by
+        init_keypose @ inv(poses[0]).  numpy, in the dtype of `poses`, as in the reference."""
+        T_relative = init_keypose @ np.linalg.inv(poses[0])
+        aligned_poses = np.zeros_like(poses)
+        aligned_poses[0] = init_keypose
+        for i in range(1, poses.shape[0]):
+            aligned_poses[i] = T_relative @ poses[i]
+        return aligned_poses
+
+    def get_tum_poses(self, init_keypose=None):
+        """[tum poses [N,7], timestamps [N]]; with init_keypose the poses are re-anchored on it first (what the clip stage of
+        tool/pose_test.py:463 writes)."""
+        from ...tool.hierarchical import get_tum_poses
+        poses = self.get_im_poses()
+        if init_keypose is not None:
+            poses = self.align_poses(np.array(init_keypose), poses.detach().cpu().numpy())
+        return get_tum_poses(poses)
 
     # ------------------------------------------------------------------ output files (cloud_opt_flow/base_opt.py:358-388)
     def get_init_conf(self, mode=None):

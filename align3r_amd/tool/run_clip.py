@@ -10,10 +10,14 @@ The flow of the reference's tool/demo.py and tool/depth_test.py through this pac
            [--hierarchical --clip-size 50] [--niter 300] [--schedule linear] [--lr 0.01] [--traj-format custom] [--gt-depth DIR]
            [--pointcloud scene.ply] [--clean] [--device-prep]
            [--flow [--flow-weights RAFT.pth] [--gt-masks DIR] [--not-shared-focal]]
+           [--flow-hierarchical [--clip-size 10] [--device-resident] [--flow-weights ...] [--gt-masks DIR] [--not-shared-focal]]
 
 --flow is the sequence of the reference's tool/pose_test.py:154-216: the flow-regularised aligner (cloud_opt_flow) with self-computed
 motion masks on a swinstride-5-noncyclic graph, and on top of the usual outputs pred_focal.txt, dynamic_mask_X.png, their 3x3-enlarged
 copies enlarged_dynamic_mask_X.png (5x5 with --gt-masks) and init_conf_X.npy.
+--flow-hierarchical is tool/pose_test.py --mode eval_pose_h (:346-479): the same aligner and settings for a keyframe graph and then
+for every clip of --clip-size frames (default 10 in this mode), each clip initialised on and re-anchored at its keyframe; with
+--device-resident the pair forwards stay on the device and every clip takes the device initialisation.
 """
 from __future__ import annotations
 
@@ -39,7 +43,7 @@ def parse(argv=None):
     ap.add_argument("--scene-graph", default=None, help="default: swin-3-noncyclic, with --flow swinstride-5-noncyclic")
     ap.add_argument("--batch-size", type=int, default=16)
     ap.add_argument("--hierarchical", action="store_true", help="keyframe -> clip alignment (tool/depth_test.py:628-676)")
-    ap.add_argument("--clip-size", type=int, default=50)
+    ap.add_argument("--clip-size", type=int, default=None, help="default: 50 with --hierarchical, 10 with --flow-hierarchical")
     ap.add_argument("--niter", type=int, default=300)
     ap.add_argument("--schedule", default="linear")
     ap.add_argument("--lr", type=float, default=0.01)
@@ -57,6 +61,11 @@ def parse(argv=None):
     ap.add_argument("--flow-weights", default=None, metavar="PATH", help="RAFT checkpoint of --flow (flow_net=)")
     ap.add_argument("--gt-masks", default=None, metavar="DIR", help="--flow with motion masks read from DIR instead of self-computed ones")
     ap.add_argument("--not-shared-focal", action="store_true", help="--flow: one focal per image instead of a shared one")
+    ap.add_argument("--flow-hierarchical", action="store_true",
+                    help="keyframe -> clip alignment with the flow-regularised aligner (tool/pose_test.py --mode eval_pose_h); implies the "
+                         "--flow settings")
+    ap.add_argument("--device-resident", action="store_true",
+                    help="--flow-hierarchical: keep the pair forwards' outputs on the device")
     ap.add_argument("--device-prep", action="store_true",
                     help="un-project, normalise, resize and crop the mono-depth priors, and normalise the images, on --device (csrc/prep.hip: "
                          "the same numbers as the host path, which stays the default)")
@@ -67,7 +76,13 @@ def parse(argv=None):
     a = ap.parse_args(argv)
     if a.flow and a.hierarchical:
         ap.error("--flow cannot be combined with --hierarchical: the keyframe / clip alignment has no flow term")
-    if not a.flow:
+    if a.flow_hierarchical and (a.flow or a.hierarchical):
+        ap.error("--flow-hierarchical stands alone: it implies the --flow settings and is its own keyframe / clip driver")
+    if a.device_resident and not a.flow_hierarchical:
+        ap.error("--device-resident belongs to --flow-hierarchical")
+    if a.clip_size is None:
+        a.clip_size = 10 if a.flow_hierarchical else 50          # pose_test.py:346 / depth_test.py:636
+    if not (a.flow or a.flow_hierarchical):
         for given, name in ((a.flow_weights, "--flow-weights"), (a.gt_masks, "--gt-masks"), (a.not_shared_focal, "--not-shared-focal")):
             if given:
                 ap.error(f"{name} belongs to --flow")
@@ -91,13 +106,20 @@ def main(argv=None):
     model = AsymmetricCroCo3DStereo.from_pretrained(a.weights).to(a.device)
     imgs, _ = load_images(a.images, a.size, verbose=verbose, traj_format=a.traj_format, start=a.start, interval=a.interval,
                           depth_prior_name=a.depth_prior_name, prep_device=a.device if a.device_prep else None,
-                          dynamic_mask_root=a.gt_masks if a.flow and a.gt_masks else os.path.join(a.out, "__no_masks__"))
+                          dynamic_mask_root=a.gt_masks if (a.flow or a.flow_hierarchical) and a.gt_masks
+                          else os.path.join(a.out, "__no_masks__"))
     os.makedirs(a.out, exist_ok=True)
     clouds, n_points = ([] if a.pointcloud else None), None
-    if a.hierarchical and len(imgs) >= 3:
+    if a.flow_hierarchical and len(imgs) < 3:
+        raise RuntimeError("--flow-hierarchical needs at least 3 frames")
+    if (a.hierarchical or a.flow_hierarchical) and len(imgs) >= 3:
+        extra = {}
+        if a.flow_hierarchical:
+            extra = dict(flow=dict(shared_focal=not a.not_shared_focal, use_self_mask=not a.gt_masks, flow_net=a.flow_weights),
+                         device_resident=a.device_resident)
         res = hz.hierarchical_alignment(imgs, model, a.device, clip_size=a.clip_size, niter=a.niter, schedule=a.schedule, lr=a.lr,
                                         min_conf_thr=a.min_conf_thr, batch_size=a.batch_size, verbose=verbose, output_dir=a.out,
-                                        pointcloud_collector=clouds, clean=a.clean, obs_dtype=a.obs_dtype)
+                                        pointcloud_collector=clouds, clean=a.clean, obs_dtype=a.obs_dtype, **extra)
         depths = res["depths"]
         if a.pointcloud:
             n_points = write_ply_parts(a.pointcloud, [(c["xyz"], c["rgb"]) for c in clouds])
