@@ -53,22 +53,28 @@ def unitquat_to_rotmat(q):
     return torch.stack(rows, -1).reshape(q.shape[:-1] + (3, 3))
 
 
+def rotmats_to_unitquats(R):
+    """[B,3,3] rotation matrices (numpy) -> [B,4] XYZW unit quaternions, float32 (stands in for roma.rotmat_to_unitquat,
+    base_opt.py:203): the numerically stable largest-component branch selection, in float64, every branch evaluated and one
+    selected per matrix.  The package's one implementation of the formula."""
+    R = np.asarray(R, dtype=np.float64)
+    m = lambda i, j: R[:, i, j]
+    tr = m(0, 0) + m(1, 1) + m(2, 2)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        s0 = np.sqrt(np.maximum(tr + 1.0, 1e-300)) * 2
+        b0 = np.stack([(m(2, 1) - m(1, 2)) / s0, (m(0, 2) - m(2, 0)) / s0, (m(1, 0) - m(0, 1)) / s0, 0.25 * s0], -1)
+        s1 = np.sqrt(np.maximum(1.0 + m(0, 0) - m(1, 1) - m(2, 2), 1e-300)) * 2
+        b1 = np.stack([0.25 * s1, (m(0, 1) + m(1, 0)) / s1, (m(0, 2) + m(2, 0)) / s1, (m(2, 1) - m(1, 2)) / s1], -1)
+        s2 = np.sqrt(np.maximum(1.0 + m(1, 1) - m(0, 0) - m(2, 2), 1e-300)) * 2
+        b2 = np.stack([(m(0, 1) + m(1, 0)) / s2, 0.25 * s2, (m(1, 2) + m(2, 1)) / s2, (m(0, 2) - m(2, 0)) / s2], -1)
+        s3 = np.sqrt(np.maximum(1.0 + m(2, 2) - m(0, 0) - m(1, 1), 1e-300)) * 2
+        b3 = np.stack([(m(0, 2) + m(2, 0)) / s3, (m(1, 2) + m(2, 1)) / s3, 0.25 * s3, (m(1, 0) - m(0, 1)) / s3], -1)
+    c0 = (tr > 0)[:, None]
+    c1 = ((m(0, 0) > m(1, 1)) & (m(0, 0) > m(2, 2)))[:, None]
+    c2 = (m(1, 1) > m(2, 2))[:, None]
+    return np.where(c0, b0, np.where(c1, b1, np.where(c2, b2, b3))).astype(np.float32)
+
+
 def rotmat_to_unitquat(R):
-    """Rotation matrix -> XYZW unit quaternion (stands in for roma.rotmat_to_unitquat, base_opt.py:203):
-    the numerically stable largest-component branch selection."""
-    R = torch.as_tensor(R, dtype=torch.float64)
-    m00, m01, m02, m10, m11, m12, m20, m21, m22 = R.reshape(9).tolist()
-    tr = m00 + m11 + m22
-    if tr > 0:
-        s = np.sqrt(tr + 1.0) * 2
-        q = ((m21 - m12) / s, (m02 - m20) / s, (m10 - m01) / s, 0.25 * s)
-    elif m00 > m11 and m00 > m22:
-        s = np.sqrt(1.0 + m00 - m11 - m22) * 2
-        q = (0.25 * s, (m01 + m10) / s, (m02 + m20) / s, (m21 - m12) / s)
-    elif m11 > m22:
-        s = np.sqrt(1.0 + m11 - m00 - m22) * 2
-        q = ((m01 + m10) / s, 0.25 * s, (m12 + m21) / s, (m02 - m20) / s)
-    else:
-        s = np.sqrt(1.0 + m22 - m00 - m11) * 2
-        q = ((m02 + m20) / s, (m12 + m21) / s, 0.25 * s, (m10 - m01) / s)
-    return torch.tensor(q, dtype=torch.float32)
+    """One rotation matrix (tensor, array or nested list) -> XYZW unit quaternion, a float32 CPU tensor."""
+    return torch.from_numpy(rotmats_to_unitquats(torch.as_tensor(R, dtype=torch.float64).reshape(1, 3, 3).cpu().numpy())[0])

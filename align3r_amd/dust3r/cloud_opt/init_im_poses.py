@@ -12,14 +12,21 @@ parity with cv2 (its RANSAC is stochastic and absent; the fixture replaces it by
 of its own algorithm and to ground truth (tests/init_cases.py, tests/test_gpu_init.py) and validated by what it is for: the
 alignment loss after initialisation and the recovered geometry on synthetic scenes (tests/test_gpu_api.py).
 It is a one-off O(E*P) host-orchestrated step, not the inner loop.
+Everything the tree decides -- the spanning tree, the root, the walk with its re-queues, which step gives which image its pose,
+which edge gives which image its focal (the quirk included), who goes to PnP, the verbose lines -- depends on the E edge scores
+only and is decided ONCE, by plan_spanning_tree (pure host code, tests/test_mst_plan_cpu.py).  Two executors run that plan:
+minimum_spanning_tree (torch arithmetic; host inputs, ragged shapes, per-image presets) and _mst_device (launches of liba3r, the
+path production takes).  The quaternion formula both tails write is commons.rotmats_to_unitquats.
 """
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import numpy as np
 import scipy.sparse as sp
 import torch
 
-from .commons import rotmat_to_unitquat, signed_log1p
+from .commons import rotmat_to_unitquat, rotmats_to_unitquats, signed_log1p
 
 
 PNP_MAX_POINTS = 16384
@@ -86,29 +93,6 @@ def rigid_points_registration_batched(X, Y, W, y_index):
     ar = torch.arange(E, device=dev, dtype=torch.int64)
     yi = torch.as_tensor(y_index, device=dev, dtype=torch.int64)
     return umeyama_solve(X, Y, W, ar * (P * 3), yi * (P * 3), ar * P, P)
-
-
-def rotmat_to_unitquat_batched(R):
-    """[B,3,3] rotation matrices (device) -> [B,4] XYZW unit quaternions, the same largest-component branch selection as
-    commons.rotmat_to_unitquat, evaluated for all branches and selected per matrix (no synchronisation)."""
-    R = R.double()
-    m = lambda i, j: R[:, i, j]
-    tr = m(0, 0) + m(1, 1) + m(2, 2)
-    def branch(sq, q):
-        s = torch.sqrt(sq.clamp(min=1e-300)) * 2
-        return torch.stack([c(s) for c in q], -1)
-    b0 = branch(tr + 1.0, (lambda s: (m(2, 1) - m(1, 2)) / s, lambda s: (m(0, 2) - m(2, 0)) / s, lambda s: (m(1, 0) - m(0, 1)) / s,
-                           lambda s: 0.25 * s))
-    b1 = branch(1.0 + m(0, 0) - m(1, 1) - m(2, 2), (lambda s: 0.25 * s, lambda s: (m(0, 1) + m(1, 0)) / s,
-                                                    lambda s: (m(0, 2) + m(2, 0)) / s, lambda s: (m(2, 1) - m(1, 2)) / s))
-    b2 = branch(1.0 + m(1, 1) - m(0, 0) - m(2, 2), (lambda s: (m(0, 1) + m(1, 0)) / s, lambda s: 0.25 * s,
-                                                    lambda s: (m(1, 2) + m(2, 1)) / s, lambda s: (m(0, 2) - m(2, 0)) / s))
-    b3 = branch(1.0 + m(2, 2) - m(0, 0) - m(1, 1), (lambda s: (m(0, 2) + m(2, 0)) / s, lambda s: (m(1, 2) + m(2, 1)) / s,
-                                                    lambda s: 0.25 * s, lambda s: (m(1, 0) - m(0, 1)) / s))
-    c0 = (tr > 0)[:, None]
-    c1 = ((m(0, 0) > m(1, 1)) & (m(0, 0) > m(2, 2)))[:, None]
-    c2 = (m(1, 1) > m(2, 2))[:, None]
-    return torch.where(c0, b0, torch.where(c1, b1, torch.where(c2, b2, b3))).float()
 
 
 def inv_rigid(T):
@@ -255,96 +239,117 @@ def compute_edge_scores(edges, conf_i, conf_j):
     return {tuple(e): float(si[k] * sj[k]) for k, e in enumerate(edges)}
 
 
-def minimum_spanning_tree(imshapes, edges, pred_i, pred_j, conf_i, conf_j, im_conf, min_conf_thr, device, init_priors=None,
-                          has_im_poses=True, verbose=True):
-    """pred_* [E,H,W,3], conf_* [E,H,W] device tensors, or per-edge lists when the images have different shapes.
-    Returns (pts3d list, msp_edges, im_focals list, im_poses [N,4,4])."""
-    n_imgs = len(imshapes)
-    E = len(edges)
-    eidx = {tuple(e): k for k, e in enumerate(edges)}
-    scores = compute_edge_scores(edges, conf_i, conf_j)
+class TreePlan(NamedTuple):
+    """What init='mst' decides from the edge scores alone (plan_spanning_tree); both executors below run it."""
+    root: tuple          # (i, j, k0): the two images placed first and their edge
+    root_maps: tuple     # ((side, edge, image),) * 2: the stacked map (side 0 = pred_i, 1 = pred_j) that fills each root image
+    keyed: bool          # init_priors: the key pose moves both root maps; image 0 takes the key pose and the key focal
+    steps: list          # (edge k, known side 0 = i | 1 = j, known image, new image), in order
+    pose_src: dict       # image -> 'eye' | 'key' | index of the step whose (R, T) is its pose
+    focal_src: dict      # image -> 'key' | the edge whose first-view Weiszfeld focal it takes
+    missing: list        # the images without a pose, ascending: handed to PnP
+    lines: list          # (score, i, j, i_is_new, j_is_new) per visited edge: the verbose lines (print_tree_lines)
+    requeued: int        # how often the walk put an edge back ("let's try again later")
+
+
+def plan_spanning_tree(n_imgs, edges, scores, rooted_at_image0=False):
+    """The spanning tree over -scores (scipy.sparse.csgraph), its root and the walk over it (:129-252), on the host and from the
+    scores alone: no tensor, no device, no printing.  scores: {(i, j): float} for every edge.  rooted_at_image0 (init_priors,
+    cloud_opt_flow/init_im_poses.py:173-215): the root is the first tree edge, best first, that touches image 0."""
+    edges = [tuple(e) for e in edges]
+    eidx = {e: k for k, e in enumerate(edges)}
     graph = sp.dok_array((n_imgs, n_imgs))
     for (i, j), v in scores.items():
         graph[i, j] = -v
     msp = sp.csgraph.minimum_spanning_tree(graph).tocoo()
     todo = sorted(zip(-msp.data, msp.row.tolist(), msp.col.tolist()))
-    edge_focal = estimate_focals(pred_i) if has_im_poses else None      # every edge's Weiszfeld focal of its first view, one batch
-    pts3d = [None] * n_imgs
-    im_poses = [None] * n_imgs
-    im_focals = [None] * n_imgs
-    if init_priors is None:
-        score, i, j = todo.pop()
-    else:
-        while todo:
+    if rooted_at_image0:
+        for _ in range(len(todo)):                # the edges passed over go back to the far end
             score, i, j = todo.pop()
             if i == 0 or j == 0:
                 break
             todo.insert(0, (score, i, j))
-    if verbose:
-        print(f' init edge ({i}*,{j}*) {score=}')
-    k = eidx[(i, j)]
-    pts3d[i], pts3d[j] = pred_i[k].clone(), pred_j[k].clone()
-    done = {i, j}
-    if has_im_poses:
-        if init_priors is None:
-            im_poses[i] = torch.eye(4, device=device)
-            im_focals[i] = edge_focal[k]
-        else:
-            keypose = torch.as_tensor(np.array(init_priors[0]).astype(np.float32), device=device)
-            keyfocal = float(init_priors[2][0])
-            if i == 0:
-                im_poses[i], im_focals[i] = keypose, keyfocal
-                pts3d[i], pts3d[j] = geotrf(keypose, pts3d[i]), geotrf(keypose, pts3d[j])
-            elif j == 0:
-                im_poses[j], im_focals[j] = keypose, keyfocal
-                kk = eidx[(j, i)]
-                pts3d[i], pts3d[j] = geotrf(keypose, pred_j[kk].clone()), geotrf(keypose, pred_i[kk].clone())
-    msp_edges = [(i, j)]
-    last_k = k
+        assert i == 0 or j == 0, 'every image has an edge, so the spanning forest has one at image 0'
+    else:
+        score, i, j = todo.pop()
+    k0 = eidx[(i, j)]
+    root = (i, j, k0)
+    if rooted_at_image0 and i != 0:               # j == 0: the reverse edge's maps live in image 0's frame
+        kk = eidx[(j, i)]
+        root_maps = ((1, kk, i), (0, kk, j))
+    else:
+        root_maps = ((0, k0, i), (1, k0, j))
+    pose_src = {0: 'key'} if rooted_at_image0 else {i: 'eye'}
+    focal_src = {0: 'key'} if rooted_at_image0 else {i: k0}
+    lines = [(score, i, j, True, True)]
+    done, steps, requeued, last_k = {i, j}, [], 0, k0
     while todo:
         score, i, j = todo.pop()
-        if im_focals[i] is None:
-            im_focals[i] = edge_focal[last_k]      # the reference uses the PREVIOUS edge's map here (:199)
-        if i in done:
-            if verbose:
-                print(f' init edge ({i},{j}*) {score=}')
-            assert j not in done
-            k = last_k = eidx[(i, j)]
-            s, R, T = rigid_points_registration(pred_i[k], pts3d[i], conf_i[k])
-            pts3d[j] = geotrf(sRT_to_4x4(s, R, T, device), pred_j[k])
-            done.add(j)
-            msp_edges.append((i, j))
-            if has_im_poses and im_poses[i] is None:
-                im_poses[i] = sRT_to_4x4(1, R, T, device)
-        elif j in done:
-            if verbose:
-                print(f' init edge ({i}*,{j}) {score=}')
+        focal_src.setdefault(i, last_k)           # the reference uses the PREVIOUS edge's map here (:199), re-queued edges included
+        if (i in done) == (j in done):
             assert i not in done
-            k = last_k = eidx[(i, j)]
-            s, R, T = rigid_points_registration(pred_j[k], pts3d[j], conf_j[k])
-            pts3d[i] = geotrf(sRT_to_4x4(s, R, T, device), pred_i[k])
-            done.add(i)
-            msp_edges.append((i, j))
-            if has_im_poses and im_poses[i] is None:
-                im_poses[i] = sRT_to_4x4(1, R, T, device)
-        else:
             todo.insert(0, (score, i, j))
-    if has_im_poses:
-        order = sorted(scores.items(), key=lambda kv: -kv[1])
-        for (i, j), _ in order:
-            if im_focals[i] is None:
-                im_focals[i] = edge_focal[eidx[(i, j)]]
-        missing = [i for i in range(n_imgs) if im_poses[i] is None]            # every missing pose in ONE device batch
-        for i, res in zip(missing, linear_pnp_many([(pts3d[i], im_focals[i], (im_conf[i] > min_conf_thr).to(device), None) for i in missing])):
-            if res:
-                im_focals[i], im_poses[i] = res
-        for i in missing:
-            if im_poses[i] is None:
-                im_poses[i] = torch.eye(4, device=device)
-        im_poses = torch.stack(im_poses)
-    else:
-        im_poses = im_focals = None
-    return pts3d, msp_edges, im_focals, im_poses
+            requeued += 1
+            continue
+        k = last_k = eidx[(i, j)]
+        steps.append((k, 0, i, j) if i in done else (k, 1, j, i))
+        lines.append((score, i, j, i not in done, j not in done))
+        done |= {i, j}
+        pose_src.setdefault(i, len(steps) - 1)    # always the edge's first image, whichever side is new
+    for (i, j), _ in sorted(scores.items(), key=lambda kv: -kv[1]):
+        focal_src.setdefault(i, eidx[(i, j)])
+    missing = [i for i in range(n_imgs) if i not in pose_src]
+    return TreePlan(root, root_maps, bool(rooted_at_image0), steps, pose_src, focal_src, missing, lines, requeued)
+
+
+def print_tree_lines(plan):
+    """The reference's verbose lines: a star marks the image an edge places."""
+    for score, i, j, i_new, j_new in plan.lines:
+        print(f" init edge ({i}{'*' * i_new},{j}{'*' * j_new}) {score=}")
+
+
+def _plan_focals(plan, n_imgs, edge_focal, init_priors):
+    """Per image: the focal the plan assigns it (None: no edge has it as its first view)."""
+    im_focals = [None] * n_imgs
+    for img, src in plan.focal_src.items():
+        im_focals[img] = float(init_priors[2][0]) if src == 'key' else edge_focal[src]
+    return im_focals
+
+
+def minimum_spanning_tree(imshapes, edges, pred_i, pred_j, conf_i, conf_j, im_conf, min_conf_thr, device, init_priors=None,
+                          has_im_poses=True, verbose=True):
+    """plan_spanning_tree executed in torch.  pred_* [E,H,W,3], conf_* [E,H,W] device tensors, or per-edge lists when the images
+    have different shapes.  Returns (pts3d list, msp_edges, im_focals list, im_poses [N,4,4])."""
+    n_imgs = len(imshapes)
+    plan = plan_spanning_tree(n_imgs, edges, compute_edge_scores(edges, conf_i, conf_j), init_priors is not None)
+    if verbose:
+        print_tree_lines(plan)
+    edge_focal = estimate_focals(pred_i) if has_im_poses else None      # every edge's Weiszfeld focal of its first view, one batch
+    preds, confs = (pred_i, pred_j), (conf_i, conf_j)
+    pts3d = [None] * n_imgs
+    if plan.keyed:
+        keypose = torch.as_tensor(np.array(init_priors[0]).astype(np.float32), device=device)
+    for side, k, img in plan.root_maps:
+        pts3d[img] = geotrf(keypose, preds[side][k]) if plan.keyed else preds[side][k].clone()
+    sols = []
+    for k, side, known, new in plan.steps:
+        s, R, T = rigid_points_registration(preds[side][k], pts3d[known], confs[side][k])
+        pts3d[new] = geotrf(sRT_to_4x4(s, R, T, device), preds[1 - side][k])
+        sols.append((R, T))
+    msp_edges = [plan.root[:2]] + [tuple(edges[k]) for k, _, _, _ in plan.steps]
+    if not has_im_poses:
+        return pts3d, msp_edges, None, None
+    im_focals = _plan_focals(plan, n_imgs, edge_focal, init_priors)
+    im_poses = [None] * n_imgs
+    for img, src in plan.pose_src.items():
+        im_poses[img] = keypose if src == 'key' else torch.eye(4, device=device) if src == 'eye' else sRT_to_4x4(1, *sols[src], device)
+    items = [(pts3d[i], im_focals[i], (im_conf[i] > min_conf_thr).to(device), None) for i in plan.missing]
+    for i, res in zip(plan.missing, linear_pnp_many(items)):             # every missing pose in ONE device batch
+        if res:
+            im_focals[i], im_poses[i] = res
+        else:
+            im_poses[i] = torch.eye(4, device=device)
+    return pts3d, msp_edges, im_focals, torch.stack(im_poses)
 
 
 def edge_views(scene, dev, preds=None):
@@ -364,33 +369,13 @@ def edge_views(scene, dev, preds=None):
 
 
 # ------------------------------------------------------------------------------------------------ device fast path
-def _quat_xyzw_np(R):
-    """[B,3,3] rotation matrices (numpy) -> [B,4] XYZW unit quaternions; branch selection as commons.rotmat_to_unitquat."""
-    R = np.asarray(R, dtype=np.float64)
-    m = lambda i, j: R[:, i, j]
-    tr = m(0, 0) + m(1, 1) + m(2, 2)
-    with np.errstate(invalid='ignore', divide='ignore'):
-        s0 = np.sqrt(np.maximum(tr + 1.0, 1e-300)) * 2
-        b0 = np.stack([(m(2, 1) - m(1, 2)) / s0, (m(0, 2) - m(2, 0)) / s0, (m(1, 0) - m(0, 1)) / s0, 0.25 * s0], -1)
-        s1 = np.sqrt(np.maximum(1.0 + m(0, 0) - m(1, 1) - m(2, 2), 1e-300)) * 2
-        b1 = np.stack([0.25 * s1, (m(0, 1) + m(1, 0)) / s1, (m(0, 2) + m(2, 0)) / s1, (m(2, 1) - m(1, 2)) / s1], -1)
-        s2 = np.sqrt(np.maximum(1.0 + m(1, 1) - m(0, 0) - m(2, 2), 1e-300)) * 2
-        b2 = np.stack([(m(0, 1) + m(1, 0)) / s2, 0.25 * s2, (m(1, 2) + m(2, 1)) / s2, (m(0, 2) - m(2, 0)) / s2], -1)
-        s3 = np.sqrt(np.maximum(1.0 + m(2, 2) - m(0, 0) - m(1, 1), 1e-300)) * 2
-        b3 = np.stack([(m(0, 2) + m(2, 0)) / s3, (m(1, 2) + m(2, 1)) / s3, 0.25 * s3, (m(1, 0) - m(0, 1)) / s3], -1)
-    c0 = (tr > 0)[:, None]
-    c1 = ((m(0, 0) > m(1, 1)) & (m(0, 0) > m(2, 2)))[:, None]
-    c2 = (m(1, 1) > m(2, 2))[:, None]
-    return np.where(c0, b0, np.where(c1, b1, np.where(c2, b2, b3))).astype(np.float32)
-
-
 def _signed_log1p_np(x):
     return (np.sign(x) * np.log1p(np.abs(x))).astype(np.float32)
 
 
 def _mst_device(scene, niter_PnP=10, init_priors=None):
     """init_minimum_spanning_tree + init_from_pts3d for a problem whose images share one shape and whose predictions are on the GPU:
-    the same steps as the generic code below, with every per-pixel pass a launch of liba3r (csrc/init_maps.hip, the Umeyama / PnP
+    the same plan (plan_spanning_tree) as minimum_spanning_tree runs, with every per-pixel pass a launch of liba3r (csrc/init_maps.hip, the Umeyama / PnP
     solvers of init.hip) and the algebra on poses / quaternions in numpy on the host from three small read-backs -- no torch
     arithmetic on the device, hence no dependence on which torch kernels (or rocBLAS) a process has loaded so far: the first call
     costs what every later call costs.
@@ -407,7 +392,6 @@ def _mst_device(scene, niter_PnP=10, init_priors=None):
     edges = [tuple(e) for e in scene.edges]
     E, N, P = len(edges), scene.n_imgs, scene.max_area
     H, W = scene.imshape
-    eidx = {e: k for k, e in enumerate(edges)}
     pred_i, pred_j = scene._device_predictions(dev)                         # [E, P, 3]
     conf_i, conf_j = scene._raw_conf_i, scene._raw_conf_j                    # [E, P]
     # ---- edge scores (commons.py:20-25) and every edge's Weiszfeld focal of its first view: two launches, one read-back each
@@ -418,80 +402,25 @@ def _mst_device(scene, niter_PnP=10, init_priors=None):
     mean = mean.cpu().numpy()
     edge_focal = focal_dev.cpu().numpy().tolist()
     scores = {e: float(np.float32(mean[2 * k]) * np.float32(mean[2 * k + 1])) for k, e in enumerate(edges)}
-    graph = sp.dok_array((N, N))
-    for (i, j), v in scores.items():
-        graph[i, j] = -v
-    msp = sp.csgraph.minimum_spanning_tree(graph).tocoo()
-    todo = sorted(zip(-msp.data, msp.row.tolist(), msp.col.tolist()))
     # ---- the walk over the tree is decided on the host (it depends on the scores only), then enqueued: per tree edge one
     # registration of the known side onto the world points so far and one similarity applied to the other side
-    im_focals = [None] * N
-    pose_src = {}                                 # image -> 'eye' | 'key' | index of the tree step whose (R, T) is its pose
-    if init_priors is None:
-        score, i, j = todo.pop()
-    else:
-        while todo:                               # the first tree edge that touches image 0; the others go back to the far end
-            score, i, j = todo.pop()
-            if i == 0 or j == 0:
-                break
-            todo.insert(0, (score, i, j))
+    plan = plan_spanning_tree(N, edges, scores, init_priors is not None)
     if scene.verbose:
-        print(f' init edge ({i}*,{j}*) {score=}')
-    k0 = eidx[(i, j)]
+        print_tree_lines(plan)
+    steps, preds, confs = plan.steps, (pred_i, pred_j), (conf_i, conf_j)
     pts = torch.empty((N, P, 3), dtype=torch.float32, device=dev)
-    done = {i, j}
+    at = lambda t, byte: C.c_void_p(t.data_ptr() + byte)
     keypose = None
-    if init_priors is None:
-        pts[i].copy_(pred_i[k0])
-        pts[j].copy_(pred_j[k0])
-        pose_src[i] = 'eye'
-        im_focals[i] = edge_focal[k0]
-    else:
+    if plan.keyed:
         keypose = np.array(init_priors[0]).astype(np.float32)
-        keyfocal = float(init_priors[2][0])
-        if i == 0:
-            root = ((pred_i, k0, i), (pred_j, k0, j))
-        elif j == 0:                              # the reverse edge's maps live in image 0's frame
-            kk = eidx[(j, i)]
-            root = ((pred_j, kk, i), (pred_i, kk, j))
-        else:                                     # no tree edge touches image 0: the reference leaves the maps where they are
-            root = None
-            pts[i].copy_(pred_i[k0])
-            pts[j].copy_(pred_j[k0])
-        if root is not None:
-            pose_src[0] = 'key'
-            im_focals[0] = keyfocal
-            rec = np.concatenate(([1.0], keypose[:3, :3].reshape(9), keypose[:3, 3])).astype(np.float32)
-            rec_dev = torch.from_numpy(rec).to(dev)
+        rec = np.concatenate(([1.0], keypose[:3, :3].reshape(9), keypose[:3, 3])).astype(np.float32)
+        rec_dev = torch.from_numpy(rec).to(dev)
+    for side, k, img in plan.root_maps:
+        if plan.keyed:
             with torch.cuda.device(dev):
-                for src, k, img in root:
-                    check(lib.a3r_sim3_apply(C.c_void_p(src.data_ptr() + 12 * P * k), ptr(rec_dev), 0, 1.0,
-                                             C.c_void_p(pts.data_ptr() + 12 * P * img), P, stream_ptr()), "a3r_sim3_apply")
-    steps = []                                    # (edge k, known side 0 = i | 1 = j, known image, new image)
-    last_k = k0
-    while todo:
-        score, i, j = todo.pop()
-        if im_focals[i] is None:
-            im_focals[i] = edge_focal[last_k]      # the reference uses the PREVIOUS edge's map here (:199)
-        if i in done:
-            if scene.verbose:
-                print(f' init edge ({i},{j}*) {score=}')
-            assert j not in done
-            k = last_k = eidx[(i, j)]
-            steps.append((k, 0, i, j))
-            done.add(j)
-        elif j in done:
-            if scene.verbose:
-                print(f' init edge ({i}*,{j}) {score=}')
-            assert i not in done
-            k = last_k = eidx[(i, j)]
-            steps.append((k, 1, j, i))
-            done.add(i)
+                check(lib.a3r_sim3_apply(at(preds[side], 12 * P * k), ptr(rec_dev), 0, 1.0, at(pts, 12 * P * img), P, stream_ptr()), "a3r_sim3_apply")
         else:
-            todo.insert(0, (score, i, j))
-            continue
-        if i not in pose_src:
-            pose_src[i] = len(steps) - 1
+            pts[img].copy_(preds[side][k])
     T = len(steps)
     nch = int(lib.a3r_umeyama_chunks(P))
     st = stream_ptr()
@@ -500,42 +429,36 @@ def _mst_device(scene, niter_PnP=10, init_priors=None):
         off_dev = torch.from_numpy(np.ascontiguousarray(off.T)).to(dev)          # [3, T]: x, y, w element offsets
         partial = torch.empty((nch, 17), dtype=torch.float64, device=dev)
         tree_sols = torch.empty((T, 13), dtype=torch.float32, device=dev)
-        at = lambda t, byte: C.c_void_p(t.data_ptr() + byte)
         with torch.cuda.device(dev):
             for t, (k, side, known, new) in enumerate(steps):
-                x, w, other = (pred_i, conf_i, pred_j) if side == 0 else (pred_j, conf_j, pred_i)
-                check(lib.a3r_umeyama_moments(ptr(x), ptr(pts), ptr(w), at(off_dev, 8 * t), at(off_dev, 8 * (T + t)), at(off_dev, 8 * (2 * T + t)),
+                check(lib.a3r_umeyama_moments(ptr(preds[side]), ptr(pts), ptr(confs[side]), at(off_dev, 8 * t), at(off_dev, 8 * (T + t)), at(off_dev, 8 * (2 * T + t)),
                                               1, P, ptr(partial), st), "a3r_umeyama_moments")
                 check(lib.a3r_umeyama_solve(ptr(partial), nch, 1, at(tree_sols, 52 * t), st), "a3r_umeyama_solve")
-                check(lib.a3r_sim3_apply(at(other, 12 * P * k), at(tree_sols, 52 * t), 1, 1.0, at(pts, 12 * P * new), P, st), "a3r_sim3_apply")
+                check(lib.a3r_sim3_apply(at(preds[1 - side], 12 * P * k), at(tree_sols, 52 * t), 1, 1.0, at(pts, 12 * P * new), P, st), "a3r_sim3_apply")
     # ---- all E pairwise registrations pred_i[e] -> pts[i] (init_from_pts3d :100-109), enqueued before the first read-back
     offs = np.asarray([[e * P * 3 for e in range(E)], [i * P * 3 for i, _ in edges], [e * P for e in range(E)]], dtype=np.int64)
     offs_dev = torch.from_numpy(offs).to(dev)
     sols = umeyama_solve(pred_i, pts, conf_i, offs_dev[0], offs_dev[1], offs_dev[2], P)
     tree = tree_sols.cpu().numpy() if T else np.zeros((0, 13), np.float32)
     im_poses = np.tile(np.eye(4, dtype=np.float32), (N, 1, 1))
-    for img, src in pose_src.items():
+    for img, src in plan.pose_src.items():
         if src == 'key':
             im_poses[img] = keypose
         elif src != 'eye':
             im_poses[img, :3, :3] = tree[src, 1:10].reshape(3, 3)
             im_poses[img, :3, 3] = tree[src, 10:13]
-    order = sorted(scores.items(), key=lambda kv: -kv[1])
-    for (i, j), _ in order:
-        if im_focals[i] is None:
-            im_focals[i] = edge_focal[eidx[(i, j)]]
-    missing = [i for i in range(N) if i not in pose_src]                     # every missing pose in ONE device batch
-    if missing:
+    im_focals = _plan_focals(plan, N, edge_focal, init_priors)
+    if plan.missing:                                                         # every missing pose in ONE device batch
         masks = _native.mask_gt(scene._im_conf_stack, scene.min_conf_thr)
-        res = linear_pnp_many([(pts[i].view(H, W, 3), im_focals[i], masks[i].view(H, W), None) for i in missing])
-        for i, r in zip(missing, res):
+        res = linear_pnp_many([(pts[i].view(H, W, 3), im_focals[i], masks[i].view(H, W), None) for i in plan.missing])
+        for i, r in zip(plan.missing, res):
             if r:
                 im_focals[i] = r[0]
                 im_poses[i] = r[1].cpu().numpy()
     sols = sols.cpu().numpy()
     # ---- pairwise poses, global scale, image poses, depth maps, focals: what init_from_pts3d writes into the optimiser (:100-126)
     pw = np.empty((E, 8), np.float32)
-    pw[:, 0:4] = _quat_xyzw_np(sols[:, 1:10].reshape(E, 3, 3))
+    pw[:, 0:4] = rotmats_to_unitquats(sols[:, 1:10].reshape(E, 3, 3))
     pw[:, 4:7] = _signed_log1p_np(sols[:, 10:13] / sols[:, 0:1])
     pw[:, 7] = np.log(sols[:, 0])
     s_factor = float(np.exp(np.float32(np.log(scene.base_scale)) - pw[:, 7].mean(dtype=np.float32))) if scene.norm_pw_scale else 1.0
@@ -547,17 +470,12 @@ def _mst_device(scene, niter_PnP=10, init_priors=None):
     new = dict(pw_poses=torch.from_numpy(pw))
     if eng.flags['train_poses']:
         poses = np.empty((N, 7), np.float32)
-        poses[:, 0:4] = _quat_xyzw_np(im_poses[:, :3, :3])
+        poses[:, 0:4] = rotmats_to_unitquats(im_poses[:, :3, :3])
         poses[:, 4:7] = _signed_log1p_np(im_poses[:, :3, 3])
         new['im_poses'] = torch.from_numpy(poses)
     if eng.flags['train_focals']:
         focals = eng.params['im_focals'].cpu().numpy().copy()
-        if getattr(eng, 'shared_focal', False):
-            focals[0] = scene.focal_break * float(np.log(_shared_focal(im_focals)))
-        else:
-            for i in range(N):
-                if im_focals[i] is not None:
-                    focals[i] = scene.focal_break * float(np.log(im_focals[i]))
+        _write_focal_rows(scene, focals, im_focals, np.zeros(N, bool))
         new['im_focals'] = torch.from_numpy(focals)
     eng.set_params(**new)
     _state_written(scene)
@@ -570,12 +488,33 @@ def _shared_focal(im_focals):
     return sum(im_focals) / len(im_focals)
 
 
+def _write_focal_rows(scene, focals, im_focals, known_focal):
+    """The engine's focal rows (tensor or array, written in place): focal_break * log f for every image that has an estimate and
+    is not preset; a shared_focal problem has one row, the mean estimate."""
+    eng = scene._need_engine()
+    if eng.shared_focal:
+        if eng.flags['train_focals']:
+            focals[0] = scene.focal_break * float(np.log(_shared_focal(im_focals)))
+        return
+    for i, f in enumerate(im_focals):
+        if f is not None and not known_focal[i]:
+            focals[i] = scene.focal_break * float(np.log(f))
+
+
+def _pad_rows(t, P):
+    """[n, ...] -> [P, ...], zero-filled (what optimizer._ravel_hw does to a map that is already flat)."""
+    return torch.cat((t, t.new_zeros((P - len(t),) + tuple(t.shape[1:])))) if len(t) < P else t
+
+
+def _quat_rows(R, like):
+    """[B,3,3] device rotations -> [B,4] unit quaternions next to `like`: one read-back, commons.rotmats_to_unitquats, one upload."""
+    return torch.from_numpy(rotmats_to_unitquats(R.detach().cpu().numpy())).to(device=like.device, dtype=like.dtype)
+
+
 def _state_written(scene):
     """The end of init_from_pts3d: the flow variant captures the depth maps for its prior BEFORE the loss is evaluated
     (cloud_opt_flow/init_im_poses.py:149-154), then the verbose line."""
-    hook = getattr(scene, '_mst_state_written', None)
-    if hook is not None:
-        hook()
+    scene._mst_state_written()
     if scene.verbose:
         print(' init loss =', float(scene()))
 
@@ -584,7 +523,7 @@ def _frozen_masks(scene):
     """Per image: is the pose / the focal preset?  (get_known_poses / get_known_focal_mask of the reference.)  The stacked class
     presets all images at once (its train_* flags); ModularPointCloudOptimizer keeps per-image masks in scene._frozen."""
     eng, N = scene._need_engine(), scene.n_imgs
-    fz = getattr(scene, '_frozen', None)
+    fz = scene._frozen
     pose = np.ones(N, bool) if not eng.flags['train_poses'] else (fz['pose'].copy() if fz else np.zeros(N, bool))
     focal = np.ones(N, bool) if not eng.flags['train_focals'] else (fz['focal'].copy() if fz else np.zeros(N, bool))
     return pose, focal
@@ -595,9 +534,9 @@ def init_minimum_spanning_tree(scene, init_priors=None, niter_PnP=10):
     eng = scene._need_engine()
     dev = eng.device
     known_pose, known_focal = _frozen_masks(scene)
-    fz = getattr(scene, '_frozen', None)
+    fz = scene._frozen
     per_image = fz is not None and (fz['pose'].any() or fz['focal'].any())       # the device path knows handle-wide switches only
-    if getattr(scene, '_fast', False) and eng.flags['train_poses'] and scene.n_imgs > 1 and not per_image:
+    if scene._fast and eng.flags['train_poses'] and scene.n_imgs > 1 and not per_image:
         return _mst_device(scene, niter_PnP, init_priors)
     E, N, P = len(scene.edges), scene.n_imgs, scene.max_area
     stacked = scene._device_predictions(dev)               # held to the end of this function: the registrations below read side i again
@@ -620,11 +559,10 @@ def init_minimum_spanning_tree(scene, init_priors=None, niter_PnP=10):
     pw = eng.params['pw_poses'].clone()
     # all E pairwise registrations pred_i[e] -> pts3d[i] in ONE launch of the moments kernel + one batched 3x3 SVD
     # (stacked buffers zero-filled to max_area; the padded tail carries zero confidence = zero weight)
-    pad = lambda t: torch.cat((t, t.new_zeros((P - len(t),) + tuple(t.shape[1:])))) if len(t) < P else t
     sols = rigid_points_registration_batched(stacked[0].reshape(E, P, 3),
-                                             torch.stack([pad(p.reshape(-1, 3).float()) for p in pts3d]).contiguous(),
+                                             torch.stack([_pad_rows(p.reshape(-1, 3).float(), P) for p in pts3d]).contiguous(),
                                              scene._raw_conf_i.to(dev).reshape(E, P).float().contiguous(), [i for i, _ in scene.edges])
-    pw[:, 0:4] = rotmat_to_unitquat_batched(sols[:, 1:10].reshape(E, 3, 3))
+    pw[:, 0:4] = _quat_rows(sols[:, 1:10].reshape(E, 3, 3), pw)
     pw[:, 4:7] = signed_log1p(sols[:, 10:13] / sols[:, 0:1])
     pw[:, 7] = sols[:, 0].log()
     s_factor = torch.exp(np.log(scene.base_scale) - pw[:, 7].mean()) if scene.norm_pw_scale else 1.0      # stays on the device
@@ -638,16 +576,12 @@ def init_minimum_spanning_tree(scene, init_priors=None, niter_PnP=10):
         w2c = inv_rigid(im_poses)
         for i in range(N):
             d = geotrf(w2c[i], pts3d[i].reshape(-1, 3))[:, 2]
-            depth[i] = pad(d).log().nan_to_num(neginf=0)          # _set_depthmap: _ravel_hw zero-fill, log(0) -> 0
+            depth[i] = _pad_rows(d, P).log().nan_to_num(neginf=0)  # _set_depthmap: _ravel_hw zero-fill, log(0) -> 0
     free = torch.from_numpy(~known_pose).to(poses.device)
     if free.any():
-        poses[free, 0:4] = rotmat_to_unitquat_batched(im_poses[:, :3, :3])[free].to(poses.dtype)
+        poses[free, 0:4] = _quat_rows(im_poses[:, :3, :3], poses)[free]
         poses[free, 4:7] = signed_log1p(im_poses[:, :3, 3])[free].to(poses.dtype)
-    for i in range(N):
-        if im_focals[i] is not None and not known_focal[i] and not getattr(eng, 'shared_focal', False):
-            focals[i] = scene.focal_break * float(np.log(im_focals[i]))
-    if getattr(eng, 'shared_focal', False) and eng.flags['train_focals']:
-        focals[0] = scene.focal_break * float(np.log(_shared_focal(im_focals)))
+    _write_focal_rows(scene, focals, im_focals, known_focal)
     eng.set_params(pw_poses=pw, depth=depth, im_poses=poses, im_focals=focals)
     _state_written(scene)
 
@@ -677,7 +611,6 @@ def init_from_known_poses(scene, niter_PnP=10, min_conf_thr=3):
         raise AssertionError('not all focals are known')          # the reference asserts nkf == n_imgs
     E, P = len(scene.edges), scene.max_area
     pred_i, pred_j, conf_i, _ = edge_views(scene, dev)
-    pad = lambda t: torch.cat((t, t.new_zeros((P - len(t),) + tuple(t.shape[1:])))) if len(t) < P else t
     known_poses = scene.get_im_poses()
     im_focals = scene.get_focals().reshape(-1)
     im_pp = scene.get_principal_points()
@@ -703,5 +636,5 @@ def init_from_known_poses(scene, niter_PnP=10, min_conf_thr=3):
     if not scene.if_use_mono:
         for n in range(scene.n_imgs):
             _, e, s = best[n]
-            depth[n] = pad(pred_i[e][:, :, 2].reshape(-1) * s).log().nan_to_num(neginf=0)
+            depth[n] = _pad_rows(pred_i[e][:, :, 2].reshape(-1) * s, P).log().nan_to_num(neginf=0)
     eng.set_params(pw_poses=pw, depth=depth)

@@ -27,6 +27,7 @@ from .commons import get_conf_trf, get_imshapes, rotmat_to_unitquat, signed_expm
 
 class PointCloudOptimizer:
     POSE_DIM = 7
+    _frozen = None                  # per-image preset masks: ModularPointCloudOptimizer only (init_im_poses._frozen_masks)
 
     def __init__(self, view1, view2, pred1, pred2, if_use_mono, mono_depths, dist='l1', conf='log', min_conf_thr=3,
                  base_scale=0.5, allow_pw_adaptors=False, pw_break=20, rand_pose=torch.randn, iterationsCount=None,
@@ -494,6 +495,9 @@ class PointCloudOptimizer:
     def _init_known_poses(self, niter_PnP):
         from .init_im_poses import init_from_known_poses              # PnP stand-in: parity unpinned (see that module)
         init_from_known_poses(self, niter_PnP=niter_PnP, min_conf_thr=self.min_conf_thr)
+
+    def _mst_state_written(self):
+        """Called by init='mst' once the state is written and before its verbose loss line; the flow class captures its prior here."""
 
     def _init_from(self, init, init_priors, niter_PnP):
         if init is None:

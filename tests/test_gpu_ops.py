@@ -347,9 +347,11 @@ def test_init_map_kernels():
 
 def test_mst_fast_path_matches_generic_path():
     """The device fast path of init='mst' (one image shape, predictions on the GPU: per-pixel passes as launches, pose algebra in
-    numpy) against the generic torch implementation of the same steps on the same scene: same tree, same poses / focals / depths
-    up to fp32 rounding.  (Both restate init_im_poses.py:69-252; this pins them to each other at a size the reference fixture of test_gpu_mst_parity.py,
-    which pins each of them to the reference, does not reach.)"""
+    numpy) against the generic torch implementation of the same steps on the same scene: same poses / focals / depths up to fp32
+    rounding.  Both EXECUTE one plan -- init_im_poses.plan_spanning_tree decides the tree, the root, the walk, the pose and focal
+    sources and the PnP set from the edge scores, pinned to the reference's walk on the CPU by tests/test_mst_plan_cpu.py -- so what
+    this compares is the arithmetic of the two executors (launches of liba3r + numpy against torch), at a size the reference fixture
+    of test_gpu_mst_parity.py, which pins each of them to the reference, does not reach."""
     import bench
     from align3r_amd.dust3r.cloud_opt import global_aligner
     from align3r_amd.dust3r.image_pairs import make_pairs
