@@ -95,6 +95,9 @@ class PrepDesc(C.Structure):
                 ("idx_y_host", c_void), ("w_y", c_void)]
 
 
+DEPTH_ALIGN_MODES = {"lad": 0, "lstsq": 1, "scale": 2, "median": 3}      # A3R_DEPTH_ALIGN_* of include/a3r.h
+DEPTH_INFO_DOUBLES, DEPTH_METRIC_DOUBLES = 16, 8
+
 EPI_NONE, EPI_GELU, EPI_RESID, EPI_RELU, EPI_ROPE, EPI_RESID2, EPI_PIXSHUF, EPI_HEAD = range(8)
 
 # name -> (restype, argtypes); every symbol declared in include/a3r.h
@@ -223,6 +226,9 @@ SIGNATURES = {
     "a3r_prep_pointmap": (C.c_int, [c_void, C.c_double, C.POINTER(PrepDesc), c_void, C.c_size_t, c_void, c_void]),
     "a3r_prep_resize3": (C.c_int, [c_void, C.POINTER(PrepDesc), c_void, C.c_size_t, c_void, c_void]),
     "a3r_prep_image": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void, c_void]),
+    "a3r_depth_eval_workspace_bytes": (C.c_size_t, [C.c_long]),
+    "a3r_depth_align": (C.c_int, [c_void, c_void, C.c_long, C.c_double, C.c_int, c_void, C.c_size_t, c_void, c_void, c_void]),
+    "a3r_depth_metrics": (C.c_int, [c_void, c_void, C.c_long, C.c_double, c_void, c_void, C.c_size_t, c_void, c_void]),
 }
 
 _lib = None

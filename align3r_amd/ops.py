@@ -601,3 +601,50 @@ def prep_image(u8):
     with torch.cuda.device(u8.device):
         check(_lib.load().a3r_prep_image(ptr(u8), H, W, ptr(img), ptr(mask), stream_ptr()), "prep_image")
     return img, mask.view(torch.bool)
+
+
+def _depth_eval_args(pred, gt, what):
+    for t, name in ((pred, "pred"), (gt, "gt")):
+        _req(t, name)
+    if pred.shape != gt.shape:
+        raise ValueError(f"{what}: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} differ in shape")
+    if pred.device != gt.device:
+        raise RuntimeError(f"{what}: pred is on {pred.device}, gt on {gt.device}")
+    lib = _lib.load()
+    n = pred.numel()
+    ws_bytes = int(lib.a3r_depth_eval_workspace_bytes(n))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=pred.device)
+    return lib, n, ws, ws_bytes
+
+
+def depth_align(pred, gt, depth_max=70.0, mode="lad"):
+    """One scale and shift for the whole clip over the pixels with 1e-3 < gt < depth_max (a3r_depth_align, csrc/metrics.hip; the rules
+    of tool/depth_metrics.align_depth).  pred, gt: contiguous float32 device tensors of one shape.  mode: 'lad', 'lstsq', 'scale',
+    'median'.  Enqueue-only; returns device tensors st [2] float64 = (scale, shift) and info [16] float64 (include/a3r.h: n_valid, the
+    LAD objective, passes, enlargements, the middle order statistics of pred and of gt, the medians, the LAD normalisation)."""
+    if mode not in _lib.DEPTH_ALIGN_MODES:
+        raise ValueError(f"bad alignment {mode=}")
+    lib, n, ws, ws_bytes = _depth_eval_args(pred, gt, "depth_align")
+    st = torch.empty(2, dtype=torch.float64, device=pred.device)
+    info = torch.empty(_lib.DEPTH_INFO_DOUBLES, dtype=torch.float64, device=pred.device)
+    with torch.cuda.device(pred.device):
+        check(lib.a3r_depth_align(ptr(pred), ptr(gt), n, float(depth_max), _lib.DEPTH_ALIGN_MODES[mode], ptr(ws), ws_bytes, ptr(st), ptr(info),
+                                  stream_ptr()), "depth_align")
+    return st, info           # the workspace is freed stream-ordered after the kernels
+
+
+def depth_metrics(pred, gt, depth_max, scale, shift=None):
+    """AbsRel, SqRel, RMSE, logRMSE, delta < 1.25^k, n_valid of clip(scale * pred + shift, 1e-5, depth_max) against gt over the pixels
+    with 1e-3 < gt < depth_max (a3r_depth_metrics).  scale, shift: two numbers, or scale = the device tensor [2] float64 that depth_align
+    returned (then nothing leaves the device in between).  Enqueue-only; returns a device tensor [8] float64 in that order."""
+    lib, n, ws, ws_bytes = _depth_eval_args(pred, gt, "depth_metrics")
+    if isinstance(scale, torch.Tensor) and shift is None:
+        st = scale
+        if not (st.is_cuda and st.device == pred.device and st.dtype == torch.float64 and st.is_contiguous() and st.numel() == 2):
+            raise RuntimeError("depth_metrics: (scale, shift) as a tensor must be a contiguous float64 tensor [2] on pred's device")
+    else:
+        st = torch.tensor([float(scale), float(shift)], dtype=torch.float64).to(pred.device)
+    out = torch.empty(_lib.DEPTH_METRIC_DOUBLES, dtype=torch.float64, device=pred.device)
+    with torch.cuda.device(pred.device):
+        check(lib.a3r_depth_metrics(ptr(pred), ptr(gt), n, float(depth_max), ptr(st), ptr(ws), ws_bytes, ptr(out), stream_ptr()), "depth_metrics")
+    return out

@@ -8,7 +8,7 @@ The flow of the reference's tool/demo.py and tool/depth_test.py through this pac
 
     python -m align3r_amd.tool.run_clip --images DIR --weights CKPT.pth --out OUT [--size 512] [--scene-graph swin-3-noncyclic]
            [--hierarchical --clip-size 50] [--niter 300] [--schedule linear] [--lr 0.01] [--traj-format custom] [--gt-depth DIR]
-           [--pointcloud scene.ply] [--clean] [--device-prep]
+           [--metrics-device] [--pointcloud scene.ply] [--clean] [--device-prep]
            [--flow [--flow-weights RAFT.pth] [--gt-masks DIR] [--not-shared-focal]]
            [--flow-hierarchical [--clip-size 10] [--device-resident] [--flow-weights ...] [--gt-masks DIR] [--not-shared-focal]]
 
@@ -50,6 +50,9 @@ def parse(argv=None):
     ap.add_argument("--min-conf-thr", type=float, default=3.0)
     ap.add_argument("--gt-depth", default=None, help="folder of per-frame ground-truth depth .npy (same order) -> AbsRel etc.")
     ap.add_argument("--depth-max", type=float, default=70.0)
+    ap.add_argument("--metrics-device", action="store_true",
+                    help="evaluate --gt-depth on --device (csrc/metrics.hip: the LAD scale + shift and the metric sums as HIP kernels; the "
+                         "host numpy + scipy path stays the default)")
     ap.add_argument("--gt-traj", default=None, help="ground-truth camera trajectory, TUM file `t x y z qx qy qz qw` (same frames) -> ATE / RPE")
     ap.add_argument("--pointcloud", default=None, metavar="PATH",
                     help="write the aligned scene as a binary PLY (with --hierarchical: every clip's points, appended in clip order)")
@@ -80,6 +83,8 @@ def parse(argv=None):
         ap.error("--flow-hierarchical stands alone: it implies the --flow settings and is its own keyframe / clip driver")
     if a.device_resident and not a.flow_hierarchical:
         ap.error("--device-resident belongs to --flow-hierarchical")
+    if a.metrics_device and not a.gt_depth:
+        ap.error("--metrics-device belongs to --gt-depth")
     if a.clip_size is None:
         a.clip_size = 10 if a.flow_hierarchical else 50          # pose_test.py:346 / depth_test.py:636
     if not (a.flow or a.flow_hierarchical):
@@ -110,6 +115,7 @@ def main(argv=None):
                           else os.path.join(a.out, "__no_masks__"))
     os.makedirs(a.out, exist_ok=True)
     clouds, n_points = ([] if a.pointcloud else None), None
+    depths_dev = None                  # --metrics-device: the aligned depth maps as the scene holds them, on the device
     if a.flow_hierarchical and len(imgs) < 3:
         raise RuntimeError("--flow-hierarchical needs at least 3 frames")
     if (a.hierarchical or a.flow_hierarchical) and len(imgs) >= 3:
@@ -147,7 +153,10 @@ def main(argv=None):
             scene.compute_global_alignment(init="mst", niter=a.niter, schedule=a.schedule, lr=a.lr)
             if a.clean:
                 scene.clean_pointcloud()
-        depths = [d.detach().cpu().numpy() for d in scene.get_depthmaps()]
+        depths_dev = scene.get_depthmaps()
+        depths = [d.detach().cpu().numpy() for d in depths_dev]
+        if not (a.metrics_device and mode == GlobalAlignerMode.PointCloudOptimizer):
+            depths_dev = None
         hz.save_trajectory_tum_format(hz.get_tum_poses(scene.get_im_poses()), os.path.join(a.out, "pred_traj.txt"))
         hz.save_intrinsics(scene.get_intrinsics(), os.path.join(a.out, "pred_intrinsics.txt"))
         hz.save_frame_arrays(depths, a.out, "frame_{:04d}.npy")
@@ -166,7 +175,11 @@ def main(argv=None):
     if a.gt_depth:
         files = sorted(glob.glob(os.path.join(a.gt_depth, "*.npy")))[a.start:a.start + len(depths)]
         gt = np.stack([np.load(f) for f in files])
-        metrics = evaluate_depth(np.stack(depths), gt, depth_max=a.depth_max, mode="lad")
+        if a.metrics_device:
+            metrics = evaluate_depth(list(depths_dev) if depths_dev is not None else np.stack(depths), gt, depth_max=a.depth_max, mode="lad",
+                                     device=a.device)
+        else:
+            metrics = evaluate_depth(np.stack(depths), gt, depth_max=a.depth_max, mode="lad")
         if verbose:
             print("depth metrics (LAD scale+shift):", {k: round(v, 5) if isinstance(v, float) else v for k, v in metrics.items()})
     pose = None

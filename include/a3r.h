@@ -771,6 +771,36 @@ int a3r_prep_pointmap(const float* depth, double focal, const a3r_prep_desc* d, 
 int a3r_prep_resize3(const float* src, const a3r_prep_desc* d, void* ws, size_t ws_bytes, float* out, void* stream);
 int a3r_prep_image(const unsigned char* u8, int H, int W, float* img, unsigned char* mask, void* stream);
 
+/* Video-depth evaluation (tool/depth_metrics.py; the reference's tool/depth_test.py:689-835) on the device: ONE scale and shift for
+ * the whole clip, a clip to [1e-5, depth_max], AbsRel / SqRel / RMSE / logRMSE / delta.  pred, gt: float32 device buffers of n =
+ * T * H * W elements; a pixel is valid iff 1e-3 < gt < depth_max (both strict, so a NaN gt is invalid); every sum is float64 over
+ * the float32 inputs.  Streaming reductions with per-workgroup partials folded in a fixed order by one workgroup: no floating-point
+ * atomics, the same call twice gives the same bits.  16-byte loads when pred and gt are both 16-byte aligned, scalar loads otherwise.
+ * Both calls only enqueue on `stream`: nothing is allocated, synchronised or read back.
+ * a3r_depth_align writes st_dev = (scale, shift) and info_dev [A3R_DEPTH_INFO_DOUBLES]:
+ *   [0] n_valid   [1] sum |s p + t - g| at (scale, shift)   [2] passes over the data of the solve   [3] enlargements of the LAD start region
+ *   [4] [5] the two middle order statistics of the valid pred (equal for an odd count)   [6] [7] those of the valid gt   [8] median pred
+ *   [9] median gt   [10] [11] the LAD normalisation (s0, T): the search runs on (s / s0, t / T)
+ * With fewer than 2 valid pixels scale = shift = NaN and info[0] says why.  Modes: LAD (least absolute deviations scale + shift, central-cut
+ * ellipsoid method driven by a one-wave kernel), LSTSQ (least squares scale + shift, centred sums), SCALE (mean ratio + 10 IRLS passes,
+ * shift 0; the passes amplify rounding about 1e12 times, so this rule adds the valid pixels in order with numpy's summation tree and
+ * returns the host's bits; it uses the 8 n bytes of the workspace that hold the compacted maps), MEDIAN (ratio of the medians, shift 0; np.median semantics).
+ * a3r_depth_metrics reads (scale, shift) from st_dev and writes out_dev [A3R_DEPTH_METRIC_DOUBLES]: abs_rel, sq_rel, rmse, log_rmse,
+ * d1, d2, d3, n_valid (the means are NaN when n_valid = 0).
+ * A3R_EINVAL before anything is launched: a null pointer, n <= 0, a depth_max that is not above 1e-3, an unknown mode, a workspace that
+ * is too small or not 16-byte aligned. */
+#define A3R_DEPTH_ALIGN_LAD 0
+#define A3R_DEPTH_ALIGN_LSTSQ 1
+#define A3R_DEPTH_ALIGN_SCALE 2
+#define A3R_DEPTH_ALIGN_MEDIAN 3
+#define A3R_DEPTH_INFO_DOUBLES 16
+#define A3R_DEPTH_METRIC_DOUBLES 8
+size_t a3r_depth_eval_workspace_bytes(long n);
+int a3r_depth_align(const float* pred, const float* gt, long n, double depth_max, int mode, void* workspace, size_t workspace_bytes,
+                    double* st_dev, double* info_dev, void* stream);
+int a3r_depth_metrics(const float* pred, const float* gt, long n, double depth_max, const double* st_dev, void* workspace,
+                      size_t workspace_bytes, double* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
