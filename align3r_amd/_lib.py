@@ -170,6 +170,8 @@ SIGNATURES = {
     "a3r_model_decode": (C.c_int, [c_void, c_void, c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void, c_void, c_void, C.c_size_t, c_void]),
     "a3r_model_tap": (C.c_int, [c_void, C.c_char_p, C.POINTER(c_void), C.POINTER(C.c_size_t)]),
     "a3r_model_set_tap_level": (C.c_int, [c_void, C.c_int]),
+    "a3r_model_set_dedup": (C.c_int, [c_void, C.c_int]),
+    "a3r_model_last_dedup": (C.c_int, [c_void, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "a3r_model_range_check": (C.c_int, [c_void, c_void, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "a3r_model_reset_ranges": (C.c_int, [c_void]),
     "a3r_model_range_stats": (C.c_int, [c_void, c_void, c_void, C.c_int, C.POINTER(C.c_int)]),

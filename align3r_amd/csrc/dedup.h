@@ -1,0 +1,51 @@
+// Duplicate inputs of one pair-forward batch (dedup.hip finds them on the device, model.hip runs the frame-only parts of the plan on
+// the distinct ones).  This header is plain C++ -- no HIP types -- so that the host grouping below can be tested by a stand-alone
+// CPU program (tests/test_dedup_cpu.py).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+namespace a3r {
+
+// Host grouping.  rep[s] (s < n) is the representative of slot s: the smallest slot whose content equals slot s's, so rep[s] <= s
+// and rep[rep[s]] == rep[s].  Writes the distinct slots in ascending order to uniq[0..U) and the row of each slot's representative
+// in that list to map[0..n) (a surjection onto 0..U-1 with map[uniq[k]] == k), and returns U.  Returns -1 and writes nothing
+// meaningful when rep is not such a table (the caller then runs the plan without merging anything).
+inline int dedup_group(const int32_t* rep, int n, int32_t* uniq, int32_t* map) {
+    if (!rep || !uniq || !map || n <= 0) return -1;
+    int U = 0;
+    for (int s = 0; s < n; s++) {
+        const int32_t r = rep[s];
+        if (r < 0 || r > s) return -1;
+        if (r == s) {
+            uniq[U] = s;
+            map[s] = U++;
+        } else {
+            if (rep[r] != r) return -1;
+            map[s] = map[r];
+        }
+    }
+    return U;
+}
+
+// ---- device side (dedup.hip).  An item is one image [3, H, W] or one pred_depth map [H, W, 3]: `words` 32-bit words each, a
+// multiple of 4.  Slot s < 4 B of a call is item s % B of group s / B, the groups being img1, img2, pd1, pd2; slots 0 .. 2 B - 1
+// are the image kind, 2 B .. 4 B - 1 the depth-prior kind, and a representative is looked for inside a slot's own kind only.
+constexpr int DEDUP_MAX_SLOTS = 2048;        // 4 B at most; larger batches run without merging
+// device words: keys [DEDUP_MAX_SLOTS][2] of 64 bits, then rep [DEDUP_MAX_SLOTS] (index inside the kind) and the mismatch flag
+constexpr size_t DEDUP_KEY_BYTES = (size_t)DEDUP_MAX_SLOTS * 16;
+constexpr size_t DEDUP_REP_INTS = DEDUP_MAX_SLOTS + 1;
+// slots [first, 4 B): first = 0 for a whole forward, 2 B for the decode call (no images).  const_key: every key is zero, so the
+// grouping rests on the verification alone (a3r_model_set_dedup mode 2).  Enqueues: clear, key kernel, representative kernel,
+// verify kernel; rep_flag[4 B] ends up nonzero when some slot differs from its representative in any bit.
+int dedup_find(const float* img1, const float* img2, const float* pd1, const float* pd2, int B, long words, int first, bool const_key,
+               void* keys, int32_t* rep_flag, void* stream);
+
+// ---- the plan's ops on distinct items (elementwise.hip)
+// a3r_patchify of the U items uniq[k] (device, indices inside the kind) of the 2 B items of img_a followed by img_b
+int patchify_indexed(const float* img_a, const float* img_b, const int32_t* uniq, int U, int B, float* cols, int C, int H, int W, long sb,
+                     long sc, long sy, long sx, void* stream);
+// dst[(s * N + n) * C + c] = src[(map[s] * N + n) * C + c] for the slots s < S (map on the device); C a multiple of 4
+int gather_rows(const float* src, float* dst, const int32_t* map, int S, int N, int C, void* stream);
+
+}  // namespace a3r

@@ -4,6 +4,7 @@
 #include "common.h"
 #include "bf3.h"
 #include "fh2.h"
+#include "dedup.h"
 #include <cmath>
 #include <cstdlib>
 
@@ -260,6 +261,31 @@ __global__ void patchify_kernel(const float* __restrict__ img, float* __restrict
         const int tx = (int)(t % nw), ty = (int)((t / nw) % nh), b = (int)(t / ((long)nw * nh));
         const int c = k >> 8, py = (k >> 4) & 15, px = k & 15;
         cols[i] = img[b * sb + c * sc + (long)(ty * 16 + py) * sy + (long)(tx * 16 + px) * sx];
+    }
+}
+
+// the same for the U distinct items of a batch (dedup.h): row block k is item uniq[k] of the 2 B items img_a[0..B), img_b[0..B)
+__global__ void patchify_indexed_kernel(const float* __restrict__ img_a, const float* __restrict__ img_b, const int* __restrict__ uniq,
+                                        float* __restrict__ cols, int U, int B, int C, int H, int W, long sb, long sc, long sy, long sx) {
+    const int nh = H / 16, nw = W / 16, K = C * 256;
+    const long total = (long)U * nh * nw * K;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int k = (int)(i % K);
+        const long t = i / K;
+        const int tx = (int)(t % nw), ty = (int)((t / nw) % nh), u = (int)(t / ((long)nw * nh));
+        const int c = k >> 8, py = (k >> 4) & 15, px = k & 15;
+        const int s = uniq[u];
+        const float* img = s < B ? img_a + s * sb : img_b + (s - B) * sb;
+        cols[i] = img[c * sc + (long)(ty * 16 + py) * sy + (long)(tx * 16 + px) * sx];
+    }
+}
+
+// rows of the distinct items back to every slot that holds one: dst row block s = src row block map[s], blocks of N rows of C4 float4
+__global__ void gather_rows_kernel(const f32x4* __restrict__ src, f32x4* __restrict__ dst, const int* __restrict__ map, int S, long NC4) {
+    const long total = (long)S * NC4;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int s = (int)(i / NC4);
+        dst[i] = src[(long)map[s] * NC4 + (i - s * NC4)];
     }
 }
 
@@ -608,6 +634,30 @@ extern "C" int a3r_patchify(const float* img, float* cols, int B, int C, int H, 
     ProfScope prof(PK_ELEMENTWISE, 8.0 * total, as_stream(stream));
     hipLaunchKernelGGL(patchify_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), img, cols, B, C, H, W, sb, sc,
                        sy, sx);
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+int a3r::patchify_indexed(const float* img_a, const float* img_b, const int32_t* uniq, int U, int B, float* cols, int C, int H, int W,
+                          long sb, long sc, long sy, long sx, void* stream) {
+    A3R_CHECK_ARG(img_a && img_b && uniq && cols, "patchify_indexed: null pointer");
+    A3R_CHECK_ARG(H > 0 && H % 16 == 0 && W > 0 && W % 16 == 0 && B > 0 && U > 0 && U <= 2 * B, "patchify_indexed: bad shape");
+    const long total = (long)U * (H / 16) * (W / 16) * C * 256;
+    ProfScope prof(PK_ELEMENTWISE, 8.0 * total, as_stream(stream));
+    hipLaunchKernelGGL(patchify_indexed_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), img_a, img_b, uniq, cols, U, B, C,
+                       H, W, sb, sc, sy, sx);
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+int a3r::gather_rows(const float* src, float* dst, const int32_t* map, int S, int N, int C, void* stream) {
+    A3R_CHECK_ARG(src && dst && map, "gather_rows: null pointer");
+    A3R_CHECK_ARG(S > 0 && N > 0 && C > 0 && C % 4 == 0, "gather_rows: bad shape");
+    A3R_CHECK_ARG(((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0, "gather_rows: buffers must be 16-byte aligned");
+    const long NC4 = (long)N * (C / 4), total = (long)S * NC4;
+    ProfScope prof(PK_ELEMENTWISE, 32.0 * total, as_stream(stream));
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), reinterpret_cast<const f32x4*>(src),
+                       reinterpret_cast<f32x4*>(dst), map, S, NC4);
     A3R_LAUNCH_CHECK();
     return A3R_OK;
 }

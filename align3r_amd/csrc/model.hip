@@ -8,8 +8,10 @@
 //   postprocess                                      dust3r/heads/postprocess.py:10-58
 // Data layout: tokens [rows, C] with rows = (side, batch, token): the first B*N rows belong to view 1,
 // the next B*N rows to view 2 (this is the reference's torch.cat((img1, img2)) batch order), maps are
-// channels-last.  All buffers live in the caller's workspace; nothing here allocates device memory.
+// channels-last.  All buffers live in the caller's workspace; nothing here allocates device memory, except the handle's 64 KB of
+// key / map words for the duplicate search (find_distinct).
 #include "plan.h"
+#include "dedup.h"
 #include <new>
 #include <cstdlib>
 #include <cstring>
@@ -63,6 +65,19 @@ struct a3r_model_s {
     // fixed at finalize from the two weight vectors (gamma pointer -> scale); see ln_static_scale
     std::map<const float*, float> ln_scale;
     int tap_level = 0;               // a3r_model_set_tap_level: decoder level copied to the taps "level" / "pc0" (parity tests), 0 = none
+    // duplicate inputs (dedup.h; a3r_model_set_dedup): 0 = every slot is encoded, 1 = the frame-only parts of the plan run once per
+    // distinct image / pred_depth map of the batch, 2 = as 1 with a constant key (debugging: the verification alone decides)
+    int dedup_mode = 1;
+    int last_img_unique = 0, last_pd_unique = 0, last_fell_back = 0;      // a3r_model_last_dedup
+    // the handle's own small buffers (the only device memory it allocates, at its first merging call): keys, representatives and
+    // flag, the uploaded lists (uniq_img, map_img, uniq_pd, map_pd: DEDUP_MAX_SLOTS / 2 words each), and the pinned host words of
+    // the one read-back and the one upload of a call
+    void* dd_dev = nullptr;
+    int32_t* dd_host = nullptr;
+    ~a3r_model_s() {
+        if (dd_dev) (void)hipFree(dd_dev);
+        if (dd_host) (void)hipHostFree(dd_host);
+    }
 };
 
 static int n_pc_blocks(const a3r_model_config& c) { return c.dec_depth / 2 - 2; }
@@ -91,6 +106,8 @@ extern "C" int a3r_model_create(const a3r_model_config* cfg, a3r_model_t* out) {
     for (const Mode& md : modes)
         if (gemm && !strcmp(gemm, md.name)) { m->gemm_form = md.gemm; m->products = md.products; m->fh2_passes = md.passes; }
     m->map_form = m->gemm_form == Form::FH2 && conv && !strcmp(conv, "bf3") ? Form::BF3 : m->gemm_form;
+    if (const char* dd = getenv("A3R_DEDUP"))      // the default of new handles (a3r_model_set_dedup); anything but 0 / 2 leaves it on
+        m->dedup_mode = !strcmp(dd, "0") ? 0 : !strcmp(dd, "2") ? 2 : 1;
     // sized here so that the host-side sizing pass (a3r_model_workspace_bytes) works before finalize
     m->enc.assign(cfg->enc_depth, BlockW());
     m->pc.assign(n_pc_blocks(*cfg), BlockW());
@@ -705,15 +722,27 @@ float* fusion_map(Plan& P, const FusionW& w, const float* x0, const float* x0r3,
     return r;
 }
 
+// The distinct inputs of a call (dedup.h): n_img / n_pd of the 2 B images / pred_depth maps are distinct (2 B: that kind is not
+// merged).  Device lists: uniq_* [n] the distinct slots, map_* [2 B] each slot's row in that list (null in the sizing pass).
+struct Distinct { int n_img, n_pd; const int32_t *uniq_img, *map_img, *uniq_pd, *map_pd; };
+
 // phase: 0 = whole forward from images; 1 = encoder only (img1 [B,...] -> feat_out [B,N,E]);
 //        2 = decoder + heads from cached encoder features (feat1_in / feat2_in [B,N,E]).
+// dd: run the parts of the plan that depend on one frame alone -- the encoder, and the depth-prior token branch -- on the distinct
+// frames only and copy their rows to every slot.  The ops, their order and so the fh2 site numbers are those of the plain plan;
+// only row counts differ, and every row is computed as it is there.
 int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, const float* pd1, const float* pd2, int B,
              int H, int W, float* pts1, float* conf1, float* pts2, float* conf2, void* ws, size_t ws_bytes, void* stream,
              size_t* peak, int phase = 0, const float* feat1_in = nullptr, const float* feat2_in = nullptr,
-             float* feat_out = nullptr) {
+             float* feat_out = nullptr, const Distinct* dd = nullptr) {
     const a3r_model_config& c = m->cfg;
     const int E = c.enc_embed_dim, D = c.dec_embed_dim, F = c.feature_dim, L = c.last_dim;
     const int nh = H / 16, nw = W / 16, N = nh * nw, BN = B * N, M2 = 2 * BN;
+    // rows of the image / depth-prior stages; merged kinds only (d_img, d_pd)
+    // (the distinct frames' enc_norm rows wait in the first three decoder level buffers, which must hold them: E <= 3 D at least)
+    const bool d_img = dd && phase == 0 && dd->n_img < 2 * B && (size_t)dd->n_img * N * E <= 3 * (size_t)M2 * D;
+    const bool d_pd = dd && dd->n_pd < 2 * B;
+    const int Mi = d_img ? dd->n_img * N : M2, Mp = d_pd ? dd->n_pd * N : M2;
     struct ProductsGuard {      // the handle's arithmetic mode for the duration of this plan
         int prev; bool on;
         ProductsGuard(bool on_, int p) : prev(6), on(on_) { if (on) prev = a3r_bf3_set_products(p); }
@@ -781,48 +810,73 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
             P.rc = A3R_EHIP;
         }
     };
+    // Distinct inputs only (dd): no allocation is added.  The depth-prior tokens of the distinct maps, pcu [Mp, D], live in hook
+    // buffer B, which the decoder first writes at level hook_b, after the last dec_blocks_pc block (dec_depth / 2 - 2 < hook_b); the
+    // distinct frames' enc_norm rows wait in fbuf[0..2] (contiguous, idle until the decoder starts) for their copy to `feat`.
+    float* pcu = d_pd ? fbuf[3] : pc;
+    float* featu = d_img ? fbuf[0] : feat;
+    if (!dry && d_img && (fbuf[1] != fbuf[0] + (size_t)M2 * D || fbuf[2] != fbuf[1] + (size_t)M2 * D)) {
+        set_error("a3r_model_forward: internal: the decoder level buffers are not contiguous");
+        return A3R_ESTATE;
+    }
+    // the row-pair layout (P.pair) of a stage on Mi or Mp rows needs that row count to be even; the 2 B N-row stages keep theirs
+    const bool pair_all = P.pair;
+    auto copy_rows = [&](const float* src, float* dst, const int32_t* map, int C) {      // distinct rows -> the rows of all 2 B slots
+        if (!P.skip()) P.rc = gather_rows(src, dst, map, 2 * B, N, C, stream);
+    };
+    // point-map patch embedding (model.py:244-248); pred_depth is [B,H,W,3]: channel stride 1
+    auto embed_pc = [&](float* cols, float* cols3) {
+        if (!P.skip()) {
+            const long sb = 3L * H * W, sc = 1, sy = 3L * W, sx = 3;
+            if (d_pd) P.rc = patchify_indexed(pd1, pd2, dd->uniq_pd, dd->n_pd, B, cols, 3, H, W, sb, sc, sy, sx, stream);
+            else if (!(P.rc = a3r_patchify(pd1, cols, B, 3, H, W, sb, sc, sy, sx, stream)))
+                P.rc = a3r_patchify(pd2, cols + (size_t)BN * 768, B, 3, H, W, sb, sc, sy, sx, stream);
+        }
+        P.pair = pair_all && Mp % 2 == 0;
+        P.linear(P.gin_from(cols, cols3, Mp, 768), 768, m->pepc_w, pcu, D, Mp, D, 768, P.epi(A3R_EPI_NONE, m->pepc_b));
+        P.pair = pair_all;
+    };
     const size_t mark = ar.off;
     // ---------------- encoder (model.py:151-163)
     if (phase == 2) {
         // cached per-frame features: gather the two views' rows into the [2*B*N, E] layout the decoder expects
-        float* cols = ar.alloc((size_t)M2 * 768);
-        float* cols3 = P.gin_scratch(M2, 768);
+        float* cols = ar.alloc((size_t)Mp * 768);
+        float* cols3 = P.gin_scratch(Mp, 768);
         if (!dry) {
             const size_t bytes = (size_t)BN * E * sizeof(float);
             hipError_t e1 = hipMemcpyAsync(feat, feat1_in, bytes, hipMemcpyDeviceToDevice, as_stream(stream));
             hipError_t e2 = hipMemcpyAsync(feat + (size_t)BN * E, feat2_in, bytes, hipMemcpyDeviceToDevice, as_stream(stream));
             if (e1 != hipSuccess || e2 != hipSuccess) { set_error("a3r_model_decode: feature copy failed"); return A3R_EHIP; }
-            const long sb = 3L * H * W, sc = 1, sy = 3L * W, sx = 3;
-            if ((P.rc = a3r_patchify(pd1, cols, B, 3, H, W, sb, sc, sy, sx, stream))) return P.rc;
-            if ((P.rc = a3r_patchify(pd2, cols + (size_t)BN * 768, B, 3, H, W, sb, sc, sy, sx, stream))) return P.rc;
         }
-        P.linear(P.gin_from(cols, cols3, M2, 768), 768, m->pepc_w, pc, D, M2, D, 768, P.epi(A3R_EPI_NONE, m->pepc_b));
+        embed_pc(cols, cols3);
     } else {
-        float* cols = ar.alloc((size_t)M2 * 768);
-        float* cols3 = P.gin_scratch(M2, 768);
-        float* x = ar.alloc((size_t)M2 * E);
-        float* xn = P.gin_alloc(M2, E);
-        float* qkv = P.gin_alloc(M2, 3 * E);
-        float* att = P.gin_alloc(M2, E);
-        float* hid = P.gin_alloc(M2, E * c.mlp_ratio);
+        const int Mc = Mi > Mp ? Mi : Mp;
+        float* cols = ar.alloc((size_t)Mc * 768);
+        float* cols3 = P.gin_scratch(Mc, 768);
+        float* x = ar.alloc((size_t)Mi * E);
+        float* xn = P.gin_alloc(Mi, E);
+        float* qkv = P.gin_alloc(Mi, 3 * E);
+        float* att = P.gin_alloc(Mi, E);
+        float* hid = P.gin_alloc(Mi, E * c.mlp_ratio);
         if (!dry) {
             const long sb = 3L * H * W, sc = (long)H * W, sy = W, sx = 1;
-            if ((P.rc = a3r_patchify(img1, cols, B, 3, H, W, sb, sc, sy, sx, stream))) return P.rc;
-            if ((P.rc = a3r_patchify(img2, cols + (size_t)BN * 768, B, 3, H, W, sb, sc, sy, sx, stream))) return P.rc;
+            if (d_img) {
+                if ((P.rc = patchify_indexed(img1, img2, dd->uniq_img, dd->n_img, B, cols, 3, H, W, sb, sc, sy, sx, stream))) return P.rc;
+            } else {
+                if ((P.rc = a3r_patchify(img1, cols, B, 3, H, W, sb, sc, sy, sx, stream))) return P.rc;
+                if ((P.rc = a3r_patchify(img2, cols + (size_t)BN * 768, B, 3, H, W, sb, sc, sy, sx, stream))) return P.rc;
+            }
         }
-        P.linear(P.gin_from(cols, cols3, M2, 768), 768, m->pe_w, x, E, M2, E, 768, P.epi(A3R_EPI_NONE, m->pe_b));
+        P.pair = pair_all && Mi % 2 == 0;
+        P.linear(P.gin_from(cols, cols3, Mi, 768), 768, m->pe_w, x, E, Mi, E, 768, P.epi(A3R_EPI_NONE, m->pe_b));
         for (int i = 0; i < c.enc_depth; i++) {
-            P.self_block(m->enc[i], x, x, M2, E, c.enc_num_heads, N, nw, xn, qkv, att);
-            P.mlp(m->enc[i], m->enc[i].n2w, m->enc[i].n2b, x, M2, E, E * c.mlp_ratio, xn, hid);
+            P.self_block(m->enc[i], x, x, Mi, E, c.enc_num_heads, N, nw, xn, qkv, att);
+            P.mlp(m->enc[i], m->enc[i].n2w, m->enc[i].n2b, x, Mi, E, E * c.mlp_ratio, xn, hid);
         }
-        P.ln_f32(x, m->encn_w, m->encn_b, feat, M2, E);
-        // point-map patch embedding (model.py:244-248); pred_depth is [B,H,W,3]: channel stride 1
-        if (!dry) {
-            const long sb = 3L * H * W, sc = 1, sy = 3L * W, sx = 3;
-            if ((P.rc = a3r_patchify(pd1, cols, B, 3, H, W, sb, sc, sy, sx, stream))) return P.rc;
-            if ((P.rc = a3r_patchify(pd2, cols + (size_t)BN * 768, B, 3, H, W, sb, sc, sy, sx, stream))) return P.rc;
-        }
-        P.linear(P.gin_from(cols, cols3, M2, 768), 768, m->pepc_w, pc, D, M2, D, 768, P.epi(A3R_EPI_NONE, m->pepc_b));
+        P.pair = pair_all;
+        P.ln_f32(x, m->encn_w, m->encn_b, featu, Mi, E);
+        if (d_img) copy_rows(featu, feat, dd->map_img, E);
+        embed_pc(cols, cols3);
     }
     ar.off = mark;
     tap_copy(tap_pc0, pc);
@@ -844,6 +898,8 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
             float* feat3 = P.gin_scratch(M2, E);
             P.linear(P.gin_from(feat, feat3, M2, E), E, m->de_w, cur, D, M2, D, E, P.epi(A3R_EPI_NONE, m->de_b));
         }
+        // (distinct maps only: their tokens are copied to all slots' rows first, so the zero-conv and its epilogue stay as they are)
+        if (d_pd) copy_rows(pcu, pc, dd->map_pd, D);
         P.linear(P.gin_from(pc, pc3, M2, D), D, m->zc_w[0], cur, D, M2, D, D, P.epi(A3R_EPI_RESID, m->zc_b[0], cur));
         int next_free = 1;
         const int npc = n_pc_blocks(c);
@@ -894,8 +950,11 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
                           P.epi(A3R_EPI_RESID, nullptr), o0, o1);
             }
             if (i < npc) {   // model.py:223-226
-                P.self_block(m->pc[i], pc, pc, M2, D, c.dec_num_heads, N, nw, xn, qkv, att);
-                P.mlp(m->pc[i], m->pc[i].n2w, m->pc[i].n2b, pc, M2, D, hidden, xn, hid);
+                P.pair = pair_all && Mp % 2 == 0;
+                P.self_block(m->pc[i], pcu, pcu, Mp, D, c.dec_num_heads, N, nw, xn, qkv, att);
+                P.mlp(m->pc[i], m->pc[i].n2w, m->pc[i].n2b, pcu, Mp, D, hidden, xn, hid);
+                P.pair = pair_all;
+                if (d_pd) copy_rows(pcu, pc, dd->map_pd, D);
                 P.linear(P.gin_from(pc, pc3, M2, D), D, m->zc_w[i + 1], nxt, D, M2, D, D, P.epi(A3R_EPI_RESID, m->zc_b[i + 1], nxt));
             }
             if (level == hook_a) lvl_a = nxt;
@@ -1041,11 +1100,74 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
 }
 }  // namespace
 
+// ---- the distinct inputs of one call: key, representative and verify kernels, ONE read-back (with one stream synchronise, at the
+// start of the call), the host grouping and one upload of its lists.  *use = false: run the plain plan (switched off, parity taps
+// on, a batch beyond DEDUP_MAX_SLOTS, nothing to merge, or a slot that differs from its representative: a key collision).
+namespace {
+constexpr int DD_HALF = DEDUP_MAX_SLOTS / 2;                       // slots of one kind at most
+constexpr size_t DD_HOST_LIST = (DEDUP_REP_INTS + 63) / 64 * 64;   // pinned host words: rep + flag | the four lists
+constexpr size_t DD_REP_OFF = DEDUP_KEY_BYTES;                     // device bytes: keys | rep + flag | uniq_img, map_img, uniq_pd, map_pd
+constexpr size_t DD_LIST_OFF = DD_REP_OFF + DD_HOST_LIST * 4;
+constexpr size_t DD_DEV_BYTES = DD_LIST_OFF + (size_t)4 * DD_HALF * 4;
+
+int find_distinct(a3r_model_s* m, const float* img1, const float* img2, const float* pd1, const float* pd2, int B, int H, int W,
+                  bool images, void* stream, Distinct* d, bool* use) {
+    *use = false;
+    m->last_img_unique = m->last_pd_unique = 2 * B;
+    m->last_fell_back = 0;
+    if (m->dedup_mode == 0 || m->tap_level > 0 || 4 * B > DEDUP_MAX_SLOTS) return A3R_OK;
+    if (!m->dd_dev) A3R_HIP(hipMalloc(&m->dd_dev, DD_DEV_BYTES));
+    if (!m->dd_host) A3R_HIP(hipHostMalloc(reinterpret_cast<void**>(&m->dd_host), (DD_HOST_LIST + 4 * DD_HALF) * sizeof(int32_t), hipHostMallocDefault));
+    char* dev = static_cast<char*>(m->dd_dev);
+    int32_t* rep_dev = reinterpret_cast<int32_t*>(dev + DD_REP_OFF);
+    int32_t* list_dev = reinterpret_cast<int32_t*>(dev + DD_LIST_OFF);
+    const int S = 2 * B, first = images ? 0 : S;
+    if (int rc = dedup_find(img1, img2, pd1, pd2, B, 3L * H * W, first, m->dedup_mode == 2, dev, rep_dev, stream)) return rc;
+    hipStream_t st = as_stream(stream);
+    A3R_HIP(hipMemcpyAsync(m->dd_host, rep_dev, (size_t)(2 * S + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    A3R_HIP(hipStreamSynchronize(st));
+    const int32_t* rep = m->dd_host;
+    if (rep[2 * S] != 0) {
+        m->last_fell_back = 1;
+        return A3R_OK;
+    }
+    int32_t* list = m->dd_host + DD_HOST_LIST;
+    int n_img = S;
+    if (images) {
+        n_img = dedup_group(rep, S, list, list + DD_HALF);
+        // the distinct frames' enc_norm rows must fit the buffers they wait in (run_plan)
+        const a3r_model_config& c = m->cfg;
+        if (n_img > 0 && (size_t)n_img * c.enc_embed_dim > 3 * (size_t)S * c.dec_embed_dim) n_img = S;
+    }
+    const int n_pd = dedup_group(rep + S, S, list + 2 * DD_HALF, list + 3 * DD_HALF);
+    if (n_img <= 0 || n_pd <= 0) {       // not a representative table: cannot happen, and is not trusted if it does
+        m->last_fell_back = 1;
+        return A3R_OK;
+    }
+    m->last_img_unique = n_img;
+    m->last_pd_unique = n_pd;
+    if (n_img == S && n_pd == S) return A3R_OK;
+    A3R_HIP(hipMemcpyAsync(list_dev, list, (size_t)4 * DD_HALF * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    *d = {n_img, n_pd, list_dev, list_dev + DD_HALF, list_dev + 2 * DD_HALF, list_dev + 3 * DD_HALF};
+    *use = true;
+    return A3R_OK;
+}
+}  // namespace
+
 extern "C" size_t a3r_model_workspace_bytes(a3r_model_t m, int B, int H, int W) {
     if (!m || B <= 0 || H <= 0 || W <= 0 || H % 16 || W % 16) return 0;
-    size_t peak = 0;
-    run_plan(m, true, nullptr, nullptr, nullptr, nullptr, B, H, W, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &peak);
-    return peak;
+    // the largest of the plain plan and the plans on distinct inputs: those only shrink stages and reuse idle buffers, largest with
+    // one duplicate (2 B - 1 distinct), of the depth priors alone or of both kinds
+    size_t need = 0;
+    const Distinct cases[3] = {{2 * B, 2 * B, nullptr, nullptr, nullptr, nullptr}, {2 * B, 2 * B - 1, nullptr, nullptr, nullptr, nullptr},
+                               {2 * B - 1, 2 * B - 1, nullptr, nullptr, nullptr, nullptr}};
+    for (const Distinct& d : cases) {
+        size_t peak = 0;
+        run_plan(m, true, nullptr, nullptr, nullptr, nullptr, B, H, W, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &peak, 0,
+                 nullptr, nullptr, nullptr, &d);
+        if (peak > need) need = peak;
+    }
+    return need;
 }
 
 extern "C" int a3r_model_forward(a3r_model_t m, const float* img1, const float* img2, const float* pd1, const float* pd2,
@@ -1064,7 +1186,11 @@ extern "C" int a3r_model_forward(a3r_model_t m, const float* img1, const float* 
     A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "a3r_model_forward: workspace must be 256-byte aligned");
     const size_t need_bytes = a3r_model_workspace_bytes(m, B, H, W);
     A3R_CHECK_ARG(workspace_bytes >= need_bytes, "a3r_model_forward: workspace too small (%zu < %zu)", workspace_bytes, need_bytes);
-    return run_plan(m, false, img1, img2, pd1, pd2, B, H, W, pts1, conf1, pts2, conf2, workspace, workspace_bytes, stream, nullptr);
+    Distinct d;
+    bool merge = false;
+    if (int rc = find_distinct(m, img1, img2, pd1, pd2, B, H, W, true, stream, &d, &merge)) return rc;
+    return run_plan(m, false, img1, img2, pd1, pd2, B, H, W, pts1, conf1, pts2, conf2, workspace, workspace_bytes, stream, nullptr, 0,
+                    nullptr, nullptr, nullptr, merge ? &d : nullptr);
 }
 
 static int check_forward_args(a3r_model_t m, int B, int H, int W, const void* workspace, const char* who) {
@@ -1106,8 +1232,25 @@ extern "C" int a3r_model_decode(a3r_model_t m, const float* feat1, const float* 
     A3R_CHECK_ARG(feat1 && feat2 && pd1 && pd2 && pts1 && conf1 && pts2 && conf2, "a3r_model_decode: null pointer");
     const size_t need_bytes = a3r_model_workspace_bytes(m, B, H, W);      // the whole-forward plan bounds the decode plan
     A3R_CHECK_ARG(workspace_bytes >= need_bytes, "a3r_model_decode: workspace too small (%zu < %zu)", workspace_bytes, need_bytes);
+    Distinct d;
+    bool merge = false;
+    if (int rc = find_distinct(m, nullptr, nullptr, pd1, pd2, B, H, W, false, stream, &d, &merge)) return rc;
     return run_plan(m, false, nullptr, nullptr, pd1, pd2, B, H, W, pts1, conf1, pts2, conf2, workspace, workspace_bytes, stream,
-                    nullptr, 2, feat1, feat2, nullptr);
+                    nullptr, 2, feat1, feat2, nullptr, merge ? &d : nullptr);
+}
+
+extern "C" int a3r_model_set_dedup(a3r_model_t m, int mode) {
+    A3R_CHECK_ARG(m && mode >= 0 && mode <= 2, "a3r_model_set_dedup: mode must be 0 (off), 1 (on) or 2 (constant key)");
+    m->dedup_mode = mode;
+    return A3R_OK;
+}
+
+extern "C" int a3r_model_last_dedup(a3r_model_t m, int* n_img_unique, int* n_pd_unique, int* fell_back) {
+    A3R_CHECK_ARG(m && n_img_unique && n_pd_unique && fell_back, "a3r_model_last_dedup: null argument");
+    *n_img_unique = m->last_img_unique;
+    *n_pd_unique = m->last_pd_unique;
+    *fell_back = m->last_fell_back;
+    return A3R_OK;
 }
 
 extern "C" int a3r_model_set_tap_level(a3r_model_t m, int level) {

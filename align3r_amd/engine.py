@@ -155,6 +155,17 @@ class PairEngine:
     def reset_ranges(self):
         check(self.lib.a3r_model_reset_ranges(self.handle), "a3r_model_reset_ranges")
 
+    def set_dedup(self, mode):
+        """Duplicate frames inside one forward / decode call (include/a3r.h, a3r_model_set_dedup): 0 = off, 1 = on (default),
+        2 = on with a constant key (debugging).  Outputs are bitwise the same in every mode."""
+        check(self.lib.a3r_model_set_dedup(self.handle, int(mode)), "a3r_model_set_dedup")
+
+    def last_dedup(self):
+        """(diagnostic) (distinct images, distinct pred_depth maps, fell_back) of the last forward / decode call."""
+        ni, nd, fb = C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.a3r_model_last_dedup(self.handle, C.byref(ni), C.byref(nd), C.byref(fb)), "a3r_model_last_dedup")
+        return ni.value, nd.value, bool(fb.value)
+
     def set_tap_level(self, level):
         """Keep copies of decoder level `level` and of the point-cloud tokens for tap("level") / tap("pc0") (parity tests); 0 = off."""
         check(self.lib.a3r_model_set_tap_level(self.handle, int(level)), "a3r_model_set_tap_level")

@@ -401,6 +401,20 @@ int a3r_model_encode(a3r_model_t m, const float* img, int B, int H, int W, float
 int a3r_model_decode(a3r_model_t m, const float* feat1, const float* feat2, const float* pd1, const float* pd2, int B,
                      int H, int W, float* pts1, float* conf1, float* pts2, float* conf2, void* workspace,
                      size_t workspace_bytes, void* stream);
+/* Duplicate inputs inside one call.  A batch cut from a clip repeats its frames (42 pairs of a 16-frame window graph hold 84 image
+ * slots and 16 distinct images), and the encoder and the depth-prior token branch depend on one frame alone.  a3r_model_forward and
+ * a3r_model_decode therefore find the slots whose images / pred_depth maps are equal bit for bit (the two kinds independently: a
+ * 128-bit content key per slot proposes, a bitwise comparison on the device decides), run those parts once per distinct frame and
+ * copy the rows to every slot.  Outputs are bitwise those of the plain plan, the fh2 sites and their scales are the same, and the
+ * workspace requirement does not change.  Cost: one small read-back and ONE stream synchronise at the start of the call, and about
+ * 64 KB of device and pinned host memory owned by the handle.  A comparison that fails (a key collision) makes the call run the
+ * plain plan.  With a tap level set, or with more than 512 pairs in a call, the plain plan runs.
+ * mode: 0 = off, 1 = on (the default; the environment variable A3R_DEDUP = 0 / 1 / 2 sets the default of new handles), 2 = on with
+ * a constant key, so that the comparison alone decides (debugging).
+ * a3r_model_last_dedup: what the last forward / decode did -- distinct images and pred_depth maps among its 2 B slots each (2 B
+ * where nothing was merged; decode has no images), and whether a failed comparison sent it to the plain plan. */
+int a3r_model_set_dedup(a3r_model_t m, int mode);
+int a3r_model_last_dedup(a3r_model_t m, int* n_img_unique, int* n_pd_unique, int* fell_back);
 /* Debug taps for the parity tests: intermediate tensors inside the workspace after a forward; returns device pointer + element
  * count.  name: "feat" (enc_norm output, model.py:163), "hook_a" / "hook_b" (the decoder levels the DPT head reads,
  * dpt_head.py:101), "dec_last" (dec_norm output, model.py:231-232); after a3r_model_set_tap_level(m, L > 0) also "level" (the two
