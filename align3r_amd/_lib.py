@@ -156,6 +156,7 @@ SIGNATURES = {
     "a3r_depth_init": (C.c_int, [c_void, c_void, C.c_float, C.c_int, C.c_long, c_void, c_void]),
     "a3r_mask_gt": (C.c_int, [c_void, C.c_float, c_void, C.c_long, c_void]),
     "a3r_upsample2x_fh2": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_void, c_void]),
+    "a3r_combine_resid_fh2": (C.c_int, [c_void, c_void, c_void, c_void, c_void, c_void, C.c_int, C.c_long, C.c_int, C.c_float, c_void, c_void]),
     "a3r_conv3x3_fh2": (C.c_int, [c_void, c_void, C.c_float, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Epilogue), c_void]),
     "a3r_head_final": (C.c_int, [c_void, c_void, c_void, c_void, c_void, C.c_long, C.c_int, c_void]),
     "a3r_model_create": (C.c_int, [C.POINTER(ModelConfigC), C.POINTER(c_void)]),
@@ -172,6 +173,8 @@ SIGNATURES = {
     "a3r_model_set_tap_level": (C.c_int, [c_void, C.c_int]),
     "a3r_model_set_dedup": (C.c_int, [c_void, C.c_int]),
     "a3r_model_last_dedup": (C.c_int, [c_void, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "a3r_model_set_dedup_head": (C.c_int, [c_void, C.c_int]),
+    "a3r_model_last_dedup_sides": (C.c_int, [c_void, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "a3r_model_range_check": (C.c_int, [c_void, c_void, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "a3r_model_reset_ranges": (C.c_int, [c_void]),
     "a3r_model_range_stats": (C.c_int, [c_void, c_void, c_void, C.c_int, C.POINTER(C.c_int)]),

@@ -28,18 +28,38 @@ inline int dedup_group(const int32_t* rep, int n, int32_t* uniq, int32_t* map) {
     return U;
 }
 
-// ---- device side (dedup.hip).  An item is one image [3, H, W] or one pred_depth map [H, W, 3]: `words` 32-bit words each, a
-// multiple of 4.  Slot s < 4 B of a call is item s % B of group s / B, the groups being img1, img2, pd1, pd2; slots 0 .. 2 B - 1
+// One side of the batch.  rep is the table above over the 2 B slots of the first kind (img1 then img2); side s holds the slots
+// [s B, (s + 1) B).  Writes the side's distinct contents to uniq[0..U), each as the FIRST SLOT OF THAT SIDE holding it (so
+// s B <= uniq[k] < (s + 1) B even when the representative sits on the other side; ascending), and for every slot b < B of the side
+// its row in that list to map[0..B) (map[uniq[k] - s B] == k), and returns U.  The DPT heads run their frame-only branch on these
+// (model.hip).  Returns -1 when rep is not a representative table.
+inline int dedup_group_side(const int32_t* rep, int B, int s, int32_t* uniq, int32_t* map) {
+    if (!rep || !uniq || !map || B <= 0 || s < 0 || s > 1) return -1;
+    const int base = s * B;
+    int U = 0;
+    for (int b = 0; b < B; b++) {
+        const int32_t r = rep[base + b];
+        if (r < 0 || r > base + b || rep[r] != r) return -1;
+        int k = 0;
+        while (k < U && rep[uniq[k]] != r) k++;
+        if (k == U) uniq[U++] = base + b;
+        map[b] = k;
+    }
+    return U;
+}
+
+// ---- device side (dedup.hip).  An item of the first kind is one image [3, H, W] -- or, for the decode call, one frame's encoder
+// features [N, E] --, one of the second kind a pred_depth map [H, W, 3]: words_a / words_pd 32-bit words each, multiples of 4.  Slot s < 4 B of a call is item s % B of group s / B, the groups being img1, img2, pd1, pd2; slots 0 .. 2 B - 1
 // are the image kind, 2 B .. 4 B - 1 the depth-prior kind, and a representative is looked for inside a slot's own kind only.
 constexpr int DEDUP_MAX_SLOTS = 2048;        // 4 B at most; larger batches run without merging
 // device words: keys [DEDUP_MAX_SLOTS][2] of 64 bits, then rep [DEDUP_MAX_SLOTS] (index inside the kind) and the mismatch flag
 constexpr size_t DEDUP_KEY_BYTES = (size_t)DEDUP_MAX_SLOTS * 16;
 constexpr size_t DEDUP_REP_INTS = DEDUP_MAX_SLOTS + 1;
-// slots [first, 4 B): first = 0 for a whole forward, 2 B for the decode call (no images).  const_key: every key is zero, so the
+// slots [first, 4 B): first = 0 with items of the first kind, 2 B without (a decode call that does not look at its features).  const_key: every key is zero, so the
 // grouping rests on the verification alone (a3r_model_set_dedup mode 2).  Enqueues: clear, key kernel, representative kernel,
 // verify kernel; rep_flag[4 B] ends up nonzero when some slot differs from its representative in any bit.
-int dedup_find(const float* img1, const float* img2, const float* pd1, const float* pd2, int B, long words, int first, bool const_key,
-               void* keys, int32_t* rep_flag, void* stream);
+int dedup_find(const float* img1, const float* img2, const float* pd1, const float* pd2, int B, long words_a, long words_pd, int first,
+               bool const_key, void* keys, int32_t* rep_flag, void* stream);
 
 // ---- the plan's ops on distinct items (elementwise.hip)
 // a3r_patchify of the U items uniq[k] (device, indices inside the kind) of the 2 B items of img_a followed by img_b
@@ -47,5 +67,11 @@ int patchify_indexed(const float* img_a, const float* img_b, const int32_t* uniq
                      long sc, long sy, long sx, void* stream);
 // dst[(s * N + n) * C + c] = src[(map[s] * N + n) * C + c] for the slots s < S (map on the device); C a multiple of 4
 int gather_rows(const float* src, float* dst, const int32_t* map, int S, int N, int C, void* stream);
+// The second conv of refinenet1.resConfUnit1 on distinct frames (a3r.h: a3r_combine_resid_fh2 is the same with a C signature)
+int combine_resid_fh2(const float* c, const float* r0, const float* p2, const int32_t* map, float* s, void* sr2, int S, long P, int C,
+                      float scale, unsigned* absmax, void* stream);
+// the same with p2 = the bilinear 2x (a3r_upsample2x, cropped to Hc x Wc) of x [S, H, W, C] made on the fly; P = Hc Wc
+int upsample2x_combine_fh2(const float* x, const float* c, const float* r0, const int32_t* map, float* s, void* sr2, int S, int H, int W,
+                           int C, int Hc, int Wc, float scale, unsigned* absmax, void* stream);
 
 }  // namespace a3r

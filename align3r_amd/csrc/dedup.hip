@@ -9,7 +9,7 @@ namespace {
 
 constexpr int UNITS_PER_BLOCK = 2048;      // 16-byte units per workgroup: 8 per thread, 32 KB
 
-struct Items { const uint4* base[4]; };    // img1, img2, pd1, pd2
+struct Items { const uint4* base[4]; long units[2]; };    // img1, img2, pd1, pd2; 16-byte units per item of either kind
 
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {      // the splitmix64 finaliser
     z ^= z >> 30; z *= 0xbf58476d1ce4e5b9ull;
@@ -25,9 +25,10 @@ __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
 
 // key[slot] = sum over the slot's 16-byte units i of two mixes of (unit, i), modulo 2^64 each: the sum commutes, so waves add their
 // parts in any order, and the position enters every term, so permuted content gives another key.
-// grid: x over chunks of UNITS_PER_BLOCK units, y over slots first .. 4 B - 1
-__global__ __launch_bounds__(256) void dedup_key_kernel(Items it, int B, long units, int first, unsigned long long* __restrict__ keys) {
+// grid: x over chunks of UNITS_PER_BLOCK units (of the longer kind), y over slots first .. 4 B - 1
+__global__ __launch_bounds__(256) void dedup_key_kernel(Items it, int B, int first, unsigned long long* __restrict__ keys) {
     const int slot = first + blockIdx.y;
+    const long units = it.units[slot >= 2 * B];
     const uint4* __restrict__ p = it.base[slot / B] + (long)(slot % B) * units;
     const long u0 = (long)blockIdx.x * UNITS_PER_BLOCK;
     uint64_t k0 = 0, k1 = 0;
@@ -63,9 +64,10 @@ __global__ void dedup_rep_kernel(const unsigned long long* __restrict__ keys, in
 }
 
 // raises *flag when a slot differs from its representative; same grid as the key kernel
-__global__ __launch_bounds__(256) void dedup_verify_kernel(Items it, int B, long units, int first, const int* __restrict__ rep,
+__global__ __launch_bounds__(256) void dedup_verify_kernel(Items it, int B, int first, const int* __restrict__ rep,
                                                            int* __restrict__ flag) {
     const int slot = first + blockIdx.y;
+    const long units = it.units[slot >= 2 * B];
     const int r = (slot < 2 * B ? 0 : 2 * B) + rep[slot];
     if (r == slot) return;
     const uint4* __restrict__ p = it.base[slot / B] + (long)(slot % B) * units;
@@ -85,27 +87,29 @@ __global__ __launch_bounds__(256) void dedup_verify_kernel(Items it, int B, long
 
 }  // namespace
 
-int dedup_find(const float* img1, const float* img2, const float* pd1, const float* pd2, int B, long words, int first, bool const_key,
-               void* keys, int32_t* rep_flag, void* stream) {
-    A3R_CHECK_ARG(B > 0 && 4 * B <= DEDUP_MAX_SLOTS && words > 0 && words % 4 == 0 && (first == 0 || first == 2 * B),
-                  "dedup_find: bad shape (B=%d, words=%ld, first=%d)", B, words, first);
+int dedup_find(const float* img1, const float* img2, const float* pd1, const float* pd2, int B, long words_a, long words_pd, int first,
+               bool const_key, void* keys, int32_t* rep_flag, void* stream) {
+    A3R_CHECK_ARG(B > 0 && 4 * B <= DEDUP_MAX_SLOTS && words_pd > 0 && words_pd % 4 == 0 && (first == 0 || first == 2 * B) &&
+                      (first > 0 || (words_a > 0 && words_a % 4 == 0)),
+                  "dedup_find: bad shape (B=%d, words=%ld / %ld, first=%d)", B, words_a, words_pd, first);
     A3R_CHECK_ARG(pd1 && pd2 && (first > 0 || (img1 && img2)) && keys && rep_flag, "dedup_find: null pointer");
     const Items it = {{reinterpret_cast<const uint4*>(img1), reinterpret_cast<const uint4*>(img2), reinterpret_cast<const uint4*>(pd1),
-                       reinterpret_cast<const uint4*>(pd2)}};
+                       reinterpret_cast<const uint4*>(pd2)},
+                      {first == 0 ? words_a / 4 : 0, words_pd / 4}};
     for (const uint4* p : it.base)
         A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(p) & 15) == 0, "dedup_find: inputs must be 16-byte aligned");
     hipStream_t st = as_stream(stream);
-    const long units = words / 4;
+    const long units = it.units[0] > it.units[1] ? it.units[0] : it.units[1];
     const int nslots = 4 * B - first;
     A3R_HIP(hipMemsetAsync(keys, 0, (size_t)4 * B * 16, st));
     A3R_HIP(hipMemsetAsync(rep_flag, 0, (size_t)(4 * B + 1) * sizeof(int32_t), st));
-    ProfScope prof(PK_ELEMENTWISE, 3.0 * 4 * words * nslots, st);
+    ProfScope prof(PK_ELEMENTWISE, 3.0 * 16 * (it.units[0] * (2 * B - first) + it.units[1] * 2 * B), st);
     const dim3 grid((unsigned)((units + UNITS_PER_BLOCK - 1) / UNITS_PER_BLOCK), (unsigned)nslots);
     if (!const_key)
-        hipLaunchKernelGGL(dedup_key_kernel, grid, dim3(256), 0, st, it, B, units, first, static_cast<unsigned long long*>(keys));
+        hipLaunchKernelGGL(dedup_key_kernel, grid, dim3(256), 0, st, it, B, first, static_cast<unsigned long long*>(keys));
     hipLaunchKernelGGL(dedup_rep_kernel, dim3((nslots + 255) / 256), dim3(256), 0, st, static_cast<const unsigned long long*>(keys), B,
                        first, rep_flag);
-    hipLaunchKernelGGL(dedup_verify_kernel, grid, dim3(256), 0, st, it, B, units, first, rep_flag, rep_flag + 4 * B);
+    hipLaunchKernelGGL(dedup_verify_kernel, grid, dim3(256), 0, st, it, B, first, rep_flag, rep_flag + 4 * B);
     A3R_LAUNCH_CHECK();
     return A3R_OK;
 }

@@ -289,6 +289,45 @@ __global__ void gather_rows_kernel(const f32x4* __restrict__ src, f32x4* __restr
     }
 }
 
+// ------------------------------------------------------------------------------------------- residual combine on distinct frames
+// What the RESID2 epilogue of refinenet1.resConfUnit1's second conv produces, when that conv (and the skip it adds) ran on the U
+// distinct frames of a side only (dedup.h): for slot b < S with k = map[b], per pixel row and channel
+//     s[b] = c[k] + (r0[k] + p2[b])                (the epilogue's order: (acc + bias) + (resid + resid2), gemm_common.h)
+//     sr2[b] = fh2 of relu(s[b]) * scale, max |stored| -> *absmax
+// c, r0 [U, P, C], p2, s [S, P, C] fp32, sr2 [S P, C] fh2.  A thread makes 8 channels of one pixel row (two 16-byte loads per input,
+// 32 contiguous bytes per output) and walks the rows with the grid's stride: the index divisions happen once per thread, and a
+// workgroup publishes one statistics atomic.
+__global__ __launch_bounds__(256) void combine_resid_fh2_kernel(const float* __restrict__ c, const float* __restrict__ r0,
+                                                                const float* __restrict__ p2, const int* __restrict__ map,
+                                                                float* __restrict__ s, char* __restrict__ sr2, long rows, long P, int C8,
+                                                                float scale, unsigned* __restrict__ absmax) {
+    const long stride = (long)gridDim.x * 256, i0 = (long)blockIdx.x * 256 + threadIdx.x;
+    const long dr = stride / C8;
+    const int dk = (int)(stride - dr * C8);
+    long row = i0 / C8;
+    int kg = (int)(i0 - row * C8);
+    long b = row / P, pr = row - b * P;                        // slot, pixel row inside the slot
+    float amax = 0.f;
+    while (row < rows) {
+        const long src = (((long)map[b] * P + pr) * C8 + kg) * 2, dst = (row * C8 + kg) * 2;      // in float4
+        f32x4 o[2];
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const f32x4 v = reinterpret_cast<const f32x4*>(c)[src + h] +
+                            (reinterpret_cast<const f32x4*>(r0)[src + h] + reinterpret_cast<const f32x4*>(p2)[dst + h]);
+            reinterpret_cast<f32x4*>(s)[dst + h] = v;
+            o[h] = f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)} * scale;
+            amax = fh2_amax4(amax, o[h]);
+        }
+        fh2_store8(sr2 + row * ((size_t)C8 * 32), kg * 8, o[0], o[1]);
+        kg += dk; row += dr; pr += dr;
+        if (kg >= C8) { kg -= C8; row++; pr++; }
+        if (pr >= P) { const long q = pr / P; b += q; pr -= q * P; }
+    }
+    __shared__ unsigned s_red[4];
+    fh2_publish_block(absmax, amax, s_red);                   // every thread arrives here
+}
+
 // ------------------------------------------------------------------------------------------- bilinear x2, align_corners=True
 // Index arithmetic in fp32 exactly as ATen's upsample_bilinear2d (scale = (in-1)/(out-1); src = scale*dst).
 // BF3: write the result in bf3 form (rows = output pixels, K = C) -- the input of the following 1x1 / 3x3 conv on the bf3 kernel.
@@ -355,6 +394,52 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const float* __restrict
         __shared__ unsigned s_red[4];
         fh2_publish_block(absmax, amax, s_red);
     }
+}
+
+// The same combine (combine_resid_fh2_kernel) inside the producer of its per-slot residual: p2 = the bilinear 2x of x, as
+// upsample2x_kernel<0> computes it (bilerp4: the same rounding order), is neither written nor read back.  x [S, H, W, C] fp32;
+// c, r0 [U, Hc, Wc, C]; s [S, Hc, Wc, C]; sr2 its fh2 twin.  Grid and thread layout of upsample2x_kernel<2>.
+__global__ __launch_bounds__(256) void upsample2x_combine_kernel(const float* __restrict__ x, const float* __restrict__ c,
+                                                                 const float* __restrict__ r0, const int* __restrict__ map,
+                                                                 float* __restrict__ s, char* __restrict__ sr2, int B, int H, int W, int C4,
+                                                                 int Hc, int Wc, float scale, unsigned* __restrict__ absmax) {
+    const float sh = (2 * H > 1) ? (float)(H - 1) / (float)(2 * H - 1) : 0.f;
+    const float sw = (2 * W > 1) ? (float)(W - 1) / (float)(2 * W - 1) : 0.f;
+    const f32x4* xv = reinterpret_cast<const f32x4*>(x);
+    const unsigned CG = (unsigned)C4 / 2;                      // channel groups (of 8) per pixel
+    const unsigned idx = blockIdx.x * 256u + threadIdx.x;
+    const unsigned ox = idx / CG, cg = (idx - ox * CG) * 2;    // cg: first float4 of this thread
+    const bool live = ox < (unsigned)Wc;                     // (no early return: the range statistics need every lane at the end)
+    const float fx = sw * (float)ox;
+    int x0 = (int)fx;
+    x0 = x0 < W - 1 ? x0 : W - 1;
+    const int x1 = x0 < W - 1 ? x0 + 1 : x0;
+    const float lx1 = fx - (float)x0, lx0 = 1.f - lx1;
+    float amax = 0.f;
+    for (int row = blockIdx.y; live && row < B * Hc; row += gridDim.y) {   // (slot, output row): uniform per workgroup
+        const int b = row / Hc, oy = row - b * Hc;
+        const float fy = sh * (float)oy;
+        int y0 = (int)fy;
+        y0 = y0 < H - 1 ? y0 : H - 1;
+        const int y1 = y0 < H - 1 ? y0 + 1 : y0;
+        const float ly1 = fy - (float)y0, ly0 = 1.f - ly1;
+        const long rb = (long)b * H;
+        const f32x4* q0 = xv + (rb + y0) * W * C4 + cg;
+        const f32x4* q1 = xv + (rb + y1) * W * C4 + cg;
+        const long pix = (long)row * Wc + ox, src = (((long)map[b] * Hc + oy) * Wc + ox) * C4 + cg;
+        f32x4 o[2];
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            const f32x4 p2 = bilerp4(q0[(long)x0 * C4 + q], q0[(long)x1 * C4 + q], q1[(long)x0 * C4 + q], q1[(long)x1 * C4 + q], lx0, lx1, ly0, ly1);
+            const f32x4 v = reinterpret_cast<const f32x4*>(c)[src + q] + (reinterpret_cast<const f32x4*>(r0)[src + q] + p2);
+            reinterpret_cast<f32x4*>(s)[pix * C4 + cg + q] = v;
+            o[q] = f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)} * scale;
+            amax = fh2_amax4(amax, o[q]);
+        }
+        fh2_store8(sr2 + pix * ((size_t)C4 * 16), cg * 4, o[0], o[1]);
+    }
+    __shared__ unsigned s_red[4];
+    fh2_publish_block(absmax, amax, s_red);
 }
 
 // ------------------------------------------------------------------------------------------- head final
@@ -662,6 +747,29 @@ int a3r::gather_rows(const float* src, float* dst, const int32_t* map, int S, in
     return A3R_OK;
 }
 
+int a3r::combine_resid_fh2(const float* c, const float* r0, const float* p2, const int32_t* map, float* s, void* sr2, int S, long P, int C,
+                           float scale, unsigned* absmax, void* stream) {
+    A3R_CHECK_ARG(c && r0 && p2 && map && s && sr2, "a3r_combine_resid_fh2: null pointer");
+    A3R_CHECK_ARG(S > 0 && P > 0 && C > 0 && C % 8 == 0 && (long)S * P < (1L << 31), "a3r_combine_resid_fh2: bad shape (C must be a multiple of 8)");
+    A3R_CHECK_ARG(scale > 0.f && std::isfinite(scale), "a3r_combine_resid_fh2: scale must be positive and finite");
+    A3R_CHECK_ARG(((reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(r0) | reinterpret_cast<uintptr_t>(p2) |
+                    reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(sr2)) & 15) == 0,
+                  "a3r_combine_resid_fh2: buffers must be 16-byte aligned");
+    const long rows = (long)S * P, total = rows * (C / 8);
+    ProfScope prof(PK_ELEMENTWISE, 5.0 * 32 * total, as_stream(stream));
+    const long blocks = (total + 255) / 256;
+    // persistent grid (8 workgroups per CU), as the split pass
+    hipLaunchKernelGGL(combine_resid_fh2_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, as_stream(stream), c, r0, p2,
+                       map, s, static_cast<char*>(sr2), rows, P, C / 8, scale, absmax);
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+extern "C" int a3r_combine_resid_fh2(const float* c, const float* r0, const float* p2, const int32_t* map, float* s, void* sr2, int S,
+                                     long P, int C, float scale, unsigned* absmax, void* stream) {
+    return a3r::combine_resid_fh2(c, r0, p2, map, s, sr2, S, P, C, scale, absmax, stream);
+}
+
 static inline dim3 upsample_grid(int B, int Hc, int Wc, int groups) {      // groups: threads per output pixel
     const long rows = (long)B * Hc;
     return dim3((unsigned)(((long)Wc * groups + 255) / 256), (unsigned)(rows < 65535 ? rows : 65535));
@@ -704,6 +812,26 @@ extern "C" int a3r_upsample2x_fh2(const float* x, void* y2, int B, int H, int W,
     const unsigned ycap = (grid.y + 7) / 8;
     if (grid.y > ycap) grid.y = ycap;
     hipLaunchKernelGGL(upsample2x_kernel<2>, grid, dim3(256), 0, as_stream(stream), x, static_cast<float*>(y2), B, H, W,
+                       C / 4, Hc, Wc, scale, absmax);
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+int a3r::upsample2x_combine_fh2(const float* x, const float* c, const float* r0, const int32_t* map, float* s, void* sr2, int B, int H, int W,
+                                int C, int Hc, int Wc, float scale, unsigned* absmax, void* stream) {
+    A3R_CHECK_ARG(x && c && r0 && map && s && sr2, "upsample2x_combine_fh2: null pointer");
+    A3R_CHECK_ARG(scale > 0.f && std::isfinite(scale), "upsample2x_combine_fh2: scale must be positive and finite");
+    A3R_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "upsample2x_combine_fh2: bad shape (C must be a multiple of 8)");
+    A3R_CHECK_ARG(Hc > 0 && Hc <= 2 * H && Wc > 0 && Wc <= 2 * W, "upsample2x_combine_fh2: crop window larger than the 2x map");
+    A3R_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(r0) |
+                    reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(sr2)) & 15) == 0,
+                  "upsample2x_combine_fh2: buffers must be 16-byte aligned");
+    const long total = (long)B * Hc * Wc * (C / 4);
+    ProfScope prof(PK_ELEMENTWISE, 40.0 * total + 4.0 * B * H * W * C, as_stream(stream));
+    dim3 grid = upsample_grid(B, Hc, Wc, C / 8);
+    const unsigned ycap = (grid.y + 7) / 8;                   // as a3r_upsample2x_fh2: ~8 rows and one statistics atomic per workgroup
+    if (grid.y > ycap) grid.y = ycap;
+    hipLaunchKernelGGL(upsample2x_combine_kernel, grid, dim3(256), 0, as_stream(stream), x, c, r0, map, s, static_cast<char*>(sr2), B, H, W,
                        C / 4, Hc, Wc, scale, absmax);
     A3R_LAUNCH_CHECK();
     return A3R_OK;

@@ -69,8 +69,13 @@ struct a3r_model_s {
     // distinct image / pred_depth map of the batch, 2 = as 1 with a constant key (debugging: the verification alone decides)
     int dedup_mode = 1;
     int last_img_unique = 0, last_pd_unique = 0, last_fell_back = 0;      // a3r_model_last_dedup
+    // a3r_model_set_dedup_head: the DPT heads' level-0 branch runs once per distinct frame of a side (run_plan, HeadMerge)
+    int dedup_head = 1;
+    int dedup_head_fold = 1;         // A/B switch (A3R_DEDUP_HEAD_FOLD=0): 0 = the combine runs as a pass of its own after the 2x up-sample
+    int last_side_unique[2] = {0, 0}, last_side_merged[2] = {0, 0};      // a3r_model_last_dedup_sides
     // the handle's own small buffers (the only device memory it allocates, at its first merging call): keys, representatives and
-    // flag, the uploaded lists (uniq_img, map_img, uniq_pd, map_pd: DEDUP_MAX_SLOTS / 2 words each), and the pinned host words of
+    // flag, the uploaded lists (uniq_img, map_img, uniq_pd, map_pd, the two sides' uniq, the two sides' map: DEDUP_MAX_SLOTS / 2
+    // words each), and the pinned host words of
     // the one read-back and the one upload of a call
     void* dd_dev = nullptr;
     int32_t* dd_host = nullptr;
@@ -108,6 +113,8 @@ extern "C" int a3r_model_create(const a3r_model_config* cfg, a3r_model_t* out) {
     m->map_form = m->gemm_form == Form::FH2 && conv && !strcmp(conv, "bf3") ? Form::BF3 : m->gemm_form;
     if (const char* dd = getenv("A3R_DEDUP"))      // the default of new handles (a3r_model_set_dedup); anything but 0 / 2 leaves it on
         m->dedup_mode = !strcmp(dd, "0") ? 0 : !strcmp(dd, "2") ? 2 : 1;
+    if (const char* dh = getenv("A3R_DEDUP_HEAD")) m->dedup_head = strcmp(dh, "0") != 0;      // (a3r_model_set_dedup_head)
+    if (const char* df = getenv("A3R_DEDUP_HEAD_FOLD")) m->dedup_head_fold = strcmp(df, "0") != 0;
     // sized here so that the host-side sizing pass (a3r_model_workspace_bytes) works before finalize
     m->enc.assign(cfg->enc_depth, BlockW());
     m->pc.assign(n_pc_blocks(*cfg), BlockW());
@@ -550,6 +557,21 @@ struct Plan {
         const Site s = out_site(mf, ym);
         if (!rc) rc = op_upsample2x(mf, x, ym, B, H, W, C, Hc, Wc, s.scale, s.stat, stream);
     }
+    // s = c[map] + (r[map] + extra) and the fh2 form of relu(s): the RESID2 epilogue + aux output of a conv that ran on distinct frames
+    void combine_map(const float* c, const float* r, const float* extra, const int32_t* map, float* s, float* sr2, int S, long px, int C) {
+        if (skip()) return;
+        traced("combine_resid", S, (int)px, C);
+        const Site st = site(sr2);
+        if (!rc) rc = combine_resid_fh2(c, r, extra, map, s, sr2, S, px, C, st.scale, st.stat, stream);
+    }
+    // the same with extra = the bilinear 2x of x [S, H, W, C] made inside the kernel
+    void up_combine_map(const float* x, const float* c, const float* r, const int32_t* map, float* s, float* sr2, int S, int H, int W,
+                        int C, int Hc, int Wc) {
+        if (skip()) return;
+        traced("upsample2x_combine", H, W, C);
+        const Site st = site(sr2);
+        if (!rc) rc = upsample2x_combine_fh2(x, c, r, map, s, sr2, S, H, W, C, Hc, Wc, st.scale, st.stat, stream);
+    }
     // LayerNorm whose output feeds a GEMM (written directly in the GEMMs' operand form)
     void ln(const float* x, const float* w, const float* b, float* yg, int M, int D) {
         if (skip()) return;
@@ -673,9 +695,22 @@ void rcu_map(Plan& P, const RcuW& w, const float* x, const float* xr3, const flo
     P.conv_map(tmp3, w.c2w, out, B, H, W, F, F, 1, e2);
 }
 
+// The level-0 branch of a head on the distinct frames of its side (fh2 maps): x1 / x1r3 of fusion_map hold U < B images, slot b's
+// being map[b] (device).  fold: x0 of fusion_map is not there -- the previous fusion block left its output before the bilinear 2x
+// (x0_lo [B, lo_h, lo_w, F]) and the combine pass interpolates it on the fly.
+struct HeadMerge { int U; const int32_t* map; bool fold; const float* x0_lo; int lo_h, lo_w; };
+static bool dpt_ref_order() {       // A/B switch: up-sample first, as the reference does
+    static const bool on = getenv("A3R_DPT_REF_ORDER") != nullptr;
+    return on;
+}
+
 // returns fp32 [B, Hc, Wc, F], or its operand form when `last` (refinenet1's output only feeds head.0's 3x3 conv)
+// hm: resConfUnit1 depends on the pair through the residual x0 alone -- its two convs run on hm->U images, the second with the
+// bias-only epilogue, and combine_map adds the skip and x0 per slot in the RESID2 epilogue's order and writes the fh2 twin (that
+// conv's auxiliary site: the sites keep their number and order).  lo_out: leave the block's output before the bilinear 2x there
+// and return null (the fp32 up-sample has no site) -- the next block's combine pass makes the 2x map itself (HeadMerge::fold).
 float* fusion_map(Plan& P, const FusionW& w, const float* x0, const float* x0r3, const float* x1, const float* x1r3, bool two, int B,
-                  int H, int W, int F, int Hc, int Wc, bool last) {
+                  int H, int W, int F, int Hc, int Wc, bool last, const HeadMerge* hm = nullptr, const float** lo_out = nullptr) {
     Arena& ar = P.ar;
     const size_t px = (size_t)B * H * W, n = px * F;
     float* tmp3 = P.map_alloc(px, F);
@@ -683,13 +718,21 @@ float* fusion_map(Plan& P, const FusionW& w, const float* x0, const float* x0r3,
     if (two) {
         float* s = ar.alloc(n);
         float* sr3 = P.map_alloc(px, F);
-        rcu_map(P, w.r1, x1, x1r3, x0, tmp3, s, sr3, B, H, W, F);     // output + resConfUnit1(xs[1])
+        if (hm) {
+            float* c = ar.alloc((size_t)hm->U * H * W * F);
+            OpEpi e1 = P.epi(A3R_EPI_RELU, w.r1.c1b);
+            e1.out_op = 1;
+            P.conv_map(x1r3, w.r1.c1w, tmp3, hm->U, H, W, F, F, 1, e1);
+            P.conv_map(tmp3, w.r1.c2w, c, hm->U, H, W, F, F, 1, P.epi(A3R_EPI_NONE, w.r1.c2b));
+            if (hm->fold) P.up_combine_map(hm->x0_lo, c, x1, hm->map, s, sr3, B, hm->lo_h, hm->lo_w, F, H, W);
+            else P.combine_map(c, x1, x0, hm->map, s, sr3, B, (long)H * W, F);
+        } else
+            rcu_map(P, w.r1, x1, x1r3, x0, tmp3, s, sr3, B, H, W, F);     // output + resConfUnit1(xs[1])
         cur = s; cur3 = sr3;
     } else {
         cur = x0; cur3 = x0r3;
     }
-    static const bool ref_order = getenv("A3R_DPT_REF_ORDER") != nullptr;    // A/B switch: up-sample first, as the reference does
-    if (ref_order) {
+    if (dpt_ref_order()) {
         float* o = ar.alloc(n);
         rcu_map(P, w.r2, cur, cur3, nullptr, tmp3, o, nullptr, B, H, W, F);
         const size_t opx = (size_t)B * Hc * Wc;
@@ -712,6 +755,10 @@ float* fusion_map(Plan& P, const FusionW& w, const float* x0, const float* x0r3,
     P.linear(o3, F, w.ow, lo, F, (int)px, F, F, P.epi(A3R_EPI_NONE, w.ob), /*plain_x=*/true);
     const size_t opx = (size_t)B * Hc * Wc;
     float* r;
+    if (lo_out) {
+        *lo_out = lo;
+        return nullptr;
+    }
     if (last) {
         r = P.map_alloc(opx, F);
         P.up_map(lo, r, B, H, W, F, Hc, Wc);
@@ -724,13 +771,35 @@ float* fusion_map(Plan& P, const FusionW& w, const float* x0, const float* x0r3,
 
 // The distinct inputs of a call (dedup.h): n_img / n_pd of the 2 B images / pred_depth maps are distinct (2 B: that kind is not
 // merged).  Device lists: uniq_* [n] the distinct slots, map_* [2 B] each slot's row in that list (null in the sizing pass).
-struct Distinct { int n_img, n_pd; const int32_t *uniq_img, *map_img, *uniq_pd, *map_pd; };
+// Per side s (slots [s B, (s + 1) B) of the first kind): n_side[s] distinct frames when the head of that side merges its level-0
+// branch (head_merge_fits), B when it does not; uniq_side[s] [n_side[s]] the first slot of the side holding each, map_side[s] [B].
+struct Distinct {
+    int n_img, n_pd; const int32_t *uniq_img, *map_img, *uniq_pd, *map_pd;
+    int n_side[2]; const int32_t *uniq_side[2], *map_side[2];
+};
+
+// Bytes of a head's level-0 buffers with n images in them, as the arena rounds them: a0, l0, l03, r0, r0r3; the merged branch adds
+// the compact enc_norm rows and the bias-only output c of resConfUnit1's second conv.  fh2 maps take 4 bytes per element.
+size_t head_level0_bytes(const a3r_model_config& c, int N, int n, bool merged) {
+    const size_t px = (size_t)n * N, F = c.feature_dim, l = c.layer_dims[0];
+    const size_t fl[7] = {px * l, px * 16 * l, px * 16 * l, px * 16 * F, px * 16 * F, px * c.enc_embed_dim, px * 16 * F};
+    size_t b = 0;
+    for (int i = 0; i < (merged ? 7 : 5); i++) b += align_up(fl[i] * 4, 256);
+    return b;
+}
+// A side with U distinct frames merges when its level-0 buffers fit in what the plain plan reserves for them, so that the
+// workspace requirement does not move: U (33 l + 48 F + E) <= B (33 l + 32 F) up to rounding, U <= 0.69 B for ViT-L heads
+// (l = 96, F = 256, E = 1024).
+bool head_merge_fits(const a3r_model_config& c, int N, int B, int U) {
+    return U > 0 && U < B && head_level0_bytes(c, N, U, true) <= head_level0_bytes(c, N, B, false);
+}
 
 // phase: 0 = whole forward from images; 1 = encoder only (img1 [B,...] -> feat_out [B,N,E]);
 //        2 = decoder + heads from cached encoder features (feat1_in / feat2_in [B,N,E]).
 // dd: run the parts of the plan that depend on one frame alone -- the encoder, and the depth-prior token branch -- on the distinct
 // frames only and copy their rows to every slot.  The ops, their order and so the fh2 site numbers are those of the plain plan;
-// only row counts differ, and every row is computed as it is there.
+// only row counts differ, and every row is computed as it is there.  dd->n_side: the same for the level-0 branch of each DPT head
+// (fh2 maps only), whose rows are put back by the combine pass (fusion_map).
 int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, const float* pd1, const float* pd2, int B,
              int H, int W, float* pts1, float* conf1, float* pts2, float* conf2, void* ws, size_t ws_bytes, void* stream,
              size_t* peak, int phase = 0, const float* feat1_in = nullptr, const float* feat2_in = nullptr,
@@ -978,30 +1047,40 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
         ar.off = mark;
         const HeadW& Hd = m->head[s];
         const int* ld = c.layer_dims;
-        const float* t0 = feat + (size_t)s * BN * E;
+        const float* t0 = feat + (size_t)s * BN * E;      // (t0: the level-0 rows of this side)
         const float* t1 = lvl_a + (dry ? 0 : (size_t)s * BN * D);
         const float* t2 = lvl_b + (dry ? 0 : (size_t)s * BN * D);
         const float* t3 = dec_last + (size_t)s * BN * D;
         const int h3 = (nh + 2 - 3) / 2 + 1, w3 = (nw + 2 - 3) / 2 + 1;
         // act_postprocess (dpt_block.py:353-405)
         // 1x1 adapters: in fh2 mode a split pass + the fh2 GEMM (5x the exact-fp32 MFMA kernel's rate) instead of a3r_linear
-        auto adapter = [&](const float* t, int K, const float* w, const float* b, float* y, int N) {
-            if (P.gf != Form::FH2) { P.linear_f32(t, K, w, y, N, BN, N, K, P.epi(A3R_EPI_NONE, b)); return; }
+        auto adapter = [&](const float* t, int K, const float* w, const float* b, float* y, int N, int rows) {
+            if (P.gf != Form::FH2) { P.linear_f32(t, K, w, y, N, rows, N, K, P.epi(A3R_EPI_NONE, b)); return; }
             const size_t keep = ar.off;
-            float* t2 = P.gin_scratch(BN, K);
-            P.linear(P.gin_from(t, t2, BN, K), K, w, y, N, BN, N, K, P.epi(A3R_EPI_NONE, b));
+            float* t2 = P.gin_scratch(rows, K);
+            P.linear(P.gin_from(t, t2, rows, K), K, w, y, N, rows, N, K, P.epi(A3R_EPI_NONE, b));
             ar.off = keep;                                          // the split is dead once the GEMM is enqueued (stream order)
         };
-        float* a0 = ar.alloc((size_t)BN * ld[0]);
-        adapter(t0, E, Hd.a0w, Hd.a0b, a0, ld[0]);
-        float* l0 = ar.alloc((size_t)BN * 16 * ld[0]);
+        // level 0 (enc_norm rows) depends on the frame alone: B0 images, the side's distinct ones when its head merges
+        const int B0 = dd && P.mf == Form::FH2 ? dd->n_side[s] : B;
+        // (the combine pass folded into refinenet2's 2x up-sample, whose fp32 output only it would read)
+        HeadMerge hmerge = {B0, dd ? dd->map_side[s] : nullptr, B0 < B && m->dedup_head_fold && !dpt_ref_order(), nullptr, 2 * nh, 2 * nw};
+        const size_t BN0 = (size_t)B0 * N;
+        if (B0 < B) {
+            float* fu = ar.alloc(BN0 * E);
+            if (!P.skip()) P.rc = gather_rows(feat, fu, dd->uniq_side[s], B0, N, E, stream);
+            t0 = fu;
+        }
+        float* a0 = ar.alloc(BN0 * ld[0]);
+        adapter(t0, E, Hd.a0w, Hd.a0b, a0, ld[0], (int)BN0);
+        float* l0 = ar.alloc(BN0 * 16 * ld[0]);
         {
             OpEpi e = P.epi(A3R_EPI_PIXSHUF, Hd.a0tb);
             e.ps_s = 4; e.ps_h = nh; e.ps_w = nw; e.ps_cout = ld[0];
-            P.linear_f32(a0, ld[0], Hd.a0tw, l0, ld[0], BN, 16 * ld[0], ld[0], e);
+            P.linear_f32(a0, ld[0], Hd.a0tw, l0, ld[0], (int)BN0, 16 * ld[0], ld[0], e);
         }
         float* a1 = ar.alloc((size_t)BN * ld[1]);
-        adapter(t1, D, Hd.a1w, Hd.a1b, a1, ld[1]);
+        adapter(t1, D, Hd.a1w, Hd.a1b, a1, ld[1], BN);
         float* l1 = ar.alloc((size_t)BN * 4 * ld[1]);
         {
             OpEpi e = P.epi(A3R_EPI_PIXSHUF, Hd.a1tb);
@@ -1009,9 +1088,9 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
             P.linear_f32(a1, ld[1], Hd.a1tw, l1, ld[1], BN, 4 * ld[1], ld[1], e);
         }
         float* l2 = ar.alloc((size_t)BN * ld[2]);
-        adapter(t2, D, Hd.a2w, Hd.a2b, l2, ld[2]);
+        adapter(t2, D, Hd.a2w, Hd.a2b, l2, ld[2], BN);
         float* a3 = ar.alloc((size_t)BN * ld[3]);
-        adapter(t3, D, Hd.a3w, Hd.a3b, a3, ld[3]);
+        adapter(t3, D, Hd.a3w, Hd.a3b, a3, ld[3], BN);
         float* l3 = P.map_alloc((size_t)B * h3 * w3, ld[3]);          // only feeds layer4_rn's conv: in map form
         if (P.mf == Form::F32) {
             P.conv(a3, Hd.a3cw, l3, B, nh, nw, ld[3], ld[3], 2, P.epi(A3R_EPI_NONE, Hd.a3cb));
@@ -1050,15 +1129,15 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
 
         } else {
             // conv inputs in map form (small maps: plain split passes)
-            float* l03 = P.map_alloc((size_t)BN * 16, ld[0]);
-            P.split_map(l0, l03, (long)BN * 16, ld[0]);
+            float* l03 = P.map_alloc(BN0 * 16, ld[0]);
+            P.split_map(l0, l03, (long)BN0 * 16, ld[0]);
             float* l13 = P.map_alloc((size_t)BN * 4, ld[1]);
             P.split_map(l1, l13, (long)BN * 4, ld[1]);
             float* l23 = P.map_alloc(BN, ld[2]);
             P.split_map(l2, l23, BN, ld[2]);
             // scratch.layer_rn (no bias): fp32 for the skip connection + pre-activated map form for the first RCU conv
-            float* r0 = ar.alloc((size_t)BN * 16 * F);
-            float* r0r3 = P.map_alloc((size_t)BN * 16, F);
+            float* r0 = ar.alloc(BN0 * 16 * F);
+            float* r0r3 = P.map_alloc(BN0 * 16, F);
             float* r1 = ar.alloc((size_t)BN * 4 * F);
             float* r1r3 = P.map_alloc((size_t)BN * 4, F);
             float* r2 = ar.alloc((size_t)BN * F);
@@ -1066,15 +1145,16 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
             float* r3 = ar.alloc((size_t)B * h3 * w3 * F);
             float* r3r3 = P.map_alloc((size_t)B * h3 * w3, F);
             auto rn_epi = [&](float* aux) { OpEpi e = P.epi(A3R_EPI_NONE, nullptr); e.aux_op = aux; e.aux_relu = 1; return e; };
-            P.conv_map(l03, Hd.rn[0], r0, B, 4 * nh, 4 * nw, ld[0], F, 1, rn_epi(r0r3));
+            P.conv_map(l03, Hd.rn[0], r0, B0, 4 * nh, 4 * nw, ld[0], F, 1, rn_epi(r0r3));
             P.conv_map(l13, Hd.rn[1], r1, B, 2 * nh, 2 * nw, ld[1], F, 1, rn_epi(r1r3));
             P.conv_map(l23, Hd.rn[2], r2, B, nh, nw, ld[2], F, 1, rn_epi(r2r3));
             P.conv_map(l3, Hd.rn[3], r3, B, h3, w3, ld[3], F, 1, rn_epi(r3r3));      // l3 is in map form already
             // refinement (dpt_head.py:57-60)
             float* p4 = fusion_map(P, Hd.ref[3], r3, r3r3, nullptr, nullptr, false, B, h3, w3, F, nh, nw, false);
             float* p3 = fusion_map(P, Hd.ref[2], p4, nullptr, r2, r2r3, true, B, nh, nw, F, 2 * nh, 2 * nw, false);
-            float* p2 = fusion_map(P, Hd.ref[1], p3, nullptr, r1, r1r3, true, B, 2 * nh, 2 * nw, F, 4 * nh, 4 * nw, false);
-            float* p13 = fusion_map(P, Hd.ref[0], p2, nullptr, r0, r0r3, true, B, 4 * nh, 4 * nw, F, 8 * nh, 8 * nw, true);
+            float* p2 = fusion_map(P, Hd.ref[1], p3, nullptr, r1, r1r3, true, B, 2 * nh, 2 * nw, F, 4 * nh, 4 * nw, false, nullptr,
+                                   hmerge.fold ? &hmerge.x0_lo : nullptr);
+            float* p13 = fusion_map(P, Hd.ref[0], p2, nullptr, r0, r0r3, true, B, 4 * nh, 4 * nw, F, 8 * nh, 8 * nw, true, B0 < B ? &hmerge : nullptr);
             // head (dpt_block.py:323-330)
             float* h0 = ar.alloc((size_t)B * Hh * Wh * (F / 2));
             P.conv_map(p13, Hd.h0w, h0, B, Hh, Wh, F, F / 2, 1, P.epi(A3R_EPI_NONE, Hd.h0b));
@@ -1101,28 +1181,34 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
 }  // namespace
 
 // ---- the distinct inputs of one call: key, representative and verify kernels, ONE read-back (with one stream synchronise, at the
-// start of the call), the host grouping and one upload of its lists.  *use = false: run the plain plan (switched off, parity taps
+// start of the call), the host grouping and one upload of its lists.  a1 / a2: the items of the first kind, words_a words each --
+// the images of a forward (encode: they are merged for the encoder too), the cached features of a decode call, which only the heads'
+// level-0 branch merges (null: a decode call that does not look at them).  *use = false: run the plain plan (switched off, parity taps
 // on, a batch beyond DEDUP_MAX_SLOTS, nothing to merge, or a slot that differs from its representative: a key collision).
 namespace {
 constexpr int DD_HALF = DEDUP_MAX_SLOTS / 2;                       // slots of one kind at most
-constexpr size_t DD_HOST_LIST = (DEDUP_REP_INTS + 63) / 64 * 64;   // pinned host words: rep + flag | the four lists
-constexpr size_t DD_REP_OFF = DEDUP_KEY_BYTES;                     // device bytes: keys | rep + flag | uniq_img, map_img, uniq_pd, map_pd
+constexpr size_t DD_HOST_LIST = (DEDUP_REP_INTS + 63) / 64 * 64;   // pinned host words: rep + flag | the DD_LISTS lists
+constexpr size_t DD_REP_OFF = DEDUP_KEY_BYTES;                     // device bytes: keys | rep + flag | the DD_LISTS lists
 constexpr size_t DD_LIST_OFF = DD_REP_OFF + DD_HOST_LIST * 4;
-constexpr size_t DD_DEV_BYTES = DD_LIST_OFF + (size_t)4 * DD_HALF * 4;
+constexpr int DD_LISTS = 6;                                        // uniq_img, map_img, uniq_pd, map_pd, uniq_side [2][B], map_side [2][B]
+constexpr size_t DD_DEV_BYTES = DD_LIST_OFF + (size_t)DD_LISTS * DD_HALF * 4;
 
-int find_distinct(a3r_model_s* m, const float* img1, const float* img2, const float* pd1, const float* pd2, int B, int H, int W,
-                  bool images, void* stream, Distinct* d, bool* use) {
+int find_distinct(a3r_model_s* m, const float* a1, const float* a2, long words_a, bool encode, const float* pd1, const float* pd2, int B,
+                  int H, int W, void* stream, Distinct* d, bool* use) {
     *use = false;
     m->last_img_unique = m->last_pd_unique = 2 * B;
     m->last_fell_back = 0;
+    m->last_side_unique[0] = m->last_side_unique[1] = B;
+    m->last_side_merged[0] = m->last_side_merged[1] = 0;
     if (m->dedup_mode == 0 || m->tap_level > 0 || 4 * B > DEDUP_MAX_SLOTS) return A3R_OK;
     if (!m->dd_dev) A3R_HIP(hipMalloc(&m->dd_dev, DD_DEV_BYTES));
-    if (!m->dd_host) A3R_HIP(hipHostMalloc(reinterpret_cast<void**>(&m->dd_host), (DD_HOST_LIST + 4 * DD_HALF) * sizeof(int32_t), hipHostMallocDefault));
+    if (!m->dd_host) A3R_HIP(hipHostMalloc(reinterpret_cast<void**>(&m->dd_host), (DD_HOST_LIST + DD_LISTS * DD_HALF) * sizeof(int32_t), hipHostMallocDefault));
     char* dev = static_cast<char*>(m->dd_dev);
     int32_t* rep_dev = reinterpret_cast<int32_t*>(dev + DD_REP_OFF);
     int32_t* list_dev = reinterpret_cast<int32_t*>(dev + DD_LIST_OFF);
-    const int S = 2 * B, first = images ? 0 : S;
-    if (int rc = dedup_find(img1, img2, pd1, pd2, B, 3L * H * W, first, m->dedup_mode == 2, dev, rep_dev, stream)) return rc;
+    const bool first_kind = a1 && a2;
+    const int S = 2 * B, first = first_kind ? 0 : S;
+    if (int rc = dedup_find(a1, a2, pd1, pd2, B, words_a, 3L * H * W, first, m->dedup_mode == 2, dev, rep_dev, stream)) return rc;
     hipStream_t st = as_stream(stream);
     A3R_HIP(hipMemcpyAsync(m->dd_host, rep_dev, (size_t)(2 * S + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     A3R_HIP(hipStreamSynchronize(st));
@@ -1132,23 +1218,36 @@ int find_distinct(a3r_model_s* m, const float* img1, const float* img2, const fl
         return A3R_OK;
     }
     int32_t* list = m->dd_host + DD_HOST_LIST;
+    const a3r_model_config& c = m->cfg;
     int n_img = S;
-    if (images) {
+    if (encode && first_kind) {
         n_img = dedup_group(rep, S, list, list + DD_HALF);
         // the distinct frames' enc_norm rows must fit the buffers they wait in (run_plan)
-        const a3r_model_config& c = m->cfg;
         if (n_img > 0 && (size_t)n_img * c.enc_embed_dim > 3 * (size_t)S * c.dec_embed_dim) n_img = S;
     }
+    // the heads' level-0 branch: each side's own distinct frames (the lists of both sides share one DD_HALF-word block: 2 B words)
+    int n_side[2] = {B, B};
+    if (first_kind && m->dedup_head && m->map_form == Form::FH2)
+        for (int s = 0; s < 2; s++) {
+            const int u = dedup_group_side(rep, B, s, list + 4 * DD_HALF + s * B, list + 5 * DD_HALF + s * B);
+            if (u <= 0) { n_img = 0; break; }
+            m->last_side_unique[s] = u;
+            if (head_merge_fits(c, (H / 16) * (W / 16), B, u)) n_side[s] = u;
+        }
     const int n_pd = dedup_group(rep + S, S, list + 2 * DD_HALF, list + 3 * DD_HALF);
     if (n_img <= 0 || n_pd <= 0) {       // not a representative table: cannot happen, and is not trusted if it does
         m->last_fell_back = 1;
+        m->last_side_unique[0] = m->last_side_unique[1] = B;
         return A3R_OK;
     }
     m->last_img_unique = n_img;
     m->last_pd_unique = n_pd;
-    if (n_img == S && n_pd == S) return A3R_OK;
-    A3R_HIP(hipMemcpyAsync(list_dev, list, (size_t)4 * DD_HALF * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    *d = {n_img, n_pd, list_dev, list_dev + DD_HALF, list_dev + 2 * DD_HALF, list_dev + 3 * DD_HALF};
+    if (n_img == S && n_pd == S && n_side[0] == B && n_side[1] == B) return A3R_OK;
+    m->last_side_merged[0] = n_side[0] < B;
+    m->last_side_merged[1] = n_side[1] < B;
+    A3R_HIP(hipMemcpyAsync(list_dev, list, (size_t)DD_LISTS * DD_HALF * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    *d = {n_img, n_pd, list_dev, list_dev + DD_HALF, list_dev + 2 * DD_HALF, list_dev + 3 * DD_HALF,
+          {n_side[0], n_side[1]}, {list_dev + 4 * DD_HALF, list_dev + 4 * DD_HALF + B}, {list_dev + 5 * DD_HALF, list_dev + 5 * DD_HALF + B}};
     *use = true;
     return A3R_OK;
 }
@@ -1157,10 +1256,16 @@ int find_distinct(a3r_model_s* m, const float* img1, const float* img2, const fl
 extern "C" size_t a3r_model_workspace_bytes(a3r_model_t m, int B, int H, int W) {
     if (!m || B <= 0 || H <= 0 || W <= 0 || H % 16 || W % 16) return 0;
     // the largest of the plain plan and the plans on distinct inputs: those only shrink stages and reuse idle buffers, largest with
-    // one duplicate (2 B - 1 distinct), of the depth priors alone or of both kinds
+    // one duplicate (2 B - 1 distinct), of the depth priors alone or of both kinds; and the heads' merged level-0 branch at the
+    // largest number of distinct frames a side is admitted with (head_merge_fits: its buffers grow with that number)
     size_t need = 0;
-    const Distinct cases[3] = {{2 * B, 2 * B, nullptr, nullptr, nullptr, nullptr}, {2 * B, 2 * B - 1, nullptr, nullptr, nullptr, nullptr},
-                               {2 * B - 1, 2 * B - 1, nullptr, nullptr, nullptr, nullptr}};
+    int u_max = B - 1;
+    while (u_max > 0 && !head_merge_fits(m->cfg, (H / 16) * (W / 16), B, u_max)) u_max--;
+    const int u_side = u_max > 0 && m->map_form == Form::FH2 ? u_max : B;
+    const Distinct cases[4] = {{2 * B, 2 * B, nullptr, nullptr, nullptr, nullptr, {B, B}, {nullptr, nullptr}, {nullptr, nullptr}},
+                               {2 * B, 2 * B - 1, nullptr, nullptr, nullptr, nullptr, {B, B}, {nullptr, nullptr}, {nullptr, nullptr}},
+                               {2 * B - 1, 2 * B - 1, nullptr, nullptr, nullptr, nullptr, {B, B}, {nullptr, nullptr}, {nullptr, nullptr}},
+                               {2 * B, 2 * B, nullptr, nullptr, nullptr, nullptr, {u_side, u_side}, {nullptr, nullptr}, {nullptr, nullptr}}};
     for (const Distinct& d : cases) {
         size_t peak = 0;
         run_plan(m, true, nullptr, nullptr, nullptr, nullptr, B, H, W, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &peak, 0,
@@ -1188,7 +1293,7 @@ extern "C" int a3r_model_forward(a3r_model_t m, const float* img1, const float* 
     A3R_CHECK_ARG(workspace_bytes >= need_bytes, "a3r_model_forward: workspace too small (%zu < %zu)", workspace_bytes, need_bytes);
     Distinct d;
     bool merge = false;
-    if (int rc = find_distinct(m, img1, img2, pd1, pd2, B, H, W, true, stream, &d, &merge)) return rc;
+    if (int rc = find_distinct(m, img1, img2, 3L * H * W, true, pd1, pd2, B, H, W, stream, &d, &merge)) return rc;
     return run_plan(m, false, img1, img2, pd1, pd2, B, H, W, pts1, conf1, pts2, conf2, workspace, workspace_bytes, stream, nullptr, 0,
                     nullptr, nullptr, nullptr, merge ? &d : nullptr);
 }
@@ -1234,7 +1339,11 @@ extern "C" int a3r_model_decode(a3r_model_t m, const float* feat1, const float* 
     A3R_CHECK_ARG(workspace_bytes >= need_bytes, "a3r_model_decode: workspace too small (%zu < %zu)", workspace_bytes, need_bytes);
     Distinct d;
     bool merge = false;
-    if (int rc = find_distinct(m, nullptr, nullptr, pd1, pd2, B, H, W, false, stream, &d, &merge)) return rc;
+    // (the features are only looked at for the heads' level-0 branch: fh2 maps, a3r_model_set_dedup_head)
+    const bool look = m->dedup_head && m->map_form == Form::FH2;
+    const long words_f = (long)(H / 16) * (W / 16) * m->cfg.enc_embed_dim;
+    if (int rc = find_distinct(m, look ? feat1 : nullptr, look ? feat2 : nullptr, words_f, false, pd1, pd2, B, H, W, stream, &d, &merge))
+        return rc;
     return run_plan(m, false, nullptr, nullptr, pd1, pd2, B, H, W, pts1, conf1, pts2, conf2, workspace, workspace_bytes, stream,
                     nullptr, 2, feat1, feat2, nullptr, merge ? &d : nullptr);
 }
@@ -1242,6 +1351,21 @@ extern "C" int a3r_model_decode(a3r_model_t m, const float* feat1, const float* 
 extern "C" int a3r_model_set_dedup(a3r_model_t m, int mode) {
     A3R_CHECK_ARG(m && mode >= 0 && mode <= 2, "a3r_model_set_dedup: mode must be 0 (off), 1 (on) or 2 (constant key)");
     m->dedup_mode = mode;
+    return A3R_OK;
+}
+
+extern "C" int a3r_model_set_dedup_head(a3r_model_t m, int on) {
+    A3R_CHECK_ARG(m, "a3r_model_set_dedup_head: null handle");
+    m->dedup_head = on != 0;
+    return A3R_OK;
+}
+
+extern "C" int a3r_model_last_dedup_sides(a3r_model_t m, int* u1, int* u2, int* merged1, int* merged2) {
+    A3R_CHECK_ARG(m && u1 && u2 && merged1 && merged2, "a3r_model_last_dedup_sides: null argument");
+    *u1 = m->last_side_unique[0];
+    *u2 = m->last_side_unique[1];
+    *merged1 = m->last_side_merged[0];
+    *merged2 = m->last_side_merged[1];
     return A3R_OK;
 }
 

@@ -166,6 +166,18 @@ class PairEngine:
         check(self.lib.a3r_model_last_dedup(self.handle, C.byref(ni), C.byref(nd), C.byref(fb)), "a3r_model_last_dedup")
         return ni.value, nd.value, bool(fb.value)
 
+    def set_dedup_head(self, on):
+        """The DPT heads' level-0 branch once per distinct frame of a side (include/a3r.h, a3r_model_set_dedup_head); default on.
+        Outputs are bitwise the same either way."""
+        check(self.lib.a3r_model_set_dedup_head(self.handle, int(bool(on))), "a3r_model_set_dedup_head")
+
+    def last_dedup_sides(self):
+        """(diagnostic) (distinct frames of side 1, of side 2, side 1 merged, side 2 merged) of the last forward / decode call."""
+        u1, u2, m1, m2 = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.a3r_model_last_dedup_sides(self.handle, C.byref(u1), C.byref(u2), C.byref(m1), C.byref(m2)),
+              "a3r_model_last_dedup_sides")
+        return u1.value, u2.value, bool(m1.value), bool(m2.value)
+
     def set_tap_level(self, level):
         """Keep copies of decoder level `level` and of the point-cloud tokens for tap("level") / tap("pc0") (parity tests); 0 = off."""
         check(self.lib.a3r_model_set_tap_level(self.handle, int(level)), "a3r_model_set_tap_level")

@@ -354,6 +354,12 @@ int a3r_upsample2x_bf3(const float* x, void* y3, int B, int H, int W, int C, int
  * kernel; scale a power of two, absmax (device, may be NULL) receives max |scale * y| as in a3r_split_fh2 */
 int a3r_upsample2x_fh2(const float* x, void* y2, int B, int H, int W, int C, int Hc, int Wc, float scale, unsigned* absmax,
                        void* stream);
+/* The residual epilogue of a conv that ran on distinct frames only: c, r0 [U, P, C] fp32 (bias-only conv output and its skip
+ * input), p2, s [S, P, C] fp32, map [S] (device) the row of each slot in 0..U-1.  s[b] = c[map[b]] + (r0[map[b]] + p2[b]) -- the
+ * RESID2 epilogue's order of additions -- and sr2 [S P, C] = relu(s) * scale in fh2 form, absmax as a3r_split_fh2.  C % 8 == 0,
+ * S P < 2^31, 16-byte aligned buffers. */
+int a3r_combine_resid_fh2(const float* c, const float* r0, const float* p2, const int32_t* map, float* s, void* sr2, int S, long P,
+                          int C, float scale, unsigned* absmax, void* stream);
 
 /* last 1x1 conv (128 -> 4) + postprocess (dpt_block.py:329, postprocess.py:10-58):
  * x [P, C] -> pts3d [P, 3] = xyz/max(|xyz|,1e-8)*expm1(|xyz|), conf [P] = 1 + exp(c). */
@@ -415,6 +421,19 @@ int a3r_model_decode(a3r_model_t m, const float* feat1, const float* feat2, cons
  * where nothing was merged; decode has no images), and whether a failed comparison sent it to the plain plan. */
 int a3r_model_set_dedup(a3r_model_t m, int mode);
 int a3r_model_last_dedup(a3r_model_t m, int* n_img_unique, int* n_pd_unique, int* fell_back);
+/* The DPT heads' level-0 branch.  Each head reads the enc_norm rows of its side; the adapter, the 4x transposed conv, layer_rn[0] and
+ * the two 3x3 convs of refinenet1.resConfUnit1 depend on that frame alone (the pair enters as a residual).  With the fh2 maps (the
+ * default arithmetic) a forward or decode call runs them once per DISTINCT frame of the side -- decode finds equal feature rows as
+ * forward finds equal images, in the same read-back -- and a combine pass (a3r_combine_resid_fh2, by default folded into the 2x
+ * up-sample that produces the residual) adds the pair's residual per slot in the conv epilogue's own order of additions: outputs,
+ * fh2 sites, scales and statistics are bitwise the plain plan's, and the workspace requirement does not change.  A side merges when it has fewer distinct frames than slots and its level-0 buffers still
+ * fit what the plain plan reserves for them (about 0.69 B distinct frames at most for ViT-L); the two sides decide separately.
+ * Dedup mode 0, a failed comparison, a tap level and the bf3 / f32 maps run the plain head.
+ * on: 1 (the default; environment variable A3R_DEDUP_HEAD = 0 / 1 for new handles) or 0.
+ * a3r_model_last_dedup_sides: distinct frames of side 1 / side 2 of the last forward / decode call (B where they were not looked
+ * for), and whether that side's head ran merged. */
+int a3r_model_set_dedup_head(a3r_model_t m, int on);
+int a3r_model_last_dedup_sides(a3r_model_t m, int* u1, int* u2, int* merged1, int* merged2);
 /* Debug taps for the parity tests: intermediate tensors inside the workspace after a forward; returns device pointer + element
  * count.  name: "feat" (enc_norm output, model.py:163), "hook_a" / "hook_b" (the decoder levels the DPT head reads,
  * dpt_head.py:101), "dec_last" (dec_norm output, model.py:231-232); after a3r_model_set_tap_level(m, L > 0) also "level" (the two
