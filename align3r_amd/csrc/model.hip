@@ -1,6 +1,6 @@
 // AsymmetricCroCo3DStereo.forward as a fixed launch plan over liba3r's kernels (host code only).
 //
-// Mirrors, step for step (all under /root/reference/):
+// Mirrors, step for step (paths inside the reference project):
 //   forward / _encode_image_pairs / _encode_image   dust3r/model.py:241-257,151-174
 //   _decoder (+ dec_blocks_pc / zero_convs branch)  dust3r/model.py:201-233
 //   Block / DecoderBlock                             croco/models/blocks.py:114-191
@@ -12,6 +12,7 @@
 // key / map words for the duplicate search (find_distinct).
 #include "plan.h"
 #include "dedup.h"
+#include <algorithm>
 #include <new>
 #include <cstdlib>
 #include <cstring>
@@ -140,45 +141,46 @@ extern "C" int a3r_model_set_weight(a3r_model_t m, const char* name, const float
 
 // ------------------------------------------------------------------------------------------- packing plan
 namespace {
-// kind 0: conv3x3 [Cout=a,Cin=b]; 1: convT [Cin=a,Cout=b,s]; 2: kv-concat (D=a); 3: rope tables; 4: twin of the [a, b] weight `name` in
-// Form s (an fh2 twin has 256 bytes behind it: scratch of the max|w| reduction that fixes its scale); 6: range statistics words
-struct PackItem { std::string name; int kind; int a, b, s; size_t off; };
+// CONV3X3 [Cout=a,Cin=b]; CONVT [Cin=a,Cout=b,s]; KV_CONCAT (D=a); ROPE tables; TWIN of the [a, b] weight `name` in Form s (an fh2
+// twin has 256 bytes behind it: scratch of the max|w| reduction that fixes its scale); STATS: the range statistics words
+enum class Pack { CONV3X3, CONVT, KV_CONCAT, ROPE, TWIN, STATS };
+struct PackItem { std::string name; Pack kind; int a, b, s; size_t off; };
 
 std::vector<PackItem> pack_plan(a3r_model_s* m, size_t* total) {
     const a3r_model_config& c = m->cfg;
     std::vector<PackItem> v;
     size_t off = 0;
-    auto add = [&](const std::string& n, int kind, int a, int b, int s, size_t nfloat) {
+    auto add = [&](const std::string& n, Pack kind, int a, int b, int s, size_t nfloat) {
         v.push_back({n, kind, a, b, s, off});
         off = align_up(off + nfloat * 4, 256);
     };
     const int F = c.feature_dim;
     for (int h = 1; h <= 2; h++) {
         const std::string p = "downstream_head" + std::to_string(h) + ".dpt.";
-        for (int i = 0; i < 4; i++) add(p + "scratch.layer" + std::to_string(i + 1) + "_rn.weight", 0, F, c.layer_dims[i], 0, (size_t)F * c.layer_dims[i] * 9);
+        for (int i = 0; i < 4; i++) add(p + "scratch.layer" + std::to_string(i + 1) + "_rn.weight", Pack::CONV3X3, F, c.layer_dims[i], 0, (size_t)F * c.layer_dims[i] * 9);
         for (int r = 1; r <= 4; r++)
             for (int u = 1; u <= 2; u++)
                 for (int k = 1; k <= 2; k++)
-                    add(p + "scratch.refinenet" + std::to_string(r) + ".resConfUnit" + std::to_string(u) + ".conv" + std::to_string(k) + ".weight", 0, F, F, 0, (size_t)F * F * 9);
-        add(p + "head.0.weight", 0, F / 2, F, 0, (size_t)(F / 2) * F * 9);
-        add(p + "head.2.weight", 0, c.last_dim, F / 2, 0, (size_t)c.last_dim * (F / 2) * 9);
-        add(p + "act_postprocess.3.1.weight", 0, c.layer_dims[3], c.layer_dims[3], 0, (size_t)c.layer_dims[3] * c.layer_dims[3] * 9);
-        add(p + "act_postprocess.0.1.weight", 1, c.layer_dims[0], c.layer_dims[0], 4, (size_t)c.layer_dims[0] * c.layer_dims[0] * 16);
-        add(p + "act_postprocess.1.1.weight", 1, c.layer_dims[1], c.layer_dims[1], 2, (size_t)c.layer_dims[1] * c.layer_dims[1] * 4);
+                    add(p + "scratch.refinenet" + std::to_string(r) + ".resConfUnit" + std::to_string(u) + ".conv" + std::to_string(k) + ".weight", Pack::CONV3X3, F, F, 0, (size_t)F * F * 9);
+        add(p + "head.0.weight", Pack::CONV3X3, F / 2, F, 0, (size_t)(F / 2) * F * 9);
+        add(p + "head.2.weight", Pack::CONV3X3, c.last_dim, F / 2, 0, (size_t)c.last_dim * (F / 2) * 9);
+        add(p + "act_postprocess.3.1.weight", Pack::CONV3X3, c.layer_dims[3], c.layer_dims[3], 0, (size_t)c.layer_dims[3] * c.layer_dims[3] * 9);
+        add(p + "act_postprocess.0.1.weight", Pack::CONVT, c.layer_dims[0], c.layer_dims[0], 4, (size_t)c.layer_dims[0] * c.layer_dims[0] * 16);
+        add(p + "act_postprocess.1.1.weight", Pack::CONVT, c.layer_dims[1], c.layer_dims[1], 2, (size_t)c.layer_dims[1] * c.layer_dims[1] * 4);
     }
     const int D = c.dec_embed_dim;
     for (int d = 0; d < 2; d++)
         for (int i = 0; i < c.dec_depth; i++) {
             const std::string p = std::string(d ? "dec_blocks2." : "dec_blocks.") + std::to_string(i) + ".cross_attn.";
-            add(p + "kv", 2, D, 0, 0, (size_t)2 * D * D + 2 * D);
+            add(p + "kv", Pack::KV_CONCAT, D, 0, 0, (size_t)2 * D * D + 2 * D);
         }
-    v.push_back({"rope", 3, 0, 0, 0, off});
+    v.push_back({"rope", Pack::ROPE, 0, 0, 0, off});
     off = align_up(off + (size_t)2 * a3r_model_s::MAX_POS * 16 * 4, 256);
-    v.push_back({"range_stats", 6, 0, 0, 0, off});
+    v.push_back({"range_stats", Pack::STATS, 0, 0, 0, off});
     off = align_up(off + (size_t)a3r_model_s::MAX_SITES * 4, 256);
     if (m->gemm_form != Form::F32) {
         auto twin = [&](const std::string& n, int N, int K, Form f) {
-            v.push_back({n, 4, N, K, (int)f, off});
+            v.push_back({n, Pack::TWIN, N, K, (int)f, off});
             off = align_up(off + (f == Form::FH2 ? a3r_fh2_bytes(N, K) + 256 : a3r_bf3_w_bytes(N, K)), 256);
         };
         auto twin_lin = [&](const std::string& n, int N, int K) { twin(n, N, K, m->gemm_form); };
@@ -210,7 +212,7 @@ std::vector<PackItem> pack_plan(a3r_model_s* m, size_t* total) {
         // DPT heads: every packed 3x3 conv weight [Cout, 9 Cin] and the 1x1 out_conv of the fusion blocks
         std::vector<PackItem> convs;
         for (const PackItem& it : v)
-            if (it.kind == 0) convs.push_back(it);
+            if (it.kind == Pack::CONV3X3) convs.push_back(it);
         for (const PackItem& it : convs) twin(it.name, it.a, 9 * it.b, m->map_form);
         for (int h = 1; h <= 2; h++)
             for (int r = 1; r <= 4; r++)
@@ -272,35 +274,30 @@ static float ln_static_scale(float g, float b, int D) {
     return std::ldexp(1.f, k);
 }
 
-extern "C" int a3r_model_finalize(a3r_model_t m, void* packed, size_t packed_bytes, void* stream) {
-    A3R_CHECK_ARG(m && packed, "a3r_model_finalize: null argument");
-    size_t total = 0;
-    std::vector<PackItem> plan = pack_plan(m, &total);
-    A3R_CHECK_ARG(packed_bytes >= total, "a3r_model_finalize: packed buffer too small (%zu < %zu)", packed_bytes, total);
-    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(packed) & 255) == 0, "a3r_model_finalize: packed buffer must be 256-byte aligned");
+using PackedPtrs = std::map<std::string, const float*>;
+
+// the repacked weights of the plan (everything but the twins, which follow the binding: shapes are validated there) -> pk
+static int repack_weights(a3r_model_s* m, const std::vector<PackItem>& plan, char* pk, void* stream, PackedPtrs& packed_ptr) {
     const a3r_model_config& c = m->cfg;
-    const int E = c.enc_embed_dim, D = c.dec_embed_dim, F = c.feature_dim, L = c.last_dim;
+    const int D = c.dec_embed_dim;
     hipStream_t st = as_stream(stream);
-    char* pk = static_cast<char*>(packed);
-    std::map<std::string, const float*> packed_ptr;
-    // --- repack
     for (const PackItem& it : plan) {
         float* dst = reinterpret_cast<float*>(pk + it.off);
-        if (it.kind == 4) continue;      // after binding (shapes are validated there)
-        if (it.kind == 6) {
+        if (it.kind == Pack::TWIN) continue;
+        if (it.kind == Pack::STATS) {
             m->stats = reinterpret_cast<unsigned*>(dst);
             A3R_HIP(hipMemsetAsync(dst, 0, (size_t)a3r_model_s::MAX_SITES * 4, st));
             continue;
         }
-        if (it.kind == 0) {
+        if (it.kind == Pack::CONV3X3) {
             const float* src;
             NEED(it.name, &src, it.a, it.b, 3, 3);
             if (int rc = a3r_pack_conv3x3(src, dst, it.a, it.b, stream)) return rc;
-        } else if (it.kind == 1) {
+        } else if (it.kind == Pack::CONVT) {
             const float* src;
             NEED(it.name, &src, it.a, it.b, it.s, it.s);
             if (int rc = a3r_pack_convT(src, dst, it.a, it.b, it.s, stream)) return rc;
-        } else if (it.kind == 2) {
+        } else if (it.kind == Pack::KV_CONCAT) {
             const std::string p = it.name.substr(0, it.name.size() - 2);   // strip "kv"
             const float *kw, *kb, *vw, *vb;
             NEED(p + "projk.weight", &kw, D, D); NEED(p + "projk.bias", &kb, D);
@@ -321,6 +318,86 @@ extern "C" int a3r_model_finalize(a3r_model_t m, void* packed, size_t packed_byt
         }
         packed_ptr[it.name] = dst;
     }
+    return A3R_OK;
+}
+
+static int bind_head(a3r_model_s* m, int h, PackedPtrs& packed_ptr) {
+    const a3r_model_config& c = m->cfg;
+    const int E = c.enc_embed_dim, D = c.dec_embed_dim, F = c.feature_dim, L = c.last_dim;
+    HeadW& H = m->head[h];
+    const std::string p = "downstream_head" + std::to_string(h + 1) + ".dpt.";
+    const int* ld = c.layer_dims;
+    NEED(p + "act_postprocess.0.0.weight", &H.a0w, ld[0], E, 1, 1); NEED(p + "act_postprocess.0.0.bias", &H.a0b, ld[0]);
+    NEED(p + "act_postprocess.0.1.bias", &H.a0tb, ld[0]);
+    NEED(p + "act_postprocess.1.0.weight", &H.a1w, ld[1], D, 1, 1); NEED(p + "act_postprocess.1.0.bias", &H.a1b, ld[1]);
+    NEED(p + "act_postprocess.1.1.bias", &H.a1tb, ld[1]);
+    NEED(p + "act_postprocess.2.0.weight", &H.a2w, ld[2], D, 1, 1); NEED(p + "act_postprocess.2.0.bias", &H.a2b, ld[2]);
+    NEED(p + "act_postprocess.3.0.weight", &H.a3w, ld[3], D, 1, 1); NEED(p + "act_postprocess.3.0.bias", &H.a3b, ld[3]);
+    NEED(p + "act_postprocess.3.1.bias", &H.a3cb, ld[3]);
+    H.a0tw = packed_ptr[p + "act_postprocess.0.1.weight"];
+    H.a1tw = packed_ptr[p + "act_postprocess.1.1.weight"];
+    H.a3cw = packed_ptr[p + "act_postprocess.3.1.weight"];
+    for (int i = 0; i < 4; i++) H.rn[i] = packed_ptr[p + "scratch.layer" + std::to_string(i + 1) + "_rn.weight"];
+    for (int r = 0; r < 4; r++) {
+        const std::string q = p + "scratch.refinenet" + std::to_string(r + 1) + ".";
+        NEED(q + "out_conv.weight", &H.ref[r].ow, F, F, 1, 1); NEED(q + "out_conv.bias", &H.ref[r].ob, F);
+        RcuW* rr[2] = {&H.ref[r].r1, &H.ref[r].r2};
+        for (int u = 0; u < 2; u++) {
+            const std::string qq = q + "resConfUnit" + std::to_string(u + 1) + ".";
+            rr[u]->c1w = packed_ptr[qq + "conv1.weight"]; rr[u]->c2w = packed_ptr[qq + "conv2.weight"];
+            NEED(qq + "conv1.bias", &rr[u]->c1b, F); NEED(qq + "conv2.bias", &rr[u]->c2b, F);
+        }
+    }
+    H.h0w = packed_ptr[p + "head.0.weight"]; NEED(p + "head.0.bias", &H.h0b, F / 2);
+    H.h2w = packed_ptr[p + "head.2.weight"]; NEED(p + "head.2.bias", &H.h2b, L);
+    NEED(p + "head.4.weight", &H.h4w, 4, L, 1, 1); NEED(p + "head.4.bias", &H.h4b, 4);
+    return A3R_OK;
+}
+
+// static scales of the LayerNorm -> fh2 sites (fh2 mode)
+static int ln_scales(a3r_model_s* m, void* stream) {
+    const int E = m->cfg.enc_embed_dim, D = m->cfg.dec_embed_dim;
+    hipStream_t st = as_stream(stream);
+    m->ln_scale.clear();
+    if (m->gemm_form != Form::FH2) return A3R_OK;
+    std::vector<std::pair<const float*, const float*>> lns;      // (gamma, beta) of every LayerNorm whose output feeds a GEMM
+    auto add_block = [&](const BlockW& b, bool cross) {
+        lns.push_back({b.n1w, b.n1b}); lns.push_back({b.n2w, b.n2b});
+        if (cross) { lns.push_back({b.n3w, b.n3b}); lns.push_back({b.nyw, b.nyb}); }
+    };
+    for (const BlockW& b : m->enc) add_block(b, false);
+    for (const BlockW& b : m->pc) add_block(b, false);
+    for (const BlockW& b : m->dec1) add_block(b, true);
+    for (const BlockW& b : m->dec2) add_block(b, true);
+    float* scratch = reinterpret_cast<float*>(m->stats);          // two words of the (still unused) statistics area
+    for (size_t i = 0; i < lns.size(); i++) {
+        const int Dn = i < 2 * m->enc.size() ? E : D;
+        float gb[2] = {0.f, 0.f};
+        if (int rc = a3r_absmax(lns[i].first, Dn, scratch, stream)) return rc;
+        if (int rc = a3r_absmax(lns[i].second, Dn, scratch + 1, stream)) return rc;
+        A3R_HIP(hipMemcpyAsync(gb, scratch, 8, hipMemcpyDeviceToHost, st));
+        A3R_HIP(hipStreamSynchronize(st));
+        if (!std::isfinite(gb[0]) || !std::isfinite(gb[1])) {
+            set_error("a3r_model_finalize: a LayerNorm weight contains non-finite values");
+            return A3R_EINVAL;
+        }
+        m->ln_scale[lns[i].first] = ln_static_scale(gb[0], gb[1], Dn);
+    }
+    A3R_HIP(hipMemsetAsync(m->stats, 0, 8, st));
+    return A3R_OK;
+}
+
+extern "C" int a3r_model_finalize(a3r_model_t m, void* packed, size_t packed_bytes, void* stream) {
+    A3R_CHECK_ARG(m && packed, "a3r_model_finalize: null argument");
+    size_t total = 0;
+    std::vector<PackItem> plan = pack_plan(m, &total);
+    A3R_CHECK_ARG(packed_bytes >= total, "a3r_model_finalize: packed buffer too small (%zu < %zu)", packed_bytes, total);
+    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(packed) & 255) == 0, "a3r_model_finalize: packed buffer must be 256-byte aligned");
+    const a3r_model_config& c = m->cfg;
+    const int E = c.enc_embed_dim, D = c.dec_embed_dim;
+    char* pk = static_cast<char*>(packed);
+    PackedPtrs packed_ptr;
+    if (int rc = repack_weights(m, plan, pk, stream, packed_ptr)) return rc;
     // --- bind
     NEED("patch_embed.proj.weight", &m->pe_w, E, 3, 16, 16); NEED("patch_embed.proj.bias", &m->pe_b, E);
     NEED("patch_embed_point_cloud.proj.weight", &m->pepc_w, D, 3, 16, 16); NEED("patch_embed_point_cloud.proj.bias", &m->pepc_b, D);
@@ -350,67 +427,13 @@ extern "C" int a3r_model_finalize(a3r_model_t m, void* packed, size_t packed_byt
         NEED("zero_convs." + std::to_string(i) + ".0.weight", &m->zc_w[i], D, D, 1);
         NEED("zero_convs." + std::to_string(i) + ".0.bias", &m->zc_b[i], D);
     }
-    for (int h = 0; h < 2; h++) {
-        HeadW& H = m->head[h];
-        const std::string p = "downstream_head" + std::to_string(h + 1) + ".dpt.";
-        const int* ld = c.layer_dims;
-        NEED(p + "act_postprocess.0.0.weight", &H.a0w, ld[0], E, 1, 1); NEED(p + "act_postprocess.0.0.bias", &H.a0b, ld[0]);
-        NEED(p + "act_postprocess.0.1.bias", &H.a0tb, ld[0]);
-        NEED(p + "act_postprocess.1.0.weight", &H.a1w, ld[1], D, 1, 1); NEED(p + "act_postprocess.1.0.bias", &H.a1b, ld[1]);
-        NEED(p + "act_postprocess.1.1.bias", &H.a1tb, ld[1]);
-        NEED(p + "act_postprocess.2.0.weight", &H.a2w, ld[2], D, 1, 1); NEED(p + "act_postprocess.2.0.bias", &H.a2b, ld[2]);
-        NEED(p + "act_postprocess.3.0.weight", &H.a3w, ld[3], D, 1, 1); NEED(p + "act_postprocess.3.0.bias", &H.a3b, ld[3]);
-        NEED(p + "act_postprocess.3.1.bias", &H.a3cb, ld[3]);
-        H.a0tw = packed_ptr[p + "act_postprocess.0.1.weight"];
-        H.a1tw = packed_ptr[p + "act_postprocess.1.1.weight"];
-        H.a3cw = packed_ptr[p + "act_postprocess.3.1.weight"];
-        for (int i = 0; i < 4; i++) H.rn[i] = packed_ptr[p + "scratch.layer" + std::to_string(i + 1) + "_rn.weight"];
-        for (int r = 0; r < 4; r++) {
-            const std::string q = p + "scratch.refinenet" + std::to_string(r + 1) + ".";
-            NEED(q + "out_conv.weight", &H.ref[r].ow, F, F, 1, 1); NEED(q + "out_conv.bias", &H.ref[r].ob, F);
-            RcuW* rr[2] = {&H.ref[r].r1, &H.ref[r].r2};
-            for (int u = 0; u < 2; u++) {
-                const std::string qq = q + "resConfUnit" + std::to_string(u + 1) + ".";
-                rr[u]->c1w = packed_ptr[qq + "conv1.weight"]; rr[u]->c2w = packed_ptr[qq + "conv2.weight"];
-                NEED(qq + "conv1.bias", &rr[u]->c1b, F); NEED(qq + "conv2.bias", &rr[u]->c2b, F);
-            }
-        }
-        H.h0w = packed_ptr[p + "head.0.weight"]; NEED(p + "head.0.bias", &H.h0b, F / 2);
-        H.h2w = packed_ptr[p + "head.2.weight"]; NEED(p + "head.2.bias", &H.h2b, L);
-        NEED(p + "head.4.weight", &H.h4w, 4, L, 1, 1); NEED(p + "head.4.bias", &H.h4b, 4);
-    }
-    // --- static scales of the LayerNorm -> fh2 sites (fh2 mode)
-    m->ln_scale.clear();
-    if (m->gemm_form == Form::FH2) {
-        std::vector<std::pair<const float*, const float*>> lns;      // (gamma, beta) of every LayerNorm whose output feeds a GEMM
-        auto add_block = [&](const BlockW& b, bool cross) {
-            lns.push_back({b.n1w, b.n1b}); lns.push_back({b.n2w, b.n2b});
-            if (cross) { lns.push_back({b.n3w, b.n3b}); lns.push_back({b.nyw, b.nyb}); }
-        };
-        for (const BlockW& b : m->enc) add_block(b, false);
-        for (const BlockW& b : m->pc) add_block(b, false);
-        for (const BlockW& b : m->dec1) add_block(b, true);
-        for (const BlockW& b : m->dec2) add_block(b, true);
-        float* scratch = reinterpret_cast<float*>(m->stats);          // two words of the (still unused) statistics area
-        for (size_t i = 0; i < lns.size(); i++) {
-            const int Dn = i < 2 * m->enc.size() ? E : D;
-            float gb[2] = {0.f, 0.f};
-            if (int rc = a3r_absmax(lns[i].first, Dn, scratch, stream)) return rc;
-            if (int rc = a3r_absmax(lns[i].second, Dn, scratch + 1, stream)) return rc;
-            A3R_HIP(hipMemcpyAsync(gb, scratch, 8, hipMemcpyDeviceToHost, st));
-            A3R_HIP(hipStreamSynchronize(st));
-            if (!std::isfinite(gb[0]) || !std::isfinite(gb[1])) {
-                set_error("a3r_model_finalize: a LayerNorm weight contains non-finite values");
-                return A3R_EINVAL;
-            }
-            m->ln_scale[lns[i].first] = ln_static_scale(gb[0], gb[1], Dn);
-        }
-        A3R_HIP(hipMemsetAsync(m->stats, 0, 8, st));
-    }
+    for (int h = 0; h < 2; h++)
+        if (int rc = bind_head(m, h, packed_ptr)) return rc;
+    if (int rc = ln_scales(m, stream)) return rc;
     // --- twins of the nn.Linear and conv weights
     m->twins.t.clear();
     for (const PackItem& it : plan) {
-        if (it.kind != 4) continue;
+        if (it.kind != Pack::TWIN) continue;
         auto pit = packed_ptr.find(it.name);                             // a repacked weight (3x3 convs, the concatenated cross-attention k/v) ...
         const float* src = pit != packed_ptr.end() ? pit->second : m->w.find(it.name)->p;      // ... or one bound (and shape-checked) above
         float* scratch = reinterpret_cast<float*>(pk + it.off + a3r_fh2_bytes(it.a, it.b));
@@ -480,7 +503,9 @@ struct Plan {
     Form gf = Form::FH2, mf = Form::FH2;
     // BF3 GEMMs only: buffers that are only ever read as the A operand of a GEMM (LayerNorm / attention / fc1+GELU outputs, split
     // activations) are kept in the row-pair form of the layout (bf3.h) when the row counts of both views are even
-    bool pair = false;
+    // (pair_all: the call's; a stage on fewer rows than both views' needs that row count to be even too: rows)
+    bool pair = false, pair_all = false;
+    void rows(long M) { pair = pair_all && M % 2 == 0; }
     float* gin_alloc(size_t rows, int K) { return ar.alloc(form_floats(gf, rows, K)); }
     float* gin_scratch(size_t rows, int K) { return ar.alloc(gf == Form::F32 ? 0 : form_floats(gf, rows, K)); }     // only needed for splitting
     template <class T> T* gin_at(T* base, size_t rows, int K) const { return base + form_floats(gf, rows, K); }
@@ -502,7 +527,6 @@ struct Plan {
         split(gf, pair, "split_gin", x, scratch, M, K);
         return scratch;
     }
-    void split_map(const float* x, float* ym, long M, int K) { split(mf, false, "split_map", x, ym, M, K); }
     const Twin* twin(const float* w, Form f) { return f == Form::F32 ? nullptr : m->twins.get(w, f, WHO, rc); }
     // the range fields of an fh2 launch: the operand's scale, and a site for the fh2 output (y itself or the aux twin)
     void range_epi(a3r_epilogue& e, const void* x2, const void* y) {
@@ -543,19 +567,25 @@ struct Plan {
         e.x_pair = pair ? 1 : 0;
         if (!rc) rc = op_linear_grouped(gf, g, so.scale, so.stat, lda, ldc, M, N, K, e, stream);
     }
-    // ---- the DPT heads' ops on maps in operand form
-    void conv_map(const float* xm, const float* wp, float* y, int B, int H, int W, int Cin, int Cout, int stride, const OpEpi& e0) {
+    // ---- the DPT heads' ops on maps in operand form.  F32 maps are the degenerate operand form: the form of x is x itself (map_twin
+    // allocates nothing, split_map does nothing), an auxiliary output has nowhere to go (aux), and a consumer that wants relu(x)
+    // applies the ReLU as it loads (relu_a, rcu_conv1)
+    float* map_twin(float* x, size_t rows, int K) { return mf == Form::F32 ? x : map_alloc(rows, K); }
+    void split_map(const float* x, float* ym, long M, int K) { if (mf != Form::F32) split(mf, false, "split_map", x, ym, M, K); }
+    void aux(OpEpi& e, float* twin, bool relu) { if (mf != Form::F32) { e.aux_op = twin; e.aux_relu = relu ? 1 : 0; } }
+    void conv(const float* xm, const float* wp, float* y, int B, int H, int W, int Cin, int Cout, int stride, const OpEpi& e0) {
         if (skip()) return;
-        traced("conv3x3_map", H, W, Cin);
+        traced("conv3x3", H, W, Cin);
         const Twin* tw = twin(wp, mf);
         const a3r_epilogue e = retarget(e0, mf, [&](a3r_epilogue& r) { range_epi(r, xm, y); });
         if (!rc) rc = op_conv3x3(mf, xm, wp, tw, y, B, H, W, Cin, Cout, stride, e, stream);
     }
-    void up_map(const float* x, float* ym, int B, int H, int W, int C, int Hc, int Wc) {
+    // bilinear 2x of an fp32 map, written in form f (the map form, or F32 for a consumer that needs the values)
+    void up(Form f, const float* x, float* y, int B, int H, int W, int C, int Hc, int Wc) {
         if (skip()) return;
-        traced("upsample2x_map", H, W, C);
-        const Site s = out_site(mf, ym);
-        if (!rc) rc = op_upsample2x(mf, x, ym, B, H, W, C, Hc, Wc, s.scale, s.stat, stream);
+        traced("upsample2x", H, W, C);
+        const Site s = out_site(f, y);
+        if (!rc) rc = op_upsample2x(f, x, y, B, H, W, C, Hc, Wc, s.scale, s.stat, stream);
     }
     // s = c[map] + (r[map] + extra) and the fh2 form of relu(s): the RESID2 epilogue + aux output of a conv that ran on distinct frames
     void combine_map(const float* c, const float* r, const float* extra, const int32_t* map, float* s, float* sr2, int S, long px, int C) {
@@ -606,16 +636,6 @@ struct Plan {
         rc = gf == Form::BF3 ? a3r_attention_bf3(q, ldq, k, ldk, v, ldv, o, ldo, B, H, Nq, Nk, pair, stream)
                    : a3r_attention(q, ldq, k, ldk, v, ldv, o, ldo, B, H, Nq, Nk, stream);
     }
-    void conv(const float* x, const float* wp, float* y, int B, int H, int W, int Cin, int Cout, int stride, const a3r_epilogue& e) {
-        if (skip()) return;
-        traced("conv3x3", H, W, Cin);
-        rc = a3r_conv3x3(x, wp, y, B, H, W, Cin, Cout, stride, &e, stream);
-    }
-    void up(const float* x, float* y, int B, int H, int W, int C, int Hc, int Wc) {
-        if (skip()) return;
-        traced("upsample2x", H, W, C);
-        rc = a3r_upsample2x(x, y, B, H, W, C, Hc, Wc, stream);
-    }
     // projection feeding attention: RoPE on the leading columns, output in gin form
     OpEpi rope_epi(const float* bias, int rope_cols, int ntok, int gw) {
         OpEpi e = epi(A3R_EPI_ROPE, bias);
@@ -649,50 +669,23 @@ struct Plan {
     }
 };
 
-// rcu (dpt_block.py:120-142): out = conv2(relu(conv1(relu(x)))) + x (+ extra)
-void rcu(Plan& P, const RcuW& w, const float* x, const float* extra, float* tmp, float* out, int B, int H, int W, int F) {
-    OpEpi e1 = P.epi(A3R_EPI_RELU, w.c1b);
-    e1.relu_a = 1;
-    P.conv(x, w.c1w, tmp, B, H, W, F, F, 1, e1);
-    OpEpi e2 = extra ? P.epi(A3R_EPI_RESID2, w.c2b, x, extra) : P.epi(A3R_EPI_RESID, w.c2b, x);
-    P.conv(tmp, w.c2w, out, B, H, W, F, F, 1, e2);
-}
-
-// FeatureFusionBlock_custom.forward (dpt_block.py:186-218): returns [B, Hc, Wc, F] with (Hc,Wc) = crop of (2H,2W)
-// (`two` says whether xs[1] exists: pointers are null during the dry sizing pass, so it cannot be inferred from x1)
-float* fusion(Plan& P, const FusionW& w, const float* x0, const float* x1, bool two, int B, int H, int W, int F, int Hc, int Wc) {
-    Arena& ar = P.ar;
-    const size_t n = (size_t)B * H * W * F;
-    float* tmp = ar.alloc(n);
-    float* cur;
-    if (two) {
-        float* s = ar.alloc(n);
-        rcu(P, w.r1, x1, x0, tmp, s, B, H, W, F);     // output + resConfUnit1(xs[1])
-        cur = s;
-    } else {
-        cur = const_cast<float*>(x0);
-    }
-    float* o = ar.alloc(n);
-    rcu(P, w.r2, cur, nullptr, tmp, o, B, H, W, F);
-    float* u = ar.alloc((size_t)B * Hc * Wc * F);
-    P.up(o, u, B, H, W, F, Hc, Wc);
-    float* r = ar.alloc((size_t)B * Hc * Wc * F);
-    P.linear_f32(u, F, w.ow, r, F, B * Hc * Wc, F, F, P.epi(A3R_EPI_NONE, w.ob));
-    return r;
-}
-
-// ---- the same blocks on maps in operand form (bf3 or fh2).  A conv input lives in operand form; where the fp32 value is also needed
-// (skip connections) the producer writes both (aux_op), pre-activated when the consumer is an RCU (which starts with a ReLU).
-// x: fp32 [B,H,W,F]; xr3: operand form of relu(x); tmp3: operand-form scratch; out: fp32; out_r3: operand form of relu(out) or null
-// (aux_relu = false: out_r3 is the operand form of out itself, for a consumer that does not start with a ReLU)
-void rcu_map(Plan& P, const RcuW& w, const float* x, const float* xr3, const float* extra, float* tmp3, float* out, float* out_r3,
-             int B, int H, int W, int F, bool aux_relu = true) {
+// ---- the DPT blocks on maps in operand form (F32, bf3 or fh2).  A conv input lives in operand form; where the fp32 value is also
+// needed (skip connections) the producer writes both (Plan::aux), pre-activated when the consumer is an RCU (which starts with a ReLU).
+// first conv of an rcu (dpt_block.py:120-142): tmp3 = operand form of relu(conv1(relu(x))), xr3 being the operand form of relu(x)
+void rcu_conv1(Plan& P, const RcuW& w, const float* xr3, float* tmp3, int B, int H, int W, int F) {
     OpEpi e1 = P.epi(A3R_EPI_RELU, w.c1b);
     e1.out_op = 1;
-    P.conv_map(xr3, w.c1w, tmp3, B, H, W, F, F, 1, e1);
+    e1.relu_a = P.mf == Form::F32;      // xr3 is x itself there
+    P.conv(xr3, w.c1w, tmp3, B, H, W, F, F, 1, e1);
+}
+// rcu: out = conv2(relu(conv1(relu(x)))) + x (+ extra).  x: fp32 [B,H,W,F]; xr3: operand form of relu(x); tmp3: operand-form scratch;
+// out: fp32; out_r3: operand form of relu(out) or null (aux_relu = false: of out itself, for a consumer that does not start with a ReLU)
+void rcu_map(Plan& P, const RcuW& w, const float* x, const float* xr3, const float* extra, float* tmp3, float* out, float* out_r3,
+             int B, int H, int W, int F, bool aux_relu = true) {
+    rcu_conv1(P, w, xr3, tmp3, B, H, W, F);
     OpEpi e2 = extra ? P.epi(A3R_EPI_RESID2, w.c2b, x, extra) : P.epi(A3R_EPI_RESID, w.c2b, x);
-    if (out_r3) { e2.aux_op = out_r3; e2.aux_relu = aux_relu ? 1 : 0; }
-    P.conv_map(tmp3, w.c2w, out, B, H, W, F, F, 1, e2);
+    if (out_r3) P.aux(e2, out_r3, aux_relu);
+    P.conv(tmp3, w.c2w, out, B, H, W, F, F, 1, e2);
 }
 
 // The level-0 branch of a head on the distinct frames of its side (fh2 maps): x1 / x1r3 of fusion_map hold U < B images, slot b's
@@ -704,7 +697,10 @@ static bool dpt_ref_order() {       // A/B switch: up-sample first, as the refer
     return on;
 }
 
-// returns fp32 [B, Hc, Wc, F], or its operand form when `last` (refinenet1's output only feeds head.0's 3x3 conv)
+// FeatureFusionBlock_custom.forward (dpt_block.py:186-218) on x0 (the previous block's output; x0r3: its pre-activated operand form,
+// read only when the block has no xs[1]) and x1 = xs[1] (`two` says whether it exists: pointers are null during the dry sizing pass).
+// Returns fp32 [B, Hc, Wc, F] with (Hc, Wc) = crop of (2H, 2W), or its operand form when `last` (refinenet1's output only feeds
+// head.0's 3x3 conv).
 // hm: resConfUnit1 depends on the pair through the residual x0 alone -- its two convs run on hm->U images, the second with the
 // bias-only epilogue, and combine_map adds the skip and x0 per slot in the RESID2 epilogue's order and writes the fh2 twin (that
 // conv's auxiliary site: the sites keep their number and order).  lo_out: leave the block's output before the bilinear 2x there
@@ -712,18 +708,16 @@ static bool dpt_ref_order() {       // A/B switch: up-sample first, as the refer
 float* fusion_map(Plan& P, const FusionW& w, const float* x0, const float* x0r3, const float* x1, const float* x1r3, bool two, int B,
                   int H, int W, int F, int Hc, int Wc, bool last, const HeadMerge* hm = nullptr, const float** lo_out = nullptr) {
     Arena& ar = P.ar;
-    const size_t px = (size_t)B * H * W, n = px * F;
+    const size_t px = (size_t)B * H * W, n = px * F, opx = (size_t)B * Hc * Wc;
     float* tmp3 = P.map_alloc(px, F);
     const float *cur, *cur3;
     if (two) {
         float* s = ar.alloc(n);
-        float* sr3 = P.map_alloc(px, F);
+        float* sr3 = P.map_twin(s, px, F);
         if (hm) {
             float* c = ar.alloc((size_t)hm->U * H * W * F);
-            OpEpi e1 = P.epi(A3R_EPI_RELU, w.r1.c1b);
-            e1.out_op = 1;
-            P.conv_map(x1r3, w.r1.c1w, tmp3, hm->U, H, W, F, F, 1, e1);
-            P.conv_map(tmp3, w.r1.c2w, c, hm->U, H, W, F, F, 1, P.epi(A3R_EPI_NONE, w.r1.c2b));
+            rcu_conv1(P, w.r1, x1r3, tmp3, hm->U, H, W, F);
+            P.conv(tmp3, w.r1.c2w, c, hm->U, H, W, F, F, 1, P.epi(A3R_EPI_NONE, w.r1.c2b));
             if (hm->fold) P.up_combine_map(hm->x0_lo, c, x1, hm->map, s, sr3, B, hm->lo_h, hm->lo_w, F, H, W);
             else P.combine_map(c, x1, x0, hm->map, s, sr3, B, (long)H * W, F);
         } else
@@ -732,40 +726,28 @@ float* fusion_map(Plan& P, const FusionW& w, const float* x0, const float* x0r3,
     } else {
         cur = x0; cur3 = x0r3;
     }
-    if (dpt_ref_order()) {
-        float* o = ar.alloc(n);
+    float* o = ar.alloc(n);
+    if (dpt_ref_order() || P.mf == Form::F32) {
+        // the reference's order: up-sample, then out_conv.  F32 maps always run it (a map has no operand form to hand to the 1x1 GEMM)
         rcu_map(P, w.r2, cur, cur3, nullptr, tmp3, o, nullptr, B, H, W, F);
-        const size_t opx = (size_t)B * Hc * Wc;
         float* u3 = P.map_alloc(opx, F);
-        P.up_map(o, u3, B, H, W, F, Hc, Wc);
+        P.up(P.mf, o, u3, B, H, W, F, Hc, Wc);
         OpEpi e = P.epi(A3R_EPI_NONE, w.ob);
-        float* r;
-        if (last) { r = P.map_alloc(opx, F); e.out_op = 1; }
-        else r = ar.alloc(opx * F);
+        e.out_op = last;
+        float* r = last ? P.map_alloc(opx, F) : ar.alloc(opx * F);
         P.linear(u3, F, w.ow, r, F, (int)opx, F, F, e, /*plain_x=*/true);
         return r;
     }
     // out_conv (1x1, dpt_block.py:216) is applied BEFORE the bilinear 2x instead of after it: both are linear maps over
     // different axes (channels / pixels) and the interpolation weights sum to one, so conv(up(x)) + b == up(conv(x) + b) up
     // to fp32 rounding -- a quarter of the 1x1 GEMM's rows, and the full-resolution map is written once instead of three times.
-    float* o = ar.alloc(n);
     float* o3 = P.map_alloc(px, F);
     rcu_map(P, w.r2, cur, cur3, nullptr, tmp3, o, o3, B, H, W, F, /*aux_relu=*/false);
     float* lo = ar.alloc(n);
     P.linear(o3, F, w.ow, lo, F, (int)px, F, F, P.epi(A3R_EPI_NONE, w.ob), /*plain_x=*/true);
-    const size_t opx = (size_t)B * Hc * Wc;
-    float* r;
-    if (lo_out) {
-        *lo_out = lo;
-        return nullptr;
-    }
-    if (last) {
-        r = P.map_alloc(opx, F);
-        P.up_map(lo, r, B, H, W, F, Hc, Wc);
-    } else {
-        r = ar.alloc(opx * F);
-        P.up(lo, r, B, H, W, F, Hc, Wc);
-    }
+    if (lo_out) { *lo_out = lo; return nullptr; }
+    float* r = last ? P.map_alloc(opx, F) : ar.alloc(opx * F);
+    P.up(last ? P.mf : Form::F32, lo, r, B, H, W, F, Hc, Wc);
     return r;
 }
 
@@ -777,6 +759,10 @@ struct Distinct {
     int n_img, n_pd; const int32_t *uniq_img, *map_img, *uniq_pd, *map_pd;
     int n_side[2]; const int32_t *uniq_side[2], *map_side[2];
 };
+// the sizing pass: counts, no lists
+Distinct distinct_counts(int n_img, int n_pd, int n_side) {
+    return {n_img, n_pd, nullptr, nullptr, nullptr, nullptr, {n_side, n_side}, {nullptr, nullptr}, {nullptr, nullptr}};
+}
 
 // Bytes of a head's level-0 buffers with n images in them, as the arena rounds them: a0, l0, l03, r0, r0r3; the merged branch adds
 // the compact enc_norm rows and the bias-only output c of resConfUnit1's second conv.  fh2 maps take 4 bytes per element.
@@ -794,42 +780,323 @@ bool head_merge_fits(const a3r_model_config& c, int N, int B, int U) {
     return U > 0 && U < B && head_level0_bytes(c, N, U, true) <= head_level0_bytes(c, N, B, false);
 }
 
-// phase: 0 = whole forward from images; 1 = encoder only (img1 [B,...] -> feat_out [B,N,E]);
-//        2 = decoder + heads from cached encoder features (feat1_in / feat2_in [B,N,E]).
+// ---- one call of the plan.  phase: 0 = whole forward from images; 1 = encoder only (img[0] [B,...] -> feat_out [B,N,E]);
+// 2 = decoder + heads from cached encoder features (feat_in [B,N,E] per view).  dry: the sizing pass (every pointer null).
 // dd: run the parts of the plan that depend on one frame alone -- the encoder, and the depth-prior token branch -- on the distinct
 // frames only and copy their rows to every slot.  The ops, their order and so the fh2 site numbers are those of the plain plan;
 // only row counts differ, and every row is computed as it is there.  dd->n_side: the same for the level-0 branch of each DPT head
 // (fh2 maps only), whose rows are put back by the combine pass (fusion_map).
-int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, const float* pd1, const float* pd2, int B,
-             int H, int W, float* pts1, float* conf1, float* pts2, float* conf2, void* ws, size_t ws_bytes, void* stream,
-             size_t* peak, int phase = 0, const float* feat1_in = nullptr, const float* feat2_in = nullptr,
-             float* feat_out = nullptr, const Distinct* dd = nullptr) {
-    const a3r_model_config& c = m->cfg;
-    const int E = c.enc_embed_dim, D = c.dec_embed_dim, F = c.feature_dim, L = c.last_dim;
-    const int nh = H / 16, nw = W / 16, N = nh * nw, BN = B * N, M2 = 2 * BN;
-    // rows of the image / depth-prior stages; merged kinds only (d_img, d_pd)
-    // (the distinct frames' enc_norm rows wait in the first three decoder level buffers, which must hold them: E <= 3 D at least)
-    const bool d_img = dd && phase == 0 && dd->n_img < 2 * B && (size_t)dd->n_img * N * E <= 3 * (size_t)M2 * D;
-    const bool d_pd = dd && dd->n_pd < 2 * B;
-    const int Mi = d_img ? dd->n_img * N : M2, Mp = d_pd ? dd->n_pd * N : M2;
-    struct ProductsGuard {      // the handle's arithmetic mode for the duration of this plan
-        int prev; bool on;
-        ProductsGuard(bool on_, int p) : prev(6), on(on_) { if (on) prev = a3r_bf3_set_products(p); }
-        ~ProductsGuard() { if (on) a3r_bf3_set_products(prev); }
-    } products_guard(!dry && m->gemm_form != Form::F32, m->products);
-    struct PassesGuard {
-        int prev; bool on;
-        PassesGuard(bool on_, int p) : prev(3), on(on_) { if (on) prev = a3r_fh2_set_passes(p); }
-        ~PassesGuard() { if (on) a3r_fh2_set_passes(prev); }
-    } passes_guard(!dry && m->gemm_form == Form::FH2, m->fh2_passes);
+struct Call {
+    int phase = 0, B = 0, H = 0, W = 0;
+    bool dry = false;
+    const float *img[2] = {nullptr, nullptr}, *pd[2] = {nullptr, nullptr};      // the two views' inputs ...
+    float *pts[2] = {nullptr, nullptr}, *conf[2] = {nullptr, nullptr};          // ... and outputs
+    const float* feat_in[2] = {nullptr, nullptr};
+    float* feat_out = nullptr;
+    void *ws = nullptr, *stream = nullptr;
+    size_t ws_bytes = 0;
+    const Distinct* dd = nullptr;
+};
+
+// its shapes: widths, the token grid, rows of one view (BN) and of both (M2), and the rows of the image / depth-prior stages: Mi / Mp
+// < M2 for a merged kind (d_img, d_pd).  The distinct frames' enc_norm rows wait in the first three decoder level buffers, which
+// must hold them: E <= 3 D at least.
+struct Dims {
+    const a3r_model_config& c;
+    int B, H, W, E, D, F, L, nh, nw, N, BN, M2;
+    bool d_img, d_pd;
+    int Mi, Mp;
+    Dims(const a3r_model_config& c_, const Call& k)
+        : c(c_), B(k.B), H(k.H), W(k.W), E(c.enc_embed_dim), D(c.dec_embed_dim), F(c.feature_dim), L(c.last_dim), nh(k.H / 16),
+          nw(k.W / 16), N(nh * nw), BN(B * N), M2(2 * BN),
+          d_img(k.dd && k.phase == 0 && k.dd->n_img < 2 * B && (size_t)k.dd->n_img * N * E <= 3 * (size_t)M2 * D),
+          d_pd(k.dd && k.dd->n_pd < 2 * B), Mi(d_img ? k.dd->n_img * N : M2), Mp(d_pd ? k.dd->n_pd * N : M2) {}
+};
+
+// the buffers that outlive a stage (allocated below the arena mark the stages reset to), and what the stages hand on in them
+struct Levels {
+    float *feat, *pc, *fbuf[4], *dec_last;      // enc_norm output = level 0; depth-prior tokens; ping, pong, hook A, hook B; dec_norm
+    float *tap_lvl, *tap_pc0;                   // debug taps (a3r_model_set_tap_level) or null
+    // Distinct inputs only: no allocation is added.  The depth-prior tokens of the distinct maps, pcu [Mp, D], live in hook buffer
+    // B, which the decoder first writes at level hook_b, after the last dec_blocks_pc block (dec_depth / 2 - 2 < hook_b); the
+    // distinct frames' enc_norm rows wait in fbuf[0..2] (contiguous, idle until the decoder starts) for their copy to `feat`.
+    float *featu, *pcu;
+    const float *lvl_a = nullptr, *lvl_b = nullptr;      // the decoder levels the heads hook (decoder_stage)
+};
+
+// distinct rows -> the rows of all 2 B slots
+void copy_rows(Plan& P, const Dims& g, const float* src, float* dst, const int32_t* map, int C) {
+    if (!P.skip()) P.rc = gather_rows(src, dst, map, 2 * g.B, g.N, C, P.stream);
+}
+void tap_copy(Plan& P, const Dims& g, float* dst, const float* src) {
+    if (P.dry() || P.rc != A3R_OK || !dst) return;
+    if (hipMemcpyAsync(dst, src, (size_t)g.M2 * g.D * 4, hipMemcpyDeviceToDevice, as_stream(P.stream)) != hipSuccess) {
+        set_error("a3r_model_forward: tap copy failed");
+        P.rc = A3R_EHIP;
+    }
+}
+
+// ViT encoder (_encode_image model.py:151-163) on M = n N rows: the images of k.img -- the distinct ones (d_img), both views', or
+// the B frames of an encode call (img[1] null) -- patchified into cols, enc_norm rows to `out`
+void encoder_stage(Plan& P, const Call& k, const Dims& g, float* cols, float* cols3, int M, float* out) {
+    a3r_model_s* m = P.m;
+    const int E = g.E, hidden = E * g.c.mlp_ratio;
+    float* x = P.ar.alloc((size_t)M * E);
+    float* xn = P.gin_alloc(M, E);
+    float* qkv = P.gin_alloc(M, 3 * E);
+    float* att = P.gin_alloc(M, E);
+    float* hid = P.gin_alloc(M, hidden);
+    if (!P.skip()) {
+        const long sb = 3L * g.H * g.W, sc = (long)g.H * g.W, sy = g.W, sx = 1;
+        if (g.d_img) P.rc = patchify_indexed(k.img[0], k.img[1], k.dd->uniq_img, k.dd->n_img, g.B, cols, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
+        else if (!(P.rc = a3r_patchify(k.img[0], cols, g.B, 3, g.H, g.W, sb, sc, sy, sx, P.stream)) && k.img[1])
+            P.rc = a3r_patchify(k.img[1], cols + (size_t)g.BN * 768, g.B, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
+    }
+    P.rows(M);
+    P.linear(P.gin_from(cols, cols3, M, 768), 768, m->pe_w, x, E, M, E, 768, P.epi(A3R_EPI_NONE, m->pe_b));
+    for (const BlockW& w : m->enc) {
+        P.self_block(w, x, x, M, E, g.c.enc_num_heads, g.N, g.nw, xn, qkv, att);
+        P.mlp(w, w.n2w, w.n2b, x, M, E, hidden, xn, hid);
+    }
+    P.rows(g.M2);
+    P.ln_f32(x, m->encn_w, m->encn_b, out, M, E);
+}
+
+// decode call: the cached per-frame features of the two views, gathered into the [2 B N, E] layout the decoder expects
+void load_features(Plan& P, const Call& k, const Dims& g, float* feat) {
+    if (P.skip()) return;
+    const size_t bytes = (size_t)g.BN * g.E * sizeof(float);
+    hipError_t e1 = hipMemcpyAsync(feat, k.feat_in[0], bytes, hipMemcpyDeviceToDevice, as_stream(P.stream));
+    hipError_t e2 = hipMemcpyAsync(feat + (size_t)g.BN * g.E, k.feat_in[1], bytes, hipMemcpyDeviceToDevice, as_stream(P.stream));
+    if (e1 != hipSuccess || e2 != hipSuccess) { set_error("a3r_model_decode: feature copy failed"); P.rc = A3R_EHIP; }
+}
+
+// point-map patch embedding (model.py:244-248) of the Mp rows of the (distinct) depth priors -> pcu; pred_depth is [B,H,W,3]:
+// channel stride 1
+void embed_pc_stage(Plan& P, const Call& k, const Dims& g, float* cols, float* cols3, float* pcu) {
+    if (!P.skip()) {
+        const long sb = 3L * g.H * g.W, sc = 1, sy = 3L * g.W, sx = 3;
+        if (g.d_pd) P.rc = patchify_indexed(k.pd[0], k.pd[1], k.dd->uniq_pd, k.dd->n_pd, g.B, cols, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
+        else if (!(P.rc = a3r_patchify(k.pd[0], cols, g.B, 3, g.H, g.W, sb, sc, sy, sx, P.stream)))
+            P.rc = a3r_patchify(k.pd[1], cols + (size_t)g.BN * 768, g.B, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
+    }
+    P.rows(g.Mp);
+    P.linear(P.gin_from(cols, cols3, g.Mp, 768), 768, P.m->pepc_w, pcu, g.D, g.Mp, g.D, 768, P.epi(A3R_EPI_NONE, P.m->pepc_b));
+    P.rows(g.M2);
+}
+
+// gin buffers of the decoder, [2 B N, .] rows: side 1 of each starts at gin_at(., BN, .)
+struct DecBufs { float *xn, *yn, *qkv, *qb, *kv, *att, *hid; };
+
+// DecoderBlock.forward (blocks.py:186-191) of dec_blocks[i] on view 1 and dec_blocks2[i] on view 2, cur -> nxt [2 B N, D].  Both
+// decoders advance together: side s reads x = cur[s], y = cur[1-s] (model.py:218-220) and every same-shape projection of the two
+// sides is one grouped launch.
+void decoder_block_pair(Plan& P, const Dims& g, const BlockW& w0, const BlockW& w1, const float* cur, float* nxt, const DecBufs& t) {
+    const int B = g.B, N = g.N, BN = g.BN, D = g.D, nw = g.nw, heads = g.c.dec_num_heads, hidden = D * g.c.mlp_ratio;
+    const size_t S = (size_t)BN * D;                   // side stride in a [2*BN, D] buffer
+    const float *x0 = cur, *x1 = cur + S;
+    float *o0 = nxt, *o1 = nxt + S;
+    float *xn = t.xn, *yn = t.yn, *qkv = t.qkv, *qb = t.qb, *kv = t.kv, *att = t.att, *hid = t.hid;
+    // x = x + attn(norm1(x))                                   blocks.py:187
+    float* xn1 = P.gin_at(xn, BN, D);                  // side 1 of the gin buffers
+    float* yn1 = P.gin_at(yn, BN, D);
+    P.ln(x0, w0.n1w, w0.n1b, xn, BN, D);
+    P.ln(x1, w1.n1w, w1.n1b, xn1, BN, D);
+    float* att1 = P.gin_at(att, BN, D);
+    P.linear2(xn, xn1, D, w0.qkvw, w1.qkvw, w0.qkvb, w1.qkvb, qkv, P.gin_at(qkv, BN, 3 * D), 3 * D, BN, 3 * D, D,
+              P.rope_epi(nullptr, 2 * D, N, nw));
+    P.attn(qkv, 3 * D, P.gin_col(qkv, D), 3 * D, P.gin_col(qkv, 2 * D), 3 * D, att, D, 2 * B, heads, N, N, nullptr, att1);
+    P.linear2(att, att1, D, w0.projw, w1.projw, w0.projb, w1.projb, o0, o1, D, BN, D, D, P.epi(A3R_EPI_RESID, nullptr), x0, x1);
+    // y_ = norm_y(y); x = x + cross_attn(norm2(x), y_, y_)     blocks.py:188-189
+    P.ln(x1, w0.nyw, w0.nyb, yn, BN, D);               // side 0 attends to view 2's tokens
+    P.ln(x0, w1.nyw, w1.nyb, yn1, BN, D);
+    P.ln(o0, w0.n2w, w0.n2b, xn, BN, D);
+    P.ln(o1, w1.n2w, w1.n2b, xn1, BN, D);
+    P.linear2(xn, xn1, D, w0.qw, w1.qw, w0.qb, w1.qb, qb, P.gin_at(qb, BN, D), D, BN, D, D, P.rope_epi(nullptr, D, N, nw));
+    P.linear2(yn, yn1, D, w0.kvw, w1.kvw, w0.kvb, w1.kvb, kv, P.gin_at(kv, BN, 2 * D), 2 * D, BN, 2 * D, D,
+              P.rope_epi(nullptr, D, N, nw));
+    P.attn(qb, D, kv, 2 * D, P.gin_col(kv, D), 2 * D, att, D, 2 * B, heads, N, N, kv, att1);
+    P.linear2(att, att1, D, w0.cprojw, w1.cprojw, w0.cprojb, w1.cprojb, o0, o1, D, BN, D, D, P.epi(A3R_EPI_RESID, nullptr), o0, o1);
+    // x = x + mlp(norm3(x))                                    blocks.py:190
+    P.ln(o0, w0.n3w, w0.n3b, xn, BN, D);
+    P.ln(o1, w1.n3w, w1.n3b, xn1, BN, D);
+    float* hid1 = P.gin_at(hid, BN, hidden);
+    P.linear2(xn, xn1, D, w0.fc1w, w1.fc1w, w0.fc1b, w1.fc1b, hid, hid1, hidden, BN, hidden, D, P.gin_epi(A3R_EPI_GELU, nullptr));
+    P.linear2(hid, hid1, hidden, w0.fc2w, w1.fc2w, w0.fc2b, w1.fc2b, o0, o1, D, BN, D, hidden, P.epi(A3R_EPI_RESID, nullptr), o0, o1);
+}
+
+// _decoder (model.py:201-233): decoder_embed, the two decoders with the dec_blocks_pc / zero_convs branch on the depth-prior tokens,
+// dec_norm.  Leaves the hooked levels in v.lvl_a / v.lvl_b and the last one in v.dec_last.
+void decoder_stage(Plan& P, const Call& k, const Dims& g, Levels& v) {
+    a3r_model_s* m = P.m;
+    const a3r_model_config& c = g.c;
+    const int D = g.D, E = g.E, M2 = g.M2, Mp = g.Mp, hidden = D * c.mlp_ratio;
+    const int hook_a = c.dec_depth * 2 / 4, hook_b = c.dec_depth * 3 / 4;   // levels 6 and 9 for depth 12
+    const DecBufs t = {P.gin_alloc(M2, D), P.gin_alloc(M2, D), P.gin_alloc(M2, 3 * D), P.gin_alloc(M2, D), P.gin_alloc(M2, 2 * D),
+                       P.gin_alloc(M2, D), P.gin_alloc(M2, hidden)};      // (a braced list is evaluated in order: so are the allocations)
+    float* pc3 = P.gin_scratch(M2, D);
+    float* cur = v.fbuf[0];
+    float* feat3 = P.gin_scratch(M2, E);
+    P.linear(P.gin_from(v.feat, feat3, M2, E), E, m->de_w, cur, D, M2, D, E, P.epi(A3R_EPI_NONE, m->de_b));
+    // zero_convs[i] of the depth-prior tokens, added to level x in place (distinct maps only: their tokens are copied to all slots'
+    // rows first, so the zero-conv and its epilogue stay as they are)
+    auto add_pc = [&](int i, float* x) {
+        if (g.d_pd) copy_rows(P, g, v.pcu, v.pc, k.dd->map_pd, D);
+        P.linear(P.gin_from(v.pc, pc3, M2, D), D, m->zc_w[i], x, D, M2, D, D, P.epi(A3R_EPI_RESID, m->zc_b[i], x));
+    };
+    add_pc(0, cur);
+    const int npc = n_pc_blocks(c);
+    for (int i = 0; i < c.dec_depth; i++) {
+        const int level = i + 1;
+        float* nxt = level == hook_a ? v.fbuf[2] : level == hook_b ? v.fbuf[3] : cur == v.fbuf[0] ? v.fbuf[1] : v.fbuf[0];
+        decoder_block_pair(P, g, m->dec1[i], m->dec2[i], cur, nxt, t);
+        if (i < npc) {   // model.py:223-226
+            P.rows(Mp);
+            P.self_block(m->pc[i], v.pcu, v.pcu, Mp, D, c.dec_num_heads, g.N, g.nw, t.xn, t.qkv, t.att);
+            P.mlp(m->pc[i], m->pc[i].n2w, m->pc[i].n2b, v.pcu, Mp, D, hidden, t.xn, t.hid);
+            P.rows(M2);
+            add_pc(i + 1, nxt);
+        }
+        if (level == hook_a) v.lvl_a = nxt;
+        if (level == hook_b) v.lvl_b = nxt;
+        if (level == m->tap_level) tap_copy(P, g, v.tap_lvl, nxt);
+        cur = nxt;
+    }
+    P.ln_f32(cur, m->decn_w, m->decn_b, v.dec_last, M2, D);   // model.py:231-232
+}
+
+// act_postprocess (dpt_block.py:353-405) of the head of side s: the four hooked levels -> the maps l[0..3] that layer_rn reads, in
+// operand form (l[3] is written in it; the others are split: small maps, plain split passes).  Level 0 (enc_norm rows) depends on
+// the frame alone: B0 images, the side's distinct ones when its head merges.
+void head_levels(Plan& P, const Call& k, const Dims& g, const Levels& v, int s, int B0, float* (&l)[4]) {
+    Arena& ar = P.ar;
+    const HeadW& Hd = P.m->head[s];
+    const int *ld = g.c.layer_dims, nh = g.nh, nw = g.nw, B = g.B, BN = g.BN, E = g.E, D = g.D;
+    const int h3 = (nh + 2 - 3) / 2 + 1, w3 = (nw + 2 - 3) / 2 + 1;
+    auto side = [&](const float* x, int cols) { return x ? x + (size_t)s * BN * cols : nullptr; };      // (null in the sizing pass)
+    // 1x1 adapters: in fh2 mode a split pass + the fh2 GEMM (5x the exact-fp32 MFMA kernel's rate) instead of a3r_linear
+    auto adapter = [&](const float* t, int K, const float* w, const float* b, float* y, int cout, int rows) {
+        if (P.gf != Form::FH2) { P.linear_f32(t, K, w, y, cout, rows, cout, K, P.epi(A3R_EPI_NONE, b)); return; }
+        const size_t keep = ar.off;
+        float* tg = P.gin_scratch(rows, K);
+        P.linear(P.gin_from(t, tg, rows, K), K, w, y, cout, rows, cout, K, P.epi(A3R_EPI_NONE, b));
+        ar.off = keep;                                          // the split is dead once the GEMM is enqueued (stream order)
+    };
+    // the transposed conv (kernel = stride = ps) behind an adapter: a GEMM whose epilogue scatters the ps x ps pixels
+    auto pixshuf = [&](const float* a, const float* w, const float* b, float* y, int ps, int C, int rows) {
+        OpEpi e = P.epi(A3R_EPI_PIXSHUF, b);
+        e.ps_s = ps; e.ps_h = nh; e.ps_w = nw; e.ps_cout = C;
+        P.linear_f32(a, C, w, y, C, rows, ps * ps * C, C, e);
+    };
+    const size_t BN0 = (size_t)B0 * g.N;
+    const float* t0 = side(v.feat, E);
+    if (B0 < B) {
+        float* fu = ar.alloc(BN0 * E);
+        if (!P.skip()) P.rc = gather_rows(v.feat, fu, k.dd->uniq_side[s], B0, g.N, E, P.stream);
+        t0 = fu;
+    }
+    float* a0 = ar.alloc(BN0 * ld[0]);
+    adapter(t0, E, Hd.a0w, Hd.a0b, a0, ld[0], (int)BN0);
+    float* l0 = ar.alloc(BN0 * 16 * ld[0]);
+    pixshuf(a0, Hd.a0tw, Hd.a0tb, l0, 4, ld[0], (int)BN0);
+    float* a1 = ar.alloc((size_t)BN * ld[1]);
+    adapter(side(v.lvl_a, D), D, Hd.a1w, Hd.a1b, a1, ld[1], BN);
+    float* l1 = ar.alloc((size_t)BN * 4 * ld[1]);
+    pixshuf(a1, Hd.a1tw, Hd.a1tb, l1, 2, ld[1], BN);
+    float* l2 = ar.alloc((size_t)BN * ld[2]);
+    adapter(side(v.lvl_b, D), D, Hd.a2w, Hd.a2b, l2, ld[2], BN);
+    float* a3 = ar.alloc((size_t)BN * ld[3]);
+    adapter(side(v.dec_last, D), D, Hd.a3w, Hd.a3b, a3, ld[3], BN);
+    l[3] = P.map_alloc((size_t)B * h3 * w3, ld[3]);
+    float* a33 = P.map_twin(a3, BN, ld[3]);
+    P.split_map(a3, a33, BN, ld[3]);
+    OpEpi e = P.epi(A3R_EPI_NONE, Hd.a3cb);
+    e.out_op = 1;
+    P.conv(a33, Hd.a3cw, l[3], B, nh, nw, ld[3], ld[3], 2, e);
+    l[0] = P.map_twin(l0, BN0 * 16, ld[0]);
+    P.split_map(l0, l[0], (long)BN0 * 16, ld[0]);
+    l[1] = P.map_twin(l1, (size_t)BN * 4, ld[1]);
+    P.split_map(l1, l[1], (long)BN * 4, ld[1]);
+    l[2] = P.map_twin(l2, BN, ld[2]);
+    P.split_map(l2, l[2], BN, ld[2]);
+}
+
+// One DPT head (dpt_head.py:34-66), the one of side s: act_postprocess, scratch.layer_rn, the four fusion blocks, head.0 / .2 / .4
+// and the postprocess.  Every map is fp32 with a twin in operand form where a conv reads it (under F32 the map itself).
+void head_stage(Plan& P, const Call& k, const Dims& g, const Levels& v, int s) {
+    a3r_model_s* m = P.m;
+    Arena& ar = P.ar;
+    const HeadW& Hd = m->head[s];
+    const int *ld = g.c.layer_dims, nh = g.nh, nw = g.nw, B = g.B, H = g.H, W = g.W, BN = g.BN, F = g.F, L = g.L;
+    const int h3 = (nh + 2 - 3) / 2 + 1, w3 = (nw + 2 - 3) / 2 + 1;
+    const int B0 = k.dd && P.mf == Form::FH2 ? k.dd->n_side[s] : B;
+    // (the combine pass folded into refinenet2's 2x up-sample, whose fp32 output only it would read)
+    HeadMerge hmerge = {B0, k.dd ? k.dd->map_side[s] : nullptr, B0 < B && m->dedup_head_fold && !dpt_ref_order(), nullptr, 2 * nh, 2 * nw};
+    const size_t BN0 = (size_t)B0 * g.N;
+    float* l[4];
+    head_levels(P, k, g, v, s, B0, l);
+    // scratch.layer_rn (no bias): fp32 for the skip connection + pre-activated map form for the first RCU conv
+    float* r0 = ar.alloc(BN0 * 16 * F);
+    float* r0r3 = P.map_twin(r0, BN0 * 16, F);
+    float* r1 = ar.alloc((size_t)BN * 4 * F);
+    float* r1r3 = P.map_twin(r1, (size_t)BN * 4, F);
+    float* r2 = ar.alloc((size_t)BN * F);
+    float* r2r3 = P.map_twin(r2, BN, F);
+    float* r3 = ar.alloc((size_t)B * h3 * w3 * F);
+    float* r3r3 = P.map_twin(r3, (size_t)B * h3 * w3, F);
+    auto rn_epi = [&](float* twin) { OpEpi e = P.epi(A3R_EPI_NONE, nullptr); P.aux(e, twin, true); return e; };
+    P.conv(l[0], Hd.rn[0], r0, B0, 4 * nh, 4 * nw, ld[0], F, 1, rn_epi(r0r3));
+    P.conv(l[1], Hd.rn[1], r1, B, 2 * nh, 2 * nw, ld[1], F, 1, rn_epi(r1r3));
+    P.conv(l[2], Hd.rn[2], r2, B, nh, nw, ld[2], F, 1, rn_epi(r2r3));
+    P.conv(l[3], Hd.rn[3], r3, B, h3, w3, ld[3], F, 1, rn_epi(r3r3));
+    // refinement (dpt_head.py:57-60)
+    float* p4 = fusion_map(P, Hd.ref[3], r3, r3r3, nullptr, nullptr, false, B, h3, w3, F, nh, nw, false);
+    float* p3 = fusion_map(P, Hd.ref[2], p4, nullptr, r2, r2r3, true, B, nh, nw, F, 2 * nh, 2 * nw, false);
+    float* p2 = fusion_map(P, Hd.ref[1], p3, nullptr, r1, r1r3, true, B, 2 * nh, 2 * nw, F, 4 * nh, 4 * nw, false, nullptr,
+                           hmerge.fold ? &hmerge.x0_lo : nullptr);
+    float* p13 = fusion_map(P, Hd.ref[0], p2, nullptr, r0, r0r3, true, B, 4 * nh, 4 * nw, F, 8 * nh, 8 * nw, true, B0 < B ? &hmerge : nullptr);
+    // head (dpt_block.py:323-330)
+    const int Hh = 8 * nh, Wh = 8 * nw;
+    float* h0 = ar.alloc((size_t)B * Hh * Wh * (F / 2));
+    P.conv(p13, Hd.h0w, h0, B, Hh, Wh, F, F / 2, 1, P.epi(A3R_EPI_NONE, Hd.h0b));
+    float* hu3 = P.map_alloc((size_t)B * H * W, F / 2);
+    P.up(P.mf, h0, hu3, B, Hh, Wh, F / 2, H, W);
+    if (P.mf == Form::FH2 && L == 128) {
+        // head.2 (3x3 conv + ReLU), head.4 (1x1 conv 128 -> 4) and the postprocess in ONE launch: the [B H W, 128] map is
+        // neither written nor read back (8.4 GB per head and step at 42 pairs), dpt_block.py:323-329 + postprocess.py:10-58
+        OpEpi e = P.epi(A3R_EPI_HEAD, Hd.h2b);
+        e.head_w = Hd.h4w; e.head_b = Hd.h4b; e.head_conf = k.conf[s];
+        P.conv(hu3, Hd.h2w, k.pts[s], B, H, W, F / 2, L, 1, e);
+        return;
+    }
+    float* h2 = ar.alloc((size_t)B * H * W * L);
+    P.conv(hu3, Hd.h2w, h2, B, H, W, F / 2, L, 1, P.epi(A3R_EPI_RELU, Hd.h2b));
+    if (!P.skip()) P.rc = a3r_head_final(h2, Hd.h4w, Hd.h4b, k.pts[s], k.conf[s], (long)B * H * W, L, P.stream);
+}
+
+// a process-wide arithmetic mode (a3r_bf3_set_products, a3r_fh2_set_passes) set to the handle's for the duration of a plan
+template <int (*Set)(int)> struct ModeGuard {
+    int prev = 0; bool on;
+    ModeGuard(bool on_, int v) : on(on_) { if (on) prev = Set(v); }
+    ~ModeGuard() { if (on) Set(prev); }
+};
+
+// The plan of one call: the persistent buffers, then the stages, each starting from the same arena mark.  The order of the
+// allocations and of the sites, both observable ("Where a fused producer or consumer is wired in"), is the order of the
+// stage calls here and of the lines inside each stage.
+int run_plan(a3r_model_s* m, const Call& k, size_t* peak = nullptr) {
+    const Dims g(m->cfg, k);
+    const bool dry = k.dry;
+    ModeGuard<a3r_bf3_set_products> products_guard(!dry && m->gemm_form != Form::F32, m->products);
+    ModeGuard<a3r_fh2_set_passes> passes_guard(!dry && m->gemm_form == Form::FH2, m->fh2_passes);
     Plan P;
-    P.m = m; P.stream = stream; P.phase = phase; P.gf = m->gemm_form; P.mf = m->map_form;
+    P.m = m; P.stream = k.stream; P.phase = k.phase; P.gf = m->gemm_form; P.mf = m->map_form;
     if (!dry && P.gf == Form::FH2) {
-        if (hipMemsetAsync(m->stats, 0, (size_t)a3r_model_s::MAX_SITES * 4, as_stream(stream)) != hipSuccess) {
+        if (hipMemsetAsync(m->stats, 0, (size_t)a3r_model_s::MAX_SITES * 4, as_stream(k.stream)) != hipSuccess) {
             set_error("a3r_model_forward: clearing the range statistics failed");
             return A3R_EHIP;
         }
-        m->last_phase = phase;
+        m->last_phase = k.phase;
         m->last_sites = 0;
     }
     struct SitesGuard {      // however the plan returns: how many sites it walked
@@ -837,343 +1104,62 @@ int run_plan(a3r_model_s* m, bool dry, const float* img1, const float* img2, con
         ~SitesGuard() { if (on) m->last_sites = P->site_no < a3r_model_s::MAX_SITES ? P->site_no : a3r_model_s::MAX_SITES; }
     } sites_guard{m, &P, !dry};
     static const bool plain_act = getenv("A3R_BF3_PLAIN_ACT") != nullptr;      // A/B switch: keep every activation in plain rows
-    P.pair = P.gf == Form::BF3 && BN % 2 == 0 && !plain_act;
-    P.ar = {static_cast<char*>(ws), 0, ws_bytes, dry, 0};
+    P.pair = P.pair_all = P.gf == Form::BF3 && g.BN % 2 == 0 && !plain_act;
+    P.ar = {static_cast<char*>(k.ws), 0, k.ws_bytes, dry, 0};
     Arena& ar = P.ar;
-    if (phase == 1) {
-        // ---------------- encoder only, B images (_encode_image model.py:151-163): per-frame features for caching.
-        // The reference re-encodes a frame for every pair it appears in; the result does not depend on the pair.
-        float* cols = ar.alloc((size_t)BN * 768);
-        float* cols3 = P.gin_scratch(BN, 768);
-        float* x = ar.alloc((size_t)BN * E);
-        float* xn = P.gin_alloc(BN, E);
-        float* qkv = P.gin_alloc(BN, 3 * E);
-        float* att = P.gin_alloc(BN, E);
-        float* hid = P.gin_alloc(BN, E * c.mlp_ratio);
-        if (!dry) {
-            const long sb = 3L * H * W, sc = (long)H * W, sy = W, sx = 1;
-            if ((P.rc = a3r_patchify(img1, cols, B, 3, H, W, sb, sc, sy, sx, stream))) return P.rc;
-        }
-        P.linear(P.gin_from(cols, cols3, BN, 768), 768, m->pe_w, x, E, BN, E, 768, P.epi(A3R_EPI_NONE, m->pe_b));
-        for (int i = 0; i < c.enc_depth; i++) {
-            P.self_block(m->enc[i], x, x, BN, E, c.enc_num_heads, N, nw, xn, qkv, att);
-            P.mlp(m->enc[i], m->enc[i].n2w, m->enc[i].n2b, x, BN, E, E * c.mlp_ratio, xn, hid);
-        }
-        P.ln_f32(x, m->encn_w, m->encn_b, dry ? nullptr : feat_out, BN, E);
+    const int D = g.D, E = g.E, M2 = g.M2;
+    if (k.phase == 1) {
+        // encoder only: per-frame features for caching.  The reference re-encodes a frame for every pair it appears in; the result
+        // does not depend on the pair.
+        float* cols = ar.alloc((size_t)g.BN * 768);
+        float* cols3 = P.gin_scratch(g.BN, 768);
+        encoder_stage(P, k, g, cols, cols3, g.BN, k.feat_out);
         if (peak) *peak = ar.peak;
         return P.rc;
     }
     // ---------------- persistent buffers
-    float* feat = ar.alloc((size_t)M2 * E);       // enc_norm output = level 0
-    float* pc = ar.alloc((size_t)M2 * D);
-    float* fbuf[4];
-    for (int i = 0; i < 4; i++) fbuf[i] = ar.alloc((size_t)M2 * D);   // ping, pong, hook A, hook B
-    float* dec_last = ar.alloc((size_t)M2 * D);
-    // debug taps (a3r_model_set_tap_level): copies of one decoder level and of the point-cloud tokens before their first block
-    float* tap_lvl = m->tap_level > 0 ? ar.alloc((size_t)M2 * D) : nullptr;
-    float* tap_pc0 = m->tap_level > 0 ? ar.alloc((size_t)M2 * D) : nullptr;
-    auto tap_copy = [&](float* dst, const float* src) {
-        if (dry || P.rc != A3R_OK || !dst) return;
-        if (hipMemcpyAsync(dst, src, (size_t)M2 * D * 4, hipMemcpyDeviceToDevice, as_stream(stream)) != hipSuccess) {
-            set_error("a3r_model_forward: tap copy failed");
-            P.rc = A3R_EHIP;
-        }
-    };
-    // Distinct inputs only (dd): no allocation is added.  The depth-prior tokens of the distinct maps, pcu [Mp, D], live in hook
-    // buffer B, which the decoder first writes at level hook_b, after the last dec_blocks_pc block (dec_depth / 2 - 2 < hook_b); the
-    // distinct frames' enc_norm rows wait in fbuf[0..2] (contiguous, idle until the decoder starts) for their copy to `feat`.
-    float* pcu = d_pd ? fbuf[3] : pc;
-    float* featu = d_img ? fbuf[0] : feat;
-    if (!dry && d_img && (fbuf[1] != fbuf[0] + (size_t)M2 * D || fbuf[2] != fbuf[1] + (size_t)M2 * D)) {
+    Levels v;
+    v.feat = ar.alloc((size_t)M2 * E);
+    v.pc = ar.alloc((size_t)M2 * D);
+    for (int i = 0; i < 4; i++) v.fbuf[i] = ar.alloc((size_t)M2 * D);
+    v.dec_last = ar.alloc((size_t)M2 * D);
+    // debug taps: copies of one decoder level and of the point-cloud tokens before their first block
+    v.tap_lvl = m->tap_level > 0 ? ar.alloc((size_t)M2 * D) : nullptr;
+    v.tap_pc0 = m->tap_level > 0 ? ar.alloc((size_t)M2 * D) : nullptr;
+    v.pcu = g.d_pd ? v.fbuf[3] : v.pc;
+    v.featu = g.d_img ? v.fbuf[0] : v.feat;
+    if (!dry && g.d_img && (v.fbuf[1] != v.fbuf[0] + (size_t)M2 * D || v.fbuf[2] != v.fbuf[1] + (size_t)M2 * D)) {
         set_error("a3r_model_forward: internal: the decoder level buffers are not contiguous");
         return A3R_ESTATE;
     }
-    // the row-pair layout (P.pair) of a stage on Mi or Mp rows needs that row count to be even; the 2 B N-row stages keep theirs
-    const bool pair_all = P.pair;
-    auto copy_rows = [&](const float* src, float* dst, const int32_t* map, int C) {      // distinct rows -> the rows of all 2 B slots
-        if (!P.skip()) P.rc = gather_rows(src, dst, map, 2 * B, N, C, stream);
-    };
-    // point-map patch embedding (model.py:244-248); pred_depth is [B,H,W,3]: channel stride 1
-    auto embed_pc = [&](float* cols, float* cols3) {
-        if (!P.skip()) {
-            const long sb = 3L * H * W, sc = 1, sy = 3L * W, sx = 3;
-            if (d_pd) P.rc = patchify_indexed(pd1, pd2, dd->uniq_pd, dd->n_pd, B, cols, 3, H, W, sb, sc, sy, sx, stream);
-            else if (!(P.rc = a3r_patchify(pd1, cols, B, 3, H, W, sb, sc, sy, sx, stream)))
-                P.rc = a3r_patchify(pd2, cols + (size_t)BN * 768, B, 3, H, W, sb, sc, sy, sx, stream);
-        }
-        P.pair = pair_all && Mp % 2 == 0;
-        P.linear(P.gin_from(cols, cols3, Mp, 768), 768, m->pepc_w, pcu, D, Mp, D, 768, P.epi(A3R_EPI_NONE, m->pepc_b));
-        P.pair = pair_all;
-    };
     const size_t mark = ar.off;
-    // ---------------- encoder (model.py:151-163)
-    if (phase == 2) {
-        // cached per-frame features: gather the two views' rows into the [2*B*N, E] layout the decoder expects
-        float* cols = ar.alloc((size_t)Mp * 768);
-        float* cols3 = P.gin_scratch(Mp, 768);
-        if (!dry) {
-            const size_t bytes = (size_t)BN * E * sizeof(float);
-            hipError_t e1 = hipMemcpyAsync(feat, feat1_in, bytes, hipMemcpyDeviceToDevice, as_stream(stream));
-            hipError_t e2 = hipMemcpyAsync(feat + (size_t)BN * E, feat2_in, bytes, hipMemcpyDeviceToDevice, as_stream(stream));
-            if (e1 != hipSuccess || e2 != hipSuccess) { set_error("a3r_model_decode: feature copy failed"); return A3R_EHIP; }
-        }
-        embed_pc(cols, cols3);
-    } else {
-        const int Mc = Mi > Mp ? Mi : Mp;
-        float* cols = ar.alloc((size_t)Mc * 768);
-        float* cols3 = P.gin_scratch(Mc, 768);
-        float* x = ar.alloc((size_t)Mi * E);
-        float* xn = P.gin_alloc(Mi, E);
-        float* qkv = P.gin_alloc(Mi, 3 * E);
-        float* att = P.gin_alloc(Mi, E);
-        float* hid = P.gin_alloc(Mi, E * c.mlp_ratio);
-        if (!dry) {
-            const long sb = 3L * H * W, sc = (long)H * W, sy = W, sx = 1;
-            if (d_img) {
-                if ((P.rc = patchify_indexed(img1, img2, dd->uniq_img, dd->n_img, B, cols, 3, H, W, sb, sc, sy, sx, stream))) return P.rc;
-            } else {
-                if ((P.rc = a3r_patchify(img1, cols, B, 3, H, W, sb, sc, sy, sx, stream))) return P.rc;
-                if ((P.rc = a3r_patchify(img2, cols + (size_t)BN * 768, B, 3, H, W, sb, sc, sy, sx, stream))) return P.rc;
-            }
-        }
-        P.pair = pair_all && Mi % 2 == 0;
-        P.linear(P.gin_from(cols, cols3, Mi, 768), 768, m->pe_w, x, E, Mi, E, 768, P.epi(A3R_EPI_NONE, m->pe_b));
-        for (int i = 0; i < c.enc_depth; i++) {
-            P.self_block(m->enc[i], x, x, Mi, E, c.enc_num_heads, N, nw, xn, qkv, att);
-            P.mlp(m->enc[i], m->enc[i].n2w, m->enc[i].n2b, x, Mi, E, E * c.mlp_ratio, xn, hid);
-        }
-        P.pair = pair_all;
-        P.ln_f32(x, m->encn_w, m->encn_b, featu, Mi, E);
-        if (d_img) copy_rows(featu, feat, dd->map_img, E);
-        embed_pc(cols, cols3);
+    // ---------------- encoder (or the cached features) and the depth-prior embedding, which share the patch columns
+    const int Mc = k.phase == 2 ? g.Mp : g.Mi > g.Mp ? g.Mi : g.Mp;
+    float* cols = ar.alloc((size_t)Mc * 768);
+    float* cols3 = P.gin_scratch(Mc, 768);
+    if (k.phase == 2) load_features(P, k, g, v.feat);
+    else {
+        encoder_stage(P, k, g, cols, cols3, g.Mi, v.featu);
+        if (g.d_img) copy_rows(P, g, v.featu, v.feat, k.dd->map_img, E);
     }
+    embed_pc_stage(P, k, g, cols, cols3, v.pcu);
     ar.off = mark;
-    tap_copy(tap_pc0, pc);
-    // ---------------- decoder (model.py:201-233)
-    const int hook_a = c.dec_depth * 2 / 4, hook_b = c.dec_depth * 3 / 4;   // levels 6 and 9 for depth 12
-    const float *lvl_a = nullptr, *lvl_b = nullptr;
-    {
-        const int hidden = D * c.mlp_ratio;
-        float* xn = P.gin_alloc(M2, D);
-        float* yn = P.gin_alloc(M2, D);
-        float* qkv = P.gin_alloc(M2, 3 * D);
-        float* qb = P.gin_alloc(M2, D);
-        float* kv = P.gin_alloc(M2, 2 * D);
-        float* att = P.gin_alloc(M2, D);
-        float* hid = P.gin_alloc(M2, hidden);
-        float* pc3 = P.gin_scratch(M2, D);
-        float* cur = fbuf[0];
-        {
-            float* feat3 = P.gin_scratch(M2, E);
-            P.linear(P.gin_from(feat, feat3, M2, E), E, m->de_w, cur, D, M2, D, E, P.epi(A3R_EPI_NONE, m->de_b));
-        }
-        // (distinct maps only: their tokens are copied to all slots' rows first, so the zero-conv and its epilogue stay as they are)
-        if (d_pd) copy_rows(pcu, pc, dd->map_pd, D);
-        P.linear(P.gin_from(pc, pc3, M2, D), D, m->zc_w[0], cur, D, M2, D, D, P.epi(A3R_EPI_RESID, m->zc_b[0], cur));
-        int next_free = 1;
-        const int npc = n_pc_blocks(c);
-        for (int i = 0; i < c.dec_depth; i++) {
-            const int level = i + 1;
-            float* nxt;
-            if (level == hook_a) nxt = fbuf[2];
-            else if (level == hook_b) nxt = fbuf[3];
-            else { nxt = (cur == fbuf[0]) ? fbuf[1] : fbuf[0]; }
-            (void)next_free;
-            {
-                // both decoders advance together: side s reads x = cur[s], y = cur[1-s] (model.py:218-220) and
-                // every same-shape projection of the two sides is one grouped launch.
-                const BlockW& w0 = m->dec1[i];
-                const BlockW& w1 = m->dec2[i];
-                const size_t S = (size_t)BN * D;                   // side stride in a [2*BN, D] buffer
-                const float *x0 = cur, *x1 = cur + S;
-                float *o0 = nxt, *o1 = nxt + S;
-                // x = x + attn(norm1(x))                                   blocks.py:187
-                float* xn1 = P.gin_at(xn, BN, D);                  // side 1 of the gin buffers
-                float* yn1 = P.gin_at(yn, BN, D);
-                P.ln(x0, w0.n1w, w0.n1b, xn, BN, D);
-                P.ln(x1, w1.n1w, w1.n1b, xn1, BN, D);
-                float* att1 = P.gin_at(att, BN, D);
-                P.linear2(xn, xn1, D, w0.qkvw, w1.qkvw, w0.qkvb, w1.qkvb, qkv, P.gin_at(qkv, BN, 3 * D), 3 * D, BN, 3 * D, D,
-                          P.rope_epi(nullptr, 2 * D, N, nw));
-                P.attn(qkv, 3 * D, P.gin_col(qkv, D), 3 * D, P.gin_col(qkv, 2 * D), 3 * D, att, D, 2 * B, c.dec_num_heads, N, N, nullptr, att1);
-                P.linear2(att, att1, D, w0.projw, w1.projw, w0.projb, w1.projb, o0, o1, D, BN, D, D,
-                          P.epi(A3R_EPI_RESID, nullptr), x0, x1);
-                // y_ = norm_y(y); x = x + cross_attn(norm2(x), y_, y_)     blocks.py:188-189
-                P.ln(x1, w0.nyw, w0.nyb, yn, BN, D);               // side 0 attends to view 2's tokens
-                P.ln(x0, w1.nyw, w1.nyb, yn1, BN, D);
-                P.ln(o0, w0.n2w, w0.n2b, xn, BN, D);
-                P.ln(o1, w1.n2w, w1.n2b, xn1, BN, D);
-                P.linear2(xn, xn1, D, w0.qw, w1.qw, w0.qb, w1.qb, qb, P.gin_at(qb, BN, D), D, BN, D, D, P.rope_epi(nullptr, D, N, nw));
-                P.linear2(yn, yn1, D, w0.kvw, w1.kvw, w0.kvb, w1.kvb, kv, P.gin_at(kv, BN, 2 * D), 2 * D, BN, 2 * D, D,
-                          P.rope_epi(nullptr, D, N, nw));
-                P.attn(qb, D, kv, 2 * D, P.gin_col(kv, D), 2 * D, att, D, 2 * B, c.dec_num_heads, N, N, kv, att1);
-                P.linear2(att, att1, D, w0.cprojw, w1.cprojw, w0.cprojb, w1.cprojb, o0, o1, D, BN, D, D,
-                          P.epi(A3R_EPI_RESID, nullptr), o0, o1);
-                // x = x + mlp(norm3(x))                                    blocks.py:190
-                P.ln(o0, w0.n3w, w0.n3b, xn, BN, D);
-                P.ln(o1, w1.n3w, w1.n3b, xn1, BN, D);
-                float* hid1 = P.gin_at(hid, BN, hidden);
-                P.linear2(xn, xn1, D, w0.fc1w, w1.fc1w, w0.fc1b, w1.fc1b, hid, hid1, hidden, BN, hidden, D,
-                          P.gin_epi(A3R_EPI_GELU, nullptr));
-                P.linear2(hid, hid1, hidden, w0.fc2w, w1.fc2w, w0.fc2b, w1.fc2b, o0, o1, D, BN, D, hidden,
-                          P.epi(A3R_EPI_RESID, nullptr), o0, o1);
-            }
-            if (i < npc) {   // model.py:223-226
-                P.pair = pair_all && Mp % 2 == 0;
-                P.self_block(m->pc[i], pcu, pcu, Mp, D, c.dec_num_heads, N, nw, xn, qkv, att);
-                P.mlp(m->pc[i], m->pc[i].n2w, m->pc[i].n2b, pcu, Mp, D, hidden, xn, hid);
-                P.pair = pair_all;
-                if (d_pd) copy_rows(pcu, pc, dd->map_pd, D);
-                P.linear(P.gin_from(pc, pc3, M2, D), D, m->zc_w[i + 1], nxt, D, M2, D, D, P.epi(A3R_EPI_RESID, m->zc_b[i + 1], nxt));
-            }
-            if (level == hook_a) lvl_a = nxt;
-            if (level == hook_b) lvl_b = nxt;
-            if (level == m->tap_level) tap_copy(tap_lvl, nxt);
-            cur = nxt;
-        }
-        P.ln_f32(cur, m->decn_w, m->decn_b, dec_last, M2, D);   // model.py:231-232
-    }
+    tap_copy(P, g, v.tap_pc0, v.pc);
+    // ---------------- decoder
+    decoder_stage(P, k, g, v);
     ar.off = mark;
     if (!dry) {
         m->taps.clear();
-        m->taps["feat"] = {feat, (size_t)M2 * E};
-        m->taps["hook_a"] = {lvl_a, (size_t)M2 * D};
-        m->taps["hook_b"] = {lvl_b, (size_t)M2 * D};
-        m->taps["dec_last"] = {dec_last, (size_t)M2 * D};
-        if (tap_lvl) { m->taps["level"] = {tap_lvl, (size_t)M2 * D}; m->taps["pc0"] = {tap_pc0, (size_t)M2 * D}; }
+        m->taps["feat"] = {v.feat, (size_t)M2 * E};
+        m->taps["hook_a"] = {v.lvl_a, (size_t)M2 * D};
+        m->taps["hook_b"] = {v.lvl_b, (size_t)M2 * D};
+        m->taps["dec_last"] = {v.dec_last, (size_t)M2 * D};
+        if (v.tap_lvl) { m->taps["level"] = {v.tap_lvl, (size_t)M2 * D}; m->taps["pc0"] = {v.tap_pc0, (size_t)M2 * D}; }
     }
-    // ---------------- DPT heads (dpt_head.py:34-66), one per view, fp32
+    // ---------------- DPT heads, one per view
     for (int s = 0; s < 2; s++) {
         ar.off = mark;
-        const HeadW& Hd = m->head[s];
-        const int* ld = c.layer_dims;
-        const float* t0 = feat + (size_t)s * BN * E;      // (t0: the level-0 rows of this side)
-        const float* t1 = lvl_a + (dry ? 0 : (size_t)s * BN * D);
-        const float* t2 = lvl_b + (dry ? 0 : (size_t)s * BN * D);
-        const float* t3 = dec_last + (size_t)s * BN * D;
-        const int h3 = (nh + 2 - 3) / 2 + 1, w3 = (nw + 2 - 3) / 2 + 1;
-        // act_postprocess (dpt_block.py:353-405)
-        // 1x1 adapters: in fh2 mode a split pass + the fh2 GEMM (5x the exact-fp32 MFMA kernel's rate) instead of a3r_linear
-        auto adapter = [&](const float* t, int K, const float* w, const float* b, float* y, int N, int rows) {
-            if (P.gf != Form::FH2) { P.linear_f32(t, K, w, y, N, rows, N, K, P.epi(A3R_EPI_NONE, b)); return; }
-            const size_t keep = ar.off;
-            float* t2 = P.gin_scratch(rows, K);
-            P.linear(P.gin_from(t, t2, rows, K), K, w, y, N, rows, N, K, P.epi(A3R_EPI_NONE, b));
-            ar.off = keep;                                          // the split is dead once the GEMM is enqueued (stream order)
-        };
-        // level 0 (enc_norm rows) depends on the frame alone: B0 images, the side's distinct ones when its head merges
-        const int B0 = dd && P.mf == Form::FH2 ? dd->n_side[s] : B;
-        // (the combine pass folded into refinenet2's 2x up-sample, whose fp32 output only it would read)
-        HeadMerge hmerge = {B0, dd ? dd->map_side[s] : nullptr, B0 < B && m->dedup_head_fold && !dpt_ref_order(), nullptr, 2 * nh, 2 * nw};
-        const size_t BN0 = (size_t)B0 * N;
-        if (B0 < B) {
-            float* fu = ar.alloc(BN0 * E);
-            if (!P.skip()) P.rc = gather_rows(feat, fu, dd->uniq_side[s], B0, N, E, stream);
-            t0 = fu;
-        }
-        float* a0 = ar.alloc(BN0 * ld[0]);
-        adapter(t0, E, Hd.a0w, Hd.a0b, a0, ld[0], (int)BN0);
-        float* l0 = ar.alloc(BN0 * 16 * ld[0]);
-        {
-            OpEpi e = P.epi(A3R_EPI_PIXSHUF, Hd.a0tb);
-            e.ps_s = 4; e.ps_h = nh; e.ps_w = nw; e.ps_cout = ld[0];
-            P.linear_f32(a0, ld[0], Hd.a0tw, l0, ld[0], (int)BN0, 16 * ld[0], ld[0], e);
-        }
-        float* a1 = ar.alloc((size_t)BN * ld[1]);
-        adapter(t1, D, Hd.a1w, Hd.a1b, a1, ld[1], BN);
-        float* l1 = ar.alloc((size_t)BN * 4 * ld[1]);
-        {
-            OpEpi e = P.epi(A3R_EPI_PIXSHUF, Hd.a1tb);
-            e.ps_s = 2; e.ps_h = nh; e.ps_w = nw; e.ps_cout = ld[1];
-            P.linear_f32(a1, ld[1], Hd.a1tw, l1, ld[1], BN, 4 * ld[1], ld[1], e);
-        }
-        float* l2 = ar.alloc((size_t)BN * ld[2]);
-        adapter(t2, D, Hd.a2w, Hd.a2b, l2, ld[2], BN);
-        float* a3 = ar.alloc((size_t)BN * ld[3]);
-        adapter(t3, D, Hd.a3w, Hd.a3b, a3, ld[3], BN);
-        float* l3 = P.map_alloc((size_t)B * h3 * w3, ld[3]);          // only feeds layer4_rn's conv: in map form
-        if (P.mf == Form::F32) {
-            P.conv(a3, Hd.a3cw, l3, B, nh, nw, ld[3], ld[3], 2, P.epi(A3R_EPI_NONE, Hd.a3cb));
-        } else {
-            float* a33 = P.map_alloc(BN, ld[3]);
-            P.split_map(a3, a33, BN, ld[3]);
-            OpEpi e = P.epi(A3R_EPI_NONE, Hd.a3cb);
-            e.out_op = 1;
-            P.conv_map(a33, Hd.a3cw, l3, B, nh, nw, ld[3], ld[3], 2, e);
-        }
-        float* h2 = nullptr;
-        bool fused_tail = false;
-        const int Hh = 8 * nh, Wh = 8 * nw;
-        if (P.mf == Form::F32) {
-            // scratch.layer_rn (no bias)
-            float* r0 = ar.alloc((size_t)BN * 16 * F);
-            P.conv(l0, Hd.rn[0], r0, B, 4 * nh, 4 * nw, ld[0], F, 1, P.epi(A3R_EPI_NONE, nullptr));
-            float* r1 = ar.alloc((size_t)BN * 4 * F);
-            P.conv(l1, Hd.rn[1], r1, B, 2 * nh, 2 * nw, ld[1], F, 1, P.epi(A3R_EPI_NONE, nullptr));
-            float* r2 = ar.alloc((size_t)BN * F);
-            P.conv(l2, Hd.rn[2], r2, B, nh, nw, ld[2], F, 1, P.epi(A3R_EPI_NONE, nullptr));
-            float* r3 = ar.alloc((size_t)B * h3 * w3 * F);
-            P.conv(l3, Hd.rn[3], r3, B, h3, w3, ld[3], F, 1, P.epi(A3R_EPI_NONE, nullptr));
-            // refinement (dpt_head.py:57-60)
-            float* p4 = fusion(P, Hd.ref[3], r3, nullptr, false, B, h3, w3, F, nh, nw);
-            float* p3 = fusion(P, Hd.ref[2], p4, r2, true, B, nh, nw, F, 2 * nh, 2 * nw);
-            float* p2 = fusion(P, Hd.ref[1], p3, r1, true, B, 2 * nh, 2 * nw, F, 4 * nh, 4 * nw);
-            float* p1 = fusion(P, Hd.ref[0], p2, r0, true, B, 4 * nh, 4 * nw, F, 8 * nh, 8 * nw);
-            // head (dpt_block.py:323-330)
-            float* h0 = ar.alloc((size_t)B * Hh * Wh * (F / 2));
-            P.conv(p1, Hd.h0w, h0, B, Hh, Wh, F, F / 2, 1, P.epi(A3R_EPI_NONE, Hd.h0b));
-            float* hu = ar.alloc((size_t)B * H * W * (F / 2));
-            P.up(h0, hu, B, Hh, Wh, F / 2, H, W);
-            h2 = ar.alloc((size_t)B * H * W * L);
-            P.conv(hu, Hd.h2w, h2, B, H, W, F / 2, L, 1, P.epi(A3R_EPI_RELU, Hd.h2b));
-
-        } else {
-            // conv inputs in map form (small maps: plain split passes)
-            float* l03 = P.map_alloc(BN0 * 16, ld[0]);
-            P.split_map(l0, l03, (long)BN0 * 16, ld[0]);
-            float* l13 = P.map_alloc((size_t)BN * 4, ld[1]);
-            P.split_map(l1, l13, (long)BN * 4, ld[1]);
-            float* l23 = P.map_alloc(BN, ld[2]);
-            P.split_map(l2, l23, BN, ld[2]);
-            // scratch.layer_rn (no bias): fp32 for the skip connection + pre-activated map form for the first RCU conv
-            float* r0 = ar.alloc(BN0 * 16 * F);
-            float* r0r3 = P.map_alloc(BN0 * 16, F);
-            float* r1 = ar.alloc((size_t)BN * 4 * F);
-            float* r1r3 = P.map_alloc((size_t)BN * 4, F);
-            float* r2 = ar.alloc((size_t)BN * F);
-            float* r2r3 = P.map_alloc(BN, F);
-            float* r3 = ar.alloc((size_t)B * h3 * w3 * F);
-            float* r3r3 = P.map_alloc((size_t)B * h3 * w3, F);
-            auto rn_epi = [&](float* aux) { OpEpi e = P.epi(A3R_EPI_NONE, nullptr); e.aux_op = aux; e.aux_relu = 1; return e; };
-            P.conv_map(l03, Hd.rn[0], r0, B0, 4 * nh, 4 * nw, ld[0], F, 1, rn_epi(r0r3));
-            P.conv_map(l13, Hd.rn[1], r1, B, 2 * nh, 2 * nw, ld[1], F, 1, rn_epi(r1r3));
-            P.conv_map(l23, Hd.rn[2], r2, B, nh, nw, ld[2], F, 1, rn_epi(r2r3));
-            P.conv_map(l3, Hd.rn[3], r3, B, h3, w3, ld[3], F, 1, rn_epi(r3r3));      // l3 is in map form already
-            // refinement (dpt_head.py:57-60)
-            float* p4 = fusion_map(P, Hd.ref[3], r3, r3r3, nullptr, nullptr, false, B, h3, w3, F, nh, nw, false);
-            float* p3 = fusion_map(P, Hd.ref[2], p4, nullptr, r2, r2r3, true, B, nh, nw, F, 2 * nh, 2 * nw, false);
-            float* p2 = fusion_map(P, Hd.ref[1], p3, nullptr, r1, r1r3, true, B, 2 * nh, 2 * nw, F, 4 * nh, 4 * nw, false, nullptr,
-                                   hmerge.fold ? &hmerge.x0_lo : nullptr);
-            float* p13 = fusion_map(P, Hd.ref[0], p2, nullptr, r0, r0r3, true, B, 4 * nh, 4 * nw, F, 8 * nh, 8 * nw, true, B0 < B ? &hmerge : nullptr);
-            // head (dpt_block.py:323-330)
-            float* h0 = ar.alloc((size_t)B * Hh * Wh * (F / 2));
-            P.conv_map(p13, Hd.h0w, h0, B, Hh, Wh, F, F / 2, 1, P.epi(A3R_EPI_NONE, Hd.h0b));
-            float* hu3 = P.map_alloc((size_t)B * H * W, F / 2);
-            P.up_map(h0, hu3, B, Hh, Wh, F / 2, H, W);
-            if (P.mf == Form::FH2 && L == 128) {
-                // head.2 (3x3 conv + ReLU), head.4 (1x1 conv 128 -> 4) and the postprocess in ONE launch: the [B H W, 128] map is
-                // neither written nor read back (8.4 GB per head and step at 42 pairs), dpt_block.py:323-329 + postprocess.py:10-58
-                OpEpi e = P.epi(A3R_EPI_HEAD, Hd.h2b);
-                e.head_w = Hd.h4w; e.head_b = Hd.h4b; e.head_conf = s ? conf2 : conf1;
-                P.conv_map(hu3, Hd.h2w, s ? pts2 : pts1, B, H, W, F / 2, L, 1, e);
-                fused_tail = true;
-            } else {
-                h2 = ar.alloc((size_t)B * H * W * L);
-                P.conv_map(hu3, Hd.h2w, h2, B, H, W, F / 2, L, 1, P.epi(A3R_EPI_RELU, Hd.h2b));
-            }
-        }
-        if (!fused_tail && !P.skip())
-            P.rc = a3r_head_final(h2, Hd.h4w, Hd.h4b, s ? pts2 : pts1, s ? conf2 : conf1, (long)B * H * W, L, stream);
+        head_stage(P, k, g, v, s);
     }
     if (peak) *peak = ar.peak;
     return P.rc;
@@ -1251,54 +1237,20 @@ int find_distinct(a3r_model_s* m, const float* a1, const float* a2, long words_a
     *use = true;
     return A3R_OK;
 }
-}  // namespace
 
-extern "C" size_t a3r_model_workspace_bytes(a3r_model_t m, int B, int H, int W) {
-    if (!m || B <= 0 || H <= 0 || W <= 0 || H % 16 || W % 16) return 0;
-    // the largest of the plain plan and the plans on distinct inputs: those only shrink stages and reuse idle buffers, largest with
-    // one duplicate (2 B - 1 distinct), of the depth priors alone or of both kinds; and the heads' merged level-0 branch at the
-    // largest number of distinct frames a side is admitted with (head_merge_fits: its buffers grow with that number)
-    size_t need = 0;
-    int u_max = B - 1;
-    while (u_max > 0 && !head_merge_fits(m->cfg, (H / 16) * (W / 16), B, u_max)) u_max--;
-    const int u_side = u_max > 0 && m->map_form == Form::FH2 ? u_max : B;
-    const Distinct cases[4] = {{2 * B, 2 * B, nullptr, nullptr, nullptr, nullptr, {B, B}, {nullptr, nullptr}, {nullptr, nullptr}},
-                               {2 * B, 2 * B - 1, nullptr, nullptr, nullptr, nullptr, {B, B}, {nullptr, nullptr}, {nullptr, nullptr}},
-                               {2 * B - 1, 2 * B - 1, nullptr, nullptr, nullptr, nullptr, {B, B}, {nullptr, nullptr}, {nullptr, nullptr}},
-                               {2 * B, 2 * B, nullptr, nullptr, nullptr, nullptr, {u_side, u_side}, {nullptr, nullptr}, {nullptr, nullptr}}};
-    for (const Distinct& d : cases) {
-        size_t peak = 0;
-        run_plan(m, true, nullptr, nullptr, nullptr, nullptr, B, H, W, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &peak, 0,
-                 nullptr, nullptr, nullptr, &d);
-        if (peak > need) need = peak;
-    }
-    return need;
+// the sizing pass of phase `phase` with the distinct counts d (or none)
+size_t plan_peak(a3r_model_s* m, int phase, int B, int H, int W, const Distinct* d) {
+    Call k;
+    k.phase = phase; k.B = B; k.H = H; k.W = W;
+    k.dry = true;
+    k.dd = d;
+    size_t peak = 0;
+    run_plan(m, k, &peak);
+    return peak;
 }
 
-extern "C" int a3r_model_forward(a3r_model_t m, const float* img1, const float* img2, const float* pd1, const float* pd2,
-                                 int B, int H, int W, float* pts1, float* conf1, float* pts2, float* conf2, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
-    A3R_CHECK_ARG(m, "a3r_model_forward: null handle");
-    if (!m->finalized) {
-        set_error("a3r_model_forward: a3r_model_finalize has not been called");
-        return A3R_ESTATE;
-    }
-    A3R_CHECK_ARG(img1 && img2 && pd1 && pd2 && pts1 && conf1 && pts2 && conf2 && workspace, "a3r_model_forward: null pointer");
-    A3R_CHECK_ARG(B > 0, "a3r_model_forward: batch must be positive");
-    A3R_CHECK_ARG(H > 0 && H % 16 == 0, "Input image height (%d) is not a multiple of patch size (16).", H);
-    A3R_CHECK_ARG(W > 0 && W % 16 == 0, "Input image width (%d) is not a multiple of patch size (16).", W);
-    A3R_CHECK_ARG(H / 16 < a3r_model_s::MAX_POS && W / 16 < a3r_model_s::MAX_POS, "a3r_model_forward: image too large for the RoPE table");
-    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "a3r_model_forward: workspace must be 256-byte aligned");
-    const size_t need_bytes = a3r_model_workspace_bytes(m, B, H, W);
-    A3R_CHECK_ARG(workspace_bytes >= need_bytes, "a3r_model_forward: workspace too small (%zu < %zu)", workspace_bytes, need_bytes);
-    Distinct d;
-    bool merge = false;
-    if (int rc = find_distinct(m, img1, img2, 3L * H * W, true, pd1, pd2, B, H, W, stream, &d, &merge)) return rc;
-    return run_plan(m, false, img1, img2, pd1, pd2, B, H, W, pts1, conf1, pts2, conf2, workspace, workspace_bytes, stream, nullptr, 0,
-                    nullptr, nullptr, nullptr, merge ? &d : nullptr);
-}
-
-static int check_forward_args(a3r_model_t m, int B, int H, int W, const void* workspace, const char* who) {
+// what every entry point that launches a plan checks first
+int check_forward_args(a3r_model_t m, int B, int H, int W, const void* workspace, const char* who) {
     A3R_CHECK_ARG(m, "%s: null handle", who);
     if (!m->finalized) {
         set_error("%s: a3r_model_finalize has not been called", who);
@@ -1312,12 +1264,45 @@ static int check_forward_args(a3r_model_t m, int B, int H, int W, const void* wo
     A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "%s: workspace must be 256-byte aligned", who);
     return A3R_OK;
 }
+}  // namespace
+
+extern "C" size_t a3r_model_workspace_bytes(a3r_model_t m, int B, int H, int W) {
+    if (!m || B <= 0 || H <= 0 || W <= 0 || H % 16 || W % 16) return 0;
+    // the largest of the plain plan and the plans on distinct inputs: those only shrink stages and reuse idle buffers, largest with
+    // one duplicate (2 B - 1 distinct), of the depth priors alone or of both kinds; and the heads' merged level-0 branch at the
+    // largest number of distinct frames a side is admitted with (head_merge_fits: its buffers grow with that number)
+    int u_max = B - 1;
+    while (u_max > 0 && !head_merge_fits(m->cfg, (H / 16) * (W / 16), B, u_max)) u_max--;
+    const int u_side = u_max > 0 && m->map_form == Form::FH2 ? u_max : B;
+    const Distinct cases[4] = {distinct_counts(2 * B, 2 * B, B), distinct_counts(2 * B, 2 * B - 1, B), distinct_counts(2 * B - 1, 2 * B - 1, B),
+                               distinct_counts(2 * B, 2 * B, u_side)};
+    size_t need = 0;
+    for (const Distinct& d : cases) need = std::max(need, plan_peak(m, 0, B, H, W, &d));
+    return need;
+}
+
+extern "C" int a3r_model_forward(a3r_model_t m, const float* img1, const float* img2, const float* pd1, const float* pd2,
+                                 int B, int H, int W, float* pts1, float* conf1, float* pts2, float* conf2, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+    if (int rc = check_forward_args(m, B, H, W, workspace, "a3r_model_forward")) return rc;
+    A3R_CHECK_ARG(img1 && img2 && pd1 && pd2 && pts1 && conf1 && pts2 && conf2, "a3r_model_forward: null pointer");
+    const size_t need_bytes = a3r_model_workspace_bytes(m, B, H, W);
+    A3R_CHECK_ARG(workspace_bytes >= need_bytes, "a3r_model_forward: workspace too small (%zu < %zu)", workspace_bytes, need_bytes);
+    Distinct d;
+    bool merge = false;
+    if (int rc = find_distinct(m, img1, img2, 3L * H * W, true, pd1, pd2, B, H, W, stream, &d, &merge)) return rc;
+    Call k;
+    k.phase = 0; k.B = B; k.H = H; k.W = W;
+    k.img[0] = img1; k.img[1] = img2; k.pd[0] = pd1; k.pd[1] = pd2;
+    k.pts[0] = pts1; k.pts[1] = pts2; k.conf[0] = conf1; k.conf[1] = conf2;
+    k.ws = workspace; k.ws_bytes = workspace_bytes; k.stream = stream;
+    k.dd = merge ? &d : nullptr;
+    return run_plan(m, k);
+}
 
 extern "C" size_t a3r_model_encode_workspace_bytes(a3r_model_t m, int B, int H, int W) {
     if (!m || B <= 0 || H <= 0 || W <= 0 || H % 16 || W % 16) return 0;
-    size_t peak = 0;
-    run_plan(m, true, nullptr, nullptr, nullptr, nullptr, B, H, W, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &peak, 1);
-    return peak;
+    return plan_peak(m, 1, B, H, W, nullptr);
 }
 
 extern "C" int a3r_model_encode(a3r_model_t m, const float* img, int B, int H, int W, float* feat_out, void* workspace,
@@ -1326,8 +1311,11 @@ extern "C" int a3r_model_encode(a3r_model_t m, const float* img, int B, int H, i
     A3R_CHECK_ARG(img && feat_out, "a3r_model_encode: null pointer");
     const size_t need_bytes = a3r_model_encode_workspace_bytes(m, B, H, W);
     A3R_CHECK_ARG(workspace_bytes >= need_bytes, "a3r_model_encode: workspace too small (%zu < %zu)", workspace_bytes, need_bytes);
-    return run_plan(m, false, img, nullptr, nullptr, nullptr, B, H, W, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes,
-                    stream, nullptr, 1, nullptr, nullptr, feat_out);
+    Call k;
+    k.phase = 1; k.B = B; k.H = H; k.W = W;
+    k.img[0] = img; k.feat_out = feat_out;
+    k.ws = workspace; k.ws_bytes = workspace_bytes; k.stream = stream;
+    return run_plan(m, k);
 }
 
 extern "C" int a3r_model_decode(a3r_model_t m, const float* feat1, const float* feat2, const float* pd1, const float* pd2, int B,
@@ -1344,10 +1332,14 @@ extern "C" int a3r_model_decode(a3r_model_t m, const float* feat1, const float* 
     const long words_f = (long)(H / 16) * (W / 16) * m->cfg.enc_embed_dim;
     if (int rc = find_distinct(m, look ? feat1 : nullptr, look ? feat2 : nullptr, words_f, false, pd1, pd2, B, H, W, stream, &d, &merge))
         return rc;
-    return run_plan(m, false, nullptr, nullptr, pd1, pd2, B, H, W, pts1, conf1, pts2, conf2, workspace, workspace_bytes, stream,
-                    nullptr, 2, feat1, feat2, nullptr, merge ? &d : nullptr);
+    Call k;
+    k.phase = 2; k.B = B; k.H = H; k.W = W;
+    k.feat_in[0] = feat1; k.feat_in[1] = feat2; k.pd[0] = pd1; k.pd[1] = pd2;
+    k.pts[0] = pts1; k.pts[1] = pts2; k.conf[0] = conf1; k.conf[1] = conf2;
+    k.ws = workspace; k.ws_bytes = workspace_bytes; k.stream = stream;
+    k.dd = merge ? &d : nullptr;
+    return run_plan(m, k);
 }
-
 extern "C" int a3r_model_set_dedup(a3r_model_t m, int mode) {
     A3R_CHECK_ARG(m && mode >= 0 && mode <= 2, "a3r_model_set_dedup: mode must be 0 (off), 1 (on) or 2 (constant key)");
     m->dedup_mode = mode;
