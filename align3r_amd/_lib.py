@@ -157,6 +157,9 @@ SIGNATURES = {
     "a3r_mask_gt": (C.c_int, [c_void, C.c_float, c_void, C.c_long, c_void]),
     "a3r_upsample2x_fh2": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_void, c_void]),
     "a3r_combine_resid_fh2": (C.c_int, [c_void, c_void, c_void, c_void, c_void, c_void, C.c_int, C.c_long, C.c_int, C.c_float, c_void, c_void]),
+    "a3r_upsample2x_combine_fh2": (C.c_int, [c_void, c_void, c_void, c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_float, c_void, c_void]),
+    "a3r_upsample2x_set_form": (C.c_int, [C.c_int]),
     "a3r_conv3x3_fh2": (C.c_int, [c_void, c_void, C.c_float, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Epilogue), c_void]),
     "a3r_head_final": (C.c_int, [c_void, c_void, c_void, c_void, c_void, C.c_long, C.c_int, c_void]),
     "a3r_model_create": (C.c_int, [C.POINTER(ModelConfigC), C.POINTER(c_void)]),

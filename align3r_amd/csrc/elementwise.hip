@@ -5,8 +5,10 @@
 #include "bf3.h"
 #include "fh2.h"
 #include "dedup.h"
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 
 namespace a3r {
 
@@ -344,6 +346,21 @@ __device__ __forceinline__ f32x4 bilerp4(f32x4 v00, f32x4 v01, f32x4 v10, f32x4 
     return o;
 }
 
+// One axis of the map for output index o of 2 n: the two source indices and their weights.  Every operation is spelled out, the
+// fused o * s - i0 of the second weight included, so that every kernel form below rounds the weights the same way.
+struct UpAxis { int i0, i1; float l0, l1; };
+__device__ __forceinline__ float up_scale(int n) { return (2 * n > 1) ? __fdiv_rn((float)(n - 1), (float)(2 * n - 1)) : 0.f; }
+__device__ __forceinline__ UpAxis up_axis(float s, int o, int n) {
+    const float fo = (float)o;
+    int i0 = (int)__fmul_rn(s, fo);
+    i0 = i0 < n - 1 ? i0 : n - 1;
+    const int i1 = i0 < n - 1 ? i0 + 1 : i0;
+    const float l1 = __fmaf_rn(s, fo, -(float)i0);
+    return UpAxis{i0, i1, __fsub_rn(1.f, l1), l1};
+}
+
+// ---- first form (A3R_UP_FORM=v1): one output pixel per thread and step, four corners fetched per output.  The reference of the
+// second form below.
 // FMT 0: fp32, 1: bf3, 2: fh2 output.  Grid: x over (output column, channel group) of one output row, y over (batch, output row):
 // the row / batch decomposition is scalar work once per workgroup and a thread does ONE 32-bit division (the first version took
 // three 64-bit divisions by runtime values per thread).  A thread produces 4 channels (fp32 / bf3) or 8 channels (fh2: the two
@@ -353,8 +370,7 @@ template <int FMT>
 __global__ __launch_bounds__(256) void upsample2x_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int H, int W, int C4,
                                                          int Hc, int Wc, float scale, unsigned* __restrict__ absmax) {
     constexpr int Q = FMT == 2 ? 2 : 1;                        // float4 per thread
-    const float sh = (2 * H > 1) ? (float)(H - 1) / (float)(2 * H - 1) : 0.f;
-    const float sw = (2 * W > 1) ? (float)(W - 1) / (float)(2 * W - 1) : 0.f;
+    const float sh = up_scale(H), sw = up_scale(W);
     const f32x4* xv = reinterpret_cast<const f32x4*>(x);
     f32x4* yv = reinterpret_cast<f32x4*>(y);
     const unsigned CG = (unsigned)C4 / Q;                      // channel groups per pixel
@@ -362,19 +378,15 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const float* __restrict
     const unsigned ox = idx / CG, c = (idx - ox * CG) * Q;     // c: first float4 of this thread
     const bool live = ox < (unsigned)Wc;                     // (no early return in the fh2 form: the range statistics need every lane at the end)
     if (FMT != 2 && !live) return;
-    const float fx = sw * (float)ox;
-    int x0 = (int)fx;
-    x0 = x0 < W - 1 ? x0 : W - 1;
-    const int x1 = x0 < W - 1 ? x0 + 1 : x0;
-    const float lx1 = fx - (float)x0, lx0 = 1.f - lx1;
+    const UpAxis ax = up_axis(sw, (int)ox, W);
+    const int x0 = ax.i0, x1 = ax.i1;
+    const float lx0 = ax.l0, lx1 = ax.l1;
     float amax = 0.f;
     for (int row = blockIdx.y; live && row < B * Hc; row += gridDim.y) {   // (batch, output row): uniform per workgroup
         const int b = row / Hc, oy = row - b * Hc;
-        const float fy = sh * (float)oy;
-        int y0 = (int)fy;
-        y0 = y0 < H - 1 ? y0 : H - 1;
-        const int y1 = y0 < H - 1 ? y0 + 1 : y0;
-        const float ly1 = fy - (float)y0, ly0 = 1.f - ly1;
+        const UpAxis ay = up_axis(sh, oy, H);
+        const int y0 = ay.i0, y1 = ay.i1;
+        const float ly0 = ay.l0, ly1 = ay.l1;
         const long rb = (long)b * H;
         const f32x4* r0 = xv + (rb + y0) * W * C4 + c;
         const f32x4* r1 = xv + (rb + y1) * W * C4 + c;
@@ -403,26 +415,21 @@ __global__ __launch_bounds__(256) void upsample2x_combine_kernel(const float* __
                                                                  const float* __restrict__ r0, const int* __restrict__ map,
                                                                  float* __restrict__ s, char* __restrict__ sr2, int B, int H, int W, int C4,
                                                                  int Hc, int Wc, float scale, unsigned* __restrict__ absmax) {
-    const float sh = (2 * H > 1) ? (float)(H - 1) / (float)(2 * H - 1) : 0.f;
-    const float sw = (2 * W > 1) ? (float)(W - 1) / (float)(2 * W - 1) : 0.f;
+    const float sh = up_scale(H), sw = up_scale(W);
     const f32x4* xv = reinterpret_cast<const f32x4*>(x);
     const unsigned CG = (unsigned)C4 / 2;                      // channel groups (of 8) per pixel
     const unsigned idx = blockIdx.x * 256u + threadIdx.x;
     const unsigned ox = idx / CG, cg = (idx - ox * CG) * 2;    // cg: first float4 of this thread
     const bool live = ox < (unsigned)Wc;                     // (no early return: the range statistics need every lane at the end)
-    const float fx = sw * (float)ox;
-    int x0 = (int)fx;
-    x0 = x0 < W - 1 ? x0 : W - 1;
-    const int x1 = x0 < W - 1 ? x0 + 1 : x0;
-    const float lx1 = fx - (float)x0, lx0 = 1.f - lx1;
+    const UpAxis ax = up_axis(sw, (int)ox, W);
+    const int x0 = ax.i0, x1 = ax.i1;
+    const float lx0 = ax.l0, lx1 = ax.l1;
     float amax = 0.f;
     for (int row = blockIdx.y; live && row < B * Hc; row += gridDim.y) {   // (slot, output row): uniform per workgroup
         const int b = row / Hc, oy = row - b * Hc;
-        const float fy = sh * (float)oy;
-        int y0 = (int)fy;
-        y0 = y0 < H - 1 ? y0 : H - 1;
-        const int y1 = y0 < H - 1 ? y0 + 1 : y0;
-        const float ly1 = fy - (float)y0, ly0 = 1.f - ly1;
+        const UpAxis ay = up_axis(sh, oy, H);
+        const int y0 = ay.i0, y1 = ay.i1;
+        const float ly0 = ay.l0, ly1 = ay.l1;
         const long rb = (long)b * H;
         const f32x4* q0 = xv + (rb + y0) * W * C4 + cg;
         const f32x4* q1 = xv + (rb + y1) * W * C4 + cg;
@@ -441,6 +448,91 @@ __global__ __launch_bounds__(256) void upsample2x_combine_kernel(const float* __
     __shared__ unsigned s_red[4];
     fh2_publish_block(absmax, amax, s_red);
 }
+
+// ---- second form (default): a thread makes the 2 x 2 output pixels (2 kb - 1, 2 kb) x (2 jb - 1, 2 jb) of its channel group.  With
+// align_corners=True these four share their source rows (kb - 1, kb) and columns (jb - 1, jb), so the four corners are fetched ONCE
+// for four outputs: 2 sixteen-byte loads per 32-byte store where the first form issues 8, which is what bounds it (every input
+// element requested 16 times: the texture-address path, not HBM).  Whether an output really has the corners of its block's first
+// output is decided from ITS OWN up_axis, and one that has not (fp32 rounding of the source coordinate on a very large map)
+// fetches its corners as the first form does: indices, weights and bilerp4 are the first form's for every output, bit for bit.
+// The output beyond an edge of the window (-1, Hc, Wc) is skipped and lends its axis to its neighbour.
+// FMT 0: fp32 (4 channels per thread), 2: fh2 (8 channels), 3: fh2 combine (upsample2x_combine_kernel; y = sr2).
+template <int FMT>
+__global__ __launch_bounds__(256) void upsample2x_block_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ c,
+                                                               const float* __restrict__ r0, const int* __restrict__ map,
+                                                               float* __restrict__ s, int B, int H, int W, int C4, int Hc, int Wc,
+                                                               float scale, unsigned* __restrict__ absmax) {
+    constexpr int Q = FMT == 0 ? 1 : 2;                        // float4 per thread
+    const float sh = up_scale(H), sw = up_scale(W);
+    const int NKB = Hc / 2 + 1, NJB = Wc / 2 + 1;              // blocks per map column / row
+    const unsigned CG = (unsigned)C4 / Q;
+    const unsigned idx = blockIdx.x * 256u + threadIdx.x;
+    const unsigned jb = idx / CG;
+    const int cq = (int)(idx - jb * CG) * Q;                   // first float4 of this thread
+    const bool live = jb < (unsigned)NJB;                      // (no early return: the range statistics need every lane at the end)
+    const int ox[2] = {2 * (int)jb - 1, 2 * (int)jb};
+    const bool vx[2] = {ox[0] >= 0, ox[1] < Wc};
+    const UpAxis ax[2] = {up_axis(sw, vx[0] ? ox[0] : ox[1], W), up_axis(sw, vx[1] ? ox[1] : ox[0], W)};
+    const bool same_x = ax[1].i0 == ax[0].i0 && ax[1].i1 == ax[0].i1;
+    float amax = 0.f;
+    for (int rb = blockIdx.y; live && rb < B * NKB; rb += gridDim.y) {     // (batch, block row): uniform per workgroup
+        const int b = rb / NKB, kb = rb - b * NKB;
+        const int oy[2] = {2 * kb - 1, 2 * kb};
+        const bool vy[2] = {oy[0] >= 0, oy[1] < Hc};
+        const UpAxis ay[2] = {up_axis(sh, vy[0] ? oy[0] : oy[1], H), up_axis(sh, vy[1] ? oy[1] : oy[0], H)};
+        const bool same = same_x && ay[1].i0 == ay[0].i0 && ay[1].i1 == ay[0].i1;
+        const f32x4* img = reinterpret_cast<const f32x4*>(x) + (long)b * H * W * C4 + cq;
+        auto corner = [&](int yi, int xi, int q) { return img[((long)yi * W + xi) * C4 + q]; };
+        f32x4 v00[Q], v01[Q], v10[Q], v11[Q];                  // the corners of output (0, 0) of the block
+#pragma unroll
+        for (int q = 0; q < Q; q++) {
+            v00[q] = corner(ay[0].i0, ax[0].i0, q);
+            v01[q] = corner(ay[0].i0, ax[0].i1, q);
+            v10[q] = corner(ay[0].i1, ax[0].i0, q);
+            v11[q] = corner(ay[0].i1, ax[0].i1, q);
+        }
+#pragma unroll
+        for (int r = 0; r < 2; r++)
+#pragma unroll
+            for (int t = 0; t < 2; t++) {
+                if (!(vy[r] && vx[t])) continue;
+                const UpAxis &Y = ay[r], &X = ax[t];
+                f32x4 o[Q];
+                if ((r == 0 && t == 0) || same) {
+#pragma unroll
+                    for (int q = 0; q < Q; q++) o[q] = bilerp4(v00[q], v01[q], v10[q], v11[q], X.l0, X.l1, Y.l0, Y.l1);
+                } else {
+#pragma unroll
+                    for (int q = 0; q < Q; q++)
+                        o[q] = bilerp4(corner(Y.i0, X.i0, q), corner(Y.i0, X.i1, q), corner(Y.i1, X.i0, q), corner(Y.i1, X.i1, q), X.l0, X.l1,
+                                       Y.l0, Y.l1);
+                }
+                const long pix = ((long)b * Hc + oy[r]) * Wc + ox[t];
+                if (FMT == 0) reinterpret_cast<f32x4*>(y)[pix * C4 + cq] = o[0];
+                else {
+                    if (FMT == 3) {
+                        const long src = (((long)map[b] * Hc + oy[r]) * Wc + ox[t]) * C4 + cq;
+#pragma unroll
+                        for (int q = 0; q < Q; q++) {
+                            const f32x4 w = reinterpret_cast<const f32x4*>(c)[src + q] + (reinterpret_cast<const f32x4*>(r0)[src + q] + o[q]);
+                            reinterpret_cast<f32x4*>(s)[pix * C4 + cq + q] = w;
+                            o[q] = f32x4{fmaxf(w.x, 0.f), fmaxf(w.y, 0.f), fmaxf(w.z, 0.f), fmaxf(w.w, 0.f)};
+                        }
+                    }
+                    const f32x4 lo = o[0] * scale, hi = o[Q - 1] * scale;
+                    amax = fh2_amax4(fh2_amax4(amax, lo), hi);
+                    fh2_store8(reinterpret_cast<char*>(y) + pix * ((size_t)C4 * 16), cq * 4, lo, hi);
+                }
+            }
+    }
+    if (FMT != 0) {
+        __shared__ unsigned s_red[4];
+        fh2_publish_block(absmax, amax, s_red);
+    }
+}
+
+// which form the fp32, fh2 and combine entry points launch: 2 (default) or 1 (A3R_UP_FORM=v1 / a3r_upsample2x_set_form)
+static std::atomic<int> g_up_form{(getenv("A3R_UP_FORM") && !strcmp(getenv("A3R_UP_FORM"), "v1")) ? 1 : 2};
 
 // ------------------------------------------------------------------------------------------- head final
 // conv1x1 C -> 4 (+bias) then postprocess (postprocess.py:10-58). 32 lanes per pixel (C == 128: one float4 each).
@@ -775,13 +867,33 @@ static inline dim3 upsample_grid(int B, int Hc, int Wc, int groups) {      // gr
     return dim3((unsigned)(((long)Wc * groups + 255) / 256), (unsigned)(rows < 65535 ? rows : 65535));
 }
 
+// the second form's grid: x over (block column, channel group), y over (batch, block row); a workgroup of the fh2 forms loops over
+// ~`rows` block rows and publishes one statistics atomic.  Measured on the headline's maps (tools/bench_up2x.py, one session, rows
+// 1 / 2 / 3 / 4 / 8 / 16): fh2 [42, 192, 256, 128] 1644 / 1153 / 1179 / 1216 / 1291 / 1339 us, fh2 [42, 96, 128, 256] 829 / 616 / 634 / 639 /
+// 662 / 685 us -- one block row per workgroup is 140 000 atomics on one word, many rows are a serial chain of load, compute, store
+// per wave at 5 waves per SIMD; combine [42 <- 15, 48, 64, 256] 430 / 431 / 413 / 412 / 415 / 464 us.
+static inline dim3 upsample_block_grid(int B, int Hc, int Wc, int groups, unsigned rows) {
+    dim3 grid = upsample_grid(B, Hc / 2 + 1, Wc / 2 + 1, groups);
+    grid.y = (grid.y + rows - 1) / rows;
+    return grid;
+}
+
+extern "C" int a3r_upsample2x_set_form(int form) {
+    A3R_CHECK_ARG(form == 1 || form == 2, "a3r_upsample2x_set_form: form must be 1 or 2");
+    return g_up_form.exchange(form);
+}
+
 extern "C" int a3r_upsample2x(const float* x, float* y, int B, int H, int W, int C, int Hc, int Wc, void* stream) {
     A3R_CHECK_ARG(x && y, "a3r_upsample2x: null pointer");
     A3R_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "a3r_upsample2x: bad shape");
     A3R_CHECK_ARG(Hc > 0 && Hc <= 2 * H && Wc > 0 && Wc <= 2 * W, "a3r_upsample2x: crop window larger than the 2x map");
     const long total = (long)B * Hc * Wc * (C / 4);
     ProfScope prof(PK_ELEMENTWISE, 16.0 * total + 4.0 * B * H * W * C, as_stream(stream));
-    hipLaunchKernelGGL(upsample2x_kernel<0>, upsample_grid(B, Hc, Wc, C / 4), dim3(256), 0, as_stream(stream), x, y, B, H, W, C / 4, Hc, Wc, 1.f, nullptr);
+    if (g_up_form.load() == 1)
+        hipLaunchKernelGGL(upsample2x_kernel<0>, upsample_grid(B, Hc, Wc, C / 4), dim3(256), 0, as_stream(stream), x, y, B, H, W, C / 4, Hc, Wc, 1.f, nullptr);
+    else
+        hipLaunchKernelGGL(upsample2x_block_kernel<0>, upsample_block_grid(B, Hc, Wc, C / 4, 1), dim3(256), 0, as_stream(stream), x, y,
+                           nullptr, nullptr, nullptr, nullptr, B, H, W, C / 4, Hc, Wc, 1.f, nullptr);
     A3R_LAUNCH_CHECK();
     return A3R_OK;
 }
@@ -806,6 +918,12 @@ extern "C" int a3r_upsample2x_fh2(const float* x, void* y2, int B, int H, int W,
     A3R_CHECK_ARG(Hc > 0 && Hc <= 2 * H && Wc > 0 && Wc <= 2 * W, "a3r_upsample2x_fh2: crop window larger than the 2x map");
     const long total = (long)B * Hc * Wc * (C / 4);
     ProfScope prof(PK_ELEMENTWISE, 16.0 * total + 4.0 * B * H * W * C, as_stream(stream));
+    if (g_up_form.load() != 1) {
+        hipLaunchKernelGGL(upsample2x_block_kernel<2>, upsample_block_grid(B, Hc, Wc, C / 8, 2), dim3(256), 0, as_stream(stream), x,
+                           static_cast<float*>(y2), nullptr, nullptr, nullptr, nullptr, B, H, W, C / 4, Hc, Wc, scale, absmax);
+        A3R_LAUNCH_CHECK();
+        return A3R_OK;
+    }
     dim3 grid = upsample_grid(B, Hc, Wc, C / 8);
     // every workgroup loops over ~8 rows and publishes ONE statistics atomic (a long per-thread loop of dependent row loads is
     // latency-bound: 63 rows per workgroup cost +15 % on the full-resolution map; one row per workgroup is half a million atomics)
@@ -828,6 +946,12 @@ int a3r::upsample2x_combine_fh2(const float* x, const float* c, const float* r0,
                   "upsample2x_combine_fh2: buffers must be 16-byte aligned");
     const long total = (long)B * Hc * Wc * (C / 4);
     ProfScope prof(PK_ELEMENTWISE, 40.0 * total + 4.0 * B * H * W * C, as_stream(stream));
+    if (g_up_form.load() != 1) {
+        hipLaunchKernelGGL(upsample2x_block_kernel<3>, upsample_block_grid(B, Hc, Wc, C / 8, 4), dim3(256), 0, as_stream(stream), x,
+                           static_cast<float*>(sr2), c, r0, map, s, B, H, W, C / 4, Hc, Wc, scale, absmax);
+        A3R_LAUNCH_CHECK();
+        return A3R_OK;
+    }
     dim3 grid = upsample_grid(B, Hc, Wc, C / 8);
     const unsigned ycap = (grid.y + 7) / 8;                   // as a3r_upsample2x_fh2: ~8 rows and one statistics atomic per workgroup
     if (grid.y > ycap) grid.y = ycap;
@@ -835,6 +959,11 @@ int a3r::upsample2x_combine_fh2(const float* x, const float* c, const float* r0,
                        C / 4, Hc, Wc, scale, absmax);
     A3R_LAUNCH_CHECK();
     return A3R_OK;
+}
+
+extern "C" int a3r_upsample2x_combine_fh2(const float* x, const float* c, const float* r0, const int32_t* map, float* s, void* sr2, int S,
+                                          int H, int W, int C, int Hc, int Wc, float scale, unsigned* absmax, void* stream) {
+    return a3r::upsample2x_combine_fh2(x, c, r0, map, s, sr2, S, H, W, C, Hc, Wc, scale, absmax, stream);
 }
 
 extern "C" int a3r_head_final(const float* x, const float* w, const float* b, float* pts3d, float* conf, long P, int C,

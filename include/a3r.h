@@ -360,6 +360,14 @@ int a3r_upsample2x_fh2(const float* x, void* y2, int B, int H, int W, int C, int
  * S P < 2^31, 16-byte aligned buffers. */
 int a3r_combine_resid_fh2(const float* c, const float* r0, const float* p2, const int32_t* map, float* s, void* sr2, int S, long P,
                           int C, float scale, unsigned* absmax, void* stream);
+/* the same with p2 = a3r_upsample2x(x [S, H, W, C], window Hc x Wc) made inside the kernel and never written; P = Hc Wc */
+int a3r_upsample2x_combine_fh2(const float* x, const float* c, const float* r0, const int32_t* map, float* s, void* sr2, int S, int H,
+                               int W, int C, int Hc, int Wc, float scale, unsigned* absmax, void* stream);
+/* Kernel form behind a3r_upsample2x, a3r_upsample2x_fh2 and a3r_upsample2x_combine_fh2: 2 (default: a thread makes 2 x 2 output
+ * pixels from corners fetched once) or 1 (four corners fetched per output pixel); the results are bitwise equal
+ * (tests/test_gpu_up2x_forms.py).  Returns the previous form, or a negative error code.  Process-wide; environment A3R_UP_FORM=v1
+ * selects form 1 at start-up.  A development switch, not part of the reference's interface. */
+int a3r_upsample2x_set_form(int form);
 
 /* last 1x1 conv (128 -> 4) + postprocess (dpt_block.py:329, postprocess.py:10-58):
  * x [P, C] -> pts3d [P, 3] = xyz/max(|xyz|,1e-8)*expm1(|xyz|), conf [P] = 1 + exp(c). */
