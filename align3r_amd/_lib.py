@@ -178,6 +178,11 @@ SIGNATURES = {
     "a3r_model_last_dedup": (C.c_int, [c_void, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "a3r_model_set_dedup_head": (C.c_int, [c_void, C.c_int]),
     "a3r_model_last_dedup_sides": (C.c_int, [c_void, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "a3r_model_set_dedup_decoder": (C.c_int, [c_void, C.c_int]),
+    "a3r_model_last_dedup_entries": (C.c_int, [c_void, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "a3r_attention_fh2_mapped": (C.c_int, [c_void, C.c_int, c_void, C.c_int, c_void, C.c_int, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.POINTER(Fh2AttnRange), c_void, c_void, c_void]),
+    "a3r_gather_add_rows": (C.c_int, [c_void, c_void, c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, c_void]),
     "a3r_model_range_check": (C.c_int, [c_void, c_void, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "a3r_model_reset_ranges": (C.c_int, [c_void]),
     "a3r_model_range_stats": (C.c_int, [c_void, c_void, c_void, C.c_int, C.POINTER(C.c_int)]),

@@ -13,6 +13,7 @@
 // 53 KB per workgroup, so THREE workgroups of 4 waves share a CU.
 #include "common.h"
 #include "fh2.h"
+#include "dedup.h"
 #include <cmath>
 #include <atomic>
 #include <cstdlib>
@@ -43,6 +44,9 @@ struct Attn4Args {
     float scale_log2e;                      // hd^-0.5 log2(e) / (q_scale k_scale): the exp2 argument's factor on the raw scores
     float out_mul;                          // out_scale / v_scale, applied with the softmax normaliser
     unsigned* out_absmax;                   // range statistics of the stored output (fh2.h), or null
+    // a3r_attention_fh2_mapped (attn_fh2_v2_kernel only): batch b reads the q rows of image q_map[b] and the k / v rows of image
+    // kv_map[b] (device, B words each; null: image b) and writes the o rows of image b
+    const int *q_map, *kv_map;
 };
 
 typedef const __attribute__((address_space(1))) void* a4_gptr;
@@ -289,9 +293,10 @@ __global__ __launch_bounds__(A4T, 3) void attn_fh2_v2_kernel(Attn4Args a) {
     const int q_row = qb * A4Q + wave * 32 + qi;
     const int q_ld = q_row < a.Nq ? q_row : a.Nq - 1;
 
+    const int bq = a.q_map ? a.q_map[b] : b, bkv = a.kv_map ? a.kv_map[b] : b;      // uniform
     f16x8 qf[4][NPL];
     {
-        const char* qp = a.q + ((size_t)b * a.Nq + q_ld) * a.pq + h * 256;
+        const char* qp = a.q + ((size_t)bq * a.Nq + q_ld) * a.pq + h * 256;
 #pragma unroll
         for (int s = 0; s < 4; s++)
 #pragma unroll
@@ -301,8 +306,8 @@ __global__ __launch_bounds__(A4T, 3) void attn_fh2_v2_kernel(Attn4Args a) {
     const int drow = tid >> 4;
     const int dch = (tid & 15) ^ b4_swz(drow);                         // logical chunk this thread fetches
     const int dsrc = ((dch & 7) * 2 + (dch >> 3)) * 16;                // its byte offset in the fh2 row slice of the head
-    const char* kbase = a.k + (size_t)b * a.Nk * a.pk + h * 256 + dsrc;
-    const char* vbase = a.v + (size_t)b * a.Nk * a.pv + h * 256 + dsrc;
+    const char* kbase = a.k + (size_t)bkv * a.Nk * a.pk + h * 256 + dsrc;
+    const char* vbase = a.v + (size_t)bkv * a.Nk * a.pv + h * 256 + dsrc;
     auto issue = [&](const char* base, size_t pitch, int k0, char* buf) {
         char* dst = buf + wave * 1024;
 #pragma unroll
@@ -480,8 +485,25 @@ extern "C" int a3r_attention_fh2_set_form(int form) {
     return g_attn_form.exchange(form) ;
 }
 
+bool a3r::attention_fh2_takes_maps() { return g_attn_form.load(std::memory_order_relaxed) == 2 || fh2_passes() != 3; }
+
+static int attention_fh2_launch(const void* q2, int ldq, const void* k2, int ldk, const void* v2, int ldv, void* o2, int ldo, int B, int H,
+                                int Nq, int Nk, const a3r_fh2_attn_range* range, const int32_t* q_map, const int32_t* kv_map, void* stream);
+
 extern "C" int a3r_attention_fh2(const void* q2, int ldq, const void* k2, int ldk, const void* v2, int ldv, void* o2, int ldo,
                                  int B, int H, int Nq, int Nk, const a3r_fh2_attn_range* range, void* stream) {
+    return attention_fh2_launch(q2, ldq, k2, ldk, v2, ldv, o2, ldo, B, H, Nq, Nk, range, nullptr, nullptr, stream);
+}
+
+extern "C" int a3r_attention_fh2_mapped(const void* q2, int ldq, const void* k2, int ldk, const void* v2, int ldv, void* o2, int ldo,
+                                        int B, int H, int Nq, int Nk, const a3r_fh2_attn_range* range, const int32_t* q_map,
+                                        const int32_t* kv_map, void* stream) {
+    A3R_CHECK_ARG((!q_map && !kv_map) || attention_fh2_takes_maps(), "a3r_attention_fh2_mapped: kernel form 1 takes no image maps");
+    return attention_fh2_launch(q2, ldq, k2, ldk, v2, ldv, o2, ldo, B, H, Nq, Nk, range, q_map, kv_map, stream);
+}
+
+static int attention_fh2_launch(const void* q2, int ldq, const void* k2, int ldk, const void* v2, int ldv, void* o2, int ldo, int B, int H,
+                                int Nq, int Nk, const a3r_fh2_attn_range* range, const int32_t* q_map, const int32_t* kv_map, void* stream) {
     A3R_CHECK_ARG(q2 && k2 && v2 && o2, "a3r_attention_fh2: null pointer");
     a3r_fh2_attn_range r = range ? *range : a3r_fh2_attn_range{};
     float* rs[4] = {&r.q_scale, &r.k_scale, &r.v_scale, &r.out_scale};
@@ -504,7 +526,7 @@ extern "C" int a3r_attention_fh2(const void* q2, int ldq, const void* k2, int ld
     }));
     Attn4Args a = {static_cast<const char*>(q2), static_cast<const char*>(k2), static_cast<const char*>(v2), static_cast<char*>(o2),
                    (size_t)ldq * 4, (size_t)ldk * 4, (size_t)ldv * 4, (size_t)ldo * 4, B, H, Nq, Nk,
-                   0.125f * 1.4426950408889634f / (r.q_scale * r.k_scale), r.out_scale / r.v_scale, r.out_absmax};
+                   0.125f * 1.4426950408889634f / (r.q_scale * r.k_scale), r.out_scale / r.v_scale, r.out_absmax, q_map, kv_map};
     const int nqb = (Nq + A4Q - 1) / A4Q, groups = B * H;
     dim3 grid(8 * ((groups + 7) / 8) * nqb);
     ProfScope prof(PK_ATTENTION_FH2, 4.0 * B * H * (double)Nq * Nk * 64, as_stream(stream));

@@ -48,6 +48,34 @@ inline int dedup_group_side(const int32_t* rep, int B, int s, int32_t* uniq, int
     return U;
 }
 
+// Entries.  map_img / map_pd [2 B] are dedup_group's maps of the two kinds: the row of every slot's image / depth prior among the
+// distinct ones.  What the decoder computes before its first cross-attention product depends on the slot's (image, prior) pair --
+// its entry -- and on its side.  For side s (slots [s B, (s + 1) B)) writes the distinct entries to ent[s B + e], e < U[s], each as
+// the FIRST SLOT OF THAT SIDE holding it (ascending; the representatives of its image and prior may sit on the other side), and the
+// entry of slot b of the side to map_e[s B + b] (map_e[ent[s B + e]] == e).  Both lists are then padded to Um = max(U[0], U[1]) by
+// repeating the side's last entry, so that grouped launches keep one row count and compute copies of real rows only.  Returns Um,
+// or -1 when a row is outside 0 .. 2 B - 1 or an argument is missing.
+inline int dedup_group_entries(const int32_t* map_img, const int32_t* map_pd, int B, int32_t* ent, int32_t* map_e, int* U) {
+    if (!map_img || !map_pd || !ent || !map_e || !U || B <= 0) return -1;
+    for (int i = 0; i < 2 * B; i++)
+        if (map_img[i] < 0 || map_img[i] >= 2 * B || map_pd[i] < 0 || map_pd[i] >= 2 * B) return -1;
+    for (int s = 0; s < 2; s++) {
+        const int base = s * B;
+        int u = 0;
+        for (int b = 0; b < B; b++) {
+            int e = 0;
+            while (e < u && (map_img[ent[base + e]] != map_img[base + b] || map_pd[ent[base + e]] != map_pd[base + b])) e++;
+            if (e == u) ent[base + u++] = base + b;
+            map_e[base + b] = e;
+        }
+        U[s] = u;
+    }
+    const int Um = U[0] > U[1] ? U[0] : U[1];
+    for (int s = 0; s < 2; s++)
+        for (int e = U[s]; e < Um; e++) ent[s * B + e] = ent[s * B + U[s] - 1];
+    return Um;
+}
+
 // ---- device side (dedup.hip).  An item of the first kind is one image [3, H, W] -- or, for the decode call, one frame's encoder
 // features [N, E] --, one of the second kind a pred_depth map [H, W, 3]: words_a / words_pd 32-bit words each, multiples of 4.  Slot s < 4 B of a call is item s % B of group s / B, the groups being img1, img2, pd1, pd2; slots 0 .. 2 B - 1
 // are the image kind, 2 B .. 4 B - 1 the depth-prior kind, and a representative is looked for inside a slot's own kind only.
@@ -67,6 +95,8 @@ int patchify_indexed(const float* img_a, const float* img_b, const int32_t* uniq
                      long sc, long sy, long sx, void* stream);
 // dst[(s * N + n) * C + c] = src[(map[s] * N + n) * C + c] for the slots s < S (map on the device); C a multiple of 4
 int gather_rows(const float* src, float* dst, const int32_t* map, int S, int N, int C, void* stream);
+// whether a3r_attention_fh2_mapped runs the kernel form that takes image maps (attention_fh2.hip; not under A3R_ATTN=v1)
+bool attention_fh2_takes_maps();
 // The second conv of refinenet1.resConfUnit1 on distinct frames (a3r.h: a3r_combine_resid_fh2 is the same with a C signature)
 int combine_resid_fh2(const float* c, const float* r0, const float* p2, const int32_t* map, float* s, void* sr2, int S, long P, int C,
                       float scale, unsigned* absmax, void* stream);

@@ -291,6 +291,20 @@ __global__ void gather_rows_kernel(const f32x4* __restrict__ src, f32x4* __restr
     }
 }
 
+// the residual add of a linear that ran on distinct items only: dst row block s = a[map_a[s]] + b[map_b[s]], or with b null
+// dst[s] + a[map_a[s]] in place (fp32 addition commutes: either order is the RESID epilogue's sum)
+__global__ void gather_add_rows_kernel(const f32x4* __restrict__ a, const int* __restrict__ map_a, const f32x4* __restrict__ b,
+                                       const int* __restrict__ map_b, f32x4* dst, int S, long NC4) {
+    const long total = (long)S * NC4;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int s = (int)(i / NC4);
+        const long r = i - s * NC4;
+        const f32x4 va = a[(long)map_a[s] * NC4 + r];
+        const f32x4 vb = b ? b[(long)map_b[s] * NC4 + r] : dst[i];
+        dst[i] = va + vb;
+    }
+}
+
 // ------------------------------------------------------------------------------------------- residual combine on distinct frames
 // What the RESID2 epilogue of refinenet1.resConfUnit1's second conv produces, when that conv (and the skip it adds) ran on the U
 // distinct frames of a side only (dedup.h): for slot b < S with k = map[b], per pixel row and channel
@@ -835,6 +849,20 @@ int a3r::gather_rows(const float* src, float* dst, const int32_t* map, int S, in
     ProfScope prof(PK_ELEMENTWISE, 32.0 * total, as_stream(stream));
     hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), reinterpret_cast<const f32x4*>(src),
                        reinterpret_cast<f32x4*>(dst), map, S, NC4);
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+extern "C" int a3r_gather_add_rows(const float* a, const int32_t* map_a, const float* b, const int32_t* map_b, float* dst, int S, int N,
+                                   int C, void* stream) {
+    A3R_CHECK_ARG(a && map_a && dst && (!b || map_b), "a3r_gather_add_rows: null pointer");
+    A3R_CHECK_ARG(S > 0 && N > 0 && C > 0 && C % 4 == 0, "a3r_gather_add_rows: bad shape");
+    A3R_CHECK_ARG(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0,
+                  "a3r_gather_add_rows: buffers must be 16-byte aligned");
+    const long NC4 = (long)N * (C / 4), total = (long)S * NC4;
+    ProfScope prof(PK_ELEMENTWISE, 48.0 * total, as_stream(stream));
+    hipLaunchKernelGGL(gather_add_rows_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), reinterpret_cast<const f32x4*>(a),
+                       map_a, reinterpret_cast<const f32x4*>(b), map_b, reinterpret_cast<f32x4*>(dst), S, NC4);
     A3R_LAUNCH_CHECK();
     return A3R_OK;
 }

@@ -74,6 +74,9 @@ struct a3r_model_s {
     int dedup_head = 1;
     int dedup_head_fold = 1;         // A/B switch (A3R_DEDUP_HEAD_FOLD=0): 0 = the combine runs as a pass of its own after the 2x up-sample
     int last_side_unique[2] = {0, 0}, last_side_merged[2] = {0, 0};      // a3r_model_last_dedup_sides
+    // a3r_model_set_dedup_decoder: decoder_embed, the zero-convs and block 0's frame-only half on distinct rows (decoder_stage)
+    int dedup_decoder = 1;
+    int last_ent_unique[2] = {0, 0}, last_ent_merged = 0;                 // a3r_model_last_dedup_entries
     // the handle's own small buffers (the only device memory it allocates, at its first merging call): keys, representatives and
     // flag, the uploaded lists (uniq_img, map_img, uniq_pd, map_pd, the two sides' uniq, the two sides' map: DEDUP_MAX_SLOTS / 2
     // words each), and the pinned host words of
@@ -116,6 +119,7 @@ extern "C" int a3r_model_create(const a3r_model_config* cfg, a3r_model_t* out) {
         m->dedup_mode = !strcmp(dd, "0") ? 0 : !strcmp(dd, "2") ? 2 : 1;
     if (const char* dh = getenv("A3R_DEDUP_HEAD")) m->dedup_head = strcmp(dh, "0") != 0;      // (a3r_model_set_dedup_head)
     if (const char* df = getenv("A3R_DEDUP_HEAD_FOLD")) m->dedup_head_fold = strcmp(df, "0") != 0;
+    if (const char* dc = getenv("A3R_DEDUP_DEC")) m->dedup_decoder = strcmp(dc, "0") != 0;    // (a3r_model_set_dedup_decoder)
     // sized here so that the host-side sizing pass (a3r_model_workspace_bytes) works before finalize
     m->enc.assign(cfg->enc_depth, BlockW());
     m->pc.assign(n_pc_blocks(*cfg), BlockW());
@@ -622,15 +626,16 @@ struct Plan {
     // q, k, v, o are gin buffers (operand forms: straight from / to the projection GEMMs, no fp32 round trip)
     // kv_buf: the buffer k and v are columns of when it is not q's (cross-attention); o_alias: the second side's rows of o when the
     // consumer addresses them by their own pointer (linear2)
+    // q_map / kv_map (fh2 only, device, B words): image b reads the q rows of image q_map[b] and the k / v rows of image kv_map[b]
     void attn(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o, int ldo, int B, int H, int Nq, int Nk,
-              const float* kv_buf = nullptr, const float* o_alias = nullptr) {
+              const float* kv_buf = nullptr, const float* o_alias = nullptr, const int32_t* q_map = nullptr, const int32_t* kv_map = nullptr) {
         if (skip()) return;
         traced("attention", B, Nq, Nk);
         if (gf == Form::FH2) {
             const float sq = scale_of(q), skv = kv_buf ? scale_of(kv_buf) : sq;
             const Site so = site(o, o_alias);
             const a3r_fh2_attn_range r = {sq, skv, skv, so.scale, so.stat};
-            if (!rc) rc = a3r_attention_fh2(q, ldq, k, ldk, v, ldv, o, ldo, B, H, Nq, Nk, &r, stream);
+            if (!rc) rc = a3r_attention_fh2_mapped(q, ldq, k, ldk, v, ldv, o, ldo, B, H, Nq, Nk, &r, q_map, kv_map, stream);
             return;
         }
         rc = gf == Form::BF3 ? a3r_attention_bf3(q, ldq, k, ldk, v, ldv, o, ldo, B, H, Nq, Nk, pair, stream)
@@ -758,10 +763,15 @@ float* fusion_map(Plan& P, const FusionW& w, const float* x0, const float* x0r3,
 struct Distinct {
     int n_img, n_pd; const int32_t *uniq_img, *map_img, *uniq_pd, *map_pd;
     int n_side[2]; const int32_t *uniq_side[2], *map_side[2];
+    // Decoder block 0 on entries (dedup_group_entries; 0: it runs per slot): n_ent = Um entries per side, padded; ent_img / ent_pd
+    // [2 Um] the image / prior row of each side's entries, map_eo [2 B] the row s Um + e of slot (s, b)'s entry e among the 2 Um, and
+    // map_ekv [2 B] that of the other side's slot b inside side s's block, s Um + map_e[1 - s][b]: where slot (s, b)'s keys live
+    int n_ent; const int32_t *ent_img, *ent_pd, *map_eo, *map_ekv;
 };
 // the sizing pass: counts, no lists
 Distinct distinct_counts(int n_img, int n_pd, int n_side) {
-    return {n_img, n_pd, nullptr, nullptr, nullptr, nullptr, {n_side, n_side}, {nullptr, nullptr}, {nullptr, nullptr}};
+    return {n_img, n_pd, nullptr, nullptr, nullptr, nullptr, {n_side, n_side}, {nullptr, nullptr}, {nullptr, nullptr}, 0, nullptr, nullptr,
+            nullptr, nullptr};
 }
 
 // Bytes of a head's level-0 buffers with n images in them, as the arena rounds them: a0, l0, l03, r0, r0r3; the merged branch adds
@@ -925,6 +935,44 @@ void decoder_block_pair(Plan& P, const Dims& g, const BlockW& w0, const BlockW& 
     P.linear2(hid, hid1, hidden, w0.fc2w, w1.fc2w, w0.fc2b, w1.fc2b, o0, o1, D, BN, D, hidden, P.epi(A3R_EPI_RESID, nullptr), o0, o1);
 }
 
+// The same block on ENTRIES (dedup_group_entries): everything before the cross-attention product reads one side's level-0 rows
+// alone, so it runs on xe [2 Um N, D] -- the level-0 rows of each side's Um distinct (image, prior) entries, side 1 at Um N rows --
+// with the ops, their order and their sites as above.  Side s's keys and values are made from side 1 - s's entries with side s's
+// weights.  The self-attention residual goes back into xe in place, one gather puts it into the per-slot nxt, and the
+// cross-attention runs on the 2 B slots with image maps into the entries' q and k / v (dd.map_eo, dd.map_ekv).
+void decoder_block_entries(Plan& P, const Dims& g, const BlockW& w0, const BlockW& w1, float* xe, float* nxt, const DecBufs& t,
+                           const Distinct& dd) {
+    const int B = g.B, N = g.N, BN = g.BN, D = g.D, nw = g.nw, heads = g.c.dec_num_heads, hidden = D * g.c.mlp_ratio;
+    const int Um = dd.n_ent, Ue = Um * N;
+    float *xe0 = xe, *xe1 = xe + (size_t)Ue * D;
+    float *o0 = nxt, *o1 = nxt + (size_t)BN * D;
+    float *xn = t.xn, *yn = t.yn, *qkv = t.qkv, *qb = t.qb, *kv = t.kv, *att = t.att, *hid = t.hid;
+    float *xn1 = P.gin_at(xn, Ue, D), *yn1 = P.gin_at(yn, Ue, D), *att1 = P.gin_at(att, Ue, D);
+    P.ln(xe0, w0.n1w, w0.n1b, xn, Ue, D);
+    P.ln(xe1, w1.n1w, w1.n1b, xn1, Ue, D);
+    P.ln(xe1, w0.nyw, w0.nyb, yn, Ue, D);              // norm_y before the residual goes back into xe (LayerNorm outputs have no site)
+    P.ln(xe0, w1.nyw, w1.nyb, yn1, Ue, D);
+    P.linear2(xn, xn1, D, w0.qkvw, w1.qkvw, w0.qkvb, w1.qkvb, qkv, P.gin_at(qkv, Ue, 3 * D), 3 * D, Ue, 3 * D, D,
+              P.rope_epi(nullptr, 2 * D, N, nw));
+    P.attn(qkv, 3 * D, P.gin_col(qkv, D), 3 * D, P.gin_col(qkv, 2 * D), 3 * D, att, D, 2 * Um, heads, N, N, nullptr, att1);
+    P.linear2(att, att1, D, w0.projw, w1.projw, w0.projb, w1.projb, xe0, xe1, D, Ue, D, D, P.epi(A3R_EPI_RESID, nullptr), xe0, xe1);
+    P.ln(xe0, w0.n2w, w0.n2b, xn, Ue, D);
+    P.ln(xe1, w1.n2w, w1.n2b, xn1, Ue, D);
+    P.linear2(xn, xn1, D, w0.qw, w1.qw, w0.qb, w1.qb, qb, P.gin_at(qb, Ue, D), D, Ue, D, D, P.rope_epi(nullptr, D, N, nw));
+    P.linear2(yn, yn1, D, w0.kvw, w1.kvw, w0.kvb, w1.kvb, kv, P.gin_at(kv, Ue, 2 * D), 2 * D, Ue, 2 * D, D,
+              P.rope_epi(nullptr, D, N, nw));
+    if (!P.skip()) P.rc = gather_rows(xe, nxt, dd.map_eo, 2 * B, N, D, P.stream);
+    att1 = P.gin_at(att, BN, D);
+    P.attn(qb, D, kv, 2 * D, P.gin_col(kv, D), 2 * D, att, D, 2 * B, heads, N, N, kv, att1, dd.map_eo, dd.map_ekv);
+    P.linear2(att, att1, D, w0.cprojw, w1.cprojw, w0.cprojb, w1.cprojb, o0, o1, D, BN, D, D, P.epi(A3R_EPI_RESID, nullptr), o0, o1);
+    xn1 = P.gin_at(xn, BN, D);
+    P.ln(o0, w0.n3w, w0.n3b, xn, BN, D);
+    P.ln(o1, w1.n3w, w1.n3b, xn1, BN, D);
+    float* hid1 = P.gin_at(hid, BN, hidden);
+    P.linear2(xn, xn1, D, w0.fc1w, w1.fc1w, w0.fc1b, w1.fc1b, hid, hid1, hidden, BN, hidden, D, P.gin_epi(A3R_EPI_GELU, nullptr));
+    P.linear2(hid, hid1, hidden, w0.fc2w, w1.fc2w, w0.fc2b, w1.fc2b, o0, o1, D, BN, D, hidden, P.epi(A3R_EPI_RESID, nullptr), o0, o1);
+}
+
 // _decoder (model.py:201-233): decoder_embed, the two decoders with the dec_blocks_pc / zero_convs branch on the depth-prior tokens,
 // dec_norm.  Leaves the hooked levels in v.lvl_a / v.lvl_b and the last one in v.dec_last.
 void decoder_stage(Plan& P, const Call& k, const Dims& g, Levels& v) {
@@ -937,19 +985,48 @@ void decoder_stage(Plan& P, const Call& k, const Dims& g, Levels& v) {
     float* pc3 = P.gin_scratch(M2, D);
     float* cur = v.fbuf[0];
     float* feat3 = P.gin_scratch(M2, E);
-    P.linear(P.gin_from(v.feat, feat3, M2, E), E, m->de_w, cur, D, M2, D, E, P.epi(A3R_EPI_NONE, m->de_b));
-    // zero_convs[i] of the depth-prior tokens, added to level x in place (distinct maps only: their tokens are copied to all slots'
-    // rows first, so the zero-conv and its epilogue stay as they are)
+    // Distinct inputs (fh2 GEMM inputs, a3r_model_set_dedup_decoder): a linear that reads one frame's rows runs on the distinct rows
+    // with the bias-only epilogue, and a gather-add pass makes the sum the RESID epilogue makes per slot (fp32 addition commutes).
+    // The split is the same site over the same set of values.  No buffer is added: the zero-conv's rows z go to v.pc, which holds
+    // nothing once the tokens live in pcu, and decoder_embed's to dec_last, which is written after the last block.
+    const bool on = P.gf == Form::FH2 && m->dedup_decoder;
+    const bool pc_rows = on && g.d_pd, l0_rows = pc_rows && g.d_img;
+    // block 0 on entries: level 0 is made for the 2 Um entries only (nothing else reads it)
+    const bool entries = l0_rows && k.dd->n_ent > 0;
+    auto gather_add = [&](const float* a, const int32_t* ma, const float* b, const int32_t* mb, float* x, int S = 0) {
+        if (!P.skip()) P.rc = a3r_gather_add_rows(a, ma, b, mb, x, S ? S : 2 * g.B, g.N, D, P.stream);
+    };
+    // zero_convs[i] of the depth-prior tokens, added to level x in place (distinct maps without the switch: their tokens are copied
+    // to all slots' rows first, so the zero-conv and its epilogue stay as they are)
+    auto zero_conv_rows = [&](int i) {
+        P.linear(P.gin_from(v.pcu, pc3, Mp, D), D, m->zc_w[i], v.pc, D, Mp, D, D, P.epi(A3R_EPI_NONE, m->zc_b[i]));
+    };
     auto add_pc = [&](int i, float* x) {
+        if (pc_rows) {
+            zero_conv_rows(i);
+            gather_add(v.pc, k.dd->map_pd, nullptr, nullptr, x);
+            return;
+        }
         if (g.d_pd) copy_rows(P, g, v.pcu, v.pc, k.dd->map_pd, D);
         P.linear(P.gin_from(v.pc, pc3, M2, D), D, m->zc_w[i], x, D, M2, D, D, P.epi(A3R_EPI_RESID, m->zc_b[i], x));
     };
-    add_pc(0, cur);
+    if (l0_rows) {
+        // level 0 = zero_convs[0](tokens of the slot's prior) + decoder_embed(rows of the slot's frame); featu shares cur's memory and
+        // is dead once it is split
+        P.linear(P.gin_from(v.featu, feat3, g.Mi, E), E, m->de_w, v.dec_last, D, g.Mi, D, E, P.epi(A3R_EPI_NONE, m->de_b));
+        zero_conv_rows(0);
+        if (entries) gather_add(v.pc, k.dd->ent_pd, v.dec_last, k.dd->ent_img, cur, 2 * k.dd->n_ent);
+        else gather_add(v.pc, k.dd->map_pd, v.dec_last, k.dd->map_img, cur);
+    } else {
+        P.linear(P.gin_from(v.feat, feat3, M2, E), E, m->de_w, cur, D, M2, D, E, P.epi(A3R_EPI_NONE, m->de_b));
+        add_pc(0, cur);
+    }
     const int npc = n_pc_blocks(c);
     for (int i = 0; i < c.dec_depth; i++) {
         const int level = i + 1;
         float* nxt = level == hook_a ? v.fbuf[2] : level == hook_b ? v.fbuf[3] : cur == v.fbuf[0] ? v.fbuf[1] : v.fbuf[0];
-        decoder_block_pair(P, g, m->dec1[i], m->dec2[i], cur, nxt, t);
+        if (i == 0 && entries) decoder_block_entries(P, g, m->dec1[i], m->dec2[i], cur, nxt, t, *k.dd);
+        else decoder_block_pair(P, g, m->dec1[i], m->dec2[i], cur, nxt, t);
         if (i < npc) {   // model.py:223-226
             P.rows(Mp);
             P.self_block(m->pc[i], v.pcu, v.pcu, Mp, D, c.dec_num_heads, g.N, g.nw, t.xn, t.qkv, t.att);
@@ -1176,7 +1253,7 @@ constexpr int DD_HALF = DEDUP_MAX_SLOTS / 2;                       // slots of o
 constexpr size_t DD_HOST_LIST = (DEDUP_REP_INTS + 63) / 64 * 64;   // pinned host words: rep + flag | the DD_LISTS lists
 constexpr size_t DD_REP_OFF = DEDUP_KEY_BYTES;                     // device bytes: keys | rep + flag | the DD_LISTS lists
 constexpr size_t DD_LIST_OFF = DD_REP_OFF + DD_HOST_LIST * 4;
-constexpr int DD_LISTS = 6;                                        // uniq_img, map_img, uniq_pd, map_pd, uniq_side [2][B], map_side [2][B]
+constexpr int DD_LISTS = 10;          // uniq_img, map_img, uniq_pd, map_pd, uniq_side [2][B], map_side [2][B], ent_img, ent_pd, map_eo, map_ekv
 constexpr size_t DD_DEV_BYTES = DD_LIST_OFF + (size_t)DD_LISTS * DD_HALF * 4;
 
 int find_distinct(a3r_model_s* m, const float* a1, const float* a2, long words_a, bool encode, const float* pd1, const float* pd2, int B,
@@ -1186,6 +1263,8 @@ int find_distinct(a3r_model_s* m, const float* a1, const float* a2, long words_a
     m->last_fell_back = 0;
     m->last_side_unique[0] = m->last_side_unique[1] = B;
     m->last_side_merged[0] = m->last_side_merged[1] = 0;
+    m->last_ent_unique[0] = m->last_ent_unique[1] = B;
+    m->last_ent_merged = 0;
     if (m->dedup_mode == 0 || m->tap_level > 0 || 4 * B > DEDUP_MAX_SLOTS) return A3R_OK;
     if (!m->dd_dev) A3R_HIP(hipMalloc(&m->dd_dev, DD_DEV_BYTES));
     if (!m->dd_host) A3R_HIP(hipHostMalloc(reinterpret_cast<void**>(&m->dd_host), (DD_HOST_LIST + DD_LISTS * DD_HALF) * sizeof(int32_t), hipHostMallocDefault));
@@ -1228,12 +1307,44 @@ int find_distinct(a3r_model_s* m, const float* a1, const float* a2, long words_a
     }
     m->last_img_unique = n_img;
     m->last_pd_unique = n_pd;
+    // decoder block 0: each side's distinct (image, prior) entries, when both kinds merge (fh2 GEMM inputs, the attention form with maps)
+    int n_ent = 0;
+    if (m->dedup_decoder && m->gemm_form == Form::FH2 && attention_fh2_takes_maps() && n_img < S && n_pd < S) {
+        std::vector<int32_t> ent(S), map_e(S);
+        int U[2];
+        const int32_t *map_img = list + DD_HALF, *map_pd = list + 3 * DD_HALF;
+        const int um = dedup_group_entries(map_img, map_pd, B, ent.data(), map_e.data(), U);
+        if (um > 0) {
+            m->last_ent_unique[0] = U[0];
+            m->last_ent_unique[1] = U[1];
+            // The statistic of an fh2 GEMM output covers the whole last row tile: rows past M are copies of the last row, rotated at
+            // their own RoPE positions.  The q / k / v projections keep the plain plan's statistics bit for bit only where neither
+            // plan has such rows: both row counts whole multiples of the largest row tile (256).
+            const long N = (long)(H / 16) * (W / 16);
+            if (um < B && (B * N) % 256 == 0 && (um * N) % 256 == 0) {
+                n_ent = um;
+                int32_t *ent_img = list + 6 * DD_HALF, *ent_pd = list + 7 * DD_HALF, *map_eo = list + 8 * DD_HALF, *map_ekv = list + 9 * DD_HALF;
+                for (int s = 0; s < 2; s++) {
+                    for (int e = 0; e < um; e++) {
+                        ent_img[s * um + e] = map_img[ent[s * B + e]];
+                        ent_pd[s * um + e] = map_pd[ent[s * B + e]];
+                    }
+                    for (int b = 0; b < B; b++) {
+                        map_eo[s * B + b] = s * um + map_e[s * B + b];
+                        map_ekv[s * B + b] = s * um + map_e[(1 - s) * B + b];
+                    }
+                }
+            }
+        }
+    }
+    m->last_ent_merged = n_ent > 0;
     if (n_img == S && n_pd == S && n_side[0] == B && n_side[1] == B) return A3R_OK;
     m->last_side_merged[0] = n_side[0] < B;
     m->last_side_merged[1] = n_side[1] < B;
     A3R_HIP(hipMemcpyAsync(list_dev, list, (size_t)DD_LISTS * DD_HALF * sizeof(int32_t), hipMemcpyHostToDevice, st));
     *d = {n_img, n_pd, list_dev, list_dev + DD_HALF, list_dev + 2 * DD_HALF, list_dev + 3 * DD_HALF,
-          {n_side[0], n_side[1]}, {list_dev + 4 * DD_HALF, list_dev + 4 * DD_HALF + B}, {list_dev + 5 * DD_HALF, list_dev + 5 * DD_HALF + B}};
+          {n_side[0], n_side[1]}, {list_dev + 4 * DD_HALF, list_dev + 4 * DD_HALF + B}, {list_dev + 5 * DD_HALF, list_dev + 5 * DD_HALF + B},
+          n_ent, list_dev + 6 * DD_HALF, list_dev + 7 * DD_HALF, list_dev + 8 * DD_HALF, list_dev + 9 * DD_HALF};
     *use = true;
     return A3R_OK;
 }
@@ -1349,6 +1460,20 @@ extern "C" int a3r_model_set_dedup(a3r_model_t m, int mode) {
 extern "C" int a3r_model_set_dedup_head(a3r_model_t m, int on) {
     A3R_CHECK_ARG(m, "a3r_model_set_dedup_head: null handle");
     m->dedup_head = on != 0;
+    return A3R_OK;
+}
+
+extern "C" int a3r_model_set_dedup_decoder(a3r_model_t m, int on) {
+    A3R_CHECK_ARG(m, "a3r_model_set_dedup_decoder: null handle");
+    m->dedup_decoder = on != 0;
+    return A3R_OK;
+}
+
+extern "C" int a3r_model_last_dedup_entries(a3r_model_t m, int* u1, int* u2, int* merged) {
+    A3R_CHECK_ARG(m && u1 && u2 && merged, "a3r_model_last_dedup_entries: null argument");
+    *u1 = m->last_ent_unique[0];
+    *u2 = m->last_ent_unique[1];
+    *merged = m->last_ent_merged;
     return A3R_OK;
 }
 

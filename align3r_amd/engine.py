@@ -178,6 +178,17 @@ class PairEngine:
               "a3r_model_last_dedup_sides")
         return u1.value, u2.value, bool(m1.value), bool(m2.value)
 
+    def set_dedup_decoder(self, on):
+        """The decoder's frame-only work -- level 0, the zero-convs, block 0 up to its cross-attention -- on distinct rows
+        (include/a3r.h, a3r_model_set_dedup_decoder); default on.  Outputs are bitwise the same either way."""
+        check(self.lib.a3r_model_set_dedup_decoder(self.handle, int(bool(on))), "a3r_model_set_dedup_decoder")
+
+    def last_dedup_entries(self):
+        """(diagnostic) (distinct (image, depth prior) entries of side 1, of side 2, block 0 ran on them) of the last forward call."""
+        u1, u2, mg = C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.a3r_model_last_dedup_entries(self.handle, C.byref(u1), C.byref(u2), C.byref(mg)), "a3r_model_last_dedup_entries")
+        return u1.value, u2.value, bool(mg.value)
+
     def set_tap_level(self, level):
         """Keep copies of decoder level `level` and of the point-cloud tokens for tap("level") / tap("pc0") (parity tests); 0 = off."""
         check(self.lib.a3r_model_set_tap_level(self.handle, int(level)), "a3r_model_set_tap_level")

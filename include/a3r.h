@@ -284,6 +284,12 @@ typedef struct {
 } a3r_fh2_attn_range;
 int a3r_attention_fh2(const void* q2, int ldq, const void* k2, int ldk, const void* v2, int ldv, void* o2, int ldo,
                       int B, int H, int Nq, int Nk, const a3r_fh2_attn_range* range, void* stream);
+/* The same with image maps (device, B words each, or NULL = the identity): batch b takes the q rows of image q_map[b] of q2 and the
+ * k / v rows of image kv_map[b] of k2 / v2, and writes the o rows of image b -- a3r_attention_fh2 on explicitly gathered operands,
+ * bit for bit, without the gather.  With both maps NULL it is a3r_attention_fh2.  Kernel form 2 only (an error with form 1). */
+int a3r_attention_fh2_mapped(const void* q2, int ldq, const void* k2, int ldk, const void* v2, int ldv, void* o2, int ldo,
+                             int B, int H, int Nq, int Nk, const a3r_fh2_attn_range* range, const int32_t* q_map,
+                             const int32_t* kv_map, void* stream);
 /* Kernel form behind a3r_attention_fh2: 2 (default: K and V tiles by LDS-DMA, transposed LDS reads) or 1 (round 2: V staged through
  * registers); the results are bitwise equal (tests/test_gpu_fh2.py).  Returns the previous form, or a negative error code.
  * Process-wide; environment A3R_ATTN=v1 selects form 1 at start-up.  A development switch, not part of the reference's interface. */
@@ -363,6 +369,11 @@ int a3r_combine_resid_fh2(const float* c, const float* r0, const float* p2, cons
 /* the same with p2 = a3r_upsample2x(x [S, H, W, C], window Hc x Wc) made inside the kernel and never written; P = Hc Wc */
 int a3r_upsample2x_combine_fh2(const float* x, const float* c, const float* r0, const int32_t* map, float* s, void* sr2, int S, int H,
                                int W, int C, int Hc, int Wc, float scale, unsigned* absmax, void* stream);
+/* The residual add of a linear layer that ran on distinct rows only (the decoder's level 0 and zero-convs, a3r_model_set_dedup_decoder):
+ * blocks of N rows of C floats, dst [S] = a[map_a[s]] + b[map_b[s]], or with b NULL dst[s] += a[map_a[s]] in place.  fp32; maps on
+ * the device; C % 4 == 0, 16-byte aligned buffers. */
+int a3r_gather_add_rows(const float* a, const int32_t* map_a, const float* b, const int32_t* map_b, float* dst, int S, int N, int C,
+                        void* stream);
 /* Kernel form behind a3r_upsample2x, a3r_upsample2x_fh2 and a3r_upsample2x_combine_fh2: 2 (default: a thread makes 2 x 2 output
  * pixels from corners fetched once) or 1 (four corners fetched per output pixel); the results are bitwise equal
  * (tests/test_gpu_up2x_forms.py).  Returns the previous form, or a negative error code.  Process-wide; environment A3R_UP_FORM=v1
@@ -442,6 +453,22 @@ int a3r_model_last_dedup(a3r_model_t m, int* n_img_unique, int* n_pd_unique, int
  * for), and whether that side's head ran merged. */
 int a3r_model_set_dedup_head(a3r_model_t m, int on);
 int a3r_model_last_dedup_sides(a3r_model_t m, int* u1, int* u2, int* merged1, int* merged2);
+/* The decoder's frame-only work (fh2 GEMM inputs only).  decoder_embed reads one frame's enc_norm
+ * rows and the zero-convs read one depth prior's tokens: with merged inputs (a3r_model_set_dedup) they run on the distinct rows
+ * with the bias-only epilogue, and a3r_gather_add_rows adds their rows to every slot -- level 0 needs both kinds merged in a
+ * forward call, the zero-convs the depth priors (forward and decode).  Block 0 of the two decoders reads one side's level-0 rows
+ * alone up to its cross-attention product (norm1, qkv, self-attention, proj, norm2, projq, norm_y, projk/v): in a forward call
+ * with both kinds merged it runs that half on each side's distinct (image, prior) entries, Um = max(U_1, U_2) per side (the
+ * shorter list padded with copies of its last entry), and the cross-attention reads them through image maps
+ * (a3r_attention_fh2_mapped).  It does so when Um < B and B N and Um N are multiples of 256 (N tokens per frame: every batch at
+ * 512x384) -- the statistic of a q / k / v projection covers the whole last row tile, and only without a partial one is it the
+ * plain plan's bit for bit -- and not with attention kernel form 1.  Outputs, fh2 sites, scales
+ * and statistics are bitwise the plain plan's and the workspace requirement does not change.
+ * on: 1 (the default; environment variable A3R_DEDUP_DEC = 0 / 1 for new handles) or 0. */
+int a3r_model_set_dedup_decoder(a3r_model_t m, int on);
+/* a3r_model_last_dedup_entries: distinct (image, depth prior) entries of side 1 / side 2 of the last forward call (B where they
+ * were not looked for), and whether decoder block 0 ran its frame-only half on them. */
+int a3r_model_last_dedup_entries(a3r_model_t m, int* u1, int* u2, int* merged);
 /* Debug taps for the parity tests: intermediate tensors inside the workspace after a forward; returns device pointer + element
  * count.  name: "feat" (enc_norm output, model.py:163), "hook_a" / "hook_b" (the decoder levels the DPT head reads,
  * dpt_head.py:101), "dec_last" (dec_norm output, model.py:231-232); after a3r_model_set_tap_level(m, L > 0) also "level" (the two
