@@ -467,6 +467,16 @@ def upsample2x_fh2(x, crop=None, scale=1.0, absmax=None) -> Fh2:
     return out
 
 
+def upsample2x_bf3(x, crop=None) -> Bf3:
+    """upsample2x written in bf3 form (rows = output pixels, K = C; a3r_upsample2x_bf3)."""
+    _req(x, "x")
+    B, H, W, Cc = x.shape
+    Hc, Wc = crop if crop else (2 * H, 2 * W)
+    out = Bf3(torch.zeros(B * Hc * Wc * Cc * 6, device=x.device, dtype=torch.uint8), B * Hc * Wc, Cc)
+    check(_lib.load().a3r_upsample2x_bf3(ptr(x), out.data_ptr(), B, H, W, Cc, Hc, Wc, stream_ptr()), "upsample2x_bf3")
+    return out
+
+
 def upsample2x(x, crop=None):
     """F.interpolate(scale_factor=2, bilinear, align_corners=True) on channels-last [B,H,W,C]."""
     _req(x, "x")
