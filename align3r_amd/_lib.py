@@ -231,6 +231,12 @@ SIGNATURES = {
     "a3r_align_scene_count": (C.c_int, [c_void, c_void, C.c_float, c_void, c_void, C.c_size_t, c_void, C.POINTER(C.c_longlong), c_void]),
     "a3r_align_scene_export": (C.c_int, [c_void, c_void, C.c_float, c_void, c_void, c_void, C.c_size_t, C.c_longlong, c_void, c_void, c_void,
                                          C.POINTER(C.c_longlong), c_void]),
+    "a3r_align_scene_mesh_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "a3r_align_scene_mesh_count": (C.c_int, [c_void, c_void, C.c_float, c_void, c_void, C.c_size_t, C.c_int, C.POINTER(C.c_longlong),
+                                             C.POINTER(C.c_longlong), c_void]),
+    "a3r_align_scene_mesh_export": (C.c_int, [c_void, c_void, C.c_float, c_void, c_void, c_void, C.c_size_t, C.c_int, C.c_longlong,
+                                              C.c_longlong, c_void, c_void, c_void, c_void, C.POINTER(C.c_longlong),
+                                              C.POINTER(C.c_longlong), c_void]),
     "a3r_align_scene_clean_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "a3r_align_scene_clean": (C.c_int, [c_void, c_void, C.c_float, C.c_float, c_void, C.c_size_t, c_void]),
     "a3r_motion_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

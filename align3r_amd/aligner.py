@@ -306,6 +306,46 @@ class _AlignEngineBase:
         assert written.value == M
         return out
 
+    def _mesh_workspace(self):
+        return torch.empty(int(self.lib.a3r_align_scene_mesh_workspace_bytes(self.N, self.P)), dtype=torch.uint8, device=self.device)
+
+    def count_mesh(self, conf, thr, dyn=None, double_sided=False):
+        """(V, F): the vertices and faces export_mesh would return."""
+        conf, dyn, _, _ = self._scene_inputs(conf, dyn, None)
+        ws = self._mesh_workspace()
+        nv, nf = C.c_longlong(0), C.c_longlong(0)
+        with torch.cuda.device(self.device):
+            check(self.lib.a3r_align_scene_mesh_count(self._states[0].handle, ptr(conf), float(thr), ptr(dyn), ptr(ws), ws.numel(),
+                                                      int(bool(double_sided)), C.byref(nv), C.byref(nf), stream_ptr()),
+                  "a3r_align_scene_mesh_count")
+        return int(nv.value), int(nf.value)
+
+    def export_mesh(self, conf, thr, dyn=None, rgb=None, double_sided=False):
+        """The scene as a triangle mesh over the pixels export_points keeps (pts3d_to_trimesh / cat_meshes of the reference's
+        dust3r/viz.py with every index replaced by the pixel's rank among the kept pixels; include/a3r.h has the definition):
+        dict(xyz [V,3] float32 and rgb [V,3] uint8 -- bitwise those of export_points --, faces [F,3] int32 vertex ids, face_rgb [F,3]
+        uint8; the colours when `rgb` [N,P,3] uint8 is given).  Two triangles per pixel quad, each kept where its three corner pixels
+        are; double_sided adds every triangle wound backwards, in the reference's [A, A', B, B'] layout per image."""
+        conf, dyn, rgb, _ = self._scene_inputs(conf, dyn, rgb)
+        ws = self._mesh_workspace()
+        h, dev, ds = self._states[0].handle, self.device, int(bool(double_sided))
+        nv, nf = C.c_longlong(0), C.c_longlong(0)
+        with torch.cuda.device(dev):
+            check(self.lib.a3r_align_scene_mesh_count(h, ptr(conf), float(thr), ptr(dyn), ptr(ws), ws.numel(), ds, C.byref(nv), C.byref(nf),
+                                                      stream_ptr()), "a3r_align_scene_mesh_count")
+            V, F = int(nv.value), int(nf.value)
+            out = dict(xyz=torch.empty(V, 3, dtype=torch.float32, device=dev))
+            if rgb is not None:
+                out["rgb"] = torch.empty(V, 3, dtype=torch.uint8, device=dev)
+            out["faces"] = torch.empty(F, 3, dtype=torch.int32, device=dev)
+            if rgb is not None:
+                out["face_rgb"] = torch.empty(F, 3, dtype=torch.uint8, device=dev)
+            check(self.lib.a3r_align_scene_mesh_export(h, ptr(conf), float(thr), ptr(dyn), ptr(rgb), ptr(ws), ws.numel(), ds, V, F,
+                                                       ptr(out["xyz"]), ptr(out.get("rgb")), ptr(out["faces"]), ptr(out.get("face_rgb")),
+                                                       C.byref(nv), C.byref(nf), stream_ptr()), "a3r_align_scene_mesh_export")
+        assert (nv.value, nf.value) == (V, F)
+        return out
+
     def clean_confidences(self, conf, tol=0.001, bad_conf=0.0):
         """clean_pointcloud of the reference (cloud_opt/base_opt.py:468-503) on the current state: a new [N,P] float32 device tensor
         in which conf[i,p] is clipped to bad_conf wherever another, more confident view sees the point of (i,p) in front of its own

@@ -14,6 +14,9 @@
 //     earlier pixels): image-major, row-major, a function of the inputs alone.
 //   * pass 2 stages a workgroup's points in LDS (its output range is contiguous) and writes them with consecutive lanes on
 //     consecutive addresses.
+//   * the triangle mesh over the kept pixels (pts3d_to_trimesh / cat_meshes of dust3r/viz.py) repeats the scheme for faces: pass 1
+//     also leaves every pixel's rank inside its chunk in the workspace, a face count pass and a face placement pass read nothing
+//     but that map and the scanned offsets.
 #include "common.h"
 #include "scene.h"
 
@@ -115,7 +118,10 @@ struct SceneSel {
     float* out_xyz;                 // pass 2
     unsigned char* out_rgb;
     int* out_index;
+    int* rank;                      // [N, P] or null (pass 1, mesh): a kept pixel's rank inside its chunk, -1 for a dropped one
 };
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 // grid (nchunks, N).  WRITE = false: offsets[chunk] = kept pixels of the chunk.  WRITE = true: the kept pixels go to
 // offsets[chunk] + (their rank inside the chunk).
@@ -179,6 +185,19 @@ __global__ __launch_bounds__(STPB) void scene_compact_kernel(SceneView v, SceneS
         total += t;
     }
     if (!WRITE) {
+        if (s.rank) {
+            int l = before + below, r[SPX];
+#pragma unroll
+            for (int i = 0; i < SPX; i++) r[i] = keep[i] ? l++ : -1;
+            int* o = s.rank + base + p0;
+            if (VEC) {
+                if (p0 < v.P) *reinterpret_cast<i32x4*>(o) = i32x4{r[0], r[1], r[2], r[3]};
+            } else {
+#pragma unroll
+                for (int i = 0; i < SPX; i++)
+                    if (p0 + i < v.P) o[i] = r[i];
+            }
+        }
         if (tid == 0) s.offsets[n * nchunks + blockIdx.x] = total;
         return;
     }
@@ -250,6 +269,144 @@ __global__ __launch_bounds__(SCAN_TPB) void scene_scan_kernel(int* cnt, int T, i
     __syncthreads();                                     // the offsets are read back by other threads below
     if (counts_img)
         for (int n = tid; n < N; n += SCAN_TPB) counts_img[n] = cnt[(n + 1) * nchunks] - cnt[n * nchunks];
+}
+
+// ------------------------------------------------------------------------------------------- mesh
+// The triangles of pts3d_to_trimesh / cat_meshes (dust3r/viz.py) over the kept pixels, vertex ids = ranks among the kept pixels.
+// Quad (y, x), x < w - 1, y < h - 1, of image n: A = (tl, tr, bl) and B = (tr, bl, br), each present iff its three pixels are kept.
+// Validity and ids come from the rank map pass 1 left in the workspace (rank inside the chunk, -1 = dropped) and the vertex
+// offsets of the scan: vertex id of pixel q = voff[n, q / SCHUNK] + rank[n, q].  No depth, no pose is decoded here.
+// Face blocks of an image: [A, B] (nblk = 2) or [A, A', B, B'] (nblk = 4; the primed blocks are the same triangles wound backwards);
+// foff is laid out [n][block][chunk], so one flat exclusive scan gives every (image, block, chunk) its output range.
+struct SceneMesh {
+    const int* rank;                // [N, P]
+    const int* voff;                // [N * nchunks + 1] vertex offsets
+    int* foff;                      // [N * nblk * nchunks + 1]: the count pass writes counts, the scan turns them into offsets
+    const unsigned char* rgb;       // [N, P, 3] or null
+    int* out_faces;                 // [F, 3]
+    unsigned char* out_rgb;         // [F, 3] or null
+    int P, nblk;
+};
+
+// grid (nchunks, N); a thread owns 4 consecutive top-left pixels.  WRITE = false: the chunk's A and B counts.  WRITE = true: the
+// faces are staged in LDS (A in the first SCHUNK slots, B in the second) and written with consecutive lanes on consecutive addresses.
+template <bool VEC, bool WRITE>
+__global__ __launch_bounds__(STPB) void scene_faces_kernel(SceneMesh m, const int* __restrict__ imw) {
+    __shared__ int wave_total[2][STPB / 64];
+    __shared__ int st_face[WRITE ? 2 * SCHUNK * 3 : 1];
+    __shared__ unsigned char st_rgb[WRITE ? 2 * SCHUNK * 3 : 4];
+    const int n = blockIdx.y, tid = threadIdx.x, wave = tid >> 6;
+    const int nchunks = gridDim.x, p0 = blockIdx.x * SCHUNK + tid * SPX;
+    const int W = imw[n], P = m.P;
+    const size_t base = (size_t)n * P;
+    const int* __restrict__ rk = m.rank + base;
+    // ranks of the row p0 .. p0 + 4 and of the row below it; everything at and beyond P reads as dropped.  The padding pixels
+    // p >= h * w of a smaller image hold -1 themselves, which also ends the last row: its "row below" is padding or beyond P.
+    int top[SPX + 1], bot[SPX + 1];
+#pragma unroll
+    for (int i = 0; i <= SPX; i++) top[i] = bot[i] = -1;
+    const int q0 = p0 + W;
+    if (VEC) {                      // P % 4 == 0, p0 % 4 == 0: four pixels are inside P together; the row below when W % 4 == 0 too
+        if (p0 < P) {
+            const i32x4 t = *reinterpret_cast<const i32x4*>(rk + p0);
+            top[0] = t.x; top[1] = t.y; top[2] = t.z; top[3] = t.w;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < SPX; i++)
+            if (p0 + i < P) top[i] = rk[p0 + i];
+    }
+    if (p0 + SPX < P) top[SPX] = rk[p0 + SPX];
+    if (VEC && (W & 3) == 0) {      // block-uniform
+        if (q0 < P) {
+            const i32x4 t = *reinterpret_cast<const i32x4*>(rk + q0);
+            bot[0] = t.x; bot[1] = t.y; bot[2] = t.z; bot[3] = t.w;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < SPX; i++)
+            if (q0 + i < P) bot[i] = rk[q0 + i];
+    }
+    if (q0 + SPX < P) bot[SPX] = rk[q0 + SPX];
+    bool fa[SPX], fb[SPX];
+    int x = p0 % W;
+#pragma unroll
+    for (int i = 0; i < SPX; i++) {
+        const bool diag = x < W - 1 && top[i + 1] >= 0 && bot[i] >= 0;       // no quad wraps from the end of a row to the next
+        fa[i] = diag && top[i] >= 0;
+        fb[i] = diag && bot[i + 1] >= 0;
+        if (++x == W) x = 0;
+    }
+    // ranks inside the wave, A and B apart: quad order is (lane, i)
+    int below_a = 0, below_b = 0, wave_a = 0, wave_b = 0;
+#pragma unroll
+    for (int i = 0; i < SPX; i++) {
+        const unsigned long long a = __ballot(fa[i]), b = __ballot(fb[i]);
+        below_a += __builtin_amdgcn_mbcnt_hi((unsigned)(a >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)a, 0u));
+        below_b += __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+        wave_a += __popcll(a);
+        wave_b += __popcll(b);
+    }
+    if ((tid & 63) == 0) { wave_total[0][wave] = wave_a; wave_total[1][wave] = wave_b; }
+    __syncthreads();
+    int before_a = 0, before_b = 0, total_a = 0, total_b = 0;
+#pragma unroll
+    for (int k = 0; k < STPB / 64; k++) {
+        const int ta = wave_total[0][k], tb = wave_total[1][k];
+        if (k < wave) { before_a += ta; before_b += tb; }
+        total_a += ta; total_b += tb;
+    }
+    const int slot_a = n * m.nblk * nchunks + blockIdx.x, slot_b = slot_a + (m.nblk >> 1) * nchunks;
+    const bool two = m.nblk == 4;
+    if (!WRITE) {
+        if (tid == 0) {
+            m.foff[slot_a] = total_a; m.foff[slot_b] = total_b;
+            if (two) { m.foff[slot_a + nchunks] = total_a; m.foff[slot_b + nchunks] = total_b; }
+        }
+        return;
+    }
+    if (total_a + total_b == 0) return;      // workgroup-uniform
+    const int* __restrict__ vo = m.voff + n * nchunks;
+    const bool colour = m.out_rgb != nullptr;
+    int la = before_a + below_a, lb = SCHUNK + before_b + below_b;
+#pragma unroll
+    for (int i = 0; i < SPX; i++) {
+        if (!(fa[i] || fb[i])) continue;
+        const int p = p0 + i;
+        const int tr = vo[(p + 1) / SCHUNK] + top[i + 1], bl = vo[(p + W) / SCHUNK] + bot[i];
+        if (fa[i]) {
+            st_face[la * 3 + 0] = vo[p / SCHUNK] + top[i]; st_face[la * 3 + 1] = tr; st_face[la * 3 + 2] = bl;
+            if (colour) {
+                const unsigned char* src = m.rgb + (base + p) * 3;                  // the colour of the top-left pixel
+                st_rgb[la * 3 + 0] = src[0]; st_rgb[la * 3 + 1] = src[1]; st_rgb[la * 3 + 2] = src[2];
+            }
+            la++;
+        }
+        if (fb[i]) {
+            st_face[lb * 3 + 0] = tr; st_face[lb * 3 + 1] = bl; st_face[lb * 3 + 2] = vo[(p + W + 1) / SCHUNK] + bot[i + 1];
+            if (colour) {
+                const unsigned char* src = m.rgb + (base + p + W + 1) * 3;          // the colour of the bottom-right pixel
+                st_rgb[lb * 3 + 0] = src[0]; st_rgb[lb * 3 + 1] = src[1]; st_rgb[lb * 3 + 2] = src[2];
+            }
+            lb++;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int blk = 0; blk < 4; blk++) {
+        const bool b_side = blk >= 2, rev = blk & 1;
+        if (rev && !two) continue;
+        const int slot = (b_side ? slot_b : slot_a) + (rev ? nchunks : 0), l0 = b_side ? SCHUNK : 0;
+        const size_t o = (size_t)m.foff[slot];
+        // the count pass saw the same rank map, so this is its count; stay inside the range whatever the workspace holds
+        const int total = min(b_side ? total_b : total_a, m.foff[slot + 1] - m.foff[slot]);
+        for (int k = tid; k < total * 3; k += STPB) {
+            const int f = k / 3, c = k - f * 3;
+            m.out_faces[o * 3 + k] = st_face[(l0 + f) * 3 + (rev ? 2 - c : c)];
+        }
+        if (colour)
+            for (int k = tid; k < total * 3; k += STPB) m.out_rgb[o * 3 + k] = st_rgb[l0 * 3 + k];
+    }
 }
 
 // ------------------------------------------------------------------------------------------- clean_pointcloud
@@ -423,7 +580,7 @@ static int scene_count(a3r_align_t a, const char* who, const float* conf, float 
     *vec = v->P % 4 == 0 && aligned16(v->depth) && aligned16(conf) && (!v->mono || aligned16(v->mono)) && (!dyn || aligned16(dyn)) &&
            (!rgb || aligned16(rgb));
     s->conf = conf; s->dyn = dyn; s->rgb = rgb; s->thr = thr; s->offsets = static_cast<int*>(workspace);
-    s->out_xyz = nullptr; s->out_rgb = nullptr; s->out_index = nullptr;
+    s->out_xyz = nullptr; s->out_rgb = nullptr; s->out_index = nullptr; s->rank = nullptr;
     const int nch = scene_nchunks(v->P), T = v->N * nch;
     launch_compact<false>(*v, *s, *vec, st);
     hipLaunchKernelGGL(scene_scan_kernel, dim3(1), dim3(SCAN_TPB), 0, st, s->offsets, T, v->N, nch, counts_dev);
@@ -468,6 +625,113 @@ extern "C" int a3r_align_scene_export(a3r_align_t a, const float* conf, float th
     if (total == 0) return A3R_OK;
     s.out_xyz = out_xyz; s.out_rgb = out_rgb; s.out_index = out_index;
     launch_compact<true>(v, s, vec, st);
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+// mesh workspace: vertex offsets [T + 1] | face offsets [4 T + 1] | rank map [N, P], each part rounded up to 256 bytes (T = N * nchunks)
+static size_t mesh_voff_bytes(int N, int P) { return align_up(((size_t)N * scene_nchunks(P) + 1) * sizeof(int), 256); }
+static size_t mesh_foff_bytes(int N, int P) { return align_up(((size_t)4 * N * scene_nchunks(P) + 1) * sizeof(int), 256); }
+
+extern "C" size_t a3r_align_scene_mesh_workspace_bytes(int N, int P) {
+    if (N <= 0 || P <= 0) return 0;
+    return mesh_voff_bytes(N, P) + mesh_foff_bytes(N, P) + align_up((size_t)N * P * sizeof(int), 256);
+}
+
+template <bool WRITE>
+static void launch_faces(const SceneView& v, const SceneMesh& m, hipStream_t st) {
+    const dim3 grid(scene_nchunks(v.P), v.N), block(STPB);
+    if (v.P % 4 == 0) hipLaunchKernelGGL((scene_faces_kernel<true, WRITE>), grid, block, 0, st, m, v.imw);
+    else              hipLaunchKernelGGL((scene_faces_kernel<false, WRITE>), grid, block, 0, st, m, v.imw);
+}
+
+// pass 1 (vertex counts + rank map), scan, face counts, scan; both totals come back to the host (synchronises the stream)
+static int mesh_count(a3r_align_t a, const char* who, const float* conf, float thr, const uint8_t* dyn, const uint8_t* rgb, void* workspace,
+                      size_t workspace_bytes, int double_sided, hipStream_t st, SceneView* v, SceneSel* s, SceneMesh* m, bool* vec,
+                      long long* n_vertices, long long* n_faces) {
+    A3R_CHECK_ARG(conf, "%s: null confidence buffer", who);
+    A3R_CHECK_ARG(double_sided == 0 || double_sided == 1, "%s: double_sided = %d is neither 0 nor 1", who, double_sided);
+    if (int rc = align_scene_view(a, st, v, who)) return rc;
+    const int nblk = double_sided ? 4 : 2;
+    // vertex ids are int32; the faces of an image are at most 2 (4) per pixel, and their offsets are int32 as well
+    A3R_CHECK_ARG((size_t)v->N * v->P < (1ull << 31), "%s: N * P = %zu does not fit the int32 vertex index", who, (size_t)v->N * v->P);
+    A3R_CHECK_ARG((size_t)nblk * v->N * v->P < (1ull << 31), "%s: up to %d * N * P = %zu faces do not fit the int32 face offsets", who, nblk,
+                  (size_t)nblk * v->N * v->P);
+    const size_t need = a3r_align_scene_mesh_workspace_bytes(v->N, v->P);
+    A3R_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
+    A3R_CHECK_ARG(aligned16(workspace), "%s: workspace must be 16-byte aligned", who);
+    *vec = v->P % 4 == 0 && aligned16(v->depth) && aligned16(conf) && (!v->mono || aligned16(v->mono)) && (!dyn || aligned16(dyn)) &&
+           (!rgb || aligned16(rgb));
+    char* ws = static_cast<char*>(workspace);
+    int* voff = reinterpret_cast<int*>(ws);
+    int* foff = reinterpret_cast<int*>(ws + mesh_voff_bytes(v->N, v->P));
+    int* rank = reinterpret_cast<int*>(ws + mesh_voff_bytes(v->N, v->P) + mesh_foff_bytes(v->N, v->P));
+    s->conf = conf; s->dyn = dyn; s->rgb = rgb; s->thr = thr; s->offsets = voff;
+    s->out_xyz = nullptr; s->out_rgb = nullptr; s->out_index = nullptr; s->rank = rank;
+    m->rank = rank; m->voff = voff; m->foff = foff; m->rgb = nullptr; m->out_faces = nullptr; m->out_rgb = nullptr;
+    m->P = v->P; m->nblk = nblk;
+    const int nch = scene_nchunks(v->P), T = v->N * nch, TF = T * nblk;
+    launch_compact<false>(*v, *s, *vec, st);
+    hipLaunchKernelGGL(scene_scan_kernel, dim3(1), dim3(SCAN_TPB), 0, st, voff, T, v->N, nch, static_cast<int*>(nullptr));
+    launch_faces<false>(*v, *m, st);
+    hipLaunchKernelGGL(scene_scan_kernel, dim3(1), dim3(SCAN_TPB), 0, st, foff, TF, v->N, nblk * nch, static_cast<int*>(nullptr));
+    A3R_LAUNCH_CHECK();
+    int totals[2] = {0, 0};
+    A3R_HIP(hipMemcpyAsync(&totals[0], voff + T, sizeof(int), hipMemcpyDeviceToHost, st));
+    A3R_HIP(hipMemcpyAsync(&totals[1], foff + TF, sizeof(int), hipMemcpyDeviceToHost, st));
+    A3R_HIP(hipStreamSynchronize(st));
+    *n_vertices = totals[0];
+    *n_faces = totals[1];
+    return A3R_OK;
+}
+
+extern "C" int a3r_align_scene_mesh_count(a3r_align_t a, const float* conf, float thr, const uint8_t* dyn, void* workspace,
+                                          size_t workspace_bytes, int double_sided, long long* n_vertices_host, long long* n_faces_host,
+                                          void* stream) {
+    A3R_CHECK_ARG(n_vertices_host && n_faces_host, "a3r_align_scene_mesh_count: null n_vertices_host / n_faces_host");
+    SceneView v;
+    SceneSel s;
+    SceneMesh m;
+    bool vec;
+    *n_vertices_host = *n_faces_host = 0;
+    return mesh_count(a, "a3r_align_scene_mesh_count", conf, thr, dyn, nullptr, workspace, workspace_bytes, double_sided, as_stream(stream), &v,
+                      &s, &m, &vec, n_vertices_host, n_faces_host);
+}
+
+extern "C" int a3r_align_scene_mesh_export(a3r_align_t a, const float* conf, float thr, const uint8_t* dyn, const uint8_t* rgb, void* workspace,
+                                           size_t workspace_bytes, int double_sided, long long vertex_capacity, long long face_capacity,
+                                           float* out_xyz, uint8_t* out_vertex_rgb, int* out_faces, uint8_t* out_face_rgb,
+                                           long long* n_vertices_host, long long* n_faces_host, void* stream) {
+    const char* who = "a3r_align_scene_mesh_export";
+    A3R_CHECK_ARG(n_vertices_host && n_faces_host, "%s: null n_vertices_host / n_faces_host", who);
+    A3R_CHECK_ARG(vertex_capacity >= 0 && face_capacity >= 0, "%s: negative capacity", who);
+    A3R_CHECK_ARG(out_xyz || vertex_capacity == 0, "%s: null out_xyz (only a vertex capacity of 0 needs no buffer)", who);
+    A3R_CHECK_ARG(out_faces || face_capacity == 0, "%s: null out_faces (only a face capacity of 0 needs no buffer)", who);
+    A3R_CHECK_ARG(!out_vertex_rgb || rgb, "%s: out_vertex_rgb needs the rgb source buffer", who);
+    A3R_CHECK_ARG(!out_face_rgb || rgb, "%s: out_face_rgb needs the rgb source buffer", who);
+    hipStream_t st = as_stream(stream);
+    SceneView v;
+    SceneSel s;
+    SceneMesh m;
+    bool vec;
+    long long nv = 0, nf = 0;
+    *n_vertices_host = *n_faces_host = 0;
+    // the counts are always taken afresh: the offsets and the rank map in the workspace then belong to exactly these inputs
+    if (int rc = mesh_count(a, who, conf, thr, dyn, out_vertex_rgb ? rgb : nullptr, workspace, workspace_bytes, double_sided, st, &v, &s, &m,
+                            &vec, &nv, &nf))
+        return rc;
+    *n_vertices_host = nv;
+    *n_faces_host = nf;
+    A3R_CHECK_ARG(nv <= vertex_capacity, "%s: vertex capacity %lld is smaller than the %lld kept pixels (nothing was written)", who,
+                  vertex_capacity, nv);
+    A3R_CHECK_ARG(nf <= face_capacity, "%s: face capacity %lld is smaller than the %lld faces (nothing was written)", who, face_capacity, nf);
+    if (nv == 0) return A3R_OK;
+    s.out_xyz = out_xyz; s.out_rgb = out_vertex_rgb; s.rank = nullptr;
+    launch_compact<true>(v, s, vec, st);
+    if (nf > 0) {
+        m.rgb = rgb; m.out_faces = out_faces; m.out_rgb = out_face_rgb;
+        launch_faces<true>(v, m, st);
+    }
     A3R_LAUNCH_CHECK();
     return A3R_OK;
 }

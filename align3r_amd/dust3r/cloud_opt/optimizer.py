@@ -392,20 +392,43 @@ class PointCloudOptimizer:
         n * max_area + p.  Kept: conf > min_conf_thr (as given; None = self.min_conf_thr, the pixels of get_masks()), finite
         coordinates and, with mask_dynamic, outside the scene's dynamic masks.  Image-major, row-major order."""
         e = self._need_engine()
-        N, P = self.n_imgs, self.max_area
+        conf, thr, dyn, rgb = self._scene_out_inputs(min_conf_thr, mask_dynamic, 'get_pointcloud')
+        return e.export_points(conf, thr, dyn=dyn, rgb=rgb, with_index=with_index)
+
+    def _scene_out_inputs(self, min_conf_thr, mask_dynamic, who):
+        """(conf [N,P], thr, dyn [N,P] or None, rgb [N,P,3] uint8 or None): what get_pointcloud and get_mesh hand to the engine."""
+        P = self.max_area
         thr = self.min_conf_thr if min_conf_thr is None else min_conf_thr
         conf = torch.stack([_ravel_hw(c.to(self.device).float()[..., None], P)[:, 0] for c in self._mask_confidences()])
         dyn = None
         if mask_dynamic:
             masks = getattr(self, 'dynamic_masks', None)
             if masks is None:
-                raise RuntimeError('get_pointcloud(mask_dynamic=True): this scene has no dynamic masks')
+                raise RuntimeError(f'{who}(mask_dynamic=True): this scene has no dynamic masks')
             dyn = torch.stack([_ravel_hw(torch.as_tensor(m).to(self.device).to(torch.uint8)[..., None], P)[:, 0] for m in masks])
         rgb = None
         if self.imgs is not None:
             rgb = torch.stack([_ravel_hw(torch.from_numpy(np.clip(np.rint(255.0 * np.asarray(im)), 0, 255).astype(np.uint8)), P)
                                for im in self.imgs])
-        return e.export_points(conf, float(thr), dyn=dyn, rgb=rgb, with_index=with_index)
+        return conf, float(thr), dyn, rgb
+
+    def get_mesh(self, min_conf_thr=None, mask_dynamic=False, double_sided=False):
+        """The aligned scene as one triangle mesh (the default output of the reference's get_3D_model_from_scene: pts3d_to_trimesh /
+        cat_meshes of dust3r/viz.py), built on the device by the aligner handle: dict of device tensors xyz [V,3] float32 and
+        rgb [V,3] uint8 -- the vertices are exactly the points of get_pointcloud() with the same arguments --, faces [F,3] int32
+        vertex ids and face_rgb [F,3] uint8 (the colours when the scene holds its frames).  Two triangles per pixel quad, each kept
+        where its three corner pixels are; double_sided adds every triangle wound backwards, as the reference does."""
+        e = self._need_engine()
+        conf, thr, dyn, rgb = self._scene_out_inputs(min_conf_thr, mask_dynamic, 'get_mesh')
+        return e.export_mesh(conf, thr, dyn=dyn, rgb=rgb, double_sided=double_sided)
+
+    def save_mesh(self, path, **kw):
+        """get_mesh(**kw) written as a binary little-endian PLY (tool/pointcloud.py: write_ply_mesh); returns the dict."""
+        from ...tool.pointcloud import write_ply_mesh
+        m = self.get_mesh(**kw)
+        host = lambda k: m[k].cpu().numpy() if k in m else None
+        write_ply_mesh(path, host('xyz'), host('faces'), host('rgb'), host('face_rgb'))
+        return m
 
     def save_pointcloud(self, path, **kw):
         """get_pointcloud(**kw) written as a binary little-endian PLY (tool/pointcloud.py); returns the dict."""

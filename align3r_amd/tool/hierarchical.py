@@ -124,8 +124,15 @@ def _flow_options(flow):
     return {**FLOW_DEFAULTS, **flow}
 
 
+def _collect_mesh(scene, mesh_collector, double_sided):
+    if mesh_collector is None:
+        return
+    m = scene.get_mesh(double_sided=double_sided)
+    mesh_collector.append({k: (m[k].cpu().numpy() if k in m else None) for k in ('xyz', 'rgb', 'faces', 'face_rgb')})
+
+
 def _hierarchical_flow(imgs, model, device, opt, *, clip_size, niter, schedule, lr, min_conf_thr, batch_size, verbose,
-                       output_dir, pointcloud_collector, clean, obs_dtype, device_resident):
+                       output_dir, pointcloud_collector, clean, obs_dtype, device_resident, mesh_collector, mesh_double_sided):
     """The two stages of tool/pose_test.py:346-479 (--mode eval_pose_h): keyframes, then every clip, through the flow-regularised
     aligner; every clip is initialised on its keyframe (init_priors) and its poses are re-anchored on the keyframe pose."""
     from ..dust3r.cloud_opt_flow import GlobalAlignerMode, global_aligner
@@ -194,6 +201,7 @@ def _hierarchical_flow(imgs, model, device, opt, *, clip_size, niter, schedule, 
         if pointcloud_collector is not None:
             pc = scene.get_pointcloud()
             pointcloud_collector.append(dict(xyz=pc['xyz'].cpu().numpy(), rgb=pc['rgb'].cpu().numpy() if 'rgb' in pc else None))
+        _collect_mesh(scene, mesh_collector, mesh_double_sided)
         if output_dir is not None:                  # per clip, with running offsets (pose_test.py:463-475)
             traj = [np.concatenate([traj[0], pred_traj[0]], axis=0), np.concatenate([traj[1], pred_traj[1] + offset], axis=0)]
             save_trajectory_tum_format(traj, os.path.join(output_dir, 'pred_traj.txt'))
@@ -212,13 +220,16 @@ def _hierarchical_flow(imgs, model, device, opt, *, clip_size, niter, schedule, 
 
 def hierarchical_alignment(imgs, model, device, *, clip_size=50, niter=300, schedule='linear', lr=0.05, min_conf_thr=3,
                            if_use_mono=False, mono_depths=(), batch_size=1, clamp_conf=None, verbose=False, output_dir=None,
-                           pointcloud_collector=None, clean=False, obs_dtype='fp32', flow=None, device_resident=False):
+                           pointcloud_collector=None, clean=False, obs_dtype='fp32', flow=None, device_resident=False,
+                           mesh_collector=None, mesh_double_sided=False):
     """Keyframe pass + per-clip passes (depth_test.py:636-676).  `imgs`: view dicts (load_images).  Returns a dict with the
     per-frame lists `depths`, `confs`, `poses` ([4,4] cam-to-world in the keyframes' frame), `focals`, `intrinsics`, plus
     `keyframes_id`, `clip_size` and the keyframe scene's own results; writes pred_traj.txt / pred_intrinsics.txt /
     frame_XXXX.npy / conf_X.npy under `output_dir` when given (demo.py:225-243).
     `pointcloud_collector`: a list that receives, in clip order, every clip scene's get_pointcloud() as host arrays
     dict(xyz, rgb | None); off by default.
+    `mesh_collector`: a list that receives, in clip order, every clip scene's get_mesh(double_sided=mesh_double_sided) as host
+    arrays dict(xyz, rgb | None, faces, face_rgb | None), faces indexing the clip's own vertices; off by default.
     `clean`: scene.clean_pointcloud() on the keyframe scene and on every clip scene right after its alignment (pose_test.py:205,475),
     so the confidences returned, written and thresholded by the collector are the cleaned ones; off by default.
     `flow`: None = the plain aligner over my_make_pairs graphs (tool/depth_test.py).  A dict (FLOW_DEFAULTS names the options;
@@ -241,7 +252,7 @@ def hierarchical_alignment(imgs, model, device, *, clip_size=50, niter=300, sche
         return _hierarchical_flow(imgs, model, device, opt, clip_size=clip_size, niter=niter, schedule=schedule, lr=lr,
                                   min_conf_thr=min_conf_thr, batch_size=batch_size, verbose=verbose,
                                   output_dir=output_dir, pointcloud_collector=pointcloud_collector, clean=clean, obs_dtype=obs_dtype,
-                                  device_resident=device_resident)
+                                  device_resident=device_resident, mesh_collector=mesh_collector, mesh_double_sided=mesh_double_sided)
     if device_resident:
         raise ValueError('hierarchical_alignment: device_resident belongs to the flow pipeline (flow=dict(...))')
     if clamp_conf is None:
@@ -287,6 +298,7 @@ def hierarchical_alignment(imgs, model, device, *, clip_size=50, niter=300, sche
         if pointcloud_collector is not None:
             pc = scene.get_pointcloud()
             pointcloud_collector.append(dict(xyz=pc['xyz'].cpu().numpy(), rgb=pc['rgb'].cpu().numpy() if 'rgb' in pc else None))
+        _collect_mesh(scene, mesh_collector, mesh_double_sided)
     if output_dir is not None:
         os.makedirs(output_dir, exist_ok=True)
         save_trajectory_tum_format(get_tum_poses(res['poses']), os.path.join(output_dir, 'pred_traj.txt'))

@@ -56,6 +56,11 @@ def parse(argv=None):
     ap.add_argument("--gt-traj", default=None, help="ground-truth camera trajectory, TUM file `t x y z qx qy qz qw` (same frames) -> ATE / RPE")
     ap.add_argument("--pointcloud", default=None, metavar="PATH",
                     help="write the aligned scene as a binary PLY (with --hierarchical: every clip's points, appended in clip order)")
+    ap.add_argument("--mesh", default=None, metavar="PATH",
+                    help="write the aligned scene as a triangle mesh (binary PLY: the kept points as vertices, two triangles per pixel "
+                         "quad whose corners are kept; with --hierarchical: every clip's mesh, appended in clip order)")
+    ap.add_argument("--mesh-double-sided", action="store_true",
+                    help="--mesh: every triangle also wound backwards (what the reference hands to its viewer against face culling)")
     ap.add_argument("--clean", action="store_true",
                     help="scene.clean_pointcloud() after every alignment: confidences of points another, more confident view sees through "
                          "drop to 0 before conf_X.npy and --pointcloud are written (tool/demo.py: clean_depth)")
@@ -85,6 +90,8 @@ def parse(argv=None):
         ap.error("--device-resident belongs to --flow-hierarchical")
     if a.metrics_device and not a.gt_depth:
         ap.error("--metrics-device belongs to --gt-depth")
+    if a.mesh_double_sided and not a.mesh:
+        ap.error("--mesh-double-sided belongs to --mesh")
     if a.clip_size is None:
         a.clip_size = 10 if a.flow_hierarchical else 50          # pose_test.py:346 / depth_test.py:636
     if not (a.flow or a.flow_hierarchical):
@@ -105,7 +112,7 @@ def main(argv=None):
     from ..dust3r.utils.image_pose import load_images
     from . import hierarchical as hz
     from .depth_metrics import evaluate_depth
-    from .pointcloud import write_ply_parts
+    from .pointcloud import write_ply_mesh_parts, write_ply_parts
 
     verbose = not a.quiet
     model = AsymmetricCroCo3DStereo.from_pretrained(a.weights).to(a.device)
@@ -115,6 +122,7 @@ def main(argv=None):
                           else os.path.join(a.out, "__no_masks__"))
     os.makedirs(a.out, exist_ok=True)
     clouds, n_points = ([] if a.pointcloud else None), None
+    meshes, n_mesh = ([] if a.mesh else None), None              # n_mesh: (vertices, faces) written
     depths_dev = None                  # --metrics-device: the aligned depth maps as the scene holds them, on the device
     if a.flow_hierarchical and len(imgs) < 3:
         raise RuntimeError("--flow-hierarchical needs at least 3 frames")
@@ -125,10 +133,13 @@ def main(argv=None):
                          device_resident=a.device_resident)
         res = hz.hierarchical_alignment(imgs, model, a.device, clip_size=a.clip_size, niter=a.niter, schedule=a.schedule, lr=a.lr,
                                         min_conf_thr=a.min_conf_thr, batch_size=a.batch_size, verbose=verbose, output_dir=a.out,
-                                        pointcloud_collector=clouds, clean=a.clean, obs_dtype=a.obs_dtype, **extra)
+                                        pointcloud_collector=clouds, clean=a.clean, obs_dtype=a.obs_dtype, mesh_collector=meshes,
+                                        mesh_double_sided=a.mesh_double_sided, **extra)
         depths = res["depths"]
         if a.pointcloud:
             n_points = write_ply_parts(a.pointcloud, [(c["xyz"], c["rgb"]) for c in clouds])
+        if a.mesh:
+            n_mesh = write_ply_mesh_parts(a.mesh, [(m["xyz"], m["faces"], m["rgb"], m["face_rgb"]) for m in meshes])
     else:
         if len(imgs) == 1:
             imgs = [imgs[0], dict(imgs[0], idx=1)]
@@ -171,6 +182,11 @@ def main(argv=None):
             if mode != GlobalAlignerMode.PointCloudOptimizer:
                 raise RuntimeError("--pointcloud needs at least 3 frames (the two-frame PairViewer has no aligner handle to export from)")
             n_points = int(scene.save_pointcloud(a.pointcloud)["xyz"].shape[0])
+        if a.mesh:
+            if mode != GlobalAlignerMode.PointCloudOptimizer:
+                raise RuntimeError("--mesh needs at least 3 frames (the two-frame PairViewer has no aligner handle to export from)")
+            m = scene.save_mesh(a.mesh, double_sided=a.mesh_double_sided)
+            n_mesh = (int(m["xyz"].shape[0]), int(m["faces"].shape[0]))
     metrics = None
     if a.gt_depth:
         files = sorted(glob.glob(os.path.join(a.gt_depth, "*.npy")))[a.start:a.start + len(depths)]
@@ -195,6 +211,8 @@ def main(argv=None):
     res_out = dict(n_frames=len(depths), out=a.out, metrics=metrics, pose_metrics=pose)
     if a.pointcloud:
         res_out["pointcloud"], res_out["n_points"] = a.pointcloud, n_points
+    if a.mesh:
+        res_out["mesh"], res_out["n_vertices"], res_out["n_faces"] = a.mesh, n_mesh[0], n_mesh[1]
     return res_out
 
 

@@ -751,6 +751,39 @@ int a3r_align_scene_export(a3r_align_t a, const float* conf, float thr, const ui
                            size_t workspace_bytes, long long capacity, float* out_xyz, uint8_t* out_rgb, int* out_index,
                            long long* n_written_host, void* stream);
 
+/* Scene out as a triangle mesh (pts3d_to_trimesh / cat_meshes of dust3r/viz.py, the default form of get_3D_model_from_scene), with
+ * the inputs and the kept rule of a3r_align_scene_export.
+ *   Vertices: the kept pixels, image-major and row-major -- bitwise the out_xyz / out_rgb of a3r_align_scene_export on the same
+ *     inputs.  A vertex's id is its rank in that order; kept pixels that end up in no triangle stay in the list.
+ *   Quads: for image n of shape (h, w) every (y, x), 0 <= y < h - 1, 0 <= x < w - 1, row-major, with the corners tl = (y, x),
+ *     tr = (y, x + 1), bl = (y + 1, x), br = (y + 1, x + 1) (each image's own w; no quad wraps from the end of a row to the next).
+ *     Triangle A = (tl, tr, bl) exists iff those three pixels are kept, its colour is rgb[tl];
+ *     triangle B = (tr, bl, br) exists iff those three pixels are kept, its colour is rgb[br].
+ *   Face order: images in order; inside an image with double_sided = 0 all existing A (quad order), then all existing B; with
+ *     double_sided = 1 the reference's [A, A', B, B'], A' = (bl, tr, tl) and B' = (br, bl, tr) being the same triangles wound
+ *     backwards, each block in quad order, with the colours of A and B.
+ *   out_faces [F,3] int32 vertex ids, out_face_rgb [F,3] uint8.  cat_meshes([pts3d_to_trimesh(img_n, pts_n, kept_n)]) indexes the
+ *     dense grids (image offsets = cumulative h * w); this mesh is that one with every index replaced by the pixel's rank among the
+ *     kept pixels.
+ * Passes, no atomics (the output is a function of the inputs alone): per-chunk vertex counts + a rank map (rank inside the chunk,
+ * -1 = dropped), scan, per-chunk face counts from the rank map alone, scan, vertex placement, face placement.
+ * workspace: a3r_align_scene_mesh_workspace_bytes(N, P) bytes, 16-byte aligned (vertex offsets, face offsets, rank map [N,P] int32).
+ * Both entry points synchronise the stream (the counts return to the host).  N * P and the face bound 2 * N * P (double_sided:
+ * 4 * N * P) must be below 2^31.
+ *   a3r_align_scene_mesh_count : *n_vertices_host = V, *n_faces_host = F.
+ *   a3r_align_scene_mesh_export: counts afresh, then writes out_xyz [V,3], out_faces [F,3] and, where non-NULL, out_vertex_rgb [V,3]
+ *     and out_face_rgb [F,3] (both need rgb).  A3R_EINVAL BEFORE any output element is written: a null handle, conf or workspace, a
+ *     workspace that is too small or misaligned, a colour output without rgb, vertex_capacity < V or face_capacity < F (the needed
+ *     counts are still returned), totals that do not fit.  Elements at and beyond V / F are never written; V = 0 and F = 0 are
+ *     successes. */
+size_t a3r_align_scene_mesh_workspace_bytes(int N, int P);
+int a3r_align_scene_mesh_count(a3r_align_t a, const float* conf, float thr, const uint8_t* dyn, void* workspace, size_t workspace_bytes,
+                               int double_sided, long long* n_vertices_host, long long* n_faces_host, void* stream);
+int a3r_align_scene_mesh_export(a3r_align_t a, const float* conf, float thr, const uint8_t* dyn, const uint8_t* rgb, void* workspace,
+                                size_t workspace_bytes, int double_sided, long long vertex_capacity, long long face_capacity,
+                                float* out_xyz, uint8_t* out_vertex_rgb, int* out_faces, uint8_t* out_face_rgb,
+                                long long* n_vertices_host, long long* n_faces_host, void* stream);
+
 /* clean_pointcloud (cloud_opt/base_opt.py:468-503) on the handle's CURRENT state: conf [N,P] fp32 (device) is updated in place, as if
  * the images were processed in order i = 0 .. N-1 and, for every pixel p < h_i * w_i of image i, the other views j in increasing order:
  *     (cx, cy, z) = R_j^T (world(i,p) - t_j);  u = rint(f_j cx / z + ppx_j), v = rint(f_j cy / z + ppy_j)   (half to even)
