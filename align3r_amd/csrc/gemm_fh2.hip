@@ -15,6 +15,7 @@
 // gemm_common.h (bias, GELU, residuals, RoPE, fp32 / bf3 outputs); out_fh2 writes the two-plane fp16 form for the next GEMM.
 #include "gemm_common.h"
 #include "fh2.h"
+#include "fh2_chooser.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -484,28 +485,10 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x
     fh2_publish_block(out, m, s_red);
 }
 
-struct Fh2Tile { int bm, bn, occ; double eff; };
-// 0: 256x128, 16 waves (4x4), 3 stages of 48 KB, one workgroup per CU.   1: 128x64, 8 waves (4x2), two workgroups per CU, for launches
-// whose tile count quantises badly.   2: 128x128, 8 waves (2x4), 2 stages of 32 KB, TWO workgroups per CU -- one workgroup's epilogue
-// (and its barrier waits) run under the other's matrix work: +4 % over tile 0 on the forward's shapes although it moves 1.33x the
-// operand bytes per flop (same-call A/B, tools/bench_fh2.py).   3: 256x128 with 8 waves of 64x64 (a third fewer LDS fragment reads,
-// 224 VGPRs): 17 % slower (two waves per SIMD hide neither the barrier nor the longer per-wave epilogue); kept for A3R_FH2_TILE=3.
-static const Fh2Tile kFh2Tiles[4] = {{256, 128, 1, 0.96}, {128, 64, 2, 0.82}, {128, 128, 2, 1.0}, {256, 128, 1, 0.0}};
-
-static int choose_fh2_tile(int M, int N, int groups) {
-    if (const char* f = getenv("A3R_FH2_TILE")) {      // developer override: 0 | 1
-        const int t = atoi(f);
-        if (t >= 0 && t < 4) return t;
-    }
-    int best_t = 0;
-    double best = 1e300;
-    for (int t = 0; t < 3; t++) {
-        const long n = (long)((M + kFh2Tiles[t].bm - 1) / kFh2Tiles[t].bm) * ((N + kFh2Tiles[t].bn - 1) / kFh2Tiles[t].bn) * groups;
-        const long slots = 256L * kFh2Tiles[t].occ;
-        const double cost = (double)((n + slots - 1) / slots) * kFh2Tiles[t].bm * kFh2Tiles[t].bn * kFh2Tiles[t].occ / kFh2Tiles[t].eff;
-        if (cost < best * 0.999) { best = cost; best_t = t; }
-    }
-    return best_t;
+// the tile table and the chooser: fh2_chooser.h.  A3R_FH2_TILE=0..3 (developer override) is read per call.
+static int fh2_forced_tile() {
+    const char* f = getenv("A3R_FH2_TILE");
+    return f ? atoi(f) : -1;
 }
 
 // process-wide arithmetic mode of the fh2 matrix kernels (a3r_fh2_set_passes): 3 (fp32-grade, default) or 1 (fp16 operands)
@@ -529,7 +512,7 @@ static int launch_fh2(Fh2Args& fa, hipStream_t st) {
     GemmArgs& g = fa.g;
     g.direct_epilogue = 0;
     static const int gm_env = getenv("A3R_FH2_GM") ? atoi(getenv("A3R_FH2_GM")) : 0;
-    int t = choose_fh2_tile(g.M, g.N, g.groups);
+    int t = choose_fh2_tile(g.M, g.N, g.groups, fh2_forced_tile(), AMODE == 0);      // the table behind the fit holds linear shapes only
     if (g.epi.epi == A3R_EPI_HEAD && t != 0) t = 2;   // the HEAD epilogue is built for tiles 0 and 2
     if (AMODE == 1 && t == 3) t = 2;                  // (tile 3 is a linear-only lab tile; the 128x64 tile serves convolutions with
                                                       // 64 or 192 output channels -- the flow network's -- without a half-empty tile)
