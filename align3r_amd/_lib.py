@@ -248,6 +248,12 @@ SIGNATURES = {
     "a3r_depth_eval_workspace_bytes": (C.c_size_t, [C.c_long]),
     "a3r_depth_align": (C.c_int, [c_void, c_void, C.c_long, C.c_double, C.c_int, c_void, C.c_size_t, c_void, c_void, c_void]),
     "a3r_depth_metrics": (C.c_int, [c_void, c_void, C.c_long, C.c_double, c_void, c_void, C.c_size_t, c_void, c_void]),
+    "a3r_nn_chunks": (C.c_int, [C.c_longlong, C.c_longlong, C.c_int]),
+    "a3r_nn_workspace_bytes": (C.c_size_t, [C.c_longlong, C.c_longlong, C.c_int]),
+    "a3r_nn_search": (C.c_int, [c_void, C.c_longlong, c_void, C.c_longlong, C.c_int, c_void, C.c_size_t, c_void, c_void, c_void]),
+    "a3r_match_workspace_bytes": (C.c_size_t, [C.c_longlong, C.c_longlong, C.c_int]),
+    "a3r_reciprocal_matches": (C.c_int, [c_void, C.c_longlong, c_void, C.c_longlong, C.c_int, c_void, C.c_size_t, c_void, c_void, c_void,
+                                         C.c_longlong, c_void, C.POINTER(C.c_longlong), c_void]),
 }
 
 _lib = None

@@ -437,6 +437,40 @@ class PointCloudOptimizer:
         write_ply(path, pc['xyz'].cpu().numpy(), pc['rgb'].cpu().numpy() if 'rgb' in pc else None)
         return pc
 
+    def get_matches(self, i, j, min_conf_thr=None, mask_dynamic=False):
+        """Dense pixel correspondences between images i and j: the reciprocal 3-D nearest neighbours (find_reciprocal_matches of
+        dust3r/utils/geometry.py, computed by csrc/match.hip) between the kept points of the two images -- the rows that
+        get_pointcloud(min_conf_thr, mask_dynamic, with_index=True) returns for them, same keep rule.  Dict of device tensors, one row
+        per match in ascending order of image j's kept pixels: idx_i, idx_j [M] int32 pixel indices y * w + x in each image's own
+        shape; xy_i, xy_j [M,2] int32, x first (as xy_grid); xyz_i, xyz_j [M,3] the matched points; and count = M."""
+        for k in (i, j):
+            if not 0 <= int(k) < self.n_imgs:
+                raise IndexError(f'get_matches: image {k} is outside the scene of {self.n_imgs} images')
+        i, j = int(i), int(j)
+        if i == j:
+            raise ValueError(f'get_matches: i == j == {i}: a correspondence needs two images')
+        return self.matches_from_cloud(self.get_pointcloud(min_conf_thr=min_conf_thr, mask_dynamic=mask_dynamic, with_index=True), i, j)
+
+    def matches_from_cloud(self, pc, i, j):
+        """get_matches(i, j) on a cloud already exported with get_pointcloud(..., with_index=True): a caller that wants many pairs
+        exports once.  i and j are taken as checked."""
+        from ... import ops
+        index, xyz, P = pc['index'], pc['xyz'], self.max_area
+        # the cloud is image-major: the rows of image n are those with n * P <= index < (n + 1) * P (the export keeps N * P below
+        # 2^31, so every edge fits the index's int32)
+        edges = torch.tensor([i * P, (i + 1) * P, j * P, (j + 1) * P], dtype=index.dtype, device=index.device)
+        i0, i1, j0, j1 = torch.searchsorted(index, edges).tolist()
+        m = ops.reciprocal_matches(xyz[i0:i1], xyz[j0:j1])
+        k1, k2 = m['pairs'][:, 0].long(), m['pairs'][:, 1].long()
+        out = dict(count=m['count'])
+        for name, n, lo, hi, k in (('i', i, i0, i1, k1), ('j', j, j0, j1, k2)):
+            p = index[lo:hi][k] - n * P
+            w = self.imshapes[n][1]
+            out['idx_' + name] = p
+            out['xy_' + name] = torch.stack([p % w, torch.div(p, w, rounding_mode='floor')], 1)
+            out['xyz_' + name] = xyz[lo:hi][k]
+        return out
+
     def clean_pointcloud(self, tol=0.001, bad_conf=0, dbg=()):
         """base_opt.py:268-278: lower the confidence of points that another, more confident view sees through.  Computed by the
         aligner handle from its own state (csrc/scene.hip, AlignEngine.clean_confidences): the decisions are those of the

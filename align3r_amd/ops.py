@@ -658,3 +658,60 @@ def depth_metrics(pred, gt, depth_max, scale, shift=None):
     with torch.cuda.device(pred.device):
         check(lib.a3r_depth_metrics(ptr(pred), ptr(gt), n, float(depth_max), ptr(st), ptr(ws), ws_bytes, ptr(out), stream_ptr()), "depth_metrics")
     return out
+
+
+def _req_points(t, name):
+    _req(t, name)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise RuntimeError(f"{name} must be [n, 3]")
+    return t
+
+
+def nn_chunks(n_query, n_data, chunks=0) -> int:
+    """The number of data ranges a search of these sizes uses (a3r_nn_chunks): `chunks` itself when forced, the library's choice for 0."""
+    return int(_lib.load().a3r_nn_chunks(int(n_query), int(n_data), int(chunks)))
+
+
+def nn_search(query, data, chunks=0, return_dist=False):
+    """Exact nearest neighbour of every query point among the data points (a3r_nn_search, csrc/match.hip): float64 squared distances
+    from direct differences, the lowest index of a tie, -1 where no data point is at a finite distance (include/a3r.h has the
+    definition).  query [nq,3], data [nd,3]: contiguous float32 device tensors.  chunks: 0 = the library's choice, >= 1 forces that
+    many data ranges (the result does not depend on it).  Enqueue-only; returns index [nq] int32, and with return_dist also the
+    squared distance [nq] float64 (+inf where the index is -1)."""
+    _req_points(query, "query"); _req_points(data, "data")
+    if query.device != data.device:
+        raise RuntimeError(f"nn_search: query is on {query.device}, data on {data.device}")
+    lib, dev = _lib.load(), query.device
+    nq, nd = query.shape[0], data.shape[0]
+    ws_bytes = int(lib.a3r_nn_workspace_bytes(nq, nd, int(chunks)))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    index = torch.empty(nq, dtype=torch.int32, device=dev)
+    dist = torch.empty(nq, dtype=torch.float64, device=dev) if return_dist else None
+    with torch.cuda.device(dev):
+        check(lib.a3r_nn_search(ptr(query), nq, ptr(data), nd, int(chunks), ptr(ws), ws_bytes, ptr(index), ptr(dist), stream_ptr()), "nn_search")
+    return (index, dist) if return_dist else index          # the workspace is freed stream-ordered after the kernels
+
+
+def reciprocal_matches(p1, p2, chunks=0):
+    """find_reciprocal_matches (dust3r/utils/geometry.py:351-367) on the device with nn_search's neighbour rule (a3r_reciprocal_matches).
+    p1 [n1,3], p2 [n2,3]: contiguous float32 device tensors.  Returns a dict of device tensors: nn2_in_P1 [n2] int32, nn1_in_P2 [n1]
+    int32, reciprocal_in_P2 [n2] bool, pairs [M,2] int32 = (k1, k2) of the reciprocal k2 in ascending k2, and count = M (an int: the
+    call synchronises once to learn it)."""
+    _req_points(p1, "p1"); _req_points(p2, "p2")
+    if p1.device != p2.device:
+        raise RuntimeError(f"reciprocal_matches: p1 is on {p1.device}, p2 on {p2.device}")
+    lib, dev = _lib.load(), p1.device
+    n1, n2 = p1.shape[0], p2.shape[0]
+    ws_bytes = int(lib.a3r_match_workspace_bytes(n1, n2, int(chunks)))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    nn2 = torch.empty(n2, dtype=torch.int32, device=dev)
+    nn1 = torch.empty(n1, dtype=torch.int32, device=dev)
+    rec = torch.empty(n2, dtype=torch.uint8, device=dev)
+    cap = min(n1, n2)                                        # a k1 is the partner of at most one k2
+    pairs = torch.empty((cap, 2), dtype=torch.int32, device=dev)
+    count = C.c_longlong(0)
+    with torch.cuda.device(dev):
+        check(lib.a3r_reciprocal_matches(ptr(p1), n1, ptr(p2), n2, int(chunks), ptr(ws), ws_bytes, ptr(nn2), ptr(nn1), ptr(rec), cap,
+                                         ptr(pairs), C.byref(count), stream_ptr()), "reciprocal_matches")
+    M = int(count.value)
+    return dict(nn2_in_P1=nn2, nn1_in_P2=nn1, reciprocal_in_P2=rec.view(torch.bool), pairs=pairs[:M], count=M)

@@ -5,10 +5,11 @@ The flow of the reference's tool/demo.py and tool/depth_test.py through this pac
     load_images (N3)  ->  make_pairs  ->  inference (HIP pair forward)  ->  global_aligner / hierarchical_alignment (HIP aligner, N2)
     ->  pred_traj.txt, pred_intrinsics.txt, frame_XXXX.npy, conf_X.npy   (+ depth metrics when ground truth is given)
     ->  --pointcloud PATH: the aligned scene as a binary PLY (points above --min-conf-thr, compacted on the device)
+    ->  --matches DIR: matches_{i}_{i+1}.npz, the reciprocal 3-D nearest-neighbour pixel correspondences of consecutive frames
 
     python -m align3r_amd.tool.run_clip --images DIR --weights CKPT.pth --out OUT [--size 512] [--scene-graph swin-3-noncyclic]
            [--hierarchical --clip-size 50] [--niter 300] [--schedule linear] [--lr 0.01] [--traj-format custom] [--gt-depth DIR]
-           [--metrics-device] [--pointcloud scene.ply] [--clean] [--device-prep]
+           [--metrics-device] [--pointcloud scene.ply] [--matches DIR] [--clean] [--device-prep]
            [--flow [--flow-weights RAFT.pth] [--gt-masks DIR] [--not-shared-focal]]
            [--flow-hierarchical [--clip-size 10] [--device-resident] [--flow-weights ...] [--gt-masks DIR] [--not-shared-focal]]
 
@@ -61,6 +62,12 @@ def parse(argv=None):
                          "quad whose corners are kept; with --hierarchical: every clip's mesh, appended in clip order)")
     ap.add_argument("--mesh-double-sided", action="store_true",
                     help="--mesh: every triangle also wound backwards (what the reference hands to its viewer against face culling)")
+    ap.add_argument("--matches", default=None, metavar="DIR",
+                    help="after the alignment (and after --clean) write DIR/matches_{i}_{i+1}.npz for every consecutive frame pair: the "
+                         "reciprocal 3-D nearest neighbours between the two frames' points above --min-conf-thr (scene.get_matches, "
+                         "csrc/match.hip; keys idx_i idx_j xy_i xy_j xyz_i xyz_j count); with --flow the dynamic pixels are masked out. "
+                         "Refused with --hierarchical and --flow-hierarchical: their clips are aligned one after another and no "
+                         "scene holds two neighbouring clips' frames at once")
     ap.add_argument("--clean", action="store_true",
                     help="scene.clean_pointcloud() after every alignment: confidences of points another, more confident view sees through "
                          "drop to 0 before conf_X.npy and --pointcloud are written (tool/demo.py: clean_depth)")
@@ -86,6 +93,8 @@ def parse(argv=None):
         ap.error("--flow cannot be combined with --hierarchical: the keyframe / clip alignment has no flow term")
     if a.flow_hierarchical and (a.flow or a.hierarchical):
         ap.error("--flow-hierarchical stands alone: it implies the --flow settings and is its own keyframe / clip driver")
+    if a.matches and (a.hierarchical or a.flow_hierarchical):
+        ap.error("--matches cannot be combined with --hierarchical or --flow-hierarchical: it needs one scene holding all frames")
     if a.device_resident and not a.flow_hierarchical:
         ap.error("--device-resident belongs to --flow-hierarchical")
     if a.metrics_device and not a.gt_depth:
@@ -101,6 +110,19 @@ def parse(argv=None):
     if a.scene_graph is None:
         a.scene_graph = "swinstride-5-noncyclic" if a.flow else "swin-3-noncyclic"
     return a
+
+
+def write_matches(scene, out_dir, mask_dynamic=False):
+    """scene.get_matches(i, i + 1) for every consecutive pair as out_dir/matches_{i}_{i+1}.npz (host arrays); returns the counts."""
+    os.makedirs(out_dir, exist_ok=True)
+    counts = []
+    pc = scene.get_pointcloud(mask_dynamic=mask_dynamic, with_index=True)          # one export for all pairs
+    for i in range(scene.n_imgs - 1):
+        m = scene.matches_from_cloud(pc, i, i + 1)
+        np.savez(os.path.join(out_dir, f"matches_{i}_{i + 1}.npz"),
+                 **{k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in m.items()})
+        counts.append(int(m["count"]))
+    return counts
 
 
 def main(argv=None):
@@ -123,6 +145,7 @@ def main(argv=None):
     os.makedirs(a.out, exist_ok=True)
     clouds, n_points = ([] if a.pointcloud else None), None
     meshes, n_mesh = ([] if a.mesh else None), None              # n_mesh: (vertices, faces) written
+    n_matches = None                   # --matches: matches written per consecutive pair
     depths_dev = None                  # --metrics-device: the aligned depth maps as the scene holds them, on the device
     if a.flow_hierarchical and len(imgs) < 3:
         raise RuntimeError("--flow-hierarchical needs at least 3 frames")
@@ -182,6 +205,10 @@ def main(argv=None):
             if mode != GlobalAlignerMode.PointCloudOptimizer:
                 raise RuntimeError("--pointcloud needs at least 3 frames (the two-frame PairViewer has no aligner handle to export from)")
             n_points = int(scene.save_pointcloud(a.pointcloud)["xyz"].shape[0])
+        if a.matches:
+            if mode != GlobalAlignerMode.PointCloudOptimizer:
+                raise RuntimeError("--matches needs at least 3 frames (the two-frame PairViewer has no aligner handle to export from)")
+            n_matches = write_matches(scene, a.matches, mask_dynamic=a.flow)
         if a.mesh:
             if mode != GlobalAlignerMode.PointCloudOptimizer:
                 raise RuntimeError("--mesh needs at least 3 frames (the two-frame PairViewer has no aligner handle to export from)")
@@ -211,6 +238,8 @@ def main(argv=None):
     res_out = dict(n_frames=len(depths), out=a.out, metrics=metrics, pose_metrics=pose)
     if a.pointcloud:
         res_out["pointcloud"], res_out["n_points"] = a.pointcloud, n_points
+    if a.matches:
+        res_out["matches"], res_out["n_matches"] = a.matches, n_matches
     if a.mesh:
         res_out["mesh"], res_out["n_vertices"], res_out["n_faces"] = a.mesh, n_mesh[0], n_mesh[1]
     return res_out

@@ -902,6 +902,47 @@ int a3r_depth_align(const float* pred, const float* gt, long n, double depth_max
 int a3r_depth_metrics(const float* pred, const float* gt, long n, double depth_max, const double* st_dev, void* workspace,
                       size_t workspace_bytes, double* out_dev, void* stream);
 
+/* Point correspondences (csrc/match.hip): exact 3-D nearest neighbours by brute force and the reciprocity test of
+ * find_reciprocal_matches (dust3r/utils/geometry.py:351-367, two KD-trees on the host there).  Points are fp32 [n,3], device memory.
+ * For a query q and a data point k, in float64 with every operation rounded on its own (no fused multiply-add):
+ *     dx = (double)q.x - (double)data[k].x  (dy, dz likewise);   d2 = (dx * dx + dy * dy) + dz * dz
+ *     nn(q) = the SMALLEST k with d2(q, k) = min over { k : d2(q, k) < +inf },   -1 if that set is empty
+ * -- what numpy gives with dx*dx + dy*dy + dz*dz on float64 copies and np.argmin's first-minimum rule.  The search starts from
+ * (+inf, -1) and compares with a strict <, so a NaN or infinite coordinate, in the query or in the data, never wins and never becomes
+ * an index, and an empty data set gives -1 everywhere.
+ * Passes, no atomics and no data-dependent control flow (the output is a function of the inputs alone): the data set is cut into
+ * `chunks` contiguous index ranges [n_data c / chunks, n_data (c + 1) / chunks) on a second grid axis, each (query, range) leaves one
+ * partial (d2, index), and a fold walks a query's partials in ascending range order with the same strict <; the result therefore does
+ * not depend on `chunks`.  chunks = 0 lets the library choose (a3r_nn_chunks says what it chose: enough workgroups to fill the device,
+ * never more ranges than LDS tiles of data, at most 64); chunks >= 1 forces that many ranges (at most 65535; ranges are empty when
+ * chunks > n_data).  It is the tuning knob of the search.
+ * workspace: a3r_nn_workspace_bytes(n_query, n_data, chunks) bytes, 16-byte aligned: partial d2 [chunks, n_query] float64, then partial
+ * index [chunks, n_query] int32, each rounded up to 256 bytes; 0 bytes (workspace may be NULL) when either size is 0.
+ *   a3r_nn_search: out_index [n_query] int32; out_dist2 [n_query] float64 or NULL = the minimum, +inf where the index is -1.  It only
+ *     enqueues on `stream`: nothing is allocated, synchronised or read back.
+ * Reciprocal matches of (p1 [n1,3], p2 [n2,3]), the reference's contract:
+ *     nn2_in_p1[k2] = nn of p2[k2] in p1;   nn1_in_p2[k1] = nn of p1[k1] in p2
+ *     reciprocal_in_p2[k2] = (nn2_in_p1[k2] >= 0 and nn1_in_p2[nn2_in_p1[k2]] == k2)
+ * The match list is the pairs (nn2_in_p1[k2], k2) of the reciprocal k2 in ascending k2, M of them (flags and per-block counts by wave
+ * ballots, an exclusive scan, placement by rank).
+ * workspace: a3r_match_workspace_bytes(n1, n2, chunks) bytes, 16-byte aligned: the search partials of the larger direction,
+ * nn1_in_p2 [n1] int32, the block offsets; 0 bytes when either size is 0.
+ *   a3r_reciprocal_matches: writes nn2_in_p1 [n2], reciprocal_in_p2 [n2] (0 / 1) and, where non-NULL, nn1_in_p2 [n1] and
+ *     out_pairs [M,2] int32 (k1, k2).  *n_matches_host = M.  It synchronises the stream once (the count returns to the host); the pairs
+ *     are enqueued after that.  With out_pairs given, capacity (in pairs) < M is A3R_EINVAL BEFORE any pair is written, with
+ *     *n_matches_host = the needed count and the three other outputs complete; elements at and beyond M are never written; without
+ *     out_pairs the capacity is not looked at.  n1 = 0 or n2 = 0 is a success with zero matches (-1 and 0 everywhere).
+ * A3R_EINVAL before anything is launched: a null pointer to a non-empty array, a negative size, a size at or above 2^31, chunks
+ * outside [0, 65535], a workspace that is too small or misaligned, a negative capacity, a null n_matches_host. */
+int a3r_nn_chunks(long long n_query, long long n_data, int chunks);           /* the range count a search uses; 0 for refused arguments */
+size_t a3r_nn_workspace_bytes(long long n_query, long long n_data, int chunks);
+int a3r_nn_search(const float* query, long long n_query, const float* data, long long n_data, int chunks, void* workspace,
+                  size_t workspace_bytes, int* out_index, double* out_dist2, void* stream);
+size_t a3r_match_workspace_bytes(long long n1, long long n2, int chunks);
+int a3r_reciprocal_matches(const float* p1, long long n1, const float* p2, long long n2, int chunks, void* workspace,
+                           size_t workspace_bytes, int* nn2_in_p1, int* nn1_in_p2, unsigned char* reciprocal_in_p2, long long capacity,
+                           int* out_pairs, long long* n_matches_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
