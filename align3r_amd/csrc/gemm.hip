@@ -24,6 +24,55 @@
 namespace a3r {
 
 constexpr int BK = 32, LDP = 36;
+static_assert(BK == 32, "the shared entry checks ask for K % 32 == 0");
+
+// Epilogue over the 32x32 MFMA accumulators of one wave: acc[i][j] covers rows m0 + wrow0 + 32 i .. and columns
+// n0 + wcol0 + 32 j ..; element e of a lane sits at row (e&3) + 8 (e>>2) + 4 (lane>>5), column lane&31.
+template <int TM, int TN, bool FULL>
+__device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const GroupPtrs& P, f32x16 (&acc)[TM][TN], int m0, int n0,
+                                              int wrow0, int wcol0, int lane) {
+    const a3r_epilogue& ep = g.epi;
+    const int half = lane >> 5, lcol = lane & 31;
+    const int epi = ep.epi;
+#pragma unroll
+    for (int j = 0; j < TN; j++) {
+        const int colbase = n0 + wcol0 + j * 32;
+        const int col = colbase + lcol;
+        const bool col_ok = FULL || col < g.N;
+        const float bias = (P.bias && col_ok) ? P.bias[epi == A3R_EPI_PIXSHUF ? col % ep.ps_cout : col] : 0.f;
+        const bool do_rope = epi == A3R_EPI_ROPE && colbase < ep.rope_cols;   // wave-uniform (rope_cols % 64 == 0)
+        const bool rope_x = (colbase & 32) != 0;                               // second half of the head rotates with x
+#pragma unroll
+        for (int i = 0; i < TM; i++) {
+#pragma unroll
+            for (int e = 0; e < 16; e++) {
+                const int row = m0 + wrow0 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
+                float v = acc[i][j][e] + bias;
+                if (do_rope) {
+                    const float other = __shfl_xor(v, 16);            // the partner (d, d+16) of a 32-wide tile's column is 16 lanes away
+                    v = rope_rotate(ep, v, other, row, lcol & 15, rope_x, (lcol & 16) != 0);
+                }
+                if ((FULL || row < g.M) && col_ok) {
+                    if (epi == A3R_EPI_GELU) v = gelu_erf(v);
+                    else if (epi == A3R_EPI_RELU) v = fmaxf(v, 0.f);
+                    else if (epi == A3R_EPI_RESID) v = P.resid[(size_t)row * g.ldc + col] + v;
+                    else if (epi == A3R_EPI_RESID2) v = P.resid[(size_t)row * g.ldc + col] + P.resid2[(size_t)row * g.ldc + col] + v;
+                    if (epi == A3R_EPI_PIXSHUF) {
+                        const int s = ep.ps_s, hw = ep.ps_h * ep.ps_w;
+                        const int b = row / hw, rem = row - b * hw;
+                        const int y = rem / ep.ps_w, x = rem - y * ep.ps_w;
+                        const int tap = col / ep.ps_cout, co = col - tap * ep.ps_cout;
+                        const int dy = tap / s, dx = tap - dy * s;
+                        const size_t opix = ((size_t)b * ep.ps_h * s + (y * s + dy)) * (ep.ps_w * s) + (x * s + dx);
+                        P.C[opix * ep.ps_cout + co] = v;
+                    } else {
+                        P.C[(size_t)row * g.ldc + col] = v;
+                    }
+                }
+            }
+        }
+    }
+}
 
 // AMODE 0: A is [M, lda] row-major.  AMODE 1: implicit 3x3 conv gather.
 // FULL: M % BM == 0 && N % BN == 0 (no bounds predication; AMODE 0 only).  RELU_A: relu on the A operand.
@@ -36,7 +85,8 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
     float* As = reinterpret_cast<float*>(smem);                 // [2][BM][LDP]
     float* Bs = As + 2 * BM * LDP;                              // [2][BN][LDP]
 
-    // XCD-aware bijective remap (blocks b and b+8 share an XCD)
+    // XCD-aware bijective remap (blocks b and b+8 share an XCD); written out here: through tile_in_group (gemm_tile.h) every
+    // instantiation compiles to other instructions
     const int nwg = g.tiles_per_group * g.groups;
     const int orig = blockIdx.x;
     const int xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
@@ -160,13 +210,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
 
 template <int AMODE, int BM, int BN, bool FULL, bool RELU_A>
 static int launch_variant(const GemmArgs& g, hipStream_t st) {
-    auto kern = gemm_kernel<AMODE, BM, BN, FULL, RELU_A>;
-    constexpr int lds = 2 * (BM + BN) * LDP * 4;
-    static PerDeviceOnce attr_once;
-    A3R_HIP(attr_once.ensure([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds); }));
-    hipLaunchKernelGGL(kern, dim3(g.tiles_per_group * g.groups), dim3(256), lds, st, g);
-    A3R_LAUNCH_CHECK();
-    return A3R_OK;
+    return launch_tiles<gemm_kernel<AMODE, BM, BN, FULL, RELU_A>, 256, 2 * (BM + BN) * LDP * 4>(g, g, st);
 }
 
 // Tile choice.  Workgroups resident on a CU share its MFMA pipes, so a launch of n equal workgroups takes about
@@ -192,10 +236,7 @@ static int launch_gemm(int amode, GemmArgs& g, hipStream_t st) {
         int a = 0, b = 0;
         if (sscanf(f, "%dx%d", &a, &b) == 2 && ((a == 128 && (b == 128 || b == 64)) || (a == 64 && b == 64))) { bm = a; bn = b; }
     }
-    g.tiles_m = (g.M + bm - 1) / bm;
-    g.tiles_n = (g.N + bn - 1) / bn;
-    g.tiles_per_group = g.tiles_m * g.tiles_n;
-    const bool full = g.M % bm == 0 && g.N % bn == 0;
+    const bool full = set_tiles(g, bm, bn);
     const bool relu = g.epi.relu_a != 0;
     ProfScope prof(amode == 0 ? PK_LINEAR : PK_CONV, 2.0 * g.M * g.N * g.K * g.groups, st);
 #define A3R_TILE_DISPATCH(AM, FULLV, RELUV)                                                  \
@@ -219,21 +260,15 @@ using namespace a3r;
 
 extern "C" int a3r_linear_grouped(const a3r_group_ptrs* groups, int n_groups, int lda, int ldc, int M, int N, int K,
                                   const a3r_epilogue* epi, void* stream) {
-    A3R_CHECK_ARG(groups && n_groups >= 1 && n_groups <= 4, "a3r_linear_grouped: 1..4 groups required");
-    A3R_CHECK_ARG(M > 0 && N > 0 && K > 0, "a3r_linear: M, N, K must be positive (got %d, %d, %d)", M, N, K);
-    A3R_CHECK_ARG(K % BK == 0, "a3r_linear: K (%d) must be a multiple of %d", K, BK);
+    if (int rc = check_linear_dims("a3r_linear", groups && n_groups >= 1 && n_groups <= 4, M, N, K)) return rc;
     A3R_CHECK_ARG(lda >= K && lda % 4 == 0 && ldc >= 1, "a3r_linear: bad leading dimensions lda=%d ldc=%d", lda, ldc);
     if (int rc = check_epilogue(epi, M, N, "a3r_linear")) return rc;
     GemmArgs g = {};
     if (epi) g.epi = *epi;
     A3R_CHECK_ARG(!g.epi.relu_a, "a3r_linear: relu_a is only available on a3r_conv3x3");
-    for (int i = 0; i < n_groups; i++) {
-        g.grp[i] = {groups[i].x, groups[i].w, groups[i].y, groups[i].bias, groups[i].resid, groups[i].resid2};
-        if (int rc = check_group(g.grp[i], g.epi.epi, "a3r_linear")) return rc;
-    }
-    g.groups = n_groups;
-    g.lda = lda; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
-    if (g.epi.epi != A3R_EPI_PIXSHUF) A3R_CHECK_ARG(ldc >= N, "a3r_linear: ldc (%d) < N (%d)", ldc, N);
+    for (int i = 0; i < n_groups; i++)
+        if (int rc = set_group(g, i, groups[i].x, groups[i].w, groups[i].y, groups[i].bias, groups[i].resid, groups[i].resid2, "a3r_linear")) return rc;
+    if (int rc = set_linear_dims(g, n_groups, lda, ldc, M, N, K, "a3r_linear")) return rc;
     return launch_gemm(0, g, as_stream(stream));
 }
 
@@ -245,21 +280,9 @@ extern "C" int a3r_linear(const float* x, int lda, const float* w, float* y, int
 
 extern "C" int a3r_conv3x3(const float* x, const float* wp, float* y, int B, int H, int W, int Cin, int Cout,
                            int stride, const a3r_epilogue* epi, void* stream) {
-    A3R_CHECK_ARG(x && wp && y, "a3r_conv3x3: null pointer");
-    A3R_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cout > 0, "a3r_conv3x3: bad shape");
-    A3R_CHECK_ARG(Cin > 0 && Cin % BK == 0, "a3r_conv3x3: Cin (%d) must be a multiple of %d", Cin, BK);
-    A3R_CHECK_ARG(stride == 1 || stride == 2, "a3r_conv3x3: stride must be 1 or 2");
     GemmArgs g = {};
-    g.cH = H; g.cW = W; g.cCin = Cin; g.cStride = stride;
-    g.cHo = (H + 2 - 3) / stride + 1;
-    g.cWo = (W + 2 - 3) / stride + 1;
-    g.lda = 0; g.ldc = Cout;
-    g.M = B * g.cHo * g.cWo; g.N = Cout; g.K = 9 * Cin;
-    if (int rc = check_epilogue(epi, g.M, g.N, "a3r_conv3x3")) return rc;
-    if (epi) g.epi = *epi;
+    if (int rc = set_conv_args(g, "a3r_conv3x3", x && wp && y, B, H, W, Cin, Cout, stride, epi, false, false)) return rc;
     A3R_CHECK_ARG(g.epi.epi != A3R_EPI_PIXSHUF && g.epi.epi != A3R_EPI_ROPE, "a3r_conv3x3: unsupported epilogue");
-    g.groups = 1;
-    g.grp[0] = {x, wp, y, g.epi.bias, g.epi.resid, g.epi.resid2};
-    if (int rc = check_group(g.grp[0], g.epi.epi, "a3r_conv3x3")) return rc;
+    if (int rc = set_group(g, 0, x, wp, y, g.epi.bias, g.epi.resid, g.epi.resid2, "a3r_conv3x3")) return rc;
     return launch_gemm(1, g, as_stream(stream));
 }

@@ -3,13 +3,13 @@
 //
 // Both operands arrive pre-split into three bf16 planes (bf3.h: x = x0 + x1 + x2 EXACTLY), and
 //     a b  =  a0b0 + (a0b1 + a1b0) + (a0b2 + a1b1 + a2b0)  +  [a1b2 + a2b1 + a2b2, dropped: <= 2^-23 |a b|]
-// is evaluated as six bf16 MFMA passes per k-step (v_mfma_f32_16x16x32_bf16, or 32x32x16).  Every bf16 x bf16 product is exact in the
+// is evaluated as six bf16 MFMA passes per k-step (v_mfma_f32_16x16x32_bf16).  Every bf16 x bf16 product is exact in the
 // fp32 accumulator, so the only errors are the dropped terms (below one fp32 ulp of the product) and the fp32
 // summation itself -- the same error class as the reference's fp32 GEMM (measured in tests/test_gpu_ops.py against
 // float64: not larger than the exact-fp32 MFMA kernel's).  Serves the same call sites as a3r_linear
 // (croco/models/blocks.py:58-169 qkv / proj / fc1 / fc2 / projq / projk / projv, patch embeddings, decoder_embed).
 //
-// Structure (64-wide waves): a workgroup computes a BM x BN tile with WM x WN waves, each wave a grid of 32x32 MFMA
+// Structure (64-wide waves): a workgroup computes a BM x BN tile with WM x WN waves, each wave a grid of 16x16 MFMA
 // accumulators.  K is walked in BK-deep stages copied global -> LDS by LDS-DMA (global_load_lds_dwordx4: no VGPR
 // staging, no ds_write), NS stages deep, one raw s_barrier per stage with a counted s_waitcnt vmcnt so that the
 // next stage's DMA stays in flight across the barrier.  The LDS image of a stage is the plain row-major bf3 tile
@@ -23,24 +23,11 @@
 
 namespace a3r {
 
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-// s_waitcnt takes an immediate: dispatch over the counts that occur (stages in flight x DMAs per stage per wave)
-__device__ __forceinline__ void wait_vmcnt_dyn(int n) {
-    switch (n) {
-        case 0: wait_vmcnt<0>(); break;   case 1: wait_vmcnt<1>(); break;   case 2: wait_vmcnt<2>(); break;
-        case 3: wait_vmcnt<3>(); break;   case 4: wait_vmcnt<4>(); break;   case 5: wait_vmcnt<5>(); break;
-        case 6: wait_vmcnt<6>(); break;   case 7: wait_vmcnt<7>(); break;   case 8: wait_vmcnt<8>(); break;
-        case 9: wait_vmcnt<9>(); break;   case 10: wait_vmcnt<10>(); break; case 12: wait_vmcnt<12>(); break;
-        default: wait_vmcnt<0>(); break;                                    // always safe
-    }
-}
-
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
-// MF: MFMA shape -- 32: v_mfma_f32_32x32x16_bf16 (two 16-deep k-steps per BK = 32 stage); 16: v_mfma_f32_16x16x32_bf16
-// (one 32-deep k-step per stage; at the clocks the chip holds under bf16 MFMA load it delivers ~1.15x the FLOP/s of the
-// 32x32 shape, MI355X_MICROARCH.md "DVFS give-back" (7), and measured here: tools/gemm_bf3_lab.hip).
+// The MFMA is v_mfma_f32_16x16x32_bf16, one 32-deep k-step per stage: at the clocks the chip holds under bf16 MFMA load it delivers
+// ~1.15x the FLOP/s of the 32x32x16 shape (MI355X_MICROARCH.md "DVFS give-back" (7), and measured here: tools/gemm_bf3_lab.hip).
 // all-zero source for the padding taps of the implicit conv (LDS-DMA has no predicated zero fill)
 __device__ __attribute__((aligned(16))) unsigned int g_bf3_zero[4];
 
@@ -49,39 +36,33 @@ __device__ __attribute__((aligned(16))) unsigned int g_bf3_zero[4];
 // 6 BK contiguous bytes of one input pixel, or zeros where the tap falls into the padding.
 // NP: plane products evaluated -- 6: fp32-accurate (default); 3: a0b0 + a0b1 + a1b0 (operands effectively 16 bits, error
 // ~2^-17 per product); 1: a0b0 only = plain bf16 operands with fp32 accumulation (BASELINE config 5's "bf16-MFMA mode").
-template <int AMODE, int BM, int BN, int BK, int WM, int WN, int NS, int MF, bool FULL, int NP>
+template <int AMODE, int BM, int BN, int WM, int WN, int NS, bool FULL, int NP>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_bf3_kernel(GemmArgs g) {
-    constexpr bool M16 = MF == 16;
-    static_assert(MF == 32 || (MF == 16 && BK == 32), "16x16x32 MFMA needs BK = 32");
-    static_assert(BK == 32, "the row-pair weight layout is addressed in 32-deep k blocks");
-    constexpr int NT = WM * WN * 64, KG = BK / 8, U = 3 * KG, G = KG, PER = 16 / G;
+    constexpr int BK = 32;                 // one MFMA k-step; the row-pair weight layout is addressed in 32-deep k blocks
+    constexpr int NT = WM * WN * 64, KG = BK / 8, U = 3 * KG;
     constexpr int WTM = BM / WM, WTN = BN / WN;
     constexpr int SA = BM * U, SB = BN * U;                                 // 16-byte units per stage
     constexpr int LA = (SA + NT - 1) / NT, LB = (SB + NT - 1) / NT;         // DMAs per thread per stage (the last one may cover only the first waves)
     static_assert(SA % 64 == 0 && SB % 64 == 0, "whole waves");
     static_assert(WTN % 32 == 0 && WTM % 32 == 0, "wave tiles are multiples of 32 (RoPE epilogue pairs columns d, d+16)");
     constexpr int STAGE = (SA + SB) * 16;
+    // a wave whose share of a stage's last DMA round is empty issues one DMA fewer per operand
+    constexpr int PA = SA % NT != 0, PB = SB % NT != 0;
+    static_assert(vmcnt_stages_listed(vmcnt_listed, NS - 1, LA + LB) && vmcnt_stages_listed(vmcnt_listed, NS - 1, LA + LB - PA) && vmcnt_stages_listed(vmcnt_listed, NS - 1, LA + LB - PB) &&
+                  vmcnt_stages_listed(vmcnt_listed, NS - 1, LA + LB - PA - PB), "a vmcnt this variant asks for is missing from wait_vmcnt_dyn");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
-    // XCD-aware bijective remap (blocks b and b+8 share an XCD), then group / tile decomposition
-    const int nwg = g.tiles_per_group * g.groups;
-    const int orig = blockIdx.x;
-    const int xcd = orig & 7, q = nwg >> 3, r8 = nwg & 7;
-    int wgid = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (orig >> 3);
-    const int grp = wgid / g.tiles_per_group;
-    wgid -= grp * g.tiles_per_group;
+    int grp, tile_m, tile_n;
+    tile_row_major(tile_in_group(g.tiles_per_group, g.groups, grp), g.tiles_n, tile_m, tile_n);
     const GroupPtrs& P = g.grp[grp];
-    const int tile_m = wgid / g.tiles_n, tile_n = wgid - tile_m * g.tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
-    const size_t pitch = (size_t)g.K * 6;
-    // Source-side rotation of a row's units (the LDS image itself is lane-linear).  32x32x16 operands: 16-lane read groups
-    // hold 16 different rows at one unit -> rotate single units by (r / PER) % G.  16x16x32 operands: a read group holds
+    // Source-side rotation of a row's units (the LDS image itself is lane-linear): a 16-lane read group of the 16x16x32 operand holds
     // rows {0-3, 12-15} at k-group kg and rows {4-11} at kg + 1 -> rotate whole k-groups (3 units) by 2 for rows 8..15 mod 16.
-    auto src_unit = [&](int r, int cp) { return M16 ? (cp + 6 * ((r >> 3) & 1)) % U : (cp + (r / PER) % G) % U; };
+    auto src_unit = [&](int r, int cp) { return (cp + 6 * ((r >> 3) & 1)) % U; };
     const char* srcA[LA];       // AMODE 0: row pointer at k = 0; AMODE 1: the centre tap's pixel, channel 0
     int tapsA[LA];              // AMODE 1: bit t set <=> tap t = 3 dy + dx lies inside the map
     const char* srcB[LB];
@@ -152,117 +133,51 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf3_kernel(GemmArgs g) {
     };
     for (int t = 0; t < NS - 1 && t < nk; t++) issue(t, t);
 
-    if constexpr (!M16) {
-        constexpr int TM = WTM / 32, TN = WTN / 32;
-        f32x16 acc[TM][TN];
+    constexpr int TM = WTM / 16, TN = WTN / 16;
+    f32x4 acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; i++)
+#pragma unroll
+        for (int j = 0; j < TN; j++)
+#pragma unroll
+            for (int e = 0; e < 4; e++) acc[i][j][e] = 0.f;
+    // lane (row = lane & 15, k-group = lane >> 4) reads, per plane p, unit 3 ((kg - rot) mod 4) + p of its row
+    const int frow = lane & 15, kg = lane >> 4, rotk = 2 * ((frow >> 3) & 1);
+    int offA[3], offB[3];
+#pragma unroll
+    for (int p = 0; p < 3; p++) {
+        const int c = 3 * ((kg - rotk + 4) % 4) + p;
+        offA[p] = ((wm * WTM + frow) * U + c) * 16;
+        offB[p] = SA * 16 + ((wn * WTN + frow) * U + c) * 16;
+    }
+    for (int kt = 0; kt < nk; kt++) {
+        acquire(kt);
+        const char* sb = smem + (kt % NS) * STAGE;
+        bf16x8 af[TM][3], bf[TN][3];
 #pragma unroll
         for (int i = 0; i < TM; i++)
 #pragma unroll
-            for (int j = 0; j < TN; j++)
+            for (int p = 0; p < 3; p++) af[i][p] = *reinterpret_cast<const bf16x8*>(sb + offA[p] + i * 16 * U * 16);
 #pragma unroll
-                for (int e = 0; e < 16; e++) acc[i][j][e] = 0.f;
-        // lane (row = lane & 31, k-half = lane >> 5) reads, per k-step s and plane p, unit (2 s + h) 3 + p of its row
-        const int frow = lane & 31, fh = lane >> 5, rot = (frow / PER) % G;
-        int offA[BK / 16][3], offB[BK / 16][3];
+        for (int j = 0; j < TN; j++)
 #pragma unroll
-        for (int s = 0; s < BK / 16; s++)
+            for (int p = 0; p < 3; p++) bf[j][p] = *reinterpret_cast<const bf16x8*>(sb + offB[p] + j * 16 * U * 16);
 #pragma unroll
-            for (int p = 0; p < 3; p++) {
-                const int c = ((2 * s + fh) * 3 + p - rot + U) % U;
-                offA[s][p] = ((wm * WTM + frow) * U + c) * 16;
-                offB[s][p] = SA * 16 + ((wn * WTN + frow) * U + c) * 16;
-            }
-        for (int kt = 0; kt < nk; kt++) {
-            acquire(kt);
-            const char* sb = smem + (kt % NS) * STAGE;
+        for (int i = 0; i < TM; i++)
 #pragma unroll
-            for (int s = 0; s < BK / 16; s++) {
-                bf16x8 af[TM][3], bf[TN][3];
-#pragma unroll
-                for (int i = 0; i < TM; i++)
-#pragma unroll
-                    for (int p = 0; p < 3; p++) af[i][p] = *reinterpret_cast<const bf16x8*>(sb + offA[s][p] + i * 32 * U * 16);
-#pragma unroll
-                for (int j = 0; j < TN; j++)
-#pragma unroll
-                    for (int p = 0; p < 3; p++) bf[j][p] = *reinterpret_cast<const bf16x8*>(sb + offB[s][p] + j * 32 * U * 16);
-#pragma unroll
-                for (int i = 0; i < TM; i++)
-#pragma unroll
-                    for (int j = 0; j < TN; j++) {
-                        // smallest terms first
-                        if (NP == 6) {
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][2], bf[j][0], acc[i][j], 0, 0, 0);
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], bf[j][1], acc[i][j], 0, 0, 0);
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][2], acc[i][j], 0, 0, 0);
-                        }
-                        if (NP >= 3) {
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], bf[j][0], acc[i][j], 0, 0, 0);
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][1], acc[i][j], 0, 0, 0);
-                        }
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][0], acc[i][j], 0, 0, 0);
-                    }
-            }
+            for (int j = 0; j < TN; j++) bf3_mma<NP>(acc[i][j], af[i], bf[j]);
+    }
+    static_assert(NS * STAGE >= WM * WN * epi_lds_wave_bytes(WTM) || TN != 2, "the LDS epilogue image fits in the stage ring");
+    if (TN == 2 && epilogue16_lds_ok(g, P)) {                 // wave-uniform
+        __syncthreads();                                       // every wave is done reading the last stage
+        if constexpr (TN == 2)
+        {
+            float amax_unused = 0.f;                           // (range statistics exist on the fh2 kernels only)
+            gemm_epilogue16_lds<TM, TN, FULL>(g, P, acc, m0, n0, wm * WTM, wn * WTN, lane,
+                                              reinterpret_cast<float*>(smem + wave * epi_lds_wave_bytes(WTM)), &amax_unused);
         }
-        gemm_epilogue<TM, TN, FULL>(g, P, acc, m0, n0, wm * WTM, wn * WTN, lane);
     } else {
-        constexpr int TM = WTM / 16, TN = WTN / 16;
-        f32x4 acc[TM][TN];
-#pragma unroll
-        for (int i = 0; i < TM; i++)
-#pragma unroll
-            for (int j = 0; j < TN; j++)
-#pragma unroll
-                for (int e = 0; e < 4; e++) acc[i][j][e] = 0.f;
-        // lane (row = lane & 15, k-group = lane >> 4) reads, per plane p, unit 3 ((kg - rot) mod 4) + p of its row
-        const int frow = lane & 15, kg = lane >> 4, rotk = 2 * ((frow >> 3) & 1);
-        int offA[3], offB[3];
-#pragma unroll
-        for (int p = 0; p < 3; p++) {
-            const int c = 3 * ((kg - rotk + 4) % 4) + p;
-            offA[p] = ((wm * WTM + frow) * U + c) * 16;
-            offB[p] = SA * 16 + ((wn * WTN + frow) * U + c) * 16;
-        }
-        for (int kt = 0; kt < nk; kt++) {
-            acquire(kt);
-            const char* sb = smem + (kt % NS) * STAGE;
-            bf16x8 af[TM][3], bf[TN][3];
-#pragma unroll
-            for (int i = 0; i < TM; i++)
-#pragma unroll
-                for (int p = 0; p < 3; p++) af[i][p] = *reinterpret_cast<const bf16x8*>(sb + offA[p] + i * 16 * U * 16);
-#pragma unroll
-            for (int j = 0; j < TN; j++)
-#pragma unroll
-                for (int p = 0; p < 3; p++) bf[j][p] = *reinterpret_cast<const bf16x8*>(sb + offB[p] + j * 16 * U * 16);
-#pragma unroll
-            for (int i = 0; i < TM; i++)
-#pragma unroll
-                for (int j = 0; j < TN; j++) {
-                    if (NP == 6) {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][2], bf[j][0], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][1], bf[j][1], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][0], bf[j][2], acc[i][j], 0, 0, 0);
-                    }
-                    if (NP >= 3) {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][1], bf[j][0], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][0], bf[j][1], acc[i][j], 0, 0, 0);
-                    }
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][0], bf[j][0], acc[i][j], 0, 0, 0);
-                }
-        }
-        static_assert(NS * STAGE >= WM * WN * epi_lds_wave_bytes(WTM) || TN != 2, "the LDS epilogue image fits in the stage ring");
-        if (TN == 2 && epilogue16_lds_ok(g, P)) {                 // wave-uniform
-            __syncthreads();                                       // every wave is done reading the last stage
-            if constexpr (TN == 2)
-            {
-                float amax_unused = 0.f;                           // (range statistics exist on the fh2 kernels only)
-                gemm_epilogue16_lds<TM, TN, FULL>(g, P, acc, m0, n0, wm * WTM, wn * WTN, lane,
-                                                  reinterpret_cast<float*>(smem + wave * epi_lds_wave_bytes(WTM)), &amax_unused);
-            }
-        } else {
-            gemm_epilogue16<TM, TN, FULL>(g, P, acc, m0, n0, wm * WTM, wn * WTN, lane);
-        }
+        gemm_epilogue16<TM, TN, FULL>(g, P, acc, m0, n0, wm * WTM, wn * WTN, lane);
     }
 }
 
@@ -280,19 +195,13 @@ __global__ __launch_bounds__(512) void gemm_bf3_w2h_kernel(GemmArgs g) {
     char* As = smem;                        // [2][256 rows][12 units]
     char* Hs = smem + 2 * A_BYTES;          // [2 halves][128 rows][12 units]
 
-    const int nwg = g.tiles_per_group * g.groups;
-    const int orig = blockIdx.x;
-    const int xcd = orig & 7, q = nwg >> 3, r8 = nwg & 7;
-    int wgid = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (orig >> 3);
-    const int grp = wgid / g.tiles_per_group;
-    wgid -= grp * g.tiles_per_group;
+    int grp, tile_m, tile_n;
+    tile_row_major(tile_in_group(g.tiles_per_group, g.groups, grp), g.tiles_n, tile_m, tile_n);
     const GroupPtrs& P = g.grp[grp];
-    const int tile_m = wgid / g.tiles_n, tile_n = wgid - tile_m * g.tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const size_t pitch = (size_t)g.K * 6;
     // 32-bit byte offsets from the tile's first row (256 rows x <= 24 KB); rows past M / N re-read the last valid row
     unsigned offA[LA], offW[2][LH];
 #pragma unroll
@@ -368,19 +277,7 @@ __global__ __launch_bounds__(512) void gemm_bf3_w2h_kernel(GemmArgs g) {
 #pragma unroll
                 for (int j = 0; j < 4; j++)
 #pragma unroll
-                    for (int i = 0; i < 2; i++) {
-                        f32x4& a = acc[half * 4 + c * 2 + (j >> 1)][i][j & 1];
-                        if (NP == 6) {
-                            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][2], bf[j][0], a, 0, 0, 0);
-                            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][1], bf[j][1], a, 0, 0, 0);
-                            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][0], bf[j][2], a, 0, 0, 0);
-                        }
-                        if (NP >= 3) {
-                            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][1], bf[j][0], a, 0, 0, 0);
-                            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][0], bf[j][1], a, 0, 0, 0);
-                        }
-                        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][0], bf[j][0], a, 0, 0, 0);
-                    }
+                    for (int i = 0; i < 2; i++) bf3_mma<NP>(acc[half * 4 + c * 2 + (j >> 1)][i][j & 1], af[i], bf[j]);
             }
         }
     }
@@ -433,27 +330,14 @@ static int choose_bf3_tile(int M, int N, int groups, bool linear) {
 static int g_bf3_products = 6;
 int bf3_products() { return g_bf3_products; }
 
-template <int AMODE, int BM, int BN, int BK, int WM, int WN, int NS, int MF, bool FULL, int NP>
+template <int AMODE, int BM, int BN, int WM, int WN, int NS, bool FULL, int NP>
 static int launch_bf3_variant(const GemmArgs& g, hipStream_t st) {
-    auto kern = gemm_bf3_kernel<AMODE, BM, BN, BK, WM, WN, NS, MF, FULL, NP>;
-    constexpr int lds = NS * (BM + BN) * (3 * BK / 8) * 16;
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    static PerDeviceOnce attr_once;
-    A3R_HIP(attr_once.ensure([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds); }));
-    hipLaunchKernelGGL(kern, dim3(g.tiles_per_group * g.groups), dim3(WM * WN * 64), lds, st, g);
-    A3R_LAUNCH_CHECK();
-    return A3R_OK;
+    return launch_tiles<gemm_bf3_kernel<AMODE, BM, BN, WM, WN, NS, FULL, NP>, WM * WN * 64, NS * (BM + BN) * 192>(g, g, st);
 }
 
 template <bool FULL, int NP>
 static int launch_bf3_w2h(const GemmArgs& g, hipStream_t st) {
-    auto kern = gemm_bf3_w2h_kernel<FULL, NP>;
-    constexpr int lds = 2 * 256 * 192 + 2 * 128 * 192;
-    static PerDeviceOnce attr_once;
-    A3R_HIP(attr_once.ensure([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds); }));
-    hipLaunchKernelGGL(kern, dim3(g.tiles_per_group * g.groups), dim3(512), lds, st, g);
-    A3R_LAUNCH_CHECK();
-    return A3R_OK;
+    return launch_tiles<gemm_bf3_w2h_kernel<FULL, NP>, 512, 2 * 256 * 192 + 2 * 128 * 192>(g, g, st);
 }
 
 template <int AMODE>
@@ -461,11 +345,7 @@ static int launch_bf3(GemmArgs& g, hipStream_t st) {
     static const bool direct_epi = getenv("A3R_BF3_DIRECT_EPI") != nullptr;
     g.direct_epilogue = direct_epi ? 1 : 0;
     const int t = choose_bf3_tile(g.M, g.N, g.groups, AMODE == 0);
-    const int bm = kTiles[t].bm, bn = kTiles[t].bn;
-    g.tiles_m = (g.M + bm - 1) / bm;
-    g.tiles_n = (g.N + bn - 1) / bn;
-    g.tiles_per_group = g.tiles_m * g.tiles_n;
-    const bool full = g.M % bm == 0 && g.N % bn == 0;
+    const bool full = set_tiles(g, kTiles[t].bm, kTiles[t].bn);
     // algorithmic bytes: A once (linear: M K 6; conv: the input map B H W Cin 6), W once, results / residuals once
     const double mn = (double)g.M * g.N;
     const double a_bytes = AMODE == 0 ? 6.0 * g.M * g.K : 6.0 * (g.M / (g.cHo * g.cWo)) * g.cH * g.cW * g.cCin;
@@ -475,12 +355,12 @@ static int launch_bf3(GemmArgs& g, hipStream_t st) {
                    g.groups * (a_bytes + 6.0 * g.N * g.K + c_bytes));
 #define A3R_BF3_DISPATCH(NPV)                                                                                                   \
     do {                                                                                                                        \
-        if (t == 0) return full ? launch_bf3_variant<AMODE, 256, 128, 32, 4, 4, 2, 16, true, NPV>(g, st)                        \
-                                : launch_bf3_variant<AMODE, 256, 128, 32, 4, 4, 2, 16, false, NPV>(g, st);                      \
-        if (t == 1) return full ? launch_bf3_variant<AMODE, 128, 64, 32, 2, 2, 2, 16, true, NPV>(g, st)                         \
-                                : launch_bf3_variant<AMODE, 128, 64, 32, 2, 2, 2, 16, false, NPV>(g, st);                       \
-        return full ? launch_bf3_variant<AMODE, 64, 64, 32, 2, 2, 3, 16, true, NPV>(g, st)                                      \
-                    : launch_bf3_variant<AMODE, 64, 64, 32, 2, 2, 3, 16, false, NPV>(g, st);                                    \
+        if (t == 0) return full ? launch_bf3_variant<AMODE, 256, 128, 4, 4, 2, true, NPV>(g, st)                                \
+                                : launch_bf3_variant<AMODE, 256, 128, 4, 4, 2, false, NPV>(g, st);                              \
+        if (t == 1) return full ? launch_bf3_variant<AMODE, 128, 64, 2, 2, 2, true, NPV>(g, st)                                 \
+                                : launch_bf3_variant<AMODE, 128, 64, 2, 2, 2, false, NPV>(g, st);                               \
+        return full ? launch_bf3_variant<AMODE, 64, 64, 2, 2, 3, true, NPV>(g, st)                                              \
+                    : launch_bf3_variant<AMODE, 64, 64, 2, 2, 3, false, NPV>(g, st);                                            \
     } while (0)
     if (AMODE == 0 && t == 3) {
         const int np = g_bf3_products;
@@ -534,23 +414,15 @@ extern "C" int a3r_split_bf3_w(const float* w, int ldw, void* y, long N, int K, 
 
 extern "C" int a3r_linear_bf3_grouped(const a3r_group_ptrs_bf3* groups, int n_groups, int ldc, int M, int N, int K,
                                       const a3r_epilogue* epi, void* stream) {
-    A3R_CHECK_ARG(groups && n_groups >= 1 && n_groups <= 4, "a3r_linear_bf3_grouped: 1..4 groups required");
-    A3R_CHECK_ARG(M > 0 && N > 0 && K > 0, "a3r_linear_bf3: M, N, K must be positive (got %d, %d, %d)", M, N, K);
-    A3R_CHECK_ARG(K % 32 == 0, "a3r_linear_bf3: K (%d) must be a multiple of 32", K);
+    if (int rc = check_linear_dims("a3r_linear_bf3", groups && n_groups >= 1 && n_groups <= 4, M, N, K)) return rc;
     A3R_CHECK_ARG(ldc >= 1, "a3r_linear_bf3: bad leading dimension ldc=%d", ldc);
     if (int rc = check_epilogue(epi, M, N, "a3r_linear_bf3", true)) return rc;
     GemmArgs g = {};
     if (epi) g.epi = *epi;
     A3R_CHECK_ARG(!g.epi.relu_a, "a3r_linear_bf3: relu_a is only available on a3r_conv3x3");
-    for (int i = 0; i < n_groups; i++) {
-        g.grp[i] = {static_cast<const float*>(groups[i].x3), static_cast<const float*>(groups[i].w3), groups[i].y, groups[i].bias,
-                    groups[i].resid, groups[i].resid2};
-        if (int rc = check_group(g.grp[i], g.epi.epi, "a3r_linear_bf3")) return rc;
-    }
-    g.groups = n_groups;
-    g.lda = K; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
-    if (g.epi.epi != A3R_EPI_PIXSHUF) A3R_CHECK_ARG(ldc >= N, "a3r_linear_bf3: ldc (%d) < N (%d)", ldc, N);
-    if (g.epi.out_bf3) A3R_CHECK_ARG(ldc == N, "a3r_linear_bf3: out_bf3 needs ldc == N");
+    for (int i = 0; i < n_groups; i++)
+        if (int rc = set_group(g, i, groups[i].x3, groups[i].w3, groups[i].y, groups[i].bias, groups[i].resid, groups[i].resid2, "a3r_linear_bf3")) return rc;
+    if (int rc = set_linear_dims(g, n_groups, K, ldc, M, N, K, "a3r_linear_bf3")) return rc;
     return launch_bf3<0>(g, as_stream(stream));
 }
 
@@ -562,23 +434,11 @@ extern "C" int a3r_linear_bf3(const void* x3, const void* w3, float* y, int ldc,
 
 extern "C" int a3r_conv3x3_bf3(const void* x3, const void* wp3, float* y, int B, int H, int W, int Cin, int Cout, int stride,
                                const a3r_epilogue* epi, void* stream) {
-    A3R_CHECK_ARG(x3 && wp3 && y, "a3r_conv3x3_bf3: null pointer");
-    A3R_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cout > 0, "a3r_conv3x3_bf3: bad shape");
-    A3R_CHECK_ARG(Cin > 0 && Cin % 32 == 0, "a3r_conv3x3_bf3: Cin (%d) must be a multiple of 32", Cin);
-    A3R_CHECK_ARG(stride == 1 || stride == 2, "a3r_conv3x3_bf3: stride must be 1 or 2");
     GemmArgs g = {};
-    g.cH = H; g.cW = W; g.cCin = Cin; g.cStride = stride;
-    g.cHo = (H + 2 - 3) / stride + 1;
-    g.cWo = (W + 2 - 3) / stride + 1;
-    g.lda = 0; g.ldc = Cout;
-    g.M = B * g.cHo * g.cWo; g.N = Cout; g.K = 9 * Cin;
-    if (int rc = check_epilogue(epi, g.M, g.N, "a3r_conv3x3_bf3", true)) return rc;
-    if (epi) g.epi = *epi;
+    if (int rc = set_conv_args(g, "a3r_conv3x3_bf3", x3 && wp3 && y, B, H, W, Cin, Cout, stride, epi, true, false)) return rc;
     A3R_CHECK_ARG(g.epi.epi != A3R_EPI_PIXSHUF && g.epi.epi != A3R_EPI_ROPE, "a3r_conv3x3_bf3: unsupported epilogue");
     A3R_CHECK_ARG(!g.epi.relu_a, "a3r_conv3x3_bf3: relu_a is not available (the producer writes the pre-activated bf3 input: aux_relu)");
     A3R_CHECK_ARG(!g.epi.x_pair && !g.epi.out_pair, "a3r_conv3x3_bf3: the row-pair layout is for a3r_linear_bf3 operands only");
-    g.groups = 1;
-    g.grp[0] = {static_cast<const float*>(x3), static_cast<const float*>(wp3), y, g.epi.bias, g.epi.resid, g.epi.resid2};
-    if (int rc = check_group(g.grp[0], g.epi.epi, "a3r_conv3x3_bf3")) return rc;
+    if (int rc = set_group(g, 0, x3, wp3, y, g.epi.bias, g.epi.resid, g.epi.resid2, "a3r_conv3x3_bf3")) return rc;
     return launch_bf3<1>(g, as_stream(stream));
 }

@@ -1,9 +1,11 @@
-// Pieces shared by the MFMA GEMM kernels of liba3r (gemm.hip: exact-fp32 MFMA; gemm_bf3.hip: split-bf16 MFMA):
-// launch arguments, the fused epilogue (bias / GELU / ReLU / residuals / RoPE-2D / pixel-shuffle) and argument checks.
+// Pieces shared by the MFMA GEMM kernels of liba3r (gemm.hip: exact-fp32 MFMA; gemm_bf3.hip: three-plane bf16 MFMA; gemm_fh2.hip:
+// two-plane fp16 MFMA): the tile scaffold (gemm_tile.h), the fused epilogue over 16x16 accumulators (bias / GELU / ReLU / residuals /
+// RoPE-2D / pixel-shuffle, direct and LDS-staged) and the argument checks of the entry points.
 #pragma once
 #include "common.h"
 #include "bf3.h"
 #include "fh2.h"
+#include "gemm_tile.h"
 
 // Between a wave's writes of its private LDS image and its own reads of it (and back): the LDS pipeline executes one wave's DS
 // instructions in program order, so only the COMPILER has to be kept from moving them across each other (wave_barrier); with
@@ -15,30 +17,6 @@
 #endif
 
 namespace a3r {
-
-struct GroupPtrs {
-    const float* A;
-    const float* Wt;        // [N, K]
-    float* C;
-    const float* bias;
-    const float* resid;
-    const float* resid2;
-    // fh2 kernels: the power of two the out_fh2 / aux_fh2 output is stored with, and the word receiving max |out_scale * value| (or null)
-    float out_scale;
-    unsigned* out_absmax;
-};
-
-struct GemmArgs {
-    GroupPtrs grp[4];
-    int groups, tiles_per_group;
-    int lda, ldc;
-    int M, N, K;
-    int tiles_m, tiles_n;
-    a3r_epilogue epi;       // pointers inside are ignored (taken from grp[]) except the rope tables
-    // implicit conv (AMODE 1): A = x [B, H, W, Cin]
-    int cH, cW, cCin, cHo, cWo, cStride;
-    int direct_epilogue;    // A/B switch (env A3R_BF3_DIRECT_EPI): keep the accumulator-layout epilogue instead of the LDS-staged one
-};
 
 // gelu(x) = 0.5 x (1 + erf(x / sqrt 2)) (nn.GELU default, blocks.py:66) with erf from Abramowitz & Stegun 7.1.26
 // (|error| <= 1.5e-7, the size of an fp32 rounding of erf): q = 0.5 (1 - erf|z|) = 0.5 t (a1 + t (a2 + ...)) exp(-z^2),
@@ -55,57 +33,17 @@ __device__ __forceinline__ float gelu_erf(float x) {
     return x >= 0.f ? __fmaf_rn(-x, q, x) : x * q;
 }
 
-// Epilogue over the 32x32 MFMA accumulators of one wave: acc[i][j] covers rows m0 + wrow0 + 32 i .. and columns
-// n0 + wcol0 + 32 j ..; element e of a lane sits at row (e&3) + 8 (e>>2) + 4 (lane>>5), column lane&31.
-template <int TM, int TN, bool FULL>
-__device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const GroupPtrs& P, f32x16 (&acc)[TM][TN], int m0, int n0,
-                                              int wrow0, int wcol0, int lane) {
-    const a3r_epilogue& ep = g.epi;
-    const int half = lane >> 5, lcol = lane & 31;
-    const int epi = ep.epi;
-#pragma unroll
-    for (int j = 0; j < TN; j++) {
-        const int colbase = n0 + wcol0 + j * 32;
-        const int col = colbase + lcol;
-        const bool col_ok = FULL || col < g.N;
-        const float bias = (P.bias && col_ok) ? P.bias[epi == A3R_EPI_PIXSHUF ? col % ep.ps_cout : col] : 0.f;
-        const bool do_rope = epi == A3R_EPI_ROPE && colbase < ep.rope_cols;   // wave-uniform (rope_cols % 64 == 0)
-        const bool rope_x = (colbase & 32) != 0;                               // second half of the head rotates with x
-#pragma unroll
-        for (int i = 0; i < TM; i++) {
-#pragma unroll
-            for (int e = 0; e < 16; e++) {
-                const int row = m0 + wrow0 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
-                float v = acc[i][j][e] + bias;
-                if (do_rope) {
-                    // pairs (d, d+16) inside each 32-wide half of the head (RoPE2D pos_embed.py:130-157)
-                    const float other = __shfl_xor(v, 16);
-                    const int tok = row % ep.tokens_per_image;
-                    const int py = tok / ep.grid_w, px = tok - py * ep.grid_w;
-                    const int p = rope_x ? px : py;
-                    const float c = ep.rope_cos[p * 16 + (lcol & 15)], s = ep.rope_sin[p * 16 + (lcol & 15)];
-                    v = (lcol & 16) ? v * c + other * s : v * c - other * s;
-                }
-                if ((FULL || row < g.M) && col_ok) {
-                    if (epi == A3R_EPI_GELU) v = gelu_erf(v);
-                    else if (epi == A3R_EPI_RELU) v = fmaxf(v, 0.f);
-                    else if (epi == A3R_EPI_RESID) v = P.resid[(size_t)row * g.ldc + col] + v;
-                    else if (epi == A3R_EPI_RESID2) v = P.resid[(size_t)row * g.ldc + col] + P.resid2[(size_t)row * g.ldc + col] + v;
-                    if (epi == A3R_EPI_PIXSHUF) {
-                        const int s = ep.ps_s, hw = ep.ps_h * ep.ps_w;
-                        const int b = row / hw, rem = row - b * hw;
-                        const int y = rem / ep.ps_w, x = rem - y * ep.ps_w;
-                        const int tap = col / ep.ps_cout, co = col - tap * ep.ps_cout;
-                        const int dy = tap / s, dx = tap - dy * s;
-                        const size_t opix = ((size_t)b * ep.ps_h * s + (y * s + dy)) * (ep.ps_w * s) + (x * s + dx);
-                        P.C[opix * ep.ps_cout + co] = v;
-                    } else {
-                        P.C[(size_t)row * g.ldc + col] = v;
-                    }
-                }
-            }
-        }
-    }
+// The RoPE-2D rotation of the generic epilogues: pairs (d, d+16) inside each 32-wide half of the head (RoPE2D pos_embed.py:130-157);
+// d = this lane's position in [0, 16), plus: this element is the second of its pair.  The token position by integer division and a
+// contractable v c +- other s.  (fh2_epilogue_out_body has its own form, with another rounding: see there.)  The column facts
+// around it -- col, col_ok, bias, the partner bias, do_rope / rope_x / second -- stay written out at each site: moved into a function
+// they compile to other instructions in every kernel that holds these epilogues, the fh2 kernels included.
+__device__ __forceinline__ float rope_rotate(const a3r_epilogue& ep, float v, float other, int row, int d, bool rope_x, bool plus) {
+    const int tok = row % ep.tokens_per_image;
+    const int py = tok / ep.grid_w, px = tok - py * ep.grid_w;
+    const int p = rope_x ? px : py;
+    const float c = ep.rope_cos[p * 16 + d], s = ep.rope_sin[p * 16 + d];
+    return plus ? v * c + other * s : v * c - other * s;
 }
 
 // The same epilogue over 16x16 accumulators (v_mfma_f32_16x16x32_bf16): acc[i][j] covers rows m0 + wrow0 + 16 i .. and
@@ -147,13 +85,8 @@ __device__ __forceinline__ void gemm_epilogue16_body(const GemmArgs& g, const Gr
                 const int row = m0 + wrow0 + i * 16 + quad * 4 + e;
                 v[e] = acc[i][j][e] + bias;
                 if (do_rope) {
-                    // pairs (d, d+16) inside each 32-wide half of the head (RoPE2D pos_embed.py:130-157)
                     const float other = acc[i][j ^ 1][e] + bias_o;
-                    const int tok = row % ep.tokens_per_image;
-                    const int py = tok / ep.grid_w, px = tok - py * ep.grid_w;
-                    const int p = rope_x ? px : py;
-                    const float c = ep.rope_cos[p * 16 + lcol], s = ep.rope_sin[p * 16 + lcol];
-                    v[e] = second ? v[e] * c + other * s : v[e] * c - other * s;
+                    v[e] = rope_rotate(ep, v[e], other, row, lcol, rope_x, second);
                 }
                 const bool ok = (FULL || row < g.M) && col_ok;
                 if (epi == A3R_EPI_GELU) v[e] = gelu_erf(v[e]);
@@ -252,11 +185,7 @@ __device__ __forceinline__ void gemm_epilogue16_lds_body(const GemmArgs& g, cons
         if (do_rope) {
             const int row = m0 + wrow0 + i * 16 + quad * 4 + e;
             const float other = acc[i][j ^ 1][e] + bias_o;
-            const int tok = row % ep.tokens_per_image;
-            const int py = tok / ep.grid_w, px = tok - py * ep.grid_w;
-            const int pp = rope_x ? px : py;
-            const float c = ep.rope_cos[pp * 16 + lcol], sn = ep.rope_sin[pp * 16 + lcol];
-            v = second ? v * c + other * sn : v * c - other * sn;
+            v = rope_rotate(ep, v, other, row, lcol, rope_x, second);
         }
         if (epi == A3R_EPI_GELU) v = gelu_erf(v);
         else if (epi == A3R_EPI_RELU) v = fmaxf(v, 0.f);
@@ -452,6 +381,45 @@ static inline int check_group(const GroupPtrs& p, int epi, const char* who) {
                   "%s: x and w must be 16-byte aligned", who);
     if (epi == A3R_EPI_RESID || epi == A3R_EPI_RESID2) A3R_CHECK_ARG(p.resid, "%s: RESID epilogue without resid", who);
     if (epi == A3R_EPI_RESID2) A3R_CHECK_ARG(p.resid2, "%s: RESID2 epilogue without resid2", who);
+    return A3R_OK;
+}
+
+// ---- what the entry points of the three families share; the rules of one family (fh2 scales, out_fh2 / aux_fh2, x_pair, PIXSHUF)
+// stay with it.  who: the entry point's name without "_grouped".  Every check returns before anything is launched.
+static inline int check_linear_dims(const char* who, bool groups_ok, int M, int N, int K) {
+    A3R_CHECK_ARG(groups_ok, "%s_grouped: 1..4 groups required", who);
+    A3R_CHECK_ARG(M > 0 && N > 0 && K > 0, "%s: M, N, K must be positive (got %d, %d, %d)", who, M, N, K);
+    A3R_CHECK_ARG(K % 32 == 0, "%s: K (%d) must be a multiple of 32", who, K);
+    return A3R_OK;
+}
+// group i's operands (the fh2 entry points add out_scale / out_absmax afterwards)
+static inline int set_group(GemmArgs& g, int i, const void* x, const void* w, float* y, const float* bias, const float* resid,
+                            const float* resid2, const char* who) {
+    g.grp[i] = {static_cast<const float*>(x), static_cast<const float*>(w), y, bias, resid, resid2};
+    return check_group(g.grp[i], g.epi.epi, who);
+}
+static inline int set_linear_dims(GemmArgs& g, int n_groups, int lda, int ldc, int M, int N, int K, const char* who) {
+    g.groups = n_groups;
+    g.lda = lda; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
+    if (g.epi.epi != A3R_EPI_PIXSHUF) A3R_CHECK_ARG(ldc >= N, "%s: ldc (%d) < N (%d)", who, ldc, N);
+    if (g.epi.out_bf3) A3R_CHECK_ARG(ldc == N, "%s: out_bf3 needs ldc == N", who);
+    return A3R_OK;
+}
+// 3x3 conv (padding 1): shape checks, the geometry, the epilogue -> g (one group; its operands: set_group)
+static inline int set_conv_args(GemmArgs& g, const char* who, bool ptrs_ok, int B, int H, int W, int Cin, int Cout, int stride,
+                                const a3r_epilogue* epi, bool bf3_kernel, bool fh2_kernel) {
+    A3R_CHECK_ARG(ptrs_ok, "%s: null pointer", who);
+    A3R_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "%s: bad shape", who);
+    A3R_CHECK_ARG(Cin % 32 == 0, "%s: Cin (%d) must be a multiple of 32", who, Cin);
+    A3R_CHECK_ARG(stride == 1 || stride == 2, "%s: stride must be 1 or 2", who);
+    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+    const long M = (long)B * Ho * Wo;                 // the kernels index rows with int
+    A3R_CHECK_ARG(M < (1L << 31), "%s: map too large", who);
+    if (int rc = check_epilogue(epi, (int)M, Cout, who, bf3_kernel, fh2_kernel)) return rc;
+    if (epi) g.epi = *epi;
+    g.cH = H; g.cW = W; g.cCin = Cin; g.cHo = Ho; g.cWo = Wo; g.cStride = stride;
+    g.groups = 1;
+    g.lda = 0; g.ldc = Cout; g.M = (int)M; g.N = Cout; g.K = 9 * Cin;
     return A3R_OK;
 }
 

@@ -23,14 +23,16 @@ namespace a3r {
 
 typedef __attribute__((address_space(3))) void* fh2_lptr;
 
-template <int N> __device__ __forceinline__ void fh2_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// The counts these kernels ask for.  Their own list, not wait_vmcnt_dyn's: with the cases 7 and 10 that only the bf3 list has, the
+// switch compiles to other instructions in ten of these kernels.
+constexpr bool fh2_vmcnt_listed(int n) { return (n >= 0 && n <= 6) || n == 8 || n == 9 || n == 12; }
 __device__ __forceinline__ void fh2_wait_vmcnt_dyn(int n) {
     switch (n) {
-        case 0: fh2_wait_vmcnt<0>(); break;   case 1: fh2_wait_vmcnt<1>(); break;   case 2: fh2_wait_vmcnt<2>(); break;
-        case 3: fh2_wait_vmcnt<3>(); break;   case 4: fh2_wait_vmcnt<4>(); break;   case 5: fh2_wait_vmcnt<5>(); break;
-        case 6: fh2_wait_vmcnt<6>(); break;   case 8: fh2_wait_vmcnt<8>(); break;   case 9: fh2_wait_vmcnt<9>(); break;
-        case 12: fh2_wait_vmcnt<12>(); break;
-        default: fh2_wait_vmcnt<0>(); break;                                // always safe
+        case 0: wait_vmcnt<0>(); break;   case 1: wait_vmcnt<1>(); break;   case 2: wait_vmcnt<2>(); break;
+        case 3: wait_vmcnt<3>(); break;   case 4: wait_vmcnt<4>(); break;   case 5: wait_vmcnt<5>(); break;
+        case 6: wait_vmcnt<6>(); break;   case 8: wait_vmcnt<8>(); break;   case 9: wait_vmcnt<9>(); break;
+        case 12: wait_vmcnt<12>(); break;
+        default: wait_vmcnt<0>(); break;                                // always safe
     }
 }
 
@@ -228,10 +230,12 @@ __global__ __launch_bounds__(WM * WN * 64, (BM / WM) * (BN / WN) > 2048 ? 2 : 4)
     static_assert(SA % NT == 0 && SB % NT == 0, "whole DMA rounds");
     constexpr int LA = SA / NT, LB = SB / NT, LPS = LA + LB;               // DMAs per thread per stage
     static_assert(WTN % 32 == 0 && WTM % 32 == 0, "wave tiles are multiples of 32 columns (epilogue blocks) and of 32 rows");
+    static_assert(vmcnt_stages_listed(fh2_vmcnt_listed, NS, LPS), "a vmcnt this variant asks for is missing from fh2_wait_vmcnt_dyn");
     constexpr int STAGE = (SA + SB) * 16;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
-    // XCD-aware bijective remap (blocks b and b+8 share an XCD), then group / tile decomposition
+    // XCD-aware bijective remap (blocks b and b+8 share an XCD), then group / tile decomposition.  Written out here, like the conv
+    // geometry below: through the helpers of gemm_tile.h these kernels compile to other instructions, and they sit at the register cap
     const int nwg = g.tiles_per_group * g.groups;
     const int orig = blockIdx.x;
     const int xcd = orig & 7, q = nwg >> 3, r8 = nwg & 7;
@@ -365,7 +369,7 @@ __global__ __launch_bounds__(WM * WN * 64, (BM / WM) * (BN / WN) > 2048 ? 2 : 4)
         const char* sb = smem + nbuf * STAGE;
         if constexpr (NEXT) {
             __builtin_amdgcn_s_waitcnt(0xc07f);                // lgkmcnt(0): stage kt is in registers: its buffer may be overwritten after the barrier
-            if (kt + NS <= nk) fh2_wait_vmcnt<(NS - 2) * LPS>();
+            if (kt + NS <= nk) wait_vmcnt<(NS - 2) * LPS>();
             else fh2_wait_vmcnt_dyn((nk - kt - 2) * LPS);
             __builtin_amdgcn_s_barrier();
             if (kt + NS < nk) issue(kt + NS, nbuf == 0 ? NS - 1 : nbuf - 1);
@@ -497,14 +501,8 @@ int fh2_passes() { return g_fh2_passes; }
 
 template <int BM, int BN, int WM, int WN, int NS, bool FULL, int AMODE = 0, int PASSES = 3>
 static int launch_fh2_variant(const Fh2Args& fa, hipStream_t st) {
-    auto kern = gemm_fh2_kernel<BM, BN, WM, WN, NS, FULL, AMODE, PASSES>;
-    constexpr int ring = NS * (BM + BN) * 128, epi = WM * WN * epi_lds_wave_bytes(BM / WM), lds = ring > epi ? ring : epi;
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    static PerDeviceOnce attr_once;
-    A3R_HIP(attr_once.ensure([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds); }));
-    hipLaunchKernelGGL(kern, dim3(fa.g.tiles_per_group * fa.g.groups), dim3(WM * WN * 64), lds, st, fa);
-    A3R_LAUNCH_CHECK();
-    return A3R_OK;
+    constexpr int ring = NS * (BM + BN) * 128, epi = WM * WN * epi_lds_wave_bytes(BM / WM);       // the epilogue images reuse the stage ring
+    return launch_tiles<gemm_fh2_kernel<BM, BN, WM, WN, NS, FULL, AMODE, PASSES>, WM * WN * 64, (ring > epi ? ring : epi)>(fa.g, fa, st);
 }
 
 template <int AMODE>
@@ -517,15 +515,11 @@ static int launch_fh2(Fh2Args& fa, hipStream_t st) {
     if (AMODE == 1 && t == 3) t = 2;                  // (tile 3 is a linear-only lab tile; the 128x64 tile serves convolutions with
                                                       // 64 or 192 output channels -- the flow network's -- without a half-empty tile)
     if (g_fh2_passes == 1) t = 2;
-    const int bm = kFh2Tiles[t].bm, bn = kFh2Tiles[t].bn;
-    g.tiles_m = (g.M + bm - 1) / bm;
-    g.tiles_n = (g.N + bn - 1) / bn;
-    g.tiles_per_group = g.tiles_m * g.tiles_n;
+    const bool full = set_tiles(g, kFh2Tiles[t].bm, kFh2Tiles[t].bn);
     // measured (tools/bench_fh2.py, A3R_FH2_GM=1|4|8|16): 8 row tiles per block is +6 % over the row-major order on the forward's
     // K <= 1024 shapes (fc1 +11 %) and cuts the fabric bytes by a third; the K >= 3072 shapes (2 MB of A per row tile) lose 1-2 %
     fa.gm = gm_env > 0 ? gm_env : (g.K >= 2048 ? 1 : 8);
     if (fa.gm > g.tiles_m) fa.gm = g.tiles_m;
-    const bool full = g.M % bm == 0 && g.N % bn == 0;
     const double mn = (double)g.M * g.N;
     const double c_bytes = mn * (4.0 + (g.epi.aux_fh2 ? 4.0 : 0.0) + (g.epi.epi == A3R_EPI_RESID ? 4.0 : g.epi.epi == A3R_EPI_RESID2 ? 8.0 : 0.0));
     // algorithmic bytes: operands once (the conv's input map once, not once per tap), weights once, outputs once
@@ -607,9 +601,7 @@ extern "C" float a3r_fh2_weight_scale(float absmax) {
 
 extern "C" int a3r_linear_fh2_grouped(const a3r_group_ptrs_fh2* groups, int n_groups, int ldc, int M, int N, int K,
                                       const a3r_epilogue* epi, void* stream) {
-    A3R_CHECK_ARG(groups && n_groups >= 1 && n_groups <= 4, "a3r_linear_fh2_grouped: 1..4 groups required");
-    A3R_CHECK_ARG(M > 0 && N > 0 && K > 0, "a3r_linear_fh2: M, N, K must be positive (got %d, %d, %d)", M, N, K);
-    A3R_CHECK_ARG(K % 32 == 0, "a3r_linear_fh2: K (%d) must be a multiple of 32", K);
+    if (int rc = check_linear_dims("a3r_linear_fh2", groups && n_groups >= 1 && n_groups <= 4, M, N, K)) return rc;
     A3R_CHECK_ARG(ldc >= 1, "a3r_linear_fh2: bad leading dimension ldc=%d", ldc);
     if (int rc = check_epilogue(epi, M, N, "a3r_linear_fh2", true, true)) return rc;
     Fh2Args fa = {};
@@ -631,16 +623,13 @@ extern "C" int a3r_linear_fh2_grouped(const a3r_group_ptrs_fh2* groups, int n_gr
     for (int i = 0; i < n_groups; i++) {
         float xs, os;
         if (int rc = fh2_scales(groups[i].x_scale, groups[i].out_scale, "a3r_linear_fh2", &xs, &os)) return rc;
-        g.grp[i] = {static_cast<const float*>(groups[i].x2), static_cast<const float*>(groups[i].w2), groups[i].y, groups[i].bias,
-                    groups[i].resid, groups[i].resid2, os, groups[i].out_absmax};
-        if (int rc = check_group(g.grp[i], g.epi.epi, "a3r_linear_fh2")) return rc;
+        if (int rc = set_group(g, i, groups[i].x2, groups[i].w2, groups[i].y, groups[i].bias, groups[i].resid, groups[i].resid2, "a3r_linear_fh2")) return rc;
+        g.grp[i].out_scale = os;
+        g.grp[i].out_absmax = groups[i].out_absmax;
         A3R_CHECK_ARG(groups[i].w_scale > 0.f, "a3r_linear_fh2: w_scale must be positive");
         fa.inv_wscale[i] = fh2_acc_factor(g.epi, groups[i].w_scale, xs, os);
     }
-    g.groups = n_groups;
-    g.lda = K; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
-    A3R_CHECK_ARG(ldc >= N, "a3r_linear_fh2: ldc (%d) < N (%d)", ldc, N);
-    if (g.epi.out_bf3) A3R_CHECK_ARG(ldc == N, "a3r_linear_fh2: out_bf3 needs ldc == N");
+    if (int rc = set_linear_dims(g, n_groups, K, ldc, M, N, K, "a3r_linear_fh2")) return rc;      // (PIXSHUF was refused above)
     return launch_fh2<0>(fa, as_stream(stream));
 }
 
@@ -653,18 +642,11 @@ extern "C" int a3r_linear_fh2(const void* x2, const void* w2, float w_scale, flo
 
 extern "C" int a3r_conv3x3_fh2(const void* x2, const void* wp2, float w_scale, float* y, int B, int H, int W, int Cin, int Cout, int stride,
                                const a3r_epilogue* epi, void* stream) {
-    A3R_CHECK_ARG(x2 && wp2 && y, "a3r_conv3x3_fh2: null pointer");
-    A3R_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "a3r_conv3x3_fh2: bad shape");
-    A3R_CHECK_ARG(stride == 1 || stride == 2, "a3r_conv3x3_fh2: stride must be 1 or 2");
-    A3R_CHECK_ARG(Cin % 32 == 0, "a3r_conv3x3_fh2: Cin (%d) must be a multiple of 32", Cin);
-    A3R_CHECK_ARG(w_scale > 0.f, "a3r_conv3x3_fh2: w_scale must be positive");
-    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-    const long M = (long)B * Ho * Wo;
-    A3R_CHECK_ARG(M < (1L << 31) && (long)B * H * W * Cin * 4 < (1L << 46), "a3r_conv3x3_fh2: map too large");
-    if (int rc = check_epilogue(epi, (int)M, Cout, "a3r_conv3x3_fh2", true, true)) return rc;
     Fh2Args fa = {};
     GemmArgs& g = fa.g;
-    if (epi) g.epi = *epi;
+    if (int rc = set_conv_args(g, "a3r_conv3x3_fh2", x2 && wp2 && y, B, H, W, Cin, Cout, stride, epi, true, true)) return rc;
+    A3R_CHECK_ARG(w_scale > 0.f, "a3r_conv3x3_fh2: w_scale must be positive");
+    A3R_CHECK_ARG((long)B * H * W * Cin * 4 < (1L << 46), "a3r_conv3x3_fh2: map too large");      // the DMA windows are placed with 32-bit offsets
     A3R_CHECK_ARG(!g.epi.relu_a && !g.epi.x_pair && !g.epi.out_pair && !g.epi.out_bf3 && !g.epi.aux_bf3,
                   "a3r_conv3x3_fh2: relu_a / row-pair / bf3 outputs do not apply (the producer writes the pre-activated fh2 input: aux_fh2 + aux_relu)");
     A3R_CHECK_ARG(g.epi.epi != A3R_EPI_PIXSHUF && g.epi.epi != A3R_EPI_ROPE, "a3r_conv3x3_fh2: PIXSHUF / ROPE are not available");
@@ -675,11 +657,9 @@ extern "C" int a3r_conv3x3_fh2(const void* x2, const void* wp2, float w_scale, f
         A3R_CHECK_ARG(Cout % 8 == 0 && (reinterpret_cast<uintptr_t>(g.epi.aux_fh2) & 15) == 0, "a3r_conv3x3_fh2: aux_fh2 needs Cout %% 8 == 0 and a 16-byte aligned buffer");
     float xs, os;
     if (int rc = fh2_scales(g.epi.x_scale, g.epi.out_scale, "a3r_conv3x3_fh2", &xs, &os)) return rc;
-    g.grp[0] = {static_cast<const float*>(x2), static_cast<const float*>(wp2), y, g.epi.bias, g.epi.resid, g.epi.resid2, os, g.epi.out_absmax};
-    if (int rc = check_group(g.grp[0], g.epi.epi, "a3r_conv3x3_fh2")) return rc;
+    if (int rc = set_group(g, 0, x2, wp2, y, g.epi.bias, g.epi.resid, g.epi.resid2, "a3r_conv3x3_fh2")) return rc;
+    g.grp[0].out_scale = os;
+    g.grp[0].out_absmax = g.epi.out_absmax;
     fa.inv_wscale[0] = fh2_acc_factor(g.epi, w_scale, xs, os);
-    g.groups = 1;
-    g.M = (int)M; g.N = Cout; g.K = 9 * Cin; g.lda = g.K; g.ldc = Cout;
-    g.cH = H; g.cW = W; g.cCin = Cin; g.cHo = Ho; g.cWo = Wo; g.cStride = stride;
     return launch_fh2<1>(fa, as_stream(stream));
 }

@@ -219,6 +219,21 @@ def test_errors_are_loud(ops):
         ops.linear(rnd(4, 32), rnd(8, 32), relu_acc=True)
 
 
+def test_conv3x3_refuses_2_to_32_output_pixels():
+    """B = 65536 maps of 256 x 256 are M = 2^32 output pixels: every family refuses (A3R_EINVAL, "map too large") instead of wrapping
+    M to 0 in int.  The check is an argument check: it returns before anything is launched, so small real buffers are enough."""
+    from align3r_amd import _lib
+    lib = _lib.load()
+    buf = torch.zeros(1 << 16, device="cuda", dtype=torch.float32)
+    B, H, W, Cin, Cout = 65536, 256, 256, 32, 32
+    p, st = _lib.ptr(buf), _lib.stream_ptr()
+    for name, args in (("a3r_conv3x3", (p, p, p)), ("a3r_conv3x3_bf3", (p, p, p)), ("a3r_conv3x3_fh2", (p, p, 1.0, p))):
+        assert getattr(lib, name)(*args, B, H, W, Cin, Cout, 1, None, st) == -1, name          # A3R_EINVAL
+        assert f"{name}: map too large" in lib.a3r_last_error().decode()
+    torch.cuda.synchronize()
+    assert float(buf.abs().max()) == 0.0
+
+
 def test_umeyama_moments_kernel():
     """a3r_umeyama_moments (the registrations of the aligner's initialisation, init_im_poses.py:415-418): raw moments of B weighted
     point-set pairs against float64 numpy, and the similarity recovered from them."""
