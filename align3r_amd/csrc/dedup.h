@@ -76,6 +76,113 @@ inline int dedup_group_entries(const int32_t* map_img, const int32_t* map_pd, in
     return Um;
 }
 
+// ---- frames kept across calls (a3r_model_set_frame_cache).  The device looks every distinct image of a call up among the stored
+// ones (frame_cache_lookup below: the key proposes, a bitwise comparison decides); this table is the host's side of it: which
+// entries hold a frame, and how recently each was used.  Plain C++ as well (tests/test_frame_cache_cpu.py).
+constexpr int FC_MAX_ENTRIES = 256;          // entries at most (their validity travels to the lookup kernel as a bit mask)
+struct FrameCacheMask { uint32_t w[FC_MAX_ENTRIES / 32]; };
+
+struct FrameCacheTable {
+    int cap = 0;
+    uint64_t clock = 0;
+    uint64_t stamp[FC_MAX_ENTRIES] = {};     // clock of the entry's last use; 0 = the entry is free
+    void reset(int capacity) {
+        cap = capacity < 0 ? 0 : capacity > FC_MAX_ENTRIES ? FC_MAX_ENTRIES : capacity;
+        flush();
+    }
+    void flush() {
+        clock = 0;
+        for (uint64_t& s : stamp) s = 0;
+    }
+    int size() const {
+        int n = 0;
+        for (int e = 0; e < cap; e++) n += stamp[e] != 0;
+        return n;
+    }
+    FrameCacheMask mask() const {
+        FrameCacheMask k = {};
+        for (int e = 0; e < cap; e++)
+            if (stamp[e]) k.w[e / 32] |= 1u << (e % 32);
+        return k;
+    }
+    // One call.  hit[k] (k < U) is the entry whose frame equals the call's k-th distinct image, or -1.  Writes to ent[k] the entry
+    // image k is read from (a hit) or stored to (a miss), or -1 for a miss that is not stored: a miss takes the free entry of the
+    // smallest index, then the least recently used entry, never one this call hit or filled, and when those run out the remaining
+    // misses (in list order) are not stored.  n[0..2] = hits, misses, evictions.  Every entry the call touches becomes the most
+    // recently used, in list order.  Returns 0, or -1 and changes nothing when hit is not such a list (an index out of range, a
+    // free entry, or one entry named twice); the caller then runs without the cache.
+    int assign(const int32_t* hit, int U, int32_t* ent, int* n) {
+        if (!hit || !ent || !n || U < 0) return -1;
+        bool used[FC_MAX_ENTRIES] = {};
+        for (int k = 0; k < U; k++) {
+            const int32_t e = hit[k];
+            if (e < -1 || e >= cap) return -1;
+            if (e >= 0) {
+                if (!stamp[e] || used[e]) return -1;
+                used[e] = true;
+            }
+        }
+        n[0] = n[1] = n[2] = 0;
+        for (int k = 0; k < U; k++) {
+            int e = hit[k];
+            if (e >= 0) n[0]++;
+            else {
+                n[1]++;
+                for (int c = 0; c < cap && e < 0; c++)
+                    if (!stamp[c] && !used[c]) e = c;
+                if (e < 0) {
+                    for (int c = 0; c < cap; c++)
+                        if (!used[c] && (e < 0 || stamp[c] < stamp[e])) e = c;
+                    if (e >= 0) n[2]++;
+                }
+                if (e >= 0) used[e] = true;
+            }
+            ent[k] = e;
+        }
+        for (int k = 0; k < U; k++)
+            if (ent[k] >= 0) stamp[ent[k]] = ++clock;
+        return 0;
+    }
+};
+
+// The caller's storage as `cap` entries, one array per field: keys [cap][2] of 64 bits, the statistics words [cap][FC_STAT_WORDS]
+// of the call that computed the entry, the lookup's mismatch flags [cap][2 B], the images [cap][words_img] and their enc_norm rows
+// [cap][words_feat] (both multiples of 4 words).  cap = 0: the storage holds no entry of this size.
+constexpr int FC_STAT_WORDS = 1024;
+constexpr int FC_MAX_PAIRS = 512;            // larger calls run without the cache
+struct FrameCacheLayout {
+    int cap; long words_img, words_feat;
+    char *keys, *stats, *flags, *img, *feat;
+};
+inline size_t frame_cache_entry_bytes(long words_img, long words_feat) {
+    return 16 + (size_t)FC_STAT_WORDS * 4 + (size_t)4 * FC_MAX_PAIRS * 2 + ((size_t)words_img + (size_t)words_feat) * 4;
+}
+inline FrameCacheLayout frame_cache_layout(void* base, size_t bytes, long words_img, long words_feat) {
+    const size_t n = bytes / frame_cache_entry_bytes(words_img, words_feat);
+    const int cap = base ? (int)(n > (size_t)FC_MAX_ENTRIES ? (size_t)FC_MAX_ENTRIES : n) : 0;
+    char* p = static_cast<char*>(base);
+    FrameCacheLayout l = {cap, words_img, words_feat, p, nullptr, nullptr, nullptr, nullptr};
+    l.stats = l.keys + (size_t)cap * 16;
+    l.flags = l.stats + (size_t)cap * FC_STAT_WORDS * 4;
+    l.img = l.flags + (size_t)cap * 4 * FC_MAX_PAIRS * 2;
+    l.feat = l.img + (size_t)cap * words_img * 4;
+    return l;
+}
+// device side (dedup.hip), queued after dedup_find on the same stream.  keys / rep: dedup_find's; for every slot s < 2 B that is
+// its own representative, hit[s] = the valid entry (mask) whose key and whose every bit equal the slot's image, else -1; -1 for the
+// other slots.  B <= FC_MAX_PAIRS.
+int frame_cache_lookup(const float* img1, const float* img2, int B, const void* keys, const int32_t* rep, const FrameCacheLayout& l,
+                       const FrameCacheMask& mask, int32_t* hit, void* stream);
+// The call's U distinct images uniq[k] (device lists, as below): rows[k] = the stored rows of entry ent[k] where miss[k] < 0 (a
+// hit), else fresh[miss[k]] -- the enc_norm rows of the miss[k]-th encoded image -- which, with image and key, also go to entry
+// ent[k] when that is >= 0.
+int frame_cache_exchange(const float* img1, const float* img2, int B, const void* keys, const FrameCacheLayout& l, const int32_t* uniq,
+                         const int32_t* ent, const int32_t* miss, int U, const float* fresh, float* rows, void* stream);
+// The statistics words [lo, hi) of the call: stored with every entry the call filled, then raised to the largest word of the
+// entries it hit.
+int frame_cache_stats(const FrameCacheLayout& l, const int32_t* ent, const int32_t* miss, int U, unsigned* stats, int lo, int hi,
+                      void* stream);
+
 // ---- device side (dedup.hip).  An item of the first kind is one image [3, H, W] -- or, for the decode call, one frame's encoder
 // features [N, E] --, one of the second kind a pred_depth map [H, W, 3]: words_a / words_pd 32-bit words each, multiples of 4.  Slot s < 4 B of a call is item s % B of group s / B, the groups being img1, img2, pd1, pd2; slots 0 .. 2 B - 1
 // are the image kind, 2 B .. 4 B - 1 the depth-prior kind, and a representative is looked for inside a slot's own kind only.

@@ -85,7 +85,168 @@ __global__ __launch_bounds__(256) void dedup_verify_kernel(Items it, int B, int 
     if (diff) *flag = 1;
 }
 
+// ---- frames kept across calls (dedup.h, FrameCacheLayout)
+struct Images { const uint4* base[2]; };      // img1, img2: slot s < 2 B is item s % B of base[s / B]
+
+__device__ __forceinline__ bool fc_valid(const FrameCacheMask& m, int e) { return (m.w[e >> 5] >> (e & 31)) & 1u; }
+
+// flag[e * 2 B + slot] becomes nonzero when the image of slot -- a representative -- differs from that of the valid entry e with
+// the slot's key; grid: x over chunks of UNITS_PER_BLOCK units, y over the 2 B slots
+__global__ __launch_bounds__(256) void fc_compare_kernel(Images im, int B, long units, const unsigned long long* __restrict__ keys,
+                                                         const int* __restrict__ rep, const unsigned long long* __restrict__ ekeys,
+                                                         const uint4* __restrict__ eimg, int cap, FrameCacheMask mask,
+                                                         int* __restrict__ flag) {
+    const int slot = blockIdx.y;
+    if (rep[slot] != slot) return;
+    const unsigned long long k0 = keys[2 * slot], k1 = keys[2 * slot + 1];
+    const uint4* __restrict__ p = im.base[slot / B] + (long)(slot % B) * units;
+    const long u0 = (long)blockIdx.x * UNITS_PER_BLOCK;
+    for (int e = 0; e < cap; e++) {
+        if (!fc_valid(mask, e) || ekeys[2 * e] != k0 || ekeys[2 * e + 1] != k1) continue;
+        const uint4* __restrict__ q = eimg + (long)e * units;
+        unsigned diff = 0;
+#pragma unroll
+        for (int j = 0; j < UNITS_PER_BLOCK / 256; j++) {
+            const long u = u0 + j * 256 + threadIdx.x;
+            if (u < units) {
+                const uint4 a = p[u], b = q[u];
+                diff |= (a.x ^ b.x) | (a.y ^ b.y) | (a.z ^ b.z) | (a.w ^ b.w);
+            }
+        }
+        if (diff) flag[(long)e * 2 * B + slot] = 1;
+    }
+}
+
+// hit[slot] = the first valid entry with the slot's key and no mismatch flag, -1 without one or for a slot that is not its own
+// representative; one thread per slot
+__global__ void fc_pick_kernel(int B, const unsigned long long* __restrict__ keys, const int* __restrict__ rep,
+                               const unsigned long long* __restrict__ ekeys, int cap, FrameCacheMask mask, const int* __restrict__ flag,
+                               int* __restrict__ hit) {
+    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= 2 * B) return;
+    int h = -1;
+    if (rep[slot] == slot) {
+        const unsigned long long k0 = keys[2 * slot], k1 = keys[2 * slot + 1];
+        for (int e = 0; e < cap && h < 0; e++)
+            if (fc_valid(mask, e) && ekeys[2 * e] == k0 && ekeys[2 * e + 1] == k1 && !flag[(long)e * 2 * B + slot]) h = e;
+    }
+    hit[slot] = h;
+}
+
+// grid: x over chunks of UNITS_PER_BLOCK units of the longer of image and rows, y over the U distinct images
+__global__ __launch_bounds__(256) void fc_exchange_kernel(Images im, int B, long units_img, long units_feat,
+                                                          const unsigned long long* __restrict__ keys, unsigned long long* __restrict__ ekeys,
+                                                          uint4* __restrict__ eimg, uint4* __restrict__ efeat, const int* __restrict__ uniq,
+                                                          const int* __restrict__ ent, const int* __restrict__ miss,
+                                                          const uint4* __restrict__ fresh, uint4* __restrict__ rows) {
+    const int k = blockIdx.y, e = ent[k], j = miss[k];
+    const long u0 = (long)blockIdx.x * UNITS_PER_BLOCK;
+    uint4* __restrict__ dst = rows + (long)k * units_feat;
+    if (j < 0) {                                   // a hit: the stored rows
+        if (e < 0) return;                         // (never: a hit names its entry)
+        const uint4* __restrict__ src = efeat + (long)e * units_feat;
+        for (int i = 0; i < UNITS_PER_BLOCK / 256; i++) {
+            const long u = u0 + i * 256 + threadIdx.x;
+            if (u < units_feat) dst[u] = src[u];
+        }
+        return;
+    }
+    const uint4* __restrict__ src = fresh + (long)j * units_feat;
+    uint4* __restrict__ keep = e >= 0 ? efeat + (long)e * units_feat : nullptr;
+    for (int i = 0; i < UNITS_PER_BLOCK / 256; i++) {
+        const long u = u0 + i * 256 + threadIdx.x;
+        if (u < units_feat) {
+            const uint4 v = src[u];
+            dst[u] = v;
+            if (keep) keep[u] = v;
+        }
+    }
+    if (e < 0) return;
+    const int slot = uniq[k];
+    const uint4* __restrict__ p = im.base[slot / B] + (long)(slot % B) * units_img;
+    uint4* __restrict__ q = eimg + (long)e * units_img;
+    for (int i = 0; i < UNITS_PER_BLOCK / 256; i++) {
+        const long u = u0 + i * 256 + threadIdx.x;
+        if (u < units_img) q[u] = p[u];
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 2) ekeys[2 * e + threadIdx.x] = keys[2 * slot + threadIdx.x];
+}
+
+// one thread per statistics word lo + i
+__global__ void fc_stats_kernel(unsigned* __restrict__ estats, const int* __restrict__ ent, const int* __restrict__ miss, int U,
+                                unsigned* __restrict__ stats, int lo, int hi) {
+    const int i = lo + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= hi) return;
+    const unsigned own = stats[i];
+    unsigned w = own;
+    for (int k = 0; k < U; k++) {
+        const int e = ent[k];
+        if (e < 0) continue;
+        unsigned* s = estats + (long)e * FC_STAT_WORDS + i;
+        if (miss[k] >= 0) *s = own;
+        else w = *s > w ? *s : w;                  // words are bit patterns of non-negative floats: ordered as unsigned
+    }
+    stats[i] = w;
+}
+
+bool fc_layout_ok(const FrameCacheLayout& l) {
+    return l.cap > 0 && l.cap <= FC_MAX_ENTRIES && l.keys && l.words_img > 0 && l.words_img % 4 == 0 && l.words_feat > 0 &&
+           l.words_feat % 4 == 0 && (reinterpret_cast<uintptr_t>(l.keys) & 15) == 0;
+}
+
 }  // namespace
+
+int frame_cache_lookup(const float* img1, const float* img2, int B, const void* keys, const int32_t* rep, const FrameCacheLayout& l,
+                       const FrameCacheMask& mask, int32_t* hit, void* stream) {
+    A3R_CHECK_ARG(B > 0 && B <= FC_MAX_PAIRS && fc_layout_ok(l), "frame_cache_lookup: bad shape (B=%d, %d entries)", B, l.cap);
+    A3R_CHECK_ARG(img1 && img2 && keys && rep && hit && ((reinterpret_cast<uintptr_t>(img1) | reinterpret_cast<uintptr_t>(img2)) & 15) == 0,
+                  "frame_cache_lookup: null or misaligned pointer");
+    hipStream_t st = as_stream(stream);
+    const Images im = {{reinterpret_cast<const uint4*>(img1), reinterpret_cast<const uint4*>(img2)}};
+    const long units = l.words_img / 4;
+    int* flag = reinterpret_cast<int*>(l.flags);
+    const unsigned long long* ekeys = reinterpret_cast<const unsigned long long*>(l.keys);
+    A3R_HIP(hipMemsetAsync(flag, 0, (size_t)l.cap * 2 * B * sizeof(int), st));
+    ProfScope prof(PK_ELEMENTWISE, 2.0 * 16 * units * 2 * B, st);
+    const dim3 grid((unsigned)((units + UNITS_PER_BLOCK - 1) / UNITS_PER_BLOCK), (unsigned)(2 * B));
+    hipLaunchKernelGGL(fc_compare_kernel, grid, dim3(256), 0, st, im, B, units, static_cast<const unsigned long long*>(keys), rep, ekeys,
+                       reinterpret_cast<const uint4*>(l.img), l.cap, mask, flag);
+    hipLaunchKernelGGL(fc_pick_kernel, dim3((2 * B + 255) / 256), dim3(256), 0, st, B, static_cast<const unsigned long long*>(keys), rep,
+                       ekeys, l.cap, mask, flag, hit);
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+int frame_cache_exchange(const float* img1, const float* img2, int B, const void* keys, const FrameCacheLayout& l, const int32_t* uniq,
+                         const int32_t* ent, const int32_t* miss, int U, const float* fresh, float* rows, void* stream) {
+    A3R_CHECK_ARG(B > 0 && B <= FC_MAX_PAIRS && U > 0 && U <= 2 * B && fc_layout_ok(l), "frame_cache_exchange: bad shape (B=%d, U=%d)", B, U);
+    A3R_CHECK_ARG(img1 && img2 && keys && uniq && ent && miss && fresh && rows &&
+                      ((reinterpret_cast<uintptr_t>(fresh) | reinterpret_cast<uintptr_t>(rows)) & 15) == 0,
+                  "frame_cache_exchange: null or misaligned pointer");
+    hipStream_t st = as_stream(stream);
+    const Images im = {{reinterpret_cast<const uint4*>(img1), reinterpret_cast<const uint4*>(img2)}};
+    const long ui = l.words_img / 4, uf = l.words_feat / 4, units = ui > uf ? ui : uf;
+    ProfScope prof(PK_ELEMENTWISE, 16.0 * U * (3 * uf + 2 * ui), st);
+    const dim3 grid((unsigned)((units + UNITS_PER_BLOCK - 1) / UNITS_PER_BLOCK), (unsigned)U);
+    hipLaunchKernelGGL(fc_exchange_kernel, grid, dim3(256), 0, st, im, B, ui, uf, static_cast<const unsigned long long*>(keys),
+                       reinterpret_cast<unsigned long long*>(l.keys), reinterpret_cast<uint4*>(l.img), reinterpret_cast<uint4*>(l.feat),
+                       uniq, ent, miss, reinterpret_cast<const uint4*>(fresh), reinterpret_cast<uint4*>(rows));
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+int frame_cache_stats(const FrameCacheLayout& l, const int32_t* ent, const int32_t* miss, int U, unsigned* stats, int lo, int hi,
+                      void* stream) {
+    A3R_CHECK_ARG(fc_layout_ok(l) && ent && miss && stats && U > 0 && lo >= 0 && lo <= hi && hi <= FC_STAT_WORDS,
+                  "frame_cache_stats: bad argument (sites %d .. %d)", lo, hi);
+    if (hi == lo) return A3R_OK;
+    hipStream_t st = as_stream(stream);
+    ProfScope prof(PK_ELEMENTWISE, 4.0 * (hi - lo) * (U + 2), st);
+    hipLaunchKernelGGL(fc_stats_kernel, dim3((hi - lo + 255) / 256), dim3(256), 0, st, reinterpret_cast<unsigned*>(l.stats), ent, miss, U,
+                       stats, lo, hi);
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
 
 int dedup_find(const float* img1, const float* img2, const float* pd1, const float* pd2, int B, long words_a, long words_pd, int first,
                bool const_key, void* keys, int32_t* rep_flag, void* stream) {

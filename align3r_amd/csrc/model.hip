@@ -8,8 +8,9 @@
 //   postprocess                                      dust3r/heads/postprocess.py:10-58
 // Data layout: tokens [rows, C] with rows = (side, batch, token): the first B*N rows belong to view 1,
 // the next B*N rows to view 2 (this is the reference's torch.cat((img1, img2)) batch order), maps are
-// channels-last.  All buffers live in the caller's workspace; nothing here allocates device memory, except the handle's 64 KB of
-// key / map words for the duplicate search (find_distinct).
+// channels-last.  All buffers live in the caller's workspace; nothing here allocates device memory, except the handle's key / map
+// words for the duplicate search (find_distinct, about 100 KB).  The frames kept across calls live in storage the caller installs
+// (a3r_model_set_frame_cache).
 #include "plan.h"
 #include "dedup.h"
 #include <algorithm>
@@ -83,6 +84,13 @@ struct a3r_model_s {
     // the one read-back and the one upload of a call
     void* dd_dev = nullptr;
     int32_t* dd_host = nullptr;
+    // frames kept across calls (a3r_model_set_frame_cache): the caller's storage, the host table of its entries (dedup.h) and the
+    // resolution they were stored at; what the last forward did with it (a3r_model_last_frame_cache: hits, misses, evictions)
+    void* fc_buf = nullptr;
+    size_t fc_bytes = 0;
+    FrameCacheTable fc_table;
+    int fc_H = 0, fc_W = 0;
+    int last_fc[3] = {0, 0, 0};
     ~a3r_model_s() {
         if (dd_dev) (void)hipFree(dd_dev);
         if (dd_host) (void)hipHostFree(dd_host);
@@ -140,6 +148,7 @@ extern "C" int a3r_model_set_weight(a3r_model_t m, const char* name, const float
     A3R_CHECK_ARG(m, "a3r_model_set_weight: bad argument");
     if (int rc = m->w.set("a3r_model_set_weight", name, ptr, ndim, shape)) return rc;
     m->finalized = false;
+    m->fc_table.flush();          // stored rows belong to the weights they were computed with
     return A3R_OK;
 }
 
@@ -444,6 +453,7 @@ extern "C" int a3r_model_finalize(a3r_model_t m, void* packed, size_t packed_byt
         if (int rc = m->twins.pack(src, (Form)it.s, src, pk + it.off, it.a, it.b, scratch, "a3r_model_finalize", it.name.c_str(), stream)) return rc;
     }
     m->finalized = true;
+    m->fc_table.flush();
     return A3R_OK;
 }
 
@@ -458,6 +468,9 @@ struct Plan {
     bool trace = getenv("A3R_TRACE") != nullptr;   // debugging aid: name + synchronise every op
     int opno = 0;
     bool dry() const { return ar.dry; }
+    // mute: the ops are walked -- allocations, sites and their scales as ever -- but launch nothing (the encoder stage of a call
+    // whose every frame was found in the frame cache)
+    bool mute = false;
     // ---- fh2 range control: every op that WRITES an fh2 tensor is a site (numbered in plan order) with its own power-of-two
     // scale; the scale travels with the buffer pointer to the ops that read it
     int phase = 0, site_no = 0;
@@ -523,7 +536,7 @@ struct Plan {
         if (skip()) return;
         traced(what, (int)M, K);
         const Site s = out_site(f, y);
-        if (!rc) rc = op_split(f, x, K, y, M, K, row_pair, s.scale, s.stat, stream);
+        if (!rc && !mute) rc = op_split(f, x, K, y, M, K, row_pair, s.scale, s.stat, stream);
     }
     // fp32 activation -> GEMM input: a split pass into `scratch`, the array itself on the exact-fp32 kernels
     const float* gin_from(const float* x, float* scratch, long M, int K) {
@@ -548,7 +561,7 @@ struct Plan {
         const Twin* tw = twin(w, f);
         a3r_epilogue e = retarget(e0, f, [&](a3r_epilogue& r) { range_epi(r, xg, y); });
         e.x_pair = (f == Form::BF3 && pair && !plain_x) ? 1 : 0;
-        if (!rc) rc = op_linear(f, xg, lda, w, tw, y, ldc, M, N, K, e, stream);
+        if (!rc && !mute) rc = op_linear(f, xg, lda, w, tw, y, ldc, M, N, K, e, stream);
     }
     // nn.Linear / 1x1 conv on a plain fp32 activation (DPT adapters), exact-fp32 MFMA
     void linear_f32(const float* x, int lda, const float* w, float* y, int ldc, int M, int N, int K, const a3r_epilogue& e) {
@@ -615,13 +628,13 @@ struct Plan {
             auto it = m->ln_scale.find(w);
             const float sc = it == m->ln_scale.end() ? 1.f : it->second;
             buf_scale[yg] = sc;
-            rc = a3r_layernorm_fh2(x, w, b, yg, M, D, 1e-6f, sc, nullptr, stream);
-        } else rc = gf == Form::BF3 ? a3r_layernorm_bf3(x, w, b, yg, M, D, 1e-6f, pair, stream) : a3r_layernorm(x, w, b, yg, M, D, 1e-6f, stream);
+            if (!mute) rc = a3r_layernorm_fh2(x, w, b, yg, M, D, 1e-6f, sc, nullptr, stream);
+        } else if (!mute) rc = gf == Form::BF3 ? a3r_layernorm_bf3(x, w, b, yg, M, D, 1e-6f, pair, stream) : a3r_layernorm(x, w, b, yg, M, D, 1e-6f, stream);
     }
     void ln_f32(const float* x, const float* w, const float* b, float* y, int M, int D) {
         if (skip()) return;
         traced("layernorm_f32", M, D);
-        rc = a3r_layernorm(x, w, b, y, M, D, 1e-6f, stream);
+        if (!mute) rc = a3r_layernorm(x, w, b, y, M, D, 1e-6f, stream);
     }
     // q, k, v, o are gin buffers (operand forms: straight from / to the projection GEMMs, no fp32 round trip)
     // kv_buf: the buffer k and v are columns of when it is not q's (cross-attention); o_alias: the second side's rows of o when the
@@ -635,9 +648,10 @@ struct Plan {
             const float sq = scale_of(q), skv = kv_buf ? scale_of(kv_buf) : sq;
             const Site so = site(o, o_alias);
             const a3r_fh2_attn_range r = {sq, skv, skv, so.scale, so.stat};
-            if (!rc) rc = a3r_attention_fh2_mapped(q, ldq, k, ldk, v, ldv, o, ldo, B, H, Nq, Nk, &r, q_map, kv_map, stream);
+            if (!rc && !mute) rc = a3r_attention_fh2_mapped(q, ldq, k, ldk, v, ldv, o, ldo, B, H, Nq, Nk, &r, q_map, kv_map, stream);
             return;
         }
+        if (mute) return;
         rc = gf == Form::BF3 ? a3r_attention_bf3(q, ldq, k, ldk, v, ldv, o, ldo, B, H, Nq, Nk, pair, stream)
                    : a3r_attention(q, ldq, k, ldk, v, ldv, o, ldo, B, H, Nq, Nk, stream);
     }
@@ -767,7 +781,13 @@ struct Distinct {
     // [2 Um] the image / prior row of each side's entries, map_eo [2 B] the row s Um + e of slot (s, b)'s entry e among the 2 Um, and
     // map_ekv [2 B] that of the other side's slot b inside side s's block, s Um + map_e[1 - s][b]: where slot (s, b)'s keys live
     int n_ent; const int32_t *ent_img, *ent_pd, *map_eo, *map_ekv;
+    // Frames kept across calls (null: none are): the encoder runs on the n_miss images uniq_miss [n_miss] that were not found
+    // (slots, device), and image k < n_img takes its enc_norm rows from entry ent[k] when miss[k] < 0, else the miss[k]-th
+    // encoded image's, which go to entry ent[k] when that is >= 0 (frame_cache_exchange).  The image stage then runs on the
+    // distinct list even when that holds all 2 B slots.
+    const struct CacheCall* fc = nullptr;
 };
+struct CacheCall { FrameCacheLayout lay; const void* keys; int n_miss; const int32_t *uniq_miss, *ent, *miss; };
 // the sizing pass: counts, no lists
 Distinct distinct_counts(int n_img, int n_pd, int n_side) {
     return {n_img, n_pd, nullptr, nullptr, nullptr, nullptr, {n_side, n_side}, {nullptr, nullptr}, {nullptr, nullptr}, 0, nullptr, nullptr,
@@ -819,7 +839,7 @@ struct Dims {
     Dims(const a3r_model_config& c_, const Call& k)
         : c(c_), B(k.B), H(k.H), W(k.W), E(c.enc_embed_dim), D(c.dec_embed_dim), F(c.feature_dim), L(c.last_dim), nh(k.H / 16),
           nw(k.W / 16), N(nh * nw), BN(B * N), M2(2 * BN),
-          d_img(k.dd && k.phase == 0 && k.dd->n_img < 2 * B && (size_t)k.dd->n_img * N * E <= 3 * (size_t)M2 * D),
+          d_img(k.dd && k.phase == 0 && (k.dd->n_img < 2 * B || k.dd->fc) && (size_t)k.dd->n_img * N * E <= 3 * (size_t)M2 * D),
           d_pd(k.dd && k.dd->n_pd < 2 * B), Mi(d_img ? k.dd->n_img * N : M2), Mp(d_pd ? k.dd->n_pd * N : M2) {}
 };
 
@@ -846,8 +866,9 @@ void tap_copy(Plan& P, const Dims& g, float* dst, const float* src) {
     }
 }
 
-// ViT encoder (_encode_image model.py:151-163) on M = n N rows: the images of k.img -- the distinct ones (d_img), both views', or
-// the B frames of an encode call (img[1] null) -- patchified into cols, enc_norm rows to `out`
+// ViT encoder (_encode_image model.py:151-163) on M = n N rows: the images of k.img -- the distinct ones (d_img; with a frame
+// cache those of them it does not hold), both views', or the B frames of an encode call (img[1] null) -- patchified into cols,
+// enc_norm rows to `out`.  Under P.mute (no image left to encode) M is one image's rows and nothing is launched.
 void encoder_stage(Plan& P, const Call& k, const Dims& g, float* cols, float* cols3, int M, float* out) {
     a3r_model_s* m = P.m;
     const int E = g.E, hidden = E * g.c.mlp_ratio;
@@ -856,9 +877,11 @@ void encoder_stage(Plan& P, const Call& k, const Dims& g, float* cols, float* co
     float* qkv = P.gin_alloc(M, 3 * E);
     float* att = P.gin_alloc(M, E);
     float* hid = P.gin_alloc(M, hidden);
-    if (!P.skip()) {
+    if (!P.skip() && !P.mute) {
         const long sb = 3L * g.H * g.W, sc = (long)g.H * g.W, sy = g.W, sx = 1;
-        if (g.d_img) P.rc = patchify_indexed(k.img[0], k.img[1], k.dd->uniq_img, k.dd->n_img, g.B, cols, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
+        const CacheCall* fc = g.d_img ? k.dd->fc : nullptr;
+        if (fc) P.rc = patchify_indexed(k.img[0], k.img[1], fc->uniq_miss, fc->n_miss, g.B, cols, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
+        else if (g.d_img) P.rc = patchify_indexed(k.img[0], k.img[1], k.dd->uniq_img, k.dd->n_img, g.B, cols, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
         else if (!(P.rc = a3r_patchify(k.img[0], cols, g.B, 3, g.H, g.W, sb, sc, sy, sx, P.stream)) && k.img[1])
             P.rc = a3r_patchify(k.img[1], cols + (size_t)g.BN * 768, g.B, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
     }
@@ -1215,7 +1238,23 @@ int run_plan(a3r_model_s* m, const Call& k, size_t* peak = nullptr) {
     float* cols = ar.alloc((size_t)Mc * 768);
     float* cols3 = P.gin_scratch(Mc, 768);
     if (k.phase == 2) load_features(P, k, g, v.feat);
-    else {
+    else if (const CacheCall* fc = g.d_img ? k.dd->fc : nullptr) {
+        // Frames kept across calls: the encoder runs on the images the cache does not hold and leaves their rows in `feat`, idle
+        // until the copy below; the exchange pass puts every distinct frame's rows, stored or fresh, into featu and the fresh ones
+        // with their images into their entries.  The encoder's sites keep their numbers; their statistics words are completed
+        // from the entries' (frame_cache_stats).
+        const int lo = P.site_no;
+        P.mute = fc->n_miss == 0;
+        encoder_stage(P, k, g, cols, cols3, P.mute ? g.N : fc->n_miss * g.N, v.feat);
+        P.mute = false;
+        if (!P.skip())
+            P.rc = frame_cache_exchange(k.img[0], k.img[1], g.B, fc->keys, fc->lay, k.dd->uniq_img, fc->ent, fc->miss, k.dd->n_img, v.feat,
+                                        v.featu, P.stream);
+        if (!P.skip() && P.gf == Form::FH2)
+            P.rc = frame_cache_stats(fc->lay, fc->ent, fc->miss, k.dd->n_img, m->stats, lo, std::min(P.site_no, (int)a3r_model_s::MAX_SITES),
+                                     P.stream);
+        copy_rows(P, g, v.featu, v.feat, k.dd->map_img, E);
+    } else {
         encoder_stage(P, k, g, cols, cols3, g.Mi, v.featu);
         if (g.d_img) copy_rows(P, g, v.featu, v.feat, k.dd->map_img, E);
     }
@@ -1250,15 +1289,30 @@ int run_plan(a3r_model_s* m, const Call& k, size_t* peak = nullptr) {
 // on, a batch beyond DEDUP_MAX_SLOTS, nothing to merge, or a slot that differs from its representative: a key collision).
 namespace {
 constexpr int DD_HALF = DEDUP_MAX_SLOTS / 2;                       // slots of one kind at most
-constexpr size_t DD_HOST_LIST = (DEDUP_REP_INTS + 63) / 64 * 64;   // pinned host words: rep + flag | the DD_LISTS lists
-constexpr size_t DD_REP_OFF = DEDUP_KEY_BYTES;                     // device bytes: keys | rep + flag | the DD_LISTS lists
+// pinned host words: rep + flag + the frame cache's answer for the 2 B image slots (B <= FC_MAX_PAIRS) | the DD_LISTS lists
+constexpr size_t DD_HOST_LIST = (DEDUP_REP_INTS + 2 * FC_MAX_PAIRS + 63) / 64 * 64;
+constexpr size_t DD_REP_OFF = DEDUP_KEY_BYTES;                     // device bytes: keys | rep + flag + answer | the DD_LISTS lists
 constexpr size_t DD_LIST_OFF = DD_REP_OFF + DD_HOST_LIST * 4;
-constexpr int DD_LISTS = 10;          // uniq_img, map_img, uniq_pd, map_pd, uniq_side [2][B], map_side [2][B], ent_img, ent_pd, map_eo, map_ekv
+// uniq_img, map_img, uniq_pd, map_pd, uniq_side [2][B], map_side [2][B], ent_img, ent_pd, map_eo, map_ekv; frame cache: uniq_miss, ent, miss
+constexpr int DD_LISTS = 13;
 constexpr size_t DD_DEV_BYTES = DD_LIST_OFF + (size_t)DD_LISTS * DD_HALF * 4;
+static_assert(FC_STAT_WORDS == a3r_model_s::MAX_SITES, "an entry stores one word per site");
+
+// The storage of the frame cache as entries of this resolution (dedup.h); a change of resolution empties the table
+FrameCacheLayout frame_cache_at(a3r_model_s* m, int H, int W) {
+    const FrameCacheLayout lay = frame_cache_layout(m->fc_buf, m->fc_bytes, 3L * H * W, (long)(H / 16) * (W / 16) * m->cfg.enc_embed_dim);
+    if (H != m->fc_H || W != m->fc_W || lay.cap != m->fc_table.cap) {
+        m->fc_table.reset(lay.cap);
+        m->fc_H = H;
+        m->fc_W = W;
+    }
+    return lay;
+}
 
 int find_distinct(a3r_model_s* m, const float* a1, const float* a2, long words_a, bool encode, const float* pd1, const float* pd2, int B,
-                  int H, int W, void* stream, Distinct* d, bool* use) {
+                  int H, int W, void* stream, Distinct* d, bool* use, CacheCall* cc = nullptr) {
     *use = false;
+    m->last_fc[0] = m->last_fc[1] = m->last_fc[2] = 0;
     m->last_img_unique = m->last_pd_unique = 2 * B;
     m->last_fell_back = 0;
     m->last_side_unique[0] = m->last_side_unique[1] = B;
@@ -1275,7 +1329,16 @@ int find_distinct(a3r_model_s* m, const float* a1, const float* a2, long words_a
     const int S = 2 * B, first = first_kind ? 0 : S;
     if (int rc = dedup_find(a1, a2, pd1, pd2, B, words_a, 3L * H * W, first, m->dedup_mode == 2, dev, rep_dev, stream)) return rc;
     hipStream_t st = as_stream(stream);
-    A3R_HIP(hipMemcpyAsync(m->dd_host, rep_dev, (size_t)(2 * S + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    // frames kept across calls: the lookup's answer for the 2 B image slots follows the flag in the same read-back
+    bool cached = cc && m->fc_buf && encode && first_kind && B <= FC_MAX_PAIRS;
+    if (cached) {
+        cc->lay = frame_cache_at(m, H, W);
+        cc->keys = dev;
+        A3R_CHECK_ARG(cc->lay.cap > 0, "a3r_model_forward: the frame cache's storage (%zu bytes) is smaller than one entry at %d x %d (%zu bytes)",
+                      m->fc_bytes, H, W, frame_cache_entry_bytes(cc->lay.words_img, cc->lay.words_feat));
+        if (int rc = frame_cache_lookup(a1, a2, B, dev, rep_dev, cc->lay, m->fc_table.mask(), rep_dev + 2 * S + 1, stream)) return rc;
+    }
+    A3R_HIP(hipMemcpyAsync(m->dd_host, rep_dev, (size_t)(2 * S + 1 + (cached ? S : 0)) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     A3R_HIP(hipStreamSynchronize(st));
     const int32_t* rep = m->dd_host;
     if (rep[2 * S] != 0) {
@@ -1338,13 +1401,33 @@ int find_distinct(a3r_model_s* m, const float* a1, const float* a2, long words_a
         }
     }
     m->last_ent_merged = n_ent > 0;
-    if (n_img == S && n_pd == S && n_side[0] == B && n_side[1] == B) return A3R_OK;
+    // The frame cache: hits and misses among the distinct images, victims for the misses (FrameCacheTable::assign), the lists of
+    // the exchange pass.  It needs the image stage on the distinct list, whose rows must fit where they wait (above).
+    cached = cached && (size_t)n_img * c.enc_embed_dim <= 3 * (size_t)S * c.dec_embed_dim;
+    if (cached) {
+        const int32_t *uniq = list, *answer = rep + 2 * S + 1;
+        int32_t *uniq_miss = list + 10 * DD_HALF, *ent = list + 11 * DD_HALF, *miss = list + 12 * DD_HALF;
+        for (int k = 0; k < n_img; k++) miss[k] = answer[uniq[k]];
+        cached = m->fc_table.assign(miss, n_img, ent, m->last_fc) == 0;
+        if (cached) {
+            cc->n_miss = 0;
+            for (int k = 0; k < n_img; k++) {
+                const bool hit = miss[k] >= 0;
+                if (!hit) uniq_miss[cc->n_miss] = uniq[k];
+                miss[k] = hit ? -1 : cc->n_miss++;
+            }
+            cc->uniq_miss = list_dev + 10 * DD_HALF;
+            cc->ent = list_dev + 11 * DD_HALF;
+            cc->miss = list_dev + 12 * DD_HALF;
+        }
+    }
+    if (!cached && n_img == S && n_pd == S && n_side[0] == B && n_side[1] == B) return A3R_OK;
     m->last_side_merged[0] = n_side[0] < B;
     m->last_side_merged[1] = n_side[1] < B;
     A3R_HIP(hipMemcpyAsync(list_dev, list, (size_t)DD_LISTS * DD_HALF * sizeof(int32_t), hipMemcpyHostToDevice, st));
     *d = {n_img, n_pd, list_dev, list_dev + DD_HALF, list_dev + 2 * DD_HALF, list_dev + 3 * DD_HALF,
           {n_side[0], n_side[1]}, {list_dev + 4 * DD_HALF, list_dev + 4 * DD_HALF + B}, {list_dev + 5 * DD_HALF, list_dev + 5 * DD_HALF + B},
-          n_ent, list_dev + 6 * DD_HALF, list_dev + 7 * DD_HALF, list_dev + 8 * DD_HALF, list_dev + 9 * DD_HALF};
+          n_ent, list_dev + 6 * DD_HALF, list_dev + 7 * DD_HALF, list_dev + 8 * DD_HALF, list_dev + 9 * DD_HALF, cached ? cc : nullptr};
     *use = true;
     return A3R_OK;
 }
@@ -1401,14 +1484,17 @@ extern "C" int a3r_model_forward(a3r_model_t m, const float* img1, const float* 
     A3R_CHECK_ARG(workspace_bytes >= need_bytes, "a3r_model_forward: workspace too small (%zu < %zu)", workspace_bytes, need_bytes);
     Distinct d;
     bool merge = false;
-    if (int rc = find_distinct(m, img1, img2, 3L * H * W, true, pd1, pd2, B, H, W, stream, &d, &merge)) return rc;
+    CacheCall cc;
+    int rc = find_distinct(m, img1, img2, 3L * H * W, true, pd1, pd2, B, H, W, stream, &d, &merge, &cc);
     Call k;
     k.phase = 0; k.B = B; k.H = H; k.W = W;
     k.img[0] = img1; k.img[1] = img2; k.pd[0] = pd1; k.pd[1] = pd2;
     k.pts[0] = pts1; k.pts[1] = pts2; k.conf[0] = conf1; k.conf[1] = conf2;
     k.ws = workspace; k.ws_bytes = workspace_bytes; k.stream = stream;
     k.dd = merge ? &d : nullptr;
-    return run_plan(m, k);
+    if (!rc) rc = run_plan(m, k);
+    if (rc) m->fc_table.flush();          // entries this call was to fill may not have been written
+    return rc;
 }
 
 extern "C" size_t a3r_model_encode_workspace_bytes(a3r_model_t m, int B, int H, int W) {
@@ -1453,7 +1539,36 @@ extern "C" int a3r_model_decode(a3r_model_t m, const float* feat1, const float* 
 }
 extern "C" int a3r_model_set_dedup(a3r_model_t m, int mode) {
     A3R_CHECK_ARG(m && mode >= 0 && mode <= 2, "a3r_model_set_dedup: mode must be 0 (off), 1 (on) or 2 (constant key)");
+    if (mode != m->dedup_mode) m->fc_table.flush();      // (stored keys are those of the mode they were made in)
     m->dedup_mode = mode;
+    return A3R_OK;
+}
+
+extern "C" size_t a3r_model_frame_cache_bytes(a3r_model_t m, int H, int W, int frames) {
+    if (!m || H <= 0 || W <= 0 || H % 16 || W % 16 || frames <= 0 || frames > FC_MAX_ENTRIES) return 0;
+    return (size_t)frames * frame_cache_entry_bytes(3L * H * W, (long)(H / 16) * (W / 16) * m->cfg.enc_embed_dim);
+}
+
+extern "C" int a3r_model_set_frame_cache(a3r_model_t m, void* buf, size_t bytes) {
+    A3R_CHECK_ARG(m, "a3r_model_set_frame_cache: null handle");
+    m->fc_table.reset(0);
+    m->fc_buf = nullptr;
+    m->fc_bytes = 0;
+    m->fc_H = m->fc_W = 0;
+    if (!buf || !bytes) return A3R_OK;
+    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "a3r_model_set_frame_cache: storage must be 256-byte aligned");
+    const size_t least = a3r_model_frame_cache_bytes(m, 16, 16, 1);
+    A3R_CHECK_ARG(bytes >= least, "a3r_model_set_frame_cache: storage too small for one entry of the smallest image (%zu < %zu)", bytes, least);
+    m->fc_buf = buf;
+    m->fc_bytes = bytes;
+    return A3R_OK;
+}
+
+extern "C" int a3r_model_last_frame_cache(a3r_model_t m, int* hits, int* misses, int* evictions) {
+    A3R_CHECK_ARG(m && hits && misses && evictions, "a3r_model_last_frame_cache: null argument");
+    *hits = m->last_fc[0];
+    *misses = m->last_fc[1];
+    *evictions = m->last_fc[2];
     return A3R_OK;
 }
 
@@ -1535,6 +1650,8 @@ extern "C" int a3r_model_range_check(a3r_model_t m, void* stream, int* n_adjuste
         sc[i] = std::ldexp(1.f, k);
         (*n_adjusted)++;
     }
+    // a call that has to be repeated stored nothing worth keeping, and stored rows do not outlive the scales they were made with
+    if (*n_adjusted || *n_nonfinite) m->fc_table.flush();
     return A3R_OK;
 }
 
@@ -1559,5 +1676,6 @@ extern "C" int a3r_model_range_scales(a3r_model_t m, int phase, float* scales, i
 extern "C" int a3r_model_reset_ranges(a3r_model_t m) {
     A3R_CHECK_ARG(m, "a3r_model_reset_ranges: null handle");
     for (auto& v : m->site_scale) v.clear();
+    m->fc_table.flush();
     return A3R_OK;
 }

@@ -19,8 +19,13 @@ from .weights import ModelConfig, param_spec
 
 
 class PairEngine:
-    def __init__(self, cfg: ModelConfig, state_dict: Dict[str, "torch.Tensor | np.ndarray"], device="cuda:0"):
+    def __init__(self, cfg: ModelConfig, state_dict: Dict[str, "torch.Tensor | np.ndarray"], device="cuda:0", frame_cache=32):
+        """frame_cache: frames whose encoder rows the handle keeps across forward calls (include/a3r.h, a3r_model_set_frame_cache),
+        0 = none; the environment variable A3R_FRAME_CACHE overrides it.  The storage (about 5.5 MB per frame at 512x384) is
+        allocated at the first forward of a resolution."""
         self.lib = _lib.load()
+        self.frame_cache = max(0, min(256, int(os.environ.get("A3R_FRAME_CACHE", frame_cache))))
+        self._fc_store, self._fc_hw = None, None
         self.cfg = cfg
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -95,6 +100,8 @@ class PairEngine:
             if self.workspace is None or self.workspace.numel() < need:
                 self.workspace = None
                 self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+            if self.frame_cache and self._fc_hw != (H, W):
+                self.set_frame_cache(self.frame_cache, H, W)
             if out is None:
                 out = dict(pts3d_1=torch.empty((B, H, W, 3), device=self.device), conf_1=torch.empty((B, H, W), device=self.device),
                            pts3d_2=torch.empty((B, H, W, 3), device=self.device), conf_2=torch.empty((B, H, W), device=self.device))
@@ -154,6 +161,29 @@ class PairEngine:
 
     def reset_ranges(self):
         check(self.lib.a3r_model_reset_ranges(self.handle), "a3r_model_reset_ranges")
+
+    def set_frame_cache(self, frames, H=None, W=None, nbytes=None):
+        """Storage for `frames` frames at H x W (or of nbytes bytes) for the frames kept across forward calls; 0 removes it.  Called
+        by forward at the first call of a resolution; a call by hand fixes the capacity until the resolution changes."""
+        check(self.lib.a3r_model_set_frame_cache(self.handle, None, 0), "a3r_model_set_frame_cache")
+        self._fc_store, self._fc_hw = None, None
+        self.frame_cache = int(frames)
+        if not self.frame_cache:
+            return
+        if nbytes is None:
+            nbytes = int(self.lib.a3r_model_frame_cache_bytes(self.handle, H, W, self.frame_cache))
+            if nbytes == 0:
+                raise RuntimeError(f"frame cache: bad size ({self.frame_cache} frames at {H}x{W})")
+        with torch.cuda.device(self.device):
+            store = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        check(self.lib.a3r_model_set_frame_cache(self.handle, ptr(store), nbytes), "a3r_model_set_frame_cache")
+        self._fc_store, self._fc_hw = store, (H, W)
+
+    def last_frame_cache(self):
+        """(hits, misses, evictions) of the last forward among its distinct images; zeros when it ran without the frame cache."""
+        h, m, e = C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.a3r_model_last_frame_cache(self.handle, C.byref(h), C.byref(m), C.byref(e)), "a3r_model_last_frame_cache")
+        return h.value, m.value, e.value
 
     def set_dedup(self, mode):
         """Duplicate frames inside one forward / decode call (include/a3r.h, a3r_model_set_dedup): 0 = off, 1 = on (default),

@@ -432,7 +432,7 @@ int a3r_model_decode(a3r_model_t m, const float* feat1, const float* feat2, cons
  * 128-bit content key per slot proposes, a bitwise comparison on the device decides), run those parts once per distinct frame and
  * copy the rows to every slot.  Outputs are bitwise those of the plain plan, the fh2 sites and their scales are the same, and the
  * workspace requirement does not change.  Cost: one small read-back and ONE stream synchronise at the start of the call, and about
- * 64 KB of device and pinned host memory owned by the handle.  A comparison that fails (a key collision) makes the call run the
+ * 100 KB of device and pinned host memory owned by the handle.  A comparison that fails (a key collision) makes the call run the
  * plain plan.  With a tap level set, or with more than 512 pairs in a call, the plain plan runs.
  * mode: 0 = off, 1 = on (the default; the environment variable A3R_DEDUP = 0 / 1 / 2 sets the default of new handles), 2 = on with
  * a constant key, so that the comparison alone decides (debugging).
@@ -469,6 +469,29 @@ int a3r_model_set_dedup_decoder(a3r_model_t m, int on);
 /* a3r_model_last_dedup_entries: distinct (image, depth prior) entries of side 1 / side 2 of the last forward call (B where they
  * were not looked for), and whether decoder block 0 ran its frame-only half on them. */
 int a3r_model_last_dedup_entries(a3r_model_t m, int* u1, int* u2, int* merged);
+/* Frames kept ACROSS calls.  Consecutive calls on one clip repeat their frames (a window graph cut into calls of 16 or more pairs),
+ * and a frame's enc_norm rows depend on that frame alone.  With storage installed, a3r_model_forward looks every distinct image of
+ * the call up among the frames the handle has stored -- on the device, in the same read-back and behind the same single
+ * synchronise as the duplicate search: the 128-bit key proposes, a comparison of every bit with the stored copy of the image
+ * decides, so a frame is only ever taken for itself -- encodes the images it did not find, and copies the rows of the others from
+ * the storage.  Outputs are bitwise those of a handle without storage; sites, scales and the workspace requirement do not change.
+ * The encoder sites' statistics words are those of the frames encoded in this call, raised to the words stored with the entries it
+ * read (the words of the call that encoded them): the first call's words exactly when a batch repeats, an upper bound otherwise.
+ * Storage: `frames` entries of a3r_model_frame_cache_bytes(m, H, W, frames) bytes together (0 for a bad argument; at most 256
+ * entries), each the image, its rows, the key and 8 KB of words; buf is device memory, 256-byte aligned, and stays the caller's.
+ * buf == NULL or bytes == 0 removes it.  Storage too small for one entry of the smallest image is refused; a forward at a resolution
+ * of which the storage holds no entry fails with A3R_EINVAL before it writes anything.  The least recently used entry makes room,
+ * never one the same call reads; a call with more new frames than entries stores the first ones.
+ * The entries are dropped by a3r_model_set_weight, a3r_model_finalize, a3r_model_reset_ranges, a3r_model_range_check when it
+ * adjusts a site or finds a non-finite word, a change of the dedup mode, a call at another resolution and a failed call (the
+ * arithmetic mode is fixed when the handle is created).  A call runs as if there were no storage, and leaves it alone, with dedup mode 0, a tap level,
+ * more than 512 pairs, a failed comparison among the call's own slots, or encoder widths whose rows do not fit the buffers they wait
+ * in (enc_embed_dim > 3 dec_embed_dim).  a3r_model_decode and a3r_model_encode do not use it.
+ * a3r_model_last_frame_cache: distinct images of the last forward found / not found in the storage, and entries it replaced (all 0
+ * when the call did not use the storage). */
+size_t a3r_model_frame_cache_bytes(a3r_model_t m, int H, int W, int frames);
+int a3r_model_set_frame_cache(a3r_model_t m, void* buf, size_t bytes);
+int a3r_model_last_frame_cache(a3r_model_t m, int* hits, int* misses, int* evictions);
 /* Debug taps for the parity tests: intermediate tensors inside the workspace after a forward; returns device pointer + element
  * count.  name: "feat" (enc_norm output, model.py:163), "hook_a" / "hook_b" (the decoder levels the DPT head reads,
  * dpt_head.py:101), "dec_last" (dec_norm output, model.py:231-232); after a3r_model_set_tap_level(m, L > 0) also "level" (the two
