@@ -183,6 +183,52 @@ int frame_cache_exchange(const float* img1, const float* img2, int B, const void
 int frame_cache_stats(const FrameCacheLayout& l, const int32_t* ent, const int32_t* miss, int U, unsigned* stats, int lo, int hi,
                       void* stream);
 
+// ---- frame products kept across calls (a3r_model_set_frame_products): what the plan makes from one depth prior alone -- the
+// outputs z_0 .. z_n of the zero-convs -- in a second storage of the same layout (the `feat` of an entry: the levels' [N, D] rows
+// one after the other), with a FrameCacheTable of its own and the lookup above on the pred_depth slots.
+// The sites of the ops a call may skip, which do not form one range: a bit per statistics word.
+struct SiteMask {
+    uint32_t w[FC_STAT_WORDS / 32] = {};
+    void add(int lo, int hi) {          // sites [lo, hi), clipped to the words there are
+        for (int i = lo < 0 ? 0 : lo; i < hi && i < FC_STAT_WORDS; i++) w[i / 32] |= 1u << (i % 32);
+    }
+    bool has(int i) const { return i >= 0 && i < FC_STAT_WORDS && ((w[i / 32] >> (i % 32)) & 1u); }
+};
+// The lists of one call, after FrameCacheTable::assign.  hit[k] (k < U) is the lookup's answer for the call's k-th distinct prior
+// (an entry, or -1).  Writes miss[k] = -1 for a hit, else the prior's row j among the n_miss priors the branch runs on, whose
+// slots uniq[k] go to uniq_miss[j]; and for each of the n rows row[i] (a distinct prior each) where the gather-add pass finds its
+// z: src[i] = the entry of a hit, or ~j (negative) for the j-th fresh row block.  *n_store = the misses that have an entry to go
+// to (ent[k] >= 0).  Returns n_miss, or -1 for a row outside 0 .. U - 1 or a missing argument.
+inline int prior_lists(const int32_t* hit, const int32_t* ent, const int32_t* uniq, int U, int32_t* miss, int32_t* uniq_miss,
+                       const int32_t* row, int n, int32_t* src, int* n_store) {
+    if (!hit || !ent || !uniq || !miss || !uniq_miss || !row || !src || !n_store || U <= 0 || n < 0) return -1;
+    int n_miss = 0;
+    *n_store = 0;
+    for (int k = 0; k < U; k++) {
+        if (hit[k] >= 0) { miss[k] = -1; continue; }
+        uniq_miss[n_miss] = uniq[k];
+        miss[k] = n_miss++;
+        *n_store += ent[k] >= 0;
+    }
+    for (int i = 0; i < n; i++) {
+        const int32_t k = row[i];
+        if (k < 0 || k >= U) return -1;
+        src[i] = miss[k] < 0 ? hit[k] : ~miss[k];
+    }
+    return n_miss;
+}
+// Device side.  For every distinct item k < U that was not found (miss[k] >= 0) and has an entry (ent[k] >= 0): with `fresh`, the
+// part_words words of fresh row block miss[k] go to words [part_off, part_off + part_words) of the entry's `feat`; without, the
+// item itself (slot uniq[k] of img1 / img2) and its key go to the entry.
+int frame_cache_store(const float* img1, const float* img2, int B, const void* keys, const FrameCacheLayout& l, const int32_t* uniq,
+                      const int32_t* ent, const int32_t* miss, int U, const float* fresh, long part_off, long part_words, void* stream);
+// frame_cache_stats on the words of `sites`
+int frame_cache_stats_sites(const FrameCacheLayout& l, const int32_t* ent, const int32_t* miss, int U, unsigned* stats,
+                            const SiteMask& sites, void* stream);
+// a3r_gather_add_rows whose rows a come from two places (a3r.h: a3r_gather_add_rows_src is the same with a C signature)
+int gather_add_rows_src(const float* store, long stride, const float* fresh, const int32_t* src, const float* b, const int32_t* map_b,
+                        float* dst, int S, int N, int C, void* stream);
+
 // ---- device side (dedup.hip).  An item of the first kind is one image [3, H, W] -- or, for the decode call, one frame's encoder
 // features [N, E] --, one of the second kind a pred_depth map [H, W, 3]: words_a / words_pd 32-bit words each, multiples of 4.  Slot s < 4 B of a call is item s % B of group s / B, the groups being img1, img2, pd1, pd2; slots 0 .. 2 B - 1
 // are the image kind, 2 B .. 4 B - 1 the depth-prior kind, and a representative is looked for inside a slot's own kind only.

@@ -172,11 +172,40 @@ __global__ __launch_bounds__(256) void fc_exchange_kernel(Images im, int B, long
     if (blockIdx.x == 0 && threadIdx.x < 2) ekeys[2 * e + threadIdx.x] = keys[2 * slot + threadIdx.x];
 }
 
-// one thread per statistics word lo + i
-__global__ void fc_stats_kernel(unsigned* __restrict__ estats, const int* __restrict__ ent, const int* __restrict__ miss, int U,
-                                unsigned* __restrict__ stats, int lo, int hi) {
-    const int i = lo + blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= hi) return;
+// fc_exchange_kernel's stores alone, in parts: a missed item k with an entry e puts units_part units of fresh block miss[k] at
+// unit `off` of the entry's rows, or without `fresh` its own bits and key; same grid
+__global__ __launch_bounds__(256) void fc_store_kernel(Images im, int B, long units_img, long units_feat, long off, long units_part,
+                                                       const unsigned long long* __restrict__ keys, unsigned long long* __restrict__ ekeys,
+                                                       uint4* __restrict__ eimg, uint4* __restrict__ efeat, const int* __restrict__ uniq,
+                                                       const int* __restrict__ ent, const int* __restrict__ miss,
+                                                       const uint4* __restrict__ fresh) {
+    const int k = blockIdx.y, e = ent[k], j = miss[k];
+    if (j < 0 || e < 0) return;
+    const long u0 = (long)blockIdx.x * UNITS_PER_BLOCK;
+    if (fresh) {
+        const uint4* __restrict__ src = fresh + (long)j * units_part;
+        uint4* __restrict__ dst = efeat + (long)e * units_feat + off;
+        for (int i = 0; i < UNITS_PER_BLOCK / 256; i++) {
+            const long u = u0 + i * 256 + threadIdx.x;
+            if (u < units_part) dst[u] = src[u];
+        }
+        return;
+    }
+    const int slot = uniq[k];
+    const uint4* __restrict__ p = im.base[slot / B] + (long)(slot % B) * units_img;
+    uint4* __restrict__ q = eimg + (long)e * units_img;
+    for (int i = 0; i < UNITS_PER_BLOCK / 256; i++) {
+        const long u = u0 + i * 256 + threadIdx.x;
+        if (u < units_img) q[u] = p[u];
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 2) ekeys[2 * e + threadIdx.x] = keys[2 * slot + threadIdx.x];
+}
+
+// one thread per statistics word: those of `sites`
+__global__ void fc_stats_sites_kernel(unsigned* __restrict__ estats, const int* __restrict__ ent, const int* __restrict__ miss, int U,
+                                      unsigned* __restrict__ stats, SiteMask sites) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= FC_STAT_WORDS || !((sites.w[i >> 5] >> (i & 31)) & 1u)) return;
     const unsigned own = stats[i];
     unsigned w = own;
     for (int k = 0; k < U; k++) {
@@ -235,17 +264,43 @@ int frame_cache_exchange(const float* img1, const float* img2, int B, const void
     return A3R_OK;
 }
 
-int frame_cache_stats(const FrameCacheLayout& l, const int32_t* ent, const int32_t* miss, int U, unsigned* stats, int lo, int hi,
-                      void* stream) {
-    A3R_CHECK_ARG(fc_layout_ok(l) && ent && miss && stats && U > 0 && lo >= 0 && lo <= hi && hi <= FC_STAT_WORDS,
-                  "frame_cache_stats: bad argument (sites %d .. %d)", lo, hi);
-    if (hi == lo) return A3R_OK;
+int frame_cache_store(const float* img1, const float* img2, int B, const void* keys, const FrameCacheLayout& l, const int32_t* uniq,
+                      const int32_t* ent, const int32_t* miss, int U, const float* fresh, long part_off, long part_words, void* stream) {
+    A3R_CHECK_ARG(B > 0 && B <= FC_MAX_PAIRS && U > 0 && U <= 2 * B && fc_layout_ok(l), "frame_cache_store: bad shape (B=%d, U=%d)", B, U);
+    A3R_CHECK_ARG(uniq && ent && miss && (fresh || (img1 && img2 && keys)) && (reinterpret_cast<uintptr_t>(fresh) & 15) == 0,
+                  "frame_cache_store: null or misaligned pointer");
+    A3R_CHECK_ARG(!fresh || (part_off >= 0 && part_words > 0 && part_off % 4 == 0 && part_words % 4 == 0 && part_off + part_words <= l.words_feat),
+                  "frame_cache_store: words %ld + %ld outside an entry's %ld", part_off, part_words, l.words_feat);
     hipStream_t st = as_stream(stream);
-    ProfScope prof(PK_ELEMENTWISE, 4.0 * (hi - lo) * (U + 2), st);
-    hipLaunchKernelGGL(fc_stats_kernel, dim3((hi - lo + 255) / 256), dim3(256), 0, st, reinterpret_cast<unsigned*>(l.stats), ent, miss, U,
-                       stats, lo, hi);
+    const Images im = {{reinterpret_cast<const uint4*>(img1), reinterpret_cast<const uint4*>(img2)}};
+    const long ui = l.words_img / 4, units = fresh ? part_words / 4 : ui;
+    ProfScope prof(PK_ELEMENTWISE, 32.0 * U * units, st);
+    const dim3 grid((unsigned)((units + UNITS_PER_BLOCK - 1) / UNITS_PER_BLOCK), (unsigned)U);
+    hipLaunchKernelGGL(fc_store_kernel, grid, dim3(256), 0, st, im, B, ui, l.words_feat / 4, part_off / 4, part_words / 4,
+                       static_cast<const unsigned long long*>(keys), reinterpret_cast<unsigned long long*>(l.keys),
+                       reinterpret_cast<uint4*>(l.img), reinterpret_cast<uint4*>(l.feat), uniq, ent, miss, reinterpret_cast<const uint4*>(fresh));
     A3R_LAUNCH_CHECK();
     return A3R_OK;
+}
+
+int frame_cache_stats_sites(const FrameCacheLayout& l, const int32_t* ent, const int32_t* miss, int U, unsigned* stats,
+                            const SiteMask& sites, void* stream) {
+    A3R_CHECK_ARG(fc_layout_ok(l) && l.stats && ent && miss && stats && U > 0, "frame_cache_stats: bad argument");
+    hipStream_t st = as_stream(stream);
+    ProfScope prof(PK_ELEMENTWISE, 4.0 * FC_STAT_WORDS * (U + 2), st);
+    hipLaunchKernelGGL(fc_stats_sites_kernel, dim3(FC_STAT_WORDS / 256), dim3(256), 0, st, reinterpret_cast<unsigned*>(l.stats), ent, miss,
+                       U, stats, sites);
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+int frame_cache_stats(const FrameCacheLayout& l, const int32_t* ent, const int32_t* miss, int U, unsigned* stats, int lo, int hi,
+                      void* stream) {
+    A3R_CHECK_ARG(lo >= 0 && lo <= hi && hi <= FC_STAT_WORDS, "frame_cache_stats: bad argument (sites %d .. %d)", lo, hi);
+    if (hi == lo) return A3R_OK;
+    SiteMask sites;
+    sites.add(lo, hi);
+    return frame_cache_stats_sites(l, ent, miss, U, stats, sites, stream);
 }
 
 int dedup_find(const float* img1, const float* img2, const float* pd1, const float* pd2, int B, long words_a, long words_pd, int first,
@@ -276,3 +331,11 @@ int dedup_find(const float* img1, const float* img2, const float* pd1, const flo
 }
 
 }  // namespace a3r
+
+extern "C" int a3r_frame_cache_stats_sites(void* storage, size_t bytes, int64_t words_item, int64_t words_rows, const int32_t* ent,
+                                           const int32_t* miss, int U, unsigned* stats, const uint32_t* site_mask, void* stream) {
+    A3R_CHECK_ARG(storage && site_mask && words_item > 0 && words_rows > 0, "a3r_frame_cache_stats_sites: bad argument");
+    a3r::SiteMask sites;
+    for (int i = 0; i < a3r::FC_STAT_WORDS / 32; i++) sites.w[i] = site_mask[i];
+    return a3r::frame_cache_stats_sites(a3r::frame_cache_layout(storage, bytes, words_item, words_rows), ent, miss, U, stats, sites, stream);
+}

@@ -305,6 +305,22 @@ __global__ void gather_add_rows_kernel(const f32x4* __restrict__ a, const int* _
     }
 }
 
+// the same with the row blocks of a in two places (dedup.h, frame products): src[s] >= 0 names an entry of `store`, whose blocks lie
+// stride4 float4 apart, src[s] < 0 the fresh block ~src[s]
+__global__ void gather_add_rows_src_kernel(const f32x4* __restrict__ store, long stride4, const f32x4* __restrict__ fresh,
+                                           const int* __restrict__ src, const f32x4* __restrict__ b, const int* __restrict__ map_b,
+                                           f32x4* dst, int S, long NC4) {
+    const long total = (long)S * NC4;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int s = (int)(i / NC4);
+        const long r = i - s * NC4;
+        const int e = src[s];
+        const f32x4 va = e >= 0 ? store[(long)e * stride4 + r] : fresh[(long)~e * NC4 + r];
+        const f32x4 vb = b ? b[(long)map_b[s] * NC4 + r] : dst[i];
+        dst[i] = va + vb;
+    }
+}
+
 // ------------------------------------------------------------------------------------------- residual combine on distinct frames
 // What the RESID2 epilogue of refinenet1.resConfUnit1's second conv produces, when that conv (and the skip it adds) ran on the U
 // distinct frames of a side only (dedup.h): for slot b < S with k = map[b], per pixel row and channel
@@ -865,6 +881,26 @@ extern "C" int a3r_gather_add_rows(const float* a, const int32_t* map_a, const f
                        map_a, reinterpret_cast<const f32x4*>(b), map_b, reinterpret_cast<f32x4*>(dst), S, NC4);
     A3R_LAUNCH_CHECK();
     return A3R_OK;
+}
+
+int a3r::gather_add_rows_src(const float* store, long stride, const float* fresh, const int32_t* src, const float* b, const int32_t* map_b,
+                             float* dst, int S, int N, int C, void* stream) {
+    A3R_CHECK_ARG(store && fresh && src && dst && (!b || map_b), "a3r_gather_add_rows_src: null pointer");
+    A3R_CHECK_ARG(S > 0 && N > 0 && C > 0 && C % 4 == 0 && stride >= (long)N * C && stride % 4 == 0, "a3r_gather_add_rows_src: bad shape");
+    A3R_CHECK_ARG(((reinterpret_cast<uintptr_t>(store) | reinterpret_cast<uintptr_t>(fresh) | reinterpret_cast<uintptr_t>(b) |
+                    reinterpret_cast<uintptr_t>(dst)) & 15) == 0, "a3r_gather_add_rows_src: buffers must be 16-byte aligned");
+    const long NC4 = (long)N * (C / 4), total = (long)S * NC4;
+    ProfScope prof(PK_ELEMENTWISE, 48.0 * total, as_stream(stream));
+    hipLaunchKernelGGL(gather_add_rows_src_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream),
+                       reinterpret_cast<const f32x4*>(store), stride / 4, reinterpret_cast<const f32x4*>(fresh), src,
+                       reinterpret_cast<const f32x4*>(b), map_b, reinterpret_cast<f32x4*>(dst), S, NC4);
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+extern "C" int a3r_gather_add_rows_src(const float* store, long stride, const float* fresh, const int32_t* src, const float* b,
+                                       const int32_t* map_b, float* dst, int S, int N, int C, void* stream) {
+    return a3r::gather_add_rows_src(store, stride, fresh, src, b, map_b, dst, S, N, C, stream);
 }
 
 int a3r::combine_resid_fh2(const float* c, const float* r0, const float* p2, const int32_t* map, float* s, void* sr2, int S, long P, int C,

@@ -9,8 +9,8 @@
 // Data layout: tokens [rows, C] with rows = (side, batch, token): the first B*N rows belong to view 1,
 // the next B*N rows to view 2 (this is the reference's torch.cat((img1, img2)) batch order), maps are
 // channels-last.  All buffers live in the caller's workspace; nothing here allocates device memory, except the handle's key / map
-// words for the duplicate search (find_distinct, about 100 KB).  The frames kept across calls live in storage the caller installs
-// (a3r_model_set_frame_cache).
+// words for the duplicate search (find_distinct, about 130 KB).  The frames and depth priors kept across calls live in storage the
+// caller installs (a3r_model_set_frame_cache, a3r_model_set_frame_products).
 #include "plan.h"
 #include "dedup.h"
 #include <algorithm>
@@ -91,6 +91,18 @@ struct a3r_model_s {
     FrameCacheTable fc_table;
     int fc_H = 0, fc_W = 0;
     int last_fc[3] = {0, 0, 0};
+    // frame products kept across calls (a3r_model_set_frame_products): the caller's second storage, which holds as many depth priors
+    // with their zero-conv outputs as the frame cache holds frames, the table of those entries, and what the last forward did
+    // with it (a3r_model_last_frame_products: hits, misses, evictions)
+    void* fp_buf = nullptr;
+    size_t fp_bytes = 0;
+    FrameCacheTable pd_table;
+    int last_pd[3] = {0, 0, 0};
+    // whatever was stored under other weights, scales, keys or after a failed call is forgotten
+    void drop_stored() {
+        fc_table.flush();
+        pd_table.flush();
+    }
     ~a3r_model_s() {
         if (dd_dev) (void)hipFree(dd_dev);
         if (dd_host) (void)hipHostFree(dd_host);
@@ -148,7 +160,7 @@ extern "C" int a3r_model_set_weight(a3r_model_t m, const char* name, const float
     A3R_CHECK_ARG(m, "a3r_model_set_weight: bad argument");
     if (int rc = m->w.set("a3r_model_set_weight", name, ptr, ndim, shape)) return rc;
     m->finalized = false;
-    m->fc_table.flush();          // stored rows belong to the weights they were computed with
+    m->drop_stored();          // stored rows belong to the weights they were computed with
     return A3R_OK;
 }
 
@@ -453,7 +465,7 @@ extern "C" int a3r_model_finalize(a3r_model_t m, void* packed, size_t packed_byt
         if (int rc = m->twins.pack(src, (Form)it.s, src, pk + it.off, it.a, it.b, scratch, "a3r_model_finalize", it.name.c_str(), stream)) return rc;
     }
     m->finalized = true;
-    m->fc_table.flush();
+    m->drop_stored();
     return A3R_OK;
 }
 
@@ -471,6 +483,7 @@ struct Plan {
     // mute: the ops are walked -- allocations, sites and their scales as ever -- but launch nothing (the encoder stage of a call
     // whose every frame was found in the frame cache)
     bool mute = false;
+    SiteMask prior_sites;      // the sites of the depth-prior branch, whose words the stored priors complete (PriorScope)
     // ---- fh2 range control: every op that WRITES an fh2 tensor is a site (numbered in plan order) with its own power-of-two
     // scale; the scale travels with the buffer pointer to the ops that read it
     int phase = 0, site_no = 0;
@@ -786,8 +799,29 @@ struct Distinct {
     // encoded image's, which go to entry ent[k] when that is >= 0 (frame_cache_exchange).  The image stage then runs on the
     // distinct list even when that holds all 2 B slots.
     const struct CacheCall* fc = nullptr;
+    // Depth priors kept across calls with their zero-conv outputs (null: none are): the prior branch -- patch embedding,
+    // dec_blocks_pc, zero-convs -- runs on the n_miss priors uniq_miss [n_miss] that were not found (slots inside the kind, device);
+    // prior k < n_pd is entry ent[k]'s when miss[k] < 0, else the miss[k]-th of those, whose z rows and map go to entry ent[k]
+    // when that is >= 0 (n_store of them do).  src [2 B] / src_ent [2 n_ent]: where the gather-add pass finds the z rows of a
+    // slot / of a block-0 entry (prior_lists).  The prior stage then runs on the distinct list even when that holds all 2 B slots.
+    const struct PriorCall* pp = nullptr;
 };
 struct CacheCall { FrameCacheLayout lay; const void* keys; int n_miss; const int32_t *uniq_miss, *ent, *miss; };
+struct PriorCall { FrameCacheLayout lay; const void* keys; int n_miss, n_store; const int32_t *uniq_miss, *ent, *miss, *src, *src_ent; };
+
+// The ops of the prior branch walked while one of these lives: launched on the misses' rows, or not at all (Plan::mute) when the
+// call found every prior, and their sites noted for the statistics pass that ends decoder_stage
+struct PriorScope {
+    Plan& P;
+    const PriorCall* pp;
+    int lo;
+    PriorScope(Plan& P_, const PriorCall* pp_) : P(P_), pp(pp_), lo(P_.site_no) { if (pp) P.mute = pp->n_miss == 0; }
+    ~PriorScope() {
+        if (!pp) return;
+        P.mute = false;
+        P.prior_sites.add(lo, P.site_no);
+    }
+};
 // the sizing pass: counts, no lists
 Distinct distinct_counts(int n_img, int n_pd, int n_side) {
     return {n_img, n_pd, nullptr, nullptr, nullptr, nullptr, {n_side, n_side}, {nullptr, nullptr}, {nullptr, nullptr}, 0, nullptr, nullptr,
@@ -836,11 +870,14 @@ struct Dims {
     int B, H, W, E, D, F, L, nh, nw, N, BN, M2;
     bool d_img, d_pd;
     int Mi, Mp;
+    const PriorCall* pp;      // the stored priors of this call, and the rows the prior branch then runs on (one image's when muted)
+    int prior_rows() const { return !pp ? Mp : pp->n_miss ? pp->n_miss * N : N; }
     Dims(const a3r_model_config& c_, const Call& k)
         : c(c_), B(k.B), H(k.H), W(k.W), E(c.enc_embed_dim), D(c.dec_embed_dim), F(c.feature_dim), L(c.last_dim), nh(k.H / 16),
           nw(k.W / 16), N(nh * nw), BN(B * N), M2(2 * BN),
           d_img(k.dd && k.phase == 0 && (k.dd->n_img < 2 * B || k.dd->fc) && (size_t)k.dd->n_img * N * E <= 3 * (size_t)M2 * D),
-          d_pd(k.dd && k.dd->n_pd < 2 * B), Mi(d_img ? k.dd->n_img * N : M2), Mp(d_pd ? k.dd->n_pd * N : M2) {}
+          d_pd(k.dd && (k.dd->n_pd < 2 * B || k.dd->pp)), Mi(d_img ? k.dd->n_img * N : M2), Mp(d_pd ? k.dd->n_pd * N : M2),
+          pp(k.dd ? k.dd->pp : nullptr) {}
 };
 
 // the buffers that outlive a stage (allocated below the arena mark the stages reset to), and what the stages hand on in them
@@ -906,16 +943,25 @@ void load_features(Plan& P, const Call& k, const Dims& g, float* feat) {
 
 // point-map patch embedding (model.py:244-248) of the Mp rows of the (distinct) depth priors -> pcu; pred_depth is [B,H,W,3]:
 // channel stride 1
+// With stored priors (g.pp) the rows are those of the priors not found, and their maps and keys go to their entries.
 void embed_pc_stage(Plan& P, const Call& k, const Dims& g, float* cols, float* cols3, float* pcu) {
-    if (!P.skip()) {
-        const long sb = 3L * g.H * g.W, sc = 1, sy = 3L * g.W, sx = 3;
-        if (g.d_pd) P.rc = patchify_indexed(k.pd[0], k.pd[1], k.dd->uniq_pd, k.dd->n_pd, g.B, cols, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
-        else if (!(P.rc = a3r_patchify(k.pd[0], cols, g.B, 3, g.H, g.W, sb, sc, sy, sx, P.stream)))
-            P.rc = a3r_patchify(k.pd[1], cols + (size_t)g.BN * 768, g.B, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
+    const PriorCall* pp = g.pp;
+    const int Mq = g.prior_rows();
+    {
+        PriorScope scope(P, pp);
+        if (!P.skip() && !P.mute) {
+            const long sb = 3L * g.H * g.W, sc = 1, sy = 3L * g.W, sx = 3;
+            if (pp) P.rc = patchify_indexed(k.pd[0], k.pd[1], pp->uniq_miss, pp->n_miss, g.B, cols, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
+            else if (g.d_pd) P.rc = patchify_indexed(k.pd[0], k.pd[1], k.dd->uniq_pd, k.dd->n_pd, g.B, cols, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
+            else if (!(P.rc = a3r_patchify(k.pd[0], cols, g.B, 3, g.H, g.W, sb, sc, sy, sx, P.stream)))
+                P.rc = a3r_patchify(k.pd[1], cols + (size_t)g.BN * 768, g.B, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
+        }
+        P.rows(Mq);
+        P.linear(P.gin_from(cols, cols3, Mq, 768), 768, P.m->pepc_w, pcu, g.D, Mq, g.D, 768, P.epi(A3R_EPI_NONE, P.m->pepc_b));
+        P.rows(g.M2);
     }
-    P.rows(g.Mp);
-    P.linear(P.gin_from(cols, cols3, g.Mp, 768), 768, P.m->pepc_w, pcu, g.D, g.Mp, g.D, 768, P.epi(A3R_EPI_NONE, P.m->pepc_b));
-    P.rows(g.M2);
+    if (pp && pp->n_store && !P.skip())
+        P.rc = frame_cache_store(k.pd[0], k.pd[1], g.B, pp->keys, pp->lay, k.dd->uniq_pd, pp->ent, pp->miss, k.dd->n_pd, nullptr, 0, 0, P.stream);
 }
 
 // gin buffers of the decoder, [2 B N, .] rows: side 1 of each starts at gin_at(., BN, .)
@@ -1001,7 +1047,7 @@ void decoder_block_entries(Plan& P, const Dims& g, const BlockW& w0, const Block
 void decoder_stage(Plan& P, const Call& k, const Dims& g, Levels& v) {
     a3r_model_s* m = P.m;
     const a3r_model_config& c = g.c;
-    const int D = g.D, E = g.E, M2 = g.M2, Mp = g.Mp, hidden = D * c.mlp_ratio;
+    const int D = g.D, E = g.E, M2 = g.M2, hidden = D * c.mlp_ratio;
     const int hook_a = c.dec_depth * 2 / 4, hook_b = c.dec_depth * 3 / 4;   // levels 6 and 9 for depth 12
     const DecBufs t = {P.gin_alloc(M2, D), P.gin_alloc(M2, D), P.gin_alloc(M2, 3 * D), P.gin_alloc(M2, D), P.gin_alloc(M2, 2 * D),
                        P.gin_alloc(M2, D), P.gin_alloc(M2, hidden)};      // (a braced list is evaluated in order: so are the allocations)
@@ -1013,21 +1059,34 @@ void decoder_stage(Plan& P, const Call& k, const Dims& g, Levels& v) {
     // The split is the same site over the same set of values.  No buffer is added: the zero-conv's rows z go to v.pc, which holds
     // nothing once the tokens live in pcu, and decoder_embed's to dec_last, which is written after the last block.
     const bool on = P.gf == Form::FH2 && m->dedup_decoder;
-    const bool pc_rows = on && g.d_pd, l0_rows = pc_rows && g.d_img;
+    const bool pc_rows = (on && g.d_pd) || g.pp, l0_rows = on && pc_rows && g.d_img;      // (stored priors need the gather-add form)
     // block 0 on entries: level 0 is made for the 2 Um entries only (nothing else reads it)
     const bool entries = l0_rows && k.dd->n_ent > 0;
-    auto gather_add = [&](const float* a, const int32_t* ma, const float* b, const int32_t* mb, float* x, int S = 0) {
-        if (!P.skip()) P.rc = a3r_gather_add_rows(a, ma, b, mb, x, S ? S : 2 * g.B, g.N, D, P.stream);
+    // Stored priors (g.pp; with or without the switch): the branch runs on the Mq rows of the priors not found, each zero-conv's fresh rows
+    // z_i go to their entries, and the gather-add reads every slot's z_i where it lies, in an entry or among the fresh rows.
+    const PriorCall* pp = g.pp;
+    const int Mq = g.prior_rows();
+    const long zw = (long)g.N * D;                     // words of one z_i in an entry
+    // x[s] = z_i[prior of s] + b[mb[s]] (b null: + x[s]) for S row blocks; mz / sz: the priors' rows in v.pc / their sources (pp)
+    auto gather_add = [&](int i, const int32_t* mz, const int32_t* sz, const float* b, const int32_t* mb, float* x, int S) {
+        if (P.skip()) return;
+        if (pp) P.rc = gather_add_rows_src(reinterpret_cast<const float*>(pp->lay.feat) + i * zw, pp->lay.words_feat, v.pc, sz, b, mb, x, S, g.N, D, P.stream);
+        else P.rc = a3r_gather_add_rows(v.pc, mz, b, mb, x, S, g.N, D, P.stream);
     };
     // zero_convs[i] of the depth-prior tokens, added to level x in place (distinct maps without the switch: their tokens are copied
     // to all slots' rows first, so the zero-conv and its epilogue stay as they are)
     auto zero_conv_rows = [&](int i) {
-        P.linear(P.gin_from(v.pcu, pc3, Mp, D), D, m->zc_w[i], v.pc, D, Mp, D, D, P.epi(A3R_EPI_NONE, m->zc_b[i]));
+        {
+            PriorScope scope(P, pp);
+            P.linear(P.gin_from(v.pcu, pc3, Mq, D), D, m->zc_w[i], v.pc, D, Mq, D, D, P.epi(A3R_EPI_NONE, m->zc_b[i]));
+        }
+        if (pp && pp->n_store && !P.skip())
+            P.rc = frame_cache_store(nullptr, nullptr, g.B, nullptr, pp->lay, k.dd->uniq_pd, pp->ent, pp->miss, k.dd->n_pd, v.pc, i * zw, zw, P.stream);
     };
     auto add_pc = [&](int i, float* x) {
         if (pc_rows) {
             zero_conv_rows(i);
-            gather_add(v.pc, k.dd->map_pd, nullptr, nullptr, x);
+            gather_add(i, k.dd->map_pd, pp ? pp->src : nullptr, nullptr, nullptr, x, 2 * g.B);
             return;
         }
         if (g.d_pd) copy_rows(P, g, v.pcu, v.pc, k.dd->map_pd, D);
@@ -1038,8 +1097,8 @@ void decoder_stage(Plan& P, const Call& k, const Dims& g, Levels& v) {
         // is dead once it is split
         P.linear(P.gin_from(v.featu, feat3, g.Mi, E), E, m->de_w, v.dec_last, D, g.Mi, D, E, P.epi(A3R_EPI_NONE, m->de_b));
         zero_conv_rows(0);
-        if (entries) gather_add(v.pc, k.dd->ent_pd, v.dec_last, k.dd->ent_img, cur, 2 * k.dd->n_ent);
-        else gather_add(v.pc, k.dd->map_pd, v.dec_last, k.dd->map_img, cur);
+        if (entries) gather_add(0, k.dd->ent_pd, pp ? pp->src_ent : nullptr, v.dec_last, k.dd->ent_img, cur, 2 * k.dd->n_ent);
+        else gather_add(0, k.dd->map_pd, pp ? pp->src : nullptr, v.dec_last, k.dd->map_img, cur, 2 * g.B);
     } else {
         P.linear(P.gin_from(v.feat, feat3, M2, E), E, m->de_w, cur, D, M2, D, E, P.epi(A3R_EPI_NONE, m->de_b));
         add_pc(0, cur);
@@ -1051,10 +1110,13 @@ void decoder_stage(Plan& P, const Call& k, const Dims& g, Levels& v) {
         if (i == 0 && entries) decoder_block_entries(P, g, m->dec1[i], m->dec2[i], cur, nxt, t, *k.dd);
         else decoder_block_pair(P, g, m->dec1[i], m->dec2[i], cur, nxt, t);
         if (i < npc) {   // model.py:223-226
-            P.rows(Mp);
-            P.self_block(m->pc[i], v.pcu, v.pcu, Mp, D, c.dec_num_heads, g.N, g.nw, t.xn, t.qkv, t.att);
-            P.mlp(m->pc[i], m->pc[i].n2w, m->pc[i].n2b, v.pcu, Mp, D, hidden, t.xn, t.hid);
-            P.rows(M2);
+            {
+                PriorScope scope(P, pp);
+                P.rows(Mq);
+                P.self_block(m->pc[i], v.pcu, v.pcu, Mq, D, c.dec_num_heads, g.N, g.nw, t.xn, t.qkv, t.att);
+                P.mlp(m->pc[i], m->pc[i].n2w, m->pc[i].n2b, v.pcu, Mq, D, hidden, t.xn, t.hid);
+                P.rows(M2);
+            }
             add_pc(i + 1, nxt);
         }
         if (level == hook_a) v.lvl_a = nxt;
@@ -1062,6 +1124,8 @@ void decoder_stage(Plan& P, const Call& k, const Dims& g, Levels& v) {
         if (level == m->tap_level) tap_copy(P, g, v.tap_lvl, nxt);
         cur = nxt;
     }
+    // the prior branch's statistics words: kept with the entries this call filled, completed from those it read
+    if (pp && !P.skip()) P.rc = frame_cache_stats_sites(pp->lay, pp->ent, pp->miss, k.dd->n_pd, m->stats, P.prior_sites, P.stream);
     P.ln_f32(cur, m->decn_w, m->decn_b, v.dec_last, M2, D);   // model.py:231-232
 }
 
@@ -1289,12 +1353,14 @@ int run_plan(a3r_model_s* m, const Call& k, size_t* peak = nullptr) {
 // on, a batch beyond DEDUP_MAX_SLOTS, nothing to merge, or a slot that differs from its representative: a key collision).
 namespace {
 constexpr int DD_HALF = DEDUP_MAX_SLOTS / 2;                       // slots of one kind at most
-// pinned host words: rep + flag + the frame cache's answer for the 2 B image slots (B <= FC_MAX_PAIRS) | the DD_LISTS lists
-constexpr size_t DD_HOST_LIST = (DEDUP_REP_INTS + 2 * FC_MAX_PAIRS + 63) / 64 * 64;
+// pinned host words: rep + flag + the frame cache's answer for the 2 B image slots (B <= FC_MAX_PAIRS) + the prior storage's for
+// the 2 B pred_depth slots | the DD_LISTS lists
+constexpr size_t DD_HOST_LIST = (DEDUP_REP_INTS + 4 * FC_MAX_PAIRS + 63) / 64 * 64;
 constexpr size_t DD_REP_OFF = DEDUP_KEY_BYTES;                     // device bytes: keys | rep + flag + answer | the DD_LISTS lists
 constexpr size_t DD_LIST_OFF = DD_REP_OFF + DD_HOST_LIST * 4;
-// uniq_img, map_img, uniq_pd, map_pd, uniq_side [2][B], map_side [2][B], ent_img, ent_pd, map_eo, map_ekv; frame cache: uniq_miss, ent, miss
-constexpr int DD_LISTS = 13;
+// uniq_img, map_img, uniq_pd, map_pd, uniq_side [2][B], map_side [2][B], ent_img, ent_pd, map_eo, map_ekv; frame cache: uniq_miss, ent, miss;
+// stored priors: uniq_miss, ent, miss, src, src_ent
+constexpr int DD_LISTS = 18;
 constexpr size_t DD_DEV_BYTES = DD_LIST_OFF + (size_t)DD_LISTS * DD_HALF * 4;
 static_assert(FC_STAT_WORDS == a3r_model_s::MAX_SITES, "an entry stores one word per site");
 
@@ -1303,16 +1369,30 @@ FrameCacheLayout frame_cache_at(a3r_model_s* m, int H, int W) {
     const FrameCacheLayout lay = frame_cache_layout(m->fc_buf, m->fc_bytes, 3L * H * W, (long)(H / 16) * (W / 16) * m->cfg.enc_embed_dim);
     if (H != m->fc_H || W != m->fc_W || lay.cap != m->fc_table.cap) {
         m->fc_table.reset(lay.cap);
+        m->pd_table.reset(0);
         m->fc_H = H;
         m->fc_W = W;
     }
     return lay;
 }
+// Words of an entry of the products storage at this resolution: the pred_depth map, and the rows z_0 .. z_n of the zero-convs
+long prior_words_map(int H, int W) { return 3L * H * W; }
+long prior_words_rows(const a3r_model_config& c, int H, int W) { return (long)(n_pc_blocks(c) + 1) * (H / 16) * (W / 16) * c.dec_embed_dim; }
+// The products storage as `cap` entries (the frame cache's count, after frame_cache_at) of this resolution; cap 0 in the answer:
+// it has no room for that many and is not used
+FrameCacheLayout prior_store_at(a3r_model_s* m, int H, int W, int cap) {
+    const long wm = prior_words_map(H, W), wr = prior_words_rows(m->cfg, H, W);
+    const size_t need = (size_t)cap * frame_cache_entry_bytes(wm, wr);
+    const FrameCacheLayout lay = frame_cache_layout(m->fp_buf && m->fp_bytes >= need ? m->fp_buf : nullptr, need, wm, wr);
+    if (lay.cap != m->pd_table.cap) m->pd_table.reset(lay.cap);
+    return lay;
+}
 
 int find_distinct(a3r_model_s* m, const float* a1, const float* a2, long words_a, bool encode, const float* pd1, const float* pd2, int B,
-                  int H, int W, void* stream, Distinct* d, bool* use, CacheCall* cc = nullptr) {
+                  int H, int W, void* stream, Distinct* d, bool* use, CacheCall* cc = nullptr, PriorCall* pc = nullptr) {
     *use = false;
     m->last_fc[0] = m->last_fc[1] = m->last_fc[2] = 0;
+    m->last_pd[0] = m->last_pd[1] = m->last_pd[2] = 0;
     m->last_img_unique = m->last_pd_unique = 2 * B;
     m->last_fell_back = 0;
     m->last_side_unique[0] = m->last_side_unique[1] = B;
@@ -1338,7 +1418,19 @@ int find_distinct(a3r_model_s* m, const float* a1, const float* a2, long words_a
                       m->fc_bytes, H, W, frame_cache_entry_bytes(cc->lay.words_img, cc->lay.words_feat));
         if (int rc = frame_cache_lookup(a1, a2, B, dev, rep_dev, cc->lay, m->fc_table.mask(), rep_dev + 2 * S + 1, stream)) return rc;
     }
-    A3R_HIP(hipMemcpyAsync(m->dd_host, rep_dev, (size_t)(2 * S + 1 + (cached ? S : 0)) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    // priors kept across calls: the same lookup on the pred_depth slots (keys and representatives of the second kind), its answer
+    // behind the images'.  They ride on the frame cache (as many entries, dropped and bypassed with it) and feed the decoder's
+    // gather-add form, whatever a3r_model_set_dedup_decoder says: a handle with that switch off reads the same stored words.
+    bool stored_pd = cached && pc && m->fp_buf && m->gemm_form == Form::FH2;
+    if (stored_pd) {
+        pc->lay = prior_store_at(m, H, W, cc->lay.cap);
+        pc->keys = dev + (size_t)S * 16;
+        stored_pd = pc->lay.cap > 0;
+        if (stored_pd)
+            if (int rc = frame_cache_lookup(pd1, pd2, B, pc->keys, rep_dev + S, pc->lay, m->pd_table.mask(), rep_dev + 3 * S + 1, stream)) return rc;
+    }
+    A3R_HIP(hipMemcpyAsync(m->dd_host, rep_dev, (size_t)(2 * S + 1 + (cached ? S : 0) + (stored_pd ? S : 0)) * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, st));
     A3R_HIP(hipStreamSynchronize(st));
     const int32_t* rep = m->dd_host;
     if (rep[2 * S] != 0) {
@@ -1421,13 +1513,39 @@ int find_distinct(a3r_model_s* m, const float* a1, const float* a2, long words_a
             cc->miss = list_dev + 12 * DD_HALF;
         }
     }
-    if (!cached && n_img == S && n_pd == S && n_side[0] == B && n_side[1] == B) return A3R_OK;
+    // The stored priors: hits, misses and victims among the distinct pred_depth maps, and the lists of the prior branch
+    if (stored_pd) {
+        const int32_t *uniq = list + 2 * DD_HALF, *map_pd = list + 3 * DD_HALF, *answer = rep + 3 * S + 1;
+        int32_t *uniq_miss = list + 13 * DD_HALF, *ent = list + 14 * DD_HALF, *miss = list + 15 * DD_HALF, *src = list + 16 * DD_HALF,
+                *src_ent = list + 17 * DD_HALF;
+        std::vector<int32_t> hit(n_pd);
+        for (int k = 0; k < n_pd; k++) hit[k] = answer[uniq[k]];
+        stored_pd = m->pd_table.assign(hit.data(), n_pd, ent, m->last_pd) == 0;
+        if (stored_pd) {
+            int n_store = 0;
+            pc->n_miss = prior_lists(hit.data(), ent, uniq, n_pd, miss, uniq_miss, map_pd, S, src, &n_store);
+            if (pc->n_miss < 0) {               // (never: map_pd is dedup_group's)
+                m->drop_stored();
+                m->last_fell_back = 1;
+                return A3R_OK;
+            }
+            for (int i = 0; i < 2 * n_ent; i++) src_ent[i] = src[uniq[list[7 * DD_HALF + i]]];      // ent_pd names distinct priors
+            pc->n_store = n_store;
+            pc->uniq_miss = list_dev + 13 * DD_HALF;
+            pc->ent = list_dev + 14 * DD_HALF;
+            pc->miss = list_dev + 15 * DD_HALF;
+            pc->src = list_dev + 16 * DD_HALF;
+            pc->src_ent = list_dev + 17 * DD_HALF;
+        }
+    }
+    if (!cached && !stored_pd && n_img == S && n_pd == S && n_side[0] == B && n_side[1] == B) return A3R_OK;
     m->last_side_merged[0] = n_side[0] < B;
     m->last_side_merged[1] = n_side[1] < B;
     A3R_HIP(hipMemcpyAsync(list_dev, list, (size_t)DD_LISTS * DD_HALF * sizeof(int32_t), hipMemcpyHostToDevice, st));
     *d = {n_img, n_pd, list_dev, list_dev + DD_HALF, list_dev + 2 * DD_HALF, list_dev + 3 * DD_HALF,
           {n_side[0], n_side[1]}, {list_dev + 4 * DD_HALF, list_dev + 4 * DD_HALF + B}, {list_dev + 5 * DD_HALF, list_dev + 5 * DD_HALF + B},
-          n_ent, list_dev + 6 * DD_HALF, list_dev + 7 * DD_HALF, list_dev + 8 * DD_HALF, list_dev + 9 * DD_HALF, cached ? cc : nullptr};
+          n_ent, list_dev + 6 * DD_HALF, list_dev + 7 * DD_HALF, list_dev + 8 * DD_HALF, list_dev + 9 * DD_HALF, cached ? cc : nullptr,
+          stored_pd ? pc : nullptr};
     *use = true;
     return A3R_OK;
 }
@@ -1485,7 +1603,8 @@ extern "C" int a3r_model_forward(a3r_model_t m, const float* img1, const float* 
     Distinct d;
     bool merge = false;
     CacheCall cc;
-    int rc = find_distinct(m, img1, img2, 3L * H * W, true, pd1, pd2, B, H, W, stream, &d, &merge, &cc);
+    PriorCall pc;
+    int rc = find_distinct(m, img1, img2, 3L * H * W, true, pd1, pd2, B, H, W, stream, &d, &merge, &cc, &pc);
     Call k;
     k.phase = 0; k.B = B; k.H = H; k.W = W;
     k.img[0] = img1; k.img[1] = img2; k.pd[0] = pd1; k.pd[1] = pd2;
@@ -1493,7 +1612,7 @@ extern "C" int a3r_model_forward(a3r_model_t m, const float* img1, const float* 
     k.ws = workspace; k.ws_bytes = workspace_bytes; k.stream = stream;
     k.dd = merge ? &d : nullptr;
     if (!rc) rc = run_plan(m, k);
-    if (rc) m->fc_table.flush();          // entries this call was to fill may not have been written
+    if (rc) m->drop_stored();          // entries this call was to fill may not have been written
     return rc;
 }
 
@@ -1539,7 +1658,7 @@ extern "C" int a3r_model_decode(a3r_model_t m, const float* feat1, const float* 
 }
 extern "C" int a3r_model_set_dedup(a3r_model_t m, int mode) {
     A3R_CHECK_ARG(m && mode >= 0 && mode <= 2, "a3r_model_set_dedup: mode must be 0 (off), 1 (on) or 2 (constant key)");
-    if (mode != m->dedup_mode) m->fc_table.flush();      // (stored keys are those of the mode they were made in)
+    if (mode != m->dedup_mode) m->drop_stored();      // (stored keys are those of the mode they were made in)
     m->dedup_mode = mode;
     return A3R_OK;
 }
@@ -1552,6 +1671,7 @@ extern "C" size_t a3r_model_frame_cache_bytes(a3r_model_t m, int H, int W, int f
 extern "C" int a3r_model_set_frame_cache(a3r_model_t m, void* buf, size_t bytes) {
     A3R_CHECK_ARG(m, "a3r_model_set_frame_cache: null handle");
     m->fc_table.reset(0);
+    m->pd_table.reset(0);
     m->fc_buf = nullptr;
     m->fc_bytes = 0;
     m->fc_H = m->fc_W = 0;
@@ -1569,6 +1689,31 @@ extern "C" int a3r_model_last_frame_cache(a3r_model_t m, int* hits, int* misses,
     *hits = m->last_fc[0];
     *misses = m->last_fc[1];
     *evictions = m->last_fc[2];
+    return A3R_OK;
+}
+
+extern "C" size_t a3r_model_frame_products_bytes(a3r_model_t m, int H, int W, int frames) {
+    if (!m || H <= 0 || W <= 0 || H % 16 || W % 16 || frames <= 0 || frames > FC_MAX_ENTRIES) return 0;
+    return (size_t)frames * frame_cache_entry_bytes(prior_words_map(H, W), prior_words_rows(m->cfg, H, W));
+}
+
+extern "C" int a3r_model_set_frame_products(a3r_model_t m, void* buf, size_t bytes) {
+    A3R_CHECK_ARG(m, "a3r_model_set_frame_products: null handle");
+    m->pd_table.reset(0);
+    m->fp_buf = nullptr;
+    m->fp_bytes = 0;
+    if (!buf || !bytes) return A3R_OK;
+    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "a3r_model_set_frame_products: storage must be 256-byte aligned");
+    m->fp_buf = buf;
+    m->fp_bytes = bytes;
+    return A3R_OK;
+}
+
+extern "C" int a3r_model_last_frame_products(a3r_model_t m, int* hits, int* misses, int* evictions) {
+    A3R_CHECK_ARG(m && hits && misses && evictions, "a3r_model_last_frame_products: null argument");
+    *hits = m->last_pd[0];
+    *misses = m->last_pd[1];
+    *evictions = m->last_pd[2];
     return A3R_OK;
 }
 
@@ -1651,7 +1796,7 @@ extern "C" int a3r_model_range_check(a3r_model_t m, void* stream, int* n_adjuste
         (*n_adjusted)++;
     }
     // a call that has to be repeated stored nothing worth keeping, and stored rows do not outlive the scales they were made with
-    if (*n_adjusted || *n_nonfinite) m->fc_table.flush();
+    if (*n_adjusted || *n_nonfinite) m->drop_stored();
     return A3R_OK;
 }
 
@@ -1676,6 +1821,6 @@ extern "C" int a3r_model_range_scales(a3r_model_t m, int phase, float* scales, i
 extern "C" int a3r_model_reset_ranges(a3r_model_t m) {
     A3R_CHECK_ARG(m, "a3r_model_reset_ranges: null handle");
     for (auto& v : m->site_scale) v.clear();
-    m->fc_table.flush();
+    m->drop_stored();
     return A3R_OK;
 }

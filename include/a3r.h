@@ -374,6 +374,15 @@ int a3r_upsample2x_combine_fh2(const float* x, const float* c, const float* r0, 
  * the device; C % 4 == 0, 16-byte aligned buffers. */
 int a3r_gather_add_rows(const float* a, const int32_t* map_a, const float* b, const int32_t* map_b, float* dst, int S, int N, int C,
                         void* stream);
+/* The same with the row blocks of a in two places (stored frame products, a3r_model_set_frame_products): src[s] >= 0 is the block
+ * at store + src[s] * stride floats, src[s] < 0 the block ~src[s] of fresh [., N, C]; stride >= N C, stride % 4 == 0. */
+int a3r_gather_add_rows_src(const float* store, long stride, const float* fresh, const int32_t* src, const float* b, const int32_t* map_b,
+                            float* dst, int S, int N, int C, void* stream);
+/* (tests) the statistics pass of the storages kept across calls on the words named by site_mask (host, 32 words, bit i = word i):
+ * `storage` is laid out as by a3r_model_set_frame_cache for items of words_item and rows of words_rows words; stats[i] is stored
+ * with every entry ent[k] >= 0 that the call filled (miss[k] >= 0), then raised to the largest word of the entries it read. */
+int a3r_frame_cache_stats_sites(void* storage, size_t bytes, int64_t words_item, int64_t words_rows, const int32_t* ent,
+                                const int32_t* miss, int U, unsigned* stats, const uint32_t* site_mask, void* stream);
 /* Kernel form behind a3r_upsample2x, a3r_upsample2x_fh2 and a3r_upsample2x_combine_fh2: 2 (default: a thread makes 2 x 2 output
  * pixels from corners fetched once) or 1 (four corners fetched per output pixel); the results are bitwise equal
  * (tests/test_gpu_up2x_forms.py).  Returns the previous form, or a negative error code.  Process-wide; environment A3R_UP_FORM=v1
@@ -492,6 +501,25 @@ int a3r_model_last_dedup_entries(a3r_model_t m, int* u1, int* u2, int* merged);
 size_t a3r_model_frame_cache_bytes(a3r_model_t m, int H, int W, int frames);
 int a3r_model_set_frame_cache(a3r_model_t m, void* buf, size_t bytes);
 int a3r_model_last_frame_cache(a3r_model_t m, int* hits, int* misses, int* evictions);
+/* Frame products kept across calls: a second, optional storage beside the frame cache for what the plan makes from one pred_depth
+ * map alone -- patch_embed_point_cloud, the dec_blocks_pc blocks and the zero-convs.  Per entry it holds the map (3 H W floats), the
+ * zero-conv outputs z_0 .. z_n ((dec_depth / 2 - 1) N dec_embed_dim floats), the key and 8 KB of words: about 14 MB at 512 x 384.
+ * With it, a3r_model_forward looks every distinct pred_depth map of the call up as it does the images (key, then every bit; same
+ * read-back, same synchronise), runs the branch on the maps it did not find, stores their z rows, and the decoder's gather-add
+ * passes read every slot's z rows where they lie.  A call that finds all of its maps launches nothing of the branch.  Outputs are
+ * bitwise those of a handle without storage; sites, scales and the workspace requirement do not change; the branch's statistics
+ * words follow the frame cache's rule.
+ * The storage is used only while a frame cache is installed and it has room for as many entries as that has at the call's
+ * resolution (a3r_model_frame_products_bytes(m, H, W, frames) with the same `frames`); a smaller one is ignored.  It has a table
+ * and a least-recently-used order of its own, is dropped and bypassed exactly where the frame cache is, and is not used outside
+ * the default fh2 arithmetic.  a3r_model_set_dedup_decoder does not concern it: stored maps take the zero-convs' gather-add form
+ * in either setting, so that both settings read the same stored words.  buf: device memory, 256-byte aligned, the caller's; NULL
+ * or bytes == 0 removes it.
+ * a3r_model_last_frame_products: distinct pred_depth maps of the last forward found / not found, and entries replaced (all 0 when
+ * the call did not use the storage). */
+size_t a3r_model_frame_products_bytes(a3r_model_t m, int H, int W, int frames);
+int a3r_model_set_frame_products(a3r_model_t m, void* buf, size_t bytes);
+int a3r_model_last_frame_products(a3r_model_t m, int* hits, int* misses, int* evictions);
 /* Debug taps for the parity tests: intermediate tensors inside the workspace after a forward; returns device pointer + element
  * count.  name: "feat" (enc_norm output, model.py:163), "hook_a" / "hook_b" (the decoder levels the DPT head reads,
  * dpt_head.py:101), "dec_last" (dec_norm output, model.py:231-232); after a3r_model_set_tap_level(m, L > 0) also "level" (the two
