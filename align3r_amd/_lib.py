@@ -95,7 +95,11 @@ class PrepDesc(C.Structure):
                 ("idx_y_host", c_void), ("w_y", c_void)]
 
 
-DEPTH_ALIGN_MODES = {"lad": 0, "lstsq": 1, "scale": 2, "median": 3}      # A3R_DEPTH_ALIGN_* of include/a3r.h
+class RenderCam(C.Structure):
+    _fields_ = [("w2c", C.c_double * 12), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
+DEPTH_ALIGN_MODES ={"lad": 0, "lstsq": 1, "scale": 2, "median": 3}      # A3R_DEPTH_ALIGN_* of include/a3r.h
 DEPTH_INFO_DOUBLES, DEPTH_METRIC_DOUBLES = 16, 8
 
 EPI_NONE, EPI_GELU, EPI_RESID, EPI_RELU, EPI_ROPE, EPI_RESID2, EPI_PIXSHUF, EPI_HEAD = range(8)
@@ -262,6 +266,10 @@ SIGNATURES = {
     "a3r_match_workspace_bytes": (C.c_size_t, [C.c_longlong, C.c_longlong, C.c_int]),
     "a3r_reciprocal_matches": (C.c_int, [c_void, C.c_longlong, c_void, C.c_longlong, C.c_int, c_void, C.c_size_t, c_void, c_void, c_void,
                                          C.c_longlong, c_void, C.POINTER(C.c_longlong), c_void]),
+    "a3r_render_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "a3r_render_points": (C.c_int, [c_void, c_void, C.c_longlong, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, c_void,
+                                    c_void, C.c_size_t, c_void, c_void, c_void, c_void]),
+    "a3r_render_set_form": (C.c_int, [C.c_int]),
 }
 
 _lib = None

@@ -437,6 +437,70 @@ class PointCloudOptimizer:
         write_ply(path, pc['xyz'].cpu().numpy(), pc['rgb'].cpu().numpy() if 'rgb' in pc else None)
         return pc
 
+    # ------------------------------------------------------------------ pictures (stands in for the reference's scene.show())
+    def render(self, cam2world, K, shape, min_conf_thr=None, mask_dynamic=False, radius=0, background=(255, 255, 255), with_index=False):
+        """The aligned scene seen from any cameras: the points and colours of get_pointcloud(min_conf_thr, mask_dynamic), drawn as
+        z-buffered square splats of (2 radius + 1)^2 pixels (ops.render_points, csrc/render.hip).  cam2world [C,3 or 4,4] camera
+        poses and K [C,3,3] intrinsics (numpy or torch, any float type; the poses are inverted by tool/render.py: world_to_camera),
+        shape = (H, W).  Dict of device tensors: depth [C,H,W] float32 (0 = empty), rgb [C,H,W,3] uint8 (when the scene holds its
+        frames) and, with_index, index [C,H,W] int32 = the winner's row of get_pointcloud()'s arrays (-1 = empty)."""
+        pc = self.get_pointcloud(min_conf_thr=min_conf_thr, mask_dynamic=mask_dynamic)
+        return self.render_cloud(pc, cam2world, K, shape, radius=radius, background=background, with_index=with_index)
+
+    def render_cloud(self, pc, cam2world, K, shape, radius=0, background=(255, 255, 255), with_index=False):
+        """render() on a cloud already exported with get_pointcloud(): a caller that renders many times exports once."""
+        from ... import ops
+        from ...tool.render import world_to_camera
+        host = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        return ops.render_points(pc['xyz'], pc.get('rgb'), w2c=world_to_camera(cam2world), K=host(K).astype(np.float64), shape=shape,
+                                 radius=radius, background=background, want_index=with_index)
+
+    def render_views(self, idx=None, min_conf_thr=None, mask_dynamic=False, radius=0, background=(255, 255, 255), with_index=False,
+                     points_of=None):
+        """The scene seen from its own cameras (get_im_poses, get_focals, get_principal_points), each at its image's own shape:
+        a list, in the order of idx (None = every image), of dicts depth [h,w], rgb [h,w,3] and, with_index, index [h,w] as
+        render() returns them.  Cameras of equal shape go into one call.  points_of = image numbers: only the kept points of those
+        images are drawn (None = the whole scene), and index counts rows of that selection -- with points_of=[i] and radius 0, view
+        i shows at every kept pixel of image i that pixel's own rank among them."""
+        idx = list(range(self.n_imgs)) if idx is None else [int(i) for i in (idx if np.iterable(idx) else [idx])]
+        for i in idx:
+            if not 0 <= i < self.n_imgs:
+                raise IndexError(f'render_views: image {i} is outside the scene of {self.n_imgs} images')
+        pc = self.get_pointcloud(min_conf_thr=min_conf_thr, mask_dynamic=mask_dynamic, with_index=points_of is not None)
+        if points_of is not None:
+            own = torch.zeros(self.n_imgs, dtype=torch.bool, device=pc['index'].device)
+            own[[int(n) for n in (points_of if np.iterable(points_of) else [points_of])]] = True
+            rows = own[torch.div(pc['index'], self.max_area, rounding_mode='floor').long()]
+            pc = {k: v[rows].contiguous() for k, v in pc.items()}
+        poses = self.get_im_poses().detach().cpu().numpy().astype(np.float64)
+        f = self.get_focals().detach().cpu().numpy().astype(np.float64).reshape(-1)
+        pp = self.get_principal_points().detach().cpu().numpy().astype(np.float64)
+        K = np.zeros((self.n_imgs, 3, 3))
+        K[:, 0, 0] = K[:, 1, 1] = f
+        K[:, :2, 2] = pp
+        K[:, 2, 2] = 1
+        out = [None] * len(idx)
+        for shape in sorted({tuple(self.imshapes[i]) for i in idx}):
+            slots = [s for s, i in enumerate(idx) if tuple(self.imshapes[i]) == shape]
+            sel = [idx[s] for s in slots]
+            r = self.render_cloud(pc, poses[sel], K[sel], shape, radius=radius, background=background, with_index=with_index)
+            for c, s in enumerate(slots):
+                out[s] = {k: v[c] for k, v in r.items()}
+        return out
+
+    def save_renders(self, dir, idx=None, **kw):
+        """render_views(idx, **kw) written as dir/render_XXXX.png (XXXX = the image number; tool/render.py: write_png); returns the
+        list of render_views.  A scene without frames has no colours: its pictures are the coverage, 255 where a point landed and 0
+        elsewhere."""
+        from ...tool.render import write_png
+        os.makedirs(dir, exist_ok=True)
+        idx = list(range(self.n_imgs)) if idx is None else [int(i) for i in (idx if np.iterable(idx) else [idx])]
+        views = self.render_views(idx, **kw)
+        for i, v in zip(idx, views):
+            pic = v['rgb'] if 'rgb' in v else (v['depth'] > 0).to(torch.uint8) * 255
+            write_png(os.path.join(dir, f'render_{i:04d}.png'), pic)
+        return views
+
     def get_matches(self, i, j, min_conf_thr=None, mask_dynamic=False):
         """Dense pixel correspondences between images i and j: the reciprocal 3-D nearest neighbours (find_reciprocal_matches of
         dust3r/utils/geometry.py, computed by csrc/match.hip) between the kept points of the two images -- the rows that

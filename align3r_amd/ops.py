@@ -715,3 +715,82 @@ def reciprocal_matches(p1, p2, chunks=0):
                                          ptr(pairs), C.byref(count), stream_ptr()), "reciprocal_matches")
     M = int(count.value)
     return dict(nn2_in_P1=nn2, nn1_in_P2=nn1, reciprocal_in_P2=rec.view(torch.bool), pairs=pairs[:M], count=M)
+
+
+def render_set_form(form: int) -> int:
+    """The splat's form (a3r_render_set_form; bit 0: a grid axis over the cameras, bit 1: no read before the atomic, bit 2: the reads
+    one pixel at a time): a developer's A/B switch that does not change the pictures.  Returns the previous value; -1 only queries."""
+    return int(_lib.load().a3r_render_set_form(int(form)))
+
+
+def _host_f64(a, name):
+    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    if a.dtype != np.float64:
+        raise ValueError(f"render_points: {name} must be float64, got {a.dtype}")
+    return a
+
+
+def render_cameras(w2c, K):
+    """The camera table of render_points, [C,16] float64 (a3r_render_cam: [R|t] row-major, fx, fy, cx, cy), from w2c [C,3,4] or
+    [C,4,4] and K [C,3,3], both float64 (numpy or torch).  A non-zero skew is a ValueError."""
+    w2c, K = _host_f64(w2c, "w2c"), _host_f64(K, "K")
+    if w2c.ndim != 3 or w2c.shape[1] not in (3, 4) or w2c.shape[2] != 4:
+        raise ValueError(f"render_points: w2c is [C,3,4] or [C,4,4], got {w2c.shape}")
+    C_ = w2c.shape[0]
+    if K.shape != (C_, 3, 3):
+        raise ValueError(f"render_points: K is [C,3,3] with C = {C_}, got {K.shape}")
+    if np.any(K[:, 0, 1] != 0):
+        raise ValueError("render_points: K has a non-zero skew K[0,1]; the renderer's cameras are fx, fy, cx, cy")
+    cams = np.empty((C_, 16), np.float64)
+    cams[:, :12] = w2c[:, :3, :].reshape(C_, 12)
+    cams[:, 12], cams[:, 13], cams[:, 14], cams[:, 15] = K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]
+    return cams
+
+
+def render_points(xyz, rgb=None, w2c=None, K=None, shape=None, radius=0, near=1e-6, background=(255, 255, 255), want_index=False,
+                  cams=None):
+    """A point cloud drawn into the pictures of C pinhole cameras as z-buffered square splats (a3r_render_points, csrc/render.hip;
+    include/a3r.h has the definition: float64 projection, half-to-even pixel, the nearest point wins a pixel and the lowest index an
+    exact depth tie -- bitwise reproducible).  xyz [M,3]: contiguous float32 device tensor; rgb [M,3]: contiguous uint8 device
+    tensor or None.  w2c [C,3,4] or [C,4,4] and K [C,3,3]: float64 world-to-camera transforms and intrinsics (tool/render.py:
+    world_to_camera inverts poses), or cams = the table render_cameras() made of them.  shape = (H, W); radius in [0, 8]: the
+    splat covers (2 radius + 1)^2 pixels; near: the smallest camera depth that draws.  Enqueue-only; returns a dict of device
+    tensors: depth [C,H,W] float32 (0 where nothing landed), rgb [C,H,W,3] uint8 (with rgb; `background` where nothing landed) and,
+    with want_index, index [C,H,W] int32 (the winner's row of xyz, -1 where nothing landed)."""
+    _req_points(xyz, "xyz")
+    if rgb is not None and not (isinstance(rgb, torch.Tensor) and rgb.device == xyz.device and rgb.dtype == torch.uint8 and rgb.is_contiguous()
+                                and rgb.shape == xyz.shape):
+        raise RuntimeError("render_points: rgb must be a contiguous uint8 tensor [M,3] on xyz's device")
+    if cams is None:
+        if w2c is None or K is None:
+            raise ValueError("render_points: w2c and K (or cams) are needed")
+        cams = render_cameras(w2c, K)
+    cams = np.ascontiguousarray(cams, dtype=np.float64)
+    if cams.ndim != 2 or cams.shape[1] != 16:
+        raise ValueError(f"render_points: cams is [C,16], got {cams.shape}")
+    if shape is None or len(shape) != 2:
+        raise ValueError("render_points: shape = (H, W) is needed")
+    H, W = int(shape[0]), int(shape[1])
+    bg = np.asarray(background)
+    if bg.shape != (3,) or np.any(bg != bg.astype(np.uint8)):
+        raise ValueError(f"render_points: background is three values in [0, 255], got {background!r}")
+    bg = np.ascontiguousarray(bg, dtype=np.uint8)
+    assert C.sizeof(_lib.RenderCam) == 128 == cams.strides[0]
+    lib, dev, n_cams, M = _lib.load(), xyz.device, cams.shape[0], xyz.shape[0]
+    ws_bytes = int(lib.a3r_render_workspace_bytes(n_cams, H, W))            # 0 for sizes the call below refuses
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    out_shape = (n_cams, H, W) if ws_bytes else (0, 0, 0)
+    depth = torch.empty(out_shape, dtype=torch.float32, device=dev)
+    out_rgb = torch.empty(out_shape + (3,), dtype=torch.uint8, device=dev) if rgb is not None else None
+    index = torch.empty(out_shape, dtype=torch.int32, device=dev) if want_index else None
+    cams_dev = torch.from_numpy(cams.reshape(-1).copy()).to(dev) if n_cams else None
+    with torch.cuda.device(dev):
+        check(lib.a3r_render_points(ptr(xyz), ptr(rgb), M, ptr(cams_dev), cams.ctypes.data if n_cams else None, n_cams, H, W, int(radius),
+                                    float(near), bg.ctypes.data, ptr(ws), ws_bytes, ptr(depth), ptr(out_rgb), ptr(index), stream_ptr()),
+              "render_points")
+    out = dict(depth=depth)              # the camera table and the workspace are freed stream-ordered after the kernels
+    if out_rgb is not None:
+        out["rgb"] = out_rgb
+    if index is not None:
+        out["index"] = index
+    return out

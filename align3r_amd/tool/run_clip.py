@@ -6,10 +6,11 @@ The flow of the reference's tool/demo.py and tool/depth_test.py through this pac
     ->  pred_traj.txt, pred_intrinsics.txt, frame_XXXX.npy, conf_X.npy   (+ depth metrics when ground truth is given)
     ->  --pointcloud PATH: the aligned scene as a binary PLY (points above --min-conf-thr, compacted on the device)
     ->  --matches DIR: matches_{i}_{i+1}.npz, the reciprocal 3-D nearest-neighbour pixel correspondences of consecutive frames
+    ->  --render DIR: render_XXXX.png, the whole aligned scene drawn from every frame's own camera (z-buffered point splats)
 
     python -m align3r_amd.tool.run_clip --images DIR --weights CKPT.pth --out OUT [--size 512] [--scene-graph swin-3-noncyclic]
            [--hierarchical --clip-size 50] [--niter 300] [--schedule linear] [--lr 0.01] [--traj-format custom] [--gt-depth DIR]
-           [--metrics-device] [--pointcloud scene.ply] [--matches DIR] [--clean] [--device-prep]
+           [--metrics-device] [--pointcloud scene.ply] [--matches DIR] [--render DIR [--render-radius R]] [--clean] [--device-prep]
            [--flow [--flow-weights RAFT.pth] [--gt-masks DIR] [--not-shared-focal]]
            [--flow-hierarchical [--clip-size 10] [--device-resident] [--flow-weights ...] [--gt-masks DIR] [--not-shared-focal]]
 
@@ -68,6 +69,14 @@ def parse(argv=None):
                          "csrc/match.hip; keys idx_i idx_j xy_i xy_j xyz_i xyz_j count); with --flow the dynamic pixels are masked out. "
                          "Refused with --hierarchical and --flow-hierarchical: their clips are aligned one after another and no "
                          "scene holds two neighbouring clips' frames at once")
+    ap.add_argument("--render", default=None, metavar="DIR",
+                    help="after the alignment (and after --clean) write DIR/render_XXXX.png for every frame: the whole aligned scene -- "
+                         "the points above --min-conf-thr -- drawn from that frame's own camera at the frame's own size as z-buffered "
+                         "point splats (scene.save_renders, csrc/render.hip); with --flow the dynamic pixels are masked out. "
+                         "Refused with --hierarchical and --flow-hierarchical: their clips are aligned one after another and no "
+                         "scene holds all frames at once")
+    ap.add_argument("--render-radius", type=int, default=None, metavar="R",
+                    help="--render: a point covers (2 R + 1)^2 pixels, R in [0, 8] (default 1)")
     ap.add_argument("--clean", action="store_true",
                     help="scene.clean_pointcloud() after every alignment: confidences of points another, more confident view sees through "
                          "drop to 0 before conf_X.npy and --pointcloud are written (tool/demo.py: clean_depth)")
@@ -95,6 +104,14 @@ def parse(argv=None):
         ap.error("--flow-hierarchical stands alone: it implies the --flow settings and is its own keyframe / clip driver")
     if a.matches and (a.hierarchical or a.flow_hierarchical):
         ap.error("--matches cannot be combined with --hierarchical or --flow-hierarchical: it needs one scene holding all frames")
+    if a.render and (a.hierarchical or a.flow_hierarchical):
+        ap.error("--render cannot be combined with --hierarchical or --flow-hierarchical: it needs one scene holding all frames")
+    if a.render_radius is not None and not a.render:
+        ap.error("--render-radius belongs to --render")
+    if a.render_radius is None:
+        a.render_radius = 1
+    if not 0 <= a.render_radius <= 8:
+        ap.error("--render-radius is in [0, 8]")
     if a.device_resident and not a.flow_hierarchical:
         ap.error("--device-resident belongs to --flow-hierarchical")
     if a.metrics_device and not a.gt_depth:
@@ -146,6 +163,7 @@ def main(argv=None):
     clouds, n_points = ([] if a.pointcloud else None), None
     meshes, n_mesh = ([] if a.mesh else None), None              # n_mesh: (vertices, faces) written
     n_matches = None                   # --matches: matches written per consecutive pair
+    n_renders = None                   # --render: pictures written
     depths_dev = None                  # --metrics-device: the aligned depth maps as the scene holds them, on the device
     if a.flow_hierarchical and len(imgs) < 3:
         raise RuntimeError("--flow-hierarchical needs at least 3 frames")
@@ -209,6 +227,10 @@ def main(argv=None):
             if mode != GlobalAlignerMode.PointCloudOptimizer:
                 raise RuntimeError("--matches needs at least 3 frames (the two-frame PairViewer has no aligner handle to export from)")
             n_matches = write_matches(scene, a.matches, mask_dynamic=a.flow)
+        if a.render:
+            if mode != GlobalAlignerMode.PointCloudOptimizer:
+                raise RuntimeError("--render needs at least 3 frames (the two-frame PairViewer has no aligner handle to export from)")
+            n_renders = len(scene.save_renders(a.render, mask_dynamic=a.flow, radius=a.render_radius))
         if a.mesh:
             if mode != GlobalAlignerMode.PointCloudOptimizer:
                 raise RuntimeError("--mesh needs at least 3 frames (the two-frame PairViewer has no aligner handle to export from)")
@@ -240,6 +262,8 @@ def main(argv=None):
         res_out["pointcloud"], res_out["n_points"] = a.pointcloud, n_points
     if a.matches:
         res_out["matches"], res_out["n_matches"] = a.matches, n_matches
+    if a.render:
+        res_out["render"], res_out["n_renders"] = a.render, n_renders
     if a.mesh:
         res_out["mesh"], res_out["n_vertices"], res_out["n_faces"] = a.mesh, n_mesh[0], n_mesh[1]
     return res_out

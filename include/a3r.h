@@ -994,6 +994,48 @@ int a3r_reciprocal_matches(const float* p1, long long n1, const float* p2, long 
                            size_t workspace_bytes, int* nn2_in_p1, int* nn1_in_p2, unsigned char* reciprocal_in_p2, long long capacity,
                            int* out_pairs, long long* n_matches_host, void* stream);
 
+/* Rendering (csrc/render.hip): a point cloud drawn into the pictures of n_cams pinhole cameras as z-buffered square splats -- what
+ * stands in for the reference's interactive scene.show() (dust3r/cloud_opt/base_opt.py) on a machine without a display, and the
+ * primitive of occlusion-aware reprojection checks.  The reference has no renderer; this text is the specification.
+ * A camera holds a world-to-camera transform [R|t] (w2c: 12 doubles, row-major 3x4) and fx, fy, cx, cy (doubles, no skew).  The other
+ * inputs are the image size H x W, an integer radius in [0, 8] and near_z, finite and > 0.  For camera c and point m with fp32
+ * coordinates (x, y, z), on float64 copies of the coordinates, every operation rounded on its own (no fused multiply-add):
+ *     xc = (R00 * x + R01 * y) + R02 * z + t0          (yc from row 1, zc from row 2 likewise)
+ *     u = fx * (xc / zc) + cx,   v = fy * (yc / zc) + cy,   zf = (float)zc
+ *     drawn  iff  zc >= near_z, zf is finite, u and v are finite, |u| < 2^30 and |v| < 2^30
+ *                 (a NaN or infinite coordinate and a point behind the camera never draw)
+ *     col = (int)rint(u), row = (int)rint(v), half to even (as a3r_align_scene_clean rounds)
+ *     footprint = every pixel (row + dy, col + dx) with |dx|, |dy| <= radius that lies inside the image
+ *     every pixel of the footprint takes the 64-bit key  (bits(zf) << 32) | m
+ * A pixel's result is the MINIMUM key over all points: the nearest point and, at equal zf, the lowest point index (zf > 0, so the
+ * bits of zf order as zf does).  Outputs:
+ *     depth [n_cams,H,W] fp32 = zf of the winner, 0 where nothing landed
+ *     index [n_cams,H,W] int32 (or NULL) = the winner's m, -1 where nothing landed
+ *     out_rgb [n_cams,H,W,3] uint8 (or NULL; needs rgb [M,3]) = rgb[m] of the winner, `background` where nothing landed
+ * Contract: the minimum of integers does not depend on the order of its operands, so the pictures are bitwise reproducible from
+ * call to call although the splat runs on atomics, and they are bitwise what numpy's np.minimum.at gives on uint64 keys formed
+ * as above (tests/render_cases.py: render_ref).  Leaving out rgb / out_rgb or index changes nothing in the other outputs.
+ * Three kernels in stream order: the key planes are filled with all ones, the splat (atomic minimum on unsigned 64-bit words in
+ * global memory, one thread per point), the resolve of keys to depth / index / colour.  Nothing is allocated, synchronised or read
+ * back, so the call can be captured into a graph.  workspace: a3r_render_workspace_bytes(n_cams, H, W) bytes, 16-byte aligned (the
+ * key planes [n_cams,H,W] of 8 bytes; 0 for refused sizes).  cams_dev: the cameras in device memory; cams_host: the same table in
+ * host memory, validated before anything is launched.  `stream` is a hipStream_t, passed as void* like everywhere in this header.
+ * A3R_EINVAL before anything is launched, naming the argument: a null pointer to a non-empty array (xyz with M > 0, either camera
+ * table, depth, the workspace, background with out_rgb), M < 0 or M >= 2^31, n_cams <= 0, a non-positive H or W,
+ * n_cams * H * W >= 2^31, radius outside [0, 8], near_z not finite or <= 0, a non-finite camera entry, out_rgb without rgb (M > 0),
+ * a workspace that is too small or misaligned.  M = 0 is a success with every pixel empty.
+ * a3r_render_set_form: the splat's form, a developer's A/B switch that does not change the pictures (returns the previous value;
+ * values outside [0, 7] only query).  Bit 0: a grid axis over the cameras instead of the camera loop inside the thread.  Bit 1:
+ * every atomic is issued instead of first reading the pixel's key and skipping the atomic that cannot lower it.  Bit 2: the keys
+ * of a footprint are read one pixel at a time instead of nine at a time (no effect with bit 1 or at radius 0).  Default 0. */
+typedef struct { double w2c[12]; double fx, fy, cx, cy; } a3r_render_cam;
+size_t a3r_render_workspace_bytes(int n_cams, int H, int W);
+int a3r_render_points(const float* xyz, const unsigned char* rgb, long long M, const a3r_render_cam* cams_dev,
+                      const a3r_render_cam* cams_host, int n_cams, int H, int W, int radius, double near_z,
+                      const unsigned char background[3], void* ws, size_t ws_bytes, float* depth, unsigned char* out_rgb, int* index,
+                      void* stream);
+int a3r_render_set_form(int form);
+
 #ifdef __cplusplus
 }
 #endif
