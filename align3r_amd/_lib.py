@@ -190,6 +190,13 @@ SIGNATURES = {
     "a3r_model_frame_products_bytes": (C.c_size_t, [c_void, C.c_int, C.c_int, C.c_int]),
     "a3r_model_set_frame_products": (C.c_int, [c_void, c_void, C.c_size_t]),
     "a3r_model_last_frame_products": (C.c_int, [c_void, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "a3r_model_head_products_bytes": (C.c_size_t, [c_void, C.c_int, C.c_int, C.c_int]),
+    "a3r_model_set_head_products": (C.c_int, [c_void, c_void, C.c_size_t]),
+    "a3r_model_last_head_products": (C.c_int, [c_void, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "a3r_combine_resid_fh2_src": (C.c_int, [c_void, c_void, c_void, c_void, C.c_long, c_void, c_void, c_void, c_void, C.c_int, C.c_long,
+                                            C.c_int, C.c_float, c_void, c_void]),
+    "a3r_upsample2x_combine_fh2_src": (C.c_int, [c_void, c_void, c_void, c_void, c_void, C.c_long, c_void, c_void, c_void, C.c_int, C.c_int,
+                                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_void, c_void]),
     "a3r_gather_add_rows_src": (C.c_int, [c_void, C.c_long, c_void, c_void, c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, c_void]),
     "a3r_frame_cache_stats_sites": (C.c_int, [c_void, C.c_size_t, C.c_int64, C.c_int64, c_void, c_void, C.c_int, c_void, c_void, c_void]),
     "a3r_attention_fh2_mapped": (C.c_int, [c_void, C.c_int, c_void, C.c_int, c_void, C.c_int, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

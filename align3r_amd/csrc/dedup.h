@@ -225,9 +225,82 @@ int frame_cache_store(const float* img1, const float* img2, int B, const void* k
 // frame_cache_stats on the words of `sites`
 int frame_cache_stats_sites(const FrameCacheLayout& l, const int32_t* ent, const int32_t* miss, int U, unsigned* stats,
                             const SiteMask& sites, void* stream);
+// the same on words given directly: estats [cap][FC_STAT_WORDS] (the head products' words of one side)
+int stats_sites_words(unsigned* estats, int cap, const int32_t* ent, const int32_t* miss, int U, unsigned* stats, const SiteMask& sites,
+                      void* stream);
 // a3r_gather_add_rows whose rows a come from two places (a3r.h: a3r_gather_add_rows_src is the same with a C signature)
 int gather_add_rows_src(const float* store, long stride, const float* fresh, const int32_t* src, const float* b, const int32_t* map_b,
                         float* dst, int S, int N, int C, void* stream);
+
+// ---- head products kept across calls (a3r_model_set_head_products): what the DPT head of side s makes from one frame alone -- r0,
+// the output of layer_rn[0], and c, the bias-only output of resConfUnit1's second conv, [16 N, F] fp32 each -- in a third storage
+// indexed by the FRAME CACHE's entries: no lookup of its own, the image lookup already says which entry a distinct image is.  The
+// host keeps one valid bit per (entry, side).
+struct HeadBits {
+    uint8_t b[FC_MAX_ENTRIES] = {};
+    void flush() { for (uint8_t& x : b) x = 0; }                 // with every flush or reset of the frame cache's table
+    void clear(int e) { if (e >= 0 && e < FC_MAX_ENTRIES) b[e] = 0; }      // the frame cache filled or replaced entry e
+    bool has(int e, int s) const { return e >= 0 && e < FC_MAX_ENTRIES && ((b[e] >> s) & 1); }
+    void set(int e, int s) { if (e >= 0 && e < FC_MAX_ENTRIES) b[e] |= (uint8_t)(1u << s); }
+    int count() const { int n = 0; for (uint8_t x : b) n += (x & 1) + ((x >> 1) & 1); return n; }
+};
+// The storage as `cap` entries: the statistics words [2][cap][FC_STAT_WORDS] (side-major: one side's are an array [cap][FC_STAT_WORDS], as a frame
+// cache's are), then the rows [cap][2 sides][r0, c][words] (words = 16 N F, a multiple of 64).
+inline size_t head_products_entry_bytes(long words) { return (size_t)2 * FC_STAT_WORDS * 4 + (size_t)4 * words * 4; }
+struct HeadStore {
+    int cap; long words;
+    char *stats, *rows;
+    long stride() const { return 4 * words; }                  // floats from one entry's block to the next entry's
+    const float* r0(int s) const { return reinterpret_cast<const float*>(rows) + (size_t)(2 * s) * words; }
+    const float* c(int s) const { return reinterpret_cast<const float*>(rows) + (size_t)(2 * s + 1) * words; }
+    unsigned* side_words(int s) const { return reinterpret_cast<unsigned*>(stats) + (size_t)s * cap * FC_STAT_WORDS; }      // [cap][FC_STAT_WORDS]
+};
+inline HeadStore head_store_layout(void* base, int cap, long words) {
+    char* p = static_cast<char*>(base);
+    return {base ? cap : 0, words, p, p + (size_t)cap * 2 * FC_STAT_WORDS * 4};
+}
+// The lists of one side of one call, after FrameCacheTable::assign and the clearing of the replaced entries' bits.  The side has U
+// distinct frames; frame k is the call's distinct image row[k] (< n_img), whose entry in the frame cache is ent[row[k]] (-1: it
+// has none) and which the lookup found there when miss[row[k]] < 0.  A frame is STORED when it was found and bit (entry, side) is
+// set.  Writes for every frame k: hent[k] = its entry or -1, hmiss[k] = -1 when stored, else its row j among the n_fresh frames the
+// branch runs on, whose slots uniq[k] go to uniq_fresh[j]; and for every slot b < B of the side (frame map[b]) the signed source
+// of its c and r0: src[b] = the entry when stored, else ~j (the j-th fresh row block of the arena).  A fresh frame with an entry is
+// stored there by the call (*n_store of them) and its bit is set; one without is computed, read from the arena and not stored.
+// Returns n_fresh, or -1 and changes nothing for an index out of range or a missing argument.
+inline int head_lists(HeadBits& bits, int s, const int32_t* ent, const int32_t* miss, int n_img, const int32_t* row, const int32_t* uniq,
+                      int U, const int32_t* map, int B, int32_t* hent, int32_t* hmiss, int32_t* uniq_fresh, int32_t* src, int* n_store) {
+    if (!ent || !miss || !row || !uniq || !map || !hent || !hmiss || !uniq_fresh || !src || !n_store || s < 0 || s > 1 || U <= 0 || B <= 0 ||
+        n_img <= 0)
+        return -1;
+    for (int k = 0; k < U; k++)
+        if (row[k] < 0 || row[k] >= n_img || ent[row[k]] < -1 || ent[row[k]] >= FC_MAX_ENTRIES) return -1;
+    for (int b = 0; b < B; b++)
+        if (map[b] < 0 || map[b] >= U) return -1;
+    int n_fresh = 0;
+    *n_store = 0;
+    for (int k = 0; k < U; k++) {
+        const int32_t e = ent[row[k]];
+        hent[k] = e;
+        if (miss[row[k]] < 0 && bits.has(e, s)) { hmiss[k] = -1; continue; }
+        uniq_fresh[n_fresh] = uniq[k];
+        hmiss[k] = n_fresh++;
+        if (e >= 0) { bits.set(e, s); (*n_store)++; }
+    }
+    for (int b = 0; b < B; b++) src[b] = hmiss[map[b]] < 0 ? hent[map[b]] : ~hmiss[map[b]];
+    return n_fresh;
+}
+// Device side: the r0 and c blocks (words floats each) of every fresh frame k < U that has an entry (hmiss[k] >= 0, hent[k] >= 0)
+// go to side s of that entry.
+int head_products_store(const HeadStore& st, int s, const int32_t* hent, const int32_t* hmiss, int U, const float* r0, const float* c,
+                        void* stream);
+// combine_resid_fh2 / upsample2x_combine_fh2 (below) whose c and r0 come from two places: src[b] >= 0 names an entry of the
+// storage, whose blocks lie `stride` floats apart from store_c / store_r0, src[b] < 0 the fresh block ~src[b] of c / r0
+// (a3r.h: a3r_combine_resid_fh2_src, a3r_upsample2x_combine_fh2_src)
+int combine_resid_fh2_src(const float* c, const float* r0, const float* store_c, const float* store_r0, long stride, const int32_t* src,
+                          const float* p2, float* s, void* sr2, int S, long P, int C, float scale, unsigned* absmax, void* stream);
+int upsample2x_combine_fh2_src(const float* x, const float* c, const float* r0, const float* store_c, const float* store_r0, long stride,
+                               const int32_t* src, float* s, void* sr2, int S, int H, int W, int C, int Hc, int Wc, float scale,
+                               unsigned* absmax, void* stream);
 
 // ---- device side (dedup.hip).  An item of the first kind is one image [3, H, W] -- or, for the decode call, one frame's encoder
 // features [N, E] --, one of the second kind a pred_depth map [H, W, 3]: words_a / words_pd 32-bit words each, multiples of 4.  Slot s < 4 B of a call is item s % B of group s / B, the groups being img1, img2, pd1, pd2; slots 0 .. 2 B - 1

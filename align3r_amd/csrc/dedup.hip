@@ -201,6 +201,21 @@ __global__ __launch_bounds__(256) void fc_store_kernel(Images im, int B, long un
     if (blockIdx.x == 0 && threadIdx.x < 2) ekeys[2 * e + threadIdx.x] = keys[2 * slot + threadIdx.x];
 }
 
+// fc_store_kernel's sibling for the head products: a fresh frame k with an entry puts its r0 block (blockIdx.z = 0) or c block (1),
+// `units` 16-byte units each, into its side of the entry; grid x over chunks, y over the side's frames
+__global__ __launch_bounds__(256) void hp_store_kernel(const uint4* __restrict__ r0, const uint4* __restrict__ c, uint4* __restrict__ side,
+                                                       long units, const int* __restrict__ hent, const int* __restrict__ hmiss) {
+    const int k = blockIdx.y, e = hent[k], j = hmiss[k];
+    if (j < 0 || e < 0) return;
+    const uint4* __restrict__ src = (blockIdx.z ? c : r0) + (long)j * units;
+    uint4* __restrict__ dst = side + ((long)e * 4 + blockIdx.z) * units;       // an entry: [2 sides][r0, c][units]
+    const long u0 = (long)blockIdx.x * UNITS_PER_BLOCK;
+    for (int i = 0; i < UNITS_PER_BLOCK / 256; i++) {
+        const long u = u0 + i * 256 + threadIdx.x;
+        if (u < units) dst[u] = src[u];
+    }
+}
+
 // one thread per statistics word: those of `sites`
 __global__ void fc_stats_sites_kernel(unsigned* __restrict__ estats, const int* __restrict__ ent, const int* __restrict__ miss, int U,
                                       unsigned* __restrict__ stats, SiteMask sites) {
@@ -283,15 +298,37 @@ int frame_cache_store(const float* img1, const float* img2, int B, const void* k
     return A3R_OK;
 }
 
-int frame_cache_stats_sites(const FrameCacheLayout& l, const int32_t* ent, const int32_t* miss, int U, unsigned* stats,
-                            const SiteMask& sites, void* stream) {
-    A3R_CHECK_ARG(fc_layout_ok(l) && l.stats && ent && miss && stats && U > 0, "frame_cache_stats: bad argument");
+int head_products_store(const HeadStore& hs, int s, const int32_t* hent, const int32_t* hmiss, int U, const float* r0, const float* c,
+                        void* stream) {
+    A3R_CHECK_ARG(hs.cap > 0 && hs.cap <= FC_MAX_ENTRIES && hs.rows && hs.words > 0 && hs.words % 4 == 0 && (s == 0 || s == 1) && U > 0 &&
+                      U <= FC_MAX_PAIRS, "head_products_store: bad shape (%d entries, side %d, U=%d)", hs.cap, s, U);
+    A3R_CHECK_ARG(hent && hmiss && r0 && c && ((reinterpret_cast<uintptr_t>(r0) | reinterpret_cast<uintptr_t>(c) |
+                                                 reinterpret_cast<uintptr_t>(hs.rows)) & 15) == 0,
+                  "head_products_store: null or misaligned pointer");
     hipStream_t st = as_stream(stream);
-    ProfScope prof(PK_ELEMENTWISE, 4.0 * FC_STAT_WORDS * (U + 2), st);
-    hipLaunchKernelGGL(fc_stats_sites_kernel, dim3(FC_STAT_WORDS / 256), dim3(256), 0, st, reinterpret_cast<unsigned*>(l.stats), ent, miss,
-                       U, stats, sites);
+    const long units = hs.words / 4;
+    ProfScope prof(PK_ELEMENTWISE, 64.0 * U * units, st);
+    const dim3 grid((unsigned)((units + UNITS_PER_BLOCK - 1) / UNITS_PER_BLOCK), (unsigned)U, 2);
+    hipLaunchKernelGGL(hp_store_kernel, grid, dim3(256), 0, st, reinterpret_cast<const uint4*>(r0), reinterpret_cast<const uint4*>(c),
+                       reinterpret_cast<uint4*>(hs.rows) + (long)(2 * s) * units, units, hent, hmiss);
     A3R_LAUNCH_CHECK();
     return A3R_OK;
+}
+
+int stats_sites_words(unsigned* estats, int cap, const int32_t* ent, const int32_t* miss, int U, unsigned* stats, const SiteMask& sites,
+                      void* stream) {
+    A3R_CHECK_ARG(estats && cap > 0 && cap <= FC_MAX_ENTRIES && ent && miss && stats && U > 0, "frame_cache_stats: bad argument");
+    hipStream_t st = as_stream(stream);
+    ProfScope prof(PK_ELEMENTWISE, 4.0 * FC_STAT_WORDS * (U + 2), st);
+    hipLaunchKernelGGL(fc_stats_sites_kernel, dim3(FC_STAT_WORDS / 256), dim3(256), 0, st, estats, ent, miss, U, stats, sites);
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+int frame_cache_stats_sites(const FrameCacheLayout& l, const int32_t* ent, const int32_t* miss, int U, unsigned* stats,
+                            const SiteMask& sites, void* stream) {
+    A3R_CHECK_ARG(fc_layout_ok(l) && l.stats, "frame_cache_stats: bad argument");
+    return stats_sites_words(reinterpret_cast<unsigned*>(l.stats), l.cap, ent, miss, U, stats, sites, stream);
 }
 
 int frame_cache_stats(const FrameCacheLayout& l, const int32_t* ent, const int32_t* miss, int U, unsigned* stats, int lo, int hi,

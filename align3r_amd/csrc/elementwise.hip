@@ -329,10 +329,25 @@ __global__ void gather_add_rows_src_kernel(const f32x4* __restrict__ store, long
 // c, r0 [U, P, C], p2, s [S, P, C] fp32, sr2 [S P, C] fh2.  A thread makes 8 channels of one pixel row (two 16-byte loads per input,
 // 32 contiguous bytes per output) and walks the rows with the grid's stride: the index divisions happen once per thread, and a
 // workgroup publishes one statistics atomic.
+//
+// SRC (dedup.h, head products: c and r0 of a frame may lie in the caller's storage): map[b] is a signed source -- e >= 0 names the
+// block of entry e, hs.stride floats apart from hs.c / hs.r0, e < 0 the fresh block ~e of c / r0.  Only the base pointers and the
+// block index of the two loads differ, uniformly per slot; the arithmetic is the same code.
+struct CombineSrc { const float *c, *r0; long stride; };
+template <bool SRC>
+__device__ __forceinline__ long combine_block(const CombineSrc& hs, int e, const float* __restrict__& c, const float* __restrict__& r0) {
+    if (!SRC) return e;
+    if (e < 0) return ~e;
+    c = hs.c + (long)e * hs.stride;
+    r0 = hs.r0 + (long)e * hs.stride;
+    return 0;
+}
+
+template <bool SRC>
 __global__ __launch_bounds__(256) void combine_resid_fh2_kernel(const float* __restrict__ c, const float* __restrict__ r0,
                                                                 const float* __restrict__ p2, const int* __restrict__ map,
                                                                 float* __restrict__ s, char* __restrict__ sr2, long rows, long P, int C8,
-                                                                float scale, unsigned* __restrict__ absmax) {
+                                                                float scale, unsigned* __restrict__ absmax, CombineSrc hs) {
     const long stride = (long)gridDim.x * 256, i0 = (long)blockIdx.x * 256 + threadIdx.x;
     const long dr = stride / C8;
     const int dk = (int)(stride - dr * C8);
@@ -341,12 +356,14 @@ __global__ __launch_bounds__(256) void combine_resid_fh2_kernel(const float* __r
     long b = row / P, pr = row - b * P;                        // slot, pixel row inside the slot
     float amax = 0.f;
     while (row < rows) {
-        const long src = (((long)map[b] * P + pr) * C8 + kg) * 2, dst = (row * C8 + kg) * 2;      // in float4
+        const float *__restrict__ cs = c, *__restrict__ rs = r0;
+        const long blk = combine_block<SRC>(hs, map[b], cs, rs);
+        const long src = ((blk * P + pr) * C8 + kg) * 2, dst = (row * C8 + kg) * 2;      // in float4
         f32x4 o[2];
 #pragma unroll
         for (int h = 0; h < 2; h++) {
-            const f32x4 v = reinterpret_cast<const f32x4*>(c)[src + h] +
-                            (reinterpret_cast<const f32x4*>(r0)[src + h] + reinterpret_cast<const f32x4*>(p2)[dst + h]);
+            const f32x4 v = reinterpret_cast<const f32x4*>(cs)[src + h] +
+                            (reinterpret_cast<const f32x4*>(rs)[src + h] + reinterpret_cast<const f32x4*>(p2)[dst + h]);
             reinterpret_cast<f32x4*>(s)[dst + h] = v;
             o[h] = f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)} * scale;
             amax = fh2_amax4(amax, o[h]);
@@ -441,10 +458,11 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const float* __restrict
 // The same combine (combine_resid_fh2_kernel) inside the producer of its per-slot residual: p2 = the bilinear 2x of x, as
 // upsample2x_kernel<0> computes it (bilerp4: the same rounding order), is neither written nor read back.  x [S, H, W, C] fp32;
 // c, r0 [U, Hc, Wc, C]; s [S, Hc, Wc, C]; sr2 its fh2 twin.  Grid and thread layout of upsample2x_kernel<2>.
+template <bool SRC>
 __global__ __launch_bounds__(256) void upsample2x_combine_kernel(const float* __restrict__ x, const float* __restrict__ c,
                                                                  const float* __restrict__ r0, const int* __restrict__ map,
                                                                  float* __restrict__ s, char* __restrict__ sr2, int B, int H, int W, int C4,
-                                                                 int Hc, int Wc, float scale, unsigned* __restrict__ absmax) {
+                                                                 int Hc, int Wc, float scale, unsigned* __restrict__ absmax, CombineSrc hs) {
     const float sh = up_scale(H), sw = up_scale(W);
     const f32x4* xv = reinterpret_cast<const f32x4*>(x);
     const unsigned CG = (unsigned)C4 / 2;                      // channel groups (of 8) per pixel
@@ -463,12 +481,14 @@ __global__ __launch_bounds__(256) void upsample2x_combine_kernel(const float* __
         const long rb = (long)b * H;
         const f32x4* q0 = xv + (rb + y0) * W * C4 + cg;
         const f32x4* q1 = xv + (rb + y1) * W * C4 + cg;
-        const long pix = (long)row * Wc + ox, src = (((long)map[b] * Hc + oy) * Wc + ox) * C4 + cg;
+        const float *__restrict__ cs = c, *__restrict__ rs = r0;
+        const long blk = combine_block<SRC>(hs, map[b], cs, rs);
+        const long pix = (long)row * Wc + ox, src = ((blk * Hc + oy) * Wc + ox) * C4 + cg;
         f32x4 o[2];
 #pragma unroll
         for (int q = 0; q < 2; q++) {
             const f32x4 p2 = bilerp4(q0[(long)x0 * C4 + q], q0[(long)x1 * C4 + q], q1[(long)x0 * C4 + q], q1[(long)x1 * C4 + q], lx0, lx1, ly0, ly1);
-            const f32x4 v = reinterpret_cast<const f32x4*>(c)[src + q] + (reinterpret_cast<const f32x4*>(r0)[src + q] + p2);
+            const f32x4 v = reinterpret_cast<const f32x4*>(cs)[src + q] + (reinterpret_cast<const f32x4*>(rs)[src + q] + p2);
             reinterpret_cast<f32x4*>(s)[pix * C4 + cg + q] = v;
             o[q] = f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)} * scale;
             amax = fh2_amax4(amax, o[q]);
@@ -486,12 +506,13 @@ __global__ __launch_bounds__(256) void upsample2x_combine_kernel(const float* __
 // output is decided from ITS OWN up_axis, and one that has not (fp32 rounding of the source coordinate on a very large map)
 // fetches its corners as the first form does: indices, weights and bilerp4 are the first form's for every output, bit for bit.
 // The output beyond an edge of the window (-1, Hc, Wc) is skipped and lends its axis to its neighbour.
-// FMT 0: fp32 (4 channels per thread), 2: fh2 (8 channels), 3: fh2 combine (upsample2x_combine_kernel; y = sr2).
+// FMT 0: fp32 (4 channels per thread), 2: fh2 (8 channels), 3: fh2 combine (upsample2x_combine_kernel; y = sr2), 4: the combine
+// with signed sources (CombineSrc).
 template <int FMT>
 __global__ __launch_bounds__(256) void upsample2x_block_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ c,
                                                                const float* __restrict__ r0, const int* __restrict__ map,
                                                                float* __restrict__ s, int B, int H, int W, int C4, int Hc, int Wc,
-                                                               float scale, unsigned* __restrict__ absmax) {
+                                                               float scale, unsigned* __restrict__ absmax, CombineSrc hs) {
     constexpr int Q = FMT == 0 ? 1 : 2;                        // float4 per thread
     const float sh = up_scale(H), sw = up_scale(W);
     const int NKB = Hc / 2 + 1, NJB = Wc / 2 + 1;              // blocks per map column / row
@@ -540,11 +561,13 @@ __global__ __launch_bounds__(256) void upsample2x_block_kernel(const float* __re
                 const long pix = ((long)b * Hc + oy[r]) * Wc + ox[t];
                 if (FMT == 0) reinterpret_cast<f32x4*>(y)[pix * C4 + cq] = o[0];
                 else {
-                    if (FMT == 3) {
-                        const long src = (((long)map[b] * Hc + oy[r]) * Wc + ox[t]) * C4 + cq;
+                    if (FMT >= 3) {
+                        const float *__restrict__ cs = c, *__restrict__ rs = r0;
+                        const long blk = combine_block<FMT == 4>(hs, map[b], cs, rs);
+                        const long src = ((blk * Hc + oy[r]) * Wc + ox[t]) * C4 + cq;
 #pragma unroll
                         for (int q = 0; q < Q; q++) {
-                            const f32x4 w = reinterpret_cast<const f32x4*>(c)[src + q] + (reinterpret_cast<const f32x4*>(r0)[src + q] + o[q]);
+                            const f32x4 w = reinterpret_cast<const f32x4*>(cs)[src + q] + (reinterpret_cast<const f32x4*>(rs)[src + q] + o[q]);
                             reinterpret_cast<f32x4*>(s)[pix * C4 + cq + q] = w;
                             o[q] = f32x4{fmaxf(w.x, 0.f), fmaxf(w.y, 0.f), fmaxf(w.z, 0.f), fmaxf(w.w, 0.f)};
                         }
@@ -903,27 +926,52 @@ extern "C" int a3r_gather_add_rows_src(const float* store, long stride, const fl
     return a3r::gather_add_rows_src(store, stride, fresh, src, b, map_b, dst, S, N, C, stream);
 }
 
-int a3r::combine_resid_fh2(const float* c, const float* r0, const float* p2, const int32_t* map, float* s, void* sr2, int S, long P, int C,
-                           float scale, unsigned* absmax, void* stream) {
-    A3R_CHECK_ARG(c && r0 && p2 && map && s && sr2, "a3r_combine_resid_fh2: null pointer");
-    A3R_CHECK_ARG(S > 0 && P > 0 && C > 0 && C % 8 == 0 && (long)S * P < (1L << 31), "a3r_combine_resid_fh2: bad shape (C must be a multiple of 8)");
-    A3R_CHECK_ARG(scale > 0.f && std::isfinite(scale), "a3r_combine_resid_fh2: scale must be positive and finite");
+// one body for the two entry points: hs null = c / r0 hold the blocks map names; else map is the signed source list
+static int combine_resid_launch(const char* who, const float* c, const float* r0, const CombineSrc* hs, const float* p2, const int32_t* map,
+                                float* s, void* sr2, int S, long P, int C, float scale, unsigned* absmax, void* stream) {
+    A3R_CHECK_ARG(p2 && map && s && sr2 && (hs ? (c && r0) || (hs->c && hs->r0) : c && r0), "%s: null pointer", who);
+    A3R_CHECK_ARG(S > 0 && P > 0 && C > 0 && C % 8 == 0 && (long)S * P < (1L << 31), "%s: bad shape (C must be a multiple of 8)", who);
+    A3R_CHECK_ARG(!hs || (hs->stride >= P * C && hs->stride % 4 == 0 && !hs->c == !hs->r0 && !c == !r0), "%s: bad storage stride or pointers", who);
+    A3R_CHECK_ARG(scale > 0.f && std::isfinite(scale), "%s: scale must be positive and finite", who);
     A3R_CHECK_ARG(((reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(r0) | reinterpret_cast<uintptr_t>(p2) |
-                    reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(sr2)) & 15) == 0,
-                  "a3r_combine_resid_fh2: buffers must be 16-byte aligned");
+                    reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(sr2) | (hs ? reinterpret_cast<uintptr_t>(hs->c) : 0) |
+                    (hs ? reinterpret_cast<uintptr_t>(hs->r0) : 0)) & 15) == 0,
+                  "%s: buffers must be 16-byte aligned", who);
     const long rows = (long)S * P, total = rows * (C / 8);
     ProfScope prof(PK_ELEMENTWISE, 5.0 * 32 * total, as_stream(stream));
     const long blocks = (total + 255) / 256;
     // persistent grid (8 workgroups per CU), as the split pass
-    hipLaunchKernelGGL(combine_resid_fh2_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, as_stream(stream), c, r0, p2,
-                       map, s, static_cast<char*>(sr2), rows, P, C / 8, scale, absmax);
+    const dim3 grid((unsigned)(blocks < 2048 ? blocks : 2048));
+    if (hs)
+        hipLaunchKernelGGL(combine_resid_fh2_kernel<true>, grid, dim3(256), 0, as_stream(stream), c, r0, p2, map, s, static_cast<char*>(sr2),
+                           rows, P, C / 8, scale, absmax, *hs);
+    else
+        hipLaunchKernelGGL(combine_resid_fh2_kernel<false>, grid, dim3(256), 0, as_stream(stream), c, r0, p2, map, s, static_cast<char*>(sr2),
+                           rows, P, C / 8, scale, absmax, CombineSrc{});
     A3R_LAUNCH_CHECK();
     return A3R_OK;
+}
+
+int a3r::combine_resid_fh2(const float* c, const float* r0, const float* p2, const int32_t* map, float* s, void* sr2, int S, long P, int C,
+                           float scale, unsigned* absmax, void* stream) {
+    return combine_resid_launch("a3r_combine_resid_fh2", c, r0, nullptr, p2, map, s, sr2, S, P, C, scale, absmax, stream);
 }
 
 extern "C" int a3r_combine_resid_fh2(const float* c, const float* r0, const float* p2, const int32_t* map, float* s, void* sr2, int S,
                                      long P, int C, float scale, unsigned* absmax, void* stream) {
     return a3r::combine_resid_fh2(c, r0, p2, map, s, sr2, S, P, C, scale, absmax, stream);
+}
+
+int a3r::combine_resid_fh2_src(const float* c, const float* r0, const float* store_c, const float* store_r0, long stride, const int32_t* src,
+                               const float* p2, float* s, void* sr2, int S, long P, int C, float scale, unsigned* absmax, void* stream) {
+    const CombineSrc hs = {store_c, store_r0, stride};
+    return combine_resid_launch("a3r_combine_resid_fh2_src", c, r0, &hs, p2, src, s, sr2, S, P, C, scale, absmax, stream);
+}
+
+extern "C" int a3r_combine_resid_fh2_src(const float* c, const float* r0, const float* store_c, const float* store_r0, long stride,
+                                         const int32_t* src, const float* p2, float* s, void* sr2, int S, long P, int C, float scale,
+                                         unsigned* absmax, void* stream) {
+    return a3r::combine_resid_fh2_src(c, r0, store_c, store_r0, stride, src, p2, s, sr2, S, P, C, scale, absmax, stream);
 }
 
 static inline dim3 upsample_grid(int B, int Hc, int Wc, int groups) {      // groups: threads per output pixel
@@ -957,7 +1005,7 @@ extern "C" int a3r_upsample2x(const float* x, float* y, int B, int H, int W, int
         hipLaunchKernelGGL(upsample2x_kernel<0>, upsample_grid(B, Hc, Wc, C / 4), dim3(256), 0, as_stream(stream), x, y, B, H, W, C / 4, Hc, Wc, 1.f, nullptr);
     else
         hipLaunchKernelGGL(upsample2x_block_kernel<0>, upsample_block_grid(B, Hc, Wc, C / 4, 1), dim3(256), 0, as_stream(stream), x, y,
-                           nullptr, nullptr, nullptr, nullptr, B, H, W, C / 4, Hc, Wc, 1.f, nullptr);
+                           nullptr, nullptr, nullptr, nullptr, B, H, W, C / 4, Hc, Wc, 1.f, nullptr, CombineSrc{});
     A3R_LAUNCH_CHECK();
     return A3R_OK;
 }
@@ -984,7 +1032,7 @@ extern "C" int a3r_upsample2x_fh2(const float* x, void* y2, int B, int H, int W,
     ProfScope prof(PK_ELEMENTWISE, 16.0 * total + 4.0 * B * H * W * C, as_stream(stream));
     if (g_up_form.load() != 1) {
         hipLaunchKernelGGL(upsample2x_block_kernel<2>, upsample_block_grid(B, Hc, Wc, C / 8, 2), dim3(256), 0, as_stream(stream), x,
-                           static_cast<float*>(y2), nullptr, nullptr, nullptr, nullptr, B, H, W, C / 4, Hc, Wc, scale, absmax);
+                           static_cast<float*>(y2), nullptr, nullptr, nullptr, nullptr, B, H, W, C / 4, Hc, Wc, scale, absmax, CombineSrc{});
         A3R_LAUNCH_CHECK();
         return A3R_OK;
     }
@@ -999,35 +1047,67 @@ extern "C" int a3r_upsample2x_fh2(const float* x, void* y2, int B, int H, int W,
     return A3R_OK;
 }
 
-int a3r::upsample2x_combine_fh2(const float* x, const float* c, const float* r0, const int32_t* map, float* s, void* sr2, int B, int H, int W,
-                                int C, int Hc, int Wc, float scale, unsigned* absmax, void* stream) {
-    A3R_CHECK_ARG(x && c && r0 && map && s && sr2, "upsample2x_combine_fh2: null pointer");
-    A3R_CHECK_ARG(scale > 0.f && std::isfinite(scale), "upsample2x_combine_fh2: scale must be positive and finite");
-    A3R_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "upsample2x_combine_fh2: bad shape (C must be a multiple of 8)");
-    A3R_CHECK_ARG(Hc > 0 && Hc <= 2 * H && Wc > 0 && Wc <= 2 * W, "upsample2x_combine_fh2: crop window larger than the 2x map");
+// one body for the two entry points (combine_resid_launch)
+static int upsample2x_combine_launch(const char* who, const float* x, const float* c, const float* r0, const CombineSrc* hs,
+                                     const int32_t* map, float* s, void* sr2, int B, int H, int W, int C, int Hc, int Wc, float scale,
+                                     unsigned* absmax, void* stream) {
+    A3R_CHECK_ARG(x && map && s && sr2 && (hs ? (c && r0) || (hs->c && hs->r0) : c && r0), "%s: null pointer", who);
+    A3R_CHECK_ARG(scale > 0.f && std::isfinite(scale), "%s: scale must be positive and finite", who);
+    A3R_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "%s: bad shape (C must be a multiple of 8)", who);
+    A3R_CHECK_ARG(Hc > 0 && Hc <= 2 * H && Wc > 0 && Wc <= 2 * W, "%s: crop window larger than the 2x map", who);
+    A3R_CHECK_ARG(!hs || (hs->stride >= (long)Hc * Wc * C && hs->stride % 4 == 0 && !hs->c == !hs->r0 && !c == !r0),
+                  "%s: bad storage stride or pointers", who);
     A3R_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(r0) |
-                    reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(sr2)) & 15) == 0,
-                  "upsample2x_combine_fh2: buffers must be 16-byte aligned");
+                    reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(sr2) | (hs ? reinterpret_cast<uintptr_t>(hs->c) : 0) |
+                    (hs ? reinterpret_cast<uintptr_t>(hs->r0) : 0)) & 15) == 0,
+                  "%s: buffers must be 16-byte aligned", who);
     const long total = (long)B * Hc * Wc * (C / 4);
     ProfScope prof(PK_ELEMENTWISE, 40.0 * total + 4.0 * B * H * W * C, as_stream(stream));
     if (g_up_form.load() != 1) {
-        hipLaunchKernelGGL(upsample2x_block_kernel<3>, upsample_block_grid(B, Hc, Wc, C / 8, 4), dim3(256), 0, as_stream(stream), x,
-                           static_cast<float*>(sr2), c, r0, map, s, B, H, W, C / 4, Hc, Wc, scale, absmax);
+        const dim3 grid = upsample_block_grid(B, Hc, Wc, C / 8, 4);
+        if (hs)
+            hipLaunchKernelGGL(upsample2x_block_kernel<4>, grid, dim3(256), 0, as_stream(stream), x, static_cast<float*>(sr2), c, r0, map, s, B,
+                               H, W, C / 4, Hc, Wc, scale, absmax, *hs);
+        else
+            hipLaunchKernelGGL(upsample2x_block_kernel<3>, grid, dim3(256), 0, as_stream(stream), x, static_cast<float*>(sr2), c, r0, map, s, B,
+                               H, W, C / 4, Hc, Wc, scale, absmax, CombineSrc{});
         A3R_LAUNCH_CHECK();
         return A3R_OK;
     }
     dim3 grid = upsample_grid(B, Hc, Wc, C / 8);
     const unsigned ycap = (grid.y + 7) / 8;                   // as a3r_upsample2x_fh2: ~8 rows and one statistics atomic per workgroup
     if (grid.y > ycap) grid.y = ycap;
-    hipLaunchKernelGGL(upsample2x_combine_kernel, grid, dim3(256), 0, as_stream(stream), x, c, r0, map, s, static_cast<char*>(sr2), B, H, W,
-                       C / 4, Hc, Wc, scale, absmax);
+    if (hs)
+        hipLaunchKernelGGL(upsample2x_combine_kernel<true>, grid, dim3(256), 0, as_stream(stream), x, c, r0, map, s, static_cast<char*>(sr2), B,
+                           H, W, C / 4, Hc, Wc, scale, absmax, *hs);
+    else
+        hipLaunchKernelGGL(upsample2x_combine_kernel<false>, grid, dim3(256), 0, as_stream(stream), x, c, r0, map, s, static_cast<char*>(sr2), B,
+                           H, W, C / 4, Hc, Wc, scale, absmax, CombineSrc{});
     A3R_LAUNCH_CHECK();
     return A3R_OK;
+}
+
+int a3r::upsample2x_combine_fh2(const float* x, const float* c, const float* r0, const int32_t* map, float* s, void* sr2, int B, int H, int W,
+                                int C, int Hc, int Wc, float scale, unsigned* absmax, void* stream) {
+    return upsample2x_combine_launch("upsample2x_combine_fh2", x, c, r0, nullptr, map, s, sr2, B, H, W, C, Hc, Wc, scale, absmax, stream);
 }
 
 extern "C" int a3r_upsample2x_combine_fh2(const float* x, const float* c, const float* r0, const int32_t* map, float* s, void* sr2, int S,
                                           int H, int W, int C, int Hc, int Wc, float scale, unsigned* absmax, void* stream) {
     return a3r::upsample2x_combine_fh2(x, c, r0, map, s, sr2, S, H, W, C, Hc, Wc, scale, absmax, stream);
+}
+
+int a3r::upsample2x_combine_fh2_src(const float* x, const float* c, const float* r0, const float* store_c, const float* store_r0, long stride,
+                                    const int32_t* src, float* s, void* sr2, int B, int H, int W, int C, int Hc, int Wc, float scale,
+                                    unsigned* absmax, void* stream) {
+    const CombineSrc hs = {store_c, store_r0, stride};
+    return upsample2x_combine_launch("a3r_upsample2x_combine_fh2_src", x, c, r0, &hs, src, s, sr2, B, H, W, C, Hc, Wc, scale, absmax, stream);
+}
+
+extern "C" int a3r_upsample2x_combine_fh2_src(const float* x, const float* c, const float* r0, const float* store_c, const float* store_r0,
+                                              long stride, const int32_t* src, float* s, void* sr2, int S, int H, int W, int C, int Hc,
+                                              int Wc, float scale, unsigned* absmax, void* stream) {
+    return a3r::upsample2x_combine_fh2_src(x, c, r0, store_c, store_r0, stride, src, s, sr2, S, H, W, C, Hc, Wc, scale, absmax, stream);
 }
 
 extern "C" int a3r_head_final(const float* x, const float* w, const float* b, float* pts3d, float* conf, long P, int C,

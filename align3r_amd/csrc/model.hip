@@ -9,8 +9,8 @@
 // Data layout: tokens [rows, C] with rows = (side, batch, token): the first B*N rows belong to view 1,
 // the next B*N rows to view 2 (this is the reference's torch.cat((img1, img2)) batch order), maps are
 // channels-last.  All buffers live in the caller's workspace; nothing here allocates device memory, except the handle's key / map
-// words for the duplicate search (find_distinct, about 130 KB).  The frames and depth priors kept across calls live in storage the
-// caller installs (a3r_model_set_frame_cache, a3r_model_set_frame_products).
+// words for the duplicate search (find_distinct, about 140 KB).  The frames, depth priors and head products kept across calls live in
+// storage the caller installs (a3r_model_set_frame_cache, a3r_model_set_frame_products, a3r_model_set_head_products).
 #include "plan.h"
 #include "dedup.h"
 #include <algorithm>
@@ -98,10 +98,23 @@ struct a3r_model_s {
     size_t fp_bytes = 0;
     FrameCacheTable pd_table;
     int last_pd[3] = {0, 0, 0};
+    // head products kept across calls (a3r_model_set_head_products): the caller's third storage, indexed by the frame cache's
+    // entries, one valid bit per (entry, side) (dedup.h), and what the last forward did with it per side
+    // (a3r_model_last_head_products: hits, misses among the distinct frames of a merging side)
+    void* hp_buf = nullptr;
+    size_t hp_bytes = 0;
+    HeadBits hp_bits;
+    int last_hp[2][2] = {{0, 0}, {0, 0}};
+    // the frame cache's table emptied or resized: the head products' bits name its entries
+    void reset_frames(int capacity) {
+        fc_table.reset(capacity);
+        hp_bits.flush();
+    }
     // whatever was stored under other weights, scales, keys or after a failed call is forgotten
     void drop_stored() {
         fc_table.flush();
         pd_table.flush();
+        hp_bits.flush();
     }
     ~a3r_model_s() {
         if (dd_dev) (void)hipFree(dd_dev);
@@ -472,6 +485,16 @@ extern "C" int a3r_model_finalize(a3r_model_t m, void* packed, size_t packed_byt
 // ------------------------------------------------------------------------------------------- launch plan
 namespace {
 
+// Head products kept across calls (null: none are): the level-0 branch of side s's head runs on the n_fresh distinct frames of the
+// side that are not stored, uniq_fresh [n_fresh] (slots, device); frame k < n_side[s] is entry hent[k]'s when hmiss[k] < 0, else
+// the hmiss[k]-th of those, whose r0 and c go to entry hent[k] when that is >= 0 (n_store of them do).  src [B]: where the combine
+// pass finds the c and r0 of a slot (head_lists).
+// With n_fresh == 0 the branch's ops are walked muted on one frame's rows, as the encoder's and the prior branch's are.
+struct HeadCall {
+    HeadStore st; int n_fresh, n_store; const int32_t *uniq_fresh, *hent, *hmiss, *src;
+    int frames() const { return n_fresh ? n_fresh : 1; }      // frames the branch's ops are walked with
+};
+
 struct Plan {
     a3r_model_s* m;
     Arena ar;
@@ -484,6 +507,7 @@ struct Plan {
     // whose every frame was found in the frame cache)
     bool mute = false;
     SiteMask prior_sites;      // the sites of the depth-prior branch, whose words the stored priors complete (PriorScope)
+    SiteMask head_sites[2];    // the sites of each head's level-0 branch, whose words the stored head products complete (HeadScope)
     // ---- fh2 range control: every op that WRITES an fh2 tensor is a site (numbered in plan order) with its own power-of-two
     // scale; the scale travels with the buffer pointer to the ops that read it
     int phase = 0, site_no = 0;
@@ -580,7 +604,7 @@ struct Plan {
     void linear_f32(const float* x, int lda, const float* w, float* y, int ldc, int M, int N, int K, const a3r_epilogue& e) {
         if (skip()) return;
         traced("linear_f32", M, N, K);
-        rc = a3r_linear(x, lda, w, y, ldc, M, N, K, &e, stream);
+        if (!mute) rc = a3r_linear(x, lda, w, y, ldc, M, N, K, &e, stream);
     }
     // the same-shape projection of both decoders (dec_blocks[i] on view 1, dec_blocks2[i] on view 2) in one launch
     void linear2(const float* x0, const float* x1, int lda, const float* w0, const float* w1, const float* b0, const float* b1,
@@ -608,7 +632,7 @@ struct Plan {
         traced("conv3x3", H, W, Cin);
         const Twin* tw = twin(wp, mf);
         const a3r_epilogue e = retarget(e0, mf, [&](a3r_epilogue& r) { range_epi(r, xm, y); });
-        if (!rc) rc = op_conv3x3(mf, xm, wp, tw, y, B, H, W, Cin, Cout, stride, e, stream);
+        if (!rc && !mute) rc = op_conv3x3(mf, xm, wp, tw, y, B, H, W, Cin, Cout, stride, e, stream);
     }
     // bilinear 2x of an fp32 map, written in form f (the map form, or F32 for a consumer that needs the values)
     void up(Form f, const float* x, float* y, int B, int H, int W, int C, int Hc, int Wc) {
@@ -618,19 +642,26 @@ struct Plan {
         if (!rc) rc = op_upsample2x(f, x, y, B, H, W, C, Hc, Wc, s.scale, s.stat, stream);
     }
     // s = c[map] + (r[map] + extra) and the fh2 form of relu(s): the RESID2 epilogue + aux output of a conv that ran on distinct frames
-    void combine_map(const float* c, const float* r, const float* extra, const int32_t* map, float* s, float* sr2, int S, long px, int C) {
+    // hc (head products of side hs): c and r are the fresh frames' blocks, and every slot reads its own where hc->src says, in
+    // the storage or there
+    void combine_map(const float* c, const float* r, const float* extra, const int32_t* map, float* s, float* sr2, int S, long px, int C,
+                     const HeadCall* hc, int hs) {
         if (skip()) return;
         traced("combine_resid", S, (int)px, C);
         const Site st = site(sr2);
-        if (!rc) rc = combine_resid_fh2(c, r, extra, map, s, sr2, S, px, C, st.scale, st.stat, stream);
+        if (rc) return;
+        if (hc) rc = combine_resid_fh2_src(c, r, hc->st.c(hs), hc->st.r0(hs), hc->st.stride(), hc->src, extra, s, sr2, S, px, C, st.scale, st.stat, stream);
+        else rc = combine_resid_fh2(c, r, extra, map, s, sr2, S, px, C, st.scale, st.stat, stream);
     }
     // the same with extra = the bilinear 2x of x [S, H, W, C] made inside the kernel
     void up_combine_map(const float* x, const float* c, const float* r, const int32_t* map, float* s, float* sr2, int S, int H, int W,
-                        int C, int Hc, int Wc) {
+                        int C, int Hc, int Wc, const HeadCall* hc, int hs) {
         if (skip()) return;
         traced("upsample2x_combine", H, W, C);
         const Site st = site(sr2);
-        if (!rc) rc = upsample2x_combine_fh2(x, c, r, map, s, sr2, S, H, W, C, Hc, Wc, st.scale, st.stat, stream);
+        if (rc) return;
+        if (hc) rc = upsample2x_combine_fh2_src(x, c, r, hc->st.c(hs), hc->st.r0(hs), hc->st.stride(), hc->src, s, sr2, S, H, W, C, Hc, Wc, st.scale, st.stat, stream);
+        else rc = upsample2x_combine_fh2(x, c, r, map, s, sr2, S, H, W, C, Hc, Wc, st.scale, st.stat, stream);
     }
     // LayerNorm whose output feeds a GEMM (written directly in the GEMMs' operand form)
     void ln(const float* x, const float* w, const float* b, float* yg, int M, int D) {
@@ -723,7 +754,22 @@ void rcu_map(Plan& P, const RcuW& w, const float* x, const float* xr3, const flo
 // The level-0 branch of a head on the distinct frames of its side (fh2 maps): x1 / x1r3 of fusion_map hold U < B images, slot b's
 // being map[b] (device).  fold: x0 of fusion_map is not there -- the previous fusion block left its output before the bilinear 2x
 // (x0_lo [B, lo_h, lo_w, F]) and the combine pass interpolates it on the fly.
-struct HeadMerge { int U; const int32_t* map; bool fold; const float* x0_lo; int lo_h, lo_w; };
+// hc (head products kept across calls, side `side`): the branch runs on the hc->n_fresh frames of the U that are not stored -- the
+// buffers keep their size, fewer rows of them are used -- and the combine pass reads every slot's c and r0 where hc->src says.
+struct HeadMerge { int U; const int32_t* map; bool fold; const float* x0_lo; int lo_h, lo_w; const HeadCall* hc; int side; };
+// The ops of a head's level-0 branch walked while one of these lives: launched on the fresh frames' rows, or not at all
+// (Plan::mute) when every frame of the side is stored, and their sites noted for the statistics pass of head_stage (as PriorScope)
+struct HeadScope {
+    Plan& P;
+    const HeadCall* hc;
+    int side, lo;
+    HeadScope(Plan& P_, const HeadCall* hc_, int s) : P(P_), hc(hc_), side(s), lo(P_.site_no) { if (hc) P.mute = hc->n_fresh == 0; }
+    ~HeadScope() {
+        if (!hc) return;
+        P.mute = false;
+        P.head_sites[side].add(lo, P.site_no);
+    }
+};
 static bool dpt_ref_order() {       // A/B switch: up-sample first, as the reference does
     static const bool on = getenv("A3R_DPT_REF_ORDER") != nullptr;
     return on;
@@ -748,10 +794,16 @@ float* fusion_map(Plan& P, const FusionW& w, const float* x0, const float* x0r3,
         float* sr3 = P.map_twin(s, px, F);
         if (hm) {
             float* c = ar.alloc((size_t)hm->U * H * W * F);
-            rcu_conv1(P, w.r1, x1r3, tmp3, hm->U, H, W, F);
-            P.conv(tmp3, w.r1.c2w, c, hm->U, H, W, F, F, 1, P.epi(A3R_EPI_NONE, w.r1.c2b));
-            if (hm->fold) P.up_combine_map(hm->x0_lo, c, x1, hm->map, s, sr3, B, hm->lo_h, hm->lo_w, F, H, W);
-            else P.combine_map(c, x1, x0, hm->map, s, sr3, B, (long)H * W, F);
+            const HeadCall* hc = hm->hc;
+            const int Uf = hc ? hc->frames() : hm->U;
+            {
+                HeadScope scope(P, hc, hm->side);
+                rcu_conv1(P, w.r1, x1r3, tmp3, Uf, H, W, F);
+                P.conv(tmp3, w.r1.c2w, c, Uf, H, W, F, F, 1, P.epi(A3R_EPI_NONE, w.r1.c2b));
+            }
+            if (hc && hc->n_store && !P.skip()) P.rc = head_products_store(hc->st, hm->side, hc->hent, hc->hmiss, hm->U, x1, c, P.stream);
+            if (hm->fold) P.up_combine_map(hm->x0_lo, c, x1, hm->map, s, sr3, B, hm->lo_h, hm->lo_w, F, H, W, hc, hm->side);
+            else P.combine_map(c, x1, x0, hm->map, s, sr3, B, (long)H * W, F, hc, hm->side);
         } else
             rcu_map(P, w.r1, x1, x1r3, x0, tmp3, s, sr3, B, H, W, F);     // output + resConfUnit1(xs[1])
         cur = s; cur3 = sr3;
@@ -805,6 +857,8 @@ struct Distinct {
     // when that is >= 0 (n_store of them do).  src [2 B] / src_ent [2 n_ent]: where the gather-add pass finds the z rows of a
     // slot / of a block-0 entry (prior_lists).  The prior stage then runs on the distinct list even when that holds all 2 B slots.
     const struct PriorCall* pp = nullptr;
+    // Head products kept across calls, per side (null: that side's head computes its level-0 branch for all its n_side[s] frames)
+    const HeadCall* hp[2] = {nullptr, nullptr};
 };
 struct CacheCall { FrameCacheLayout lay; const void* keys; int n_miss; const int32_t *uniq_miss, *ent, *miss; };
 struct PriorCall { FrameCacheLayout lay; const void* keys; int n_miss, n_store; const int32_t *uniq_miss, *ent, *miss, *src, *src_ent; };
@@ -1132,7 +1186,8 @@ void decoder_stage(Plan& P, const Call& k, const Dims& g, Levels& v) {
 // act_postprocess (dpt_block.py:353-405) of the head of side s: the four hooked levels -> the maps l[0..3] that layer_rn reads, in
 // operand form (l[3] is written in it; the others are split: small maps, plain split passes).  Level 0 (enc_norm rows) depends on
 // the frame alone: B0 images, the side's distinct ones when its head merges.
-void head_levels(Plan& P, const Call& k, const Dims& g, const Levels& v, int s, int B0, float* (&l)[4]) {
+// hc (head products): the level-0 ops run on the hc->n_fresh frames of the B0 that are not stored, in the buffers of B0.
+void head_levels(Plan& P, const Call& k, const Dims& g, const Levels& v, int s, int B0, const HeadCall* hc, float* (&l)[4]) {
     Arena& ar = P.ar;
     const HeadW& Hd = P.m->head[s];
     const int *ld = g.c.layer_dims, nh = g.nh, nw = g.nw, B = g.B, BN = g.BN, E = g.E, D = g.D;
@@ -1153,16 +1208,22 @@ void head_levels(Plan& P, const Call& k, const Dims& g, const Levels& v, int s, 
         P.linear_f32(a, C, w, y, C, rows, ps * ps * C, C, e);
     };
     const size_t BN0 = (size_t)B0 * g.N;
+    const int R0 = (hc ? hc->frames() : B0) * g.N;             // rows the level-0 ops run on (one frame's when muted)
     const float* t0 = side(v.feat, E);
-    if (B0 < B) {
-        float* fu = ar.alloc(BN0 * E);
-        if (!P.skip()) P.rc = gather_rows(v.feat, fu, k.dd->uniq_side[s], B0, g.N, E, P.stream);
-        t0 = fu;
+    float *a0, *l0;
+    {
+        HeadScope scope(P, hc, s);
+        if (B0 < B) {
+            float* fu = ar.alloc(BN0 * E);
+            if (!P.skip() && !P.mute)
+                P.rc = gather_rows(v.feat, fu, hc ? hc->uniq_fresh : k.dd->uniq_side[s], R0 / g.N, g.N, E, P.stream);
+            t0 = fu;
+        }
+        a0 = ar.alloc(BN0 * ld[0]);
+        adapter(t0, E, Hd.a0w, Hd.a0b, a0, ld[0], R0);
+        l0 = ar.alloc(BN0 * 16 * ld[0]);
+        pixshuf(a0, Hd.a0tw, Hd.a0tb, l0, 4, ld[0], R0);
     }
-    float* a0 = ar.alloc(BN0 * ld[0]);
-    adapter(t0, E, Hd.a0w, Hd.a0b, a0, ld[0], (int)BN0);
-    float* l0 = ar.alloc(BN0 * 16 * ld[0]);
-    pixshuf(a0, Hd.a0tw, Hd.a0tb, l0, 4, ld[0], (int)BN0);
     float* a1 = ar.alloc((size_t)BN * ld[1]);
     adapter(side(v.lvl_a, D), D, Hd.a1w, Hd.a1b, a1, ld[1], BN);
     float* l1 = ar.alloc((size_t)BN * 4 * ld[1]);
@@ -1178,7 +1239,10 @@ void head_levels(Plan& P, const Call& k, const Dims& g, const Levels& v, int s, 
     e.out_op = 1;
     P.conv(a33, Hd.a3cw, l[3], B, nh, nw, ld[3], ld[3], 2, e);
     l[0] = P.map_twin(l0, BN0 * 16, ld[0]);
-    P.split_map(l0, l[0], (long)BN0 * 16, ld[0]);
+    {
+        HeadScope scope(P, hc, s);
+        P.split_map(l0, l[0], (long)R0 * 16, ld[0]);
+    }
     l[1] = P.map_twin(l1, (size_t)BN * 4, ld[1]);
     P.split_map(l1, l[1], (long)BN * 4, ld[1]);
     l[2] = P.map_twin(l2, BN, ld[2]);
@@ -1195,10 +1259,12 @@ void head_stage(Plan& P, const Call& k, const Dims& g, const Levels& v, int s) {
     const int h3 = (nh + 2 - 3) / 2 + 1, w3 = (nw + 2 - 3) / 2 + 1;
     const int B0 = k.dd && P.mf == Form::FH2 ? k.dd->n_side[s] : B;
     // (the combine pass folded into refinenet2's 2x up-sample, whose fp32 output only it would read)
-    HeadMerge hmerge = {B0, k.dd ? k.dd->map_side[s] : nullptr, B0 < B && m->dedup_head_fold && !dpt_ref_order(), nullptr, 2 * nh, 2 * nw};
+    const HeadCall* hc = k.dd && B0 < B ? k.dd->hp[s] : nullptr;
+    HeadMerge hmerge = {B0, k.dd ? k.dd->map_side[s] : nullptr, B0 < B && m->dedup_head_fold && !dpt_ref_order(), nullptr, 2 * nh, 2 * nw,
+                        hc, s};
     const size_t BN0 = (size_t)B0 * g.N;
     float* l[4];
-    head_levels(P, k, g, v, s, B0, l);
+    head_levels(P, k, g, v, s, B0, hc, l);
     // scratch.layer_rn (no bias): fp32 for the skip connection + pre-activated map form for the first RCU conv
     float* r0 = ar.alloc(BN0 * 16 * F);
     float* r0r3 = P.map_twin(r0, BN0 * 16, F);
@@ -1209,7 +1275,10 @@ void head_stage(Plan& P, const Call& k, const Dims& g, const Levels& v, int s) {
     float* r3 = ar.alloc((size_t)B * h3 * w3 * F);
     float* r3r3 = P.map_twin(r3, (size_t)B * h3 * w3, F);
     auto rn_epi = [&](float* twin) { OpEpi e = P.epi(A3R_EPI_NONE, nullptr); P.aux(e, twin, true); return e; };
-    P.conv(l[0], Hd.rn[0], r0, B0, 4 * nh, 4 * nw, ld[0], F, 1, rn_epi(r0r3));
+    {
+        HeadScope scope(P, hc, s);
+        P.conv(l[0], Hd.rn[0], r0, hc ? hc->frames() : B0, 4 * nh, 4 * nw, ld[0], F, 1, rn_epi(r0r3));
+    }
     P.conv(l[1], Hd.rn[1], r1, B, 2 * nh, 2 * nw, ld[1], F, 1, rn_epi(r1r3));
     P.conv(l[2], Hd.rn[2], r2, B, nh, nw, ld[2], F, 1, rn_epi(r2r3));
     P.conv(l[3], Hd.rn[3], r3, B, h3, w3, ld[3], F, 1, rn_epi(r3r3));
@@ -1219,6 +1288,8 @@ void head_stage(Plan& P, const Call& k, const Dims& g, const Levels& v, int s) {
     float* p2 = fusion_map(P, Hd.ref[1], p3, nullptr, r1, r1r3, true, B, 2 * nh, 2 * nw, F, 4 * nh, 4 * nw, false, nullptr,
                            hmerge.fold ? &hmerge.x0_lo : nullptr);
     float* p13 = fusion_map(P, Hd.ref[0], p2, nullptr, r0, r0r3, true, B, 4 * nh, 4 * nw, F, 8 * nh, 8 * nw, true, B0 < B ? &hmerge : nullptr);
+    // the level-0 branch's statistics words: kept with the (entry, side) this call filled, completed from those it read
+    if (hc && !P.skip()) P.rc = stats_sites_words(hc->st.side_words(s), hc->st.cap, hc->hent, hc->hmiss, B0, m->stats, P.head_sites[s], P.stream);
     // head (dpt_block.py:323-330)
     const int Hh = 8 * nh, Wh = 8 * nw;
     float* h0 = ar.alloc((size_t)B * Hh * Wh * (F / 2));
@@ -1359,8 +1430,8 @@ constexpr size_t DD_HOST_LIST = (DEDUP_REP_INTS + 4 * FC_MAX_PAIRS + 63) / 64 * 
 constexpr size_t DD_REP_OFF = DEDUP_KEY_BYTES;                     // device bytes: keys | rep + flag + answer | the DD_LISTS lists
 constexpr size_t DD_LIST_OFF = DD_REP_OFF + DD_HOST_LIST * 4;
 // uniq_img, map_img, uniq_pd, map_pd, uniq_side [2][B], map_side [2][B], ent_img, ent_pd, map_eo, map_ekv; frame cache: uniq_miss, ent, miss;
-// stored priors: uniq_miss, ent, miss, src, src_ent
-constexpr int DD_LISTS = 18;
+// stored priors: uniq_miss, ent, miss, src, src_ent; head products, both sides in one block as uniq_side: hent, hmiss, uniq_fresh, src
+constexpr int DD_LISTS = 22;
 constexpr size_t DD_DEV_BYTES = DD_LIST_OFF + (size_t)DD_LISTS * DD_HALF * 4;
 static_assert(FC_STAT_WORDS == a3r_model_s::MAX_SITES, "an entry stores one word per site");
 
@@ -1368,7 +1439,7 @@ static_assert(FC_STAT_WORDS == a3r_model_s::MAX_SITES, "an entry stores one word
 FrameCacheLayout frame_cache_at(a3r_model_s* m, int H, int W) {
     const FrameCacheLayout lay = frame_cache_layout(m->fc_buf, m->fc_bytes, 3L * H * W, (long)(H / 16) * (W / 16) * m->cfg.enc_embed_dim);
     if (H != m->fc_H || W != m->fc_W || lay.cap != m->fc_table.cap) {
-        m->fc_table.reset(lay.cap);
+        m->reset_frames(lay.cap);
         m->pd_table.reset(0);
         m->fc_H = H;
         m->fc_W = W;
@@ -1388,10 +1459,15 @@ FrameCacheLayout prior_store_at(a3r_model_s* m, int H, int W, int cap) {
     return lay;
 }
 
+// Words of one r0 / c block of the head products at this resolution: [16 N, F]
+long head_words(const a3r_model_config& c, int H, int W) { return 16L * (H / 16) * (W / 16) * c.feature_dim; }
+
 int find_distinct(a3r_model_s* m, const float* a1, const float* a2, long words_a, bool encode, const float* pd1, const float* pd2, int B,
-                  int H, int W, void* stream, Distinct* d, bool* use, CacheCall* cc = nullptr, PriorCall* pc = nullptr) {
+                  int H, int W, void* stream, Distinct* d, bool* use, CacheCall* cc = nullptr, PriorCall* pc = nullptr,
+                  HeadCall* hc = nullptr) {
     *use = false;
     m->last_fc[0] = m->last_fc[1] = m->last_fc[2] = 0;
+    m->last_hp[0][0] = m->last_hp[0][1] = m->last_hp[1][0] = m->last_hp[1][1] = 0;
     m->last_pd[0] = m->last_pd[1] = m->last_pd[2] = 0;
     m->last_img_unique = m->last_pd_unique = 2 * B;
     m->last_fell_back = 0;
@@ -1505,7 +1581,10 @@ int find_distinct(a3r_model_s* m, const float* a1, const float* a2, long words_a
             cc->n_miss = 0;
             for (int k = 0; k < n_img; k++) {
                 const bool hit = miss[k] >= 0;
-                if (!hit) uniq_miss[cc->n_miss] = uniq[k];
+                if (!hit) {
+                    uniq_miss[cc->n_miss] = uniq[k];
+                    m->hp_bits.clear(ent[k]);      // the entry now holds another frame: what the heads made of the old one is stale
+                }
                 miss[k] = hit ? -1 : cc->n_miss++;
             }
             cc->uniq_miss = list_dev + 10 * DD_HALF;
@@ -1538,6 +1617,35 @@ int find_distinct(a3r_model_s* m, const float* a1, const float* a2, long words_a
             pc->src_ent = list_dev + 17 * DD_HALF;
         }
     }
+    // The head products: which of a merging side's distinct frames are stored, and the lists of its level-0 branch.  They ride on
+    // the frame cache (its entries, dropped and bypassed with it); a side that does not merge neither reads nor writes them.
+    const HeadCall* hp[2] = {nullptr, nullptr};
+    if (cached && hc && m->hp_buf && m->map_form == Form::FH2 && m->gemm_form == Form::FH2) {
+        const long words = head_words(c, H, W);
+        const HeadStore st = head_store_layout(m->hp_bytes >= (size_t)cc->lay.cap * head_products_entry_bytes(words) ? m->hp_buf : nullptr,
+                                               cc->lay.cap, words);
+        const int32_t *map_img = list + DD_HALF, *ent = list + 11 * DD_HALF, *miss = list + 12 * DD_HALF;
+        for (int s = 0; s < 2 && st.cap > 0; s++) {
+            if (n_side[s] >= B) continue;
+            const int off = s * B, U = n_side[s];
+            const int32_t *uniq_side = list + 4 * DD_HALF + off, *map_side = list + 5 * DD_HALF + off;
+            std::vector<int32_t> row(U);
+            for (int k = 0; k < U; k++) row[k] = map_img[uniq_side[k]];
+            int n_store = 0;
+            const int n_fresh = head_lists(m->hp_bits, s, ent, miss, n_img, row.data(), uniq_side, U, map_side, B, list + 18 * DD_HALF + off,
+                                           list + 19 * DD_HALF + off, list + 20 * DD_HALF + off, list + 21 * DD_HALF + off, &n_store);
+            if (n_fresh < 0) {                  // (never: the lists are dedup_group's and assign's)
+                m->drop_stored();
+                m->last_fell_back = 1;
+                return A3R_OK;
+            }
+            hc[s] = {st, n_fresh, n_store, list_dev + 20 * DD_HALF + off, list_dev + 18 * DD_HALF + off, list_dev + 19 * DD_HALF + off,
+                     list_dev + 21 * DD_HALF + off};
+            hp[s] = &hc[s];
+            m->last_hp[s][0] = U - n_fresh;
+            m->last_hp[s][1] = n_fresh;
+        }
+    }
     if (!cached && !stored_pd && n_img == S && n_pd == S && n_side[0] == B && n_side[1] == B) return A3R_OK;
     m->last_side_merged[0] = n_side[0] < B;
     m->last_side_merged[1] = n_side[1] < B;
@@ -1546,6 +1654,8 @@ int find_distinct(a3r_model_s* m, const float* a1, const float* a2, long words_a
           {n_side[0], n_side[1]}, {list_dev + 4 * DD_HALF, list_dev + 4 * DD_HALF + B}, {list_dev + 5 * DD_HALF, list_dev + 5 * DD_HALF + B},
           n_ent, list_dev + 6 * DD_HALF, list_dev + 7 * DD_HALF, list_dev + 8 * DD_HALF, list_dev + 9 * DD_HALF, cached ? cc : nullptr,
           stored_pd ? pc : nullptr};
+    d->hp[0] = hp[0];
+    d->hp[1] = hp[1];
     *use = true;
     return A3R_OK;
 }
@@ -1604,7 +1714,8 @@ extern "C" int a3r_model_forward(a3r_model_t m, const float* img1, const float* 
     bool merge = false;
     CacheCall cc;
     PriorCall pc;
-    int rc = find_distinct(m, img1, img2, 3L * H * W, true, pd1, pd2, B, H, W, stream, &d, &merge, &cc, &pc);
+    HeadCall hc[2];
+    int rc = find_distinct(m, img1, img2, 3L * H * W, true, pd1, pd2, B, H, W, stream, &d, &merge, &cc, &pc, hc);
     Call k;
     k.phase = 0; k.B = B; k.H = H; k.W = W;
     k.img[0] = img1; k.img[1] = img2; k.pd[0] = pd1; k.pd[1] = pd2;
@@ -1670,7 +1781,7 @@ extern "C" size_t a3r_model_frame_cache_bytes(a3r_model_t m, int H, int W, int f
 
 extern "C" int a3r_model_set_frame_cache(a3r_model_t m, void* buf, size_t bytes) {
     A3R_CHECK_ARG(m, "a3r_model_set_frame_cache: null handle");
-    m->fc_table.reset(0);
+    m->reset_frames(0);
     m->pd_table.reset(0);
     m->fc_buf = nullptr;
     m->fc_bytes = 0;
@@ -1714,6 +1825,32 @@ extern "C" int a3r_model_last_frame_products(a3r_model_t m, int* hits, int* miss
     *hits = m->last_pd[0];
     *misses = m->last_pd[1];
     *evictions = m->last_pd[2];
+    return A3R_OK;
+}
+
+extern "C" size_t a3r_model_head_products_bytes(a3r_model_t m, int H, int W, int frames) {
+    if (!m || H <= 0 || W <= 0 || H % 16 || W % 16 || frames <= 0 || frames > FC_MAX_ENTRIES) return 0;
+    return (size_t)frames * head_products_entry_bytes(head_words(m->cfg, H, W));
+}
+
+extern "C" int a3r_model_set_head_products(a3r_model_t m, void* buf, size_t bytes) {
+    A3R_CHECK_ARG(m, "a3r_model_set_head_products: null handle");
+    m->hp_bits.flush();
+    m->hp_buf = nullptr;
+    m->hp_bytes = 0;
+    if (!buf || !bytes) return A3R_OK;
+    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "a3r_model_set_head_products: storage must be 256-byte aligned");
+    m->hp_buf = buf;
+    m->hp_bytes = bytes;
+    return A3R_OK;
+}
+
+extern "C" int a3r_model_last_head_products(a3r_model_t m, int* hits, int* misses) {
+    A3R_CHECK_ARG(m && hits && misses, "a3r_model_last_head_products: null argument");
+    for (int s = 0; s < 2; s++) {
+        hits[s] = m->last_hp[s][0];
+        misses[s] = m->last_hp[s][1];
+    }
     return A3R_OK;
 }
 

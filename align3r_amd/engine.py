@@ -20,16 +20,19 @@ from .weights import ModelConfig, param_spec
 
 class PairEngine:
     def __init__(self, cfg: ModelConfig, state_dict: Dict[str, "torch.Tensor | np.ndarray"], device="cuda:0", frame_cache=32,
-                 frame_products=True):
+                 frame_products=True, head_products=True):
         """frame_cache: frames whose encoder rows the handle keeps across forward calls (include/a3r.h, a3r_model_set_frame_cache),
         0 = none; the environment variable A3R_FRAME_CACHE overrides it.  The storage (about 5.5 MB per frame at 512x384) is
         allocated at the first forward of a resolution.
         frame_products: keep as many depth priors with their zero-conv rows beside it (a3r_model_set_frame_products, about 14 MB
-        per prior at 512x384); A3R_FRAME_PRODUCTS=0 overrides it.  Without memory for them the engine runs with the frame cache alone."""
+        per prior at 512x384); A3R_FRAME_PRODUCTS=0 overrides it.  Without memory for them the engine runs with the frame cache alone.
+        head_products: keep what the DPT heads make of a frame alone for as many frames (a3r_model_set_head_products, about 50 MB
+        per frame at 512x384); A3R_HEAD_PRODUCTS=0 overrides it.  Without memory for them the engine runs without that storage."""
         self.lib = _lib.load()
         self.frame_cache = max(0, min(256, int(os.environ.get("A3R_FRAME_CACHE", frame_cache))))
         self.frame_products = bool(frame_products) and os.environ.get("A3R_FRAME_PRODUCTS", "1") != "0"
-        self._fc_store, self._fc_hw, self._fp_store = None, None, None
+        self.head_products = bool(head_products) and os.environ.get("A3R_HEAD_PRODUCTS", "1") != "0"
+        self._fc_store, self._fc_hw, self._fp_store, self._hp_store = None, None, None, None
         self.cfg = cfg
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -171,7 +174,8 @@ class PairEngine:
         by forward at the first call of a resolution; a call by hand fixes the capacity until the resolution changes."""
         check(self.lib.a3r_model_set_frame_cache(self.handle, None, 0), "a3r_model_set_frame_cache")
         check(self.lib.a3r_model_set_frame_products(self.handle, None, 0), "a3r_model_set_frame_products")
-        self._fc_store, self._fc_hw, self._fp_store = None, None, None
+        check(self.lib.a3r_model_set_head_products(self.handle, None, 0), "a3r_model_set_head_products")
+        self._fc_store, self._fc_hw, self._fp_store, self._hp_store = None, None, None, None
         self.frame_cache = int(frames)
         if not self.frame_cache:
             return
@@ -185,6 +189,8 @@ class PairEngine:
         self._fc_store, self._fc_hw = store, (H, W)
         if self.frame_products and H and W:
             self.set_frame_products(int(self.lib.a3r_model_frame_products_bytes(self.handle, H, W, self.frame_cache)))
+        if self.head_products and H and W:
+            self.set_head_products(int(self.lib.a3r_model_head_products_bytes(self.handle, H, W, self.frame_cache)))
 
     def set_frame_products(self, nbytes):
         """Storage of nbytes bytes for the frame products kept across forward calls; 0 removes it.  Called with the frame cache's
@@ -200,6 +206,28 @@ class PairEngine:
             return
         check(self.lib.a3r_model_set_frame_products(self.handle, ptr(store), int(nbytes)), "a3r_model_set_frame_products")
         self._fp_store = store
+
+    def set_head_products(self, nbytes):
+        """Storage of nbytes bytes for the head products kept across forward calls; 0 removes it.  Called with the frame cache's
+        entry count by set_frame_cache; when the device has no memory for it the engine goes on without."""
+        check(self.lib.a3r_model_set_head_products(self.handle, None, 0), "a3r_model_set_head_products")
+        self._hp_store = None
+        if not nbytes:
+            return
+        try:
+            with torch.cuda.device(self.device):
+                store = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        except torch.cuda.OutOfMemoryError:
+            return
+        check(self.lib.a3r_model_set_head_products(self.handle, ptr(store), int(nbytes)), "a3r_model_set_head_products")
+        self._hp_store = store
+
+    def last_head_products(self):
+        """((hits, misses) of side 1, (hits, misses) of side 2) of the last forward among the distinct frames of each side's head;
+        zeros for a side that ran without that storage."""
+        h, m = (C.c_int * 2)(), (C.c_int * 2)()
+        check(self.lib.a3r_model_last_head_products(self.handle, h, m), "a3r_model_last_head_products")
+        return (h[0], m[0]), (h[1], m[1])
 
     def last_frame_cache(self):
         """(hits, misses, evictions) of the last forward among its distinct images; zeros when it ran without the frame cache."""

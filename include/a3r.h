@@ -369,6 +369,16 @@ int a3r_combine_resid_fh2(const float* c, const float* r0, const float* p2, cons
 /* the same with p2 = a3r_upsample2x(x [S, H, W, C], window Hc x Wc) made inside the kernel and never written; P = Hc Wc */
 int a3r_upsample2x_combine_fh2(const float* x, const float* c, const float* r0, const int32_t* map, float* s, void* sr2, int S, int H,
                                int W, int C, int Hc, int Wc, float scale, unsigned* absmax, void* stream);
+/* The two combine passes with c and r0 in two places (stored head products, a3r_model_set_head_products): src [S] (device) is a
+ * signed source per slot -- src[b] >= 0: the blocks at store_c / store_r0 + src[b] * stride floats; src[b] < 0: the blocks ~src[b]
+ * of c / r0 [., P, C].  stride >= P C, stride % 4 == 0.  The pair (c, r0) or the pair (store_c, store_r0) may be NULL when src
+ * never names it.  Arithmetic, rounding order and statistics are those of the calls above: only where the two loads go differs. */
+int a3r_combine_resid_fh2_src(const float* c, const float* r0, const float* store_c, const float* store_r0, long stride,
+                              const int32_t* src, const float* p2, float* s, void* sr2, int S, long P, int C, float scale,
+                              unsigned* absmax, void* stream);
+int a3r_upsample2x_combine_fh2_src(const float* x, const float* c, const float* r0, const float* store_c, const float* store_r0,
+                                   long stride, const int32_t* src, float* s, void* sr2, int S, int H, int W, int C, int Hc, int Wc,
+                                   float scale, unsigned* absmax, void* stream);
 /* The residual add of a linear layer that ran on distinct rows only (the decoder's level 0 and zero-convs, a3r_model_set_dedup_decoder):
  * blocks of N rows of C floats, dst [S] = a[map_a[s]] + b[map_b[s]], or with b NULL dst[s] += a[map_a[s]] in place.  fp32; maps on
  * the device; C % 4 == 0, 16-byte aligned buffers. */
@@ -520,6 +530,26 @@ int a3r_model_last_frame_cache(a3r_model_t m, int* hits, int* misses, int* evict
 size_t a3r_model_frame_products_bytes(a3r_model_t m, int H, int W, int frames);
 int a3r_model_set_frame_products(a3r_model_t m, void* buf, size_t bytes);
 int a3r_model_last_frame_products(a3r_model_t m, int* hits, int* misses, int* evictions);
+/* Head products kept across calls: a third, optional storage, indexed by the FRAME CACHE's entries, for what the DPT head of a
+ * side makes from one frame alone -- the level-0 branch of a3r_model_set_dedup_head: adapter, 4x transposed conv, layer_rn[0] and
+ * the two convs of refinenet1.resConfUnit1.  Per entry and side it holds r0 (the output of layer_rn[0]) and c (the bias-only output
+ * of the second conv), [16 N, feature_dim] fp32 each, and 4 KB of words: 50.3 MB per entry at 512 x 384 with ViT-L heads.  It has no
+ * lookup of its own -- the image lookup already says which entry a distinct image is -- and the handle keeps one valid bit per
+ * (entry, side), cleared when the frame cache fills or replaces the entry.  A side whose head merges (the admission rule of
+ * a3r_model_set_dedup_head, unchanged, as is a3r_model_last_dedup_sides) runs the branch on those of its distinct frames whose bit
+ * is not set, stores their r0 and c where the frame has an entry, and the combine pass reads every slot's c and r0 where they lie:
+ * nothing stored is copied.  A side whose every frame is stored launches nothing of the branch.  A side that does not merge neither
+ * reads nor writes the storage.  Outputs are bitwise those of a handle without it; sites, scales and the workspace requirement do
+ * not change; the branch's statistics words follow the frame cache's rule, with words of their own per (entry, side).
+ * The storage is used only while a frame cache is installed and it has room for as many entries as that has at the call's
+ * resolution (a3r_model_head_products_bytes(m, H, W, frames) with the same `frames`); a smaller one is ignored and never written.
+ * It is dropped and bypassed exactly where the frame cache is, not used outside the default fh2 arithmetic, and not used by
+ * a3r_model_decode.  buf: device memory, 256-byte aligned, the caller's; NULL or bytes == 0 removes it.
+ * a3r_model_last_head_products: per side s, hits[s] / misses[s] = distinct frames of the side's head in the last forward that were
+ * stored / were computed (both 0 for a side that did not use the storage). */
+size_t a3r_model_head_products_bytes(a3r_model_t m, int H, int W, int frames);
+int a3r_model_set_head_products(a3r_model_t m, void* buf, size_t bytes);
+int a3r_model_last_head_products(a3r_model_t m, int hits[2], int misses[2]);
 /* Debug taps for the parity tests: intermediate tensors inside the workspace after a forward; returns device pointer + element
  * count.  name: "feat" (enc_norm output, model.py:163), "hook_a" / "hook_b" (the decoder levels the DPT head reads,
  * dpt_head.py:101), "dec_last" (dec_norm output, model.py:231-232); after a3r_model_set_tap_level(m, L > 0) also "level" (the two
