@@ -277,6 +277,8 @@ SIGNATURES = {
     "a3r_render_points": (C.c_int, [c_void, c_void, C.c_longlong, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, c_void,
                                     c_void, C.c_size_t, c_void, c_void, c_void, c_void]),
     "a3r_render_set_form": (C.c_int, [C.c_int]),
+    "a3r_track_points": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, C.c_int, c_void, c_void, C.c_int, C.c_int,
+                                   c_void, C.c_longlong, C.c_double, c_void, c_void, c_void, c_void, c_void]),
 }
 
 _lib = None

@@ -535,6 +535,104 @@ class PointCloudOptimizer:
             out['xyz_' + name] = xyz[lo:hi][k]
         return out
 
+    # ------------------------------------------------------------------ motion: tracks and scene flow (csrc/track.hip)
+    def _own_flow(self):
+        """(flow_ij, flow_ji) of the scene's edges when the scene holds them (the flow class does), else None."""
+        return None
+
+    def _track(self, steps, seeds, fb_thr, min_conf_thr, mask_dynamic, flow, who):
+        """ops.track_points on the scene: xyz = engine.points(), keep = the rule of get_pointcloud() (conf > thr and, with
+        mask_dynamic, outside the dynamic masks; the finite test is the tracker's own), flow = (flow_ij, flow_ji) aligned with
+        self.edges.  steps [C,S,4]; returns the dict of ops.track_points."""
+        from ... import ops
+        if not self._uniform:
+            raise RuntimeError(f'{who}: the scene holds images of more than one shape; flow fields are stacked [E,2,H,W] and a track '
+                               'keeps one pixel grid through all frames')
+        if flow is None:
+            flow = self._own_flow()
+        if flow is None:
+            raise RuntimeError(f'{who}: this scene holds no optical flow; pass flow=(flow_ij, flow_ji), each [E,2,H,W] in the order of '
+                               'scene.edges (the flow aligner with flow_loss_weight > 0 keeps its own)')
+        (H, W), E, N = self.imshapes[0], len(self.edges), self.n_imgs
+        flow = [torch.as_tensor(f) for f in flow]
+        for f, name in zip(flow, ('flow_ij', 'flow_ji')):
+            if f.numel() != E * 2 * H * W:
+                raise ValueError(f'{who}: {name} holds {f.numel()} values, not [E,2,H,W] = [{E},2,{H},{W}]')
+        e = self._need_engine()
+        dev = e.device
+        fields = [f.to(dev, torch.float32).reshape(E, 2, H, W).contiguous() for f in flow]      # the scene's own fields: no copy
+        conf, thr, dyn, _ = self._scene_out_inputs(min_conf_thr, mask_dynamic, who)
+        keep = conf > thr
+        if dyn is not None:
+            keep &= dyn == 0
+        if seeds is not None:
+            seeds = torch.as_tensor(np.asarray(seeds.detach().cpu() if torch.is_tensor(seeds) else seeds, dtype=np.float32))
+            if seeds.dim() != 2 or seeds.shape[1] != 2:
+                raise ValueError(f'{who}: seeds are (x, y) rows [M,2], got {tuple(seeds.shape)}')
+            seeds = seeds.to(dev).contiguous()
+        return ops.track_points(e.points().view(N, H, W, 3), keep.view(N, H, W).contiguous(), fields[0], fields[1], steps, seeds=seeds,
+                                fb_thr=fb_thr)
+
+    def _check_frames(self, frames, who):
+        frames = [int(f) for f in frames]
+        for f in frames:
+            if not 0 <= f < self.n_imgs:
+                raise IndexError(f'{who}: image {f} is outside the scene of {self.n_imgs} images')
+        return frames
+
+    def get_tracks(self, frames=None, seeds=None, fb_thr=3.0, min_conf_thr=None, mask_dynamic=False, flow=None):
+        """3-D trajectories: the points at `seeds` ([M,2] (x, y) positions in image frames[0]; None = every pixel) followed through
+        `frames` (None = all images in order; any order along edges of the graph, see tool/tracks.py: plan_steps) by the optical
+        flow of the edges, and read off the aligned point maps (ops.track_points, csrc/track.hip; include/a3r.h has the definition).
+        A track ends where it leaves the image or where forward and backward flow disagree by fb_thr pixels or more.  Dict of device
+        tensors with T = len(frames): xy [T,M,2] float32 positions, xyz [T,M,3] float32 world points, pix [T,M] int32 = row * W + col
+        of the pixel read (-1 = ended), state [T,M] uint8 (2 = visible: the pixel is one get_pointcloud(min_conf_thr, mask_dynamic)
+        keeps and xyz is its point; 1 = followed, not visible; 0 = ended), and frames.  flow = (flow_ij, flow_ji) [E,2,H,W] in the
+        order of scene.edges; the flow aligner uses its own fields."""
+        from ...tool.tracks import plan_steps
+        frames = self._check_frames(range(self.n_imgs) if frames is None else frames, 'get_tracks')
+        if len(frames) < 2:
+            raise ValueError('get_tracks: a track needs at least two frames')
+        out = self._track(plan_steps(self.edges, frames)[None], seeds, fb_thr, min_conf_thr, mask_dynamic, flow, 'get_tracks')
+        out = {k: v[0] for k, v in out.items()}
+        out['frames'] = frames
+        return out
+
+    def get_scene_flow(self, i=None, j=None, fb_thr=3.0, min_conf_thr=None, mask_dynamic=False, flow=None):
+        """Scene flow from image i to image j (two images joined by an edge): every pixel of i followed one step and the two point
+        maps subtracted.  Dict of device tensors: flow3d [H,W,3] float32 = xyz_j(target) - xyz_i(pixel), zeros where not valid;
+        valid [H,W] bool = the pixel is visible in i, its track reaches j (inside the image, forward and backward flow agree within
+        fb_thr) and lands on a visible pixel (state 2 of get_tracks at both ends); target_xy [H,W,2] float32 and target_pix [H,W]
+        int32 (-1 where the track ended).  Without i and j: every edge of the graph in one launch, the same tensors stacked on a
+        leading axis in the order of scene.edges, and edges."""
+        from ...tool.tracks import plan_steps
+        if (i is None) != (j is None):
+            raise ValueError('get_scene_flow: pass both images or neither (neither = every edge of the graph)')
+        if i is None:
+            steps = np.asarray([[(a, b, e, 0)] for e, (a, b) in enumerate(self.edges)], np.int32).reshape(len(self.edges), 1, 4)
+        else:
+            i, j = self._check_frames((i, j), 'get_scene_flow')
+            if i == j:
+                raise ValueError(f'get_scene_flow: i == j == {i}: motion needs two images')
+            steps = plan_steps(self.edges, (i, j))[None]
+        t = self._track(steps, None, fb_thr, min_conf_thr, mask_dynamic, flow, 'get_scene_flow')
+        H, W = self.imshapes[0]
+        valid = (t['state'][:, 0] == 2) & (t['state'][:, 1] == 2)
+        flow3d = torch.where(valid[..., None], t['xyz'][:, 1] - t['xyz'][:, 0], torch.zeros((), device=valid.device))
+        out = dict(flow3d=flow3d.view(-1, H, W, 3), valid=valid.view(-1, H, W), target_xy=t['xy'][:, 1].reshape(-1, H, W, 2),
+                   target_pix=t['pix'][:, 1].reshape(-1, H, W))
+        if i is None:
+            out['edges'] = list(self.edges)
+            return out
+        return {k: v[0] for k, v in out.items()}
+
+    def save_tracks(self, path, **kw):
+        """get_tracks(**kw) written as an npz of host arrays (tool/tracks.py: write_tracks_npz); returns the dict."""
+        from ...tool.tracks import write_tracks_npz
+        tr = self.get_tracks(**kw)
+        write_tracks_npz(path, tr)
+        return tr
+
     def clean_pointcloud(self, tol=0.001, bad_conf=0, dbg=()):
         """base_opt.py:268-278: lower the confidence of points that another, more confident view sees through.  Computed by the
         aligner handle from its own state (csrc/scene.hip, AlignEngine.clean_confidences): the decisions are those of the

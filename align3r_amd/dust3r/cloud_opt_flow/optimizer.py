@@ -333,6 +333,12 @@ class PointCloudOptimizer(_Base):
     def _mask_confidences(self):
         return self.init_conf_maps if self.thr_for_init_conf else self.im_conf
 
+    def _own_flow(self):
+        """The fields the flow term reads: the engine's device tensors [E,2,P] once it is built (get_tracks / get_scene_flow view
+        them as [E,2,H,W] without a copy), before that the fields the constructor was given or computed."""
+        held = getattr(self.engine, 'flow', None) or self._flow
+        return None if held is None else (held['flow_ij'], held['flow_ji'])
+
     @property
     def flow_loss_flag(self):
         return self._need_engine().flow_dropped

@@ -794,3 +794,54 @@ def render_points(xyz, rgb=None, w2c=None, K=None, shape=None, radius=0, near=1e
     if index is not None:
         out["index"] = index
     return out
+
+
+def track_points(xyz, keep, flow_a, flow_b, steps, seeds=None, fb_thr=3.0):
+    """Points followed through a clip by chaining optical-flow fields, read off the point maps at every frame they pass
+    (a3r_track_points, csrc/track.hip; include/a3r.h has the definition: float64 bilinear samples, a track ends where it leaves the
+    image or where forward and backward flow disagree by fb_thr pixels or more, the pixel by half-to-even rounding -- bitwise the
+    numpy restatement).  xyz [N,H,W,3] float32, keep [N,H,W] uint8 or bool, flow_a / flow_b [E,2,H,W] float32: contiguous device
+    tensors.  steps [C,S,4] (or [S,4]: one chain) integers, rows (frame_from, frame_to, edge, reversed): a host array, or a tensor
+    anywhere (a device tensor is read back once for the entry checks).  seeds [M,2] float32 device tensor of (x, y), or None =
+    every pixel.  Enqueue-only; returns a dict of device tensors xy [C,S+1,M,2] float32, xyz [C,S+1,M,3] float32, pix [C,S+1,M]
+    int32 and state [C,S+1,M] uint8 (2 = visible, 1 = followed but not visible, 0 = ended)."""
+    _req(xyz, "xyz"); _req(flow_a, "flow_a"); _req(flow_b, "flow_b")
+    dev = xyz.device
+    if xyz.dim() != 4 or xyz.shape[3] != 3:
+        raise RuntimeError(f"track_points: xyz is [N,H,W,3], got {tuple(xyz.shape)}")
+    N, H, W = xyz.shape[:3]
+    if not (isinstance(keep, torch.Tensor) and keep.device == dev and keep.dtype in (torch.uint8, torch.bool) and keep.is_contiguous()
+            and tuple(keep.shape) == (N, H, W)):
+        raise RuntimeError("track_points: keep must be a contiguous uint8 or bool tensor [N,H,W] on xyz's device")
+    if keep.dtype == torch.bool:
+        keep = keep.view(torch.uint8)
+    if not (flow_a.device == flow_b.device == dev and flow_a.dim() == 4 and tuple(flow_a.shape[1:]) == (2, H, W)
+            and flow_b.shape == flow_a.shape):
+        raise RuntimeError(f"track_points: flow_a / flow_b are [E,2,{H},{W}] on xyz's device, got {tuple(flow_a.shape)} and "
+                           f"{tuple(flow_b.shape)}")
+    E = flow_a.shape[0]
+    st = steps.detach().cpu().numpy() if isinstance(steps, torch.Tensor) else np.asarray(steps)
+    if st.ndim == 2:
+        st = st[None]
+    if st.ndim != 3 or st.shape[2] != 4 or st.dtype.kind not in "iu":
+        raise ValueError(f"track_points: steps is an integer array [C,S,4] or [S,4], got {st.dtype} {st.shape}")
+    if st.size and (st.min() < -(1 << 31) or st.max() >= (1 << 31)):
+        raise ValueError("track_points: a step entry does not fit int32")
+    st = np.ascontiguousarray(st, dtype=np.int32)
+    Cn, S = st.shape[:2]
+    if seeds is not None:
+        _req(seeds, "seeds")
+        if seeds.device != dev or seeds.dim() != 2 or seeds.shape[1] != 2:
+            raise RuntimeError(f"track_points: seeds is [M,2] on xyz's device, got {tuple(seeds.shape)}")
+    M = H * W if seeds is None else seeds.shape[0]
+    lib = _lib.load()
+    ok = Cn * (S + 1) * M < (1 << 31)                      # otherwise the call below refuses before it reads the outputs
+    lead = (Cn, S + 1, M) if ok else (0, 0, 0)
+    out = dict(xy=torch.empty(lead + (2,), dtype=torch.float32, device=dev), xyz=torch.empty(lead + (3,), dtype=torch.float32, device=dev),
+               pix=torch.empty(lead, dtype=torch.int32, device=dev), state=torch.empty(lead, dtype=torch.uint8, device=dev))
+    st_dev = torch.from_numpy(st.reshape(-1).copy()).to(dev) if st.size else None
+    with torch.cuda.device(dev):
+        check(lib.a3r_track_points(ptr(xyz), ptr(keep), N, H, W, ptr(flow_a), ptr(flow_b), E, ptr(st_dev), st.ctypes.data if st.size else None,
+                                   Cn, S, ptr(seeds), M, float(fb_thr), ptr(out["xy"]), ptr(out["xyz"]), ptr(out["pix"]), ptr(out["state"]),
+                                   stream_ptr()), "track_points")
+    return out                                            # the device copy of the steps is freed stream-ordered after the kernel

@@ -7,11 +7,14 @@ The flow of the reference's tool/demo.py and tool/depth_test.py through this pac
     ->  --pointcloud PATH: the aligned scene as a binary PLY (points above --min-conf-thr, compacted on the device)
     ->  --matches DIR: matches_{i}_{i+1}.npz, the reciprocal 3-D nearest-neighbour pixel correspondences of consecutive frames
     ->  --render DIR: render_XXXX.png, the whole aligned scene drawn from every frame's own camera (z-buffered point splats)
+    ->  --flow --tracks PATH.npz: a grid of points of one frame followed through all later frames (3-D trajectories)
+    ->  --flow --scene-flow DIR: scene_flow_{i}_{i+1}.npz, the 3-D motion of every pixel between consecutive frames
 
     python -m align3r_amd.tool.run_clip --images DIR --weights CKPT.pth --out OUT [--size 512] [--scene-graph swin-3-noncyclic]
            [--hierarchical --clip-size 50] [--niter 300] [--schedule linear] [--lr 0.01] [--traj-format custom] [--gt-depth DIR]
            [--metrics-device] [--pointcloud scene.ply] [--matches DIR] [--render DIR [--render-radius R]] [--clean] [--device-prep]
-           [--flow [--flow-weights RAFT.pth] [--gt-masks DIR] [--not-shared-focal]]
+           [--flow [--flow-weights RAFT.pth] [--gt-masks DIR] [--not-shared-focal]
+                   [--tracks PATH.npz [--track-start K] [--track-stride G]] [--scene-flow DIR]]
            [--flow-hierarchical [--clip-size 10] [--device-resident] [--flow-weights ...] [--gt-masks DIR] [--not-shared-focal]]
 
 --flow is the sequence of the reference's tool/pose_test.py:154-216: the flow-regularised aligner (cloud_opt_flow) with self-computed
@@ -77,6 +80,19 @@ def parse(argv=None):
                          "scene holds all frames at once")
     ap.add_argument("--render-radius", type=int, default=None, metavar="R",
                     help="--render: a point covers (2 R + 1)^2 pixels, R in [0, 8] (default 1)")
+    ap.add_argument("--tracks", default=None, metavar="PATH.npz",
+                    help="--flow: after the alignment (and after --clean) follow a grid of points of frame --track-start through all later "
+                         "frames by the optical flow of consecutive frames and write their 3-D trajectories (scene.get_tracks, "
+                         "csrc/track.hip; keys xy xyz pix state frames; state 2 = on a pixel above --min-conf-thr, 1 = followed but not "
+                         "visible, 0 = ended; dynamic pixels are NOT masked out: moving points are what a track is for). "
+                         "Refused with --hierarchical and --flow-hierarchical: their clips are aligned one after another and no "
+                         "scene holds all frames at once")
+    ap.add_argument("--track-start", type=int, default=None, metavar="K", help="--tracks: the frame the grid is seeded in (default 0)")
+    ap.add_argument("--track-stride", type=int, default=None, metavar="G", help="--tracks: a seed every G pixels (default 8)")
+    ap.add_argument("--scene-flow", default=None, metavar="DIR",
+                    help="--flow: after the alignment (and after --clean) write DIR/scene_flow_{i}_{i+1}.npz for every consecutive frame "
+                         "pair: the 3-D motion vector of every pixel (scene.get_scene_flow; keys flow3d valid target_xy target_pix). "
+                         "Refused with --hierarchical and --flow-hierarchical like --tracks")
     ap.add_argument("--clean", action="store_true",
                     help="scene.clean_pointcloud() after every alignment: confidences of points another, more confident view sees through "
                          "drop to 0 before conf_X.npy and --pointcloud are written (tool/demo.py: clean_depth)")
@@ -106,6 +122,20 @@ def parse(argv=None):
         ap.error("--matches cannot be combined with --hierarchical or --flow-hierarchical: it needs one scene holding all frames")
     if a.render and (a.hierarchical or a.flow_hierarchical):
         ap.error("--render cannot be combined with --hierarchical or --flow-hierarchical: it needs one scene holding all frames")
+    for given, name in ((a.tracks, "--tracks"), (a.scene_flow, "--scene-flow")):
+        if given and (a.hierarchical or a.flow_hierarchical):
+            ap.error(f"{name} cannot be combined with --hierarchical or --flow-hierarchical: it needs one scene holding all frames")
+        if given and not a.flow:
+            ap.error(f"{name} needs --flow: tracks and scene flow follow the optical flow the flow aligner holds")
+    for given, name in ((a.track_start, "--track-start"), (a.track_stride, "--track-stride")):
+        if given is not None and not a.tracks:
+            ap.error(f"{name} belongs to --tracks")
+    a.track_start = 0 if a.track_start is None else a.track_start
+    a.track_stride = 8 if a.track_stride is None else a.track_stride
+    if a.track_start < 0:
+        ap.error("--track-start is a frame number >= 0")
+    if a.track_stride < 1:
+        ap.error("--track-stride is at least 1")
     if a.render_radius is not None and not a.render:
         ap.error("--render-radius belongs to --render")
     if a.render_radius is None:
@@ -142,6 +172,28 @@ def write_matches(scene, out_dir, mask_dynamic=False):
     return counts
 
 
+def write_tracks(scene, path, start=0, stride=8):
+    """A grid of seeds every `stride` pixels of frame `start`, followed through all later frames (scene.save_tracks); returns the
+    number of tracks."""
+    from .tracks import grid_seeds
+    if not 0 <= start < scene.n_imgs - 1:
+        raise RuntimeError(f"--track-start {start}: a track needs a later frame (the clip has {scene.n_imgs})")
+    tr = scene.save_tracks(path, frames=range(start, scene.n_imgs), seeds=grid_seeds(scene.imshapes[start], stride))
+    return int(tr["state"].shape[1])
+
+
+def write_scene_flow(scene, out_dir):
+    """scene.get_scene_flow(i, i + 1) for every consecutive pair as out_dir/scene_flow_{i}_{i+1}.npz (host arrays); returns the
+    numbers of valid pixels."""
+    os.makedirs(out_dir, exist_ok=True)
+    counts = []
+    for i in range(scene.n_imgs - 1):
+        f = scene.get_scene_flow(i, i + 1)
+        np.savez(os.path.join(out_dir, f"scene_flow_{i}_{i + 1}.npz"), **{k: v.cpu().numpy() for k, v in f.items()})
+        counts.append(int(f["valid"].sum()))
+    return counts
+
+
 def main(argv=None):
     a = parse(argv)
     from ..dust3r.cloud_opt import GlobalAlignerMode, global_aligner
@@ -164,6 +216,7 @@ def main(argv=None):
     meshes, n_mesh = ([] if a.mesh else None), None              # n_mesh: (vertices, faces) written
     n_matches = None                   # --matches: matches written per consecutive pair
     n_renders = None                   # --render: pictures written
+    n_tracks, n_scene_flow = None, None          # --tracks: tracks written; --scene-flow: valid pixels per consecutive pair
     depths_dev = None                  # --metrics-device: the aligned depth maps as the scene holds them, on the device
     if a.flow_hierarchical and len(imgs) < 3:
         raise RuntimeError("--flow-hierarchical needs at least 3 frames")
@@ -231,6 +284,10 @@ def main(argv=None):
             if mode != GlobalAlignerMode.PointCloudOptimizer:
                 raise RuntimeError("--render needs at least 3 frames (the two-frame PairViewer has no aligner handle to export from)")
             n_renders = len(scene.save_renders(a.render, mask_dynamic=a.flow, radius=a.render_radius))
+        if a.tracks:                         # both need --flow, and --flow three frames or more: the scene is the flow aligner's
+            n_tracks = write_tracks(scene, a.tracks, a.track_start, a.track_stride)
+        if a.scene_flow:
+            n_scene_flow = write_scene_flow(scene, a.scene_flow)
         if a.mesh:
             if mode != GlobalAlignerMode.PointCloudOptimizer:
                 raise RuntimeError("--mesh needs at least 3 frames (the two-frame PairViewer has no aligner handle to export from)")
@@ -264,6 +321,10 @@ def main(argv=None):
         res_out["matches"], res_out["n_matches"] = a.matches, n_matches
     if a.render:
         res_out["render"], res_out["n_renders"] = a.render, n_renders
+    if a.tracks:
+        res_out["tracks"], res_out["n_tracks"] = a.tracks, n_tracks
+    if a.scene_flow:
+        res_out["scene_flow"], res_out["n_scene_flow_valid"] = a.scene_flow, n_scene_flow
     if a.mesh:
         res_out["mesh"], res_out["n_vertices"], res_out["n_faces"] = a.mesh, n_mesh[0], n_mesh[1]
     return res_out

@@ -1066,6 +1066,50 @@ int a3r_render_points(const float* xyz, const unsigned char* rgb, long long M, c
                       void* stream);
 int a3r_render_set_form(int form);
 
+/* Tracks and scene flow (csrc/track.hip): points followed through a clip by chaining the optical-flow fields of the scene's edges,
+ * read off the aligned point maps at every frame they pass.  The reference has no such output (it computes the forward-backward
+ * consistency of its flows, OccMask of dust3r/utils/goem_opt.py, stores it and never reads it); this text is the specification.
+ * Inputs, all images of one shape H x W:
+ *     xyz [N,H,W,3] fp32 world points, keep [N,H,W] uint8 (non-zero = the pixel counts)
+ *     flow_a, flow_b [E,2,H,W] fp32: the flow of every edge in both directions (the scene's flow_ij / flow_ji); channel 0 = x, 1 = y
+ *     steps [C,S,4] int32: C chains of S steps, each row (frame_from, frame_to, edge, reversed); the forward field of a step is
+ *         reversed ? flow_b[edge] : flow_a[edge] and its backward field the other one
+ *     seeds [M,2] fp32 (x, y) positions shared by all chains, or NULL = every pixel: M = H * W, x = m % W, y = m / W
+ *     fb_thr: the forward-backward threshold in pixels (inf switches the check off)
+ * All arithmetic is float64 on float64 copies of the fp32 inputs, every operation rounded on its own (no fused multiply-add).
+ *     bilinear(F, x, y) for 0 <= x <= W - 1, 0 <= y <= H - 1:
+ *         x0 = floor(x), x1 = min(x0 + 1, W - 1), ax = x - x0;   y0, y1, ay likewise
+ *         top = F[y0,x0] + ax * (F[y0,x1] - F[y0,x0]),   bot likewise on row y1,   val = top + ay * (bot - top)
+ *         (at integer coordinates and finite neighbours this is exactly F[y0,x0])
+ * A track starts at (x, y) = its seed and is alive iff both coordinates are finite and inside [0, W-1] x [0, H-1].  It is recorded
+ * at t = 0 in frame steps[c,0].frame_from (frame 0 when S = 0).  Then, for every step s:
+ *     1. f = bilinear(fwd, x, y);  xn = x + f.x, yn = y + f.y.  The track ends unless xn, yn are finite and inside the image (the
+ *        out-of-bounds rule of OccMask).
+ *     2. b = bilinear(bwd, xn, yn);  dx = f.x + b.x, dy = f.y + b.y.  The track ends unless dx * dx + dy * dy < fb_thr * fb_thr (a
+ *        NaN ends it).  This DIFFERS from OccMask on purpose: OccMask tests |dx + dy| < th, the absolute value of the SUM of the
+ *        two components, which passes a pixel whose x and y errors cancel (dx = 10, dy = -10); the rule here is the Euclidean
+ *        length of the disagreement.
+ *     3. Otherwise (x, y) = (xn, yn) and the track is recorded at t = s + 1 in frame_to.
+ * An ended track stays ended.  record(t, n) of a living track:
+ *     col = rint(x), row = rint(y), half to even (as a3r_render_points rounds);  pix = row * W + col;  xy[t] = ((float)x, (float)y)
+ *     state = 2 if keep[n,pix] is set and the three coordinates of xyz[n,pix] are finite, and then xyz[t] = xyz[n,pix];
+ *     state = 1 otherwise (followed, not visible), xyz[t] = 0
+ * and of an ended one: state 0, pix -1, xy and xyz zeros.  Outputs (planar: at every t the tracks are contiguous):
+ *     out_xy [C,S+1,M,2] fp32, out_xyz [C,S+1,M,3] fp32, out_pix [C,S+1,M] int32, out_state [C,S+1,M] uint8
+ * Scene flow is the case S = 1 with NULL seeds: xyz[1] - xyz[0] where state 2 holds at both ends.
+ * Contract: the outputs are bitwise those of the numpy restatement (tests/track_cases.py: track_ref) and the same from call to
+ * call.  One kernel, one thread per (chain, track) with the steps in a loop; no atomics, no LDS; nothing is allocated,
+ * synchronised or read back, so the call can be captured into a graph.  steps_dev: the steps in device memory; steps_host: the
+ * same table in host memory, validated before anything is launched.  `stream` is a hipStream_t, passed as void*.
+ * A3R_EINVAL before anything is launched, naming the argument: a non-positive H or W, H * W >= 2^31, N <= 0, a negative E, C or S,
+ * M < 0 or M >= 2^31, NULL seeds with M neither H * W nor 0, C * (S + 1) * M >= 2^31, fb_thr NaN or negative; then, unless M = 0 or C = 0
+ * (a success that writes nothing): a null xyz, keep or output, and with S > 0 a null flow field or step table, a frame_from or
+ * frame_to outside [0, N), an edge outside [0, E), reversed outside {0, 1}, a frame_from that is not the frame_to of the step
+ * before it. */
+int a3r_track_points(const float* xyz, const unsigned char* keep, int N, int H, int W, const float* flow_a, const float* flow_b, int E,
+                     const int* steps_dev, const int* steps_host, int C, int S, const float* seeds, long long M, double fb_thr,
+                     float* out_xy, float* out_xyz, int* out_pix, unsigned char* out_state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
