@@ -178,10 +178,6 @@ int frame_cache_lookup(const float* img1, const float* img2, int B, const void* 
 // ent[k] when that is >= 0.
 int frame_cache_exchange(const float* img1, const float* img2, int B, const void* keys, const FrameCacheLayout& l, const int32_t* uniq,
                          const int32_t* ent, const int32_t* miss, int U, const float* fresh, float* rows, void* stream);
-// The statistics words [lo, hi) of the call: stored with every entry the call filled, then raised to the largest word of the
-// entries it hit.
-int frame_cache_stats(const FrameCacheLayout& l, const int32_t* ent, const int32_t* miss, int U, unsigned* stats, int lo, int hi,
-                      void* stream);
 
 // ---- frame products kept across calls (a3r_model_set_frame_products): what the plan makes from one depth prior alone -- the
 // outputs z_0 .. z_n of the zero-convs -- in a second storage of the same layout (the `feat` of an entry: the levels' [N, D] rows
@@ -222,10 +218,9 @@ inline int prior_lists(const int32_t* hit, const int32_t* ent, const int32_t* un
 // item itself (slot uniq[k] of img1 / img2) and its key go to the entry.
 int frame_cache_store(const float* img1, const float* img2, int B, const void* keys, const FrameCacheLayout& l, const int32_t* uniq,
                       const int32_t* ent, const int32_t* miss, int U, const float* fresh, long part_off, long part_words, void* stream);
-// frame_cache_stats on the words of `sites`
-int frame_cache_stats_sites(const FrameCacheLayout& l, const int32_t* ent, const int32_t* miss, int U, unsigned* stats,
-                            const SiteMask& sites, void* stream);
-// the same on words given directly: estats [cap][FC_STAT_WORDS] (the head products' words of one side)
+// The statistics words `sites` of the call, for any of the stores: estats [cap][FC_STAT_WORDS] are the entries' words (a
+// FrameCacheLayout's `stats`, or the head products' words of one side).  The call's words are stored with every entry it filled
+// (miss[k] >= 0, ent[k] >= 0), then raised to the largest word of the entries it read (miss[k] < 0).
 int stats_sites_words(unsigned* estats, int cap, const int32_t* ent, const int32_t* miss, int U, unsigned* stats, const SiteMask& sites,
                       void* stream);
 // a3r_gather_add_rows whose rows a come from two places (a3r.h: a3r_gather_add_rows_src is the same with a C signature)
@@ -329,5 +324,182 @@ int combine_resid_fh2(const float* c, const float* r0, const float* p2, const in
 // the same with p2 = the bilinear 2x (a3r_upsample2x, cropped to Hc x Wc) of x [S, H, W, C] made on the fly; P = Hc Wc
 int upsample2x_combine_fh2(const float* x, const float* c, const float* r0, const int32_t* map, float* s, void* sr2, int S, int H, int W,
                            int C, int Hc, int Wc, float scale, unsigned* absmax, void* stream);
+
+// ---- the lists of one call.  Every list the host builds, in the order they lie in memory: one block of DD_HALF-word lists, which
+// the host fills (pinned words) and one upload copies to the device; both blocks are viewed through this struct, so a member of
+// the device view is the device address of that list.  The lists of the two sides (uniq_side, map_side, hp_*) share one member:
+// side s's B words start at word s B.
+constexpr int DD_HALF = DEDUP_MAX_SLOTS / 2;                       // slots of one kind at most
+struct CallLists {
+    using List = int32_t[DD_HALF];
+    List uniq_img, map_img, uniq_pd, map_pd;         // dedup_group of the two kinds
+    List uniq_side, map_side;                        // dedup_group_side, [2][B]
+    List ent_img, ent_pd, map_eo, map_ekv;           // decoder block 0 on entries (dedup_group_entries; model.hip, Distinct)
+    List fc_fresh, fc_ent, fc_miss;                  // the frame cache: the images to encode, FrameCacheTable::assign's entries
+    List pd_fresh, pd_ent, pd_miss, pd_src, pd_src_ent;      // the stored priors (prior_lists); src_ent [2 n_ent]: src of the entries' priors
+    List hp_ent, hp_miss, hp_fresh, hp_src;          // the head products (head_lists), [2][B]
+};
+constexpr int DD_LISTS = sizeof(CallLists) / sizeof(CallLists::List);
+static_assert(sizeof(CallLists) == (size_t)DD_LISTS * DD_HALF * sizeof(int32_t), "CallLists is its lists and nothing else");
+
+// Bytes of a head's level-0 buffers with n images of N tokens in them, as the arena rounds them: a0, l0, l03, r0, r0r3; the merged
+// branch adds the compact enc_norm rows and the bias-only output c of resConfUnit1's second conv.  fh2 maps take 4 bytes per
+// element.  E, F, l: enc_embed_dim, feature_dim, layer_dims[0].
+inline size_t head_level0_bytes(int E, int F, int l, int N, int n, bool merged) {
+    const size_t px = (size_t)n * N, f = F;
+    const size_t fl[7] = {px * l, px * 16 * l, px * 16 * l, px * 16 * f, px * 16 * f, px * E, px * 16 * f};
+    size_t b = 0;
+    for (int i = 0; i < (merged ? 7 : 5); i++) b += (fl[i] * 4 + 255) / 256 * 256;
+    return b;
+}
+// A side with U distinct frames merges when its level-0 buffers fit in what the plain plan reserves for them, so that the
+// workspace requirement does not move: U (33 l + 48 F + E) <= B (33 l + 32 F) up to rounding, U <= 0.69 B for ViT-L heads
+// (l = 96, F = 256, E = 1024).
+inline bool head_merge_fits(int E, int F, int l, int N, int B, int U) {
+    return U > 0 && U < B && head_level0_bytes(E, F, l, N, U, true) <= head_level0_bytes(E, F, l, N, B, false);
+}
+
+// What the planner is told about a call, in plain numbers.  rep [4 B]: dedup_find's representatives of the two kinds; flag: its
+// mismatch word; hit_img / hit_pd [2 B]: frame_cache_lookup's answers for the image / pred_depth slots, null when that store was
+// not looked up in this call (absent, or bypassed).
+struct CallInputs {
+    const int32_t* rep; int32_t flag; const int32_t *hit_img, *hit_pd;
+    int B, H, W;
+    int E, D, F, l0;                 // enc_embed_dim, dec_embed_dim, feature_dim, layer_dims[0]
+    bool encode, first_kind;         // a forward from images (they are merged for the encoder too); the first kind was looked at
+    bool dedup_head, dedup_decoder;  // a3r_model_set_dedup_head, a3r_model_set_dedup_decoder
+    bool gemm_fh2, map_fh2;          // the GEMM inputs / the DPT maps are fh2
+    bool attn_maps;                  // attention_fh2_takes_maps()
+    bool heads;                      // a head-products storage with room for every entry of the frame cache is installed
+};
+// What the planner decided: the counts a3r_model_last_* report, and what the plan runs on.
+struct CallPlan {
+    bool use = false;                // the plan runs on the lists; else the plain plan
+    bool fell_back = false;          // a slot differs from its representative, or a list is not what it must be
+    bool drop = false;               // the tables no longer describe the storage: forget everything stored
+    int n_img, n_pd;                 // distinct images / priors (2 B: that kind is not merged)
+    int side_unique[2];              // distinct frames of each side, and whether its head merges on them (n_side < B)
+    int n_side[2], side_merged[2] = {0, 0};
+    int n_ent = 0, ent_unique[2];    // decoder block 0: entries per side, padded (0: per slot); each side's distinct entries
+    // the stores this call uses, what it runs (fresh) and keeps (store) of each, and hits, misses, evictions
+    bool fc = false, pd = false, hp[2] = {false, false};
+    int fc_fresh = 0, fc_store = 0, pd_fresh = 0, pd_store = 0, hp_fresh[2] = {0, 0}, hp_store[2] = {0, 0};
+    int fc_n[3] = {0, 0, 0}, pd_n[3] = {0, 0, 0};
+    explicit CallPlan(int B = 0) : n_img(2 * B), n_pd(2 * B), side_unique{B, B}, n_side{B, B}, ent_unique{B, B} {}
+    int hp_hits(int s) const { return hp[s] ? n_side[s] - hp_fresh[s] : 0; }
+    int hp_misses(int s) const { return hp[s] ? hp_fresh[s] : 0; }
+};
+
+// The host's part of a call, between the one read-back and the one upload: groups the slots, asks the tables of the three stores
+// for entries, and fills L.  The tables change as the call will change the storage; a call that falls back before it touches
+// them leaves them as they were.
+inline CallPlan plan_call(const CallInputs& in, FrameCacheTable& fc_table, FrameCacheTable& pd_table, HeadBits& hp_bits, CallLists& L) {
+    const int B = in.B, S = 2 * B;
+    const int32_t* rep = in.rep;
+    CallPlan p(B);
+    if (in.flag != 0) {
+        p.fell_back = true;
+        return p;
+    }
+    // the distinct frames' enc_norm rows must fit the buffers they wait in (run_plan)
+    auto rows_fit = [&](int n) { return (size_t)n * in.E <= 3 * (size_t)S * in.D; };
+    int n_img = S;
+    if (in.encode && in.first_kind) {
+        n_img = dedup_group(rep, S, L.uniq_img, L.map_img);
+        if (n_img > 0 && !rows_fit(n_img)) n_img = S;
+    }
+    // the heads' level-0 branch: each side's own distinct frames
+    if (in.first_kind && in.dedup_head && in.map_fh2)
+        for (int s = 0; s < 2; s++) {
+            const int u = dedup_group_side(rep, B, s, L.uniq_side + s * B, L.map_side + s * B);
+            if (u <= 0) { n_img = 0; break; }
+            p.side_unique[s] = u;
+            if (head_merge_fits(in.E, in.F, in.l0, (in.H / 16) * (in.W / 16), B, u)) p.n_side[s] = u;
+        }
+    const int n_pd = dedup_group(rep + S, S, L.uniq_pd, L.map_pd);
+    if (n_img <= 0 || n_pd <= 0) {       // not a representative table: cannot happen, and is not trusted if it does
+        p = CallPlan(B);
+        p.fell_back = true;
+        return p;
+    }
+    p.n_img = n_img;
+    p.n_pd = n_pd;
+    // decoder block 0: each side's distinct (image, prior) entries, when both kinds merge (fh2 GEMM inputs, the attention form with maps)
+    int n_ent = 0;
+    if (in.dedup_decoder && in.gemm_fh2 && in.attn_maps && n_img < S && n_pd < S) {
+        int32_t ent[DD_HALF], map_e[DD_HALF];
+        const int um = dedup_group_entries(L.map_img, L.map_pd, B, ent, map_e, p.ent_unique);      // (-1: it wrote nothing)
+        // The statistic of an fh2 GEMM output covers the whole last row tile: rows past M are copies of the last row, rotated at
+        // their own RoPE positions.  The q / k / v projections keep the plain plan's statistics bit for bit only where neither
+        // plan has such rows: both row counts whole multiples of the largest row tile (256).
+        const long N = (long)(in.H / 16) * (in.W / 16);
+        if (um > 0 && um < B && (B * N) % 256 == 0 && (um * N) % 256 == 0) {
+            n_ent = um;
+            for (int s = 0; s < 2; s++) {
+                for (int e = 0; e < um; e++) {
+                    L.ent_img[s * um + e] = L.map_img[ent[s * B + e]];
+                    L.ent_pd[s * um + e] = L.map_pd[ent[s * B + e]];
+                }
+                for (int b = 0; b < B; b++) {
+                    L.map_eo[s * B + b] = s * um + map_e[s * B + b];
+                    L.map_ekv[s * B + b] = s * um + map_e[(1 - s) * B + b];
+                }
+            }
+        }
+    }
+    p.n_ent = n_ent;
+    // The frame cache: hits and misses among the distinct images, victims for the misses (FrameCacheTable::assign), the lists of
+    // the exchange pass.  It needs the image stage on the distinct list, whose rows must fit where they wait (above).
+    p.fc = in.hit_img && rows_fit(n_img);
+    if (p.fc) {
+        for (int k = 0; k < n_img; k++) L.fc_miss[k] = in.hit_img[L.uniq_img[k]];
+        p.fc = fc_table.assign(L.fc_miss, n_img, L.fc_ent, p.fc_n) == 0;
+    }
+    if (p.fc)
+        for (int k = 0; k < n_img; k++) {
+            const bool hit = L.fc_miss[k] >= 0;
+            if (!hit) {
+                L.fc_fresh[p.fc_fresh] = L.uniq_img[k];
+                p.fc_store += L.fc_ent[k] >= 0;
+                hp_bits.clear(L.fc_ent[k]);      // the entry now holds another frame: what the heads made of the old one is stale
+            }
+            L.fc_miss[k] = hit ? -1 : p.fc_fresh++;
+        }
+    // The stored priors: hits, misses and victims among the distinct pred_depth maps, and the lists of the prior branch
+    if (in.hit_pd) {
+        int32_t hit[DD_HALF];
+        for (int k = 0; k < n_pd; k++) hit[k] = in.hit_pd[L.uniq_pd[k]];
+        p.pd = pd_table.assign(hit, n_pd, L.pd_ent, p.pd_n) == 0;
+        if (p.pd) {
+            p.pd_fresh = prior_lists(hit, L.pd_ent, L.uniq_pd, n_pd, L.pd_miss, L.pd_fresh, L.map_pd, S, L.pd_src, &p.pd_store);
+            if (p.pd_fresh < 0) {               // (never: map_pd is dedup_group's)
+                p.drop = p.fell_back = true;
+                return p;
+            }
+            for (int i = 0; i < 2 * n_ent; i++) L.pd_src_ent[i] = L.pd_src[L.uniq_pd[L.ent_pd[i]]];      // ent_pd names distinct priors
+        }
+    }
+    // The head products: which of a merging side's distinct frames are stored, and the lists of its level-0 branch.  They ride on
+    // the frame cache (its entries, dropped and bypassed with it); a side that does not merge neither reads nor writes them.
+    if (p.fc && in.heads && in.map_fh2 && in.gemm_fh2)
+        for (int s = 0; s < 2; s++) {
+            if (p.n_side[s] >= B) continue;
+            const int off = s * B, U = p.n_side[s];
+            int32_t row[DD_HALF];
+            for (int k = 0; k < U; k++) row[k] = L.map_img[L.uniq_side[off + k]];
+            p.hp_fresh[s] = head_lists(hp_bits, s, L.fc_ent, L.fc_miss, n_img, row, L.uniq_side + off, U, L.map_side + off, B, L.hp_ent + off,
+                                       L.hp_miss + off, L.hp_fresh + off, L.hp_src + off, &p.hp_store[s]);
+            if (p.hp_fresh[s] < 0) {            // (never: the lists are dedup_group's and assign's)
+                p.drop = p.fell_back = true;
+                return p;
+            }
+            p.hp[s] = true;
+        }
+    if (!p.fc && !p.pd && n_img == S && n_pd == S && p.n_side[0] == B && p.n_side[1] == B) return p;      // nothing to merge
+    p.side_merged[0] = p.n_side[0] < B;
+    p.side_merged[1] = p.n_side[1] < B;
+    p.use = true;
+    return p;
+}
 
 }  // namespace a3r

@@ -317,27 +317,12 @@ int head_products_store(const HeadStore& hs, int s, const int32_t* hent, const i
 
 int stats_sites_words(unsigned* estats, int cap, const int32_t* ent, const int32_t* miss, int U, unsigned* stats, const SiteMask& sites,
                       void* stream) {
-    A3R_CHECK_ARG(estats && cap > 0 && cap <= FC_MAX_ENTRIES && ent && miss && stats && U > 0, "frame_cache_stats: bad argument");
+    A3R_CHECK_ARG(estats && cap > 0 && cap <= FC_MAX_ENTRIES && ent && miss && stats && U > 0, "stats_sites_words: bad argument");
     hipStream_t st = as_stream(stream);
     ProfScope prof(PK_ELEMENTWISE, 4.0 * FC_STAT_WORDS * (U + 2), st);
     hipLaunchKernelGGL(fc_stats_sites_kernel, dim3(FC_STAT_WORDS / 256), dim3(256), 0, st, estats, ent, miss, U, stats, sites);
     A3R_LAUNCH_CHECK();
     return A3R_OK;
-}
-
-int frame_cache_stats_sites(const FrameCacheLayout& l, const int32_t* ent, const int32_t* miss, int U, unsigned* stats,
-                            const SiteMask& sites, void* stream) {
-    A3R_CHECK_ARG(fc_layout_ok(l) && l.stats, "frame_cache_stats: bad argument");
-    return stats_sites_words(reinterpret_cast<unsigned*>(l.stats), l.cap, ent, miss, U, stats, sites, stream);
-}
-
-int frame_cache_stats(const FrameCacheLayout& l, const int32_t* ent, const int32_t* miss, int U, unsigned* stats, int lo, int hi,
-                      void* stream) {
-    A3R_CHECK_ARG(lo >= 0 && lo <= hi && hi <= FC_STAT_WORDS, "frame_cache_stats: bad argument (sites %d .. %d)", lo, hi);
-    if (hi == lo) return A3R_OK;
-    SiteMask sites;
-    sites.add(lo, hi);
-    return frame_cache_stats_sites(l, ent, miss, U, stats, sites, stream);
 }
 
 int dedup_find(const float* img1, const float* img2, const float* pd1, const float* pd2, int B, long words_a, long words_pd, int first,
@@ -374,5 +359,7 @@ extern "C" int a3r_frame_cache_stats_sites(void* storage, size_t bytes, int64_t 
     A3R_CHECK_ARG(storage && site_mask && words_item > 0 && words_rows > 0, "a3r_frame_cache_stats_sites: bad argument");
     a3r::SiteMask sites;
     for (int i = 0; i < a3r::FC_STAT_WORDS / 32; i++) sites.w[i] = site_mask[i];
-    return a3r::frame_cache_stats_sites(a3r::frame_cache_layout(storage, bytes, words_item, words_rows), ent, miss, U, stats, sites, stream);
+    const a3r::FrameCacheLayout l = a3r::frame_cache_layout(storage, bytes, words_item, words_rows);
+    A3R_CHECK_ARG(a3r::fc_layout_ok(l) && l.stats, "a3r_frame_cache_stats_sites: bad argument");
+    return a3r::stats_sites_words(reinterpret_cast<unsigned*>(l.stats), l.cap, ent, miss, U, stats, sites, stream);
 }

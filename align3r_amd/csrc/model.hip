@@ -70,41 +70,45 @@ struct a3r_model_s {
     // duplicate inputs (dedup.h; a3r_model_set_dedup): 0 = every slot is encoded, 1 = the frame-only parts of the plan run once per
     // distinct image / pred_depth map of the batch, 2 = as 1 with a constant key (debugging: the verification alone decides)
     int dedup_mode = 1;
-    int last_img_unique = 0, last_pd_unique = 0, last_fell_back = 0;      // a3r_model_last_dedup
     // a3r_model_set_dedup_head: the DPT heads' level-0 branch runs once per distinct frame of a side (run_plan, HeadMerge)
     int dedup_head = 1;
     int dedup_head_fold = 1;         // A/B switch (A3R_DEDUP_HEAD_FOLD=0): 0 = the combine runs as a pass of its own after the 2x up-sample
-    int last_side_unique[2] = {0, 0}, last_side_merged[2] = {0, 0};      // a3r_model_last_dedup_sides
     // a3r_model_set_dedup_decoder: decoder_embed, the zero-convs and block 0's frame-only half on distinct rows (decoder_stage)
     int dedup_decoder = 1;
-    int last_ent_unique[2] = {0, 0}, last_ent_merged = 0;                 // a3r_model_last_dedup_entries
+    // what the planner decided for the last forward or decode call (dedup.h): the counts that a3r_model_last_dedup, _sides,
+    // _entries, a3r_model_last_frame_cache, _frame_products and _head_products report
+    CallPlan last;
     // the handle's own small buffers (the only device memory it allocates, at its first merging call): keys, representatives and
-    // flag, the uploaded lists (uniq_img, map_img, uniq_pd, map_pd, the two sides' uniq, the two sides' map: DEDUP_MAX_SLOTS / 2
-    // words each), and the pinned host words of
-    // the one read-back and the one upload of a call
+    // flag, the uploaded lists (CallLists), and the pinned host words of the one read-back and the one upload of a call
     void* dd_dev = nullptr;
     int32_t* dd_host = nullptr;
+    // A storage the caller installs for what is kept across calls: device memory, 256-byte aligned, the caller's
+    struct Storage {
+        void* buf = nullptr;
+        size_t bytes = 0;
+        int set(void* b, size_t n, const char* who) {      // (null or no bytes: removes it)
+            buf = nullptr;
+            bytes = 0;
+            if (!b || !n) return A3R_OK;
+            A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(b) & 255) == 0, "%s: storage must be 256-byte aligned", who);
+            buf = b;
+            bytes = n;
+            return A3R_OK;
+        }
+    };
     // frames kept across calls (a3r_model_set_frame_cache): the caller's storage, the host table of its entries (dedup.h) and the
-    // resolution they were stored at; what the last forward did with it (a3r_model_last_frame_cache: hits, misses, evictions)
-    void* fc_buf = nullptr;
-    size_t fc_bytes = 0;
+    // resolution they were stored at
+    Storage fc;
     FrameCacheTable fc_table;
     int fc_H = 0, fc_W = 0;
-    int last_fc[3] = {0, 0, 0};
     // frame products kept across calls (a3r_model_set_frame_products): the caller's second storage, which holds as many depth priors
-    // with their zero-conv outputs as the frame cache holds frames, the table of those entries, and what the last forward did
-    // with it (a3r_model_last_frame_products: hits, misses, evictions)
-    void* fp_buf = nullptr;
-    size_t fp_bytes = 0;
+    // with their zero-conv outputs as the frame cache holds frames, and the table of those entries
+    Storage fp;
     FrameCacheTable pd_table;
-    int last_pd[3] = {0, 0, 0};
     // head products kept across calls (a3r_model_set_head_products): the caller's third storage, indexed by the frame cache's
-    // entries, one valid bit per (entry, side) (dedup.h), and what the last forward did with it per side
-    // (a3r_model_last_head_products: hits, misses among the distinct frames of a merging side)
-    void* hp_buf = nullptr;
-    size_t hp_bytes = 0;
+    // entries, one valid bit per (entry, side) (dedup.h)
+    Storage hp;
     HeadBits hp_bits;
-    int last_hp[2][2] = {{0, 0}, {0, 0}};
     // the frame cache's table emptied or resized: the head products' bits name its entries
     void reset_frames(int capacity) {
         fc_table.reset(capacity);
@@ -485,15 +489,24 @@ extern "C" int a3r_model_finalize(a3r_model_t m, void* packed, size_t packed_byt
 // ------------------------------------------------------------------------------------------- launch plan
 namespace {
 
-// Head products kept across calls (null: none are): the level-0 branch of side s's head runs on the n_fresh distinct frames of the
-// side that are not stored, uniq_fresh [n_fresh] (slots, device); frame k < n_side[s] is entry hent[k]'s when hmiss[k] < 0, else
-// the hmiss[k]-th of those, whose r0 and c go to entry hent[k] when that is >= 0 (n_store of them do).  src [B]: where the combine
-// pass finds the c and r0 of a slot (head_lists).
-// With n_fresh == 0 the branch's ops are walked muted on one frame's rows, as the encoder's and the prior branch's are.
-struct HeadCall {
-    HeadStore st; int n_fresh, n_store; const int32_t *uniq_fresh, *hent, *hmiss, *src;
-    int frames() const { return n_fresh ? n_fresh : 1; }      // frames the branch's ops are walked with
+// What one of the stores kept across calls does in a call (device lists; dedup.h, CallLists).  The branch whose products are kept
+// runs on the n_fresh distinct items that are not stored, uniq_fresh [n_fresh] (slots); item k of the call's U distinct ones is
+// entry ent[k]'s when miss[k] < 0, else the miss[k]-th of those, whose products go to entry ent[k] when that is >= 0 (n_store of
+// them do).  src: where the pass that consumes the products finds those of a slot, in an entry (>= 0) or among the fresh blocks
+// (~j) (prior_lists, head_lists; null for the frame cache, whose exchange pass reads ent / miss).
+// With n_fresh == 0 the branch's ops are walked muted (Plan::mute) on one item's rows.
+struct StoreCall {
+    int n_fresh, n_store; const int32_t *uniq_fresh, *ent, *miss, *src;
+    int frames() const { return n_fresh ? n_fresh : 1; }      // items the branch's ops are walked with
 };
+// the frame cache (images, U = n_img) and the stored priors (pred_depth maps, U = n_pd; src [2 B], src_ent [2 n_ent]: the z rows
+// of a slot / of a block-0 entry): the storage as entries, and the call's keys of that kind
+struct FrameCall : StoreCall {
+    FrameCacheLayout lay; const void* keys; const int32_t* src_ent;
+    unsigned* stat_words() const { return reinterpret_cast<unsigned*>(lay.stats); }      // [cap][FC_STAT_WORDS]
+};
+// the head products of one side (U = n_side[s], src [B]: the c and r0 of a slot)
+struct HeadCall : StoreCall { HeadStore st; };
 
 struct Plan {
     a3r_model_s* m;
@@ -506,8 +519,9 @@ struct Plan {
     // mute: the ops are walked -- allocations, sites and their scales as ever -- but launch nothing (the encoder stage of a call
     // whose every frame was found in the frame cache)
     bool mute = false;
-    SiteMask prior_sites;      // the sites of the depth-prior branch, whose words the stored priors complete (PriorScope)
-    SiteMask head_sites[2];    // the sites of each head's level-0 branch, whose words the stored head products complete (HeadScope)
+    // the sites of the branches whose products are kept across calls (StoreScope), whose words the entries read complete: the
+    // encoder's, the depth-prior branch's, the level-0 branch's of each head
+    SiteMask enc_sites, prior_sites, head_sites[2];
     // ---- fh2 range control: every op that WRITES an fh2 tensor is a site (numbered in plan order) with its own power-of-two
     // scale; the scale travels with the buffer pointer to the ops that read it
     int phase = 0, site_no = 0;
@@ -757,17 +771,19 @@ void rcu_map(Plan& P, const RcuW& w, const float* x, const float* xr3, const flo
 // hc (head products kept across calls, side `side`): the branch runs on the hc->n_fresh frames of the U that are not stored -- the
 // buffers keep their size, fewer rows of them are used -- and the combine pass reads every slot's c and r0 where hc->src says.
 struct HeadMerge { int U; const int32_t* map; bool fold; const float* x0_lo; int lo_h, lo_w; const HeadCall* hc; int side; };
-// The ops of a head's level-0 branch walked while one of these lives: launched on the fresh frames' rows, or not at all
-// (Plan::mute) when every frame of the side is stored, and their sites noted for the statistics pass of head_stage (as PriorScope)
-struct HeadScope {
+// The ops of a branch whose products store `sc` keeps (null: none does), walked while one of these lives: launched on the fresh
+// items' rows, or not at all (Plan::mute) when every item is stored, and their sites noted in `sites` for the statistics pass
+// that follows the branch (stats_sites_words)
+struct StoreScope {
     Plan& P;
-    const HeadCall* hc;
-    int side, lo;
-    HeadScope(Plan& P_, const HeadCall* hc_, int s) : P(P_), hc(hc_), side(s), lo(P_.site_no) { if (hc) P.mute = hc->n_fresh == 0; }
-    ~HeadScope() {
-        if (!hc) return;
+    const StoreCall* sc;
+    SiteMask& sites;
+    int lo;
+    StoreScope(Plan& P_, const StoreCall* sc_, SiteMask& sites_) : P(P_), sc(sc_), sites(sites_), lo(P_.site_no) { if (sc) P.mute = sc->n_fresh == 0; }
+    ~StoreScope() {
+        if (!sc) return;
         P.mute = false;
-        P.head_sites[side].add(lo, P.site_no);
+        sites.add(lo, P.site_no);
     }
 };
 static bool dpt_ref_order() {       // A/B switch: up-sample first, as the reference does
@@ -797,11 +813,11 @@ float* fusion_map(Plan& P, const FusionW& w, const float* x0, const float* x0r3,
             const HeadCall* hc = hm->hc;
             const int Uf = hc ? hc->frames() : hm->U;
             {
-                HeadScope scope(P, hc, hm->side);
+                StoreScope scope(P, hc, P.head_sites[hm->side]);
                 rcu_conv1(P, w.r1, x1r3, tmp3, Uf, H, W, F);
                 P.conv(tmp3, w.r1.c2w, c, Uf, H, W, F, F, 1, P.epi(A3R_EPI_NONE, w.r1.c2b));
             }
-            if (hc && hc->n_store && !P.skip()) P.rc = head_products_store(hc->st, hm->side, hc->hent, hc->hmiss, hm->U, x1, c, P.stream);
+            if (hc && hc->n_store && !P.skip()) P.rc = head_products_store(hc->st, hm->side, hc->ent, hc->miss, hm->U, x1, c, P.stream);
             if (hm->fold) P.up_combine_map(hm->x0_lo, c, x1, hm->map, s, sr3, B, hm->lo_h, hm->lo_w, F, H, W, hc, hm->side);
             else P.combine_map(c, x1, x0, hm->map, s, sr3, B, (long)H * W, F, hc, hm->side);
         } else
@@ -846,56 +862,22 @@ struct Distinct {
     // [2 Um] the image / prior row of each side's entries, map_eo [2 B] the row s Um + e of slot (s, b)'s entry e among the 2 Um, and
     // map_ekv [2 B] that of the other side's slot b inside side s's block, s Um + map_e[1 - s][b]: where slot (s, b)'s keys live
     int n_ent; const int32_t *ent_img, *ent_pd, *map_eo, *map_ekv;
-    // Frames kept across calls (null: none are): the encoder runs on the n_miss images uniq_miss [n_miss] that were not found
-    // (slots, device), and image k < n_img takes its enc_norm rows from entry ent[k] when miss[k] < 0, else the miss[k]-th
-    // encoded image's, which go to entry ent[k] when that is >= 0 (frame_cache_exchange).  The image stage then runs on the
-    // distinct list even when that holds all 2 B slots.
-    const struct CacheCall* fc = nullptr;
+    // Frames kept across calls (null: none are): the encoder runs on the images that were not found, and image k < n_img takes
+    // its enc_norm rows from its entry or from the encoded ones, which go to their entries (frame_cache_exchange).  The image
+    // stage then runs on the distinct list even when that holds all 2 B slots.
+    const FrameCall* fc = nullptr;
     // Depth priors kept across calls with their zero-conv outputs (null: none are): the prior branch -- patch embedding,
-    // dec_blocks_pc, zero-convs -- runs on the n_miss priors uniq_miss [n_miss] that were not found (slots inside the kind, device);
-    // prior k < n_pd is entry ent[k]'s when miss[k] < 0, else the miss[k]-th of those, whose z rows and map go to entry ent[k]
-    // when that is >= 0 (n_store of them do).  src [2 B] / src_ent [2 n_ent]: where the gather-add pass finds the z rows of a
-    // slot / of a block-0 entry (prior_lists).  The prior stage then runs on the distinct list even when that holds all 2 B slots.
-    const struct PriorCall* pp = nullptr;
+    // dec_blocks_pc, zero-convs -- runs on the priors that were not found, whose z rows and map go to their entries; the
+    // gather-add pass finds the z rows where src / src_ent say.  The prior stage then runs on the distinct list even when that
+    // holds all 2 B slots.
+    const FrameCall* pp = nullptr;
     // Head products kept across calls, per side (null: that side's head computes its level-0 branch for all its n_side[s] frames)
     const HeadCall* hp[2] = {nullptr, nullptr};
-};
-struct CacheCall { FrameCacheLayout lay; const void* keys; int n_miss; const int32_t *uniq_miss, *ent, *miss; };
-struct PriorCall { FrameCacheLayout lay; const void* keys; int n_miss, n_store; const int32_t *uniq_miss, *ent, *miss, *src, *src_ent; };
-
-// The ops of the prior branch walked while one of these lives: launched on the misses' rows, or not at all (Plan::mute) when the
-// call found every prior, and their sites noted for the statistics pass that ends decoder_stage
-struct PriorScope {
-    Plan& P;
-    const PriorCall* pp;
-    int lo;
-    PriorScope(Plan& P_, const PriorCall* pp_) : P(P_), pp(pp_), lo(P_.site_no) { if (pp) P.mute = pp->n_miss == 0; }
-    ~PriorScope() {
-        if (!pp) return;
-        P.mute = false;
-        P.prior_sites.add(lo, P.site_no);
-    }
 };
 // the sizing pass: counts, no lists
 Distinct distinct_counts(int n_img, int n_pd, int n_side) {
     return {n_img, n_pd, nullptr, nullptr, nullptr, nullptr, {n_side, n_side}, {nullptr, nullptr}, {nullptr, nullptr}, 0, nullptr, nullptr,
             nullptr, nullptr};
-}
-
-// Bytes of a head's level-0 buffers with n images in them, as the arena rounds them: a0, l0, l03, r0, r0r3; the merged branch adds
-// the compact enc_norm rows and the bias-only output c of resConfUnit1's second conv.  fh2 maps take 4 bytes per element.
-size_t head_level0_bytes(const a3r_model_config& c, int N, int n, bool merged) {
-    const size_t px = (size_t)n * N, F = c.feature_dim, l = c.layer_dims[0];
-    const size_t fl[7] = {px * l, px * 16 * l, px * 16 * l, px * 16 * F, px * 16 * F, px * c.enc_embed_dim, px * 16 * F};
-    size_t b = 0;
-    for (int i = 0; i < (merged ? 7 : 5); i++) b += align_up(fl[i] * 4, 256);
-    return b;
-}
-// A side with U distinct frames merges when its level-0 buffers fit in what the plain plan reserves for them, so that the
-// workspace requirement does not move: U (33 l + 48 F + E) <= B (33 l + 32 F) up to rounding, U <= 0.69 B for ViT-L heads
-// (l = 96, F = 256, E = 1024).
-bool head_merge_fits(const a3r_model_config& c, int N, int B, int U) {
-    return U > 0 && U < B && head_level0_bytes(c, N, U, true) <= head_level0_bytes(c, N, B, false);
 }
 
 // ---- one call of the plan.  phase: 0 = whole forward from images; 1 = encoder only (img[0] [B,...] -> feat_out [B,N,E]);
@@ -924,8 +906,8 @@ struct Dims {
     int B, H, W, E, D, F, L, nh, nw, N, BN, M2;
     bool d_img, d_pd;
     int Mi, Mp;
-    const PriorCall* pp;      // the stored priors of this call, and the rows the prior branch then runs on (one image's when muted)
-    int prior_rows() const { return !pp ? Mp : pp->n_miss ? pp->n_miss * N : N; }
+    const FrameCall* pp;      // the stored priors of this call, and the rows the prior branch then runs on (one image's when muted)
+    int prior_rows() const { return pp ? pp->frames() * N : Mp; }
     Dims(const a3r_model_config& c_, const Call& k)
         : c(c_), B(k.B), H(k.H), W(k.W), E(c.enc_embed_dim), D(c.dec_embed_dim), F(c.feature_dim), L(c.last_dim), nh(k.H / 16),
           nw(k.W / 16), N(nh * nw), BN(B * N), M2(2 * BN),
@@ -970,8 +952,8 @@ void encoder_stage(Plan& P, const Call& k, const Dims& g, float* cols, float* co
     float* hid = P.gin_alloc(M, hidden);
     if (!P.skip() && !P.mute) {
         const long sb = 3L * g.H * g.W, sc = (long)g.H * g.W, sy = g.W, sx = 1;
-        const CacheCall* fc = g.d_img ? k.dd->fc : nullptr;
-        if (fc) P.rc = patchify_indexed(k.img[0], k.img[1], fc->uniq_miss, fc->n_miss, g.B, cols, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
+        const FrameCall* fc = g.d_img ? k.dd->fc : nullptr;
+        if (fc) P.rc = patchify_indexed(k.img[0], k.img[1], fc->uniq_fresh, fc->n_fresh, g.B, cols, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
         else if (g.d_img) P.rc = patchify_indexed(k.img[0], k.img[1], k.dd->uniq_img, k.dd->n_img, g.B, cols, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
         else if (!(P.rc = a3r_patchify(k.img[0], cols, g.B, 3, g.H, g.W, sb, sc, sy, sx, P.stream)) && k.img[1])
             P.rc = a3r_patchify(k.img[1], cols + (size_t)g.BN * 768, g.B, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
@@ -999,13 +981,13 @@ void load_features(Plan& P, const Call& k, const Dims& g, float* feat) {
 // channel stride 1
 // With stored priors (g.pp) the rows are those of the priors not found, and their maps and keys go to their entries.
 void embed_pc_stage(Plan& P, const Call& k, const Dims& g, float* cols, float* cols3, float* pcu) {
-    const PriorCall* pp = g.pp;
+    const FrameCall* pp = g.pp;
     const int Mq = g.prior_rows();
     {
-        PriorScope scope(P, pp);
+        StoreScope scope(P, pp, P.prior_sites);
         if (!P.skip() && !P.mute) {
             const long sb = 3L * g.H * g.W, sc = 1, sy = 3L * g.W, sx = 3;
-            if (pp) P.rc = patchify_indexed(k.pd[0], k.pd[1], pp->uniq_miss, pp->n_miss, g.B, cols, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
+            if (pp) P.rc = patchify_indexed(k.pd[0], k.pd[1], pp->uniq_fresh, pp->n_fresh, g.B, cols, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
             else if (g.d_pd) P.rc = patchify_indexed(k.pd[0], k.pd[1], k.dd->uniq_pd, k.dd->n_pd, g.B, cols, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
             else if (!(P.rc = a3r_patchify(k.pd[0], cols, g.B, 3, g.H, g.W, sb, sc, sy, sx, P.stream)))
                 P.rc = a3r_patchify(k.pd[1], cols + (size_t)g.BN * 768, g.B, 3, g.H, g.W, sb, sc, sy, sx, P.stream);
@@ -1118,7 +1100,7 @@ void decoder_stage(Plan& P, const Call& k, const Dims& g, Levels& v) {
     const bool entries = l0_rows && k.dd->n_ent > 0;
     // Stored priors (g.pp; with or without the switch): the branch runs on the Mq rows of the priors not found, each zero-conv's fresh rows
     // z_i go to their entries, and the gather-add reads every slot's z_i where it lies, in an entry or among the fresh rows.
-    const PriorCall* pp = g.pp;
+    const FrameCall* pp = g.pp;
     const int Mq = g.prior_rows();
     const long zw = (long)g.N * D;                     // words of one z_i in an entry
     // x[s] = z_i[prior of s] + b[mb[s]] (b null: + x[s]) for S row blocks; mz / sz: the priors' rows in v.pc / their sources (pp)
@@ -1131,7 +1113,7 @@ void decoder_stage(Plan& P, const Call& k, const Dims& g, Levels& v) {
     // to all slots' rows first, so the zero-conv and its epilogue stay as they are)
     auto zero_conv_rows = [&](int i) {
         {
-            PriorScope scope(P, pp);
+            StoreScope scope(P, pp, P.prior_sites);
             P.linear(P.gin_from(v.pcu, pc3, Mq, D), D, m->zc_w[i], v.pc, D, Mq, D, D, P.epi(A3R_EPI_NONE, m->zc_b[i]));
         }
         if (pp && pp->n_store && !P.skip())
@@ -1165,7 +1147,7 @@ void decoder_stage(Plan& P, const Call& k, const Dims& g, Levels& v) {
         else decoder_block_pair(P, g, m->dec1[i], m->dec2[i], cur, nxt, t);
         if (i < npc) {   // model.py:223-226
             {
-                PriorScope scope(P, pp);
+                StoreScope scope(P, pp, P.prior_sites);
                 P.rows(Mq);
                 P.self_block(m->pc[i], v.pcu, v.pcu, Mq, D, c.dec_num_heads, g.N, g.nw, t.xn, t.qkv, t.att);
                 P.mlp(m->pc[i], m->pc[i].n2w, m->pc[i].n2b, v.pcu, Mq, D, hidden, t.xn, t.hid);
@@ -1179,7 +1161,7 @@ void decoder_stage(Plan& P, const Call& k, const Dims& g, Levels& v) {
         cur = nxt;
     }
     // the prior branch's statistics words: kept with the entries this call filled, completed from those it read
-    if (pp && !P.skip()) P.rc = frame_cache_stats_sites(pp->lay, pp->ent, pp->miss, k.dd->n_pd, m->stats, P.prior_sites, P.stream);
+    if (pp && !P.skip()) P.rc = stats_sites_words(pp->stat_words(), pp->lay.cap, pp->ent, pp->miss, k.dd->n_pd, m->stats, P.prior_sites, P.stream);
     P.ln_f32(cur, m->decn_w, m->decn_b, v.dec_last, M2, D);   // model.py:231-232
 }
 
@@ -1212,7 +1194,7 @@ void head_levels(Plan& P, const Call& k, const Dims& g, const Levels& v, int s, 
     const float* t0 = side(v.feat, E);
     float *a0, *l0;
     {
-        HeadScope scope(P, hc, s);
+        StoreScope scope(P, hc, P.head_sites[s]);
         if (B0 < B) {
             float* fu = ar.alloc(BN0 * E);
             if (!P.skip() && !P.mute)
@@ -1240,7 +1222,7 @@ void head_levels(Plan& P, const Call& k, const Dims& g, const Levels& v, int s, 
     P.conv(a33, Hd.a3cw, l[3], B, nh, nw, ld[3], ld[3], 2, e);
     l[0] = P.map_twin(l0, BN0 * 16, ld[0]);
     {
-        HeadScope scope(P, hc, s);
+        StoreScope scope(P, hc, P.head_sites[s]);
         P.split_map(l0, l[0], (long)R0 * 16, ld[0]);
     }
     l[1] = P.map_twin(l1, (size_t)BN * 4, ld[1]);
@@ -1276,7 +1258,7 @@ void head_stage(Plan& P, const Call& k, const Dims& g, const Levels& v, int s) {
     float* r3r3 = P.map_twin(r3, (size_t)B * h3 * w3, F);
     auto rn_epi = [&](float* twin) { OpEpi e = P.epi(A3R_EPI_NONE, nullptr); P.aux(e, twin, true); return e; };
     {
-        HeadScope scope(P, hc, s);
+        StoreScope scope(P, hc, P.head_sites[s]);
         P.conv(l[0], Hd.rn[0], r0, hc ? hc->frames() : B0, 4 * nh, 4 * nw, ld[0], F, 1, rn_epi(r0r3));
     }
     P.conv(l[1], Hd.rn[1], r1, B, 2 * nh, 2 * nw, ld[1], F, 1, rn_epi(r1r3));
@@ -1289,7 +1271,7 @@ void head_stage(Plan& P, const Call& k, const Dims& g, const Levels& v, int s) {
                            hmerge.fold ? &hmerge.x0_lo : nullptr);
     float* p13 = fusion_map(P, Hd.ref[0], p2, nullptr, r0, r0r3, true, B, 4 * nh, 4 * nw, F, 8 * nh, 8 * nw, true, B0 < B ? &hmerge : nullptr);
     // the level-0 branch's statistics words: kept with the (entry, side) this call filled, completed from those it read
-    if (hc && !P.skip()) P.rc = stats_sites_words(hc->st.side_words(s), hc->st.cap, hc->hent, hc->hmiss, B0, m->stats, P.head_sites[s], P.stream);
+    if (hc && !P.skip()) P.rc = stats_sites_words(hc->st.side_words(s), hc->st.cap, hc->ent, hc->miss, B0, m->stats, P.head_sites[s], P.stream);
     // head (dpt_block.py:323-330)
     const int Hh = 8 * nh, Wh = 8 * nw;
     float* h0 = ar.alloc((size_t)B * Hh * Wh * (F / 2));
@@ -1373,21 +1355,20 @@ int run_plan(a3r_model_s* m, const Call& k, size_t* peak = nullptr) {
     float* cols = ar.alloc((size_t)Mc * 768);
     float* cols3 = P.gin_scratch(Mc, 768);
     if (k.phase == 2) load_features(P, k, g, v.feat);
-    else if (const CacheCall* fc = g.d_img ? k.dd->fc : nullptr) {
+    else if (const FrameCall* fc = g.d_img ? k.dd->fc : nullptr) {
         // Frames kept across calls: the encoder runs on the images the cache does not hold and leaves their rows in `feat`, idle
         // until the copy below; the exchange pass puts every distinct frame's rows, stored or fresh, into featu and the fresh ones
         // with their images into their entries.  The encoder's sites keep their numbers; their statistics words are completed
-        // from the entries' (frame_cache_stats).
-        const int lo = P.site_no;
-        P.mute = fc->n_miss == 0;
-        encoder_stage(P, k, g, cols, cols3, P.mute ? g.N : fc->n_miss * g.N, v.feat);
-        P.mute = false;
+        // from the entries' (stats_sites_words).
+        {
+            StoreScope scope(P, fc, P.enc_sites);
+            encoder_stage(P, k, g, cols, cols3, fc->frames() * g.N, v.feat);
+        }
         if (!P.skip())
             P.rc = frame_cache_exchange(k.img[0], k.img[1], g.B, fc->keys, fc->lay, k.dd->uniq_img, fc->ent, fc->miss, k.dd->n_img, v.feat,
                                         v.featu, P.stream);
         if (!P.skip() && P.gf == Form::FH2)
-            P.rc = frame_cache_stats(fc->lay, fc->ent, fc->miss, k.dd->n_img, m->stats, lo, std::min(P.site_no, (int)a3r_model_s::MAX_SITES),
-                                     P.stream);
+            P.rc = stats_sites_words(fc->stat_words(), fc->lay.cap, fc->ent, fc->miss, k.dd->n_img, m->stats, P.enc_sites, P.stream);
         copy_rows(P, g, v.featu, v.feat, k.dd->map_img, E);
     } else {
         encoder_stage(P, k, g, cols, cols3, g.Mi, v.featu);
@@ -1418,26 +1399,22 @@ int run_plan(a3r_model_s* m, const Call& k, size_t* peak = nullptr) {
 }  // namespace
 
 // ---- the distinct inputs of one call: key, representative and verify kernels, ONE read-back (with one stream synchronise, at the
-// start of the call), the host grouping and one upload of its lists.  a1 / a2: the items of the first kind, words_a words each --
+// start of the call), the host planner (dedup.h, plan_call) and one upload of its lists.  a1 / a2: the items of the first kind, words_a words each --
 // the images of a forward (encode: they are merged for the encoder too), the cached features of a decode call, which only the heads'
 // level-0 branch merges (null: a decode call that does not look at them).  *use = false: run the plain plan (switched off, parity taps
 // on, a batch beyond DEDUP_MAX_SLOTS, nothing to merge, or a slot that differs from its representative: a key collision).
 namespace {
-constexpr int DD_HALF = DEDUP_MAX_SLOTS / 2;                       // slots of one kind at most
 // pinned host words: rep + flag + the frame cache's answer for the 2 B image slots (B <= FC_MAX_PAIRS) + the prior storage's for
-// the 2 B pred_depth slots | the DD_LISTS lists
+// the 2 B pred_depth slots | the lists (dedup.h, CallLists)
 constexpr size_t DD_HOST_LIST = (DEDUP_REP_INTS + 4 * FC_MAX_PAIRS + 63) / 64 * 64;
-constexpr size_t DD_REP_OFF = DEDUP_KEY_BYTES;                     // device bytes: keys | rep + flag + answer | the DD_LISTS lists
+constexpr size_t DD_REP_OFF = DEDUP_KEY_BYTES;                     // device bytes: keys | rep + flag + answer | the lists
 constexpr size_t DD_LIST_OFF = DD_REP_OFF + DD_HOST_LIST * 4;
-// uniq_img, map_img, uniq_pd, map_pd, uniq_side [2][B], map_side [2][B], ent_img, ent_pd, map_eo, map_ekv; frame cache: uniq_miss, ent, miss;
-// stored priors: uniq_miss, ent, miss, src, src_ent; head products, both sides in one block as uniq_side: hent, hmiss, uniq_fresh, src
-constexpr int DD_LISTS = 22;
-constexpr size_t DD_DEV_BYTES = DD_LIST_OFF + (size_t)DD_LISTS * DD_HALF * 4;
+constexpr size_t DD_DEV_BYTES = DD_LIST_OFF + sizeof(CallLists);
 static_assert(FC_STAT_WORDS == a3r_model_s::MAX_SITES, "an entry stores one word per site");
 
 // The storage of the frame cache as entries of this resolution (dedup.h); a change of resolution empties the table
 FrameCacheLayout frame_cache_at(a3r_model_s* m, int H, int W) {
-    const FrameCacheLayout lay = frame_cache_layout(m->fc_buf, m->fc_bytes, 3L * H * W, (long)(H / 16) * (W / 16) * m->cfg.enc_embed_dim);
+    const FrameCacheLayout lay = frame_cache_layout(m->fc.buf, m->fc.bytes, 3L * H * W, (long)(H / 16) * (W / 16) * m->cfg.enc_embed_dim);
     if (H != m->fc_H || W != m->fc_W || lay.cap != m->fc_table.cap) {
         m->reset_frames(lay.cap);
         m->pd_table.reset(0);
@@ -1454,7 +1431,7 @@ long prior_words_rows(const a3r_model_config& c, int H, int W) { return (long)(n
 FrameCacheLayout prior_store_at(a3r_model_s* m, int H, int W, int cap) {
     const long wm = prior_words_map(H, W), wr = prior_words_rows(m->cfg, H, W);
     const size_t need = (size_t)cap * frame_cache_entry_bytes(wm, wr);
-    const FrameCacheLayout lay = frame_cache_layout(m->fp_buf && m->fp_bytes >= need ? m->fp_buf : nullptr, need, wm, wr);
+    const FrameCacheLayout lay = frame_cache_layout(m->fp.buf && m->fp.bytes >= need ? m->fp.buf : nullptr, need, wm, wr);
     if (lay.cap != m->pd_table.cap) m->pd_table.reset(lay.cap);
     return lay;
 }
@@ -1463,41 +1440,33 @@ FrameCacheLayout prior_store_at(a3r_model_s* m, int H, int W, int cap) {
 long head_words(const a3r_model_config& c, int H, int W) { return 16L * (H / 16) * (W / 16) * c.feature_dim; }
 
 int find_distinct(a3r_model_s* m, const float* a1, const float* a2, long words_a, bool encode, const float* pd1, const float* pd2, int B,
-                  int H, int W, void* stream, Distinct* d, bool* use, CacheCall* cc = nullptr, PriorCall* pc = nullptr,
+                  int H, int W, void* stream, Distinct* d, bool* use, FrameCall* cc = nullptr, FrameCall* pc = nullptr,
                   HeadCall* hc = nullptr) {
     *use = false;
-    m->last_fc[0] = m->last_fc[1] = m->last_fc[2] = 0;
-    m->last_hp[0][0] = m->last_hp[0][1] = m->last_hp[1][0] = m->last_hp[1][1] = 0;
-    m->last_pd[0] = m->last_pd[1] = m->last_pd[2] = 0;
-    m->last_img_unique = m->last_pd_unique = 2 * B;
-    m->last_fell_back = 0;
-    m->last_side_unique[0] = m->last_side_unique[1] = B;
-    m->last_side_merged[0] = m->last_side_merged[1] = 0;
-    m->last_ent_unique[0] = m->last_ent_unique[1] = B;
-    m->last_ent_merged = 0;
+    m->last = CallPlan(B);
     if (m->dedup_mode == 0 || m->tap_level > 0 || 4 * B > DEDUP_MAX_SLOTS) return A3R_OK;
     if (!m->dd_dev) A3R_HIP(hipMalloc(&m->dd_dev, DD_DEV_BYTES));
-    if (!m->dd_host) A3R_HIP(hipHostMalloc(reinterpret_cast<void**>(&m->dd_host), (DD_HOST_LIST + DD_LISTS * DD_HALF) * sizeof(int32_t), hipHostMallocDefault));
+    if (!m->dd_host) A3R_HIP(hipHostMalloc(reinterpret_cast<void**>(&m->dd_host), DD_HOST_LIST * sizeof(int32_t) + sizeof(CallLists), hipHostMallocDefault));
     char* dev = static_cast<char*>(m->dd_dev);
     int32_t* rep_dev = reinterpret_cast<int32_t*>(dev + DD_REP_OFF);
-    int32_t* list_dev = reinterpret_cast<int32_t*>(dev + DD_LIST_OFF);
     const bool first_kind = a1 && a2;
     const int S = 2 * B, first = first_kind ? 0 : S;
     if (int rc = dedup_find(a1, a2, pd1, pd2, B, words_a, 3L * H * W, first, m->dedup_mode == 2, dev, rep_dev, stream)) return rc;
     hipStream_t st = as_stream(stream);
+    const a3r_model_config& c = m->cfg;
     // frames kept across calls: the lookup's answer for the 2 B image slots follows the flag in the same read-back
-    bool cached = cc && m->fc_buf && encode && first_kind && B <= FC_MAX_PAIRS;
+    const bool cached = cc && m->fc.buf && encode && first_kind && B <= FC_MAX_PAIRS;
     if (cached) {
         cc->lay = frame_cache_at(m, H, W);
         cc->keys = dev;
         A3R_CHECK_ARG(cc->lay.cap > 0, "a3r_model_forward: the frame cache's storage (%zu bytes) is smaller than one entry at %d x %d (%zu bytes)",
-                      m->fc_bytes, H, W, frame_cache_entry_bytes(cc->lay.words_img, cc->lay.words_feat));
+                      m->fc.bytes, H, W, frame_cache_entry_bytes(cc->lay.words_img, cc->lay.words_feat));
         if (int rc = frame_cache_lookup(a1, a2, B, dev, rep_dev, cc->lay, m->fc_table.mask(), rep_dev + 2 * S + 1, stream)) return rc;
     }
     // priors kept across calls: the same lookup on the pred_depth slots (keys and representatives of the second kind), its answer
     // behind the images'.  They ride on the frame cache (as many entries, dropped and bypassed with it) and feed the decoder's
     // gather-add form, whatever a3r_model_set_dedup_decoder says: a handle with that switch off reads the same stored words.
-    bool stored_pd = cached && pc && m->fp_buf && m->gemm_form == Form::FH2;
+    bool stored_pd = cached && pc && m->fp.buf && m->gemm_form == Form::FH2;
     if (stored_pd) {
         pc->lay = prior_store_at(m, H, W, cc->lay.cap);
         pc->keys = dev + (size_t)S * 16;
@@ -1505,157 +1474,45 @@ int find_distinct(a3r_model_s* m, const float* a1, const float* a2, long words_a
         if (stored_pd)
             if (int rc = frame_cache_lookup(pd1, pd2, B, pc->keys, rep_dev + S, pc->lay, m->pd_table.mask(), rep_dev + 3 * S + 1, stream)) return rc;
     }
+    // head products kept across calls: no lookup of their own, a storage with room for every entry of the frame cache
+    HeadStore hst = head_store_layout(nullptr, 0, 0);
+    if (cached && hc && m->hp.buf) {
+        const long words = head_words(c, H, W);
+        hst = head_store_layout(m->hp.bytes >= (size_t)cc->lay.cap * head_products_entry_bytes(words) ? m->hp.buf : nullptr, cc->lay.cap, words);
+    }
     A3R_HIP(hipMemcpyAsync(m->dd_host, rep_dev, (size_t)(2 * S + 1 + (cached ? S : 0) + (stored_pd ? S : 0)) * sizeof(int32_t),
                            hipMemcpyDeviceToHost, st));
     A3R_HIP(hipStreamSynchronize(st));
     const int32_t* rep = m->dd_host;
-    if (rep[2 * S] != 0) {
-        m->last_fell_back = 1;
-        return A3R_OK;
+    const CallInputs in = {rep, rep[2 * S], cached ? rep + 2 * S + 1 : nullptr, stored_pd ? rep + 3 * S + 1 : nullptr, B, H, W,
+                           c.enc_embed_dim, c.dec_embed_dim, c.feature_dim, c.layer_dims[0], encode, first_kind, m->dedup_head != 0,
+                           m->dedup_decoder != 0, m->gemm_form == Form::FH2, m->map_form == Form::FH2, attention_fh2_takes_maps(),
+                           hst.cap > 0};
+    CallLists& host = *reinterpret_cast<CallLists*>(m->dd_host + DD_HOST_LIST);
+    const CallPlan p = m->last = plan_call(in, m->fc_table, m->pd_table, m->hp_bits, host);
+    if (p.drop) m->drop_stored();
+    if (!p.use) return A3R_OK;
+    A3R_HIP(hipMemcpyAsync(dev + DD_LIST_OFF, &host, sizeof(CallLists), hipMemcpyHostToDevice, st));
+    const CallLists* L = reinterpret_cast<const CallLists*>(dev + DD_LIST_OFF);      // (the device's: its members are device addresses)
+    *d = {p.n_img, p.n_pd, L->uniq_img, L->map_img, L->uniq_pd, L->map_pd, {p.n_side[0], p.n_side[1]}, {L->uniq_side, L->uniq_side + B},
+          {L->map_side, L->map_side + B}, p.n_ent, L->ent_img, L->ent_pd, L->map_eo, L->map_ekv};
+    if (p.fc) {
+        static_cast<StoreCall&>(*cc) = {p.fc_fresh, p.fc_store, L->fc_fresh, L->fc_ent, L->fc_miss, nullptr};
+        cc->src_ent = nullptr;
+        d->fc = cc;
     }
-    int32_t* list = m->dd_host + DD_HOST_LIST;
-    const a3r_model_config& c = m->cfg;
-    int n_img = S;
-    if (encode && first_kind) {
-        n_img = dedup_group(rep, S, list, list + DD_HALF);
-        // the distinct frames' enc_norm rows must fit the buffers they wait in (run_plan)
-        if (n_img > 0 && (size_t)n_img * c.enc_embed_dim > 3 * (size_t)S * c.dec_embed_dim) n_img = S;
+    if (p.pd) {
+        static_cast<StoreCall&>(*pc) = {p.pd_fresh, p.pd_store, L->pd_fresh, L->pd_ent, L->pd_miss, L->pd_src};
+        pc->src_ent = L->pd_src_ent;
+        d->pp = pc;
     }
-    // the heads' level-0 branch: each side's own distinct frames (the lists of both sides share one DD_HALF-word block: 2 B words)
-    int n_side[2] = {B, B};
-    if (first_kind && m->dedup_head && m->map_form == Form::FH2)
-        for (int s = 0; s < 2; s++) {
-            const int u = dedup_group_side(rep, B, s, list + 4 * DD_HALF + s * B, list + 5 * DD_HALF + s * B);
-            if (u <= 0) { n_img = 0; break; }
-            m->last_side_unique[s] = u;
-            if (head_merge_fits(c, (H / 16) * (W / 16), B, u)) n_side[s] = u;
+    for (int s = 0; s < 2; s++)
+        if (p.hp[s]) {
+            const int off = s * B;
+            static_cast<StoreCall&>(hc[s]) = {p.hp_fresh[s], p.hp_store[s], L->hp_fresh + off, L->hp_ent + off, L->hp_miss + off, L->hp_src + off};
+            hc[s].st = hst;
+            d->hp[s] = &hc[s];
         }
-    const int n_pd = dedup_group(rep + S, S, list + 2 * DD_HALF, list + 3 * DD_HALF);
-    if (n_img <= 0 || n_pd <= 0) {       // not a representative table: cannot happen, and is not trusted if it does
-        m->last_fell_back = 1;
-        m->last_side_unique[0] = m->last_side_unique[1] = B;
-        return A3R_OK;
-    }
-    m->last_img_unique = n_img;
-    m->last_pd_unique = n_pd;
-    // decoder block 0: each side's distinct (image, prior) entries, when both kinds merge (fh2 GEMM inputs, the attention form with maps)
-    int n_ent = 0;
-    if (m->dedup_decoder && m->gemm_form == Form::FH2 && attention_fh2_takes_maps() && n_img < S && n_pd < S) {
-        std::vector<int32_t> ent(S), map_e(S);
-        int U[2];
-        const int32_t *map_img = list + DD_HALF, *map_pd = list + 3 * DD_HALF;
-        const int um = dedup_group_entries(map_img, map_pd, B, ent.data(), map_e.data(), U);
-        if (um > 0) {
-            m->last_ent_unique[0] = U[0];
-            m->last_ent_unique[1] = U[1];
-            // The statistic of an fh2 GEMM output covers the whole last row tile: rows past M are copies of the last row, rotated at
-            // their own RoPE positions.  The q / k / v projections keep the plain plan's statistics bit for bit only where neither
-            // plan has such rows: both row counts whole multiples of the largest row tile (256).
-            const long N = (long)(H / 16) * (W / 16);
-            if (um < B && (B * N) % 256 == 0 && (um * N) % 256 == 0) {
-                n_ent = um;
-                int32_t *ent_img = list + 6 * DD_HALF, *ent_pd = list + 7 * DD_HALF, *map_eo = list + 8 * DD_HALF, *map_ekv = list + 9 * DD_HALF;
-                for (int s = 0; s < 2; s++) {
-                    for (int e = 0; e < um; e++) {
-                        ent_img[s * um + e] = map_img[ent[s * B + e]];
-                        ent_pd[s * um + e] = map_pd[ent[s * B + e]];
-                    }
-                    for (int b = 0; b < B; b++) {
-                        map_eo[s * B + b] = s * um + map_e[s * B + b];
-                        map_ekv[s * B + b] = s * um + map_e[(1 - s) * B + b];
-                    }
-                }
-            }
-        }
-    }
-    m->last_ent_merged = n_ent > 0;
-    // The frame cache: hits and misses among the distinct images, victims for the misses (FrameCacheTable::assign), the lists of
-    // the exchange pass.  It needs the image stage on the distinct list, whose rows must fit where they wait (above).
-    cached = cached && (size_t)n_img * c.enc_embed_dim <= 3 * (size_t)S * c.dec_embed_dim;
-    if (cached) {
-        const int32_t *uniq = list, *answer = rep + 2 * S + 1;
-        int32_t *uniq_miss = list + 10 * DD_HALF, *ent = list + 11 * DD_HALF, *miss = list + 12 * DD_HALF;
-        for (int k = 0; k < n_img; k++) miss[k] = answer[uniq[k]];
-        cached = m->fc_table.assign(miss, n_img, ent, m->last_fc) == 0;
-        if (cached) {
-            cc->n_miss = 0;
-            for (int k = 0; k < n_img; k++) {
-                const bool hit = miss[k] >= 0;
-                if (!hit) {
-                    uniq_miss[cc->n_miss] = uniq[k];
-                    m->hp_bits.clear(ent[k]);      // the entry now holds another frame: what the heads made of the old one is stale
-                }
-                miss[k] = hit ? -1 : cc->n_miss++;
-            }
-            cc->uniq_miss = list_dev + 10 * DD_HALF;
-            cc->ent = list_dev + 11 * DD_HALF;
-            cc->miss = list_dev + 12 * DD_HALF;
-        }
-    }
-    // The stored priors: hits, misses and victims among the distinct pred_depth maps, and the lists of the prior branch
-    if (stored_pd) {
-        const int32_t *uniq = list + 2 * DD_HALF, *map_pd = list + 3 * DD_HALF, *answer = rep + 3 * S + 1;
-        int32_t *uniq_miss = list + 13 * DD_HALF, *ent = list + 14 * DD_HALF, *miss = list + 15 * DD_HALF, *src = list + 16 * DD_HALF,
-                *src_ent = list + 17 * DD_HALF;
-        std::vector<int32_t> hit(n_pd);
-        for (int k = 0; k < n_pd; k++) hit[k] = answer[uniq[k]];
-        stored_pd = m->pd_table.assign(hit.data(), n_pd, ent, m->last_pd) == 0;
-        if (stored_pd) {
-            int n_store = 0;
-            pc->n_miss = prior_lists(hit.data(), ent, uniq, n_pd, miss, uniq_miss, map_pd, S, src, &n_store);
-            if (pc->n_miss < 0) {               // (never: map_pd is dedup_group's)
-                m->drop_stored();
-                m->last_fell_back = 1;
-                return A3R_OK;
-            }
-            for (int i = 0; i < 2 * n_ent; i++) src_ent[i] = src[uniq[list[7 * DD_HALF + i]]];      // ent_pd names distinct priors
-            pc->n_store = n_store;
-            pc->uniq_miss = list_dev + 13 * DD_HALF;
-            pc->ent = list_dev + 14 * DD_HALF;
-            pc->miss = list_dev + 15 * DD_HALF;
-            pc->src = list_dev + 16 * DD_HALF;
-            pc->src_ent = list_dev + 17 * DD_HALF;
-        }
-    }
-    // The head products: which of a merging side's distinct frames are stored, and the lists of its level-0 branch.  They ride on
-    // the frame cache (its entries, dropped and bypassed with it); a side that does not merge neither reads nor writes them.
-    const HeadCall* hp[2] = {nullptr, nullptr};
-    if (cached && hc && m->hp_buf && m->map_form == Form::FH2 && m->gemm_form == Form::FH2) {
-        const long words = head_words(c, H, W);
-        const HeadStore st = head_store_layout(m->hp_bytes >= (size_t)cc->lay.cap * head_products_entry_bytes(words) ? m->hp_buf : nullptr,
-                                               cc->lay.cap, words);
-        const int32_t *map_img = list + DD_HALF, *ent = list + 11 * DD_HALF, *miss = list + 12 * DD_HALF;
-        for (int s = 0; s < 2 && st.cap > 0; s++) {
-            if (n_side[s] >= B) continue;
-            const int off = s * B, U = n_side[s];
-            const int32_t *uniq_side = list + 4 * DD_HALF + off, *map_side = list + 5 * DD_HALF + off;
-            std::vector<int32_t> row(U);
-            for (int k = 0; k < U; k++) row[k] = map_img[uniq_side[k]];
-            int n_store = 0;
-            const int n_fresh = head_lists(m->hp_bits, s, ent, miss, n_img, row.data(), uniq_side, U, map_side, B, list + 18 * DD_HALF + off,
-                                           list + 19 * DD_HALF + off, list + 20 * DD_HALF + off, list + 21 * DD_HALF + off, &n_store);
-            if (n_fresh < 0) {                  // (never: the lists are dedup_group's and assign's)
-                m->drop_stored();
-                m->last_fell_back = 1;
-                return A3R_OK;
-            }
-            hc[s] = {st, n_fresh, n_store, list_dev + 20 * DD_HALF + off, list_dev + 18 * DD_HALF + off, list_dev + 19 * DD_HALF + off,
-                     list_dev + 21 * DD_HALF + off};
-            hp[s] = &hc[s];
-            m->last_hp[s][0] = U - n_fresh;
-            m->last_hp[s][1] = n_fresh;
-        }
-    }
-    if (!cached && !stored_pd && n_img == S && n_pd == S && n_side[0] == B && n_side[1] == B) return A3R_OK;
-    m->last_side_merged[0] = n_side[0] < B;
-    m->last_side_merged[1] = n_side[1] < B;
-    A3R_HIP(hipMemcpyAsync(list_dev, list, (size_t)DD_LISTS * DD_HALF * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    *d = {n_img, n_pd, list_dev, list_dev + DD_HALF, list_dev + 2 * DD_HALF, list_dev + 3 * DD_HALF,
-          {n_side[0], n_side[1]}, {list_dev + 4 * DD_HALF, list_dev + 4 * DD_HALF + B}, {list_dev + 5 * DD_HALF, list_dev + 5 * DD_HALF + B},
-          n_ent, list_dev + 6 * DD_HALF, list_dev + 7 * DD_HALF, list_dev + 8 * DD_HALF, list_dev + 9 * DD_HALF, cached ? cc : nullptr,
-          stored_pd ? pc : nullptr};
-    d->hp[0] = hp[0];
-    d->hp[1] = hp[1];
     *use = true;
     return A3R_OK;
 }
@@ -1694,7 +1551,8 @@ extern "C" size_t a3r_model_workspace_bytes(a3r_model_t m, int B, int H, int W) 
     // one duplicate (2 B - 1 distinct), of the depth priors alone or of both kinds; and the heads' merged level-0 branch at the
     // largest number of distinct frames a side is admitted with (head_merge_fits: its buffers grow with that number)
     int u_max = B - 1;
-    while (u_max > 0 && !head_merge_fits(m->cfg, (H / 16) * (W / 16), B, u_max)) u_max--;
+    const a3r_model_config& c = m->cfg;
+    while (u_max > 0 && !head_merge_fits(c.enc_embed_dim, c.feature_dim, c.layer_dims[0], (H / 16) * (W / 16), B, u_max)) u_max--;
     const int u_side = u_max > 0 && m->map_form == Form::FH2 ? u_max : B;
     const Distinct cases[4] = {distinct_counts(2 * B, 2 * B, B), distinct_counts(2 * B, 2 * B - 1, B), distinct_counts(2 * B - 1, 2 * B - 1, B),
                                distinct_counts(2 * B, 2 * B, u_side)};
@@ -1712,8 +1570,7 @@ extern "C" int a3r_model_forward(a3r_model_t m, const float* img1, const float* 
     A3R_CHECK_ARG(workspace_bytes >= need_bytes, "a3r_model_forward: workspace too small (%zu < %zu)", workspace_bytes, need_bytes);
     Distinct d;
     bool merge = false;
-    CacheCall cc;
-    PriorCall pc;
+    FrameCall cc, pc;
     HeadCall hc[2];
     int rc = find_distinct(m, img1, img2, 3L * H * W, true, pd1, pd2, B, H, W, stream, &d, &merge, &cc, &pc, hc);
     Call k;
@@ -1783,23 +1640,20 @@ extern "C" int a3r_model_set_frame_cache(a3r_model_t m, void* buf, size_t bytes)
     A3R_CHECK_ARG(m, "a3r_model_set_frame_cache: null handle");
     m->reset_frames(0);
     m->pd_table.reset(0);
-    m->fc_buf = nullptr;
-    m->fc_bytes = 0;
     m->fc_H = m->fc_W = 0;
-    if (!buf || !bytes) return A3R_OK;
-    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "a3r_model_set_frame_cache: storage must be 256-byte aligned");
+    if (int rc = m->fc.set(buf, bytes, "a3r_model_set_frame_cache")) return rc;
     const size_t least = a3r_model_frame_cache_bytes(m, 16, 16, 1);
-    A3R_CHECK_ARG(bytes >= least, "a3r_model_set_frame_cache: storage too small for one entry of the smallest image (%zu < %zu)", bytes, least);
-    m->fc_buf = buf;
-    m->fc_bytes = bytes;
-    return A3R_OK;
+    if (!m->fc.buf || bytes >= least) return A3R_OK;
+    m->fc = {};
+    set_error("a3r_model_set_frame_cache: storage too small for one entry of the smallest image (%zu < %zu)", bytes, least);
+    return A3R_EINVAL;
 }
 
 extern "C" int a3r_model_last_frame_cache(a3r_model_t m, int* hits, int* misses, int* evictions) {
     A3R_CHECK_ARG(m && hits && misses && evictions, "a3r_model_last_frame_cache: null argument");
-    *hits = m->last_fc[0];
-    *misses = m->last_fc[1];
-    *evictions = m->last_fc[2];
+    *hits = m->last.fc_n[0];
+    *misses = m->last.fc_n[1];
+    *evictions = m->last.fc_n[2];
     return A3R_OK;
 }
 
@@ -1811,20 +1665,14 @@ extern "C" size_t a3r_model_frame_products_bytes(a3r_model_t m, int H, int W, in
 extern "C" int a3r_model_set_frame_products(a3r_model_t m, void* buf, size_t bytes) {
     A3R_CHECK_ARG(m, "a3r_model_set_frame_products: null handle");
     m->pd_table.reset(0);
-    m->fp_buf = nullptr;
-    m->fp_bytes = 0;
-    if (!buf || !bytes) return A3R_OK;
-    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "a3r_model_set_frame_products: storage must be 256-byte aligned");
-    m->fp_buf = buf;
-    m->fp_bytes = bytes;
-    return A3R_OK;
+    return m->fp.set(buf, bytes, "a3r_model_set_frame_products");
 }
 
 extern "C" int a3r_model_last_frame_products(a3r_model_t m, int* hits, int* misses, int* evictions) {
     A3R_CHECK_ARG(m && hits && misses && evictions, "a3r_model_last_frame_products: null argument");
-    *hits = m->last_pd[0];
-    *misses = m->last_pd[1];
-    *evictions = m->last_pd[2];
+    *hits = m->last.pd_n[0];
+    *misses = m->last.pd_n[1];
+    *evictions = m->last.pd_n[2];
     return A3R_OK;
 }
 
@@ -1836,20 +1684,14 @@ extern "C" size_t a3r_model_head_products_bytes(a3r_model_t m, int H, int W, int
 extern "C" int a3r_model_set_head_products(a3r_model_t m, void* buf, size_t bytes) {
     A3R_CHECK_ARG(m, "a3r_model_set_head_products: null handle");
     m->hp_bits.flush();
-    m->hp_buf = nullptr;
-    m->hp_bytes = 0;
-    if (!buf || !bytes) return A3R_OK;
-    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "a3r_model_set_head_products: storage must be 256-byte aligned");
-    m->hp_buf = buf;
-    m->hp_bytes = bytes;
-    return A3R_OK;
+    return m->hp.set(buf, bytes, "a3r_model_set_head_products");
 }
 
 extern "C" int a3r_model_last_head_products(a3r_model_t m, int* hits, int* misses) {
     A3R_CHECK_ARG(m && hits && misses, "a3r_model_last_head_products: null argument");
     for (int s = 0; s < 2; s++) {
-        hits[s] = m->last_hp[s][0];
-        misses[s] = m->last_hp[s][1];
+        hits[s] = m->last.hp_hits(s);
+        misses[s] = m->last.hp_misses(s);
     }
     return A3R_OK;
 }
@@ -1868,26 +1710,26 @@ extern "C" int a3r_model_set_dedup_decoder(a3r_model_t m, int on) {
 
 extern "C" int a3r_model_last_dedup_entries(a3r_model_t m, int* u1, int* u2, int* merged) {
     A3R_CHECK_ARG(m && u1 && u2 && merged, "a3r_model_last_dedup_entries: null argument");
-    *u1 = m->last_ent_unique[0];
-    *u2 = m->last_ent_unique[1];
-    *merged = m->last_ent_merged;
+    *u1 = m->last.ent_unique[0];
+    *u2 = m->last.ent_unique[1];
+    *merged = m->last.n_ent > 0;
     return A3R_OK;
 }
 
 extern "C" int a3r_model_last_dedup_sides(a3r_model_t m, int* u1, int* u2, int* merged1, int* merged2) {
     A3R_CHECK_ARG(m && u1 && u2 && merged1 && merged2, "a3r_model_last_dedup_sides: null argument");
-    *u1 = m->last_side_unique[0];
-    *u2 = m->last_side_unique[1];
-    *merged1 = m->last_side_merged[0];
-    *merged2 = m->last_side_merged[1];
+    *u1 = m->last.side_unique[0];
+    *u2 = m->last.side_unique[1];
+    *merged1 = m->last.side_merged[0];
+    *merged2 = m->last.side_merged[1];
     return A3R_OK;
 }
 
 extern "C" int a3r_model_last_dedup(a3r_model_t m, int* n_img_unique, int* n_pd_unique, int* fell_back) {
     A3R_CHECK_ARG(m && n_img_unique && n_pd_unique && fell_back, "a3r_model_last_dedup: null argument");
-    *n_img_unique = m->last_img_unique;
-    *n_pd_unique = m->last_pd_unique;
-    *fell_back = m->last_fell_back;
+    *n_img_unique = m->last.n_img;
+    *n_pd_unique = m->last.n_pd;
+    *fell_back = m->last.fell_back;
     return A3R_OK;
 }
 
