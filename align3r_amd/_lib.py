@@ -210,6 +210,7 @@ SIGNATURES = {
     "a3r_raft_destroy": (C.c_int, [c_void]),
     "a3r_raft_set_weight": (C.c_int, [c_void, C.c_char_p, c_void, C.c_int, C.POINTER(C.c_int64)]),
     "a3r_raft_packed_bytes": (C.c_size_t, [c_void]),
+    "a3r_raft_corr_width": (C.c_int, [c_void]),
     "a3r_raft_finalize": (C.c_int, [c_void, c_void, C.c_size_t, c_void]),
     "a3r_raft_workspace_bytes": (C.c_size_t, [c_void, C.c_int, C.c_int, C.c_int]),
     "a3r_raft_set_arith": (C.c_int, [c_void, C.c_int]),

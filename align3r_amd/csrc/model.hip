@@ -1178,10 +1178,9 @@ void head_levels(Plan& P, const Call& k, const Dims& g, const Levels& v, int s, 
     // 1x1 adapters: in fh2 mode a split pass + the fh2 GEMM (5x the exact-fp32 MFMA kernel's rate) instead of a3r_linear
     auto adapter = [&](const float* t, int K, const float* w, const float* b, float* y, int cout, int rows) {
         if (P.gf != Form::FH2) { P.linear_f32(t, K, w, y, cout, rows, cout, K, P.epi(A3R_EPI_NONE, b)); return; }
-        const size_t keep = ar.off;
+        ArenaScope scope(ar);                                   // the split is dead once the GEMM is enqueued (stream order)
         float* tg = P.gin_scratch(rows, K);
         P.linear(P.gin_from(t, tg, rows, K), K, w, y, cout, rows, cout, K, P.epi(A3R_EPI_NONE, b));
-        ar.off = keep;                                          // the split is dead once the GEMM is enqueued (stream order)
     };
     // the transposed conv (kernel = stride = ps) behind an adapter: a GEMM whose epilogue scatters the ps x ps pixels
     auto pixshuf = [&](const float* a, const float* w, const float* b, float* y, int ps, int C, int rows) {
@@ -1349,37 +1348,40 @@ int run_plan(a3r_model_s* m, const Call& k, size_t* peak = nullptr) {
         set_error("a3r_model_forward: internal: the decoder level buffers are not contiguous");
         return A3R_ESTATE;
     }
-    const size_t mark = ar.off;
     // ---------------- encoder (or the cached features) and the depth-prior embedding, which share the patch columns
-    const int Mc = k.phase == 2 ? g.Mp : g.Mi > g.Mp ? g.Mi : g.Mp;
-    float* cols = ar.alloc((size_t)Mc * 768);
-    float* cols3 = P.gin_scratch(Mc, 768);
-    if (k.phase == 2) load_features(P, k, g, v.feat);
-    else if (const FrameCall* fc = g.d_img ? k.dd->fc : nullptr) {
-        // Frames kept across calls: the encoder runs on the images the cache does not hold and leaves their rows in `feat`, idle
-        // until the copy below; the exchange pass puts every distinct frame's rows, stored or fresh, into featu and the fresh ones
-        // with their images into their entries.  The encoder's sites keep their numbers; their statistics words are completed
-        // from the entries' (stats_sites_words).
-        {
-            StoreScope scope(P, fc, P.enc_sites);
-            encoder_stage(P, k, g, cols, cols3, fc->frames() * g.N, v.feat);
+    {
+        ArenaScope stage(ar);
+        const int Mc = k.phase == 2 ? g.Mp : g.Mi > g.Mp ? g.Mi : g.Mp;
+        float* cols = ar.alloc((size_t)Mc * 768);
+        float* cols3 = P.gin_scratch(Mc, 768);
+        if (k.phase == 2) load_features(P, k, g, v.feat);
+        else if (const FrameCall* fc = g.d_img ? k.dd->fc : nullptr) {
+            // Frames kept across calls: the encoder runs on the images the cache does not hold and leaves their rows in `feat`, idle
+            // until the copy below; the exchange pass puts every distinct frame's rows, stored or fresh, into featu and the fresh ones
+            // with their images into their entries.  The encoder's sites keep their numbers; their statistics words are completed
+            // from the entries' (stats_sites_words).
+            {
+                StoreScope scope(P, fc, P.enc_sites);
+                encoder_stage(P, k, g, cols, cols3, fc->frames() * g.N, v.feat);
+            }
+            if (!P.skip())
+                P.rc = frame_cache_exchange(k.img[0], k.img[1], g.B, fc->keys, fc->lay, k.dd->uniq_img, fc->ent, fc->miss, k.dd->n_img, v.feat,
+                                            v.featu, P.stream);
+            if (!P.skip() && P.gf == Form::FH2)
+                P.rc = stats_sites_words(fc->stat_words(), fc->lay.cap, fc->ent, fc->miss, k.dd->n_img, m->stats, P.enc_sites, P.stream);
+            copy_rows(P, g, v.featu, v.feat, k.dd->map_img, E);
+        } else {
+            encoder_stage(P, k, g, cols, cols3, g.Mi, v.featu);
+            if (g.d_img) copy_rows(P, g, v.featu, v.feat, k.dd->map_img, E);
         }
-        if (!P.skip())
-            P.rc = frame_cache_exchange(k.img[0], k.img[1], g.B, fc->keys, fc->lay, k.dd->uniq_img, fc->ent, fc->miss, k.dd->n_img, v.feat,
-                                        v.featu, P.stream);
-        if (!P.skip() && P.gf == Form::FH2)
-            P.rc = stats_sites_words(fc->stat_words(), fc->lay.cap, fc->ent, fc->miss, k.dd->n_img, m->stats, P.enc_sites, P.stream);
-        copy_rows(P, g, v.featu, v.feat, k.dd->map_img, E);
-    } else {
-        encoder_stage(P, k, g, cols, cols3, g.Mi, v.featu);
-        if (g.d_img) copy_rows(P, g, v.featu, v.feat, k.dd->map_img, E);
+        embed_pc_stage(P, k, g, cols, cols3, v.pcu);
     }
-    embed_pc_stage(P, k, g, cols, cols3, v.pcu);
-    ar.off = mark;
     tap_copy(P, g, v.tap_pc0, v.pc);
     // ---------------- decoder
-    decoder_stage(P, k, g, v);
-    ar.off = mark;
+    {
+        ArenaScope stage(ar);
+        decoder_stage(P, k, g, v);
+    }
     if (!dry) {
         m->taps.clear();
         m->taps["feat"] = {v.feat, (size_t)M2 * E};
@@ -1390,7 +1392,7 @@ int run_plan(a3r_model_s* m, const Call& k, size_t* peak = nullptr) {
     }
     // ---------------- DPT heads, one per view
     for (int s = 0; s < 2; s++) {
-        ar.off = mark;
+        ArenaScope stage(ar);
         head_stage(P, k, g, v, s);
     }
     if (peak) *peak = ar.peak;

@@ -66,6 +66,15 @@ struct Arena {
         return dry || rc != A3R_OK;
     }
 };
+// a stage's scratch: what is allocated inside the scope is released, back to the mark, when the scope ends (`peak` keeps counting
+// it; what the stage enqueued still runs first: stream order)
+struct ArenaScope {
+    Arena& ar;
+    const size_t mark;
+    explicit ArenaScope(Arena& a) : ar(a), mark(a.off) {}
+    ~ArenaScope() { ar.off = mark; }
+    ArenaScope(const ArenaScope&) = delete;
+};
 
 // ---- the form a matrix operand [rows, K] is stored in: plain fp32; three bf16 planes (bf3.h, 6 K bytes per row); two fp16 planes of
 // scale * x (fh2.h, 4 K bytes per row: exactly the fp32 matrix's)

@@ -8,15 +8,17 @@
 //   CorrBlock2 (pyramid over down-sampled fmap2)       corr.py:10-60, utils/utils.py:76-91 (bilinear_sampler)
 //   BasicUpdateBlock2 / BasicMotionEncoder2            update.py:99-174
 //   ConvNextBlock / LayerNorm                          layer.py:35-104
-// Round 3: the default arithmetic is the two-plane fp16 form (fh2 kernels, a3r_raft_set_arith(1)); the three-plane bf16 form below
-// stays as the fp32-range fallback (a3r_raft_set_arith(0)) that RaftEngine re-runs when a3r_raft_range reports a value outside fp16.
-// Every 3x3 convolution and every 1x1 / Linear runs on the exact three-plane bf16 matrix-core kernels (gemm_bf3.hip: fp32-accurate, fp32
-// range -- the flow network is a few per cent of a clip's work, so it takes the form that needs no range control); the all-pairs
-// correlation is that GEMM with the second feature map as the weight operand.  What has no GEMM shape is here: the 7x7 stems on 3 / 6 /
-// 2 channels, the depthwise 7x7 of ConvNeXt, the strided gather of the 1x1 shortcuts, 2x2 averaging, the correlation lookup and the
-// convex up-sampling.  BatchNorm (evaluation mode) is folded into the convolutions by the caller (align3r_amd/raft_weights.py
-// fold_batchnorm), as are the ConvNeXt layer scale (into pwconv2) and the 0.25 of the up-sampling weights (raft.py:216).
-// Maps are channels-last fp32 [B, h, w, C]; all buffers live in the caller's workspace.
+// Every 3x3 convolution and every 1x1 / Linear runs on liba3r's matrix-core kernels, in one of two operand forms (plan.h, Form)
+// chosen per handle by a3r_raft_set_arith; the all-pairs correlation is the same GEMM with the second feature map as the weight
+// operand.  The default is FH2, two fp16 planes (gemm_fh2.hip: fp32-grade while every stored value stays inside fp16's range).  Its
+// range control is one device word: every fh2 producer of a call reports max |stored value| into it, a3r_raft_range reads it back,
+// and a caller that finds it at or above 2^15 repeats the call in the other form (RaftEngine does).  That form is BF3, three bf16
+// planes (gemm_bf3.hip: fp32-accurate with fp32's range, twice the matrix passes).  Weights are packed in both forms at finalize.
+// What has no GEMM shape is in this file: the 7x7 stems on 3 / 6 / 2 channels, the depthwise 7x7 of ConvNeXt, the strided gather of
+// the 1x1 shortcuts, 2x2 averaging, the correlation lookup and the convex up-sampling.  BatchNorm (evaluation mode) is folded into
+// the convolutions by the caller (align3r_amd/raft_weights.py fold_batchnorm), as are the ConvNeXt layer scale (into pwconv2) and
+// the 0.25 of the up-sampling weights (raft.py:216).  Maps are channels-last fp32 [B, h, w, C]; all buffers live in the caller's
+// workspace.  Below: the kernels, the weights as the plan reads them (bound once, at finalize), the pack plan, the launch plan.
 #include "plan.h"
 #include <cstdlib>
 #include <new>
@@ -317,92 +319,128 @@ static void launch_direct_conv(const DirectConvArgs& a, hipStream_t st) {
     else hipLaunchKernelGGL(direct_conv_kernel, dim3(grid1d((long)a.B * a.Ho * ((a.Wo + DC_PX - 1) / DC_PX) * a.Cout)), dim3(256), 0, st, a);
 }
 
+// ------------------------------------------------------------------------------------------- the weights, as the plan reads them
+// Resolved once, by a3r_raft_finalize; the structs follow the network.  Shapes and block geometry are filled in by a3r_raft_create
+// (the sizing pass needs them and runs on a handle without weights), pointers by finalize.
+// a 3x3 convolution (K = 9 Cin) or a 1x1 / Linear as the matrix [N, K]: its twins in the packed buffer -- BOTH the bf3 image and the
+// fh2 image, so that a3r_raft_set_arith can switch between them after finalize -- and its bias
+struct RConvW { Twin w; const float* b = nullptr; int N = 0, K = 0; };
+// a 7x7 direct or depthwise convolution: the weight, transposed into the packed buffer, and its bias
+struct RDirectW { const float* wt = nullptr; const float* b = nullptr; };
+struct RNormW { const float* w = nullptr; const float* b = nullptr; };
+struct RBlockW { int cin = 0, dim = 0, stride = 1; bool project = false; RConvW conv1, conv2, down; };      // BasicBlock (`down`: if project)
+struct REncoderW { RDirectW stem; std::vector<RBlockW> blocks; RConvW final_conv; };                         // ResNetFPN
+struct RMotionW { RConvW convc1, convc2, convf2, conv; RDirectW convf1; };                                   // BasicMotionEncoder2
+struct RRefineW { RDirectW dw; RNormW norm; RConvW pw1, pw2, fin; };                                         // ConvNextBlock
+struct RHeadsW { RConvW flow0, flow2, up0, up2; };                                                           // flow_head, upsample_weight
+struct RaftW { REncoderW cnet, fnet; RConvW init_conv; RHeadsW heads; RMotionW enc; std::vector<RRefineW> refine; };
+
+// ------------------------------------------------------------------------------------------- weight plan
+// One walk over the network names every weight the launch plan reads: `name`.weight and `name`.bias, what becomes of the weight in
+// the packed buffer, and the field of RaftW that receives the result.
+enum class Pack {
+    CONV3,       // [N, K / 9, 3, 3] -> twins, through an fp32 [N, 3, 3, Cin] staging copy at `tmp`
+    LINEAR,      // [N, K] or [N, K, 1, 1] -> twins
+    DIRECT,      // 7x7 direct [N, K / 49, 7, 7] or depthwise [N, 1, 7, 7] (K = 49) -> fp32 [K][N]
+    NORM,        // LayerNorm weight and bias [N]: nothing packed
+};
+struct RItem {
+    std::string name; Pack kind; int N, K;
+    RConvW* conv = nullptr; RDirectW* direct = nullptr; RNormW* norm = nullptr;
+    size_t off = 0, tmp = 0, off2 = 0;      // packed image (bf3 twin or transposed fp32), conv staging, fh2 twin
+};
+struct PackPlan {
+    std::vector<RItem> items;
+    size_t total = 0;
+    void add(RItem it) {
+        it.off = total;
+        const bool twin = it.kind == Pack::CONV3 || it.kind == Pack::LINEAR;
+        if (twin) total = align_up(total + a3r_bf3_w_bytes(it.N, it.K), 256);
+        else if (it.kind == Pack::DIRECT) total = align_up(total + (size_t)it.N * it.K * 4, 256);
+        if (it.kind == Pack::CONV3) { it.tmp = total; total = align_up(total + (size_t)it.N * it.K * 4, 256); }
+        if (twin) { it.conv->N = it.N; it.conv->K = it.K; }
+        items.push_back(it);
+    }
+    void conv3(const std::string& n, int cout, int cin, RConvW* w) { RItem it{n, Pack::CONV3, cout, 9 * cin}; it.conv = w; add(it); }
+    void linear(const std::string& n, int N, int K, RConvW* w) { RItem it{n, Pack::LINEAR, N, K}; it.conv = w; add(it); }
+    void direct(const std::string& n, int cout, int cin, RDirectW* w) { RItem it{n, Pack::DIRECT, cout, 49 * cin}; it.direct = w; add(it); }
+    void norm(const std::string& n, int N, RNormW* w) { RItem it{n, Pack::NORM, N, 0}; it.norm = w; add(it); }
+};
+
+// K of convc1: the correlation features levels (2 r + 1)^2, padded to the GEMM's K granularity (the lookup kernel writes the zeros)
+static int corr_width(const a3r_raft_config& c) {
+    const int win = 2 * c.radius + 1;
+    return (c.corr_levels * win * win + 31) / 32 * 32;
+}
+
+static void encoder_items(PackPlan& pp, const std::string& p, const a3r_raft_config& c, int output_dim, REncoderW* e) {
+    e->blocks.resize(c.n_blocks[0] + c.n_blocks[1] + c.n_blocks[2]);      // (the items point into it: sized once)
+    RBlockW* b = e->blocks.data();
+    int in_planes = c.initial_dim;
+    for (int li = 0; li < 3; li++) {
+        const int dim = c.block_dims[li];
+        for (int bi = 0; bi < c.n_blocks[li]; bi++, b++) {
+            const std::string q = p + ".layer" + std::to_string(li + 1) + "." + std::to_string(bi);
+            b->cin = bi == 0 ? in_planes : dim;
+            b->dim = dim;
+            b->stride = bi == 0 && li > 0 ? 2 : 1;
+            b->project = !(b->stride == 1 && b->cin == dim);               // layer.py:122-129
+            pp.conv3(q + ".conv1", dim, b->cin, &b->conv1);
+            pp.conv3(q + ".conv2", dim, dim, &b->conv2);
+            if (b->project) pp.linear(q + ".downsample.0", dim, b->cin, &b->down);
+        }
+        in_planes = dim;
+    }
+    pp.linear(p + ".final_conv", output_dim, c.block_dims[2], &e->final_conv);
+}
+
+// The packed layout is the order of the lines here (observable: a3r_raft_packed_bytes, tests/golden/plan_sizes.json)
+static void raft_pack_plan(const a3r_raft_config& c, PackPlan& pp, RaftW* w) {
+    const int d = c.dim;
+    const std::string e = "update_block.encoder.";
+    pp.direct("cnet.conv1", c.initial_dim, 6, &w->cnet.stem);
+    pp.direct("fnet.conv1", c.initial_dim, 3, &w->fnet.stem);
+    pp.direct(e + "convf1", d, 2, &w->enc.convf1);
+    encoder_items(pp, "cnet", c, 2 * d, &w->cnet);
+    encoder_items(pp, "fnet", c, 2 * d, &w->fnet);
+    pp.conv3("init_conv", 2 * d, 2 * d, &w->init_conv);
+    pp.conv3("upsample_weight.0", 2 * d, d, &w->heads.up0);
+    pp.linear("upsample_weight.2", 576, 2 * d, &w->heads.up2);
+    pp.conv3("flow_head.0", 2 * d, d, &w->heads.flow0);
+    pp.conv3("flow_head.2", 6, 2 * d, &w->heads.flow2);
+    pp.linear(e + "convc1", 2 * d, corr_width(c), &w->enc.convc1);
+    pp.conv3(e + "convc2", d + d / 2, 2 * d, &w->enc.convc2);
+    pp.conv3(e + "convf2", d / 2, d, &w->enc.convf2);
+    pp.conv3(e + "conv", d - 2, 2 * d, &w->enc.conv);
+    w->refine.resize(c.num_blocks);
+    for (int i = 0; i < c.num_blocks; i++) {
+        const std::string q = "update_block.refine." + std::to_string(i) + ".";
+        RRefineW& r = w->refine[i];
+        pp.direct(q + "dwconv", 3 * d, 1, &r.dw);
+        pp.norm(q + "norm", 3 * d, &r.norm);
+        pp.linear(q + "pwconv1", 4 * d, 3 * d, &r.pw1);
+        pp.linear(q + "pwconv2", 3 * d, 4 * d, &r.pw2);
+        pp.linear(q + "final", d, 3 * d, &r.fin);
+    }
+    // second image of every conv / linear weight: fh2 form (4 bytes per element); then one line for the range statistic and the
+    // absmax scratch word of the packing pass
+    for (RItem& it : pp.items)
+        if (it.conv) { it.off2 = pp.total; pp.total = align_up(pp.total + (size_t)it.N * it.K * 4, 256); }
+    pp.total = align_up(pp.total + 256, 256);
+}
+
 }  // namespace a3r
 using namespace a3r;
 
 struct a3r_raft_s {
     a3r_raft_config cfg;
-    WeightTable w;
+    WeightTable w;                                  // what a3r_raft_set_weight registered
+    PackPlan pack;                                  // a3r_raft_create: the layout of the packed buffer ...
+    RaftW bound;                                    // ... and the shapes of the bound weights; a3r_raft_finalize: their pointers
     bool finalized = false;
-    // conv / linear weight name -> its twins in the packed buffer: BOTH the bf3 image and the fh2 image (the default arithmetic), so
-    // that a3r_raft_set_arith can switch between them after finalize
-    TwinTable<std::string> twins;
-    std::map<std::string, const float*> aux;        // depthwise weights transposed
     bool use_fh2 = true;                            // a3r_raft_set_arith
     unsigned* stat = nullptr;                       // device word: max |value written in fh2 form| of the last forward (range check)
 };
-
-// ------------------------------------------------------------------------------------------- weight plan
-namespace {
-struct RItem { std::string name; int kind; int N, K; size_t off, tmp; size_t off2 = 0; };      // kind 0: conv3x3 [N, K/9 ch]; 1: linear [N, K]; 2: depthwise [C=N]; 3: direct conv [N, K = Cin 49], transposed
-
-void resnet_convs(const std::string& p, const a3r_raft_config& c, std::vector<RItem>* v, int output_dim, size_t* off) {
-    auto add = [&](const std::string& n, int kind, int N, int K) {
-        RItem it{n, kind, N, K, *off, 0, 0};
-        *off = align_up(*off + a3r_bf3_w_bytes(N, K), 256);
-        if (kind == 0) { it.tmp = *off; *off = align_up(*off + (size_t)N * K * 4, 256); }      // fp32 [Cout, 3, 3, Cin] staging
-        v->push_back(it);
-    };
-    int in_planes = c.initial_dim;
-    for (int li = 0; li < 3; li++) {
-        const int dim = c.block_dims[li];
-        for (int bi = 0; bi < c.n_blocks[li]; bi++) {
-            const std::string q = p + ".layer" + std::to_string(li + 1) + "." + std::to_string(bi);
-            const int cin = bi == 0 ? in_planes : dim, stride = bi == 0 && li > 0 ? 2 : 1;
-            add(q + ".conv1.weight", 0, dim, 9 * cin);
-            add(q + ".conv2.weight", 0, dim, 9 * dim);
-            if (!(stride == 1 && cin == dim)) add(q + ".downsample.0.weight", 1, dim, cin);
-        }
-        in_planes = dim;
-    }
-    add(p + ".final_conv.weight", 1, output_dim, c.block_dims[2]);
-}
-
-std::vector<RItem> raft_pack_plan(const a3r_raft_config& c, size_t* total) {
-    std::vector<RItem> v;
-    size_t off = 0;
-    const int d = c.dim;
-    auto add = [&](const std::string& n, int kind, int N, int K) {
-        RItem it{n, kind, N, K, off, 0, 0};
-        if (kind == 2) { off = align_up(off + (size_t)N * 49 * 4, 256); v.push_back(it); return; }
-        if (kind == 3) { off = align_up(off + (size_t)N * K * 4, 256); v.push_back(it); return; }      // direct-conv weight, transposed
-        off = align_up(off + a3r_bf3_w_bytes(N, K), 256);
-        if (kind == 0) { it.tmp = off; off = align_up(off + (size_t)N * K * 4, 256); }
-        v.push_back(it);
-    };
-    add("cnet.conv1.weight", 3, c.initial_dim, 6 * 49);
-    add("fnet.conv1.weight", 3, c.initial_dim, 3 * 49);
-    add("update_block.encoder.convf1.weight", 3, d, 2 * 49);
-    resnet_convs("cnet", c, &v, 2 * d, &off);
-    resnet_convs("fnet", c, &v, 2 * d, &off);
-    add("init_conv.weight", 0, 2 * d, 9 * 2 * d);
-    add("upsample_weight.0.weight", 0, 2 * d, 9 * d);
-    add("upsample_weight.2.weight", 1, 576, 2 * d);
-    add("flow_head.0.weight", 0, 2 * d, 9 * d);
-    add("flow_head.2.weight", 0, 6, 9 * 2 * d);
-    const int cc = c.corr_levels * (2 * c.radius + 1) * (2 * c.radius + 1), ccp = (cc + 31) / 32 * 32;
-    const std::string e = "update_block.encoder.";
-    add(e + "convc1.weight", 1, 2 * d, ccp);
-    add(e + "convc2.weight", 0, d + d / 2, 9 * 2 * d);
-    add(e + "convf2.weight", 0, d / 2, 9 * d);
-    add(e + "conv.weight", 0, d - 2, 9 * 2 * d);
-    for (int i = 0; i < c.num_blocks; i++) {
-        const std::string q = "update_block.refine." + std::to_string(i) + ".";
-        add(q + "dwconv.weight", 2, 3 * d, 49);
-        add(q + "pwconv1.weight", 1, 4 * d, 3 * d);
-        add(q + "pwconv2.weight", 1, 3 * d, 4 * d);
-        add(q + "final.weight", 1, d, 3 * d);
-    }
-    // second image of every conv / linear weight: fh2 form (4 bytes per element); then one line for the range statistic and the
-    // absmax scratch word of the packing pass
-    for (RItem& it : v)
-        if (it.kind == 0 || it.kind == 1) { it.off2 = off; off = align_up(off + (size_t)it.N * it.K * 4, 256); }
-    off = align_up(off + 256, 256);
-    *total = off;
-    return v;
-}
-
-}  // namespace
 
 extern "C" int a3r_raft_create(const a3r_raft_config* cfg, a3r_raft_t* out) {
     A3R_CHECK_ARG(cfg && out, "a3r_raft_create: null argument");
@@ -414,6 +452,7 @@ extern "C" int a3r_raft_create(const a3r_raft_config* cfg, a3r_raft_t* out) {
     a3r_raft_s* m = new (std::nothrow) a3r_raft_s();
     A3R_CHECK_ARG(m, "out of host memory");
     m->cfg = *cfg;
+    raft_pack_plan(m->cfg, m->pack, &m->bound);
     *out = m;
     return A3R_OK;
 }
@@ -431,58 +470,66 @@ extern "C" int a3r_raft_set_weight(a3r_raft_t m, const char* name, const float* 
 }
 
 extern "C" size_t a3r_raft_packed_bytes(a3r_raft_t m) {
-    if (!m) return 0;
-    size_t total = 0;
-    raft_pack_plan(m->cfg, &total);
-    return total;
+    return m ? m->pack.total : 0;
+}
+
+extern "C" int a3r_raft_corr_width(a3r_raft_t m) {
+    return m ? corr_width(m->cfg) : 0;
+}
+
+// One item of the pack plan: its weight into the packed buffer pk, weight and bias into the item's field of the bound weights.
+// A name that was not registered is A3R_ESTATE, a shape that does not fit A3R_EINVAL, either with the name in a3r_last_error.
+static int bind_item(a3r_raft_s* m, const RItem& it, char* pk, TwinTable<std::string>& twins, void* stream) {
+    const char* who = "a3r_raft_finalize";
+    const std::string wn = it.name + ".weight";
+    const float *src, *bias;
+    if (int rc = m->w.need(it.name + ".bias", {it.N}, who, &bias)) return rc;
+    if (it.kind == Pack::NORM) {
+        *it.norm = {nullptr, bias};
+        return m->w.need(wn, {it.N}, who, &it.norm->w);
+    }
+    if (it.kind == Pack::DIRECT) {
+        if (int rc = m->w.need(wn, {it.N, it.K / 49, 7, 7}, who, &src)) return rc;
+        float* wt = reinterpret_cast<float*>(pk + it.off);
+        hipLaunchKernelGGL(transpose_kernel, dim3((it.N * it.K + 255) / 256), dim3(256), 0, as_stream(stream), src, wt, it.N, it.K);
+        A3R_LAUNCH_CHECK();
+        *it.direct = {wt, bias};
+        return A3R_OK;
+    }
+    if (it.kind == Pack::CONV3) {
+        const int cin = it.K / 9;
+        if (int rc = m->w.need(wn, {it.N, cin, 3, 3}, who, &src)) return rc;
+        float* tmp = reinterpret_cast<float*>(pk + it.tmp);
+        if (int rc = a3r_pack_conv3x3(src, tmp, it.N, cin, stream)) return rc;
+        src = tmp;
+    } else {
+        // Linear weights are [N, K]; 1x1 convolutions [N, K, 1, 1]
+        const WeightTable::Ref* wi = m->w.find(wn);
+        if (!wi) { set_error("%s: missing weight '%s'", who, wn.c_str()); return A3R_ESTATE; }
+        const std::vector<int64_t>& sh = wi->shape;
+        const bool ok = (sh.size() == 2 || (sh.size() == 4 && sh[2] == 1 && sh[3] == 1)) && sh[0] == it.N && sh[1] == it.K;
+        A3R_CHECK_ARG(ok, "%s: weight '%s' must be [%d, %d] (or [%d, %d, 1, 1])", who, wn.c_str(), it.N, it.K, it.N, it.K);
+        src = wi->p;
+    }
+    float* scratch = reinterpret_cast<float*>(pk + m->pack.total - 128);     // the absmax word of the fh2 packing
+    if (int rc = twins.pack(wn, Form::BF3, src, pk + it.off, it.N, it.K, nullptr, who, wn.c_str(), stream)) return rc;
+    if (int rc = twins.pack(wn, Form::FH2, src, pk + it.off2, it.N, it.K, scratch, who, wn.c_str(), stream)) return rc;
+    it.conv->w = twins.t[wn];
+    it.conv->b = bias;
+    return A3R_OK;
 }
 
 extern "C" int a3r_raft_finalize(a3r_raft_t m, void* packed, size_t packed_bytes, void* stream) {
     A3R_CHECK_ARG(m && packed, "a3r_raft_finalize: null argument");
-    size_t total = 0;
-    std::vector<RItem> plan = raft_pack_plan(m->cfg, &total);
+    const size_t total = m->pack.total;
     A3R_CHECK_ARG(packed_bytes >= total, "a3r_raft_finalize: packed buffer too small (%zu < %zu)", packed_bytes, total);
     A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(packed) & 255) == 0, "a3r_raft_finalize: packed buffer must be 256-byte aligned");
     char* pk = static_cast<char*>(packed);
-    m->twins.t.clear();
-    m->aux.clear();
+    m->finalized = false;
     m->stat = reinterpret_cast<unsigned*>(pk + total - 256);
-    const char* who = "a3r_raft_finalize";
-    float* scratch = reinterpret_cast<float*>(pk + total - 128);     // the absmax word of the fh2 packing
-    for (const RItem& it : plan) {
-        const float* src;
-        if (it.kind == 0 || it.kind == 1) {
-            if (it.kind == 0) {
-                const int cin = it.K / 9;
-                if (int rc = m->w.need(it.name, {it.N, cin, 3, 3}, who, &src)) return rc;
-                float* tmp = reinterpret_cast<float*>(pk + it.tmp);
-                if (int rc = a3r_pack_conv3x3(src, tmp, it.N, cin, stream)) return rc;
-                src = tmp;
-            } else {
-                // Linear weights are [N, K]; 1x1 convolutions [N, K, 1, 1]
-                const WeightTable::Ref* wi = m->w.find(it.name);
-                if (!wi) { set_error("a3r_raft_finalize: missing weight '%s'", it.name.c_str()); return A3R_ESTATE; }
-                const std::vector<int64_t>& sh = wi->shape;
-                const bool ok = (sh.size() == 2 && sh[0] == it.N && sh[1] == it.K) || (sh.size() == 4 && sh[0] == it.N && sh[1] == it.K && sh[2] == 1 && sh[3] == 1);
-                A3R_CHECK_ARG(ok, "a3r_raft_finalize: weight '%s' must be [%d, %d] (or [%d, %d, 1, 1])", it.name.c_str(), it.N, it.K, it.N, it.K);
-                src = wi->p;
-            }
-            if (int rc = m->twins.pack(it.name, Form::BF3, src, pk + it.off, it.N, it.K, nullptr, who, it.name.c_str(), stream)) return rc;
-            if (int rc = m->twins.pack(it.name, Form::FH2, src, pk + it.off2, it.N, it.K, scratch, who, it.name.c_str(), stream)) return rc;
-        } else if (it.kind == 3) {
-            if (int rc = m->w.need(it.name, {it.N, it.K / 49, 7, 7}, who, &src)) return rc;
-            float* wt = reinterpret_cast<float*>(pk + it.off);
-            hipLaunchKernelGGL(transpose_kernel, dim3((it.N * it.K + 255) / 256), dim3(256), 0, as_stream(stream), src, wt, it.N, it.K);
-            A3R_LAUNCH_CHECK();
-            m->aux[it.name] = wt;
-        } else {
-            if (int rc = m->w.need(it.name, {it.N, 1, 7, 7}, who, &src)) return rc;
-            float* wt = reinterpret_cast<float*>(pk + it.off);
-            hipLaunchKernelGGL(transpose_kernel, dim3((it.N * 49 + 255) / 256), dim3(256), 0, as_stream(stream), src, wt, it.N, 49);
-            A3R_LAUNCH_CHECK();
-            m->aux[it.name] = wt;
-        }
-    }
+    TwinTable<std::string> twins;
+    for (const RItem& it : m->pack.items)
+        if (int rc = bind_item(m, it, pk, twins, stream)) return rc;
     m->finalized = true;
     return A3R_OK;
 }
@@ -496,19 +543,9 @@ struct RPlan {
     int rc = A3R_OK;
     static constexpr const char* WHO = "a3r_raft_forward";
     bool skip() { return ar.skip(rc, WHO); }
-    const float* wptr(const std::string& n) {
-        const WeightTable::Ref* r = m->w.find(n);
-        if (!r && !rc) { set_error("a3r_raft_forward: missing weight '%s'", n.c_str()); rc = A3R_ESTATE; }
-        return r ? r->p : nullptr;
-    }
-    const float* auxw(const std::string& n) {
-        auto it = m->aux.find(n);
-        if (it == m->aux.end()) { if (!rc) { set_error("a3r_raft_forward: weight '%s' was not packed", n.c_str()); rc = A3R_ESTATE; } return nullptr; }
-        return it->second;
-    }
-    OpEpi epi(int kind, const float* bias, const float* resid = nullptr) {
+    OpEpi epi(int kind, const float* resid = nullptr) {      // (the bias is the bound weight's: target)
         OpEpi e = {};
-        e.epi = kind; e.bias = bias; e.resid = resid;
+        e.epi = kind; e.resid = resid;
         return e;
     }
     // Operands ("xo" maps and matrices, out_op / aux_op epilogues) are in form f: FH2 (3 fp16 passes, 4 operand bytes) unless
@@ -517,27 +554,30 @@ struct RPlan {
     // fh2 producer reports max |stored value| into the one word m->stat, which the caller checks against fp16's range after the forward.
     Form f = Form::FH2;
     float* alloc_op(size_t rows, int K) { return ar.alloc(form_floats(Form::BF3, rows, K)); }
-    a3r_epilogue target(const OpEpi& e0, const std::string& name) {
+    a3r_epilogue target(const OpEpi& e0, const float* bias) {
         a3r_epilogue e = retarget(e0, f, [&](a3r_epilogue& r) { r.out_absmax = (r.out_fh2 || r.aux_fh2) ? m->stat : nullptr; });
-        e.bias = wptr(name + ".bias");
+        e.bias = bias;
         return e;
     }
-    // 3x3 convolution `name` (weight / bias) on the operand-form map xo [B, H, W, Cin]
-    void conv3(const float* xo, const std::string& name, float* y, int B, int H, int W, int Cin, int Cout, int stride, const OpEpi& e0) {
+    // 3x3 convolution c on the operand-form map xo [B, H, W, c.K / 9] -> y [B, Ho, Wo, c.N]
+    void conv3(const float* xo, const RConvW& c, float* y, int B, int H, int W, int stride, const OpEpi& e0) {
         if (skip()) return;
-        const a3r_epilogue e = target(e0, name);
-        const Twin* tw = m->twins.get(name + ".weight", f, WHO, rc);
-        if (!rc) rc = op_conv3x3(f, xo, nullptr, tw, y, B, H, W, Cin, Cout, stride, e, stream);
+        rc = op_conv3x3(f, xo, nullptr, &c.w, y, B, H, W, c.K / 9, c.N, stride, target(e0, c.b), stream);
     }
-    void linear(const float* xo, const std::string& name, float* y, int ldc, long M, int N, int K, const OpEpi& e0) {
+    // 1x1 convolution / Linear c on the operand-form rows xo [M, c.K] -> y [M, c.N]
+    void linear(const float* xo, const RConvW& c, float* y, long M, const OpEpi& e0) {
         if (skip()) return;
-        const a3r_epilogue e = target(e0, name);
-        const Twin* tw = m->twins.get(name + ".weight", f, WHO, rc);
-        if (!rc) rc = op_linear(f, xo, 0, nullptr, tw, y, ldc, (int)M, N, K, e, stream);
+        rc = op_linear(f, xo, 0, nullptr, &c.w, y, c.N, (int)M, c.N, c.K, target(e0, c.b), stream);
     }
     void split(const float* x, int ldx, float* yo, long M, int K) {
         if (skip()) return;
         rc = op_split(f, x, ldx, yo, M, K, false, 1.f, m->stat, stream);
+    }
+    // LayerNorm (eps 1e-6) of the fp32 rows x [M, C] into operand form
+    void layernorm(const float* x, const RNormW& n, float* yo, long M, int C) {
+        if (skip()) return;
+        rc = f == Form::FH2 ? a3r_layernorm_fh2(x, n.w, n.b, yo, (int)M, C, 1e-6f, 1.f, m->stat, stream)
+                            : a3r_layernorm_bf3(x, n.w, n.b, yo, (int)M, C, 1e-6f, 0, stream);
     }
     template <class F> void launch(F&& f) {
         if (skip()) return;
@@ -547,196 +587,213 @@ struct RPlan {
     void pack_cols(float* dst, int ldd, int c0, const float* src, int lds, int Cs, long rows) {
         launch([&](hipStream_t st) { hipLaunchKernelGGL(pack_cols_kernel, dim3(grid1d(rows * Cs)), dim3(256), 0, st, dst, ldd, c0, src, lds, Cs, rows); });
     }
+    // n floats device to device: the given feature maps, the correlation's copy of fmap1, and the taps (dst null: not asked for)
+    void copy(float* dst, const float* src, size_t n) {
+        if (skip() || !dst) return;
+        if (hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToDevice, as_stream(stream)) != hipSuccess) { set_error("a3r_raft_forward: device copy failed"); rc = A3R_EHIP; }
+    }
+    // a 7x7 direct convolution (padding 3, ReLU) of B maps [H, W] -> y [B, Ho, Wo, Cout]; src: where input element (b, c, y, x) sits
+    struct Planes { const float *x0, *x1; int c0, c1; long sb, sc, sy, sx; float in_mul, in_add; };
+    void conv7(const RDirectW& w, const Planes& src, int B, int H, int W, int stride, int Cout, float* y) {
+        DirectConvArgs a = {};
+        a.x0 = src.x0; a.x1 = src.x1; a.c0 = src.c0; a.c1 = src.c1;
+        a.sb = src.sb; a.sc = src.sc; a.sy = src.sy; a.sx = src.sx;
+        a.B = B; a.H = H; a.W = W; a.k = 7; a.stride = stride; a.pad = 3;
+        a.Ho = (H - 1) / stride + 1; a.Wo = (W - 1) / stride + 1; a.Cout = Cout;
+        a.in_mul = src.in_mul; a.in_add = src.in_add;
+        a.w = w.wt; a.bias = w.b; a.relu = 1; a.y = y;
+        launch([&](hipStream_t st) { launch_direct_conv(a, st); });
+    }
 };
 
 // ResNetFPN.forward (extractor.py:338-350) after the stem: s = relu(bn1(conv1(x))) [nimg, H2, W2, C0] fp32 is given.  Writes
 // final_conv's output to out (fp32 [nimg, h, w, out_dim]) or, when out3 is given, in operand form to out3.
-void resnet(RPlan& P, const std::string& p, float* s, int nimg, int H2, int W2, float* out, float* out3, int out_dim) {
-    const a3r_raft_config& c = P.m->cfg;
+void resnet(RPlan& P, const REncoderW& enc, float* s, int nimg, int H2, int W2, float* out, float* out3) {
     Arena& ar = P.ar;
-    int h = H2, w = W2, in_planes = c.initial_dim;
+    int h = H2, w = W2;
+    const int C0 = P.m->cfg.initial_dim;
     const float* x = s;                                  // fp32 block input
-    float* x3 = P.alloc_op((size_t)nimg * h * w, in_planes);
-    P.split(x, in_planes, x3, (long)nimg * h * w, in_planes);
-    for (int li = 0; li < 3; li++) {
-        const int dim = c.block_dims[li];
-        for (int bi = 0; bi < c.n_blocks[li]; bi++) {
-            const std::string q = p + ".layer" + std::to_string(li + 1) + "." + std::to_string(bi);
-            const int cin = bi == 0 ? in_planes : dim, stride = bi == 0 && li > 0 ? 2 : 1;
-            const int ho = (h - 1) / stride + 1, wo = (w - 1) / stride + 1;
-            const size_t px = (size_t)nimg * ho * wo;
-            // y = relu(bn1(conv1(x)))                                                        layer.py:134
-            float* y3 = P.alloc_op(px, dim);
-            OpEpi e1 = P.epi(A3R_EPI_RELU, nullptr);
-            e1.out_op = 1;
-            P.conv3(x3, q + ".conv1", y3, nimg, h, w, cin, dim, stride, e1);
-            // shortcut: x, or bn3(conv1x1 stride s (x))                                      layer.py:122-129,137-138
-            const float* sc = x;
-            if (!(stride == 1 && cin == dim)) {
-                const float* g3 = x3;
-                if (stride == 2) {
-                    float* gx = ar.alloc(px * cin);
-                    P.launch([&](hipStream_t st) {
-                        hipLaunchKernelGGL(gather_s2_kernel, dim3(grid1d((long)px * cin / 4)), dim3(256), 0, st, x, gx, nimg, h, w, ho, wo, cin / 4);
-                    });
-                    float* gx3 = P.alloc_op(px, cin);
-                    P.split(gx, cin, gx3, (long)px, cin);
-                    g3 = gx3;
-                }
-                float* scb = ar.alloc(px * dim);
-                P.linear(g3, q + ".downsample.0", scb, dim, (long)px, dim, cin, P.epi(A3R_EPI_NONE, nullptr));
-                sc = scb;
+    float* x3 = P.alloc_op((size_t)nimg * h * w, C0);
+    P.split(x, C0, x3, (long)nimg * h * w, C0);
+    for (const RBlockW& b : enc.blocks) {
+        const int cin = b.cin, dim = b.dim;
+        const int ho = (h - 1) / b.stride + 1, wo = (w - 1) / b.stride + 1;
+        const size_t px = (size_t)nimg * ho * wo;
+        // y = relu(bn1(conv1(x)))                                                        layer.py:134
+        float* y3 = P.alloc_op(px, dim);
+        OpEpi e1 = P.epi(A3R_EPI_RELU);
+        e1.out_op = 1;
+        P.conv3(x3, b.conv1, y3, nimg, h, w, b.stride, e1);
+        // shortcut: x, or bn3(conv1x1 stride s (x))                                      layer.py:122-129,137-138
+        const float* sc = x;
+        if (b.project) {
+            const float* g3 = x3;
+            if (b.stride == 2) {
+                float* gx = ar.alloc(px * cin);
+                P.launch([&](hipStream_t st) {
+                    hipLaunchKernelGGL(gather_s2_kernel, dim3(grid1d((long)px * cin / 4)), dim3(256), 0, st, x, gx, nimg, h, w, ho, wo, cin / 4);
+                });
+                float* gx3 = P.alloc_op(px, cin);
+                P.split(gx, cin, gx3, (long)px, cin);
+                g3 = gx3;
             }
-            // y = relu(bn2(conv2(y))); out = relu(shortcut + y)                              layer.py:135-141: ONE launch
-            float* o = ar.alloc(px * dim);
-            float* o3 = P.alloc_op(px, dim);
-            OpEpi e2 = P.epi(A3R_EPI_RESID, nullptr, sc);
-            e2.relu_acc = 1; e2.relu_out = 1; e2.aux_op = o3;
-            P.conv3(y3, q + ".conv2", o, nimg, ho, wo, dim, dim, 1, e2);
-            x = o; x3 = o3; h = ho; w = wo;
+            float* scb = ar.alloc(px * dim);
+            P.linear(g3, b.down, scb, (long)px, P.epi(A3R_EPI_NONE));
+            sc = scb;
         }
-        in_planes = dim;
+        // y = relu(bn2(conv2(y))); out = relu(shortcut + y)                              layer.py:135-141: ONE launch
+        float* o = ar.alloc(px * dim);
+        float* o3 = P.alloc_op(px, dim);
+        OpEpi e2 = P.epi(A3R_EPI_RESID, sc);
+        e2.relu_acc = 1; e2.relu_out = 1; e2.aux_op = o3;
+        P.conv3(y3, b.conv2, o, nimg, ho, wo, 1, e2);
+        x = o; x3 = o3; h = ho; w = wo;
     }
-    OpEpi ef = P.epi(A3R_EPI_NONE, nullptr);
+    OpEpi ef = P.epi(A3R_EPI_NONE);
     if (out3) ef.out_op = 1;
-    P.linear(x3, p + ".final_conv", out3 ? out3 : out, out_dim, (long)nimg * h * w, out_dim, c.block_dims[2], ef);
+    P.linear(x3, enc.final_conv, out3 ? out3 : out, (long)nimg * h * w, ef);
 }
 
-// RAFT2.forward(test_mode=True) (raft.py:185-246) for B pairs.  img1 / img2 [B, 3, H, W] with values in [0, 255]; flow_out [B, 2, H, W]
-// (the last prediction; the reference up-samples every iteration's flow and returns the list, its caller keeps `[1]`).
-// taps: optional intermediate copies for the parity tests (any pointer may be null).
-// phase 0: the whole forward (fmap1_in / fmap2_in given: the feature network is skipped and those per-frame features are used);
-// phase 1: the feature network alone on B frames `img1` -> fmap_out [B, h, w, 2 dim] (a3r_raft_encode)
-int raft_plan(a3r_raft_s* m, bool dry, const float* img1, const float* img2, int B, int H, int W, int iters, float* flow_out, void* ws,
-              size_t ws_bytes, void* stream, size_t* peak, const a3r_raft_taps* taps, int phase = 0, const float* fmap1_in = nullptr,
-              const float* fmap2_in = nullptr, float* fmap_out = nullptr) {
-    const a3r_raft_config& c = m->cfg;
-    const int d = c.dim, h = H / 8, w = W / 8, H2 = (H - 1) / 2 + 1, W2 = (W - 1) / 2 + 1;
-    const long hw = (long)h * w, Bhw = (long)B * hw;
-    const int win = 2 * c.radius + 1, cc = c.corr_levels * win * win, ccp = (cc + 31) / 32 * 32;
-    RPlan P;
-    P.m = m; P.stream = stream; P.f = m->use_fh2 ? Form::FH2 : Form::BF3;
-    const bool fh2 = P.f == Form::FH2;
-    P.ar = {static_cast<char*>(ws), 0, ws_bytes, dry, 0};
+// ---- one call of the plan.  phase 0: RAFT2.forward(test_mode=True) (raft.py:185-246) for B pairs, img1 / img2 [B, 3, H, W] with
+// values in [0, 255] -> flow_out [B, 2, H, W] (the last prediction; the reference up-samples every iteration's flow and returns the
+// list, its caller keeps `[1]`); with fmap1_in / fmap2_in the feature network is skipped and those per-frame features are used.
+// phase 1: the feature network alone on the B frames img1 -> fmap_out [B, h, w, 2 dim] (a3r_raft_encode).
+// taps: optional intermediate copies for the parity tests (any pointer may be null).  dry: the sizing pass (every pointer null).
+struct RaftCall {
+    int phase = 0, B = 0, H = 0, W = 0, iters = 0;
+    bool dry = false;
+    const float *img1 = nullptr, *img2 = nullptr, *fmap1_in = nullptr, *fmap2_in = nullptr;
+    float *fmap_out = nullptr, *flow_out = nullptr;
+    a3r_raft_taps taps = {};
+    void *ws = nullptr, *stream = nullptr;
+    size_t ws_bytes = 0;
+};
+
+// its shapes: hidden width d and feature width D, the eighth-resolution map h x w (hw pixels, Bhw in the batch), the stems' half
+// resolution, the correlation window and feature count (cc, padded: ccp), and the pyramid's levels
+struct RaftDims {
+    const a3r_raft_config& c;
+    int B, H, W, d, D, h, w, H2, W2;
+    long hw, Bhw;
+    int win, cc, ccp, hl[4], wl[4];
+    RaftDims(const a3r_raft_config& c_, const RaftCall& k)
+        : c(c_), B(k.B), H(k.H), W(k.W), d(c.dim), D(2 * c.dim), h(k.H / 8), w(k.W / 8), H2((k.H - 1) / 2 + 1), W2((k.W - 1) / 2 + 1),
+          hw((long)h * w), Bhw(B * hw), win(2 * c.radius + 1), cc(c.corr_levels * win * win), ccp(corr_width(c)) {
+        for (int l = 0, a = h, b = w; l < 4; l++, a /= 2, b /= 2) { hl[l] = a; wl[l] = b; }      // corr.py:22
+    }
+    size_t stem_floats() const { return (size_t)B * H2 * W2 * c.initial_dim; }      // one stem's output
+};
+
+// the buffers that outlive a stage (allocated below the arena mark the stages release to)
+struct RState {
+    float* cn;           // init_conv output: [net | context]
+    float* fm3;          // fnet(image1), fnet(image2) in operand form (rows: all of image1, then image2)
+    float* fm;           // the same in fp32 (the pyramid's 2x2 means, the taps)
+    float* corr[4];      // the correlation pyramid
+    float* net;          // hidden state
+    float* X;            // [net | context | motion features]: the ConvNeXt blocks' input (update.py:170-173)
+    float* flow8;        // coarse flow
+    float* fu;           // flow_head output: flow update (2) + info (4)
+    float* wgt;          // .25 * upsample_weight(net)
+};
+// the scratch of the heads and of one iteration, allocated once above the mark (names ending in 3: operand form)
+struct RIter { float *n3, *t3, *lk, *lk3, *c13, *cf, *tmp, *f1, *f13, *cf3, *dw, *ln3, *hid3, *S, *S3; };
+
+// a 7x7 stem on image planes [B, 3, H, W] in [0, 255], normalised to 2 x / 255 - 1 on the way in (raft.py:194-195); x1: a second
+// image, concatenated along channels (raft.py:207)
+void stem(RPlan& P, const RDirectW& w, const float* x0, const float* x1, const RaftDims& g, float* y) {
+    const RPlan::Planes src = {x0, x1, 3, x1 ? 3 : 0, 3L * g.H * g.W, (long)g.H * g.W, g.W, 1, 2.f / 255.f, -1.f};
+    P.conv7(w, src, g.B, g.H, g.W, 2, g.c.initial_dim, y);
+}
+
+// context network on cat(image1, image2) and init_conv (raft.py:207-209); net, context = split(cnet) (raft.py:210)
+void context_stage(RPlan& P, const RaftCall& k, const RaftDims& g, const RState& v) {
+    const RaftW& wt = P.m->bound;
+    {
+        ArenaScope scope(P.ar);
+        float* s = P.ar.alloc(g.stem_floats());
+        stem(P, wt.cnet.stem, k.img1, k.img2, g, s);
+        float* c3 = P.alloc_op(g.Bhw, g.D);
+        resnet(P, wt.cnet, s, g.B, g.H2, g.W2, nullptr, c3);
+        P.conv3(c3, wt.init_conv, v.cn, g.B, g.h, g.w, 1, P.epi(A3R_EPI_NONE));
+    }
+    P.copy(k.taps.cnet, v.cn, (size_t)g.Bhw * g.D);
+    P.pack_cols(v.net, g.d, 0, v.cn, g.D, g.d, g.Bhw);
+    P.pack_cols(v.X, 3 * g.d, g.d, v.cn + g.d, g.D, g.d, g.Bhw);
+}
+
+// feature network (raft.py:222-223; its rows do not depend on what else is in the batch) on both images -> out [2 B, h, w, D], or
+// the per-frame features a3r_raft_encode computed once, copied there.  Phase 1: on the B frames img1 -> out [B, h, w, D]
+void feature_stage(RPlan& P, const RaftCall& k, const RaftDims& g, float* out) {
+    ArenaScope scope(P.ar);
+    if (k.fmap1_in && k.fmap2_in) {
+        const size_t n = (size_t)g.Bhw * g.D;
+        P.copy(out, k.fmap1_in, n);
+        P.copy(out + n, k.fmap2_in, n);
+        return;
+    }
+    const REncoderW& fnet = P.m->bound.fnet;
+    const int sides = k.phase == 1 ? 1 : 2;
+    float* s = P.ar.alloc(sides * g.stem_floats());
+    stem(P, fnet.stem, k.img1, nullptr, g, s);
+    if (sides == 2) stem(P, fnet.stem, k.img2, nullptr, g, s + g.stem_floats());
+    if (k.phase == 1 && k.dry) P.ar.alloc(g.Bhw * g.D);      // (a3r_raft_encode's sizing has always counted the output map)
+    resnet(P, fnet, s, sides * g.B, g.H2, g.W2, out, nullptr);
+}
+
+// fh2 operands of the correlation: feature maps have no fixed magnitude (a checkpoint's final_conv decides it), and two fp16 planes
+// at scale 1 are fp32-grade only while max|x| is in [2^-2, 2^15] (fh2.h).  So every image's map is stored with its own power of two,
+// the one a weight matrix would get (max|s x| in [2^12, 2^13)), from that image's max|fmap| -- read back here: the ONE wait on the
+// stream of an fh2 call (bf3 calls have none).  Per image, not per batch: a pair's flow must not depend on what else is in the batch.
+// s1 / s2 [B]: the scales of fmap1 / sqrt(D) and of fmap2, 1 on entry; amx: 2 B device words.
+void corr_scales(RPlan& P, const RaftDims& g, const float* fm, float* amx, std::vector<float>& s1, std::vector<float>& s2) {
+    if (P.f != Form::FH2 || P.skip()) return;
+    const int B = g.B;
+    std::vector<float> mx(2 * B, 0.f);
+    hipStream_t st = as_stream(P.stream);
+    const long n_per = g.hw * g.D;
+    bool ok = hipMemsetAsync(amx, 0, (size_t)2 * B * 4, st) == hipSuccess;
+    if (ok) {
+        const long blocks = (n_per + 1023) / 1024;
+        hipLaunchKernelGGL(image_absmax_kernel, dim3((unsigned)(blocks < 64 ? blocks : 64), 2 * B), dim3(256), 0, st, fm, n_per, reinterpret_cast<unsigned*>(amx));
+        ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(mx.data(), amx, (size_t)2 * B * 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipStreamSynchronize(st) == hipSuccess;
+    }
+    if (!ok) { set_error("a3r_raft_forward: reading the feature maps' range failed"); P.rc = A3R_EHIP; }
+    for (int b = 0; b < B && ok; b++) {                     // (zero / non-finite maximum: scale 1; the split then reports it)
+        s1[b] = a3r_fh2_weight_scale(mx[b] / sqrtf((float)g.D));
+        s2[b] = a3r_fh2_weight_scale(mx[B + b]);
+    }
+}
+
+// the correlation pyramid (corr.py:11-23): corr_l[b] = fmap1[b] @ fmap2_l[b]^T / sqrt(dim) (corr.py:53-60).  fmap1 is scaled once;
+// fmap2_l, 2 x 2 means of level l - 1, enters as the GEMM's weight operand
+void corr_stage(RPlan& P, const RaftCall& k, const RaftDims& g, const RState& v) {
     Arena& ar = P.ar;
-    if (!dry && fh2 && m->stat && hipMemsetAsync(m->stat, 0, 4, as_stream(stream)) != hipSuccess) {
-        set_error("a3r_raft_forward: clearing the range statistic failed");
-        return A3R_EHIP;
-    }
-    auto tap = [&](float* dst, const float* src, size_t n) {
-        if (dry || P.rc || !dst) return;
-        if (hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToDevice, as_stream(stream)) != hipSuccess) { set_error("a3r_raft_forward: tap copy failed"); P.rc = A3R_EHIP; }
-    };
-    if (phase == 1) {
-        // the feature network on B frames: fnet(2 x / 255 - 1) (raft.py:222-223); its rows do not depend on what else is in the batch
-        float* s = ar.alloc((size_t)B * H2 * W2 * c.initial_dim);
-        P.launch([&](hipStream_t st) {
-            DirectConvArgs a = {img1, nullptr, 3, 0, 3L * H * W, (long)H * W, W, 1, B, H, W, 7, 2, 3, H2, W2, c.initial_dim, 2.f / 255.f, -1.f,
-                                P.auxw("fnet.conv1.weight"), P.wptr("fnet.conv1.bias"), 1, s};
-            launch_direct_conv(a, st);
-        });
-        float* fo = dry ? ar.alloc(Bhw * 2 * d) : fmap_out;
-        resnet(P, "fnet", s, B, H2, W2, fo, nullptr, 2 * d);
-        if (peak) *peak = ar.peak;
-        return P.rc;
-    }
-    // ---------------- persistent buffers
-    float* cn = ar.alloc(Bhw * 2 * d);                  // init_conv output: [net | context]
-    float* fm3 = P.alloc_op(2 * Bhw, 2 * d);             // fnet(image1), fnet(image2) in operand form (rows: all of image1, then image2)
-    float* fm = ar.alloc(2 * Bhw * 2 * d);              // the same in fp32 (the pyramid's 2x2 means, the taps)
-    float* corr[4] = {nullptr, nullptr, nullptr, nullptr};
-    int hl[4], wl[4];
+    const int B = g.B, D = g.D;
+    const long hw = g.hw, Bhw = g.Bhw;
+    const bool fh2 = P.f == Form::FH2;
+    unsigned* stat = P.m->stat;
     {
-        int a = h, b = w;
-        for (int l = 0; l < c.corr_levels; l++) { hl[l] = a; wl[l] = b; corr[l] = ar.alloc((size_t)Bhw * a * b); a /= 2; b /= 2; }
-    }
-    float* net = ar.alloc(Bhw * d);
-    float* X = ar.alloc(Bhw * 3 * d);                   // [net | context | motion features]: the ConvNeXt blocks' input (update.py:170-173)
-    float* flow8 = ar.alloc(Bhw * 2);
-    float* fu = ar.alloc(Bhw * 6);                      // flow_head output: flow update (2) + info (4)
-    float* wgt = ar.alloc(Bhw * 576);
-    const size_t mark = ar.off;
-    // ---------------- context network on cat(image1, image2) (raft.py:207-209)
-    {
-        float* s = ar.alloc((size_t)B * H2 * W2 * c.initial_dim);
-        P.launch([&](hipStream_t st) {
-            DirectConvArgs a = {img1, img2, 3, 3, 3L * H * W, (long)H * W, W, 1, B, H, W, 7, 2, 3, H2, W2, c.initial_dim, 2.f / 255.f, -1.f,
-                                P.auxw("cnet.conv1.weight"), P.wptr("cnet.conv1.bias"), 1, s};
-            launch_direct_conv(a, st);
-        });
-        float* c3 = P.alloc_op(Bhw, 2 * d);
-        resnet(P, "cnet", s, B, H2, W2, nullptr, c3, 2 * d);
-        P.conv3(c3, "init_conv", cn, B, h, w, 2 * d, 2 * d, 1, P.epi(A3R_EPI_NONE, nullptr));
-    }
-    ar.off = mark;
-    tap(taps ? taps->cnet : nullptr, cn, (size_t)Bhw * 2 * d);
-    // net, context = split(cnet) (raft.py:210)
-    P.pack_cols(net, d, 0, cn, 2 * d, d, Bhw);
-    P.pack_cols(X, 3 * d, d, cn + d, 2 * d, d, Bhw);
-    // ---------------- feature network on both images (raft.py:222-223) and the correlation pyramid (corr.py:11-23)
-    if (fmap1_in && fmap2_in) {                                      // per-frame features computed once by a3r_raft_encode
-        if (!P.skip()) {
-            const size_t bytes = (size_t)Bhw * 2 * d * 4;
-            if (hipMemcpyAsync(fm, fmap1_in, bytes, hipMemcpyDeviceToDevice, as_stream(stream)) != hipSuccess ||
-                hipMemcpyAsync(fm + (size_t)Bhw * 2 * d, fmap2_in, bytes, hipMemcpyDeviceToDevice, as_stream(stream)) != hipSuccess) {
-                set_error("a3r_raft_forward_features: copy failed"); P.rc = A3R_EHIP;
-            }
-        }
-    } else {
-        float* s = ar.alloc((size_t)2 * B * H2 * W2 * c.initial_dim);
-        for (int k = 0; k < 2; k++)
-            P.launch([&](hipStream_t st) {
-                DirectConvArgs a = {k ? img2 : img1, nullptr, 3, 0, 3L * H * W, (long)H * W, W, 1, B, H, W, 7, 2, 3, H2, W2, c.initial_dim, 2.f / 255.f, -1.f,
-                                    P.auxw("fnet.conv1.weight"), P.wptr("fnet.conv1.bias"), 1, s + (size_t)k * B * H2 * W2 * c.initial_dim};
-                launch_direct_conv(a, st);
-            });
-        resnet(P, "fnet", s, 2 * B, H2, W2, fm, nullptr, 2 * d);
-    }
-    ar.off = mark;
-    tap(taps ? taps->fmap : nullptr, fm, (size_t)2 * Bhw * 2 * d);
-    {
-        // corr_l[b] = fmap1[b] @ fmap2_l[b]^T / sqrt(dim) (corr.py:53-60): fmap1 is scaled once, fmap2_l enters as the GEMM's weight operand
-        const int D = 2 * d;
+        ArenaScope scope(ar);
         float* f1s = ar.alloc(Bhw * D);
-        if (!P.skip()) {
-            if (hipMemcpyAsync(f1s, fm, (size_t)Bhw * D * 4, hipMemcpyDeviceToDevice, as_stream(stream)) != hipSuccess) { set_error("a3r_raft_forward: copy failed"); P.rc = A3R_EHIP; }
-        }
+        P.copy(f1s, v.fm, (size_t)Bhw * D);
         P.launch([&](hipStream_t st) { hipLaunchKernelGGL(scale_kernel, dim3(grid1d(Bhw * D)), dim3(256), 0, st, f1s, 1.f / sqrtf((float)D), Bhw * D); });
-        // fh2 operands of the correlation: feature maps have no fixed magnitude (a checkpoint's final_conv decides it), and two fp16
-        // planes at scale 1 are fp32-grade only while max|x| is in [2^-2, 2^15] (fh2.h).  So every image's map is stored with its own
-        // power of two, the one a weight matrix would get (max|s x| in [2^12, 2^13)), from that image's max|fmap| -- read back here,
-        // one wait per call.  Per image, not per batch: a pair's flow must not depend on what else is in the batch.
         std::vector<float> s1(B, 1.f), s2(B, 1.f);
         float* amx = ar.alloc(2 * B);
-        if (fh2 && !P.skip()) {
-            std::vector<float> mx(2 * B, 0.f);
-            hipStream_t st = as_stream(stream);
-            const long n_per = hw * D;
-            bool ok = hipMemsetAsync(amx, 0, (size_t)2 * B * 4, st) == hipSuccess;
-            if (ok) {
-                const long blocks = (n_per + 1023) / 1024;
-                hipLaunchKernelGGL(image_absmax_kernel, dim3((unsigned)(blocks < 64 ? blocks : 64), 2 * B), dim3(256), 0, st, fm, n_per, reinterpret_cast<unsigned*>(amx));
-                ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(mx.data(), amx, (size_t)2 * B * 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
-                     hipStreamSynchronize(st) == hipSuccess;
-            }
-            if (!ok) { set_error("a3r_raft_forward: reading the feature maps' range failed"); P.rc = A3R_EHIP; }
-            for (int b = 0; b < B && ok; b++) {                     // (zero / non-finite maximum: scale 1; the split then reports it)
-                s1[b] = a3r_fh2_weight_scale(mx[b] / sqrtf((float)D));
-                s2[b] = a3r_fh2_weight_scale(mx[B + b]);
-            }
-        }
+        corr_scales(P, g, v.fm, amx, s1, s2);
         if (fh2) {
             for (int b = 0; b < B && !P.skip(); b++)
-                P.rc = op_split(P.f, f1s + (size_t)b * hw * D, D, fm3 + form_floats(P.f, (size_t)b * hw, D), hw, D, false, s1[b], m->stat, stream);
+                P.rc = op_split(P.f, f1s + (size_t)b * hw * D, D, v.fm3 + form_floats(P.f, (size_t)b * hw, D), hw, D, false, s1[b], stat, P.stream);
         } else {
-            P.split(f1s, D, fm3, Bhw, D);
+            P.split(f1s, D, v.fm3, Bhw, D);
         }
-        float* f2 = fm + (size_t)Bhw * D;                           // level 0 of fmap2
-        float* f2n = ar.alloc((size_t)B * (h / 2) * (w / 2) * D);
-        float* f2m = ar.alloc((size_t)B * (h / 4 > 0 ? h / 4 : 1) * (w / 4 > 0 ? w / 4 : 1) * D);
+        float* f2 = v.fm + (size_t)Bhw * D;                         // level 0 of fmap2
+        float* f2n = ar.alloc((size_t)B * (g.h / 2) * (g.w / 2) * D);
+        float* f2m = ar.alloc((size_t)B * (g.h / 4 > 0 ? g.h / 4 : 1) * (g.w / 4 > 0 ? g.w / 4 : 1) * D);
         float* w3 = ar.alloc((size_t)a3r_bf3_w_bytes(hw, D) / 4 + 64);
-        for (int l = 0; l < c.corr_levels; l++) {
-            const long n2 = (long)hl[l] * wl[l];
+        for (int l = 0; l < g.c.corr_levels; l++) {
+            const long n2 = (long)g.hl[l] * g.wl[l];
             for (int b = 0; b < B; b++) {
                 if (P.skip()) break;
                 // fmap2_l[b] in the weight layout of the form, with image b's scale under fh2
@@ -744,131 +801,198 @@ int raft_plan(a3r_raft_s* m, bool dry, const float* img1, const float* img2, int
                 a3r_epilogue e = {};
                 if (fh2) e.x_scale = s1[b];
                 const Twin tw = {w3, w3, s2[b]};
-                P.rc = op_split(P.f, f2 + (size_t)b * n2 * D, D, w3, n2, D, /*row_pair=*/true, s2[b], m->stat, stream);
-                if (!P.rc) P.rc = op_linear(P.f, fm3 + form_floats(P.f, (size_t)b * hw, D), 0, nullptr, &tw, corr[l] + (size_t)b * hw * n2, (int)n2, (int)hw, (int)n2, D, e, stream);
+                P.rc = op_split(P.f, f2 + (size_t)b * n2 * D, D, w3, n2, D, /*row_pair=*/true, s2[b], stat, P.stream);
+                if (!P.rc) P.rc = op_linear(P.f, v.fm3 + form_floats(P.f, (size_t)b * hw, D), 0, nullptr, &tw, v.corr[l] + (size_t)b * hw * n2, (int)n2, (int)hw, (int)n2, D, e, P.stream);
             }
-            if (l + 1 < c.corr_levels) {                             // fmap2 <- interpolate(fmap2, 0.5) (corr.py:22)
+            if (l + 1 < g.c.corr_levels) {                           // fmap2 <- interpolate(fmap2, 0.5) (corr.py:22)
                 float* dst = (f2 == f2n) ? f2m : f2n;
-                const int ha = hl[l], wa = wl[l], hb = hl[l + 1], wb = wl[l + 1];
+                const int ha = g.hl[l], wa = g.wl[l], hb = g.hl[l + 1], wb = g.wl[l + 1];
                 const float* src = f2;
                 P.launch([&](hipStream_t st) { hipLaunchKernelGGL(halve_kernel, dim3(grid1d((long)B * hb * wb * D)), dim3(256), 0, st, src, dst, B, ha, wa, hb, wb, D); });
                 f2 = dst;
             }
         }
     }
-    ar.off = mark;
-    if (taps) for (int l = 0; l < c.corr_levels; l++) tap(taps->corr_pyr[l], corr[l], (size_t)Bhw * hl[l] * wl[l]);
-    // ---------------- heads on a hidden state (raft.py:213-216, 230-231): fu = flow_head(net), wgt = .25 * upsample_weight(net)
-    float* n3 = P.alloc_op(Bhw, d);
-    float* t3 = P.alloc_op(Bhw, 2 * d);
-    auto heads = [&]() {
-        P.split(net, d, n3, Bhw, d);
-        OpEpi er = P.epi(A3R_EPI_RELU, nullptr);
-        er.out_op = 1;
-        P.conv3(n3, "flow_head.0", t3, B, h, w, d, 2 * d, 1, er);
-        P.conv3(t3, "flow_head.2", fu, B, h, w, 2 * d, 6, 1, P.epi(A3R_EPI_NONE, nullptr));
-        P.conv3(n3, "upsample_weight.0", t3, B, h, w, d, 2 * d, 1, er);
-        P.linear(t3, "upsample_weight.2", wgt, 576, Bhw, 576, 2 * d, P.epi(A3R_EPI_NONE, nullptr));
-    };
-    heads();
-    tap(taps ? taps->flow_update0 : nullptr, fu, (size_t)Bhw * 6);
-    tap(taps ? taps->weight0 : nullptr, wgt, (size_t)Bhw * 576);
-    P.pack_cols(flow8, 2, 0, fu, 6, 2, Bhw);                         // flow_8x = flow_update[:, :2] (raft.py:217)
-    // ---------------- iterations (raft.py:225-238)
-    float* lk = ar.alloc(Bhw * ccp);
-    float* lk3 = P.alloc_op(Bhw, ccp);
-    float* c13 = P.alloc_op(Bhw, 2 * d);
-    float* cf = ar.alloc(Bhw * 2 * d);                                // cat([cor, flo]) (update.py:113)
-    float* tmp = ar.alloc(Bhw * 2 * d);
-    float* f1 = ar.alloc(Bhw * d);
-    float* f13 = P.alloc_op(Bhw, d);
-    float* cf3 = P.alloc_op(Bhw, 2 * d);
-    float* dw = ar.alloc(Bhw * 3 * d);
-    float* ln3 = P.alloc_op(Bhw, 3 * d);
-    float* hid3 = P.alloc_op(Bhw, 4 * d);
-    float* S = ar.alloc(Bhw * 3 * d);
-    float* S3 = P.alloc_op(Bhw, 3 * d);
-    const std::string enc = "update_block.encoder.";
-    for (int it = 0; it < iters; it++) {
-        // corr = corr_fn(coords_grid + flow_8x) (raft.py:227-228)
+    for (int l = 0; l < g.c.corr_levels; l++) P.copy(k.taps.corr_pyr[l], v.corr[l], (size_t)Bhw * g.hl[l] * g.wl[l]);
+}
+
+// heads on the hidden state (raft.py:213-216, 230-231): fu = flow_head(net), wgt = .25 * upsample_weight(net)
+void heads(RPlan& P, const RaftDims& g, const RState& v, const RIter& t) {
+    const RHeadsW& hd = P.m->bound.heads;
+    P.split(v.net, g.d, t.n3, g.Bhw, g.d);
+    OpEpi er = P.epi(A3R_EPI_RELU);
+    er.out_op = 1;
+    P.conv3(t.n3, hd.flow0, t.t3, g.B, g.h, g.w, 1, er);
+    P.conv3(t.t3, hd.flow2, v.fu, g.B, g.h, g.w, 1, P.epi(A3R_EPI_NONE));
+    P.conv3(t.n3, hd.up0, t.t3, g.B, g.h, g.w, 1, er);
+    P.linear(t.t3, hd.up2, v.wgt, g.Bhw, P.epi(A3R_EPI_NONE));
+}
+
+// corr = corr_fn(coords_grid + flow_8x) (raft.py:227-228) -> lk [Bhw, ccp]
+void lookup(RPlan& P, const RaftDims& g, const RState& v, const RIter& t) {
+    LookupArgs a = {};
+    for (int l = 0; l < g.c.corr_levels; l++) { a.corr[l] = v.corr[l]; a.hl[l] = g.hl[l]; a.wl[l] = g.wl[l]; }
+    a.flow = v.flow8; a.out = t.lk; a.ldo = g.ccp; a.B = g.B; a.h = g.h; a.w = g.w; a.r = g.c.radius; a.levels = g.c.corr_levels;
+    P.launch([&](hipStream_t st) { hipLaunchKernelGGL(corr_lookup_kernel, dim3(grid1d(g.Bhw * g.ccp)), dim3(256), 0, st, a); });
+}
+
+// BasicMotionEncoder2 (update.py:99-117): lk, flow8 -> the motion features, columns 2 d .. 3 d of X
+void motion_encoder(RPlan& P, const RaftDims& g, const RState& v, const RIter& t) {
+    const RMotionW& me = P.m->bound.enc;
+    const int B = g.B, h = g.h, w = g.w, d = g.d;
+    const long Bhw = g.Bhw;
+    P.split(t.lk, g.ccp, t.lk3, Bhw, g.ccp);
+    OpEpi er = P.epi(A3R_EPI_RELU);
+    er.out_op = 1;
+    P.linear(t.lk3, me.convc1, t.c13, Bhw, er);                                         // cor = relu(convc1(corr))
+    P.conv3(t.c13, me.convc2, t.tmp, B, h, w, 1, P.epi(A3R_EPI_RELU));                   // cor = relu(convc2(cor))
+    P.pack_cols(t.cf, 2 * d, 0, t.tmp, d + d / 2, d + d / 2, Bhw);
+    // flo = relu(convf1(flow)): 7x7 on the 2 channels of the channels-last coarse flow
+    const RPlan::Planes flow = {v.flow8, nullptr, 2, 0, g.hw * 2, 1, (long)w * 2, 2, 1.f, 0.f};
+    P.conv7(me.convf1, flow, B, h, w, 1, d, t.f1);
+    P.split(t.f1, d, t.f13, Bhw, d);
+    P.conv3(t.f13, me.convf2, t.tmp, B, h, w, 1, P.epi(A3R_EPI_RELU));                   // flo = relu(convf2(flo))
+    P.pack_cols(t.cf, 2 * d, d + d / 2, t.tmp, d / 2, d / 2, Bhw);                       // cat([cor, flo]) (update.py:113)
+    P.split(t.cf, 2 * d, t.cf3, Bhw, 2 * d);
+    P.conv3(t.cf3, me.conv, t.tmp, B, h, w, 1, P.epi(A3R_EPI_RELU));                     // out = relu(conv(cat))
+    P.pack_cols(v.X, 3 * d, 2 * d, t.tmp, d - 2, d - 2, Bhw);                            // motion = cat([out, flow])
+    P.pack_cols(v.X, 3 * d, 3 * d - 2, v.flow8, 2, 2, Bhw);
+}
+
+// refine: net = ConvNextBlock_i(cat([net, inp])) for every block (update.py:170-173, layer.py:35-70)
+void refine(RPlan& P, const RaftDims& g, const RState& v, const RIter& t) {
+    const int B = g.B, h = g.h, w = g.w, d = g.d;
+    const long Bhw = g.Bhw;
+    for (const RRefineW& r : P.m->bound.refine) {
+        P.pack_cols(v.X, 3 * d, 0, v.net, d, d, Bhw);
         P.launch([&](hipStream_t st) {
-            LookupArgs a = {};
-            for (int l = 0; l < c.corr_levels; l++) { a.corr[l] = corr[l]; a.hl[l] = hl[l]; a.wl[l] = wl[l]; }
-            a.flow = flow8; a.out = lk; a.ldo = ccp; a.B = B; a.h = h; a.w = w; a.r = c.radius; a.levels = c.corr_levels;
-            hipLaunchKernelGGL(corr_lookup_kernel, dim3(grid1d(Bhw * ccp)), dim3(256), 0, st, a);
+            hipLaunchKernelGGL(dwconv7_kernel, dim3(grid1d((long)B * h * ((w + 3) / 4) * 3 * d)), dim3(256), 0, st, v.X, r.dw.wt, r.dw.b, t.dw, B, h, w, 3 * d);
         });
-        if (it == 0) tap(taps ? taps->lookup0 : nullptr, lk, (size_t)Bhw * ccp);
-        // BasicMotionEncoder2 (update.py:99-117)
-        P.split(lk, ccp, lk3, Bhw, ccp);
-        OpEpi er = P.epi(A3R_EPI_RELU, nullptr);
-        er.out_op = 1;
-        P.linear(lk3, enc + "convc1", c13, 2 * d, Bhw, 2 * d, ccp, er);                                     // cor = relu(convc1(corr))
-        P.conv3(c13, enc + "convc2", tmp, B, h, w, 2 * d, d + d / 2, 1, P.epi(A3R_EPI_RELU, nullptr));     // cor = relu(convc2(cor))
-        P.pack_cols(cf, 2 * d, 0, tmp, d + d / 2, d + d / 2, Bhw);
-        P.launch([&](hipStream_t st) {                                                                      // flo = relu(convf1(flow)): 7x7 on 2 channels
-            DirectConvArgs a = {flow8, nullptr, 2, 0, hw * 2, 1, (long)w * 2, 2, B, h, w, 7, 1, 3, h, w, d, 1.f, 0.f,
-                                P.auxw(enc + "convf1.weight"), P.wptr(enc + "convf1.bias"), 1, f1};
-            launch_direct_conv(a, st);
-        });
-        P.split(f1, d, f13, Bhw, d);
-        P.conv3(f13, enc + "convf2", tmp, B, h, w, d, d / 2, 1, P.epi(A3R_EPI_RELU, nullptr));              // flo = relu(convf2(flo))
-        P.pack_cols(cf, 2 * d, d + d / 2, tmp, d / 2, d / 2, Bhw);
-        P.split(cf, 2 * d, cf3, Bhw, 2 * d);
-        P.conv3(cf3, enc + "conv", tmp, B, h, w, 2 * d, d - 2, 1, P.epi(A3R_EPI_RELU, nullptr));            // out = relu(conv(cat))
-        P.pack_cols(X, 3 * d, 2 * d, tmp, d - 2, d - 2, Bhw);                                                // motion = cat([out, flow])
-        P.pack_cols(X, 3 * d, 3 * d - 2, flow8, 2, 2, Bhw);
-        if (it == 0 && taps && taps->motion0 && !P.skip()) {
-            // (tap: the motion features alone, [Bhw, d])
-            hipLaunchKernelGGL(pack_cols_kernel, dim3(grid1d(Bhw * d)), dim3(256), 0, as_stream(stream), taps->motion0, d, 0, X + 2 * d, 3 * d, d, Bhw);
-        }
-        // refine: net = ConvNextBlock_i(cat([net, inp])) (update.py:170-173, layer.py:35-70)
-        for (int r = 0; r < c.num_blocks; r++) {
-            const std::string q = "update_block.refine." + std::to_string(r) + ".";
-            P.pack_cols(X, 3 * d, 0, net, d, d, Bhw);
-            P.launch([&](hipStream_t st) {
-                auto wi = P.m->aux.find(q + "dwconv.weight");
-                hipLaunchKernelGGL(dwconv7_kernel, dim3(grid1d((long)B * h * ((w + 3) / 4) * 3 * d)), dim3(256), 0, st, X, wi->second, P.wptr(q + "dwconv.bias"), dw, B, h, w, 3 * d);
-            });
-            if (!P.skip())
-                P.rc = fh2 ? a3r_layernorm_fh2(dw, P.wptr(q + "norm.weight"), P.wptr(q + "norm.bias"), ln3, (int)Bhw, 3 * d, 1e-6f, 1.f, m->stat, stream)
-                               : a3r_layernorm_bf3(dw, P.wptr(q + "norm.weight"), P.wptr(q + "norm.bias"), ln3, (int)Bhw, 3 * d, 1e-6f, 0, stream);
-            OpEpi eg = P.epi(A3R_EPI_GELU, nullptr);
-            eg.out_op = 1;
-            P.linear(ln3, q + "pwconv1", hid3, 4 * d, Bhw, 4 * d, 3 * d, eg);
-            OpEpi es = P.epi(A3R_EPI_RESID, nullptr, X);                                              // input + gamma * pwconv2(...) (gamma folded)
-            es.aux_op = S3;
-            P.linear(hid3, q + "pwconv2", S, 3 * d, Bhw, 3 * d, 4 * d, es);
-            P.linear(S3, q + "final", net, d, Bhw, d, 3 * d, P.epi(A3R_EPI_NONE, nullptr));
-        }
-        heads();
-        P.launch([&](hipStream_t st) { hipLaunchKernelGGL(flow_add_kernel, dim3(grid1d(Bhw * 2)), dim3(256), 0, st, flow8, fu, 6, Bhw); });
-        if (taps && it < 4) {
-            tap(taps->net[it], net, (size_t)Bhw * d);
-            tap(taps->flow8[it], flow8, (size_t)Bhw * 2);
+        P.layernorm(t.dw, r.norm, t.ln3, Bhw, 3 * d);
+        OpEpi eg = P.epi(A3R_EPI_GELU);
+        eg.out_op = 1;
+        P.linear(t.ln3, r.pw1, t.hid3, Bhw, eg);
+        OpEpi es = P.epi(A3R_EPI_RESID, v.X);                                            // input + gamma * pwconv2(...) (gamma folded)
+        es.aux_op = t.S3;
+        P.linear(t.hid3, r.pw2, t.S, Bhw, es);
+        P.linear(t.S3, r.fin, v.net, Bhw, P.epi(A3R_EPI_NONE));
+    }
+}
+
+// The plan of one call: the persistent buffers, then the stages.  What the sizing pass, the goldens (tests/golden/plan_sizes.json)
+// and a bitwise comparison with an earlier build all rest on, and what an edit here must therefore keep:
+//   * the order and the sizes of the allocations are the order of the lines here and inside each stage (workspace layout is
+//     observable), and a stage's scratch is released to the same arena mark when the stage ends;
+//   * the order of the launches, and the buffer each launch reads and writes;
+//   * every operand buffer is sized for BF3, the larger form, so that the layout does not depend on the arithmetic;
+//   * one range word, m->stat, receives every fh2 producer's maximum, and is cleared once, before the first launch;
+//   * an fh2 call waits on the stream exactly once (corr_scales), a bf3 call never;
+//   * no name is looked up: every weight was bound by a3r_raft_finalize (RaftW).
+int raft_plan(a3r_raft_s* m, const RaftCall& k, size_t* peak = nullptr) {
+    const RaftDims g(m->cfg, k);
+    RPlan P;
+    P.m = m; P.stream = k.stream; P.f = m->use_fh2 ? Form::FH2 : Form::BF3;
+    P.ar = {static_cast<char*>(k.ws), 0, k.ws_bytes, k.dry, 0};
+    Arena& ar = P.ar;
+    if (!k.dry && P.f == Form::FH2 && m->stat && hipMemsetAsync(m->stat, 0, 4, as_stream(k.stream)) != hipSuccess) {
+        set_error("a3r_raft_forward: clearing the range statistic failed");
+        return A3R_EHIP;
+    }
+    if (k.phase == 1) {
+        feature_stage(P, k, g, k.fmap_out);
+        if (peak) *peak = ar.peak;
+        return P.rc;
+    }
+    const int d = g.d;
+    const long Bhw = g.Bhw;
+    // ---------------- persistent buffers
+    RState v = {};
+    v.cn = ar.alloc(Bhw * 2 * d);
+    v.fm3 = P.alloc_op(2 * Bhw, 2 * d);
+    v.fm = ar.alloc(2 * Bhw * 2 * d);
+    for (int l = 0; l < g.c.corr_levels; l++) v.corr[l] = ar.alloc((size_t)Bhw * g.hl[l] * g.wl[l]);
+    v.net = ar.alloc(Bhw * d);
+    v.X = ar.alloc(Bhw * 3 * d);
+    v.flow8 = ar.alloc(Bhw * 2);
+    v.fu = ar.alloc(Bhw * 6);
+    v.wgt = ar.alloc(Bhw * 576);
+    // ---------------- context, features (raft.py:222-223), correlation pyramid: each in its own scope above this mark
+    context_stage(P, k, g, v);
+    feature_stage(P, k, g, v.fm);
+    P.copy(k.taps.fmap, v.fm, (size_t)2 * Bhw * 2 * d);
+    corr_stage(P, k, g, v);
+    // ---------------- scratch of the heads and the iterations
+    RIter t = {};
+    t.n3 = P.alloc_op(Bhw, d);
+    t.t3 = P.alloc_op(Bhw, 2 * d);
+    t.lk = ar.alloc(Bhw * g.ccp);
+    t.lk3 = P.alloc_op(Bhw, g.ccp);
+    t.c13 = P.alloc_op(Bhw, 2 * d);
+    t.cf = ar.alloc(Bhw * 2 * d);
+    t.tmp = ar.alloc(Bhw * 2 * d);
+    t.f1 = ar.alloc(Bhw * d);
+    t.f13 = P.alloc_op(Bhw, d);
+    t.cf3 = P.alloc_op(Bhw, 2 * d);
+    t.dw = ar.alloc(Bhw * 3 * d);
+    t.ln3 = P.alloc_op(Bhw, 3 * d);
+    t.hid3 = P.alloc_op(Bhw, 4 * d);
+    t.S = ar.alloc(Bhw * 3 * d);
+    t.S3 = P.alloc_op(Bhw, 3 * d);
+    // ---------------- the first prediction, from the context network alone (raft.py:213-217)
+    heads(P, g, v, t);
+    P.copy(k.taps.flow_update0, v.fu, (size_t)Bhw * 6);
+    P.copy(k.taps.weight0, v.wgt, (size_t)Bhw * 576);
+    P.pack_cols(v.flow8, 2, 0, v.fu, 6, 2, Bhw);                     // flow_8x = flow_update[:, :2]
+    // ---------------- iterations (raft.py:225-238)
+    for (int it = 0; it < k.iters; it++) {
+        lookup(P, g, v, t);
+        if (it == 0) P.copy(k.taps.lookup0, t.lk, (size_t)Bhw * g.ccp);
+        motion_encoder(P, g, v, t);
+        if (it == 0 && k.taps.motion0) P.pack_cols(k.taps.motion0, d, 0, v.X + 2 * d, 3 * d, d, Bhw);      // (tap: the motion features alone)
+        refine(P, g, v, t);
+        heads(P, g, v, t);
+        P.launch([&](hipStream_t st) { hipLaunchKernelGGL(flow_add_kernel, dim3(grid1d(Bhw * 2)), dim3(256), 0, st, v.flow8, v.fu, 6, Bhw); });
+        if (it < 4) {
+            P.copy(k.taps.net[it], v.net, (size_t)Bhw * d);
+            P.copy(k.taps.flow8[it], v.flow8, (size_t)Bhw * 2);
         }
     }
     // flow_up = upsample_data(flow_8x, info_8x, weight_update)[0] (raft.py:183-199, 236)
-    P.launch([&](hipStream_t st) { hipLaunchKernelGGL(convex_upsample_kernel, dim3(grid1d(Bhw * 64)), dim3(256), 0, st, flow8, wgt, flow_out, B, h, w); });
+    P.launch([&](hipStream_t st) { hipLaunchKernelGGL(convex_upsample_kernel, dim3(grid1d(Bhw * 64)), dim3(256), 0, st, v.flow8, v.wgt, k.flow_out, g.B, g.h, g.w); });
     if (peak) *peak = ar.peak;
     return P.rc;
 }
 }  // namespace
 
-static int raft_check(a3r_raft_t m, int B, int H, int W, int iters, const char* who) {
+// the sizing pass: the workspace a call of this phase and shape needs (no allocation depends on the number of iterations)
+static size_t raft_size(a3r_raft_t m, int phase, int B, int H, int W) {
+    RaftCall k;
+    k.phase = phase; k.B = B; k.H = H; k.W = W; k.dry = true;
+    size_t peak = 0;
+    raft_plan(m, k, &peak);
+    return peak;
+}
+
+// what the three forward entry points share: their checks, then the launch pass of call k.  pointers: the entry's own are all given
+static int raft_run(a3r_raft_t m, const RaftCall& k, bool pointers, const char* who) {
+    const int B = k.B, H = k.H, W = k.W;
     A3R_CHECK_ARG(m, "%s: null handle", who);
-    A3R_CHECK_ARG(B > 0 && iters >= 0, "%s: batch must be positive, iters non-negative", who);
+    A3R_CHECK_ARG(B > 0 && k.iters >= 0, "%s: batch must be positive, iters non-negative", who);
     // InputPadder (utils.py:11-28) pads to multiples of 8; the pyramid halves the 1/8 map corr_levels times (corr.py:22)
     A3R_CHECK_ARG(H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0, "%s: image size %dx%d must be a multiple of 8 (pad first, as InputPadder does)", who, H, W);
     A3R_CHECK_ARG(((H / 8) >> (m->cfg.corr_levels - 1)) >= 2 && ((W / 8) >> (m->cfg.corr_levels - 1)) >= 2,
                   "%s: image %dx%d too small for a %d-level correlation pyramid", who, H, W, m->cfg.corr_levels);
-    return A3R_OK;
+    if (!m->finalized) { set_error("%s: a3r_raft_finalize has not been called", who); return A3R_ESTATE; }
+    A3R_CHECK_ARG(pointers && k.ws, "%s: null pointer", who);
+    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(k.ws) & 255) == 0, "%s: workspace must be 256-byte aligned", who);
+    const size_t need_bytes = raft_size(m, k.phase, B, H, W);
+    A3R_CHECK_ARG(k.ws_bytes >= need_bytes, "%s: workspace too small (%zu < %zu)", who, k.ws_bytes, need_bytes);
+    return raft_plan(m, k);
 }
 
 extern "C" size_t a3r_raft_workspace_bytes(a3r_raft_t m, int B, int H, int W) {
     if (!m || B <= 0 || H <= 0 || W <= 0 || H % 8 || W % 8) return 0;
-    size_t peak = 0;
-    raft_plan(m, true, nullptr, nullptr, B, H, W, 1, nullptr, nullptr, 0, nullptr, &peak, nullptr);
-    return peak;
+    return raft_size(m, 0, B, H, W);
 }
 
 extern "C" int a3r_raft_set_arith(a3r_raft_t m, int fh2) {
@@ -888,34 +1012,28 @@ extern "C" int a3r_raft_range(a3r_raft_t m, float* max_abs_host, void* stream) {
 
 extern "C" int a3r_raft_encode(a3r_raft_t m, const float* image, int B, int H, int W, float* fmap, void* workspace, size_t workspace_bytes,
                                void* stream) {
-    if (int rc = raft_check(m, B, H, W, 0, "a3r_raft_encode")) return rc;
-    if (!m->finalized) { set_error("a3r_raft_encode: a3r_raft_finalize has not been called"); return A3R_ESTATE; }
-    A3R_CHECK_ARG(image && fmap && workspace, "a3r_raft_encode: null pointer");
-    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "a3r_raft_encode: workspace must be 256-byte aligned");
-    size_t need_bytes = 0;
-    raft_plan(m, true, nullptr, nullptr, B, H, W, 0, nullptr, nullptr, 0, nullptr, &need_bytes, nullptr, 1);
-    A3R_CHECK_ARG(workspace_bytes >= need_bytes, "a3r_raft_encode: workspace too small (%zu < %zu)", workspace_bytes, need_bytes);
-    return raft_plan(m, false, image, nullptr, B, H, W, 0, nullptr, workspace, workspace_bytes, stream, nullptr, nullptr, 1, nullptr, nullptr, fmap);
+    RaftCall k;
+    k.phase = 1; k.B = B; k.H = H; k.W = W;
+    k.img1 = image; k.fmap_out = fmap;
+    k.ws = workspace; k.ws_bytes = workspace_bytes; k.stream = stream;
+    return raft_run(m, k, image && fmap, "a3r_raft_encode");
 }
 
 extern "C" int a3r_raft_forward_features(a3r_raft_t m, const float* image1, const float* image2, const float* fmap1, const float* fmap2, int B,
                                          int H, int W, int iters, float* flow, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = raft_check(m, B, H, W, iters, "a3r_raft_forward_features")) return rc;
-    if (!m->finalized) { set_error("a3r_raft_forward_features: a3r_raft_finalize has not been called"); return A3R_ESTATE; }
-    A3R_CHECK_ARG(image1 && image2 && fmap1 && fmap2 && flow && workspace, "a3r_raft_forward_features: null pointer");
-    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "a3r_raft_forward_features: workspace must be 256-byte aligned");
-    const size_t need_bytes = a3r_raft_workspace_bytes(m, B, H, W);
-    A3R_CHECK_ARG(workspace_bytes >= need_bytes, "a3r_raft_forward_features: workspace too small (%zu < %zu)", workspace_bytes, need_bytes);
-    return raft_plan(m, false, image1, image2, B, H, W, iters, flow, workspace, workspace_bytes, stream, nullptr, nullptr, 0, fmap1, fmap2);
+    RaftCall k;
+    k.B = B; k.H = H; k.W = W; k.iters = iters;
+    k.img1 = image1; k.img2 = image2; k.fmap1_in = fmap1; k.fmap2_in = fmap2; k.flow_out = flow;
+    k.ws = workspace; k.ws_bytes = workspace_bytes; k.stream = stream;
+    return raft_run(m, k, image1 && image2 && fmap1 && fmap2 && flow, "a3r_raft_forward_features");
 }
 
 extern "C" int a3r_raft_forward(a3r_raft_t m, const float* image1, const float* image2, int B, int H, int W, int iters, float* flow,
                                 void* workspace, size_t workspace_bytes, const a3r_raft_taps* taps, void* stream) {
-    if (int rc = raft_check(m, B, H, W, iters, "a3r_raft_forward")) return rc;
-    if (!m->finalized) { set_error("a3r_raft_forward: a3r_raft_finalize has not been called"); return A3R_ESTATE; }
-    A3R_CHECK_ARG(image1 && image2 && flow && workspace, "a3r_raft_forward: null pointer");
-    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "a3r_raft_forward: workspace must be 256-byte aligned");
-    const size_t need_bytes = a3r_raft_workspace_bytes(m, B, H, W);
-    A3R_CHECK_ARG(workspace_bytes >= need_bytes, "a3r_raft_forward: workspace too small (%zu < %zu)", workspace_bytes, need_bytes);
-    return raft_plan(m, false, image1, image2, B, H, W, iters, flow, workspace, workspace_bytes, stream, nullptr, taps);
+    RaftCall k;
+    k.B = B; k.H = H; k.W = W; k.iters = iters;
+    k.img1 = image1; k.img2 = image2; k.flow_out = flow;
+    if (taps) k.taps = *taps;
+    k.ws = workspace; k.ws_bytes = workspace_bytes; k.stream = stream;
+    return raft_run(m, k, image1 && image2 && flow, "a3r_raft_forward");
 }

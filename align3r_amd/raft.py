@@ -18,11 +18,11 @@ from ._lib import RaftConfigC, RaftTaps, check, ptr, stream_ptr
 from .raft_weights import RAFT_M, RaftConfig, fold_batchnorm, raft_param_spec
 
 
-def engine_weights(state_dict: Dict[str, "np.ndarray | torch.Tensor"], cfg: RaftConfig) -> Dict[str, np.ndarray]:
+def engine_weights(state_dict: Dict[str, "np.ndarray | torch.Tensor"], cfg: RaftConfig, corr_width: int) -> Dict[str, np.ndarray]:
     """Reference state_dict -> the weight set a3r_raft_set_weight takes (include/a3r.h section 3b): evaluation-mode BatchNorm folded
     into the convolution in front of it; ConvNeXt's layer scale folded into pwconv2 (`x = gamma * pwconv2(...)`, layer.py:64-66); the
     0.25 of `.25 * self.upsample_weight(net)` (raft.py:216) folded into upsample_weight.2; convc1's correlation channels zero-padded
-    to a multiple of 32 (the GEMM's K granularity -- the lookup kernel writes zeros there)."""
+    to corr_width, the library's a3r_raft_corr_width (the GEMM's K granularity -- the lookup kernel writes zeros there)."""
     sd = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in state_dict.items()}
     sd = {k[7:] if k.startswith("module.") else k: v for k, v in sd.items()}            # third_party/raft.py:64-70
     missing = [n for n, _, _ in raft_param_spec(cfg) if n not in sd]
@@ -37,10 +37,8 @@ def engine_weights(state_dict: Dict[str, "np.ndarray | torch.Tensor"], cfg: Raft
     out["upsample_weight.2.weight"] = (out["upsample_weight.2.weight"] * np.float32(0.25)).astype(np.float32)
     out["upsample_weight.2.bias"] = (out["upsample_weight.2.bias"] * np.float32(0.25)).astype(np.float32)
     w = out["update_block.encoder.convc1.weight"]
-    cc = w.shape[1]
-    ccp = (cc + 31) // 32 * 32
-    wp = np.zeros((w.shape[0], ccp, 1, 1), np.float32)
-    wp[:, :cc] = w
+    wp = np.zeros((w.shape[0], corr_width, 1, 1), np.float32)
+    wp[:, :w.shape[1]] = w
     out["update_block.encoder.convc1.weight"] = wp
     return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in out.items()}
 
@@ -58,7 +56,7 @@ class RaftEngine:
         check(self.lib.a3r_raft_create(C.byref(c), C.byref(self.handle)), "a3r_raft_create")
         self.weights = {}
         with torch.cuda.device(self.device):
-            for name, arr in engine_weights(state_dict, cfg).items():
+            for name, arr in engine_weights(state_dict, cfg, self.lib.a3r_raft_corr_width(self.handle)).items():
                 t = torch.from_numpy(arr).to(self.device)
                 self.weights[name] = t
                 shp = (C.c_int64 * t.dim())(*t.shape)
@@ -110,73 +108,61 @@ class RaftEngine:
             self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self.workspace
 
+    def _check(self, t, name, shape):
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+            raise RuntimeError(f"{name}: expected contiguous float32 {shape} on {self.device}, got {tuple(t.shape)} {t.dtype} {t.device}")
+
+    def _run(self, what, shape, B, H, W, call):
+        """One entry point of the library: `call(out, workspace)` enqueues it; returns the new tensor `out` of `shape`."""
+        with torch.cuda.device(self.device):
+            ws = self._workspace(B, H, W)
+            out = torch.empty(shape, device=self.device, dtype=torch.float32)
+
+            def launch():
+                check(call(out, ws), what)
+                return out
+            return self._ranged(launch)
+
+    @staticmethod
+    def _taps_struct(taps):
+        """dict name -> device tensor as the library's a3r_raft_taps (corr_pyr0..3, net0..3 and flow8_0..3 are its arrays)."""
+        tp = RaftTaps()
+        for k, t in taps.items():
+            if k[:-1] in ("corr_pyr", "net") and k[-1].isdigit():
+                getattr(tp, k[:-1])[int(k[-1])] = t.data_ptr()
+            elif k.startswith("flow8_"):
+                tp.flow8[int(k[6:])] = t.data_ptr()
+            else:
+                setattr(tp, k, t.data_ptr())
+        return tp
+
     def encode(self, image):
         """The feature network alone (a3r_raft_encode): image [B, 3, H, W] in [0, 255] -> fmap [B, H/8, W/8, 2 dim].  A frame's features
         do not depend on its partner; forward(..., fmaps=(fmap1, fmap2)) then skips the feature network."""
         B, _, H, W = image.shape
-        if tuple(image.shape) != (B, 3, H, W) or image.dtype != torch.float32 or not image.is_contiguous() or image.device != self.device:
-            raise RuntimeError(f"image: expected contiguous float32 {(B, 3, H, W)} on {self.device}")
-        with torch.cuda.device(self.device):
-            ws = self._workspace(B, H, W)
-            fmap = torch.empty((B, H // 8, W // 8, 2 * self.cfg.dim), device=self.device, dtype=torch.float32)
-
-            def launch():
-                check(self.lib.a3r_raft_encode(self.handle, ptr(image), B, H, W, ptr(fmap), ptr(ws), ws.numel(), stream_ptr()), "a3r_raft_encode")
-                return fmap
-            return self._ranged(launch)
+        self._check(image, "image", (B, 3, H, W))
+        return self._run("a3r_raft_encode", (B, H // 8, W // 8, 2 * self.cfg.dim), B, H, W, lambda fmap, ws: self.lib.a3r_raft_encode(
+            self.handle, ptr(image), B, H, W, ptr(fmap), ptr(ws), ws.numel(), stream_ptr()))
 
     def forward(self, image1, image2, iters=20, taps=None, fmaps=None):
         """image* [B, 3, H, W] in [0, 255] (device fp32) -> flow [B, 2, H, W].  taps: dict name -> preallocated device tensor
         (parity tests): cnet, fmap, corr_pyr0..3, flow_update0, weight0, lookup0, motion0, net0..3, flow8_0..3.
         fmaps: (fmap1, fmap2) from encode() of the two frame batches."""
         B, _, H, W = image1.shape
-        if fmaps is not None:
-            f1, f2 = fmaps
-            shp = (B, H // 8, W // 8, 2 * self.cfg.dim)
-            for t, nm in ((image1, "image1"), (image2, "image2")):
-                if tuple(t.shape) != (B, 3, H, W) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
-                    raise RuntimeError(f"{nm}: expected contiguous float32 {(B, 3, H, W)} on {self.device}")
-            for t, nm in ((f1, "fmap1"), (f2, "fmap2")):
-                if tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
-                    raise RuntimeError(f"{nm}: expected contiguous float32 {shp} on {self.device}")
-            if taps:
-                raise RuntimeError("taps are only available without fmaps")
-            with torch.cuda.device(self.device):
-                ws = self._workspace(B, H, W)
-                flow = torch.empty((B, 2, H, W), device=self.device, dtype=torch.float32)
-
-                def launch():
-                    check(self.lib.a3r_raft_forward_features(self.handle, ptr(image1), ptr(image2), ptr(f1), ptr(f2), B, H, W, int(iters), ptr(flow),
-                                                             ptr(ws), ws.numel(), stream_ptr()), "a3r_raft_forward_features")
-                    return flow
-                return self._ranged(launch)
-        for t, nm in ((image1, "image1"), (image2, "image2")):
-            if tuple(t.shape) != (B, 3, H, W) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
-                raise RuntimeError(f"{nm}: expected contiguous float32 {(B, 3, H, W)} on {self.device}, got {tuple(t.shape)} {t.dtype} {t.device}")
-        with torch.cuda.device(self.device):
-            need = int(self.lib.a3r_raft_workspace_bytes(self.handle, B, H, W))
-            if need == 0:
-                raise RuntimeError(f"RAFT: image size {H}x{W} must be a multiple of 8")
-            if self.workspace is None or self.workspace.numel() < need:
-                self.workspace = None
-                self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-            flow = torch.empty((B, 2, H, W), device=self.device, dtype=torch.float32)
-            tp = None
-            if taps:
-                tp = RaftTaps()
-                for k, t in taps.items():
-                    if k[:-1] in ("corr_pyr", "net") and k[-1].isdigit():
-                        getattr(tp, k[:-1])[int(k[-1])] = t.data_ptr()
-                    elif k.startswith("flow8_"):
-                        tp.flow8[int(k[6:])] = t.data_ptr()
-                    else:
-                        setattr(tp, k, t.data_ptr())
-
-            def launch():
-                check(self.lib.a3r_raft_forward(self.handle, ptr(image1), ptr(image2), B, H, W, int(iters), ptr(flow), ptr(self.workspace),
-                                                self.workspace.numel(), C.byref(tp) if tp is not None else None, stream_ptr()), "a3r_raft_forward")
-                return flow
-            return self._ranged(launch)
+        self._check(image1, "image1", (B, 3, H, W))
+        self._check(image2, "image2", (B, 3, H, W))
+        if fmaps is None:
+            tp = self._taps_struct(taps) if taps else None
+            return self._run("a3r_raft_forward", (B, 2, H, W), B, H, W, lambda flow, ws: self.lib.a3r_raft_forward(
+                self.handle, ptr(image1), ptr(image2), B, H, W, int(iters), ptr(flow), ptr(ws), ws.numel(),
+                C.byref(tp) if tp is not None else None, stream_ptr()))
+        f1, f2 = fmaps
+        self._check(f1, "fmap1", (B, H // 8, W // 8, 2 * self.cfg.dim))
+        self._check(f2, "fmap2", (B, H // 8, W // 8, 2 * self.cfg.dim))
+        if taps:
+            raise RuntimeError("taps are only available without fmaps")
+        return self._run("a3r_raft_forward_features", (B, 2, H, W), B, H, W, lambda flow, ws: self.lib.a3r_raft_forward_features(
+            self.handle, ptr(image1), ptr(image2), ptr(f1), ptr(f2), B, H, W, int(iters), ptr(flow), ptr(ws), ws.numel(), stream_ptr()))
 
 
 class RAFT2:

@@ -582,7 +582,9 @@ int a3r_model_range_scales(a3r_model_t m, int phase, float* scales, int capacity
  *      third_party/raft.py:39-73 -> third_party/RAFT/core/raft.py:152-246), csrc/raft.hip.
  *      Weights: the reference's state_dict names with evaluation-mode BatchNorm folded into the convolution in front of it, the
  *      ConvNeXt layer scale `gamma` folded into pwconv2, the factor 0.25 of raft.py:216 folded into upsample_weight.2, and
- *      update_block.encoder.convc1's input channels zero-padded to a multiple of 32 (align3r_amd/raft_weights.py does all four).
+ *      update_block.encoder.convc1's input channels zero-padded to a3r_raft_corr_width (a multiple of 32; align3r_amd/raft.py
+ *      engine_weights does all four).  Every weight the network reads is bound by a3r_raft_finalize: an incomplete set is reported
+ *      there (A3R_ESTATE, A3R_EINVAL for a wrong shape, the weight's name in a3r_last_error), never by a forward.
  */
 typedef struct {
     int initial_dim;       /* 64 */
@@ -610,6 +612,8 @@ int a3r_raft_create(const a3r_raft_config* cfg, a3r_raft_t* out);
 int a3r_raft_destroy(a3r_raft_t m);
 int a3r_raft_set_weight(a3r_raft_t m, const char* name, const float* ptr, int ndim, const int64_t* shape);
 size_t a3r_raft_packed_bytes(a3r_raft_t m);
+/* input channels of update_block.encoder.convc1 as the library takes it: corr_levels (2 radius + 1)^2 rounded up to a multiple of 32 */
+int a3r_raft_corr_width(a3r_raft_t m);
 int a3r_raft_finalize(a3r_raft_t m, void* packed, size_t packed_bytes, void* stream);
 size_t a3r_raft_workspace_bytes(a3r_raft_t m, int B, int H, int W);
 /* flow [B, 2, H, W] = RAFT2(image1, image2, iters, test_mode=True)[1]: image* [B, 3, H, W] with values in [0, 255] (the reference

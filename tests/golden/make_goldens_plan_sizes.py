@@ -17,7 +17,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 MODES = {"unset": (None, None), "f32": ("f32", None), "bf3": ("bf3", None), "bf3x3": ("bf3x3", None), "bf16": ("bf16", None),
          "f16": ("f16", None), "unset+conv_bf3": (None, "bf3")}
 MODEL_SHAPES = [(1, 48, 80), (2, 64, 96), (3, 48, 80), (1, 512, 288), (42, 384, 512)]      # odd and even row counts: pair mode
-RAFT_SHAPES = [(1, 128, 128), (2, 136, 160), (12, 384, 512)]
+# (1, 136, 168): an odd 17 x 21 eighth-resolution map, so every pyramid level is a floor
+RAFT_SHAPES = [(1, 128, 128), (2, 136, 160), (12, 384, 512), (3, 128, 160), (1, 136, 168), (48, 288, 512)]
 
 
 def _setenv(name, value):

@@ -317,3 +317,104 @@ def test_cloud_opt_flow_computes_its_flow_with_the_hip_raft():
     assert np.isfinite(loss)
     with pytest.raises(RuntimeError, match="no RAFT checkpoint"):
         global_aligner(out, "cuda", verbose=False, flow_loss_weight=0.01)
+
+
+# ---- the C ABI itself (ctypes): weights are bound once, by a3r_raft_finalize (csrc/raft.hip, RaftW)
+class _RawRaft:
+    """One a3r_raft handle driven through the C ABI: create, set every weight of `weights`, finalize (rc kept), forward."""
+
+    def __init__(self, weights):
+        import ctypes as C
+        from align3r_amd import _lib
+        self.C, self.L, self.lib = C, _lib, _lib.load()
+        cfg = RAFT_TINY
+        c = _lib.RaftConfigC(cfg.initial_dim, (C.c_int * 3)(*cfg.block_dims), (C.c_int * 3)(*cfg.n_blocks), cfg.dim, cfg.radius,
+                             cfg.corr_levels, cfg.num_blocks)
+        self.handle = C.c_void_p()
+        _lib.check(self.lib.a3r_raft_create(C.byref(c), C.byref(self.handle)), "a3r_raft_create")
+        self.tensors = {}
+        for name, arr in weights.items():
+            self.set_weight(name, arr)
+        self.packed = torch.empty(int(self.lib.a3r_raft_packed_bytes(self.handle)), dtype=torch.uint8, device="cuda")
+        self.finalize_rc = self.finalize()
+
+    def set_weight(self, name, arr):
+        t = self.tensors[name] = dev(arr)
+        shp = (self.C.c_int64 * t.dim())(*t.shape)
+        self.L.check(self.lib.a3r_raft_set_weight(self.handle, name.encode(), self.L.ptr(t), t.dim(), shp), name)
+
+    def finalize(self):
+        rc = self.lib.a3r_raft_finalize(self.handle, self.L.ptr(self.packed), self.packed.numel(), self.L.stream_ptr())
+        torch.cuda.synchronize()
+        return rc
+
+    def forward(self, i1, i2, iters=2):
+        """(rc, flow)"""
+        B, _, H, W = i1.shape
+        ws = torch.empty(int(self.lib.a3r_raft_workspace_bytes(self.handle, B, H, W)), dtype=torch.uint8, device="cuda")
+        flow = torch.zeros(B, 2, H, W, device="cuda")
+        rc = self.lib.a3r_raft_forward(self.handle, self.L.ptr(i1), self.L.ptr(i2), B, H, W, iters, self.L.ptr(flow), self.L.ptr(ws),
+                                       ws.numel(), None, self.L.stream_ptr())
+        torch.cuda.synchronize()
+        return rc, flow
+
+    def error(self):
+        return self.lib.a3r_last_error().decode(errors="replace")
+
+    def close(self):
+        self.lib.a3r_raft_destroy(self.handle)
+
+
+@pytest.fixture(scope="module")
+def raw():
+    """(the weight set a3r_raft_set_weight takes for RAFT_TINY, one pair of 128 x 160 frames on the device); neither is modified."""
+    from align3r_amd import _lib
+    from align3r_amd.raft import engine_weights
+    probe = _RawRaft({})
+    width = _lib.load().a3r_raft_corr_width(probe.handle)
+    probe.close()
+    assert width == (RAFT_TINY.corr_channel + 31) // 32 * 32
+    i1, i2 = synthetic_raft_frames(1, 128, 160, 31)
+    return engine_weights(synthetic_raft_state_dict(RAFT_TINY, 0), RAFT_TINY, width), dev(i1), dev(i2)
+
+
+@pytest.mark.parametrize("name", ["cnet.conv1.bias", "update_block.refine.1.norm.weight", "update_block.refine.0.dwconv.weight"])
+def test_raft_finalize_reports_an_incomplete_weight_set(raw, name):
+    """A bias, a norm weight, a depthwise weight left out: a3r_raft_finalize refuses and names it (before this was bound at finalize,
+    a forward found it missing with earlier kernels already enqueued, and the depthwise launch did not look at all); the handle
+    stays unfinalized, so a forward refuses too."""
+    weights, i1, i2 = raw
+    assert name in weights
+    h = _RawRaft({k: v for k, v in weights.items() if k != name})
+    try:
+        assert h.finalize_rc != 0 and name in h.error()
+        rc, _ = h.forward(i1, i2)
+        assert rc != 0 and "has not been called" in h.error()
+    finally:
+        h.close()
+
+
+def test_raft_set_weight_after_finalize_needs_a_new_finalize(raw):
+    """The bound pointers of a finalized handle cannot go stale: a3r_raft_set_weight clears `finalized`, every forward refuses until
+    a3r_raft_finalize has bound again, and the flow is then that of a fresh handle built with the changed weight, bit for bit."""
+    weights, i1, i2 = raw
+    name = "flow_head.2.bias"
+    changed = dict(weights)
+    changed[name] = (weights[name] + np.float32(0.25)).astype(np.float32)
+    h, fresh = _RawRaft(weights), _RawRaft(changed)
+    try:
+        assert h.finalize_rc == 0 and fresh.finalize_rc == 0
+        rc, before = h.forward(i1, i2)
+        assert rc == 0, h.error()
+        h.set_weight(name, changed[name])
+        rc, _ = h.forward(i1, i2)
+        assert rc != 0 and "has not been called" in h.error()
+        assert h.finalize() == 0, h.error()
+        rc, after = h.forward(i1, i2)
+        assert rc == 0, h.error()
+        rc, want = fresh.forward(i1, i2)
+        assert rc == 0, fresh.error()
+        assert torch.equal(after, want) and not torch.equal(after, before)
+    finally:
+        h.close()
+        fresh.close()
