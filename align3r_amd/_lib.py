@@ -101,6 +101,7 @@ class RenderCam(C.Structure):
 
 DEPTH_ALIGN_MODES ={"lad": 0, "lstsq": 1, "scale": 2, "median": 3}      # A3R_DEPTH_ALIGN_* of include/a3r.h
 DEPTH_INFO_DOUBLES, DEPTH_METRIC_DOUBLES = 16, 8
+VOXEL_BEST, VOXEL_MEAN = 0, 1                                           # A3R_VOXEL_* of include/a3r.h
 
 EPI_NONE, EPI_GELU, EPI_RESID, EPI_RELU, EPI_ROPE, EPI_RESID2, EPI_PIXSHUF, EPI_HEAD = range(8)
 
@@ -280,6 +281,11 @@ SIGNATURES = {
     "a3r_render_set_form": (C.c_int, [C.c_int]),
     "a3r_track_points": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, C.c_int, c_void, c_void, C.c_int, C.c_int,
                                    c_void, C.c_longlong, C.c_double, c_void, c_void, c_void, c_void, c_void]),
+    "a3r_voxel_workspace_bytes": (C.c_size_t, [C.c_longlong, C.c_longlong, C.c_int]),
+    "a3r_voxel_count": (C.c_int, [c_void, c_void, C.c_longlong, C.c_double, C.c_int, C.c_int, C.c_longlong, c_void, C.c_size_t,
+                                  C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), c_void]),
+    "a3r_voxel_export": (C.c_int, [c_void, c_void, c_void, C.c_longlong, C.c_double, C.c_int, C.c_int, C.c_longlong, c_void, C.c_size_t,
+                                   C.c_longlong, c_void, c_void, c_void, c_void, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), c_void]),
 }
 
 _lib = None

@@ -386,14 +386,36 @@ class PointCloudOptimizer:
         """The confidence maps get_masks() thresholds."""
         return self.im_conf
 
-    def get_pointcloud(self, min_conf_thr=None, mask_dynamic=False, with_index=False):
+    def get_pointcloud(self, min_conf_thr=None, mask_dynamic=False, with_index=False, voxel_size=None, reduce='best', min_count=1):
         """The aligned scene as one compacted point cloud, computed on the device by the aligner handle (csrc/scene.hip): dict of
         device tensors xyz [M,3] float32, rgb [M,3] uint8 (when the scene holds its frames) and, with_index, index [M] int32 =
         n * max_area + p.  Kept: conf > min_conf_thr (as given; None = self.min_conf_thr, the pixels of get_masks()), finite
-        coordinates and, with mask_dynamic, outside the scene's dynamic masks.  Image-major, row-major order."""
+        coordinates and, with mask_dynamic, outside the scene's dynamic masks.  Image-major, row-major order.
+
+        voxel_size: that cloud reduced to one point per occupied cell of a grid of this edge (ops.voxel_downsample, csrc/voxel.hip):
+        the most confident point of a cell (reduce='best') or the mean of its points and colours ('mean'), cells with fewer than
+        min_count points left out -- a point seen once is a floater.  The dict gains count [V] int32 = the points of the cell;
+        index is the winner's pixel, and the order stays image-major, row-major.  Points further than 2^20 cells from the origin
+        are in no cell; their number is reported by a warning."""
         e = self._need_engine()
         conf, thr, dyn, rgb = self._scene_out_inputs(min_conf_thr, mask_dynamic, 'get_pointcloud')
-        return e.export_points(conf, thr, dyn=dyn, rgb=rgb, with_index=with_index)
+        if voxel_size is None:
+            return e.export_points(conf, thr, dyn=dyn, rgb=rgb, with_index=with_index)
+        from ... import ops
+        pc = e.export_points(conf, thr, dyn=dyn, rgb=rgb, with_index=True)
+        priority = conf.reshape(-1)[pc['index'].long()].contiguous()
+        vx = ops.voxel_downsample(pc['xyz'], voxel_size, priority=priority, rgb=pc.get('rgb'), reduce=reduce, min_count=min_count)
+        if vx['dropped']:
+            import warnings
+            warnings.warn(f"get_pointcloud(voxel_size={voxel_size}): {vx['dropped']} of {pc['xyz'].shape[0]} points lie beyond 2^20 "
+                          "cells from the origin and are in no voxel")
+        out = dict(xyz=vx['xyz'])
+        if 'rgb' in vx:
+            out['rgb'] = vx['rgb']
+        out['count'] = vx['count']
+        if with_index:
+            out['index'] = pc['index'][vx['index'].long()]
+        return out
 
     def _scene_out_inputs(self, min_conf_thr, mask_dynamic, who):
         """(conf [N,P], thr, dyn [N,P] or None, rgb [N,P,3] uint8 or None): what get_pointcloud and get_mesh hand to the engine."""

@@ -796,6 +796,87 @@ def render_points(xyz, rgb=None, w2c=None, K=None, shape=None, radius=0, near=1e
     return out
 
 
+VOXEL_REDUCE = {"best": _lib.VOXEL_BEST, "mean": _lib.VOXEL_MEAN}
+
+
+def voxel_default_slots(M: int) -> int:
+    """The table size voxel_downsample(slots=0) uses: the smallest power of two >= 2 M, at most 2^31."""
+    s = 1
+    while s < 2 * M and s < (1 << 31):
+        s <<= 1
+    return s
+
+
+def _voxel_args(xyz, voxel, priority, rgb, reduce, min_count, slots):
+    """The checks of voxel_downsample; every refusal is a ValueError raised before the library is touched.  The scalars first, then
+    every tensor's type, dtype, shape and layout, the devices last."""
+    voxel = float(voxel)
+    if not (np.isfinite(voxel) and voxel > 0):
+        raise ValueError(f"voxel_downsample: voxel = {voxel} must be finite and positive")
+    if reduce not in VOXEL_REDUCE:
+        raise ValueError(f"voxel_downsample: reduce = {reduce!r} is neither 'best' nor 'mean'")
+    if int(min_count) != min_count or min_count < 1:
+        raise ValueError(f"voxel_downsample: min_count = {min_count!r} must be an integer >= 1")
+    if int(slots) != slots or slots < 0 or int(slots) & (int(slots) - 1):
+        raise ValueError(f"voxel_downsample: slots = {slots!r} must be 0 or a power of two above the point count")
+    slots = int(slots)
+
+    def tensor(t, name, dtype, shape):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"voxel_downsample: {name} must be a torch tensor, got {type(t).__name__}")
+        if t.dtype != dtype:
+            raise ValueError(f"voxel_downsample: {name} must be {dtype}, got {t.dtype}")
+        if t.dim() != len(shape) or any(want is not None and have != want for have, want in zip(t.shape, shape)):
+            raise ValueError(f"voxel_downsample: {name} has shape {tuple(t.shape)}, expected {['M' if w is None else w for w in shape]}")
+        if not t.is_contiguous():
+            raise ValueError(f"voxel_downsample: {name} must be contiguous")
+    tensor(xyz, "xyz", torch.float32, (None, 3))
+    M = xyz.shape[0]
+    if priority is not None:
+        tensor(priority, "priority", torch.float32, (M,))
+    if rgb is not None:
+        tensor(rgb, "rgb", torch.uint8, (M, 3))
+    if M >= 1 << 31:
+        raise ValueError(f"voxel_downsample: M = {M} points: the count must stay below 2^31")
+    if slots and (slots <= M or slots > 1 << 31):
+        raise ValueError(f"voxel_downsample: slots = {slots} must exceed the {M} points and stay at or below 2^31")
+    for t, name in ((xyz, "xyz"), (priority, "priority"), (rgb, "rgb")):
+        if t is not None and (t.device.type != "cuda" or t.device != xyz.device):
+            raise ValueError(f"voxel_downsample: {name} must be on the device (with xyz), it is on {t.device}")
+    return M, voxel, int(min_count), slots
+
+
+def voxel_downsample(xyz, voxel, priority=None, rgb=None, reduce="best", min_count=1, slots=0):
+    """A point cloud reduced to one point per occupied cell of a grid of edge `voxel` (a3r_voxel_export, csrc/voxel.hip; include/a3r.h
+    has the definition: float64 cells, the highest priority wins a cell and the lowest row an exact tie, integer sums for the mean --
+    bitwise the numpy restatement).  xyz [M,3] float32, priority [M] float32 or None, rgb [M,3] uint8 or None: contiguous device
+    tensors.  reduce: 'best' = the winner's own row, 'mean' = the unweighted mean of the cell's points and colours.  min_count: cells
+    with fewer points are left out.  slots: 0 = a hash table of the smallest power of two >= 2 M entries, otherwise a power of two
+    above M (the result does not depend on it).  Returns a dict: xyz [V,3] float32, rgb [V,3] uint8 (with rgb), index [V] int32 = the
+    winner's row, ascending, count [V] int32 = the cell's points, and dropped = the number of points in no cell (non-finite, or
+    beyond +-2^20 cells from the origin), a Python int.  One call into the library, which synchronises once to learn V; the outputs
+    are written into M-row buffers and returned as V-row copies."""
+    M, voxel, min_count, slots = _voxel_args(xyz, voxel, priority, rgb, reduce, min_count, slots)
+    lib, dev, mode = _lib.load(), xyz.device, VOXEL_REDUCE[reduce]
+    ws_bytes = int(lib.a3r_voxel_workspace_bytes(M, slots, mode))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    out_xyz = torch.empty((M, 3), dtype=torch.float32, device=dev)
+    out_rgb = torch.empty((M, 3), dtype=torch.uint8, device=dev) if rgb is not None else None
+    index = torch.empty(M, dtype=torch.int32, device=dev)
+    count = torch.empty(M, dtype=torch.int32, device=dev)
+    V, dropped = C.c_longlong(0), C.c_longlong(0)
+    with torch.cuda.device(dev):
+        check(lib.a3r_voxel_export(ptr(xyz), ptr(priority), ptr(rgb), M, voxel, mode, min_count, slots, ptr(ws), ws_bytes, M, ptr(out_xyz),
+                                   ptr(out_rgb), ptr(index), ptr(count), C.byref(V), C.byref(dropped), stream_ptr()), "voxel_downsample")
+    V = int(V.value)
+    narrow = lambda t: t if V == M else t[:V].clone()
+    out = dict(xyz=narrow(out_xyz))
+    if out_rgb is not None:
+        out["rgb"] = narrow(out_rgb)
+    out.update(index=narrow(index), count=narrow(count), dropped=int(dropped.value))
+    return out
+
+
 def track_points(xyz, keep, flow_a, flow_b, steps, seeds=None, fb_thr=3.0):
     """Points followed through a clip by chaining optical-flow fields, read off the point maps at every frame they pass
     (a3r_track_points, csrc/track.hip; include/a3r.h has the definition: float64 bilinear samples, a track ends where it leaves the

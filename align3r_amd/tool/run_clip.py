@@ -5,6 +5,7 @@ The flow of the reference's tool/demo.py and tool/depth_test.py through this pac
     load_images (N3)  ->  make_pairs  ->  inference (HIP pair forward)  ->  global_aligner / hierarchical_alignment (HIP aligner, N2)
     ->  pred_traj.txt, pred_intrinsics.txt, frame_XXXX.npy, conf_X.npy   (+ depth metrics when ground truth is given)
     ->  --pointcloud PATH: the aligned scene as a binary PLY (points above --min-conf-thr, compacted on the device)
+        --pointcloud-voxel V: one point per occupied cell of a grid of edge V instead of every pixel (hashed on the device)
     ->  --matches DIR: matches_{i}_{i+1}.npz, the reciprocal 3-D nearest-neighbour pixel correspondences of consecutive frames
     ->  --render DIR: render_XXXX.png, the whole aligned scene drawn from every frame's own camera (z-buffered point splats)
     ->  --flow --tracks PATH.npz: a grid of points of one frame followed through all later frames (3-D trajectories)
@@ -12,7 +13,8 @@ The flow of the reference's tool/demo.py and tool/depth_test.py through this pac
 
     python -m align3r_amd.tool.run_clip --images DIR --weights CKPT.pth --out OUT [--size 512] [--scene-graph swin-3-noncyclic]
            [--hierarchical --clip-size 50] [--niter 300] [--schedule linear] [--lr 0.01] [--traj-format custom] [--gt-depth DIR]
-           [--metrics-device] [--pointcloud scene.ply] [--matches DIR] [--render DIR [--render-radius R]] [--clean] [--device-prep]
+           [--metrics-device] [--pointcloud scene.ply [--pointcloud-voxel V [--pointcloud-reduce best|mean] [--pointcloud-min-count C]]]
+           [--matches DIR] [--render DIR [--render-radius R]] [--clean] [--device-prep]
            [--flow [--flow-weights RAFT.pth] [--gt-masks DIR] [--not-shared-focal]
                    [--tracks PATH.npz [--track-start K] [--track-stride G]] [--scene-flow DIR]]
            [--flow-hierarchical [--clip-size 10] [--device-resident] [--flow-weights ...] [--gt-masks DIR] [--not-shared-focal]]
@@ -61,6 +63,14 @@ def parse(argv=None):
     ap.add_argument("--gt-traj", default=None, help="ground-truth camera trajectory, TUM file `t x y z qx qy qz qw` (same frames) -> ATE / RPE")
     ap.add_argument("--pointcloud", default=None, metavar="PATH",
                     help="write the aligned scene as a binary PLY (with --hierarchical: every clip's points, appended in clip order)")
+    ap.add_argument("--pointcloud-voxel", type=float, default=None, metavar="V",
+                    help="--pointcloud: one point per occupied cell of a grid of edge V, in scene units (ops.voxel_downsample, "
+                         "csrc/voxel.hip): the most confident point of a cell; with --hierarchical and --flow-hierarchical the clips' "
+                         "clouds are reduced together after the last clip, the earliest clip's point winning a cell")
+    ap.add_argument("--pointcloud-reduce", choices=("best", "mean"), default=None,
+                    help="--pointcloud-voxel: the cell's winner as it is (best, the default) or the mean of the cell's points and colours")
+    ap.add_argument("--pointcloud-min-count", type=int, default=None, metavar="C",
+                    help="--pointcloud-voxel: leave out cells with fewer than C points (default 1; 2 removes points seen once)")
     ap.add_argument("--mesh", default=None, metavar="PATH",
                     help="write the aligned scene as a triangle mesh (binary PLY: the kept points as vertices, two triangles per pixel "
                          "quad whose corners are kept; with --hierarchical: every clip's mesh, appended in clip order)")
@@ -142,6 +152,17 @@ def parse(argv=None):
         a.render_radius = 1
     if not 0 <= a.render_radius <= 8:
         ap.error("--render-radius is in [0, 8]")
+    if a.pointcloud_voxel is not None and not a.pointcloud:
+        ap.error("--pointcloud-voxel belongs to --pointcloud")
+    for given, name in ((a.pointcloud_reduce, "--pointcloud-reduce"), (a.pointcloud_min_count, "--pointcloud-min-count")):
+        if given is not None and a.pointcloud_voxel is None:
+            ap.error(f"{name} belongs to --pointcloud-voxel")
+    a.pointcloud_reduce = a.pointcloud_reduce or "best"
+    a.pointcloud_min_count = 1 if a.pointcloud_min_count is None else a.pointcloud_min_count
+    if a.pointcloud_voxel is not None and not (np.isfinite(a.pointcloud_voxel) and a.pointcloud_voxel > 0):
+        ap.error("--pointcloud-voxel is a finite edge length > 0")
+    if a.pointcloud_min_count < 1:
+        ap.error("--pointcloud-min-count is at least 1")
     if a.device_resident and not a.flow_hierarchical:
         ap.error("--device-resident belongs to --flow-hierarchical")
     if a.metrics_device and not a.gt_depth:
@@ -170,6 +191,25 @@ def write_matches(scene, out_dir, mask_dynamic=False):
                  **{k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in m.items()})
         counts.append(int(m["count"]))
     return counts
+
+
+def write_voxel_cloud(path, clouds, voxel, reduce="best", min_count=1, device="cuda"):
+    """The clouds of the hierarchical drivers' collector (host dicts xyz, rgb in clip order) concatenated, uploaded and reduced by one
+    ops.voxel_downsample call without priorities -- the earliest clip's point wins a cell -- and written as one PLY.  Returns
+    (points written, points collected)."""
+    from .. import ops
+    from .pointcloud import write_ply
+    xyz = np.concatenate([np.asarray(c["xyz"], np.float32).reshape(-1, 3) for c in clouds]) if clouds else np.zeros((0, 3), np.float32)
+    colour = bool(clouds) and all(c["rgb"] is not None for c in clouds)
+    rgb = np.concatenate([np.asarray(c["rgb"], np.uint8).reshape(-1, 3) for c in clouds]) if colour else None
+    vx = ops.voxel_downsample(torch.from_numpy(xyz).to(device), voxel, rgb=torch.from_numpy(rgb).to(device) if colour else None,
+                              reduce=reduce, min_count=min_count)
+    if vx["dropped"]:
+        import warnings
+        warnings.warn(f"--pointcloud-voxel {voxel}: {vx['dropped']} of {len(xyz)} points lie beyond 2^20 cells from the origin and are "
+                      "in no voxel")
+    write_ply(path, vx["xyz"].cpu().numpy(), vx["rgb"].cpu().numpy() if colour else None)
+    return int(vx["xyz"].shape[0]), len(xyz)
 
 
 def write_tracks(scene, path, start=0, stride=8):
@@ -212,7 +252,10 @@ def main(argv=None):
                           dynamic_mask_root=a.gt_masks if (a.flow or a.flow_hierarchical) and a.gt_masks
                           else os.path.join(a.out, "__no_masks__"))
     os.makedirs(a.out, exist_ok=True)
-    clouds, n_points = ([] if a.pointcloud else None), None
+    clouds, n_points, n_points_full = ([] if a.pointcloud else None), None, None
+    voxel_kw = {}
+    if a.pointcloud_voxel is not None:
+        voxel_kw = dict(voxel_size=a.pointcloud_voxel, reduce=a.pointcloud_reduce, min_count=a.pointcloud_min_count)
     meshes, n_mesh = ([] if a.mesh else None), None              # n_mesh: (vertices, faces) written
     n_matches = None                   # --matches: matches written per consecutive pair
     n_renders = None                   # --render: pictures written
@@ -230,8 +273,11 @@ def main(argv=None):
                                         pointcloud_collector=clouds, clean=a.clean, obs_dtype=a.obs_dtype, mesh_collector=meshes,
                                         mesh_double_sided=a.mesh_double_sided, **extra)
         depths = res["depths"]
-        if a.pointcloud:
-            n_points = write_ply_parts(a.pointcloud, [(c["xyz"], c["rgb"]) for c in clouds])
+        if a.pointcloud and voxel_kw:
+            n_points, n_points_full = write_voxel_cloud(a.pointcloud, clouds, a.pointcloud_voxel, a.pointcloud_reduce, a.pointcloud_min_count,
+                                                        a.device)
+        elif a.pointcloud:
+            n_points = n_points_full = write_ply_parts(a.pointcloud, [(c["xyz"], c["rgb"]) for c in clouds])
         if a.mesh:
             n_mesh = write_ply_mesh_parts(a.mesh, [(m["xyz"], m["faces"], m["rgb"], m["face_rgb"]) for m in meshes])
     else:
@@ -275,7 +321,9 @@ def main(argv=None):
         if a.pointcloud:
             if mode != GlobalAlignerMode.PointCloudOptimizer:
                 raise RuntimeError("--pointcloud needs at least 3 frames (the two-frame PairViewer has no aligner handle to export from)")
-            n_points = int(scene.save_pointcloud(a.pointcloud)["xyz"].shape[0])
+            pc = scene.save_pointcloud(a.pointcloud, **voxel_kw)
+            n_points = int(pc["xyz"].shape[0])
+            n_points_full = int(scene.get_pointcloud()["xyz"].shape[0]) if voxel_kw else n_points
         if a.matches:
             if mode != GlobalAlignerMode.PointCloudOptimizer:
                 raise RuntimeError("--matches needs at least 3 frames (the two-frame PairViewer has no aligner handle to export from)")
@@ -316,7 +364,7 @@ def main(argv=None):
             print("pose metrics (Sim(3)-aligned):", {k: round(v, 5) for k, v in pose.items()})
     res_out = dict(n_frames=len(depths), out=a.out, metrics=metrics, pose_metrics=pose)
     if a.pointcloud:
-        res_out["pointcloud"], res_out["n_points"] = a.pointcloud, n_points
+        res_out["pointcloud"], res_out["n_points"], res_out["n_points_full"] = a.pointcloud, n_points, n_points_full
     if a.matches:
         res_out["matches"], res_out["n_matches"] = a.matches, n_matches
     if a.render:

@@ -1114,6 +1114,56 @@ int a3r_track_points(const float* xyz, const unsigned char* keep, int N, int H, 
                      const int* steps_dev, const int* steps_host, int C, int S, const float* seeds, long long M, double fb_thr,
                      float* out_xy, float* out_xyz, int* out_pix, unsigned char* out_state, void* stream);
 
+/* Voxel-grid downsampling (csrc/voxel.hip): the points of a cloud grouped by the cell of a regular grid they fall into, one point out
+ * per cell, with the number of points that fell into it.  The reference has no such routine (its users run a voxel filter on the
+ * host afterwards); this text is the specification.  Inputs: xyz [M,3] fp32, priority [M] fp32 or NULL, rgb [M,3] uint8 or NULL,
+ * voxel (the cell's edge), reduce, min_count.  All arithmetic is float64 on float64 copies, every operation rounded on its own.
+ *     r_a = x_a / voxel,  q_a = floor(r_a)  for a = x, y, z
+ *     the point is IN A VOXEL iff its coordinates are finite and -2^20 <= q_a < 2^20 for all three (compared as doubles); every
+ *         other point is dropped and counted in *dropped_host
+ *     key = ((q_x + 2^20) << 42) | ((q_y + 2^20) << 21) | (q_z + 2^20)     (63 bits)
+ *     value = (w << 32) | i  with i the point's row; w = 0 without priority, else with b = the fp32 bits of priority[i]:
+ *         w = ~(b ^ (b >> 31 ? 0xffffffff : 0x80000000)), and w = 0xffffffff for a NaN: the larger priority has the smaller w
+ *     the WINNER of a voxel is the minimum value over its points: the highest priority, the lowest row at an exact tie; a NaN
+ *         priority wins only against NaNs.  count = the number of points with the voxel's key.
+ *     kept voxels: count >= min_count, in ascending winner row (the output is a sub-sequence of the input)
+ * Outputs, one row per kept voxel: out_index [V] int32 = the winner's row, out_count [V] int32 (either may be NULL), and
+ *     reduce = A3R_VOXEL_BEST: out_xyz [V,3] and out_rgb [V,3] (or NULL) are the winner's rows, byte for byte
+ *     reduce = A3R_VOXEL_MEAN: the unweighted mean over the voxel's points, order-independent by integer sums:
+ *         t_a = (uint64)floor((r_a - q_a) * 2^24) per point,  S_a = the sum of t_a over the voxel (64-bit integers)
+ *         out_xyz_a = (float)(((double)q_a + ((double)S_a + 0.5 * count) / ((double)count * 2^24)) * voxel)
+ *         out_rgb_c = (2 * sum_c + count) / (2 * count) in integer arithmetic, sum_c = the sum of the channel over the voxel
+ * Contract: minima and sums of integers do not depend on the order of their operands, so the outputs are bitwise reproducible from
+ * call to call although the table is built with atomics, and bitwise the numpy restatement (tests/voxel_cases.py: voxel_ref).  Leaving
+ * out priority, rgb / out_rgb, out_index or out_count changes nothing in the other outputs.
+ * The table: open addressing with linear probing over `slots` entries (key, best value, count; six 64-bit sums more in mean mode).
+ * slots is a power of two above M and at most 2^31; slots = 0 means the smallest power of two >= 2 M (at most 2^31).  Where a key
+ * lands depends on the arrival order; nothing that is returned depends on it.  Passes in stream order: fill, insert (one thread per
+ * point: an agent-scope read of the slot's key, a 64-bit compare-and-swap on an empty slot, then an atomic minimum and atomic adds on
+ * the slot of its key, or the next slot; no locks, no waiting, at most `slots` probes; neighbouring lanes of a wave that share a key
+ * fold their integer minimum and sums into one lane first, which changes no word of the table), flag + per-chunk counts, scan,
+ * placement.
+ * Two phases, as a3r_align_scene_count / _export:
+ *   a3r_voxel_count  : *n_voxels_host = V, *dropped_host = the dropped points.
+ *   a3r_voxel_export : counts afresh; capacity < V is refused with A3R_EINVAL, the message names V and NOTHING is written; otherwise
+ *                      V rows are written.  *n_voxels_host = V and *dropped_host are set in both cases.
+ * Both synchronise `stream` once (the counts return to the host).  workspace: a3r_voxel_workspace_bytes(M, slots, reduce) bytes,
+ * 16-byte aligned: 256 + 4 (ceil(M / 1024) + 1) + 4 M + 20 slots bytes, 48 slots more for A3R_VOXEL_MEAN, each part rounded up to
+ * 256 (0 for refused sizes).
+ * A3R_EINVAL before anything is launched, naming the argument: M < 0 or M >= 2^31, an unknown reduce, voxel not finite or <= 0,
+ * min_count < 1, slots not a power of two, slots <= M or above 2^31, a null xyz with M > 0, a null count pointer, a workspace that
+ * is too small or misaligned, a negative capacity, a null out_xyz with capacity > 0, out_rgb without rgb.  A3R_ESTATE: a probe
+ * found no free slot (impossible while slots > M; a guard).  M = 0 is a success with V = 0. */
+#define A3R_VOXEL_BEST 0
+#define A3R_VOXEL_MEAN 1
+size_t a3r_voxel_workspace_bytes(long long M, long long slots, int reduce);
+int a3r_voxel_count(const float* xyz, const float* priority, long long M, double voxel, int reduce, int min_count, long long slots,
+                    void* workspace, size_t workspace_bytes, long long* n_voxels_host, long long* dropped_host, void* stream);
+int a3r_voxel_export(const float* xyz, const float* priority, const unsigned char* rgb, long long M, double voxel, int reduce,
+                     int min_count, long long slots, void* workspace, size_t workspace_bytes, long long capacity, float* out_xyz,
+                     unsigned char* out_rgb, int* out_index, int* out_count, long long* n_voxels_host, long long* dropped_host,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
