@@ -219,6 +219,19 @@ SIGNATURES = {
     "a3r_raft_encode": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, C.c_size_t, c_void]),
     "a3r_raft_forward_features": (C.c_int, [c_void, c_void, c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void, C.c_size_t, c_void]),
     "a3r_raft_forward": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void, C.c_size_t, C.POINTER(RaftTaps), c_void]),
+    "a3r_flow_conv7_planes": (C.c_int, [c_void, c_void, C.c_int, c_void, c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                        C.c_float, C.c_int, C.c_int, c_void]),
+    "a3r_flow_conv7_flow": (C.c_int, [c_void, c_void, c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void]),
+    "a3r_flow_dwconv7": (C.c_int, [c_void, c_void, c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void]),
+    "a3r_flow_gather_s2": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void]),
+    "a3r_flow_halve": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void]),
+    "a3r_flow_corr_lookup": (C.c_int, [C.POINTER(c_void), C.POINTER(C.c_int), C.POINTER(C.c_int), c_void, c_void, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_int, C.c_int, c_void]),
+    "a3r_flow_convex_upsample": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, c_void]),
+    "a3r_flow_scale": (C.c_int, [c_void, C.c_float, C.c_long, c_void]),
+    "a3r_flow_pack_cols": (C.c_int, [c_void, C.c_int, C.c_int, c_void, C.c_int, C.c_int, C.c_long, c_void]),
+    "a3r_flow_add": (C.c_int, [c_void, c_void, C.c_int, C.c_long, c_void]),
+    "a3r_flow_image_absmax": (C.c_int, [c_void, C.c_long, C.c_int, c_void, c_void]),
     "a3r_align_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "a3r_align_create": (C.c_int, [C.POINTER(AlignDesc), C.POINTER(c_void), c_void]),
     "a3r_align_pack_obs": (C.c_int, [c_void, c_void, C.c_int, C.c_long, c_void, c_void, c_void]),

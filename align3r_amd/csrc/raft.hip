@@ -18,9 +18,11 @@
 // the 1x1 shortcuts, 2x2 averaging, the correlation lookup and the convex up-sampling.  BatchNorm (evaluation mode) is folded into
 // the convolutions by the caller (align3r_amd/raft_weights.py fold_batchnorm), as are the ConvNeXt layer scale (into pwconv2) and
 // the 0.25 of the up-sampling weights (raft.py:216).  Maps are channels-last fp32 [B, h, w, C]; all buffers live in the caller's
-// workspace.  Below: the kernels, the weights as the plan reads them (bound once, at finalize), the pack plan, the launch plan.
+// workspace.  Below: the kernels and their launchers, the weights as the plan reads them (bound once, at finalize), the pack plan,
+// the launch plan, and the operator entries a3r_flow_* that run one kernel each through the same launchers.
 #include "plan.h"
 #include <cstdlib>
+#include <initializer_list>
 #include <new>
 
 namespace a3r {
@@ -204,7 +206,6 @@ __global__ __launch_bounds__(256) void scale_kernel(float* __restrict__ x, float
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) x[i] *= s;
 }
 
-// dst[r, c0 + c] = src[r, c] (c < Cs): channel concatenation of channels-last maps (torch.cat(dim=1) of the reference's NCHW tensors)
 // max |x| of each of gridDim.y equally long images (out: one zeroed word per image; a non-negative float compares like its bit pattern)
 __global__ __launch_bounds__(256) void image_absmax_kernel(const float* __restrict__ x, long n_per, unsigned* __restrict__ out) {
     const float* p = x + (size_t)blockIdx.y * n_per;
@@ -214,6 +215,7 @@ __global__ __launch_bounds__(256) void image_absmax_kernel(const float* __restri
     if ((threadIdx.x & 63) == 0) atomicMax(out + blockIdx.y, __float_as_uint(m));
 }
 
+// dst[r, c0 + c] = src[r, c] (c < Cs): channel concatenation of channels-last maps (torch.cat(dim=1) of the reference's NCHW tensors)
 __global__ __launch_bounds__(256) void pack_cols_kernel(float* __restrict__ dst, int ldd, int c0, const float* __restrict__ src, int lds, int Cs, long rows) {
     const long total = rows * Cs;
     for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
@@ -309,14 +311,69 @@ static inline unsigned grid1d(long n) {
     return (unsigned)(b < 1 ? 1 : b > 65536 ? 65536 : b);
 }
 
+// ------------------------------------------------------------------------------------------- launchers
+// One function per kernel: the plan below and the operator entries at the end of the file (a3r_flow_*, which the float64 pins of
+// tests/test_gpu_flow_kernels_f64.py call) launch through these, so the grid a test runs is the grid of production.
 // 7x7 convolutions of 2..6 input channels (stems, convf1): the fixed-size kernel where it applies, the generic one otherwise
-static void launch_direct_conv(const DirectConvArgs& a, hipStream_t st) {
+// (force_generic: the entries' form 1; A3R_RAFT_DIRECT_CONV=generic does the same for a whole process)
+static void launch_direct_conv(const DirectConvArgs& a, hipStream_t st, bool force_generic = false) {
     constexpr int PX = 8;
     const long work = (long)a.B * a.Ho * ((a.Wo + PX - 1) / PX) * a.Cout;
-    static const bool generic = getenv("A3R_RAFT_DIRECT_CONV") && std::string(getenv("A3R_RAFT_DIRECT_CONV")) == "generic";     // A/B switch
+    static const bool env_generic = getenv("A3R_RAFT_DIRECT_CONV") && std::string(getenv("A3R_RAFT_DIRECT_CONV")) == "generic";     // A/B switch
+    const bool generic = env_generic || force_generic;
     if (!generic && a.k == 7 && a.stride == 2) hipLaunchKernelGGL((direct_conv_fixed_kernel<7, 2, PX>), dim3(grid1d(work)), dim3(256), 0, st, a);
     else if (!generic && a.k == 7 && a.stride == 1) hipLaunchKernelGGL((direct_conv_fixed_kernel<7, 1, PX>), dim3(grid1d(work)), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(direct_conv_kernel, dim3(grid1d((long)a.B * a.Ho * ((a.Wo + DC_PX - 1) / DC_PX) * a.Cout)), dim3(256), 0, st, a);
+}
+// a 7x7 convolution, padding 3, of B maps [H, W] given as strided planes (see DirectConvArgs) -> y [B, Ho, Wo, Cout]
+struct Planes { const float *x0, *x1; int c0, c1; long sb, sc, sy, sx; float in_mul, in_add; };
+static void launch_conv7(const Planes& src, const float* wt, const float* bias, int B, int H, int W, int stride, int Cout, int relu, float* y,
+                         hipStream_t st, bool force_generic = false) {
+    DirectConvArgs a = {};
+    a.x0 = src.x0; a.x1 = src.x1; a.c0 = src.c0; a.c1 = src.c1;
+    a.sb = src.sb; a.sc = src.sc; a.sy = src.sy; a.sx = src.sx;
+    a.B = B; a.H = H; a.W = W; a.k = 7; a.stride = stride; a.pad = 3;
+    a.Ho = (H - 1) / stride + 1; a.Wo = (W - 1) / stride + 1; a.Cout = Cout;
+    a.in_mul = src.in_mul; a.in_add = src.in_add;
+    a.w = wt; a.bias = bias; a.relu = relu; a.y = y;
+    launch_direct_conv(a, st, force_generic);
+}
+// image planes [B, c, H, W] (one source, or two concatenated along channels); the channels-last 2-channel coarse flow [B, h, w, 2]
+static Planes image_planes(const float* x0, const float* x1, int c, int H, int W, float in_mul, float in_add) {
+    return {x0, x1, c, x1 ? c : 0, (long)c * H * W, (long)H * W, W, 1, in_mul, in_add};
+}
+static Planes flow_planes(const float* flow, int h, int w) { return {flow, nullptr, 2, 0, (long)h * w * 2, 1, (long)w * 2, 2, 1.f, 0.f}; }
+static void launch_transpose(const float* w, float* wt, int N, int K, hipStream_t st) {
+    hipLaunchKernelGGL(transpose_kernel, dim3((N * K + 255) / 256), dim3(256), 0, st, w, wt, N, K);
+}
+static void launch_dwconv7(const float* x, const float* wt, const float* bias, float* y, int B, int h, int w, int C, hipStream_t st) {
+    hipLaunchKernelGGL(dwconv7_kernel, dim3(grid1d((long)B * h * ((w + 3) / 4) * C)), dim3(256), 0, st, x, wt, bias, y, B, h, w, C);
+}
+static void launch_gather_s2(const float* x, float* y, int B, int h, int w, int ho, int wo, int C, hipStream_t st) {
+    hipLaunchKernelGGL(gather_s2_kernel, dim3(grid1d((long)B * ho * wo * C / 4)), dim3(256), 0, st, x, y, B, h, w, ho, wo, C / 4);
+}
+static void launch_halve(const float* x, float* y, int B, int h, int w, int ho, int wo, int C, hipStream_t st) {
+    hipLaunchKernelGGL(halve_kernel, dim3(grid1d((long)B * ho * wo * C)), dim3(256), 0, st, x, y, B, h, w, ho, wo, C);
+}
+static void launch_scale(float* x, float s, long n, hipStream_t st) {
+    hipLaunchKernelGGL(scale_kernel, dim3(grid1d(n)), dim3(256), 0, st, x, s, n);
+}
+static void launch_pack_cols(float* dst, int ldd, int c0, const float* src, int lds, int Cs, long rows, hipStream_t st) {
+    hipLaunchKernelGGL(pack_cols_kernel, dim3(grid1d(rows * Cs)), dim3(256), 0, st, dst, ldd, c0, src, lds, Cs, rows);
+}
+static void launch_flow_add(float* flow, const float* upd, int ldu, long rows, hipStream_t st) {
+    hipLaunchKernelGGL(flow_add_kernel, dim3(grid1d(rows * 2)), dim3(256), 0, st, flow, upd, ldu, rows);
+}
+// out [images] words, zeroed by the caller on the same stream
+static void launch_image_absmax(const float* x, long n_per, int images, unsigned* out, hipStream_t st) {
+    const long blocks = (n_per + 1023) / 1024;
+    hipLaunchKernelGGL(image_absmax_kernel, dim3((unsigned)(blocks < 64 ? blocks : 64), images), dim3(256), 0, st, x, n_per, out);
+}
+static void launch_corr_lookup(const LookupArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(corr_lookup_kernel, dim3(grid1d((long)a.B * a.h * a.w * a.ldo)), dim3(256), 0, st, a);
+}
+static void launch_convex_upsample(const float* flow, const float* mask, float* out, int B, int h, int w, hipStream_t st) {
+    hipLaunchKernelGGL(convex_upsample_kernel, dim3(grid1d((long)B * h * w * 64)), dim3(256), 0, st, flow, mask, out, B, h, w);
 }
 
 // ------------------------------------------------------------------------------------------- the weights, as the plan reads them
@@ -491,7 +548,7 @@ static int bind_item(a3r_raft_s* m, const RItem& it, char* pk, TwinTable<std::st
     if (it.kind == Pack::DIRECT) {
         if (int rc = m->w.need(wn, {it.N, it.K / 49, 7, 7}, who, &src)) return rc;
         float* wt = reinterpret_cast<float*>(pk + it.off);
-        hipLaunchKernelGGL(transpose_kernel, dim3((it.N * it.K + 255) / 256), dim3(256), 0, as_stream(stream), src, wt, it.N, it.K);
+        launch_transpose(src, wt, it.N, it.K, as_stream(stream));
         A3R_LAUNCH_CHECK();
         *it.direct = {wt, bias};
         return A3R_OK;
@@ -585,7 +642,7 @@ struct RPlan {
         if (hipGetLastError() != hipSuccess) { set_error("a3r_raft_forward: kernel launch failed"); rc = A3R_EHIP; }
     }
     void pack_cols(float* dst, int ldd, int c0, const float* src, int lds, int Cs, long rows) {
-        launch([&](hipStream_t st) { hipLaunchKernelGGL(pack_cols_kernel, dim3(grid1d(rows * Cs)), dim3(256), 0, st, dst, ldd, c0, src, lds, Cs, rows); });
+        launch([&](hipStream_t st) { launch_pack_cols(dst, ldd, c0, src, lds, Cs, rows, st); });
     }
     // n floats device to device: the given feature maps, the correlation's copy of fmap1, and the taps (dst null: not asked for)
     void copy(float* dst, const float* src, size_t n) {
@@ -593,16 +650,8 @@ struct RPlan {
         if (hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToDevice, as_stream(stream)) != hipSuccess) { set_error("a3r_raft_forward: device copy failed"); rc = A3R_EHIP; }
     }
     // a 7x7 direct convolution (padding 3, ReLU) of B maps [H, W] -> y [B, Ho, Wo, Cout]; src: where input element (b, c, y, x) sits
-    struct Planes { const float *x0, *x1; int c0, c1; long sb, sc, sy, sx; float in_mul, in_add; };
     void conv7(const RDirectW& w, const Planes& src, int B, int H, int W, int stride, int Cout, float* y) {
-        DirectConvArgs a = {};
-        a.x0 = src.x0; a.x1 = src.x1; a.c0 = src.c0; a.c1 = src.c1;
-        a.sb = src.sb; a.sc = src.sc; a.sy = src.sy; a.sx = src.sx;
-        a.B = B; a.H = H; a.W = W; a.k = 7; a.stride = stride; a.pad = 3;
-        a.Ho = (H - 1) / stride + 1; a.Wo = (W - 1) / stride + 1; a.Cout = Cout;
-        a.in_mul = src.in_mul; a.in_add = src.in_add;
-        a.w = w.wt; a.bias = w.b; a.relu = 1; a.y = y;
-        launch([&](hipStream_t st) { launch_direct_conv(a, st); });
+        launch([&](hipStream_t st) { launch_conv7(src, w.wt, w.b, B, H, W, stride, Cout, /*relu=*/1, y, st); });
     }
 };
 
@@ -630,9 +679,7 @@ void resnet(RPlan& P, const REncoderW& enc, float* s, int nimg, int H2, int W2, 
             const float* g3 = x3;
             if (b.stride == 2) {
                 float* gx = ar.alloc(px * cin);
-                P.launch([&](hipStream_t st) {
-                    hipLaunchKernelGGL(gather_s2_kernel, dim3(grid1d((long)px * cin / 4)), dim3(256), 0, st, x, gx, nimg, h, w, ho, wo, cin / 4);
-                });
+                P.launch([&](hipStream_t st) { launch_gather_s2(x, gx, nimg, h, w, ho, wo, cin, st); });
                 float* gx3 = P.alloc_op(px, cin);
                 P.split(gx, cin, gx3, (long)px, cin);
                 g3 = gx3;
@@ -702,8 +749,7 @@ struct RIter { float *n3, *t3, *lk, *lk3, *c13, *cf, *tmp, *f1, *f13, *cf3, *dw,
 // a 7x7 stem on image planes [B, 3, H, W] in [0, 255], normalised to 2 x / 255 - 1 on the way in (raft.py:194-195); x1: a second
 // image, concatenated along channels (raft.py:207)
 void stem(RPlan& P, const RDirectW& w, const float* x0, const float* x1, const RaftDims& g, float* y) {
-    const RPlan::Planes src = {x0, x1, 3, x1 ? 3 : 0, 3L * g.H * g.W, (long)g.H * g.W, g.W, 1, 2.f / 255.f, -1.f};
-    P.conv7(w, src, g.B, g.H, g.W, 2, g.c.initial_dim, y);
+    P.conv7(w, image_planes(x0, x1, 3, g.H, g.W, 2.f / 255.f, -1.f), g.B, g.H, g.W, 2, g.c.initial_dim, y);
 }
 
 // context network on cat(image1, image2) and init_conv (raft.py:207-209); net, context = split(cnet) (raft.py:210)
@@ -754,8 +800,7 @@ void corr_scales(RPlan& P, const RaftDims& g, const float* fm, float* amx, std::
     const long n_per = g.hw * g.D;
     bool ok = hipMemsetAsync(amx, 0, (size_t)2 * B * 4, st) == hipSuccess;
     if (ok) {
-        const long blocks = (n_per + 1023) / 1024;
-        hipLaunchKernelGGL(image_absmax_kernel, dim3((unsigned)(blocks < 64 ? blocks : 64), 2 * B), dim3(256), 0, st, fm, n_per, reinterpret_cast<unsigned*>(amx));
+        launch_image_absmax(fm, n_per, 2 * B, reinterpret_cast<unsigned*>(amx), st);
         ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(mx.data(), amx, (size_t)2 * B * 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
              hipStreamSynchronize(st) == hipSuccess;
     }
@@ -778,7 +823,7 @@ void corr_stage(RPlan& P, const RaftCall& k, const RaftDims& g, const RState& v)
         ArenaScope scope(ar);
         float* f1s = ar.alloc(Bhw * D);
         P.copy(f1s, v.fm, (size_t)Bhw * D);
-        P.launch([&](hipStream_t st) { hipLaunchKernelGGL(scale_kernel, dim3(grid1d(Bhw * D)), dim3(256), 0, st, f1s, 1.f / sqrtf((float)D), Bhw * D); });
+        P.launch([&](hipStream_t st) { launch_scale(f1s, 1.f / sqrtf((float)D), Bhw * D, st); });
         std::vector<float> s1(B, 1.f), s2(B, 1.f);
         float* amx = ar.alloc(2 * B);
         corr_scales(P, g, v.fm, amx, s1, s2);
@@ -808,7 +853,7 @@ void corr_stage(RPlan& P, const RaftCall& k, const RaftDims& g, const RState& v)
                 float* dst = (f2 == f2n) ? f2m : f2n;
                 const int ha = g.hl[l], wa = g.wl[l], hb = g.hl[l + 1], wb = g.wl[l + 1];
                 const float* src = f2;
-                P.launch([&](hipStream_t st) { hipLaunchKernelGGL(halve_kernel, dim3(grid1d((long)B * hb * wb * D)), dim3(256), 0, st, src, dst, B, ha, wa, hb, wb, D); });
+                P.launch([&](hipStream_t st) { launch_halve(src, dst, B, ha, wa, hb, wb, D, st); });
                 f2 = dst;
             }
         }
@@ -833,7 +878,7 @@ void lookup(RPlan& P, const RaftDims& g, const RState& v, const RIter& t) {
     LookupArgs a = {};
     for (int l = 0; l < g.c.corr_levels; l++) { a.corr[l] = v.corr[l]; a.hl[l] = g.hl[l]; a.wl[l] = g.wl[l]; }
     a.flow = v.flow8; a.out = t.lk; a.ldo = g.ccp; a.B = g.B; a.h = g.h; a.w = g.w; a.r = g.c.radius; a.levels = g.c.corr_levels;
-    P.launch([&](hipStream_t st) { hipLaunchKernelGGL(corr_lookup_kernel, dim3(grid1d(g.Bhw * g.ccp)), dim3(256), 0, st, a); });
+    P.launch([&](hipStream_t st) { launch_corr_lookup(a, st); });
 }
 
 // BasicMotionEncoder2 (update.py:99-117): lk, flow8 -> the motion features, columns 2 d .. 3 d of X
@@ -848,8 +893,7 @@ void motion_encoder(RPlan& P, const RaftDims& g, const RState& v, const RIter& t
     P.conv3(t.c13, me.convc2, t.tmp, B, h, w, 1, P.epi(A3R_EPI_RELU));                   // cor = relu(convc2(cor))
     P.pack_cols(t.cf, 2 * d, 0, t.tmp, d + d / 2, d + d / 2, Bhw);
     // flo = relu(convf1(flow)): 7x7 on the 2 channels of the channels-last coarse flow
-    const RPlan::Planes flow = {v.flow8, nullptr, 2, 0, g.hw * 2, 1, (long)w * 2, 2, 1.f, 0.f};
-    P.conv7(me.convf1, flow, B, h, w, 1, d, t.f1);
+    P.conv7(me.convf1, flow_planes(v.flow8, h, w), B, h, w, 1, d, t.f1);
     P.split(t.f1, d, t.f13, Bhw, d);
     P.conv3(t.f13, me.convf2, t.tmp, B, h, w, 1, P.epi(A3R_EPI_RELU));                   // flo = relu(convf2(flo))
     P.pack_cols(t.cf, 2 * d, d + d / 2, t.tmp, d / 2, d / 2, Bhw);                       // cat([cor, flo]) (update.py:113)
@@ -865,9 +909,7 @@ void refine(RPlan& P, const RaftDims& g, const RState& v, const RIter& t) {
     const long Bhw = g.Bhw;
     for (const RRefineW& r : P.m->bound.refine) {
         P.pack_cols(v.X, 3 * d, 0, v.net, d, d, Bhw);
-        P.launch([&](hipStream_t st) {
-            hipLaunchKernelGGL(dwconv7_kernel, dim3(grid1d((long)B * h * ((w + 3) / 4) * 3 * d)), dim3(256), 0, st, v.X, r.dw.wt, r.dw.b, t.dw, B, h, w, 3 * d);
-        });
+        P.launch([&](hipStream_t st) { launch_dwconv7(v.X, r.dw.wt, r.dw.b, t.dw, B, h, w, 3 * d, st); });
         P.layernorm(t.dw, r.norm, t.ln3, Bhw, 3 * d);
         OpEpi eg = P.epi(A3R_EPI_GELU);
         eg.out_op = 1;
@@ -951,14 +993,14 @@ int raft_plan(a3r_raft_s* m, const RaftCall& k, size_t* peak = nullptr) {
         if (it == 0 && k.taps.motion0) P.pack_cols(k.taps.motion0, d, 0, v.X + 2 * d, 3 * d, d, Bhw);      // (tap: the motion features alone)
         refine(P, g, v, t);
         heads(P, g, v, t);
-        P.launch([&](hipStream_t st) { hipLaunchKernelGGL(flow_add_kernel, dim3(grid1d(Bhw * 2)), dim3(256), 0, st, v.flow8, v.fu, 6, Bhw); });
+        P.launch([&](hipStream_t st) { launch_flow_add(v.flow8, v.fu, 6, Bhw, st); });
         if (it < 4) {
             P.copy(k.taps.net[it], v.net, (size_t)Bhw * d);
             P.copy(k.taps.flow8[it], v.flow8, (size_t)Bhw * 2);
         }
     }
     // flow_up = upsample_data(flow_8x, info_8x, weight_update)[0] (raft.py:183-199, 236)
-    P.launch([&](hipStream_t st) { hipLaunchKernelGGL(convex_upsample_kernel, dim3(grid1d(Bhw * 64)), dim3(256), 0, st, v.flow8, v.wgt, k.flow_out, g.B, g.h, g.w); });
+    P.launch([&](hipStream_t st) { launch_convex_upsample(v.flow8, v.wgt, k.flow_out, g.B, g.h, g.w, st); });
     if (peak) *peak = ar.peak;
     return P.rc;
 }
@@ -1036,4 +1078,133 @@ extern "C" int a3r_raft_forward(a3r_raft_t m, const float* image1, const float* 
     if (taps) k.taps = *taps;
     k.ws = workspace; k.ws_bytes = workspace_bytes; k.stream = stream;
     return raft_run(m, k, image1 && image2 && flow, "a3r_raft_forward");
+}
+
+// ------------------------------------------------------------------------------------------- operator entries
+// The kernels of this file one by one, through the launchers the plan uses (a3r.h has the contracts).  Sizes are bounded so that every
+// int the kernels compute stays an int; buffers are the caller's.
+#define A3R_FLOW_DIMS(who, ...) A3R_CHECK_ARG(flow_dims_ok({__VA_ARGS__}), who ": dimensions must be positive and their product below 2^31")
+static bool flow_dims_ok(std::initializer_list<long> dims) {
+    long n = 1;
+    for (long d : dims) {
+        if (d <= 0 || d > 0x7fffffffL) return false;
+        n *= d;
+        if (n > 0x7fffffffL) return false;
+    }
+    return true;
+}
+
+extern "C" int a3r_flow_conv7_planes(const float* x0, const float* x1, int c, const float* w, const float* bias, float* wt, float* y, int B,
+                                     int H, int W, int Cout, float in_mul, float in_add, int relu, int form, void* stream) {
+    A3R_CHECK_ARG(x0 && w && wt && y, "a3r_flow_conv7_planes: null pointer");
+    A3R_CHECK_ARG(c >= 1 && c <= 3, "a3r_flow_conv7_planes: 1..3 channels per source (got %d)", c);
+    A3R_CHECK_ARG(form == 0 || form == 1, "a3r_flow_conv7_planes: form must be 0 (as the plan chooses) or 1 (generic kernel)");
+    A3R_FLOW_DIMS("a3r_flow_conv7_planes", B, c, H, W);
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, Cin = x1 ? 2 * c : c;
+    A3R_FLOW_DIMS("a3r_flow_conv7_planes", B, Ho, Wo, Cout);
+    A3R_FLOW_DIMS("a3r_flow_conv7_planes", Cout, Cin * 49);
+    launch_transpose(w, wt, Cout, Cin * 49, as_stream(stream));
+    launch_conv7(image_planes(x0, x1, c, H, W, in_mul, in_add), wt, bias, B, H, W, 2, Cout, relu != 0, y, as_stream(stream), form == 1);
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+extern "C" int a3r_flow_conv7_flow(const float* flow, const float* w, const float* bias, float* wt, float* y, int B, int h, int wd, int Cout,
+                                   int relu, int form, void* stream) {
+    A3R_CHECK_ARG(flow && w && wt && y, "a3r_flow_conv7_flow: null pointer");
+    A3R_CHECK_ARG(form == 0 || form == 1, "a3r_flow_conv7_flow: form must be 0 (as the plan chooses) or 1 (generic kernel)");
+    A3R_FLOW_DIMS("a3r_flow_conv7_flow", B, h, wd, Cout);
+    A3R_FLOW_DIMS("a3r_flow_conv7_flow", Cout, 2 * 49);
+    launch_transpose(w, wt, Cout, 2 * 49, as_stream(stream));
+    launch_conv7(flow_planes(flow, h, wd), wt, bias, B, h, wd, 1, Cout, relu != 0, y, as_stream(stream), form == 1);
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+extern "C" int a3r_flow_dwconv7(const float* x, const float* w, const float* bias, float* wt, float* y, int B, int h, int wd, int C, void* stream) {
+    A3R_CHECK_ARG(x && w && bias && wt && y, "a3r_flow_dwconv7: null pointer");
+    A3R_FLOW_DIMS("a3r_flow_dwconv7", B, h, wd, C);
+    launch_transpose(w, wt, C, 49, as_stream(stream));
+    launch_dwconv7(x, wt, bias, y, B, h, wd, C, as_stream(stream));
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+extern "C" int a3r_flow_gather_s2(const float* x, float* y, int B, int h, int wd, int C, void* stream) {
+    A3R_CHECK_ARG(x && y, "a3r_flow_gather_s2: null pointer");
+    A3R_CHECK_ARG(C % 4 == 0, "a3r_flow_gather_s2: C must be a multiple of 4 (got %d)", C);
+    A3R_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0, "a3r_flow_gather_s2: x and y must be 16-byte aligned");
+    A3R_FLOW_DIMS("a3r_flow_gather_s2", B, h, wd, C);
+    launch_gather_s2(x, y, B, h, wd, (h - 1) / 2 + 1, (wd - 1) / 2 + 1, C, as_stream(stream));
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+extern "C" int a3r_flow_halve(const float* x, float* y, int B, int h, int wd, int C, void* stream) {
+    A3R_CHECK_ARG(x && y, "a3r_flow_halve: null pointer");
+    A3R_CHECK_ARG(h >= 2 && wd >= 2, "a3r_flow_halve: map %dx%d smaller than one 2x2 block", h, wd);
+    A3R_FLOW_DIMS("a3r_flow_halve", B, h, wd, C);
+    launch_halve(x, y, B, h, wd, h / 2, wd / 2, C, as_stream(stream));
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+extern "C" int a3r_flow_corr_lookup(const float* const* corr, const int* hl, const int* wl, const float* flow, float* out, int ldo, int B, int h,
+                                    int wd, int r, int levels, void* stream) {
+    A3R_CHECK_ARG(corr && hl && wl && flow && out, "a3r_flow_corr_lookup: null pointer");
+    A3R_CHECK_ARG(levels >= 1 && levels <= 4 && r >= 1 && r <= 8, "a3r_flow_corr_lookup: levels in 1..4, r in 1..8");
+    A3R_CHECK_ARG(ldo >= levels * (2 * r + 1) * (2 * r + 1), "a3r_flow_corr_lookup: ldo %d below the %d channels", ldo, levels * (2 * r + 1) * (2 * r + 1));
+    A3R_FLOW_DIMS("a3r_flow_corr_lookup", B, h, wd);
+    A3R_CHECK_ARG((long)B * h * wd * ldo < (1L << 40), "a3r_flow_corr_lookup: output too large");
+    LookupArgs a = {};
+    for (int l = 0; l < levels; l++) {
+        A3R_CHECK_ARG(corr[l], "a3r_flow_corr_lookup: null level %d", l);
+        A3R_CHECK_ARG(hl[l] >= 2 && wl[l] >= 2, "a3r_flow_corr_lookup: level %d is %dx%d, smaller than 2x2 (2 v / (n - 1) - 1 needs n >= 2)", l, hl[l], wl[l]);
+        A3R_FLOW_DIMS("a3r_flow_corr_lookup", hl[l], wl[l]);
+        a.corr[l] = corr[l]; a.hl[l] = hl[l]; a.wl[l] = wl[l];
+    }
+    a.flow = flow; a.out = out; a.ldo = ldo; a.B = B; a.h = h; a.w = wd; a.r = r; a.levels = levels;
+    launch_corr_lookup(a, as_stream(stream));
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+extern "C" int a3r_flow_convex_upsample(const float* flow, const float* mask, float* out, int B, int h, int wd, void* stream) {
+    A3R_CHECK_ARG(flow && mask && out, "a3r_flow_convex_upsample: null pointer");
+    A3R_FLOW_DIMS("a3r_flow_convex_upsample", B, h, wd, 64);
+    launch_convex_upsample(flow, mask, out, B, h, wd, as_stream(stream));
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+extern "C" int a3r_flow_scale(float* x, float s, long n, void* stream) {
+    A3R_CHECK_ARG(x && n > 0, "a3r_flow_scale: null pointer or empty array");
+    launch_scale(x, s, n, as_stream(stream));
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+extern "C" int a3r_flow_pack_cols(float* dst, int ldd, int c0, const float* src, int lds, int Cs, long rows, void* stream) {
+    A3R_CHECK_ARG(dst && src, "a3r_flow_pack_cols: null pointer");
+    A3R_CHECK_ARG(rows > 0 && Cs > 0 && c0 >= 0 && lds >= Cs && ldd >= c0 + Cs, "a3r_flow_pack_cols: columns %d..%d of %d from %d of %d do not fit", c0,
+                  c0 + Cs, ldd, Cs, lds);
+    launch_pack_cols(dst, ldd, c0, src, lds, Cs, rows, as_stream(stream));
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+extern "C" int a3r_flow_add(float* flow, const float* upd, int ldu, long rows, void* stream) {
+    A3R_CHECK_ARG(flow && upd && rows > 0 && ldu >= 2, "a3r_flow_add: null pointer, no rows or ldu below 2");
+    launch_flow_add(flow, upd, ldu, rows, as_stream(stream));
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
+}
+
+extern "C" int a3r_flow_image_absmax(const float* x, long n_per, int images, unsigned* out, void* stream) {
+    A3R_CHECK_ARG(x && out, "a3r_flow_image_absmax: null pointer");
+    A3R_CHECK_ARG(n_per > 0 && images > 0 && images <= 65535, "a3r_flow_image_absmax: n_per positive, 1..65535 images");
+    A3R_HIP(hipMemsetAsync(out, 0, (size_t)images * 4, as_stream(stream)));
+    launch_image_absmax(x, n_per, images, out, as_stream(stream));
+    A3R_LAUNCH_CHECK();
+    return A3R_OK;
 }

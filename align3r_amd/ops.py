@@ -499,6 +499,133 @@ def head_final(x, w, b):
     return pts, conf
 
 
+# ---- the flow network's kernels without a GEMM shape (csrc/raft.hip, a3r_flow_*), through the launchers the network's plan uses
+def _flow_out(out, shape, like, name):
+    if out is None:
+        return torch.empty(shape, device=like.device, dtype=torch.float32)
+    if tuple(_req(out, name).shape) != tuple(shape):
+        raise RuntimeError(f"{name} must have shape {tuple(shape)}")
+    return out
+
+
+def flow_conv7_planes(x0, w, bias=None, x1=None, in_mul=1.0, in_add=0.0, relu=True, form=0, out=None):
+    """7x7 convolution, padding 3, stride 2, of the planes x0 [B, c, H, W] (x1: a second source, concatenated along channels), every
+    element entering as x * in_mul + in_add; w [Cout, Cin, 7, 7] -> channels-last [B, Ho, Wo, Cout].  form 1: the generic kernel."""
+    B, c, H, W = _req(x0, "x0").shape
+    if x1 is not None and _req(x1, "x1").shape != x0.shape:
+        raise RuntimeError("x1 must have the shape of x0")
+    Cout, Cin = w.shape[:2]
+    if tuple(_req(w, "w").shape) != (Cout, c * (2 if x1 is not None else 1), 7, 7):
+        raise RuntimeError("w must be [Cout, Cin, 7, 7] with Cin the channels of the sources")
+    if bias is not None and tuple(_req(bias, "bias").shape) != (Cout,):
+        raise RuntimeError("bias must be [Cout]")
+    out = _flow_out(out, (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cout), x0, "out")
+    wt = torch.empty(Cin * 49 * Cout, device=x0.device, dtype=torch.float32)
+    check(_lib.load().a3r_flow_conv7_planes(ptr(x0), ptr(x1), c, ptr(w), ptr(bias), ptr(wt), ptr(out), B, H, W, Cout, in_mul, in_add,
+                                            int(relu), form, stream_ptr()), "flow_conv7_planes")
+    return out
+
+
+def flow_conv7_flow(flow, w, bias=None, relu=True, form=0, out=None):
+    """7x7 convolution, padding 3, stride 1, of the channels-last coarse flow [B, h, w, 2]; w [Cout, 2, 7, 7] -> [B, h, w, Cout]."""
+    B, h, wd, two = _req(flow, "flow").shape
+    Cout = w.shape[0]
+    if two != 2 or tuple(_req(w, "w").shape) != (Cout, 2, 7, 7):
+        raise RuntimeError("flow must be [B, h, w, 2] and w [Cout, 2, 7, 7]")
+    if bias is not None and tuple(_req(bias, "bias").shape) != (Cout,):
+        raise RuntimeError("bias must be [Cout]")
+    out = _flow_out(out, (B, h, wd, Cout), flow, "out")
+    wt = torch.empty(98 * Cout, device=flow.device, dtype=torch.float32)
+    check(_lib.load().a3r_flow_conv7_flow(ptr(flow), ptr(w), ptr(bias), ptr(wt), ptr(out), B, h, wd, Cout, int(relu), form, stream_ptr()),
+          "flow_conv7_flow")
+    return out
+
+
+def flow_dwconv7(x, w, bias, out=None):
+    """depthwise 7x7, padding 3, on channels-last x [B, h, w, C]; w [C, 1, 7, 7] or [C, 49], bias [C]."""
+    B, h, wd, Cc = _req(x, "x").shape
+    if _req(w, "w").numel() != Cc * 49 or w.shape[0] != Cc or tuple(_req(bias, "bias").shape) != (Cc,):
+        raise RuntimeError("w must be [C, 49] and bias [C]")
+    out = _flow_out(out, x.shape, x, "out")
+    wt = torch.empty(49 * Cc, device=x.device, dtype=torch.float32)
+    check(_lib.load().a3r_flow_dwconv7(ptr(x), ptr(w), ptr(bias), ptr(wt), ptr(out), B, h, wd, Cc, stream_ptr()), "flow_dwconv7")
+    return out
+
+
+def flow_gather_s2(x, out=None):
+    """x [B, h, w, C][:, ::2, ::2] (the sampling of a 1x1 convolution with stride 2); C % 4 == 0."""
+    B, h, wd, Cc = _req(x, "x").shape
+    out = _flow_out(out, (B, (h - 1) // 2 + 1, (wd - 1) // 2 + 1, Cc), x, "out")
+    check(_lib.load().a3r_flow_gather_s2(ptr(x), ptr(out), B, h, wd, Cc, stream_ptr()), "flow_gather_s2")
+    return out
+
+
+def flow_halve(x, out=None):
+    """F.interpolate(scale_factor=0.5, mode='bilinear') of channels-last x [B, h, w, C]: 2x2 means -> [B, h // 2, w // 2, C]."""
+    B, h, wd, Cc = _req(x, "x").shape
+    out = _flow_out(out, (B, h // 2, wd // 2, Cc), x, "out")
+    check(_lib.load().a3r_flow_halve(ptr(x), ptr(out), B, h, wd, Cc, stream_ptr()), "flow_halve")
+    return out
+
+
+def flow_corr_lookup(corr, flow, r, ldo=None, out=None):
+    """Correlation lookup: corr, a list of levels [B h w, h_l, w_l]; flow [B, h, w, 2] -> [B h w, ldo], channel l (2r+1)^2 + a (2r+1) + c,
+    the columns past levels (2r+1)^2 zero."""
+    B, h, wd, two = _req(flow, "flow").shape
+    n = len(corr)
+    if two != 2 or not 1 <= n <= 4 or any(_req(c, "corr").dim() != 3 or c.shape[0] != B * h * wd for c in corr):
+        raise RuntimeError("flow must be [B, h, w, 2] and corr 1..4 levels [B h w, h_l, w_l]")
+    ldo = n * (2 * r + 1) ** 2 if ldo is None else ldo
+    out = _flow_out(out, (B * h * wd, ldo), flow, "out")
+    ptrs = (C.c_void_p * n)(*[c.data_ptr() for c in corr])
+    hl, wl = (C.c_int * n)(*[c.shape[1] for c in corr]), (C.c_int * n)(*[c.shape[2] for c in corr])
+    check(_lib.load().a3r_flow_corr_lookup(ptrs, hl, wl, ptr(flow), ptr(out), ldo, B, h, wd, r, n, stream_ptr()), "flow_corr_lookup")
+    return out
+
+
+def flow_convex_upsample(flow, mask, out=None):
+    """Convex up-sampling: flow [B, h, w, 2], mask [B, h, w, 576] (channel k 64 + i 8 + j) -> [B, 2, 8 h, 8 w]."""
+    B, h, wd, two = _req(flow, "flow").shape
+    if two != 2 or tuple(_req(mask, "mask").shape) != (B, h, wd, 576):
+        raise RuntimeError("flow must be [B, h, w, 2] and mask [B, h, w, 576]")
+    out = _flow_out(out, (B, 2, 8 * h, 8 * wd), flow, "out")
+    check(_lib.load().a3r_flow_convex_upsample(ptr(flow), ptr(mask), ptr(out), B, h, wd, stream_ptr()), "flow_convex_upsample")
+    return out
+
+
+def flow_scale(x, s):
+    """x *= s, in place."""
+    check(_lib.load().a3r_flow_scale(ptr(_req(x, "x")), s, x.numel(), stream_ptr()), "flow_scale")
+    return x
+
+
+def flow_pack_cols(dst, c0, src, Cs=None):
+    """dst [rows, ldd][:, c0:c0 + Cs] = src [rows, lds][:, :Cs], in place."""
+    rows, ldd = _req(dst, "dst").shape
+    if _req(src, "src").dim() != 2 or src.shape[0] != rows:
+        raise RuntimeError("src must have the rows of dst")
+    Cs = src.shape[1] if Cs is None else Cs
+    check(_lib.load().a3r_flow_pack_cols(ptr(dst), ldd, c0, ptr(src), src.shape[1], Cs, rows, stream_ptr()), "flow_pack_cols")
+    return dst
+
+
+def flow_add(flow, upd):
+    """flow [rows, 2] += upd [rows, ldu][:, :2], in place."""
+    rows, two = _req(flow, "flow").shape
+    if two != 2 or _req(upd, "upd").dim() != 2 or upd.shape[0] != rows:
+        raise RuntimeError("flow must be [rows, 2] and upd [rows, ldu]")
+    check(_lib.load().a3r_flow_add(ptr(flow), ptr(upd), upd.shape[1], rows, stream_ptr()), "flow_add")
+    return flow
+
+
+def flow_image_absmax(x):
+    """max |x| of every image of x [images, ...] -> float32 [images] (the bits of a non-negative float, as the kernel's atomic max leaves them)."""
+    images = _req(x, "x").shape[0]
+    out = torch.full((images,), -1, device=x.device, dtype=torch.int32)
+    check(_lib.load().a3r_flow_image_absmax(ptr(x), x.numel() // images, images, ptr(out), stream_ptr()), "flow_image_absmax")
+    return out.view(torch.float32)
+
+
 MOTION_ENTRY = np.dtype([('depth_row', '<i4'), ('flow_row', '<i4'), ('image', '<i4'), ('pad', '<i4'), ('depth_rt', '<f4', (4,)),
                          ('Hm', '<f4', (9,)), ('Kt', '<f4', (3,))])
 

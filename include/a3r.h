@@ -640,6 +640,39 @@ int a3r_raft_encode(a3r_raft_t m, const float* image, int B, int H, int W, float
 int a3r_raft_forward_features(a3r_raft_t m, const float* image1, const float* image2, const float* fmap1, const float* fmap2, int B, int H,
                               int W, int iters, float* flow, void* workspace, size_t workspace_bytes, void* stream);
 
+/* (3c) The flow network's kernels that have no GEMM shape, one by one (csrc/raft.hip): each entry goes through the launcher the plan
+ *      of a3r_raft_forward uses, so its grid is production's.  Maps are channels-last fp32 unless said otherwise; every buffer is the
+ *      caller's; nothing waits for the stream.  Dimensions must be positive with a product below 2^31. */
+/* 7x7 convolution, padding 3, stride 2, of image planes: x0 (and x1 unless NULL, concatenated along channels, raft.py:207), each
+ * [B, c, H, W] with c in 1..3, every element entering as x * in_mul + in_add (raft.py:194-195) -> y [B, Ho, Wo, Cout], Ho = (H - 1) / 2
+ * + 1.  w: [Cout, Cin, 7, 7] as PyTorch stores it (Cin = c or 2 c); wt: Cout Cin 49 floats of workspace that receive its transpose
+ * (as a3r_raft_finalize makes it); bias [Cout] or NULL; relu: clamp at zero.  form: 0 = the kernel the plan chooses, 1 = the generic
+ * kernel (what A3R_RAFT_DIRECT_CONV=generic selects for a whole process); the two agree bit for bit. */
+int a3r_flow_conv7_planes(const float* x0, const float* x1, int c, const float* w, const float* bias, float* wt, float* y, int B, int H,
+                          int W, int Cout, float in_mul, float in_add, int relu, int form, void* stream);
+/* the same, stride 1, on the channels-last 2-channel coarse flow [B, h, w, 2] (update.py:105) -> y [B, h, w, Cout]; w [Cout, 2, 7, 7] */
+int a3r_flow_conv7_flow(const float* flow, const float* w, const float* bias, float* wt, float* y, int B, int h, int w_, int Cout, int relu,
+                        int form, void* stream);
+/* depthwise 7x7, padding 3 (layer.py:52): x, y [B, h, w, C]; w [C, 49] ([C, 1, 7, 7]); wt: 49 C floats of workspace; bias [C] */
+int a3r_flow_dwconv7(const float* x, const float* w, const float* bias, float* wt, float* y, int B, int h, int w_, int C, void* stream);
+/* y [B, (h - 1) / 2 + 1, (w - 1) / 2 + 1, C] = x [B, h, w, C] at even rows and columns (layer.py:125); C % 4 == 0, 16-byte aligned */
+int a3r_flow_gather_s2(const float* x, float* y, int B, int h, int w_, int C, void* stream);
+/* y [B, h / 2, w / 2, C] = F.interpolate(x, scale_factor=0.5, mode='bilinear') (corr.py:22): 2x2 means; h, w >= 2 */
+int a3r_flow_halve(const float* x, float* y, int B, int h, int w_, int C, void* stream);
+/* Correlation lookup (corr.py:25-50, utils.py:76-91): corr[l] [B h w, hl[l], wl[l]] for l < levels (host arrays of `levels` entries;
+ * 1..4 levels, each at least 2x2), flow [B, h, w, 2], r in 1..8 -> out [B h w, ldo]: channel l (2r+1)^2 + a (2r+1) + c is level l
+ * sampled at ((x + fx) / 2^l + a - r, (y + fy) / 2^l + c - r), zeros outside; columns from levels (2r+1)^2 to ldo are set to zero. */
+int a3r_flow_corr_lookup(const float* const* corr, const int* hl, const int* wl, const float* flow, float* out, int ldo, int B, int h, int w_,
+                         int r, int levels, void* stream);
+/* Convex up-sampling (raft.py:183-199): flow [B, h, w, 2], mask [B, h, w, 576] -> out [B, 2, 8 h, 8 w] (planes) */
+int a3r_flow_convex_upsample(const float* flow, const float* mask, float* out, int B, int h, int w_, void* stream);
+/* the movers: x[i] *= s (i < n); dst[r, c0 + c] = src[r, c] (c < Cs, r < rows; rows of ldd / lds floats); flow [rows, 2] += upd [rows, ldu]
+ * [:, 0:2]; out[i] = bits of max |x| over image i of `images` (<= 65535) images of n_per floats (out is cleared first) */
+int a3r_flow_scale(float* x, float s, long n, void* stream);
+int a3r_flow_pack_cols(float* dst, int ldd, int c0, const float* src, int lds, int Cs, long rows, void* stream);
+int a3r_flow_add(float* flow, const float* upd, int ldu, long rows, void* stream);
+int a3r_flow_image_absmax(const float* x, long n_per, int images, unsigned* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * (4) global alignment inner loop: PointCloudOptimizer (cloud_opt/optimizer.py, base_opt.py)
  */

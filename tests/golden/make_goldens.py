@@ -2,7 +2,7 @@
 """Generate the golden fixtures under tests/golden/ by RUNNING THE REFERENCE in the build container.
 
 Usage (build container only -- /root/reference does not exist on the GPU box):
-    python tests/golden/make_goldens.py [--only pairs|ops|tiny|vitl|vitlhi|align|alignx|alignflow|alignprior|prep|hier|flowgeo|raft|raftclip|raftclip64] [--out tests/golden]
+    python tests/golden/make_goldens.py [--only pairs|ops|tiny|vitl|vitlhi|align|alignx|alignflow|alignprior|prep|hier|flowgeo|raft|raftclip|raftclip64|raftodd] [--out tests/golden]
 
 What it does
   * puts /root/reference on sys.path (read-only, bytecode writing disabled) and imports the
@@ -989,6 +989,32 @@ def _raftclip_arrays(dtype):
     return {k: np.ascontiguousarray(v) for k, v in g.items()}
 
 
+def _write_parts(out, stem, g):
+    """g (name -> float32 array) as numbered parts <stem>.<n>.npz, each below RAFTCLIP_PART_BYTES: arrays in insertion order, an array
+    larger than a part cut along its flattened length into `name@k` pieces (tests/test_gpu_raft.py:load_parts).  Returns the count."""
+    parts, cur, size = [], {}, 0
+    room = RAFTCLIP_PART_BYTES - 20000                          # zip directory and .npy headers
+    for k, v in g.items():
+        flat, k0, n = v.reshape(-1), 0, 0
+        while k0 < flat.size:
+            if size >= room - 4096:
+                parts.append(cur)
+                cur, size = {}, 0
+            take = min(flat.size - k0, (room - size) // 4)
+            cur[f"{k}@{n}"] = flat[k0:k0 + take]
+            size += 4 * take
+            k0, n = k0 + take, n + 1
+        cur[k + "@shape"] = np.asarray(v.shape, np.int64)
+    parts.append(cur)
+    for f in os.listdir(out):
+        assert not (f.startswith(stem + ".") and f.endswith(".npz") and int(f.split(".")[1]) >= len(parts)), f"stale part {f}"
+    for n, part in enumerate(parts):
+        path = os.path.join(out, f"{stem}.{n}.npz")
+        np.savez_compressed(path, **part)
+        assert os.path.getsize(path) < RAFTCLIP_PART_BYTES, (path, os.path.getsize(path))
+    return len(parts)
+
+
 def gen_raftclip(out):
     """RAFT2 at the sizes the pipeline runs, and with small feature maps -- kept out of raft.npz so that file regenerates unchanged.
 
@@ -1015,26 +1041,7 @@ def gen_raftclip(out):
     assert all(v.dtype == np.float32 for v in g.values())
     for k, p2 in RAFTCLIP_LOW16_FROM_LOW8.items():              # exact in fp32 (checked here), so stored once
         assert np.array_equal(g.pop("low16_" + k), g["low8_" + k] * np.float32(2.0 ** p2)), k
-    parts, cur, size = [], {}, 0
-    room = RAFTCLIP_PART_BYTES - 20000                          # zip directory and .npy headers
-    for k, v in g.items():
-        flat, k0, n = v.reshape(-1), 0, 0
-        while k0 < flat.size:
-            if size >= room - 4096:
-                parts.append(cur)
-                cur, size = {}, 0
-            take = min(flat.size - k0, (room - size) // 4)
-            cur[f"{k}@{n}"] = flat[k0:k0 + take]
-            size += 4 * take
-            k0, n = k0 + take, n + 1
-        cur[k + "@shape"] = np.asarray(v.shape, np.int64)
-    parts.append(cur)
-    for f in os.listdir(out):
-        assert not (f.startswith("raft_clip.") and f.endswith(".npz") and int(f.split(".")[1]) >= len(parts)), f"stale part {f}"
-    for n, part in enumerate(parts):
-        path = os.path.join(out, f"raft_clip.{n}.npz")
-        np.savez_compressed(path, **part)
-        assert os.path.getsize(path) < RAFTCLIP_PART_BYTES, (path, os.path.getsize(path))
+    parts = range(_write_parts(out, "raft_clip", g))
     print("raftclip:", {k: v.shape for k, v in g.items()}, f"in {len(parts)} parts")
     print("raftclip: max|flow|", {k: float(np.abs(v).max()) for k, v in g.items() if k.endswith("_flow")})
     print("raftclip: max|tap| ", {k: float(np.abs(v).max()) for k, v in g.items() if k.startswith("low") and "fmap" in k})
@@ -1055,6 +1062,66 @@ def gen_raftclip64(out):
         e = np.abs(g32[k].astype(np.float64) - g64[k]).max() / np.abs(g64[k]).max()
         print(f"raftclip64: {k:20s} max|fp64| {np.abs(g64[k]).max():.6g}  fp32-vs-fp64 {e:.2e}")
         assert e < 1e-5, (k, e)
+
+
+RAFTODD = (176, 168, 41)          # H, W, frame seed: the 1/8 map is 22 x 21, its pyramid 22x21, 11x10, 5x5, 2x2
+
+
+def gen_raftodd(out):
+    """RAFT2 on a frame whose widths are ragged for the flow kernels' column groups: 176 x 168, so the stems' half-resolution map is
+    88 x 84 (84 % 8 = 4: direct_conv_fixed_kernel's last thread of a row owns 4 of its 8 columns) and the 1/8 map 22 x 21 (21 % 4 = 1:
+    dwconv7_kernel's last thread owns one column), with odd pyramid levels in both directions and a 2 x 2 last level (the lookup's
+    2 v / (n - 1) - 1 round trip at n = 2).  Every other golden has widths that are multiples of both.
+    raft_odd.<n>.npz (2.1 MB of float32 that hardly compresses: numbered parts as raft_clip's, each below RAFTCLIP_PART_BYTES;
+    tests/test_gpu_raft.py:load_parts reads them): RAFT_TINY, 1 pair, frame seed 41, 3 iterations, stepped by hand as gen_raft does: context network, both feature
+    maps, correlation levels 1..3 (level 0 is 462 x 462 and is pinned operator by operator in tests/test_gpu_flow_kernels_f64.py),
+    the first lookup and motion features, hidden state and coarse flow after every iteration, the final flow; RAFT_M, the same
+    pair, 20 iterations as the reference calls it: the final flow."""
+    from align3r_amd.raft_weights import RAFT_M, RAFT_TINY, synthetic_raft_frames as raft_images
+    build, corr_mod, utils_mod = _raft_reference()
+    H, W, seed = RAFTODD
+    B, iters = 1, 3
+    i1, i2 = raft_images(B, H, W, seed)
+    g = {}
+    net = build(RAFT_TINY)
+    with torch.no_grad():
+        ref = net(torch.from_numpy(i1), torch.from_numpy(i2), iters=iters, test_mode=True)
+        a = 2 * (torch.from_numpy(i1) / 255.0) - 1.0
+        b = 2 * (torch.from_numpy(i2) / 255.0) - 1.0
+        cnet = net.init_conv(net.cnet(torch.cat([a, b], dim=1)))
+        g["t_cnet"] = cnet.permute(0, 2, 3, 1).numpy()
+        d = RAFT_TINY.dim
+        hid, context = torch.split(cnet, [d, d], dim=1)
+        fu = net.flow_head(hid)
+        flow8 = fu[:, :2]
+        f1, f2 = net.fnet(a), net.fnet(b)
+        g["t_fmap1"], g["t_fmap2"] = f1.permute(0, 2, 3, 1).numpy(), f2.permute(0, 2, 3, 1).numpy()
+        corr_fn = corr_mod.CorrBlock2(f1, f2, net.args)
+        for lv, c in enumerate(corr_fn.corr_pyramid):
+            if lv > 0:
+                g[f"t_corr_pyr{lv}"] = c[:, 0].numpy()
+        assert tuple(corr_fn.corr_pyramid[3].shape[-2:]) == (2, 2)
+        dil = torch.ones(B, 1, H // 8, W // 8)
+        for it in range(iters):
+            coords2 = utils_mod.coords_grid2(B, H // 8, W // 8, device="cpu") + flow8
+            corr = corr_fn(coords2, dilation=dil)
+            if it == 0:
+                g["t_corr_lookup0"] = corr.permute(0, 2, 3, 1).numpy()
+                g["t_motion0"] = net.update_block.encoder(flow8, corr).permute(0, 2, 3, 1).numpy()
+            hid = net.update_block(hid, context, corr, flow8)
+            fu = net.flow_head(hid)
+            flow8 = flow8 + fu[:, :2]
+            g[f"t_net_{it}"] = hid.permute(0, 2, 3, 1).numpy()
+            g[f"t_flow8_{it}"] = flow8.permute(0, 2, 3, 1).numpy()
+        up, _ = net.upsample_data(flow8, fu[:, 2:], .25 * net.upsample_weight(hid))
+        assert torch.equal(up, ref[1]), "hand-stepped forward differs from RAFT2.forward"
+        g["t_flow"] = up.numpy()
+        g["m_flow"] = build(RAFT_M)(torch.from_numpy(i1), torch.from_numpy(i2), iters=20, test_mode=True)[1].numpy()
+    g = {k: np.ascontiguousarray(v) for k, v in g.items()}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in g.values())
+    n = _write_parts(out, "raft_odd", g)
+    print("raftodd:", {k: v.shape for k, v in g.items()}, f"in {n} parts")
+    print("raftodd: max|flow|", float(np.abs(g["t_flow"]).max()), float(np.abs(g["m_flow"]).max()))
 
 
 def main():

@@ -18,9 +18,15 @@ Both of the above run in BOTH arithmetics (A3R_RAFT = fh2, bf3): the fallback is
   * small feature maps (fnet.final_conv x 2^-8 and x 2^-16): feature maps, the four correlation levels, the first lookup and motion
     features at 1e-4 of each tap's maximum.  Before the correlation operands got a per-image power-of-two scale (csrc/raft.hip) the fh2
     correlation taps measured 2.5e-5 (2^-8) and 5.7e-3 (2^-16, failing); now <= 7.8e-7 in both cases, bf3 <= 8.5e-7.
-What is pinned: every stage at 128 x 160 in both arithmetics, the final flow at four sizes, the correlation path over a 2^16 range of
-feature-map magnitudes.  Not pinned: intermediate stages of RAFT_M, and large (> 2^15) feature maps against the reference (the
-fallback test checks those bitwise against bf3 only).
+  * a ragged frame, 176 x 168 (tests/golden/raft_odd.<n>.npz, make_goldens.py --only raftodd): half-resolution width 84 (% 8 = 4) in
+    the stems, a 22 x 21 eighth-resolution map (w % 4 = 1 in the depthwise convolution) with pyramid 22x21, 11x10, 5x5, 2x2: RAFT_TINY
+    stage by stage and RAFT_M's final flow after 20 iterations, both arithmetics, at 1e-4.
+What is pinned: every stage at 128 x 160 and at 176 x 168 in both arithmetics, the final flow at five sizes, the correlation path over
+a 2^16 range of feature-map magnitudes.  The kernels of csrc/raft.hip that have no GEMM shape are pinned one by one against float64 at
+their own tolerances, ragged tails, border arithmetic and second loop trips included, in tests/test_gpu_flow_kernels_f64.py (DESIGN
+has the table).  Not pinned: intermediate stages of RAFT_M, level 0 of the correlation pyramid at 176 x 168 (462 x 462 values: its
+GEMM is pinned at 128 x 160, its lookup operator by operator), and large (> 2^15) feature maps against the reference (the fallback
+test checks those bitwise against bf3 only).
 """
 import os
 
@@ -177,6 +183,59 @@ def test_raft_m_at_the_sizes_the_pipeline_runs(gc, monkeypatch, arith, tag, H, W
         assert tuple(out3.shape) == (3, 2, H, W)
         assert torch.equal(out3[1], out[1][0])
         assert not torch.equal(out3[0], out[1][0])
+
+
+@pytest.fixture(scope="module")
+def go():
+    """raft_odd (make_goldens.py --only raftodd): one pair of 176 x 168 frames, frame seed 41"""
+    return load_parts("raft_odd")
+
+
+@pytest.mark.parametrize("arith", ARITH)
+def test_raft_ragged_widths(go, monkeypatch, arith):
+    """176 x 168: no width of this frame is a multiple of a kernel's column group -- 84 columns at half resolution (8 per thread in the
+    stems), 21 at one eighth (4 per thread in the depthwise convolution, 8 in convf1) -- and the pyramid is 22x21, 11x10, 5x5, 2x2.
+    RAFT_TINY, 3 iterations, every stored stage, and RAFT_M's final flow after 20 iterations, each at TOL of its own maximum."""
+    from align3r_amd.raft import RAFT2
+    cfg = RAFT_TINY
+    eng = engine(monkeypatch, arith, cfg, synthetic_raft_state_dict(cfg, 0))
+    B, H, W, iters = 1, 176, 168, 3
+    h, w, d = H // 8, W // 8, cfg.dim
+    i1, i2 = synthetic_raft_frames(B, H, W, 41)
+    ccp = (cfg.corr_channel + 31) // 32 * 32
+    z = lambda *s: torch.full(s, float("nan"), device="cuda")
+    taps = dict(cnet=z(B, h, w, 2 * d), fmap=z(2 * B, h, w, 2 * d), lookup0=z(B, h, w, ccp), motion0=z(B, h, w, d))
+    hl, wl = h, w
+    for l in range(cfg.corr_levels):
+        taps[f"corr_pyr{l}"] = z(B * h * w, hl, wl)
+        hl, wl = hl // 2, wl // 2
+    assert (hl * 2, wl * 2) == (2, 2)
+    for it in range(iters):
+        taps[f"net{it}"] = z(B, h, w, d)
+        taps[f"flow8_{it}"] = z(B, h, w, 2)
+    flow = eng.forward(dev(i1), dev(i2), iters=iters, taps=taps)
+    t = {k: v.cpu().numpy() for k, v in taps.items()}
+    assert all(np.isfinite(v).all() for v in t.values())            # every tap fully written
+    m = dict(cnet=rel_err(t["cnet"], go["t_cnet"]), fmap1=rel_err(t["fmap"][:B], go["t_fmap1"]), fmap2=rel_err(t["fmap"][B:], go["t_fmap2"]))
+    for l in range(1, cfg.corr_levels):
+        m[f"corr_pyr{l}"] = rel_err(t[f"corr_pyr{l}"], go[f"t_corr_pyr{l}"])
+    m["lookup0"] = rel_err(t["lookup0"][..., :cfg.corr_channel], go["t_corr_lookup0"])
+    assert not t["lookup0"][..., cfg.corr_channel:].any()
+    m["motion0"] = rel_err(t["motion0"], go["t_motion0"])
+    for it in range(iters):
+        m[f"net{it}"] = rel_err(t[f"net{it}"], go[f"t_net_{it}"])
+        m[f"flow8_{it}"] = rel_err(t[f"flow8_{it}"], go[f"t_flow8_{it}"])
+    m["flow"] = rel_err(flow.cpu().numpy(), go["t_flow"])
+    assert eng.range_fallbacks == 0
+    net = RAFT2(RAFT_M, synthetic_raft_state_dict(RAFT_M, 0)).to("cuda").eval()
+    assert net._engine.fh2 == (arith == "fh2")
+    out = net(dev(i1), dev(i2), iters=20, test_mode=True)[1]
+    assert tuple(out.shape) == (1, 2, H, W)
+    m["m_flow_iter20"] = rel_err(out.cpu().numpy(), go["m_flow"])
+    record_margin(f"raft_ragged_vs_reference_{arith}", **m)
+    bad = {k: v for k, v in m.items() if not v < TOL}
+    assert not bad, bad
+    assert net._engine.range_fallbacks == 0
 
 
 @pytest.mark.parametrize("arith", ARITH)
