@@ -11,12 +11,11 @@
 // statistics are per-lane (one cross-half exchange), and the exponentiated tile is directly the B operand
 // of the second product O^T = V^T P^T -- no LDS round trip or lane movement for P.
 // K/V tiles of 64 keys are staged global -> registers -> LDS (double-buffered, rows padded to 68 floats).
-#include "common.h"
+#include "attention_tile.h"
 
 namespace a3r {
 
-constexpr int AQ = 128;     // queries per workgroup
-constexpr int AK = 64;      // keys per tile
+constexpr int AK = ATTN_K;  // keys per tile
 constexpr int ALD = 68;     // padded LDS row (floats)
 constexpr int ATTN_LDS_BYTES = 2 * 2 * AK * ALD * 4;   // 69,632 B
 
@@ -33,15 +32,8 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(AttnArgs a) {
     float* Vs = Ks + 2 * AK * ALD;                // [2][AK][ALD]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int qi = lane & 31, half = lane >> 5;
-    // XCD-aware mapping: the query blocks of one (batch, head) re-read the same K/V; workgroup ids are dealt
-    // round-robin over the 8 XCDs (private L2s), so give all query blocks of a head to ONE XCD.
-    const int nqb = (a.Nq + AQ - 1) / AQ;
-    const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
-    const int group = (seq / nqb) * 8 + xcd, qb = seq - (seq / nqb) * nqb;
-    if (group >= a.B * a.H) return;                 // uniform per workgroup
-    const int h = group % a.H, b = group / a.H;
-    const int q_row = qb * AQ + wave * 32 + qi;
-    const int q_ld = q_row < a.Nq ? q_row : a.Nq - 1;
+    int b, h, q_row, q_ld;
+    if (!attn_place(a.Nq, a.B, a.H, wave, qi, b, h, q_row, q_ld)) return;
 
     // Q fragment (B operand of S^T = K Q^T): lane holds Q[q][8*kb + 4*half + t], pre-scaled by hd^-0.5
     f32x4 qf[8];
@@ -110,7 +102,8 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(AttnArgs a) {
                 s[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(k1v[tt], qf[kb][tt], s[1], 0, 0, 0);
             }
         }
-        // ---- online softmax (keys of this lane: kt*32 + (e&3) + 8*(e>>2) + 4*half)
+        // ---- online softmax over both blocks at once, written out (attention_tile.h says why); keys of this lane:
+        //      kt*32 + (e&3) + 8*(e>>2) + 4*half
         if (k0 + AK > a.Nk) {
 #pragma unroll
             for (int kt = 0; kt < 2; kt++)
@@ -158,19 +151,8 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(AttnArgs a) {
         if (t + 1 < ntiles) store_tile(buf ^ 1);
         __syncthreads();
     }
-    const float l_tot = l_run + __shfl_xor(l_run, 32);
-    const float inv_l = 1.f / l_tot;
-    if (q_row < a.Nq) {
-        float* op = a.o + ((size_t)b * a.Nq + q_row) * a.ldo + h * 64 + 4 * half;
-#pragma unroll
-        for (int dt = 0; dt < 2; dt++)
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                f32x4 v = {oacc[dt][4 * g] * inv_l, oacc[dt][4 * g + 1] * inv_l, oacc[dt][4 * g + 2] * inv_l,
-                           oacc[dt][4 * g + 3] * inv_l};
-                *reinterpret_cast<f32x4*>(op + dt * 32 + 8 * g) = v;
-            }
-    }
+    float* op = a.o + ((size_t)b * a.Nq + q_row) * a.ldo;
+    attn_normalise_store(oacc, l_run, 1.f, q_row < a.Nq, h, half, [&](int col, f32x4 v) { *reinterpret_cast<f32x4*>(op + col) = v; });
 }
 
 }  // namespace a3r
@@ -178,20 +160,7 @@ using namespace a3r;
 
 extern "C" int a3r_attention(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o,
                              int ldo, int B, int H, int Nq, int Nk, void* stream) {
-    A3R_CHECK_ARG(q && k && v && o, "a3r_attention: null pointer");
-    A3R_CHECK_ARG(B > 0 && H > 0 && Nq > 0 && Nk > 0, "a3r_attention: bad shape B=%d H=%d Nq=%d Nk=%d", B, H, Nq, Nk);
-    A3R_CHECK_ARG(ldq >= H * 64 && ldk >= H * 64 && ldv >= H * 64 && ldo >= H * 64, "a3r_attention: row strides < H*64");
-    A3R_CHECK_ARG(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0, "a3r_attention: row strides must be multiples of 4");
-    A3R_CHECK_ARG(((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
-                    reinterpret_cast<uintptr_t>(o)) & 15) == 0, "a3r_attention: pointers must be 16-byte aligned");
-    static PerDeviceOnce attr_once;
-    A3R_HIP(attr_once.ensure([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    ATTN_LDS_BYTES); }));
-    AttnArgs a = {q, k, v, o, ldq, ldk, ldv, ldo, B, H, Nq, Nk};
-    const int nqb = (Nq + AQ - 1) / AQ, groups = B * H;
-    dim3 grid(8 * ((groups + 7) / 8) * nqb);
-    ProfScope prof(PK_ATTENTION, 4.0 * B * H * (double)Nq * Nk * 64, as_stream(stream));
-    hipLaunchKernelGGL(attn_kernel, grid, dim3(256), ATTN_LDS_BYTES, as_stream(stream), a);
-    A3R_LAUNCH_CHECK();
-    return A3R_OK;
+    if (int rc = attention_check_args("a3r_attention", q, k, v, o, ldq, ldk, ldv, ldo, B, H, Nq, Nk, 4)) return rc;
+    const AttnArgs a = {q, k, v, o, ldq, ldk, ldv, ldo, B, H, Nq, Nk};
+    return launch_attention<attn_kernel, ATTN_LDS_BYTES>(PK_ATTENTION, a, stream);
 }

@@ -8,11 +8,10 @@
 // O^T = V^T P^T run on v_mfma_f32_32x32x16_f16, the online softmax is fp32 on the accumulators, and P -- in [0, 1] -- is split into
 // two fp16 planes of 1024 p in registers (22 significant bits down to p = 2^-13, absolute error 2^-35 below that) and used directly
 // as the B operand; the factor 1024 is divided out with the softmax normaliser.  O is written in fh2 form for the output
-// projection.  Structure, staging and LDS layouts as attention_bf3.hip (K tiles by LDS-DMA into a double buffer, V tiles through
-// registers into a transposed, key-permuted image, two 32-key online-softmax blocks per 64-key tile); the two-plane images are
-// 53 KB per workgroup, so THREE workgroups of 4 waves share a CU.
-#include "common.h"
-#include "fh2.h"
+// projection.  The first form has the structure, staging and LDS layouts of attention_bf3.hip (AttnStaged<2>, attention_tile.h: K tiles
+// by LDS-DMA into a double buffer, V tiles through registers into a transposed, key-permuted image, two 32-key online-softmax blocks
+// per 64-key tile); the two-plane images are 53 KB per workgroup.
+#include "attention_tile.h"
 #include "dedup.h"
 #include <cmath>
 #include <atomic>
@@ -20,21 +19,8 @@
 #include <string>
 
 namespace a3r {
-int fh2_passes();      // gemm_fh2.hip: 3 (default) or 1 (a3r_fh2_set_passes)
 
-constexpr int A4T = 256;                    // threads per workgroup (4 waves, 32 queries each)
-constexpr int A4Q = 128;                    // queries per workgroup
-constexpr int A4K = 64;                     // keys per tile
-constexpr int A4_KUNITS = 17;               // K row: 16 units (8 d-groups x 2 planes) + 1 pad unit (an odd stride: conflict-free b128 reads)
-constexpr int A4_KROW = A4_KUNITS * 16;
-constexpr int A4_KSLOTS = A4K * A4_KUNITS;  // 1088 DMA slots per tile
-constexpr int A4KI = (A4_KSLOTS + A4T - 1) / A4T;   // 5 per thread, the last one only on wave 0
-constexpr int A4VI = (A4K * 16) / A4T;      // 4 V units per thread
-constexpr int A4_KS_BYTES = A4K * A4_KROW;  // one K tile (two of them)
-constexpr int A4_VROW = 9 * 16;             // V^T row: 64 keys x 2 B + 1 pad unit
-constexpr int A4_VT_BYTES = 2 * 64 * A4_VROW;   // V^T tile: 2 planes x 64 d
-constexpr int A4_LDS_BYTES = 2 * A4_KS_BYTES + A4_VT_BYTES;   // 53,248 B
-constexpr float A4_PSHIFT = 10.f;     // P is carried as 2^10 p in its two fp16 planes (p <= 1: 1024 p keeps 21+ bits above fp16's subnormal range)
+typedef AttnStaged<2> A4S;
 
 struct Attn4Args {
     const char *q, *k, *v;
@@ -49,78 +35,37 @@ struct Attn4Args {
     const int *q_map, *kv_map;
 };
 
-typedef const __attribute__((address_space(1))) void* a4_gptr;
-typedef __attribute__((address_space(3))) void* a4_lptr;
-typedef uint32_t a4_u32x4 __attribute__((ext_vector_type(4)));
+// what both forms end with: O = oacc out_mul / l (P and l both carry the factor 2^10: it cancels) in fh2 form, and the statistic
+__device__ __forceinline__ void attn_fh2_finish(const Attn4Args& a, const f32x16 (&oacc)[2], float l_run, int b, int h, int q_row, int half) {
+    float amax = 0.f;
+    char* op = a.o + ((size_t)b * a.Nq + q_row) * a.po;
+    attn_normalise_store(oacc, l_run, a.out_mul, q_row < a.Nq, h, half, [&](int col, f32x4 v) {
+        amax = fh2_amax4(amax, v);
+        fh2_store4(op, col, v);
+    });
+    __shared__ unsigned s_amax[ATTN_T / 64];
+    fh2_publish_block(a.out_absmax, amax, s_amax);
+}
 
-__global__ __launch_bounds__(A4T, 2) void attn_fh2_kernel(Attn4Args a) {
+__global__ __launch_bounds__(ATTN_T, 2) void attn_fh2_kernel(Attn4Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* Ks = smem;                                // [2][64 rows][17 units]
-    char* Vt = smem + 2 * A4_KS_BYTES;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int qi = lane & 31, half = lane >> 5;
-    // XCD-aware mapping: all query blocks of one (batch, head) land on ONE XCD
-    const int nqb = (a.Nq + A4Q - 1) / A4Q;
-    const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
-    const int group = (seq / nqb) * 8 + xcd, qb = seq - (seq / nqb) * nqb;
-    if (group >= a.B * a.H) return;                 // uniform per workgroup
-    const int h = group % a.H, b = group / a.H;
-    const int q_row = qb * A4Q + wave * 32 + qi;
-    const int q_ld = q_row < a.Nq ? q_row : a.Nq - 1;
+    int b, h, q_row, q_ld;
+    if (!attn_place(a.Nq, a.B, a.H, wave, qi, b, h, q_row, q_ld)) return;
 
     // Q operand (B of S^T = K Q^T): lane (query, half) holds, per 16-deep d-step s and plane p, unit (2 s + half) 2 + p of its head
     f16x8 qf[4][2];
     {
-        const char* qp = a.q + ((size_t)b * a.Nq + q_ld) * a.pq + h * 256;
+        const char* qp = a.q + ((size_t)b * a.Nq + q_ld) * a.pq + h * A4S::HEAD_BYTES;
 #pragma unroll
         for (int s = 0; s < 4; s++)
 #pragma unroll
             for (int p = 0; p < 2; p++) qf[s][p] = *reinterpret_cast<const f16x8*>(qp + ((2 * s + half) * 2 + p) * 16);
     }
-
-    // ---- staging
-    // K: LDS-DMA of 64 x 17 = 1088 slots (4 per thread + one more on wave 0); slot u = (row u / 17, unit u % 17), the pad unit
-    //    re-reads unit 0.  V: 1024 units through registers, 4 per thread; unit u -> (key = u & 63 = tid & 63,
-    //    gp = u >> 6 = 2 d-group + plane): a wave walks the keys of one (d-group, plane).
-    const char* kbase = a.k + (size_t)b * a.Nk * a.pk + h * 256;
-    const char* vbase = a.v + (size_t)b * a.Nk * a.pv + h * 256;
-    auto issue_k = [&](int k0, int buf) {
-        char* base = Ks + buf * A4_KS_BYTES + wave * 1024;
-#pragma unroll
-        for (int i = 0; i < A4KI; i++) {
-            if (i == A4KI - 1 && wave != 0) break;                // slots 1024..1087: one wave
-            const int u = min(tid + A4T * i, A4_KSLOTS - 1);
-            const int row = (u * 3856) >> 16;                     // u / 17 for u < 1088
-            const int cu = u - row * 17;
-            const int kk = min(k0 + row, a.Nk - 1);               // keys past Nk: finite copies, masked to -inf below
-            __builtin_amdgcn_global_load_lds((a4_gptr)(kbase + (size_t)kk * a.pk + (cu == 16 ? 0 : cu) * 16),
-                                             (a4_lptr)(base + A4T * 16 * i), 16, 0, 0);
-        }
-    };
-    // V^T position of this thread's key: pos = 32 kt + 16 s2 + 8 hh + j with t = key & 15: hh = (t >> 2) & 1,
-    // j = (t & 3) + 4 (t >> 3)   (the order the S^T accumulator holds its keys)
-    const int vkey = tid & 63, vt = vkey & 15;
-    const int vpos2 = ((vkey & 48) + ((vt >> 2) & 1) * 8 + (vt & 3) + 4 * (vt >> 3)) * 2;
-    a4_u32x4 rv[A4VI];
-    auto load_v = [&](int k0) {
-        const int vk = min(k0 + vkey, a.Nk - 1);
-        const char* src = vbase + (size_t)vk * a.pv + wave * 16;
-#pragma unroll
-        for (int i = 0; i < A4VI; i++) rv[i] = *reinterpret_cast<const a4_u32x4*>(src + 4 * 16 * i);      // gp = wave + 4 i
-    };
-    auto store_v = [&]() {
-#pragma unroll
-        for (int i = 0; i < A4VI; i++) {
-            const int gp = wave + 4 * i, g = gp >> 1, p = gp & 1;                                        // wave-uniform
-            char* dst = Vt + (p * 64 + 8 * g) * A4_VROW + vpos2;
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const uint32_t w = rv[i][j >> 1];
-                *reinterpret_cast<uint16_t*>(dst + j * A4_VROW) = (j & 1) ? (uint16_t)(w >> 16) : (uint16_t)(w & 0xffffu);
-            }
-        }
-    };
+    A4S stage(smem, a.k + (size_t)b * a.Nk * a.pk + h * A4S::HEAD_BYTES, a.v + (size_t)b * a.Nk * a.pv + h * A4S::HEAD_BYTES, a.pk, a.pv,
+              a.Nk, tid, wave);
 
     f32x16 oacc[2];
 #pragma unroll
@@ -130,21 +75,20 @@ __global__ __launch_bounds__(A4T, 2) void attn_fh2_kernel(Attn4Args a) {
     float m_run = -INFINITY, l_run = 0.f;
     const float SCALE_LOG2E = a.scale_log2e;                    // hd^-0.5 (and the operands' power-of-two scales) folded into the exp2 argument
 
-    const int kfrag = qi * A4_KROW + half * 32;       // this lane's K operand: row qi (+32 kb), units (2 st + half) 2 + p
-    const int vfrag = qi * A4_VROW + half * 16;       // this lane's V^T operand: row d = qi (+32 db), unit 4 kb + 2 s2 + half
-    const int ntiles = (a.Nk + A4K - 1) / A4K;
-    issue_k(0, 0);
-    load_v(0);
-    store_v();
+    const int kfrag = A4S::kfrag(qi, half), vfrag = A4S::vfrag(qi, half);
+    const int ntiles = (a.Nk + ATTN_K - 1) / ATTN_K;
+    stage.issue_k(0, 0);
+    stage.load_v(0);
+    stage.store_v();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     for (int t = 0; t < ntiles; t++) {
-        const int k0 = t * A4K;
+        const int k0 = t * ATTN_K;
         if (t + 1 < ntiles) {
-            issue_k(k0 + A4K, (t + 1) & 1);        // that buffer was last read in iteration t-1: every wave has passed a barrier since
-            load_v(k0 + A4K);
+            stage.issue_k(k0 + ATTN_K, (t + 1) & 1);        // that buffer was last read in iteration t-1: every wave has passed a barrier since
+            stage.load_v(k0 + ATTN_K);
         }
-        const char* Kt = Ks + (t & 1) * A4_KS_BYTES;
+        const char* Kt = stage.Ks + (t & 1) * A4S::KS_BYTES;
         // two 32-key blocks, each a full online-softmax step (keeps one score tile live at a time)
 #pragma unroll
         for (int kb = 0; kb < 2; kb++) {
@@ -157,89 +101,37 @@ __global__ __launch_bounds__(A4T, 2) void attn_fh2_kernel(Attn4Args a) {
                 f16x8 kf[2];
 #pragma unroll
                 for (int p = 0; p < 2; p++)
-                    kf[p] = *reinterpret_cast<const f16x8*>(Kt + kfrag + kb * 32 * A4_KROW + st * 64 + p * 16);
-                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[1], qf[st][0], s, 0, 0, 0);
-                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[0], qf[st][1], s, 0, 0, 0);
-                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[0], qf[st][0], s, 0, 0, 0);
+                    kf[p] = *reinterpret_cast<const f16x8*>(Kt + kfrag + kb * 32 * A4S::KROW + st * 64 + p * 16);
+                fh2_mma32<3>(s, kf, qf[st]);
             }
-            // ---- online softmax (keys of this lane: k0 + 32 kb + (e&3) + 8*(e>>2) + 4*half)
-            if (k0 + kb * 32 + 32 > a.Nk) {
-#pragma unroll
-                for (int e = 0; e < 16; e++) {
-                    const int key = k0 + kb * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
-                    if (key >= a.Nk) s[e] = -INFINITY;
-                }
-            }
-            float mx = s[0];
-#pragma unroll
-            for (int e = 1; e < 16; e++) mx = fmaxf(mx, s[e]);
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            const float m_new = fmaxf(m_run, mx);        // finite: block kb = 0 of every tile has a valid key, and m_run carries it on
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * SCALE_LOG2E);
-            m_run = m_new;
-            // p 2^10 = exp2(s c - m c + 10) by ONE fma per element: the power of two that the fp16 planes of P need (A4_PSCALE) rides
-            // in the exponent, and l accumulates the scaled values (an exact scaling: O / l is unchanged)
-            const float off = __fmaf_rn(-m_new, SCALE_LOG2E, A4_PSHIFT);
-            float lsum = 0.f;
-#pragma unroll
-            for (int e = 0; e < 16; e++) {
-                const float p = __builtin_amdgcn_exp2f(__fmaf_rn(s[e], SCALE_LOG2E, off));
-                s[e] = p;
-                lsum += p;
-            }
-            l_run = l_run * alpha + lsum;
-            if (__builtin_amdgcn_ballot_w64(alpha != 1.f)) {          // the running max moved for some query of this wave (rare after the first tiles)
-#pragma unroll
-                for (int i = 0; i < 2; i++)
-#pragma unroll
-                    for (int e = 0; e < 16; e++) oacc[i][e] *= alpha;
-            }
+            attn_softmax32<ATTN_EXP_FMA>(s, k0 + kb * 32, half, a.Nk, SCALE_LOG2E, m_run, l_run, oacc);
             // ---- O^T += V^T P^T: split 1024 P into two fp16 planes (k-step s2 = accumulator elements 8 s2 .. 8 s2 + 7)
 #pragma unroll
             for (int s2 = 0; s2 < 2; s2++) {
-                a4_u32x4 pf[2];
+                u32x4 pf[2];
 #pragma unroll
                 for (int mm = 0; mm < 4; mm++) {
                     uint32_t p0, p1;
                     fh2_split2(s[8 * s2 + 2 * mm], s[8 * s2 + 2 * mm + 1], p0, p1);
                     pf[0][mm] = p0; pf[1][mm] = p1;
                 }
-                const f16x8 b0 = __builtin_bit_cast(f16x8, pf[0]), b1 = __builtin_bit_cast(f16x8, pf[1]);
+                const f16x8 pb[2] = {__builtin_bit_cast(f16x8, pf[0]), __builtin_bit_cast(f16x8, pf[1])};
 #pragma unroll
                 for (int db = 0; db < 2; db++) {
                     f16x8 vf[2];
 #pragma unroll
                     for (int p = 0; p < 2; p++)
-                        vf[p] = *reinterpret_cast<const f16x8*>(Vt + vfrag + (p * 64 + db * 32) * A4_VROW + (kb * 4 + s2 * 2) * 16);
-                    oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[1], b0, oacc[db], 0, 0, 0);
-                    oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[0], b1, oacc[db], 0, 0, 0);
-                    oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[0], b0, oacc[db], 0, 0, 0);
+                        vf[p] = *reinterpret_cast<const f16x8*>(stage.Vt + vfrag + (p * 64 + db * 32) * A4S::VROW + (kb * 4 + s2 * 2) * 16);
+                    fh2_mma32<3>(oacc[db], vf, pb);
                 }
             }
         }
         __syncthreads();                       // every wave is done with this tile's V^T image
-        if (t + 1 < ntiles) store_v();
+        if (t + 1 < ntiles) stage.store_v();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's K DMAs for tile t+1 have landed
         __syncthreads();
     }
-    const float l_tot = l_run + __shfl_xor(l_run, 32);
-    const float inv_l = a.out_mul / l_tot;                    // P and l both carry the factor 2^10: it cancels
-    float amax = 0.f;
-    if (q_row < a.Nq) {
-        // lane (query, half) holds d = 32 db + 8 g + 4 half + (0..3): half of each plane's unit
-        char* op = a.o + ((size_t)b * a.Nq + q_row) * a.po;
-#pragma unroll
-        for (int db = 0; db < 2; db++)
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                const f32x4 v = {oacc[db][4 * g] * inv_l, oacc[db][4 * g + 1] * inv_l, oacc[db][4 * g + 2] * inv_l,
-                                 oacc[db][4 * g + 3] * inv_l};
-                amax = fh2_amax4(amax, v);
-                fh2_store4(op, h * 64 + db * 32 + 8 * g + 4 * half, v);
-            }
-    }
-    __shared__ unsigned s_amax[A4T / 64];
-    fh2_publish_block(a.out_absmax, amax, s_amax);
+    attn_fh2_finish(a, oacc, l_run, b, h, q_row, half);
 }
 
 
@@ -254,18 +146,9 @@ __global__ __launch_bounds__(A4T, 2) void attn_fh2_kernel(Attn4Args a) {
 // c ^ swz(row), swz(row) = ((row & 3) << 2) | ((row >> 2) & 3): conflict-free for the row reads of the 32x32x16 A operand (S^T = K Q^T)
 // and for the transposed reads (cdna_hip_programming.md T10, image (b)).  K double-buffered, V single-buffered (its DMA for tile t + 1
 // is issued when every wave has finished tile t and has the first block's QK^T and softmax to land): 48 KB, three workgroups per CU.
-#ifndef A3R_ATTN_SB
-#define A3R_ATTN_SB 1
-#endif
-#if A3R_ATTN_SB == 1
 #define B4_PIN() __builtin_amdgcn_sched_barrier(0)
-#elif A3R_ATTN_SB == 2
-#define B4_PIN() __builtin_amdgcn_sched_barrier(0x6)        // VALU and SALU may cross, MFMA and DS may not
-#else
-#define B4_PIN()
-#endif
 constexpr int B4_ROW = 256;
-constexpr int B4_TILE = A4K * B4_ROW;          // 16 KB
+constexpr int B4_TILE = ATTN_K * B4_ROW;       // 16 KB
 constexpr int B4_LDS_BYTES = 3 * B4_TILE;      // K[2] + V
 typedef short b4_s16x4 __attribute__((ext_vector_type(4)));
 typedef short b4_s16x8 __attribute__((ext_vector_type(8)));
@@ -277,7 +160,7 @@ __device__ __forceinline__ b4_s16x4 b4_tr_read(const char* p) {
 
 // PASSES 1 (a3r_fh2_set_passes(1)): first planes only -- q0 k0 and v0 p0 with p rounded to one fp16 -- the 16-bit operand mode.
 template <int PASSES>
-__global__ __launch_bounds__(A4T, 3) void attn_fh2_v2_kernel(Attn4Args a) {
+__global__ __launch_bounds__(ATTN_T, 3) void attn_fh2_v2_kernel(Attn4Args a) {
     constexpr int NPL = PASSES == 1 ? 1 : 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Ks = smem;                                // [2][64 keys][256 B]
@@ -285,13 +168,8 @@ __global__ __launch_bounds__(A4T, 3) void attn_fh2_v2_kernel(Attn4Args a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int qi = lane & 31, half = lane >> 5;
-    const int nqb = (a.Nq + A4Q - 1) / A4Q;
-    const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
-    const int group = (seq / nqb) * 8 + xcd, qb = seq - (seq / nqb) * nqb;
-    if (group >= a.B * a.H) return;                 // uniform per workgroup
-    const int h = group % a.H, b = group / a.H;
-    const int q_row = qb * A4Q + wave * 32 + qi;
-    const int q_ld = q_row < a.Nq ? q_row : a.Nq - 1;
+    int b, h, q_row, q_ld;
+    if (!attn_place(a.Nq, a.B, a.H, wave, qi, b, h, q_row, q_ld)) return;
 
     const int bq = a.q_map ? a.q_map[b] : b, bkv = a.kv_map ? a.kv_map[b] : b;      // uniform
     f16x8 qf[4][NPL];
@@ -313,7 +191,7 @@ __global__ __launch_bounds__(A4T, 3) void attn_fh2_v2_kernel(Attn4Args a) {
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const int kk = min(k0 + drow + 16 * i, a.Nk - 1);          // keys past Nk: finite copies (masked to -inf / multiplied by p = 0)
-            __builtin_amdgcn_global_load_lds((a4_gptr)(base + (size_t)kk * pitch), (a4_lptr)(dst + 4096 * i), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((attn_gptr)(base + (size_t)kk * pitch), (attn_lptr)(dst + 4096 * i), 16, 0, 0);
         }
     };
     // ---- fragment addresses (bytes inside a tile)
@@ -344,15 +222,15 @@ __global__ __launch_bounds__(A4T, 3) void attn_fh2_v2_kernel(Attn4Args a) {
         for (int e = 0; e < 16; e++) oacc[i][e] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;
     const float SCALE_LOG2E = a.scale_log2e;
-    const int ntiles = (a.Nk + A4K - 1) / A4K;
+    const int ntiles = (a.Nk + ATTN_K - 1) / ATTN_K;
     issue(kbase, a.pk, 0, Ks);
     issue(vbase, a.pv, 0, Vs);
     asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                   // Q and K tile 0 have landed (V tile 0 may be in flight)
     __syncthreads();
     for (int t = 0; t < ntiles; t++) {
-        const int k0 = t * A4K;
+        const int k0 = t * ATTN_K;
         const bool more = t + 1 < ntiles;                              // uniform
-        if (more) issue(kbase, a.pk, k0 + A4K, Ks + ((t + 1) & 1) * B4_TILE);      // that buffer was last read in tile t - 1
+        if (more) issue(kbase, a.pk, k0 + ATTN_K, Ks + ((t + 1) & 1) * B4_TILE);      // that buffer was last read in tile t - 1
         const char* Kt = Ks + (t & 1) * B4_TILE;
 #pragma unroll
         for (int kb = 0; kb < 2; kb++) {
@@ -370,43 +248,10 @@ __global__ __launch_bounds__(A4T, 3) void attn_fh2_v2_kernel(Attn4Args a) {
                     for (int p = 0; p < NPL; p++) kf[(st + 1) & 1][p] = *reinterpret_cast<const f16x8*>(Kt + kb * 32 * B4_ROW + koff[st + 1][p]);
                 }
                 B4_PIN();
-                if constexpr (PASSES == 3) {
-                    s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[st & 1][NPL - 1], qf[st][0], s, 0, 0, 0);
-                    s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[st & 1][0], qf[st][NPL - 1], s, 0, 0, 0);
-                }
-                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[st & 1][0], qf[st][0], s, 0, 0, 0);
+                fh2_mma32<PASSES>(s, kf[st & 1], qf[st]);
                 B4_PIN();
             }
-            // ---- online softmax, exactly as the first form
-            if (k0 + kb * 32 + 32 > a.Nk) {
-#pragma unroll
-                for (int e = 0; e < 16; e++) {
-                    const int key = k0 + kb * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
-                    if (key >= a.Nk) s[e] = -INFINITY;
-                }
-            }
-            float mx = s[0];
-#pragma unroll
-            for (int e = 1; e < 16; e++) mx = fmaxf(mx, s[e]);
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            const float m_new = fmaxf(m_run, mx);
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * SCALE_LOG2E);
-            m_run = m_new;
-            const float off = __fmaf_rn(-m_new, SCALE_LOG2E, A4_PSHIFT);
-            float lsum = 0.f;
-#pragma unroll
-            for (int e = 0; e < 16; e++) {
-                const float p = __builtin_amdgcn_exp2f(__fmaf_rn(s[e], SCALE_LOG2E, off));
-                s[e] = p;
-                lsum += p;
-            }
-            l_run = l_run * alpha + lsum;
-            if (__builtin_amdgcn_ballot_w64(alpha != 1.f)) {
-#pragma unroll
-                for (int i = 0; i < 2; i++)
-#pragma unroll
-                    for (int e = 0; e < 16; e++) oacc[i][e] *= alpha;
-            }
+            attn_softmax32<ATTN_EXP_FMA>(s, k0 + kb * 32, half, a.Nk, SCALE_LOG2E, m_run, l_run, oacc);
             if (kb == 0) {
                 // V tile t: this wave's DMAs (issued at the end of tile t - 1, i.e. BEFORE K tile t + 1's) have landed, then everybody's
                 if (more) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -414,64 +259,44 @@ __global__ __launch_bounds__(A4T, 3) void attn_fh2_v2_kernel(Attn4Args a) {
                 __syncthreads();
             }
             // ---- O^T += V^T P^T; the transposed V fragments of the next (s2, db) are requested before the current MFMAs
-            a4_u32x4 pf[2][NPL];
+            f16x8 pb[2][NPL];
 #pragma unroll
-            for (int s2 = 0; s2 < 2; s2++)
+            for (int s2 = 0; s2 < 2; s2++) {
+                u32x4 pf[2];
 #pragma unroll
                 for (int mm = 0; mm < 4; mm++) {
                     uint32_t p0, p1;
-                    fh2_split2(s[8 * s2 + 2 * mm], s[8 * s2 + 2 * mm + 1], p0, p1);       // (PASSES 1: the residual plane is dead code)
-                    pf[s2][0][mm] = p0;
-                    if constexpr (PASSES == 3) pf[s2][NPL - 1][mm] = p1;
+                    fh2_split2(s[8 * s2 + 2 * mm], s[8 * s2 + 2 * mm + 1], p0, p1);
+                    pf[0][mm] = p0; pf[1][mm] = p1;
                 }
-            auto vread = [&](int step, b4_s16x8 (&vf)[NPL]) {           // step = 2 s2 + db
+#pragma unroll
+                for (int p = 0; p < NPL; p++) pb[s2][p] = __builtin_bit_cast(f16x8, pf[p]);      // (PASSES 1: the residual plane is dead code)
+            }
+            auto vread = [&](int step, f16x8 (&vf)[NPL]) {              // step = 2 s2 + db
                 const int s2 = step >> 1, db = step & 1;
                 const char* base = Vs + (kb * 32 + s2 * 16) * B4_ROW;
 #pragma unroll
                 for (int p = 0; p < NPL; p++) {
                     const b4_s16x4 lo = b4_tr_read(base + voff[p][db][0]), hi = b4_tr_read(base + voff[p][db][1]);
-                    vf[p] = b4_s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                    vf[p] = __builtin_bit_cast(f16x8, b4_s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
                 }
             };
-            b4_s16x8 vf[2][NPL];
+            f16x8 vf[2][NPL];
             vread(0, vf[0]);
 #pragma unroll
             for (int step = 0; step < 4; step++) {
                 if (step < 3) vread(step + 1, vf[(step + 1) & 1]);
                 B4_PIN();
-                const int s2 = step >> 1, db = step & 1;
-                const f16x8 b0 = __builtin_bit_cast(f16x8, pf[s2][0]), b1 = __builtin_bit_cast(f16x8, pf[s2][NPL - 1]);
-                const f16x8 v0 = __builtin_bit_cast(f16x8, vf[step & 1][0]), v1 = __builtin_bit_cast(f16x8, vf[step & 1][NPL - 1]);
-                if constexpr (PASSES == 3) {
-                    oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v1, b0, oacc[db], 0, 0, 0);
-                    oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v0, b1, oacc[db], 0, 0, 0);
-                }
-                oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v0, b0, oacc[db], 0, 0, 0);
+                fh2_mma32<PASSES>(oacc[step & 1], vf[step & 1], pb[step >> 1]);
                 B4_PIN();
             }
         }
         // every wave is done with V tile t and K tile t; K tile t + 1 (issued at the top of this iteration) has landed for everybody
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (more) issue(vbase, a.pv, k0 + A4K, Vs);
+        if (more) issue(vbase, a.pv, k0 + ATTN_K, Vs);
     }
-    const float l_tot = l_run + __shfl_xor(l_run, 32);
-    const float inv_l = a.out_mul / l_tot;
-    float amax = 0.f;
-    if (q_row < a.Nq) {
-        char* op = a.o + ((size_t)b * a.Nq + q_row) * a.po;
-#pragma unroll
-        for (int db = 0; db < 2; db++)
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                const f32x4 v = {oacc[db][4 * g] * inv_l, oacc[db][4 * g + 1] * inv_l, oacc[db][4 * g + 2] * inv_l,
-                                 oacc[db][4 * g + 3] * inv_l};
-                amax = fh2_amax4(amax, v);
-                fh2_store4(op, h * 64 + db * 32 + 8 * g + 4 * half, v);
-            }
-    }
-    __shared__ unsigned s_amax[A4T / 64];
-    fh2_publish_block(a.out_absmax, amax, s_amax);
+    attn_fh2_finish(a, oacc, l_run, b, h, q_row, half);
 }
 
 // which kernel form a3r_attention_fh2 launches: 2 (default) or 1 (A3R_ATTN=v1 / a3r_attention_fh2_set_form)
@@ -488,7 +313,22 @@ extern "C" int a3r_attention_fh2_set_form(int form) {
 bool a3r::attention_fh2_takes_maps() { return g_attn_form.load(std::memory_order_relaxed) == 2 || fh2_passes() != 3; }
 
 static int attention_fh2_launch(const void* q2, int ldq, const void* k2, int ldk, const void* v2, int ldv, void* o2, int ldo, int B, int H,
-                                int Nq, int Nk, const a3r_fh2_attn_range* range, const int32_t* q_map, const int32_t* kv_map, void* stream);
+                                int Nq, int Nk, const a3r_fh2_attn_range* range, const int32_t* q_map, const int32_t* kv_map, void* stream) {
+    if (int rc = attention_check_args("a3r_attention_fh2", q2, k2, v2, o2, ldq, ldk, ldv, ldo, B, H, Nq, Nk, 8)) return rc;
+    a3r_fh2_attn_range r = range ? *range : a3r_fh2_attn_range{};
+    float* rs[4] = {&r.q_scale, &r.k_scale, &r.v_scale, &r.out_scale};
+    for (float* p : rs) {
+        if (*p == 0.f) *p = 1.f;
+        A3R_CHECK_ARG(*p > 0.f && std::isfinite(*p), "a3r_attention_fh2: scales must be positive and finite");
+    }
+    const Attn4Args a = {static_cast<const char*>(q2), static_cast<const char*>(k2), static_cast<const char*>(v2), static_cast<char*>(o2),
+                         (size_t)ldq * 4, (size_t)ldk * 4, (size_t)ldv * 4, (size_t)ldo * 4, B, H, Nq, Nk,
+                         0.125f * 1.4426950408889634f / (r.q_scale * r.k_scale), r.out_scale / r.v_scale, r.out_absmax, q_map, kv_map};
+    if (g_attn_form.load(std::memory_order_relaxed) == 1 && fh2_passes() == 3)      // A/B switch: the register-staged V form
+        return launch_attention<attn_fh2_kernel, A4S::LDS_BYTES>(PK_ATTENTION_FH2, a, stream);
+    if (fh2_passes() == 1) return launch_attention<attn_fh2_v2_kernel<1>, B4_LDS_BYTES>(PK_ATTENTION_FH2, a, stream);
+    return launch_attention<attn_fh2_v2_kernel<3>, B4_LDS_BYTES>(PK_ATTENTION_FH2, a, stream);
+}
 
 extern "C" int a3r_attention_fh2(const void* q2, int ldq, const void* k2, int ldk, const void* v2, int ldv, void* o2, int ldo,
                                  int B, int H, int Nq, int Nk, const a3r_fh2_attn_range* range, void* stream) {
@@ -500,39 +340,4 @@ extern "C" int a3r_attention_fh2_mapped(const void* q2, int ldq, const void* k2,
                                         const int32_t* kv_map, void* stream) {
     A3R_CHECK_ARG((!q_map && !kv_map) || attention_fh2_takes_maps(), "a3r_attention_fh2_mapped: kernel form 1 takes no image maps");
     return attention_fh2_launch(q2, ldq, k2, ldk, v2, ldv, o2, ldo, B, H, Nq, Nk, range, q_map, kv_map, stream);
-}
-
-static int attention_fh2_launch(const void* q2, int ldq, const void* k2, int ldk, const void* v2, int ldv, void* o2, int ldo, int B, int H,
-                                int Nq, int Nk, const a3r_fh2_attn_range* range, const int32_t* q_map, const int32_t* kv_map, void* stream) {
-    A3R_CHECK_ARG(q2 && k2 && v2 && o2, "a3r_attention_fh2: null pointer");
-    a3r_fh2_attn_range r = range ? *range : a3r_fh2_attn_range{};
-    float* rs[4] = {&r.q_scale, &r.k_scale, &r.v_scale, &r.out_scale};
-    for (float* p : rs) {
-        if (*p == 0.f) *p = 1.f;
-        A3R_CHECK_ARG(*p > 0.f && std::isfinite(*p), "a3r_attention_fh2: scales must be positive and finite");
-    }
-    A3R_CHECK_ARG(B > 0 && H > 0 && Nq > 0 && Nk > 0, "a3r_attention_fh2: bad shape B=%d H=%d Nq=%d Nk=%d", B, H, Nq, Nk);
-    A3R_CHECK_ARG(ldq >= H * 64 && ldk >= H * 64 && ldv >= H * 64 && ldo >= H * 64, "a3r_attention_fh2: row strides < H*64");
-    A3R_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0, "a3r_attention_fh2: row strides must be multiples of 8");
-    A3R_CHECK_ARG(((reinterpret_cast<uintptr_t>(q2) | reinterpret_cast<uintptr_t>(k2) | reinterpret_cast<uintptr_t>(v2) |
-                    reinterpret_cast<uintptr_t>(o2)) & 15) == 0, "a3r_attention_fh2: pointers must be 16-byte aligned");
-    const bool v1 = g_attn_form.load(std::memory_order_relaxed) == 1 && fh2_passes() == 3;      // A/B switch: the register-staged V form
-    static PerDeviceOnce attr_once;
-    A3R_HIP(attr_once.ensure([&] {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fh2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, A4_LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fh2_v2_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, B4_LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fh2_v2_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, B4_LDS_BYTES);
-        return e;
-    }));
-    Attn4Args a = {static_cast<const char*>(q2), static_cast<const char*>(k2), static_cast<const char*>(v2), static_cast<char*>(o2),
-                   (size_t)ldq * 4, (size_t)ldk * 4, (size_t)ldv * 4, (size_t)ldo * 4, B, H, Nq, Nk,
-                   0.125f * 1.4426950408889634f / (r.q_scale * r.k_scale), r.out_scale / r.v_scale, r.out_absmax, q_map, kv_map};
-    const int nqb = (Nq + A4Q - 1) / A4Q, groups = B * H;
-    dim3 grid(8 * ((groups + 7) / 8) * nqb);
-    ProfScope prof(PK_ATTENTION_FH2, 4.0 * B * H * (double)Nq * Nk * 64, as_stream(stream));
-    if (v1) hipLaunchKernelGGL(attn_fh2_kernel, grid, dim3(A4T), A4_LDS_BYTES, as_stream(stream), a);
-    else if (fh2_passes() == 1) hipLaunchKernelGGL(attn_fh2_v2_kernel<1>, grid, dim3(A4T), B4_LDS_BYTES, as_stream(stream), a);
-    else hipLaunchKernelGGL(attn_fh2_v2_kernel<3>, grid, dim3(A4T), B4_LDS_BYTES, as_stream(stream), a);
-    A3R_LAUNCH_CHECK();
-    return A3R_OK;
 }

@@ -26,6 +26,8 @@ typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
 typedef float fh2_f32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t fh2_u32x4 __attribute__((ext_vector_type(4)));
 
+int fh2_passes();         // 3 | 1: the process-wide pass count of the fh2 kernels (gemm_fh2.hip, a3r_fh2_set_passes)
+
 __host__ __device__ inline size_t fh2_row_bytes(int K) { return (size_t)K * 4; }
 
 __device__ __forceinline__ uint32_t pk_f16(float a, float b) {       // v_cvt_pkrtz is round-to-zero: use the rn conversions

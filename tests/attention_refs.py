@@ -15,7 +15,7 @@ F32, F16 = np.float32, np.float16
 U22, U25, U12 = 2.0 ** -22, 2.0 ** -25, 2.0 ** -12
 HD = 64
 LOG2E_F32 = F32(1.4426950408889634)
-PSHIFT = F32(10.0)                       # A4_PSHIFT of csrc/attention_fh2.hip: P is carried as 2^10 p
+PSHIFT = F32(10.0)                       # ATTN_PSHIFT of csrc/attention_tile.h: P is carried as 2^10 p
 
 FAMILIES = ("plain", "sharp", "ties", "voff", "ramp", "peak0", "peakmid", "peaklast", "high", "low")
 
