@@ -99,6 +99,11 @@ class RenderCam(C.Structure):
     _fields_ = [("w2c", C.c_double * 12), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
 
 
+class TsdfCam(C.Structure):
+    _fields_ = [("w2c", C.c_double * 12), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("h", C.c_int), ("w", C.c_int)]
+
+
 DEPTH_ALIGN_MODES ={"lad": 0, "lstsq": 1, "scale": 2, "median": 3}      # A3R_DEPTH_ALIGN_* of include/a3r.h
 DEPTH_INFO_DOUBLES, DEPTH_METRIC_DOUBLES = 16, 8
 VOXEL_BEST, VOXEL_MEAN = 0, 1                                           # A3R_VOXEL_* of include/a3r.h
@@ -299,6 +304,15 @@ SIGNATURES = {
                                   C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), c_void]),
     "a3r_voxel_export": (C.c_int, [c_void, c_void, c_void, C.c_longlong, C.c_double, C.c_int, C.c_int, C.c_longlong, c_void, C.c_size_t,
                                    C.c_longlong, c_void, c_void, c_void, c_void, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), c_void]),
+    "a3r_tsdf_integrate": (C.c_int, [c_void, c_void, c_void, c_void, c_void, C.c_int, C.c_longlong, c_void, C.c_double, C.c_int, C.c_int,
+                                     C.c_int, C.c_double, C.c_double, C.c_double, c_void, c_void, c_void, c_void, c_void]),
+    "a3r_tsdf_set_form": (C.c_int, [C.c_int]),
+    "a3r_tsdf_mesh_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "a3r_tsdf_mesh_count": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_double, c_void, C.c_size_t, C.POINTER(C.c_longlong),
+                                      C.POINTER(C.c_longlong), c_void]),
+    "a3r_tsdf_mesh_export": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_double, C.c_double, c_void, C.c_size_t,
+                                       C.c_longlong, C.c_longlong, c_void, c_void, c_void, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                       c_void]),
 }
 
 _lib = None

@@ -452,6 +452,110 @@ class PointCloudOptimizer:
         write_ply_mesh(path, host('xyz'), host('faces'), host('rgb'), host('face_rgb'))
         return m
 
+    def _tsdf_inputs(self, min_conf_thr, mask_dynamic, weight, who):
+        """What get_tsdf hands to ops.tsdf_integrate: depth and weight [N,P] float32, rgb [N,P,3] uint8 or None, the camera table,
+        and the kept cloud (xyz, index) the weights were cut from."""
+        from ... import ops
+        from ...tool.render import world_to_camera
+        if weight not in ('conf', 'uniform'):
+            raise ValueError(f"{who}: weight = {weight!r} is neither 'conf' nor 'uniform'")
+        e = self._need_engine()
+        conf, thr, dyn, rgb = self._scene_out_inputs(min_conf_thr, mask_dynamic, who)
+        pc = e.export_points(conf, thr, dyn=dyn, rgb=None, with_index=True)
+        idx = pc['index'].long()
+        wt = torch.zeros(conf.numel(), dtype=torch.float32, device=conf.device)
+        wt[idx] = conf.reshape(-1)[idx] if weight == 'conf' else 1.0
+        depth = self.get_depthmaps(raw=True).detach().float().contiguous()
+        poses = self.get_im_poses().detach().cpu().numpy().astype(np.float64)
+        K = np.zeros((self.n_imgs, 3, 3))
+        K[:, 0, 0] = K[:, 1, 1] = self.get_focals().detach().cpu().numpy().astype(np.float64).reshape(-1)
+        K[:, :2, 2] = self.get_principal_points().detach().cpu().numpy().astype(np.float64)
+        K[:, 2, 2] = 1
+        cams = ops.tsdf_cameras(world_to_camera(poses), K, [tuple(s) for s in self.imshapes])
+        if rgb is not None:
+            rgb = rgb.to(conf.device).contiguous()
+        return depth, wt.view(conf.shape), rgb, cams, pc
+
+    def get_tsdf(self, voxel_size, trunc=None, bounds=None, min_conf_thr=None, mask_dynamic=False, weight='conf', max_depth=None,
+                 max_voxels=2 ** 28):
+        """The aligned depth maps fused into one dense grid of truncated signed distances (ops.tsdf_integrate, csrc/tsdf.hip;
+        include/a3r.h has the definition): every voxel of edge voxel_size takes, over the frames that see it, the weighted mean of
+        min(1, (depth - its own camera depth) / trunc), frames that see a surface more than trunc in front of it left out.  trunc
+        defaults to 3 voxel_size.  A pixel's weight is its confidence (weight='conf') or 1 ('uniform') where get_pointcloud() keeps
+        the pixel with the same min_conf_thr and mask_dynamic, 0 elsewhere; depths beyond max_depth are not integrated.  The depths
+        are get_depthmaps(), the cameras the scene's own in float64, as render_views builds them.  bounds = (origin, dims) fixes the
+        grid; None takes the box of the kept points within max_depth, padded by trunc: origin = floor((min - trunc) / v) v and
+        dims = floor((max + trunc) / v) + 1 - floor((min - trunc) / v), on the host in float64.  More than max_voxels voxels is a
+        ValueError.  Returns tsdf [nz,ny,nx] float32 (1 where nothing was seen), weight [nz,ny,nx] float32, rgb [nz,ny,nx,3] uint8
+        (None for a scene without frames), origin (three floats), voxel, dims = (nx, ny, nz)."""
+        from ... import ops
+        who = 'get_tsdf'
+        v = float(voxel_size)
+        if not (np.isfinite(v) and v > 0):
+            raise ValueError(f'{who}: voxel_size = {voxel_size} must be finite and positive')
+        trunc = 3 * v if trunc is None else float(trunc)
+        if not (np.isfinite(trunc) and trunc > 0):
+            raise ValueError(f'{who}: trunc = {trunc} must be finite and positive')
+        far = float('inf') if max_depth is None else float(max_depth)
+        if not far > 0:
+            raise ValueError(f'{who}: max_depth = {max_depth} must be positive')
+        depth, wt, rgb, cams, pc = self._tsdf_inputs(min_conf_thr, mask_dynamic, weight, who)
+        if bounds is None:
+            xyz = pc['xyz']
+            if far < float('inf'):
+                xyz = xyz[depth.reshape(-1)[pc['index'].long()] <= far]
+            if xyz.shape[0] == 0:
+                raise ValueError(f'{who}: no pixel is kept within max_depth: there is nothing to put a box around (bounds= sets one)')
+            lo_pt = xyz.min(0).values.cpu().numpy().astype(np.float64)
+            hi_pt = xyz.max(0).values.cpu().numpy().astype(np.float64)
+            lo = np.floor((lo_pt - trunc) / v)
+            hi = np.floor((hi_pt + trunc) / v) + 1
+            origin, dims = lo * v, hi - lo
+        else:
+            origin, dims = bounds
+            origin = np.asarray(origin, dtype=np.float64).reshape(-1)
+        if len(dims) != 3 or not all(np.isfinite(n) and n >= 1 for n in dims):
+            raise ValueError(f'{who}: dims = {tuple(dims)!r} is three positive counts')
+        dims = tuple(int(n) for n in dims)
+        if dims[0] * dims[1] * dims[2] > max_voxels:
+            raise ValueError(f'{who}: dims = {dims} are {dims[0] * dims[1] * dims[2]} voxels, more than max_voxels = {max_voxels}: '
+                             'narrow the box with bounds= or max_depth=, or take a larger voxel')
+        tsdf, wsum, colours = ops.tsdf_integrate(depth, wt, rgb, cams, origin, dims, v, trunc, max_depth=far)
+        return tsdf, wsum, colours, tuple(float(o) for o in origin), v, dims
+
+    def get_fused_mesh(self, voxel_size, trunc=None, bounds=None, min_conf_thr=None, mask_dynamic=False, weight='conf', max_depth=None,
+                       max_voxels=2 ** 28, min_weight=None):
+        """One surface for the whole scene: the zero set of get_tsdf(...) as a triangle mesh by surface nets (ops.tsdf_mesh): dict of
+        device tensors xyz [V,3] float32, rgb [V,3] uint8 (when the scene holds its frames) and faces [F,3] int32.  A voxel counts
+        as observed where its weight is at least min_weight; None = the smallest positive weight the scene assigns to a pixel,
+        i.e. seen at least once."""
+        from ... import ops
+        if min_weight is None:
+            if weight == 'conf':
+                wt = self._tsdf_inputs(min_conf_thr, mask_dynamic, weight, 'get_fused_mesh')[1]
+                positive = wt[wt > 0]
+                min_weight = float(positive.min()) if positive.numel() else 1.0
+            else:
+                min_weight = 1.0
+        tsdf, wsum, colours, origin, v, _ = self.get_tsdf(voxel_size, trunc=trunc, bounds=bounds, min_conf_thr=min_conf_thr,
+                                                          mask_dynamic=mask_dynamic, weight=weight, max_depth=max_depth,
+                                                          max_voxels=max_voxels)
+        xyz, rgb, faces = ops.tsdf_mesh(tsdf, wsum, colours, origin, v, min_weight)
+        out = dict(xyz=xyz)
+        if rgb is not None:
+            out['rgb'] = rgb
+        out['faces'] = faces
+        return out
+
+    def save_fused_mesh(self, path, voxel_size, **kw):
+        """get_fused_mesh(voxel_size, **kw) written as a binary little-endian PLY (tool/pointcloud.py: write_ply_mesh); returns the
+        dict."""
+        from ...tool.pointcloud import write_ply_mesh
+        m = self.get_fused_mesh(voxel_size, **kw)
+        host = lambda k: m[k].cpu().numpy() if k in m else None
+        write_ply_mesh(path, host('xyz'), host('faces'), host('rgb'))
+        return m
+
     def save_pointcloud(self, path, **kw):
         """get_pointcloud(**kw) written as a binary little-endian PLY (tool/pointcloud.py); returns the dict."""
         from ...tool.pointcloud import write_ply

@@ -1053,3 +1053,178 @@ def track_points(xyz, keep, flow_a, flow_b, steps, seeds=None, fb_thr=3.0):
                                    Cn, S, ptr(seeds), M, float(fb_thr), ptr(out["xy"]), ptr(out["xyz"]), ptr(out["pix"]), ptr(out["state"]),
                                    stream_ptr()), "track_points")
     return out                                            # the device copy of the steps is freed stream-ordered after the kernel
+
+
+def _tsdf_scalar(who, name, value):
+    value = float(value)
+    if not (np.isfinite(value) and value > 0):
+        raise ValueError(f"{who}: {name} = {value} must be finite and positive")
+    return value
+
+
+def _tsdf_grid(who, origin, dims, voxel):
+    """The grid's checks shared by tsdf_integrate and tsdf_mesh: (origin float64 [3], (nx, ny, nz), voxel)."""
+    voxel = _tsdf_scalar(who, "voxel", voxel)
+    origin = np.ascontiguousarray(np.asarray(origin, dtype=np.float64).reshape(-1))
+    if origin.shape != (3,) or not np.all(np.isfinite(origin)):
+        raise ValueError(f"{who}: origin is three finite numbers, got {origin!r}")
+    if len(dims) != 3 or any(int(n) != n or n <= 0 for n in dims):
+        raise ValueError(f"{who}: dims = {tuple(dims)!r} is three positive integers (nx, ny, nz)")
+    nx, ny, nz = (int(n) for n in dims)
+    if nx * ny * nz >= 1 << 31:
+        raise ValueError(f"{who}: dims = ({nx}, {ny}, {nz}): nx * ny * nz = {nx * ny * nz} must stay below 2^31")
+    return origin, (nx, ny, nz), voxel
+
+
+def _tsdf_tensor(who, t, name, dtype, shape):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{who}: {name} must be a torch tensor, got {type(t).__name__}")
+    if t.dtype != dtype:
+        raise ValueError(f"{who}: {name} must be {dtype}, got {t.dtype}")
+    if t.dim() != len(shape) or any(want is not None and have != want for have, want in zip(t.shape, shape)):
+        raise ValueError(f"{who}: {name} has shape {tuple(t.shape)}, expected {[w if w is not None else '*' for w in shape]}")
+    if not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be contiguous")
+
+
+def _tsdf_devices(who, first, tensors):
+    for t, name in tensors:
+        if t is not None and (t.device.type != "cuda" or t.device != first.device):
+            raise ValueError(f"{who}: {name} must be on the device (with {tensors[0][1]}), it is on {t.device}")
+
+
+def tsdf_cameras(w2c, K, shapes):
+    """The camera table of tsdf_integrate, [N,17] float64 (a3r_tsdf_cam: [R|t] row-major, fx, fy, cx, cy, then h and w as two int32 in
+    the last column), from w2c [N,3,4] or [N,4,4] and K [N,3,3], both float64 (numpy or torch), and shapes = N pairs (h, w).  A
+    non-zero skew, a non-finite entry and a non-positive shape are ValueErrors."""
+    who = "tsdf_cameras"
+    as_f64 = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    w2c, K = as_f64(w2c), as_f64(K)
+    for a, name in ((w2c, "w2c"), (K, "K")):
+        if a.dtype != np.float64:
+            raise ValueError(f"{who}: {name} must be float64, got {a.dtype}")
+    if w2c.ndim != 3 or w2c.shape[1] not in (3, 4) or w2c.shape[2] != 4:
+        raise ValueError(f"{who}: w2c is [N,3,4] or [N,4,4], got {w2c.shape}")
+    N = w2c.shape[0]
+    if K.shape != (N, 3, 3):
+        raise ValueError(f"{who}: K is [N,3,3] with N = {N}, got {K.shape}")
+    if np.any(K[:, 0, 1] != 0):
+        raise ValueError(f"{who}: K has a non-zero skew K[0,1]; the cameras are fx, fy, cx, cy")
+    shapes = np.asarray(shapes)
+    if shapes.shape != (N, 2) or np.any(shapes != shapes.astype(np.int64)) or np.any(shapes <= 0) or np.any(shapes >= 1 << 31):
+        raise ValueError(f"{who}: shapes is N = {N} pairs (h, w) of positive integers, got {shapes.tolist()!r}")
+    cams = np.zeros((N, 17), np.float64)
+    cams[:, :12] = w2c[:, :3, :].reshape(N, 12)
+    cams[:, 12], cams[:, 13], cams[:, 14], cams[:, 15] = K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]
+    if not np.all(np.isfinite(cams[:, :16])):
+        raise ValueError(f"{who}: w2c and K must be finite")
+    cams[:, 16:].view(np.int32)[:] = shapes.astype(np.int32)
+    return cams
+
+
+def tsdf_camera_shapes(cams):
+    """(h, w) per camera of a tsdf_cameras table, int32 [N,2]."""
+    return np.ascontiguousarray(cams)[:, 16:].view(np.int32).copy()
+
+
+def _tsdf_integrate_args(depth, weight, rgb, cams, origin, dims, voxel, trunc, near, max_depth):
+    """The checks of tsdf_integrate; every refusal is a ValueError raised before the library is touched.  The scalars first, then
+    every tensor's type, dtype, shape and layout, the camera table, the devices last."""
+    who = "tsdf_integrate"
+    origin, dims, voxel = _tsdf_grid(who, origin, dims, voxel)
+    trunc = _tsdf_scalar(who, "trunc", trunc)
+    near = _tsdf_scalar(who, "near", near)
+    max_depth = float(max_depth)
+    if not max_depth > 0:
+        raise ValueError(f"{who}: max_depth = {max_depth} must be positive (inf = no limit)")
+    _tsdf_tensor(who, depth, "depth", torch.float32, (None, None))
+    N, P = depth.shape
+    _tsdf_tensor(who, weight, "weight", torch.float32, (N, P))
+    if rgb is not None:
+        _tsdf_tensor(who, rgb, "rgb", torch.uint8, (N, P, 3))
+    if N * P >= 1 << 31:
+        raise ValueError(f"{who}: N * P = {N} * {P} must stay below 2^31")
+    if not isinstance(cams, np.ndarray) or cams.dtype != np.float64 or cams.shape != (N, 17):
+        raise ValueError(f"{who}: cams is the float64 table [N,17] of tsdf_cameras with N = {N}, got "
+                         f"{getattr(cams, 'shape', type(cams).__name__)}")
+    cams = np.ascontiguousarray(cams)
+    if not np.all(np.isfinite(cams[:, :16])):
+        raise ValueError(f"{who}: cams holds a non-finite entry")
+    for n, (h, w) in enumerate(tsdf_camera_shapes(cams).tolist()):
+        if h <= 0 or w <= 0 or h * w > P:
+            raise ValueError(f"{who}: camera {n}: h * w = {h} * {w} must be positive and at most P = {P}")
+    _tsdf_devices(who, depth, [(depth, "depth"), (weight, "weight"), (rgb, "rgb")])
+    return cams, origin, dims, voxel, trunc, near, max_depth
+
+
+def tsdf_integrate(depth, weight, rgb, cams, origin, dims, voxel, trunc, near=1e-6, max_depth=float("inf"), skip_stats=None):
+    """Depth maps fused into a dense grid of truncated signed distances (a3r_tsdf_integrate, csrc/tsdf.hip; include/a3r.h has the
+    definition: float64, every voxel walks the frames in ascending order with its sums in registers -- bitwise the numpy
+    restatement).  depth, weight [N,P] float32 and rgb [N,P,3] uint8 or None: contiguous device tensors, pixel (row, col) of frame n
+    at n * P + row * w + col; cams: the table of tsdf_cameras(); origin (3 numbers), dims = (nx, ny, nz), voxel, trunc, near,
+    max_depth: the grid and the gates.  skip_stats: None or a device tensor of two int64 the call adds its brick-test counts to.
+    Enqueue-only; returns device tensors tsdf [nz,ny,nx] float32 (1 where nothing was seen), wsum [nz,ny,nx] float32 and
+    rgb [nz,ny,nx,3] uint8 (None without rgb)."""
+    cams, origin, (nx, ny, nz), voxel, trunc, near, max_depth = _tsdf_integrate_args(depth, weight, rgb, cams, origin, dims, voxel, trunc,
+                                                                                     near, max_depth)
+    if skip_stats is not None:
+        _tsdf_tensor("tsdf_integrate", skip_stats, "skip_stats", torch.int64, (2,))
+        _tsdf_devices("tsdf_integrate", depth, [(depth, "depth"), (skip_stats, "skip_stats")])
+    assert C.sizeof(_lib.TsdfCam) == 136 == cams.shape[1] * cams.itemsize
+    lib, dev, (N, P) = _lib.load(), depth.device, depth.shape
+    tsdf = torch.empty((nz, ny, nx), dtype=torch.float32, device=dev)
+    wsum = torch.empty((nz, ny, nx), dtype=torch.float32, device=dev)
+    out_rgb = torch.empty((nz, ny, nx, 3), dtype=torch.uint8, device=dev) if rgb is not None else None
+    cams_dev = torch.from_numpy(cams.reshape(-1).copy()).to(dev) if N else None
+    with torch.cuda.device(dev):
+        check(lib.a3r_tsdf_integrate(ptr(depth), ptr(weight), ptr(rgb), ptr(cams_dev), cams.ctypes.data if N else None, N, P,
+                                     origin.ctypes.data, voxel, nx, ny, nz, trunc, near, max_depth, ptr(tsdf), ptr(wsum), ptr(out_rgb),
+                                     ptr(skip_stats), stream_ptr()), "tsdf_integrate")
+    return tsdf, wsum, out_rgb            # the camera table is freed stream-ordered after the kernel
+
+
+def tsdf_set_form(form):
+    """a3r_tsdf_set_form: bit 0 set = no brick test; returns the previous form.  The outputs do not depend on it."""
+    return int(_lib.load().a3r_tsdf_set_form(int(form)))
+
+
+def _tsdf_mesh_args(tsdf, wsum, rgb, origin, voxel, min_weight):
+    who = "tsdf_mesh"
+    min_weight = _tsdf_scalar(who, "min_weight", min_weight)
+    _tsdf_tensor(who, tsdf, "tsdf", torch.float32, (None, None, None))
+    nz, ny, nx = tsdf.shape
+    origin, dims, voxel = _tsdf_grid(who, origin, (nx, ny, nz), voxel)
+    if nx * ny * nz > (1 << 31) // 6:
+        raise ValueError(f"{who}: dims = ({nx}, {ny}, {nz}): more than 2^31 / 6 voxels (the face count is a 32-bit integer)")
+    _tsdf_tensor(who, wsum, "wsum", torch.float32, (nz, ny, nx))
+    if rgb is not None:
+        _tsdf_tensor(who, rgb, "rgb", torch.uint8, (nz, ny, nx, 3))
+    _tsdf_devices(who, tsdf, [(tsdf, "tsdf"), (wsum, "wsum"), (rgb, "rgb")])
+    return origin, dims, voxel, min_weight
+
+
+def tsdf_mesh(tsdf, wsum, rgb, origin, voxel, min_weight, capacity=None):
+    """The zero surface of a TSDF grid as one triangle mesh by surface nets (a3r_tsdf_mesh_count / _export, csrc/tsdf.hip;
+    include/a3r.h has the definition -- bitwise the numpy restatement).  tsdf, wsum [nz,ny,nx] float32 and rgb [nz,ny,nx,3] uint8 or
+    None as tsdf_integrate returned them; a voxel counts as observed where wsum >= min_weight.  Returns device tensors xyz [V,3]
+    float32, rgb [V,3] uint8 (None without rgb) and faces [F,3] int32.  Two calls into the library, each synchronising once;
+    capacity = (vertices, faces) skips the first and is refused by the second when it is too small."""
+    origin, (nx, ny, nz), voxel, min_weight = _tsdf_mesh_args(tsdf, wsum, rgb, origin, voxel, min_weight)
+    lib, dev = _lib.load(), tsdf.device
+    ws_bytes = int(lib.a3r_tsdf_mesh_workspace_bytes(nx, ny, nz))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    V, F = C.c_longlong(0), C.c_longlong(0)
+    with torch.cuda.device(dev):
+        if capacity is None:
+            check(lib.a3r_tsdf_mesh_count(ptr(tsdf), ptr(wsum), nx, ny, nz, min_weight, ptr(ws), ws_bytes, C.byref(V), C.byref(F),
+                                          stream_ptr()), "tsdf_mesh")
+            capacity = (int(V.value), int(F.value))
+        cap_v, cap_f = int(capacity[0]), int(capacity[1])
+        xyz = torch.empty((cap_v, 3), dtype=torch.float32, device=dev)
+        out_rgb = torch.empty((cap_v, 3), dtype=torch.uint8, device=dev) if rgb is not None else None
+        faces = torch.empty((cap_f, 3), dtype=torch.int32, device=dev)
+        check(lib.a3r_tsdf_mesh_export(ptr(tsdf), ptr(wsum), ptr(rgb), nx, ny, nz, origin.ctypes.data, voxel, min_weight, ptr(ws), ws_bytes,
+                                       cap_v, cap_f, ptr(xyz) if cap_v else None, ptr(out_rgb) if cap_v else None,
+                                       ptr(faces) if cap_f else None, C.byref(V), C.byref(F), stream_ptr()), "tsdf_mesh")
+    V, F = int(V.value), int(F.value)
+    return xyz[:V], (out_rgb[:V] if out_rgb is not None else None), faces[:F]

@@ -8,6 +8,7 @@ The flow of the reference's tool/demo.py and tool/depth_test.py through this pac
         --pointcloud-voxel V: one point per occupied cell of a grid of edge V instead of every pixel (hashed on the device)
     ->  --matches DIR: matches_{i}_{i+1}.npz, the reciprocal 3-D nearest-neighbour pixel correspondences of consecutive frames
     ->  --render DIR: render_XXXX.png, the whole aligned scene drawn from every frame's own camera (z-buffered point splats)
+    ->  --fused-mesh PATH --fused-voxel V: one surface for the whole clip, the depth maps fused into a TSDF grid of edge V (binary PLY)
     ->  --flow --tracks PATH.npz: a grid of points of one frame followed through all later frames (3-D trajectories)
     ->  --flow --scene-flow DIR: scene_flow_{i}_{i+1}.npz, the 3-D motion of every pixel between consecutive frames
 
@@ -15,6 +16,7 @@ The flow of the reference's tool/demo.py and tool/depth_test.py through this pac
            [--hierarchical --clip-size 50] [--niter 300] [--schedule linear] [--lr 0.01] [--traj-format custom] [--gt-depth DIR]
            [--metrics-device] [--pointcloud scene.ply [--pointcloud-voxel V [--pointcloud-reduce best|mean] [--pointcloud-min-count C]]]
            [--matches DIR] [--render DIR [--render-radius R]] [--clean] [--device-prep]
+           [--fused-mesh PATH --fused-voxel V [--fused-trunc T] [--fused-max-depth D]]
            [--flow [--flow-weights RAFT.pth] [--gt-masks DIR] [--not-shared-focal]
                    [--tracks PATH.npz [--track-start K] [--track-stride G]] [--scene-flow DIR]]
            [--flow-hierarchical [--clip-size 10] [--device-resident] [--flow-weights ...] [--gt-masks DIR] [--not-shared-focal]]
@@ -90,6 +92,17 @@ def parse(argv=None):
                          "scene holds all frames at once")
     ap.add_argument("--render-radius", type=int, default=None, metavar="R",
                     help="--render: a point covers (2 R + 1)^2 pixels, R in [0, 8] (default 1)")
+    ap.add_argument("--fused-mesh", default=None, metavar="PATH",
+                    help="after the alignment (and after --clean) fuse the aligned depth maps of all frames into one TSDF grid of edge "
+                         "--fused-voxel and write its zero surface as one triangle mesh (binary PLY; scene.save_fused_mesh, "
+                         "csrc/tsdf.hip): the pixels above --min-conf-thr weighted by their confidence; with --flow the dynamic pixels "
+                         "are masked out. Refused with --hierarchical and --flow-hierarchical: their clips are aligned one after "
+                         "another and no scene holds all frames at once")
+    ap.add_argument("--fused-voxel", type=float, default=None, metavar="V", help="--fused-mesh: the voxel's edge in scene units (required)")
+    ap.add_argument("--fused-trunc", type=float, default=None, metavar="T",
+                    help="--fused-mesh: the truncation distance in scene units (default 3 V)")
+    ap.add_argument("--fused-max-depth", type=float, default=None, metavar="D",
+                    help="--fused-mesh: depths beyond D are not fused and do not widen the grid (default: no limit)")
     ap.add_argument("--tracks", default=None, metavar="PATH.npz",
                     help="--flow: after the alignment (and after --clean) follow a grid of points of frame --track-start through all later "
                          "frames by the optical flow of consecutive frames and write their 3-D trajectories (scene.get_tracks, "
@@ -146,6 +159,15 @@ def parse(argv=None):
         ap.error("--track-start is a frame number >= 0")
     if a.track_stride < 1:
         ap.error("--track-stride is at least 1")
+    if a.fused_mesh and (a.hierarchical or a.flow_hierarchical):
+        ap.error("--fused-mesh cannot be combined with --hierarchical or --flow-hierarchical: it needs one scene holding all frames")
+    if a.fused_mesh and a.fused_voxel is None:
+        ap.error("--fused-mesh needs --fused-voxel")
+    for given, name in ((a.fused_voxel, "--fused-voxel"), (a.fused_trunc, "--fused-trunc"), (a.fused_max_depth, "--fused-max-depth")):
+        if given is not None and not a.fused_mesh:
+            ap.error(f"{name} belongs to --fused-mesh")
+        if given is not None and not (np.isfinite(given) and given > 0):
+            ap.error(f"{name} is a finite length > 0")
     if a.render_radius is not None and not a.render:
         ap.error("--render-radius belongs to --render")
     if a.render_radius is None:
@@ -212,6 +234,13 @@ def write_voxel_cloud(path, clouds, voxel, reduce="best", min_count=1, device="c
     return int(vx["xyz"].shape[0]), len(xyz)
 
 
+def write_fused_mesh(scene, a):
+    """--fused-mesh: scene.save_fused_mesh with the driver's settings (the dynamic pixels masked out with --flow); returns
+    (vertices, faces) written."""
+    m = scene.save_fused_mesh(a.fused_mesh, a.fused_voxel, trunc=a.fused_trunc, max_depth=a.fused_max_depth, mask_dynamic=a.flow)
+    return int(m["xyz"].shape[0]), int(m["faces"].shape[0])
+
+
 def write_tracks(scene, path, start=0, stride=8):
     """A grid of seeds every `stride` pixels of frame `start`, followed through all later frames (scene.save_tracks); returns the
     number of tracks."""
@@ -259,6 +288,7 @@ def main(argv=None):
     meshes, n_mesh = ([] if a.mesh else None), None              # n_mesh: (vertices, faces) written
     n_matches = None                   # --matches: matches written per consecutive pair
     n_renders = None                   # --render: pictures written
+    n_fused = None                     # --fused-mesh: (vertices, faces) written
     n_tracks, n_scene_flow = None, None          # --tracks: tracks written; --scene-flow: valid pixels per consecutive pair
     depths_dev = None                  # --metrics-device: the aligned depth maps as the scene holds them, on the device
     if a.flow_hierarchical and len(imgs) < 3:
@@ -332,6 +362,10 @@ def main(argv=None):
             if mode != GlobalAlignerMode.PointCloudOptimizer:
                 raise RuntimeError("--render needs at least 3 frames (the two-frame PairViewer has no aligner handle to export from)")
             n_renders = len(scene.save_renders(a.render, mask_dynamic=a.flow, radius=a.render_radius))
+        if a.fused_mesh:
+            if mode != GlobalAlignerMode.PointCloudOptimizer:
+                raise RuntimeError("--fused-mesh needs at least 3 frames (the two-frame PairViewer has no aligner handle to export from)")
+            n_fused = write_fused_mesh(scene, a)
         if a.tracks:                         # both need --flow, and --flow three frames or more: the scene is the flow aligner's
             n_tracks = write_tracks(scene, a.tracks, a.track_start, a.track_stride)
         if a.scene_flow:
@@ -369,6 +403,8 @@ def main(argv=None):
         res_out["matches"], res_out["n_matches"] = a.matches, n_matches
     if a.render:
         res_out["render"], res_out["n_renders"] = a.render, n_renders
+    if a.fused_mesh:
+        res_out["fused_mesh"], res_out["n_fused_vertices"], res_out["n_fused_faces"] = a.fused_mesh, n_fused[0], n_fused[1]
     if a.tracks:
         res_out["tracks"], res_out["n_tracks"] = a.tracks, n_tracks
     if a.scene_flow:

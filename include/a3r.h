@@ -1197,6 +1197,77 @@ int a3r_voxel_export(const float* xyz, const float* priority, const unsigned cha
                      unsigned char* out_rgb, int* out_index, int* out_count, long long* n_voxels_host, long long* dropped_host,
                      void* stream);
 
+/* TSDF fusion (csrc/tsdf.hip): the aligned depth maps of a clip integrated into one dense grid of truncated signed distances, and
+ * the grid's zero surface as one triangle mesh.  The reference has no such routine; this text is the specification.  All arithmetic
+ * is float64, every operation rounded on its own (no fused products).
+ * GRID: origin[3], voxel (the cell's edge), dims (nx, ny, nz).  Voxel (i, j, k) has the centre
+ *     X = ox + ((double)i + 0.5) * voxel,  Y = oy + ((double)j + 0.5) * voxel,  Z = oz + ((double)k + 0.5) * voxel
+ * and the linear index (k * ny + j) * nx + i: the arrays are [nz, ny, nx].
+ * INPUTS: depth [N,P] fp32, weight [N,P] fp32, rgb [N,P,3] uint8 or NULL, a camera table [N] of a3r_tsdf_cam = a3r_render_cam plus
+ * the image's own shape (h, w).  Pixel (row, col) of frame n sits at n * P + row * w + col (every map flattened and padded to P,
+ * so frames of mixed shapes share one array).
+ * INTEGRATE: a voxel walks the frames n = 0 .. N - 1 in ascending order with W = S = Wc = C[0..2] = 0:
+ *   1. xc = (R00 * X + R01 * Y) + R02 * Z + t0, yc and zc likewise with rows 1 and 2 of w2c;  u = fx * (xc / zc) + cx,
+ *      v = fy * (yc / zc) + cy  (the renderer's expressions).
+ *   2. the frame is skipped unless  zc >= near,  |u| < 2^30 and |v| < 2^30,  col = rint(u) in [0, w) and row = rint(v) in [0, h)
+ *      (half to even).
+ *   3. d = (double)depth[p], wd = (double)weight[p]; skipped unless both are finite and  wd > 0,  d > 0,  d <= max_depth  (every
+ *      comparison is false for a NaN).
+ *   4. sdf = d - zc; skipped if sdf < -trunc (the voxel is hidden behind the surface).
+ *   5. t = min(1.0, sdf / trunc);  W += wd;  S += wd * t.
+ *   6. only where sdf <= trunc and rgb is given:  Wc += wd;  C[ch] += wd * (double)rgb[p][ch].
+ * OUTPUTS, each element written once:  tsdf [nz,ny,nx] fp32 = (float)(S / W), 1.0f where W == 0;  wsum fp32 = (float)W;
+ * out_rgb [nz,ny,nx,3] uint8 (or NULL) = rint(C[ch] / Wc) clipped to 255, 0 where Wc == 0.
+ * Contract: the sums live in registers and are sequential in frame order, there are no atomics: the outputs are bitwise
+ * reproducible and bitwise the numpy restatement (tests/tsdf_cases.py: tsdf_ref).  Swapping two frames may change the last bit.
+ * a3r_tsdf_integrate is enqueue-only (no synchronisation; it can be captured into a graph).  cams_dev is read by the kernel,
+ * cams_host (the same table in host memory) by the checks.  skip_stats: NULL, or two device words that the call ADDS to: the
+ * (brick, frame) pairs it met and the pairs its brick test skipped (a measurement; the only atomics of the file).
+ * A3R_EINVAL before anything is launched, naming the field: dims not positive or nx * ny * nz >= 2^31; voxel, trunc or near not
+ * finite or <= 0; max_depth <= 0 or NaN (infinity = no limit); a non-finite origin; N or P negative, N * P >= 2^31; a null array
+ * with N > 0; a non-finite camera entry; h or w <= 0, h * w > P; out_rgb without rgb.  N = 0 writes the empty grid.
+ * a3r_tsdf_set_form: a developer's A/B switch that does not change the outputs (returns the previous value; values outside [0, 1]
+ * only query).  Bit 0 set: no brick test.  Default 0: a workgroup (a brick of 32 x 8 x 1 voxels) first projects the corners of its
+ * box of voxel centres into every frame and leaves out the frames in which, by margins far above the rounding error, every voxel
+ * lies behind `near` or more than a pixel outside the image -- frames in which no voxel of the brick passes step 2.
+ * SURFACE (surface nets; no case table) from tsdf and wsum:
+ *   a voxel is OBSERVED iff (double)wsum >= min_weight (min_weight > 0);  inside(f) = f < 0.
+ *   cell (i, j, k), i < nx - 1, j < ny - 1, k < nz - 1, has the corners c = dx + 2 dy + 4 dz = voxel (i + dx, j + dy, k + dz); it
+ *     is ACTIVE iff all 8 corners are observed and their inside values differ.
+ *   the cell's 12 edges are the corner pairs (a, b), a < b, that differ in one bit, in lexicographic order (0,1) (0,2) (0,4)
+ *     (1,3) (1,5) (2,3) (2,6) (3,7) (4,5) (4,6) (5,7) (6,7).  An edge CROSSES iff inside(fa) != inside(fb); then
+ *     s = (double)fa / ((double)fa - (double)fb) and the crossing is, per axis, da + s * (db - da) with da, db the corners' offsets.
+ *   the cell's VERTEX: m = the per-axis sum of the crossings in edge order divided by their count;
+ *     x = (float)(ox + (((double)i + 0.5) + m_x) * voxel), y and z likewise;  colour (with rgb) = (2 * sum + 8) / 16 per channel in
+ *     integer arithmetic over the 8 corners.  Vertex ids = the rank of the active cells in linear order of (k, j, i).
+ *   FACES: a grid edge from voxel g along axis a (g_a + 1 < n_a) whose ends differ in inside, with b = (a + 1) % 3,
+ *     c = (a + 2) % 3 and 1 <= g_b <= n_b - 2, 1 <= g_c <= n_c - 2, has the four cells q0 = g - e_b - e_c, q1 = g - e_c, q2 = g,
+ *     q3 = g - e_b; it carries a quad iff all four are active: the triangles (q0, q1, q2), (q0, q2, q3) when inside(f(g)),
+ *     otherwise (q0, q2, q1), (q0, q3, q2).  Faces are ordered by (linear index of g, a).
+ *   Compaction without atomics: a count pass by wave ballots that leaves a rank map, an exclusive scan, a placement pass.
+ * Two phases, as a3r_voxel_count / _export:
+ *   a3r_tsdf_mesh_count  : *n_vertices_host = V, *n_faces_host = F.
+ *   a3r_tsdf_mesh_export : counts afresh; a capacity below V or F is refused with A3R_EINVAL, the message names both counts and
+ *                          NOTHING is written; otherwise out_xyz [V,3] fp32, out_rgb [V,3] uint8 (or NULL) and out_faces [F,3]
+ *                          int32 are written.  The counts are set in both cases.
+ * Both synchronise `stream` once.  workspace: a3r_tsdf_mesh_workspace_bytes(nx, ny, nz) bytes, 16-byte aligned:
+ * 2 * 4 (ceil(nvox / 1024) + 1) + 4 nvox, each part rounded up to 256 (0 for refused sizes).  A3R_EINVAL as above for the grid, and
+ * for nx * ny * nz above 2^31 / 6 (the face count is an int), min_weight not finite or <= 0, a null tsdf / wsum / count pointer, a
+ * workspace that is too small or misaligned, a negative capacity, a null output with a positive capacity, out_rgb without rgb. */
+typedef struct { double w2c[12]; double fx, fy, cx, cy; int h, w; } a3r_tsdf_cam;
+int a3r_tsdf_integrate(const float* depth, const float* weight, const unsigned char* rgb, const a3r_tsdf_cam* cams_dev,
+                       const a3r_tsdf_cam* cams_host, int N, long long P, const double origin[3], double voxel, int nx, int ny, int nz,
+                       double trunc, double near_z, double max_depth, float* tsdf, float* wsum, unsigned char* out_rgb,
+                       unsigned long long* skip_stats, void* stream);
+int a3r_tsdf_set_form(int form);
+size_t a3r_tsdf_mesh_workspace_bytes(int nx, int ny, int nz);
+int a3r_tsdf_mesh_count(const float* tsdf, const float* wsum, int nx, int ny, int nz, double min_weight, void* workspace,
+                        size_t workspace_bytes, long long* n_vertices_host, long long* n_faces_host, void* stream);
+int a3r_tsdf_mesh_export(const float* tsdf, const float* wsum, const unsigned char* rgb, int nx, int ny, int nz, const double origin[3],
+                         double voxel, double min_weight, void* workspace, size_t workspace_bytes, long long vertex_capacity,
+                         long long face_capacity, float* out_xyz, unsigned char* out_rgb, int* out_faces, long long* n_vertices_host,
+                         long long* n_faces_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
