@@ -70,6 +70,14 @@ struct PerDeviceOnce {
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }      // a: a power of two
+
+// the workspace argument of an entry that needs `need` bytes of it, 16-byte aligned
+inline int check_workspace(const char* who, const void* ws, size_t ws_bytes, size_t need) {
+    A3R_CHECK_ARG(ws && ws_bytes >= need, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
+    A3R_CHECK_ARG(aligned_to(ws, 16), "%s: workspace must be 16-byte aligned", who);
+    return A3R_OK;
+}
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));

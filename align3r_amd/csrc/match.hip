@@ -15,8 +15,9 @@
 //     instructions.  Each (query, chunk) leaves one partial (d2, index) in the workspace, laid out [chunk][query].
 //   * fold: one thread per query walks its partials in ascending chunk order with the same strict `<`: since the ranges ascend,
 //     that is the definition's answer whatever the chunk count.
-//   * reciprocity: flags and per-block counts (wave64 ballots), one exclusive scan, placement by rank (the scheme of scene.hip).
+//   * reciprocity: flags, then the flagged k2 compacted by the count / scan / place scheme of compact.h.
 #include "common.h"
+#include "compact.h"
 #include <cmath>
 
 namespace a3r {
@@ -29,7 +30,6 @@ constexpr int NN_UNROLL = 4;                    // a tile is padded with NaN poi
 constexpr int NN_MAX_CHUNKS = 65535;            // the second grid axis
 constexpr int RM_PER = 4;                       // consecutive k2 per thread in the reciprocity passes
 constexpr int RM_BLOCK = NN_TPB * RM_PER;
-constexpr int RM_SCAN_TPB = 1024;
 
 // grid (ceil(nq / NN_QBLOCK), chunks).  Query j of a thread is blockIdx.x * NN_QBLOCK + j * NN_TPB + tid (consecutive lanes on
 // consecutive queries).  Chunk c owns the data range [nd * c / chunks, nd * (c + 1) / chunks), empty when chunks > nd.
@@ -106,7 +106,7 @@ template <bool WRITE>
 __global__ __launch_bounds__(NN_TPB) void reciprocal_kernel(const int* __restrict__ nn2, const int* __restrict__ nn1, int n1, int n2,
                                                            unsigned char* flags, int* offsets, int* __restrict__ out_pairs) {
     __shared__ int wave_total[NN_TPB / 64];
-    const int tid = threadIdx.x, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const long long k0 = (long long)blockIdx.x * RM_BLOCK + tid * RM_PER;
     bool keep[RM_PER];
     int k1[RM_PER];
@@ -117,22 +117,8 @@ __global__ __launch_bounds__(NN_TPB) void reciprocal_kernel(const int* __restric
         if (WRITE) keep[i] = k2 < n2 && flags[k2] != 0;
         else       keep[i] = k1[i] >= 0 && k1[i] < n1 && nn1[k1[i]] == k2;
     }
-    int below = 0, in_wave = 0;
-#pragma unroll
-    for (int i = 0; i < RM_PER; i++) {
-        const unsigned long long b = __ballot(keep[i]);
-        below += __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-        in_wave += __popcll(b);
-    }
-    if ((tid & 63) == 0) wave_total[wave] = in_wave;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < NN_TPB / 64; k++) {
-        const int t = wave_total[k];
-        if (k < wave) before += t;
-        total += t;
-    }
+    int first, total;
+    block_rank<NN_TPB, RM_PER>(keep, wave_total, &first, &total);
     if (!WRITE) {
 #pragma unroll
         for (int i = 0; i < RM_PER; i++)
@@ -140,43 +126,14 @@ __global__ __launch_bounds__(NN_TPB) void reciprocal_kernel(const int* __restric
         if (tid == 0) offsets[blockIdx.x] = total;
         return;
     }
-    // the order inside a wave is (lane, i): `below` counts the flags of lower lanes over all i, so rank the own ones after it
     const int lim = offsets[blockIdx.x + 1];                     // the count pass saw the same flags; stay inside the range regardless
-    int pos = offsets[blockIdx.x] + before + below;
+    int pos = offsets[blockIdx.x] + first;
 #pragma unroll
     for (int i = 0; i < RM_PER; i++) {
         if (!keep[i]) continue;
         if (pos < lim) { out_pairs[(size_t)pos * 2 + 0] = k1[i]; out_pairs[(size_t)pos * 2 + 1] = (int)(k0 + i); }
         pos++;
     }
-}
-
-// One workgroup: cnt[0 .. T) (block counts) -> exclusive offsets in place, cnt[T] = total.  A thread owns a contiguous segment; the
-// segment sums are scanned through LDS.
-__global__ __launch_bounds__(RM_SCAN_TPB) void match_scan_kernel(int* cnt, int T) {
-    __shared__ int sh[2][RM_SCAN_TPB];
-    const int tid = threadIdx.x;
-    const int seg = (T + RM_SCAN_TPB - 1) / RM_SCAN_TPB;
-    const int lo = (int)min((long long)tid * seg, (long long)T), hi = (int)min((long long)lo + seg, (long long)T);
-    int sum = 0;
-    for (int k = lo; k < hi; k++) sum += cnt[k];
-    int cur = 0;
-    sh[0][tid] = sum;
-    __syncthreads();
-    for (int off = 1; off < RM_SCAN_TPB; off <<= 1) {            // inclusive Hillis-Steele scan, double-buffered
-        int val = sh[cur][tid];
-        if (tid >= off) val += sh[cur][tid - off];
-        sh[cur ^ 1][tid] = val;
-        cur ^= 1;
-        __syncthreads();
-    }
-    int run = sh[cur][tid] - sum;
-    for (int k = lo; k < hi; k++) {
-        const int t = cnt[k];
-        cnt[k] = run;
-        run += t;
-    }
-    if (tid == RM_SCAN_TPB - 1) cnt[T] = sh[cur][tid];
 }
 
 // The chunk count of a search.  Forced: as given.  Chosen: enough (query blocks x chunks) workgroups for sixteen per CU of the 256
@@ -196,7 +153,6 @@ static int nn_resolve_chunks(long long nq, long long nd, int chunks) {
 static size_t nn_part_d2_bytes(long long nq, int chunks) { return align_up((size_t)nq * chunks * sizeof(double), 256); }
 static size_t nn_part_idx_bytes(long long nq, int chunks) { return align_up((size_t)nq * chunks * sizeof(int), 256); }
 static bool nn_size_ok(long long n) { return n >= 0 && n < (1ll << 31); }
-static bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 static size_t nn_workspace_bytes(long long nq, long long nd, int chunks) {
     if (!nn_size_ok(nq) || !nn_size_ok(nd) || chunks < 0 || chunks > NN_MAX_CHUNKS || nq == 0 || nd == 0) return 0;
@@ -251,8 +207,8 @@ extern "C" int a3r_nn_search(const float* query, long long n_query, const float*
     A3R_CHECK_ARG(data || n_data == 0, "%s: null data", who);
     A3R_CHECK_ARG(out_index || n_query == 0, "%s: null out_index", who);
     const size_t need = nn_workspace_bytes(n_query, n_data, chunks);
-    A3R_CHECK_ARG(need == 0 || (workspace && workspace_bytes >= need), "%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
-    A3R_CHECK_ARG(need == 0 || aligned_to(workspace, 16), "%s: workspace must be 16-byte aligned", who);
+    if (need != 0)
+        if (int rc = check_workspace(who, workspace, workspace_bytes, need)) return rc;
     nn_enqueue(query, n_query, data, n_data, chunks, workspace, out_index, out_dist2, as_stream(stream));
     A3R_LAUNCH_CHECK();
     return A3R_OK;
@@ -260,7 +216,7 @@ extern "C" int a3r_nn_search(const float* query, long long n_query, const float*
 
 extern "C" size_t a3r_match_workspace_bytes(long long n1, long long n2, int chunks) {
     if (!nn_size_ok(n1) || !nn_size_ok(n2) || chunks < 0 || chunks > NN_MAX_CHUNKS || n1 == 0 || n2 == 0) return 0;
-    return rm_search_bytes(n1, n2, chunks) + rm_nn1_bytes(n1) + align_up((size_t)(rm_blocks(n2) + 1) * sizeof(int), 256);
+    return rm_search_bytes(n1, n2, chunks) + rm_nn1_bytes(n1) + compact_offsets_bytes((size_t)rm_blocks(n2));
 }
 
 extern "C" int a3r_reciprocal_matches(const float* p1, long long n1, const float* p2, long long n2, int chunks, void* workspace,
@@ -276,8 +232,8 @@ extern "C" int a3r_reciprocal_matches(const float* p1, long long n1, const float
     A3R_CHECK_ARG(p2 || n2 == 0, "%s: null p2", who);
     A3R_CHECK_ARG((nn2_in_p1 && reciprocal_in_p2) || n2 == 0, "%s: null nn2_in_p1 / reciprocal_in_p2", who);
     const size_t need = a3r_match_workspace_bytes(n1, n2, chunks);
-    A3R_CHECK_ARG(need == 0 || (workspace && workspace_bytes >= need), "%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
-    A3R_CHECK_ARG(need == 0 || aligned_to(workspace, 16), "%s: workspace must be 16-byte aligned", who);
+    if (need != 0)
+        if (int rc = check_workspace(who, workspace, workspace_bytes, need)) return rc;
     hipStream_t st = as_stream(stream);
     if (n1 == 0 || n2 == 0) {           // no neighbour on either side: -1 everywhere, nothing reciprocal
         if (n2 > 0) {
@@ -297,11 +253,11 @@ extern "C" int a3r_reciprocal_matches(const float* p1, long long n1, const float
     nn_enqueue(p1, n1, p2, n2, chunks, ws, nn1, nullptr, st);             // stream order: the first search's fold has read its partials
     hipLaunchKernelGGL((reciprocal_kernel<false>), dim3(nblk), dim3(NN_TPB), 0, st, nn2_in_p1, nn1, (int)n1, (int)n2, reciprocal_in_p2, offsets,
                        static_cast<int*>(nullptr));
-    hipLaunchKernelGGL(match_scan_kernel, dim3(1), dim3(RM_SCAN_TPB), 0, st, offsets, nblk);
+    compact_scan(offsets, nblk, st);
     A3R_LAUNCH_CHECK();
     if (nn1_in_p2) A3R_HIP(hipMemcpyAsync(nn1_in_p2, nn1, (size_t)n1 * sizeof(int), hipMemcpyDeviceToDevice, st));
     int total = 0;
-    A3R_HIP(hipMemcpyAsync(&total, offsets + nblk, sizeof(int), hipMemcpyDeviceToHost, st));
+    A3R_HIP(compact_read_total(offsets, nblk, &total, st));
     A3R_HIP(hipStreamSynchronize(st));
     *n_matches_host = total;
     if (!out_pairs) return A3R_OK;

@@ -11,8 +11,8 @@
 //                             four wave sums added in wave order by thread 0, one partial row per workgroup.  16-byte loads when
 //                             pred and gt are both 16-byte aligned (the n % 4 tail goes to the first threads), scalar loads otherwise.
 //                             MODE: first moments, centred second moments, the LAD sums, the metric sums.
-//   'scale' (mean ratio + 10 IRLS passes) is the exception: it compacts the valid pixels in order and adds with numpy's summation
-//   tree, bit for bit the host's sums (see there for why).
+//   'scale' (mean ratio + 10 IRLS passes) is the exception: it compacts the valid pixels in order (the workgroup rank of compact.h)
+//   and adds with numpy's summation tree, bit for bit the host's sums (see there for why).
 //   depth_hist_kernel         one 8-bit digit of the radix select, for four order statistics at once (the two middle ones of the valid
 //                             pred and of the valid gt): LDS histograms, integer atomics to the global ones.
 // One-wave kernels between the passes fold the partial rows in a fixed order (lane l adds rows l, l + 64, ..., then a butterfly)
@@ -26,6 +26,7 @@
 // grows fourfold and the search restarts (at most LAD_ROUNDS rounds; the best point is kept across rounds).  All rounds are enqueued;
 // once the solve is done the remaining kernels return at their first instruction.
 #include "common.h"
+#include "compact.h"
 
 #include <cmath>
 
@@ -67,7 +68,6 @@ constexpr int NPT = 128;                        // threads of a buffer's workgro
 static size_t dws_cnt_bytes(long long n) { return align_up((size_t)((n + SCH - 1) / SCH) * sizeof(unsigned), 256); }
 static size_t dws_compact_bytes(long long n) { return align_up((size_t)n * sizeof(float), 256); }
 static size_t dws_csum_bytes(long long n) { return align_up((size_t)((n + NPB - 1) / NPB) * 2 * sizeof(double), 256); }
-static bool d_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 struct DepthView {
     const float* pred;
@@ -382,18 +382,17 @@ __global__ __launch_bounds__(64) void depth_mom2_step_kernel(DepthView v) {
 
 // grid (ceil(n / SCH)): valid pixels of the chunk
 __global__ __launch_bounds__(DTPB) void depth_count_kernel(DepthView v) {
-    __shared__ unsigned sh[DTPB / 64];
-    const int tid = threadIdx.x;
-    const long long e0 = (long long)blockIdx.x * SCH + tid * 4;
-    unsigned c = 0;
+    __shared__ int wave_total[DTPB / 64];
+    const long long e0 = (long long)blockIdx.x * SCH + threadIdx.x * 4;
+    bool ok[4];
 #pragma unroll
-    for (int k = 0; k < 4; k++)
-        if (e0 + k < v.n) { const float g = v.gt[e0 + k]; c += (g > v.lo && g < v.hi) ? 1u : 0u; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-    if ((tid & 63) == 0) sh[tid >> 6] = c;
-    __syncthreads();
-    if (tid == 0) v.cnt[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+    for (int k = 0; k < 4; k++) {
+        ok[k] = false;
+        if (e0 + k < v.n) { const float g = v.gt[e0 + k]; ok[k] = g > v.lo && g < v.hi; }
+    }
+    int first, total;
+    block_rank<DTPB, 4>(ok, wave_total, &first, &total);
+    if (threadIdx.x == 0) v.cnt[blockIdx.x] = (unsigned)total;
 }
 
 // one workgroup: exclusive prefix sums of the nb chunk counts, in place; the total
@@ -420,25 +419,18 @@ __global__ __launch_bounds__(DTPB) void depth_scan_kernel(DepthView v, int nb) {
 
 // grid (ceil(n / SCH)): the valid pixels of the chunk to their places in the compacted arrays, in order
 __global__ __launch_bounds__(DTPB) void depth_scatter_kernel(DepthView v) {
-    __shared__ unsigned sh[DTPB / 64];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const long long e0 = (long long)blockIdx.x * SCH + tid * 4;
+    __shared__ int wave_total[DTPB / 64];
+    const long long e0 = (long long)blockIdx.x * SCH + threadIdx.x * 4;
     float p[4], g[4];
     bool ok[4];
-    unsigned c = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         ok[k] = false; p[k] = 0.f; g[k] = 0.f;
         if (e0 + k < v.n) { p[k] = v.pred[e0 + k]; g[k] = v.gt[e0 + k]; ok[k] = g[k] > v.lo && g[k] < v.hi; }
-        c += ok[k] ? 1u : 0u;
     }
-    unsigned inc = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(inc, o); if (lane >= o) inc += t; }
-    if (lane == 63) sh[w] = inc;
-    __syncthreads();
-    unsigned r = v.cnt[blockIdx.x] + inc - c;
-    for (int k = 0; k < w; k++) r += sh[k];
+    int first, total;
+    block_rank<DTPB, 4>(ok, wave_total, &first, &total);
+    unsigned r = v.cnt[blockIdx.x] + (unsigned)first;
 #pragma unroll
     for (int k = 0; k < 4; k++)
         if (ok[k]) { v.cp[r] = p[k]; v.cg[r] = g[k]; r++; }
@@ -594,7 +586,7 @@ static int depth_check(const char* who, const float* pred, const float* gt, long
     A3R_CHECK_ARG(ws, "%s: null workspace", who);
     const size_t need = a3r_depth_eval_workspace_bytes(n);
     A3R_CHECK_ARG(ws_bytes >= need, "%s: workspace_bytes too small (%zu < %zu)", who, ws_bytes, need);
-    A3R_CHECK_ARG(d_aligned(ws, 16), "%s: workspace must be 16-byte aligned", who);
+    A3R_CHECK_ARG(aligned_to(ws, 16), "%s: workspace must be 16-byte aligned", who);
     v.pred = pred; v.gt = gt; v.n = n;
     v.lo = (float)1e-3; v.hi = (float)depth_max; v.dmax = depth_max;
     const long long per = (long long)DTPB * 4;
@@ -629,7 +621,7 @@ extern "C" int a3r_depth_align(const float* pred, const float* gt, long n, doubl
     A3R_CHECK_ARG(st_dev, "%s: null st_dev", who);
     A3R_CHECK_ARG(info_dev, "%s: null info_dev", who);
     hipStream_t st = as_stream(stream);
-    const bool vec = d_aligned(pred, 16) && d_aligned(gt, 16);
+    const bool vec = aligned_to(pred, 16) && aligned_to(gt, 16);
     const dim3 one(1), wave(64);
     hipLaunchKernelGGL(depth_init_kernel, one, wave, 0, st, v);
     if (mode == A3R_DEPTH_ALIGN_LAD || mode == A3R_DEPTH_ALIGN_MEDIAN) {
@@ -677,7 +669,7 @@ extern "C" int a3r_depth_metrics(const float* pred, const float* gt, long n, dou
     A3R_CHECK_ARG(st_dev, "%s: null st_dev", who);
     A3R_CHECK_ARG(out_dev, "%s: null out_dev", who);
     hipStream_t st = as_stream(stream);
-    const bool vec = d_aligned(pred, 16) && d_aligned(gt, 16);
+    const bool vec = aligned_to(pred, 16) && aligned_to(gt, 16);
     hipLaunchKernelGGL(depth_metrics_init_kernel, dim3(1), dim3(64), 0, st, v, st_dev);
     depth_pass<DP_METRICS, false>(v, vec, st);
     hipLaunchKernelGGL(depth_metrics_finish_kernel, dim3(1), dim3(64), 0, st, v, out_dev);

@@ -34,7 +34,6 @@ static int motion_nchunks(int P) { return (P + MCHUNK - 1) / MCHUNK; }
 static size_t motion_err_bytes(int M, int P) { return align_up((size_t)2 * M * P * sizeof(float), 256); }
 static size_t motion_partial_bytes(int M, int P) { return align_up((size_t)2 * M * motion_nchunks(P) * 4 * sizeof(float), 256); }
 static size_t motion_stats_bytes(int M) { return align_up((size_t)2 * M * 2 * sizeof(float), 256); }
-static bool m_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 struct MotionView {
     int M2, N, E, P, W, nch;
@@ -224,8 +223,7 @@ extern "C" int a3r_motion_masks(const a3r_motion_desc* d, void* ws, size_t ws_by
     A3R_CHECK_ARG(d->motion_mask_thre == d->motion_mask_thre, "%s: motion_mask_thre is NaN", who);
     const int M2 = 2 * d->M, P = d->H * d->W;
     const size_t need = a3r_motion_workspace_bytes(d->M, d->N, P);
-    A3R_CHECK_ARG(ws && ws_bytes >= need, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
-    A3R_CHECK_ARG(m_aligned(ws, 16), "%s: workspace must be 16-byte aligned", who);
+    if (int rc = check_workspace(who, ws, ws_bytes, need)) return rc;
     for (int e = 0; e < M2; e++) {
         const a3r_motion_entry& r = d->entries_host[e];
         A3R_CHECK_ARG(r.depth_row >= 0 && r.depth_row < 2 * d->E, "%s: entry %d: depth_row %d is outside [0, %d)", who, e, r.depth_row, 2 * d->E);
@@ -251,8 +249,8 @@ extern "C" int a3r_motion_masks(const a3r_motion_desc* d, void* ws, size_t ws_by
     v.err = reinterpret_cast<float*>(w);
     v.partial = reinterpret_cast<float*>(w + motion_err_bytes(d->M, P));
     v.stats = reinterpret_cast<float*>(w + motion_err_bytes(d->M, P) + motion_partial_bytes(d->M, P));
-    const bool vec = P % 4 == 0 && m_aligned(d->pred_i, 16) && m_aligned(d->pred_j, 16) && m_aligned(d->flow_ij, 16) && m_aligned(d->flow_ji, 16) &&
-                     m_aligned(masks, 4) && (!mean_err || m_aligned(mean_err, 16));
+    const bool vec = P % 4 == 0 && aligned_to(d->pred_i, 16) && aligned_to(d->pred_j, 16) && aligned_to(d->flow_ij, 16) && aligned_to(d->flow_ji, 16) &&
+                     aligned_to(masks, 4) && (!mean_err || aligned_to(mean_err, 16));
     const dim3 block(MTPB);
     if (vec) hipLaunchKernelGGL((motion_err_kernel<true>), dim3(v.nch, M2), block, 0, st, v);
     else     hipLaunchKernelGGL((motion_err_kernel<false>), dim3(v.nch, M2), block, 0, st, v);

@@ -45,7 +45,6 @@ static int prep_nchunks(long long P) { return (int)((P + PCHUNK - 1) / PCHUNK); 
 static size_t prep_inter_bytes(int Hs, int Wc) { return align_up((size_t)Hs * Wc * 3 * sizeof(double), 256); }
 static size_t prep_partial_bytes(int Hs, int Ws) { return align_up((size_t)prep_nchunks((long long)Hs * Ws) * 8 * sizeof(float), 256); }
 static size_t prep_stats_bytes() { return 256; }
-static bool p_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 struct PrepView {
     int Hs, Ws, P, nch;
@@ -338,11 +337,10 @@ static int prep_check(const char* who, const float* src, const a3r_prep_desc* d,
                   "%s: the crop window (y0=%d x0=%d Hc=%d Wc=%d) is outside the resized map %d x %d", who, d->y0, d->x0, d->Hc, d->Wc, d->Hr, d->Wr);
     A3R_CHECK_ARG(src && out, "%s: null source or output buffer", who);
     A3R_CHECK_ARG(d->idx_x && d->idx_x_host && d->w_x && d->idx_y && d->idx_y_host && d->w_y, "%s: null index or weight table", who);
-    A3R_CHECK_ARG(p_aligned(d->idx_x, 16) && p_aligned(d->w_x, 16) && p_aligned(d->idx_y, 16) && p_aligned(d->w_y, 16),
+    A3R_CHECK_ARG(aligned_to(d->idx_x, 16) && aligned_to(d->w_x, 16) && aligned_to(d->idx_y, 16) && aligned_to(d->w_y, 16),
                   "%s: the device tables must be 16-byte aligned", who);
     const size_t need = a3r_prep_workspace_bytes(d->Hs, d->Ws, d->Wc);
-    A3R_CHECK_ARG(ws && ws_bytes >= need, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
-    A3R_CHECK_ARG(p_aligned(ws, 16), "%s: workspace must be 16-byte aligned", who);
+    if (int rc = check_workspace(who, ws, ws_bytes, need)) return rc;
     for (long long k = 0; k < (long long)d->Wr * d->taps; k++)
         A3R_CHECK_ARG(d->idx_x_host[k] >= 0 && d->idx_x_host[k] < d->Ws, "%s: idx_x[%lld, %lld] = %d is outside [0, %d)", who, k / d->taps,
                       k % d->taps, d->idx_x_host[k], d->Ws);
@@ -372,7 +370,7 @@ static void prep_resample(const PrepView& v, int taps, const float* src, float* 
     if (taps == 8) hipLaunchKernelGGL((prep_hpass_kernel<8, DEPTH>), gh, block, 0, st, v, src);
     else           hipLaunchKernelGGL((prep_hpass_kernel<4, DEPTH>), gh, block, 0, st, v, src);
     const dim3 gv((v.Wc * 3 + PCHUNK - 1) / PCHUNK, v.Hc);
-    const bool vec = (v.Wc * 3) % 4 == 0 && p_aligned(out, 16);
+    const bool vec = (v.Wc * 3) % 4 == 0 && aligned_to(out, 16);
 #define A3R_PREP_VPASS(T, V) hipLaunchKernelGGL((prep_vpass_kernel<T, V>), gv, block, 0, st, v, out)
     if (taps == 8) { if (vec) A3R_PREP_VPASS(8, true); else A3R_PREP_VPASS(8, false); }
     else           { if (vec) A3R_PREP_VPASS(4, true); else A3R_PREP_VPASS(4, false); }
@@ -388,7 +386,7 @@ extern "C" int a3r_prep_pointmap(const float* depth, double focal, const a3r_pre
     A3R_CHECK_ARG(std::isfinite(focal) && focal != 0.0, "%s: the focal must be finite and non-zero (%g)", who, focal);
     v.focal = focal;
     hipStream_t st = as_stream(stream);
-    if (v.P % 4 == 0 && p_aligned(depth, 16)) hipLaunchKernelGGL((prep_minmax_kernel<true>), dim3(v.nch), dim3(PTPB), 0, st, v, depth);
+    if (v.P % 4 == 0 && aligned_to(depth, 16)) hipLaunchKernelGGL((prep_minmax_kernel<true>), dim3(v.nch), dim3(PTPB), 0, st, v, depth);
     else                                      hipLaunchKernelGGL((prep_minmax_kernel<false>), dim3(v.nch), dim3(PTPB), 0, st, v, depth);
     hipLaunchKernelGGL(prep_fold_kernel, dim3(1), dim3(PTPB), 0, st, v);
     prep_resample<true>(v, d->taps, depth, out, st);
@@ -414,7 +412,7 @@ extern "C" int a3r_prep_image(const unsigned char* u8, int H, int W, float* img,
     const int P = H * W;
     const dim3 grid((P + PCHUNK - 1) / PCHUNK), block(PTPB);
     hipStream_t st = as_stream(stream);
-    if (P % 4 == 0 && p_aligned(u8, 4) && p_aligned(img, 16) && p_aligned(mask, 4))
+    if (P % 4 == 0 && aligned_to(u8, 4) && aligned_to(img, 16) && aligned_to(mask, 4))
         hipLaunchKernelGGL((prep_image_kernel<true>), grid, block, 0, st, u8, P, img, mask);
     else
         hipLaunchKernelGGL((prep_image_kernel<false>), grid, block, 0, st, u8, P, img, mask);

@@ -176,8 +176,7 @@ extern "C" int a3r_render_points(const float* xyz, const unsigned char* rgb, lon
             A3R_CHECK_ARG(std::isfinite(e[k]), "%s: camera %d: entry %d (w2c[0..11], fx, fy, cx, cy) is not finite", who, c, k);
     }
     const size_t need = a3r_render_workspace_bytes(n_cams, H, W);
-    A3R_CHECK_ARG(ws && ws_bytes >= need, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
-    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: workspace must be 16-byte aligned", who);
+    if (int rc = check_workspace(who, ws, ws_bytes, need)) return rc;
 
     unsigned long long* keys = static_cast<unsigned long long*>(ws);
     const long long n = (long long)n_cams * H * W;

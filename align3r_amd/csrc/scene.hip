@@ -8,10 +8,8 @@
 // the arithmetic of align_main_kernel's pixel_forward.  Streaming kernels, HBM-bound:
 //   * a workgroup owns SCHUNK = 1024 consecutive pixels of one image, a thread 4 CONSECUTIVE pixels (16-byte loads when P % 4 == 0
 //     and the buffers are 16-byte aligned, scalar loads otherwise);
-//   * compaction in two passes, no atomics: pass 1 counts the kept pixels of every chunk (wave64 ballots + popcounts), one small
-//     kernel turns the N * nchunks counts into exclusive offsets, pass 2 recomputes the points and places them.  A kept pixel's
-//     position is offset[chunk] + (kept pixels of lower waves) + (kept pixels of lower lanes) + (kept among the thread's own
-//     earlier pixels): image-major, row-major, a function of the inputs alone.
+//   * compaction by the count / scan / place scheme of compact.h: pass 1 counts the kept pixels of every chunk, pass 2 recomputes
+//     the points and places them at offset[chunk] + rank: image-major, row-major, a function of the inputs alone.
 //   * pass 2 stages a workgroup's points in LDS (its output range is contiguous) and writes them with consecutive lanes on
 //     consecutive addresses.
 //   * the triangle mesh over the kept pixels (pts3d_to_trimesh / cat_meshes of dust3r/viz.py) repeats the scheme for faces: pass 1
@@ -19,7 +17,7 @@
 //     but that map and the scanned offsets.
 #include "common.h"
 #include "scene.h"
-#include "scan.h"
+#include "compact.h"
 
 namespace a3r {
 
@@ -132,7 +130,7 @@ __global__ __launch_bounds__(STPB) void scene_compact_kernel(SceneView v, SceneS
     __shared__ float st_xyz[WRITE ? SCHUNK * 3 : 1];
     __shared__ int st_index[WRITE ? SCHUNK : 1];
     __shared__ unsigned char st_rgb[WRITE ? SCHUNK * 3 : 4];
-    const int n = blockIdx.y, tid = threadIdx.x, wave = tid >> 6;
+    const int n = blockIdx.y, tid = threadIdx.x;
     const int nchunks = gridDim.x, p0 = blockIdx.x * SCHUNK + tid * SPX;
     const SceneCam c = load_cam(img_xf, imw, imarea, n);
     const size_t base = (size_t)n * v.P;
@@ -167,26 +165,12 @@ __global__ __launch_bounds__(STPB) void scene_compact_kernel(SceneView v, SceneS
                   __builtin_isfinite(w[i][0]) && __builtin_isfinite(w[i][1]) && __builtin_isfinite(w[i][2]);
         if (++x == c.W) { x = 0; y++; }
     }
-    // rank inside the wave: the threads own consecutive pixel quads, so the order is (lane, i)
-    int below = 0, in_wave = 0, mine = 0;
-#pragma unroll
-    for (int i = 0; i < SPX; i++) {
-        const unsigned long long b = __ballot(keep[i]);
-        below += __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-        in_wave += __popcll(b);
-    }
-    if ((tid & 63) == 0) wave_total[wave] = in_wave;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < STPB / 64; k++) {
-        const int t = wave_total[k];
-        if (k < wave) before += t;
-        total += t;
-    }
+    // the threads own consecutive pixel quads, so the order is (thread, i)
+    int first, total;
+    block_rank<STPB, SPX>(keep, wave_total, &first, &total);
     if (!WRITE) {
         if (s.rank) {
-            int l = before + below, r[SPX];
+            int l = first, r[SPX];
 #pragma unroll
             for (int i = 0; i < SPX; i++) r[i] = keep[i] ? l++ : -1;
             int* o = s.rank + base + p0;
@@ -215,7 +199,7 @@ __global__ __launch_bounds__(STPB) void scene_compact_kernel(SceneView v, SceneS
                 if (p0 + k / 3 < v.P) c3[k >> 2] |= (unsigned)src[k] << (8 * (k & 3));
         }
     }
-    int l = before + below;
+    int l = first;
 #pragma unroll
     for (int i = 0; i < SPX; i++) {
         if (!keep[i]) continue;
@@ -261,10 +245,10 @@ struct SceneMesh {
 // faces are staged in LDS (A in the first SCHUNK slots, B in the second) and written with consecutive lanes on consecutive addresses.
 template <bool VEC, bool WRITE>
 __global__ __launch_bounds__(STPB) void scene_faces_kernel(SceneMesh m, const int* __restrict__ imw) {
-    __shared__ int wave_total[2][STPB / 64];
+    __shared__ int wave_total[2 * (STPB / 64)];
     __shared__ int st_face[WRITE ? 2 * SCHUNK * 3 : 1];
     __shared__ unsigned char st_rgb[WRITE ? 2 * SCHUNK * 3 : 4];
-    const int n = blockIdx.y, tid = threadIdx.x, wave = tid >> 6;
+    const int n = blockIdx.y, tid = threadIdx.x;
     const int nchunks = gridDim.x, p0 = blockIdx.x * SCHUNK + tid * SPX;
     const int W = imw[n], P = m.P;
     const size_t base = (size_t)n * P;
@@ -297,7 +281,9 @@ __global__ __launch_bounds__(STPB) void scene_faces_kernel(SceneMesh m, const in
             if (q0 + i < P) bot[i] = rk[q0 + i];
     }
     if (q0 + SPX < P) bot[SPX] = rk[q0 + SPX];
-    bool fa[SPX], fb[SPX];
+    bool face[2 * SPX];               // the two flag sets of one block_rank: A, then B
+    bool* const fa = face;
+    bool* const fb = face + SPX;
     int x = p0 % W;
 #pragma unroll
     for (int i = 0; i < SPX; i++) {
@@ -306,25 +292,10 @@ __global__ __launch_bounds__(STPB) void scene_faces_kernel(SceneMesh m, const in
         fb[i] = diag && bot[i + 1] >= 0;
         if (++x == W) x = 0;
     }
-    // ranks inside the wave, A and B apart: quad order is (lane, i)
-    int below_a = 0, below_b = 0, wave_a = 0, wave_b = 0;
-#pragma unroll
-    for (int i = 0; i < SPX; i++) {
-        const unsigned long long a = __ballot(fa[i]), b = __ballot(fb[i]);
-        below_a += __builtin_amdgcn_mbcnt_hi((unsigned)(a >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)a, 0u));
-        below_b += __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-        wave_a += __popcll(a);
-        wave_b += __popcll(b);
-    }
-    if ((tid & 63) == 0) { wave_total[0][wave] = wave_a; wave_total[1][wave] = wave_b; }
-    __syncthreads();
-    int before_a = 0, before_b = 0, total_a = 0, total_b = 0;
-#pragma unroll
-    for (int k = 0; k < STPB / 64; k++) {
-        const int ta = wave_total[0][k], tb = wave_total[1][k];
-        if (k < wave) { before_a += ta; before_b += tb; }
-        total_a += ta; total_b += tb;
-    }
+    // A and B ranked apart under one barrier: quad order is (thread, i)
+    int first[2], total[2];
+    block_rank<STPB, SPX, 2>(face, wave_total, first, total);
+    const int total_a = total[0], total_b = total[1];
     const int slot_a = n * m.nblk * nchunks + blockIdx.x, slot_b = slot_a + (m.nblk >> 1) * nchunks;
     const bool two = m.nblk == 4;
     if (!WRITE) {
@@ -337,7 +308,7 @@ __global__ __launch_bounds__(STPB) void scene_faces_kernel(SceneMesh m, const in
     if (total_a + total_b == 0) return;      // workgroup-uniform
     const int* __restrict__ vo = m.voff + n * nchunks;
     const bool colour = m.out_rgb != nullptr;
-    int la = before_a + below_a, lb = SCHUNK + before_b + below_b;
+    int la = first[0], lb = SCHUNK + first[1];
 #pragma unroll
     for (int i = 0; i < SPX; i++) {
         if (!(fa[i] || fb[i])) continue;
@@ -498,7 +469,6 @@ __global__ __launch_bounds__(STPB) void scene_clean_kernel(SceneView v, float* c
 }
 
 static int scene_nchunks(int P) { return (P + SCHUNK - 1) / SCHUNK; }
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace a3r
 
@@ -507,7 +477,7 @@ using namespace a3r;
 
 extern "C" size_t a3r_align_scene_workspace_bytes(int N, int P) {
     if (N <= 0 || P <= 0) return 0;
-    return align_up(((size_t)N * scene_nchunks(P) + 1) * sizeof(int), 256);
+    return compact_offsets_bytes((size_t)N * scene_nchunks(P));
 }
 
 extern "C" int a3r_align_scene_points(a3r_align_t a, float* out_xyz, void* stream) {
@@ -515,7 +485,7 @@ extern "C" int a3r_align_scene_points(a3r_align_t a, float* out_xyz, void* strea
     hipStream_t st = as_stream(stream);
     SceneView v;
     if (int rc = align_scene_view(a, st, &v, "a3r_align_scene_points")) return rc;
-    const bool vec = v.P % 4 == 0 && aligned16(v.depth) && aligned16(out_xyz) && (!v.mono || aligned16(v.mono));
+    const bool vec = v.P % 4 == 0 && aligned_to(v.depth, 16) && aligned_to(out_xyz, 16) && (!v.mono || aligned_to(v.mono, 16));
     const dim3 grid(scene_nchunks(v.P), v.N), block(STPB);
 #define A3R_SCENE_LAUNCH(MONOV, VECV) \
     hipLaunchKernelGGL((scene_points_kernel<MONOV, VECV>), grid, block, 0, st, v, out_xyz, v.img_xf, v.imw, v.imarea)
@@ -546,16 +516,16 @@ static int scene_count(a3r_align_t a, const char* who, const float* conf, float 
     const size_t need = a3r_align_scene_workspace_bytes(v->N, v->P);
     A3R_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
     A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "%s: workspace must be 4-byte aligned", who);
-    *vec = v->P % 4 == 0 && aligned16(v->depth) && aligned16(conf) && (!v->mono || aligned16(v->mono)) && (!dyn || aligned16(dyn)) &&
-           (!rgb || aligned16(rgb));
+    *vec = v->P % 4 == 0 && aligned_to(v->depth, 16) && aligned_to(conf, 16) && (!v->mono || aligned_to(v->mono, 16)) && (!dyn || aligned_to(dyn, 16)) &&
+           (!rgb || aligned_to(rgb, 16));
     s->conf = conf; s->dyn = dyn; s->rgb = rgb; s->thr = thr; s->offsets = static_cast<int*>(workspace);
     s->out_xyz = nullptr; s->out_rgb = nullptr; s->out_index = nullptr; s->rank = nullptr;
     const int nch = scene_nchunks(v->P), T = v->N * nch;
     launch_compact<false>(*v, *s, *vec, st);
-    hipLaunchKernelGGL(scene_scan_kernel, dim3(1), dim3(SCAN_TPB), 0, st, s->offsets, T, v->N, nch, counts_dev);
+    compact_scan(s->offsets, T, st, v->N, nch, counts_dev);
     A3R_LAUNCH_CHECK();
     int total_i = 0;
-    A3R_HIP(hipMemcpyAsync(&total_i, s->offsets + T, sizeof(int), hipMemcpyDeviceToHost, st));
+    A3R_HIP(compact_read_total(s->offsets, T, &total_i, st));
     A3R_HIP(hipStreamSynchronize(st));
     *total = total_i;
     return A3R_OK;
@@ -599,12 +569,10 @@ extern "C" int a3r_align_scene_export(a3r_align_t a, const float* conf, float th
 }
 
 // mesh workspace: vertex offsets [T + 1] | face offsets [4 T + 1] | rank map [N, P], each part rounded up to 256 bytes (T = N * nchunks)
-static size_t mesh_voff_bytes(int N, int P) { return align_up(((size_t)N * scene_nchunks(P) + 1) * sizeof(int), 256); }
-static size_t mesh_foff_bytes(int N, int P) { return align_up(((size_t)4 * N * scene_nchunks(P) + 1) * sizeof(int), 256); }
-
 extern "C" size_t a3r_align_scene_mesh_workspace_bytes(int N, int P) {
     if (N <= 0 || P <= 0) return 0;
-    return mesh_voff_bytes(N, P) + mesh_foff_bytes(N, P) + align_up((size_t)N * P * sizeof(int), 256);
+    const size_t T = (size_t)N * scene_nchunks(P);
+    return compact_offsets_bytes(T) + compact_offsets_bytes(4 * T) + align_up((size_t)N * P * sizeof(int), 256);
 }
 
 template <bool WRITE>
@@ -627,27 +595,26 @@ static int mesh_count(a3r_align_t a, const char* who, const float* conf, float t
     A3R_CHECK_ARG((size_t)nblk * v->N * v->P < (1ull << 31), "%s: up to %d * N * P = %zu faces do not fit the int32 face offsets", who, nblk,
                   (size_t)nblk * v->N * v->P);
     const size_t need = a3r_align_scene_mesh_workspace_bytes(v->N, v->P);
-    A3R_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
-    A3R_CHECK_ARG(aligned16(workspace), "%s: workspace must be 16-byte aligned", who);
-    *vec = v->P % 4 == 0 && aligned16(v->depth) && aligned16(conf) && (!v->mono || aligned16(v->mono)) && (!dyn || aligned16(dyn)) &&
-           (!rgb || aligned16(rgb));
+    if (int rc = check_workspace(who, workspace, workspace_bytes, need)) return rc;
+    *vec = v->P % 4 == 0 && aligned_to(v->depth, 16) && aligned_to(conf, 16) && (!v->mono || aligned_to(v->mono, 16)) && (!dyn || aligned_to(dyn, 16)) &&
+           (!rgb || aligned_to(rgb, 16));
+    const int nch = scene_nchunks(v->P), T = v->N * nch, TF = T * nblk;
     char* ws = static_cast<char*>(workspace);
     int* voff = reinterpret_cast<int*>(ws);
-    int* foff = reinterpret_cast<int*>(ws + mesh_voff_bytes(v->N, v->P));
-    int* rank = reinterpret_cast<int*>(ws + mesh_voff_bytes(v->N, v->P) + mesh_foff_bytes(v->N, v->P));
+    int* foff = reinterpret_cast<int*>(ws + compact_offsets_bytes(T));
+    int* rank = reinterpret_cast<int*>(ws + compact_offsets_bytes(T) + compact_offsets_bytes(4 * (size_t)T));
     s->conf = conf; s->dyn = dyn; s->rgb = rgb; s->thr = thr; s->offsets = voff;
     s->out_xyz = nullptr; s->out_rgb = nullptr; s->out_index = nullptr; s->rank = rank;
     m->rank = rank; m->voff = voff; m->foff = foff; m->rgb = nullptr; m->out_faces = nullptr; m->out_rgb = nullptr;
     m->P = v->P; m->nblk = nblk;
-    const int nch = scene_nchunks(v->P), T = v->N * nch, TF = T * nblk;
     launch_compact<false>(*v, *s, *vec, st);
-    hipLaunchKernelGGL(scene_scan_kernel, dim3(1), dim3(SCAN_TPB), 0, st, voff, T, v->N, nch, static_cast<int*>(nullptr));
+    compact_scan(voff, T, st);
     launch_faces<false>(*v, *m, st);
-    hipLaunchKernelGGL(scene_scan_kernel, dim3(1), dim3(SCAN_TPB), 0, st, foff, TF, v->N, nblk * nch, static_cast<int*>(nullptr));
+    compact_scan(foff, TF, st);
     A3R_LAUNCH_CHECK();
     int totals[2] = {0, 0};
-    A3R_HIP(hipMemcpyAsync(&totals[0], voff + T, sizeof(int), hipMemcpyDeviceToHost, st));
-    A3R_HIP(hipMemcpyAsync(&totals[1], foff + TF, sizeof(int), hipMemcpyDeviceToHost, st));
+    A3R_HIP(compact_read_total(voff, T, &totals[0], st));
+    A3R_HIP(compact_read_total(foff, TF, &totals[1], st));
     A3R_HIP(hipStreamSynchronize(st));
     *n_vertices = totals[0];
     *n_faces = totals[1];
@@ -721,11 +688,10 @@ extern "C" int a3r_align_scene_clean(a3r_align_t a, float* conf, float tol, floa
     SceneView v;
     if (int rc = align_scene_view(a, st, &v, who)) return rc;
     const size_t need = a3r_align_scene_clean_workspace_bytes(v.N, v.P);
-    A3R_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
-    A3R_CHECK_ARG(aligned16(workspace), "%s: workspace must be 16-byte aligned", who);
+    if (int rc = check_workspace(who, workspace, workspace_bytes, need)) return rc;
     float* cam = static_cast<float*>(workspace);
     float* dense = reinterpret_cast<float*>(static_cast<char*>(workspace) + clean_cam_bytes(v.N));
-    const bool vec = v.P % 4 == 0 && aligned16(v.depth) && aligned16(conf) && (!v.mono || aligned16(v.mono));
+    const bool vec = v.P % 4 == 0 && aligned_to(v.depth, 16) && aligned_to(conf, 16) && (!v.mono || aligned_to(v.mono, 16));
     const float keep_frac = (float)(1.0 - (double)tol);
     const int nch = scene_nchunks(v.P);
 #define A3R_SCENE_LAUNCH(MONOV, VECV)                                                                                                      \

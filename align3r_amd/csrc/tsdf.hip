@@ -21,10 +21,10 @@
 //
 // Surface: cells of 2 x 2 x 2 voxels whose corners are all observed (wsum >= min_weight) and differ in sign carry one vertex, the
 // mean of the zero crossings of the cell's edges; a grid edge whose ends differ in sign carries a quad between the vertices of its
-// four cells.  Compaction as in scene.hip: a count pass by wave ballots that leaves a rank map, the scan of scan.h, a placement
-// pass; vertex ids are the ranks of the active cells in linear order, faces are ordered by (voxel, axis).
+// four cells.  Compaction by the count / scan / place scheme of compact.h, the count pass leaving a rank map; vertex ids are
+// the ranks of the active cells in linear order, faces are ordered by (voxel, axis).
 #include "common.h"
-#include "scan.h"
+#include "compact.h"
 #include <cmath>
 
 namespace a3r {
@@ -239,30 +239,6 @@ __device__ __forceinline__ bool tsdf_cell_active(const TsdfMesh& m, int i, int j
     return observed && any_in && any_out;
 }
 
-// the rank of a thread's flagged items among the workgroup's, in (thread, item) order, and the workgroup's total
-template <int ITEMS>
-__device__ __forceinline__ void tsdf_block_rank(const bool (&flag)[ITEMS], int* wave_total, int& first, int& total) {
-    const int tid = threadIdx.x, wave = tid >> 6;
-    int below = 0, in_wave = 0;
-#pragma unroll
-    for (int q = 0; q < ITEMS; q++) {
-        const unsigned long long b = __ballot(flag[q]);
-        below += __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-        in_wave += __popcll(b);
-    }
-    if ((tid & 63) == 0) wave_total[wave] = in_wave;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < TS_TPB / 64; w++) {
-        const int t = wave_total[w];
-        if (w < wave) before += t;
-        total += t;
-    }
-    first = before + below;
-}
-
 // grid (T).  WRITE = false: rank[l] = the cell's rank inside the chunk or -1, voff[chunk] = active cells of the chunk.
 // WRITE = true: the vertex of every active cell goes to row voff[chunk] + rank.
 template <bool WRITE>
@@ -282,7 +258,7 @@ __global__ __launch_bounds__(TS_TPB) void tsdf_cells_kernel(TsdfMesh m) {
         }
     }
     int first, total;
-    tsdf_block_rank<TM_PPT>(act, wave_total, first, total);
+    block_rank<TS_TPB, TM_PPT>(act, wave_total, &first, &total);
     if (!WRITE) {
         if (threadIdx.x == 0) m.voff[blockIdx.x] = total;
         int r = first;
@@ -363,7 +339,7 @@ __global__ __launch_bounds__(TS_TPB) void tsdf_faces_kernel(TsdfMesh m) {
         }
     }
     int first, total;
-    tsdf_block_rank<TM_PPT * 3>(quad, wave_total, first, total);
+    block_rank<TS_TPB, TM_PPT * 3>(quad, wave_total, &first, &total);
     if (!WRITE) {
         if (threadIdx.x == 0) m.foff[blockIdx.x] = total;
         return;
@@ -397,7 +373,7 @@ static long long tsdf_nvox(int nx, int ny, int nz) {
     return xy * nz >= (1ll << 31) ? 1ll << 31 : xy * nz;    // xy * nz below 2^62
 }
 static long long tsdf_nchunks(long long nvox) { return (nvox + TM_CHUNK - 1) / TM_CHUNK; }
-static size_t tsdf_off_bytes(long long nvox) { return align_up(((size_t)tsdf_nchunks(nvox) + 1) * sizeof(int), 256); }
+static size_t tsdf_off_bytes(long long nvox) { return compact_offsets_bytes((size_t)tsdf_nchunks(nvox)); }
 
 }  // namespace a3r
 
@@ -478,8 +454,7 @@ static int tsdf_mesh_count(const char* who, const float* tsdf, const float* wsum
     A3R_CHECK_ARG(min_weight > 0 && min_weight < INFINITY, "%s: min_weight = %g must be finite and positive", who, min_weight);
     A3R_CHECK_ARG(tsdf && wsum, "%s: null tsdf / wsum", who);
     const size_t need = a3r_tsdf_mesh_workspace_bytes(nx, ny, nz);
-    A3R_CHECK_ARG(ws && ws_bytes >= need, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
-    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: workspace must be 16-byte aligned", who);
+    if (int rc = check_workspace(who, ws, ws_bytes, need)) return rc;
     char* p = static_cast<char*>(ws);
     m->tsdf = tsdf; m->wsum = wsum; m->min_weight = min_weight; m->nvox = nvox;
     m->voff = reinterpret_cast<int*>(p);   p += tsdf_off_bytes(nvox);
@@ -489,12 +464,12 @@ static int tsdf_mesh_count(const char* who, const float* tsdf, const float* wsum
     const dim3 grid(T), tpb(TS_TPB);
     hipLaunchKernelGGL((tsdf_cells_kernel<false>), grid, tpb, 0, st, *m);
     hipLaunchKernelGGL((tsdf_faces_kernel<false>), grid, tpb, 0, st, *m);
-    hipLaunchKernelGGL(scene_scan_kernel, dim3(1), dim3(SCAN_TPB), 0, st, m->voff, T, 0, 0, static_cast<int*>(nullptr));
-    hipLaunchKernelGGL(scene_scan_kernel, dim3(1), dim3(SCAN_TPB), 0, st, m->foff, T, 0, 0, static_cast<int*>(nullptr));
+    compact_scan(m->voff, T, st);
+    compact_scan(m->foff, T, st);
     A3R_LAUNCH_CHECK();
     int nv = 0, nq = 0;
-    A3R_HIP(hipMemcpyAsync(&nv, m->voff + T, sizeof(int), hipMemcpyDeviceToHost, st));
-    A3R_HIP(hipMemcpyAsync(&nq, m->foff + T, sizeof(int), hipMemcpyDeviceToHost, st));
+    A3R_HIP(compact_read_total(m->voff, T, &nv, st));
+    A3R_HIP(compact_read_total(m->foff, T, &nq, st));
     A3R_HIP(hipStreamSynchronize(st));
     *V = nv;
     *F = 2ll * nq;

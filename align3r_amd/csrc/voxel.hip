@@ -17,12 +17,10 @@
 //             best values only decrease, as the renderer's keys do), adds 1 to the count and, in mean mode, its fixed-point offsets
 //             and colours to the slot's sums; otherwise it moves on.  No lock, no wait.  The slot is left in slot[i].  Neighbouring
 //             lanes of a wave that share a key are folded into one lane first (voxel_insert_kernel: COMBINE).
-//   * flag:   point i wins iff best[slot[i]] carries row i and count[slot[i]] >= min_count; a workgroup counts the winners of its
-//             VX_CHUNK consecutive points (wave64 ballots), the scan of scan.h turns the counts into offsets, the same kernel
-//             with WRITE places the winners: rank = offset[chunk] + winners of lower waves + of lower lanes + the thread's own
-//             earlier ones, i.e. ascending row.
+//   * flag:   point i wins iff best[slot[i]] carries row i and count[slot[i]] >= min_count; the winners are compacted by the
+//             count / scan / place scheme of compact.h over chunks of VX_CHUNK consecutive points, i.e. in ascending row.
 #include "common.h"
-#include "scan.h"
+#include "compact.h"
 #include <cmath>
 
 namespace a3r {
@@ -208,7 +206,7 @@ struct VoxelOut {
 template <bool WRITE, bool MEAN>
 __global__ __launch_bounds__(VX_TPB) void voxel_compact_kernel(VoxelTable t, int M, unsigned min_count, VoxelOut o) {
     __shared__ int wave_total[VX_TPB / 64];
-    const int tid = threadIdx.x, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const long long p0 = (long long)blockIdx.x * VX_CHUNK + tid * VX_PPT;
     unsigned s[VX_PPT], cnt[VX_PPT];
     if (p0 + VX_PPT <= M) {         // the slot array is 16-byte aligned and p0 a multiple of 4
@@ -227,30 +225,16 @@ __global__ __launch_bounds__(VX_TPB) void voxel_compact_kernel(VoxelTable t, int
             keep[i] = (unsigned)t.best[s[i]] == (unsigned)(p0 + i) && cnt[i] >= min_count;
         }
     }
-    // rank inside the wave: the threads own consecutive point quads, so the order is (lane, i)
-    int below = 0, in_wave = 0;
-#pragma unroll
-    for (int i = 0; i < VX_PPT; i++) {
-        const unsigned long long b = __ballot(keep[i]);
-        below += __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-        in_wave += __popcll(b);
-    }
-    if ((tid & 63) == 0) wave_total[wave] = in_wave;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < VX_TPB / 64; k++) {
-        const int w = wave_total[k];
-        if (k < wave) before += w;
-        total += w;
-    }
+    // the threads own consecutive point quads, so the order is (thread, i)
+    int first, total;
+    block_rank<VX_TPB, VX_PPT>(keep, wave_total, &first, &total);
     if (!WRITE) {
         if (tid == 0) t.offsets[blockIdx.x] = total;
         return;
     }
     // the count pass saw the same table, so these are its ranks; stay inside the chunk's range whatever the workspace holds
     const long long end = t.offsets[blockIdx.x + 1];
-    long long l = (long long)t.offsets[blockIdx.x] + before + below;
+    long long l = (long long)t.offsets[blockIdx.x] + first;
 #pragma unroll
     for (int i = 0; i < VX_PPT; i++) {
         if (!keep[i] || l >= end) continue;
@@ -299,7 +283,7 @@ static bool voxel_sizes_ok(long long M, long long slots, int reduce) {
 // head | offsets [nchunks + 1] | slot [M] | keys [slots] | best [slots] | count [slots] | sums [slots, 6] (mean), each part rounded
 // up to 256 bytes
 static size_t voxel_head_bytes() { return 256; }
-static size_t voxel_offsets_bytes(long long M) { return align_up(((size_t)voxel_nchunks(M) + 1) * sizeof(int), 256); }
+static size_t voxel_offsets_bytes(long long M) { return compact_offsets_bytes((size_t)voxel_nchunks(M)); }
 static size_t voxel_slot_bytes(long long M) { return align_up((size_t)M * sizeof(unsigned), 256); }
 
 }  // namespace a3r
@@ -331,8 +315,7 @@ static int voxel_count(const char* who, const float* xyz, const float* priority,
     A3R_CHECK_ARG(slots <= VX_MAX_SLOTS, "%s: slots = %lld is above 2^31", who, slots);
     A3R_CHECK_ARG(xyz || M == 0, "%s: null xyz", who);
     const size_t need = a3r_voxel_workspace_bytes(M, slots, reduce);
-    A3R_CHECK_ARG(ws && ws_bytes >= need, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
-    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: workspace must be 16-byte aligned", who);
+    if (int rc = check_workspace(who, ws, ws_bytes, need)) return rc;
     *n_voxels = 0;
     *dropped = 0;
     if (M == 0) return A3R_OK;
@@ -362,12 +345,12 @@ static int voxel_count(const char* who, const float* xyz, const float* priority,
 #undef A3R_VX_INSERT_MODE
 #undef A3R_VX_INSERT
     hipLaunchKernelGGL((voxel_compact_kernel<false, false>), dim3(T), tpb, 0, st, *t, (int)M, (unsigned)min_count, VoxelOut{});
-    hipLaunchKernelGGL(scene_scan_kernel, dim3(1), dim3(SCAN_TPB), 0, st, t->offsets, T, 0, 0, static_cast<int*>(nullptr));
+    compact_scan(t->offsets, T, st);
     A3R_LAUNCH_CHECK();
     unsigned head[2] = {0u, 0u};
     int total = 0;
     A3R_HIP(hipMemcpyAsync(head, t->head, sizeof(head), hipMemcpyDeviceToHost, st));
-    A3R_HIP(hipMemcpyAsync(&total, t->offsets + T, sizeof(int), hipMemcpyDeviceToHost, st));
+    A3R_HIP(compact_read_total(t->offsets, T, &total, st));
     A3R_HIP(hipStreamSynchronize(st));
     if (head[0] != 0u) {
         set_error("%s: a probe walked all %lld slots without finding a free one (the table was not the one this call filled)", who, slots);
