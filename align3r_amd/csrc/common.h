@@ -71,6 +71,8 @@ struct PerDeviceOnce {
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }      // a: a power of two
+template <class... P>
+inline bool all_aligned16(const P*... p) { return (aligned_to(p, 16) && ...); }      // every pointer (null counts as aligned)
 
 // the workspace argument of an entry that needs `need` bytes of it, 16-byte aligned
 inline int check_workspace(const char* who, const void* ws, size_t ws_bytes, size_t need) {

@@ -223,9 +223,7 @@ int frame_cache_store(const float* img1, const float* img2, int B, const void* k
 // (miss[k] >= 0, ent[k] >= 0), then raised to the largest word of the entries it read (miss[k] < 0).
 int stats_sites_words(unsigned* estats, int cap, const int32_t* ent, const int32_t* miss, int U, unsigned* stats, const SiteMask& sites,
                       void* stream);
-// a3r_gather_add_rows whose rows a come from two places (a3r.h: a3r_gather_add_rows_src is the same with a C signature)
-int gather_add_rows_src(const float* store, long stride, const float* fresh, const int32_t* src, const float* b, const int32_t* map_b,
-                        float* dst, int S, int N, int C, void* stream);
+// (the gather-add pass that reads src is a3r_gather_add_rows_src of a3r.h: a3r_gather_add_rows whose rows a come from two places)
 
 // ---- head products kept across calls (a3r_model_set_head_products): what the DPT head of side s makes from one frame alone -- r0,
 // the output of layer_rn[0], and c, the bias-only output of resConfUnit1's second conv, [16 N, F] fp32 each -- in a third storage
@@ -288,14 +286,9 @@ inline int head_lists(HeadBits& bits, int s, const int32_t* ent, const int32_t* 
 // go to side s of that entry.
 int head_products_store(const HeadStore& st, int s, const int32_t* hent, const int32_t* hmiss, int U, const float* r0, const float* c,
                         void* stream);
-// combine_resid_fh2 / upsample2x_combine_fh2 (below) whose c and r0 come from two places: src[b] >= 0 names an entry of the
-// storage, whose blocks lie `stride` floats apart from store_c / store_r0, src[b] < 0 the fresh block ~src[b] of c / r0
-// (a3r.h: a3r_combine_resid_fh2_src, a3r_upsample2x_combine_fh2_src)
-int combine_resid_fh2_src(const float* c, const float* r0, const float* store_c, const float* store_r0, long stride, const int32_t* src,
-                          const float* p2, float* s, void* sr2, int S, long P, int C, float scale, unsigned* absmax, void* stream);
-int upsample2x_combine_fh2_src(const float* x, const float* c, const float* r0, const float* store_c, const float* store_r0, long stride,
-                               const int32_t* src, float* s, void* sr2, int S, int H, int W, int C, int Hc, int Wc, float scale,
-                               unsigned* absmax, void* stream);
+// The combine passes of a side whose c and r0 come from two places (a3r.h: a3r_combine_resid_fh2_src,
+// a3r_upsample2x_combine_fh2_src) read head_lists' src: src[b] >= 0 names an entry of the storage, whose blocks lie `stride`
+// floats apart from store_c / store_r0 (HeadStore::c, r0, stride), src[b] < 0 the fresh block ~src[b] of c / r0.
 
 // ---- device side (dedup.hip).  An item of the first kind is one image [3, H, W] -- or, for the decode call, one frame's encoder
 // features [N, E] --, one of the second kind a pred_depth map [H, W, 3]: words_a / words_pd 32-bit words each, multiples of 4.  Slot s < 4 B of a call is item s % B of group s / B, the groups being img1, img2, pd1, pd2; slots 0 .. 2 B - 1
@@ -318,12 +311,8 @@ int patchify_indexed(const float* img_a, const float* img_b, const int32_t* uniq
 int gather_rows(const float* src, float* dst, const int32_t* map, int S, int N, int C, void* stream);
 // whether a3r_attention_fh2_mapped runs the kernel form that takes image maps (attention_fh2.hip; not under A3R_ATTN=v1)
 bool attention_fh2_takes_maps();
-// The second conv of refinenet1.resConfUnit1 on distinct frames (a3r.h: a3r_combine_resid_fh2 is the same with a C signature)
-int combine_resid_fh2(const float* c, const float* r0, const float* p2, const int32_t* map, float* s, void* sr2, int S, long P, int C,
-                      float scale, unsigned* absmax, void* stream);
-// the same with p2 = the bilinear 2x (a3r_upsample2x, cropped to Hc x Wc) of x [S, H, W, C] made on the fly; P = Hc Wc
-int upsample2x_combine_fh2(const float* x, const float* c, const float* r0, const int32_t* map, float* s, void* sr2, int S, int H, int W,
-                           int C, int Hc, int Wc, float scale, unsigned* absmax, void* stream);
+// (the second conv of refinenet1.resConfUnit1 on distinct frames is a3r_combine_resid_fh2 of a3r.h, or a3r_upsample2x_combine_fh2
+// with its residual, the bilinear 2x of x cropped to Hc x Wc, made on the fly)
 
 // ---- the lists of one call.  Every list the host builds, in the order they lie in memory: one block of DD_HALF-word lists, which
 // the host fills (pinned words) and one upload copies to the device; both blocks are viewed through this struct, so a member of

@@ -12,6 +12,38 @@
 
 namespace a3r {
 
+// ------------------------------------------------------------------------------------------- pieces the kernels below share
+// The sum and the sum of squares of a float4, added left to right, and LayerNorm's affine step.  The products of sumsq4 are not
+// fused into its sums and the affine step is an explicit fma (contraction is off here as in every kernel that calls these): the
+// output forms of one operator must round identically (bf3 / fh2 output == split of the fp32 output, tested).
+__device__ __forceinline__ float sum4(f32x4 v) { return v.x + v.y + v.z + v.w; }
+__device__ __forceinline__ float sumsq4(f32x4 v) {
+#pragma clang fp contract(off)
+    return v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+}
+__device__ __forceinline__ f32x4 ln_affine4(f32x4 v, float rstd, f32x4 wv, f32x4 bv) {
+#pragma clang fp contract(off)
+    const f32x4 t = v * rstd;
+    return f32x4{__builtin_fmaf(t.x, wv.x, bv.x), __builtin_fmaf(t.y, wv.y, bv.y), __builtin_fmaf(t.z, wv.z, bv.z),
+                 __builtin_fmaf(t.w, wv.w, bv.w)};
+}
+// The tail of an fh2 producer for one 8-k group: scale, range statistics, the two planes' 16-byte units.
+__device__ __forceinline__ void fh2_emit8(char* row, int k0, f32x4 lo, f32x4 hi, float scale, float& amax) {
+    lo = lo * scale;
+    hi = hi * scale;
+    amax = fh2_amax4(fh2_amax4(amax, lo), hi);
+    fh2_store8(row, k0, lo, hi);
+}
+// The residual combine for one float4 (combine_resid_fh2_kernel below): v = c + (r0 + p2), the epilogue's order of additions, goes
+// to *s; relu(v) * scale, which enters the range statistics, is returned for the caller's fh2_store8.
+__device__ __forceinline__ f32x4 combine_emit(f32x4 c, f32x4 r0, f32x4 p2, f32x4* s, float scale, float& amax) {
+    const f32x4 v = c + (r0 + p2);
+    *s = v;
+    const f32x4 o = f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)} * scale;
+    amax = fh2_amax4(amax, o);
+    return o;
+}
+
 // ------------------------------------------------------------------------------------------- LayerNorm
 // nn.LayerNorm(D, eps) (croco.py:34; blocks.py:118-123,180-185): one wave per row, row kept in registers.
 // BF3: write the normalised row in bf3 form (bf3.h) instead of fp32 -- the input format of gemm_bf3.hip.
@@ -28,14 +60,14 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 #pragma unroll
     for (int i = 0; i < VPL; i++) {
         v[i] = xr[lane + 64 * i];
-        s += v[i].x + v[i].y + v[i].z + v[i].w;
+        s += sum4(v[i]);
     }
     const float mean = wave_sum(s) / (float)D;
     float ss = 0.f;
 #pragma unroll
     for (int i = 0; i < VPL; i++) {
         v[i] = v[i] - mean;
-        ss += v[i].x * v[i].x + v[i].y * v[i].y + v[i].z * v[i].z + v[i].w * v[i].w;
+        ss += sumsq4(v[i]);
     }
     const float rstd = 1.f / sqrtf(wave_sum(ss) / (float)D + eps);
     f32x4* yr = reinterpret_cast<f32x4*>(y + (size_t)row * D);
@@ -44,10 +76,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     char* y3 = reinterpret_cast<char*>(y) + bf3_row_offset(row, D, pair);
 #pragma unroll
     for (int i = 0; i < VPL; i++) {
-        // explicit fma: the fp32 and the bf3 instantiation must round identically (bf3 output == split of the fp32 output, tested)
-        const f32x4 t = v[i] * rstd, wv = wr[lane + 64 * i], bv = br[lane + 64 * i];
-        const f32x4 o = {__builtin_fmaf(t.x, wv.x, bv.x), __builtin_fmaf(t.y, wv.y, bv.y), __builtin_fmaf(t.z, wv.z, bv.z),
-                         __builtin_fmaf(t.w, wv.w, bv.w)};
+        const f32x4 o = ln_affine4(v[i], rstd, wr[lane + 64 * i], br[lane + 64 * i]);
         if (BF3) bf3_store4(y3, (lane + 64 * i) * 4, o, pair);
         else yr[lane + 64 * i] = o;
     }
@@ -79,8 +108,8 @@ __global__ __launch_bounds__(256) void layernorm_pair_kernel(const float* __rest
     }
 #pragma unroll
     for (int i = 0; i < VPL; i++) {
-        s0 += v0[i].x + v0[i].y + v0[i].z + v0[i].w;
-        s1 += v1[i].x + v1[i].y + v1[i].z + v1[i].w;
+        s0 += sum4(v0[i]);
+        s1 += sum4(v1[i]);
     }
     const float mean0 = wave_sum(s0) / (float)D, mean1 = wave_sum(s1) / (float)D;
     float ss0 = 0.f, ss1 = 0.f;
@@ -88,8 +117,8 @@ __global__ __launch_bounds__(256) void layernorm_pair_kernel(const float* __rest
     for (int i = 0; i < VPL; i++) {
         v0[i] = v0[i] - mean0;
         v1[i] = v1[i] - mean1;
-        ss0 += v0[i].x * v0[i].x + v0[i].y * v0[i].y + v0[i].z * v0[i].z + v0[i].w * v0[i].w;
-        ss1 += v1[i].x * v1[i].x + v1[i].y * v1[i].y + v1[i].z * v1[i].z + v1[i].w * v1[i].w;
+        ss0 += sumsq4(v0[i]);
+        ss1 += sumsq4(v1[i]);
     }
     const float rstd0 = 1.f / sqrtf(wave_sum(ss0) / (float)D + eps), rstd1 = 1.f / sqrtf(wave_sum(ss1) / (float)D + eps);
     const f32x4* wr = reinterpret_cast<const f32x4*>(w);
@@ -99,13 +128,8 @@ __global__ __launch_bounds__(256) void layernorm_pair_kernel(const float* __rest
     for (int i = 0; i < VPL; i++) {
         char* img = img_all[wave][i & 1];
         const f32x4 wv = wr[lane + 64 * i], bv = br[lane + 64 * i];
-        const f32x4 t0 = v0[i] * rstd0, t1 = v1[i] * rstd1;
-        const f32x4 o0 = {__builtin_fmaf(t0.x, wv.x, bv.x), __builtin_fmaf(t0.y, wv.y, bv.y), __builtin_fmaf(t0.z, wv.z, bv.z),
-                          __builtin_fmaf(t0.w, wv.w, bv.w)};
-        const f32x4 o1 = {__builtin_fmaf(t1.x, wv.x, bv.x), __builtin_fmaf(t1.y, wv.y, bv.y), __builtin_fmaf(t1.z, wv.z, bv.z),
-                          __builtin_fmaf(t1.w, wv.w, bv.w)};
-        bf3_store4(img, lane * 4, o0, 1);                                      // row parity 0: offset 0 of every 384-byte k block
-        bf3_store4(img + 192, lane * 4, o1, 1);                                // row parity 1: + 192
+        bf3_store4(img, lane * 4, ln_affine4(v0[i], rstd0, wv, bv), 1);        // row parity 0: offset 0 of every 384-byte k block
+        bf3_store4(img + 192, lane * 4, ln_affine4(v1[i], rstd1, wv, bv), 1);  // row parity 1: + 192
         __builtin_amdgcn_s_waitcnt(0xc07f);                                    // lgkmcnt(0): the image is wave-private
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -137,7 +161,7 @@ __global__ __launch_bounds__(256) void layernorm_fh2_kernel(const float* __restr
         const bool in = lane + 64 * i < G;
         v[i][0] = in ? xr[2 * (lane + 64 * i)] : f32x4{0.f, 0.f, 0.f, 0.f};
         v[i][1] = in ? xr[2 * (lane + 64 * i) + 1] : f32x4{0.f, 0.f, 0.f, 0.f};
-        s += (v[i][0].x + v[i][0].y + v[i][0].z + v[i][0].w) + (v[i][1].x + v[i][1].y + v[i][1].z + v[i][1].w);
+        s += sum4(v[i][0]) + sum4(v[i][1]);
     }
     const float mean = wave_sum(s) / (float)D;
     float ss = 0.f;
@@ -147,7 +171,7 @@ __global__ __launch_bounds__(256) void layernorm_fh2_kernel(const float* __restr
 #pragma unroll
         for (int h = 0; h < 2; h++) {
             v[i][h] = v[i][h] - mean;
-            if (in) ss += v[i][h].x * v[i][h].x + v[i][h].y * v[i][h].y + v[i][h].z * v[i][h].z + v[i][h].w * v[i][h].w;
+            if (in) ss += sumsq4(v[i][h]);
         }
     }
     const float rstd = 1.f / sqrtf(wave_sum(ss) / (float)D + eps);
@@ -161,9 +185,7 @@ __global__ __launch_bounds__(256) void layernorm_fh2_kernel(const float* __restr
 #pragma unroll
         for (int h = 0; h < 2; h++) {
             const int c = 2 * (lane + 64 * i) + h;
-            const f32x4 t = v[i][h] * rstd, wv = wr[c], bv = br[c];
-            o[h] = f32x4{__builtin_fmaf(t.x, wv.x, bv.x), __builtin_fmaf(t.y, wv.y, bv.y), __builtin_fmaf(t.z, wv.z, bv.z),
-                         __builtin_fmaf(t.w, wv.w, bv.w)} * scale;
+            o[h] = ln_affine4(v[i][h], rstd, wr[c], br[c]) * scale;
             if (STATS) amax = fh2_amax4(amax, o[h]);
         }
         fh2_store8(yr, (lane + 64 * i) * 8, o[0], o[1]);
@@ -174,60 +196,50 @@ __global__ __launch_bounds__(256) void layernorm_fh2_kernel(const float* __restr
         fh2_publish_block(absmax, amax, s_red);
     }
 }
-// any D % 32 == 0: lanes stride over the row's 8-k groups (three passes over an L1/L2-resident row)
-__global__ __launch_bounds__(256) void layernorm_fh2_generic_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                                     const float* __restrict__ b, char* __restrict__ y2, int M, int D, float eps,
-                                                                     float scale, unsigned* __restrict__ absmax) {
+// generic fallback, one wave per row, three passes over an L1/L2-resident row.  FMT 0: fp32 (any D % 4 == 0), 1: bf3 (D % 8 == 0),
+// 2: fh2 (D % 32 == 0: lanes stride over the row's 8-k groups).  The rows loop is the persistent one of layernorm_fh2_kernel; the
+// fp32 and bf3 launches have a workgroup per four rows, so it runs once there.
+template <int FMT>
+__global__ __launch_bounds__(256) void layernorm_generic_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                 const float* __restrict__ b, void* __restrict__ y, int M, int D, float eps,
+                                                                 int pair, float scale, unsigned* __restrict__ absmax) {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x & 63;
     float amax = 0.f;
     for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < M; row += gridDim.x * 4) {
-    const float* xr = x + (size_t)row * D;
-    float s = 0.f;
-    for (int i = lane; i < D; i += 64) s += xr[i];
-    const float mean = wave_sum(s) / (float)D;
-    float ss = 0.f;
-    for (int i = lane; i < D; i += 64) { const float c = xr[i] - mean; ss += c * c; }
-    const float rstd = 1.f / sqrtf(wave_sum(ss) / (float)D + eps);
-    char* yr = y2 + (size_t)row * fh2_row_bytes(D);
-    for (int k0 = lane * 8; k0 < D; k0 += 512) {
-        f32x4 o[2];
+        const float* xr = x + (size_t)row * D;
+        float s = 0.f;
+        for (int i = lane; i < D; i += 64) s += xr[i];
+        const float mean = wave_sum(s) / (float)D;
+        float ss = 0.f;
+        for (int i = lane; i < D; i += 64) { const float c = xr[i] - mean; ss += c * c; }
+        const float rstd = 1.f / sqrtf(wave_sum(ss) / (float)D + eps);
+        auto out = [&](int k) { return __builtin_fmaf((xr[k] - mean) * rstd, w[k], b[k]); };
+        if (FMT == 2) {
+            char* yr = static_cast<char*>(y) + (size_t)row * fh2_row_bytes(D);
+            for (int k0 = lane * 8; k0 < D; k0 += 512) {
+                f32x4 o[2];
 #pragma unroll
-        for (int j = 0; j < 8; j++) o[j >> 2][j & 3] = __builtin_fmaf((xr[k0 + j] - mean) * rstd, w[k0 + j], b[k0 + j]) * scale;
-        amax = fh2_amax4(fh2_amax4(amax, o[0]), o[1]);
-        fh2_store8(yr, k0, o[0], o[1]);
-    }
-    }
-    __shared__ unsigned s_red[4];
-    fh2_publish_block(absmax, amax, s_red);
-}
-
-// generic fallback (any D % 4 == 0; D % 8 == 0 for BF3): one wave per row, three passes over an L1/L2-resident row
-template <bool BF3>
-__global__ __launch_bounds__(256) void layernorm_generic_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                                 const float* __restrict__ b, float* __restrict__ y, int M,
-                                                                 int D, float eps, int pair) {
-#pragma clang fp contract(off)
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= M) return;
-    const float* xr = x + (size_t)row * D;
-    float s = 0.f;
-    for (int i = lane; i < D; i += 64) s += xr[i];
-    const float mean = wave_sum(s) / (float)D;
-    float ss = 0.f;
-    for (int i = lane; i < D; i += 64) { const float c = xr[i] - mean; ss += c * c; }
-    const float rstd = 1.f / sqrtf(wave_sum(ss) / (float)D + eps);
-    if (BF3) {
-        char* y3 = reinterpret_cast<char*>(y) + bf3_row_offset(row, D, pair);
-        for (int i = lane * 4; i < D; i += 256) {
-            f32x4 o;
+                for (int j = 0; j < 8; j++) o[j >> 2][j & 3] = out(k0 + j) * scale;
+                amax = fh2_amax4(fh2_amax4(amax, o[0]), o[1]);
+                fh2_store8(yr, k0, o[0], o[1]);
+            }
+        } else if (FMT == 1) {
+            char* y3 = static_cast<char*>(y) + bf3_row_offset(row, D, pair);
+            for (int i = lane * 4; i < D; i += 256) {
+                f32x4 o;
 #pragma unroll
-            for (int j = 0; j < 4; j++) o[j] = __builtin_fmaf((xr[i + j] - mean) * rstd, w[i + j], b[i + j]);
-            bf3_store4(y3, i, o, pair);
+                for (int j = 0; j < 4; j++) o[j] = out(i + j);
+                bf3_store4(y3, i, o, pair);
+            }
+        } else {
+            float* yr = static_cast<float*>(y) + (size_t)row * D;
+            for (int i = lane; i < D; i += 64) yr[i] = out(i);
         }
-    } else {
-        float* yr = y + (size_t)row * D;
-        for (int i = lane; i < D; i += 64) yr[i] = __builtin_fmaf((xr[i] - mean) * rstd, w[i], b[i]);
+    }
+    if (FMT == 2) {
+        __shared__ unsigned s_red[4];
+        fh2_publish_block(absmax, amax, s_red);
     }
 }
 
@@ -361,13 +373,9 @@ __global__ __launch_bounds__(256) void combine_resid_fh2_kernel(const float* __r
         const long src = ((blk * P + pr) * C8 + kg) * 2, dst = (row * C8 + kg) * 2;      // in float4
         f32x4 o[2];
 #pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const f32x4 v = reinterpret_cast<const f32x4*>(cs)[src + h] +
-                            (reinterpret_cast<const f32x4*>(rs)[src + h] + reinterpret_cast<const f32x4*>(p2)[dst + h]);
-            reinterpret_cast<f32x4*>(s)[dst + h] = v;
-            o[h] = f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)} * scale;
-            amax = fh2_amax4(amax, o[h]);
-        }
+        for (int h = 0; h < 2; h++)
+            o[h] = combine_emit(reinterpret_cast<const f32x4*>(cs)[src + h], reinterpret_cast<const f32x4*>(rs)[src + h],
+                                reinterpret_cast<const f32x4*>(p2)[dst + h], reinterpret_cast<f32x4*>(s) + dst + h, scale, amax);
         fh2_store8(sr2 + row * ((size_t)C8 * 32), kg * 8, o[0], o[1]);
         kg += dk; row += dr; pr += dr;
         if (kg >= C8) { kg -= C8; row++; pr++; }
@@ -406,25 +414,53 @@ __device__ __forceinline__ UpAxis up_axis(float s, int o, int n) {
     return UpAxis{i0, i1, __fsub_rn(1.f, l1), l1};
 }
 
+// The output stage the two kernel forms below share.  o[] = the interpolated float4(s) of output pixel (oy, ox) of slot b, pixel
+// number pix of the output, for the thread's channels, cq its first float4.  FMT 0: fp32, 1: bf3, 2: fh2, 3: fh2 combine -- combine_resid_fh2_kernel inside the
+// producer of its per-slot residual: p2 = o, as FMT 0 computes it (bilerp4: the same rounding order), is neither written nor read
+// back; c, r0 [U, Hc, Wc, C]; s [S, Hc, Wc, C]; y = sr2 its fh2 twin --, 4: the combine with signed sources (CombineSrc).
+template <int FMT>
+__device__ __forceinline__ void up2x_emit(const f32x4* o, float* __restrict__ y, const float* __restrict__ c, const float* __restrict__ r0,
+                                          const int* __restrict__ map, float* __restrict__ s, const CombineSrc& hs, int b, int oy, int ox,
+                                          long pix, int Hc, int Wc, int C4, int cq, float scale, float& amax) {
+    if (FMT == 0) reinterpret_cast<f32x4*>(y)[pix * C4 + cq] = o[0];
+    else if (FMT == 1) bf3_store4(reinterpret_cast<char*>(y) + pix * ((size_t)C4 * 24), cq * 4, o[0]);
+    else {
+        char* row = reinterpret_cast<char*>(y) + pix * ((size_t)C4 * 16);
+        if (FMT == 2) fh2_emit8(row, cq * 4, o[0], o[1], scale, amax);
+        else {
+            const float *__restrict__ cs = c, *__restrict__ rs = r0;
+            const long blk = combine_block<FMT == 4>(hs, map[b], cs, rs);
+            const long src = ((blk * Hc + oy) * Wc + ox) * C4 + cq;
+            f32x4 e[2];
+#pragma unroll
+            for (int q = 0; q < 2; q++)
+                e[q] = combine_emit(reinterpret_cast<const f32x4*>(cs)[src + q], reinterpret_cast<const f32x4*>(rs)[src + q], o[q],
+                                    reinterpret_cast<f32x4*>(s) + pix * C4 + cq + q, scale, amax);
+            fh2_store8(row, cq * 4, e[0], e[1]);
+        }
+    }
+}
+
 // ---- first form (A3R_UP_FORM=v1): one output pixel per thread and step, four corners fetched per output.  The reference of the
 // second form below.
-// FMT 0: fp32, 1: bf3, 2: fh2 output.  Grid: x over (output column, channel group) of one output row, y over (batch, output row):
+// FMT as up2x_emit.  Grid: x over (output column, channel group) of one output row, y over (batch, output row):
 // the row / batch decomposition is scalar work once per workgroup and a thread does ONE 32-bit division (the first version took
 // three 64-bit divisions by runtime values per thread).  A thread produces 4 channels (fp32 / bf3) or 8 channels (fh2: the two
 // planes' 16-byte units of one 8-k group = 32 contiguous bytes, and half the index arithmetic per element -- PMC showed the
 // 4-channel fh2 form VALU-bound at 150 instructions per thread).
 template <int FMT>
-__global__ __launch_bounds__(256) void upsample2x_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int H, int W, int C4,
-                                                         int Hc, int Wc, float scale, unsigned* __restrict__ absmax) {
-    constexpr int Q = FMT == 2 ? 2 : 1;                        // float4 per thread
+__global__ __launch_bounds__(256) void upsample2x_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ c,
+                                                         const float* __restrict__ r0, const int* __restrict__ map, float* __restrict__ s,
+                                                         int B, int H, int W, int C4, int Hc, int Wc, float scale,
+                                                         unsigned* __restrict__ absmax, CombineSrc hs) {
+    constexpr int Q = FMT >= 2 ? 2 : 1;                        // float4 per thread
     const float sh = up_scale(H), sw = up_scale(W);
     const f32x4* xv = reinterpret_cast<const f32x4*>(x);
-    f32x4* yv = reinterpret_cast<f32x4*>(y);
     const unsigned CG = (unsigned)C4 / Q;                      // channel groups per pixel
     const unsigned idx = blockIdx.x * 256u + threadIdx.x;
-    const unsigned ox = idx / CG, c = (idx - ox * CG) * Q;     // c: first float4 of this thread
-    const bool live = ox < (unsigned)Wc;                     // (no early return in the fh2 form: the range statistics need every lane at the end)
-    if (FMT != 2 && !live) return;
+    const unsigned ox = idx / CG, cq = (idx - ox * CG) * Q;    // cq: first float4 of this thread
+    const bool live = ox < (unsigned)Wc;                     // (no early return in the fh2 forms: the range statistics need every lane at the end)
+    if (FMT < 2 && !live) return;
     const UpAxis ax = up_axis(sw, (int)ox, W);
     const int x0 = ax.i0, x1 = ax.i1;
     const float lx0 = ax.l0, lx1 = ax.l1;
@@ -435,68 +471,18 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const float* __restrict
         const int y0 = ay.i0, y1 = ay.i1;
         const float ly0 = ay.l0, ly1 = ay.l1;
         const long rb = (long)b * H;
-        const f32x4* r0 = xv + (rb + y0) * W * C4 + c;
-        const f32x4* r1 = xv + (rb + y1) * W * C4 + c;
+        const f32x4* q0 = xv + (rb + y0) * W * C4 + cq;
+        const f32x4* q1 = xv + (rb + y1) * W * C4 + cq;
         f32x4 o[Q];
 #pragma unroll
         for (int q = 0; q < Q; q++)
-            o[q] = bilerp4(r0[(long)x0 * C4 + q], r0[(long)x1 * C4 + q], r1[(long)x0 * C4 + q], r1[(long)x1 * C4 + q], lx0, lx1, ly0, ly1);
-        const long pix = (long)row * Wc + ox;
-        if (FMT == 1) bf3_store4(reinterpret_cast<char*>(y) + pix * ((size_t)C4 * 24), c * 4, o[0]);
-        else if (FMT == 2) {
-            const f32x4 lo = o[0] * scale, hi = o[Q - 1] * scale;
-            amax = fh2_amax4(fh2_amax4(amax, lo), hi);
-            fh2_store8(reinterpret_cast<char*>(y) + pix * ((size_t)C4 * 16), c * 4, lo, hi);
-        } else yv[pix * C4 + c] = o[0];
+            o[q] = bilerp4(q0[(long)x0 * C4 + q], q0[(long)x1 * C4 + q], q1[(long)x0 * C4 + q], q1[(long)x1 * C4 + q], lx0, lx1, ly0, ly1);
+        up2x_emit<FMT>(o, y, c, r0, map, s, hs, b, oy, (int)ox, (long)row * Wc + ox, Hc, Wc, C4, (int)cq, scale, amax);
     }
-    if (FMT == 2) {
+    if (FMT >= 2) {
         __shared__ unsigned s_red[4];
         fh2_publish_block(absmax, amax, s_red);
     }
-}
-
-// The same combine (combine_resid_fh2_kernel) inside the producer of its per-slot residual: p2 = the bilinear 2x of x, as
-// upsample2x_kernel<0> computes it (bilerp4: the same rounding order), is neither written nor read back.  x [S, H, W, C] fp32;
-// c, r0 [U, Hc, Wc, C]; s [S, Hc, Wc, C]; sr2 its fh2 twin.  Grid and thread layout of upsample2x_kernel<2>.
-template <bool SRC>
-__global__ __launch_bounds__(256) void upsample2x_combine_kernel(const float* __restrict__ x, const float* __restrict__ c,
-                                                                 const float* __restrict__ r0, const int* __restrict__ map,
-                                                                 float* __restrict__ s, char* __restrict__ sr2, int B, int H, int W, int C4,
-                                                                 int Hc, int Wc, float scale, unsigned* __restrict__ absmax, CombineSrc hs) {
-    const float sh = up_scale(H), sw = up_scale(W);
-    const f32x4* xv = reinterpret_cast<const f32x4*>(x);
-    const unsigned CG = (unsigned)C4 / 2;                      // channel groups (of 8) per pixel
-    const unsigned idx = blockIdx.x * 256u + threadIdx.x;
-    const unsigned ox = idx / CG, cg = (idx - ox * CG) * 2;    // cg: first float4 of this thread
-    const bool live = ox < (unsigned)Wc;                     // (no early return: the range statistics need every lane at the end)
-    const UpAxis ax = up_axis(sw, (int)ox, W);
-    const int x0 = ax.i0, x1 = ax.i1;
-    const float lx0 = ax.l0, lx1 = ax.l1;
-    float amax = 0.f;
-    for (int row = blockIdx.y; live && row < B * Hc; row += gridDim.y) {   // (slot, output row): uniform per workgroup
-        const int b = row / Hc, oy = row - b * Hc;
-        const UpAxis ay = up_axis(sh, oy, H);
-        const int y0 = ay.i0, y1 = ay.i1;
-        const float ly0 = ay.l0, ly1 = ay.l1;
-        const long rb = (long)b * H;
-        const f32x4* q0 = xv + (rb + y0) * W * C4 + cg;
-        const f32x4* q1 = xv + (rb + y1) * W * C4 + cg;
-        const float *__restrict__ cs = c, *__restrict__ rs = r0;
-        const long blk = combine_block<SRC>(hs, map[b], cs, rs);
-        const long pix = (long)row * Wc + ox, src = ((blk * Hc + oy) * Wc + ox) * C4 + cg;
-        f32x4 o[2];
-#pragma unroll
-        for (int q = 0; q < 2; q++) {
-            const f32x4 p2 = bilerp4(q0[(long)x0 * C4 + q], q0[(long)x1 * C4 + q], q1[(long)x0 * C4 + q], q1[(long)x1 * C4 + q], lx0, lx1, ly0, ly1);
-            const f32x4 v = reinterpret_cast<const f32x4*>(cs)[src + q] + (reinterpret_cast<const f32x4*>(rs)[src + q] + p2);
-            reinterpret_cast<f32x4*>(s)[pix * C4 + cg + q] = v;
-            o[q] = f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)} * scale;
-            amax = fh2_amax4(amax, o[q]);
-        }
-        fh2_store8(sr2 + pix * ((size_t)C4 * 16), cg * 4, o[0], o[1]);
-    }
-    __shared__ unsigned s_red[4];
-    fh2_publish_block(absmax, amax, s_red);
 }
 
 // ---- second form (default): a thread makes the 2 x 2 output pixels (2 kb - 1, 2 kb) x (2 jb - 1, 2 jb) of its channel group.  With
@@ -506,8 +492,7 @@ __global__ __launch_bounds__(256) void upsample2x_combine_kernel(const float* __
 // output is decided from ITS OWN up_axis, and one that has not (fp32 rounding of the source coordinate on a very large map)
 // fetches its corners as the first form does: indices, weights and bilerp4 are the first form's for every output, bit for bit.
 // The output beyond an edge of the window (-1, Hc, Wc) is skipped and lends its axis to its neighbour.
-// FMT 0: fp32 (4 channels per thread), 2: fh2 (8 channels), 3: fh2 combine (upsample2x_combine_kernel; y = sr2), 4: the combine
-// with signed sources (CombineSrc).
+// FMT as up2x_emit, without the bf3 form: 0 makes 4 channels per thread, 2 to 4 make 8.
 template <int FMT>
 __global__ __launch_bounds__(256) void upsample2x_block_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ c,
                                                                const float* __restrict__ r0, const int* __restrict__ map,
@@ -558,24 +543,7 @@ __global__ __launch_bounds__(256) void upsample2x_block_kernel(const float* __re
                         o[q] = bilerp4(corner(Y.i0, X.i0, q), corner(Y.i0, X.i1, q), corner(Y.i1, X.i0, q), corner(Y.i1, X.i1, q), X.l0, X.l1,
                                        Y.l0, Y.l1);
                 }
-                const long pix = ((long)b * Hc + oy[r]) * Wc + ox[t];
-                if (FMT == 0) reinterpret_cast<f32x4*>(y)[pix * C4 + cq] = o[0];
-                else {
-                    if (FMT >= 3) {
-                        const float *__restrict__ cs = c, *__restrict__ rs = r0;
-                        const long blk = combine_block<FMT == 4>(hs, map[b], cs, rs);
-                        const long src = ((blk * Hc + oy[r]) * Wc + ox[t]) * C4 + cq;
-#pragma unroll
-                        for (int q = 0; q < Q; q++) {
-                            const f32x4 w = reinterpret_cast<const f32x4*>(cs)[src + q] + (reinterpret_cast<const f32x4*>(rs)[src + q] + o[q]);
-                            reinterpret_cast<f32x4*>(s)[pix * C4 + cq + q] = w;
-                            o[q] = f32x4{fmaxf(w.x, 0.f), fmaxf(w.y, 0.f), fmaxf(w.z, 0.f), fmaxf(w.w, 0.f)};
-                        }
-                    }
-                    const f32x4 lo = o[0] * scale, hi = o[Q - 1] * scale;
-                    amax = fh2_amax4(fh2_amax4(amax, lo), hi);
-                    fh2_store8(reinterpret_cast<char*>(y) + pix * ((size_t)C4 * 16), cq * 4, lo, hi);
-                }
+                up2x_emit<FMT>(o, y, c, r0, map, s, hs, b, oy[r], ox[t], ((long)b * Hc + oy[r]) * Wc + ox[t], Hc, Wc, C4, cq, scale, amax);
             }
     }
     if (FMT != 0) {
@@ -705,62 +673,19 @@ static inline int grid_for(long total, int block = 256) {
     return (int)(g < 1 ? 1 : (g > 65536 ? 65536 : g));
 }
 
-// ------------------------------------------------------------------------------------------- weighted Umeyama moments
-// The raw second moments of B weighted point-set pairs (x_b, y_b, w_b), P points each, for the similarity registrations of the
-// aligner's initialisation (cloud_opt/init_im_poses.py:415-418: s R x + T ~ y): per problem and 1024-point chunk 17 doubles
-//   [0] sum w   [1..3] sum w x   [4..6] sum w y   [7] sum w |x|^2   [8..16] sum w y_r x_c (r major)
-// One launch for all problems (e.g. every edge of the pair graph); fixed summation order, no atomics.
-__global__ __launch_bounds__(256) void umeyama_moments_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                               const float* __restrict__ w, const long* __restrict__ xo,
-                                                               const long* __restrict__ yo, const long* __restrict__ wo, int P,
-                                                               double* __restrict__ partial) {
-    __shared__ double red[4][17];
-    const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* xb = x + xo[b];
-    const float* yb = y + yo[b];
-    const float* wb = w + wo[b];
-    double a[17];
-#pragma unroll
-    for (int j = 0; j < 17; j++) a[j] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const int p = chunk * 1024 + i * 256 + tid;
-        if (p < P) {
-            const double ww = wb[p];
-            const double x0 = xb[3 * p], x1 = xb[3 * p + 1], x2 = xb[3 * p + 2];
-            const double y0 = yb[3 * p], y1 = yb[3 * p + 1], y2 = yb[3 * p + 2];
-            a[0] += ww;
-            a[1] += ww * x0; a[2] += ww * x1; a[3] += ww * x2;
-            a[4] += ww * y0; a[5] += ww * y1; a[6] += ww * y2;
-            a[7] += ww * (x0 * x0 + x1 * x1 + x2 * x2);
-            a[8] += ww * y0 * x0; a[9] += ww * y0 * x1; a[10] += ww * y0 * x2;
-            a[11] += ww * y1 * x0; a[12] += ww * y1 * x1; a[13] += ww * y1 * x2;
-            a[14] += ww * y2 * x0; a[15] += ww * y2 * x1; a[16] += ww * y2 * x2;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 17; j++) {
-        double v = a[j];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if (lane == 0) red[wave][j] = v;
-    }
-    __syncthreads();
-    if (tid < 17) partial[((size_t)b * gridDim.x + chunk) * 17 + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
-}
-
 }  // namespace a3r
 using namespace a3r;
 
-extern "C" int a3r_umeyama_chunks(int P) { return P > 0 ? (P + 1023) / 1024 : 0; }
-
-extern "C" int a3r_umeyama_moments(const float* x, const float* y, const float* w, const long* x_off, const long* y_off,
-                                   const long* w_off, int B, int P, double* partial, void* stream) {
-    A3R_CHECK_ARG(x && y && w && x_off && y_off && w_off && partial, "a3r_umeyama_moments: null pointer");
-    A3R_CHECK_ARG(B > 0 && B <= 65535 && P > 0, "a3r_umeyama_moments: bad shape B=%d P=%d", B, P);
-    hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(umeyama_moments_kernel, dim3(a3r_umeyama_chunks(P), B), dim3(256), 0, st, x, y, w, x_off, y_off, w_off, P, partial);
-    A3R_LAUNCH_CHECK();
+// the entry checks several producers share, with the texts their entries have always printed
+static int check_scale(const char* who, float scale) {
+    A3R_CHECK_ARG(scale > 0.f && std::isfinite(scale), "%s: scale must be positive and finite", who);
+    return A3R_OK;
+}
+// c_multiple: 4 (fp32 output) or 8 (the packed forms, whose text names it)
+static int check_up2x_shape(const char* who, int B, int H, int W, int C, int c_multiple, int Hc, int Wc) {
+    A3R_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % c_multiple == 0,
+                  c_multiple == 8 ? "%s: bad shape (C must be a multiple of 8)" : "%s: bad shape", who);
+    A3R_CHECK_ARG(Hc > 0 && Hc <= 2 * H && Wc > 0 && Wc <= 2 * W, "%s: crop window larger than the 2x map", who);
     return A3R_OK;
 }
 
@@ -769,8 +694,7 @@ static int launch_layernorm(const float* x, const float* w, const float* b, floa
     hipStream_t st = as_stream(stream);
     ProfScope prof(PK_LAYERNORM, (BF3 ? 10.0 : 8.0) * M * D, st);
     dim3 grid((M + 3) / 4), block(256);
-    static const bool one_row = getenv("A3R_LN_ONE_ROW") != nullptr;           // developer A/B switch
-    if (BF3 && pair && !one_row && (D == 1024 || D == 768 || D == 256)) {
+    if (BF3 && pair && (D == 1024 || D == 768 || D == 256)) {
         const dim3 g2((M + 7) / 8);
         char* y3 = reinterpret_cast<char*>(y);
         if (D == 1024) hipLaunchKernelGGL(layernorm_pair_kernel<4>, g2, block, 0, st, x, w, b, y3, M, D, eps);
@@ -782,7 +706,7 @@ static int launch_layernorm(const float* x, const float* w, const float* b, floa
     if (D == 1024) hipLaunchKernelGGL((layernorm_kernel<4, BF3>), grid, block, 0, st, x, w, b, y, M, D, eps, pair);
     else if (D == 768) hipLaunchKernelGGL((layernorm_kernel<3, BF3>), grid, block, 0, st, x, w, b, y, M, D, eps, pair);
     else if (D == 256) hipLaunchKernelGGL((layernorm_kernel<1, BF3>), grid, block, 0, st, x, w, b, y, M, D, eps, pair);
-    else hipLaunchKernelGGL(layernorm_generic_kernel<BF3>, grid, block, 0, st, x, w, b, y, M, D, eps, pair);
+    else hipLaunchKernelGGL(layernorm_generic_kernel<BF3 ? 1 : 0>, grid, block, 0, st, x, w, b, y, M, D, eps, pair, 1.f, nullptr);
     A3R_LAUNCH_CHECK();
     return A3R_OK;
 }
@@ -794,25 +718,32 @@ extern "C" int a3r_layernorm(const float* x, const float* w, const float* b, flo
     return launch_layernorm<false>(x, w, b, y, M, D, eps, stream);
 }
 
+template <int VPL>   // the register kernel for rows of up to 512 VPL, with or without the range statistics
+static void launch_ln_fh2(bool stats, dim3 grid, hipStream_t st, const float* x, const float* w, const float* b, char* y, int M, int D,
+                          float eps, float scale, unsigned* absmax) {
+    if (stats) hipLaunchKernelGGL((layernorm_fh2_kernel<VPL, true>), grid, dim3(256), 0, st, x, w, b, y, M, D, eps, scale, absmax);
+    else hipLaunchKernelGGL((layernorm_fh2_kernel<VPL, false>), grid, dim3(256), 0, st, x, w, b, y, M, D, eps, scale, absmax);
+}
+
 extern "C" int a3r_layernorm_fh2(const float* x, const float* w, const float* b, void* y2, int M, int D, float eps, float scale,
                                  unsigned* absmax, void* stream) {
     A3R_CHECK_ARG(x && w && b && y2, "a3r_layernorm_fh2: null pointer");
-    A3R_CHECK_ARG(scale > 0.f && std::isfinite(scale), "a3r_layernorm_fh2: scale must be positive and finite");
+    if (int rc = check_scale("a3r_layernorm_fh2", scale)) return rc;
     A3R_CHECK_ARG(M > 0 && D > 0 && D % 32 == 0, "a3r_layernorm_fh2: bad shape M=%d D=%d (D must be a multiple of 32)", M, D);
-    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(y2) & 15) == 0, "a3r_layernorm_fh2: y2 must be 16-byte aligned");
+    A3R_CHECK_ARG(aligned_to(y2, 16), "a3r_layernorm_fh2: y2 must be 16-byte aligned");
     hipStream_t st = as_stream(stream);
     ProfScope prof(PK_LAYERNORM, 8.0 * M * D, st);
     const int nblk = (M + 3) / 4;
     // with statistics: a persistent rows loop (16 workgroups per CU, one atomic each); without: one row per wave
-    dim3 grid(absmax && nblk > 4096 ? 4096 : nblk), block(256);
+    const dim3 grid(absmax && nblk > 4096 ? 4096 : nblk);
     char* y = static_cast<char*>(y2);
     // rows up to 1536 wide stay in registers (one, two or three 8-k groups per lane; D = 768 uses two with the upper lanes idle in
     // the second: 2.7 -> 4.5+ TB/s against the three-pass generic kernel it used before)
-    const bool aligned = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
-    if (aligned && D <= 512) { if (absmax) hipLaunchKernelGGL((layernorm_fh2_kernel<1, true>), grid, block, 0, st, x, w, b, y, M, D, eps, scale, absmax); else hipLaunchKernelGGL((layernorm_fh2_kernel<1, false>), grid, block, 0, st, x, w, b, y, M, D, eps, scale, absmax); }
-    else if (aligned && D <= 1024) { if (absmax) hipLaunchKernelGGL((layernorm_fh2_kernel<2, true>), grid, block, 0, st, x, w, b, y, M, D, eps, scale, absmax); else hipLaunchKernelGGL((layernorm_fh2_kernel<2, false>), grid, block, 0, st, x, w, b, y, M, D, eps, scale, absmax); }
-    else if (aligned && D <= 1536) { if (absmax) hipLaunchKernelGGL((layernorm_fh2_kernel<3, true>), grid, block, 0, st, x, w, b, y, M, D, eps, scale, absmax); else hipLaunchKernelGGL((layernorm_fh2_kernel<3, false>), grid, block, 0, st, x, w, b, y, M, D, eps, scale, absmax); }
-    else hipLaunchKernelGGL(layernorm_fh2_generic_kernel, grid, block, 0, st, x, w, b, y, M, D, eps, scale, absmax);
+    const bool aligned = all_aligned16(x, w, b);
+    if (aligned && D <= 512) launch_ln_fh2<1>(absmax, grid, st, x, w, b, y, M, D, eps, scale, absmax);
+    else if (aligned && D <= 1024) launch_ln_fh2<2>(absmax, grid, st, x, w, b, y, M, D, eps, scale, absmax);
+    else if (aligned && D <= 1536) launch_ln_fh2<3>(absmax, grid, st, x, w, b, y, M, D, eps, scale, absmax);
+    else hipLaunchKernelGGL(layernorm_generic_kernel<2>, grid, dim3(256), 0, st, x, w, b, y2, M, D, eps, 0, scale, absmax);
     A3R_LAUNCH_CHECK();
     return A3R_OK;
 }
@@ -822,7 +753,7 @@ extern "C" int a3r_layernorm_bf3(const float* x, const float* w, const float* b,
     A3R_CHECK_ARG(x && w && b && y3, "a3r_layernorm_bf3: null pointer");
     A3R_CHECK_ARG(M > 0 && D > 0 && D % 8 == 0, "a3r_layernorm_bf3: bad shape M=%d D=%d (D must be a multiple of 8)", M, D);
     A3R_CHECK_ARG(!pair || D % 32 == 0, "a3r_layernorm_bf3: the row-pair layout needs D (%d) to be a multiple of 32", D);
-    A3R_CHECK_ARG((reinterpret_cast<uintptr_t>(y3) & 15) == 0, "a3r_layernorm_bf3: y3 must be 16-byte aligned");
+    A3R_CHECK_ARG(aligned_to(y3, 16), "a3r_layernorm_bf3: y3 must be 16-byte aligned");
     return launch_layernorm<true>(x, w, b, static_cast<float*>(y3), M, D, eps, stream, pair ? 1 : 0);
 }
 
@@ -883,7 +814,7 @@ int a3r::patchify_indexed(const float* img_a, const float* img_b, const int32_t*
 int a3r::gather_rows(const float* src, float* dst, const int32_t* map, int S, int N, int C, void* stream) {
     A3R_CHECK_ARG(src && dst && map, "gather_rows: null pointer");
     A3R_CHECK_ARG(S > 0 && N > 0 && C > 0 && C % 4 == 0, "gather_rows: bad shape");
-    A3R_CHECK_ARG(((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0, "gather_rows: buffers must be 16-byte aligned");
+    A3R_CHECK_ARG(all_aligned16(src, dst), "gather_rows: buffers must be 16-byte aligned");
     const long NC4 = (long)N * (C / 4), total = (long)S * NC4;
     ProfScope prof(PK_ELEMENTWISE, 32.0 * total, as_stream(stream));
     hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), reinterpret_cast<const f32x4*>(src),
@@ -896,8 +827,7 @@ extern "C" int a3r_gather_add_rows(const float* a, const int32_t* map_a, const f
                                    int C, void* stream) {
     A3R_CHECK_ARG(a && map_a && dst && (!b || map_b), "a3r_gather_add_rows: null pointer");
     A3R_CHECK_ARG(S > 0 && N > 0 && C > 0 && C % 4 == 0, "a3r_gather_add_rows: bad shape");
-    A3R_CHECK_ARG(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0,
-                  "a3r_gather_add_rows: buffers must be 16-byte aligned");
+    A3R_CHECK_ARG(all_aligned16(a, b, dst), "a3r_gather_add_rows: buffers must be 16-byte aligned");
     const long NC4 = (long)N * (C / 4), total = (long)S * NC4;
     ProfScope prof(PK_ELEMENTWISE, 48.0 * total, as_stream(stream));
     hipLaunchKernelGGL(gather_add_rows_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), reinterpret_cast<const f32x4*>(a),
@@ -906,12 +836,11 @@ extern "C" int a3r_gather_add_rows(const float* a, const int32_t* map_a, const f
     return A3R_OK;
 }
 
-int a3r::gather_add_rows_src(const float* store, long stride, const float* fresh, const int32_t* src, const float* b, const int32_t* map_b,
-                             float* dst, int S, int N, int C, void* stream) {
+extern "C" int a3r_gather_add_rows_src(const float* store, long stride, const float* fresh, const int32_t* src, const float* b,
+                                       const int32_t* map_b, float* dst, int S, int N, int C, void* stream) {
     A3R_CHECK_ARG(store && fresh && src && dst && (!b || map_b), "a3r_gather_add_rows_src: null pointer");
     A3R_CHECK_ARG(S > 0 && N > 0 && C > 0 && C % 4 == 0 && stride >= (long)N * C && stride % 4 == 0, "a3r_gather_add_rows_src: bad shape");
-    A3R_CHECK_ARG(((reinterpret_cast<uintptr_t>(store) | reinterpret_cast<uintptr_t>(fresh) | reinterpret_cast<uintptr_t>(b) |
-                    reinterpret_cast<uintptr_t>(dst)) & 15) == 0, "a3r_gather_add_rows_src: buffers must be 16-byte aligned");
+    A3R_CHECK_ARG(all_aligned16(store, fresh, b, dst), "a3r_gather_add_rows_src: buffers must be 16-byte aligned");
     const long NC4 = (long)N * (C / 4), total = (long)S * NC4;
     ProfScope prof(PK_ELEMENTWISE, 48.0 * total, as_stream(stream));
     hipLaunchKernelGGL(gather_add_rows_src_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream),
@@ -921,22 +850,14 @@ int a3r::gather_add_rows_src(const float* store, long stride, const float* fresh
     return A3R_OK;
 }
 
-extern "C" int a3r_gather_add_rows_src(const float* store, long stride, const float* fresh, const int32_t* src, const float* b,
-                                       const int32_t* map_b, float* dst, int S, int N, int C, void* stream) {
-    return a3r::gather_add_rows_src(store, stride, fresh, src, b, map_b, dst, S, N, C, stream);
-}
-
 // one body for the two entry points: hs null = c / r0 hold the blocks map names; else map is the signed source list
 static int combine_resid_launch(const char* who, const float* c, const float* r0, const CombineSrc* hs, const float* p2, const int32_t* map,
                                 float* s, void* sr2, int S, long P, int C, float scale, unsigned* absmax, void* stream) {
     A3R_CHECK_ARG(p2 && map && s && sr2 && (hs ? (c && r0) || (hs->c && hs->r0) : c && r0), "%s: null pointer", who);
     A3R_CHECK_ARG(S > 0 && P > 0 && C > 0 && C % 8 == 0 && (long)S * P < (1L << 31), "%s: bad shape (C must be a multiple of 8)", who);
     A3R_CHECK_ARG(!hs || (hs->stride >= P * C && hs->stride % 4 == 0 && !hs->c == !hs->r0 && !c == !r0), "%s: bad storage stride or pointers", who);
-    A3R_CHECK_ARG(scale > 0.f && std::isfinite(scale), "%s: scale must be positive and finite", who);
-    A3R_CHECK_ARG(((reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(r0) | reinterpret_cast<uintptr_t>(p2) |
-                    reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(sr2) | (hs ? reinterpret_cast<uintptr_t>(hs->c) : 0) |
-                    (hs ? reinterpret_cast<uintptr_t>(hs->r0) : 0)) & 15) == 0,
-                  "%s: buffers must be 16-byte aligned", who);
+    if (int rc = check_scale(who, scale)) return rc;
+    A3R_CHECK_ARG(all_aligned16(c, r0, p2, s, sr2, hs ? hs->c : nullptr, hs ? hs->r0 : nullptr), "%s: buffers must be 16-byte aligned", who);
     const long rows = (long)S * P, total = rows * (C / 8);
     ProfScope prof(PK_ELEMENTWISE, 5.0 * 32 * total, as_stream(stream));
     const long blocks = (total + 255) / 256;
@@ -952,31 +873,25 @@ static int combine_resid_launch(const char* who, const float* c, const float* r0
     return A3R_OK;
 }
 
-int a3r::combine_resid_fh2(const float* c, const float* r0, const float* p2, const int32_t* map, float* s, void* sr2, int S, long P, int C,
-                           float scale, unsigned* absmax, void* stream) {
-    return combine_resid_launch("a3r_combine_resid_fh2", c, r0, nullptr, p2, map, s, sr2, S, P, C, scale, absmax, stream);
-}
-
 extern "C" int a3r_combine_resid_fh2(const float* c, const float* r0, const float* p2, const int32_t* map, float* s, void* sr2, int S,
                                      long P, int C, float scale, unsigned* absmax, void* stream) {
-    return a3r::combine_resid_fh2(c, r0, p2, map, s, sr2, S, P, C, scale, absmax, stream);
-}
-
-int a3r::combine_resid_fh2_src(const float* c, const float* r0, const float* store_c, const float* store_r0, long stride, const int32_t* src,
-                               const float* p2, float* s, void* sr2, int S, long P, int C, float scale, unsigned* absmax, void* stream) {
-    const CombineSrc hs = {store_c, store_r0, stride};
-    return combine_resid_launch("a3r_combine_resid_fh2_src", c, r0, &hs, p2, src, s, sr2, S, P, C, scale, absmax, stream);
+    return combine_resid_launch("a3r_combine_resid_fh2", c, r0, nullptr, p2, map, s, sr2, S, P, C, scale, absmax, stream);
 }
 
 extern "C" int a3r_combine_resid_fh2_src(const float* c, const float* r0, const float* store_c, const float* store_r0, long stride,
                                          const int32_t* src, const float* p2, float* s, void* sr2, int S, long P, int C, float scale,
                                          unsigned* absmax, void* stream) {
-    return a3r::combine_resid_fh2_src(c, r0, store_c, store_r0, stride, src, p2, s, sr2, S, P, C, scale, absmax, stream);
+    const CombineSrc hs = {store_c, store_r0, stride};
+    return combine_resid_launch("a3r_combine_resid_fh2_src", c, r0, &hs, p2, src, s, sr2, S, P, C, scale, absmax, stream);
 }
 
-static inline dim3 upsample_grid(int B, int Hc, int Wc, int groups) {      // groups: threads per output pixel
-    const long rows = (long)B * Hc;
-    return dim3((unsigned)(((long)Wc * groups + 255) / 256), (unsigned)(rows < 65535 ? rows : 65535));
+// The first form's grid.  groups: threads per output pixel.  rows: output rows a workgroup loops over.  The fh2 forms take ~8 and
+// publish ONE statistics atomic per workgroup (a long per-thread loop of dependent row loads is latency-bound: 63 rows per
+// workgroup cost +15 % on the full-resolution map; one row per workgroup is half a million atomics).
+static inline dim3 upsample_grid(int B, int Hc, int Wc, int groups, unsigned rows = 1) {
+    const long all = (long)B * Hc;
+    const unsigned y = (unsigned)(all < 65535 ? all : 65535);
+    return dim3((unsigned)(((long)Wc * groups + 255) / 256), (y + rows - 1) / rows);
 }
 
 // the second form's grid: x over (block column, channel group), y over (batch, block row); a workgroup of the fh2 forms loops over
@@ -985,9 +900,7 @@ static inline dim3 upsample_grid(int B, int Hc, int Wc, int groups) {      // gr
 // 662 / 685 us -- one block row per workgroup is 140 000 atomics on one word, many rows are a serial chain of load, compute, store
 // per wave at 5 waves per SIMD; combine [42 <- 15, 48, 64, 256] 430 / 431 / 413 / 412 / 415 / 464 us.
 static inline dim3 upsample_block_grid(int B, int Hc, int Wc, int groups, unsigned rows) {
-    dim3 grid = upsample_grid(B, Hc / 2 + 1, Wc / 2 + 1, groups);
-    grid.y = (grid.y + rows - 1) / rows;
-    return grid;
+    return upsample_grid(B, Hc / 2 + 1, Wc / 2 + 1, groups, rows);
 }
 
 extern "C" int a3r_upsample2x_set_form(int form) {
@@ -995,29 +908,36 @@ extern "C" int a3r_upsample2x_set_form(int form) {
     return g_up_form.exchange(form);
 }
 
+// one launch for the 2x entries: output format FMT (up2x_emit) in the form the process runs, each on its grid
+template <int FMT>
+static void launch_up2x(dim3 grid_v1, dim3 grid_v2, void* stream, const float* x, void* y, const float* c, const float* r0, const int32_t* map,
+                        float* s, int B, int H, int W, int C, int Hc, int Wc, float scale, unsigned* absmax, const CombineSrc& hs) {
+    if (g_up_form.load() == 1)
+        hipLaunchKernelGGL(upsample2x_kernel<FMT>, grid_v1, dim3(256), 0, as_stream(stream), x, static_cast<float*>(y), c, r0, map, s, B, H, W,
+                           C / 4, Hc, Wc, scale, absmax, hs);
+    else
+        hipLaunchKernelGGL(upsample2x_block_kernel<FMT>, grid_v2, dim3(256), 0, as_stream(stream), x, static_cast<float*>(y), c, r0, map, s, B,
+                           H, W, C / 4, Hc, Wc, scale, absmax, hs);
+}
+
 extern "C" int a3r_upsample2x(const float* x, float* y, int B, int H, int W, int C, int Hc, int Wc, void* stream) {
     A3R_CHECK_ARG(x && y, "a3r_upsample2x: null pointer");
-    A3R_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "a3r_upsample2x: bad shape");
-    A3R_CHECK_ARG(Hc > 0 && Hc <= 2 * H && Wc > 0 && Wc <= 2 * W, "a3r_upsample2x: crop window larger than the 2x map");
+    if (int rc = check_up2x_shape("a3r_upsample2x", B, H, W, C, 4, Hc, Wc)) return rc;
     const long total = (long)B * Hc * Wc * (C / 4);
     ProfScope prof(PK_ELEMENTWISE, 16.0 * total + 4.0 * B * H * W * C, as_stream(stream));
-    if (g_up_form.load() == 1)
-        hipLaunchKernelGGL(upsample2x_kernel<0>, upsample_grid(B, Hc, Wc, C / 4), dim3(256), 0, as_stream(stream), x, y, B, H, W, C / 4, Hc, Wc, 1.f, nullptr);
-    else
-        hipLaunchKernelGGL(upsample2x_block_kernel<0>, upsample_block_grid(B, Hc, Wc, C / 4, 1), dim3(256), 0, as_stream(stream), x, y,
-                           nullptr, nullptr, nullptr, nullptr, B, H, W, C / 4, Hc, Wc, 1.f, nullptr, CombineSrc{});
+    launch_up2x<0>(upsample_grid(B, Hc, Wc, C / 4), upsample_block_grid(B, Hc, Wc, C / 4, 1), stream, x, y, nullptr, nullptr, nullptr, nullptr,
+                   B, H, W, C, Hc, Wc, 1.f, nullptr, CombineSrc{});
     A3R_LAUNCH_CHECK();
     return A3R_OK;
 }
 
 extern "C" int a3r_upsample2x_bf3(const float* x, void* y3, int B, int H, int W, int C, int Hc, int Wc, void* stream) {
     A3R_CHECK_ARG(x && y3, "a3r_upsample2x_bf3: null pointer");
-    A3R_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "a3r_upsample2x_bf3: bad shape (C must be a multiple of 8)");
-    A3R_CHECK_ARG(Hc > 0 && Hc <= 2 * H && Wc > 0 && Wc <= 2 * W, "a3r_upsample2x_bf3: crop window larger than the 2x map");
+    if (int rc = check_up2x_shape("a3r_upsample2x_bf3", B, H, W, C, 8, Hc, Wc)) return rc;
     const long total = (long)B * Hc * Wc * (C / 4);
     ProfScope prof(PK_ELEMENTWISE, 24.0 * total + 4.0 * B * H * W * C, as_stream(stream));
-    hipLaunchKernelGGL(upsample2x_kernel<1>, upsample_grid(B, Hc, Wc, C / 4), dim3(256), 0, as_stream(stream), x, static_cast<float*>(y3), B, H, W,
-                       C / 4, Hc, Wc, 1.f, nullptr);
+    hipLaunchKernelGGL(upsample2x_kernel<1>, upsample_grid(B, Hc, Wc, C / 4), dim3(256), 0, as_stream(stream), x, static_cast<float*>(y3),
+                       nullptr, nullptr, nullptr, nullptr, B, H, W, C / 4, Hc, Wc, 1.f, nullptr, CombineSrc{});
     A3R_LAUNCH_CHECK();
     return A3R_OK;
 }
@@ -1025,24 +945,12 @@ extern "C" int a3r_upsample2x_bf3(const float* x, void* y3, int B, int H, int W,
 extern "C" int a3r_upsample2x_fh2(const float* x, void* y2, int B, int H, int W, int C, int Hc, int Wc, float scale, unsigned* absmax,
                                   void* stream) {
     A3R_CHECK_ARG(x && y2, "a3r_upsample2x_fh2: null pointer");
-    A3R_CHECK_ARG(scale > 0.f && std::isfinite(scale), "a3r_upsample2x_fh2: scale must be positive and finite");
-    A3R_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "a3r_upsample2x_fh2: bad shape (C must be a multiple of 8)");
-    A3R_CHECK_ARG(Hc > 0 && Hc <= 2 * H && Wc > 0 && Wc <= 2 * W, "a3r_upsample2x_fh2: crop window larger than the 2x map");
+    if (int rc = check_scale("a3r_upsample2x_fh2", scale)) return rc;
+    if (int rc = check_up2x_shape("a3r_upsample2x_fh2", B, H, W, C, 8, Hc, Wc)) return rc;
     const long total = (long)B * Hc * Wc * (C / 4);
     ProfScope prof(PK_ELEMENTWISE, 16.0 * total + 4.0 * B * H * W * C, as_stream(stream));
-    if (g_up_form.load() != 1) {
-        hipLaunchKernelGGL(upsample2x_block_kernel<2>, upsample_block_grid(B, Hc, Wc, C / 8, 2), dim3(256), 0, as_stream(stream), x,
-                           static_cast<float*>(y2), nullptr, nullptr, nullptr, nullptr, B, H, W, C / 4, Hc, Wc, scale, absmax, CombineSrc{});
-        A3R_LAUNCH_CHECK();
-        return A3R_OK;
-    }
-    dim3 grid = upsample_grid(B, Hc, Wc, C / 8);
-    // every workgroup loops over ~8 rows and publishes ONE statistics atomic (a long per-thread loop of dependent row loads is
-    // latency-bound: 63 rows per workgroup cost +15 % on the full-resolution map; one row per workgroup is half a million atomics)
-    const unsigned ycap = (grid.y + 7) / 8;
-    if (grid.y > ycap) grid.y = ycap;
-    hipLaunchKernelGGL(upsample2x_kernel<2>, grid, dim3(256), 0, as_stream(stream), x, static_cast<float*>(y2), B, H, W,
-                       C / 4, Hc, Wc, scale, absmax);
+    launch_up2x<2>(upsample_grid(B, Hc, Wc, C / 8, 8), upsample_block_grid(B, Hc, Wc, C / 8, 2), stream, x, y2, nullptr, nullptr, nullptr,
+                   nullptr, B, H, W, C, Hc, Wc, scale, absmax, CombineSrc{});
     A3R_LAUNCH_CHECK();
     return A3R_OK;
 }
@@ -1052,62 +960,31 @@ static int upsample2x_combine_launch(const char* who, const float* x, const floa
                                      const int32_t* map, float* s, void* sr2, int B, int H, int W, int C, int Hc, int Wc, float scale,
                                      unsigned* absmax, void* stream) {
     A3R_CHECK_ARG(x && map && s && sr2 && (hs ? (c && r0) || (hs->c && hs->r0) : c && r0), "%s: null pointer", who);
-    A3R_CHECK_ARG(scale > 0.f && std::isfinite(scale), "%s: scale must be positive and finite", who);
-    A3R_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "%s: bad shape (C must be a multiple of 8)", who);
-    A3R_CHECK_ARG(Hc > 0 && Hc <= 2 * H && Wc > 0 && Wc <= 2 * W, "%s: crop window larger than the 2x map", who);
+    if (int rc = check_scale(who, scale)) return rc;
+    if (int rc = check_up2x_shape(who, B, H, W, C, 8, Hc, Wc)) return rc;
     A3R_CHECK_ARG(!hs || (hs->stride >= (long)Hc * Wc * C && hs->stride % 4 == 0 && !hs->c == !hs->r0 && !c == !r0),
                   "%s: bad storage stride or pointers", who);
-    A3R_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(r0) |
-                    reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(sr2) | (hs ? reinterpret_cast<uintptr_t>(hs->c) : 0) |
-                    (hs ? reinterpret_cast<uintptr_t>(hs->r0) : 0)) & 15) == 0,
-                  "%s: buffers must be 16-byte aligned", who);
+    A3R_CHECK_ARG(all_aligned16(x, c, r0, s, sr2, hs ? hs->c : nullptr, hs ? hs->r0 : nullptr), "%s: buffers must be 16-byte aligned", who);
     const long total = (long)B * Hc * Wc * (C / 4);
     ProfScope prof(PK_ELEMENTWISE, 40.0 * total + 4.0 * B * H * W * C, as_stream(stream));
-    if (g_up_form.load() != 1) {
-        const dim3 grid = upsample_block_grid(B, Hc, Wc, C / 8, 4);
-        if (hs)
-            hipLaunchKernelGGL(upsample2x_block_kernel<4>, grid, dim3(256), 0, as_stream(stream), x, static_cast<float*>(sr2), c, r0, map, s, B,
-                               H, W, C / 4, Hc, Wc, scale, absmax, *hs);
-        else
-            hipLaunchKernelGGL(upsample2x_block_kernel<3>, grid, dim3(256), 0, as_stream(stream), x, static_cast<float*>(sr2), c, r0, map, s, B,
-                               H, W, C / 4, Hc, Wc, scale, absmax, CombineSrc{});
-        A3R_LAUNCH_CHECK();
-        return A3R_OK;
-    }
-    dim3 grid = upsample_grid(B, Hc, Wc, C / 8);
-    const unsigned ycap = (grid.y + 7) / 8;                   // as a3r_upsample2x_fh2: ~8 rows and one statistics atomic per workgroup
-    if (grid.y > ycap) grid.y = ycap;
-    if (hs)
-        hipLaunchKernelGGL(upsample2x_combine_kernel<true>, grid, dim3(256), 0, as_stream(stream), x, c, r0, map, s, static_cast<char*>(sr2), B,
-                           H, W, C / 4, Hc, Wc, scale, absmax, *hs);
-    else
-        hipLaunchKernelGGL(upsample2x_combine_kernel<false>, grid, dim3(256), 0, as_stream(stream), x, c, r0, map, s, static_cast<char*>(sr2), B,
-                           H, W, C / 4, Hc, Wc, scale, absmax, CombineSrc{});
+    const dim3 grid_v1 = upsample_grid(B, Hc, Wc, C / 8, 8), grid_v2 = upsample_block_grid(B, Hc, Wc, C / 8, 4);
+    if (hs) launch_up2x<4>(grid_v1, grid_v2, stream, x, sr2, c, r0, map, s, B, H, W, C, Hc, Wc, scale, absmax, *hs);
+    else launch_up2x<3>(grid_v1, grid_v2, stream, x, sr2, c, r0, map, s, B, H, W, C, Hc, Wc, scale, absmax, CombineSrc{});
     A3R_LAUNCH_CHECK();
     return A3R_OK;
 }
 
-int a3r::upsample2x_combine_fh2(const float* x, const float* c, const float* r0, const int32_t* map, float* s, void* sr2, int B, int H, int W,
-                                int C, int Hc, int Wc, float scale, unsigned* absmax, void* stream) {
-    return upsample2x_combine_launch("upsample2x_combine_fh2", x, c, r0, nullptr, map, s, sr2, B, H, W, C, Hc, Wc, scale, absmax, stream);
-}
-
+// (the text of this entry's checks has never carried the a3r_ prefix)
 extern "C" int a3r_upsample2x_combine_fh2(const float* x, const float* c, const float* r0, const int32_t* map, float* s, void* sr2, int S,
                                           int H, int W, int C, int Hc, int Wc, float scale, unsigned* absmax, void* stream) {
-    return a3r::upsample2x_combine_fh2(x, c, r0, map, s, sr2, S, H, W, C, Hc, Wc, scale, absmax, stream);
-}
-
-int a3r::upsample2x_combine_fh2_src(const float* x, const float* c, const float* r0, const float* store_c, const float* store_r0, long stride,
-                                    const int32_t* src, float* s, void* sr2, int B, int H, int W, int C, int Hc, int Wc, float scale,
-                                    unsigned* absmax, void* stream) {
-    const CombineSrc hs = {store_c, store_r0, stride};
-    return upsample2x_combine_launch("a3r_upsample2x_combine_fh2_src", x, c, r0, &hs, src, s, sr2, B, H, W, C, Hc, Wc, scale, absmax, stream);
+    return upsample2x_combine_launch("upsample2x_combine_fh2", x, c, r0, nullptr, map, s, sr2, S, H, W, C, Hc, Wc, scale, absmax, stream);
 }
 
 extern "C" int a3r_upsample2x_combine_fh2_src(const float* x, const float* c, const float* r0, const float* store_c, const float* store_r0,
                                               long stride, const int32_t* src, float* s, void* sr2, int S, int H, int W, int C, int Hc,
                                               int Wc, float scale, unsigned* absmax, void* stream) {
-    return a3r::upsample2x_combine_fh2_src(x, c, r0, store_c, store_r0, stride, src, s, sr2, S, H, W, C, Hc, Wc, scale, absmax, stream);
+    const CombineSrc hs = {store_c, store_r0, stride};
+    return upsample2x_combine_launch("a3r_upsample2x_combine_fh2_src", x, c, r0, &hs, src, s, sr2, S, H, W, C, Hc, Wc, scale, absmax, stream);
 }
 
 extern "C" int a3r_head_final(const float* x, const float* w, const float* b, float* pts3d, float* conf, long P, int C,
@@ -1117,7 +994,7 @@ extern "C" int a3r_head_final(const float* x, const float* w, const float* b, fl
     long blocks = (P + 7) / 8;
     if (blocks > 16384) blocks = 16384;
     ProfScope prof(PK_ELEMENTWISE, 4.0 * P * (C + 4), as_stream(stream));
-    if (C == 128 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w)) & 15) == 0) {
+    if (C == 128 && all_aligned16(x, w)) {
         long nb = (P + 31) / 32;                                   // a block of four waves takes 32 pixels per step
         if (nb > 8192) nb = 8192;
         hipLaunchKernelGGL(head_final128_kernel, dim3((int)nb), dim3(256), 0, as_stream(stream), x, w, b, pts3d, conf, P);

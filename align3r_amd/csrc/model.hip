@@ -664,8 +664,8 @@ struct Plan {
         traced("combine_resid", S, (int)px, C);
         const Site st = site(sr2);
         if (rc) return;
-        if (hc) rc = combine_resid_fh2_src(c, r, hc->st.c(hs), hc->st.r0(hs), hc->st.stride(), hc->src, extra, s, sr2, S, px, C, st.scale, st.stat, stream);
-        else rc = combine_resid_fh2(c, r, extra, map, s, sr2, S, px, C, st.scale, st.stat, stream);
+        if (hc) rc = a3r_combine_resid_fh2_src(c, r, hc->st.c(hs), hc->st.r0(hs), hc->st.stride(), hc->src, extra, s, sr2, S, px, C, st.scale, st.stat, stream);
+        else rc = a3r_combine_resid_fh2(c, r, extra, map, s, sr2, S, px, C, st.scale, st.stat, stream);
     }
     // the same with extra = the bilinear 2x of x [S, H, W, C] made inside the kernel
     void up_combine_map(const float* x, const float* c, const float* r, const int32_t* map, float* s, float* sr2, int S, int H, int W,
@@ -674,8 +674,8 @@ struct Plan {
         traced("upsample2x_combine", H, W, C);
         const Site st = site(sr2);
         if (rc) return;
-        if (hc) rc = upsample2x_combine_fh2_src(x, c, r, hc->st.c(hs), hc->st.r0(hs), hc->st.stride(), hc->src, s, sr2, S, H, W, C, Hc, Wc, st.scale, st.stat, stream);
-        else rc = upsample2x_combine_fh2(x, c, r, map, s, sr2, S, H, W, C, Hc, Wc, st.scale, st.stat, stream);
+        if (hc) rc = a3r_upsample2x_combine_fh2_src(x, c, r, hc->st.c(hs), hc->st.r0(hs), hc->st.stride(), hc->src, s, sr2, S, H, W, C, Hc, Wc, st.scale, st.stat, stream);
+        else rc = a3r_upsample2x_combine_fh2(x, c, r, map, s, sr2, S, H, W, C, Hc, Wc, st.scale, st.stat, stream);
     }
     // LayerNorm whose output feeds a GEMM (written directly in the GEMMs' operand form)
     void ln(const float* x, const float* w, const float* b, float* yg, int M, int D) {
@@ -1106,7 +1106,7 @@ void decoder_stage(Plan& P, const Call& k, const Dims& g, Levels& v) {
     // x[s] = z_i[prior of s] + b[mb[s]] (b null: + x[s]) for S row blocks; mz / sz: the priors' rows in v.pc / their sources (pp)
     auto gather_add = [&](int i, const int32_t* mz, const int32_t* sz, const float* b, const int32_t* mb, float* x, int S) {
         if (P.skip()) return;
-        if (pp) P.rc = gather_add_rows_src(reinterpret_cast<const float*>(pp->lay.feat) + i * zw, pp->lay.words_feat, v.pc, sz, b, mb, x, S, g.N, D, P.stream);
+        if (pp) P.rc = a3r_gather_add_rows_src(reinterpret_cast<const float*>(pp->lay.feat) + i * zw, pp->lay.words_feat, v.pc, sz, b, mb, x, S, g.N, D, P.stream);
         else P.rc = a3r_gather_add_rows(v.pc, mz, b, mb, x, S, g.N, D, P.stream);
     };
     // zero_convs[i] of the depth-prior tokens, added to level x in place (distinct maps without the switch: their tokens are copied

@@ -1,5 +1,5 @@
 """Scenes, float64 oracles and agreement rules for the solvers of the MST initialisation (tests/test_init_cases_cpu.py,
-tests/test_gpu_init.py): the batched PnP and the Umeyama solve of csrc/init.hip, umeyama_moments_kernel of csrc/elementwise.hip and
+tests/test_gpu_init.py): the batched PnP, the Umeyama solve and umeyama_moments_kernel of csrc/init.hip and
 the per-pixel passes of csrc/init_maps.hip.  numpy only.
 
 PnP.  `pnp_oracle` restates the algorithm in the header of csrc/init.hip in float64 on the fp32-rounded inputs the kernel reads:

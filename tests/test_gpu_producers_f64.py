@@ -19,12 +19,12 @@ Launcher branches (every hipLaunchKernelGGL of the entry points named in the lef
   a3r_layernorm_fh2    layernorm_fh2_kernel<1, stats | none>    test_layernorm_fh2 D = 32, 64, 480, 512 (480: last lane group partly filled)
                        layernorm_fh2_kernel<2, stats | none>    test_layernorm_fh2 D = 544, 768, 1024
                        layernorm_fh2_kernel<3, stats | none>    test_layernorm_fh2 D = 1056, 1280, 1536
-                       layernorm_fh2_generic_kernel             test_layernorm_fh2 D = 1568, 2048; test_layernorm_fh2_unaligned (D = 256)
+                       layernorm_generic_kernel<fh2>            test_layernorm_fh2 D = 1568, 2048; test_layernorm_fh2_unaligned (D = 256)
                        persistent row loop, second trip         test_layernorm_fh2_persistent (16391, 32): 4098 row blocks on 4096 workgroups
   a3r_upsample2x       upsample2x_kernel<fp32> (form 1)         test_upsample2x_f64, every shape; y loop second trip: B = 4100 and 7300
                        upsample2x_block_kernel<fp32> (form 2)   test_upsample2x_f64, every shape; y loop second trip: B = 7300
   a3r_upsample2x_bf3   upsample2x_kernel<bf3>                   test_upsample2x_bf3; y loop second trip: (4100, 8, 3, 8)
-  a3r_upsample2x_fh2,  upsample2x_kernel<fh2>, upsample2x_block_kernel<fh2 | combine>, upsample2x_combine_kernel: bitwise on the fp32
+  a3r_upsample2x_fh2,  upsample2x_kernel<fh2 | combine>, upsample2x_block_kernel<fh2 | combine>: bitwise on the fp32
   .._combine_fh2       form in test_gpu_up2x_forms.py / test_gpu_fh2_range.py / test_gpu_dedup_head.py (not repeated here)
   a3r_head_final       head_final_kernel                        test_head_final (1, 8) (7, 36) (9, 132: j += 32 loop) (969, 256)
                        uniform trip loop, second trip           test_head_final (131085, 8)
